@@ -2,7 +2,16 @@
 """bench.py — headline benchmark of the hot path on MI355X: batched Lomb-Scargle (BASELINE.json configs[1]) + the BLS
 transit search (configs[3]) + the accuracy columns of the metric, in ONE JSON line.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline needs: it builds the inputs, runs W warm-up and K timed steps of the headline path
+(`value`, `ms_per_step`, the `roofline` priced on their kernel time) and prints the line.  `--full` adds everything listed
+below beside the headline: the CPU baselines and accuracy checks against the reference, the other LS method, the `--repeats`
+blocks, the shader-clock probes, host_to_host, api_end_to_end, pipeline_end_to_end, configs[2]_on_1_gpu and the BLS, PLD
+and flatten blocks (the same for the secondary workloads: their baselines, accuracy, clock probe and API block).
+`--dump-outputs DIR`: after the timed steps, what the timed path computed in its last step is written as DIR/<name>.npy
+(float64, or float32 where the output is float32; at most 64 MB in all, a larger output keeps a fixed seeded sample of its
+elements; NaN and infinities are written as 0.0 and listed in DIR/<name>_nonfinite.npy, sample_outputs).  The inputs are seeded: two builds run with the same arguments can be compared file by file.
 
 N > 1: the driver launches one rank per GPU (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`);
 run by hand without WORLD_SIZE in the environment, `--gpus N` re-executes itself under torch.distributed.run with N
@@ -73,7 +82,7 @@ def parse(argv=None):
     ap.add_argument("--chunks", type=int, default=4, help="target chunks per step (comm/compute overlap)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the astropy runs (cpu_baseline AND accuracy)")
     ap.add_argument("--workload", default="ls", choices=["ls", "api", "bls", "pld", "flatten", "lschi2", "pgsmooth", "fold", "regress"])
-    ap.add_argument("--repeats", type=int, default=5, help="workload ls: blocks of K steps behind roofline.frac_median / _min / _max")
+    ap.add_argument("--repeats", type=int, default=5, help="workload ls, --full: blocks of K steps behind roofline.frac_median / _min / _max")
     ap.add_argument("--no-api", action="store_true", help="workload ls: skip the api_end_to_end block (Python batch API, host included)")
     ap.add_argument("--regressors", type=int, default=135, help="regress: design-matrix columns K")
     ap.add_argument("--nterms", type=int, default=2, help="lschi2: Fourier terms")
@@ -81,7 +90,7 @@ def parse(argv=None):
     ap.add_argument("--pld-cadences", type=int, default=3500)
     ap.add_argument("--ls-method", default="both", choices=["both", "exact", "fast"],
                     help="fast: the reference's default method (extirpolation + FFT), the headline; exact: direct fp64 trig "
-                         "sums; both (default): headline = fast, the exact kernel is measured too and reported beside it")
+                         "sums; both (default): headline = fast, with --full the exact kernel is measured too and reported beside it")
     ap.add_argument("--gather", default="summary", choices=["summary", "spectra", "none"],
                     help="N>1: what is all-gathered over RCCL each step: per-target (max power, argmax), the full spectra, or nothing")
     ap.add_argument("--periods", type=int, default=50000)
@@ -104,6 +113,12 @@ def parse(argv=None):
                     help="workload ls: targets of the configs[2]-on-one-GPU block (north_star's 10k x 1e5 shape in one call); 0 = skip")
     ap.add_argument("--no-pipeline", action="store_true", help="workload ls: skip the pipeline_end_to_end block (device-resident chain)")
     ap.add_argument("--dry", action="store_true", help="CPU only: form the process group (gloo), barrier, max over ranks; no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline (CPU baselines, accuracy, the other LS method, "
+                         "--repeats, clock probes, host/API/pipeline blocks, configs[2], BLS, PLD, flatten); without it the "
+                         "run sets up, warms up, times --steps steps of the headline and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args(argv)
     args.api_headline = args.workload == "api"
     if args.api_headline:
@@ -113,7 +128,44 @@ def parse(argv=None):
         args.no_bls = args.no_pld = args.no_flatten = args.no_host = args.no_cpu_baseline = args.no_pipeline = True
         args.no_api = False
         args.c2_targets = 0
+    # the headline metric keeps its name with and without --full
+    args.metric_bls = not args.no_bls
+    if not args.full:
+        args.no_cpu_baseline = args.no_bls = args.no_pld = args.no_flatten = args.no_host = args.no_pipeline = True
+        args.no_api = not args.api_headline
+        args.c2_targets, args.repeats = 0, 1
+        if args.ls_method == "both":
+            args.ls_method = "fast"
     return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def sample_outputs(named):
+    """--dump-outputs: [(name, torch tensor)] -> {name: numpy array}, float32 / float64 kept, anything else as float64.  An
+    output of more elements than its share of DUMP_LIMIT_BYTES (24 B each: the value and room for its non-finite record)
+    keeps, flattened, the elements at the flat indices np.unique(np.random.default_rng(0).integers(0, size, share)): the
+    same sample in every run of the same shape.  Every dumped value is finite: a NaN or an infinity (the 'lk_amplitude'
+    spectra hold NaN where the reference takes the square root of a negative power) is written as 0.0, and
+    <name>_nonfinite, float64 (k, 2), lists each one as (flat index into <name>, 0 for NaN / +1 for +inf / -1 for -inf)."""
+    import torch
+    share = (DUMP_LIMIT_BYTES - 4096 * 2 * len(named)) // 24 // len(named)
+    out = {}
+    for name, x in named:
+        if x.numel() > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, x.numel(), share))
+            x = x.reshape(-1)[torch.from_numpy(idx).to(x.device)]
+        a = x.cpu().numpy()
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        bad = np.flatnonzero(~np.isfinite(a))
+        if bad.size:
+            flat = a.reshape(-1)
+            out[name + "_nonfinite"] = np.stack([bad.astype(np.float64), np.sign(np.nan_to_num(flat[bad], nan=0.0))], axis=1)
+            a = a.copy()
+            a.reshape(-1)[bad] = 0.0
+        out[name] = a
+    return out
 
 
 def effective_cores(cap=64):
@@ -663,7 +715,10 @@ def main():
     def clock_under(step_fn, steps, expect_ms):
         """Sustained shader clock [MHz] while `steps` calls of step_fn run: lk_shader_clock_mhz spins one wave on a stream of
         its own for ~70 % of the expected duration, started from a thread so that a launcher that blocks the host cannot
-        leave the probe measuring an idle GPU.  None if the probe fails (never fatal)."""
+        leave the probe measuring an idle GPU.  None if the probe fails (never fatal) or without --full (it runs steps of
+        its own)."""
+        if not args.full:
+            return None
         import threading
         spin = float(min(1000.0, max(1.0, 0.7 * expect_ms * steps)))
         mhz = ctypes.c_double(0.0)
@@ -714,9 +769,11 @@ def main():
     traffic_all = load_traffic()
     out, extra = {}, {}
     roofline = None
+    dump = bool(args.dump_outputs)
+    dumped = {}   # --dump-outputs: the headline path's outputs of its last timed step, {name: numpy array}
 
     # ================================================================================================ BLS block
-    def run_bls(Bb, first_index, steps, warmup):
+    def run_bls(Bb, first_index, steps, warmup, dump=False):
         t, y, dy, off = synth.bls_batch(3, Bb, N, first_index=first_index)
         ivar = 1.0 / dy ** 2
         nchk = min(Bb, max(args.acc_bls, 1))
@@ -742,6 +799,8 @@ def main():
             _capi.argmax_batch_dev(handle, Bb, nP, d_out.data_ptr(), d_max.data_ptr(), d_arg.data_ptr(), stream)
 
         dt, kms = timed(step, warmup, steps)
+        dumped = sample_outputs([(k, d_out[i]) for i, k in enumerate(_capi.BLS_FIELDS)] +
+                                [("max_power", d_max), ("argmax", d_arg)]) if dump else {}
         clk = clock_under(step, 1, kms)
         nb = np.ceil(period / (duration.min() / 10)) + 10
         durb = np.unique(np.round(duration / (duration.min() / 10)))
@@ -753,7 +812,7 @@ def main():
             "workload": "configs[3]: %d targets x %d cadences, %d periods x %d durations BLS per GPU" % (Bb, N, nP, len(duration)),
             "roofline": dict(bls_roofline(Bb, nP, kms, ach, traffic_all.get("bls")), shader_clock_mhz=clk),
             "argmax": d_arg.cpu().numpy(), "max_power": d_max.cpu().numpy(),
-            "period_at_max": period[np.clip(d_arg.cpu().numpy(), 0, nP - 1)],
+            "period_at_max": period[np.clip(d_arg.cpu().numpy(), 0, nP - 1)], "dumped": dumped,
         }
         # transit time at the best period of the first targets (row 4 of the seven outputs) + their inputs: the folded-flux check
         am = np.clip(res["argmax"][:nchk], 0, nP - 1)
@@ -791,7 +850,7 @@ def main():
 
 
     # ================================================================================================ PLD block
-    def run_pld(Bc, first_index, steps, warmup, base):
+    def run_pld(Bc, first_index, steps, warmup, base, dump=False):
         """configs[4]: Bc cutouts 11x11 x pld_cadences, pld_order 3, 16 PCA components, all pixels: design matrix +
         regression through lk_pld_design_batch_dev + lk_regress_batch_dev.  `base`: the numpy port's baseline dict (its
         "_results" feed one of the two accuracy checks) or None."""
@@ -831,12 +890,14 @@ def main():
             e1.record()
 
         dt, kms = timed(step, warmup, steps)
+        dumped = sample_outputs([("design_matrix", d_X), ("prior_sigma", d_ps), ("weights", d_w), ("model", d_model),
+                                 ("outlier_mask", d_out)]) if dump else {}
         clk = clock_under(step, max(2, steps), kms)
         del d_X
         acc = {}
         from lightkurve_amd.correctors.pldcorrector import PixelCube, pld_correct_batch
         gpath = os.path.join(ROOT, "tests", "golden", "pld_c5.npz")
-        if rank == 0 and first_index == 0 and Nc == 3500 and os.path.exists(gpath):
+        if args.full and rank == 0 and first_index == 0 and Nc == 3500 and os.path.exists(gpath):
             # the product path (PLDCorrector mirror: design matrix, regression, restored trend) on the cutouts the REFERENCE
             # itself corrected when the fixture was made (oracle/gen_golden.py gen_pld_c5: lightkurve's PLDCorrector on
             # these very synth cutouts — regenerated here, SHA-256 checked)
@@ -914,10 +975,10 @@ def main():
         return {"dt": dt, "kernel_ms": kms, "units_per_step": Bc, "steps": steps, "warmup": warmup, "api_end_to_end": api,
                 "metric": "PLD cutouts/sec (design matrix + regression)", "unit": "cutouts/sec",
                 "workload": "configs[4]: %d K2-like 11x11-pixel cutouts x %d cadences, 3rd-order design matrix (K=%d), "
-                            "MFMA Gram per GPU" % (Bc, Nc, K), "roofline": rl, "accuracy": acc, "Nc": Nc}
+                            "MFMA Gram per GPU" % (Bc, Nc, K), "roofline": rl, "accuracy": acc, "Nc": Nc, "dumped": dumped}
 
     # ================================================================================================ flatten block
-    def run_flatten(Bf, first_index, steps, warmup, base):
+    def run_flatten(Bf, first_index, steps, warmup, base, dump=False):
         """LightCurve.flatten (window 401, polyorder 2, niters 3) on Bf light curves of N cadences through
         lk_savgol_trend_batch_dev.  `base`: a cpu_baseline dict whose "_results" are trends of the first light curves of
         this batch (scipy under conda, or the numpy port)."""
@@ -933,6 +994,7 @@ def main():
             e1.record()
 
         dt, kms = timed(step, warmup, steps)
+        dumped = sample_outputs([("trend", d_tr)]) if dump else {}
         clk = clock_under(step, max(10, steps), kms)
         acc = None
         if base is not None and "_results" in base and first_index == 0:
@@ -983,7 +1045,7 @@ def main():
         return {"dt": dt, "kernel_ms": kms, "units_per_step": int(off[-1]), "steps": steps, "warmup": warmup, "api_end_to_end": api,
                 "metric": "flatten cadences/sec (window %d, niters 3)" % args.flatten_window, "unit": "cadences/sec",
                 "workload": "flatten: %d light curves x %d cadences, window %d, polyorder 2, niters 3 per GPU" % (Bf, N, args.flatten_window),
-                "roofline": rl, "accuracy": acc}
+                "roofline": rl, "accuracy": acc, "dumped": dumped}
 
     def block_of(res, base):
         """JSON block of a secondary workload inside the default line."""
@@ -1225,6 +1287,8 @@ def main():
         rep_kms = []
         for method in order:
             results[method] = timed(make_step(method), args.warmup, args.steps)
+            if method == headline and dump:
+                dumped = sample_outputs([("power", d_pow), ("max_power", d_max), ("argmax", d_arg)])
             peaks[method] = (d_max.cpu().numpy().copy(), d_arg.cpu().numpy().copy())
             if method == headline == "fast":
                 # the headline's kernel time again, `--repeats` - 1 more blocks of K steps right behind the timed region (before
@@ -1235,7 +1299,7 @@ def main():
         units_per_step = total_targets * M
         pairs_local = float(off[-1]) * M
         names = {"exact": "exact GLS, direct fp64 trig sums", "fast": "ls_method='fast' (reference default): extirpolation + FFT"}
-        metric = "frequencies*targets/sec (Lomb-Scargle, %s)%s" % (names[headline], "" if args.no_bls else
+        metric = "frequencies*targets/sec (Lomb-Scargle, %s)%s" % (names[headline], "" if not args.metric_bls else
                                                                    " + BLS periods*targets/sec; max-power rel-err")
         unit = "frequencies*targets/sec"
         workload = ("configs[%d]: %d TESS-like %d-cadence targets x %d freqs Lomb-Scargle %s, ls_method=%s"
@@ -1454,15 +1518,15 @@ def main():
             fres = run_flatten(args.flatten_targets, rank * args.flatten_targets, max(1, min(args.steps, 10)), 1, cpu_base_flat)
             extra["flatten"] = block_of(fres, cpu_base_flat)
     elif args.workload == "bls":
-        bres = run_bls(B, first, args.steps, args.warmup)
-        dt, kern_ms = bres["dt"], bres["kernel_ms"]
+        bres = run_bls(B, first, args.steps, args.warmup, dump)
+        dt, kern_ms, dumped = bres["dt"], bres["kernel_ms"], bres["dumped"]
         units_per_step = total_targets * args.periods
         metric, unit, workload, roofline = bres["metric"], bres["unit"], bres["workload"], bres["roofline"]
         if ref is not None and "bls" in ref and rank == 0:
             extra["accuracy"] = bls_accuracy(bres, ref["bls"])
     elif args.workload == "pld":
-        pres = run_pld(args.cutouts, rank * args.cutouts, args.steps, args.warmup, cpu_base)
-        dt, kern_ms = pres["dt"], pres["kernel_ms"]
+        pres = run_pld(args.cutouts, rank * args.cutouts, args.steps, args.warmup, cpu_base, dump)
+        dt, kern_ms, dumped = pres["dt"], pres["kernel_ms"], pres["dumped"]
         units_per_step = pres["units_per_step"] * world
         metric, unit, workload, roofline = pres["metric"], pres["unit"], pres["workload"], pres["roofline"]
         if pres["accuracy"]:
@@ -1471,8 +1535,8 @@ def main():
             extra["api_end_to_end"] = pres["api_end_to_end"]
         B, N = args.cutouts, pres["Nc"]
     elif args.workload == "flatten":
-        fres = run_flatten(B, first, args.steps, args.warmup, cpu_base)
-        dt, kern_ms = fres["dt"], fres["kernel_ms"]
+        fres = run_flatten(B, first, args.steps, args.warmup, cpu_base, dump)
+        dt, kern_ms, dumped = fres["dt"], fres["kernel_ms"], fres["dumped"]
         units_per_step = fres["units_per_step"] * world
         metric, unit, workload, roofline = fres["metric"], fres["unit"], fres["workload"], fres["roofline"]
         if fres["accuracy"]:
@@ -1503,6 +1567,8 @@ def main():
             e1.record()
 
         dt, kern_ms = timed(step, args.warmup, args.steps)
+        if dump:
+            dumped = sample_outputs([("weights", d_w), ("model", d_model), ("outlier_mask", d_out)])
         units_per_step = Bc * world
         flop = float(Bc) * Nc * (K + 1) * (K + 2)   # ONE Gram build (upper triangle: what the kernel executes); later clip passes are skipped
         metric, unit = "RegressionCorrector fits/sec (N=%d, K=%d, 5 sigma-clip iterations)" % (Nc, K), "fits/sec"
@@ -1531,6 +1597,8 @@ def main():
             e1.record()
 
         dt, kern_ms = timed(step, args.warmup, args.steps)
+        if dump:
+            dumped = sample_outputs([("power", d_p)])
         units_per_step = B * M * world
         metric, unit = "frequencies*targets/sec (Lomb-Scargle, nterms=%d, exact chi2)" % args.nterms, "frequencies*targets/sec"
         workload = "%d targets x %d cadences x %d frequencies, nterms=%d multi-term Lomb-Scargle per GPU" % (B, N, M, args.nterms)
@@ -1557,6 +1625,8 @@ def main():
             e1.record()
 
         dt, kern_ms = timed(step, args.warmup, args.steps)
+        if dump:
+            dumped = sample_outputs([("smoothed_power", d_o)])
         units_per_step = B * M * world
         members = float(B) * float(np.sum(tabs[1] - tabs[0]))   # window memberships = values the medians look at
         metric, unit = "frequencies*targets/sec (Periodogram.smooth logmedian, filter_width 0.01)", "frequencies*targets/sec"
@@ -1589,6 +1659,8 @@ def main():
             e1.record()
 
         dt, kern_ms = timed(step, args.warmup, args.steps)
+        if dump:
+            dumped = sample_outputs([("phase", d_ph), ("order", d_ord), ("flux", d_fy), ("flux_err", d_fe)])
         units_per_step = int(off[-1]) * world
         metric, unit = "fold cadences/sec (phase + stable sort + 2 gathered columns)", "cadences/sec"
         workload = "fold: %d light curves x %d cadences per GPU" % (B, N)
@@ -1600,12 +1672,16 @@ def main():
                             "the order read per gather); the sort itself runs in LDS tiles / an L2-resident slab"}
 
     if rank == 0:
+        if dump:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         value = units_per_step * args.steps / dt
         out = {
             "metric": metric, "value": value, "unit": unit, "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
             "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": workload, "targets_per_gpu": B if not strong else None,
+            "full": args.full, "config": {"workload": workload, "targets_per_gpu": B if not strong else None,
                        "targets_total": total_targets, "cadences": N,
                        "parallelism": "targets sharded over %d rank(s), no data-path collective%s"
                                       % (world, ("; RCCL all-gather of %s each step" % (

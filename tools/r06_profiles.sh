@@ -4,7 +4,7 @@
 # to be judged into profiles/).
 out=gpurun_out/r06; mkdir -p $out
 python -m pytest tests -m gpu -q > $out/pytest_gpu.log 2>&1; tail -3 $out/pytest_gpu.log
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 tools/trace_lsfast.sh $out/ls
 tools/pmc_pass.sh $out ls_fetch FETCH_SIZE --no-bls --no-pld --no-flatten --no-host --no-cpu-baseline --ls-method fast --no-api --no-pipeline --c2-targets 0 --targets 180 --steps 3 --warmup 1 --repeats 1
 tools/pmc_pass.sh $out ls_write WRITE_SIZE --no-bls --no-pld --no-flatten --no-host --no-cpu-baseline --ls-method fast --no-api --no-pipeline --c2-targets 0 --targets 180 --steps 3 --warmup 1 --repeats 1

@@ -31,5 +31,5 @@ echo "# $(date -u) B = 1 latency through the seams on the GPU box"
 $CONDA -W ignore tools/seams_latency.py 2>&1 | grep -v "Warning\|warn" | tail -40
 } | tee $O/seams_latency.txt
 unset LD_PRELOAD PYTHONPATH
-python bench.py --workload pld --steps 5 --warmup 2 > $O/bench_pld_reference_baseline.json 2> $O/bench_pld.err
+python bench.py --workload pld --full --steps 5 --warmup 2 > $O/bench_pld_reference_baseline.json 2> $O/bench_pld.err
 grep -o '"cpu_baseline": {[^}]*' $O/bench_pld_reference_baseline.json | head -c 900
