@@ -176,7 +176,6 @@ template <int U, class L, class P>
 __device__ __forceinline__ void strided_pass(int n, L load, P proc) {
     const int tid = threadIdx.x, nt = blockDim.x;
     int i = tid;
-#ifndef LK_SP_PLAIN
     for (; i + (U - 1) * nt < n; i += U * nt) {
         decltype(load(0)) v[U];
 #pragma unroll
@@ -184,7 +183,6 @@ __device__ __forceinline__ void strided_pass(int n, L load, P proc) {
 #pragma unroll
         for (int u = 0; u < U; ++u) proc(i + u * nt, v[u]);
     }
-#endif
     for (; i < n; i += nt) proc(i, load(i));
 }
 
@@ -423,7 +421,7 @@ struct NoSide {
 
 template <class Val, class Keep, class Side = NoSide>
 __device__ double block_select_sampled(int n, long long count, long long k, Val val, Keep keep, unsigned long long *sh,
-                                       double *cand, int cap, bool want_next, double *next, int dbg = -1,
+                                       double *cand, int cap, bool want_next, double *next,
                                        double *spacing = nullptr,  // *spacing: mean gap between values around rank k (0 = unknown)
                                        Side side = Side(), bool *side_ran = nullptr) {
     if (spacing) *spacing = 0.0;
@@ -506,9 +504,7 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
         keys[j] = keep(i) ? f64_sortable(val(i)) : ~0ull;
     }
     __syncthreads();
-    if (dbg == 0) return 0.0;  // (profiling aid: stop after the sample gather / sample sort / collect pass / counts)
     lds_bitonic_sort(keys, S);
-    if (dbg == 1) return 0.0;
     // sample size = number of non-padding keys (the padding sorts to the end)
     {
         int c = 0;
@@ -546,7 +542,6 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
             }
         });
         if (side_ran) *side_ran = true;
-        if (dbg == 2) return 0.0;
         long long n_less = block_count_fast(c_less, reinterpret_cast<long long *>(sh));
         long long n_eqlo = block_count_fast(c_eqlo, reinterpret_cast<long long *>(sh));
         long long n_eqhi = block_count_fast(c_eqhi, reinterpret_cast<long long *>(sh));
@@ -620,7 +615,6 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
             slo = lo + (double)ba / scale;
             shi_v = lo + (double)(bb + 1) / scale;
         }
-        if (dbg == 3) return 0.0;
         // ranks k and k + 1 relative to the candidates; if they fall among them: histogram select, else (and when that does
         // not apply) the candidates are sorted once (keys[] aliases cand[]) and rank lookups are plain LDS reads
         const long long qa = k - n_less - n_eqlo, qb = qa + 1;
@@ -637,7 +631,6 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
             __syncthreads();
             lds_bitonic_sort(keys, S2);
         }
-        if (dbg == 4) return 0.0;
         // rank r (0-based among all kept) -> value, or "miss"
         bool miss = false;
         auto at_rank = [&](long long r) -> double {
@@ -659,12 +652,9 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
         };
         // (every branch above depends only on workgroup-uniform values, so the barriers inside block_select_kth are safe)
         const double a = at_rank(k);
-        if (dbg == 5) return 0.0;
         double b = a;
         if (!miss && want_next && k + 1 < count) b = at_rank(k + 1);
-        if (dbg == 6) return 0.0;
         __syncthreads();  // every thread has read its ranks before cand[] / keys[] are reused by the caller
-        if (dbg == 7) return 0.0;
 #ifdef LK_SEL_DEBUG
         if (tid == 0 && (blockIdx.x < 2 || miss))
             printf("[sel] blk %d n %d count %lld k %lld s_all %lld delta %d lo %.17g hi %.17g less %lld eqlo %lld nc %d eqhi %lld miss %d a %.17g\n",
@@ -679,14 +669,14 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
 // numpy.median of the kept values through block_select_sampled; NaN if none kept.
 template <class Val, class Keep, class Side = NoSide>
 __device__ double block_median_sampled(int n, long long count, Val val, Keep keep, unsigned long long *sh, double *cand,
-                                       int cap, int dbg = -1, double *spacing = nullptr, Side side = Side(),
+                                       int cap, double *spacing = nullptr, Side side = Side(),
                                        bool *side_ran = nullptr) {
     if (spacing) *spacing = 0.0;
     if (side_ran) *side_ran = false;
     if (count <= 0) return __longlong_as_double(0x7ff8000000000000ll);
     const long long k = (count - 1) / 2;
     double nxt = 0.0;
-    const double a = block_select_sampled(n, count, k, val, keep, sh, cand, cap, (count & 1) == 0, &nxt, dbg, spacing, side,
+    const double a = block_select_sampled(n, count, k, val, keep, sh, cand, cap, (count & 1) == 0, &nxt, spacing, side,
                                           side_ran);
     return (count & 1) ? a : (a + nxt) * 0.5;
 }

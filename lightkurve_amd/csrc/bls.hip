@@ -177,14 +177,11 @@ __device__ __forceinline__ void bls_team_body(
     const double *__restrict__ tm, const double2 *__restrict__ yw, const int64_t *__restrict__ n_off,
     const BlsStats *__restrict__ stats, const double *__restrict__ period, const int *__restrict__ pidx, int np_group,
     int64_t nP, int B, const int *__restrict__ dur_tab, int n_dur, int max_dur, double bin_duration, int oversample,
-    int obj_flag, double *__restrict__ out7, int cap, int shape, int ablate_arg, unsigned long long *__restrict__ prof_arg) {
+    int obj_flag, double *__restrict__ out7, int cap, int shape, unsigned long long *__restrict__ prof_arg) {
 #ifdef LK_BLS_DEBUG
-    const int ablate = ablate_arg;
     unsigned long long *const prof = prof_arg;
-#else   // release build: the switches are constants and every branch on them folds away
-    constexpr int ablate = 0;
+#else   // release build: the profiling switch is a constant and every branch on it folds away
     constexpr unsigned long long *prof = nullptr;
-    (void)ablate_arg;
     (void)prof_arg;
 #endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -266,9 +263,9 @@ __device__ __forceinline__ void bls_team_body(
     // ticket says g, issues its atomics and then writes g + 1.  A wave's LDS instructions execute in program order, so
     // the next wave can only see the new ticket after the atomics before it have been applied: the bins still
     // accumulate in cadence order.
-    const int NH = (multi || (ablate & 256) != 0) ? 1 : min(NW, nh_cap);
+    const int NH = multi ? 1 : min(NW, nh_cap);
     volatile int *s_ticket = s_ctr + 2;
-    if (wave < NH && !(ablate & 1)) {
+    if (wave < NH) {
         const bool tsorted = st.sorted != 0.0;
         const double inv_bd = 1.0 / bin_duration;
         const double guard = 1e-12 * ((double)n_bins + 2.0);  // >= 1e-12 (q + 1) for every quotient of this period
@@ -443,7 +440,7 @@ __device__ __forceinline__ void bls_team_body(
     BLS_LAP(2);  // wrap pad + gmax / wmax reductions
     // Sequential chain acc = bins[i] + acc in index order (same rounding as the reference loop).  bins[0] is always 0, so
     // starting at i = 0 with acc = 0 is the same chain.  Lane 0: y, lane 1: ivar.
-    if (!multi && NW >= 2 && !(ablate & 2)) {
+    if (!multi && NW >= 2) {
         // One team, two chains.  A lone wave can issue an LDS instruction only every ~20 cycles (measured: a lane that
         // loads, adds and stores bin by bin runs at ~25 cycles per bin however the loop is pipelined; moving the operands
         // in with v_readlane costs the same in VALU issue).  So the serial pass does the minimum:
@@ -520,7 +517,7 @@ __device__ __forceinline__ void bls_team_body(
                 comp[i] = acc;
             }
         }
-    } else if (wwave == 0 && lane < 2 * G && !(ablate & 2)) {
+    } else if (wwave == 0 && lane < 2 * G) {
         // lane 2 g' + c: component c (0: y, 1: ivar) of team g'
         char *rg = region0 + (size_t)(lane >> 1) * region;
         double *comp = reinterpret_cast<double *>(rg) + ((lane & 1) ? cap : 0);
@@ -611,7 +608,7 @@ __device__ __forceinline__ void bls_team_body(
     // thr = the best objective seen so far by anyone in the team (s_thr), warm-started from a coarse lattice.
     double best = -INFINITY;
     int bk = -1, bn = -1;
-    if (!(ablate & 4)) {
+    {  // (the search's locals end here)
         const double S = sum_y, E = sum_ivar;
         const double gmax = __longlong_as_double(s_red[0]) * (1.0 + 1e-9);  // max_i |S w_i - E y_i|
         const double wmax = __longlong_as_double(s_red[1]);                 // max_i w_i
@@ -658,20 +655,18 @@ __device__ __forceinline__ void bls_team_body(
         };
         // ---- warm start: every 8th start bin x every 8th duration (1.6 % of the candidates) gives the walk below a
         //      threshold close to the final best from its first step
-        if (!(ablate & 128)) {
-            const int cn = (n_bins - dmin) / 8 + 1, ck = (n_dur + 7) / 8;
-            for (int c = tid; c < cn * ck; c += NT) {
-                const int kc = (c / cn) * 8, n = (c - (c / cn) * cn) * 8;
-                const int dur = dur_bins[kc];
-                if (n + dur > n_bins) continue;
-                const double y_in = ya[n + dur] - ya[n], ivar_in = wa[n + dur] - wa[n], ivar_out = E - ivar_in;
-                if ((ivar_in < DBL_EPSILON) || (ivar_out < DBL_EPSILON)) continue;
-                const double ab = S * ivar_in, ce = E * y_in;
-                finish(n, kc, y_in, ivar_in, ivar_out, ab - ce, (fabs(ab) + fabs(ce)) * 1e-15,
-                       fmax(best, __longlong_as_double(*s_thr)));
-            }
-            __syncthreads();
+        const int cn = (n_bins - dmin) / 8 + 1, ck = (n_dur + 7) / 8;
+        for (int c = tid; c < cn * ck; c += NT) {
+            const int kc = (c / cn) * 8, n = (c - (c / cn) * cn) * 8;
+            const int dur = dur_bins[kc];
+            if (n + dur > n_bins) continue;
+            const double y_in = ya[n + dur] - ya[n], ivar_in = wa[n + dur] - wa[n], ivar_out = E - ivar_in;
+            if ((ivar_in < DBL_EPSILON) || (ivar_out < DBL_EPSILON)) continue;
+            const double ab = S * ivar_in, ce = E * y_in;
+            finish(n, kc, y_in, ivar_in, ivar_out, ab - ce, (fabs(ab) + fabs(ce)) * 1e-15,
+                   fmax(best, __longlong_as_double(*s_thr)));
         }
+        __syncthreads();
         // objective(Nn <= ub, ivar_in >= b, ivar_out >= e) strictly below thr (1e-4 safety factor, as in the skip-ahead)
         auto block_below = [&](double ub, double b, double e, double thr) {
             if (obj_flag) return 0.5 * ub * ub < thr * b * e * e * (1.0 - 1e-4);
@@ -710,7 +705,7 @@ __device__ __forceinline__ void bls_team_body(
             //      j has Nn <= max(Z over the block) - Z[n], ivar_in >= this window's (ivar >= 0: windows only grow) and
             //      ivar_out >= this one's minus the block's length x wmax.  If that bound is strictly below thr, none of
             //      them can win: jump to the first duration that ends beyond the block.
-            if (thr > 0.0 && ivar_in >= DBL_EPSILON && !(ablate & 32)) {
+            if (thr > 0.0 && ivar_in >= DBL_EPSILON) {
                 int jend = ((j >> 6) + 1) << 6;
                 double ub, e_lb;
                 bool skip = false;
@@ -747,7 +742,7 @@ __device__ __forceinline__ void bls_team_body(
             const double ab = S * ivar_in, ce = E * y_in;
             const double Nn = ab - ce;
             // ---- how many more bins this window may grow before it could reach thr
-            if (thr > 0.0 && !(ablate & 64)) {
+            if (thr > 0.0) {
                 double mf;
                 if (obj_flag) {
                     const double q = __builtin_amdgcn_sqrt(2.0 * thr * ivar_in) * (1.0 - 1e-4);
@@ -830,9 +825,9 @@ __device__ __forceinline__ void bls_team_body(
     const double *__restrict__ tm, const double2 *__restrict__ yw, const int64_t *__restrict__ n_off,                  \
         const BlsStats *__restrict__ stats, const double *__restrict__ period, const int *__restrict__ pidx,           \
         int np_group, int64_t nP, int B, const int *__restrict__ dur_tab, int n_dur, int max_dur, double bin_duration, \
-        int oversample, int obj_flag, double *__restrict__ out7, int cap, int shape, int ablate, unsigned long long *__restrict__ prof
+        int oversample, int obj_flag, double *__restrict__ out7, int cap, int shape, unsigned long long *__restrict__ prof
 #define BLS_TEAM_PASS \
-    tm, yw, n_off, stats, period, pidx, np_group, nP, B, dur_tab, n_dur, max_dur, bin_duration, oversample, obj_flag, out7, cap, shape, ablate, prof
+    tm, yw, n_off, stats, period, pidx, np_group, nP, B, dur_tab, n_dur, max_dur, bin_duration, oversample, obj_flag, out7, cap, shape, prof
 
 // 80 VGPRs: 6 waves per SIMD, for the groups whose LDS footprint admits >= 3 teams per CU
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6, 6))) void bls_team_kernel(BLS_TEAM_ARGS) {
@@ -1213,13 +1208,12 @@ int bls_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, 
         h->bls_attr_set = 1;
     }
     const int serial_hist = (h->bls_serial_hist || h->bls_force_serial_hist) ? 2 : 0;
-    // debug knobs, read once per process: LK_BLS_ABLATE skips phases (results wrong; phase costs by difference),
-    // LK_BLS_PROF=1 prints the wall time of every launch, =2 adds per-phase clocks (their atomics distort short teams)
-#ifdef LK_BLS_DEBUG   // `make DEBUG=1`: the phase-ablation and profiling switches of the development builds
-    static const int ablate = getenv("LK_BLS_ABLATE") ? atoi(getenv("LK_BLS_ABLATE")) : 0;
+    // debug knob, read once per process: LK_BLS_PROF=1 prints the wall time of every launch, =2 adds per-phase clocks (their
+    // atomics distort short teams)
+#ifdef LK_BLS_DEBUG   // `make DEBUG=1`: the profiling switch of the development builds
     static const int prof_level = getenv("LK_BLS_PROF") ? atoi(getenv("LK_BLS_PROF")) : 0;
 #else
-    constexpr int ablate = 0, prof_level = 0;
+    constexpr int prof_level = 0;
 #endif
     const bool prof_on = prof_level != 0;
     unsigned long long *d_prof = nullptr;
@@ -1227,14 +1221,8 @@ int bls_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, 
         LK_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d_prof), 64));
         LK_HIP_CHECK(hipMemset(d_prof, 0, 64));
     }
-#ifdef LK_BLS_DEBUG   // shape experiments of the development builds
-    static const int kMultiMinWaves = getenv("LK_BLS_MULTIMIN") ? atoi(getenv("LK_BLS_MULTIMIN")) : 16;
-    static const int nh_of_nw2 = getenv("LK_BLS_NH2") ? atoi(getenv("LK_BLS_NH2")) : 2;
-    static const int nh_of_nw4 = getenv("LK_BLS_NH4") ? atoi(getenv("LK_BLS_NH4")) : 4;
-#else
     constexpr int kMultiMinWaves = 16;  // multi-period workgroups only where they keep this many waves per CU
     constexpr int nh_of_nw2 = 2, nh_of_nw4 = 4;
-#endif
     constexpr int kHistWaves = 4;   // ticket-ordered histogram waves per team (8 and 16 measure the same)
     hipEvent_t pe0 = nullptr, pe1 = nullptr;
     if (prof_on) {
@@ -1324,11 +1312,11 @@ int bls_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, 
         if (deep)
             hipLaunchKernelGGL(bls_team_deep_kernel, dim3((unsigned)nwg), dim3(nt), lds, stream, d_tm, d_yw, d_off, d_stats,
                                period_dev, d_pidx + g0, npg, nP, B, d_dur, nd, max_dur, bin_duration, oversample,
-                               use_likelihood ? 1 : 0, out7, cap, shape, ablate, d_prof);
+                               use_likelihood ? 1 : 0, out7, cap, shape, d_prof);
         else
             hipLaunchKernelGGL(bls_team_kernel, dim3((unsigned)nwg), dim3(nt), lds, stream, d_tm, d_yw, d_off, d_stats,
                                period_dev, d_pidx + g0, npg, nP, B, d_dur, nd, max_dur, bin_duration, oversample,
-                               use_likelihood ? 1 : 0, out7, cap, shape, ablate, d_prof);
+                               use_likelihood ? 1 : 0, out7, cap, shape, d_prof);
         if (prof_on) {
             unsigned long long hp[8];
             float ms = 0.f;

@@ -79,7 +79,7 @@ using lk::set_error;
 
 extern "C" {
 
-int lk_version(void) { return 100; }
+int lk_version(void) { return 101; }
 
 const char *lk_last_error(void) { return lk::g_err.c_str(); }
 
@@ -126,13 +126,6 @@ int lk_set_host_chunk_mb(lk_handle *h, int mb) {
 int lk_bls_set_ordered_histogram(lk_handle *h, int on) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     h->bls_force_serial_hist = on ? 1 : 0;
-    return LK_OK;
-}
-
-int lk_pld_set_eig_mode(lk_handle *h, int mode) {
-    LK_REQUIRE(h != nullptr, "handle is NULL");
-    LK_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (one kernel per matrix) or 1 (phase-split launches)");
-    h->pld_eig_split = mode;
     return LK_OK;
 }
 

@@ -223,23 +223,13 @@ __device__ __forceinline__ FlatSlab flat_slab(char *scratch, const int64_t *scra
 constexpr int FLAT_NT = 512;
 // waves per SIMD the select / interpolation kernels are compiled for (8 = the 64-VGPR cap that keeps FOUR 512-thread workgroups
 // on a CU: 1024 slots, the bench's 1000 light curves in one wave of workgroups)
-#ifndef FLAT_INIT_WAVES
-#define FLAT_INIT_WAVES 8
-#endif
-#ifndef FLAT_DTSEG_WAVES
-#define FLAT_DTSEG_WAVES 8
-#endif
-#ifndef FLAT_INTERP_WAVES
-#define FLAT_INTERP_WAVES 6
-#endif
+constexpr int FLAT_INIT_WAVES = 8, FLAT_DTSEG_WAVES = 8, FLAT_INTERP_WAVES = 6;
 
 // ---- phase 0: initial mask (finite & |flux - nanmedian| <= sigma nanstd & ~user_mask), lightcurve.py:1002-1010
 __global__ __launch_bounds__(FLAT_NT, FLAT_INIT_WAVES) void flat_init_kernel(const double *__restrict__ flux, const uint8_t *__restrict__ user_mask,
                                                             const int64_t *__restrict__ n_off, double sigma,
                                                             char *__restrict__ scratch, const int64_t *__restrict__ scratch_off,
-                                                            FlatState *__restrict__ state, int FIR_LDS, int dbg) {
-    // dbg (development builds, LK_FLAT_STOP=100+k): return at stop point k of the sampled select — kernel-time differences
-    // between successive stop points are the costs of its phases; -1 = run to the end
+                                                            FlatState *__restrict__ state, int FIR_LDS) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long dyn_lds[];
     unsigned long long *sh = dyn_lds;
     const int sh_words = max((int)blockDim.x, 264);
@@ -299,9 +289,7 @@ __global__ __launch_bounds__(FLAT_NT, FLAT_INIT_WAVES) void flat_init_kernel(con
     const double sd = ninf > 0 ? __longlong_as_double(0x7ff8000000000000ll)
                                : sqrt(fmax(0.0, (s2 - s1 * s1 / (double)cnt) / (double)cnt));
     __syncthreads();
-    if (dbg == 99) return;  // (stop point: statistics done, select not started)
-    const double med = block_median_sampled(N, cnt, val, notnan, sh, fir, FIR_LDS, dbg);
-    if (dbg >= 0) return;
+    const double med = block_median_sampled(N, cnt, val, notnan, sh, fir, FIR_LDS);
     strided_pass<8>(N, val, [&](int i, double f) {
         bool m = isfinite(f) && (fabs(f - med) <= sd * sigma);
         if (user_mask && user_mask[i]) m = false;
@@ -390,8 +378,7 @@ constexpr int FLAT_CUT_CAP = 384;
 
 __global__ __launch_bounds__(FLAT_NT, FLAT_DTSEG_WAVES) void flat_dtseg_kernel(const int64_t *__restrict__ n_off, double break_tol,
                                                              char *__restrict__ scratch, const int64_t *__restrict__ scratch_off,
-                                                             FlatState *__restrict__ state, int FIR_LDS, int it, int near_on,
-                                                             int dbg) {
+                                                             FlatState *__restrict__ state, int FIR_LDS, int it, int near_on) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long dyn_lds[];
     __shared__ int cut_n;
     __shared__ int cut_i[FLAT_CUT_CAP];
@@ -444,8 +431,7 @@ __global__ __launch_bounds__(FLAT_NT, FLAT_DTSEG_WAVES) void flat_dtseg_kernel(c
             if (tid == 0) cut_n = 0;  // (candidates noted against the failed guess are void)
             __syncthreads();
             bool ran = false;
-            dmed = block_median_sampled(nm - 1, cnt, dval, dkeep, sh, fir, FIR_LDS, dbg < 8 ? dbg : -1, &dspacing, note, &ran);
-            if (dbg >= 0 && dbg <= 8) return;  // (8: the whole select, fall-back routes included)
+            dmed = block_median_sampled(nm - 1, cnt, dval, dkeep, sh, fir, FIR_LDS, &dspacing, note, &ran);
             have_cuts = ran && bound_ok;
         }
         __syncthreads();
@@ -530,11 +516,7 @@ __global__ __launch_bounds__(FLAT_NT, QUAD ? 6 : 4) void flat_trend_kernel(const
                                                              const int64_t *__restrict__ scratch_off,
                                                              const FlatState *__restrict__ state, int FIR_LDS, double quad_a,
                                                              double quad_b, const double *__restrict__ edge_minv,
-                                                             double2 *__restrict__ rs_part, int dbg) {
-    // dbg (development builds, LK_FLAT_STOP=300+k; results wrong, launch time = the cost of what is left — read it off the
-    // FIRST iteration's launch in a --timeline, the later ones run on the garbage this leaves): 0 return after the state /
-    // segment reads, 1 interior tiles only, 2 edges and short segments only, 3 tiles without their output phase, 4 no trend
-    // stores, 6 / 7 / 8 tiles up to the local moments / the wave scans / the barriers around the wave totals
+                                                             double2 *__restrict__ rs_part) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long dyn_lds[];
     unsigned long long *sh = dyn_lds;
     const int sh_words = max((int)blockDim.x, 264);
@@ -551,10 +533,6 @@ __global__ __launch_bounds__(FLAT_NT, QUAD ? 6 : 4) void flat_trend_kernel(const
     const int nm = st.nm, nseg = st.nseg;
     const int half = window / 2;
     const int T = gridDim.y, y = blockIdx.y;
-    if (dbg == 0) {
-        if (nseg > 0 && segs[nseg - 1] < 0) tr[0] = 0.0;   // (keeps the reads alive)
-        return;
-    }
     int item = 0;  // running work-item number (workgroup-uniform): this workgroup takes those with item % T == y
     double rs1 = 0.0, rs2 = 0.0;
     auto put = [&](int i, double v) {
@@ -567,7 +545,7 @@ __global__ __launch_bounds__(FLAT_NT, QUAD ? 6 : 4) void flat_trend_kernel(const
         const int l = segs[sg], h = (sg + 1 < nseg) ? segs[sg + 1] : nm;
         const int len = h - l;
         if (window > len || (double)len < break_tol) {
-            if ((item++ % T) != y || dbg == 1 || dbg == 3) continue;
+            if ((item++ % T) != y) continue;
             __syncthreads();
             const double med = flat_segment_median(fm + l, len, sh, fir, FIR_LDS);
             for (int i = l + tid; i < h; i += nt) put(i, med);
@@ -614,7 +592,6 @@ __global__ __launch_bounds__(FLAT_NT, QUAD ? 6 : 4) void flat_trend_kernel(const
                     for (int q = 0; q < 4; ++q) xn[q] = xq[min(e0n + q, nin - 1)];
                 };
                 if (CHF <= 4 && j < ntile) fetch(j);
-                if (dbg == 2) j = ntile;
                 for (; j < ntile; j += T) {
                     const int o0 = o_lo + j * QTO;
                     const int no = min(QTO, o_hi - o0), ni = no + window - 1;
@@ -647,16 +624,8 @@ __global__ __launch_bounds__(FLAT_NT, QUAD ? 6 : 4) void flat_trend_kernel(const
                             s2 = fma(u * u, yv, s2);
                         }
                     }
-                    if (dbg == 6) {   // (ablation: loads + local moments only)
-                        rs1 += s0 + s1 + s2;
-                        continue;
-                    }
                     // inclusive scan over the wave, then over the waves
                     const double i0 = flat_wave_scan(s0), i1 = flat_wave_scan(s1), i2 = flat_wave_scan(s2);
-                    if (dbg == 7) {   // (ablation: + the wave scans, no barrier)
-                        rs1 += i0 + i1 + i2;
-                        continue;
-                    }
                     __syncthreads();  // shd and the prefix arrays of the previous tile are free
                     if (lane == 63) {
                         shd[wv * 3 + 0] = i0;
@@ -665,10 +634,6 @@ __global__ __launch_bounds__(FLAT_NT, QUAD ? 6 : 4) void flat_trend_kernel(const
                     }
                     __syncthreads();
                     double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-                    if (dbg == 8) {   // (ablation: + the two barriers around the wave totals, no carries / LDS stores)
-                        rs1 += i0;
-                        continue;
-                    }
                     for (int w2 = 0; w2 < wv && w2 < nwv; ++w2) {
                         r0 += shd[w2 * 3 + 0];
                         r1 += shd[w2 * 3 + 1];
@@ -704,7 +669,6 @@ __global__ __launch_bounds__(FLAT_NT, QUAD ? 6 : 4) void flat_trend_kernel(const
                         }
                     }
                     __syncthreads();
-                    if (dbg == 3) continue;
                     for (int q = tid; q < no; q += nt) {
                         const int hi = q + window - 1;
                         double w0 = p0[PX(hi)], w1 = p1[PX(hi)], w2 = p2[PX(hi)];
@@ -716,7 +680,7 @@ __global__ __launch_bounds__(FLAT_NT, QUAD ? 6 : 4) void flat_trend_kernel(const
                         const double v = (double)(q + half) - uc;
                         const double m2 = fma(v, fma(v, w0, -2.0 * w1), w2);  // sum (u - v)^2 y
                         const double tv = fma(quad_b, m2, quad_a * w0);
-                        if (dbg != 4) tr[o0 + q] = tv;
+                        tr[o0 + q] = tv;
                         const double r = xs[PX(q + half)] - tv;
                         rs1 += r;
                         rs2 = fma(r, r, rs2);
@@ -775,7 +739,7 @@ __global__ __launch_bounds__(FLAT_NT, QUAD ? 6 : 4) void flat_trend_kernel(const
             // staged in LDS; thread (side, r) streams row r of the operator (stored transposed, [side][tap][row]:
             // lanes read neighbouring rows) with 8 loads in flight — the plain tap loop was a chain of ~400
             // dependent L2 round trips and had become the longest part of the segment.
-            if ((item++ % T) != y || dbg == 1 || dbg == 3) continue;  // the pair of edges of this segment: one work item
+            if ((item++ % T) != y) continue;  // the pair of edges of this segment: one work item
             __syncthreads();
             for (int e = tid; e < 2 * window; e += nt)
                 fir[e] = e < window ? fm[l + e] : fm[h - window + (e - window)];
@@ -1155,18 +1119,10 @@ int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
     int fir_lds = 4896;
     while (fir_lds < 16384 && window > fir_lds / 2 + 1) fir_lds *= 2;
     const size_t lds_sel = (size_t)std::max(FLAT_NT, 264) * 8 + (size_t)(fir_lds + 2) * 8 + (size_t)FLAT_NT * 4;
-#ifdef LK_FLAT_PROFILE
-    const int stop_at = getenv("LK_FLAT_STOP") ? atoi(getenv("LK_FLAT_STOP")) : -1;  // profiling aid, see flat_init_kernel
-#else
-    constexpr int stop_at = -1;
-#endif
     FlatState *d_state = (FlatState *)h->ws.alloc((size_t)B * sizeof(FlatState));
     // trend workgroups per light curve: enough tiles for each (a 20 000-cadence light curve has ~19 tiles of ~1070 outputs at
     // window 401; a 4500-cadence one 4), and B x T >= ~4 workgroups per CU
-    int trend_T = (int)std::max<int64_t>(1, std::min<int64_t>(8, nmax / 4096));
-#ifdef LK_FLAT_PROFILE
-    if (getenv("LK_FLAT_T")) trend_T = std::max(1, std::min(16, atoi(getenv("LK_FLAT_T"))));
-#endif
+    const int trend_T = (int)std::max<int64_t>(1, std::min<int64_t>(8, nmax / 4096));
     double2 *d_rs = (double2 *)h->ws.alloc((size_t)B * trend_T * sizeof(double2));
     LK_REQUIRE(d_state != nullptr && d_rs != nullptr, "workspace exhausted (flatten state)");
     // the moment-form trend kernel keeps four tile arrays (three prefix sums + the inputs) of 1470 doubles: three 512-thread
@@ -1186,19 +1142,17 @@ int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
     constexpr int fir_pick = 4096;
     const size_t lds_pick = (size_t)std::max(FLAT_NT, 264) * 8 + (size_t)(fir_pick + 2) * 8 + (size_t)FLAT_NT * 4;
     hipLaunchKernelGGL(flat_init_kernel, dim3(B), dim3(FLAT_NT), lds_pick, stream, flux, user_mask, d_off, sigma, d_s, d_soff,
-                       d_state, fir_pick, (stop_at >= 99 && stop_at < 200) ? stop_at - 100 : -1);
+                       d_state, fir_pick);
     for (int it = 0; it < niters; ++it) {
         hipLaunchKernelGGL(flat_compact_kernel, dim3(B), dim3(FLAT_NT), 0, stream, t, flux, d_off, d_s, d_soff, d_state, trend, it);
         hipLaunchKernelGGL(flat_dtseg_kernel, dim3(B), dim3(FLAT_NT), lds_pick, stream, d_off, break_tol, d_s, d_soff, d_state,
-                           fir_pick, it, near_on, (stop_at >= 200 && stop_at < 300) ? stop_at - 200 : -1);
+                           fir_pick, it, near_on);
         if (quad_kernel)
             hipLaunchKernelGGL(flat_trend_kernel<true>, dim3(B, trend_T), dim3(FLAT_NT), lds_trend, stream, d_off, window, polyorder,
-                               break_tol, d_c, d_e, d_s, d_soff, d_state, fir_trend, quad_a, quad_b, d_minv, d_rs,
-                               stop_at >= 300 ? stop_at - 300 : -1);
+                               break_tol, d_c, d_e, d_s, d_soff, d_state, fir_trend, quad_a, quad_b, d_minv, d_rs);
         else
             hipLaunchKernelGGL(flat_trend_kernel<false>, dim3(B, trend_T), dim3(FLAT_NT), lds_sel, stream, d_off, window, polyorder,
-                               break_tol, d_c, d_e, d_s, d_soff, d_state, fir_lds, quad_a, quad_b, d_minv, d_rs,
-                               stop_at >= 300 ? stop_at - 300 : -1);
+                               break_tol, d_c, d_e, d_s, d_soff, d_state, fir_lds, quad_a, quad_b, d_minv, d_rs);
         hipLaunchKernelGGL(flat_clip_kernel, dim3(B), dim3(FLAT_NT), 0, stream, d_off, sigma, d_s, d_soff, d_state,
                            it == niters - 1 ? 1 : 0, d_rs, trend_T);
     }

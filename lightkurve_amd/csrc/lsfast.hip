@@ -33,10 +33,6 @@
 #include "lk_common.hpp"
 #include "ls_epilogue.hpp"
 
-#ifndef LSF_STENCIL_PROD
-#define LSF_STENCIL_PROD 1   // extirpolation weights as products of three distances (no IEEE divisions); 0: the reference's quotient form
-#endif
-
 namespace lk {
 
 typedef double lk_d2v __attribute__((ext_vector_type(2)));  // for the non-temporal load / store builtins
@@ -232,11 +228,7 @@ struct Stencil4 {
 };
 __device__ __forceinline__ Stencil4 stencil4(double x, int nfft) {
     Stencil4 st;
-#if LSF_STENCIL_PROD
     if (x == floor(x)) {  // (what fmod(x, 1.0) == 0.0 says, without the call)
-#else
-    if (fmod(x, 1.0) == 0.0) {
-#endif
         st.i0 = (int)x;
         st.n = 1;
         st.wt[0] = 1.0;
@@ -247,25 +239,16 @@ __device__ __forceinline__ Stencil4 stencil4(double x, int nfft) {
     ilo = min(max(ilo, 0), nfft - 4);
     // d1..d3 as the reference forms them: x - ilo - k (same value: ilo + k is exact in double)
     const double d0 = x - (double)ilo, d1 = d0 - 1.0, d2 = d0 - 2.0, d3 = d0 - 3.0;
-    const double prod = ((d0 * d1) * d2) * d3;
     // j = 0..3: ind = ilo + 3 - j, denominators 6, -2, 2, -6
     st.i0 = ilo;
     st.n = 4;
-#if LSF_STENCIL_PROD
-    // prod / (c_j d_j) = the product of the OTHER three distances over c_j: the Lagrange weights without the four IEEE divisions
-    // (~25 instructions each in the extirpolation phase of every column tile; same value to an ulp or two, better conditioned
-    // next to a grid point)
-    (void)prod;
+    // the reference's prod / (c_j d_j) with prod = d0 d1 d2 d3 is the product of the OTHER three distances over c_j: the Lagrange
+    // weights without the four IEEE divisions (~25 instructions each in the extirpolation phase of every column tile; same value
+    // to an ulp or two, better conditioned next to a grid point)
     st.wt[3] = ((d0 * d1) * d2) * (1.0 / 6.0);
     st.wt[2] = ((d0 * d1) * d3) * -0.5;
     st.wt[1] = ((d0 * d2) * d3) * 0.5;
     st.wt[0] = ((d1 * d2) * d3) * (-1.0 / 6.0);
-#else
-    st.wt[3] = prod / (6.0 * d3);
-    st.wt[2] = prod / (-2.0 * d2);
-    st.wt[1] = prod / (2.0 * d1);
-    st.wt[0] = prod / (-6.0 * d0);
-#endif
     return st;
 }
 
@@ -648,25 +631,7 @@ __global__ __launch_bounds__(256) void fft_cols_reg_kernel(double2 *__restrict__
 // once and kept in registers over the Q passes; rows keep their natural order k1 = Q q + s.
 constexpr int PRUNED_CT = 16;
 
-// Scheduling experiments of round 6 (tools/build_variant.sh ... "-DLSF_PRIO=<bits>"; profiles/r06_lsfast_setprio_ab.txt): wave
-// priority 3 over bit 0 the store phase of a pass, bit 1 the extirpolation phase of the column kernel, bit 2 the loads of the
-// row kernel.  Release builds compile none of them (measured: no gain at two waves per SIMD).
-#ifndef LSF_PRIO
-#define LSF_PRIO 0
-#endif
-#ifndef LSF_TWO_STREAMS
-#define LSF_TWO_STREAMS 1   // number of EXTRA streams of the chunk loop (0 .. 3); 1: -2 % on the step (profiles/r06_lsfast_two_streams_ab.txt)
-#endif
-#ifndef LSF_STAGGER
-#define LSF_STAGGER 0
-#endif
-#ifndef LSF_CHUNK_HALF_GB
-#define LSF_CHUNK_HALF_GB 3  // bytes of grids per chunk, in units of 2^29 (1.5 GiB = 60 targets at Nfft = 2^19)
-#endif
-#define LSF_SETPRIO(bit, p)                                         \
-    do {                                                            \
-        if (LSF_PRIO & (bit)) __builtin_amdgcn_s_setprio(p);        \
-    } while (0)
+constexpr int LSF_CHUNK_HALF_GB = 3;  // bytes of grids per chunk, in units of 2^29 (1.5 GiB = 60 targets at Nfft = 2^19)
 
 // Extirpolation fused in (ordered targets, `tab16` given): the workgroup's input — the cells of its 16 columns in the rows
 // that can hold samples — is not read from a spread grid but built here: the 16-cell-granular tables of lsf_tables_kernel
@@ -703,7 +668,6 @@ __global__ __launch_bounds__(PRUNED_CT * (1 << ((LP + 1) / 2)), 2) void fft_cols
         for (int e = tid; e < ru * CT; e += NT) acc[e] = make_double2(0.0, 0.0);
         __syncthreads();
         if (!(g == 1 && !fit_mean)) {  // (the unused grid stays zero)
-            LSF_SETPRIO(2, 3);
             const int b = b0 + lbt;
             const int64_t lo = n_off[b];
             const FastStats st = stats[b];
@@ -772,7 +736,6 @@ __global__ __launch_bounds__(PRUNED_CT * (1 << ((LP + 1) / 2)), 2) void fft_cols
                     }
                 }
             }
-            LSF_SETPRIO(2, 0);
         }
         __syncthreads();
         if (p1) {
@@ -834,14 +797,12 @@ __global__ __launch_bounds__(PRUNED_CT * (1 << ((LP + 1) / 2)), 2) void fft_cols
             for (int j = 0; j < Bq; ++j) u[j] = row[j];
             reg_fft<LB>(u);
             double2 w = wout;
-            LSF_SETPRIO(1, 3);
 #pragma unroll
             for (int kb = 0; kb < Bq; ++kb) {
                 const int q = jk + A * kb;
                 O[(size_t)(Q * q + s) * CT + f] = cmul(u[brev_c(kb, LB)], w);
                 w = cmul(w, stepc);
             }
-            LSF_SETPRIO(1, 0);
         }
         wjs = cmul(wjs, wj);
         wqs = cmul(wqs, wq);
@@ -1030,13 +991,11 @@ __global__ __launch_bounds__(Rows512::NT, 2) void fft_rows512_power_kernel(
     };
     double2 v[16];
     auto load = [&](const double2 *G) {
-        LSF_SETPRIO(4, 3);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const lk_d2v q = __builtin_nontemporal_load(reinterpret_cast<const lk_d2v *>(G + ((size_t)i << (m1 + 5))));
             v[i] = make_double2(q.x, q.y);
         }
-        LSF_SETPRIO(4, 0);
     };
     double2 step1, step4;  // W_512^j, W_512^{4 j}
     {
@@ -1594,11 +1553,7 @@ int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *
     const int CT = std::max(1, std::min(N2, 4096 / N1)), RT = std::max(1, std::min(N1, 4096 / N2));
     // targets per chunk: the grids (3 x 16 B x Nfft per target) stay within 1.5 GiB (LSF_CHUNK_HALF_GB; 1, 1.5 and 2 GiB
     // measure the same within the rep noise once two streams share the chunks, 4 GiB no better)
-#ifdef LSF_CHUNK_MB   // (experiments: chunks small enough for the 256-MiB Infinity Cache)
-    const size_t chunk_bytes = (size_t)LSF_CHUNK_MB << 20;
-#else
     const size_t chunk_bytes = (size_t)LSF_CHUNK_HALF_GB << 29;
-#endif
     int Bc = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, chunk_bytes / ((size_t)48 * nfft)));
     if (Bc >= 8) Bc &= ~3;  // N1 / 8 row tiles per target x a multiple of 4 targets: a whole number of rounds of 2 x 256 workgroups
     const bool reg_path = m1 >= 4 && m1 <= 10 && m2 >= 4 && m2 <= 10;
@@ -1615,7 +1570,7 @@ int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *
     const int ntab_max = std::max(ntab256, ntab16);
     h->ws.reset();
     int rc = h->ws.reserve((size_t)(B + 1) * 8 + (size_t)B * sizeof(FastStats) + 512 +
-                           (size_t)Bc * 3 * nfft * 16 * (2 + (LSF_TWO_STREAMS > 1 ? LSF_TWO_STREAMS - 1 : 0)) + (size_t)Bc * 3 * M * 16 + (size_t)B * 16 +
+                           (size_t)Bc * 3 * nfft * 16 * 2 + (size_t)Bc * 3 * M * 16 + (size_t)B * 16 +
                            (size_t)B * 4 * ntab_max * 4 + (size_t)(B + 1) * nparts_max * sizeof(PeakPart) + 16384);
     if (rc) return rc;
     int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
@@ -1627,11 +1582,6 @@ int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *
     const int tw = tile_width(m1, m2);
     double2 *d_grids2 = fused ? (double2 *)h->ws.alloc((size_t)Bc * 3 * nfft * 16) : nullptr;
     LK_REQUIRE(!fused || d_grids2 != nullptr, "workspace exhausted");
-    double2 *d_grids3[2] = {nullptr, nullptr};
-    for (int a = 0; a < LSF_TWO_STREAMS - 1 && a < 2; ++a) {
-        d_grids3[a] = fused ? (double2 *)h->ws.alloc((size_t)Bc * 3 * nfft * 16) : nullptr;
-        LK_REQUIRE(!fused || d_grids3[a] != nullptr, "workspace exhausted");
-    }
     int *d_rows = (int *)h->ws.alloc((size_t)B * 4 * 4);
     int *d_plan = (int *)h->ws.alloc(64);
     int *d_tab = reg_path ? (int *)h->ws.alloc((size_t)B * 4 * ntab_max * 4) : nullptr;
@@ -1668,38 +1618,31 @@ int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *
     // Chunks alternate between the caller's stream and a second one (each with its own intermediate: the spread-grid buffer is
     // free when every target is ordered and the pruned column kernel spreads by itself), so that the tail of a chunk's row
     // kernel and the head of the next chunk's column kernel — and, throughout, a store-heavy and a load-heavy kernel — share the
-    // GPU.  LSF_TWO_STREAMS (experiment of round 6, profiles/r06_lsfast_two_streams_ab.txt).
-    const int nstreams = (LSF_TWO_STREAMS && fused && lp != 0 && n_unordered == 0 && B > Bc) ? std::min(LSF_TWO_STREAMS + 1, 4) : 1;
-    double2 *inter_buf[4] = {d_grids2, d_grids, d_grids3[0], d_grids3[1]};
-    if (nstreams > 1) {
+    // GPU: -2 % on the step against one stream (round 6, profiles/r06_lsfast_two_streams_ab.txt).
+    const bool two_streams = fused && lp != 0 && n_unordered == 0 && B > Bc;
+    if (two_streams) {
         if (!h->ev_ls_fork) LK_HIP_CHECK(hipEventCreateWithFlags(&h->ev_ls_fork, hipEventDisableTiming));
         LK_HIP_CHECK(hipEventRecord(h->ev_ls_fork, stream));
-        for (int a = 0; a < nstreams - 1; ++a) {
-            if (!h->s_ls_aux[a]) LK_HIP_CHECK(hipStreamCreateWithFlags(&h->s_ls_aux[a], hipStreamNonBlocking));
-            if (!h->ev_ls_join[a]) LK_HIP_CHECK(hipEventCreateWithFlags(&h->ev_ls_join[a], hipEventDisableTiming));
-            if (!LSF_STAGGER) LK_HIP_CHECK(hipStreamWaitEvent(h->s_ls_aux[a], h->ev_ls_fork, 0));
-        }
+        if (!h->s_ls_aux[0]) LK_HIP_CHECK(hipStreamCreateWithFlags(&h->s_ls_aux[0], hipStreamNonBlocking));
+        if (!h->ev_ls_join[0]) LK_HIP_CHECK(hipEventCreateWithFlags(&h->ev_ls_join[0], hipEventDisableTiming));
+        LK_HIP_CHECK(hipStreamWaitEvent(h->s_ls_aux[0], h->ev_ls_fork, 0));
     }
     hipStream_t caller_stream = stream;
     // an error return between the fork and the join must not leave work on the second stream behind (the next call resets the
     // workspace those kernels use): the guard drains it
     struct AuxGuard {
-        lk_handle *h;
-        int n;
-        bool joined;
+        hipStream_t aux;  // the second stream until it has been joined, else nullptr
         ~AuxGuard() {
-            if (!joined)
-                for (int a = 0; a < n; ++a)
-                    if (h->s_ls_aux[a]) (void)hipStreamSynchronize(h->s_ls_aux[a]);
+            if (aux) (void)hipStreamSynchronize(aux);
         }
-    } aux_guard{h, nstreams - 1, nstreams == 1};
+    } aux_guard{two_streams ? h->s_ls_aux[0] : nullptr};
     int chunk_no = 0;
     for (int b0 = 0; b0 < B; b0 += Bc, ++chunk_no) {
         const int nb = std::min(Bc, B - b0);
         double2 *gr = d_grids;
-        const int lane_s = chunk_no % nstreams;
-        stream = lane_s ? h->s_ls_aux[lane_s - 1] : caller_stream;
-        double2 *inter = inter_buf[lane_s];
+        const bool on_aux = two_streams && (chunk_no & 1);
+        stream = on_aux ? h->s_ls_aux[0] : caller_stream;
+        double2 *inter = on_aux ? d_grids : d_grids2;
         // targets that are not "ordered" (unsorted time, or a 2f grid that wraps): zero their live rows, scatter with global
         // atomics.  Skipped when the plan found none (the usual batch).
         if (!reg_path) {
@@ -1729,21 +1672,17 @@ int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *
                 const SpreadArgs sa{t, y, dy, d_off, d_stats, b0, f0, df, fit_mean, n_unordered < B ? d_tab : nullptr, ntab};
                 LK_REQUIRE(launch_cols_pruned(h, lp, m1, m2, nb * 3, gr, d_rows + (size_t)b0 * 4, inter, sa, stream),
                            "no pruned column kernel for 2^%d rows", lp);
-                if (LSF_STAGGER && nstreams > 1 && chunk_no == 0) {  // the other streams start one column kernel late: opposite phases
-                    LK_HIP_CHECK(hipEventRecord(h->ev_ls_fork, stream));
-                    for (int a = 0; a < nstreams - 1; ++a) LK_HIP_CHECK(hipStreamWaitEvent(h->s_ls_aux[a], h->ev_ls_fork, 0));
-                }
             } else {
                 launch_cols_reg(h, m1, m2, nb * 3, gr, d_rows + (size_t)b0 * 4, inter, tw, stream);
             }
             LK_REQUIRE(launch_rows_power(h, m1, m2, nb, inter, fa, lp ? PRUNED_CT : tw, stream),
                        "no step-2 kernel for this layout");
             if (b0 + nb == B) {
-                for (int a = 0; a < nstreams - 1; ++a) {  // join: the caller's stream continues when all have drained
-                    LK_HIP_CHECK(hipEventRecord(h->ev_ls_join[a], h->s_ls_aux[a]));
-                    LK_HIP_CHECK(hipStreamWaitEvent(caller_stream, h->ev_ls_join[a], 0));
+                if (two_streams) {  // join: the caller's stream continues when both have drained
+                    LK_HIP_CHECK(hipEventRecord(h->ev_ls_join[0], h->s_ls_aux[0]));
+                    LK_HIP_CHECK(hipStreamWaitEvent(caller_stream, h->ev_ls_join[0], 0));
                 }
-                aux_guard.joined = true;
+                aux_guard.aux = nullptr;
                 stream = caller_stream;
                 if (d_peaks)
                     hipLaunchKernelGGL(lsf_peaks_kernel, dim3(B), dim3(64), 0, stream, d_peaks, nparts, 0, max_out, arg_out);

@@ -47,10 +47,9 @@ constexpr int PLD_DIRECT_MAX = 138;  // largest P whose Gram matrix fits LDS for
 // DesignMatrix.pca), whose OUTPUT is the basis, keeps 1e-10.
 #define PLD_EIG_TOL 1e-7
 #define PCA_EIG_TOL 1e-10
-#ifndef PLD_F32_RES
-#define PLD_F32_RES 1e-5  // relative residual above which the Chebyshev filter reads the float32 copy of C (1e-3 until round 5: with the
-                          // stop at 1e-7 the last filter step may read it too — same steps, same corrected flux, -0.4 ms per 500 cutouts)
-#endif
+constexpr double PLD_F32_RES = 1e-5;  // relative residual above which the Chebyshev filter reads the float32 copy of C (1e-3 until
+                                      // round 5: with the stop at 1e-7 the last filter step may read it too — same steps, same
+                                      // corrected flux, -0.4 ms per 500 cutouts)
 constexpr int PLD_KC = 64;    // rows of the basis staged in LDS per step of the MFMA product C Q (64 x 66 doubles also hold
                               // eig_xty's 16 partial tiles; 128 rows left no room for a second workgroup on the CU)
 constexpr int PLD_QS = PLD_LMAX + 2;  // LDS row stride of that stage (doubles)
@@ -60,9 +59,7 @@ __host__ __device__ constexpr int pld_qs32(int na) { return 16 * na + 16; }
 // Relative residual above which the Rayleigh-Ritz product itself reads the float32 copy of C on the float32 matrix cores (round 6):
 // a step that starts three decades above the float32 noise floor cannot pass the 1e-7 stop, so its Ritz pairs only have to
 // steer the filter; convergence is only ever declared from a float64 product.
-#ifndef PLD_RR32_RES
-#define PLD_RR32_RES 1e-3
-#endif
+constexpr double PLD_RR32_RES = 1e-3;
 typedef double pld_d4 __attribute__((ext_vector_type(4)));
 
 static int ncombos(int k, int order) {  // C(k + order - 1, order)
@@ -304,17 +301,11 @@ __global__ __launch_bounds__(256) void pld_products_kernel(const double *__restr
 // list: first row in row order, first column, 16-bit mask of the tiles that hold canonical pairs).
 constexpr int MG_CH = 64;  // cadences per LDS stage
 // Round 6, the masked launch (profiles/r06_pld_moment_gram.txt: 39 % of its wave cycles parked, 46 exec-mask branches per step):
-//   MG_UNIFORM   the wave-tile descriptor is read through readfirstlane — the compiler could not see through `threadIdx.x >> 6` that
-//                a wave's 64 lanes share it, and guarded every MFMA and every operand row with s_and_saveexec + s_cbranch_execz;
-//   MG_ALL_ROWS  all 4 + 4 operand rows of a wave tile are generated, needed or not: the reads of a row no tile uses sat behind a
-//                branch of their own, each with its wait — 24 unconditional ds_read_b64 per step cost less than the serialised few.
-// A/B on one box, PLD step of 500 cutouts, 3 interleaved reps: neither 29.49 ms | ALL_ROWS 28.67 | UNIFORM 29.33 | both 28.59.
-#ifndef MG_UNIFORM
-#define MG_UNIFORM 1
-#endif
-#ifndef MG_ALL_ROWS
-#define MG_ALL_ROWS 1
-#endif
+//   the wave-tile descriptor is read through readfirstlane — the compiler could not see through `threadIdx.x >> 6` that a wave's
+//   64 lanes share it, and guarded every MFMA and every operand row with s_and_saveexec + s_cbranch_execz;
+//   all 4 + 4 operand rows of a wave tile are generated, needed or not: the reads of a row no tile uses sat behind a branch of
+//   their own, each with its wait — 24 unconditional ds_read_b64 per step cost less than the serialised few.
+// A/B on one box, PLD step of 500 cutouts, 3 interleaved reps: neither 29.49 ms | all rows 28.67 | readfirstlane 29.33 | both 28.59.
 constexpr int kMomentMinCols = 100;  // product blocks at least this wide take the moment form
 template <int O, bool FULL, int PRE, int KS>  // KS: LDS row stride (k | 1) when known at compile time, else 0; PRE: MG_CH * k / 256 elements of the next stage wait in registers (4: k <= 16, 12: k <= 48)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void pld_moment_gram_kernel(
@@ -323,30 +314,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int *__restrict__ rperm, double *__restrict__ mean) {
     extern __shared__ __attribute__((aligned(16))) double mg_us[];  // 2 x MG_CH x ks
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, lq = lane >> 4, lr = lane & 15;
-#if MG_UNIFORM
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#else
-    const int wave = tid >> 6;
-#endif
     const int ks = KS > 0 ? KS : (k | 1);
     const int w = blockIdx.x * 4 + wave;
     const int4 t = wt[min(w, nwt - 1)];
-#if MG_UNIFORM
     // the wave tile is the same for the 64 lanes of a wave: say so (the compiler cannot see it through `threadIdx.x >> 6` and
     // guarded each MFMA and each operand row with an exec-mask branch — s_and_saveexec + s_cbranch_execz, 46 per step)
     const int r0 = __builtin_amdgcn_readfirstlane(t.x), c0 = __builtin_amdgcn_readfirstlane(t.y);
     const unsigned mask = w < nwt ? (unsigned)__builtin_amdgcn_readfirstlane(t.z) : 0u;
-#else
-    const int r0 = t.x, c0 = t.y;
-    const unsigned mask = w < nwt ? (unsigned)t.z : 0u;
-#endif
     // bit i: this wave tile is the one that also sums the products of row tile i over the cadences (their column means:
     // every (row, cadence) pair passes through exactly one lane of the A operand)
-#if MG_UNIFORM
     const unsigned mflag = (!FULL && w < nwt) ? (unsigned)__builtin_amdgcn_readfirstlane(t.w) : 0u;  // (the host keeps such wave tiles out of the FULL launch)
-#else
-    const unsigned mflag = (!FULL && w < nwt) ? (unsigned)t.w : 0u;  // (the host keeps such wave tiles out of the FULL launch)
-#endif
     double msum[4] = {0.0, 0.0, 0.0, 0.0};
     // rows / columns past the end are clamped, not zeroed: their accumulator entries are simply never stored
     int ia[4][O], ib[4][O];
@@ -385,13 +363,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     fetch(0);
     park(mg_us);
     __syncthreads();
-    // byte offsets of the factors inside a stage row; rows / columns that no needed tile touches are never generated
+    // byte offsets of the factors inside a stage row
     int oa[4][O], ob[4][O];
-    bool ua[4], ub[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        ua[i] = FULL || MG_ALL_ROWS || (mask & (0xfu << (4 * i))) != 0;
-        ub[i] = FULL || MG_ALL_ROWS || (mask & (0x1111u << i)) != 0;
 #pragma unroll
         for (int pos = 0; pos < O; ++pos) {
             oa[i][pos] = ia[i][pos] * 8;
@@ -405,14 +380,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     auto issue = [&](const char *rowp) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            if (ua[i]) {
 #pragma unroll
-                for (int pos = 0; pos < O; ++pos) ra[i][pos] = *reinterpret_cast<const double *>(rowp + oa[i][pos]);
-            }
-            if (ub[i]) {
+            for (int pos = 0; pos < O; ++pos) ra[i][pos] = *reinterpret_cast<const double *>(rowp + oa[i][pos]);
 #pragma unroll
-                for (int pos = 0; pos < O; ++pos) rb[i][pos] = *reinterpret_cast<const double *>(rowp + ob[i][pos]);
-            }
+            for (int pos = 0; pos < O; ++pos) rb[i][pos] = *reinterpret_cast<const double *>(rowp + ob[i][pos]);
         }
     };
     auto multiply = [&]() {
@@ -490,9 +461,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 // G[i][j] = moment of the merged multiset of columns i and j (looked up through the host-built index table) minus
 // N mean_i mean_j: the Gram matrix of the CENTRED products, written in full (both triangles).
-#ifndef MEXP_U
-#define MEXP_U 8
-#endif
+constexpr int MEXP_U = 8;  // groups of four columns per thread of the expansion (one left its stores at 2 TB/s, two at 3)
 __global__ __launch_bounds__(256) void pld_moment_expand_kernel(const double *__restrict__ Mcan, size_t mstride,
                                                                  const uint32_t *__restrict__ src,
                                                                  const double *__restrict__ mean, int Pc, int ldg, double Nd,
@@ -555,9 +524,6 @@ __global__ __launch_bounds__(256) void pld_moment_expand_kernel(const double *__
 // and C is symmetric.  A workgroup takes a tile pair (ti <= tj): gathers the block (rows of ti, columns of tj) once, writes it, and
 // writes its transpose to (tj, ti) through LDS (rows of 65 doubles): half the gathers and half the index reads, every store still a
 // 32-byte (float64) / 16-byte (float32) run.  Same values, same bits.
-#ifndef MEXP_SYM
-#define MEXP_SYM 1
-#endif
 __global__ __launch_bounds__(256) void pld_moment_expand_sym_kernel(const double *__restrict__ Mcan, size_t mstride,
                                                                      const uint32_t *__restrict__ src,
                                                                      const double *__restrict__ mean, int Pc, int ldg, double Nd,
@@ -1117,8 +1083,8 @@ static __device__ __noinline__ double eig_xm(EigCtx c, const double *X_, double 
     return part;
 }
 
-// Optional epilogue of a product (the phase-split iteration's filter steps): dst = alpha C src - beta src - gamma prev, i.e. one
-// step of the Chebyshev recurrence written by the product's own stores instead of a separate sweep over three P x l arrays.
+// Optional epilogue of a product (the Chebyshev filter steps): dst = alpha C src - beta src - gamma prev, i.e. one step of the
+// recurrence written by the product's own stores instead of a separate sweep over three P x l arrays.
 struct EigEpi {
     double alpha, beta, gamma;
     const double *prev;
@@ -1555,20 +1521,6 @@ static __device__ __noinline__ bool eig_cholqr(EigCtx c, const double *Yin, doub
     return true;
 }
 
-// Per-matrix state of the phase-split iteration (pld_eigs_* kernels below), 64 bytes in global memory.
-struct EigsState {
-    int done;       // nothing left to do here: converged, or handed to the one-kernel iteration (converged == 0)
-    int converged;
-    int it;         // Rayleigh-Ritz steps taken
-    int rr_var;     // product variant of the NEXT Rayleigh-Ritz step: 0 = float32 C on the float32 matrix cores, 2 = float64
-    int f_var;      // variant of this step's two filter products: 0, 1 = float32 C with float64 products, 2
-    int cheb;       // Chebyshev filter (else plain powers of C)
-    int pad[2];
-    double cc, ie;  // filter interval [0, theta_cut]: centre = half-width = cc, ie = 1 / cc
-    double res, th0;
-};
-static_assert(sizeof(EigsState) == 64, "EigsState is indexed with a 64-byte stride");
-
 // Top-k eigenpairs of the P x P Gram matrix of matrix b -> V (P x k, row-major), lam (k).  One workgroup per matrix.
 // scratch per matrix: 4 * P * l doubles (Q, Z, R, Y).  NA = number of 16-column tiles of the basis (l <= 16 NA): a
 // compile-time constant, because with a run-time bound the compiler keeps all 4 x 4 accumulator tiles of the product
@@ -1578,11 +1530,9 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
                                                              double *__restrict__ scratch, double *__restrict__ V,
                                                              double *__restrict__ lam, long long *__restrict__ iters_out,
                                                              int max_it, int *__restrict__ status, int cheb_on, int kc,
-                                                             int mirror, double tol, const float *__restrict__ G32 = nullptr,
-                                                             const EigsState *__restrict__ skip = nullptr) {
+                                                             int mirror, double tol, const float *__restrict__ G32 = nullptr) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x, nt = blockDim.x, b = blockIdx.x;
-    if (skip && skip[b].converged) return;  // the phase-split iteration already delivered this matrix
     double *Gb = G + (size_t)b * ldg * ldg;
     double *Vb = V + (size_t)b * P * k, *lamb = lam + (size_t)b * k;
     const int ld = l + 1;                      // odd leading dimension: conflict-free column walks
@@ -1786,186 +1736,6 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
     if (tid == 0 && status) status[b] = converged ? 1 : 0;
 }
 
-// ------------------------------------------------------------------------------------------------ phase-split iteration
-// Round 6.  The one-kernel iteration above keeps a matrix on one workgroup from the random start to the last Ritz vector: its
-// products with C (HBM streams) and its l x l eigenproblems / Cholesky factorisations (latency chains on one wave) share one
-// register budget (128 VGPRs, ~60 spilled around the calls), and since the 500 workgroups of a batch start together and do
-// identical work, the two workgroups of a CU sit in the SAME phase at the same time — the serial stretches were never hidden
-// behind the other workgroup's stream (per matrix 2.5 ms of serial phases + 4.95 ms of products = the kernel's 7.45 ms).
-// Here every phase is its own launch over all matrices, state in global memory:
-//   pld_eigs_init_kernel   mirror the Gram blocks, pseudo-random start, Cholesky-QR            (once)
-//   pld_eigs_prod_kernel   dst = C src with the filter recurrence fused into its stores        (3 per step: Rayleigh-Ritz, filter 1, 2)
-//   pld_eigs_rr_kernel     Q^T Z, l x l Jacobi, Ritz vectors + residual, stop test, filter plan
-//   pld_eigs_orth_kernel   Cholesky-QR of the filtered block
-// A product launch is nothing but streams (deep register prefetch, no serial phase inside); the small phases run two workgroups
-// per CU with nobody streaming beside them.  Per-matrix control flow lives in EigsState: converged matrices drop out of every
-// later launch by their `done` flag, precision follows the residual (float32 matrix cores -> float32 C with float64 products ->
-// float64), and whatever has not converged after the fixed number of steps the launcher queues — or hits a Cholesky breakdown —
-// is handed to the one-kernel iteration (which restarts it; `skip` = the converged flags).  No host synchronisation.
-struct EigsLds {
-    int T, W, rot, shred, vec, order, qstage;
-};
-__device__ __forceinline__ EigsLds eigs_lds(int l, int nt) {
-    const int ld = l + 1;
-    EigsLds o;
-    o.T = 0;
-    o.W = l * ld;
-    o.rot = 2 * l * ld;
-    o.shred = o.rot + 2 * l;
-    o.vec = o.shred + nt;
-    o.order = o.vec + 2 * l;
-    o.qstage = o.order + (l + 1) / 2 + 1;
-    return o;
-}
-static size_t eigs_small_lds_bytes(int l, int nt, int kc) {
-    const int ld = l + 1;
-    return ((size_t)2 * l * ld + 2 * l + nt + 2 * l + (l + 1) / 2 + 1 + (size_t)kc * PLD_QS) * 8 + 64;
-}
-
-template <int NA>
-__global__ __launch_bounds__(512) void pld_eigs_init_kernel(double *__restrict__ G, int ldg, int P, int k, int l,
-                                                            double *__restrict__ scratch, EigsState *__restrict__ state, int kc,
-                                                            int mirror, int have32) {
-    const int tid = threadIdx.x, nt = blockDim.x, b = blockIdx.x;
-    double *Gb = G + (size_t)b * ldg * ldg;
-    const EigsLds o = eigs_lds(l, nt);
-    const EigCtx ctx{o.T, o.W, o.rot, o.shred, o.vec, o.qstage, o.order, Gb, nullptr, ldg, P, k, l, l + 1, kc, 0};
-    double *Q = scratch + (size_t)b * 4 * P * l;
-    if (mirror)
-        for (int e = tid; e < P * P; e += nt) {
-            const int i = e / P, j = e - i * P;
-            if ((j >> 6) < (i >> 6)) Gb[(size_t)i * ldg + j] = Gb[(size_t)j * ldg + i];
-        }
-    for (int e = tid; e < P * l; e += nt) {  // the deterministic pseudo-random start of the one-kernel iteration
-        unsigned int x = (unsigned int)(e + 1) * 2654435761u;
-        x ^= x >> 15;
-        x *= 2246822519u;
-        x ^= x >> 13;
-        Q[e] = (double)(x & 0xffffffu) / 8388608.0 - 1.0;
-    }
-    __syncthreads();
-    if (!eig_cholqr<NA>(ctx, Q, Q)) eig_svqb<NA>(ctx, Q);
-    if (tid == 0) {
-        EigsState st;
-        st.done = 0;
-        st.converged = 0;
-        st.it = 0;
-        st.rr_var = have32 ? 0 : 2;
-        st.f_var = 2;
-        st.cheb = 0;
-        st.pad[0] = st.pad[1] = 0;
-        st.cc = st.ie = 0.0;
-        st.res = 1e300;
-        st.th0 = 0.0;
-        state[b] = st;
-    }
-}
-
-// which = 0: Z = C Q (Rayleigh-Ritz product, variant rr_var); 1: Z = a C Y - b Y - g R; 2: Q = a C Z - b Z - g Y (filter, f_var)
-// with (a, b, g) = (2 / e, 2 c / e, 1) for the Chebyshev recurrence and (1, 0, 0) for plain powers.
-template <int NA>
-__global__ __launch_bounds__(512, 4) void pld_eigs_prod_kernel(const double *__restrict__ G, const float *__restrict__ G32, int ldg,
-                                                               int P, int l, double *__restrict__ scratch,
-                                                               const EigsState *__restrict__ state, int which, int kc, int kc32) {
-    const int b = blockIdx.x;
-    const EigsState st = state[b];
-    if (st.done) return;
-    double *Q = scratch + (size_t)b * 4 * P * l, *Z = Q + (size_t)P * l, *R = Z + (size_t)P * l, *Y = R + (size_t)P * l;
-    const EigCtx ctx{0, 0, 0, 0, 0, 0, 0, const_cast<double *>(G) + (size_t)b * ldg * ldg, G32 ? G32 + (size_t)b * ldg * ldg : nullptr,
-                     ldg, P, 0, l, l + 1, kc, kc32};
-    const double *src = which == 0 ? Q : which == 1 ? Y : Z, *prev = which == 1 ? R : Y;
-    double *dst = which == 2 ? Q : Z;
-    const int var = which == 0 ? st.rr_var : st.f_var;
-    if (which == 0) {
-        if (var == 0)
-            eig_cq32<NA>(ctx, src, dst);
-        else
-            eig_cq<NA>(ctx, src, dst);
-        return;
-    }
-    const EigEpi ep = st.cheb ? EigEpi{2.0 * st.ie, 2.0 * st.ie * st.cc, 1.0, prev} : EigEpi{1.0, 0.0, 0.0, prev};
-    if (var == 0)
-        eig_cq32<NA, true>(ctx, src, dst, ep);
-    else if (var == 1)
-        eig_cq<NA, true, true>(ctx, src, dst, ep);
-    else
-        eig_cq<NA, false, true>(ctx, src, dst, ep);
-}
-
-template <int NA>
-__global__ __launch_bounds__(512) void pld_eigs_rr_kernel(int P, int k, int l, double *__restrict__ scratch,
-                                                          EigsState *__restrict__ state, double *__restrict__ V,
-                                                          double *__restrict__ lam, int kc, double tol, int cheb_on, int last,
-                                                          int have32) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int tid = threadIdx.x, nt = blockDim.x, b = blockIdx.x;
-    const EigsState st = state[b];
-    if (st.done) return;
-    const EigsLds o = eigs_lds(l, nt);
-    const int ld = l + 1;
-    const EigCtx ctx{o.T, o.W, o.rot, o.shred, o.vec, o.qstage, o.order, nullptr, nullptr, 0, P, k, l, ld, kc, 0};
-    double *T = lds + o.T, *W = lds + o.W, *shred = lds + o.shred, *vec = lds + o.vec, *theta = vec + l;
-    int *order = reinterpret_cast<int *>(lds + o.order);
-    double *Q = scratch + (size_t)b * 4 * P * l, *Z = Q + (size_t)P * l, *R = Z + (size_t)P * l, *Y = R + (size_t)P * l;
-    eig_xty(ctx, Q, Z, o.W);  // T = Q^T Z (symmetrised)
-    for (int e = tid; e < l * l; e += nt) {
-        const int a = e / l, c = e % l;
-        T[a * ld + c] = 0.5 * (W[a * ld + c] + W[c * ld + a]);
-    }
-    __syncthreads();
-    jacobi_eig_lds<false>(o.T, o.W, l, ld, o.rot, o.shred);
-    sort_desc_lds(T, l, ld, order);
-    if (tid < l) theta[tid] = T[order[tid] * ld + order[tid]];
-    __syncthreads();
-    for (int e = tid; e < l * l; e += nt) {
-        const int a = e / l, c = e % l;
-        T[a * ld + c] = W[a * ld + order[c]];
-    }
-    __syncthreads();
-    const double th0 = fabs(theta[0]), th_k = theta[k - 1], th_cut = theta[l - 1];
-    const bool cheb = th_cut > 0.0 && (((cheb_on & 1) && th_k < 1.5 * th_cut && th0 < 30.0 * th_cut) || (cheb_on & 2));
-    const double cc = 0.5 * th_cut, ie = cheb ? 1.0 / cc : 0.0;
-    // R = Q W (Ritz vectors by Ritz value), Y = Z W = C R and the residual of the k wanted pairs in one pass; with the Chebyshev
-    // filter Y is stored as the recurrence's first term X1 = (C R - c R) / e straight away (unused if this step converges)
-    const double part = eig_xm<NA, true>(ctx, Q, R, Z, Y, o.T, o.vec + l, cc, ie);
-    const double res = sqrt(block_sum_dyn(part, shred));
-    // only a float64 product can declare convergence
-    const bool conv = st.rr_var == 2 && res <= tol * th0 * sqrt((double)k);
-    if (conv) {
-        double *Vb = V + (size_t)b * P * k;
-        for (int e = tid; e < P * k; e += nt) Vb[e] = R[(size_t)(e / k) * l + (e % k)];
-        if (tid < k) lam[(size_t)b * k + tid] = theta[tid];
-    }
-    if (tid == 0) {
-        EigsState nx = st;
-        nx.it = st.it + 1;
-        nx.res = res;
-        nx.th0 = th0;
-        nx.converged = conv ? 1 : 0;
-        nx.done = (conv || last) ? 1 : 0;
-        nx.cheb = cheb ? 1 : 0;
-        nx.cc = cc;
-        nx.ie = ie;
-        const bool far = have32 && res > PLD_RR32_RES * th0;
-        nx.rr_var = far ? 0 : 2;
-        nx.f_var = far ? 0 : (have32 && res > PLD_F32_RES * th0) ? 1 : 2;
-        state[b] = nx;
-    }
-}
-
-template <int NA>
-__global__ __launch_bounds__(512) void pld_eigs_orth_kernel(int P, int k, int l, double *__restrict__ scratch,
-                                                            EigsState *__restrict__ state, int kc) {
-    const int tid = threadIdx.x, nt = blockDim.x, b = blockIdx.x;
-    if (state[b].done) return;
-    const EigsLds o = eigs_lds(l, nt);
-    const EigCtx ctx{o.T, o.W, o.rot, o.shred, o.vec, o.qstage, o.order, nullptr, nullptr, 0, P, k, l, l + 1, kc, 0};
-    double *Q = scratch + (size_t)b * 4 * P * l;
-    if (!eig_cholqr<NA>(ctx, Q, Q)) {  // breakdown (never seen on PLD blocks): the one-kernel iteration restarts this matrix
-        if (tid == 0) state[b].done = 1;
-    }
-}
-
 // U = A V diag(lam)^-1/2 into X[:, col0 : col0 + k] on the fp64 matrix cores.  One WAVE = 16 rows of A against all of V
 // (k <= 64 components = 4 column tiles), no LDS and no barriers: the first version staged 64 x 64 tiles of A and V through
 // LDS with two workgroup barriers around 16 MFMAs per wave and ran 15x off the HBM time of A.  v_mfma_f64_16x16x4:
@@ -1973,9 +1743,6 @@ __global__ __launch_bounds__(512) void pld_eigs_orth_kernel(int P, int k, int l,
 // [col = lane & 15].  The summation index of an MFMA step is free to permute: lane group q = lane >> 4 owns columns
 // p0 + 4 q .. + 3 of A (one 32-byte load when P % 4 == 0 — the four groups cover a 128-byte line of each row) and feeds
 // component j at step j, with the matching row p0 + 4 q + j of V as the B operand (4 x 128-byte rows, from L1/L2).
-#ifndef PROJ_U4
-#define PROJ_U4 1
-#endif
 typedef double pld_d4u __attribute__((ext_vector_type(4), aligned(8)));
 template <int KT, bool VEC4>  // KT = 16-column tiles of V (k <= 16 KT); VEC4: P % 4 == 0, rows of A are 32-byte aligned
 __global__ __launch_bounds__(256) void pld_project_kernel(const double *__restrict__ A, const double *__restrict__ V,
@@ -2001,7 +1768,6 @@ __global__ __launch_bounds__(256) void pld_project_kernel(const double *__restri
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] *= f;
         } else {
-#if PROJ_U4
             // P not a multiple of four (121: rows neither 16- nor 32-byte aligned): still ONE 32-byte request per lane — four
             // 8-byte loads per lane put ~24 cache lines under every instruction and fetched each line four times through an L1
             // that 32 waves' rows do not fit.  The last group starts at P - 4 and its elements are shifted into place.
@@ -2012,12 +1778,6 @@ __global__ __launch_bounds__(256) void pld_project_kernel(const double *__restri
                 const double x = sh == 0 ? raw[j] : (sh == 1 ? raw[min(j + 1, 3)] : (sh == 2 ? raw[min(j + 2, 3)] : raw[3]));
                 v[j] = x * ((row < N && p + j < P) ? 1.0 : 0.0);
             }
-#else
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = Ar[min(p + j, P - 1)];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] *= (row < N && p + j < P) ? 1.0 : 0.0;
-#endif
         }
         return v;
     };
@@ -2632,12 +2392,7 @@ static int eig_topk(lk_handle *h, double *G, int ldg, int B, int P, int k, bool 
                     double **lam_out, hipStream_t stream, Arena &ws, const float *G32 = nullptr, double tol = -1.0) {
     if (!(tol > 0.0)) tol = h->pld_eig_tol > 0.0 ? h->pld_eig_tol : PLD_EIG_TOL;   // (lk_pld_set_eig_tolerance)
     constexpr int direct_max = PLD_DIRECT_MAX;
-    // Convergence: || C r - theta r || <= eig_tol * theta_max * sqrt(k) over the k wanted pairs (PLD_EIG_TOL / PCA_EIG_TOL above).
-#ifdef LK_PLD_DEBUG   // development builds: LK_PLD_TOL sweeps the stop (tools/pld_tol_sweep.py -> profiles/r05_pld_tol_sweep.txt)
-    const double eig_tol = getenv("LK_PLD_TOL") ? atof(getenv("LK_PLD_TOL")) : tol;
-#else
-    const double eig_tol = tol;
-#endif
+    // Convergence: || C r - theta r || <= tol * theta_max * sqrt(k) over the k wanted pairs (PLD_EIG_TOL / PCA_EIG_TOL above).
     constexpr int npow_std = 3;  // C^3 (or the degree-3 Chebyshev filter) between two Rayleigh-Ritz steps
     // mid-size product blocks: a product with the 136 x 136 C is cheap next to the l x l Jacobi and the Cholesky-QR of a
     // Rayleigh-Ritz step, and their flat spectrum keeps C^8 R well conditioned — 8 products per step need 5 steps where 3
@@ -2777,93 +2532,6 @@ static int eig_topk(lk_handle *h, double *G, int ldg, int B, int P, int k, bool 
             set_error("PLD workspace exhausted (subspace)");
             return LK_ENOMEM;
         }
-        // ---- phase-split form (see pld_eigs_*): the blocks beyond the direct solver's reach with the standard three products
-        // per step.  A fixed number of steps is queued (converged matrices drop out of each launch by their flag); the
-        // one-kernel iteration below then runs for whatever is left, skipping the converged ones.
-        EigsState *d_state = nullptr;
-#ifdef LK_PLD_DEBUG
-        if (getenv("LK_PLD_SPLIT")) h->pld_eig_split = atoi(getenv("LK_PLD_SPLIT"));  // 0: one-kernel form, 1: phase-split
-        const bool split_on = h->pld_eig_split != 0;
-#else
-        const bool split_on = h->pld_eig_split != 0;
-#endif
-        const bool split = !two_pass && !wide_sub && npow == 3 && split_on;
-        if (split) {
-            d_state = (EigsState *)ws.alloc((size_t)B * sizeof(EigsState));
-            if (!d_state) {
-                set_error("PLD workspace exhausted (state)");
-                return LK_ENOMEM;
-            }
-            const int have32 = G32 != nullptr ? 1 : 0;
-            const int kc_s = l <= 32 ? 32 : 64;                       // eig_xty's partial tiles: (512 / 64) or 16 x 256 doubles
-            const int kc_p = 128;                                     // rows per float64 stage of a product: 66 KB
-            const int kc32_p = (int)(((size_t)kc_p * PLD_QS * 8) / ((size_t)pld_qs32(l <= 32 ? 2 : 4) * 4)) / 24 * 24;  // (a multiple of 8 x eig_cq32_pass's PF)
-            const size_t lds_s = eigs_small_lds_bytes(l, 512, kc_s), lds_p = (size_t)kc_p * PLD_QS * 8 + 64;
-            constexpr int nsteps_split = 6;
-            int rc_ = 0;
-#define LK_EIGS_WANT(NA_)                                                                                              \
-    do {                                                                                                               \
-        if (!rc_) rc_ = want_lds(h, reinterpret_cast<const void *>(pld_eigs_init_kernel<NA_>), 160 * 1024);             \
-        if (!rc_) rc_ = want_lds(h, reinterpret_cast<const void *>(pld_eigs_prod_kernel<NA_>), 160 * 1024);             \
-        if (!rc_) rc_ = want_lds(h, reinterpret_cast<const void *>(pld_eigs_rr_kernel<NA_>), 160 * 1024);               \
-        if (!rc_) rc_ = want_lds(h, reinterpret_cast<const void *>(pld_eigs_orth_kernel<NA_>), 160 * 1024);             \
-    } while (0)
-            // matrices [b0_, b0_ + nb_) on stream st_: every array is indexed by matrix, so a part of the batch is an offset
-#define LK_EIGS_RUN(NA_, b0_, nb_, st_)                                                                                   \
-    do {                                                                                                               \
-        double *G_ = G + (size_t)(b0_) * ldg * ldg, *scr_ = scr + (size_t)(b0_) * 4 * P * l;                            \
-        const float *G32_ = G32 ? G32 + (size_t)(b0_) * ldg * ldg : nullptr;                                            \
-        EigsState *state_ = d_state + (b0_);                                                                           \
-        double *V_ = V + (size_t)(b0_) * P * k, *lam_ = lam + (size_t)(b0_) * k;                                        \
-        hipLaunchKernelGGL(pld_eigs_init_kernel<NA_>, dim3(nb_), dim3(512), lds_s, st_, G_, ldg, P, k, l, scr_, state_, \
-                           kc_s, mirror ? 1 : 0, have32);                                                              \
-        for (int it_ = 0; it_ < nsteps_split; ++it_) {                                                                 \
-            const int last_ = it_ + 1 == nsteps_split ? 1 : 0;                                                         \
-            hipLaunchKernelGGL(pld_eigs_prod_kernel<NA_>, dim3(nb_), dim3(512), lds_p, st_, G_, G32_, ldg, P, l, scr_,  \
-                               state_, 0, kc_p, kc32_p);                                                               \
-            hipLaunchKernelGGL(pld_eigs_rr_kernel<NA_>, dim3(nb_), dim3(512), lds_s, st_, P, k, l, scr_, state_, V_,    \
-                               lam_, kc_s, eig_tol, cheb_on, last_, have32);                                           \
-            if (last_) break;                                                                                          \
-            hipLaunchKernelGGL(pld_eigs_prod_kernel<NA_>, dim3(nb_), dim3(512), lds_p, st_, G_, G32_, ldg, P, l, scr_,  \
-                               state_, 1, kc_p, kc32_p);                                                               \
-            hipLaunchKernelGGL(pld_eigs_prod_kernel<NA_>, dim3(nb_), dim3(512), lds_p, st_, G_, G32_, ldg, P, l, scr_,  \
-                               state_, 2, kc_p, kc32_p);                                                               \
-            hipLaunchKernelGGL(pld_eigs_orth_kernel<NA_>, dim3(nb_), dim3(512), lds_s, st_, P, k, l, scr_, state_,      \
-                               kc_s);                                                                                  \
-        }                                                                                                              \
-    } while (0)
-            // (Measured and dropped: the batch in two halves on two streams, the second started one product late so that one half's
-            // serial phases meet the other half's products — profiles/r06_pld_eig_modes_ab.txt: +1 % on the PLD step over one
-            // stream; a half-batch product takes as long as a full one while a small-phase launch runs beside it.)
-            if (l <= 32)
-                LK_EIGS_WANT(2);
-            else
-                LK_EIGS_WANT(4);
-            if (rc_) return rc_;
-            if (l <= 32)
-                LK_EIGS_RUN(2, 0, B, stream);
-            else
-                LK_EIGS_RUN(4, 0, B, stream);
-#undef LK_EIGS_WANT
-#undef LK_EIGS_RUN
-#ifdef LK_PLD_DEBUG
-            if (dbg_iters) {
-                std::vector<EigsState> hs((size_t)B);
-                LK_HIP_CHECK(hipMemcpyAsync(hs.data(), d_state, (size_t)B * sizeof(EigsState), hipMemcpyDeviceToHost, stream));
-                LK_HIP_CHECK(hipStreamSynchronize(stream));
-                long long sum = 0, mx = 0, nconv = 0;
-                double rmax = 0.0;
-                for (int b2 = 0; b2 < B; ++b2) {
-                    sum += hs[b2].it;
-                    mx = std::max<long long>(mx, hs[b2].it);
-                    nconv += hs[b2].converged;
-                    rmax = std::max(rmax, hs[b2].res / std::max(hs[b2].th0, 1e-300));
-                }
-                fprintf(stderr, "[pld eig split] P=%d k=%d l=%d: Rayleigh-Ritz steps mean %.1f max %lld, %lld of %d converged in the queued "
-                                "steps, largest final relative residual %.2e\n", P, k, l, (double)sum / B, mx, nconv, B, rmax);
-            }
-#endif
-        }
         // 512-thread workgroups, two per CU (LDS 57 KB each): one matrix's serial stretches (l x l Jacobi, Cholesky on one
         // wave, the random start) overlap the other's stream through C — 97.2 -> 86.6 ms per PLD step against one
         // 1024-thread workgroup per CU
@@ -2875,10 +2543,10 @@ static int eig_topk(lk_handle *h, double *G, int ldg, int B, int P, int k, bool 
         long long *d_it = dbg_iters ? (long long *)ws.alloc((size_t)B * 64) : nullptr;
         if (l <= 32)
             hipLaunchKernelGGL(pld_topk_eig_kernel<2>, dim3(B), dim3(nt_sub), lds, stream, G, ldg, P, k, l, npow, scr, V, lam,
-                               d_it, two_pass ? 8 : 400, status, cheb_on, kc, (mirror && !split) ? 1 : 0, eig_tol, G32, d_state);
+                               d_it, two_pass ? 8 : 400, status, cheb_on, kc, mirror ? 1 : 0, tol, G32);
         else
             hipLaunchKernelGGL(pld_topk_eig_kernel<4>, dim3(B), dim3(nt_sub), lds, stream, G, ldg, P, k, l, npow, scr, V, lam,
-                               d_it, two_pass ? 8 : 400, status, cheb_on, kc, (mirror && !split) ? 1 : 0, eig_tol, G32, d_state);
+                               d_it, two_pass ? 8 : 400, status, cheb_on, kc, mirror ? 1 : 0, tol, G32);
         if (d_it) {
             std::vector<long long> hit((size_t)B * 8);
             LK_HIP_CHECK(hipMemcpyAsync(hit.data(), d_it, (size_t)B * 64, hipMemcpyDeviceToHost, stream));
@@ -2921,7 +2589,7 @@ static int eig_topk(lk_handle *h, double *G, int ldg, int B, int P, int k, bool 
         const size_t lds = two_pass ? ((size_t)l * ld + 2 * l + nt_eig + 2 * l + (l + 1) / 2 + 1) * 8 + 64
                                     : ((size_t)2 * l * ld + 2 * l + 1024 + 2 * l + (l + 1) / 2 + 1) * 8 + 64;
         hipLaunchKernelGGL(pld_topk_eig_kernel<2>, dim3(B), dim3(nt_eig), lds, stream, G, ldg, P, k, l, npow, scr, V, lam,
-                           (long long *)nullptr, 400, status, cheb_on, PLD_KC, mirror ? 1 : 0, eig_tol);
+                           (long long *)nullptr, 400, status, cheb_on, PLD_KC, mirror ? 1 : 0, tol);
     }
     *V_out = V;
     *lam_out = lam;
@@ -2934,11 +2602,8 @@ struct PcaF32Source {  // the block as float32 pixels: A = (double)(mode == 0 ? 
     const double *mean;
     int mode;
 };
-#ifndef PLD_F32_SOURCE
-#define PLD_F32_SOURCE 1
-#endif
 // (can the narrow Gram kernel and the float32 projection take this block?  P >= 4 columns, at most 9 column tiles, k <= 48)
-static bool pca_f32_ok(int P, int k) { return PLD_F32_SOURCE && P >= 4 && (P + 15) / 16 <= 9 && k <= 48; }
+static bool pca_f32_ok(int P, int k) { return P >= 4 && (P + 15) / 16 <= 9 && k <= 48; }
 static int pca_block(lk_handle *h, double *A, int B, int N, int P, int k, const int64_t *d_off, double *X, int ldx,
                      int col0, hipStream_t stream, Arena &ws, bool centred = false, bool products = false,
                      double tol = -1.0, PcaF32Source fs = PcaF32Source{nullptr, nullptr, nullptr, 0}) {
@@ -3131,7 +2796,7 @@ static int pca_products_moment(lk_handle *h, const MomentPlan &pl, int B, int N,
     // early steps' filter products stream it instead (half the bytes); optional — without workspace nothing changes
     // (+ 4 KB: the product kernels' unconditional loads of the last row may run a few columns past the last matrix)
     float *G32 = (Pc > PLD_DIRECT_MAX && (Pc & 3) == 0) ? (float *)ws.alloc((size_t)B * ldg * ldg * 4 + 4096) : nullptr;
-    if (MEXP_SYM && (Pc & 3) == 0 && Pc >= 128) {
+    if ((Pc & 3) == 0 && Pc >= 128) {
         const int T = (Pc + 63) / 64;
         hipLaunchKernelGGL(pld_moment_expand_sym_kernel, dim3(T * (T + 1) / 2, B), dim3(256), 0, stream, Mcan, (size_t)pl.ldm * pl.ldm,
                            pl.d_src, d_mean, Pc, ldg, (double)N, G, G32, T);

@@ -366,31 +366,19 @@ def test_pld_pca_block_backward_error_on_a_near_degenerate_spectrum():
 
 
 @pytest.mark.parametrize("order,comps,npix", [(3, 16, 11), (2, 24, 11), (2, 16, 15)])
-def test_phase_split_eigen_iteration_matches_the_one_kernel_form(order, comps, npix):
-    """lk_pld_set_eig_mode(1): the subspace iteration of the wide PCA blocks as one launch per phase (pld_eigs_* kernels) against
-    the default one-kernel form: corrected flux equal to 1e-9 between the two (the PCA bases may differ by a rotation inside a
-    block, the regression does not see it — SURVEY App. B.8), identical outlier masks, both within the stated 1e-6 of the oracle.
-    Shapes: the 816-column third-order block (float32 matrix cores, 16 + 16 basis columns), a 300-column second-order block with
-    24 + 16 basis columns (the four-tile basis), 15 x 15 cutouts whose 225-pixel blocks have no float32 copy of C (float64
-    products only, mirrored Gram blocks)."""
-    from lightkurve_amd import synth, _capi
+def test_wide_block_eigen_iteration_matches_the_oracle(order, comps, npix):
+    """The subspace iteration of the wide PCA blocks (pld_topk_eig_kernel): identical outlier masks and corrected flux within the
+    stated 1e-6 of the oracle.  Shapes: the 816-column third-order block (float32 matrix cores, 16 + 16 basis columns), a
+    300-column second-order block with 24 + 16 basis columns (the four-tile basis), 15 x 15 cutouts whose 225-pixel blocks have
+    no float32 copy of C (float64 products only, mirrored Gram blocks)."""
+    from lightkurve_amd import synth
     cubes = []
     for i in range(3):
         t, flux, err, truth = synth.pld_cutout(4, 40 + i, n=700, npix=npix)
         cubes.append(PixelCube(t, flux, err, mission="K2"))
-    h = _capi.Handle.get(0)
-    out = {}
-    for mode in (0, 1):
-        h.pld_set_eig_mode(mode)
-        try:
-            out[mode] = pld_correct_batch(cubes, pld_order=order, pca_components=comps)
-        finally:
-            h.pld_set_eig_mode(0)
+    corr, masks = pld_correct_batch(cubes, pld_order=order, pca_components=comps)
     allm = np.ones((npix, npix), bool)
     for i, c in enumerate(cubes):
-        assert np.array_equal(out[0][1][i], out[1][1][i]), i
-        med = np.median(out[0][0][i])
-        assert np.max(np.abs(out[0][0][i] - out[1][0][i])) / med < 1e-9, i
         r = O.pld_correct(c.time, c.flux, c.flux_err, allm, allm, allm, pld_order=order, pca_components=comps, spline_degree=5)
-        assert np.array_equal(out[1][1][i], r["outlier_mask"]), i
-        assert np.max(np.abs(out[1][0][i] - r["corrected"])) / np.median(r["corrected"]) < 1e-6, i
+        assert np.array_equal(masks[i], r["outlier_mask"]), i
+        assert np.max(np.abs(corr[i] - r["corrected"])) / np.median(r["corrected"]) < 1e-6, i
