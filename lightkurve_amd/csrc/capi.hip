@@ -1,6 +1,7 @@
 // capi.hip — extern "C" boundary of liblkhip.so (declared in include/lkhip.h).
-// Host-pointer entry points stage caller buffers into HBM, call the device-pointer entry points and copy
-// the results back; the device-pointer entry points only validate, carve scratch and enqueue kernels.
+// Host-pointer entry points stage caller buffers into HBM through StagedCall (h->staging), run the same launchers as the
+// device-pointer entry points on the null stream and copy the results back; the device-pointer entry points only
+// validate, carve scratch and enqueue kernels.
 #include "lk_common.hpp"
 
 namespace lk {
@@ -72,6 +73,71 @@ void Arena::release() {
     base = nullptr;
     cap = used = 0;
 }
+
+// The device mirrors of one host-pointer call, in h->staging.  The call declares its buffers in carving order: in() is
+// copied to the device by stage(), out() back to the host by finish(), scratch() is device-only; a null host pointer
+// declares nothing and leaves its device pointer null.  stage() resets the arena, reserves exactly the declared buffers
+// at Arena::alloc's 256-byte alignment, sets the device pointers and copies the inputs in.  The copies are synchronous
+// and the launch between stage() and finish() goes on the null stream, so finish() reads what the kernels wrote.
+class StagedCall {
+  public:
+    explicit StagedCall(lk_handle *h) : h_(h) {}
+    // n elements copied in, n + pad on the device (the pad is left unwritten)
+    template <class T> StagedCall &in(const T *&dev, const T *host, size_t n, size_t pad = 0) {
+        return host ? add(dev, host, nullptr, n + pad, n, nullptr) : none(dev);
+    }
+    // n elements on the device, copied back: all of them, or the first *n_back (a count the launch reports)
+    template <class T> StagedCall &out(T *&dev, T *host, size_t n, const int64_t *n_back = nullptr) {
+        return host ? add(dev, nullptr, host, n, n, n_back) : none(dev);
+    }
+    template <class T> StagedCall &scratch(T *&dev, size_t n) { return add(dev, nullptr, nullptr, n, 0, nullptr); }
+
+    int stage() {
+        size_t total = 0;
+        for (const Buf &b : bufs_) total += (b.elem * b.n_dev + 255) & ~size_t(255);
+        h_->staging.reset();
+        // at least one byte: a zero-length buffer still gets a non-null pointer (launchers reject NULL before sizes)
+        int rc = h_->staging.reserve(std::max<size_t>(total, 1));
+        if (rc) return rc;
+        for (Buf &b : bufs_) {
+            b.dev = h_->staging.alloc(b.elem * b.n_dev);
+            b.set(b.slot, b.dev);
+            if (b.src) LK_HIP_CHECK(hipMemcpy(b.dev, b.src, b.elem * b.n_copy, hipMemcpyHostToDevice));
+        }
+        return LK_OK;
+    }
+    int finish() {
+        for (const Buf &b : bufs_)
+            if (b.dst)
+                LK_HIP_CHECK(hipMemcpy(b.dst, b.dev, b.elem * (b.n_back ? (size_t)*b.n_back : b.n_copy),
+                                       hipMemcpyDeviceToHost));
+        return LK_OK;
+    }
+
+  private:
+    struct Buf {
+        void *slot;                    // the caller's device-pointer variable, set through set()
+        void (*set)(void *slot, void *dev);
+        const void *src;               // in: host source
+        void *dst;                     // out: host destination
+        size_t elem, n_dev, n_copy;
+        const int64_t *n_back;
+        void *dev;
+    };
+    template <class T> static void set_ptr(void *slot, void *dev) { *static_cast<T **>(slot) = static_cast<T *>(dev); }
+    template <class T> StagedCall &none(T *&dev) {
+        dev = nullptr;
+        return *this;
+    }
+    template <class T>
+    StagedCall &add(T *&dev, const void *src, void *dst, size_t n_dev, size_t n_copy, const int64_t *n_back) {
+        dev = nullptr;
+        bufs_.push_back({&dev, set_ptr<T>, src, dst, sizeof(T), n_dev, n_copy, n_back, nullptr});
+        return *this;
+    }
+    lk_handle *h_;
+    std::vector<Buf> bufs_;
+};
 
 }  // namespace lk
 
@@ -196,26 +262,15 @@ int lk_ls_chi2_batch(lk_handle *h, int B, const int64_t *n_off, const double *t,
     LK_REQUIRE(t && y && power, "t, y, power must be non-NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
     const size_t ntot = (size_t)n_off[B];
-    const size_t nb = ntot * sizeof(double), fb = freq ? (size_t)M * sizeof(double) : 0;
-    const size_t pb = (size_t)B * (size_t)M * sizeof(double), sb = scale ? (size_t)B * sizeof(double) : 0;
-    h->staging.reset();
-    int rc = h->staging.reserve(3 * (nb + 256) + fb + pb + sb + 4096);
+    const double *dt, *dyv, *ddy, *dfreq, *dscale;
+    double *dpow;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).in(dyv, y, ntot).in(ddy, dy, ntot).in(dfreq, freq, (size_t)M).in(dscale, scale, (size_t)B)
+                 .out(dpow, power, (size_t)B * (size_t)M).stage();
     if (rc) return rc;
-    double *dt = (double *)h->staging.alloc(nb), *dyv = (double *)h->staging.alloc(nb);
-    double *ddy = dy ? (double *)h->staging.alloc(nb) : nullptr;
-    double *dfreq = freq ? (double *)h->staging.alloc(fb) : nullptr;
-    double *dscale = scale ? (double *)h->staging.alloc(sb) : nullptr;
-    double *dpow = (double *)h->staging.alloc(pb);
-    LK_HIP_CHECK(hipMemcpy(dt, t, nb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dyv, y, nb, hipMemcpyHostToDevice));
-    if (dy) LK_HIP_CHECK(hipMemcpy(ddy, dy, nb, hipMemcpyHostToDevice));
-    if (freq) LK_HIP_CHECK(hipMemcpy(dfreq, freq, fb, hipMemcpyHostToDevice));
-    if (scale) LK_HIP_CHECK(hipMemcpy(dscale, scale, sb, hipMemcpyHostToDevice));
     rc = lk::ls_chi2_launch(h, B, n_off, dt, dyv, ddy, dfreq, f0, df, M, nterms, fit_mean, center_data, normalization,
                             dscale, dpow, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(power, dpow, pb, hipMemcpyDeviceToHost));  // null-stream copy orders after the kernels
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 int lk_ls_power_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, const double *y, const double *dy,
@@ -245,29 +300,21 @@ int lk_fold_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, co
     LK_REQUIRE(t && phase && order, "NULL buffer");
     LK_REQUIRE(ncols >= 0 && ncols <= 16 && (ncols == 0 || (cols_in && cols_out)), "bad column list (at most 16 columns)");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t ntot = (size_t)n_off[B], nb = ntot * 8;
-    h->staging.reset();
-    int rc = h->staging.reserve((size_t)(3 + 2 * ncols) * (nb + 256) + 4096);
-    if (rc) return rc;
-    double *dt = (double *)h->staging.alloc(nb), *dph = (double *)h->staging.alloc(nb);
-    int64_t *dord = (int64_t *)h->staging.alloc(nb);
-    const double *din[16];
-    double *dout[16];
-    LK_HIP_CHECK(hipMemcpy(dt, t, nb, hipMemcpyHostToDevice));
+    const size_t ntot = (size_t)n_off[B];
+    const double *dt, *din[16];
+    double *dph, *dout[16];
+    int64_t *dord;
+    lk::StagedCall io(h);
+    io.in(dt, t, ntot).out(dph, phase, ntot).out(dord, order, ntot);
     for (int c = 0; c < ncols; ++c) {
         LK_REQUIRE(cols_in[c] && cols_out[c], "column %d is NULL", c);
-        double *a = (double *)h->staging.alloc(nb);
-        dout[c] = (double *)h->staging.alloc(nb);
-        LK_HIP_CHECK(hipMemcpy(a, cols_in[c], nb, hipMemcpyHostToDevice));
-        din[c] = a;
+        io.in(din[c], cols_in[c], ntot).out(dout[c], cols_out[c], ntot);
     }
+    int rc = io.stage();
+    if (rc) return rc;
     rc = lk::fold_launch(h, B, n_off, dt, period, epoch_time, epoch_phase, wrap_phase, normalize_phase, ncols, din, dout,
                          dph, dord, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(phase, dph, nb, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(order, dord, nb, hipMemcpyDeviceToHost));
-    for (int c = 0; c < ncols; ++c) LK_HIP_CHECK(hipMemcpy(cols_out[c], dout[c], nb, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ Periodogram.smooth
@@ -287,40 +334,38 @@ int lk_pg_boxsmooth_batch_dev(lk_handle *h, int B, int64_t M, const double *powe
     return lk::pg_boxsmooth_launch(h, B, M, power, taps, nk, out, static_cast<hipStream_t>(stream));
 }
 
-// host-pointer flavours: stage power in, run, copy the smoothed rows back
-extern "C++" {
-template <class Launch>
-static int pg_host_stage(lk_handle *h, int B, int64_t M, const double *power, double *out, Launch launch) {
+int lk_pg_logmedian_batch(lk_handle *h, int B, int64_t M, const double *power, int K, const int32_t *win_lo,
+                          const int32_t *win_hi, const int32_t *klo, const int32_t *khi, double corr, double *out) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_REQUIRE(B >= 0 && M >= 1, "need B >= 0 and M >= 1");
     if (B == 0) return LK_OK;
     LK_REQUIRE(power && out, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t pb = (size_t)B * (size_t)M * sizeof(double);
-    h->staging.reset();
-    int rc = h->staging.reserve(2 * (pb + 256) + 4096);
+    const size_t n = (size_t)B * (size_t)M;
+    const double *dp;
+    double *dout;
+    lk::StagedCall io(h);
+    int rc = io.in(dp, power, n).out(dout, out, n).stage();
     if (rc) return rc;
-    double *dp = (double *)h->staging.alloc(pb), *dout = (double *)h->staging.alloc(pb);
-    LK_HIP_CHECK(hipMemcpy(dp, power, pb, hipMemcpyHostToDevice));
-    rc = launch(dp, dout);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(out, dout, pb, hipMemcpyDeviceToHost));
-    return LK_OK;
-}
-}  // extern "C++"
-
-int lk_pg_logmedian_batch(lk_handle *h, int B, int64_t M, const double *power, int K, const int32_t *win_lo,
-                          const int32_t *win_hi, const int32_t *klo, const int32_t *khi, double corr, double *out) {
-    return pg_host_stage(h, B, M, power, out, [&](const double *dp, double *dout) {
-        return lk::pg_logmedian_launch(h, B, M, dp, K, win_lo, win_hi, klo, khi, corr, dout, nullptr);
-    });
+    rc = lk::pg_logmedian_launch(h, B, M, dp, K, win_lo, win_hi, klo, khi, corr, dout, nullptr);
+    return rc ? rc : io.finish();
 }
 
 int lk_pg_boxsmooth_batch(lk_handle *h, int B, int64_t M, const double *power, const double *taps, int nk,
                           double *out) {
-    return pg_host_stage(h, B, M, power, out, [&](const double *dp, double *dout) {
-        return lk::pg_boxsmooth_launch(h, B, M, dp, taps, nk, dout, nullptr);
-    });
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && M >= 1, "need B >= 0 and M >= 1");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(power && out, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t n = (size_t)B * (size_t)M;
+    const double *dp;
+    double *dout;
+    lk::StagedCall io(h);
+    int rc = io.in(dp, power, n).out(dout, out, n).stage();
+    if (rc) return rc;
+    rc = lk::pg_boxsmooth_launch(h, B, M, dp, taps, nk, dout, nullptr);
+    return rc ? rc : io.finish();
 }
 
 int lk_pg_acf2d_batch_dev(lk_handle *h, int B, int64_t M, const double *power, int n_win, const int32_t *win_start,
@@ -337,17 +382,14 @@ int lk_pg_acf2d_batch(lk_handle *h, int B, int64_t M, const double *power, int n
     if (B == 0 || n_win == 0) return LK_OK;
     LK_REQUIRE(power && acf2d && metric, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t pb = (size_t)B * (size_t)M * 8, ab = (size_t)B * n_win * (size_t)W * 8, mb = (size_t)B * n_win * 8;
-    h->staging.reset();
-    int rc = h->staging.reserve(pb + ab + mb + 3 * 256 + 4096);
+    const size_t nm = (size_t)B * n_win;
+    const double *dp;
+    double *da, *dm;
+    lk::StagedCall io(h);
+    int rc = io.in(dp, power, (size_t)B * (size_t)M).out(da, acf2d, nm * (size_t)W).out(dm, metric, nm).stage();
     if (rc) return rc;
-    double *dp = (double *)h->staging.alloc(pb), *da = (double *)h->staging.alloc(ab), *dm = (double *)h->staging.alloc(mb);
-    LK_HIP_CHECK(hipMemcpy(dp, power, pb, hipMemcpyHostToDevice));
     rc = lk::pg_acf2d_launch(h, B, M, dp, n_win, win_start, W, da, dm, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(acf2d, da, ab, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(metric, dm, mb, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ LS 'fast'
@@ -379,24 +421,16 @@ int lk_ls_fastchi2_batch(lk_handle *h, int B, const int64_t *n_off, const double
     if (B == 0 || M == 0) return LK_OK;
     LK_REQUIRE(t && y && power, "t, y, power must be non-NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t ntot = (size_t)n_off[B], nb = ntot * 8;
-    const size_t pb = (size_t)B * (size_t)M * 8, sb = scale ? (size_t)B * 8 : 0;
-    h->staging.reset();
-    int rc = h->staging.reserve(3 * (nb + 256) + pb + sb + 4096);
+    const size_t ntot = (size_t)n_off[B];
+    const double *dt, *dyv, *ddy, *dscale;
+    double *dpow;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).in(dyv, y, ntot).in(ddy, dy, ntot).in(dscale, scale, (size_t)B)
+                 .out(dpow, power, (size_t)B * (size_t)M).stage();
     if (rc) return rc;
-    double *dt = (double *)h->staging.alloc(nb), *dyv = (double *)h->staging.alloc(nb);
-    double *ddy = dy ? (double *)h->staging.alloc(nb) : nullptr;
-    double *dscale = scale ? (double *)h->staging.alloc(sb) : nullptr;
-    double *dpow = (double *)h->staging.alloc(pb);
-    LK_HIP_CHECK(hipMemcpy(dt, t, nb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dyv, y, nb, hipMemcpyHostToDevice));
-    if (dy) LK_HIP_CHECK(hipMemcpy(ddy, dy, nb, hipMemcpyHostToDevice));
-    if (scale) LK_HIP_CHECK(hipMemcpy(dscale, scale, sb, hipMemcpyHostToDevice));
     rc = lk::lsfastchi2_launch(h, B, n_off, dt, dyv, ddy, f0, df, M, nterms, fit_mean, center_data, normalization, dscale,
                                oversampling, dpow, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(power, dpow, pb, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 int lk_ls_fast_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, const double *y, const double *dy,
@@ -421,18 +455,14 @@ int lk_argmax_batch(lk_handle *h, int B, int64_t M, const double *x, double *max
     if (B == 0) return LK_OK;
     LK_REQUIRE(x && max_out && argmax_out, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t xb = (size_t)B * (size_t)M * sizeof(double);
-    h->staging.reset();
-    int rc = h->staging.reserve(xb + (size_t)B * 16 + 4096);
+    const double *dx;
+    double *dm;
+    int64_t *da;
+    lk::StagedCall io(h);
+    int rc = io.in(dx, x, (size_t)B * (size_t)M).out(dm, max_out, (size_t)B).out(da, argmax_out, (size_t)B).stage();
     if (rc) return rc;
-    double *dx = (double *)h->staging.alloc(xb), *dm = (double *)h->staging.alloc((size_t)B * 8);
-    int64_t *da = (int64_t *)h->staging.alloc((size_t)B * 8);
-    LK_HIP_CHECK(hipMemcpy(dx, x, xb, hipMemcpyHostToDevice));
     rc = lk::argmax_launch(h, B, M, dx, dm, da, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(max_out, dm, (size_t)B * 8, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(argmax_out, da, (size_t)B * 8, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ BLS
@@ -455,23 +485,16 @@ int lk_bls_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, con
     if (B == 0 || nP == 0) return LK_OK;
     LK_REQUIRE(t && y && ivar && period && duration && out7, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t ntot = (size_t)n_off[B], nb = ntot * sizeof(double);
-    const size_t pb = (size_t)nP * sizeof(double), ob = 7 * (size_t)B * (size_t)nP * sizeof(double);
-    h->staging.reset();
-    int rc = h->staging.reserve(3 * (nb + 256) + pb + ob + 4096);
+    const size_t ntot = (size_t)n_off[B];
+    const double *dt, *dyv, *div, *dper;
+    double *dout;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).in(dyv, y, ntot).in(div, ivar, ntot).in(dper, period, (size_t)nP)
+                 .out(dout, out7, 7 * (size_t)B * (size_t)nP).stage();
     if (rc) return rc;
-    double *dt = (double *)h->staging.alloc(nb), *dyv = (double *)h->staging.alloc(nb);
-    double *div = (double *)h->staging.alloc(nb), *dper = (double *)h->staging.alloc(pb);
-    double *dout = (double *)h->staging.alloc(ob);
-    LK_HIP_CHECK(hipMemcpy(dt, t, nb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dyv, y, nb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(div, ivar, nb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dper, period, pb, hipMemcpyHostToDevice));
     rc = lk::bls_launch(h, B, n_off, dt, dyv, div, period, dper, nP, duration, nD, oversample, use_likelihood, dout,
                         nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(out7, dout, ob, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 int lk_bls_max_period(const double *duration, int nD, int oversample, double *max_period) {
@@ -515,35 +538,19 @@ int lk_regress_cov_batch(lk_handle *h, int B, const int64_t *n_off, int K, const
     LK_REQUIRE(K >= 1, "K must be >= 1");
     LK_REQUIRE(X && y && w && model && outlier, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t ntot = (size_t)n_off[B];
-    const size_t xb = ntot * (size_t)K * 8, nb = ntot * 8, kb = (size_t)B * K * 8;
-    h->staging.reset();
-    const size_t cb = w_cov ? (size_t)B * K * K * 8 : 0;
-    int rc = h->staging.reserve(xb + 3 * (nb + 256) + 2 * (ntot + 256) + 3 * (kb + 256) + cb + 4096);
+    const size_t ntot = (size_t)n_off[B], nk = (size_t)B * K;
+    const double *dX, *dy, *derr, *dmu, *dsg;
+    const uint8_t *dcm;
+    double *dmodel, *dw, *dcov;
+    uint8_t *dout;
+    lk::StagedCall io(h);
+    int rc = io.in(dX, X, ntot * (size_t)K).in(dy, y, ntot).in(derr, err, ntot).out(dmodel, model, ntot)
+                 .in(dcm, cadence_mask, ntot).out(dout, outlier, ntot).in(dmu, prior_mu, nk).in(dsg, prior_sigma, nk)
+                 .out(dw, w, nk).out(dcov, w_cov, nk * K).stage();
     if (rc) return rc;
-    double *dX = (double *)h->staging.alloc(xb), *dy = (double *)h->staging.alloc(nb);
-    double *derr = err ? (double *)h->staging.alloc(nb) : nullptr;
-    double *dmodel = (double *)h->staging.alloc(nb);
-    uint8_t *dcm = cadence_mask ? (uint8_t *)h->staging.alloc(ntot) : nullptr;
-    uint8_t *dout = (uint8_t *)h->staging.alloc(ntot);
-    double *dmu = prior_mu ? (double *)h->staging.alloc(kb) : nullptr;
-    double *dsg = prior_sigma ? (double *)h->staging.alloc(kb) : nullptr;
-    double *dw = (double *)h->staging.alloc(kb);
-    double *dcov = w_cov ? (double *)h->staging.alloc(cb) : nullptr;
-    LK_HIP_CHECK(hipMemcpy(dX, X, xb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dy, y, nb, hipMemcpyHostToDevice));
-    if (err) LK_HIP_CHECK(hipMemcpy(derr, err, nb, hipMemcpyHostToDevice));
-    if (cadence_mask) LK_HIP_CHECK(hipMemcpy(dcm, cadence_mask, ntot, hipMemcpyHostToDevice));
-    if (prior_mu) LK_HIP_CHECK(hipMemcpy(dmu, prior_mu, kb, hipMemcpyHostToDevice));
-    if (prior_sigma) LK_HIP_CHECK(hipMemcpy(dsg, prior_sigma, kb, hipMemcpyHostToDevice));
     rc = lk::regress_launch(h, B, n_off, K, dX, dy, derr, dcm, dmu, dsg, clip_sigma, niters, dw, dmodel, dout,
                             nullptr, dcov);
-    if (rc) return rc;
-    if (w_cov) LK_HIP_CHECK(hipMemcpy(w_cov, dcov, cb, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(w, dw, kb, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(model, dmodel, nb, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(outlier, dout, ntot, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ flatten
@@ -568,22 +575,17 @@ int lk_savgol_trend_batch(lk_handle *h, int B, const int64_t *n_off, const doubl
     if (B == 0) return LK_OK;
     LK_REQUIRE(t && flux && trend, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t ntot = (size_t)n_off[B], nb = ntot * 8;
-    h->staging.reset();
-    int rc = h->staging.reserve(3 * (nb + 256) + 2 * (ntot + 256) + 4096);
+    const size_t ntot = (size_t)n_off[B];
+    const double *dt, *df;
+    const uint8_t *dm;
+    double *dtr;
+    uint8_t *dfm;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).in(df, flux, ntot).out(dtr, trend, ntot).in(dm, mask, ntot).out(dfm, fit_mask, ntot)
+                 .stage();
     if (rc) return rc;
-    double *dt = (double *)h->staging.alloc(nb), *df = (double *)h->staging.alloc(nb);
-    double *dtr = (double *)h->staging.alloc(nb);
-    uint8_t *dm = mask ? (uint8_t *)h->staging.alloc(ntot) : nullptr;
-    uint8_t *dfm = fit_mask ? (uint8_t *)h->staging.alloc(ntot) : nullptr;
-    LK_HIP_CHECK(hipMemcpy(dt, t, nb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(df, flux, nb, hipMemcpyHostToDevice));
-    if (mask) LK_HIP_CHECK(hipMemcpy(dm, mask, ntot, hipMemcpyHostToDevice));
     rc = lk::flatten_launch(h, B, n_off, dt, df, dm, window, polyorder, break_tol, niters, sigma, dtr, dfm, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(trend, dtr, nb, hipMemcpyDeviceToHost));
-    if (fit_mask) LK_HIP_CHECK(hipMemcpy(fit_mask, dfm, ntot, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ PLD design matrix
@@ -611,26 +613,16 @@ int lk_pld_design_batch(lk_handle *h, int B, int N, int P, int Pb, const float *
     LK_REQUIRE(bkg_pix && lc_flux && time && knots && X && prior_sigma, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
     const size_t bn = (size_t)B * N;
-    const size_t pb = bn * P * 4, bb = bn * Pb * 4, lb = bn * 4, tb = bn * 8, kb = (size_t)B * (n_inner + 2) * 8;
-    const size_t xb = bn * K * 8, sb = (size_t)B * K * 8;
-    h->staging.reset();
-    int rc = h->staging.reserve(pb + bb + lb + tb + kb + xb + sb + 8 * 256 + 4096);
+    const float *dp, *db, *dl;
+    const double *dt, *dk;
+    double *dX, *ds;
+    lk::StagedCall io(h);
+    int rc = io.in(dp, P > 0 ? pld_pix : nullptr, bn * P).in(db, bkg_pix, bn * Pb).in(dl, lc_flux, bn).in(dt, time, bn)
+                 .in(dk, knots, (size_t)B * (n_inner + 2)).out(dX, X, bn * K).out(ds, prior_sigma, (size_t)B * K).stage();
     if (rc) return rc;
-    float *dp = (P > 0 && pld_pix) ? (float *)h->staging.alloc(pb) : nullptr;
-    float *db = (float *)h->staging.alloc(bb), *dl = (float *)h->staging.alloc(lb);
-    double *dt = (double *)h->staging.alloc(tb), *dk = (double *)h->staging.alloc(kb);
-    double *dX = (double *)h->staging.alloc(xb), *ds = (double *)h->staging.alloc(sb);
-    if (dp) LK_HIP_CHECK(hipMemcpy(dp, pld_pix, pb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(db, bkg_pix, bb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dl, lc_flux, lb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dt, time, tb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dk, knots, kb, hipMemcpyHostToDevice));
     rc = lk::pld_design_launch(h, B, N, dp ? P : 0, Pb, dp, db, dl, dt, dk, n_inner, pld_order, pca_components, n_knots,
                                spline_degree, normalize_bkg, K, dX, ds, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(X, dX, xb, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(prior_sigma, ds, sb, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 // PLDCorrector.correct for B same-shaped cutouts, host pointers in and out: design matrices, regression + clip loop and the
@@ -648,30 +640,20 @@ int lk_pld_correct_batch(lk_handle *h, int B, int N, int P, int Pb, const float 
     const size_t bn = (size_t)B * N;
     const bool has_pld = P > 0 && pld_pix != nullptr;
     const bool shared = has_pld && pld_pix == bkg_pix && P == Pb;  // one aperture for both blocks: one upload
-    const size_t pb = bn * P * 4, bb = bn * Pb * 4, lb = bn * 4, nb = bn * 8, kb = (size_t)B * (n_inner + 2) * 8;
-    const size_t xb = bn * K * 8, sb = (size_t)B * K * 8;
-    h->staging.reset();
-    int rc = h->staging.reserve(pb + bb + lb + kb + xb + 3 * (sb + 256) + 5 * (nb + 256) + 2 * (bn + 256) + 8 * 256 + 4096);
+    const size_t nk = (size_t)B * K;
+    const float *dp, *db, *dl;
+    const double *dt, *dk, *dy, *derr;
+    const uint8_t *dcm;
+    double *dX, *ds, *dmu, *dw, *dmodel, *dsp;
+    uint8_t *dout;
+    lk::StagedCall io(h);
+    int rc = io.in(dp, has_pld && !shared ? pld_pix : nullptr, bn * P).in(db, bkg_pix, bn * Pb).in(dl, lc_flux, bn)
+                 .in(dt, time, bn).in(dk, knots, (size_t)B * (n_inner + 2)).scratch(dX, bn * K).scratch(ds, nk)
+                 .scratch(dmu, nk).out(dw, w, nk).in(dy, y, bn).in(derr, err, bn).out(dmodel, model, bn)
+                 .out(dsp, spline_part, bn).in(dcm, cadence_mask, bn).out(dout, outlier, bn).stage();
     if (rc) return rc;
-    float *dp = (has_pld && !shared) ? (float *)h->staging.alloc(pb) : nullptr;
-    float *db = (float *)h->staging.alloc(bb), *dl = (float *)h->staging.alloc(lb);
-    double *dt = (double *)h->staging.alloc(nb), *dk = (double *)h->staging.alloc(kb);
-    double *dX = (double *)h->staging.alloc(xb), *ds = (double *)h->staging.alloc(sb), *dmu = (double *)h->staging.alloc(sb);
-    double *dw = (double *)h->staging.alloc(sb), *dy = (double *)h->staging.alloc(nb);
-    double *derr = err ? (double *)h->staging.alloc(nb) : nullptr;
-    double *dmodel = (double *)h->staging.alloc(nb), *dsp = spline_part ? (double *)h->staging.alloc(nb) : nullptr;
-    uint8_t *dcm = cadence_mask ? (uint8_t *)h->staging.alloc(bn) : nullptr, *dout = (uint8_t *)h->staging.alloc(bn);
-    LK_REQUIRE(dout != nullptr, "staging arena exhausted");
-    if (dp) LK_HIP_CHECK(hipMemcpy(dp, pld_pix, pb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(db, bkg_pix, bb, hipMemcpyHostToDevice));
     if (shared) dp = db;
-    LK_HIP_CHECK(hipMemcpy(dl, lc_flux, lb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dt, time, nb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dk, knots, kb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dy, y, nb, hipMemcpyHostToDevice));
-    if (err) LK_HIP_CHECK(hipMemcpy(derr, err, nb, hipMemcpyHostToDevice));
-    if (cadence_mask) LK_HIP_CHECK(hipMemcpy(dcm, cadence_mask, bn, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemsetAsync(dmu, 0, sb, nullptr));   // prior_mu = 0 for every PLD column (pldcorrector.py:240-287)
+    LK_HIP_CHECK(hipMemsetAsync(dmu, 0, nk * 8, nullptr));   // prior_mu = 0 for every PLD column (pldcorrector.py:240-287)
     rc = lk::pld_design_launch(h, B, N, dp ? P : 0, Pb, dp, db, dl, dt, dk, n_inner, pld_order, pca_components, n_knots,
                                spline_degree, normalize_bkg, K, dX, ds, nullptr);
     if (rc) return rc;
@@ -683,11 +665,7 @@ int lk_pld_correct_batch(lk_handle *h, int B, int N, int P, int Pb, const float 
         rc = lk::model_part_launch(h, B, N, K, K - (n_knots + 1), K, dX, dw, dsp, nullptr);
         if (rc) return rc;
     }
-    LK_HIP_CHECK(hipMemcpy(w, dw, sb, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(model, dmodel, nb, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(outlier, dout, bn, hipMemcpyDeviceToHost));
-    if (dsp) LK_HIP_CHECK(hipMemcpy(spline_part, dsp, nb, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return io.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ design-matrix operations
@@ -701,16 +679,13 @@ int lk_pca_batch(lk_handle *h, int B, int N, int P, int k, const double *A, doub
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_REQUIRE(B >= 1 && N >= 1 && P >= 1 && k >= 1 && A && U, "bad arguments");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t ab = (size_t)B * N * P * 8, ub = (size_t)B * N * k * 8;
-    h->staging.reset();
-    int rc = h->staging.reserve(ab + ub + 1024);
+    const double *dA;
+    double *dU;
+    lk::StagedCall io(h);
+    int rc = io.in(dA, A, (size_t)B * N * P).out(dU, U, (size_t)B * N * k).stage();
     if (rc) return rc;
-    double *dA = (double *)h->staging.alloc(ab), *dU = (double *)h->staging.alloc(ub);
-    LK_HIP_CHECK(hipMemcpy(dA, A, ab, hipMemcpyHostToDevice));
     rc = lk::dm_pca_launch(h, B, N, P, k, dA, dU, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(U, dU, ub, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 int lk_spline_basis_batch_dev(lk_handle *h, int B, int N, const double *x, const double *knots, int n_inner, int degree,
@@ -725,17 +700,14 @@ int lk_spline_basis_batch(lk_handle *h, int B, int N, const double *x, const dou
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_REQUIRE(B >= 1 && N >= 1 && n_inner >= 0 && degree >= 0 && x && knots && out, "bad arguments");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t xb = (size_t)B * N * 8, kb = (size_t)B * (n_inner + 2) * 8, ob = (size_t)B * N * (n_inner + degree + 1) * 8;
-    h->staging.reset();
-    int rc = h->staging.reserve(xb + kb + ob + 1024);
+    const double *dx, *dk;
+    double *dout;
+    lk::StagedCall io(h);
+    int rc = io.in(dx, x, (size_t)B * N).in(dk, knots, (size_t)B * (n_inner + 2))
+                 .out(dout, out, (size_t)B * N * (n_inner + degree + 1)).stage();
     if (rc) return rc;
-    double *dx = (double *)h->staging.alloc(xb), *dk = (double *)h->staging.alloc(kb), *dout = (double *)h->staging.alloc(ob);
-    LK_HIP_CHECK(hipMemcpy(dx, x, xb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(dk, knots, kb, hipMemcpyHostToDevice));
     rc = lk::dm_spline_launch(h, B, N, dx, dk, n_inner, degree, dout, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 int lk_standardize_batch_dev(lk_handle *h, int B, int N, int P, const double *A, double *out, void *stream) {
@@ -748,16 +720,14 @@ int lk_standardize_batch(lk_handle *h, int B, int N, int P, const double *A, dou
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_REQUIRE(B >= 1 && N >= 1 && P >= 1 && A && out, "bad arguments");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t ab = (size_t)B * N * P * 8;
-    h->staging.reset();
-    int rc = h->staging.reserve(2 * ab + 1024);
+    const size_t n = (size_t)B * N * P;
+    const double *dA;
+    double *dO;
+    lk::StagedCall io(h);
+    int rc = io.in(dA, A, n).out(dO, out, n).stage();
     if (rc) return rc;
-    double *dA = (double *)h->staging.alloc(ab), *dO = (double *)h->staging.alloc(ab);
-    LK_HIP_CHECK(hipMemcpy(dA, A, ab, hipMemcpyHostToDevice));
     rc = lk::dm_standardize_launch(h, B, N, P, dA, dO, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(out, dO, ab, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ pinned host memory
@@ -965,16 +935,13 @@ int lk_sigma_clip_batch(lk_handle *h, int B, const int64_t *n_off, const double 
     LK_REQUIRE(y && outlier, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
     const size_t ntot = (size_t)n_off[B];
-    h->staging.reset();
-    int rc = h->staging.reserve(ntot * 9 + 2 * 256 + 4096);
+    const double *dy;
+    uint8_t *dm;
+    lk::StagedCall io(h);
+    int rc = io.in(dy, y, ntot).out(dm, outlier, ntot).stage();
     if (rc) return rc;
-    double *dy = (double *)h->staging.alloc(ntot * 8);
-    uint8_t *dm = (uint8_t *)h->staging.alloc(ntot);
-    LK_HIP_CHECK(hipMemcpy(dy, y, ntot * 8, hipMemcpyHostToDevice));
     rc = lk::sigma_clip_launch(h, B, n_off, dy, sigma, maxiters, dm, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(outlier, dm, ntot, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ batch ingest (N4)
@@ -998,26 +965,16 @@ int lk_ingest_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, 
     }
     LK_REQUIRE(t && flux && t_out && flux_out, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t ntot = (size_t)n_off[B], nb = ntot * 8;
-    h->staging.reset();
-    int rc = h->staging.reserve(6 * (nb + 256) + (size_t)B * 8 + 4096);
+    const size_t ntot = (size_t)n_off[B];
+    const int64_t *kept = &new_off[B];  // set by the launch
+    const double *dt, *df, *de;
+    double *dto, *dfo, *deo, *dmed;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).in(df, flux, ntot).in(de, flux_err, ntot).out(dto, t_out, ntot, kept)
+                 .out(dfo, flux_out, ntot, kept).out(deo, flux_err_out, ntot, kept).out(dmed, median_out, (size_t)B).stage();
     if (rc) return rc;
-    double *dt = (double *)h->staging.alloc(nb), *df = (double *)h->staging.alloc(nb);
-    double *de = flux_err ? (double *)h->staging.alloc(nb) : nullptr;
-    double *dto = (double *)h->staging.alloc(nb), *dfo = (double *)h->staging.alloc(nb);
-    double *deo = flux_err_out ? (double *)h->staging.alloc(nb) : nullptr;
-    double *dmed = median_out ? (double *)h->staging.alloc((size_t)B * 8) : nullptr;
-    LK_HIP_CHECK(hipMemcpy(dt, t, nb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(df, flux, nb, hipMemcpyHostToDevice));
-    if (flux_err) LK_HIP_CHECK(hipMemcpy(de, flux_err, nb, hipMemcpyHostToDevice));
     rc = lk::ingest_launch(h, B, n_off, dt, df, de, normalize, dto, dfo, deo, new_off, dmed, nullptr);
-    if (rc) return rc;
-    const size_t kb = (size_t)new_off[B] * 8;
-    LK_HIP_CHECK(hipMemcpy(t_out, dto, kb, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(flux_out, dfo, kb, hipMemcpyDeviceToHost));
-    if (flux_err_out) LK_HIP_CHECK(hipMemcpy(flux_err_out, deo, kb, hipMemcpyDeviceToHost));
-    if (median_out) LK_HIP_CHECK(hipMemcpy(median_out, dmed, (size_t)B * 8, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 int lk_fits_unpack_batch_dev(lk_handle *h, int B, const uint8_t *raw, const int64_t *raw_off_host, const int32_t *desc_host,
@@ -1043,23 +1000,16 @@ int lk_fits_unpack_batch(lk_handle *h, int B, const uint8_t *raw, const int64_t 
     LK_HIP_CHECK(hipSetDevice(h->device));
     size_t rows = 0;
     for (int b = 0; b < B; ++b) rows += (size_t)std::max(0, desc[(size_t)b * 10 + 1]);
-    const size_t nraw = (size_t)raw_off[B], nb = rows * 8;
-    h->staging.reset();
-    int rc = h->staging.reserve(nraw + 3 * (nb + 256) + rows * 4 + 4096);
+    const int64_t *kept = &new_off[B];  // set by the launch
+    const uint8_t *draw;
+    double *dto, *dfo, *deo;
+    int32_t *dqo;
+    lk::StagedCall io(h);
+    int rc = io.in(draw, raw, (size_t)raw_off[B], 16).out(dto, t_out, rows, kept).out(dfo, flux_out, rows, kept)
+                 .out(deo, flux_err_out, rows, kept).out(dqo, quality_out, rows, kept).stage();
     if (rc) return rc;
-    uint8_t *draw = (uint8_t *)h->staging.alloc(nraw + 16);
-    double *dto = (double *)h->staging.alloc(nb), *dfo = (double *)h->staging.alloc(nb);
-    double *deo = flux_err_out ? (double *)h->staging.alloc(nb) : nullptr;
-    int32_t *dqo = quality_out ? (int32_t *)h->staging.alloc(rows * 4) : nullptr;
-    LK_HIP_CHECK(hipMemcpy(draw, raw, nraw, hipMemcpyHostToDevice));
     rc = lk::fits_unpack_launch(h, B, draw, raw_off, desc, bitmask, dto, dfo, deo, dqo, new_off, nullptr);
-    if (rc) return rc;
-    const size_t kept = (size_t)new_off[B];
-    LK_HIP_CHECK(hipMemcpy(t_out, dto, kept * 8, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(flux_out, dfo, kept * 8, hipMemcpyDeviceToHost));
-    if (flux_err_out) LK_HIP_CHECK(hipMemcpy(flux_err_out, deo, kept * 8, hipMemcpyDeviceToHost));
-    if (quality_out) LK_HIP_CHECK(hipMemcpy(quality_out, dqo, kept * 4, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 int lk_fits_unpack_cube_dev(lk_handle *h, const uint8_t *raw, int row_bytes, int n_rows, int off_time, int code_time,
@@ -1081,22 +1031,22 @@ int lk_fits_unpack_cube(lk_handle *h, const uint8_t *raw, int row_bytes, int n_r
     LK_REQUIRE(raw && col_off && t_out && cubes_out && kept, "NULL buffer");
     LK_REQUIRE(row_bytes >= 1 && n_rows >= 0 && ncols >= 1 && ncols <= 4 && npix >= 1, "bad table description");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t nraw = (size_t)row_bytes * n_rows, ncube = (size_t)ncols * n_rows * npix * 4;
-    h->staging.reset();
-    int rc = h->staging.reserve(nraw + ncube + (size_t)n_rows * 12 + 4096);
+    const uint8_t *draw;
+    double *dt;
+    int32_t *dq;
+    float *dc;
+    lk::StagedCall io(h);
+    // 16 bytes of tail past raw and the cubes, 8 past the times and the quality flags
+    int rc = io.in(draw, raw, (size_t)row_bytes * n_rows, 16).out(dt, t_out, (size_t)n_rows + 1, kept)
+                 .out(dq, quality_out, (size_t)n_rows + 2, kept).scratch(dc, (size_t)ncols * n_rows * npix + 4).stage();
     if (rc) return rc;
-    uint8_t *draw = (uint8_t *)h->staging.alloc(nraw + 16);
-    double *dt = (double *)h->staging.alloc((size_t)n_rows * 8 + 8);
-    int32_t *dq = quality_out ? (int32_t *)h->staging.alloc((size_t)n_rows * 4 + 8) : nullptr;
-    float *dc = (float *)h->staging.alloc(ncube + 16);
-    LK_HIP_CHECK(hipMemcpy(draw, raw, nraw, hipMemcpyHostToDevice));
     rc = lk::fits_cube_launch(h, draw, row_bytes, n_rows, off_time, code_time, off_quality, code_quality, bitmask,
                               keep_nan_time, ncols, col_off, npix, dt, dq, dc, kept, nullptr);
     if (rc) return rc;
     LK_HIP_CHECK(hipDeviceSynchronize());
+    rc = io.finish();
+    if (rc) return rc;
     const size_t k = (size_t)*kept;
-    LK_HIP_CHECK(hipMemcpy(t_out, dt, k * 8, hipMemcpyDeviceToHost));
-    if (quality_out) LK_HIP_CHECK(hipMemcpy(quality_out, dq, k * 4, hipMemcpyDeviceToHost));
     for (int c = 0; c < ncols; ++c)  // host layout: [column][kept cadence][pixel], columns n_rows * npix apart like the device's
         LK_HIP_CHECK(hipMemcpy(cubes_out + (size_t)c * n_rows * npix, dc + (size_t)c * n_rows * npix, k * npix * 4,
                                hipMemcpyDeviceToHost));
@@ -1120,16 +1070,13 @@ int lk_transit_mask_batch(lk_handle *h, int B, const int64_t *n_off, const doubl
     LK_REQUIRE(t && mask, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
     const size_t ntot = (size_t)n_off[B];
-    h->staging.reset();
-    int rc = h->staging.reserve(ntot * 9 + 2 * 256 + 4096);
+    const double *dt;
+    uint8_t *dm;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).out(dm, mask, ntot).stage();
     if (rc) return rc;
-    double *dt = (double *)h->staging.alloc(ntot * 8);
-    uint8_t *dm = (uint8_t *)h->staging.alloc(ntot);
-    LK_HIP_CHECK(hipMemcpy(dt, t, ntot * 8, hipMemcpyHostToDevice));
     rc = lk::transit_mask_launch(h, B, n_off, dt, planet_off, period, duration, transit_time, dm, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(mask, dm, ntot, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 int lk_bin_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,
@@ -1150,23 +1097,16 @@ int lk_bin_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, con
     if (B == 0 || bin_off[B] == 0) return LK_OK;
     LK_REQUIRE(t && flux && t_out && flux_out && flux_err_out, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    const size_t ntot = (size_t)n_off[B], nb = ntot * 8, ob = (size_t)bin_off[B] * 8;
-    h->staging.reset();
-    int rc = h->staging.reserve(3 * (nb + 256) + 3 * (ob + 256) + 4096);
+    const size_t ntot = (size_t)n_off[B], nbin = (size_t)bin_off[B];
+    const double *dt, *df, *de;
+    double *dto, *dfo, *deo;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).in(df, flux, ntot).in(de, flux_err, ntot).out(dto, t_out, nbin).out(dfo, flux_out, nbin)
+                 .out(deo, flux_err_out, nbin).stage();
     if (rc) return rc;
-    double *dt = (double *)h->staging.alloc(nb), *df = (double *)h->staging.alloc(nb);
-    double *de = flux_err ? (double *)h->staging.alloc(nb) : nullptr;
-    double *dto = (double *)h->staging.alloc(ob), *dfo = (double *)h->staging.alloc(ob), *deo = (double *)h->staging.alloc(ob);
-    LK_HIP_CHECK(hipMemcpy(dt, t, nb, hipMemcpyHostToDevice));
-    LK_HIP_CHECK(hipMemcpy(df, flux, nb, hipMemcpyHostToDevice));
-    if (flux_err) LK_HIP_CHECK(hipMemcpy(de, flux_err, nb, hipMemcpyHostToDevice));
     rc = lk::bin_launch(h, B, n_off, dt, df, de, bin_off, time_bin_start, edges_sec, n_edges, bin_size_sec, has_err, dto, dfo,
                         deo, nullptr);
-    if (rc) return rc;
-    LK_HIP_CHECK(hipMemcpy(t_out, dto, ob, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(flux_out, dfo, ob, hipMemcpyDeviceToHost));
-    LK_HIP_CHECK(hipMemcpy(flux_err_out, deo, ob, hipMemcpyDeviceToHost));
-    return LK_OK;
+    return rc ? rc : io.finish();
 }
 
 }  // extern "C"

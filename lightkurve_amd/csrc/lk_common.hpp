@@ -67,7 +67,8 @@ struct lk_handle {
     int host_chunk_mb = 64;  // MiB of spectra per chunk of the pinned host pipeline (LK_HOST_CHUNK_MB at lk_init, lk_set_host_chunk_mb)
     lk::HostStage stage;
     lk::Arena ws;        // kernel scratch (prepped per-cadence records, per-target stats)
-    lk::Arena staging;   // device mirrors of host buffers for the *_batch (host pointer) entry points
+    lk::Arena staging;   // device mirrors of host buffers for the *_batch (host pointer) entry points, carved per call by
+                         // capi.hip's StagedCall (the chunked LS 'fast' pipeline carves its own double buffers)
     // host-pointer pipeline (lk_ls_fast_peaks_batch): copy-in, compute and copy-out streams + the events that order
     // the two halves of the double buffers; created on first use
     hipStream_t s_in = nullptr, s_comp = nullptr, s_out = nullptr;

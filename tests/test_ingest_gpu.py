@@ -12,13 +12,22 @@ from oracle import np_oracle as O
 pytestmark = pytest.mark.gpu
 
 
+def _null_args(monkeypatch, entry, *positions):
+    """Make the _capi wrapper's call of the C entry point `entry` pass NULL at argument `positions`: the optional outputs
+    the wrapper always asks for."""
+    from lightkurve_amd import _capi
+    real = getattr(_capi.load_library(), entry)
+    monkeypatch.setattr(_capi._lib, entry, lambda *a: real(*[None if i in positions else x for i, x in enumerate(a)]))
+
+
 def _batch(g):
     n = int(g["n"])
     return LightCurveBatch.from_lightcurves([LightCurve(time=g["time_%d" % b], flux=g["flux_%d" % b], flux_err=g["err_%d" % b])
                                              for b in range(n)]), n
 
 
-def test_remove_nans_normalize_batch_vs_reference(golden):
+def test_remove_nans_normalize_batch_vs_reference(golden, monkeypatch):
+    from lightkurve_amd import _capi
     g = golden("ingest")
     batch, n = _batch(g)
     clean = batch.remove_nans()
@@ -31,6 +40,11 @@ def test_remove_nans_normalize_batch_vs_reference(golden):
         assert np.allclose(norm[b].flux_err, g["clean_err_%d" % b], rtol=1e-15, atol=0, equal_nan=True)
         assert norm.median_flux[b] == np.nanmedian(g["flux_%d" % b])
         assert norm.meta[b]["NORMALIZED"] is True
+    # median_out NULL: the same cadences, flux and errors
+    ref = _capi.ingest_batch(batch.time, batch.flux, batch.n_off, flux_err=batch.flux_err)
+    _null_args(monkeypatch, "lk_ingest_batch", 11)
+    got = _capi.ingest_batch(batch.time, batch.flux, batch.n_off, flux_err=batch.flux_err)
+    assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(ref[:4], got[:4]))
 
 
 def test_transit_mask_batch_and_single(golden):
@@ -54,6 +68,7 @@ def test_transit_mask_batch_and_single(golden):
 
 
 def test_bin_batch_vs_reference(golden):
+    from lightkurve_amd import _capi
     g = golden("ingest")
     batch, n = _batch(g)
     for b in range(n):                      # per light curve: its own bin size, as in the golden
@@ -70,6 +85,11 @@ def test_bin_batch_vs_reference(golden):
         assert np.allclose(binned[b].time, rt, rtol=0, atol=1e-9)
         assert np.allclose(binned[b].flux, rf, rtol=1e-13, atol=0, equal_nan=True)
         assert np.allclose(binned[b].flux_err, re_, rtol=1e-12, atol=0, equal_nan=True)
+    # no flux_err (NULL) bins like errors that are all NaN
+    nan_err = np.full(batch.time.size, np.nan)
+    ref = _capi.bin_batch(batch.time, batch.flux, batch.n_off, flux_err=nan_err, time_bin_size=0.4)
+    got = _capi.bin_batch(batch.time, batch.flux, batch.n_off, time_bin_size=0.4)
+    assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(ref, got))
 
 
 def test_batch_feeds_the_periodogram_path():
@@ -89,7 +109,7 @@ def test_batch_feeds_the_periodogram_path():
     assert np.max(np.abs(P - ref)) <= 1e-12 * np.max(ref)
 
 
-def test_fits_files_to_batch_vs_reference_readers(golden):
+def test_fits_files_to_batch_vs_reference_readers(golden, monkeypatch):
     """FITS -> ragged arrays on the device (lk_fits_unpack_batch) for a mixed batch of Kepler-, TESS- and generic-layout
     files against what lightkurve's own readers return for the same files (oracle/gen_golden.py::gen_fits)."""
     import os
@@ -127,9 +147,14 @@ def test_fits_files_to_batch_vs_reference_readers(golden):
     # many files: more workgroups than one wave of CUs, records staged through LDS in several trips
     big = LightCurveBatch.from_fits(paths[:3] * 40)
     assert len(big) == 120 and np.array_equal(big[117].time, g["kepler_default_time"])
+    # flux_err_out and quality_out NULL: the same cadences and flux
+    _null_args(monkeypatch, "lk_fits_unpack_batch", 8, 9)
+    bare = LightCurveBatch.from_fits(paths)
+    assert np.array_equal(bare.n_off, batch.n_off) and np.array_equal(bare.time, batch.time)
+    assert np.array_equal(bare.flux, batch.flux, equal_nan=True)
 
 
-def test_read_dispatches_on_file_type(golden):
+def test_read_dispatches_on_file_type(golden, monkeypatch):
     """lightkurve_amd.read(path): light-curve files -> LightCurve, target-pixel files -> PixelCube (reference io/read.py)."""
     import os
     import lightkurve_amd as lka
@@ -143,6 +168,11 @@ def test_read_dispatches_on_file_type(golden):
     assert np.array_equal(hard.flux, g["kepler_hard_sap_flux"], equal_nan=True)
     cube = lka.read(os.path.join(fdir, "kepler_tpf.fits"))
     assert isinstance(cube, PixelCube) and np.array_equal(cube.flux, g["ktpf_default_flux"], equal_nan=True)
+    # lk_fits_unpack_cube with quality_out NULL: the same times and cubes
+    _null_args(monkeypatch, "lk_fits_unpack_cube", 14)
+    bare = lka.read(os.path.join(fdir, "kepler_tpf.fits"))
+    assert np.array_equal(bare.time, cube.time, equal_nan=True) and np.array_equal(bare.flux, cube.flux, equal_nan=True)
+    assert np.array_equal(bare.flux_err, cube.flux_err, equal_nan=True)
 
 
 def test_median_of_long_light_curves_is_the_exact_order_statistic():

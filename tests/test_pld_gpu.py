@@ -211,7 +211,8 @@ def test_target_pixel_file_to_cube_vs_reference_classes(golden, fname, tag, kw):
 def test_one_call_correct_equals_design_then_regress():
     """lk_pld_correct_batch (design matrices kept in device memory) against the two host-pointer calls it fuses,
     lk_pld_design_batch + lk_regress_batch: same kernels on the same inputs, so coefficients, model and outlier mask are the
-    same bits; the spline block's share of the model against numpy on the downloaded design matrix."""
+    same bits, with and without the PLD pixel block and the errors; the spline block's share of the model against numpy on the
+    downloaded design matrix."""
     from lightkurve_amd import _capi, synth
     from lightkurve_amd.correctors.pldcorrector import _percentile_knots
     B, n, npix = 3, 900, 7
@@ -226,13 +227,13 @@ def test_one_call_correct_equals_design_then_regress():
     knots = np.stack([_percentile_knots(t[b], n // 50, 5) for b in range(B)])
     cm = np.ones((B, n), bool)
     cm[1, 100:140] = False
-    for cmask in (None, cm):
-        X, ps = _capi.pld_design_batch(pix, pix, lcf, t, knots, 2, 8, 5, True)
+    for cmask, pld, e in ((None, pix, err), (cm, None, None), (cm, pix, err)):   # the last one is compared with below
+        X, ps = _capi.pld_design_batch(pld, pix, lcf, t, knots, 2, 8, 5, True)
         K = X.shape[2]
-        two = _capi.regress_batch(X.reshape(B * n, K), y.ravel(), np.arange(B + 1) * n, err=err.ravel(),
+        two = _capi.regress_batch(X.reshape(B * n, K), y.ravel(), np.arange(B + 1) * n, err=None if e is None else e.ravel(),
                                   cadence_mask=None if cmask is None else cmask.ravel(), prior_mu=np.zeros((B, K)),
                                   prior_sigma=ps, sigma=5, niters=5)
-        one = _capi.pld_correct_batch(pix, pix, lcf, t, knots, y, err, 2, 8, 5, True, cadence_mask=cmask, sigma=5, niters=5)
+        one = _capi.pld_correct_batch(pld, pix, lcf, t, knots, y, e, 2, 8, 5, True, cadence_mask=cmask, sigma=5, niters=5)
         assert np.array_equal(one["coefficients"], two["coefficients"])
         assert np.array_equal(one["model"].ravel(), two["model"])
         assert np.array_equal(one["outlier_mask"].ravel(), two["outlier_mask"])
