@@ -7,7 +7,45 @@
 
 #include <cstdint>
 
+// Route hooks.  block_select_sampled, lds_hist_select and block_median_near keep "ALWAYS the exact order statistic" through
+// workgroup-uniform branches that depend on the data; LK_SEL_ROUTE(id) marks each of them.  Release builds leave the macro empty
+// (no code); tests/select_harness.hip defines it before including this header to record which branches a problem took.
+#ifndef LK_SEL_ROUTE
+#define LK_SEL_ROUTE(id) ((void)0)
+#endif
+
 namespace lk {
+
+enum SelRoute {
+    SEL_R_CAP_SMALL_FALLBACK = 0,  // sampled: cap < 2 SEL_SAMPLE, radix select
+    SEL_R_ALL_IN_LDS,              // sampled: count <= min(cap, 2048), every kept value collected
+    SEL_R_ALL_HIST_OK,             //   ... ranked by the histogram over [min, max]
+    SEL_R_ALL_SORTED,              //   ... histogram refused (no room, ties, non-finite or empty range): sorted
+    SEL_R_SAMPLE_SMALL_FALLBACK,   // sampled: fewer than 64 sample positions kept, radix select
+    SEL_R_BRACKET,                 // sampled: pivots taken, collect pass ran (side_ran)
+    SEL_R_PIVOT_LO_INF,            //   ... lower pivot ran off the sample (-inf)
+    SEL_R_PIVOT_HI_INF,            //   ... upper pivot ran off the sample (+inf)
+    SEL_R_OVERFLOW,                // sampled: more than cap values inside the bracket
+    SEL_R_REFINE_NA_FALLBACK,      //   ... refinement does not apply (rank outside, non-finite or empty bracket): radix select
+    SEL_R_REFINE_TIES_FALLBACK,    //   ... the wanted bins still hold more than cap values (or a count mismatch): radix select
+    SEL_R_REFINED,                 //   ... sub-bracket collected
+    SEL_R_REFINED_TWO_BINS,        //   ... and the two ranks sit in different bins
+    SEL_R_CAND_HIST_OK,            // sampled: candidates ranked by lds_hist_select
+    SEL_R_CAND_HIST_REFUSED,       // sampled: lds_hist_select returned false for the candidates
+    SEL_R_CAND_SORTED,             //   ... candidates sorted (padded size fits cap)
+    SEL_R_CAND_LDS_RADIX,          //   ... padded size exceeds cap (cap not a power of two): radix select over LDS
+    SEL_R_RANK_IN_EQLO,            // sampled: a wanted rank equals the lower pivot
+    SEL_R_RANK_IN_CAND,            // sampled: a wanted rank lies among the candidates
+    SEL_R_RANK_IN_EQHI,            // sampled: a wanted rank equals the upper pivot
+    SEL_R_MISS_FALLBACK,           // sampled: a wanted rank lies outside the bracket, radix select
+    SEL_R_HIST_NA,                 // lds_hist_select: does not apply (bracket not finite / empty, no room, no candidates)
+    SEL_R_HIST_TIES,               // lds_hist_select: more than SEL_LIST values in the wanted bins
+    SEL_R_HIST_DONE,               // lds_hist_select: ranks served
+    SEL_R_NEAR_REFUSED,            // block_median_near: nothing kept, width <= 0 or a non-finite guess
+    SEL_R_NEAR_GAVE_UP,            // block_median_near: the middle ranks are not inside the window, or it holds more than cap values
+    SEL_R_NEAR_OK,                 // block_median_near: exact median from the window
+    SEL_R_COUNT
+};
 
 __device__ __forceinline__ unsigned long long f64_sortable(double x) {
     unsigned long long u = (unsigned long long)__double_as_longlong(x);
@@ -333,7 +371,10 @@ __device__ __forceinline__ bool lds_hist_select(const double *cand, int nc, int 
                                                 unsigned long long *sh, double *va, double *vb) {
     const int tid = threadIdx.x, nt = blockDim.x;
     const int nc_pad = (nc + 1) & ~1;
-    if (!(hi > lo) || !isfinite(lo) || !isfinite(hi) || nc_pad + SEL_NB / 2 + SEL_LIST + 2 > cap || nc <= 0) return false;
+    if (!(hi > lo) || !isfinite(lo) || !isfinite(hi) || nc_pad + SEL_NB / 2 + SEL_LIST + 2 > cap || nc <= 0) {
+        LK_SEL_ROUTE(SEL_R_HIST_NA);
+        return false;
+    }
     int *hist = reinterpret_cast<int *>(const_cast<double *>(cand) + nc_pad);
     double *list = const_cast<double *>(cand) + nc_pad + SEL_NB / 2;
     int *ctl = reinterpret_cast<int *>(sh + 210);       // [0] bin of qa, [1] its exclusive prefix, [2], [3] same for qb, [4] list length
@@ -381,16 +422,23 @@ __device__ __forceinline__ bool lds_hist_select(const double *cand, int nc, int 
     __syncthreads();
     const int m = ctl[4];
     if (m > SEL_LIST || (qa >= 0 && ba < 0) || (qb >= 0 && bb < 0)) {
+        LK_SEL_ROUTE(SEL_R_HIST_TIES);
         __syncthreads();
         return false;
     }
+    LK_SEL_ROUTE(SEL_R_HIST_DONE);
     if (tid < m) {
         const double v = list[tid];
         const int b = bin(v);
+        // ranked by sortable key, not by value: -0.0 == +0.0 as values, and the slot order among equal values follows the LDS
+        // atomics — by key -0.0 comes first (as in the radix select and the sort) and only identical bits tie, so the result's
+        // bits do not depend on the order the list was filled in
+        const unsigned long long kv = f64_sortable(v);
         int r = (b == ba) ? ctl[1] : ctl[3];
         for (int u = 0; u < m; ++u) {
             const double w = list[u];
-            if (bin(w) == b && (w < v || (w == v && u < tid))) ++r;
+            const unsigned long long kw = f64_sortable(w);
+            if (bin(w) == b && (kw < kv || (kw == kv && u < tid))) ++r;
         }
         if (r == qa) outv[0] = v;
         if (r == qb) outv[1] = v;
@@ -414,7 +462,8 @@ constexpr int SEL_SAMPLE = 1024;
 
 // A side computation that rides on the ONE pass over all values (the bracket's collect pass): side(i, v, lo) sees every kept
 // value v = val(i) together with `lo`, a lower bound of the order statistic being selected (the bracket's lower pivot).
-// *side_ran tells the caller whether that pass happened (the all-in-LDS and fallback routes do not run it).
+// *side_ran tells the caller whether that pass happened AND its `lo` holds (the all-in-LDS route and the fallbacks before the
+// pass do not run it; a fallback after it — bracket miss, refinement given up — voids it: the answer may lie below `lo`).
 struct NoSide {
     __device__ __forceinline__ void operator()(int, double, double) const {}
 };
@@ -442,6 +491,8 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
         int S2 = 2;
         while (S2 < nc) S2 <<= 1;
         if (S2 > cap) {
+            // (dead: the only caller is the all-in-LDS route, where nc <= min(cap, 2048), so S2 <= 2048 <= cap whenever that
+            // route runs at all (cap >= 2 SEL_SAMPLE).  Kept as it is — no route id, not counted by the route tests.)
             const double a = block_select_kth(nc, q, lds_val, lds_all, sh);
             if (want_next) *next = (q + 1 < nc) ? block_select_kth(nc, q + 1, lds_val, lds_all, sh) : a;
             return a;
@@ -454,8 +505,12 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
         __syncthreads();
         return a;
     };
-    if (cap < 2 * SEL_SAMPLE) return fallback();
+    if (cap < 2 * SEL_SAMPLE) {
+        LK_SEL_ROUTE(SEL_R_CAP_SMALL_FALLBACK);
+        return fallback();
+    }
     if (count <= (long long)min(cap, 2 * SEL_SAMPLE)) {
+        LK_SEL_ROUTE(SEL_R_ALL_IN_LDS);
         // everything fits a 2048-key sort: collect once, select in LDS (between that and `cap` values the sampled route
         // below — 1024-key sample sort, ~15 % of the values collected, histogram — beats collecting and sorting them all)
         if (tid == 0) ictl[0] = 0;
@@ -491,10 +546,12 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
             const bool nb = want_next && k + 1 < (long long)nc;
             double hva = 0.0, hvb = 0.0;
             if (k < (long long)nc && lds_hist_select(cand, nc, cap, (int)k, nb ? (int)k + 1 : -1, mn, mx, sh, &hva, &hvb)) {
+                LK_SEL_ROUTE(SEL_R_ALL_HIST_OK);
                 if (want_next) *next = nb ? hvb : hva;
                 return hva;
             }
         }
+        LK_SEL_ROUTE(SEL_R_ALL_SORTED);
         return sorted_ranks(nc, k);
     }
     // ---- strided sample -> keys[0..S), padded with +inf keys to a power of two, bitonic sort
@@ -510,7 +567,10 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
         int c = 0;
         for (int j = tid; j < S; j += nt) c += keys[j] != ~0ull ? 1 : 0;
         const long long s_all = block_count_fast(c, reinterpret_cast<long long *>(sh));
-        if (s_all < 64) return fallback();  // (uniform: every thread sees the same s_all)
+        if (s_all < 64) {  // (uniform: every thread sees the same s_all)
+            LK_SEL_ROUTE(SEL_R_SAMPLE_SMALL_FALLBACK);
+            return fallback();
+        }
         const double pos = ((double)k + 0.5) * (double)s_all / (double)count;
         // half-width of the bracket in sample ranks: the rank of the wanted value among a random sample scatters by
         // sigma = sqrt(s_all) / 2 around pos.  4 sigma (a miss — the full radix select, ~300 us — once in ~16 000 selects: with
@@ -523,6 +583,9 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
         // pivots (registers, same in every thread): -inf / +inf when the bracket runs off the sample
         const double lo = r_lo < 0 ? -INFINITY : f64_from_sortable(keys[r_lo]);
         const double hi = r_hi >= (int)s_all ? INFINITY : f64_from_sortable(keys[r_hi]);
+        LK_SEL_ROUTE(SEL_R_BRACKET);
+        if (r_lo < 0) LK_SEL_ROUTE(SEL_R_PIVOT_LO_INF);
+        if (r_hi >= (int)s_all) LK_SEL_ROUTE(SEL_R_PIVOT_HI_INF);
         __syncthreads();  // the sample (aliasing cand) is dead from here on
         if (tid == 0) ictl[0] = 0;
         __syncthreads();
@@ -555,9 +618,14 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
             // (SEL_NB counters over the linear map of (lo, hi), which is monotone: a lower bin holds smaller values), the bins
             // that hold the wanted ranks become the new bracket, and a last pass collects just those — three passes in all
             // where the radix select behind fallback() takes eight per rank.
+            LK_SEL_ROUTE(SEL_R_OVERFLOW);
             const long long q0 = k - n_less - n_eqlo;
             const bool wa = q0 >= 0 && q0 < (long long)nc, wb = want_next && k + 1 < count && q0 + 1 >= 0 && q0 + 1 < (long long)nc;
-            if (!(wa || wb) || !isfinite(lo) || !isfinite(hi) || !(hi > lo) || cap < SEL_NB) return fallback();
+            if (!(wa || wb) || !isfinite(lo) || !isfinite(hi) || !(hi > lo) || cap < SEL_NB) {
+                LK_SEL_ROUTE(SEL_R_REFINE_NA_FALLBACK);
+                if (side_ran) *side_ran = false;  // `lo` was not shown to bound the answer: the side pass is void
+                return fallback();
+            }
             const long long r_first = wa ? q0 : q0 + 1, r_last = wb ? q0 + 1 : q0;
             int *hist = reinterpret_cast<int *>(cand);
             int *ctl = reinterpret_cast<int *>(sh + 210);  // [0] first bin, [1] values below it, [2] last bin, [3] values through it
@@ -593,7 +661,11 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
             __syncthreads();
             const int ba = ctl[0], bb = ctl[2], below = ctl[1], through = ctl[3];
             __syncthreads();  // (hist aliases cand: every thread has its bins before the list is rebuilt)
-            if (ba < 0 || bb < ba || tot != nc || through - below > cap) return fallback();
+            if (ba < 0 || bb < ba || tot != nc || through - below > cap) {
+                LK_SEL_ROUTE(SEL_R_REFINE_TIES_FALLBACK);
+                if (side_ran) *side_ran = false;  // `lo` was not shown to bound the answer: the side pass is void
+                return fallback();
+            }
             if (tid == 0) ictl[0] = 0;
             __syncthreads();
             strided_pass<8>(n, [&](int i) { return val(i); }, [&](int i, double v) {
@@ -606,7 +678,13 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
                 }
             });
             __syncthreads();
-            if (ictl[0] != through - below) return fallback();
+            if (ictl[0] != through - below) {
+                LK_SEL_ROUTE(SEL_R_REFINE_TIES_FALLBACK);
+                if (side_ran) *side_ran = false;  // `lo` was not shown to bound the answer: the side pass is void
+                return fallback();
+            }
+            LK_SEL_ROUTE(SEL_R_REFINED);
+            if (bb != ba) LK_SEL_ROUTE(SEL_R_REFINED_TWO_BINS);
             // the values below the sub-bracket now count as "less"; its edges only steer the next histogram (clamped bins)
             n_less += n_eqlo + below;
             n_eqlo = 0;
@@ -623,10 +701,13 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
         double hva = 0.0, hvb = 0.0;
         const bool hist_ok = (need_a || need_b) &&
                              lds_hist_select(cand, nc, cap, need_a ? (int)qa : -1, need_b ? (int)qb : -1, slo, shi_v, sh, &hva, &hvb);
+        if (hist_ok) LK_SEL_ROUTE(SEL_R_CAND_HIST_OK);
+        if (!hist_ok && (need_a || need_b)) LK_SEL_ROUTE(SEL_R_CAND_HIST_REFUSED);
         int S2 = 2;
         while (S2 < nc) S2 <<= 1;
         const bool sorted = !hist_ok && (need_a || need_b) && S2 <= cap;
         if (sorted) {
+            LK_SEL_ROUTE(SEL_R_CAND_SORTED);
             for (int i = tid; i < S2; i += nt) keys[i] = i < nc ? f64_sortable(cand[i]) : ~0ull;
             __syncthreads();
             lds_bitonic_sort(keys, S2);
@@ -639,14 +720,22 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
                 miss = true;
                 return 0.0;
             }
-            if (q < n_eqlo) return lo;
+            if (q < n_eqlo) {
+                LK_SEL_ROUTE(SEL_R_RANK_IN_EQLO);
+                return lo;
+            }
             q -= n_eqlo;
             if (q < nc) {
+                LK_SEL_ROUTE(SEL_R_RANK_IN_CAND);
                 if (hist_ok) return q == qa ? hva : hvb;  // (q is relative to the candidates here: qa or qa + 1)
+                if (!sorted) LK_SEL_ROUTE(SEL_R_CAND_LDS_RADIX);
                 return sorted ? f64_from_sortable(keys[q]) : block_select_kth(nc, q, lds_val, lds_all, sh);
             }
             q -= nc;
-            if (q < n_eqhi) return hi;
+            if (q < n_eqhi) {
+                LK_SEL_ROUTE(SEL_R_RANK_IN_EQHI);
+                return hi;
+            }
             miss = true;
             return 0.0;
         };
@@ -660,7 +749,11 @@ __device__ double block_select_sampled(int n, long long count, long long k, Val 
             printf("[sel] blk %d n %d count %lld k %lld s_all %lld delta %d lo %.17g hi %.17g less %lld eqlo %lld nc %d eqhi %lld miss %d a %.17g\n",
                    blockIdx.x, n, count, k, s_all, delta, lo, hi, n_less, n_eqlo, nc, n_eqhi, (int)miss, a);
 #endif
-        if (miss) return fallback();
+        if (miss) {
+            LK_SEL_ROUTE(SEL_R_MISS_FALLBACK);
+            if (side_ran) *side_ran = false;  // `lo` was not shown to bound the answer: the side pass is void
+            return fallback();
+        }
         if (want_next) *next = b;
         return a;
     }
@@ -690,7 +783,10 @@ __device__ double block_median_near(int n, long long count, Val val, Keep keep, 
                                     unsigned long long *sh, double *cand, int cap, bool *ok, Side side = Side()) {
     const int tid = threadIdx.x, nt = blockDim.x;
     *ok = false;
-    if (count <= 0 || !(width > 0.0) || !isfinite(guess)) return 0.0;
+    if (count <= 0 || !(width > 0.0) || !isfinite(guess)) {
+        LK_SEL_ROUTE(SEL_R_NEAR_REFUSED);
+        return 0.0;
+    }
     int *ictl = reinterpret_cast<int *>(sh + 200);
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(cand);
     const long long k = (count - 1) / 2;
@@ -720,7 +816,11 @@ __device__ double block_median_near(int n, long long count, Val val, Keep keep, 
     if (S2 < nt && (nt & (nt - 1)) == 0) S2 = nt;  // the one-key-per-thread register sort
     const bool good = nc <= cap && S2 <= cap && q >= 0 && q + (want_next ? 1 : 0) < (long long)nc;
     __syncthreads();
-    if (!good) return 0.0;
+    if (!good) {
+        LK_SEL_ROUTE(SEL_R_NEAR_GAVE_UP);
+        return 0.0;
+    }
+    LK_SEL_ROUTE(SEL_R_NEAR_OK);
     for (int i = tid; i < S2; i += nt) keys[i] = i < nc ? f64_sortable(cand[i]) : ~0ull;
     __syncthreads();
     lds_bitonic_sort(keys, S2);

@@ -197,3 +197,29 @@ def test_own_stream_pool_reuse_and_clock_probe():
         assert 300.0 < mhz.value < 3000.0, mhz.value
     finally:
         _capi._check(_capi._lib.lk_stream_destroy(h._h, st))
+
+
+def test_bls_input_preparation_median_over_value_families_sizes_and_orders():
+    """The resident BLS input preparation's instantiation of the sampled select on the inputs tests/test_block_select_gpu.py
+    feeds the header directly (every value family at every size up to 30 000 in three orders, and the order that defeats the
+    strided sample): y == flux - median bit for bit, the median being the exact order statistic (numpy on the sorted values)."""
+    from lightkurve_amd.device import _off_ptr, _vp
+    from tests import select_harness as SH
+    cases = SH.production_batch()
+    flux = np.concatenate([v for _, v in cases])
+    off = np.concatenate([[0], np.cumsum([v.size for _, v in cases])]).astype(np.int64)
+    t = np.concatenate([np.arange(v.size, dtype=np.float64) for _, v in cases])
+    dev = DeviceLightCurveBatch.from_arrays(t, flux, None, off)
+    dev.nan_free = True                                   # no NaN flux in these inputs: nothing to compact
+    h, B, n = dev.handle, len(dev), dev.n_cadences
+    d_t, d_y, d_w = (DeviceBuffer(h, n * 8) for _ in range(3))
+    d_ref = DeviceBuffer(h, B * 8)
+    _capi._check(_capi._lib.lk_bls_prepare_batch_dev(h._h, B, _off_ptr(dev.n_off), _vp(dev.d_time.ptr), _vp(dev.d_flux.ptr), _vp(None),
+                                                     _vp(d_t.ptr), _vp(d_y.ptr), _vp(d_w.ptr), _vp(d_ref.ptr), _vp(None)))
+    y = d_y.download(np.float64, n)
+    med = np.array([SH.reference_median(v) for _, v in cases])
+    with np.errstate(all="ignore"):
+        want = flux - np.repeat(med, np.diff(off))
+    bad = [cases[b][0] for b in range(B) if not np.array_equal(y[off[b]:off[b + 1]], want[off[b]:off[b + 1]], equal_nan=True)]
+    assert not bad, bad
+    assert np.array_equal(d_t.download(np.float64, n), t) and np.all(d_w.download(np.float64, n) == 1.0)

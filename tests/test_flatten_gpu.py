@@ -251,3 +251,63 @@ def test_interpolation_without_knot_gather_edge_cases():
                 assert np.array_equal(ok, np.isfinite(g)), (i, w, s)
                 assert np.allclose(g[ok], ref[ok], rtol=1e-9, atol=0), (i, w, s, np.max(np.abs(g[ok] - ref[ok]) / np.abs(ref[ok])))
                 assert np.array_equal(fit[oo[j]:oo[j + 1]], rfit), (i, w, s)
+
+
+@pytest.mark.parametrize("n,every", [(8192, 8), (4000, 2)])
+def test_flux_median_under_a_keep_functor_that_drops_cadences(n, every):
+    """The flux median of the initial clip runs the sampled select with a keep functor that is not all-true (NaN flux).
+    8192 cadences with a NaN at every 8th index: exactly the 1024 positions the strided sample reads, so 7168 finite values
+    stand behind an EMPTY sample (block_select.hpp falls back to the radix select).  4000 cadences with every second one NaN:
+    2000 finite values, the collect-everything route under a sparse mask.  The route taken inside the production kernel
+    cannot be observed; tests/test_block_select_gpu.py shows it for the same masks through the harness."""
+    rng = np.random.default_rng(n)
+    t = np.arange(n) * (2.0 / 1440.0)
+    y = 1.0 + 2e-3 * np.sin(2 * np.pi * t / 1.3) + 5e-4 * rng.standard_normal(n)
+    y[rng.choice(n, 12, replace=False)] += 0.03
+    y[np.arange(n) % every == 0] = np.nan
+    got = _capi.savgol_trend_batch(t, y, np.array([0, n], dtype=np.int64), window_length=101)
+    ref = O.flatten_trend(t, y, window_length=101)[0]
+    ok = np.isfinite(ref)
+    assert ok.all() and np.array_equal(ok, np.isfinite(got)) and np.allclose(got[ok], ref[ok], rtol=RTOL, atol=0)
+
+
+@pytest.mark.parametrize("n,window,polyorder,cap", [(67_000, 401, 2, 5880), (69_000, 301, 3, 5880), (56_000, 101, 2, 4896),
+                                                    (57_001, 401, 4, 4896)])
+def test_one_long_segment_below_the_break_tolerance_gets_its_median(n, window, polyorder, cap):
+    """A single segment of n cadences with break_tolerance > n: `len < break_tolerance` sends the whole segment to
+    flat_segment_median, so the trend IS the median of the kept flux — a pure order statistic, `==` is what is expected (the
+    interpolation between equal knots returns them unchanged); the comparison below keeps the file's RTOL.  That median runs
+    block_median_sampled with cap = the trend kernel's LDS area, which is not a power of two: 5880 doubles in the moment-form
+    kernel (window >= 201 with polyorder <= 3), 4896 in the tap-by-tap kernel (shorter windows, or polyorder >= 4 at any window
+    up to 2449).  At these sizes the candidates of the bracket overflow neither list but leave no room for the histogram and pad
+    to a sort size above cap: the radix select over LDS.  The route inside the production kernel cannot be observed: the harness
+    cases of tests/test_block_select_gpu.py at the same cap and sizes (LDS_RADIX_INPUTS) carry the route evidence."""
+    assert cap == (5880 if window >= 201 and polyorder <= 3 else 4896)
+    rng = np.random.default_rng(n)
+    t = np.arange(n) * (2.0 / 1440.0)
+    y = 1.0 + 5e-4 * rng.standard_normal(n)
+    y[rng.choice(n, 30, replace=False)] += 0.02
+    got = _capi.savgol_trend_batch(t, y, np.array([0, n], dtype=np.int64), window_length=window, polyorder=polyorder,
+                                   break_tolerance=1e6)
+    ref, fit = O.flatten_trend(t, y, window_length=window, polyorder=polyorder, break_tolerance=1e6)
+    assert np.unique(ref).size == 1 and 0.97 * n < fit.sum() < n          # one constant: the last iteration's median
+    assert np.allclose(got, ref, rtol=RTOL, atol=0)
+
+
+def test_segment_cuts_when_the_time_step_sample_misses_the_median():
+    """The cut candidates ride on the time-step median's collect pass and are noted against its lower pivot `lo`, which bounds
+    the median only if the bracket holds it.  Here it does not: 8192 steps, every 8th one — exactly the positions the strided
+    sample reads — three times as long as the rest, so the sample sees 3 u only while the median step is 1 u; three gaps of 8 u
+    exceed 5 x median but not 5 x `lo`.  The select falls back to the radix select (block_select.hpp voids side_ran on that
+    route), and the cuts must come from the exact threshold: against the oracle, which breaks the light curve at all three."""
+    rng = np.random.default_rng(5)
+    n, u = 8193, 2.0 / 1440.0
+    dt = np.where(np.arange(n - 1) % 8 == 0, 3.0, 1.0)
+    dt[[1001, 4003, 6005]] = 8.0
+    t = np.concatenate([[0.0], np.cumsum(dt * u)])
+    y = 1.0 + 3e-3 * np.sin(2 * np.pi * t / 0.9) + 2e-4 * rng.standard_normal(n)
+    y[1002:] += 0.01                                       # a step at the first gap: fitting across it would show
+    y[4004:] -= 0.015
+    got = _capi.savgol_trend_batch(t, y, np.array([0, n], dtype=np.int64), window_length=51)
+    ref = O.flatten_trend(t, y, window_length=51)[0]
+    assert np.nanmedian(np.diff(t)) < 1.5 * u and np.allclose(got, ref, rtol=RTOL, atol=0)

@@ -201,3 +201,29 @@ def test_median_of_long_light_curves_is_the_exact_order_statistic():
     off = np.concatenate([[0], np.cumsum([f.size for f in fs])])
     _, _, _, _, med = _capi.ingest_batch(np.arange(off[-1], dtype=np.float64), np.concatenate(fs), off, normalize=False)
     assert np.array_equal(med, [np.median(f) for f in fs])
+
+
+def test_median_over_value_families_sizes_and_orders_is_the_exact_order_statistic():
+    """`normalize`'s instantiation of the sampled select (its lambdas, its out-of-line radix fallback, its LDS plan) on the
+    inputs tests/test_block_select_gpu.py feeds the header directly: every value family (ties, both zeros, +-inf, denormals, a
+    spread whose hi - lo overflows, ...) at every size up to 30 000, shuffled, ascending and descending, and the order that
+    defeats the strided sample — one ragged call.  The median is an order statistic or the IEEE mean of two: `==` (value
+    equality, NaN where the reference is NaN: the mean of -inf and +inf), and normalised flux == flux / median bit for bit."""
+    from lightkurve_amd import _capi
+    from tests import select_harness as SH
+    cases = SH.production_batch()
+    flux = np.concatenate([v for _, v in cases])
+    off = np.concatenate([[0], np.cumsum([v.size for _, v in cases])])
+    t = np.arange(flux.size, dtype=np.float64)
+    ref = np.array([SH.reference_median(v) for _, v in cases])
+    to, fo, _, new_off, med = _capi.ingest_batch(t, flux, off, normalize=False)
+    assert np.array_equal(new_off, off) and np.array_equal(fo, flux) and np.array_equal(to, t)   # nothing to drop: no NaN flux
+    bad = [cases[b][0] for b in np.flatnonzero(~((med == ref) | (np.isnan(med) & np.isnan(ref))))]
+    assert not bad, bad
+    _, fn, _, _, med2 = _capi.ingest_batch(t, flux, off, normalize=True)
+    assert np.array_equal(med2, med, equal_nan=True)
+    with np.errstate(all="ignore"):
+        want = flux / np.repeat(med, np.diff(off))        # (by the median the device returned: a zero median keeps ITS sign)
+    bad = [cases[b][0] for b in range(len(cases))
+           if not np.array_equal(fn[off[b]:off[b + 1]], want[off[b]:off[b + 1]], equal_nan=True)]
+    assert not bad, bad
