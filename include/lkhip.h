@@ -20,6 +20,9 @@
  *   lk_pld_design_batch* <- PLDCorrector.create_design_matrix, src/lightkurve/correctors/pldcorrector.py:125-287.
  *   lk_pld_correct_batch <- PLDCorrector.correct (pldcorrector.py:304-427) for a batch of cutouts: the two above fused, the
  *                           design matrices staying in device memory.
+ *   lk_cube_aperture_batch_dev / lk_cube_median_image_batch_dev / lk_pld_gather_batch_dev <- what PLDCorrector does to a
+ *                           TargetPixelFile before that (aperture photometry, NaN cadences, threshold-mask median image,
+ *                           pixel series, knots) for cubes resident in device memory; lk_pld_correct_batch_dev follows.
  *   lk_fold_batch*       <- LightCurve.fold, src/lightkurve/lightcurve.py:1089-1214 (astropy TimeSeries.fold + sort).
  *   lk_pg_logmedian_batch* / lk_pg_boxsmooth_batch* <- Periodogram.smooth, periodogram.py:182-284.
  *
@@ -449,6 +452,54 @@ int lk_pld_correct_batch(lk_handle *h, int B, int N, int P, int Pb, const float 
                          int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, const double *y,
                          const double *err, const uint8_t *cadence_mask, double clip_sigma, int niters, double *w,
                          double *model, uint8_t *outlier, double *spline_part);
+/* The same on DEVICE pointers, enqueued on `stream` (no synchronisation).  X (B x N x K doubles), prior_sigma and prior_mu
+ * (B x K doubles each) are device scratch PROVIDED BY THE CALLER and must stay untouched until the stream has passed this
+ * call: they are not parked in the handle's staging arena, which a later host-pointer call on the same handle re-carves.
+ * pld_pix == bkg_pix (same pointer, P == Pb) for one aperture.  `corrected` (nullable, B x N) receives what
+ * PLDCorrector.correct returns (pldcorrector.py:418-420): (y - model) + (spline_part - median(spline_part)) when
+ * spline_part is given (restore_trend=True; np.median: the mean of the two middle values for an even N), else y - model. */
+int lk_pld_correct_batch_dev(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
+                             const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
+                             int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, const double *y,
+                             const double *err, const uint8_t *cadence_mask, double clip_sigma, int niters, double *X,
+                             double *prior_sigma, double *prior_mu, double *w, double *model, uint8_t *outlier,
+                             double *spline_part, double *corrected, void *stream);
+
+/* ---- Resident pixel cubes: what PLDCorrector does to a target-pixel file BEFORE the design matrix, for B same-shaped
+ * float32 cutouts flux / flux_err [B][N][npix] in device memory (npix = ny * nx row-major, the layout lk_fits_unpack_cube
+ * writes per column).  All take device pointers and a stream.
+ *
+ * lk_cube_aperture_batch_dev <- TargetPixelFile.to_lightcurve(aperture_mask), flux_method='sum'
+ *   (src/lightkurve/targetpixelfile.py:868-923) + the NaN-cadence mask of PLDCorrector.__init__
+ *   (correctors/pldcorrector.py:109-120).  mask: npix bytes shared by the batch (mask_stride = 0) or B x npix
+ *   (mask_stride = npix).  flux_out / err_out: B x N float32, bit-identical to numpy on float32 cubes: the aperture's pixels
+ *   of a cadence are added one after the other in pixel order in float32, err = sqrt(sum(e * e)), NaN pixels count as 0, the
+ *   flux is NaN where no aperture pixel is finite or the whole cadence image is 0.  keep_out: B x N bytes,
+ *   !(isnan(flux) | isnan(err)).  kept_host[b]: kept cadences, nonfinite_host[b] (nullable): kept cadences with a non-finite
+ *   pixel anywhere in the image — HOST arrays: the call synchronises `stream`.
+ * lk_cube_median_image_batch_dev <- np.nanmedian(tpf.flux, axis=0) inside create_threshold_mask
+ *   (targetpixelfile.py:680-742), over the cadences with keep != 0 (keep NULL: all): median B x npix float64, exact, NaN
+ *   for a pixel without a value.  Enqueued, no synchronisation.
+ * lk_pld_gather_batch_dev <- tpf[~nan_mask] and tpf.flux[:, mask] of PLDCorrector (pldcorrector.py:109-120, 203-227) + the
+ *   percentile knots of its spline (np.percentile(time, ...), :262-268).  n: the kept cadences of EVERY cutout (LK_EINVAL
+ *   if keep says otherwise).  Compacted t_out / y_out / err_out (float64, the float32 sums widened) / lcf_out (float32), each
+ *   B x n and nullable; pld_out B x n x P / bkg_out B x n x Pb = the pixels listed in pld_idx_host / bkg_idx_host (HOST int32,
+ *   ascending pixel numbers; stride 0: one list for the batch, stride P / Pb: one per cutout; NULL with P == npix: every
+ *   pixel).  A block whose output is NULL is skipped (all pixels of all cadences kept: the block IS the cube, and
+ *   lk_cube_aperture_batch_dev's nonfinite_host answers for its pixels).  knots_out (nullable) B x (n_inner + 2) = [t[0],
+ *   lerp(t[lo_k], t[lo_k + 1], g_k) ..., t[n - 1]] with numpy's _lerp from the HOST plan knot_lo_host / knot_g_host (n_inner
+ *   each; times must be non-decreasing).  *nonfinite_host = 1 if a gathered pixel is not finite.  Synchronises. */
+int lk_cube_aperture_batch_dev(lk_handle *h, int B, int N, int npix, const float *flux, const float *flux_err,
+                               const uint8_t *mask, int mask_stride, float *flux_out, float *err_out, uint8_t *keep_out,
+                               int64_t *kept_host, int64_t *nonfinite_host, void *stream);
+int lk_cube_median_image_batch_dev(lk_handle *h, int B, int N, int npix, const float *cube, const uint8_t *keep,
+                                   double *median, void *stream);
+int lk_pld_gather_batch_dev(lk_handle *h, int B, int N, int npix, int n, const float *cube, const double *time,
+                            const float *flux32, const float *err32, const uint8_t *keep, int P, const int32_t *pld_idx_host,
+                            int pld_idx_stride, int Pb, const int32_t *bkg_idx_host, int bkg_idx_stride, int n_inner,
+                            const int32_t *knot_lo_host, const double *knot_g_host, double *t_out, double *y_out,
+                            double *err_out, float *lcf_out, float *pld_out, float *bkg_out, double *knots_out,
+                            int *nonfinite_host, void *stream);
 
 /* ---- Standalone design-matrix operations (correctors/designmatrix.py) for B same-shaped matrices ----------------
  * lk_pca_batch          <- DesignMatrix.pca(nterms), designmatrix.py:252-282 (fbpca.pca(values, nterms) -> U): the first

@@ -17,7 +17,42 @@ from .regressioncorrector import RegressionCorrector
 
 log = logging.getLogger(__name__)
 
-__all__ = ["PixelCube", "PLDCorrector", "pld_correct_batch"]
+__all__ = ["PixelCube", "PLDCorrector", "pld_correct_batch", "threshold_mask_from_median_image"]
+
+
+def threshold_mask_from_median_image(median_image, threshold=3, reference_pixel="center"):
+    """The second half of ``create_threshold_mask`` (targetpixelfile.py:700-742): the MAD cut and the 4-connected labelling on
+    the per-pixel nanmedian image (row, column) — shared with ``DevicePixelCubeBatch``, which computes that image on the GPU."""
+    median_image = np.asarray(median_image, dtype=np.float64)
+    if reference_pixel == "center":
+        reference_pixel = (median_image.shape[1] / 2, median_image.shape[0] / 2)
+    with np.errstate(all="ignore"):
+        vals = median_image[np.isfinite(median_image)].flatten()
+        mad = np.median(np.abs(vals - np.median(vals)))
+        mad_cut = (1.4826 * mad * threshold) + np.nanmedian(median_image)
+        mask = np.nan_to_num(median_image) >= mad_cut
+    if reference_pixel is None or not mask.any():
+        return mask
+    labels = np.zeros(mask.shape, dtype=int)
+    current = 0
+    for r in range(mask.shape[0]):
+        for c in range(mask.shape[1]):
+            if mask[r, c] and labels[r, c] == 0:
+                current += 1
+                labels[r, c] = current
+                stack = [(r, c)]
+                while stack:
+                    a, b = stack.pop()
+                    for da, db in ((1, 0), (-1, 0), (0, 1), (0, -1)):
+                        aa, bb = a + da, b + db
+                        if (0 <= aa < mask.shape[0] and 0 <= bb < mask.shape[1] and mask[aa, bb]
+                                and labels[aa, bb] == 0):
+                            labels[aa, bb] = current
+                            stack.append((aa, bb))
+    args = np.argwhere(labels > 0)
+    dist = [np.hypot(a[0] - reference_pixel[1], a[1] - reference_pixel[0]) for a in args]
+    closest = args[int(np.argmin(dist))]
+    return labels == labels[closest[0], closest[1]]
 
 
 class PixelCube(object):
@@ -68,36 +103,9 @@ class PixelCube(object):
     def create_threshold_mask(self, threshold=3, reference_pixel="center"):
         """Pixels whose median flux exceeds median + threshold * 1.4826 * MAD; with a reference pixel, only the
         4-connected region closest to it (targetpixelfile.py:680-742)."""
-        if reference_pixel == "center":
-            reference_pixel = (self.shape[2] / 2, self.shape[1] / 2)
         with np.errstate(all="ignore"):
             median_image = np.nanmedian(np.asarray(self.flux, dtype=np.float64), axis=0)
-        vals = median_image[np.isfinite(median_image)].flatten()
-        mad = np.median(np.abs(vals - np.median(vals)))
-        mad_cut = (1.4826 * mad * threshold) + np.nanmedian(median_image)
-        mask = np.nan_to_num(median_image) >= mad_cut
-        if reference_pixel is None or not mask.any():
-            return mask
-        labels = np.zeros(mask.shape, dtype=int)
-        current = 0
-        for r in range(mask.shape[0]):
-            for c in range(mask.shape[1]):
-                if mask[r, c] and labels[r, c] == 0:
-                    current += 1
-                    labels[r, c] = current
-                    stack = [(r, c)]
-                    while stack:
-                        a, b = stack.pop()
-                        for da, db in ((1, 0), (-1, 0), (0, 1), (0, -1)):
-                            aa, bb = a + da, b + db
-                            if (0 <= aa < mask.shape[0] and 0 <= bb < mask.shape[1] and mask[aa, bb]
-                                    and labels[aa, bb] == 0):
-                                labels[aa, bb] = current
-                                stack.append((aa, bb))
-        args = np.argwhere(labels > 0)
-        dist = [np.hypot(a[0] - reference_pixel[1], a[1] - reference_pixel[0]) for a in args]
-        closest = args[int(np.argmin(dist))]
-        return labels == labels[closest[0], closest[1]]
+        return threshold_mask_from_median_image(median_image, threshold, reference_pixel)
 
     def _parse_aperture_mask(self, aperture_mask):
         """'all' / None, 'threshold', 'background' (= not threshold), 'empty', or a boolean (row, column) array
@@ -215,6 +223,53 @@ def _percentile_knots(time, n_knots, degree):
         raise ValueError("df={} is too small for degree={}; must be >= {}".format(n_knots, degree, order))
     inner = np.percentile(time, np.linspace(0, 100, n_inner + 2)[1:-1]) if n_inner > 0 else np.zeros(0)
     return np.concatenate([[np.min(time)], inner, [np.max(time)]])
+
+
+def _percentile_knot_plan(n, n_knots, degree):
+    """Where ``_percentile_knots`` finds its interior knots in ``n`` NON-DECREASING times: (lo int32[n_inner], g float64[n_inner])
+    with knot_k = lerp(t[lo_k], t[min(lo_k + 1, n - 1)], g_k) — np.percentile's 'linear' method (virtual index (n - 1) q,
+    numpy/lib/_function_base_impl.py ``_quantile``).  Depends on n and the knot count only: the device gathers and lerps."""
+    order = degree + 1
+    n_inner = n_knots - order
+    if n_inner < 0:
+        raise ValueError("df={} is too small for degree={}; must be >= {}".format(n_knots, degree, order))
+    q = np.true_divide(np.linspace(0, 100, n_inner + 2)[1:-1], np.float64(100))
+    vi = (n - 1) * q
+    lo = np.floor(vi)
+    above = vi >= n - 1
+    lo[above] = n - 1
+    g = vi - lo
+    g[above] = 0.0
+    return lo.astype(np.int32), np.ascontiguousarray(g, dtype=np.float64)
+
+
+def _knots_from_plan(time, lo, g):
+    """[t[0], numpy's _lerp(t[lo], t[lo + 1], g) ..., t[-1]]: the arithmetic of the device's knot gather, in numpy."""
+    time = np.asarray(time, dtype=np.float64)
+    a, b = time[lo], time[np.minimum(lo + 1, len(time) - 1)]
+    d = b - a
+    inner = np.where(g >= 0.5, b - d * (1 - g), a + d * g)
+    return np.concatenate([[time[0]], inner, [time[-1]]])
+
+
+def _sequential_aperture_sums(flux, flux_err, ap):
+    """``PixelCube._aperture_sums`` for float32 cubes written as the loop the device runs (``cube_aperture_kernel``): per
+    cadence the aperture's pixels one after the other in row-major order in float32, NaN pixels (and NaN e * e) skipped,
+    flux NaN where no aperture pixel is finite or the whole image is 0, flux_err = sqrt(sum(e * e))."""
+    flux, flux_err = np.asarray(flux, dtype=np.float32), np.asarray(flux_err, dtype=np.float32)
+    n = flux.shape[0]
+    f2, e2 = flux.reshape(n, -1), flux_err.reshape(n, -1)
+    acc_f, acc_e = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+    anyfinite = np.zeros(n, dtype=bool)
+    with np.errstate(all="ignore"):
+        for p in np.flatnonzero(np.asarray(ap, dtype=bool).reshape(-1)):
+            v = f2[:, p]
+            acc_f = np.where(np.isnan(v), acc_f, acc_f + v).astype(np.float32)
+            anyfinite |= np.isfinite(v)
+            sq = (e2[:, p] * e2[:, p]).astype(np.float32)
+            acc_e = np.where(np.isnan(sq), acc_e, acc_e + sq).astype(np.float32)
+        acc_f[~anyfinite | np.all(f2 == 0, axis=1)] = np.nan
+        return acc_f, np.sqrt(acc_e)
 
 
 def _finite_columns(cube2d):

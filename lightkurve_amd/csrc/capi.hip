@@ -668,6 +668,70 @@ int lk_pld_correct_batch(lk_handle *h, int B, int N, int P, int Pb, const float 
     return io.finish();
 }
 
+// lk_pld_correct_batch on device pointers and a stream.  X, prior_sigma and prior_mu are the CALLER's device scratch, not
+// h->staging: a later host-pointer call on this handle re-carves the staging arena while `stream` may still read them.
+int lk_pld_correct_batch_dev(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
+                             const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
+                             int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, const double *y,
+                             const double *err, const uint8_t *cadence_mask, double clip_sigma, int niters, double *X,
+                             double *prior_sigma, double *prior_mu, double *w, double *model, uint8_t *outlier,
+                             double *spline_part, double *corrected, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 1 && N >= 2 && P >= 0 && Pb >= 1 && K >= 1, "bad shapes");
+    LK_REQUIRE(bkg_pix && lc_flux && time && knots && y && w && model && outlier, "NULL buffer");
+    LK_REQUIRE(X && prior_sigma && prior_mu, "NULL scratch (X: B x N x K, prior_sigma and prior_mu: B x K doubles)");
+    LK_REQUIRE(n_knots + 1 <= K, "K=%d is narrower than the spline block (%d columns)", K, n_knots + 1);
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool has_pld = P > 0 && pld_pix != nullptr;
+    LK_HIP_CHECK(hipMemsetAsync(prior_mu, 0, (size_t)B * K * 8, st));   // prior_mu = 0 for every PLD column
+    int rc = lk::pld_design_launch(h, B, N, has_pld ? P : 0, Pb, has_pld ? pld_pix : nullptr, bkg_pix, lc_flux, time, knots,
+                                   n_inner, pld_order, pca_components, n_knots, spline_degree, normalize_bkg, K, X, prior_sigma,
+                                   st);
+    if (rc) return rc;
+    std::vector<int64_t> off((size_t)B + 1);
+    for (int b = 0; b <= B; ++b) off[b] = (int64_t)b * N;
+    rc = lk::regress_launch(h, B, off.data(), K, X, y, err, cadence_mask, prior_mu, prior_sigma, clip_sigma, niters, w, model,
+                            outlier, st);
+    if (rc) return rc;
+    if (spline_part) {
+        rc = lk::model_part_launch(h, B, N, K, K - (n_knots + 1), K, X, w, spline_part, st);
+        if (rc) return rc;
+    }
+    if (corrected) return lk::pld_corrected_launch(h, B, N, y, model, spline_part, corrected, st);
+    return LK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ resident pixel cubes
+int lk_cube_aperture_batch_dev(lk_handle *h, int B, int N, int npix, const float *flux, const float *flux_err,
+                               const uint8_t *mask, int mask_stride, float *flux_out, float *err_out, uint8_t *keep_out,
+                               int64_t *kept_host, int64_t *nonfinite_host, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_aperture_launch(h, B, N, npix, flux, flux_err, mask, mask_stride, flux_out, err_out, keep_out, kept_host,
+                                    nonfinite_host, static_cast<hipStream_t>(stream));
+}
+
+int lk_cube_median_image_batch_dev(lk_handle *h, int B, int N, int npix, const float *cube, const uint8_t *keep,
+                                   double *median, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_median_image_launch(h, B, N, npix, cube, keep, median, static_cast<hipStream_t>(stream));
+}
+
+int lk_pld_gather_batch_dev(lk_handle *h, int B, int N, int npix, int n, const float *cube, const double *time,
+                            const float *flux32, const float *err32, const uint8_t *keep, int P, const int32_t *pld_idx_host,
+                            int pld_idx_stride, int Pb, const int32_t *bkg_idx_host, int bkg_idx_stride, int n_inner,
+                            const int32_t *knot_lo_host, const double *knot_g_host, double *t_out, double *y_out,
+                            double *err_out, float *lcf_out, float *pld_out, float *bkg_out, double *knots_out,
+                            int *nonfinite_host, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::pld_gather_launch(h, B, N, npix, n, cube, time, flux32, err32, keep, P, pld_idx_host, pld_idx_stride, Pb,
+                                 bkg_idx_host, bkg_idx_stride, n_inner, knot_lo_host, knot_g_host, t_out, y_out, err_out,
+                                 lcf_out, pld_out, bkg_out, knots_out, nonfinite_host, static_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------------------------ design-matrix operations
 int lk_pca_batch_dev(lk_handle *h, int B, int N, int P, int k, const double *A, double *U, void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");

@@ -185,6 +185,18 @@ int bin_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, 
                hipStream_t stream);
 int pg_acf2d_launch(lk_handle *h, int B, int64_t M, const double *power, int n_win, const int *win_start_host, int W,
                     double *acf2d, double *metric, hipStream_t stream);
+int cube_aperture_launch(lk_handle *h, int B, int N, int npix, const float *flux, const float *flux_err, const uint8_t *mask,
+                         int mask_stride, float *flux_out, float *err_out, uint8_t *keep_out, int64_t *kept_host,
+                         int64_t *nonfinite_host, hipStream_t stream);
+int cube_median_image_launch(lk_handle *h, int B, int N, int npix, const float *cube, const uint8_t *keep, double *median,
+                             hipStream_t stream);
+int pld_gather_launch(lk_handle *h, int B, int N, int npix, int n, const float *cube, const double *time, const float *flux32,
+                      const float *err32, const uint8_t *keep, int P, const int32_t *pld_idx_host, int pld_idx_stride, int Pb,
+                      const int32_t *bkg_idx_host, int bkg_idx_stride, int n_inner, const int32_t *knot_lo_host,
+                      const double *knot_g_host, double *t_out, double *y_out, double *err_out, float *lcf_out, float *pld_out,
+                      float *bkg_out, double *knots_out, int *nonfinite_host, hipStream_t stream);
+int pld_corrected_launch(lk_handle *h, int B, int N, const double *y, const double *model, const double *spline, double *out,
+                         hipStream_t stream);
 int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *y, const double *dy,
                   double f0, double df, int64_t M, int fit_mean, int center_data, int normalization,
                   const double *scale, int oversampling, double *power, hipStream_t stream, double *max_out = nullptr,

@@ -1,0 +1,382 @@
+// pixcube.hip — what PLDCorrector does to a target-pixel cutout BEFORE the design matrix, for B same-shaped float32 cubes
+// [B][N][npix] resident in HBM (lightkurve_amd/device.py: DevicePixelCubeBatch):
+//   cube_aperture   simple aperture photometry (TargetPixelFile.to_lightcurve, flux_method='sum',
+//                   src/lightkurve/targetpixelfile.py:868-923) + the NaN-cadence flags of PLDCorrector.__init__
+//                   (correctors/pldcorrector.py:109-120);
+//   cube_median     the per-pixel nanmedian image behind create_threshold_mask (targetpixelfile.py:680-742);
+//   cube_compact / cube_gather   the compaction tpf[~nan_mask], the pixel series of the PLD / background apertures
+//                   (pldcorrector.py:203-227) and the spline's percentile knots;
+//   pld_corrected   corrected = (y - model) + (spline - median(spline))   (pldcorrector.py:418-420).
+// This file is compiled with -ffp-contract=off: the float32 aperture sums must round every product and every sum on its
+// own, in pixel order, to equal numpy's (see cube_aperture_kernel), and the knot lerp numpy's _lerp.
+#include "lk_common.hpp"
+
+#include <algorithm>
+
+#include "block_select.hpp"
+
+namespace lk {
+
+constexpr int AP_T = 64;       // cadences per workgroup: one lane of wave 0 (flux) and of wave 1 (flux_err) each
+constexpr int AP_WMAX = 127;   // pixel columns per LDS chunk: 2 tiles x 64 rows x 127 dwords + the mask < 64 KB
+constexpr int MED_G = 16;      // adjacent pixels per workgroup of the median image: one 64-byte segment of every cadence row
+
+// rows x npix floats that are CONTIGUOUS in global memory -> tile[row * pitch + column]: 16-byte loads once the
+// address is aligned, scalar head and tail.
+__device__ __forceinline__ void stage_contiguous(const float *__restrict__ g, float *__restrict__ tile, int total, int npix,
+                                                 int pitch) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int mis = (int)((reinterpret_cast<uintptr_t>(g) >> 2) & 3);
+    const int head = min(total, (4 - mis) & 3);
+    if (tid < head) tile[(tid / npix) * pitch + tid % npix] = g[tid];
+    const int nvec = (total - head) >> 2;
+    const float4 *gv = reinterpret_cast<const float4 *>(g + head);
+#pragma unroll 4
+    for (int v = tid; v < nvec; v += nt) {
+        const float4 x = gv[v];
+        const int i = head + 4 * v;
+        int r = i / npix, c = i - r * npix;
+        const float e[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            tile[r * pitch + c] = e[k];
+            if (++c == npix) {
+                c = 0;
+                ++r;
+            }
+        }
+    }
+    const int i = head + 4 * nvec + tid;
+    if (i < total) tile[(i / npix) * pitch + i % npix] = g[i];
+}
+
+// columns [p0, p0 + w) of rows x npix floats -> tile[row * pitch + column - p0] (cutouts wider than one chunk)
+__device__ __forceinline__ void stage_columns(const float *__restrict__ g, float *__restrict__ tile, int rows, int npix, int p0,
+                                              int w, int pitch) {
+    for (int i = threadIdx.x; i < rows * w; i += blockDim.x) {
+        const int r = i / w, c = i - r * w;
+        tile[r * pitch + c] = g[(size_t)r * npix + p0 + c];
+    }
+}
+
+// Aperture sums of AP_T consecutive cadences of one cutout.  numpy adds the aperture's pixels of a cadence ONE AFTER THE
+// OTHER in row-major pixel order, in float32 (PixelCube._aperture_sums: `cube[:, ap]` is laid out pixel-major, so the
+// reduction over the pixels walks whole cadence vectors); flux_err = sqrt_f32(sum_f32(e * e rounded to float32)).  NaN
+// pixels (and NaN e * e) count as 0; the flux is NaN when no aperture pixel is finite, or when EVERY pixel of the cadence
+// image is 0.  So: no tree over the pixels — a lane owns a cadence and walks its row.  Walking rows in global memory would
+// put 4 * npix bytes between the lanes of a load; instead the tile (contiguous in memory: cadences x pixels) is staged
+// through LDS with coalesced 16-byte loads and every lane walks its own LDS row.  ds_read_b32 conflicts are per 32-lane
+// half on bank (address / 4) mod 32: the row pitch is odd, so the 32 rows of a half sit on 32 different banks.
+// Wave 0 sums the flux tile and wave 1 the flux_err tile; waves 2-3 only help staging.  keep = !(isnan(flux) |
+// isnan(flux_err)); counts[b] += kept cadences, counts[B + b] += kept cadences with a non-finite pixel anywhere in the image.
+__global__ __launch_bounds__(256) void cube_aperture_kernel(const float *__restrict__ flux, const float *__restrict__ ferr,
+                                                            const uint8_t *__restrict__ mask, int mask_stride, int B, int N,
+                                                            int npix, int W, int pitch, float *__restrict__ flux_out,
+                                                            float *__restrict__ err_out, uint8_t *__restrict__ keep_out,
+                                                            unsigned long long *__restrict__ counts) {
+    extern __shared__ __align__(16) float ap_tile[];
+    __shared__ float s_err[AP_T];
+    float *tf = ap_tile, *te = ap_tile + AP_T * pitch;
+    uint8_t *sm = reinterpret_cast<uint8_t *>(ap_tile + 2 * AP_T * pitch);
+    const int b = blockIdx.y, c0 = blockIdx.x * AP_T, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int rows = min(AP_T, N - c0);
+    const float *gf = flux + ((size_t)b * N + c0) * npix, *ge = ferr + ((size_t)b * N + c0) * npix;
+    const uint8_t *m = mask + (size_t)b * mask_stride;
+    float acc = 0.0f;
+    bool allzero = true, anyfinite = false, bad = false;
+    for (int p0 = 0; p0 < npix; p0 += W) {
+        const int w = min(W, npix - p0);
+        if (p0) __syncthreads();  // the previous chunk has been walked
+        if (w == npix) {
+            stage_contiguous(gf, tf, rows * npix, npix, pitch);
+            stage_contiguous(ge, te, rows * npix, npix, pitch);
+        } else {
+            stage_columns(gf, tf, rows, npix, p0, w, pitch);
+            stage_columns(ge, te, rows, npix, p0, w, pitch);
+        }
+        for (int i = tid; i < w; i += 256) sm[i] = m[p0 + i];
+        __syncthreads();
+        if (wave == 0 && lane < rows) {
+            const float *row = tf + lane * pitch;
+            for (int p = 0; p < w; ++p) {
+                const float v = row[p];
+                allzero = allzero && v == 0.0f;
+                bad = bad || !isfinite(v);
+                if (sm[p]) {
+                    if (!isnan(v)) acc = acc + v;
+                    anyfinite = anyfinite || isfinite(v);
+                }
+            }
+        } else if (wave == 1 && lane < rows) {
+            const float *row = te + lane * pitch;
+            for (int p = 0; p < w; ++p)
+                if (sm[p]) {
+                    const float e2 = row[p] * row[p];
+                    if (!isnan(e2)) acc = acc + e2;
+                }
+        }
+    }
+    if (wave == 1 && lane < rows) s_err[lane] = __fsqrt_rn(acc);
+    __syncthreads();
+    if (wave == 0) {
+        bool keep = false;
+        if (lane < rows) {
+            const float f = (anyfinite && !allzero) ? acc : __int_as_float(0x7fc00000);
+            const float e = s_err[lane];
+            keep = !(isnan(f) || isnan(e));
+            const size_t o = (size_t)b * N + c0 + lane;
+            flux_out[o] = f;
+            err_out[o] = e;
+            keep_out[o] = keep ? 1 : 0;
+        }
+        const unsigned long long kept = __ballot(keep), dirty = __ballot(keep && bad);
+        if (lane == 0) {
+            if (kept) atomicAdd(&counts[b], (unsigned long long)__popcll(kept));
+            if (dirty) atomicAdd(&counts[B + b], (unsigned long long)__popcll(dirty));
+        }
+    }
+}
+
+// np.nanmedian(cube.astype(float64), axis=0) of the cadences with keep != 0 (all of them when keep is NULL): exact order
+// statistics (block_select.hpp), the mean of the two middle values for an even count, NaN for a pixel that has no value.
+// The column of one pixel is strided by npix floats, so a workgroup owns MED_G = 16 ADJACENT pixels of one cutout and
+// selects them one after the other straight from global memory: the 16 columns share the same 64-byte segment of every
+// cadence row, so only the first pixel's passes go to HBM and the other fifteen's hit the L2 (N x 64 B per workgroup).
+// Chosen over an LDS-staged tile because this kernel only runs for data-dependent mask specs and a staged column set
+// would cap N at what fits 160 KB; the select itself makes 9 passes over a column either way.
+__global__ __launch_bounds__(256) void cube_median_image_kernel(const float *__restrict__ cube, const uint8_t *__restrict__ keep,
+                                                                int N, int npix, double *__restrict__ med) {
+    __shared__ unsigned long long sh[256];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const uint8_t *kp = keep ? keep + (size_t)b * N : nullptr;
+    const int p1 = min(npix, (int)(blockIdx.x + 1) * MED_G);
+    for (int p = blockIdx.x * MED_G; p < p1; ++p) {
+        const float *col = cube + (size_t)b * N * npix + p;
+        auto val = [&](int i) { return (double)col[(size_t)i * npix]; };
+        auto kf = [&](int i) { return (!kp || kp[i]) && !isnan(col[(size_t)i * npix]); };
+        long long cnt = 0;
+        for (int i = tid; i < N; i += 256) cnt += kf(i) ? 1 : 0;
+        cnt = block_count_dyn(cnt, reinterpret_cast<long long *>(sh));
+        const double r = block_median(N, cnt, val, kf, sh);
+        if (tid == 0) med[(size_t)b * npix + p] = r;
+    }
+}
+
+// One workgroup per cutout: exclusive scan of keep -> src[j] = cadence of the j-th kept one, the compacted time / SAP flux
+// / error columns (float64 = the float32 sums widened; lcf = the float32 flux itself) and the spline knots
+// [t[0], lerp(t[lo], t[lo + 1], g) per interior knot, t[n - 1]] (np.percentile of non-decreasing times: numpy's _lerp,
+// a + (b - a) g, replaced by b - (b - a)(1 - g) where g >= 0.5).  Nothing is written past n kept cadences; a count
+// other than n raises bit 1 of *flags.
+__global__ __launch_bounds__(256) void cube_compact_kernel(const uint8_t *__restrict__ keep, const double *__restrict__ time,
+                                                           const float *__restrict__ f32, const float *__restrict__ e32, int N,
+                                                           int n, int *__restrict__ src, double *__restrict__ t_out,
+                                                           double *__restrict__ y_out, double *__restrict__ e_out,
+                                                           float *__restrict__ lcf_out, int n_inner,
+                                                           const int *__restrict__ knot_lo, const double *__restrict__ knot_g,
+                                                           double *__restrict__ knots, int *__restrict__ flags) {
+    __shared__ int s_cnt[4];
+    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const size_t in0 = (size_t)b * N, out0 = (size_t)b * n;
+    int base = 0;
+    for (int c0 = 0; c0 < N; c0 += 256) {
+        const int i = c0 + tid;
+        const bool k = i < N && keep[in0 + i] != 0;
+        const unsigned long long bal = __ballot(k);
+        if (lane == 0) s_cnt[wave] = __popcll(bal);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) before += s_cnt[w];
+            all += s_cnt[w];
+        }
+        const int pos = base + before + __popcll(bal & ((1ull << lane) - 1ull));
+        if (k && pos < n) {
+            src[out0 + pos] = i;
+            if (t_out) t_out[out0 + pos] = time[in0 + i];
+            if (y_out) y_out[out0 + pos] = (double)f32[in0 + i];
+            if (e_out) e_out[out0 + pos] = (double)e32[in0 + i];
+            if (lcf_out) lcf_out[out0 + pos] = f32[in0 + i];
+        }
+        base += all;
+        __syncthreads();
+    }
+    if (base != n) {
+        if (tid == 0) atomicOr(flags, 2);
+        return;
+    }
+    if (!knots) return;
+    __syncthreads();  // this workgroup's own t_out is read back below
+    const double *t = t_out + out0;
+    for (int k = tid; k < n_inner + 2; k += 256) {
+        double r;
+        if (k == 0) {
+            r = t[0];
+        } else if (k == n_inner + 1) {
+            r = t[n - 1];
+        } else {
+            const int lo = knot_lo[k - 1];
+            const double g = knot_g[k - 1], a = t[lo], bb = t[min(lo + 1, n - 1)], d = bb - a;
+            r = g >= 0.5 ? bb - d * (1.0 - g) : a + d * g;
+        }
+        knots[(size_t)b * (n_inner + 2) + k] = r;
+    }
+}
+
+// out[b][j][q] = cube[b][src[b][j]][idx[b][q]] (idx NULL: every pixel in place); a value that is not finite raises bit 0 of
+// *flags.
+__global__ __launch_bounds__(256) void cube_gather_kernel(const float *__restrict__ cube, const int *__restrict__ src,
+                                                          const int *__restrict__ idx, int idx_stride, int N, int npix, int n,
+                                                          int P, float *__restrict__ out, int *__restrict__ flags) {
+    const int b = blockIdx.y;
+    const long long total = (long long)n * P;
+    const float *cb = cube + (size_t)b * N * npix;
+    const int *sb = src + (size_t)b * n;
+    const int *ib = idx ? idx + (size_t)b * idx_stride : nullptr;
+    if (*reinterpret_cast<volatile int *>(flags) & 2) return;  // cube_compact_kernel did not fill src (keep does not hold n)
+    bool bad = false;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int j = (int)(i / P), q = (int)(i - (long long)j * P);
+        const int row = sb[j];
+        if ((unsigned)row >= (unsigned)N) continue;
+        const float v = cb[(size_t)row * npix + (ib ? ib[q] : q)];
+        out[(size_t)b * total + i] = v;
+        bad = bad || !isfinite(v);
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flags, 1);
+}
+
+// out = (y - model) + (spline - np.median(spline)) per cutout, or y - model without a spline part
+__global__ __launch_bounds__(1024) void pld_corrected_kernel(const double *__restrict__ y, const double *__restrict__ model,
+                                                             const double *__restrict__ spline, int N, double *__restrict__ out) {
+    __shared__ unsigned long long sh[1024];
+    const size_t o = (size_t)blockIdx.x * N;
+    const int tid = threadIdx.x;
+    double med = 0.0;
+    if (spline) {
+        auto val = [&](int i) { return spline[o + i]; };
+        auto keep = [&](int) { return true; };
+        med = block_median(N, (long long)N, val, keep, sh);
+    }
+    for (int i = tid; i < N; i += 1024) {
+        const double d = y[o + i] - model[o + i];
+        out[o + i] = spline ? d + (spline[o + i] - med) : d;
+    }
+}
+
+int cube_aperture_launch(lk_handle *h, int B, int N, int npix, const float *flux, const float *flux_err, const uint8_t *mask,
+                         int mask_stride, float *flux_out, float *err_out, uint8_t *keep_out, int64_t *kept_host,
+                         int64_t *nonfinite_host, hipStream_t stream) {
+    LK_REQUIRE(B >= 1 && B <= 65535 && N >= 2 && npix >= 1, "need 1 <= B <= 65535, N >= 2, npix >= 1");
+    LK_REQUIRE(flux && flux_err && mask && flux_out && err_out && keep_out && kept_host, "NULL buffer");
+    LK_REQUIRE(mask_stride == 0 || mask_stride == npix, "mask_stride must be 0 (one mask for the batch) or npix");
+    LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
+    h->ws.reset();
+    int rc = h->ws.reserve((size_t)2 * B * 8 + 4096);
+    if (rc) return rc;
+    unsigned long long *d_cnt = (unsigned long long *)h->ws.alloc((size_t)2 * B * 8);
+    LK_HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t)2 * B * 8, stream));
+    const int W = std::min(npix, AP_WMAX), pitch = W | 1;
+    const size_t lds = (size_t)2 * AP_T * pitch * 4 + (size_t)((W + 15) & ~15);
+    hipLaunchKernelGGL(cube_aperture_kernel, dim3((N + AP_T - 1) / AP_T, B), dim3(256), lds, stream, flux, flux_err, mask,
+                       mask_stride, B, N, npix, W, pitch, flux_out, err_out, keep_out, d_cnt);
+    LK_HIP_CHECK(hipGetLastError());
+    std::vector<int64_t> cnt((size_t)2 * B);
+    LK_HIP_CHECK(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)2 * B * 8, hipMemcpyDeviceToHost, stream));
+    LK_HIP_CHECK(hipStreamSynchronize(stream));
+    for (int b = 0; b < B; ++b) {
+        kept_host[b] = cnt[b];
+        if (nonfinite_host) nonfinite_host[b] = cnt[(size_t)B + b];
+    }
+    return LK_OK;
+}
+
+int cube_median_image_launch(lk_handle *h, int B, int N, int npix, const float *cube, const uint8_t *keep, double *median,
+                             hipStream_t stream) {
+    (void)h;
+    LK_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && npix >= 1, "need 1 <= B <= 65535, N >= 1, npix >= 1");
+    LK_REQUIRE(cube && median, "NULL buffer");
+    LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
+    hipLaunchKernelGGL(cube_median_image_kernel, dim3((npix + MED_G - 1) / MED_G, B), dim3(256), 0, stream, cube, keep, N, npix,
+                       median);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+int pld_gather_launch(lk_handle *h, int B, int N, int npix, int n, const float *cube, const double *time, const float *flux32,
+                      const float *err32, const uint8_t *keep, int P, const int32_t *pld_idx_host, int pld_idx_stride, int Pb,
+                      const int32_t *bkg_idx_host, int bkg_idx_stride, int n_inner, const int32_t *knot_lo_host,
+                      const double *knot_g_host, double *t_out, double *y_out, double *err_out, float *lcf_out, float *pld_out,
+                      float *bkg_out, double *knots_out, int *nonfinite_host, hipStream_t stream) {
+    LK_REQUIRE(B >= 1 && B <= 65535 && N >= 2 && npix >= 1 && n >= 1 && n <= N, "need 1 <= B <= 65535, N >= 2, npix >= 1, 1 <= n <= N");
+    LK_REQUIRE(cube && keep && nonfinite_host, "NULL buffer");
+    LK_REQUIRE((!y_out && !lcf_out) || flux32, "the SAP flux columns need flux32");
+    LK_REQUIRE(!err_out || err32, "the SAP error column needs err32");
+    LK_REQUIRE(!t_out || time, "the compacted times need time");
+    LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
+    LK_REQUIRE(P >= 0 && P <= npix && Pb >= 0 && Pb <= npix, "P and Pb must be between 0 and npix");
+    LK_REQUIRE(pld_idx_host || P == 0 || P == npix, "pld_idx may only be NULL for all pixels or none");
+    LK_REQUIRE(bkg_idx_host || Pb == 0 || Pb == npix, "bkg_idx may only be NULL for all pixels or none");
+    LK_REQUIRE(pld_idx_stride == 0 || pld_idx_stride == P, "pld_idx_stride must be 0 (shared) or P");
+    LK_REQUIRE(bkg_idx_stride == 0 || bkg_idx_stride == Pb, "bkg_idx_stride must be 0 (shared) or Pb");
+    LK_REQUIRE(n_inner >= 0, "n_inner must be >= 0");
+    if (knots_out) {
+        LK_REQUIRE(t_out, "the knots are taken from the compacted times: t_out is NULL");
+        LK_REQUIRE(n_inner == 0 || (knot_lo_host && knot_g_host), "NULL knot plan");
+        for (int k = 0; k < n_inner; ++k)
+            LK_REQUIRE(knot_lo_host[k] >= 0 && knot_lo_host[k] < n && knot_g_host[k] >= 0.0 && knot_g_host[k] <= 1.0,
+                       "knot %d: index %d / weight %g outside the %d kept cadences", k, knot_lo_host[k], knot_g_host[k], n);
+    }
+    const size_t n_pi = pld_idx_host ? (size_t)(pld_idx_stride ? B : 1) * P : 0;
+    const size_t n_bi = bkg_idx_host ? (size_t)(bkg_idx_stride ? B : 1) * Pb : 0;
+    for (size_t i = 0; i < n_pi; ++i)
+        LK_REQUIRE(pld_idx_host[i] >= 0 && pld_idx_host[i] < npix, "pld_idx[%zu] = %d is not a pixel of the cutout", i, pld_idx_host[i]);
+    for (size_t i = 0; i < n_bi; ++i)
+        LK_REQUIRE(bkg_idx_host[i] >= 0 && bkg_idx_host[i] < npix, "bkg_idx[%zu] = %d is not a pixel of the cutout", i, bkg_idx_host[i]);
+    const size_t nk = knots_out ? (size_t)n_inner : 0;
+    h->ws.reset();
+    int rc = h->ws.reserve((size_t)B * n * 4 + (n_pi + n_bi) * 4 + nk * 12 + 8 * 256 + 4096);
+    if (rc) return rc;
+    int *d_src = (int *)h->ws.alloc((size_t)B * n * 4);
+    int *d_pi = n_pi ? (int *)h->ws.alloc(n_pi * 4) : nullptr, *d_bi = n_bi ? (int *)h->ws.alloc(n_bi * 4) : nullptr;
+    int *d_klo = nk ? (int *)h->ws.alloc(nk * 4) : nullptr;
+    double *d_kg = nk ? (double *)h->ws.alloc(nk * 8) : nullptr;
+    int *d_flags = (int *)h->ws.alloc(4);
+    if (n_pi && (rc = h->stage.copy(d_pi, pld_idx_host, n_pi * 4, stream))) return rc;
+    if (n_bi && (rc = h->stage.copy(d_bi, bkg_idx_host, n_bi * 4, stream))) return rc;
+    if (nk && (rc = h->stage.copy(d_klo, knot_lo_host, nk * 4, stream))) return rc;
+    if (nk && (rc = h->stage.copy(d_kg, knot_g_host, nk * 8, stream))) return rc;
+    LK_HIP_CHECK(hipMemsetAsync(d_flags, 0, 4, stream));
+    hipLaunchKernelGGL(cube_compact_kernel, dim3(B), dim3(256), 0, stream, keep, time, flux32, err32, N, n, d_src, t_out, y_out,
+                       err_out, lcf_out, n_inner, d_klo, d_kg, knots_out, d_flags);
+    LK_HIP_CHECK(hipGetLastError());
+    // (no output: the caller uses the resident cube itself as that block — all pixels, no cadence dropped — and has the
+    // finite-pixel count of cube_aperture instead)
+    const int gx = (int)std::min<int64_t>(((int64_t)n * std::max(P, Pb) + 1023) / 1024 + 1, 4096);
+    if (P > 0 && pld_out) {
+        hipLaunchKernelGGL(cube_gather_kernel, dim3(gx, B), dim3(256), 0, stream, cube, (const int *)d_src, (const int *)d_pi,
+                           pld_idx_stride, N, npix, n, P, pld_out, d_flags);
+        LK_HIP_CHECK(hipGetLastError());
+    }
+    if (Pb > 0 && bkg_out) {
+        hipLaunchKernelGGL(cube_gather_kernel, dim3(gx, B), dim3(256), 0, stream, cube, (const int *)d_src, (const int *)d_bi,
+                           bkg_idx_stride, N, npix, n, Pb, bkg_out, d_flags);
+        LK_HIP_CHECK(hipGetLastError());
+    }
+    int flags = 0;
+    LK_HIP_CHECK(hipMemcpyAsync(&flags, d_flags, 4, hipMemcpyDeviceToHost, stream));
+    LK_HIP_CHECK(hipStreamSynchronize(stream));
+    LK_REQUIRE(!(flags & 2), "keep does not flag exactly n = %d cadences in every cutout", n);
+    *nonfinite_host = flags & 1;
+    return LK_OK;
+}
+
+int pld_corrected_launch(lk_handle *h, int B, int N, const double *y, const double *model, const double *spline, double *out,
+                         hipStream_t stream) {
+    (void)h;
+    LK_REQUIRE(B >= 1 && N >= 1 && y && model && out, "bad arguments");
+    hipLaunchKernelGGL(pld_corrected_kernel, dim3(B), dim3(1024), 0, stream, y, model, spline, N, out);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+}  // namespace lk

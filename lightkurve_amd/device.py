@@ -28,7 +28,8 @@ import numpy as np
 from . import _capi
 from . import packed
 
-__all__ = ["DeviceBuffer", "DeviceLightCurveBatch", "DeviceFoldedBatch", "DeviceBLSResult", "release_device_pool"]
+__all__ = ["DeviceBuffer", "DeviceLightCurveBatch", "DeviceFoldedBatch", "DeviceBLSResult", "DevicePixelCubeBatch",
+           "release_device_pool"]
 
 _vp = ctypes.c_void_p
 _ip = ctypes.POINTER(ctypes.c_int64)
@@ -648,3 +649,374 @@ class DeviceBLSResult(object):
         got = {k: vals[i * B:(i + 1) * B] for i, k in enumerate(rows)}
         return dict(max_power=mx, argmax=am, period=self.period[a], transit_time=got["transit_time"] + t_ref,
                     duration=got["duration"], depth=got["depth"])
+
+
+# ------------------------------------------------------------------------------------------------ pixel cubes
+class DevicePixelCubeBatch(object):
+    """B same-shaped target-pixel cutouts IN HBM — the input of ``PLDCorrector`` as ``DeviceLightCurveBatch`` is the input of
+    the light-curve chain: ``d_flux`` / ``d_flux_err`` float32 [B][N][npix] (npix = ny * nx, row-major pixels: the layout
+    ``lk_fits_unpack_cube`` writes per column), ``d_time`` float64 [B][N], all on ONE stream of the process's handle.
+    ``pld_correct_batch`` does, per cutout and on the host: aperture sums, NaN-cadence removal, pixel gathers, percentile
+    knots, packing, upload.  Here the cubes go up once and ``lk_cube_aperture_batch_dev`` -> ``lk_pld_gather_batch_dev`` ->
+    ``lk_pld_correct_batch_dev`` run on them; the results are the same bits (the same PLD kernels see the same numbers).
+
+        cubes = DevicePixelCubeBatch.from_cubes(list_of_PixelCube)        # or .from_fits(paths) / .from_arrays(t, flux, err)
+        corrected, outliers = cubes.pld_correct(pld_order=3, pca_components=16)
+        lcs, d_outl = cubes.pld_correct(to_host=False)                    # DeviceLightCurveBatch: .flatten(...) ... follow
+
+    float32 cubes only; every cutout of a call must keep the same number of cadences; ``pld_correct`` needs times that are
+    finite and non-decreasing per cutout (the knots are gathered from sorted times) — ``pld_correct_batch`` takes what does
+    not fit."""
+
+    def __init__(self, d_time, d_flux, d_flux_err, time, shape, meta=None, device=0, stream=0):
+        self.handle = _capi.Handle.get(device)
+        self.device = int(device)
+        self.stream = int(stream or 0)
+        self.d_time, self.d_flux, self.d_flux_err = d_time, d_flux, d_flux_err
+        self.shape = tuple(int(v) for v in shape)                   # (B, N, ny, nx)
+        B, N, ny, nx = self.shape
+        if d_time.capacity < B * N * 8 or d_flux.capacity < B * N * ny * nx * 4 or d_flux_err.capacity < B * N * ny * nx * 4:
+            raise ValueError("device buffer smaller than the batch it is said to hold")
+        self.time = np.ascontiguousarray(time, dtype=np.float64).reshape(B, N)      # host copy (B x N doubles)
+        # checked here, on the host's copy; raised by pld_correct — a file whose kept cadences lack a TIME (read as 0.0 like
+        # TargetPixelFile.time does) still round-trips and still has aperture photometry
+        self.is_sorted = _cube_times_sorted(self.time)
+        self.meta = list(meta) if meta is not None else [{} for _ in range(B)]
+        self._keep = []                                              # host staging the stream may still be reading
+
+    # ---------------------------------------------------------------- construction
+    @classmethod
+    def from_arrays(cls, time, flux, flux_err, meta=None, device=0, stream=0):
+        """H2D once: time[B, N], flux / flux_err [B, N, ny, nx] float32 (page-locked arrays go by DMA)."""
+        time, flux, flux_err = _check_cube_arrays(time, flux, flux_err)
+        h = _capi.Handle.get(device)
+        bufs, keep = [], []
+        for a, dt in ((time, np.float64), (flux, np.float32), (flux_err, np.float32)):
+            b, k = _upload(h, a, stream, dt)
+            bufs.append(b), keep.append(k)
+        out = cls(bufs[0], bufs[1], bufs[2], time, flux.shape, meta, device, stream)
+        out._keep = keep
+        return out
+
+    @classmethod
+    def from_cubes(cls, cubes, device=0, stream=0):
+        """From a list of ``PixelCube`` of one (N, ny, nx): one packing pass into the page-locked pool, one upload per column."""
+        cubes = list(cubes)
+        if not cubes:
+            raise ValueError("DevicePixelCubeBatch needs at least one cutout")
+        shape = cubes[0].shape
+        for c in cubes:
+            if c.flux.dtype != np.float32 or c.flux_err.dtype != np.float32:
+                raise TypeError("DevicePixelCubeBatch holds float32 cubes (got %s / %s); pld_correct_batch takes the others"
+                                % (c.flux.dtype, c.flux_err.dtype))
+            if c.shape != shape:
+                raise ValueError("DevicePixelCubeBatch needs cutouts of one shape (got %s and %s)" % (c.shape, shape))
+        B = len(cubes)
+
+        def staged(key, shp, dtype):
+            try:
+                return _capi.pinned_pool("devcube:" + key, int(np.prod(shp)), dtype).reshape(shp)
+            except (OSError, RuntimeError, MemoryError):
+                return np.empty(shp, dtype=dtype)
+
+        t = staged("t", (B, shape[0]), np.float64)
+        f, e = staged("f", (B,) + shape, np.float32), staged("e", (B,) + shape, np.float32)
+
+        def fill(b):
+            t[b], f[b], e[b] = cubes[b].time, cubes[b].flux, cubes[b].flux_err
+
+        packed._pmap(fill, [(b,) for b in range(B)])
+        out = cls.from_arrays(t, f, e, [dict(c.meta) for c in cubes], device, stream)
+        out.synchronize()              # the staging pool is reused by the next packing call
+        out.time = out.time.copy()
+        return out
+
+    @classmethod
+    def from_fits(cls, paths, quality_bitmask="default", device=0, stream=0):
+        """Target-pixel files of one shape and one number of kept cadences -> a resident batch (``PixelCube.from_fits``
+        without the way back: headers on the host, ``lk_fits_unpack_cube_dev`` per file in HBM, then a device-to-device
+        copy into that file's slice of the batch — the unpacker lays its columns out for the file's OWN row count, which is
+        only known to equal the batch's once its cadence selection has run)."""
+        from . import fitsio
+        paths = list(paths)
+        if not paths:
+            raise ValueError("DevicePixelCubeBatch needs at least one file")
+        h = _capi.Handle.get(device)
+        st = _vp(stream or None)
+        lib = _capi._lib
+        bufs, shape, meta = None, None, []
+        for b, path in enumerate(paths):
+            tab = fitsio.read_fits_table(path, ext=1)
+            pc = fitsio.pixel_columns(tab, columns=("flux", "flux_err"), quality_bitmask=quality_bitmask)
+            if pc["columns"] != ["flux", "flux_err"]:
+                raise ValueError("%s has no FLUX_ERR column" % path)
+            raw = np.ascontiguousarray(tab.raw, dtype=np.uint8)
+            n_rows, row_bytes = raw.shape
+            npix = int(pc["npix"])
+            d_raw = DeviceBuffer(h, raw.nbytes + 16)
+            d_raw.upload(raw.reshape(-1), stream)
+            d_t, d_q = DeviceBuffer(h, (n_rows + 1) * 8), DeviceBuffer(h, (n_rows + 2) * 4)
+            d_c = DeviceBuffer(h, (2 * n_rows * npix + 4) * 4)
+            cols = np.ascontiguousarray(pc["col_offsets"], dtype=np.int32)
+            kept = np.zeros(1, dtype=np.int64)
+            _capi._check(lib.lk_fits_unpack_cube_dev(
+                h._h, _vp(d_raw.ptr), int(row_bytes), int(n_rows), int(pc["off_time"]), int(pc["code_time"]),
+                int(pc["off_quality"]), int(pc["code_quality"]), ctypes.c_int64(int(pc["bitmask"])), int(bool(pc["keep_nan_time"])),
+                2, cols.ctypes.data_as(_i32p), npix, _vp(d_t.ptr), _vp(d_q.ptr), _vp(d_c.ptr), _off_ptr(kept), st))
+            N = int(kept[0])
+            cube_shape = (N,) + tuple(int(v) for v in pc["shape"])
+            if len(cube_shape) != 3:
+                raise ValueError("%s: the pixel columns are not images" % path)
+            if bufs is None:
+                if N < 2:
+                    raise ValueError("%s keeps %d cadences" % (path, N))
+                shape = cube_shape
+                B = len(paths)
+                bufs = (DeviceBuffer(h, B * N * 8), DeviceBuffer(h, B * N * npix * 4), DeviceBuffer(h, B * N * npix * 4))
+            elif cube_shape[1:] != shape[1:]:
+                raise ValueError("DevicePixelCubeBatch needs cutouts of one shape (got %s and %s)" % (cube_shape, shape))
+            elif N != shape[0]:
+                raise ValueError("DevicePixelCubeBatch.from_fits needs files that keep the same number of cadences "
+                                 "(%s keeps %d, %s keeps %d)" % (path, N, paths[0], shape[0]))
+            for dst, src, nbytes in ((bufs[0].ptr + b * N * 8, d_t.ptr, N * 8),
+                                     (bufs[1].ptr + b * N * npix * 4, d_c.ptr, N * npix * 4),
+                                     (bufs[2].ptr + b * N * npix * 4, d_c.ptr + n_rows * npix * 4, N * npix * 4)):
+                _capi._check(lib.lk_memcpy_d2d(h._h, _vp(dst), _vp(src), nbytes, st))
+            meta.append({"MISSION": tab.primary.get("MISSION", tab.primary.get("TELESCOP")),
+                         "TARGETID": tab.primary.get("KEPLERID", tab.primary.get("TICID")), "FILENAME": str(path),
+                         "QUALITY_BITMASK": quality_bitmask, "LABEL": tab.primary.get("OBJECT")})
+        B, N = len(paths), shape[0]
+        time = bufs[0].download(np.float64, B * N, stream=stream)       # (synchronises; the per-file buffers may go)
+        return cls(bufs[0], bufs[1], bufs[2], time, (B,) + shape, meta, device, stream)
+
+    # ---------------------------------------------------------------- plumbing
+    def __len__(self):
+        return self.shape[0]
+
+    def synchronize(self):
+        _capi._check(_capi._lib.lk_stream_synchronize(self.handle._h, _vp(self.stream or None)))
+        self._keep = []
+
+    def to_host(self):
+        """D2H of the cubes -> list of ``PixelCube`` (round trip, for tests)."""
+        from .correctors.pldcorrector import PixelCube
+        B, N, ny, nx = self.shape
+        f = self.d_flux.download(np.float32, B * N * ny * nx, stream=self.stream).reshape(self.shape)
+        e = self.d_flux_err.download(np.float32, B * N * ny * nx, stream=self.stream).reshape(self.shape)
+        t = self.d_time.download(np.float64, B * N, stream=self.stream).reshape(B, N)
+        self._keep = []
+        out = []
+        for b in range(B):
+            c = PixelCube(t[b], f[b], e[b])
+            c.meta.update(self.meta[b])
+            out.append(c)
+        return out
+
+    # ---------------------------------------------------------------- masks
+    def _shape_mask(self, spec, sap):
+        """A mask spec that does not depend on the pixels' values -> bool (ny, nx); None for the data-dependent ones
+        ('threshold', 'background', and None for the photometric aperture = create_threshold_mask(3))."""
+        ny, nx = self.shape[2:]
+        if spec is None:
+            return None if sap else np.ones((ny, nx), dtype=bool)
+        if isinstance(spec, str):
+            if spec == "all":
+                return np.ones((ny, nx), dtype=bool)
+            if spec == "empty":
+                return np.zeros((ny, nx), dtype=bool)
+            if spec in ("threshold", "background"):
+                return None
+            raise ValueError("aperture_mask '{}' is not supported here".format(spec))
+        m = np.asarray(spec, dtype=bool)
+        if m.shape != (ny, nx):
+            raise ValueError("`aperture_mask` has shape {}, but the flux data has shape {}".format(m.shape, (ny, nx)))
+        return m
+
+    def median_images(self, d_keep=None):
+        """np.nanmedian(flux.astype(float64), axis=0) of every cutout, computed on the device (``lk_cube_median_image_batch_dev``)
+        over all cadences or those flagged in ``d_keep`` (DeviceBuffer of B x N bytes) -> float64[B, ny, nx] on the host."""
+        B, N, ny, nx = self.shape
+        d_med = DeviceBuffer(self.handle, B * ny * nx * 8)
+        _capi._check(_capi._lib.lk_cube_median_image_batch_dev(self.handle._h, B, N, ny * nx, _vp(self.d_flux.ptr),
+                                                               _vp(d_keep.ptr if d_keep is not None else None), _vp(d_med.ptr),
+                                                               _vp(self.stream or None)))
+        return d_med.download(np.float64, B * ny * nx, stream=self.stream).reshape(B, ny, nx)
+
+    def _masks(self, spec, sap, median):
+        """-> bool (ny, nx) shared by the batch, or bool (B, ny, nx) for a data-dependent spec evaluated on every cutout's own
+        median image (``median()`` computes them once per call) as ``PixelCube._parse_aperture_mask`` would."""
+        from .correctors.pldcorrector import threshold_mask_from_median_image as from_median
+        m = self._shape_mask(spec, sap)
+        if m is not None:
+            return m
+        med = median()
+        if spec == "background":
+            return np.stack([~from_median(im, threshold=0, reference_pixel=None) for im in med])
+        return np.stack([from_median(im, 3) for im in med])
+
+    def _aperture(self, aperture_mask):
+        """``lk_cube_aperture_batch_dev``: -> (d_flux32, d_err32, d_keep, kept[B], nonfinite[B])."""
+        h, (B, N, ny, nx) = self.handle, self.shape
+        ap = self._masks(aperture_mask, True, lambda: self.median_images(None))
+        d_mask, k = _upload(h, ap.reshape(-1, ny * nx), self.stream, np.uint8)
+        d_f, d_e, d_k = DeviceBuffer(h, B * N * 4), DeviceBuffer(h, B * N * 4), DeviceBuffer(h, B * N)
+        kept, dirty = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+        _capi._check(_capi._lib.lk_cube_aperture_batch_dev(h._h, B, N, ny * nx, _vp(self.d_flux.ptr), _vp(self.d_flux_err.ptr),
+                                                           _vp(d_mask.ptr), ny * nx if ap.ndim == 3 else 0, _vp(d_f.ptr),
+                                                           _vp(d_e.ptr), _vp(d_k.ptr), _off_ptr(kept), _off_ptr(dirty),
+                                                           _vp(self.stream or None)))           # (synchronises)
+        del k
+        n = int(kept[0])
+        if np.any(kept != n):
+            raise ValueError("pld_correct_batch needs cutouts with the same number of valid cadences")
+        return d_f, d_e, d_k, n, dirty
+
+    def _gather(self, d_f, d_e, d_k, n, pld_idx=None, P=0, bkg_idx=None, Pb=0, want_pld=False, want_bkg=False, knot_plan=None):
+        """``lk_pld_gather_batch_dev`` -> dict of DeviceBuffers (time, y, err, lcf, pld, bkg, knots) + 'nonfinite'."""
+        h, (B, N, ny, nx) = self.handle, self.shape
+        out = dict(time=DeviceBuffer(h, B * n * 8), y=DeviceBuffer(h, B * n * 8), err=DeviceBuffer(h, B * n * 8),
+                   lcf=DeviceBuffer(h, B * n * 4), pld=None, bkg=None, knots=None)
+        if want_pld:
+            out["pld"] = DeviceBuffer(h, B * n * P * 4)
+        if want_bkg:
+            out["bkg"] = DeviceBuffer(h, B * n * Pb * 4)
+        lo = g = None
+        n_inner = 0
+        if knot_plan is not None:
+            lo, g = knot_plan
+            n_inner = len(lo)
+            out["knots"] = DeviceBuffer(h, B * (n_inner + 2) * 8)
+
+        def ptr(key):
+            return _vp(out[key].ptr if out[key] is not None else None)
+
+        def idx(a):
+            return (None, 0) if a is None else (a.ctypes.data_as(_i32p), a.shape[1] if a.shape[0] > 1 else 0)
+
+        (pi, ps), (bi, bs) = idx(pld_idx), idx(bkg_idx)
+        flag = np.zeros(1, dtype=np.int32)
+        _capi._check(_capi._lib.lk_pld_gather_batch_dev(
+            h._h, B, N, ny * nx, n, _vp(self.d_flux.ptr), _vp(self.d_time.ptr), _vp(d_f.ptr), _vp(d_e.ptr), _vp(d_k.ptr), int(P), pi,
+            ps, int(Pb), bi, bs, n_inner, None if lo is None or not n_inner else lo.ctypes.data_as(_i32p),
+            None if g is None or not n_inner else g.ctypes.data_as(_dp), ptr("time"), ptr("y"), ptr("err"), ptr("lcf"), ptr("pld"),
+            ptr("bkg"), ptr("knots"), flag.ctypes.data_as(_i32p), _vp(self.stream or None)))    # (synchronises)
+        out["nonfinite"] = bool(flag[0])
+        return out
+
+    # ---------------------------------------------------------------- aperture photometry
+    def to_lightcurves(self, aperture_mask="all"):
+        """``PixelCube.to_lightcurve(aperture_mask)`` of every cutout without its NaN cadences (what ``PLDCorrector.__init__``
+        keeps, pldcorrector.py:109-120), resident -> ``DeviceLightCurveBatch`` (float64 = the float32 sums widened)."""
+        B = len(self)
+        d_f, d_e, d_k, n, _ = self._aperture(aperture_mask)
+        if n < 1:
+            raise ValueError("no cadence with a finite aperture flux")
+        g = self._gather(d_f, d_e, d_k, n)
+        return DeviceLightCurveBatch(g["time"], g["y"], g["err"], np.arange(B + 1, dtype=np.int64) * n,
+                                     [dict(m) for m in self.meta], self.device, self.stream, nan_free=True,
+                                     is_sorted=self.is_sorted)
+
+    # ---------------------------------------------------------------- PLD
+    def pld_correct(self, aperture_mask="all", pld_aperture_mask="all", background_aperture_mask="all", pld_order=3,
+                    pca_components=16, spline_n_knots=None, spline_degree=5, normalize_background_pixels=True,
+                    restore_trend=True, cadence_mask=None, sigma=5, niters=5, to_host=True):
+        """``pld_correct_batch`` (same defaults and meaning; reference ``PLDCorrector(tpf, aperture_mask).correct(...)``,
+        pldcorrector.py:304-427) on the resident cubes, bit-identical to it.  ``cadence_mask``: optional bool (B, n) over the
+        KEPT cadences, True = used in the fit.  ``to_host=True`` -> (corrected[B, n], outlier_mask[B, n]) numpy arrays;
+        ``to_host=False`` -> (``DeviceLightCurveBatch`` of the compacted times, the corrected flux and the SAP flux errors,
+        ``DeviceBuffer`` of the B x n outlier bytes)."""
+        from .correctors.pldcorrector import _percentile_knot_plan
+        if pca_components is None or pca_components < 1:
+            raise NotImplementedError("pca_components must be >= 1 on the HIP path")
+        if not self.is_sorted:
+            raise ValueError("DevicePixelCubeBatch.pld_correct needs finite, non-decreasing times in every cutout (the spline "
+                             "knots are gathered from sorted times); pld_correct_batch takes unsorted cutouts")
+        h, (B, N, ny, nx) = self.handle, self.shape
+        npix = ny * nx
+        d_f, d_e, d_k, n, dirty = self._aperture(aperture_mask)
+        if n < 2:
+            raise ValueError("pld_correct needs at least two cadences with a finite aperture flux (got %d)" % n)
+        cache = []
+
+        def median():                               # over the KEPT cadences (the corrector sees tpf[~nan_mask]); once per call
+            if not cache:
+                cache.append(self.median_images(d_k))
+            return cache[0]
+
+        pm = self._masks(pld_aperture_mask, False, median)
+        bm = self._masks(background_aperture_mask, False, median)
+        counts_p, counts_b = pm.reshape(-1, npix).sum(axis=1), bm.reshape(-1, npix).sum(axis=1)
+        if len(set(counts_p.tolist())) > 1 or len(set(counts_b.tolist())) > 1:
+            raise ValueError("pld_correct_batch: the per-cutout '%s' / '%s' masks select different numbers of pixels (%s PLD, %s "
+                             "background); pass masks of one size or correct these cutouts one by one"
+                             % (pld_aperture_mask, background_aperture_mask, sorted(set(counts_p.tolist())),
+                                sorted(set(counts_b.tolist()))))
+        P, Pb = int(counts_p[0]), int(counts_b[0])
+        same = pm.shape == bm.shape and np.array_equal(pm, bm)
+        resident = n == N                           # full mask and no dropped cadence: the block IS the resident cube
+
+        def index_lists(m, count):
+            if count == npix or count == 0:
+                return None
+            return np.ascontiguousarray([np.flatnonzero(r) for r in m.reshape(-1, npix)], dtype=np.int32)
+
+        pld_idx, bkg_idx = index_lists(pm, P), index_lists(bm, Pb)
+        want_pld = P > 0 and not (resident and P == npix)
+        want_bkg = Pb > 0 and not same and not (resident and Pb == npix)
+        if spline_n_knots is None:
+            spline_n_knots = int(n / 50)
+        plan = _percentile_knot_plan(n, int(spline_n_knots), int(spline_degree))
+        g = self._gather(d_f, d_e, d_k, n, pld_idx, P, None if same else bkg_idx, 0 if same else Pb, want_pld, want_bkg, plan)
+        whole_image = (P == npix and not want_pld) or (Pb == npix and not want_bkg and not same)
+        if g["nonfinite"] or (whole_image and dirty.any()):
+            raise ValueError("pld_correct_batch needs finite pixels inside the masks")
+        d_pld = g["pld"] if want_pld else (self.d_flux if P > 0 else None)
+        d_bkg = d_pld if same else (g["bkg"] if want_bkg else self.d_flux)
+        n_inner = len(plan[0])
+        n_knots = n_inner + int(spline_degree) + 1
+        K = _capi.pld_design_width(P, Pb, pld_order, pca_components, n_knots)
+        keep = []
+        d_cm = None
+        if cadence_mask is not None:
+            cm = np.ascontiguousarray(cadence_mask, dtype=np.uint8)
+            if cm.shape != (B, n):
+                raise ValueError("cadence_mask must be (B, n) = %s over the kept cadences (got %s)" % ((B, n), cm.shape))
+            d_cm, k = _upload(h, cm, self.stream, np.uint8)
+            keep.append(k)
+        d_X = DeviceBuffer(h, B * n * K * 8)
+        d_ps, d_mu, d_w = (DeviceBuffer(h, B * K * 8) for _ in range(3))
+        d_model, d_corr = DeviceBuffer(h, B * n * 8), DeviceBuffer(h, B * n * 8)
+        d_sp = DeviceBuffer(h, B * n * 8) if restore_trend else None
+        d_outl = DeviceBuffer(h, B * n)
+        _capi._check(_capi._lib.lk_pld_correct_batch_dev(
+            h._h, B, n, P, Pb, _vp(d_pld.ptr if d_pld is not None else None), _vp(d_bkg.ptr), _vp(g["lcf"].ptr), _vp(g["time"].ptr),
+            _vp(g["knots"].ptr), n_inner, int(pld_order), int(pca_components), n_knots, int(spline_degree),
+            int(bool(normalize_background_pixels)), K, _vp(g["y"].ptr), _vp(g["err"].ptr), _vp(d_cm.ptr if d_cm is not None else None),
+            float(sigma), int(niters), _vp(d_X.ptr), _vp(d_ps.ptr), _vp(d_mu.ptr), _vp(d_w.ptr), _vp(d_model.ptr), _vp(d_outl.ptr),
+            _vp(d_sp.ptr if d_sp is not None else None), _vp(d_corr.ptr), _vp(self.stream or None)))
+        if to_host:
+            corrected = d_corr.download(np.float64, B * n, stream=self.stream).reshape(B, n)
+            outl = d_outl.download(np.uint8, B * n, stream=self.stream).reshape(B, n).astype(bool)
+            return corrected, outl
+        out = DeviceLightCurveBatch(g["time"], d_corr, g["err"], np.arange(B + 1, dtype=np.int64) * n, [dict(m) for m in self.meta],
+                                    self.device, self.stream, nan_free=True, is_sorted=True)
+        # scratch and inputs the stream may still be reading: held until the batch is synchronised or dropped
+        out._keep = keep + [d_X, d_ps, d_mu, d_w, d_model, d_sp, d_pld, d_bkg, g, d_f, d_e, d_k, self]
+        return out, d_outl
+
+
+def _cube_times_sorted(time):
+    """Finite, non-decreasing times in every cutout?  ``pld_correct`` takes the spline knots from SORTED times by index."""
+    time = np.asarray(time, dtype=np.float64)
+    return bool(np.all(np.isfinite(time)) and np.all(np.diff(time, axis=-1) >= 0))
+
+
+def _check_cube_arrays(time, flux, flux_err):
+    flux, flux_err = np.asarray(flux), np.asarray(flux_err)
+    if flux.dtype != np.float32 or flux_err.dtype != np.float32:
+        raise TypeError("DevicePixelCubeBatch holds float32 cubes (got %s / %s); pld_correct_batch takes the others"
+                        % (flux.dtype, flux_err.dtype))
+    time = np.ascontiguousarray(time, dtype=np.float64)
+    if flux.ndim != 4 or flux.shape != flux_err.shape or time.shape != flux.shape[:2] or flux.shape[0] < 1:
+        raise ValueError("time must be (B, N), flux and flux_err (B, N, ny, nx)")
+    return time, np.ascontiguousarray(flux), np.ascontiguousarray(flux_err)

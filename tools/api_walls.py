@@ -2,7 +2,13 @@
 """Wall time of the product's OTHER per-batch Python entry points (bench.py's `api_end_to_end` block covers the LS ones):
 `batch.flatten_batch`, `batch.regression_correct_batch`, `batch.pld_correct_batch`, `batch.bls_batch`, one call each on a
 list of objects, median of `reps` after one warm-up, with a cProfile of the last call (top entries by cumulative time) so
-that host-side costs can be told from the GPU calls.  Usage: python tools/api_walls.py [flatten|regress|pld|bls ...]"""
+that host-side costs can be told from the GPU calls.  Usage: python tools/api_walls.py [flatten|regress|pld|bls ...]
+
+`pld_dev`: the resident PLD path (`DevicePixelCubeBatch`) against `pld_correct_batch` on the same cutouts, 100 and 500 cutouts of
+3500 x 11 x 11 (`LK_WALLS_SIZES`, default 100,500) in ONE process, the two paths alternating, median and min-max of `LK_WALLS_REPS` (default 5) repetitions each;
+every timed region ends in a stream synchronise.  `pld_host`: only the `pld_correct_batch` rows (also runs on a checkout
+that has no resident path: the baseline).  `pld_dev_trace`: only resident calls on `LK_WALLS_B` (default 500) cutouts — the
+run to put under `rocprofv3 --kernel-trace --stats` for the kernel-time sum of one call (total / the printed call count)."""
 import cProfile
 import io
 import os
@@ -34,11 +40,82 @@ def wall(fn, reps=3, profile=True):
     return 1e3 * float(np.median(ts)), txt
 
 
+def pld_cubes(B, distinct=100):
+    """B K2-like cutouts of 3500 x 11 x 11 (the first `distinct` synthetic ones, repeated: the walls do not depend on the
+    pixels' values, and 500 distinct cutouts take a minute of host time to draw)."""
+    from lightkurve_amd import synth
+    from lightkurve_amd.correctors.pldcorrector import PixelCube
+    base = []
+    for i in range(min(B, distinct)):
+        t, flux, err, _ = synth.pld_cutout(4, i, n=3500, npix=11)
+        base.append(PixelCube(t, flux, err, mission="K2"))
+    return [base[i % len(base)] for i in range(B)]
+
+
+def spread(ts):
+    ts = 1e3 * np.asarray(ts)
+    return "%8.2f ms (min %.2f, max %.2f, n=%d)" % (float(np.median(ts)), ts.min(), ts.max(), len(ts))
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    out = fn()
+    return time.perf_counter() - t0, out
+
+
+def pld_dev(which):
+    from lightkurve_amd import _capi
+    from lightkurve_amd.correctors.pldcorrector import pld_correct_batch
+    reps = int(os.environ.get("LK_WALLS_REPS", "5"))
+    kw = dict(pld_order=3, pca_components=16)
+    sync = _capi.Handle.get(0).synchronize
+    if "pld_dev_trace" in which:
+        from lightkurve_amd.device import DevicePixelCubeBatch
+        B = int(os.environ.get("LK_WALLS_B", "500"))
+        batch = DevicePixelCubeBatch.from_cubes(pld_cubes(B))
+        calls = 1 + reps
+        for _ in range(calls):
+            batch.pld_correct(**kw)
+        sync()
+        print("pld_dev_trace: %d resident pld_correct calls on %d cutouts x 3500 x 11 x 11 (order 3, 16 components)" % (calls, B))
+        return
+    resident = "pld_dev" in which
+    if resident:
+        from lightkurve_amd.device import DevicePixelCubeBatch
+    for B in (int(v) for v in os.environ.get("LK_WALLS_SIZES", "100,500").split(",")):
+        cubes = pld_cubes(B)
+        A, U, R, R2 = [], [], [], []
+        ref = pld_correct_batch(cubes, **kw)                       # warm-up of this shape, both paths
+        if resident:
+            batch = DevicePixelCubeBatch.from_cubes(cubes)
+            got = batch.pld_correct(**kw)
+            batch.pld_correct(to_host=False, **kw)[0].synchronize()
+            same = bool(np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]))
+        for _ in range(reps):
+            A.append(timed(lambda: (pld_correct_batch(cubes, **kw), sync()))[0])
+            if not resident:
+                continue
+            dt, batch = timed(lambda: DevicePixelCubeBatch.from_cubes(cubes))      # (from_cubes ends in a synchronise)
+            U.append(dt)
+            R.append(timed(lambda: (batch.pld_correct(**kw), sync()))[0])
+            R2.append(timed(lambda: batch.pld_correct(to_host=False, **kw)[0].synchronize())[0])
+        print("PLD, %d cutouts x 3500 x 11 x 11, order 3, 16 components, all pixels" % B)
+        print("  A  pld_correct_batch(list of PixelCube)            %s" % spread(A))
+        if resident:
+            print("  U  DevicePixelCubeBatch.from_cubes (once per batch) %s" % spread(U))
+            print("  R  batch.pld_correct() -> host arrays              %s" % spread(R))
+            print("  R' batch.pld_correct(to_host=False) + synchronise  %s" % spread(R2))
+            print("  resident result == pld_correct_batch result: %s; R / A = %.3f" % (same, np.median(R) / np.median(A)))
+        sys.stdout.flush()
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
     from lightkurve_amd.lightcurve import LightCurve
     which = sys.argv[1:] or ["flatten", "regress", "pld", "bls"]
+    if {"pld_dev", "pld_host", "pld_dev_trace"} & set(which):
+        pld_dev(which)
     if "flatten" in which:
         lcs = []
         for i in range(1000):
