@@ -23,6 +23,12 @@
  *   lk_cube_aperture_batch_dev / lk_cube_median_image_batch_dev / lk_pld_gather_batch_dev <- what PLDCorrector does to a
  *                           TargetPixelFile before that (aperture photometry, NaN cadences, threshold-mask median image,
  *                           pixel series, knots) for cubes resident in device memory; lk_pld_correct_batch_dev follows.
+ *   lk_cube_threshold_mask_batch_dev <- the rest of create_threshold_mask (MAD cut, 4-connected labelling, nearest region) on
+ *                           those median images, in device memory: masks, pixel counts and index lists per cutout.
+ *   lk_pld_gather_ragged_batch_dev / lk_pld_correct_ragged_batch* <- the same PLD call for cutouts whose PLD / background
+ *                           masks select DIFFERENT numbers of pixels (the reference's K2 defaults: 'threshold' /
+ *                           'background'): zero-padded pixel blocks of one row pitch plus per-cutout counts.  Limits that
+ *                           remain: one kept-cadence count per call, every count >= pca_components.
  *   lk_fold_batch*       <- LightCurve.fold, src/lightkurve/lightcurve.py:1089-1214 (astropy TimeSeries.fold + sort).
  *   lk_pg_logmedian_batch* / lk_pg_boxsmooth_batch* <- Periodogram.smooth, periodogram.py:182-284.
  *
@@ -465,6 +471,32 @@ int lk_pld_correct_batch_dev(lk_handle *h, int B, int N, int P, int Pb, const fl
                              double *prior_sigma, double *prior_mu, double *w, double *model, uint8_t *outlier,
                              double *spline_part, double *corrected, void *stream);
 
+/* Ragged pixel blocks: lk_pld_correct_batch / lk_pld_correct_batch_dev for cutouts whose PLD and background masks differ in
+ * size.  pld_pix is B x N x P and bkg_pix B x N x Pb with P / Pb the ROW PITCH (the largest count): cutout b's first
+ * p_count[b] / pb_count[b] columns are its pixels, the columns behind them hold exactly +0.0f
+ * (lk_pld_gather_ragged_batch_dev writes that layout).  p_count / pb_count: B int32 each — HOST arrays for
+ * lk_pld_correct_ragged_batch, DEVICE arrays for the _dev form; NULL = every cutout uses all P / Pb columns (then the call is
+ * the uniform one, same bits).  The result for cutout b equals the uniform call on that cutout's own columns to the PLD
+ * parity of this library (1e-6 of the flux; measured: equal bits where the pitch is <= 138 columns, 3.3e-8 at 225): zero
+ * columns have zero means and zero rows / columns in the Gram matrix, and every eigen-solver route works on matrix b's own
+ * leading count x count block and gives the padding zero eigenvector rows.  K = lk_pld_design_width(P, Pb, ...).
+ * LK_EINVAL if a count is below pca_components (the design width would differ between cutouts), below 1, or above the
+ * pitch.  The _dev form copies the 2 B counts back for that check (it synchronises `stream` once more than the uniform
+ * call). */
+int lk_pld_correct_ragged_batch(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
+                                const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
+                                int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, const double *y,
+                                const double *err, const uint8_t *cadence_mask, double clip_sigma, int niters, double *w,
+                                double *model, uint8_t *outlier, double *spline_part, const int32_t *p_count,
+                                const int32_t *pb_count);
+int lk_pld_correct_ragged_batch_dev(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
+                                    const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
+                                    int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K,
+                                    const double *y, const double *err, const uint8_t *cadence_mask, double clip_sigma,
+                                    int niters, double *X, double *prior_sigma, double *prior_mu, double *w, double *model,
+                                    uint8_t *outlier, double *spline_part, double *corrected, void *stream,
+                                    const int32_t *p_count, const int32_t *pb_count);
+
 /* ---- Resident pixel cubes: what PLDCorrector does to a target-pixel file BEFORE the design matrix, for B same-shaped
  * float32 cutouts flux / flux_err [B][N][npix] in device memory (npix = ny * nx row-major, the layout lk_fits_unpack_cube
  * writes per column).  All take device pointers and a stream.
@@ -488,7 +520,22 @@ int lk_pld_correct_batch_dev(lk_handle *h, int B, int N, int P, int Pb, const fl
  *   pixel).  A block whose output is NULL is skipped (all pixels of all cadences kept: the block IS the cube, and
  *   lk_cube_aperture_batch_dev's nonfinite_host answers for its pixels).  knots_out (nullable) B x (n_inner + 2) = [t[0],
  *   lerp(t[lo_k], t[lo_k + 1], g_k) ..., t[n - 1]] with numpy's _lerp from the HOST plan knot_lo_host / knot_g_host (n_inner
- *   each; times must be non-decreasing).  *nonfinite_host = 1 if a gathered pixel is not finite.  Synchronises. */
+ *   each; times must be non-decreasing).  *nonfinite_host = 1 if a gathered pixel is not finite.  Synchronises.
+ * lk_cube_threshold_mask_batch_dev <- threshold_mask_from_median_image (targetpixelfile.py:700-742) on the B x (ny x nx)
+ *   float64 median images of lk_cube_median_image_batch_dev, one workgroup per cutout, exactly: vals = the finite pixels,
+ *   mad = median(|vals - median(vals)|) (np.median: mean of the two middle values), cut = (1.4826 * mad * threshold) +
+ *   nanmedian(image) rounded product by product, mask = nan_to_num(image) >= cut; no finite pixel: empty mask.  use_ref != 0:
+ *   only the 4-connected region holding the masked pixel nearest to (ref_col, ref_row) stays (squared distances; the first
+ *   minimum in row-major order); an empty mask stays empty.  invert != 0 flips the result ('background' =
+ *   ~threshold_mask(0, no reference pixel)).  mask: B x npix bytes, count: B int32, idx: B x npix int32 = the selected pixel
+ *   numbers ascending, then -1.  ny * nx <= LK_CUBE_MASK_MAX_NPIX (64 x 64; the labels live in LDS), else LK_EINVAL.
+ *   Enqueued, no synchronisation.
+ * lk_pld_gather_ragged_batch_dev <- lk_pld_gather_batch_dev with per-cutout index lists of different lengths ON THE DEVICE:
+ *   pld_idx / bkg_idx are B rows of pld_idx_stride / bkg_idx_stride (>= P / Pb) int32, ascending pixel numbers then -1
+ *   (lk_cube_threshold_mask_batch_dev's idx with stride npix, or uploaded lists).  pld_out B x n x P / bkg_out B x n x Pb with
+ *   P / Pb the largest count: a padded column holds exactly +0.0f and does not count for *nonfinite_host.  An entry >= npix
+ *   is LK_EINVAL.  Everything else as lk_pld_gather_batch_dev.  Synchronises. */
+#define LK_CUBE_MASK_MAX_NPIX 4096
 int lk_cube_aperture_batch_dev(lk_handle *h, int B, int N, int npix, const float *flux, const float *flux_err,
                                const uint8_t *mask, int mask_stride, float *flux_out, float *err_out, uint8_t *keep_out,
                                int64_t *kept_host, int64_t *nonfinite_host, void *stream);
@@ -500,6 +547,15 @@ int lk_pld_gather_batch_dev(lk_handle *h, int B, int N, int npix, int n, const f
                             const int32_t *knot_lo_host, const double *knot_g_host, double *t_out, double *y_out,
                             double *err_out, float *lcf_out, float *pld_out, float *bkg_out, double *knots_out,
                             int *nonfinite_host, void *stream);
+int lk_cube_threshold_mask_batch_dev(lk_handle *h, int B, int ny, int nx, const double *median, double threshold, int use_ref,
+                                     double ref_col, double ref_row, int invert, uint8_t *mask, int32_t *count, int32_t *idx,
+                                     void *stream);
+int lk_pld_gather_ragged_batch_dev(lk_handle *h, int B, int N, int npix, int n, const float *cube, const double *time,
+                                   const float *flux32, const float *err32, const uint8_t *keep, int P, const int32_t *pld_idx,
+                                   int pld_idx_stride, int Pb, const int32_t *bkg_idx, int bkg_idx_stride, int n_inner,
+                                   const int32_t *knot_lo_host, const double *knot_g_host, double *t_out, double *y_out,
+                                   double *err_out, float *lcf_out, float *pld_out, float *bkg_out, double *knots_out,
+                                   int *nonfinite_host, void *stream);
 
 /* ---- Standalone design-matrix operations (correctors/designmatrix.py) for B same-shaped matrices ----------------
  * lk_pca_batch          <- DesignMatrix.pca(nterms), designmatrix.py:252-282 (fbpca.pca(values, nterms) -> U): the first

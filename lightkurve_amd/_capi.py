@@ -23,6 +23,7 @@ _c_ip = ctypes.POINTER(ctypes.c_int64)
 _vp = ctypes.c_void_p
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
 _c_i32p = ctypes.POINTER(ctypes.c_int32)
+CUBE_MASK_MAX_NPIX = 4096      # LK_CUBE_MASK_MAX_NPIX (include/lkhip.h): pixels per cutout of lk_cube_threshold_mask_batch_dev
 _c_fp = ctypes.POINTER(ctypes.c_float)
 
 # (name, restype, argtypes) for EVERY symbol include/lkhip.h declares — tests/test_capi_symbols.py checks the list
@@ -175,6 +176,21 @@ SIGNATURES = [
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_int,
       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
       ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_pld_correct_ragged_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_fp, _c_fp, _c_fp, _c_dp, _c_dp, ctypes.c_int,
+      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_u8p,
+      ctypes.c_double, ctypes.c_int, _c_dp, _c_dp, _c_u8p, _c_dp, _c_i32p, _c_i32p]),
+    ("lk_pld_correct_ragged_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_int,
+      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
+      ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_cube_threshold_mask_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+      ctypes.c_int, _vp, _vp, _vp, _vp]),
+    ("lk_pld_gather_ragged_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp,
+      ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _c_i32p, _c_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+      _c_i32p, _vp]),
     ("lk_cube_aperture_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _c_ip, _c_ip, _vp]),
     ("lk_cube_median_image_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
@@ -822,12 +838,14 @@ def pld_design_batch(pld_pix, bkg_pix, lc_flux, time, knots, pld_order, pca_comp
 
 
 def pld_correct_batch(pld_pix, bkg_pix, lc_flux, time, knots, y, err, pld_order, pca_components, spline_degree,
-                      normalize_bkg=True, cadence_mask=None, sigma=5.0, niters=5, want_spline=True, device=0):
+                      normalize_bkg=True, cadence_mask=None, sigma=5.0, niters=5, want_spline=True, device=0,
+                      p_count=None, pb_count=None):
     """``PLDCorrector.correct`` numerics for B same-shaped cutouts in ONE call (design matrices, regression + clip loop, the
     spline block's share of the model); the design matrices stay in device memory.  Inputs as ``pld_design_batch`` plus
     y / err (B, N) float64 = the SAP light curve; pass the SAME array as ``pld_pix`` and ``bkg_pix`` when both apertures
     are equal (uploaded once).  Returns dict(coefficients[B, K], model[B, N] (median removed), outlier_mask[B, N] bool,
-    spline[B, N] or None)."""
+    spline[B, N] or None).  ``p_count`` / ``pb_count`` (int32[B], either may be None): ragged pixel blocks — cutout b's first
+    p_count[b] / pb_count[b] columns are pixels, the rest of the row is +0.0 (``lk_pld_correct_ragged_batch``)."""
     h = Handle.get(device)
     same = pld_pix is bkg_pix
     bkg_pix = np.ascontiguousarray(bkg_pix, dtype=np.float32)
@@ -856,6 +874,17 @@ def pld_correct_batch(pld_pix, bkg_pix, lc_flux, time, knots, y, err, pld_order,
     model = np.empty((B, N), dtype=np.float64)
     outl = np.empty((B, N), dtype=np.uint8)
     sp = np.empty((B, N), dtype=np.float64) if want_spline else None
+    if p_count is not None or pb_count is not None:
+        pc = None if p_count is None else np.ascontiguousarray(p_count, dtype=np.int32)
+        bc = None if pb_count is None else np.ascontiguousarray(pb_count, dtype=np.int32)
+        if any(c is not None and c.shape != (B,) for c in (pc, bc)):
+            raise ValueError("p_count / pb_count must hold one count per cutout")
+        _check(_lib.lk_pld_correct_ragged_batch(
+            h._h, B, N, P, Pb, _ptr(pld_pix, _c_fp), _ptr(bkg_pix, _c_fp), _ptr(lc_flux, _c_fp), _ptr(time), _ptr(knots), n_inner,
+            int(pld_order), int(pca_components), n_knots, int(spline_degree), int(bool(normalize_bkg)), K, _ptr(y), _ptr(err),
+            _ptr(cm, _c_u8p), float(sigma), int(niters), _ptr(w), _ptr(model), _ptr(outl, _c_u8p), _ptr(sp),
+            _ptr(pc, _c_i32p), _ptr(bc, _c_i32p)))
+        return dict(coefficients=w, model=model, outlier_mask=outl.astype(bool), spline=sp)
     _check(_lib.lk_pld_correct_batch(h._h, B, N, P, Pb, _ptr(pld_pix, _c_fp), _ptr(bkg_pix, _c_fp), _ptr(lc_flux, _c_fp),
                                      _ptr(time), _ptr(knots), n_inner, int(pld_order), int(pca_components), n_knots,
                                      int(spline_degree), int(bool(normalize_bkg)), K, _ptr(y), _ptr(err), _ptr(cm, _c_u8p),

@@ -250,17 +250,29 @@ def estimate_cdpp_batch(lcs, transit_duration=13, savgol_window=101, savgol_poly
     return out[:, 0]
 
 
-def pld_correct_batch(cubes, gather=True, device=0, **kwargs):
+def pld_correct_batch(cubes, gather=True, device=0, ragged_masks=False, **kwargs):
     """``PLDCorrector(tpf).correct(...)`` (reference correctors/pldcorrector.py:203-427) for a list of same-shaped cutouts,
     sharded over the ranks: rank r runs ``correctors.pldcorrector.pld_correct_batch`` (design matrices + regression, two GPU
-    calls) on its block.  Returns (corrected_flux[B, N], outlier_mask[B, N]) — all B rows on every rank with ``gather``."""
-    from .correctors.pldcorrector import pld_correct_batch as one_gpu
+    calls) on its block.  ``ragged_masks`` goes to every rank's shard (PLD / background masks of different sizes per cutout);
+    masks given as bool (B, ny, nx) arrays are split with the cutouts.  Returns (corrected_flux[B, N], outlier_mask[B, N]) — all
+    B rows on every rank with ``gather``."""
+    from .correctors.pldcorrector import _per_cutout_masks, pld_correct_batch as one_gpu
     cubes = list(cubes)
+    mask_names = ("aperture_mask", "pld_aperture_mask", "background_aperture_mask")
+    per = {k: _per_cutout_masks(kwargs[k], len(cubes), cubes[0].shape[1:]) for k in mask_names if k in kwargs and cubes}
+    per = {k: m for k, m in per.items() if m is not None}
+    if per:                                   # a shard takes its own rows of the per-cutout masks: items carry their index
+        cubes = list(enumerate(cubes))
 
     def compute(local):
         if not local:
             return np.zeros((0, 2, 0))
-        flux, outl = one_gpu(local, device=device, **kwargs)
+        kw = dict(kwargs)
+        if per:
+            rows = [i for i, _ in local]
+            local = [c for _, c in local]
+            kw.update({k: m[rows] for k, m in per.items()})
+        flux, outl = one_gpu(local, device=device, ragged_masks=ragged_masks, **kw)
         return np.stack([flux, outl.astype(np.float64)], axis=1)
 
     dist_on = False
@@ -272,7 +284,9 @@ def pld_correct_batch(cubes, gather=True, device=0, **kwargs):
     if dist_on and gather:
         # an empty local block has no cadence count of its own: take it from the batch (same-shaped cutouts)
         from .correctors.pldcorrector import PLDCorrector
-        n = len(PLDCorrector(cubes[0], aperture_mask=kwargs.get("aperture_mask", "all")).lc) if cubes else 0
+        first = (cubes[0][1] if per else cubes[0]) if cubes else None
+        ap0 = per["aperture_mask"][0] if "aperture_mask" in per else kwargs.get("aperture_mask", "all")
+        n = len(PLDCorrector(first, aperture_mask=ap0).lc) if cubes else 0
 
         def compute_n(local):
             return compute(local) if local else np.zeros((0, 2, n))

@@ -386,6 +386,39 @@ def _shared_mask(first, spec, sap=False):
     return first._parse_aperture_mask(spec)
 
 
+def _per_cutout_masks(spec, B, image_shape):
+    """A mask argument given as a bool (B, ny, nx) array — one mask per cutout — or None for every other kind of spec."""
+    if spec is None or isinstance(spec, str):
+        return None
+    m = np.asarray(spec, dtype=bool)
+    if m.ndim != 3:
+        return None
+    if m.shape != (B,) + tuple(image_shape):
+        raise ValueError("per-cutout masks have shape {}, but the batch holds {} cutouts of shape {}".format(
+            m.shape, B, tuple(image_shape)))
+    return m
+
+
+def _ragged_index_lists(masks, pca_components, what="PLD"):
+    """bool (B, npix) masks of DIFFERENT sizes -> (idx int32 (B, Pmax): every cutout's selected pixel numbers ascending, then -1;
+    counts int32 (B,)) — the layout ``lk_pld_gather_ragged_batch_dev`` reads.  Every count must reach ``pca_components``: the PCA
+    keeps min(pca_components, count) columns, so a smaller block would give that cutout a narrower design matrix than the rest
+    of the call.  ValueError names the cutouts and their counts."""
+    masks = np.asarray(masks, dtype=bool)
+    if masks.ndim != 2 or masks.shape[0] < 1:
+        raise ValueError("masks must be (B, npix)")
+    counts = masks.sum(axis=1).astype(np.int32)
+    short = np.flatnonzero(counts < int(pca_components))
+    if short.size:
+        raise ValueError("ragged_masks: the %s masks of cutouts %s select %s pixels, fewer than pca_components = %d; correct these "
+                         "cutouts on their own or lower pca_components"
+                         % (what, short.tolist(), counts[short].tolist(), int(pca_components)))
+    idx = np.full((masks.shape[0], max(int(counts.max()), 1)), -1, dtype=np.int32)
+    for b, m in enumerate(masks):
+        idx[b, :counts[b]] = np.flatnonzero(m)
+    return idx, counts
+
+
 def _batch_cutout(c, ap, pm, bm, specs):
     """One cutout's share of pld_correct_batch: what ``PLDCorrector(c, aperture_mask)`` keeps (the SAP light curve without its
     NaN cadences, pldcorrector.py:109-120) and the pixel series of the two apertures, without the object construction.
@@ -418,13 +451,16 @@ def _batch_cutout(c, ap, pm, bm, specs):
 
 def pld_correct_batch(cubes, aperture_mask="all", pld_aperture_mask="all", background_aperture_mask="all",
                       pld_order=3, pca_components=16, spline_n_knots=None, spline_degree=5,
-                      normalize_background_pixels=True, restore_trend=True, sigma=5, niters=5, device=0):
+                      normalize_background_pixels=True, restore_trend=True, sigma=5, niters=5, device=0, ragged_masks=False):
     """PLDCorrector(...).correct(...) for a list of same-shaped cutouts in ONE GPU call (``lk_pld_correct_batch``: design
     matrices, regression and the spline block's share of the model; the design matrices never leave the device).  Masks
     given as arrays (or 'all' / 'empty') are shared by the batch; the data-dependent ones — ``aperture_mask=None`` (the
     reference's default, ``create_threshold_mask(3)``), 'threshold', 'background' — are evaluated on EVERY cutout, as a loop
     over ``PLDCorrector(tpf, aperture_mask).correct(...)`` would (pldcorrector.py:99-107, 203-207); such PLD / background
-    masks must then select the same NUMBER of pixels in every cutout (one design-matrix width per call).  The per-cutout host
+    masks must then select the same NUMBER of pixels in every cutout (one design-matrix width per call) unless
+    ``ragged_masks=True``: then the pixel blocks are zero-padded to the widest cutout's and go with their per-cutout counts to
+    ``lk_pld_correct_ragged_batch`` (every count >= ``pca_components``; equal sizes take the call without the keyword).  Each
+    mask may also be a bool (B, ny, nx) array, one mask per cutout.  The per-cutout host
     work (aperture sums, NaN-cadence removal, pixel gathers, percentile knots) runs on the packing thread pool and lands in
     page-locked staging buffers.  Returns (corrected_flux[B, N], outlier_mask[B, N])."""
     from .. import packed
@@ -435,18 +471,34 @@ def pld_correct_batch(cubes, aperture_mask="all", pld_aperture_mask="all", backg
         raise NotImplementedError("pca_components must be >= 1 on the HIP path")
     first = cubes[0]
     specs = (aperture_mask, pld_aperture_mask, background_aperture_mask)
-    ap = _shared_mask(first, aperture_mask, sap=True)
-    pm = _shared_mask(first, pld_aperture_mask)
-    bm = _shared_mask(first, background_aperture_mask)
+    per = [_per_cutout_masks(spec, len(cubes), first.shape[1:]) for spec in specs]
+    ap = None if per[0] is not None else _shared_mask(first, aperture_mask, sap=True)
+    pm = None if per[1] is not None else _shared_mask(first, pld_aperture_mask)
+    bm = None if per[2] is not None else _shared_mask(first, background_aperture_mask)
     for c in cubes:
         if c.shape[1:] != first.shape[1:]:
             raise ValueError("pld_correct_batch needs cutouts of one shape (got %s and %s)" % (c.shape, first.shape))
-    parts = packed._pmap(_batch_cutout, [(c, ap, pm, bm, specs) for c in cubes])
+
+    def own(i, shared_mask, b):
+        return per[i][b] if per[i] is not None else shared_mask
+
+    parts = packed._pmap(_batch_cutout, [(c, own(0, ap, b), own(1, pm, b), own(2, bm, b), specs) for b, c in enumerate(cubes)])
     n = len(parts[0][0])
     if any(len(p[0]) != n for p in parts):
         raise ValueError("pld_correct_batch needs cutouts with the same number of valid cadences")
-    B, P, Pb = len(parts), parts[0][4].shape[1], parts[0][5].shape[1]
-    if any(p[4].shape[1] != P or p[5].shape[1] != Pb for p in parts):
+    B = len(parts)
+    counts_p = np.array([p[4].shape[1] for p in parts], dtype=np.int32)
+    counts_b = np.array([p[5].shape[1] for p in parts], dtype=np.int32)
+    P, Pb = int(counts_p.max()), int(counts_b.max())         # (ragged: the row pitch of the zero-padded blocks)
+    ragged = bool(np.any(counts_p != P) or np.any(counts_b != Pb))
+    if ragged and ragged_masks:
+        for counts, what in ((counts_p, "PLD"), (counts_b, "background")):
+            short = np.flatnonzero(counts < int(pca_components))
+            if short.size and counts.max() > 0:
+                raise ValueError("ragged_masks: the %s masks of cutouts %s select %s pixels, fewer than pca_components = %d; "
+                                 "correct these cutouts on their own or lower pca_components"
+                                 % (what, short.tolist(), counts[short].tolist(), int(pca_components)))
+    elif ragged:
         raise ValueError("pld_correct_batch: the per-cutout '%s' / '%s' masks select different numbers of pixels (%s PLD, %s "
                          "background); pass masks of one size or correct these cutouts one by one"
                          % (pld_aperture_mask, background_aperture_mask, sorted({p[4].shape[1] for p in parts}),
@@ -471,9 +523,11 @@ def pld_correct_batch(cubes, aperture_mask="all", pld_aperture_mask="all", backg
     def fill(b):
         tb, fb, eb, f32, px, bx = parts[b]
         t[b], y[b], err[b], lcf[b] = tb, fb, eb, f32
-        pld[b] = px
+        pld[b, :, :px.shape[1]] = px
+        pld[b, :, px.shape[1]:] = 0.0
         if not shared:
-            bkg[b] = bx
+            bkg[b, :, :bx.shape[1]] = bx
+            bkg[b, :, bx.shape[1]:] = 0.0
         knots[b] = _percentile_knots(tb, spline_n_knots, spline_degree)
         return _all_finite(px) and (shared or _all_finite(bx))
 
@@ -481,7 +535,8 @@ def pld_correct_batch(cubes, aperture_mask="all", pld_aperture_mask="all", backg
         raise ValueError("pld_correct_batch needs finite pixels inside the masks")
     res = _capi.pld_correct_batch(pld if P else None, bkg, lcf, t, knots, y, err, pld_order, pca_components, spline_degree,
                                   normalize_background_pixels, sigma=sigma, niters=niters, want_spline=restore_trend,
-                                  device=device)
+                                  device=device, p_count=counts_p if ragged and P else None,
+                                  pb_count=counts_b if ragged else None)
     corrected = y - res["model"]
     if restore_trend:
         sp = res["spline"]

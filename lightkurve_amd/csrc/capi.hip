@@ -627,11 +627,21 @@ int lk_pld_design_batch(lk_handle *h, int B, int N, int P, int Pb, const float *
 
 // PLDCorrector.correct for B same-shaped cutouts, host pointers in and out: design matrices, regression + clip loop and the
 // spline block's share of the model in one call — X (B x N x K doubles, 1.7 GB per 500 K2 cutouts) never leaves HBM.
-int lk_pld_correct_batch(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
-                         const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
-                         int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, const double *y,
-                         const double *err, const uint8_t *cadence_mask, double clip_sigma, int niters, double *w,
-                         double *model, uint8_t *outlier, double *spline_part) {
+// Per-cutout column counts of a ragged call, on the host: each within [pca_components, pitch] (one design width per call).
+static int pld_check_counts(const char *what, const int32_t *count, int B, int pitch, int pca_components) {
+    for (int b = 0; count && b < B; ++b)
+        LK_REQUIRE(count[b] >= pca_components && count[b] >= 1 && count[b] <= pitch,
+                   "cutout %d has %d %s pixels: a ragged call needs between pca_components = %d and the row pitch %d in every cutout",
+                   b, (int)count[b], what, pca_components, pitch);
+    return LK_OK;
+}
+
+static int pld_correct_host(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
+                            const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
+                            int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, const double *y,
+                            const double *err, const uint8_t *cadence_mask, double clip_sigma, int niters, double *w,
+                            double *model, uint8_t *outlier, double *spline_part, const int32_t *p_count,
+                            const int32_t *pb_count) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_REQUIRE(B >= 1 && N >= 2 && P >= 0 && Pb >= 1 && K >= 1, "bad shapes");
     LK_REQUIRE(bkg_pix && lc_flux && time && knots && y && w && model && outlier, "NULL buffer");
@@ -644,18 +654,23 @@ int lk_pld_correct_batch(lk_handle *h, int B, int N, int P, int Pb, const float 
     const float *dp, *db, *dl;
     const double *dt, *dk, *dy, *derr;
     const uint8_t *dcm;
+    const int32_t *dpc, *dbc;
     double *dX, *ds, *dmu, *dw, *dmodel, *dsp;
     uint8_t *dout;
+    int rc = pld_check_counts("PLD", has_pld ? p_count : nullptr, B, P, pca_components);
+    if (!rc) rc = pld_check_counts("background", pb_count, B, Pb, pca_components);
+    if (rc) return rc;
     lk::StagedCall io(h);
-    int rc = io.in(dp, has_pld && !shared ? pld_pix : nullptr, bn * P).in(db, bkg_pix, bn * Pb).in(dl, lc_flux, bn)
-                 .in(dt, time, bn).in(dk, knots, (size_t)B * (n_inner + 2)).scratch(dX, bn * K).scratch(ds, nk)
-                 .scratch(dmu, nk).out(dw, w, nk).in(dy, y, bn).in(derr, err, bn).out(dmodel, model, bn)
-                 .out(dsp, spline_part, bn).in(dcm, cadence_mask, bn).out(dout, outlier, bn).stage();
+    rc = io.in(dp, has_pld && !shared ? pld_pix : nullptr, bn * P).in(db, bkg_pix, bn * Pb).in(dl, lc_flux, bn)
+             .in(dt, time, bn).in(dk, knots, (size_t)B * (n_inner + 2)).scratch(dX, bn * K).scratch(ds, nk)
+             .scratch(dmu, nk).out(dw, w, nk).in(dy, y, bn).in(derr, err, bn).out(dmodel, model, bn)
+             .out(dsp, spline_part, bn).in(dcm, cadence_mask, bn).out(dout, outlier, bn)
+             .in(dpc, has_pld ? p_count : nullptr, (size_t)B).in(dbc, pb_count, (size_t)B).stage();
     if (rc) return rc;
     if (shared) dp = db;
     LK_HIP_CHECK(hipMemsetAsync(dmu, 0, nk * 8, nullptr));   // prior_mu = 0 for every PLD column (pldcorrector.py:240-287)
     rc = lk::pld_design_launch(h, B, N, dp ? P : 0, Pb, dp, db, dl, dt, dk, n_inner, pld_order, pca_components, n_knots,
-                               spline_degree, normalize_bkg, K, dX, ds, nullptr);
+                               spline_degree, normalize_bkg, K, dX, ds, nullptr, dpc, dbc);
     if (rc) return rc;
     std::vector<int64_t> off((size_t)B + 1);
     for (int b = 0; b <= B; ++b) off[b] = (int64_t)b * N;
@@ -668,14 +683,38 @@ int lk_pld_correct_batch(lk_handle *h, int B, int N, int P, int Pb, const float 
     return io.finish();
 }
 
+int lk_pld_correct_batch(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
+                         const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
+                         int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, const double *y,
+                         const double *err, const uint8_t *cadence_mask, double clip_sigma, int niters, double *w,
+                         double *model, uint8_t *outlier, double *spline_part) {
+    return pld_correct_host(h, B, N, P, Pb, pld_pix, bkg_pix, lc_flux, time, knots, n_inner, pld_order, pca_components, n_knots,
+                            spline_degree, normalize_bkg, K, y, err, cadence_mask, clip_sigma, niters, w, model, outlier,
+                            spline_part, nullptr, nullptr);
+}
+
+// lk_pld_correct_batch for cutouts whose pixel blocks hold different numbers of real columns: cutout b's first p_count[b] /
+// pb_count[b] columns (host arrays of B entries, NULL = all of them) are pixels, the rest of the row pitch P / Pb is +0.0f.
+int lk_pld_correct_ragged_batch(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
+                                const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
+                                int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, const double *y,
+                                const double *err, const uint8_t *cadence_mask, double clip_sigma, int niters, double *w,
+                                double *model, uint8_t *outlier, double *spline_part, const int32_t *p_count,
+                                const int32_t *pb_count) {
+    return pld_correct_host(h, B, N, P, Pb, pld_pix, bkg_pix, lc_flux, time, knots, n_inner, pld_order, pca_components, n_knots,
+                            spline_degree, normalize_bkg, K, y, err, cadence_mask, clip_sigma, niters, w, model, outlier,
+                            spline_part, p_count, pb_count);
+}
+
 // lk_pld_correct_batch on device pointers and a stream.  X, prior_sigma and prior_mu are the CALLER's device scratch, not
 // h->staging: a later host-pointer call on this handle re-carves the staging arena while `stream` may still read them.
-int lk_pld_correct_batch_dev(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
-                             const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
-                             int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, const double *y,
-                             const double *err, const uint8_t *cadence_mask, double clip_sigma, int niters, double *X,
-                             double *prior_sigma, double *prior_mu, double *w, double *model, uint8_t *outlier,
-                             double *spline_part, double *corrected, void *stream) {
+static int pld_correct_dev(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
+                           const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
+                           int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, const double *y,
+                           const double *err, const uint8_t *cadence_mask, double clip_sigma, int niters, double *X,
+                           double *prior_sigma, double *prior_mu, double *w, double *model, uint8_t *outlier,
+                           double *spline_part, double *corrected, void *stream, const int32_t *p_count,
+                           const int32_t *pb_count) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_REQUIRE(B >= 1 && N >= 2 && P >= 0 && Pb >= 1 && K >= 1, "bad shapes");
     LK_REQUIRE(bkg_pix && lc_flux && time && knots && y && w && model && outlier, "NULL buffer");
@@ -684,10 +723,20 @@ int lk_pld_correct_batch_dev(lk_handle *h, int B, int N, int P, int Pb, const fl
     LK_HIP_CHECK(hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool has_pld = P > 0 && pld_pix != nullptr;
+    if (!has_pld) p_count = nullptr;
+    if (p_count || pb_count) {   // ragged: the counts come back for the check (the design launch synchronises the stream anyway)
+        std::vector<int32_t> hc((size_t)2 * B);
+        if (p_count) LK_HIP_CHECK(hipMemcpyAsync(hc.data(), p_count, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        if (pb_count) LK_HIP_CHECK(hipMemcpyAsync(hc.data() + B, pb_count, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        LK_HIP_CHECK(hipStreamSynchronize(st));
+        int rc_ = pld_check_counts("PLD", p_count ? hc.data() : nullptr, B, P, pca_components);
+        if (!rc_) rc_ = pld_check_counts("background", pb_count ? hc.data() + B : nullptr, B, Pb, pca_components);
+        if (rc_) return rc_;
+    }
     LK_HIP_CHECK(hipMemsetAsync(prior_mu, 0, (size_t)B * K * 8, st));   // prior_mu = 0 for every PLD column
     int rc = lk::pld_design_launch(h, B, N, has_pld ? P : 0, Pb, has_pld ? pld_pix : nullptr, bkg_pix, lc_flux, time, knots,
                                    n_inner, pld_order, pca_components, n_knots, spline_degree, normalize_bkg, K, X, prior_sigma,
-                                   st);
+                                   st, p_count, pb_count);
     if (rc) return rc;
     std::vector<int64_t> off((size_t)B + 1);
     for (int b = 0; b <= B; ++b) off[b] = (int64_t)b * N;
@@ -700,6 +749,30 @@ int lk_pld_correct_batch_dev(lk_handle *h, int B, int N, int P, int Pb, const fl
     }
     if (corrected) return lk::pld_corrected_launch(h, B, N, y, model, spline_part, corrected, st);
     return LK_OK;
+}
+
+int lk_pld_correct_batch_dev(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
+                             const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
+                             int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, const double *y,
+                             const double *err, const uint8_t *cadence_mask, double clip_sigma, int niters, double *X,
+                             double *prior_sigma, double *prior_mu, double *w, double *model, uint8_t *outlier,
+                             double *spline_part, double *corrected, void *stream) {
+    return pld_correct_dev(h, B, N, P, Pb, pld_pix, bkg_pix, lc_flux, time, knots, n_inner, pld_order, pca_components, n_knots,
+                           spline_degree, normalize_bkg, K, y, err, cadence_mask, clip_sigma, niters, X, prior_sigma, prior_mu, w,
+                           model, outlier, spline_part, corrected, stream, nullptr, nullptr);
+}
+
+// lk_pld_correct_batch_dev for ragged pixel blocks: p_count / pb_count are DEVICE arrays of B entries (NULL = every column).
+int lk_pld_correct_ragged_batch_dev(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
+                                    const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
+                                    int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K,
+                                    const double *y, const double *err, const uint8_t *cadence_mask, double clip_sigma,
+                                    int niters, double *X, double *prior_sigma, double *prior_mu, double *w, double *model,
+                                    uint8_t *outlier, double *spline_part, double *corrected, void *stream,
+                                    const int32_t *p_count, const int32_t *pb_count) {
+    return pld_correct_dev(h, B, N, P, Pb, pld_pix, bkg_pix, lc_flux, time, knots, n_inner, pld_order, pca_components, n_knots,
+                           spline_degree, normalize_bkg, K, y, err, cadence_mask, clip_sigma, niters, X, prior_sigma, prior_mu, w,
+                           model, outlier, spline_part, corrected, stream, p_count, pb_count);
 }
 
 // ------------------------------------------------------------------------------------------------ resident pixel cubes
@@ -730,6 +803,29 @@ int lk_pld_gather_batch_dev(lk_handle *h, int B, int N, int npix, int n, const f
     return lk::pld_gather_launch(h, B, N, npix, n, cube, time, flux32, err32, keep, P, pld_idx_host, pld_idx_stride, Pb,
                                  bkg_idx_host, bkg_idx_stride, n_inner, knot_lo_host, knot_g_host, t_out, y_out, err_out,
                                  lcf_out, pld_out, bkg_out, knots_out, nonfinite_host, static_cast<hipStream_t>(stream));
+}
+
+int lk_cube_threshold_mask_batch_dev(lk_handle *h, int B, int ny, int nx, const double *median, double threshold, int use_ref,
+                                     double ref_col, double ref_row, int invert, uint8_t *mask, int32_t *count, int32_t *idx,
+                                     void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_threshold_mask_launch(h, B, ny, nx, median, threshold, use_ref, ref_col, ref_row, invert, mask, count, idx,
+                                          static_cast<hipStream_t>(stream));
+}
+
+int lk_pld_gather_ragged_batch_dev(lk_handle *h, int B, int N, int npix, int n, const float *cube, const double *time,
+                                   const float *flux32, const float *err32, const uint8_t *keep, int P, const int32_t *pld_idx,
+                                   int pld_idx_stride, int Pb, const int32_t *bkg_idx, int bkg_idx_stride, int n_inner,
+                                   const int32_t *knot_lo_host, const double *knot_g_host, double *t_out, double *y_out,
+                                   double *err_out, float *lcf_out, float *pld_out, float *bkg_out, double *knots_out,
+                                   int *nonfinite_host, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE((P == 0 || pld_idx) && (Pb == 0 || bkg_idx), "the ragged gather needs a device index list per block");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::pld_gather_launch(h, B, N, npix, n, cube, time, flux32, err32, keep, P, nullptr, pld_idx_stride, Pb, nullptr,
+                                 bkg_idx_stride, n_inner, knot_lo_host, knot_g_host, t_out, y_out, err_out, lcf_out, pld_out,
+                                 bkg_out, knots_out, nonfinite_host, static_cast<hipStream_t>(stream), pld_idx, bkg_idx);
 }
 
 // ------------------------------------------------------------------------------------------------ design-matrix operations

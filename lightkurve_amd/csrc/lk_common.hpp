@@ -150,7 +150,8 @@ int gram_plain_f32_launch(const float *pix, const float *div, const double *mean
 int pld_design_launch(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
                       const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
                       int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, double *X,
-                      double *prior_sigma, hipStream_t stream);
+                      double *prior_sigma, hipStream_t stream, const int32_t *p_count = nullptr,
+                      const int32_t *pb_count = nullptr);
 int pld_design_width(int P, int Pb, int pld_order, int pca_components, int n_knots);
 int dm_pca_launch(lk_handle *h, int B, int N, int P, int k, const double *A, double *U, hipStream_t stream);
 int dm_spline_launch(lk_handle *h, int B, int N, const double *x, const double *knots, int n_inner, int degree, double *out,
@@ -194,7 +195,11 @@ int pld_gather_launch(lk_handle *h, int B, int N, int npix, int n, const float *
                       const float *err32, const uint8_t *keep, int P, const int32_t *pld_idx_host, int pld_idx_stride, int Pb,
                       const int32_t *bkg_idx_host, int bkg_idx_stride, int n_inner, const int32_t *knot_lo_host,
                       const double *knot_g_host, double *t_out, double *y_out, double *err_out, float *lcf_out, float *pld_out,
-                      float *bkg_out, double *knots_out, int *nonfinite_host, hipStream_t stream);
+                      float *bkg_out, double *knots_out, int *nonfinite_host, hipStream_t stream,
+                      const int32_t *pld_idx_dev = nullptr, const int32_t *bkg_idx_dev = nullptr);
+int cube_threshold_mask_launch(lk_handle *h, int B, int ny, int nx, const double *median, double threshold, int use_ref,
+                               double ref_col, double ref_row, int invert, uint8_t *mask, int32_t *count, int32_t *idx,
+                               hipStream_t stream);
 int pld_corrected_launch(lk_handle *h, int B, int N, const double *y, const double *model, const double *spline, double *out,
                          hipStream_t stream);
 int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *y, const double *dy,

@@ -223,7 +223,8 @@ __global__ __launch_bounds__(256) void cube_compact_kernel(const uint8_t *__rest
 }
 
 // out[b][j][q] = cube[b][src[b][j]][idx[b][q]] (idx NULL: every pixel in place); a value that is not finite raises bit 0 of
-// *flags.
+// *flags.  A negative idx entry is padding (lk_pld_gather_ragged_batch_dev: cutouts whose masks differ in size share one row
+// pitch): that column is +0.0f in every row and does not count as a pixel; an entry >= npix raises bit 2 and reads nothing.
 __global__ __launch_bounds__(256) void cube_gather_kernel(const float *__restrict__ cube, const int *__restrict__ src,
                                                           const int *__restrict__ idx, int idx_stride, int N, int npix, int n,
                                                           int P, float *__restrict__ out, int *__restrict__ flags) {
@@ -233,16 +234,151 @@ __global__ __launch_bounds__(256) void cube_gather_kernel(const float *__restric
     const int *sb = src + (size_t)b * n;
     const int *ib = idx ? idx + (size_t)b * idx_stride : nullptr;
     if (*reinterpret_cast<volatile int *>(flags) & 2) return;  // cube_compact_kernel did not fill src (keep does not hold n)
-    bool bad = false;
+    bool bad = false, oob = false;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int j = (int)(i / P), q = (int)(i - (long long)j * P);
         const int row = sb[j];
         if ((unsigned)row >= (unsigned)N) continue;
-        const float v = cb[(size_t)row * npix + (ib ? ib[q] : q)];
+        const int px = ib ? ib[q] : q;
+        oob = oob || px >= npix;
+        const float v = (unsigned)px < (unsigned)npix ? cb[(size_t)row * npix + px] : 0.0f;
         out[(size_t)b * total + i] = v;
         bad = bad || !isfinite(v);
     }
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flags, 1);
+    if (__any(oob) && (threadIdx.x & 63) == 0) atomicOr(flags, 4);
+}
+
+// threshold_mask_from_median_image (correctors/pldcorrector.py; reference targetpixelfile.py:700-742) of one cutout per
+// workgroup, on the float64 median image cube_median_image_kernel wrote:
+//   vals = the finite pixels; mad = median(|vals - median(vals)|); cut = (1.4826 * mad * threshold) + nanmedian(image), every
+//   product and the sum rounded on its own in that order; mask = nan_to_num(image) >= cut (NaN -> 0, +-inf -> +-DBL_MAX).
+//   No finite pixel: the medians are NaN, so is the cut, and the mask is empty.
+// With a reference pixel (use_ref) and a mask that is not empty: 4-connected labelling by minimum-label propagation in LDS
+// (label = smallest pixel number of the region; every sweep also jumps to the label's own label) until a sweep changes
+// nothing, then the region of the masked pixel nearest to (ref_col, ref_row) is kept — squared distances in double, the first
+// minimum in row-major order (np.argmin over np.argwhere; tests/test_threshold_mask_cpu.py: same order as np.hypot).
+// invert flips the result ('background' = ~threshold_mask(0, None)).  Outputs: mask bytes, the count, and the selected pixel
+// numbers in ascending order padded with -1.  lab[] holds -1 for a pixel outside the mask.
+constexpr int TM_MAX_NPIX = LK_CUBE_MASK_MAX_NPIX;
+__global__ __launch_bounds__(256) void cube_threshold_mask_kernel(const double *__restrict__ median, int ny, int nx,
+                                                                  double threshold, int use_ref, double ref_col, double ref_row,
+                                                                  int invert, uint8_t *__restrict__ mask_out,
+                                                                  int *__restrict__ count_out, int *__restrict__ idx_out) {
+    __shared__ unsigned long long sh[264];
+    __shared__ int lab[TM_MAX_NPIX];
+    __shared__ int s_flag, s_cnt[4], s_bi[256];
+    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, npix = ny * nx;
+    const double *im = median + (size_t)b * npix;
+    auto finite = [&](int i) { return isfinite(im[i]); };
+    auto notnan = [&](int i) { return !isnan(im[i]); };
+    auto raw = [&](int i) { return im[i]; };
+    long long nf = 0, nn = 0;
+    for (int i = tid; i < npix; i += 256) {
+        nf += finite(i) ? 1 : 0;
+        nn += notnan(i) ? 1 : 0;
+    }
+    nf = block_count_dyn(nf, reinterpret_cast<long long *>(sh));
+    nn = block_count_dyn(nn, reinterpret_cast<long long *>(sh));
+    const double m1 = block_median(npix, nf, raw, finite, sh);
+    auto dev = [&](int i) { return fabs(im[i] - m1); };
+    const double mad = block_median(npix, nf, dev, finite, sh);
+    const double nanmed = block_median(npix, nn, raw, notnan, sh);
+    const double cut = __dadd_rn(__dmul_rn(__dmul_rn(1.4826, mad), threshold), nanmed);
+    int any = 0;
+    for (int i = tid; i < npix; i += 256) {
+        double v = im[i];
+        if (isnan(v)) v = 0.0;
+        else if (isinf(v)) v = v > 0.0 ? 1.7976931348623157e308 : -1.7976931348623157e308;
+        const bool in = v >= cut;
+        lab[i] = in ? i : -1;
+        any |= in ? 1 : 0;
+    }
+    if (tid == 0) s_flag = 0;
+    __syncthreads();
+    if (any) s_flag = 1;
+    __syncthreads();
+    const bool nonempty = s_flag != 0;
+    if (use_ref && nonempty) {
+        volatile int *vl = lab;
+        for (;;) {
+            __syncthreads();   // every thread has read the previous sweep's flag
+            if (tid == 0) s_flag = 0;
+            __syncthreads();
+            bool ch = false;
+            for (int i = tid; i < npix; i += 256) {
+                const int own = vl[i];
+                if (own < 0) continue;
+                const int r = i / nx, c = i - r * nx;
+                int m = own;
+                if (r > 0 && vl[i - nx] >= 0) m = min(m, vl[i - nx]);
+                if (r + 1 < ny && vl[i + nx] >= 0) m = min(m, vl[i + nx]);
+                if (c > 0 && vl[i - 1] >= 0) m = min(m, vl[i - 1]);
+                if (c + 1 < nx && vl[i + 1] >= 0) m = min(m, vl[i + 1]);
+                m = min(m, vl[m]);   // (m is a masked pixel of this region: its label is one too, and never larger)
+                if (m < own) {
+                    vl[i] = m;
+                    ch = true;
+                }
+            }
+            if (ch) s_flag = 1;
+            __syncthreads();
+            if (!s_flag) break;
+        }
+        // the masked pixel nearest to the reference pixel: (squared distance, pixel number) smallest first
+        double bd = __longlong_as_double(0x7ff0000000000000ll);
+        int bi = 0x7fffffff;
+        for (int i = tid; i < npix; i += 256) {
+            if (lab[i] < 0) continue;
+            const int r = i / nx, c = i - r * nx;
+            const double dr = (double)r - ref_row, dc = (double)c - ref_col;
+            const double d2 = __dadd_rn(__dmul_rn(dr, dr), __dmul_rn(dc, dc));
+            if (d2 < bd || (d2 == bd && i < bi)) {
+                bd = d2;
+                bi = i;
+            }
+        }
+        double *shd = reinterpret_cast<double *>(sh);
+        shd[tid] = bd;
+        s_bi[tid] = bi;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) {
+                const double od = shd[tid + s];
+                const int oi = s_bi[tid + s];
+                if (od < shd[tid] || (od == shd[tid] && oi < s_bi[tid])) {
+                    shd[tid] = od;
+                    s_bi[tid] = oi;
+                }
+            }
+            __syncthreads();
+        }
+        const int keep_label = lab[s_bi[0]];
+        __syncthreads();
+        for (int i = tid; i < npix; i += 256)
+            if (lab[i] != keep_label) lab[i] = -1;
+        __syncthreads();
+    }
+    // mask, count and the ascending index list (ballot scan over chunks of 256 pixels)
+    int base = 0;
+    for (int c0 = 0; c0 < npix; c0 += 256) {
+        const int i = c0 + tid;
+        const bool sel = i < npix && ((lab[i] >= 0) != (invert != 0));
+        const unsigned long long bal = __ballot(sel);
+        if (lane == 0) s_cnt[wave] = __popcll(bal);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) before += s_cnt[w];
+            all += s_cnt[w];
+        }
+        if (i < npix) mask_out[(size_t)b * npix + i] = sel ? 1 : 0;
+        if (sel) idx_out[(size_t)b * npix + base + before + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+        base += all;
+        __syncthreads();
+    }
+    for (int i = base + tid; i < npix; i += 256) idx_out[(size_t)b * npix + i] = -1;
+    if (tid == 0) count_out[b] = base;
 }
 
 // out = (y - model) + (spline - np.median(spline)) per cutout, or y - model without a spline part
@@ -302,11 +438,30 @@ int cube_median_image_launch(lk_handle *h, int B, int N, int npix, const float *
     return LK_OK;
 }
 
+int cube_threshold_mask_launch(lk_handle *h, int B, int ny, int nx, const double *median, double threshold, int use_ref,
+                               double ref_col, double ref_row, int invert, uint8_t *mask, int32_t *count, int32_t *idx,
+                               hipStream_t stream) {
+    (void)h;
+    LK_REQUIRE(B >= 1 && ny >= 1 && nx >= 1, "need B >= 1 cutouts of at least one pixel");
+    LK_REQUIRE((int64_t)ny * nx <= LK_CUBE_MASK_MAX_NPIX, "a %d x %d cutout has more than the %d pixels the device labelling holds in LDS",
+               ny, nx, LK_CUBE_MASK_MAX_NPIX);
+    LK_REQUIRE(median && mask && count && idx, "NULL buffer");
+    LK_REQUIRE(!use_ref || (ref_col == ref_col && ref_row == ref_row), "the reference pixel is NaN");
+    hipLaunchKernelGGL(cube_threshold_mask_kernel, dim3(B), dim3(256), 0, stream, median, ny, nx, threshold, use_ref, ref_col,
+                       ref_row, invert, mask, (int *)count, (int *)idx);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
 int pld_gather_launch(lk_handle *h, int B, int N, int npix, int n, const float *cube, const double *time, const float *flux32,
                       const float *err32, const uint8_t *keep, int P, const int32_t *pld_idx_host, int pld_idx_stride, int Pb,
                       const int32_t *bkg_idx_host, int bkg_idx_stride, int n_inner, const int32_t *knot_lo_host,
                       const double *knot_g_host, double *t_out, double *y_out, double *err_out, float *lcf_out, float *pld_out,
-                      float *bkg_out, double *knots_out, int *nonfinite_host, hipStream_t stream) {
+                      float *bkg_out, double *knots_out, int *nonfinite_host, hipStream_t stream, const int32_t *pld_idx_dev,
+                      const int32_t *bkg_idx_dev) {
+    // pld_idx_dev / bkg_idx_dev (lk_pld_gather_ragged_batch_dev): per-cutout index lists already on the device, -1 = padding,
+    // any stride >= P / Pb; the kernel checks their entries, the host lists are NULL then
+    const bool ragged = pld_idx_dev || bkg_idx_dev;
     LK_REQUIRE(B >= 1 && B <= 65535 && N >= 2 && npix >= 1 && n >= 1 && n <= N, "need 1 <= B <= 65535, N >= 2, npix >= 1, 1 <= n <= N");
     LK_REQUIRE(cube && keep && nonfinite_host, "NULL buffer");
     LK_REQUIRE((!y_out && !lcf_out) || flux32, "the SAP flux columns need flux32");
@@ -314,10 +469,16 @@ int pld_gather_launch(lk_handle *h, int B, int N, int npix, int n, const float *
     LK_REQUIRE(!t_out || time, "the compacted times need time");
     LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
     LK_REQUIRE(P >= 0 && P <= npix && Pb >= 0 && Pb <= npix, "P and Pb must be between 0 and npix");
-    LK_REQUIRE(pld_idx_host || P == 0 || P == npix, "pld_idx may only be NULL for all pixels or none");
-    LK_REQUIRE(bkg_idx_host || Pb == 0 || Pb == npix, "bkg_idx may only be NULL for all pixels or none");
-    LK_REQUIRE(pld_idx_stride == 0 || pld_idx_stride == P, "pld_idx_stride must be 0 (shared) or P");
-    LK_REQUIRE(bkg_idx_stride == 0 || bkg_idx_stride == Pb, "bkg_idx_stride must be 0 (shared) or Pb");
+    LK_REQUIRE(pld_idx_host || pld_idx_dev || P == 0 || P == npix, "pld_idx may only be NULL for all pixels or none");
+    LK_REQUIRE(bkg_idx_host || bkg_idx_dev || Pb == 0 || Pb == npix, "bkg_idx may only be NULL for all pixels or none");
+    if (ragged) {
+        LK_REQUIRE(!pld_idx_host && !bkg_idx_host, "index lists are either all on the host or all on the device");
+        LK_REQUIRE(!pld_idx_dev || pld_idx_stride >= P, "pld_idx_stride must be >= P");
+        LK_REQUIRE(!bkg_idx_dev || bkg_idx_stride >= Pb, "bkg_idx_stride must be >= Pb");
+    } else {
+        LK_REQUIRE(pld_idx_stride == 0 || pld_idx_stride == P, "pld_idx_stride must be 0 (shared) or P");
+        LK_REQUIRE(bkg_idx_stride == 0 || bkg_idx_stride == Pb, "bkg_idx_stride must be 0 (shared) or Pb");
+    }
     LK_REQUIRE(n_inner >= 0, "n_inner must be >= 0");
     if (knots_out) {
         LK_REQUIRE(t_out, "the knots are taken from the compacted times: t_out is NULL");
@@ -353,19 +514,20 @@ int pld_gather_launch(lk_handle *h, int B, int N, int npix, int n, const float *
     // finite-pixel count of cube_aperture instead)
     const int gx = (int)std::min<int64_t>(((int64_t)n * std::max(P, Pb) + 1023) / 1024 + 1, 4096);
     if (P > 0 && pld_out) {
-        hipLaunchKernelGGL(cube_gather_kernel, dim3(gx, B), dim3(256), 0, stream, cube, (const int *)d_src, (const int *)d_pi,
-                           pld_idx_stride, N, npix, n, P, pld_out, d_flags);
+        hipLaunchKernelGGL(cube_gather_kernel, dim3(gx, B), dim3(256), 0, stream, cube, (const int *)d_src,
+                           pld_idx_dev ? (const int *)pld_idx_dev : (const int *)d_pi, pld_idx_stride, N, npix, n, P, pld_out, d_flags);
         LK_HIP_CHECK(hipGetLastError());
     }
     if (Pb > 0 && bkg_out) {
-        hipLaunchKernelGGL(cube_gather_kernel, dim3(gx, B), dim3(256), 0, stream, cube, (const int *)d_src, (const int *)d_bi,
-                           bkg_idx_stride, N, npix, n, Pb, bkg_out, d_flags);
+        hipLaunchKernelGGL(cube_gather_kernel, dim3(gx, B), dim3(256), 0, stream, cube, (const int *)d_src,
+                           bkg_idx_dev ? (const int *)bkg_idx_dev : (const int *)d_bi, bkg_idx_stride, N, npix, n, Pb, bkg_out, d_flags);
         LK_HIP_CHECK(hipGetLastError());
     }
     int flags = 0;
     LK_HIP_CHECK(hipMemcpyAsync(&flags, d_flags, 4, hipMemcpyDeviceToHost, stream));
     LK_HIP_CHECK(hipStreamSynchronize(stream));
     LK_REQUIRE(!(flags & 2), "keep does not flag exactly n = %d cadences in every cutout", n);
+    LK_REQUIRE(!(flags & 4), "an index list names a pixel outside the cutout's %d", npix);
     *nonfinite_host = flags & 1;
     return LK_OK;
 }

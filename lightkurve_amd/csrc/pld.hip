@@ -1530,11 +1530,20 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
                                                              double *__restrict__ scratch, double *__restrict__ V,
                                                              double *__restrict__ lam, long long *__restrict__ iters_out,
                                                              int max_it, int *__restrict__ status, int cheb_on, int kc,
-                                                             int mirror, double tol, const float *__restrict__ G32 = nullptr) {
+                                                             int mirror, double tol, const float *__restrict__ G32 = nullptr,
+                                                             const int *__restrict__ pcount = nullptr) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x, nt = blockDim.x, b = blockIdx.x;
     double *Gb = G + (size_t)b * ldg * ldg;
     double *Vb = V + (size_t)b * P * k, *lamb = lam + (size_t)b * k;
+    const size_t scr_stride = (size_t)4 * P * l;   // (of the subspace iteration: laid out for the batch's P)
+    // ragged batches: this matrix's own leading block (see pld_tridiag_eig_kernel); a block no wider than the basis takes the
+    // direct Jacobi below, whatever route the batch's widest block chose
+    if (pcount) {
+        const int Pown = min(max(pcount[b], 1), P);
+        for (int e = Pown * k + tid; e < P * k; e += nt) Vb[e] = 0.0;
+        P = Pown;
+    }
     const int ld = l + 1;                      // odd leading dimension: conflict-free column walks
     const int oT = 0, oW = l * ld, orot = 2 * l * ld, oshred = orot + 2 * l, ovec = oshred + nt, oorder = ovec + 2 * l,
               oqstage = oorder + (l + 1) / 2 + 1;
@@ -1597,11 +1606,12 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
         }
         if (tid < k) lamb[tid] = T[order[tid] * ld + order[tid]];
         if (tid == 0 && iters_out) iters_out[(size_t)b * 8] = 0;
+        if (tid == 0 && status) status[b] = 1;   // (a ragged batch's narrow block in the two-pass form: solved here)
         return;
     }
 
     // ---- subspace iteration with Rayleigh-Ritz steps
-    double *Q = scratch + (size_t)b * 4 * P * l, *Z = Q + (size_t)P * l, *R = Z + (size_t)P * l, *Y = R + (size_t)P * l;
+    double *Q = scratch + b * scr_stride, *Z = Q + (size_t)P * l, *R = Z + (size_t)P * l, *Y = R + (size_t)P * l;
     const int kc32 = (int)(((size_t)kc * PLD_QS * 8) / ((size_t)pld_qs32(NA) * 4)) / 24 * 24;  // the float32 stage fills the same LDS region
     const EigCtx ctx{oT, oW, orot, oshred, ovec, oqstage, oorder, Gb, G32 ? G32 + (size_t)b * ldg * ldg : nullptr, ldg, P, k, l, ld, kc, kc32};
     long long tprof[7] = {0, 0, 0, 0, 0, 0, 0}, tlast = iters_out ? (long long)wall_clock64() : 0;
@@ -1935,7 +1945,8 @@ __device__ __forceinline__ int td_tri(int i, int j) { return ((i * (i + 1)) >> 1
 // interleave, instead of two rounds of one latency-bound workgroup per CU.
 __global__ __launch_bounds__(TD_NT, 8) void pld_tridiag_eig_kernel(const double *__restrict__ G, int ldg, int P, int k,
                                                                     double *__restrict__ V, double *__restrict__ lam,
-                                                                    unsigned long long *__restrict__ clk, int tdl) {
+                                                                    unsigned long long *__restrict__ clk, int tdl,
+                                                                    const int *__restrict__ pcount) {
 #ifdef LK_PLD_DEBUG   // per-phase clocks of matrix 0 (100 MHz wall clock), `make DEBUG=1`
 #define TD_CLK(slot)                                                                 \
     do {                                                                             \
@@ -1959,6 +1970,15 @@ __global__ __launch_bounds__(TD_NT, 8) void pld_tridiag_eig_kernel(const double 
     }
 #endif
     const double *Gb = G + (size_t)b * ldg * ldg;
+    // Ragged batches (pcount: this matrix's own column count, k <= pcount[b] <= P): the columns behind it are padding — zero
+    // rows and columns of G.  The solver works on the leading pcount[b] x pcount[b] block alone, exactly as it would for this
+    // cutout in a call of its own, and the padding's rows of V are zero (the top-k eigenvectors of the padded matrix).
+    double *Z = V + (size_t)b * P * k;      // P x k eigenvectors (row-major): the output array itself
+    if (pcount) {
+        const int Pown = min(max(pcount[b], 1), P);
+        for (int e = Pown * k + tid; e < P * k; e += TD_NT) Z[e] = 0.0;
+        P = Pown;
+    }
     const int ntri = (P * (P + 1)) >> 1;
     double *At = lds;                       // packed lower triangle
     double *dd = At + ((ntri + 1) & ~1);    // diagonal of T
@@ -1971,7 +1991,6 @@ __global__ __launch_bounds__(TD_NT, 8) void pld_tridiag_eig_kernel(const double 
     double *lamv = vb + P;                  // k eigenvalues (descending)
     double *zinv = lamv + ((k + 1) & ~1);   // 1 / norm of the k twisted-factorisation vectors
     double *ws = zinv + ((k + 1) & ~1);     // tdl x 2 x P scratch of the twisted factorisations, [which][i][lane]
-    double *Z = V + (size_t)b * P * k;      // P x k eigenvectors (row-major): the output array itself
     // ---- load the lower triangle (G's upper triangle is always valid: element (i, j <= i) = G[j][i])
     for (int j = wave; j < P; j += NW)  // row j of G from its diagonal on: coalesced
         for (int i = j + lane; i < P; i += 64) At[td_tri(i, j)] = Gb[(size_t)j * ldg + i];
@@ -2389,7 +2408,8 @@ __global__ __launch_bounds__(TD_NT, 8) void pld_tridiag_eig_kernel(const double 
 // top-k eigenpairs of the B Gram matrices G (P x P, leading dimension ldg) -> V (B x P x k), lam (B x k), both allocated
 // from ws.  mirror: G holds the upper 64 x 64 blocks only (gram_plain_launch) and is completed in place first.
 static int eig_topk(lk_handle *h, double *G, int ldg, int B, int P, int k, bool products, bool mirror, double **V_out,
-                    double **lam_out, hipStream_t stream, Arena &ws, const float *G32 = nullptr, double tol = -1.0) {
+                    double **lam_out, hipStream_t stream, Arena &ws, const float *G32 = nullptr, double tol = -1.0,
+                    const int *pcount = nullptr) {   // pcount: per-matrix column counts of a ragged batch (device, or nullptr)
     if (!(tol > 0.0)) tol = h->pld_eig_tol > 0.0 ? h->pld_eig_tol : PLD_EIG_TOL;   // (lk_pld_set_eig_tolerance)
     constexpr int direct_max = PLD_DIRECT_MAX;
     // Convergence: || C r - theta r || <= tol * theta_max * sqrt(k) over the k wanted pairs (PLD_EIG_TOL / PCA_EIG_TOL above).
@@ -2439,7 +2459,7 @@ static int eig_topk(lk_handle *h, double *G, int ldg, int B, int P, int k, bool 
 #ifdef LK_PLD_DEBUG
         if (dbg_iters) d_clk = (unsigned long long *)ws.alloc(64 + 96 * (size_t)B + 64);
 #endif
-        hipLaunchKernelGGL(pld_tridiag_eig_kernel, dim3(B), dim3(TD_NT), lds, stream, G, ldg, P, k, V, lam, d_clk, tdl);
+        hipLaunchKernelGGL(pld_tridiag_eig_kernel, dim3(B), dim3(TD_NT), lds, stream, G, ldg, P, k, V, lam, d_clk, tdl, pcount);
 #ifdef LK_PLD_DEBUG
         if (d_clk) {
             unsigned long long hc[8];
@@ -2543,10 +2563,10 @@ static int eig_topk(lk_handle *h, double *G, int ldg, int B, int P, int k, bool 
         long long *d_it = dbg_iters ? (long long *)ws.alloc((size_t)B * 64) : nullptr;
         if (l <= 32)
             hipLaunchKernelGGL(pld_topk_eig_kernel<2>, dim3(B), dim3(nt_sub), lds, stream, G, ldg, P, k, l, npow, scr, V, lam,
-                               d_it, two_pass ? 8 : 400, status, cheb_on, kc, mirror ? 1 : 0, tol, G32);
+                               d_it, two_pass ? 8 : 400, status, cheb_on, kc, mirror ? 1 : 0, tol, G32, pcount);
         else
             hipLaunchKernelGGL(pld_topk_eig_kernel<4>, dim3(B), dim3(nt_sub), lds, stream, G, ldg, P, k, l, npow, scr, V, lam,
-                               d_it, two_pass ? 8 : 400, status, cheb_on, kc, mirror ? 1 : 0, tol, G32);
+                               d_it, two_pass ? 8 : 400, status, cheb_on, kc, mirror ? 1 : 0, tol, G32, pcount);
         if (d_it) {
             std::vector<long long> hit((size_t)B * 8);
             LK_HIP_CHECK(hipMemcpyAsync(hit.data(), d_it, (size_t)B * 64, hipMemcpyDeviceToHost, stream));
@@ -2589,7 +2609,7 @@ static int eig_topk(lk_handle *h, double *G, int ldg, int B, int P, int k, bool 
         const size_t lds = two_pass ? ((size_t)l * ld + 2 * l + nt_eig + 2 * l + (l + 1) / 2 + 1) * 8 + 64
                                     : ((size_t)2 * l * ld + 2 * l + 1024 + 2 * l + (l + 1) / 2 + 1) * 8 + 64;
         hipLaunchKernelGGL(pld_topk_eig_kernel<2>, dim3(B), dim3(nt_eig), lds, stream, G, ldg, P, k, l, npow, scr, V, lam,
-                           (long long *)nullptr, 400, status, cheb_on, PLD_KC, mirror ? 1 : 0, tol);
+                           (long long *)nullptr, 400, status, cheb_on, PLD_KC, mirror ? 1 : 0, tol, (const float *)nullptr, pcount);
     }
     *V_out = V;
     *lam_out = lam;
@@ -2606,7 +2626,7 @@ struct PcaF32Source {  // the block as float32 pixels: A = (double)(mode == 0 ? 
 static bool pca_f32_ok(int P, int k) { return P >= 4 && (P + 15) / 16 <= 9 && k <= 48; }
 static int pca_block(lk_handle *h, double *A, int B, int N, int P, int k, const int64_t *d_off, double *X, int ldx,
                      int col0, hipStream_t stream, Arena &ws, bool centred = false, bool products = false,
-                     double tol = -1.0, PcaF32Source fs = PcaF32Source{nullptr, nullptr, nullptr, 0}) {
+                     double tol = -1.0, PcaF32Source fs = PcaF32Source{nullptr, nullptr, nullptr, 0}, const int *pcount = nullptr) {
     const bool f32src = fs.pix != nullptr;
     if (!centred && !f32src) hipLaunchKernelGGL(pld_center_kernel, dim3((P + 31) / 32, B), dim3(256), 0, stream, A, N, P);
     const int KB = (P + 63) / 64, ldg = KB * 64;
@@ -2624,7 +2644,7 @@ static int pca_block(lk_handle *h, double *A, int B, int N, int P, int k, const 
         gram_plain_launch(A, d_off, B, P, G, stream, h);
     }
     double *V = nullptr, *lam = nullptr;
-    const int rc = eig_topk(h, G, ldg, B, P, k, products, true, &V, &lam, stream, ws, nullptr, tol);
+    const int rc = eig_topk(h, G, ldg, B, P, k, products, true, &V, &lam, stream, ws, nullptr, tol, pcount);
     if (rc) return rc;
     {
         const dim3 grid((N + 63) / 64, B), blk(256);
@@ -2831,7 +2851,12 @@ static int pca_products_moment(lk_handle *h, const MomentPlan &pl, int B, int N,
 int pld_design_launch(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
                       const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
                       int pca_components, int n_knots, int spline_degree, int normalize_bkg, int K, double *X,
-                      double *prior_sigma, hipStream_t stream) {
+                      double *prior_sigma, hipStream_t stream, const int32_t *p_count, const int32_t *pb_count) {
+    // p_count / pb_count (device, B entries, or nullptr): ragged batches — cutout b's pixel blocks hold p_count[b] / pb_count[b]
+    // real columns followed by columns of +0.0f up to the row pitch P / Pb.  Zero columns have zero means, zero centred values
+    // and zero rows and columns in the Gram matrix; the eigen-solvers take each matrix's own leading block (eig_topk) and give
+    // the padding zero eigenvector rows, so the projections add exact zeros.  Every count must be >= pca_components (one design
+    // width per call): the C ABI checks that before it comes here.
     LK_REQUIRE(B >= 1 && N >= 2, "need B >= 1 cutouts with N >= 2 cadences");
     LK_REQUIRE(pca_components >= 1 && pca_components <= 48, "pca_components must be between 1 and 48 on the HIP path");
     LK_REQUIRE(pld_order >= 0 && pld_order <= 4, "pld_order outside 0..4");
@@ -2866,10 +2891,12 @@ int pld_design_launch(lk_handle *h, int B, int N, int P, int Pb, const float *pl
         LK_REQUIRE(d_cm != nullptr, "PLD workspace exhausted (column means)");
         hipLaunchKernelGGL(pld_colmean_kernel, dim3(B), dim3(1024), 0, stream, pld_pix, lc_flux, 1, N, P, d_cm);
         if (pca_f32_ok(P, k1)) {  // the Gram kernel and the projection form pix / flux - mean themselves
-            rc = pca_block(h, nullptr, B, N, P, k1, d_off, X, K, col, stream, h->ws, true, false, -1.0, PcaF32Source{pld_pix, lc_flux, d_cm, 1});
+            rc = pca_block(h, nullptr, B, N, P, k1, d_off, X, K, col, stream, h->ws, true, false, -1.0, PcaF32Source{pld_pix, lc_flux, d_cm, 1},
+                           (const int *)p_count);
         } else {
             hipLaunchKernelGGL(pld_ratio_kernel, dim3((N + 31) / 32, B), dim3(256), 0, stream, pld_pix, lc_flux, 1, N, P, A, d_cm, (const float *)nullptr);
-            rc = pca_block(h, A, B, N, P, k1, d_off, X, K, col, stream, h->ws, true);
+            rc = pca_block(h, A, B, N, P, k1, d_off, X, K, col, stream, h->ws, true, false, -1.0, PcaF32Source{nullptr, nullptr, nullptr, 0},
+                           (const int *)p_count);
         }
         if (rc) return rc;
         const int col1 = col;
@@ -2945,9 +2972,10 @@ int pld_design_launch(lk_handle *h, int B, int N, int P, int Pb, const float *pl
     }
     const int kb = std::min(pca_components, Pb);
     if (bkg_f32)
-        rc = pca_block(h, nullptr, B, N, Pb, kb, d_off, X, K, col, stream, h->ws, true, false, -1.0, bkg_src);
+        rc = pca_block(h, nullptr, B, N, Pb, kb, d_off, X, K, col, stream, h->ws, true, false, -1.0, bkg_src, (const int *)pb_count);
     else
-        rc = pca_block(h, A, B, N, Pb, kb, d_off, X, K, col, stream, h->ws, true);
+        rc = pca_block(h, A, B, N, Pb, kb, d_off, X, K, col, stream, h->ws, true, false, -1.0, PcaF32Source{nullptr, nullptr, nullptr, 0},
+                       (const int *)pb_count);
     if (rc) return rc;
     col += kb;
     hipLaunchKernelGGL(pld_spline_kernel, dim3((N + 255) / 256, B), dim3(256), 0, stream, time, knots, n_inner,

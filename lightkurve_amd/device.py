@@ -828,36 +828,78 @@ class DevicePixelCubeBatch(object):
                 return None
             raise ValueError("aperture_mask '{}' is not supported here".format(spec))
         m = np.asarray(spec, dtype=bool)
+        if m.shape == (self.shape[0], ny, nx):          # one mask per cutout
+            return m
         if m.shape != (ny, nx):
             raise ValueError("`aperture_mask` has shape {}, but the flux data has shape {}".format(m.shape, (ny, nx)))
         return m
 
-    def median_images(self, d_keep=None):
-        """np.nanmedian(flux.astype(float64), axis=0) of every cutout, computed on the device (``lk_cube_median_image_batch_dev``)
-        over all cadences or those flagged in ``d_keep`` (DeviceBuffer of B x N bytes) -> float64[B, ny, nx] on the host."""
+    def _median_images_dev(self, d_keep=None):
         B, N, ny, nx = self.shape
         d_med = DeviceBuffer(self.handle, B * ny * nx * 8)
         _capi._check(_capi._lib.lk_cube_median_image_batch_dev(self.handle._h, B, N, ny * nx, _vp(self.d_flux.ptr),
                                                                _vp(d_keep.ptr if d_keep is not None else None), _vp(d_med.ptr),
                                                                _vp(self.stream or None)))
-        return d_med.download(np.float64, B * ny * nx, stream=self.stream).reshape(B, ny, nx)
+        return d_med
 
-    def _masks(self, spec, sap, median):
-        """-> bool (ny, nx) shared by the batch, or bool (B, ny, nx) for a data-dependent spec evaluated on every cutout's own
-        median image (``median()`` computes them once per call) as ``PixelCube._parse_aperture_mask`` would."""
+    def median_images(self, d_keep=None):
+        """np.nanmedian(flux.astype(float64), axis=0) of every cutout, computed on the device (``lk_cube_median_image_batch_dev``)
+        over all cadences or those flagged in ``d_keep`` (DeviceBuffer of B x N bytes) -> float64[B, ny, nx] on the host."""
+        B, N, ny, nx = self.shape
+        return self._median_images_dev(d_keep).download(np.float64, B * ny * nx, stream=self.stream).reshape(B, ny, nx)
+
+    def threshold_masks(self, threshold=3, reference_pixel="center", d_keep=None, to_host=True, invert=False, _d_median=None):
+        """``PixelCube.create_threshold_mask(threshold, reference_pixel)`` of every cutout (reference targetpixelfile.py:680-742),
+        equal to ``threshold_mask_from_median_image`` pixel for pixel, without leaving the device: the median images
+        (``lk_cube_median_image_batch_dev`` over all cadences or those flagged in ``d_keep``), then the MAD cut, the 4-connected
+        labelling and the choice of the region nearest to ``reference_pixel`` ((column, row), "center" or None) in
+        ``lk_cube_threshold_mask_batch_dev``.  ``invert=True`` returns the complement ('background' is
+        ``threshold_masks(0, None, invert=True)``).  ``to_host=True`` -> bool (B, ny, nx); ``to_host=False`` -> DeviceBuffers
+        (mask B x npix bytes, count B int32, idx B x npix int32: the selected pixel numbers ascending, then -1), enqueued on the
+        batch's stream.  Cutouts of more than ``_capi.CUBE_MASK_MAX_NPIX`` pixels take the host function (``to_host=True``
+        only)."""
         from .correctors.pldcorrector import threshold_mask_from_median_image as from_median
+        h, (B, N, ny, nx) = self.handle, self.shape
+        npix = ny * nx
+        if npix > _capi.CUBE_MASK_MAX_NPIX:
+            if not to_host:
+                raise ValueError("threshold_masks(to_host=False) holds the labels of at most %d pixels per cutout (got %d x %d)"
+                                 % (_capi.CUBE_MASK_MAX_NPIX, ny, nx))
+            med = self.median_images(d_keep)
+            m = np.stack([from_median(im, threshold, reference_pixel) for im in med])
+            return ~m if invert else m
+        if isinstance(reference_pixel, str):
+            if reference_pixel != "center":
+                raise ValueError("reference_pixel must be (column, row), 'center' or None")
+            reference_pixel = (nx / 2, ny / 2)
+        d_med = _d_median if _d_median is not None else self._median_images_dev(d_keep)
+        d_mask, d_cnt, d_idx = DeviceBuffer(h, B * npix), DeviceBuffer(h, B * 4), DeviceBuffer(h, B * npix * 4)
+        use_ref = reference_pixel is not None
+        _capi._check(_capi._lib.lk_cube_threshold_mask_batch_dev(
+            h._h, B, ny, nx, _vp(d_med.ptr), float(threshold), int(use_ref), float(reference_pixel[0]) if use_ref else 0.0,
+            float(reference_pixel[1]) if use_ref else 0.0, int(bool(invert)), _vp(d_mask.ptr), _vp(d_cnt.ptr), _vp(d_idx.ptr),
+            _vp(self.stream or None)))
+        if not to_host:
+            return d_mask, d_cnt, d_idx         # (d_med goes back to the pool: its next user is ordered behind this stream's kernel)
+        return d_mask.download(np.uint8, B * npix, stream=self.stream).reshape(B, ny, nx).astype(bool)
+
+    def _masks(self, spec, sap, d_keep, cache):
+        """-> bool (ny, nx) shared by the batch, or bool (B, ny, nx): masks given per cutout, or a data-dependent spec evaluated
+        on every cutout's own median image as ``PixelCube._parse_aperture_mask`` would — on the device (``threshold_masks``; the
+        median images are computed once per call, kept in ``cache``, and never downloaded; B x npix mask bytes come back)."""
         m = self._shape_mask(spec, sap)
         if m is not None:
             return m
-        med = median()
+        if self.shape[2] * self.shape[3] <= _capi.CUBE_MASK_MAX_NPIX and "median" not in cache:
+            cache["median"] = self._median_images_dev(d_keep)
         if spec == "background":
-            return np.stack([~from_median(im, threshold=0, reference_pixel=None) for im in med])
-        return np.stack([from_median(im, 3) for im in med])
+            return self.threshold_masks(0, None, d_keep, invert=True, _d_median=cache.get("median"))
+        return self.threshold_masks(3, "center", d_keep, _d_median=cache.get("median"))
 
     def _aperture(self, aperture_mask):
         """``lk_cube_aperture_batch_dev``: -> (d_flux32, d_err32, d_keep, kept[B], nonfinite[B])."""
         h, (B, N, ny, nx) = self.handle, self.shape
-        ap = self._masks(aperture_mask, True, lambda: self.median_images(None))
+        ap = self._masks(aperture_mask, True, None, {})
         d_mask, k = _upload(h, ap.reshape(-1, ny * nx), self.stream, np.uint8)
         d_f, d_e, d_k = DeviceBuffer(h, B * N * 4), DeviceBuffer(h, B * N * 4), DeviceBuffer(h, B * N)
         kept, dirty = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
@@ -871,8 +913,11 @@ class DevicePixelCubeBatch(object):
             raise ValueError("pld_correct_batch needs cutouts with the same number of valid cadences")
         return d_f, d_e, d_k, n, dirty
 
-    def _gather(self, d_f, d_e, d_k, n, pld_idx=None, P=0, bkg_idx=None, Pb=0, want_pld=False, want_bkg=False, knot_plan=None):
-        """``lk_pld_gather_batch_dev`` -> dict of DeviceBuffers (time, y, err, lcf, pld, bkg, knots) + 'nonfinite'."""
+    def _gather(self, d_f, d_e, d_k, n, pld_idx=None, P=0, bkg_idx=None, Pb=0, want_pld=False, want_bkg=False, knot_plan=None,
+                ragged=False):
+        """``lk_pld_gather_batch_dev`` -> dict of DeviceBuffers (time, y, err, lcf, pld, bkg, knots) + 'nonfinite'.  ``ragged``:
+        ``pld_idx`` / ``bkg_idx`` are (DeviceBuffer, stride) pairs of -1-padded per-cutout lists and P / Pb the row pitch
+        (``lk_pld_gather_ragged_batch_dev``)."""
         h, (B, N, ny, nx) = self.handle, self.shape
         out = dict(time=DeviceBuffer(h, B * n * 8), y=DeviceBuffer(h, B * n * 8), err=DeviceBuffer(h, B * n * 8),
                    lcf=DeviceBuffer(h, B * n * 4), pld=None, bkg=None, knots=None)
@@ -893,13 +938,17 @@ class DevicePixelCubeBatch(object):
         def idx(a):
             return (None, 0) if a is None else (a.ctypes.data_as(_i32p), a.shape[1] if a.shape[0] > 1 else 0)
 
-        (pi, ps), (bi, bs) = idx(pld_idx), idx(bkg_idx)
+        def didx(a):
+            return (None, 0) if a is None else (_vp(a[0].ptr), int(a[1]))
+
+        (pi, ps), (bi, bs) = (didx(pld_idx), didx(bkg_idx)) if ragged else (idx(pld_idx), idx(bkg_idx))
         flag = np.zeros(1, dtype=np.int32)
-        _capi._check(_capi._lib.lk_pld_gather_batch_dev(
+        fn = _capi._lib.lk_pld_gather_ragged_batch_dev if ragged else _capi._lib.lk_pld_gather_batch_dev
+        _capi._check(fn(
             h._h, B, N, ny * nx, n, _vp(self.d_flux.ptr), _vp(self.d_time.ptr), _vp(d_f.ptr), _vp(d_e.ptr), _vp(d_k.ptr), int(P), pi,
             ps, int(Pb), bi, bs, n_inner, None if lo is None or not n_inner else lo.ctypes.data_as(_i32p),
             None if g is None or not n_inner else g.ctypes.data_as(_dp), ptr("time"), ptr("y"), ptr("err"), ptr("lcf"), ptr("pld"),
-            ptr("bkg"), ptr("knots"), flag.ctypes.data_as(_i32p), _vp(self.stream or None)))    # (synchronises)
+            ptr("bkg"), ptr("knots"), flag.ctypes.data_as(_i32p), _vp(self.stream or None)))      # (synchronises)
         out["nonfinite"] = bool(flag[0])
         return out
 
@@ -919,13 +968,17 @@ class DevicePixelCubeBatch(object):
     # ---------------------------------------------------------------- PLD
     def pld_correct(self, aperture_mask="all", pld_aperture_mask="all", background_aperture_mask="all", pld_order=3,
                     pca_components=16, spline_n_knots=None, spline_degree=5, normalize_background_pixels=True,
-                    restore_trend=True, cadence_mask=None, sigma=5, niters=5, to_host=True):
+                    restore_trend=True, cadence_mask=None, sigma=5, niters=5, to_host=True, ragged_masks=False):
         """``pld_correct_batch`` (same defaults and meaning; reference ``PLDCorrector(tpf, aperture_mask).correct(...)``,
         pldcorrector.py:304-427) on the resident cubes, bit-identical to it.  ``cadence_mask``: optional bool (B, n) over the
         KEPT cadences, True = used in the fit.  ``to_host=True`` -> (corrected[B, n], outlier_mask[B, n]) numpy arrays;
         ``to_host=False`` -> (``DeviceLightCurveBatch`` of the compacted times, the corrected flux and the SAP flux errors,
-        ``DeviceBuffer`` of the B x n outlier bytes)."""
-        from .correctors.pldcorrector import _percentile_knot_plan
+        ``DeviceBuffer`` of the B x n outlier bytes).  Each mask may also be a bool (B, ny, nx) array, one mask per cutout.
+        ``ragged_masks=True`` accepts PLD / background masks that select DIFFERENT numbers of pixels per cutout — the usual case
+        for 'threshold' / 'background' on real fields — through zero-padded pixel blocks and per-cutout counts
+        (``lk_pld_gather_ragged_batch_dev``, ``lk_pld_correct_ragged_batch_dev``); every count must be at least
+        ``pca_components`` (ValueError names the cutouts).  When all sizes are equal the call is the one without the keyword."""
+        from .correctors.pldcorrector import _percentile_knot_plan, _ragged_index_lists
         if pca_components is None or pca_components < 1:
             raise NotImplementedError("pca_components must be >= 1 on the HIP path")
         if not self.is_sorted:
@@ -936,37 +989,49 @@ class DevicePixelCubeBatch(object):
         d_f, d_e, d_k, n, dirty = self._aperture(aperture_mask)
         if n < 2:
             raise ValueError("pld_correct needs at least two cadences with a finite aperture flux (got %d)" % n)
-        cache = []
-
-        def median():                               # over the KEPT cadences (the corrector sees tpf[~nan_mask]); once per call
-            if not cache:
-                cache.append(self.median_images(d_k))
-            return cache[0]
-
-        pm = self._masks(pld_aperture_mask, False, median)
-        bm = self._masks(background_aperture_mask, False, median)
+        cache = {}                                  # the median images over the KEPT cadences (the corrector sees tpf[~nan_mask])
+        pm = self._masks(pld_aperture_mask, False, d_k, cache)
+        bm = self._masks(background_aperture_mask, False, d_k, cache)
         counts_p, counts_b = pm.reshape(-1, npix).sum(axis=1), bm.reshape(-1, npix).sum(axis=1)
-        if len(set(counts_p.tolist())) > 1 or len(set(counts_b.tolist())) > 1:
+        ragged = len(set(counts_p.tolist())) > 1 or len(set(counts_b.tolist())) > 1
+        if ragged and not ragged_masks:
             raise ValueError("pld_correct_batch: the per-cutout '%s' / '%s' masks select different numbers of pixels (%s PLD, %s "
                              "background); pass masks of one size or correct these cutouts one by one"
                              % (pld_aperture_mask, background_aperture_mask, sorted(set(counts_p.tolist())),
                                 sorted(set(counts_b.tolist()))))
-        P, Pb = int(counts_p[0]), int(counts_b[0])
+        P, Pb = int(counts_p.max()), int(counts_b.max())       # (ragged: the row pitch of the zero-padded blocks)
         same = pm.shape == bm.shape and np.array_equal(pm, bm)
-        resident = n == N                           # full mask and no dropped cadence: the block IS the resident cube
+        resident = n == N and not ragged            # full mask and no dropped cadence: the block IS the resident cube
 
         def index_lists(m, count):
             if count == npix or count == 0:
                 return None
             return np.ascontiguousarray([np.flatnonzero(r) for r in m.reshape(-1, npix)], dtype=np.int32)
 
-        pld_idx, bkg_idx = index_lists(pm, P), index_lists(bm, Pb)
+        keep = []
+        d_pc = d_bc = None
+        if ragged:
+            # per-cutout ascending pixel lists padded with -1 to the pitch + the counts, uploaded once (B x (P + Pb + 2) int32)
+            def lists(m, what):
+                if not m.any():
+                    return None, None
+                idx, cnt = _ragged_index_lists(np.broadcast_to(m.reshape(-1, npix), (B, npix)), pca_components, what)
+                d_i, k1 = _upload(h, idx, self.stream, np.int32)
+                d_c, k2 = _upload(h, cnt, self.stream, np.int32)
+                keep.extend([k1, k2])
+                return (d_i, idx.shape[1]), d_c
+
+            pld_idx, d_pc = lists(pm, "PLD")
+            bkg_idx, d_bc = (pld_idx, d_pc) if same else lists(bm, "background")
+        else:
+            pld_idx, bkg_idx = index_lists(pm, P), index_lists(bm, Pb)
         want_pld = P > 0 and not (resident and P == npix)
         want_bkg = Pb > 0 and not same and not (resident and Pb == npix)
         if spline_n_knots is None:
             spline_n_knots = int(n / 50)
         plan = _percentile_knot_plan(n, int(spline_n_knots), int(spline_degree))
-        g = self._gather(d_f, d_e, d_k, n, pld_idx, P, None if same else bkg_idx, 0 if same else Pb, want_pld, want_bkg, plan)
+        g = self._gather(d_f, d_e, d_k, n, pld_idx, P, None if same else bkg_idx, 0 if same else Pb, want_pld, want_bkg, plan,
+                         ragged=ragged)
         whole_image = (P == npix and not want_pld) or (Pb == npix and not want_bkg and not same)
         if g["nonfinite"] or (whole_image and dirty.any()):
             raise ValueError("pld_correct_batch needs finite pixels inside the masks")
@@ -975,7 +1040,6 @@ class DevicePixelCubeBatch(object):
         n_inner = len(plan[0])
         n_knots = n_inner + int(spline_degree) + 1
         K = _capi.pld_design_width(P, Pb, pld_order, pca_components, n_knots)
-        keep = []
         d_cm = None
         if cadence_mask is not None:
             cm = np.ascontiguousarray(cadence_mask, dtype=np.uint8)
@@ -988,12 +1052,16 @@ class DevicePixelCubeBatch(object):
         d_model, d_corr = DeviceBuffer(h, B * n * 8), DeviceBuffer(h, B * n * 8)
         d_sp = DeviceBuffer(h, B * n * 8) if restore_trend else None
         d_outl = DeviceBuffer(h, B * n)
-        _capi._check(_capi._lib.lk_pld_correct_batch_dev(
-            h._h, B, n, P, Pb, _vp(d_pld.ptr if d_pld is not None else None), _vp(d_bkg.ptr), _vp(g["lcf"].ptr), _vp(g["time"].ptr),
-            _vp(g["knots"].ptr), n_inner, int(pld_order), int(pca_components), n_knots, int(spline_degree),
-            int(bool(normalize_background_pixels)), K, _vp(g["y"].ptr), _vp(g["err"].ptr), _vp(d_cm.ptr if d_cm is not None else None),
-            float(sigma), int(niters), _vp(d_X.ptr), _vp(d_ps.ptr), _vp(d_mu.ptr), _vp(d_w.ptr), _vp(d_model.ptr), _vp(d_outl.ptr),
-            _vp(d_sp.ptr if d_sp is not None else None), _vp(d_corr.ptr), _vp(self.stream or None)))
+        args = (h._h, B, n, P, Pb, _vp(d_pld.ptr if d_pld is not None else None), _vp(d_bkg.ptr), _vp(g["lcf"].ptr), _vp(g["time"].ptr),
+                _vp(g["knots"].ptr), n_inner, int(pld_order), int(pca_components), n_knots, int(spline_degree),
+                int(bool(normalize_background_pixels)), K, _vp(g["y"].ptr), _vp(g["err"].ptr), _vp(d_cm.ptr if d_cm is not None else None),
+                float(sigma), int(niters), _vp(d_X.ptr), _vp(d_ps.ptr), _vp(d_mu.ptr), _vp(d_w.ptr), _vp(d_model.ptr), _vp(d_outl.ptr),
+                _vp(d_sp.ptr if d_sp is not None else None), _vp(d_corr.ptr), _vp(self.stream or None))
+        if ragged:
+            _capi._check(_capi._lib.lk_pld_correct_ragged_batch_dev(*args, _vp(d_pc.ptr if d_pc is not None else None),
+                                                                    _vp(d_bc.ptr if d_bc is not None else None)))
+        else:
+            _capi._check(_capi._lib.lk_pld_correct_batch_dev(*args))
         if to_host:
             corrected = d_corr.download(np.float64, B * n, stream=self.stream).reshape(B, n)
             outl = d_outl.download(np.uint8, B * n, stream=self.stream).reshape(B, n).astype(bool)
@@ -1001,7 +1069,7 @@ class DevicePixelCubeBatch(object):
         out = DeviceLightCurveBatch(g["time"], d_corr, g["err"], np.arange(B + 1, dtype=np.int64) * n, [dict(m) for m in self.meta],
                                     self.device, self.stream, nan_free=True, is_sorted=True)
         # scratch and inputs the stream may still be reading: held until the batch is synchronised or dropped
-        out._keep = keep + [d_X, d_ps, d_mu, d_w, d_model, d_sp, d_pld, d_bkg, g, d_f, d_e, d_k, self]
+        out._keep = keep + [d_X, d_ps, d_mu, d_w, d_model, d_sp, d_pld, d_bkg, g, d_f, d_e, d_k, pld_idx, bkg_idx, d_pc, d_bc, self]
         return out, d_outl
 
 

@@ -8,7 +8,11 @@ that host-side costs can be told from the GPU calls.  Usage: python tools/api_wa
 3500 x 11 x 11 (`LK_WALLS_SIZES`, default 100,500) in ONE process, the two paths alternating, median and min-max of `LK_WALLS_REPS` (default 5) repetitions each;
 every timed region ends in a stream synchronise.  `pld_host`: only the `pld_correct_batch` rows (also runs on a checkout
 that has no resident path: the baseline).  `pld_dev_trace`: only resident calls on `LK_WALLS_B` (default 500) cutouts — the
-run to put under `rocprofv3 --kernel-trace --stats` for the kernel-time sum of one call (total / the printed call count)."""
+run to put under `rocprofv3 --kernel-trace --stats` for the kernel-time sum of one call (total / the printed call count).
+`pld_ragged`: the resident call on `LK_WALLS_B` (default 500) cutouts whose threshold masks have five different sizes, three ways in
+ONE process, alternating: R the ragged call (K2 default masks, `ragged_masks=True`), U the uniform call on the same cutouts with
+every pixel in both masks, G what a user writes without the keyword — one call per group of equal mask size, on resident batches
+built beforehand (their upload is not timed)."""
 import cProfile
 import io
 import os
@@ -109,6 +113,51 @@ def pld_dev(which):
         sys.stdout.flush()
 
 
+def pld_ragged():
+    from lightkurve_amd import _capi, synth
+    from lightkurve_amd.correctors.pldcorrector import PixelCube
+    from lightkurve_amd.device import DevicePixelCubeBatch
+    reps = int(os.environ.get("LK_WALLS_REPS", "7"))
+    B = int(os.environ.get("LK_WALLS_B", "500"))
+    sync = _capi.Handle.get(0).synchronize
+    base = []
+    for i, amp in enumerate((0, 30, 100, 300, 1000)):      # a static pattern of growing amplitude shrinks the threshold mask
+        t, flux, err, _ = synth.pld_cutout(4, 20 + i, n=3500, npix=11)
+        pattern = (amp * np.abs(np.random.default_rng(100 + i).standard_normal((11, 11)))).astype(np.float32)
+        base.append(PixelCube(t, (flux + pattern).astype(np.float32), err, mission="K2"))
+    counts = [int(c.create_threshold_mask(3).sum()) for c in base]
+    bcounts = [int((~c.create_threshold_mask(0, None)).sum()) for c in base]
+    G = len(base)
+    batch = DevicePixelCubeBatch.from_cubes([base[i % G] for i in range(B)])
+    groups = [DevicePixelCubeBatch.from_cubes([base[g]] * len(range(g, B, G))) for g in range(G)]
+    k2 = dict(aperture_mask=None, pld_aperture_mask="threshold", background_aperture_mask="background", pld_order=3, pca_components=16)
+    fns = {"R": lambda: batch.pld_correct(ragged_masks=True, **k2),
+           "U": lambda: batch.pld_correct(pld_order=3, pca_components=16),
+           "G": lambda: [g.pld_correct(**k2) for g in groups]}
+    for _ in range(2):                                     # warm-up of every shape the timed window uses
+        for fn in fns.values():
+            fn()
+    sync()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(lambda: (fn(), sync()))[0])
+    r, gl = fns["R"](), fns["G"]()
+    worst, masks = 0.0, True
+    for g in range(G):
+        rows = np.arange(g, B, G)
+        masks = masks and bool(np.array_equal(r[1][rows], gl[g][1]))
+        worst = max(worst, float(np.max(np.abs(r[0][rows] - gl[g][0]) / np.median(gl[g][0], axis=1)[:, None])))
+    print("PLD, %d cutouts x 3500 x 11 x 11, order 3, 16 components; threshold masks of %s pixels, background masks of %s, cycled"
+          % (B, counts, bcounts))
+    print("  R  ragged call (K2 default masks, ragged_masks=True)        %s" % spread(ts["R"]))
+    print("  U  uniform call, every pixel in both masks                  %s" % spread(ts["U"]))
+    print("  G  one call per group of equal mask size (%d groups)         %s" % (G, spread(ts["G"])))
+    print("  R / U = %.3f, R / G = %.3f; R against G: outlier masks equal %s, max |delta| / median %.3e"
+          % (np.median(ts["R"]) / np.median(ts["U"]), np.median(ts["R"]) / np.median(ts["G"]), masks, worst))
+    sys.stdout.flush()
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -116,6 +165,8 @@ def main():
     which = sys.argv[1:] or ["flatten", "regress", "pld", "bls"]
     if {"pld_dev", "pld_host", "pld_dev_trace"} & set(which):
         pld_dev(which)
+    if "pld_ragged" in which:
+        pld_ragged()
     if "flatten" in which:
         lcs = []
         for i in range(1000):
