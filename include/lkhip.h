@@ -14,6 +14,7 @@
  *                           src/lightkurve/lightcurve.py:996-1063.
  *   lk_regress_batch*    <- RegressionCorrector._fit_coefficients + the sigma-clip loop of .correct,
  *                           src/lightkurve/correctors/regressioncorrector.py:127-189, 243-279.
+ *   lk_regress_shared_batch*  the same for B targets on ONE shared design matrix (CBVCorrector.correct_gaussian_prior).
  *   lk_ls_fast_batch*    <- astropy lombscargle_fast (the DEFAULT ls_method="fast", periodogram.py:650): fast_impl.py.
  *   lk_ls_chi2_batch* / lk_ls_fastchi2_batch* <- astropy lombscargle_chi2 / lombscargle_fastchi2 (nterms > 1,
  *                           periodogram.py:948-967).
@@ -414,6 +415,30 @@ int lk_regress_cov_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, int
                              const double *err, const uint8_t *cadence_mask, const double *prior_mu,
                              const double *prior_sigma, double clip_sigma, int niters, double *w, double *model,
                              uint8_t *outlier, double *w_cov, void *stream);
+
+/* ---- The same regression for B targets that share ONE design matrix (cotrending: the CBVs of a channel, spacecraft-wide
+ * regressors).  X: N x K row-major, once for the whole batch, 1 <= K <= 64 (the kernel forms the K (K + 1) / 2 column
+ * products of X on the fly and keeps a target tile's whole normal matrix in accumulator registers; a wider matrix goes through
+ * lk_regress_batch with one copy per target); y, err (nullable = ones), cadence_mask (nullable): B x N; prior_mu /
+ * prior_sigma: B x K or both NULL; w B x K, model and outlier B x N, w_cov B x K x K or NULL, all as lk_regress_cov_batch
+ * gives them.  B <= 65535, N >= 1.  No buffer of B N K elements exists anywhere in the call.  A non-finite flux or a
+ * non-finite or non-positive error is an error (LK_EINVAL; RegressionCorrector.__init__ raises
+ * for the same light curve): the _dev call waits for that one answer before it queues the fit, then returns without
+ * further synchronisation.  Results are bitwise reproducible and do not depend on B (partial sums over cadence slices are
+ * added in slice order, no atomics). */
+int lk_regress_shared_batch(lk_handle *h, int B, int N, int K, const double *X, const double *y, const double *err,
+                            const uint8_t *cadence_mask, const double *prior_mu, const double *prior_sigma,
+                            double clip_sigma, int niters, double *w, double *model, uint8_t *outlier, double *w_cov);
+int lk_regress_shared_batch_dev(lk_handle *h, int B, int N, int K, const double *X, const double *y, const double *err,
+                                const uint8_t *cadence_mask, const double *prior_mu, const double *prior_sigma,
+                                double clip_sigma, int niters, double *w, double *model, uint8_t *outlier, double *w_cov,
+                                void *stream);
+/* CBVCorrector.correct_gaussian_prior's prior for B resident targets of N cadences: prior_mu = 0 and prior_sigma[b][:] =
+ * numpy.median(flux_err[b]) / sqrt(|alpha|) (B x K each), alpha != 0.  Device pointers; nothing comes back to the host. */
+int lk_ridge_prior_batch_dev(lk_handle *h, int B, int N, int K, const double *flux_err, double alpha, double *prior_mu,
+                             double *prior_sigma, void *stream);
+/* out[i] = a[i] - b[i] for n doubles on the device (flux - model: the corrected flux of RegressionCorrector.correct). */
+int lk_subtract_f64_dev(lk_handle *h, int64_t n, const double *a, const double *b, double *out, void *stream);
 
 /* ---- LightCurve.flatten trend: masked, gap-segmented Savitzky-Golay + sigma-clip loop + linear re-interpolation
  * t (non-decreasing per target), flux (may hold NaN); mask: 1 = EXCLUDE the cadence from the fit (lightkurve's

@@ -154,6 +154,15 @@ SIGNATURES = [
     ("lk_regress_cov_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, _c_ip, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_int, _vp,
       _vp, _vp, _vp, _vp]),
+    ("lk_regress_shared_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_u8p, _c_dp, _c_dp, ctypes.c_double,
+      ctypes.c_int, _c_dp, _c_dp, _c_u8p, _c_dp]),
+    ("lk_regress_shared_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_int, _vp,
+      _vp, _vp, _vp, _vp]),
+    ("lk_ridge_prior_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp]),
+    ("lk_subtract_f64_dev", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     ("lk_savgol_trend_batch", ctypes.c_int,
      [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
       ctypes.c_double, _c_dp, _c_u8p]),
@@ -765,6 +774,43 @@ def regress_batch(X, y, n_off, err=None, cadence_mask=None, prior_mu=None, prior
                                      _ptr(outl, _c_u8p), _ptr(cov)))
     res = dict(coefficients=w, model=model, outlier_mask=outl.astype(bool))
     if return_cov:
+        res["coefficients_cov"] = cov
+    return res
+
+
+def regress_shared_batch(X, y, err=None, cadence_mask=None, prior_mu=None, prior_sigma=None, sigma=5.0, niters=5, device=0,
+                         want_cov=False):
+    """``regress_batch`` for B targets of N cadences that share ONE design matrix ``X`` (N, K), K <= 64: ``y`` (B, N),
+    ``err`` / ``cadence_mask`` (B, N) or None, priors (B, K) (or broadcastable to it) or None.  X crosses PCIe once and no
+    (B N) x K matrix is ever built.  Returns dict(coefficients[B,K], model[B,N] (median-subtracted), outlier_mask[B,N] bool);
+    ``want_cov``: also coefficients_cov[B,K,K]."""
+    h = Handle.get(device)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("X must be 2-D (cadences x regressors)")
+    N, K = X.shape
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.ndim != 2 or y.shape[1] != N:
+        raise ValueError("y must be (B, N) with N = len(X) = %d (got shape %s)" % (N, y.shape))
+    B = y.shape[0]
+    err = None if err is None else np.ascontiguousarray(np.broadcast_to(np.asarray(err, dtype=np.float64), (B, N)))
+    cm = None if cadence_mask is None else np.ascontiguousarray(cadence_mask, dtype=np.uint8)
+    if cm is not None and cm.shape != (B, N):
+        raise ValueError("cadence_mask must be (B, N) = %s (got shape %s)" % ((B, N), cm.shape))
+    if (prior_mu is None) != (prior_sigma is None):
+        raise ValueError("Please specify both `prior_mu` and `prior_sigma`")
+    if prior_mu is not None:
+        prior_mu = _f64(np.broadcast_to(np.asarray(prior_mu, dtype=np.float64), (B, K)))
+        prior_sigma = _f64(np.broadcast_to(np.asarray(prior_sigma, dtype=np.float64), (B, K)))
+    w = np.empty((B, K), dtype=np.float64)
+    model = np.empty((B, N), dtype=np.float64)
+    outl = np.empty((B, N), dtype=np.uint8)
+    cov = np.empty((B, K, K), dtype=np.float64) if want_cov else None
+    _check(_lib.lk_regress_shared_batch(h._h, B, N, K, _ptr(X), _ptr(y), _ptr(err), _ptr(cm, _c_u8p), _ptr(prior_mu),
+                                        _ptr(prior_sigma), float(sigma), int(niters), _ptr(w), _ptr(model), _ptr(outl, _c_u8p),
+                                        _ptr(cov)))
+    res = dict(coefficients=w, model=model, outlier_mask=outl.astype(bool))
+    if want_cov:
         res["coefficients_cov"] = cov
     return res
 

@@ -108,6 +108,14 @@ def minimize_scalar_bounded(func, bounds, xatol=1e-5, maxiter=500):
     return dict(x=float(xf), fun=float(fx), nfev=num, status=flag)
 
 
+def cbv_index_list(cbv_indices, n_vectors):
+    """Basis-vector numbers as ``CBVCorrector`` takes them -> int array: 1-based, "ALL" = every vector, numbers outside
+    1..n_vectors dropped."""
+    if isinstance(cbv_indices, str) and cbv_indices == "ALL":
+        cbv_indices = np.arange(1, n_vectors + 1)
+    return np.array([i for i in np.asarray(cbv_indices) if 1 <= i <= n_vectors], dtype=int)
+
+
 class CBVCorrector(RegressionCorrector):
     def __init__(self, lc, cbvs, cbv_type="SingleScale"):
         """``cbvs``: float array (n_cadences, n_vectors), column j = basis vector number j + 1 on the cadences of lc."""
@@ -125,9 +133,7 @@ class CBVCorrector(RegressionCorrector):
     def _collection(self, cbv_indices, ext_dm):
         mats = []
         if cbv_indices is not None:
-            if isinstance(cbv_indices, str) and cbv_indices == "ALL":
-                cbv_indices = np.arange(1, self.cbvs.shape[1] + 1)
-            idx = np.array([i for i in np.asarray(cbv_indices) if 1 <= i <= self.cbvs.shape[1]], dtype=int)  # 1-based
+            idx = cbv_index_list(cbv_indices, self.cbvs.shape[1])
             mats.append(DesignMatrix(self.cbvs[:, idx - 1], columns=["VECTOR_%d" % i for i in idx], name=self.cbv_type))
         if ext_dm is not None:
             if not isinstance(ext_dm, DesignMatrix):

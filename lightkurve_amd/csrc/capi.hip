@@ -553,6 +553,53 @@ int lk_regress_cov_batch(lk_handle *h, int B, const int64_t *n_off, int K, const
     return rc ? rc : io.finish();
 }
 
+// one design matrix shared by all targets
+int lk_regress_shared_batch_dev(lk_handle *h, int B, int N, int K, const double *X, const double *y, const double *err,
+                                const uint8_t *cadence_mask, const double *prior_mu, const double *prior_sigma,
+                                double clip_sigma, int niters, double *w, double *model, uint8_t *outlier, double *w_cov,
+                                void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::regress_shared_launch(h, B, N, K, X, y, err, cadence_mask, prior_mu, prior_sigma, clip_sigma, niters, w, model,
+                                     outlier, w_cov, static_cast<hipStream_t>(stream));
+}
+
+int lk_regress_shared_batch(lk_handle *h, int B, int N, int K, const double *X, const double *y, const double *err,
+                            const uint8_t *cadence_mask, const double *prior_mu, const double *prior_sigma,
+                            double clip_sigma, int niters, double *w, double *model, uint8_t *outlier, double *w_cov) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(K >= 1 && N >= 1, "K and N must be >= 1");
+    LK_REQUIRE(X && y && w && model && outlier, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)B * N, nk = (size_t)B * K;
+    const double *dX, *dy, *derr, *dmu, *dsg;
+    const uint8_t *dcm;
+    double *dmodel, *dw, *dcov;
+    uint8_t *dout;
+    lk::StagedCall io(h);
+    int rc = io.in(dX, X, (size_t)N * K).in(dy, y, ntot).in(derr, err, ntot).out(dmodel, model, ntot)
+                 .in(dcm, cadence_mask, ntot).out(dout, outlier, ntot).in(dmu, prior_mu, nk).in(dsg, prior_sigma, nk)
+                 .out(dw, w, nk).out(dcov, w_cov, nk * K).stage();
+    if (rc) return rc;
+    rc = lk::regress_shared_launch(h, B, N, K, dX, dy, derr, dcm, dmu, dsg, clip_sigma, niters, dw, dmodel, dout, dcov, nullptr);
+    return rc ? rc : io.finish();
+}
+
+int lk_ridge_prior_batch_dev(lk_handle *h, int B, int N, int K, const double *flux_err, double alpha, double *prior_mu,
+                             double *prior_sigma, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::ridge_prior_launch(h, B, N, K, flux_err, alpha, prior_mu, prior_sigma, static_cast<hipStream_t>(stream));
+}
+
+int lk_subtract_f64_dev(lk_handle *h, int64_t n, const double *a, const double *b, double *out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::subtract_launch(h, n, a, b, out, static_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------------------------ flatten
 int lk_savgol_design(int window, int polyorder, double *coeffs, double *edge) {
     return lk::savgol_design_host(window, polyorder, coeffs, edge);

@@ -137,6 +137,12 @@ int regress_launch(lk_handle *h, int B, const int64_t *n_off_host, int K, const 
                    const double *err, const uint8_t *cmask, const double *prior_mu, const double *prior_sigma,
                    double clip_sigma, int niters, double *w, double *model, uint8_t *outl, hipStream_t stream,
                    double *w_cov = nullptr);
+int regress_shared_launch(lk_handle *h, int B, int N, int K, const double *X, const double *y, const double *err,
+                          const uint8_t *cmask, const double *prior_mu, const double *prior_sigma, double clip_sigma, int niters,
+                          double *w, double *model, uint8_t *outl, double *w_cov, hipStream_t stream);
+int ridge_prior_launch(lk_handle *h, int B, int N, int K, const double *err, double alpha, double *prior_mu, double *prior_sigma,
+                       hipStream_t stream);
+int subtract_launch(lk_handle *h, int64_t n, const double *a, const double *b, double *out, hipStream_t stream);
 int model_part_launch(lk_handle *h, int B, int N, int K, int c0, int c1, const double *X, const double *w, double *out,
                       hipStream_t stream);
 int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,

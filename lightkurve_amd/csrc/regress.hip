@@ -12,6 +12,8 @@
 //                      std, <=5 passes) and outlier |= clipped.   (reference quirk, SURVEY App. B.5: the clip
 //                      statistics include cadences outside cadence_mask and earlier outliers.)
 // Final: model = X w - median(X w).
+// Targets that share ONE design matrix (cotrending on a channel's basis vectors) take gram_shared_kernel / model_shared_kernel
+// below instead of the first and third step: see "one design matrix for all targets".
 #include <cstdlib>
 
 #include "block_select.hpp"
@@ -1159,6 +1161,391 @@ int regress_launch(lk_handle *h, int B, const int64_t *n_off_host, int K, const 
     hipLaunchKernelGGL(demedian_kernel, dim3(B), dim3(1024), 0, stream, d_off, model);
     // d_G still holds the normal matrix of the LAST iteration's fit: its inverse is the coefficient covariance
     if (w_cov) hipLaunchKernelGGL(invert_kernel, dim3(B), dim3(256), 0, stream, d_G, K, Kp, prior_sigma, d_A, w_cov);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ one design matrix for all targets
+// Cotrending a channel's targets (CBVCorrector.correct_gaussian_prior, a RegressionCorrector on spacecraft-wide regressors):
+// every target of the batch is regressed on the SAME N x K matrix X.  The B normal equations are then one dense contraction,
+//   G_b[i][j] = sum_n w_b[n] (X[n][i] X[n][j]),   rhs_b[i] = sum_n (w_b[n] y_b[n]) X[n][i],   w_b[n] = m_b[n] / err_b[n]^2,
+// [W | W o Y] (targets x cadences) times a matrix whose columns are the K (K + 1) / 2 pair products and the K columns of X.
+// A workgroup owns 16 targets x one contiguous slice of cadences; a stage of 32 cadences of X sits in LDS column-major (as in
+// gram_tri_kernel, plus one column of ones and one of zeros) and every lane forms its right operand X[n][i] X[n][j] from two
+// LDS reads — a plain column is X[n][i] times the ones column, padding is the zeros column: no branch, no second tile.  The
+// left operand comes from the targets' own flux / error / mask bytes, 16 x 32 values per stage, one per thread.  The 16-column
+// tiles of the product are dealt round-robin to the 8 waves, NS per wave.  HBM sees 18 bytes per target and cadence and pass
+// instead of 8 (K + 1) + 18.
+// Bound on K: K = 64 has 2080 pairs + 64 columns = 134 tiles, 17 per wave = 136 accumulator registers of the 256 a wave has
+// at two waves per SIMD; the LDS stage (2 x (K + 2) x 34 doubles) is 36 KB there.  Wider matrices go through lk_regress_batch.
+constexpr int SH_KMAX = 64;
+constexpr int SH_NT = 512, SH_RC = 32, SH_LD = 34, SH_TB = 16, SH_NXF = (SH_RC * SH_KMAX + SH_NT - 1) / SH_NT;
+
+// The cadence axis is split across workgroups (1000 targets are only 63 target tiles for 256 CUs).  The split is a function
+// of N alone — never of B or of the device — so the order in which a target's partial sums are added is the same in every call.
+static void shared_split(int N, int *nslice, int *len) {
+    const int s = std::max(1, std::min(16, (N + 255) / 256));
+    const int l = ((N + s - 1) / s + SH_RC - 1) / SH_RC * SH_RC;
+    *len = l;
+    *nslice = (N + l - 1) / l;
+}
+
+// part[(16 tile + row) * S + slice][NC]: the slice's share of row `row` of [W | W o Y] times the pair / plain columns
+template <int NS>
+__global__ __launch_bounds__(SH_NT) void gram_shared_kernel(const double *__restrict__ X, const double *__restrict__ y,
+                                                            const double *__restrict__ err,
+                                                            const uint8_t *__restrict__ cmask,
+                                                            const uint8_t *__restrict__ outl, int B, int N, int K, int slice,
+                                                            double *__restrict__ part, const int *__restrict__ done) {
+    __shared__ __attribute__((aligned(16))) double sx[2][(SH_KMAX + 2) * SH_LD];  // [buf][column | ones | zeros][cadence]
+    __shared__ __attribute__((aligned(16))) double sw[2][2][SH_TB * SH_LD];       // [buf][w | w y][target][cadence]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int q = lane >> 4, cc = lane & 15;
+    const int b0 = blockIdx.x * SH_TB, S = gridDim.y;
+    if (done) {  // all 16 clip loops have converged: the partial sums of the last pass stand (the reduction skips the targets)
+        const int d = done[min(b0 + (tid & 15), B - 1)];
+        if (__syncthreads_and(d)) return;
+    }
+    const int nlo = blockIdx.y * slice, nhi = min(N, nlo + slice), n = nhi - nlo;
+    const int npairs = K * (K + 1) / 2, NPT = (npairs + 15) >> 4, T = NPT + ((K + 15) >> 4), NC = T << 4;
+    const int cnt = wave < T ? (T - wave + 7) >> 3 : 0;  // this wave's tiles: wave, wave + 8, ...
+    // per slot: LDS offsets (doubles) of the lane's two factors for lane group q, cadence 0; slots beyond the run repeat
+    // its last tile (not written), a wave without tiles repeats tile 0
+    int ijoff[NS];  // (i offset | j offset << 16: one register per slot)
+    bool isx[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int tile = cnt == 0 ? 0 : wave + 8 * min(s, cnt - 1);
+        int i = K + 1, j = K + 1;  // the zeros column
+        if (tile < NPT) {
+            int rem = tile * 16 + cc;
+            if (rem < npairs) {  // pair number -> (i, j), i <= j, row-major upper triangle
+                i = 0;
+                while (rem >= K - i) {
+                    rem -= K - i;
+                    ++i;
+                }
+                j = i + rem;
+            }
+        } else {
+            const int c = (tile - NPT) * 16 + cc;
+            if (c < K) {
+                i = c;
+                j = K;  // the ones column
+            }
+        }
+        isx[s] = tile >= NPT;
+        ijoff[s] = (i * SH_LD + 2 * q) | ((j * SH_LD + 2 * q) << 16);
+    }
+    double4_t acc[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) acc[s] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    if (tid < 2 * SH_LD) {
+        const int bf = tid / SH_LD, c = tid - bf * SH_LD;
+        sx[bf][K * SH_LD + c] = 1.0;
+        sx[bf][(K + 1) * SH_LD + c] = 0.0;
+    }
+    // global -> registers -> LDS.  X: the stage is 32 K consecutive doubles, thread takes elements tid + 512 u (row and
+    // column fixed for the whole loop).  Left operand: thread (target tid / 32, cadence tid % 32).  Every load is
+    // unconditional on a clamped address; what lies beyond the slice or the batch gets weight 0.
+    int xdst[SH_NXF];
+#pragma unroll
+    for (int u = 0; u < SH_NXF; ++u) {
+        const int ec = min(tid + SH_NT * u, SH_RC * K - 1), r = ec / K;
+        xdst[u] = (ec - r * K) * SH_LD + r;
+    }
+    const double *xs = X + (size_t)nlo * K;       // the slice's rows: n K consecutive doubles
+    const int xlast = n * K - 1;
+    const int lt = tid >> 5, lc = tid & 31;
+    const bool tlive = b0 + lt < B;
+    const size_t trow = (size_t)min(b0 + lt, B - 1) * N;
+    const double *ep = err ? err : y;                // (a null array: a valid address whose value is dropped)
+    const uint8_t *cp = cmask ? cmask : outl;
+    double xv[SH_NXF], yv = 0.0, ev = 1.0;
+    uint8_t cv = 1, ov = 0;
+    auto fetch = [&](int n0) {
+#pragma unroll
+        for (int u = 0; u < SH_NXF; ++u) xv[u] = xs[min(n0 * K + tid + SH_NT * u, xlast)];  // (past the slice: weight 0)
+        const size_t g = trow + min(nlo + n0 + lc, nhi - 1);
+        yv = y[g];
+        ev = ep[g];
+        cv = cp[g];
+        ov = outl[g];
+    };
+    auto stash = [&](int buf, int n0) {
+#pragma unroll
+        for (int u = 0; u < SH_NXF; ++u)
+            if (tid + SH_NT * u < SH_RC * K) sx[buf][xdst[u]] = xv[u];
+        const bool live = tlive && n0 + lc < n && (cmask == nullptr || cv != 0) && ov == 0;
+        const double e1 = err ? ev : 1.0;
+        const double w = live ? 1.0 / (e1 * e1) : 0.0;
+        sw[buf][0][lt * SH_LD + lc] = w;
+        sw[buf][1][lt * SH_LD + lc] = live ? w * yv : 0.0;
+    };
+    fetch(0);
+    stash(0, 0);
+    __syncthreads();
+    int buf = 0;
+    constexpr int CH = NS > 12 ? 1 : 4;  // slots whose fragments are in flight together
+    for (int n0 = 0; n0 < n; n0 += SH_RC) {
+        if (n0 + SH_RC < n) fetch(n0 + SH_RC);  // (wave-uniform; the last stage stashes stale registers into the idle buffer)
+        const double *xb = sx[buf], *wb = sw[buf][0] + cc * SH_LD + 2 * q, *wyb = sw[buf][1] + cc * SH_LD + 2 * q;
+#pragma unroll 1
+        for (int m = 0; m < SH_RC / 8; ++m) {  // (not unrolled: the fragments of four steps at once do not fit beside 17 tiles)
+            // lane group q: cadences 8m + 2q, 8m + 2q + 1 of the step pair (2m, 2m + 1), as in gram_tri_kernel
+            const double2 w2 = *reinterpret_cast<const double2 *>(wb + 8 * m);
+            const double2 wy2 = *reinterpret_cast<const double2 *>(wyb + 8 * m);
+#pragma unroll
+            for (int s0 = 0; s0 < NS; s0 += CH) {
+                double2 f[CH], g[CH];
+#pragma unroll
+                for (int s = s0; s < s0 + CH && s < NS; ++s) {
+                    f[s - s0] = *reinterpret_cast<const double2 *>(xb + (ijoff[s] & 0xffff) + 8 * m);
+                    g[s - s0] = *reinterpret_cast<const double2 *>(xb + (ijoff[s] >> 16) + 8 * m);
+                }
+#pragma unroll
+                for (int s = s0; s < s0 + CH && s < NS; ++s)
+                    acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(isx[s] ? wy2.x : w2.x, f[s - s0].x * g[s - s0].x, acc[s], 0, 0, 0);
+#pragma unroll
+                for (int s = s0; s < s0 + CH && s < NS; ++s)
+                    acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(isx[s] ? wy2.y : w2.y, f[s - s0].y * g[s - s0].y, acc[s], 0, 0, 0);
+            }
+        }
+        stash(buf ^ 1, n0 + SH_RC);
+        __syncthreads();
+        buf ^= 1;
+    }
+    // C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg  (row: target, col: product column)
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        if (s < cnt) {
+            const int tile = wave + 8 * s;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                part[((size_t)(b0 + q + 4 * r) * S + blockIdx.y) * NC + tile * 16 + cc] = acc[s][r];
+        }
+}
+
+// G_b = the slices' partial sums added in slice order (no atomics: same bits every run, whatever the grid), written in the
+// layout the solve kernels read: [Kp][Kp], both triangles, the right-hand side in column K.
+__global__ __launch_bounds__(256) void gram_shared_reduce_kernel(const double *__restrict__ part, int S, int K, int Kp,
+                                                                 double *__restrict__ G, const int *__restrict__ done) {
+    const int b = blockIdx.x;
+    if (done && done[b]) return;
+    const int npairs = K * (K + 1) / 2, NPT = (npairs + 15) >> 4, NC = (NPT + ((K + 15) >> 4)) << 4;
+    const double *pb = part + (size_t)b * S * NC;
+    double *Gt = G + (size_t)b * Kp * Kp;
+    for (int e = threadIdx.x; e < npairs + K; e += 256) {
+        const int col = e < npairs ? e : NPT * 16 + (e - npairs);
+        double sum = 0.0;
+        for (int s = 0; s < S; ++s) sum += pb[(size_t)s * NC + col];
+        if (e < npairs) {
+            int i = 0, rem = e;
+            while (rem >= K - i) {
+                rem -= K - i;
+                ++i;
+            }
+            const int j = i + rem;
+            Gt[(size_t)i * Kp + j] = sum;
+            Gt[(size_t)j * Kp + i] = sum;
+        } else {
+            Gt[(size_t)(e - npairs) * Kp + K] = sum;
+        }
+    }
+}
+
+// model[b][n] = sum_k X[n][k] w[b][k]: a workgroup stages 64 rows of X and the coefficients of 32 targets in LDS once and
+// every thread (one cadence) carries four targets per trip, so a row of X is read from LDS once per four outputs and from
+// memory once per 32 targets.  The sum runs over k in ascending order.
+constexpr int MS_CB = 64, MS_TB = 32;
+__global__ __launch_bounds__(256) void model_shared_kernel(const double *__restrict__ X, const double *__restrict__ w, int B, int N,
+                                                           int K, double *__restrict__ model, const int *__restrict__ done) {
+    extern __shared__ __attribute__((aligned(16))) double ms_sm[];
+    const int ldx = K | 1;  // odd row stride: a wave's 64 rows fall on distinct banks
+    double *sx = ms_sm;                        // [64][ldx]
+    double *swt = ms_sm + MS_CB * (K + 1);     // [K][32]
+    const int tid = threadIdx.x, n0 = blockIdx.x * MS_CB, b0 = blockIdx.y * MS_TB;
+    for (int e = tid; e < MS_CB * K; e += 256) {
+        const int r = e / K, k = e - r * K;
+        sx[r * ldx + k] = X[(size_t)min(n0 + r, N - 1) * K + k];
+    }
+    for (int e = tid; e < MS_TB * K; e += 256) {
+        const int t = e / K, k = e - t * K;
+        swt[k * MS_TB + t] = w[(size_t)min(b0 + t, B - 1) * K + k];
+    }
+    __syncthreads();
+    const int c = tid & 63, wv = tid >> 6, nn = n0 + c;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const int tb = wv * 8 + g * 4;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double x = sx[c * ldx + k];
+            const double2 wa = *reinterpret_cast<const double2 *>(swt + k * MS_TB + tb);
+            const double2 wb = *reinterpret_cast<const double2 *>(swt + k * MS_TB + tb + 2);
+            a0 = fma(x, wa.x, a0);
+            a1 = fma(x, wa.y, a1);
+            a2 = fma(x, wb.x, a2);
+            a3 = fma(x, wb.y, a3);
+        }
+        const double a[4] = {a0, a1, a2, a3};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int b = b0 + tb + i;
+            if (nn < N && b < B && !(done && done[b])) model[(size_t)b * N + nn] = a[i];
+        }
+    }
+}
+
+// RegressionCorrector.__init__ raises for a non-finite flux and for a non-finite or non-positive error.  flag bits: 1 flux,
+// 2 error.  (A non-finite regressor gives NaN coefficients, as numpy.linalg.solve does and as lk_regress_batch does.)
+__global__ __launch_bounds__(256) void shared_check_kernel(const double *__restrict__ y, const double *__restrict__ err, size_t ny,
+                                                           int *__restrict__ flag) {
+    int bad = 0;
+    const size_t step = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < ny; i += step) {
+        if (!isfinite(y[i])) bad |= 1;
+        if (err) {
+            const double e = err[i];
+            if (!isfinite(e) || e <= 0.0) bad |= 2;
+        }
+    }
+    if (bad) atomicOr(flag, bad);
+}
+
+// Workspace: (B + 1) offsets + B Kp^2 normal matrices + B K (K + 1) solver scratch (twice that with w_cov) + B N clip flags +
+// B done words + the partial sums, 16 ceil(B / 16) x S x NC doubles (S <= 16 cadence slices, NC = 16 (ceil(K (K + 1) / 32) +
+// ceil(K / 16)) product columns: 25 MB for 1000 targets at K = 17).  Nothing here has B N K elements.
+int regress_shared_launch(lk_handle *h, int B, int N, int K, const double *X, const double *y, const double *err,
+                          const uint8_t *cmask, const double *prior_mu, const double *prior_sigma, double clip_sigma, int niters,
+                          double *w, double *model, uint8_t *outl, double *w_cov, hipStream_t stream) {
+    LK_REQUIRE(B >= 0, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(K >= 1, "K must be >= 1 (got %d)", K);
+    LK_REQUIRE(K <= SH_KMAX,
+               "K=%d: the shared-matrix regression takes at most %d columns; wider matrices go through lk_regress_batch "
+               "(one design matrix per target)", K, SH_KMAX);
+    LK_REQUIRE(B <= 65535, "at most 65535 targets per call on this path (got %d): split the batch", B);
+    LK_REQUIRE(N >= 1 && N < (1 << 30), "N=%d cadences outside 1..2^30", N);
+    LK_REQUIRE(X && y && w && model && outl, "NULL buffer");
+    LK_REQUIRE((prior_mu == nullptr) == (prior_sigma == nullptr), "Please specify both `prior_mu` and `prior_sigma`");
+    LK_REQUIRE(niters >= 1, "niters must be >= 1");
+    const size_t ntot = (size_t)B * N;
+    const int KB = (K + 1 + GR_BLK - 1) / GR_BLK, Kp = KB * GR_BLK;
+    int S = 1, slice = N;
+    shared_split(N, &S, &slice);
+    const int ntb = (B + SH_TB - 1) / SH_TB, npairs = K * (K + 1) / 2, T = (npairs + 15) / 16 + (K + 15) / 16, NC = 16 * T;
+    const size_t part_bytes = (size_t)ntb * SH_TB * S * NC * 8;
+    h->ws.reset();
+    int rc = h->ws.reserve((size_t)(B + 1) * 8 + (size_t)B * Kp * Kp * 8 + (size_t)B * K * (K + 1) * 8 * (w_cov ? 2 : 1) + ntot +
+                           (size_t)B * 4 + part_bytes + 4 + 8 * 256 + 4096);
+    if (rc) return rc;
+    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
+    double *d_G = (double *)h->ws.alloc((size_t)B * Kp * Kp * 8);
+    double *d_A = (double *)h->ws.alloc((size_t)B * K * (K + 1) * 8 * (w_cov ? 2 : 1));
+    uint8_t *d_flag = (uint8_t *)h->ws.alloc(ntot);
+    int *d_done = (int *)h->ws.alloc((size_t)B * 4);
+    double *d_part = (double *)h->ws.alloc(part_bytes);
+    int *d_bad = (int *)h->ws.alloc(4);
+    LK_REQUIRE(d_off && d_G && d_A && d_flag && d_done && d_part && d_bad, "workspace exhausted");
+    // the input check first: its answer is back before the fit is queued
+    LK_HIP_CHECK(hipMemsetAsync(d_bad, 0, 4, stream));
+    {
+        const int gx = (int)std::min<size_t>((ntot + 1023) / 1024, 2048);
+        hipLaunchKernelGGL(shared_check_kernel, dim3(gx), dim3(256), 0, stream, y, err, ntot, d_bad);
+        LK_HIP_CHECK(hipGetLastError());
+        int bad = 0;
+        LK_HIP_CHECK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, stream));
+        LK_HIP_CHECK(hipStreamSynchronize(stream));
+        LK_REQUIRE(!(bad & 1), "Input light curve has NaNs in the flux");
+        LK_REQUIRE(!(bad & 2), "Input light curve has NaN, infinite, zero or negative flux errors");
+    }
+    {
+        std::vector<int64_t> off((size_t)B + 1);
+        for (int b = 0; b <= B; ++b) off[b] = (int64_t)b * N;
+        const int rcs = h->stage.copy(d_off, off.data(), (size_t)(B + 1) * 8, stream);
+        if (rcs) return rcs;
+    }
+    LK_HIP_CHECK(hipMemsetAsync(outl, 0, ntot, stream));
+    LK_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)B * 4, stream));
+    const int ns = (T + 7) / 8;
+    const size_t solve_lds = ((size_t)K * (K + 1) + 2 * K + 2 * SOLVE_NW + 2) * 8;  // (<= 35 KB for K <= 64)
+    {
+        const int rc_ = want_lds(h, reinterpret_cast<const void *>(solve_lds_kernel), 160 * 1024);
+        if (rc_) return rc_;
+    }
+    const size_t model_lds = ((size_t)MS_CB * (K + 1) + (size_t)K * MS_TB) * 8;
+    for (int it = 0; it < niters; ++it) {
+        // every pass recomputes the Gram in full: it re-reads only the targets' own arrays (18 bytes per cadence)
+#define SH_GO(NS_)                                                                                                        \
+    hipLaunchKernelGGL(gram_shared_kernel<NS_>, dim3(ntb, S), dim3(SH_NT), 0, stream, X, y, err, cmask, (const uint8_t *)outl, B, \
+                       N, K, slice, d_part, (const int *)d_done)
+        if (ns <= 1) SH_GO(1);
+        else if (ns <= 2) SH_GO(2);
+        else if (ns <= 3) SH_GO(3);
+        else if (ns <= 4) SH_GO(4);
+        else if (ns <= 6) SH_GO(6);
+        else if (ns <= 8) SH_GO(8);
+        else if (ns <= 12) SH_GO(12);
+        else SH_GO(17);
+#undef SH_GO
+        hipLaunchKernelGGL(gram_shared_reduce_kernel, dim3(B), dim3(256), 0, stream, (const double *)d_part, S, K, Kp, d_G,
+                           (const int *)d_done);
+        hipLaunchKernelGGL(solve_lds_kernel, dim3(B), dim3(SOLVE_NT), solve_lds, stream, d_G, K, Kp, prior_mu, prior_sigma, w,
+                           (const int *)d_done);
+        hipLaunchKernelGGL(model_shared_kernel, dim3((N + MS_CB - 1) / MS_CB, (B + MS_TB - 1) / MS_TB), dim3(256), model_lds, stream,
+                           X, (const double *)w, B, N, K, model, (const int *)d_done);
+        hipLaunchKernelGGL(clip_kernel, dim3(B), dim3(1024), 0, stream, y, model, d_off, clip_sigma, 5, d_flag, outl, d_done,
+                           (int *)nullptr, (int *)nullptr, 0);
+    }
+    hipLaunchKernelGGL(demedian_kernel, dim3(B), dim3(1024), 0, stream, d_off, model);
+    if (w_cov) hipLaunchKernelGGL(invert_kernel, dim3(B), dim3(256), 0, stream, d_G, K, Kp, prior_sigma, d_A, w_cov);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+// CBVCorrector.correct_gaussian_prior's prior (reference cbvcorrector.py:333-395): mu = 0 and one ridge width per target,
+// sigma_b = numpy.median(flux_err_b) / sqrt(|alpha|), on every column.  One workgroup per target.
+__global__ __launch_bounds__(1024) void ridge_prior_kernel(const double *__restrict__ err, int N, int K, double alpha,
+                                                           double *__restrict__ mu, double *__restrict__ sg) {
+    __shared__ unsigned long long sh[1024];
+    const int b = blockIdx.x;
+    const double *e = err + (size_t)b * N;
+    auto val = [&](int i) { return e[i]; };
+    auto keep = [&](int) { return true; };
+    const double med = block_median(N, (long long)N, val, keep, sh);
+    const double s = med / sqrt(fabs(alpha));
+    for (int k = threadIdx.x; k < K; k += 1024) {
+        mu[(size_t)b * K + k] = 0.0;
+        sg[(size_t)b * K + k] = s;
+    }
+}
+
+int ridge_prior_launch(lk_handle *h, int B, int N, int K, const double *err, double alpha, double *prior_mu, double *prior_sigma,
+                       hipStream_t stream) {
+    (void)h;
+    LK_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && K >= 1, "bad shapes");
+    LK_REQUIRE(err && prior_mu && prior_sigma, "NULL buffer");
+    LK_REQUIRE(alpha != 0.0 && alpha == alpha, "alpha must be non-zero (alpha == 0 means no prior: pass NULL priors)");
+    hipLaunchKernelGGL(ridge_prior_kernel, dim3(B), dim3(1024), 0, stream, err, N, K, alpha, prior_mu, prior_sigma);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+__global__ __launch_bounds__(256) void subtract_kernel(const double *__restrict__ a, const double *__restrict__ b, size_t n,
+                                                       double *__restrict__ out) {
+    const size_t step = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += step) out[i] = a[i] - b[i];
+}
+
+int subtract_launch(lk_handle *h, int64_t n, const double *a, const double *b, double *out, hipStream_t stream) {
+    (void)h;
+    LK_REQUIRE(n >= 0, "n must be >= 0");
+    if (n == 0) return LK_OK;
+    LK_REQUIRE(a && b && out, "NULL buffer");
+    const int gx = (int)std::min<int64_t>((n + 1023) / 1024, 4096);
+    hipLaunchKernelGGL(subtract_kernel, dim3(gx), dim3(256), 0, stream, a, b, (size_t)n, out);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }

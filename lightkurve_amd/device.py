@@ -384,6 +384,91 @@ class DeviceLightCurveBatch(object):
             return out, tr
         return out
 
+    # ---------------------------------------------------------------- cotrending on one shared design matrix
+    def _uniform_n(self, rows, what):
+        """The one cadence count of the batch, checked against the ``rows`` of the shared design matrix (no device call)."""
+        counts = np.diff(self.n_off)
+        if len(counts) == 0:
+            raise ValueError("%s needs at least one light curve" % what)
+        if counts.min() != counts.max():
+            raise ValueError("%s needs one cadence count for every target: this batch has between %d and %d cadences per target "
+                             "and the design matrix has %d rows (regression_correct_batch takes ragged batches)"
+                             % (what, counts.min(), counts.max(), rows))
+        N = int(counts[0])
+        if rows != N:
+            raise ValueError("%s: the design matrix has %d rows, the light curves have %d cadences" % (what, rows, N))
+        return N
+
+    def regression_correct(self, X, prior_mu=None, prior_sigma=None, cadence_mask=None, sigma=5, niters=5, to_host=False):
+        """``RegressionCorrector(lc).correct(X, cadence_mask, sigma, niters)`` (reference regressioncorrector.py:191-279,
+        ``propagate_errors=False``) for every target of the batch on ONE shared design matrix: ``X`` is a host array (N, K),
+        K <= 64, or a ``DesignMatrix`` / ``DesignMatrixCollection`` (its own priors go to every target unless ``prior_mu`` /
+        ``prior_sigma``, broadcastable to (B, K), are given).  X is uploaded once; no (B N) x K matrix exists.  The corrected
+        flux is flux - model, formed on the device; flux_err is unchanged.  ``cadence_mask``: bool (B, N), True = used in the
+        fit.  ``to_host=False`` -> (``DeviceLightCurveBatch``, ``DeviceBuffer`` of the B x N outlier bytes, ``DeviceBuffer``
+        of the B x K coefficients), nothing synchronised after the input check; ``to_host=True`` -> (corrected[B, N],
+        outlier[B, N] bool, coefficients[B, K])."""
+        Xa, mu, sg = _design_arrays(X, prior_mu, prior_sigma)
+        N = self._uniform_n(Xa.shape[0], "regression_correct")
+        B, K = len(self), Xa.shape[1]
+        d_mu = d_sg = None
+        keep = []
+        h = self.handle
+        if mu is not None:
+            d_mu, k1 = _upload(h, np.broadcast_to(mu, (B, K)), self.stream)
+            d_sg, k2 = _upload(h, np.broadcast_to(sg, (B, K)), self.stream)
+            keep += [k1, k2]
+        return self._regress_shared(Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, keep)
+
+    def cbv_correct(self, cbvs, cbv_indices=np.arange(1, 9), alpha=1e-20, ext_dm=None, cadence_mask=None, sigma=5, niters=5,
+                    to_host=False):
+        """``CBVCorrector(lc, cbvs).correct_gaussian_prior(cbv_indices, alpha, ext_dm, cadence_mask)`` (reference
+        cbvcorrector.py:333-395) for every target of the batch: columns [cbvs[:, idx - 1] | ext_dm | 1] shared by all targets
+        (``cbvs``: (N, n_vectors), column j = basis vector j + 1; indices 1-based, out-of-range ones dropped, "ALL" accepted),
+        prior_mu = 0 and ONE ridge width per target, median(flux_err_b) / sqrt(|alpha|), taken on the device; ``alpha == 0``:
+        no prior.  Returns what ``regression_correct`` returns."""
+        Xa = _cbv_columns(cbvs, cbv_indices, ext_dm)
+        N = self._uniform_n(Xa.shape[0], "cbv_correct")
+        B, K = len(self), Xa.shape[1]
+        h = self.handle
+        d_mu = d_sg = None
+        if alpha != 0.0:
+            if self.d_flux_err is None:
+                raise ValueError("cbv_correct with alpha != 0 needs flux errors (the ridge width is median(flux_err) / sqrt(|alpha|))")
+            d_mu, d_sg = DeviceBuffer(h, B * K * 8), DeviceBuffer(h, B * K * 8)
+            _capi._check(_capi._lib.lk_ridge_prior_batch_dev(h._h, B, N, K, _vp(self.d_flux_err.ptr), float(alpha), _vp(d_mu.ptr),
+                                                             _vp(d_sg.ptr), _vp(self.stream or None)))
+        return self._regress_shared(Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, [])
+
+    def _regress_shared(self, Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, keep):
+        h, B, K = self.handle, len(self), Xa.shape[1]
+        d_cm = None
+        if cadence_mask is not None:
+            cm = np.ascontiguousarray(cadence_mask, dtype=np.uint8)
+            if cm.shape != (B, N):
+                raise ValueError("cadence_mask must be (B, N) = %s (got %s)" % ((B, N), cm.shape))
+            d_cm, k = _upload(h, cm, self.stream, np.uint8)
+            keep.append(k)
+        d_X, k = _upload(h, Xa, self.stream)
+        keep.append(k)
+        d_w, d_model, d_corr, d_outl = DeviceBuffer(h, B * K * 8), DeviceBuffer(h, B * N * 8), DeviceBuffer(h, B * N * 8), DeviceBuffer(h, B * N)
+        _capi._check(_capi._lib.lk_regress_shared_batch_dev(
+            h._h, B, N, K, _vp(d_X.ptr), _vp(self.d_flux.ptr), _vp(self.d_flux_err.ptr if self.d_flux_err is not None else None),
+            _vp(d_cm.ptr if d_cm is not None else None), _vp(d_mu.ptr if d_mu is not None else None),
+            _vp(d_sg.ptr if d_sg is not None else None), float(sigma), int(niters), _vp(d_w.ptr), _vp(d_model.ptr), _vp(d_outl.ptr),
+            None, _vp(self.stream or None)))
+        _capi._check(_capi._lib.lk_subtract_f64_dev(h._h, B * N, _vp(self.d_flux.ptr), _vp(d_model.ptr), _vp(d_corr.ptr),
+                                                    _vp(self.stream or None)))
+        if to_host:
+            corrected = d_corr.download(np.float64, B * N, stream=self.stream).reshape(B, N)
+            outl = d_outl.download(np.uint8, B * N, stream=self.stream).reshape(B, N).astype(bool)
+            return corrected, outl, d_w.download(np.float64, B * K, stream=self.stream).reshape(B, K)
+        out = self._new(self.d_time, d_corr, self.d_flux_err, self.n_off, nan_free=self.nan_free, is_sorted=self.is_sorted)
+        out.d_quality = self.d_quality
+        # scratch and inputs the stream may still be reading: held until the batch is synchronised or dropped
+        out._keep = keep + [d_X, d_cm, d_mu, d_sg, d_model, self]
+        return out, d_outl, d_w
+
     # ---------------------------------------------------------------- Lomb-Scargle
     def _ls_ready(self):
         """The batch the periodogram kernels see: NaN-flux cadences dropped (LombScarglePeriodogram.from_lightcurve,
@@ -1071,6 +1156,44 @@ class DevicePixelCubeBatch(object):
         # scratch and inputs the stream may still be reading: held until the batch is synchronised or dropped
         out._keep = keep + [d_X, d_ps, d_mu, d_w, d_model, d_sp, d_pld, d_bkg, g, d_f, d_e, d_k, pld_idx, bkg_idx, d_pc, d_bc, self]
         return out, d_outl
+
+
+def _design_arrays(X, prior_mu, prior_sigma):
+    """(X float64 (N, K), prior_mu, prior_sigma) of a shared design matrix: a host array, a ``DesignMatrix`` or a
+    ``DesignMatrixCollection`` (whose own priors stand in when none are given)."""
+    if hasattr(X, "prior_sigma") and hasattr(X, "X"):
+        if prior_mu is None and prior_sigma is None:
+            prior_mu, prior_sigma = np.asarray(X.prior_mu, dtype=np.float64), np.asarray(X.prior_sigma, dtype=np.float64)
+        X = X.X
+    Xa = np.ascontiguousarray(X, dtype=np.float64)
+    if Xa.ndim != 2 or Xa.shape[1] < 1:
+        raise ValueError("the design matrix must be 2-D (cadences x regressors), got shape %s" % (Xa.shape,))
+    if (prior_mu is None) != (prior_sigma is None):
+        raise ValueError("Please specify both `prior_mu` and `prior_sigma`")
+    if prior_mu is not None:
+        prior_mu, prior_sigma = np.asarray(prior_mu, dtype=np.float64), np.asarray(prior_sigma, dtype=np.float64)
+    return Xa, prior_mu, prior_sigma
+
+
+def _cbv_columns(cbvs, cbv_indices, ext_dm):
+    """The columns ``CBVCorrector._collection`` builds — [cbvs[:, idx - 1] | ext_dm | 1] — as one float64 (N, K) array."""
+    from .correctors.cbvcorrector import cbv_index_list
+    cbvs = np.asarray(cbvs, dtype=np.float64)
+    if cbvs.ndim != 2:
+        raise ValueError("cbvs must be 2-D (cadences x vectors)")
+    mats = []
+    if cbv_indices is not None:
+        mats.append(cbvs[:, cbv_index_list(cbv_indices, cbvs.shape[1]) - 1])
+    if ext_dm is not None:
+        if not (hasattr(ext_dm, "X") and hasattr(ext_dm, "prior_sigma")):
+            raise ValueError("ext_dm must be a DesignMatrix")
+        if ext_dm.shape[0] != cbvs.shape[0]:
+            raise ValueError("ext_dm must contain the same number of cadences as the basis vectors")
+        mats.append(np.asarray(ext_dm.X, dtype=np.float64))
+    if not mats:
+        raise ValueError("nothing to fit: pass cbv_indices and/or ext_dm")
+    mats.append(np.ones((cbvs.shape[0], 1)))
+    return np.ascontiguousarray(np.hstack(mats))
 
 
 def _cube_times_sorted(time):
