@@ -15,6 +15,8 @@
  *   lk_regress_batch*    <- RegressionCorrector._fit_coefficients + the sigma-clip loop of .correct,
  *                           src/lightkurve/correctors/regressioncorrector.py:127-189, 243-279.
  *   lk_regress_shared_batch*  the same for B targets on ONE shared design matrix (CBVCorrector.correct_gaussian_prior).
+ *   lk_underfit_neighbors_batch* <- correctors.metrics.underfit_metric_neighbors + _compute_correlation,
+ *                           src/lightkurve/correctors/metrics.py:141-257, 451-475, neighbours = other targets of the batch.
  *   lk_ls_fast_batch*    <- astropy lombscargle_fast (the DEFAULT ls_method="fast", periodogram.py:650): fast_impl.py.
  *   lk_ls_chi2_batch* / lk_ls_fastchi2_batch* <- astropy lombscargle_chi2 / lombscargle_fastchi2 (nterms > 1,
  *                           periodogram.py:948-967).
@@ -439,6 +441,27 @@ int lk_ridge_prior_batch_dev(lk_handle *h, int B, int N, int K, const double *fl
                              double *prior_sigma, void *stream);
 /* out[i] = a[i] - b[i] for n doubles on the device (flux - model: the corrected flux of RegressionCorrector.correct). */
 int lk_subtract_f64_dev(lk_handle *h, int64_t n, const double *a, const double *b, double *out, void *stream);
+
+/* ---- Under-fitting goodness metric of B targets whose neighbours are OTHER TARGETS OF THE SAME BATCH, given by index
+ * (reference src/lightkurve/correctors/metrics.py:141-257 underfit_metric_neighbors over _compute_correlation, :451-475; the
+ * reference fetches the neighbours' light curves from MAST — here they are the other corrected targets of the field, already
+ * in device memory).  flux: B x N, NaN-free; keep_idx: the n kept cadences shared by every target (ascending indices into
+ * [0, N): the reference's lc[cadence_mask]), or NULL = all cadences (then n == N); neighbors: B x M int32, -1 = padding.
+ * Per target t, with z_b[i] = flux_b[keep_idx[i]] / numpy.median(flux_b[keep_idx]) - 1.0 and G(a,b) = sum_i z_a[i] z_b[i]:
+ *   corr[t][p]  = G(t,j) / sqrt(G(t,t) G(j,j)) for j = neighbors[t][p] (0 when either self-product is 0: the reference's
+ *                 rms -> inf rule; NaN at padding), B x M or NULL;
+ *   metric[t]   = 2 / (1 + exp(scale * sum_p |corr[t][p]|^3 / (m + 1))), m = the valid neighbours of t,
+ *                 scale = ln(2 / 0.95 - 1) / (0.0007 + 0.8083 n^-0.5023); 1.0 when m == 0.
+ * A median of exactly zero gives non-finite z and a non-finite result, as in the reference.  The order in which G(a,b) is
+ * summed depends on n alone (not on B, M, the position in the list or the workgroup): G(t,j) and G(j,t) are the same bits, a
+ * run on a sub-batch gives the same bits, and so do two runs; no atomics.  B >= 1, 2 <= n <= N, M >= 0 (LK_EINVAL otherwise);
+ * the host flavour also checks keep_idx and every neighbour index (-1, or in [0, B) and not the target itself) — the _dev
+ * flavour treats any index outside [0, B) as padding and checks nothing else.  Scratch: B x ceil(n / 128) x 128 + B doubles of
+ * the handle's arena.  The _dev call synchronises nothing. */
+int lk_underfit_neighbors_batch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
+                                const int32_t *neighbors, double *corr, double *metric);
+int lk_underfit_neighbors_batch_dev(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
+                                    const int32_t *neighbors, double *corr, double *metric, void *stream);
 
 /* ---- LightCurve.flatten trend: masked, gap-segmented Savitzky-Golay + sigma-clip loop + linear re-interpolation
  * t (non-decreasing per target), flux (may hold NaN); mask: 1 = EXCLUDE the cadence from the fit (lightkurve's

@@ -163,6 +163,10 @@ SIGNATURES = [
     ("lk_ridge_prior_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp]),
     ("lk_subtract_f64_dev", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    ("lk_underfit_neighbors_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, _c_i32p, ctypes.c_int, _c_i32p, _c_dp, _c_dp]),
+    ("lk_underfit_neighbors_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     ("lk_savgol_trend_batch", ctypes.c_int,
      [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
       ctypes.c_double, _c_dp, _c_u8p]),
@@ -813,6 +817,55 @@ def regress_shared_batch(X, y, err=None, cadence_mask=None, prior_mu=None, prior
     if want_cov:
         res["coefficients_cov"] = cov
     return res
+
+
+# --------------------------------------------------------------------------------------------- under-fitting metric
+def underfit_arguments(B, N, neighbors, cadence_mask=None):
+    """The checks of the under-fitting metric that need no device, shared by its three front ends: ``neighbors`` -> int32
+    (B, M) C-contiguous (-1 = padding, else an index in [0, B) other than the row's own), ``cadence_mask`` (bool (N,), True
+    = used) -> ascending int32 indices of the kept cadences, or None for all of them.  Returns (neighbors, keep_idx, n)."""
+    nb = np.asarray(neighbors)
+    if nb.size == 0 and nb.ndim == 2:
+        nb = nb.astype(np.int32)
+    if nb.ndim != 2 or nb.shape[0] != B or not np.issubdtype(nb.dtype, np.integer):
+        raise ValueError("neighbors must be an integer array of shape (B, M) = (%d, M) (got %s of shape %s)" % (B, nb.dtype, nb.shape))
+    if nb.size:
+        if nb.min() < -1 or nb.max() >= B:
+            raise ValueError("a neighbour is -1 (padding) or an index in [0, %d): got values between %d and %d" % (B, nb.min(), nb.max()))
+        own = np.nonzero(nb == np.arange(B)[:, None])
+        if len(own[0]):
+            raise ValueError("a target cannot be its own neighbour: row %d lists %d" % (own[0][0], own[0][0]))
+    nb = np.ascontiguousarray(nb, dtype=np.int32)
+    keep_idx, n = None, int(N)
+    if cadence_mask is not None:
+        cm = np.asarray(cadence_mask)
+        if cm.shape != (N,):
+            raise ValueError("cadence_mask must be one bool per cadence, shape (%d,), shared by every target (got shape %s)" % (N, cm.shape))
+        keep_idx = np.ascontiguousarray(np.nonzero(cm.astype(bool))[0], dtype=np.int32)
+        n = int(keep_idx.size)
+    if n < 2:
+        raise ValueError("the under-fitting metric needs at least two kept cadences (got %d)" % n)
+    return nb, keep_idx, n
+
+
+def underfit_neighbors_batch(flux, neighbors, cadence_mask=None, device=0):
+    """The under-fitting goodness metric (reference metrics.py:141-257, 451-475) of every row of ``flux`` (B, N; NaN-free)
+    against its neighbours, which are other rows of ``flux``: ``neighbors`` int (B, M), -1 = padding; ``cadence_mask`` bool
+    (N,), True = used.  Returns dict(metric[B], correlations[B, M] (NaN at padding))."""
+    flux = np.ascontiguousarray(flux, dtype=np.float64)
+    if flux.ndim != 2 or flux.shape[0] < 1:
+        raise ValueError("flux must be (B, N) with B >= 1 (got shape %s)" % (flux.shape,))
+    B, N = flux.shape
+    nb, keep_idx, n = underfit_arguments(B, N, neighbors, cadence_mask)
+    if np.isnan(flux).any():
+        raise ValueError("the under-fitting metric needs NaN-free flux: drop the NaN cadences of every target first (remove_nans())")
+    M = nb.shape[1]
+    h = Handle.get(device)
+    metric = np.empty(B, dtype=np.float64)
+    corr = np.empty((B, M), dtype=np.float64)
+    _check(_lib.lk_underfit_neighbors_batch(h._h, B, N, _ptr(flux), n, _ptr(keep_idx, _c_i32p), M, _ptr(nb if M else None, _c_i32p),
+                                            _ptr(corr if M else None), _ptr(metric)))
+    return dict(metric=metric, correlations=corr)
 
 
 # --------------------------------------------------------------------------------------------- flatten

@@ -12,7 +12,8 @@ import numpy as np
 from ..batch import lombscargle_batch
 from ..lightcurve import LightCurve
 
-__all__ = ["overfit_metric_lombscargle", "overfit_metric_lombscargle_batch", "underfit_metric_neighbors"]
+__all__ = ["overfit_metric_lombscargle", "overfit_metric_lombscargle_batch", "underfit_metric_neighbors",
+           "underfit_metric_batch", "nearest_neighbors"]
 
 
 def _prepared(lc):
@@ -136,3 +137,37 @@ def underfit_metric_neighbors(corrected_lc, neighbor_flux):
         warnings.simplefilter("ignore")
         c = scale * np.nanmean(np.abs(corr) ** 3, axis=0)[-1]
     return float(2.0 / (1.0 + np.exp(c)))
+
+
+def underfit_metric_batch(flux, neighbors, cadence_mask=None, device=0, return_correlations=False):
+    """``underfit_metric_neighbors`` for every row of a host array ``flux`` (B, N; NaN-free) in ONE GPU call
+    (``lk_underfit_neighbors_batch``), the neighbours of a target being other rows of ``flux``: ``neighbors`` int (B, M), row
+    t = the indices of t's neighbours padded with -1 (``nearest_neighbors`` builds it from positions); ``cadence_mask`` bool
+    (N,), shared by every target, True = used (the reference's ``lc[cadence_mask]``).  Returns metric[B], and with
+    ``return_correlations`` also correlations[B, M] (NaN at padding).  A resident batch has the same call as
+    ``DeviceLightCurveBatch.under_fitting_metric``: the same kernels, the same bits."""
+    from .. import _capi
+    r = _capi.underfit_neighbors_batch(flux, neighbors, cadence_mask=cadence_mask, device=device)
+    return (r["metric"], r["correlations"]) if return_correlations else r["metric"]
+
+
+def nearest_neighbors(x, y, n_neighbors=50, chunk=1024):
+    """The ``min(n_neighbors, B - 1)`` nearest other targets of each of B targets at planar coordinates (``x``, ``y``) ->
+    int32 (B, min(n_neighbors, B - 1)), nearest first, ties broken by index, the target itself never listed (the reference
+    takes the nearest targets on the sky from a MAST search, metrics.py:274-412).  Targets are handled ``chunk`` at a time,
+    so no B x B matrix exists."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    if x.shape != y.shape:
+        raise ValueError("x and y must have one entry per target each (got %d and %d)" % (x.size, y.size))
+    B = x.size
+    k = int(min(int(n_neighbors), B - 1))
+    if k <= 0:
+        return np.zeros((B, 0), dtype=np.int32)
+    out = np.empty((B, k), dtype=np.int32)
+    for a in range(0, B, int(chunk)):
+        e = min(a + int(chunk), B)
+        d2 = (x[a:e, None] - x[None, :]) ** 2 + (y[a:e, None] - y[None, :]) ** 2
+        d2[np.arange(e - a), np.arange(a, e)] = np.inf          # never the target itself
+        out[a:e] = np.argsort(d2, axis=1, kind="stable")[:, :k]   # stable: equal distances stay in index order
+    return out

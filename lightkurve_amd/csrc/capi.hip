@@ -600,6 +600,47 @@ int lk_subtract_f64_dev(lk_handle *h, int64_t n, const double *a, const double *
     return lk::subtract_launch(h, n, a, b, out, static_cast<hipStream_t>(stream));
 }
 
+// ------------------------------------------------------------------------------------------------ under-fitting metric
+int lk_underfit_neighbors_batch_dev(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
+                                    const int32_t *neighbors, double *corr, double *metric, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::underfit_neighbors_launch(h, B, N, flux, n, keep_idx, M, neighbors, corr, metric, static_cast<hipStream_t>(stream));
+}
+
+int lk_underfit_neighbors_batch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
+                                const int32_t *neighbors, double *corr, double *metric) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 1, "B must be >= 1 (got %d)", B);
+    LK_REQUIRE(N >= 2 && n >= 2 && n <= N, "need 2 <= n <= N (got n=%d, N=%d): the metric needs at least two kept cadences", n, N);
+    LK_REQUIRE(keep_idx != nullptr || n == N, "keep_idx is NULL (all cadences) but n=%d != N=%d", n, N);
+    LK_REQUIRE(M >= 0, "M must be >= 0 (got %d)", M);
+    LK_REQUIRE(flux && metric, "NULL buffer");
+    LK_REQUIRE(M == 0 || neighbors != nullptr, "neighbors is NULL with M=%d", M);
+    if (keep_idx)
+        for (int i = 0; i < n; ++i)
+            LK_REQUIRE(keep_idx[i] >= 0 && keep_idx[i] < N && (i == 0 || keep_idx[i] > keep_idx[i - 1]),
+                       "keep_idx[%d]=%d: the kept cadences must be ascending indices in [0, %d)", i, keep_idx[i], N);
+    for (int b = 0; b < B; ++b)
+        for (int p = 0; p < M; ++p) {
+            const int32_t j = neighbors[(size_t)b * M + p];
+            LK_REQUIRE(j == -1 || (j >= 0 && j < B), "neighbors[%d][%d]=%d: a neighbour is -1 (padding) or an index in [0, %d)", b, p,
+                       (int)j, B);
+            LK_REQUIRE(j != b, "neighbors[%d][%d]=%d: a target cannot be its own neighbour", b, p, (int)j);
+        }
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t nm = (size_t)B * M;
+    const double *dflux;
+    const int32_t *dkeep, *dnbr;
+    double *dcorr, *dmetric;
+    lk::StagedCall io(h);
+    int rc = io.in(dflux, flux, (size_t)B * N).in(dkeep, keep_idx, (size_t)n).in(dnbr, M ? neighbors : nullptr, nm)
+                 .out(dcorr, M ? corr : nullptr, nm).out(dmetric, metric, (size_t)B).stage();
+    if (rc) return rc;
+    rc = lk::underfit_neighbors_launch(h, B, N, dflux, n, dkeep, M, dnbr, dcorr, dmetric, nullptr);
+    return rc ? rc : io.finish();
+}
+
 // ------------------------------------------------------------------------------------------------ flatten
 int lk_savgol_design(int window, int polyorder, double *coeffs, double *edge) {
     return lk::savgol_design_host(window, polyorder, coeffs, edge);

@@ -143,6 +143,8 @@ int regress_shared_launch(lk_handle *h, int B, int N, int K, const double *X, co
 int ridge_prior_launch(lk_handle *h, int B, int N, int K, const double *err, double alpha, double *prior_mu, double *prior_sigma,
                        hipStream_t stream);
 int subtract_launch(lk_handle *h, int64_t n, const double *a, const double *b, double *out, hipStream_t stream);
+int underfit_neighbors_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
+                              const int32_t *neighbors, double *corr, double *metric, hipStream_t stream);
 int model_part_launch(lk_handle *h, int B, int N, int K, int c0, int c1, const double *X, const double *w, double *out,
                       hipStream_t stream);
 int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,

@@ -386,16 +386,20 @@ class DeviceLightCurveBatch(object):
 
     # ---------------------------------------------------------------- cotrending on one shared design matrix
     def _uniform_n(self, rows, what):
-        """The one cadence count of the batch, checked against the ``rows`` of the shared design matrix (no device call)."""
+        """The one cadence count of the batch, checked against the ``rows`` of the shared design matrix unless ``rows`` is None
+        (no device call)."""
         counts = np.diff(self.n_off)
         if len(counts) == 0:
             raise ValueError("%s needs at least one light curve" % what)
         if counts.min() != counts.max():
+            if rows is None:
+                raise ValueError("%s needs one cadence count for every target: this batch has between %d and %d cadences per target"
+                                 % (what, counts.min(), counts.max()))
             raise ValueError("%s needs one cadence count for every target: this batch has between %d and %d cadences per target "
                              "and the design matrix has %d rows (regression_correct_batch takes ragged batches)"
                              % (what, counts.min(), counts.max(), rows))
         N = int(counts[0])
-        if rows != N:
+        if rows is not None and rows != N:
             raise ValueError("%s: the design matrix has %d rows, the light curves have %d cadences" % (what, rows, N))
         return N
 
@@ -468,6 +472,47 @@ class DeviceLightCurveBatch(object):
         # scratch and inputs the stream may still be reading: held until the batch is synchronised or dropped
         out._keep = keep + [d_X, d_cm, d_mu, d_sg, d_model, self]
         return out, d_outl, d_w
+
+    # ---------------------------------------------------------------- under-fitting metric, neighbours by index
+    def under_fitting_metric(self, neighbors, cadence_mask=None, return_correlations=False, to_host=True):
+        """``underfit_metric_neighbors`` (reference correctors/metrics.py:141-257, 451-475) for every target of the batch, the
+        neighbours being OTHER TARGETS OF THIS BATCH (the reference fetches them from MAST; after ``cbv_correct`` they are the
+        corrected targets of the same field, already in HBM): ``neighbors`` int (B, M), row t = the indices of t's neighbours,
+        padded with -1 (``correctors.metrics.nearest_neighbors`` builds it from positions); ``cadence_mask`` bool (N,), shared
+        by every target, True = used (the reference's ``lc[cadence_mask]``).  Needs one cadence count for every target and a
+        NaN-free batch (``remove_nans()``).  Zero-centred flux is fine (the correlation does not depend on the scale of
+        flux / median - 1); a median of exactly zero gives a non-finite result, as in the reference.  Returns metric[B]
+        (``to_host=True``; 8 bytes per target cross PCIe) or its ``DeviceBuffer`` (``to_host=False``: nothing synchronised);
+        ``return_correlations``: also correlations[B, M] (NaN at padding), host array or ``DeviceBuffer`` likewise."""
+        N = self._uniform_n(None, "under_fitting_metric")
+        if not self.nan_free:
+            raise ValueError("under_fitting_metric needs a NaN-free batch: call remove_nans() first (and cotrend after it)")
+        B = len(self)
+        nb, keep_idx, n = _capi.underfit_arguments(B, N, neighbors, cadence_mask)
+        M = nb.shape[1]
+        h, st = self.handle, _vp(self.stream or None)
+        d_nb = d_keep = d_corr = None
+        if M:
+            d_nb, k = _upload(h, nb, self.stream, np.int32)
+            self._keep.append(k)
+        if keep_idx is not None:
+            d_keep, k = _upload(h, keep_idx, self.stream, np.int32)
+            self._keep.append(k)
+        if return_correlations:
+            d_corr = DeviceBuffer(h, max(B * M, 1) * 8)
+        d_metric = DeviceBuffer(h, B * 8)
+        _capi._check(_capi._lib.lk_underfit_neighbors_batch_dev(
+            h._h, B, N, _vp(self.d_flux.ptr), n, _vp(d_keep.ptr if d_keep is not None else None), M,
+            _vp(d_nb.ptr if d_nb is not None else None), _vp(d_corr.ptr if (d_corr is not None and M) else None), _vp(d_metric.ptr), st))
+        # inputs the stream may still be reading: held until the batch is synchronised or dropped
+        self._keep += [d_nb, d_keep]
+        if not to_host:
+            return (d_metric, d_corr) if return_correlations else d_metric
+        metric = d_metric.download(np.float64, B, stream=self.stream)
+        if return_correlations:
+            corr = d_corr.download(np.float64, B * M, stream=self.stream) if M else np.empty(0)
+            return metric, corr.reshape(B, M)
+        return metric
 
     # ---------------------------------------------------------------- Lomb-Scargle
     def _ls_ready(self):

@@ -12,7 +12,14 @@ run to put under `rocprofv3 --kernel-trace --stats` for the kernel-time sum of o
 `pld_ragged`: the resident call on `LK_WALLS_B` (default 500) cutouts whose threshold masks have five different sizes, three ways in
 ONE process, alternating: R the ragged call (K2 default masks, `ragged_masks=True`), U the uniform call on the same cutouts with
 every pixel in both masks, G what a user writes without the keyword — one call per group of equal mask size, on resident batches
-built beforehand (their upload is not timed)."""
+built beforehand (their upload is not timed).
+
+`underfit`: the under-fitting goodness metric of `LK_WALLS_B` (default 1000) cotrended targets x `LK_WALLS_N` (default 20000)
+cadences with `LK_WALLS_M` (default 50) neighbours each, two ways in ONE process, alternating, `LK_WALLS_REPS` (default 3) times:
+R the resident call (`cbv_correct(...)[0].under_fitting_metric(neighbors, cadence_mask)`: 8 bytes per target come back), R' the
+same with `to_host=False` plus a synchronise, H the host route (download the corrected flux, then `underfit_metric_neighbors` per
+target on 16 threads).  Every timed region ends in a synchronise.  `underfit_trace`: only resident calls — the run to put
+under `rocprofv3 --kernel-trace --stats` for the two kernels' times."""
 import cProfile
 import io
 import os
@@ -158,6 +165,62 @@ def pld_ragged():
     sys.stdout.flush()
 
 
+def underfit(which):
+    from concurrent.futures import ThreadPoolExecutor
+    from lightkurve_amd import _capi
+    from lightkurve_amd.correctors import metrics
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    from lightkurve_amd.lightcurve import LightCurve
+    B, N, M = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000"), ("LK_WALLS_M", "50")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "3"))
+    rng = np.random.default_rng(7)
+    t = np.linspace(0, 27, N)
+    S = np.column_stack([np.sin(2 * np.pi * t / 13.7), (t / 27 - 0.5) ** 2])
+    y = 1000.0 * rng.uniform(0.5, 2, (B, 1)) * (1 + rng.normal(0, 0.01, (B, 2)) @ S.T + 1e-3 * rng.normal(0, 1, (B, N)))
+    cm = rng.random(N) > 0.1
+    nb = metrics.nearest_neighbors(rng.uniform(0, 1, B), rng.uniform(0, 1, B), M)
+    M = nb.shape[1]
+    raw = DeviceLightCurveBatch.from_arrays(np.tile(t, B), y.reshape(-1), (1e-3 * y).reshape(-1), np.arange(B + 1) * N).remove_nans()
+    cor = raw.cbv_correct(S, cbv_indices=[1, 2], cadence_mask=np.broadcast_to(cm, (B, N)))[0]
+    cor.synchronize()
+    sync = _capi.Handle.get(0).synchronize
+    n = int(cm.sum())
+    pitch = -(-n // 128) * 128
+    model = "pair pass reads %.2f GB of z rows (B M pitch 8), scratch %.1f MB" % (B * M * pitch * 8 / 1e9, (B * pitch * 8 + B * 8) / 1e6)
+    if "underfit_trace" in which:
+        calls = 1 + max(reps, 5)
+        for _ in range(calls):
+            cor.under_fitting_metric(nb, cadence_mask=cm, to_host=False)
+        sync()
+        print("underfit_trace: %d resident under_fitting_metric calls on %d x %d, M = %d, %d kept cadences; per call the %s"
+              % (calls, B, N, M, n, model))
+        return
+
+    def host_route():
+        flux = cor.flux_host().reshape(B, N)
+        z = flux[:, cm] / np.median(flux[:, cm], axis=1)[:, None] - 1.0
+        tk = t[cm]
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            return np.array(list(ex.map(lambda b: metrics.underfit_metric_neighbors(LightCurve(tk, flux[b, cm]), z[nb[b]].T), range(B))))
+
+    got = cor.under_fitting_metric(nb, cadence_mask=cm)                     # warm-up of both routes
+    cor.under_fitting_metric(nb, cadence_mask=cm, to_host=False)
+    sync()
+    ref = host_route()
+    R, R2, H = [], [], []
+    for _ in range(reps):
+        R.append(timed(lambda: cor.under_fitting_metric(nb, cadence_mask=cm))[0])          # (the download synchronises)
+        R2.append(timed(lambda: (cor.under_fitting_metric(nb, cadence_mask=cm, to_host=False), sync()))[0])
+        H.append(timed(host_route)[0])
+    print("under-fitting metric, %d cotrended targets x %d cadences (%d kept), %d neighbours each; %s" % (B, N, n, M, model))
+    print("  R  batch.under_fitting_metric() -> metric[B] on the host        %s" % spread(R))
+    print("  R' the same, to_host=False + synchronise                        %s" % spread(R2))
+    print("  H  download + underfit_metric_neighbors per target, 16 threads  %s" % spread(H))
+    print("  max |R - H| = %.3e; metric min %.4f median %.4f; H / R = %.0f"
+          % (float(np.max(np.abs(got - ref))), got.min(), float(np.median(got)), np.median(H) / np.median(R)))
+    sys.stdout.flush()
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -167,6 +230,8 @@ def main():
         pld_dev(which)
     if "pld_ragged" in which:
         pld_ragged()
+    if {"underfit", "underfit_trace"} & set(which):
+        underfit(which)
     if "flatten" in which:
         lcs = []
         for i in range(1000):
