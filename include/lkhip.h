@@ -17,6 +17,8 @@
  *   lk_regress_shared_batch*  the same for B targets on ONE shared design matrix (CBVCorrector.correct_gaussian_prior).
  *   lk_underfit_neighbors_batch* <- correctors.metrics.underfit_metric_neighbors + _compute_correlation,
  *                           src/lightkurve/correctors/metrics.py:141-257, 451-475, neighbours = other targets of the batch.
+ *   lk_overfit_metric_batch* <- correctors.metrics.overfit_metric_lombscargle, src/lightkurve/correctors/metrics.py:24-138,
+ *                           for B targets at once, the white noise made on the device (Philox4x32-10).
  *   lk_ls_fast_batch*    <- astropy lombscargle_fast (the DEFAULT ls_method="fast", periodogram.py:650): fast_impl.py.
  *   lk_ls_chi2_batch* / lk_ls_fastchi2_batch* <- astropy lombscargle_chi2 / lombscargle_fastchi2 (nterms > 1,
  *                           periodogram.py:948-967).
@@ -462,6 +464,48 @@ int lk_underfit_neighbors_batch(lk_handle *h, int B, int N, const double *flux, 
                                 const int32_t *neighbors, double *corr, double *metric);
 int lk_underfit_neighbors_batch_dev(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
                                     const int32_t *neighbors, double *corr, double *metric, void *stream);
+
+/* ---- Over-fitting goodness metric of B targets (reference src/lightkurve/correctors/metrics.py:24-138
+ * overfit_metric_lombscargle, as CBVCorrector.over_fitting_metric calls it on lc[cadence_mask]).  time, flux_orig, flux_corr,
+ * err_corr: B x N, NaN-free flux; keep_idx: the n kept cadences shared by every target (ascending indices into [0, N)), or
+ * NULL = all cadences (then n == N).  Per target b on its kept cadences:
+ *   z0 = flux_orig / numpy.median(flux_orig) - 1.0, z1 = flux_corr / numpy.median(flux_corr) - 1.0 (exact medians),
+ *   mean_unc = nanmean(err_corr / median(flux_corr));
+ *   P0, P1 = the default Lomb-Scargle ('fast', amplitude normalisation, fit_mean = center_data = 1, oversampling 5) of z0, z1
+ *   at the times t - t[first kept] on the grid f0 + df * arange(M) [1/d];  Pn_k = the same of g_k = normal * mean_unc;
+ *   change = P1 - P0 (NaN dropped), n_up = #(change > 0), S = sum of the positive changes;
+ *   per_k = 0 if n_up == 0, inf if n_up * nanmean(Pn_k) == 0, else S / (n_up * nanmean(Pn_k));
+ *   metric[b] = 2 / (1 + exp(max(mean_k per_k, 0))), NaN propagating as numpy's does.
+ * NOISE.  The reference draws from the global numpy.random; here a counter-based generator gives any (target, sample,
+ * cadence) the same number whatever B, the launch shape or the number of sample rounds: Philox4x32-10 (multipliers
+ * 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key = (seed & 0xffffffff, seed >> 32), counter =
+ * (i, k, first_target + b, stream_id): i the pair of kept cadences (2i, 2i + 1), k the sample, b the row.  From the output
+ * words x0..x3: u1 = (((x0 >> 5) << 26) + (x1 >> 6) + 1) 2^-53, u2 = (((x2 >> 5) << 26) + (x3 >> 6)) 2^-53,
+ * r = sqrt(-2 ln u1); cadence 2i gets r cos(2 pi u2), cadence 2i + 1 gets r sin(2 pi u2) (dropped for the last pair of an
+ * odd n).  first_target + B <= 2^32, 0 <= stream_id < 2^32.
+ * SCRATCH.  The periodograms run through the LS 'fast' launcher, which owns the handle's scratch arena, so rows, noise and
+ * spectra live in `scratch`, a 256-byte aligned device block of the caller's: z0, z1 (B n each), and per round of R samples
+ * R B n times + R B n noise + R B M spectra, plus P0, P1 (B M each).  lk_overfit_scratch_bytes returns the size for the
+ * largest R <= n_samples that fits max_scratch_bytes (0: LK_OVERFIT_SCRATCH_DEFAULT), or for R = 1 when none does; the _dev
+ * call takes the largest R that fits scratch_bytes.  R does not change a bit of the result; nor do B or the rows around a
+ * target; two runs give the same bits (every sum has an order that depends on its length alone; no atomics).
+ * B >= 1, 3 <= n <= N, M >= 2, n_samples >= 1, scratch_bytes >= the R = 1 size: LK_EINVAL otherwise.  The host flavour
+ * stages its buffers and its scratch in the handle's staging arena and also checks keep_idx.  The _dev call enqueues on
+ * `stream`; it adds no synchronisation to the LS launcher's own. */
+#define LK_OVERFIT_SCRATCH_DEFAULT ((int64_t)4 << 30)
+int lk_overfit_scratch_bytes(int B, int n, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes,
+                             int *samples_per_round);
+int lk_overfit_metric_batch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, const double *flux_corr,
+                            const double *err_corr, int n, const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples,
+                            uint64_t seed, int64_t first_target, int64_t stream_id, int64_t max_scratch_bytes, double *metric);
+int lk_overfit_metric_batch_dev(lk_handle *h, int B, int N, const double *time, const double *flux_orig, const double *flux_corr,
+                                const double *err_corr, int n, const int32_t *keep_idx, double f0, double df, int64_t M,
+                                int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id, void *scratch,
+                                int64_t scratch_bytes, double *metric, void *stream);
+/* out[b][c] = the standard normal of (target first_target + b, sample k, kept cadence c), B x n float64 on the device (16-byte
+ * aligned): the generator of lk_overfit_metric_batch on its own. */
+int lk_overfit_noise_batch_dev(lk_handle *h, int B, int n, int k, uint64_t seed, int64_t first_target, int64_t stream_id,
+                               double *out, void *stream);
 
 /* ---- LightCurve.flatten trend: masked, gap-segmented Savitzky-Golay + sigma-clip loop + linear re-interpolation
  * t (non-decreasing per target), flux (may hold NaN); mask: 1 = EXCLUDE the cadence from the fit (lightkurve's

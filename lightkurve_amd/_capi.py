@@ -167,6 +167,17 @@ SIGNATURES = [
      [_vp, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, _c_i32p, ctypes.c_int, _c_i32p, _c_dp, _c_dp]),
     ("lk_underfit_neighbors_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    ("lk_overfit_scratch_bytes", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+      ctypes.POINTER(ctypes.c_int)]),
+    ("lk_overfit_metric_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_i32p, ctypes.c_double, ctypes.c_double,
+      ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _c_dp]),
+    ("lk_overfit_metric_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
+      ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp]),
+    ("lk_overfit_noise_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
     ("lk_savgol_trend_batch", ctypes.c_int,
      [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
       ctypes.c_double, _c_dp, _c_u8p]),
@@ -866,6 +877,96 @@ def underfit_neighbors_batch(flux, neighbors, cadence_mask=None, device=0):
     _check(_lib.lk_underfit_neighbors_batch(h._h, B, N, _ptr(flux), n, _ptr(keep_idx, _c_i32p), M, _ptr(nb if M else None, _c_i32p),
                                             _ptr(corr if M else None), _ptr(metric)))
     return dict(metric=metric, correlations=corr)
+
+
+# --------------------------------------------------------------------------------------------- over-fitting metric
+OVERFIT_SCRATCH_DEFAULT = 4 << 30   # LK_OVERFIT_SCRATCH_DEFAULT in include/lkhip.h
+
+
+def overfit_grid(frequency):
+    """``frequency`` [1/d] -> (f0, df, M) as the LS 'fast' path takes a grid (f0 = frequency[0], df = frequency[1] -
+    frequency[0]); ValueError unless it is a regular grid (astropy's ``_is_regular``) of at least two ascending frequencies."""
+    from .periodogram import is_regular
+    f = np.asarray(frequency, dtype=np.float64)
+    if f.ndim != 1 or f.size < 2:
+        raise ValueError("the over-fitting metric needs a regular grid of at least two frequencies (got shape %s)" % (f.shape,))
+    if not np.all(np.isfinite(f)) or not is_regular(f) or not f[1] > f[0] or f[0] < 0:
+        raise ValueError("the over-fitting metric needs a regular, ascending grid of non-negative frequencies in 1/d (the default "
+                         "Lomb-Scargle method takes no other)")
+    return float(f[0]), float(f[1] - f[0]), int(f.size)
+
+
+def overfit_default_grid(time):
+    """The grid ``LombScarglePeriodogram.from_lightcurve`` builds for a light curve with these (kept) times: amplitude
+    normalisation, oversample factor 5, up to the Nyquist frequency (reference periodogram.py:793-798, 850-911) [1/d]."""
+    time = np.asarray(time, dtype=np.float64)
+    nyquist = 0.5 * (1.0 / np.median(np.diff(time)))
+    fs = (1.0 / (time[-1] - time[0])) / 5.0
+    return np.arange(fs, nyquist, fs)
+
+
+def overfit_arguments(N, n_samples=10, cadence_mask=None, frequency=None, seed=0, first_target=0, stream_id=0, B=1):
+    """The checks of the over-fitting metric that need no device, shared by its front ends.  Returns (keep_idx or None, n,
+    grid or None): ``cadence_mask`` (bool (N,), True = used) -> ascending int32 indices; ``frequency`` -> ``overfit_grid``."""
+    if int(n_samples) < 1:
+        raise ValueError("n_samples must be >= 1 (got %r)" % (n_samples,))
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("seed must be in [0, 2^64) (got %r)" % (seed,))
+    if int(first_target) < 0 or int(first_target) + int(B) > 1 << 32:
+        raise ValueError("first_target + B must stay within 32 bits (got %r + %d)" % (first_target, B))
+    if not 0 <= int(stream_id) < 1 << 32:
+        raise ValueError("stream_id must be in [0, 2^32) (got %r)" % (stream_id,))
+    keep_idx, n = None, int(N)
+    if cadence_mask is not None:
+        cm = np.asarray(cadence_mask)
+        if cm.shape != (N,):
+            raise ValueError("cadence_mask must be one bool per cadence, shape (%d,), shared by every target (got shape %s)" % (N, cm.shape))
+        keep_idx = np.ascontiguousarray(np.nonzero(cm.astype(bool))[0], dtype=np.int32)
+        n = int(keep_idx.size)
+    if n < 3:
+        raise ValueError("the over-fitting metric needs at least three kept cadences (got %d)" % n)
+    return keep_idx, n, (None if frequency is None else overfit_grid(frequency))
+
+
+def overfit_scratch_bytes(B, n, M, n_samples, max_scratch_bytes=None):
+    """(bytes, samples per round) of the caller-owned scratch block of ``lk_overfit_metric_batch_dev``."""
+    load_library()
+    nbytes, rounds = ctypes.c_int64(0), ctypes.c_int(0)
+    _check(_lib.lk_overfit_scratch_bytes(int(B), int(n), int(M), int(n_samples), int(max_scratch_bytes or 0), ctypes.byref(nbytes),
+                                         ctypes.byref(rounds)))
+    return nbytes.value, rounds.value
+
+
+def overfit_metric_batch(time, flux, flux_corrected, flux_err_corrected, frequency=None, n_samples=10, cadence_mask=None, seed=0,
+                         first_target=0, stream_id=0, device=0, max_scratch_bytes=None):
+    """The over-fitting goodness metric (reference metrics.py:24-138) of every row of host arrays ``flux`` / ``flux_corrected``
+    / ``flux_err_corrected`` (B, N; NaN-free flux) at ``time`` ((N,) shared, or (B, N)) -> metric[B]; the arguments of
+    ``DeviceLightCurveBatch.over_fitting_metric``."""
+    y0 = np.ascontiguousarray(flux, dtype=np.float64)
+    if y0.ndim != 2 or y0.shape[0] < 1:
+        raise ValueError("flux must be (B, N) with B >= 1 (got shape %s)" % (y0.shape,))
+    B, N = y0.shape
+    y1 = np.ascontiguousarray(flux_corrected, dtype=np.float64)
+    if flux_err_corrected is None:
+        raise ValueError("the over-fitting metric needs the flux errors of the corrected light curves")
+    e1 = np.ascontiguousarray(np.broadcast_to(np.asarray(flux_err_corrected, dtype=np.float64), y0.shape))
+    if y1.shape != y0.shape:
+        raise ValueError("flux and flux_corrected must have one shape (got %s and %s)" % (y0.shape, y1.shape))
+    t = np.asarray(time, dtype=np.float64)
+    if t.shape not in ((N,), (B, N)):
+        raise ValueError("time must be (N,) or (B, N) = (%d,) or (%d, %d) (got shape %s)" % (N, B, N, t.shape))
+    keep_idx, n, grid = overfit_arguments(N, n_samples, cadence_mask, frequency, seed, first_target, stream_id, B)
+    if np.isnan(y0).any() or np.isnan(y1).any():
+        raise ValueError("the over-fitting metric needs NaN-free flux: drop the NaN cadences of every target first (remove_nans())")
+    t = np.ascontiguousarray(np.broadcast_to(t, (B, N)))
+    if grid is None:
+        grid = overfit_grid(overfit_default_grid(t[0] if keep_idx is None else t[0, keep_idx]))
+    h = Handle.get(device)
+    metric = np.empty(B, dtype=np.float64)
+    _check(_lib.lk_overfit_metric_batch(h._h, B, N, _ptr(t), _ptr(y0), _ptr(y1), _ptr(e1), n, _ptr(keep_idx, _c_i32p), grid[0],
+                                        grid[1], grid[2], int(n_samples), int(seed), int(first_target), int(stream_id),
+                                        int(max_scratch_bytes or 0), _ptr(metric)))
+    return metric
 
 
 # --------------------------------------------------------------------------------------------- flatten

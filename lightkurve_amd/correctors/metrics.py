@@ -13,7 +13,7 @@ from ..batch import lombscargle_batch
 from ..lightcurve import LightCurve
 
 __all__ = ["overfit_metric_lombscargle", "overfit_metric_lombscargle_batch", "underfit_metric_neighbors",
-           "underfit_metric_batch", "nearest_neighbors"]
+           "underfit_metric_batch", "nearest_neighbors", "overfit_metric_batch"]
 
 
 def _prepared(lc):
@@ -56,6 +56,22 @@ def overfit_metric_lombscargle(original_lc, corrected_lc, n_samples=10, device=0
     metric = np.mean(per_iter)
     with np.errstate(over="ignore"):
         return float(2.0 / (1.0 + np.exp(np.max([metric, 0.0]))))
+
+
+def overfit_metric_batch(time, flux, flux_corrected, flux_err_corrected, frequency=None, n_samples=10, cadence_mask=None, seed=0,
+                         first_target=0, stream_id=0, device=0, max_scratch_bytes=None):
+    """``overfit_metric_lombscargle`` for every row of host arrays in ONE GPU call (``lk_overfit_metric_batch``): ``flux`` (the
+    originals), ``flux_corrected``, ``flux_err_corrected`` (B, N; NaN-free flux) at ``time`` ((N,) shared by the targets, or
+    (B, N)); ``cadence_mask`` bool (N,), True = used (the reference's ``lc[cadence_mask]``); ``frequency`` [1/d]: a regular
+    grid, or None = the grid ``LombScarglePeriodogram.from_lightcurve`` builds for target 0's kept cadences.  The white noise
+    does not come from ``numpy.random`` but from a counter-based generator on the device (Philox4x32-10 keyed by ``seed``,
+    counter (cadence pair, sample, ``first_target`` + row, ``stream_id``): include/lkhip.h), so a target's value does not depend
+    on the batch around it.  Returns metric[B].  A resident batch has the same call as
+    ``DeviceLightCurveBatch.over_fitting_metric``: the same kernels, the same bits."""
+    from .. import _capi
+    return _capi.overfit_metric_batch(time, flux, flux_corrected, flux_err_corrected, frequency=frequency, n_samples=n_samples,
+                                      cadence_mask=cadence_mask, seed=seed, first_target=first_target, stream_id=stream_id,
+                                      device=device, max_scratch_bytes=max_scratch_bytes)
 
 
 def overfit_metric_lombscargle_batch(original_lc, corrected_lcs, n_samples=1, device=0):

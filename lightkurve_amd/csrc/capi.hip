@@ -641,6 +641,58 @@ int lk_underfit_neighbors_batch(lk_handle *h, int B, int N, const double *flux, 
     return rc ? rc : io.finish();
 }
 
+// ------------------------------------------------------------------------------------------------ over-fitting metric
+int lk_overfit_scratch_bytes(int B, int n, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes,
+                             int *samples_per_round) {
+    return lk::overfit_scratch_bytes(B, n, M, n_samples, max_scratch_bytes, bytes, samples_per_round);
+}
+
+int lk_overfit_noise_batch_dev(lk_handle *h, int B, int n, int k, uint64_t seed, int64_t first_target, int64_t stream_id,
+                               double *out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::overfit_noise_launch(h, B, n, k, seed, first_target, stream_id, out, static_cast<hipStream_t>(stream));
+}
+
+int lk_overfit_metric_batch_dev(lk_handle *h, int B, int N, const double *time, const double *flux_orig, const double *flux_corr,
+                                const double *err_corr, int n, const int32_t *keep_idx, double f0, double df, int64_t M,
+                                int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id, void *scratch,
+                                int64_t scratch_bytes, double *metric, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::overfit_metric_launch(h, B, N, time, flux_orig, flux_corr, err_corr, n, keep_idx, f0, df, M, n_samples, seed,
+                                     first_target, stream_id, scratch, scratch_bytes, metric, static_cast<hipStream_t>(stream));
+}
+
+int lk_overfit_metric_batch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, const double *flux_corr,
+                            const double *err_corr, int n, const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples,
+                            uint64_t seed, int64_t first_target, int64_t stream_id, int64_t max_scratch_bytes, double *metric) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(N >= 3 && N < (1 << 30) && n <= N, "need n <= N < 2^30 (got n=%d, N=%d)", n, N);
+    LK_REQUIRE(keep_idx != nullptr || n == N, "keep_idx is NULL (all cadences) but n=%d != N=%d", n, N);
+    LK_REQUIRE(time && flux_orig && flux_corr && err_corr && metric, "NULL buffer");
+    int64_t bytes = 0;
+    int rc = lk::overfit_scratch_bytes(B, n, M, n_samples, max_scratch_bytes, &bytes, nullptr);
+    if (rc) return rc;
+    if (keep_idx)
+        for (int i = 0; i < n; ++i)
+            LK_REQUIRE(keep_idx[i] >= 0 && keep_idx[i] < N && (i == 0 || keep_idx[i] > keep_idx[i - 1]),
+                       "keep_idx[%d]=%d: the kept cadences must be ascending indices in [0, %d)", i, keep_idx[i], N);
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t bn = (size_t)B * N;
+    const double *dt, *dy0, *dy1, *de1;
+    const int32_t *dkeep;
+    double *dmetric;
+    char *dscr;
+    lk::StagedCall io(h);
+    rc = io.in(dt, time, bn).in(dy0, flux_orig, bn).in(dy1, flux_corr, bn).in(de1, err_corr, bn).in(dkeep, keep_idx, (size_t)n)
+             .out(dmetric, metric, (size_t)B).scratch(dscr, (size_t)bytes).stage();
+    if (rc) return rc;
+    rc = lk::overfit_metric_launch(h, B, N, dt, dy0, dy1, de1, n, dkeep, f0, df, M, n_samples, seed, first_target, stream_id, dscr,
+                                   bytes, dmetric, nullptr);
+    return rc ? rc : io.finish();
+}
+
 // ------------------------------------------------------------------------------------------------ flatten
 int lk_savgol_design(int window, int polyorder, double *coeffs, double *edge) {
     return lk::savgol_design_host(window, polyorder, coeffs, edge);

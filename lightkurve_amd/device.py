@@ -514,6 +514,89 @@ class DeviceLightCurveBatch(object):
             return metric, corr.reshape(B, M)
         return metric
 
+    # ---------------------------------------------------------------- over-fitting metric, noise made on the device
+    def _overfit_checks(self, original, n_samples, cadence_mask, frequency, seed, first_target, stream_id):
+        """Every check of ``over_fitting_metric`` that needs no device -> (N, keep_idx, n, grid or None)."""
+        N = self._uniform_n(None, "over_fitting_metric")
+        if not isinstance(original, DeviceLightCurveBatch):
+            raise ValueError("over_fitting_metric: `original` must be the resident batch before the correction")
+        if len(original) != len(self) or original._uniform_n(None, "over_fitting_metric (original)") != N:
+            raise ValueError("over_fitting_metric: the original batch must have the targets and cadences of the corrected one "
+                             "(%d x %d)" % (len(self), N))
+        if not (self.nan_free and original.nan_free):
+            raise ValueError("over_fitting_metric needs NaN-free batches: call remove_nans() first (and cotrend after it)")
+        if getattr(self, "d_flux_err", None) is None:
+            raise ValueError("over_fitting_metric needs the flux errors of the corrected batch (the noise level is their mean)")
+        return (N,) + _capi.overfit_arguments(N, n_samples, cadence_mask, frequency, seed, first_target, stream_id, len(self))
+
+    def over_fitting_metric(self, original, frequency=None, n_samples=10, cadence_mask=None, seed=0, first_target=0, stream_id=0,
+                            to_host=True, max_scratch_bytes=None):
+        """``overfit_metric_lombscargle(original_lc[cadence_mask], corrected_lc[cadence_mask], n_samples)`` (reference
+        correctors/metrics.py:24-138, as ``CBVCorrector.over_fitting_metric`` calls it) for every target, called ON THE
+        CORRECTED batch; ``original``: the resident batch before the correction (same targets, same cadences).  Both stay in
+        HBM: the two periodograms per target, the ``n_samples`` white-noise periodograms and their reduction to one float run
+        on the device; 8 bytes per target come back.  ``frequency`` [1/d]: a regular grid shared by the targets; None = the
+        grid ``LombScarglePeriodogram.from_lightcurve`` builds (amplitude normalisation, oversample factor 5) for target 0's
+        kept cadences (its N times are downloaded once: the targets of a cotrending channel share their cadences; a batch whose
+        targets have different times passes ``frequency``).  ``cadence_mask``: bool (N,), True = used.  The noise is not
+        ``numpy.random``'s but a counter-based generator's (Philox4x32-10 keyed by ``seed``; counter = (cadence pair, sample,
+        ``first_target`` + row, ``stream_id``)): a target's value does not depend on the batch, on ``max_scratch_bytes`` (the
+        samples are taken in rounds that keep the scratch block under it; default 4 GiB) or on the run.  Returns metric[B]
+        (``to_host=True``) or its ``DeviceBuffer`` (``to_host=False``: nothing synchronised after the periodograms' own
+        planning).  Needs one cadence count per batch, NaN-free batches, flux errors on the corrected batch, ``n_samples`` >= 1,
+        a regular grid of at least two frequencies and at least three kept cadences: ``ValueError`` before any device call."""
+        N, keep_idx, n, grid = self._overfit_checks(original, n_samples, cadence_mask, frequency, seed, first_target, stream_id)
+        B, h, st = len(self), self.handle, _vp(self.stream or None)
+        if grid is None:
+            t0 = self.d_time.download(np.float64, N, stream=self.stream)
+            grid = _capi.overfit_grid(_capi.overfit_default_grid(t0 if keep_idx is None else t0[keep_idx]))
+        nbytes, _rounds = _capi.overfit_scratch_bytes(B, n, grid[2], n_samples, max_scratch_bytes)
+        d_keep = None
+        if keep_idx is not None:
+            d_keep, k = _upload(h, keep_idx, self.stream, np.int32)
+            self._keep.append(k)
+        # (the scratch block goes back to the free list when this call returns: work on one handle is stream-ordered)
+        d_scr, d_metric = DeviceBuffer(h, nbytes), DeviceBuffer(h, B * 8)
+        _capi._check(_capi._lib.lk_overfit_metric_batch_dev(
+            h._h, B, N, _vp(self.d_time.ptr), _vp(original.d_flux.ptr), _vp(self.d_flux.ptr), _vp(self.d_flux_err.ptr), n,
+            _vp(d_keep.ptr if d_keep is not None else None), grid[0], grid[1], grid[2], int(n_samples), int(seed), int(first_target),
+            int(stream_id), _vp(d_scr.ptr), nbytes, _vp(d_metric.ptr), st))
+        self._keep += [d_keep, original]
+        if not to_host:
+            return d_metric
+        return d_metric.download(np.float64, B, stream=self.stream)
+
+    def cbv_goodness_scan(self, cbvs, alphas, neighbors=None, cbv_indices=np.arange(1, 9), cadence_mask=None, n_samples=1, seed=0,
+                          frequency=None, first_target=0, ext_dm=None, sigma=5, niters=5, max_scratch_bytes=None):
+        """Both goodness metrics of ``cbv_correct`` over a list of ridge penalties, for the whole batch (what
+        ``correctors.CBVCorrector.goodness_scan`` does for one target, here for a whole channel): for each
+        ``alphas[a]`` the batch is corrected (``cbv_correct(cbvs, cbv_indices, alpha, ext_dm, cadence_mask, sigma, niters)``),
+        scored with ``over_fitting_metric(self, ..., stream_id=a)`` and, when ``neighbors`` (int (B, M), see
+        ``under_fitting_metric``) is given, with ``under_fitting_metric``.  ``cadence_mask``: bool (N,), shared by the fit and
+        both metrics.  A plain loop of resident calls; 8 or 16 bytes per target and penalty come back.  Returns
+        dict(alpha[A], over_fitting[A, B], under_fitting[A, B] or None)."""
+        alphas = np.atleast_1d(np.asarray(alphas, dtype=np.float64))
+        B = len(self)
+        N, keep_idx, _n, grid = self._overfit_checks(self, n_samples, cadence_mask, frequency, seed, first_target, 0)
+        if grid is None:      # the default grid depends on the times alone: taken once for the whole scan
+            t0 = self.d_time.download(np.float64, N, stream=self.stream)
+            frequency = _capi.overfit_default_grid(t0 if keep_idx is None else t0[keep_idx])
+        fit_mask = None if cadence_mask is None else np.broadcast_to(np.asarray(cadence_mask, dtype=bool), (B, N))
+        over = np.empty((len(alphas), B))
+        under = np.empty((len(alphas), B)) if neighbors is not None else None
+        for a, alpha in enumerate(alphas):
+            cor = self.cbv_correct(cbvs, cbv_indices=cbv_indices, alpha=float(alpha), ext_dm=ext_dm, cadence_mask=fit_mask, sigma=sigma,
+                                   niters=niters)[0]
+            d_over = cor.over_fitting_metric(self, frequency=frequency, n_samples=n_samples, cadence_mask=cadence_mask, seed=seed,
+                                             first_target=first_target, stream_id=a, to_host=False,
+                                             max_scratch_bytes=max_scratch_bytes)
+            d_under = cor.under_fitting_metric(neighbors, cadence_mask=cadence_mask, to_host=False) if neighbors is not None else None
+            over[a] = d_over.download(np.float64, B, stream=self.stream)
+            if d_under is not None:
+                under[a] = d_under.download(np.float64, B, stream=self.stream)
+            cor.synchronize()
+        return dict(alpha=alphas, over_fitting=over, under_fitting=under)
+
     # ---------------------------------------------------------------- Lomb-Scargle
     def _ls_ready(self):
         """The batch the periodogram kernels see: NaN-flux cadences dropped (LombScarglePeriodogram.from_lightcurve,

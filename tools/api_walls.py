@@ -19,7 +19,15 @@ cadences with `LK_WALLS_M` (default 50) neighbours each, two ways in ONE process
 R the resident call (`cbv_correct(...)[0].under_fitting_metric(neighbors, cadence_mask)`: 8 bytes per target come back), R' the
 same with `to_host=False` plus a synchronise, H the host route (download the corrected flux, then `underfit_metric_neighbors` per
 target on 16 threads).  Every timed region ends in a synchronise.  `underfit_trace`: only resident calls — the run to put
-under `rocprofv3 --kernel-trace --stats` for the two kernels' times."""
+under `rocprofv3 --kernel-trace --stats` for the two kernels' times.
+
+`overfit`: the over-fitting goodness metric of `LK_WALLS_B` (default 1000) cotrended targets x `LK_WALLS_N` (default 20000)
+cadences on the default grid with `LK_WALLS_SAMPLES` (default 10) noise samples, in ONE process, alternating, `LK_WALLS_REPS`
+(default 3) times: R the resident call (`cbv_correct(...)[0].over_fitting_metric(batch)`), R' the same with `to_host=False` plus
+a synchronise, H the host route (download both batches, then `overfit_metric_lombscargle` per target; its noise is numpy's, so H
+and R agree in distribution, not in value; the loop is sequential: every one of its calls launches on the one handle, which serves
+one call at a time, so the 16 threads of `underfit`'s host route, which is host arithmetic only, do not apply).  `overfit_trace`: only resident calls — the run to put under
+`rocprofv3 --kernel-trace --stats`, in a run of its own, for the split between the LS passes and the metric's own kernels."""
 import cProfile
 import io
 import os
@@ -221,6 +229,55 @@ def underfit(which):
     sys.stdout.flush()
 
 
+def overfit(which):
+    from lightkurve_amd import _capi
+    from lightkurve_amd.correctors import metrics
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    from lightkurve_amd.lightcurve import LightCurve
+    B, N, ns = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000"), ("LK_WALLS_SAMPLES", "10")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "3"))
+    rng = np.random.default_rng(7)
+    t = np.linspace(0, 27, N)
+    S = np.column_stack([np.sin(2 * np.pi * t / 13.7), (t / 27 - 0.5) ** 2])
+    y = 1000.0 * rng.uniform(0.5, 2, (B, 1)) * (1 + rng.normal(0, 0.01, (B, 2)) @ S.T + 1e-3 * rng.normal(0, 1, (B, N)))
+    raw = DeviceLightCurveBatch.from_arrays(np.tile(t, B), y.reshape(-1), (1e-3 * y).reshape(-1), np.arange(B + 1) * N).remove_nans()
+    cor = raw.cbv_correct(S, cbv_indices=[1, 2])[0]
+    cor.synchronize()
+    sync = _capi.Handle.get(0).synchronize
+    M = len(_capi.overfit_default_grid(t))
+    nbytes, per_round = _capi.overfit_scratch_bytes(B, N, M, ns)
+    model = "%d frequencies, scratch %.2f GB in rounds of %d samples, %d LS passes of %d rows" % (M, nbytes / 1e9, per_round, 2 + ns, B)
+    if "overfit_trace" in which:
+        calls = 1 + max(reps, 3)
+        for _ in range(calls):
+            cor.over_fitting_metric(raw, n_samples=ns, to_host=False)
+        sync()
+        print("overfit_trace: %d resident over_fitting_metric calls on %d x %d, n_samples = %d; per call %s" % (calls, B, N, ns, model))
+        return
+
+    def host_route():
+        f0, f1, e1 = raw.flux_host().reshape(B, N), cor.flux_host().reshape(B, N), cor.flux_err_host().reshape(B, N)
+        return np.array([metrics.overfit_metric_lombscargle(LightCurve(t, f0[b], e1[b]), LightCurve(t, f1[b], e1[b]), n_samples=ns)
+                         for b in range(B)])
+
+    got = cor.over_fitting_metric(raw, n_samples=ns)                       # warm-up of both routes
+    cor.over_fitting_metric(raw, n_samples=ns, to_host=False)
+    sync()
+    ref = host_route()
+    R, R2, H = [], [], []
+    for _ in range(reps):
+        R.append(timed(lambda: cor.over_fitting_metric(raw, n_samples=ns))[0])            # (the download synchronises)
+        R2.append(timed(lambda: (cor.over_fitting_metric(raw, n_samples=ns, to_host=False), sync()))[0])
+        H.append(timed(host_route)[0])
+    print("over-fitting metric, %d cotrended targets x %d cadences, n_samples = %d; %s" % (B, N, ns, model))
+    print("  R  corrected.over_fitting_metric(batch) -> metric[B] on the host        %s" % spread(R))
+    print("  R' the same, to_host=False + synchronise                                %s" % spread(R2))
+    print("  H  download both + overfit_metric_lombscargle per target, sequential    %s" % spread(H))
+    print("  median metric R %.4f, H %.4f (different noise: equal in distribution); max |R - H| = %.3e; H / R = %.0f"
+          % (float(np.median(got)), float(np.median(ref)), float(np.max(np.abs(got - ref))), np.median(H) / np.median(R)))
+    sys.stdout.flush()
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -232,6 +289,8 @@ def main():
         pld_ragged()
     if {"underfit", "underfit_trace"} & set(which):
         underfit(which)
+    if {"overfit", "overfit_trace"} & set(which):
+        overfit(which)
     if "flatten" in which:
         lcs = []
         for i in range(1000):
