@@ -378,7 +378,7 @@ constexpr int FLAT_CUT_CAP = 384;
 
 __global__ __launch_bounds__(FLAT_NT, FLAT_DTSEG_WAVES) void flat_dtseg_kernel(const int64_t *__restrict__ n_off, double break_tol,
                                                              char *__restrict__ scratch, const int64_t *__restrict__ scratch_off,
-                                                             FlatState *__restrict__ state, int FIR_LDS, int it, int near_on) {
+                                                             FlatState *__restrict__ state, int FIR_LDS, int it) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long dyn_lds[];
     __shared__ int cut_n;
     __shared__ int cut_i[FLAT_CUT_CAP];
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(FLAT_NT, FLAT_DTSEG_WAVES) void flat_dtseg_kernel(c
         if (tid == 0) cut_n = 0;
         __syncthreads();
         bool near_ok = false;
-        if (it > 0 && near_on && st.dspacing > 0.0 && st.nm_prev >= nm) {
+        if (it > 0 && st.dspacing > 0.0 && st.nm_prev >= nm) {  // guided by the previous iteration's median
             const double width = st.dspacing * (3.0 * (double)(st.nm_prev - nm) + 96.0);
             dmed = block_median_near(nm - 1, cnt, dval, dkeep, st.dmed_prev, width, sh, fir, FIR_LDS, &near_ok, note);
             have_cuts = near_ok && bound_ok;
@@ -1068,11 +1068,9 @@ int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
     double *d_c = des->d_c, *d_e = des->d_e;
     // moment form of the Savitzky-Golay interior for long windows (see the kernel)
     constexpr int quad_min = 201;
-    const bool use_quad = quad_min > 0 && window >= quad_min && des->quad_b != 0.0;
+    const bool use_quad = window >= quad_min && des->quad_b != 0.0;
     const double quad_a = use_quad ? des->quad_a : 0.0, quad_b = use_quad ? des->quad_b : 0.0;
-    constexpr bool edge_moments = true;
-    const double *d_minv = edge_moments ? des->d_minv : nullptr;
-    constexpr int near_on = 1;  // guided dt median in iterations >= 1
+    const double *d_minv = des->d_minv;
     std::vector<int64_t> soff((size_t)B + 1, 0);
     for (int b = 0; b < B; ++b) {
         const int64_t n = n_off_host[b + 1] - n_off_host[b];
@@ -1146,7 +1144,7 @@ int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
     for (int it = 0; it < niters; ++it) {
         hipLaunchKernelGGL(flat_compact_kernel, dim3(B), dim3(FLAT_NT), 0, stream, t, flux, d_off, d_s, d_soff, d_state, trend, it);
         hipLaunchKernelGGL(flat_dtseg_kernel, dim3(B), dim3(FLAT_NT), lds_pick, stream, d_off, break_tol, d_s, d_soff, d_state,
-                           fir_pick, it, near_on);
+                           fir_pick, it);
         if (quad_kernel)
             hipLaunchKernelGGL(flat_trend_kernel<true>, dim3(B, trend_T), dim3(FLAT_NT), lds_trend, stream, d_off, window, polyorder,
                                break_tol, d_c, d_e, d_s, d_soff, d_state, fir_trend, quad_a, quad_b, d_minv, d_rs);

@@ -14,11 +14,10 @@
 // projection generates them on the fly (pld_project_products_kernel).  Top-k eigenpairs of C by blocked subspace
 // iteration with Rayleigh-Ritz.  Every dense step of the
 // iteration is MFMA work in one workgroup per matrix: C Q (32-byte row loads two steps ahead of the matrix cores), the
-// skinny products Q^T Z and X M, Ritz vectors + residual in one pass; three products with C per Ritz step (eight for the
-// mid-size product blocks, whose flat spectrum tolerates it), column-scaled Cholesky-QR between steps and for the random
-// start (SVQB as the fallback; small l x l eigenproblems by parallel cyclic Jacobi in LDS).  Pixel blocks of at
-// most 138 columns whose iteration does not converge in eight steps fall through to a direct Jacobi on C held in LDS;
-// for P <= 64 the Jacobi always runs on C itself.
+// skinny products Q^T Z and X M, Ritz vectors + residual in one pass; three products with C per Ritz step,
+// column-scaled Cholesky-QR between steps and for the random start (SVQB as the fallback; small l x l eigenproblems by
+// parallel cyclic Jacobi in LDS).  Blocks of 3 to 138 columns never iterate: their Gram matrix fits LDS and the direct
+// tridiagonal solver (pld_tridiag_eig_kernel) takes them; one- and two-column blocks get the Jacobi on C itself.
 // Then U = A V diag(lambda)^-1/2 (pld_project_kernel, MFMA) written straight into X.  The reference uses fbpca
 // (randomised range finder, 10 power iterations, 2 oversampling columns, unseeded RNG => not reproducible); the oracle
 // uses an exact SVD; the iteration here converges the residual ||C r - theta r|| to 1e-10 theta_max, i.e. to ten digits
@@ -38,7 +37,7 @@
 namespace lk {
 
 constexpr int PLD_LMAX = 64;  // largest small eigenproblem kept in LDS
-constexpr int PLD_DIRECT_MAX = 138;  // largest P whose Gram matrix fits LDS for the direct Jacobi (512 threads)
+constexpr int PLD_DIRECT_MAX = 138;  // largest P the direct tridiagonal solver takes: its packed triangle and scratch fit LDS (td_lds_bytes)
 // Stop of the subspace iteration: ||C r - theta r|| <= tol * theta_max * sqrt(k).  PLD design matrices: 1e-7 — the residual falls
 // 4.8 -> 1.5e-2 -> 1.5e-5 -> 8.5e-9 -> 3.2e-12 per Rayleigh-Ritz step on the 816-column blocks, and the corrected flux / the outlier
 // masks of every reference golden are UNCHANGED for any threshold down to 1e-6 (profiles/r05_pld_tol_sweep.txt: 1.5e-8 / 4.7e-8 /
@@ -56,6 +55,8 @@ constexpr int PLD_QS = PLD_LMAX + 2;  // LDS row stride of that stage (doubles)
 // row stride (floats) of the float32 stage of eig_cq32 for a basis of NA 16-column tiles: 16 NA + 16, so the four k-rows of an
 // MFMA operand read start 16 banks apart and the 64 lanes hit 64 different banks
 __host__ __device__ constexpr int pld_qs32(int na) { return 16 * na + 16; }
+// rows per stage of eig_cq32: its float32 stage fills the LDS region of eig_cq's PLD_KC x PLD_QS doubles; a multiple of 24 = 8 PF
+__host__ __device__ constexpr int pld_kc32(int na) { return (PLD_KC * PLD_QS * 8) / (pld_qs32(na) * 4) / 24 * 24; }
 // Relative residual above which the Rayleigh-Ritz product itself reads the float32 copy of C on the float32 matrix cores (round 6):
 // a step that starts three decades above the float32 noise floor cannot pass the 1e-7 stop, so its Ritz pairs only have to
 // steer the filter; convergence is only ever declared from a float64 product.
@@ -792,8 +793,6 @@ __global__ __launch_bounds__(256) void pld_spline_kernel(const double *__restric
 // ------------------------------------------------------------------------------------------------ small eigenproblems
 // Parallel cyclic Jacobi on a symmetric n x n matrix M (LDS, leading dim ld, n even); W <- eigenvectors (columns),
 // diag(M) <- eigenvalues.  All threads of the workgroup participate.  rot: n/2 x 4 doubles of LDS scratch.
-// Wt != nullptr: the eigenvectors are kept TRANSPOSED in global memory (Wt[p * n + i] = W[i][p], n x n) instead of in W
-// (LDS) — rows p and q of Wt are what a rotation touches, so the accesses stay coalesced.
 // M, W, rot, shred are OFFSETS (in doubles) into the workgroup's dynamic LDS: a non-inlined function that took them as
 // plain pointers would address LDS through flat loads and stores.
 __device__ __forceinline__ double jac_rsq(double x) {  // 1 / sqrt(x), x > 0 and normal
@@ -807,15 +806,11 @@ __device__ __forceinline__ double jac_rcp(double x) {  // 1 / x, x > 0 and norma
     return fma(y, fma(-x, y, 1.0), y);
 }
 
-template <bool WT>
-static __device__ __noinline__ void jacobi_eig_lds(int oM, int oW, int n, int ld, int orot, int oshred, double *Wt = nullptr) {
+static __device__ __noinline__ void jacobi_eig_lds(int oM, int oW, int n, int ld, int orot, int oshred) {
     extern __shared__ __attribute__((aligned(16))) double lds_dyn[];
     double *M = lds_dyn + oM, *W = lds_dyn + oW, *rot = lds_dyn + orot, *shred = lds_dyn + oshred;
     const int tid = threadIdx.x, nt = blockDim.x;
-    if (WT)
-        for (int e = tid; e < n * n; e += nt) Wt[e] = (e / n == e % n) ? 1.0 : 0.0;
-    else
-        for (int e = tid; e < n * n; e += nt) W[(e / n) * ld + (e % n)] = (e / n == e % n) ? 1.0 : 0.0;
+    for (int e = tid; e < n * n; e += nt) W[(e / n) * ld + (e % n)] = (e / n == e % n) ? 1.0 : 0.0;
     __syncthreads();
     const int half = n >> 1;
     // e / n by one multiplication (the loops below split ~1000 indices per round; the compiler's
@@ -902,17 +897,10 @@ static __device__ __noinline__ void jacobi_eig_lds(int oM, int oW, int n, int ld
                 const int pr = divn(e), i = e - pr * n;
                 const int p = roti[2 * pr], q = roti[2 * pr + 1];
                 const double c = rotcs[2 * pr], s = rotcs[2 * pr + 1];
-                if (WT) {
-                    const double wp = Wt[(size_t)p * n + i], wq = Wt[(size_t)q * n + i];
-                    Wt[(size_t)p * n + i] = c * wp - s * wq;
-                    Wt[(size_t)q * n + i] = s * wp + c * wq;
-                } else {
-                    const double wp = W[i * ld + p], wq = W[i * ld + q];
-                    W[i * ld + p] = c * wp - s * wq;
-                    W[i * ld + q] = s * wp + c * wq;
-                }
+                const double wp = W[i * ld + p], wq = W[i * ld + q];
+                W[i * ld + p] = c * wp - s * wq;
+                W[i * ld + q] = s * wp + c * wq;
             }
-            if (WT) __threadfence_block();
             __syncthreads();
         }
     }
@@ -949,8 +937,6 @@ struct EigCtx {
     double *Gb;                         // this matrix (global, leading dimension ldg)
     const float *G32b;                  // its float32 copy for the filter products of the early steps (or nullptr)
     int ldg, P, k, l, ld;
-    int kc;                             // rows of the basis per LDS stage of eig_cq (a multiple of 8)
-    int kc32;                           // rows per stage of eig_cq32 (float32 stage in the same LDS region; a multiple of 24 = 8 PF)
 };
 #define LK_EIG_LDS extern __shared__ __attribute__((aligned(16))) double lds_dyn[]
 // likewise the global operands: as plain pointer arguments they would be read with flat loads
@@ -1108,7 +1094,7 @@ static __device__ __noinline__ void eig_cq_pass(EigCtx c, const double *src_, do
     double *qstage = lds_dyn + c.qstage;
     typedef double bvec __attribute__((ext_vector_type(4)));  // (NT of its components are used)
     typedef __attribute__((address_space(1))) const float cgfloat;
-    const int nsteps = (P + 3) >> 2, KC = c.kc;
+    const int nsteps = (P + 3) >> 2, KC = PLD_KC;
     const int col_w = (tile0 + wave * NT) << 4;  // first column of this wave
     const bool active = col_w < P;
     const int n0 = col_w + NT * lr;
@@ -1259,7 +1245,7 @@ static __device__ __noinline__ void eig_cq32_pass(EigCtx c, const double *src_, 
     LK_EIG_LDS;
     float *qs = reinterpret_cast<float *>(lds_dyn + c.qstage);
     typedef __attribute__((address_space(1))) const float cgfloat;
-    const int nsteps = (P + 3) >> 2, KC = c.kc32;
+    const int nsteps = (P + 3) >> 2, KC = pld_kc32(NA);
     const int col_w = (tile0 + wave * NT) << 4;  // first column of this wave
     const bool active = col_w < P;
     const int n0 = col_w + NT * lr;
@@ -1329,7 +1315,7 @@ static __device__ __noinline__ void eig_cq32_pass(EigCtx c, const double *src_, 
         }
         __syncthreads();
         const int s_lo = k0 >> 2, s_hi = min(nsteps, (k0 + KC) >> 2);
-        for (int st = s_lo; st < s_hi; st += 2 * PF) {  // kc32 is a multiple of 8 PF: the 2 PF steps of a trip stay inside the stage
+        for (int st = s_lo; st < s_hi; st += 2 * PF) {  // pld_kc32 is a multiple of 8 PF: the 2 PF steps of a trip stay inside the stage
 #pragma unroll
             for (int u = 0; u < PF; ++u) {
                 qb[u] = load_b(st + PF + u);
@@ -1418,7 +1404,7 @@ static __device__ __noinline__ void eig_svqb(EigCtx c, double *Yv) {
         __syncthreads();
         for (int e = tid; e < l * l; e += nt) T[(e / l) * ld + (e % l)] = W[(e / l) * ld + (e % l)];
         __syncthreads();
-        jacobi_eig_lds<false>(c.T, c.W, l, ld, c.rot, c.shred);
+        jacobi_eig_lds(c.T, c.W, l, ld, c.rot, c.shred);
         double mx = 0.0;
         for (int a = 0; a < l; ++a) mx = fmax(mx, T[a * ld + a]);
         if (tid < l) {
@@ -1525,11 +1511,12 @@ static __device__ __noinline__ bool eig_cholqr(EigCtx c, const double *Yin, doub
 // scratch per matrix: 4 * P * l doubles (Q, Z, R, Y).  NA = number of 16-column tiles of the basis (l <= 16 NA): a
 // compile-time constant, because with a run-time bound the compiler keeps all 4 x 4 accumulator tiles of the product
 // with C (128 VGPRs = the whole budget of a 1024-thread workgroup) and spills around every MFMA.
+constexpr int PLD_NPOW = 3;      // products with C between two Rayleigh-Ritz steps: the degree of the Chebyshev filter (or C^3)
+constexpr int PLD_MAX_IT = 400;  // cap on the Rayleigh-Ritz steps
 template <int NA>
-__global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__ G, int ldg, int P, int k, int l, int npow,
+__global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__ G, int ldg, int P, int k, int l,
                                                              double *__restrict__ scratch, double *__restrict__ V,
                                                              double *__restrict__ lam, long long *__restrict__ iters_out,
-                                                             int max_it, int *__restrict__ status, int cheb_on, int kc,
                                                              int mirror, double tol, const float *__restrict__ G32 = nullptr,
                                                              const int *__restrict__ pcount = nullptr) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -1538,7 +1525,7 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
     double *Vb = V + (size_t)b * P * k, *lamb = lam + (size_t)b * k;
     const size_t scr_stride = (size_t)4 * P * l;   // (of the subspace iteration: laid out for the batch's P)
     // ragged batches: this matrix's own leading block (see pld_tridiag_eig_kernel); a block no wider than the basis takes the
-    // direct Jacobi below, whatever route the batch's widest block chose
+    // direct Jacobi below, though the batch's widest block chose the subspace iteration
     if (pcount) {
         const int Pown = min(max(pcount[b], 1), P);
         for (int e = Pown * k + tid; e < P * k; e += nt) Vb[e] = 0.0;
@@ -1553,42 +1540,6 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
     double *vec = lds + ovec;                  // 2 * l  (norms / theta)
     int *order = reinterpret_cast<int *>(lds + oorder);  // l ints; then qstage: PLD_KC x PLD_QS (subspace path only)
 
-    if (P <= l && l > PLD_LMAX) {
-        if (status && status[b]) return;  // the short subspace pass already converged this matrix
-        // ---- direct, mid-size (PLD_LMAX < P <= PLD_DIRECT_MAX): Jacobi on C itself with C in LDS (l x (l + 1) doubles
-        // fill it) and the eigenvectors transposed in global scratch.  A few ms per matrix, against tens of Rayleigh-
-        // Ritz steps of the subspace iteration when the spectrum of a 2nd-order product block decays slowly.
-        double *Wt = scratch + (size_t)b * l * l;
-        const int orot2 = l * ld, oshred2 = orot2 + 2 * l;
-        double *vec2 = lds + oshred2 + nt;
-        int *order2 = reinterpret_cast<int *>(vec2 + 2 * l);
-        for (int e = tid; e < l * l; e += nt) {
-            const int i = e / l, j = e % l;
-            T[i * ld + j] = (i < P && j < P) ? gsym(Gb, ldg, i, j) : 0.0;
-        }
-        __syncthreads();
-        jacobi_eig_lds<true>(oT, oT, l, ld, orot2, oshred2, Wt);
-        if (tid < l && tid >= P) T[tid * ld + tid] = -1.0;  // pad eigenvalue sorts last
-        __syncthreads();
-        // order by eigenvalue, l may exceed 64: rank by counting, one thread per entry
-        for (int a = tid; a < l; a += nt) {
-            const double v = T[a * ld + a];
-            int rank = 0;
-            for (int j = 0; j < l; ++j) {
-                const double u = T[j * ld + j];
-                rank += (u > v || (u == v && j < a)) ? 1 : 0;
-            }
-            order2[rank] = a;
-        }
-        __syncthreads();
-        for (int e = tid; e < P * k; e += nt) {
-            const int a = e / P, i = e - a * P;  // i fastest: rows of Wt are read contiguously
-            Vb[(size_t)i * k + a] = Wt[(size_t)order2[a] * l + i];
-        }
-        if (tid < k) lamb[tid] = T[order2[tid] * ld + order2[tid]];
-        if (tid == 0 && iters_out) iters_out[(size_t)b * 8] = 0;
-        return;
-    }
     if (P <= l) {
         // ---- direct: Jacobi on C itself (l = P rounded up to even; the pad row/col is zero)
         for (int e = tid; e < l * l; e += nt) {
@@ -1596,7 +1547,7 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
             T[i * ld + j] = (i < P && j < P) ? gsym(Gb, ldg, i, j) : 0.0;
         }
         __syncthreads();
-        jacobi_eig_lds<false>(oT, oW, l, ld, orot, oshred);
+        jacobi_eig_lds(oT, oW, l, ld, orot, oshred);
         if (tid < l && tid >= P) T[tid * ld + tid] = -1.0;  // pad eigenvalue sorts last
         __syncthreads();
         sort_desc_lds(T, l, ld, order);
@@ -1606,14 +1557,12 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
         }
         if (tid < k) lamb[tid] = T[order[tid] * ld + order[tid]];
         if (tid == 0 && iters_out) iters_out[(size_t)b * 8] = 0;
-        if (tid == 0 && status) status[b] = 1;   // (a ragged batch's narrow block in the two-pass form: solved here)
         return;
     }
 
     // ---- subspace iteration with Rayleigh-Ritz steps
     double *Q = scratch + b * scr_stride, *Z = Q + (size_t)P * l, *R = Z + (size_t)P * l, *Y = R + (size_t)P * l;
-    const int kc32 = (int)(((size_t)kc * PLD_QS * 8) / ((size_t)pld_qs32(NA) * 4)) / 24 * 24;  // the float32 stage fills the same LDS region
-    const EigCtx ctx{oT, oW, orot, oshred, ovec, oqstage, oorder, Gb, G32 ? G32 + (size_t)b * ldg * ldg : nullptr, ldg, P, k, l, ld, kc, kc32};
+    const EigCtx ctx{oT, oW, orot, oshred, ovec, oqstage, oorder, Gb, G32 ? G32 + (size_t)b * ldg * ldg : nullptr, ldg, P, k, l, ld};
     long long tprof[7] = {0, 0, 0, 0, 0, 0, 0}, tlast = iters_out ? (long long)wall_clock64() : 0;
     auto lap = [&](int slot) {  // debug (LK_PLD_ITERS=1): per-phase 100 MHz ticks
         if (iters_out) {
@@ -1642,10 +1591,9 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
     if (!eig_cholqr<NA>(ctx, Q, Q)) eig_svqb<NA>(ctx, Q);
     lap(0);
     int it = 0;
-    bool converged = false;
     double *theta = vec + l;  // sorted Ritz values of the current step
     bool rr32 = ctx.G32b != nullptr;  // this step's Rayleigh-Ritz product on the float32 matrix cores (PLD_RR32_RES)
-    for (; it < max_it; ++it) {
+    for (; it < PLD_MAX_IT; ++it) {
         if (rr32)
             eig_cq32<NA>(ctx, Q, Z);  // Z = C32 Q
         else
@@ -1658,7 +1606,7 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
         }
         __syncthreads();
         lap(2);
-        jacobi_eig_lds<false>(oT, oW, l, ld, orot, oshred);
+        jacobi_eig_lds(oT, oW, l, ld, orot, oshred);
         sort_desc_lds(T, l, ld, order);
         lap(3);
         // R = Q W (Ritz vectors, sorted by Ritz value), Y = Z W = C R, and the residual || C r - theta r || of the k
@@ -1670,31 +1618,27 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
             T[a * ld + c] = W[a * ld + order[c]];
         }
         __syncthreads();
-        const double th0 = fabs(theta[0]), th_k = theta[k - 1], th_cut = theta[l - 1];
+        const double th0 = fabs(theta[0]), th_cut = theta[l - 1];
         // (the filter decision needs the Ritz values only, so it is taken BEFORE the pass that writes R and Y: with the Chebyshev
         // filter that pass stores Y as the recurrence's first term X1 = (C R - c R) / e straight away — one sweep over two P x l
         // arrays less per step; unused if this step converges)
-        const bool cheb = npow >= 2 && th_cut > 0.0 &&
-                          (((cheb_on & 1) && th_k < 1.5 * th_cut && th0 < 30.0 * th_cut) || (cheb_on & 2));  // bit 1 (LK_PLD_CHEB=2/3): always
+        const bool cheb = th_cut > 0.0;
         const double cc = 0.5 * th_cut, ie = cheb ? 1.0 / cc : 0.0;
         const double part = eig_xm<NA, true>(ctx, Q, R, Z, Y, oT, ovec + l, cc, ie);
         const double res = sqrt(block_sum_dyn(part, shred));
         if (tid < k) lamb[tid] = theta[tid];
         __syncthreads();
         lap(4);
-        if (!rr32 && res <= tol * th0 * sqrt((double)k)) {  // (only a float64 product can declare convergence)
-            converged = true;
-            break;
-        }
+        if (!rr32 && res <= tol * th0 * sqrt((double)k)) break;  // (only a float64 product can declare convergence)
         rr32 = ctx.G32b != nullptr && res > PLD_RR32_RES * th0;
-        // next basis: orthonormalised p(C) R with npow - 1 more products between two Rayleigh-Ritz steps.
-        //  * flat spectrum (the wanted Ritz values sit close to the first unwanted one: product blocks): p = the Chebyshev
-        //    polynomial of degree npow that is bounded by 1 on the unwanted interval [0, theta_cut] and grows fastest
-        //    outside it — for theta_k / theta_cut = 1.2 a degree-3 step damps the unwanted part 6.8x instead of the
-        //    1.7x of C^3, so the slowly converging blocks need a fraction of the Rayleigh-Ritz steps;
-        //  * steep spectrum: the same filter (option bit 1, default) — the factors between the columns differ by many
-        //    orders of magnitude, but the Cholesky-QR scales the columns to unit length first, and measured it needs 5.0
-        //    steps where p = C^npow (option bit 1 off) needs 7.2.
+        // next basis: orthonormalised p(C) R with PLD_NPOW - 1 more products between two Rayleigh-Ritz steps.
+        //  * p = the Chebyshev polynomial of degree PLD_NPOW that is bounded by 1 on the unwanted interval [0, theta_cut] and
+        //    grows fastest outside it — for theta_k / theta_cut = 1.2 (flat spectrum: product blocks) a degree-3 step damps
+        //    the unwanted part 6.8x instead of the 1.7x of C^3.  Steep spectra take the same filter: the factors between the
+        //    columns differ by many orders of magnitude, but the Cholesky-QR scales the columns to unit length first, and
+        //    measured on the 816-column blocks it needs 5.0 Rayleigh-Ritz steps where C^3 needs 7.2;
+        //  * p = C^PLD_NPOW when the smallest Ritz value of the basis is not positive (rank-deficient blocks, whose basis
+        //    reaches into the null space): there is no interval [0, theta_cut] to filter on.
         double *src = Y, *dst = Z;
         if (cheb) {
             // x = (C - c) / e with c = e = theta_cut / 2:  X0 = R, X1 = (C R - c R) / e (stored by eig_xm above),
@@ -1705,7 +1649,7 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
             // Ritz values, the residual and the convergence test come from the float64 product of the Rayleigh-Ritz step,
             // and a float32 C limits the reachable residual to ~1e-7 theta_max, so the last steps filter in float64.
             const bool f32 = ctx.G32b != nullptr && res > PLD_F32_RES * th0;
-            for (int pw = 1; pw < npow; ++pw) {
+            for (int pw = 1; pw < PLD_NPOW; ++pw) {
                 double *nxt = free1;
                 const EigEpi ep{2.0 * ie, 2.0 * ie * cc, 1.0, prev};
                 if (f32 && res > PLD_RR32_RES * th0)  // far from the stop: float32 matrix cores (noise floor ~2e-6 of the subspace)
@@ -1721,7 +1665,7 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
             }
             src = cur;
         } else {
-            for (int pw = 1; pw < npow; ++pw) {
+            for (int pw = 1; pw < PLD_NPOW; ++pw) {
                 eig_cq<NA>(ctx, src, dst);
                 double *t2 = src;
                 src = dst;
@@ -1743,7 +1687,6 @@ __global__ __launch_bounds__(1024) void pld_topk_eig_kernel(double *__restrict__
         iters_out[(size_t)b * 8] = it;
         for (int s2 = 0; s2 < 7; ++s2) iters_out[(size_t)b * 8 + 1 + s2] = tprof[s2];
     }
-    if (tid == 0 && status) status[b] = converged ? 1 : 0;
 }
 
 // U = A V diag(lam)^-1/2 into X[:, col0 : col0 + k] on the fp64 matrix cores.  One WAVE = 16 rows of A against all of V
@@ -1910,7 +1853,7 @@ __global__ __launch_bounds__(256) void pld_project_f32_kernel(const float *__res
 // spectra, flat product-block spectra, repeated eigenvalues).  One 1024-thread workgroup per matrix (LDS: 76 KB triangle +
 // 18 KB vectors + 36 KB scratch of the twisted factorisations).
 constexpr int TD_NT = 1024, TD_LANES = 16;  // eigenvectors factorised at a time (LDS scratch 2 P doubles each); 8 where that lets two
-                                            // workgroups share a CU (td_plan)
+                                            // workgroups share a CU (the launcher's choice of tdl in eig_topk)
 
 // Wave-wide sum in every lane without the LDS crossbar: four DPP levels inside each row of 16 lanes (quad swaps, half-row and
 // row mirrors), then the four row sums through v_readlane.  ~10x shorter than six dependent ds_bpermute round trips — the
@@ -2405,25 +2348,84 @@ __global__ __launch_bounds__(TD_NT, 8) void pld_tridiag_eig_kernel(const double 
 }
 
 // ------------------------------------------------------------------------------------------------ launcher
+// LDS of the direct solver: packed triangle + six P-vectors + eigenvalues and vector norms + the scratch of `tdl` twisted
+// factorisations at a time (the eigenvectors themselves live in V)
+constexpr size_t td_lds_bytes(int P, int k, int tdl) {
+    return ((size_t)((((P * (P + 1)) / 2) + 1) & ~1) + 6 * (size_t)P + 2 * (size_t)((k + 1) & ~1) + (size_t)tdl * 2 * P) * 8 + 16;
+}
+// the formula grows with P, k and tdl, and k <= P: every shape the direct solver is given fits the 160 KB of a CU
+static_assert(td_lds_bytes(PLD_DIRECT_MAX, PLD_DIRECT_MAX, TD_LANES) <= 160 * 1024, "PLD_DIRECT_MAX: the direct solver's LDS");
+
+#ifdef LK_PLD_DEBUG
+// `make DEBUG=1`, LK_PLD_ITERS=1: the direct solver's per-phase clocks of matrix 0 and the timeline of the launch
+static int td_debug_report(const unsigned long long *d_clk, int B, int P, int k, hipStream_t stream) {
+    unsigned long long hc[8];
+    LK_HIP_CHECK(hipMemcpyAsync(hc, d_clk, 48, hipMemcpyDeviceToHost, stream));
+    LK_HIP_CHECK(hipStreamSynchronize(stream));
+    fprintf(stderr, "[pld tridiag] P=%d k=%d per matrix us: tridiagonalise %.0f | eigenvalues %.0f | twisted factorisation %.0f | "
+                    "Gram-Schmidt %.0f | back-transform %.0f\n", P, k, (hc[1] - hc[0]) * 0.01, (hc[2] - hc[1]) * 0.01,
+            (hc[3] - hc[2]) * 0.01, (hc[4] - hc[3]) * 0.01, (hc[5] - hc[4]) * 0.01);
+    // the launch as a whole: when each workgroup started and ended, and where it ran
+    std::vector<unsigned long long> tl(4 * (size_t)B);
+    LK_HIP_CHECK(hipMemcpyAsync(tl.data(), d_clk + 8, 32 * (size_t)B, hipMemcpyDeviceToHost, stream));
+    LK_HIP_CHECK(hipStreamSynchronize(stream));
+    unsigned long long t0 = ~0ull, t1 = 0;
+    for (int i = 0; i < B; ++i) {
+        t0 = std::min(t0, tl[4 * i]);
+        t1 = std::max(t1, tl[4 * i + 1]);
+    }
+    std::vector<double> st(B), du(B);
+    std::map<unsigned, int> per_cu;
+    for (int i = 0; i < B; ++i) {
+        st[i] = (tl[4 * i] - t0) * 0.01;
+        du[i] = (tl[4 * i + 1] - tl[4 * i]) * 0.01;
+        const unsigned hw = (unsigned)tl[4 * i + 2], xcc = (unsigned)(tl[4 * i + 2] >> 32) & 0xf;
+        per_cu[(xcc << 16) | (((hw >> 13) & 7) << 8) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 0xf)]++;
+    }
+    std::sort(st.begin(), st.end());
+    std::sort(du.begin(), du.end());
+    {   // phases of the fast and of the slow workgroups
+        std::vector<unsigned long long> ph(8 * (size_t)B);
+        LK_HIP_CHECK(hipMemcpyAsync(ph.data(), d_clk + 8 + 4 * (size_t)B, 64 * (size_t)B, hipMemcpyDeviceToHost, stream));
+        LK_HIP_CHECK(hipStreamSynchronize(stream));
+        const double cut = 1.25 * du[B / 2];
+        double acc[2][6] = {{0}};
+        int cnt[2] = {0, 0};
+        for (int i = 0; i < B; ++i) {
+            const int gsl = (tl[4 * i + 1] - tl[4 * i]) * 0.01 > cut ? 1 : 0;
+            cnt[gsl]++;
+            acc[gsl][0] += (ph[8 * i] - tl[4 * i]) * 0.01;
+            for (int q = 1; q < 6; ++q) acc[gsl][q] += (ph[8 * i + q] - ph[8 * i + q - 1]) * 0.01;
+        }
+        for (int gsl = 0; gsl < 2; ++gsl)
+            if (cnt[gsl])
+                fprintf(stderr, "[pld tridiag timeline] %s workgroups (%d): load %.0f | tridiagonalise %.0f | eigenvalues %.0f | twisted %.0f | "
+                                "Gram-Schmidt %.0f | back-transform %.0f\n", gsl ? "slow" : "fast", cnt[gsl], acc[gsl][0] / cnt[gsl],
+                        acc[gsl][1] / cnt[gsl], acc[gsl][2] / cnt[gsl], acc[gsl][3] / cnt[gsl], acc[gsl][4] / cnt[gsl], acc[gsl][5] / cnt[gsl]);
+        std::string slow_ids;
+        for (int i = 0; i < B && slow_ids.size() < 200; ++i)
+            if ((tl[4 * i + 1] - tl[4 * i]) * 0.01 > cut) slow_ids += std::to_string(i) + " ";
+        fprintf(stderr, "[pld tridiag timeline] slow ids: %s\n", slow_ids.c_str());
+    }
+    int mx = 0;
+    for (auto &kv : per_cu) mx = std::max(mx, kv.second);
+    int late = 0;
+    for (int i = 0; i < B; ++i) late += st[i] > 50.0 ? 1 : 0;
+    fprintf(stderr, "[pld tridiag timeline] span %.0f us | workgroup duration min %.0f median %.0f p90 %.0f max %.0f | starts: median %.0f "
+                    "p90 %.0f max %.0f, %d of %d later than 50 us | %zu CUs used, at most %d workgroups on one\n",
+            (t1 - t0) * 0.01, du[0], du[B / 2], du[(B * 9) / 10], du[B - 1], st[B / 2], st[(B * 9) / 10], st[B - 1], late, B,
+            per_cu.size(), mx);
+    return LK_OK;
+}
+#endif
+
 // top-k eigenpairs of the B Gram matrices G (P x P, leading dimension ldg) -> V (B x P x k), lam (B x k), both allocated
 // from ws.  mirror: G holds the upper 64 x 64 blocks only (gram_plain_launch) and is completed in place first.
-static int eig_topk(lk_handle *h, double *G, int ldg, int B, int P, int k, bool products, bool mirror, double **V_out,
+static int eig_topk(lk_handle *h, double *G, int ldg, int B, int P, int k, bool mirror, double **V_out,
                     double **lam_out, hipStream_t stream, Arena &ws, const float *G32 = nullptr, double tol = -1.0,
                     const int *pcount = nullptr) {   // pcount: per-matrix column counts of a ragged batch (device, or nullptr)
-    if (!(tol > 0.0)) tol = h->pld_eig_tol > 0.0 ? h->pld_eig_tol : PLD_EIG_TOL;   // (lk_pld_set_eig_tolerance)
-    constexpr int direct_max = PLD_DIRECT_MAX;
     // Convergence: || C r - theta r || <= tol * theta_max * sqrt(k) over the k wanted pairs (PLD_EIG_TOL / PCA_EIG_TOL above).
-    constexpr int npow_std = 3;  // C^3 (or the degree-3 Chebyshev filter) between two Rayleigh-Ritz steps
-    // mid-size product blocks: a product with the 136 x 136 C is cheap next to the l x l Jacobi and the Cholesky-QR of a
-    // Rayleigh-Ritz step, and their flat spectrum keeps C^8 R well conditioned — 8 products per step need 5 steps where 3
-    // need 12.  (Pixel blocks must NOT do this: their steep spectrum makes C^5 R numerically rank-deficient, the Cholesky
-    // breaks down and the iteration stalls.)
-    constexpr int npow_prod = 8;
-    // Chebyshev-filtered steps: bit 0 = for flat spectra only (round 2's first version), bit 1 = for every spectrum.
-    // Default 3: the degree-3 filter on [0, theta_cut] needs 5.0 Rayleigh-Ritz steps where C^3 needs 7.2 on the 816-column
-    // blocks (4 instead of 5 on the pixel blocks); the feared Cholesky breakdowns on steep spectra do not occur — the
-    // columns are scaled to unit length first and SVQB stands behind — PLD step 83.7 -> 77.7 ms.
-    constexpr int cheb_on = 3;
+    if (!(tol > 0.0)) tol = h->pld_eig_tol > 0.0 ? h->pld_eig_tol : PLD_EIG_TOL;   // (lk_pld_set_eig_tolerance)
 #ifdef LK_PLD_DEBUG   // `make DEBUG=1`: LK_PLD_ITERS=1 prints Rayleigh-Ritz step counts and per-phase clocks
     static const bool dbg_iters = getenv("LK_PLD_ITERS") && atoi(getenv("LK_PLD_ITERS")) != 0;
 #else
@@ -2439,180 +2441,81 @@ static int eig_topk(lk_handle *h, double *G, int ldg, int B, int P, int k, bool 
         set_error("PLD workspace exhausted (V)");
         return LK_ENOMEM;
     }
+    *V_out = V;
+    *lam_out = lam;
     // Gram matrices that fit LDS (pixel / background blocks of <= 138 pixels, the 136-column 2nd-order product block): the
     // direct tridiagonal solver — ~0.5 ms per launch and matrix instead of the 2-3 ms of a subspace iteration's
     // Rayleigh-Ritz steps at this size
-    // (P = 134 .. 138 with k in the 40s needs more than 160 KB: those shapes fall through to the subspace iteration)
-    // LDS of the direct solver: packed triangle + six P-vectors + eigenvalues and vector norms + the twisted factorisations' scratch
-    // (the eigenvectors themselves live in V).  8 factorisations at a time instead of 16 where that brings a workgroup under half
-    // a CU's LDS (P <= ~122 at k = 16: the 121-column pixel / background blocks).
-    auto td_lds_bytes = [&](int tdl_) {
-        return ((size_t)((((P * (P + 1)) / 2) + 1) & ~1) + 6 * (size_t)P + 2 * (size_t)((k + 1) & ~1) + (size_t)tdl_ * 2 * P) * 8 + 16;
-    };
-    const int tdl = (td_lds_bytes(TD_LANES) > 80 * 1024 && td_lds_bytes(TD_LANES / 2) <= 80 * 1024) ? TD_LANES / 2 : TD_LANES;
-    const size_t td_lds = td_lds_bytes(tdl);
-    if (P >= 3 && P <= PLD_DIRECT_MAX && td_lds <= 160 * 1024) {
-        const size_t lds = td_lds;
+    if (P >= 3 && P <= PLD_DIRECT_MAX) {
+        // 8 factorisations at a time instead of 16 where that brings a workgroup under half a CU's LDS, so that two share a CU
+        // (P <= ~122 at k = 16: the 121-column pixel / background blocks)
+        const int tdl = (td_lds_bytes(P, k, TD_LANES) > 80 * 1024 && td_lds_bytes(P, k, TD_LANES / 2) <= 80 * 1024) ? TD_LANES / 2 : TD_LANES;
         int rc_ = want_lds(h, reinterpret_cast<const void *>(pld_tridiag_eig_kernel), 160 * 1024);
         if (rc_) return rc_;
         unsigned long long *d_clk = nullptr;
 #ifdef LK_PLD_DEBUG
         if (dbg_iters) d_clk = (unsigned long long *)ws.alloc(64 + 96 * (size_t)B + 64);
 #endif
-        hipLaunchKernelGGL(pld_tridiag_eig_kernel, dim3(B), dim3(TD_NT), lds, stream, G, ldg, P, k, V, lam, d_clk, tdl, pcount);
+        hipLaunchKernelGGL(pld_tridiag_eig_kernel, dim3(B), dim3(TD_NT), td_lds_bytes(P, k, tdl), stream, G, ldg, P, k, V, lam, d_clk, tdl,
+                           pcount);
 #ifdef LK_PLD_DEBUG
-        if (d_clk) {
-            unsigned long long hc[8];
-            LK_HIP_CHECK(hipMemcpyAsync(hc, d_clk, 48, hipMemcpyDeviceToHost, stream));
-            LK_HIP_CHECK(hipStreamSynchronize(stream));
-            fprintf(stderr, "[pld tridiag] P=%d k=%d per matrix us: tridiagonalise %.0f | eigenvalues %.0f | twisted factorisation %.0f | "
-                            "Gram-Schmidt %.0f | back-transform %.0f\n", P, k, (hc[1] - hc[0]) * 0.01, (hc[2] - hc[1]) * 0.01,
-                    (hc[3] - hc[2]) * 0.01, (hc[4] - hc[3]) * 0.01, (hc[5] - hc[4]) * 0.01);
-            // the launch as a whole: when each workgroup started and ended, and where it ran
-            std::vector<unsigned long long> tl(4 * (size_t)B);
-            LK_HIP_CHECK(hipMemcpyAsync(tl.data(), d_clk + 8, 32 * (size_t)B, hipMemcpyDeviceToHost, stream));
-            LK_HIP_CHECK(hipStreamSynchronize(stream));
-            unsigned long long t0 = ~0ull, t1 = 0;
-            for (int i = 0; i < B; ++i) {
-                t0 = std::min(t0, tl[4 * i]);
-                t1 = std::max(t1, tl[4 * i + 1]);
-            }
-            std::vector<double> st(B), du(B);
-            std::map<unsigned, int> per_cu;
-            for (int i = 0; i < B; ++i) {
-                st[i] = (tl[4 * i] - t0) * 0.01;
-                du[i] = (tl[4 * i + 1] - tl[4 * i]) * 0.01;
-                const unsigned hw = (unsigned)tl[4 * i + 2], xcc = (unsigned)(tl[4 * i + 2] >> 32) & 0xf;
-                per_cu[(xcc << 16) | (((hw >> 13) & 7) << 8) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 0xf)]++;
-            }
-            std::sort(st.begin(), st.end());
-            std::sort(du.begin(), du.end());
-            {   // phases of the fast and of the slow workgroups
-                std::vector<unsigned long long> ph(8 * (size_t)B);
-                LK_HIP_CHECK(hipMemcpyAsync(ph.data(), d_clk + 8 + 4 * (size_t)B, 64 * (size_t)B, hipMemcpyDeviceToHost, stream));
-                LK_HIP_CHECK(hipStreamSynchronize(stream));
-                const double cut = 1.25 * du[B / 2];
-                double acc[2][6] = {{0}};
-                int cnt[2] = {0, 0};
-                for (int i = 0; i < B; ++i) {
-                    const int gsl = (tl[4 * i + 1] - tl[4 * i]) * 0.01 > cut ? 1 : 0;
-                    cnt[gsl]++;
-                    acc[gsl][0] += (ph[8 * i] - tl[4 * i]) * 0.01;
-                    for (int q = 1; q < 6; ++q) acc[gsl][q] += (ph[8 * i + q] - ph[8 * i + q - 1]) * 0.01;
-                }
-                for (int gsl = 0; gsl < 2; ++gsl)
-                    if (cnt[gsl])
-                        fprintf(stderr, "[pld tridiag timeline] %s workgroups (%d): load %.0f | tridiagonalise %.0f | eigenvalues %.0f | twisted %.0f | "
-                                        "Gram-Schmidt %.0f | back-transform %.0f\n", gsl ? "slow" : "fast", cnt[gsl], acc[gsl][0] / cnt[gsl],
-                                acc[gsl][1] / cnt[gsl], acc[gsl][2] / cnt[gsl], acc[gsl][3] / cnt[gsl], acc[gsl][4] / cnt[gsl], acc[gsl][5] / cnt[gsl]);
-                std::string slow_ids;
-                for (int i = 0; i < B && slow_ids.size() < 200; ++i)
-                    if ((tl[4 * i + 1] - tl[4 * i]) * 0.01 > cut) slow_ids += std::to_string(i) + " ";
-                fprintf(stderr, "[pld tridiag timeline] slow ids: %s\n", slow_ids.c_str());
-            }
-            int mx = 0;
-            for (auto &kv : per_cu) mx = std::max(mx, kv.second);
-            int late = 0;
-            for (int i = 0; i < B; ++i) late += st[i] > 50.0 ? 1 : 0;
-            fprintf(stderr, "[pld tridiag timeline] span %.0f us | workgroup duration min %.0f median %.0f p90 %.0f max %.0f | starts: median %.0f "
-                            "p90 %.0f max %.0f, %d of %d later than 50 us | %zu CUs used, at most %d workgroups on one\n",
-                    (t1 - t0) * 0.01, du[0], du[B / 2], du[(B * 9) / 10], du[B - 1], st[B / 2], st[(B * 9) / 10], st[B - 1], late, B,
-                    per_cu.size(), mx);
-        }
+        if (d_clk) return td_debug_report(d_clk, B, P, k, stream);
 #endif
-        *V_out = V;
-        *lam_out = lam;
         return LK_OK;
     }
-    // Mid-size blocks (PLD_LMAX < P <= PLD_DIRECT_MAX) get two passes: a SHORT subspace iteration (a pixel block with a
-    // few dominant stars converges in ~5 Rayleigh-Ritz steps), then the direct Jacobi on C itself for the matrices that
-    // did not converge (2nd-order product blocks decay slowly: ~45 steps of the iteration vs one ~15 ms Jacobi).
-    // mid-size product blocks (2nd-order: 136 columns): subspace iteration with 8 products per Rayleigh-Ritz step (5 steps,
-    // 4.4 ms per matrix) instead of the direct Jacobi on C (135 rotation rounds x ~10 sweeps, 16 ms per matrix).
-    constexpr bool prod_direct = false;
-    constexpr int prod_l = 0;  // basis width of the product blocks: the default k + 16
-    const bool wide_sub = products && !prod_direct && P > PLD_LMAX && P <= PLD_DIRECT_MAX;
-    const bool two_pass = !wide_sub && P > PLD_LMAX && P <= std::min(direct_max, PLD_DIRECT_MAX);
-    const int npow = wide_sub ? npow_prod : npow_std;
-    int *status = nullptr;
-    if (two_pass) {
-        status = (int *)ws.alloc((size_t)B * 4);
-        if (!status) {
-            set_error("PLD workspace exhausted (status)");
-            return LK_ENOMEM;
-        }
+    if (P < 3) {  // Jacobi on C itself (l = 2: P rounded up to even)
+        const int l = 2, ld = l + 1, nt = 1024;
+        const size_t lds = ((size_t)2 * l * ld + 2 * l + nt + 2 * l + (l + 1) / 2 + 1) * 8 + 64;
+        hipLaunchKernelGGL(pld_topk_eig_kernel<2>, dim3(B), dim3(nt), lds, stream, G, ldg, P, k, l, (double *)nullptr, V, lam,
+                           (long long *)nullptr, mirror ? 1 : 0, tol, (const float *)nullptr, pcount);
+        return LK_OK;
     }
-    // product blocks are known to need the Jacobi: skip their short subspace pass (status stays all zero)
-    const bool direct_only = two_pass && products;
-    if (direct_only) LK_HIP_CHECK(hipMemsetAsync(status, 0, (size_t)B * 4, stream));
-    if (P > PLD_LMAX && !direct_only) {  // subspace iteration
-        const int l = (wide_sub && prod_l > 0) ? std::min(PLD_LMAX, prod_l & ~1) : std::min(PLD_LMAX, (k + 16 + 1) & ~1), ld = l + 1;
-        double *scr = (double *)ws.alloc((size_t)B * 4 * P * l * 8);
-        if (!scr) {
-            set_error("PLD workspace exhausted (subspace)");
-            return LK_ENOMEM;
+    // P > PLD_DIRECT_MAX: subspace iteration on a basis of l = k + 16 columns (at most PLD_LMAX)
+    const int l = std::min(PLD_LMAX, (k + 16 + 1) & ~1), ld = l + 1;
+    double *scr = (double *)ws.alloc((size_t)B * 4 * P * l * 8);
+    if (!scr) {
+        set_error("PLD workspace exhausted (subspace)");
+        return LK_ENOMEM;
+    }
+    // 512-thread workgroups, two per CU (LDS 57 KB each): one matrix's serial stretches (l x l Jacobi, Cholesky on one
+    // wave, the random start) overlap the other's stream through C — 97.2 -> 86.6 ms per PLD step against one
+    // 1024-thread workgroup per CU.  The PLD_KC-row stage also holds eig_xty's (nt / 64) x 2 KB of partial tiles.
+    constexpr int nt = 512;
+    const size_t lds = ((size_t)2 * l * ld + 2 * l + nt + 2 * l + (l + 1) / 2 + 1 + PLD_KC * PLD_QS) * 8 + 64;
+    long long *d_it = dbg_iters ? (long long *)ws.alloc((size_t)B * 64) : nullptr;
+    if (l <= 32)
+        hipLaunchKernelGGL(pld_topk_eig_kernel<2>, dim3(B), dim3(nt), lds, stream, G, ldg, P, k, l, scr, V, lam, d_it, mirror ? 1 : 0, tol,
+                           G32, pcount);
+    else
+        hipLaunchKernelGGL(pld_topk_eig_kernel<4>, dim3(B), dim3(nt), lds, stream, G, ldg, P, k, l, scr, V, lam, d_it, mirror ? 1 : 0, tol,
+                           G32, pcount);
+    if (d_it) {
+        std::vector<long long> hit((size_t)B * 8);
+        LK_HIP_CHECK(hipMemcpyAsync(hit.data(), d_it, (size_t)B * 64, hipMemcpyDeviceToHost, stream));
+        LK_HIP_CHECK(hipStreamSynchronize(stream));
+        long long sum = 0, mx = 0;
+        double ph[7] = {0, 0, 0, 0, 0, 0, 0};
+        for (int b2 = 0; b2 < B; ++b2) {
+            sum += hit[(size_t)b2 * 8];
+            mx = std::max(mx, hit[(size_t)b2 * 8]);
+            for (int s2 = 0; s2 < 7; ++s2) ph[s2] += (double)hit[(size_t)b2 * 8 + 1 + s2] / B * 0.01;  // 100 MHz ticks -> us
         }
-        // 512-thread workgroups, two per CU (LDS 57 KB each): one matrix's serial stretches (l x l Jacobi, Cholesky on one
-        // wave, the random start) overlap the other's stream through C — 97.2 -> 86.6 ms per PLD step against one
-        // 1024-thread workgroup per CU
-        constexpr int nt_env = 512;
-        int nt_sub = (nt_env == 256 || nt_env == 512 || nt_env == 1024) ? nt_env : 512;
-        if (nt_sub == 256 && l > 32) nt_sub = 512;  // 16 partial tiles of eig_xty need the 64-row stage
-        const int kc = nt_sub == 256 ? 32 : PLD_KC;  // LDS stage rows: the stage also holds eig_xty's (nt / 64) x 2 KB of partial tiles
-        const size_t lds = ((size_t)2 * l * ld + 2 * l + nt_sub + 2 * l + (l + 1) / 2 + 1 + kc * PLD_QS) * 8 + 64;
-        long long *d_it = dbg_iters ? (long long *)ws.alloc((size_t)B * 64) : nullptr;
-        if (l <= 32)
-            hipLaunchKernelGGL(pld_topk_eig_kernel<2>, dim3(B), dim3(nt_sub), lds, stream, G, ldg, P, k, l, npow, scr, V, lam,
-                               d_it, two_pass ? 8 : 400, status, cheb_on, kc, mirror ? 1 : 0, tol, G32, pcount);
-        else
-            hipLaunchKernelGGL(pld_topk_eig_kernel<4>, dim3(B), dim3(nt_sub), lds, stream, G, ldg, P, k, l, npow, scr, V, lam,
-                               d_it, two_pass ? 8 : 400, status, cheb_on, kc, mirror ? 1 : 0, tol, G32, pcount);
-        if (d_it) {
-            std::vector<long long> hit((size_t)B * 8);
-            LK_HIP_CHECK(hipMemcpyAsync(hit.data(), d_it, (size_t)B * 64, hipMemcpyDeviceToHost, stream));
-            LK_HIP_CHECK(hipStreamSynchronize(stream));
-            long long sum = 0, mx = 0;
-            double ph[7] = {0, 0, 0, 0, 0, 0, 0};
-            for (int b2 = 0; b2 < B; ++b2) {
-                sum += hit[(size_t)b2 * 8];
-                mx = std::max(mx, hit[(size_t)b2 * 8]);
-                for (int s2 = 0; s2 < 7; ++s2) ph[s2] += (double)hit[(size_t)b2 * 8 + 1 + s2] / B * 0.01;  // 100 MHz ticks -> us
-            }
-            fprintf(stderr,
-                    "[pld eig] P=%d k=%d l=%d opt=%d: Rayleigh-Ritz steps mean %.1f max %lld over %d matrices; per matrix us: "
-                    "init %.0f | C*Q %.0f | Q^T Z %.0f | Jacobi %.0f | Ritz+resid %.0f | power products %.0f | CholQR %.0f\n",
-                    P, k, l, cheb_on, (double)sum / B, mx, B, ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6]);
-            if (B > 256) {  // the first workgroup of every CU against the one that came second onto it
-                for (int grp = 0; grp < 2; ++grp) {
-                    const int b_lo = grp ? 256 : 0, b_hi = grp ? std::min(B, 512) : 256;
-                    double pg[7] = {0, 0, 0, 0, 0, 0, 0};
-                    for (int b2 = b_lo; b2 < b_hi; ++b2)
-                        for (int s2 = 0; s2 < 7; ++s2) pg[s2] += (double)hit[(size_t)b2 * 8 + 1 + s2] / (b_hi - b_lo) * 0.01;
-                    fprintf(stderr, "[pld eig] matrices %d-%d: init %.0f | C*Q %.0f | Q^T Z %.0f | Jacobi %.0f | Ritz+resid %.0f | power products %.0f | "
-                                    "CholQR %.0f | sum %.0f\n", b_lo, b_hi - 1, pg[0], pg[1], pg[2], pg[3], pg[4], pg[5], pg[6],
-                            pg[0] + pg[1] + pg[2] + pg[3] + pg[4] + pg[5] + pg[6]);
-                }
+        fprintf(stderr,
+                "[pld eig] P=%d k=%d l=%d: Rayleigh-Ritz steps mean %.1f max %lld over %d matrices; per matrix us: "
+                "init %.0f | C*Q %.0f | Q^T Z %.0f | Jacobi %.0f | Ritz+resid %.0f | power products %.0f | CholQR %.0f\n",
+                P, k, l, (double)sum / B, mx, B, ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6]);
+        if (B > 256) {  // the first workgroup of every CU against the one that came second onto it
+            for (int grp = 0; grp < 2; ++grp) {
+                const int b_lo = grp ? 256 : 0, b_hi = grp ? std::min(B, 512) : 256;
+                double pg[7] = {0, 0, 0, 0, 0, 0, 0};
+                for (int b2 = b_lo; b2 < b_hi; ++b2)
+                    for (int s2 = 0; s2 < 7; ++s2) pg[s2] += (double)hit[(size_t)b2 * 8 + 1 + s2] / (b_hi - b_lo) * 0.01;
+                fprintf(stderr, "[pld eig] matrices %d-%d: init %.0f | C*Q %.0f | Q^T Z %.0f | Jacobi %.0f | Ritz+resid %.0f | power products %.0f | "
+                                "CholQR %.0f | sum %.0f\n", b_lo, b_hi - 1, pg[0], pg[1], pg[2], pg[3], pg[4], pg[5], pg[6],
+                        pg[0] + pg[1] + pg[2] + pg[3] + pg[4] + pg[5] + pg[6]);
             }
         }
     }
-    if (P <= PLD_LMAX || two_pass) {  // direct Jacobi on C
-        const int l = (P + 1) & ~1, ld = l + 1;
-        double *scr = nullptr;
-        if (two_pass) {
-            scr = (double *)ws.alloc((size_t)B * l * l * 8);
-            if (!scr) {
-                set_error("PLD workspace exhausted (eigenvectors)");
-                return LK_ENOMEM;
-            }
-        }
-        const int nt_eig = two_pass ? 512 : 1024;
-        const size_t lds = two_pass ? ((size_t)l * ld + 2 * l + nt_eig + 2 * l + (l + 1) / 2 + 1) * 8 + 64
-                                    : ((size_t)2 * l * ld + 2 * l + 1024 + 2 * l + (l + 1) / 2 + 1) * 8 + 64;
-        hipLaunchKernelGGL(pld_topk_eig_kernel<2>, dim3(B), dim3(nt_eig), lds, stream, G, ldg, P, k, l, npow, scr, V, lam,
-                           (long long *)nullptr, 400, status, cheb_on, PLD_KC, mirror ? 1 : 0, tol, (const float *)nullptr, pcount);
-    }
-    *V_out = V;
-    *lam_out = lam;
     return LK_OK;
 }
 
@@ -2625,7 +2528,7 @@ struct PcaF32Source {  // the block as float32 pixels: A = (double)(mode == 0 ? 
 // (can the narrow Gram kernel and the float32 projection take this block?  P >= 4 columns, at most 9 column tiles, k <= 48)
 static bool pca_f32_ok(int P, int k) { return P >= 4 && (P + 15) / 16 <= 9 && k <= 48; }
 static int pca_block(lk_handle *h, double *A, int B, int N, int P, int k, const int64_t *d_off, double *X, int ldx,
-                     int col0, hipStream_t stream, Arena &ws, bool centred = false, bool products = false,
+                     int col0, hipStream_t stream, Arena &ws, bool centred = false,
                      double tol = -1.0, PcaF32Source fs = PcaF32Source{nullptr, nullptr, nullptr, 0}, const int *pcount = nullptr) {
     const bool f32src = fs.pix != nullptr;
     if (!centred && !f32src) hipLaunchKernelGGL(pld_center_kernel, dim3((P + 31) / 32, B), dim3(256), 0, stream, A, N, P);
@@ -2644,7 +2547,7 @@ static int pca_block(lk_handle *h, double *A, int B, int N, int P, int k, const 
         gram_plain_launch(A, d_off, B, P, G, stream, h);
     }
     double *V = nullptr, *lam = nullptr;
-    const int rc = eig_topk(h, G, ldg, B, P, k, products, true, &V, &lam, stream, ws, nullptr, tol, pcount);
+    const int rc = eig_topk(h, G, ldg, B, P, k, true, &V, &lam, stream, ws, nullptr, tol, pcount);
     if (rc) return rc;
     {
         const dim3 grid((N + 63) / 64, B), blk(256);
@@ -2825,7 +2728,7 @@ static int pca_products_moment(lk_handle *h, const MomentPlan &pl, int B, int N,
                            (size_t)pl.ldm * pl.ldm, pl.d_src, d_mean, Pc, ldg, (double)N, G, G32);
     }
     double *V = nullptr, *lam = nullptr;
-    const int rc = eig_topk(h, G, ldg, B, Pc, ko, true, false, &V, &lam, stream, ws, G32);
+    const int rc = eig_topk(h, G, ldg, B, Pc, ko, false, &V, &lam, stream, ws, G32);
     if (rc) return rc;
     {
         const int kt = (ko + 15) / 16;
@@ -2891,11 +2794,11 @@ int pld_design_launch(lk_handle *h, int B, int N, int P, int Pb, const float *pl
         LK_REQUIRE(d_cm != nullptr, "PLD workspace exhausted (column means)");
         hipLaunchKernelGGL(pld_colmean_kernel, dim3(B), dim3(1024), 0, stream, pld_pix, lc_flux, 1, N, P, d_cm);
         if (pca_f32_ok(P, k1)) {  // the Gram kernel and the projection form pix / flux - mean themselves
-            rc = pca_block(h, nullptr, B, N, P, k1, d_off, X, K, col, stream, h->ws, true, false, -1.0, PcaF32Source{pld_pix, lc_flux, d_cm, 1},
+            rc = pca_block(h, nullptr, B, N, P, k1, d_off, X, K, col, stream, h->ws, true, -1.0, PcaF32Source{pld_pix, lc_flux, d_cm, 1},
                            (const int *)p_count);
         } else {
             hipLaunchKernelGGL(pld_ratio_kernel, dim3((N + 31) / 32, B), dim3(256), 0, stream, pld_pix, lc_flux, 1, N, P, A, d_cm, (const float *)nullptr);
-            rc = pca_block(h, A, B, N, P, k1, d_off, X, K, col, stream, h->ws, true, false, -1.0, PcaF32Source{nullptr, nullptr, nullptr, 0},
+            rc = pca_block(h, A, B, N, P, k1, d_off, X, K, col, stream, h->ws, true, -1.0, PcaF32Source{nullptr, nullptr, nullptr, 0},
                            (const int *)p_count);
         }
         if (rc) return rc;
@@ -2947,7 +2850,7 @@ int pld_design_launch(lk_handle *h, int B, int N, int P, int Pb, const float *pl
             } else {
                 hipLaunchKernelGGL(pld_products_kernel, dim3((N + PP_ROWS - 1) / PP_ROWS, B), dim3(256), 0, stream, X, K, col1, k1, o,
                                    N, Pc, d_comb, d_mean, A);
-                rc = pca_block(h, A, B, N, Pc, ko, d_off, X, K, col, stream, h->ws, true, true);
+                rc = pca_block(h, A, B, N, Pc, ko, d_off, X, K, col, stream, h->ws, true);
                 if (rc) return rc;
             }
             col += ko;
@@ -2972,9 +2875,9 @@ int pld_design_launch(lk_handle *h, int B, int N, int P, int Pb, const float *pl
     }
     const int kb = std::min(pca_components, Pb);
     if (bkg_f32)
-        rc = pca_block(h, nullptr, B, N, Pb, kb, d_off, X, K, col, stream, h->ws, true, false, -1.0, bkg_src, (const int *)pb_count);
+        rc = pca_block(h, nullptr, B, N, Pb, kb, d_off, X, K, col, stream, h->ws, true, -1.0, bkg_src, (const int *)pb_count);
     else
-        rc = pca_block(h, A, B, N, Pb, kb, d_off, X, K, col, stream, h->ws, true, false, -1.0, PcaF32Source{nullptr, nullptr, nullptr, 0},
+        rc = pca_block(h, A, B, N, Pb, kb, d_off, X, K, col, stream, h->ws, true, -1.0, PcaF32Source{nullptr, nullptr, nullptr, 0},
                        (const int *)pb_count);
     if (rc) return rc;
     col += kb;
@@ -3008,7 +2911,7 @@ int dm_pca_launch(lk_handle *h, int B, int N, int P, int k, const double *A_in, 
     double *A = (double *)h->ws.alloc((size_t)B * N * P * 8);
     LK_REQUIRE(A != nullptr, "workspace exhausted");
     LK_HIP_CHECK(hipMemcpyAsync(A, A_in, (size_t)B * N * P * 8, hipMemcpyDeviceToDevice, stream));
-    rc = pca_block(h, A, B, N, P, k, d_off, U, k, 0, stream, h->ws, false, false, PCA_EIG_TOL);
+    rc = pca_block(h, A, B, N, P, k, d_off, U, k, 0, stream, h->ws, false, PCA_EIG_TOL);
     if (rc) return rc;
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;

@@ -1123,14 +1123,13 @@ int regress_launch(lk_handle *h, int B, const int64_t *n_off_host, int K, const 
     }
     LK_HIP_CHECK(hipMemsetAsync(outl, 0, ntot, stream));
     // per-target convergence flags of the clip loop: a pass that adds no outlier ends the target's loop
-    constexpr bool early = true;
-    int *d_done = early ? (int *)h->ws.alloc((size_t)B * 4) : nullptr;
-    if (d_done) LK_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)B * 4, stream));
+    int *d_done = (int *)h->ws.alloc((size_t)B * 4);
     // the cadences each clip adds to the outlier set, for the DELTA Gram of the next pass
     constexpr int kNewCap = 256;
     int *d_newcnt = (int *)h->ws.alloc((size_t)B * 4);
     int *d_newidx = (int *)h->ws.alloc((size_t)B * kNewCap * 4);
-    LK_REQUIRE(d_newcnt && d_newidx, "workspace exhausted");
+    LK_REQUIRE(d_done && d_newcnt && d_newidx, "workspace exhausted");
+    LK_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)B * 4, stream));
     const int nblk = KB * (KB + 1) / 2;
     for (int it = 0; it < niters; ++it) {
         if (it == 0) {

@@ -63,9 +63,10 @@ def test_standardize_and_split_match_the_reference():
     assert dm3.split([]) is dm3 and dm3.split([0]) is dm3
 
 
-def test_pca_wide_block_with_many_components_falls_to_the_subspace_iteration():
-    """P = 134..138 with k in the 40s needs more than 160 KB of LDS in the direct tridiagonal solver; such
-    shapes must take the subspace iteration instead of failing (reference designmatrix.py:252-282 has no such limit)."""
+def test_pca_largest_shape_of_the_direct_solver():
+    """P = 138 columns with k = 48 components is the largest shape the direct tridiagonal solver is given (its LDS grows with
+    P and k: 117 KB here, under the 160 KB of a CU); the reference (designmatrix.py:252-282) has no such limit, so the shape
+    must not fail."""
     rng = np.random.default_rng(8)
     N, P, k = 600, 138, 48
     A = rng.normal(size=(N, 60)) @ rng.normal(size=(60, P)) * np.geomspace(1.0, 1e-3, P) + 1e-6 * rng.normal(size=(N, P))
@@ -107,3 +108,37 @@ def test_direct_solver_with_repeated_singular_values_both_gram_schmidt_paths():
         assert U.shape == (N, k)
         assert np.max(np.abs(U.T @ U - np.eye(k))) < 1e-9, k
         assert _subspace_gap(U, Uref[:, :k]) < 1e-6, k
+
+
+def _prescribed_spectrum(N, P, k, seed):
+    """A = Qn diag(sv) Qp^T of rank min(N, P): the k wanted singular values fall from 1 to 0.2, the others start a decade below
+    (0.02 .. 1e-4), so the subspace of the k leading vectors is well separated whatever the spacing inside it."""
+    rng = np.random.default_rng(seed)
+    r = min(N, P)
+    sv = np.concatenate([np.geomspace(1.0, 0.2, k), np.geomspace(0.02, 1e-4, r - k)])
+    Qn = np.linalg.qr(rng.normal(size=(N, r)))[0]
+    Qp = np.linalg.qr(rng.normal(size=(P, r)))[0]
+    return (Qn * sv) @ Qp.T
+
+
+@pytest.mark.parametrize("N,P,k", [
+    (300, 1, 1), (300, 2, 2),     # Jacobi on C itself (fewer than 3 columns)
+    (300, 3, 3),                  # smallest shape of the direct tridiagonal solver
+    (300, 139, 16),               # smallest subspace iteration, basis of 32 columns (two 16-column tiles)
+    (300, 139, 48),               # smallest subspace iteration, basis of 64 columns (four tiles)
+    (20, 150, 8),                 # rank 19 < basis width 24: the basis cannot be filled, the plain-power branch can be taken
+])
+def test_pca_at_the_boundaries_of_the_eigen_solver_routes(N, P, k):
+    """lk_pca_batch on the two sides of every boundary between the eigen-solver's routes (eig_topk in pld.hip: P < 3 Jacobi,
+    3 <= P <= 138 direct tridiagonal solver, P > 138 subspace iteration with a basis of min(64, k + 16) columns), two differently
+    scaled copies per call, against np.linalg.svd of the centred matrix.  The reference's own gap at the cut defines the
+    wanted subspace: the solver stops at a residual of 1e-10 theta_max sqrt(k), i.e. an angle of ~1e-8 across a decade."""
+    A = _prescribed_spectrum(N, P, k, 100 * P + k)
+    Uref, sref, _ = np.linalg.svd(A - A.mean(axis=0), full_matrices=False)
+    s_next = sref[k] if k < len(sref) else 0.0
+    assert sref[k - 1] - s_next > 0.05 * sref[k - 1]
+    Ub = _capi.pca_batch(np.stack([A, 3.0 * A[::-1]]), k)
+    assert Ub.shape == (2, N, k)
+    for U in (Ub[0], Ub[1][::-1]):
+        assert np.max(np.abs(U.T @ U - np.eye(k))) < 1e-9
+        assert _subspace_gap(U, Uref[:, :k]) < 1e-6
