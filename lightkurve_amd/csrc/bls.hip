@@ -1166,19 +1166,19 @@ int bls_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, 
     const int wide_slabs = n_wide ? (int)std::min<long long>((long long)B * n_wide, 2 * (long long)h->num_cu) : 0;
 
     const size_t ntot = (size_t)n_off_host[B];
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(B + 1) * 8 + (size_t)B * sizeof(BlsStats) + 3 * (ntot * 8 + 256) +
-                           (size_t)nP * 4 + dur_tab.size() * 4 + (size_t)nd * 4 + (size_t)wide_slabs * 2 * wide_cap * 8 + 8192);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    BlsStats *d_stats = (BlsStats *)h->ws.alloc((size_t)B * sizeof(BlsStats));
-    double *d_tm = (double *)h->ws.alloc(ntot * 8);
-    double2 *d_yw = (double2 *)h->ws.alloc(ntot * 16);
-    int *d_pidx = (int *)h->ws.alloc((size_t)nP * 4);
-    int *d_dur = (int *)h->ws.alloc(dur_tab.size() * 4);
-    int *d_dur_caller = (int *)h->ws.alloc((size_t)nd * 4);
-    double *d_slabs = n_wide ? (double *)h->ws.alloc((size_t)wide_slabs * 2 * wide_cap * 8) : nullptr;
-    LK_REQUIRE(!n_wide || d_slabs, "workspace exhausted (wide-period slabs)");
+    int64_t *d_off;
+    BlsStats *d_stats;
+    double *d_tm, *d_slabs;
+    double2 *d_yw;
+    int *d_pidx, *d_dur, *d_dur_caller, *d_bad;
+    Scratch ws(h, h->ws);
+    ws.buf(d_off, B + 1).buf(d_stats, B)
+        .buf(d_tm, ntot).buf(d_yw, ntot)
+        .buf(d_pidx, nP)
+        .buf(d_dur, dur_tab.size()).buf(d_dur_caller, nd)
+        .buf(d_slabs, (size_t)wide_slabs * 2 * wide_cap, n_wide != 0)
+        .buf(d_bad, 64, h->bls_attr_set != 1);  // the self-test's word, in a 256-byte slot of its own
+    if (const int rc = ws.carve(stream)) return rc;
     LK_HIP_CHECK(hipMemcpyAsync(d_dur_caller, dur_bins.data(), (size_t)nd * 4, hipMemcpyHostToDevice, stream));
     LK_HIP_CHECK(hipMemcpyAsync(d_off, n_off_host, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, stream));
     LK_HIP_CHECK(hipMemcpyAsync(d_pidx, order.data(), (size_t)nP * 4, hipMemcpyHostToDevice, stream));
@@ -1196,7 +1196,6 @@ int bls_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, 
         }
         // the histogram rests on one hardware property (same-address lanes of a ds_add_f64 are applied in lane order):
         // check it on this device once per handle and refuse to run without it
-        int *d_bad = (int *)h->ws.alloc(256);
         LK_HIP_CHECK(hipMemsetAsync(d_bad, 0, 4, stream));
         hipLaunchKernelGGL(bls_selftest_kernel, dim3(64), dim3(64), 0, stream, d_bad);
         int bad = -1;

@@ -1,7 +1,9 @@
 // capi.hip — extern "C" boundary of liblkhip.so (declared in include/lkhip.h).
 // Host-pointer entry points stage caller buffers into HBM through StagedCall (h->staging), run the same launchers as the
 // device-pointer entry points on the null stream and copy the results back; the device-pointer entry points only
-// validate, carve scratch and enqueue kernels.
+// validate and enqueue kernels.  Every launcher declares its device scratch once as a lk::Scratch plan (lk_common.hpp;
+// carve() is defined here, next to the Arena it carves) — h->ws for the kernels, h->staging for the double buffers of the
+// chunked LS 'fast' host pipeline.
 #include "lk_common.hpp"
 
 namespace lk {
@@ -74,6 +76,30 @@ void Arena::release() {
     cap = used = 0;
 }
 
+int Scratch::carve(hipStream_t stream) {
+    if (n_ > MAX_BUFS) {
+        set_error("internal: a scratch plan declares %d buffers (at most %d)", n_, MAX_BUFS);
+        return LK_EHIP;
+    }
+    size_t total = 0;
+    for (int i = 0; i < n_; ++i) total += Arena::round(bufs_[i].bytes);
+    arena_.reset();
+    // at least one byte: a zero-length buffer still gets a non-null pointer
+    int rc = arena_.reserve(std::max<size_t>(total, 1));
+    if (rc) return rc;
+    void *dev[MAX_BUFS];
+    for (int i = 0; i < n_; ++i)
+        if (!(dev[i] = arena_.alloc(bufs_[i].bytes))) {
+            arena_.reset();
+            set_error("internal: scratch plan of %zu bytes does not fit its own reservation", total);
+            return LK_EHIP;
+        }
+    for (int i = 0; i < n_; ++i) bufs_[i].set(bufs_[i].slot, dev[i]);
+    for (int i = 0; i < n_; ++i)
+        if (bufs_[i].src && (rc = h_->stage.copy(dev[i], bufs_[i].src, bufs_[i].bytes, stream))) return rc;
+    return LK_OK;
+}
+
 // The device mirrors of one host-pointer call, in h->staging.  The call declares its buffers in carving order: in() is
 // copied to the device by stage(), out() back to the host by finish(), scratch() is device-only; a null host pointer
 // declares nothing and leaves its device pointer null.  stage() resets the arena, reserves exactly the declared buffers
@@ -94,7 +120,7 @@ class StagedCall {
 
     int stage() {
         size_t total = 0;
-        for (const Buf &b : bufs_) total += (b.elem * b.n_dev + 255) & ~size_t(255);
+        for (const Buf &b : bufs_) total += Arena::round(b.elem * b.n_dev);
         h_->staging.reset();
         // at least one byte: a zero-length buffer still gets a non-null pointer (launchers reject NULL before sizes)
         int rc = h_->staging.reserve(std::max<size_t>(total, 1));
@@ -1139,20 +1165,19 @@ static int ls_fast_peaks_host(lk_handle *h, int B, const int64_t *n_off, const d
         in_max = std::max(in_max, (size_t)(n_off[b1] - n_off[b0]));
     }
     const int narr = dy ? 3 : 2;
-    const size_t in_bytes = in_max * 8, pow_bytes = (size_t)C * (size_t)M * 8;
-    h->staging.reset();
-    rc = h->staging.reserve(2 * narr * (in_bytes + 256) + 2 * (pow_bytes + 256) + 4 * ((size_t)(B + 1) * 8 + 256) + 4096);
-    if (rc) return rc;
     double *d_in[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    double *d_pow[2];
+    double *d_pow[2], *d_scale, *d_max;
+    int64_t *d_arg, *d_off_all;
+    lk::Scratch ws(h, h->staging);
     for (int s = 0; s < 2; ++s) {
-        for (int a = 0; a < narr; ++a) d_in[s][a] = (double *)h->staging.alloc(in_bytes);
-        d_pow[s] = (double *)h->staging.alloc(pow_bytes);
+        for (int a = 0; a < narr; ++a) ws.buf(d_in[s][a], in_max);
+        ws.buf(d_pow[s], (size_t)C * M);
     }
-    double *d_scale = scale ? (double *)h->staging.alloc((size_t)B * 8) : nullptr;
-    double *d_max = max_power ? (double *)h->staging.alloc((size_t)B * 8) : nullptr;
-    int64_t *d_arg = argmax ? (int64_t *)h->staging.alloc((size_t)B * 8) : nullptr;
-    int64_t *d_off_all = rebase ? (int64_t *)h->staging.alloc((size_t)(B + 1) * 8) : nullptr;
+    ws.buf(d_scale, B, scale != nullptr)
+        .buf(d_max, B, max_power != nullptr)
+        .buf(d_arg, B, argmax != nullptr)
+        .buf(d_off_all, B + 1, rebase);
+    if ((rc = ws.carve(h->s_in))) return rc;
     if (scale) LK_HIP_CHECK(hipMemcpyAsync(d_scale, scale, (size_t)B * 8, hipMemcpyHostToDevice, h->s_in));
     if (rebase) LK_HIP_CHECK(hipMemcpyAsync(d_off_all, n_off, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, h->s_in));
     std::vector<int64_t> offc((size_t)C + 1);

@@ -46,6 +46,12 @@ __global__ __launch_bounds__(1024) void rebase_copy_kernel(const double *__restr
     for (int64_t i = threadIdx.x; i < n; i += 1024) out[lo + i] = t[lo + i] - t0;
 }
 
+int rebase_launch(int B, const int64_t *d_off, const double *t, double *out, hipStream_t stream) {
+    hipLaunchKernelGGL(rebase_copy_kernel, dim3(B), dim3(1024), 0, stream, t, d_off, out);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ BLS inputs
 // One workgroup per light curve.  The arithmetic is the host front end's (lightkurve_amd/packed.py: bls_inputs), itself the
 // reference's per object: trel = t - t[0]; t_out = trel - min(trel); y_out = flux - numpy.median(flux); ivar = 1 / err^2 when
@@ -296,20 +302,9 @@ int lk_ls_fast_peaks_lc_batch_dev(lk_handle *h, int B, const int64_t *n_off_host
     if (B == 0 || M == 0) return LK_OK;
     LK_REQUIRE(time && flux, "time, flux must be non-NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // the rebased times live in the handle's SECOND arena (the kernels' scratch arena is reset by lsfast_launch); it is the
-    // staging arena of the host-pointer entry points, free whenever a *_dev call runs (one stream per handle)
-    const size_t ntot = (size_t)n_off_host[B];
-    h->staging.reset();
-    rc = h->staging.reserve(ntot * 8 + (size_t)(B + 1) * 8 + 1024);
-    if (rc) return rc;
-    double *d_trel = (double *)h->staging.alloc(ntot * 8);
-    int64_t *d_off = (int64_t *)h->staging.alloc((size_t)(B + 1) * 8);
-    rc = h->stage.copy(d_off, n_off_host, (size_t)(B + 1) * 8, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(lk::rebase_copy_kernel, dim3(B), dim3(1024), 0, st, time, d_off, d_trel);
-    return lk::lsfast_launch(h, B, n_off_host, d_trel, flux, dy, f0, df, M, fit_mean, center_data, normalization, scale,
-                             oversampling, power, st, max_power, argmax);
+    // rebase: the launcher carves the rebased times in its own plan and fills them through lk::rebase_launch
+    return lk::lsfast_launch(h, B, n_off_host, time, flux, dy, f0, df, M, fit_mean, center_data, normalization, scale,
+                             oversampling, power, static_cast<hipStream_t>(stream), max_power, argmax, true);
 }
 
 int lk_rebase_times_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, double *t_out,
@@ -321,14 +316,9 @@ int lk_rebase_times_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, co
     LK_REQUIRE(time && t_out && time != t_out, "time, t_out must be two non-NULL buffers");
     LK_HIP_CHECK(hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    h->ws.reset();
-    rc = h->ws.reserve((size_t)(B + 1) * 8 + 1024);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    if ((rc = h->stage.copy(d_off, n_off_host, (size_t)(B + 1) * 8, st))) return rc;
-    hipLaunchKernelGGL(lk::rebase_copy_kernel, dim3(B), dim3(1024), 0, st, time, d_off, t_out);
-    LK_HIP_CHECK(hipGetLastError());
-    return LK_OK;
+    int64_t *d_off;
+    if ((rc = lk::Scratch(h, h->ws).upload(d_off, n_off_host, B + 1).carve(st))) return rc;
+    return lk::rebase_launch(B, d_off, time, t_out, st);
 }
 
 int lk_segment_probe_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *x,
@@ -340,13 +330,8 @@ int lk_segment_probe_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, c
     LK_REQUIRE((time && descents_host) || (x && finite_host), "nothing to probe");
     LK_HIP_CHECK(hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    h->ws.reset();
-    rc = h->ws.reserve(3 * ((size_t)(B + 1) * 8 + 256) + 1024);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    int64_t *d_desc = (int64_t *)h->ws.alloc((size_t)B * 8);
-    int64_t *d_fin = (int64_t *)h->ws.alloc((size_t)B * 8);
-    if ((rc = h->stage.copy(d_off, n_off_host, (size_t)(B + 1) * 8, st))) return rc;
+    int64_t *d_off, *d_desc, *d_fin;
+    if ((rc = lk::Scratch(h, h->ws).upload(d_off, n_off_host, B + 1).buf(d_desc, B).buf(d_fin, B).carve(st))) return rc;
     hipLaunchKernelGGL(lk::segment_probe_kernel, dim3(B), dim3(256), 0, st, descents_host ? time : nullptr,
                        finite_host ? x : nullptr, d_off, d_desc, d_fin);
     if (descents_host) LK_HIP_CHECK(hipMemcpyAsync(descents_host, d_desc, (size_t)B * 8, hipMemcpyDeviceToHost, st));
@@ -366,12 +351,8 @@ int lk_bls_prepare_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, con
     LK_REQUIRE(time && flux && t_out && y_out && ivar_out, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    h->ws.reset();
-    rc = h->ws.reserve((size_t)(B + 1) * 8 + 1024);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    rc = h->stage.copy(d_off, n_off_host, (size_t)(B + 1) * 8, st);
-    if (rc) return rc;
+    int64_t *d_off;
+    if ((rc = lk::Scratch(h, h->ws).upload(d_off, n_off_host, B + 1).carve(st))) return rc;
     constexpr int cap = 4096;
     const size_t lds = 512 * 8 + (size_t)cap * 8;
     hipLaunchKernelGGL(lk::bls_prepare_kernel, dim3(B), dim3(lk::BLSP_NT), lds, st, time, flux, flux_err, d_off, t_out,
@@ -397,13 +378,8 @@ int lk_compact_columns_batch_dev(lk_handle *h, int B, const int64_t *n_off_host,
     lk::ColPtrs cp;
     for (int c = 0; c < 8; ++c) cp.in[c] = c < ncols ? cols_in[c] : nullptr, cp.out[c] = c < ncols ? cols_out[c] : nullptr;
     for (int c = 0; c < ncols; ++c) LK_REQUIRE(cp.in[c] && cp.out[c], "column %d is NULL", c);
-    h->ws.reset();
-    rc = h->ws.reserve(2 * ((size_t)(B + 1) * 8 + 256) + 1024);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    int64_t *d_new = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    if ((rc = h->stage.copy(d_off, n_off_host, (size_t)(B + 1) * 8, st))) return rc;
-    if ((rc = h->stage.copy(d_new, new_off_host, (size_t)(B + 1) * 8, st))) return rc;
+    int64_t *d_off, *d_new;
+    if ((rc = lk::Scratch(h, h->ws).upload(d_off, n_off_host, B + 1).upload(d_new, new_off_host, B + 1).carve(st))) return rc;
     if (elem_bytes == 4)
         hipLaunchKernelGGL(lk::compact_columns_kernel<uint32_t>, dim3(B), dim3(512), 0, st, flux, d_off, d_new, ncols, cp);
     else
@@ -420,12 +396,9 @@ int lk_gather_f64_dev(lk_handle *h, int n, const int64_t *idx_host, const double
     LK_REQUIRE(idx_host && src_dev && dst_host, "NULL buffer");
     LK_HIP_CHECK(hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    h->ws.reset();
-    int rc = h->ws.reserve(2 * ((size_t)n * 8 + 256) + 1024);
-    if (rc) return rc;
-    int64_t *d_idx = (int64_t *)h->ws.alloc((size_t)n * 8);
-    double *d_val = (double *)h->ws.alloc((size_t)n * 8);
-    if ((rc = h->stage.copy(d_idx, idx_host, (size_t)n * 8, st))) return rc;
+    int64_t *d_idx;
+    double *d_val;
+    if (int rc = lk::Scratch(h, h->ws).upload(d_idx, idx_host, n).buf(d_val, n).carve(st)) return rc;
     hipLaunchKernelGGL(lk::gather_f64_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, d_idx, src_dev, d_val);
     LK_HIP_CHECK(hipMemcpyAsync(dst_host, d_val, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     LK_HIP_CHECK(hipStreamSynchronize(st));

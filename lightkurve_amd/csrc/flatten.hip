@@ -1079,15 +1079,19 @@ int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
         // slab: tm, fm, tr (8 B each) | idx, segs (4 B each, segs + 8 entries) | mask, mask1 (1 B each)
         soff[b + 1] = soff[b] + ((3 * np * 8 + 2 * np * 4 + 32 + 2 * np + 255) & ~(int64_t)255);
     }
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)soff[B] + (size_t)B * (64 + 16 * 16) + 8192);
-    if (rc) return rc;
+    int64_t nmax = 0;
+    for (int b = 0; b < B; ++b) nmax = std::max(nmax, n_off_host[b + 1] - n_off_host[b]);
+    // trend workgroups per light curve: enough tiles for each (a 20 000-cadence light curve has ~19 tiles of ~1070 outputs at
+    // window 401; a 4500-cadence one 4), and B x T >= ~4 workgroups per CU
+    const int trend_T = (int)std::max<int64_t>(1, std::min<int64_t>(8, nmax / 4096));
+    char *d_s;
+    FlatState *d_state;
+    double2 *d_rs;
+    if (const int rc = Scratch(h, h->ws).buf(d_s, soff[B]).buf(d_state, B).buf(d_rs, (size_t)B * trend_T).carve(stream)) return rc;
     // the two offset tables travel as ONE staged copy through the handle's pinned ring (captured before this function
     // returns, ordered on the caller's stream): no host synchronisation in the launcher (it used to idle the GPU ~50 us per call)
     // They live in a buffer of the handle's own and are re-sent only when they differ from the previous call's (batches of one
     // shape follow each other in a pipeline): the copy and the queue hand-over around it cost ~15 us of idle GPU per call.
-    char *d_s = (char *)h->ws.alloc((size_t)soff[B]);
-    LK_REQUIRE(d_s, "workspace exhausted");
     std::vector<int64_t> both((size_t)2 * (B + 1));
     std::copy(n_off_host, n_off_host + B + 1, both.begin());
     std::copy(soff.begin(), soff.end(), both.begin() + B + 1);
@@ -1110,19 +1114,11 @@ int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
         h->flat_tab_stream = stream;
     }
     const int64_t *d_off = h->flat_tab_dev, *d_soff = d_off + (B + 1);
-    int64_t nmax = 0;
-    for (int b = 0; b < B; ++b) nmax = std::max(nmax, n_off_host[b + 1] - n_off_host[b]);
     // FIR / candidate area of the tap-by-tap trend kernel (short windows): 8 x 612 doubles = 4096-output tiles; doubled until
     // the window fits a tile
     int fir_lds = 4896;
     while (fir_lds < 16384 && window > fir_lds / 2 + 1) fir_lds *= 2;
     const size_t lds_sel = (size_t)std::max(FLAT_NT, 264) * 8 + (size_t)(fir_lds + 2) * 8 + (size_t)FLAT_NT * 4;
-    FlatState *d_state = (FlatState *)h->ws.alloc((size_t)B * sizeof(FlatState));
-    // trend workgroups per light curve: enough tiles for each (a 20 000-cadence light curve has ~19 tiles of ~1070 outputs at
-    // window 401; a 4500-cadence one 4), and B x T >= ~4 workgroups per CU
-    const int trend_T = (int)std::max<int64_t>(1, std::min<int64_t>(8, nmax / 4096));
-    double2 *d_rs = (double2 *)h->ws.alloc((size_t)B * trend_T * sizeof(double2));
-    LK_REQUIRE(d_state != nullptr && d_rs != nullptr, "workspace exhausted (flatten state)");
     // the moment-form trend kernel keeps four tile arrays (three prefix sums + the inputs) of 1470 doubles: three 512-thread
     // workgroups of it fit a CU's 160 KB of LDS (longer windows: sized from the tap kernel's area)
     const int fir_trend = std::max(4 * 1470, ((window > 1470 / 2 ? fir_lds : 0) / 3) * 4);

@@ -159,12 +159,11 @@ int fold_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t,
         soff[b + 1] = soff[b] + npad;
         nmax = std::max(nmax, n);
     }
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(B + 1) * 16 + (size_t)B * 24 + (size_t)soff[B] * sizeof(FoldKey) + 4096);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8), *d_soff = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    double *d_par = (double *)h->ws.alloc((size_t)B * 24);
-    FoldKey *d_keys = (FoldKey *)h->ws.alloc((size_t)soff[B] * sizeof(FoldKey));
+    int64_t *d_off, *d_soff;
+    double *d_par;
+    FoldKey *d_keys;
+    if (const int rc = Scratch(h, h->ws).buf(d_off, B + 1).buf(d_soff, B + 1).buf(d_par, (size_t)3 * B).buf(d_keys, soff[B]).carve(stream))
+        return rc;
     std::vector<double> par((size_t)3 * B);
     for (int b = 0; b < B; ++b) {
         par[b] = period_host[b];

@@ -144,14 +144,8 @@ int ingest_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *
         const int64_t n = n_off_host[b + 1] - n_off_host[b];
         LK_REQUIRE(n >= 0 && n < ((int64_t)1 << 30), "target %d has %lld cadences", b, (long long)n);
     }
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(B + 1) * 8 * 3 + 4096);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    int64_t *d_kept = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    int64_t *d_new = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    rc = h->stage.copy(d_off, n_off_host, (size_t)(B + 1) * 8, stream);
-    if (rc) return rc;
+    int64_t *d_off, *d_kept, *d_new;
+    if (const int rc = Scratch(h, h->ws).upload(d_off, n_off_host, B + 1).buf(d_kept, B + 1).buf(d_new, B + 1).carve(stream)) return rc;
     hipLaunchKernelGGL(ingest_count_kernel, dim3(B), dim3(256), 0, stream, flux, d_off, d_kept);
     hipLaunchKernelGGL(ingest_scan_kernel, dim3(1), dim3(1024), 0, stream, d_kept, B, d_new);
     constexpr int cap = 4096;
@@ -299,14 +293,11 @@ int fits_unpack_launch(lk_handle *h, int B, const uint8_t *raw, const int64_t *r
         }
         max_row = std::max(max_row, d[0]);
     }
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(B + 1) * 8 * 4 + (size_t)B * sizeof(FitsDesc) + 4096);
-    if (rc) return rc;
-    int64_t *d_roff = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    int64_t *d_mask = (int64_t *)h->ws.alloc((size_t)B * 8);
-    int64_t *d_kept = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    int64_t *d_new = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    FitsDesc *d_desc = (FitsDesc *)h->ws.alloc((size_t)B * sizeof(FitsDesc));
+    int64_t *d_roff, *d_mask, *d_kept, *d_new;
+    FitsDesc *d_desc;
+    if (const int rc = Scratch(h, h->ws).buf(d_roff, B + 1).buf(d_mask, B).buf(d_kept, B + 1).buf(d_new, B + 1)
+            .buf(d_desc, B).carve(stream))
+        return rc;
     LK_HIP_CHECK(hipMemcpyAsync(d_roff, raw_off_host, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, stream));
     LK_HIP_CHECK(hipMemcpyAsync(d_mask, bitmask_host, (size_t)B * 8, hipMemcpyHostToDevice, stream));
     LK_HIP_CHECK(hipMemcpyAsync(d_desc, desc_host, (size_t)B * sizeof(FitsDesc), hipMemcpyHostToDevice, stream));
@@ -370,14 +361,13 @@ int fits_cube_launch(lk_handle *h, const uint8_t *raw, int row_bytes, int n_rows
         *kept_host = 0;
         return LK_OK;
     }
-    h->ws.reset();
-    int rc = h->ws.reserve(64 + sizeof(FitsDesc) + (size_t)n_rows * 4 + (size_t)n_rows * 16 + 4096);
-    if (rc) return rc;
-    int64_t *d_roff = (int64_t *)h->ws.alloc(16), *d_mask = (int64_t *)h->ws.alloc(8);
-    int64_t *d_kept = (int64_t *)h->ws.alloc(16), *d_new = (int64_t *)h->ws.alloc(16);
-    FitsDesc *d_desc = (FitsDesc *)h->ws.alloc(sizeof(FitsDesc));
-    int *d_rows = (int *)h->ws.alloc((size_t)n_rows * 4);
-    double *d_dummy = (double *)h->ws.alloc((size_t)n_rows * 8);  // the scalar kernel's flux slot (TIME again), unused
+    int64_t *d_roff, *d_mask, *d_kept, *d_new;
+    FitsDesc *d_desc;
+    int *d_rows;
+    double *d_dummy;  // the scalar kernel's flux slot (TIME again), unused
+    if (const int rc = Scratch(h, h->ws).buf(d_roff, 2).buf(d_mask, 1).buf(d_kept, 2).buf(d_new, 2).buf(d_desc, 1).buf(d_rows, n_rows)
+            .buf(d_dummy, n_rows).carve(stream))
+        return rc;
     const int64_t roff[2] = {0, (int64_t)row_bytes * n_rows};
     const FitsDesc desc{row_bytes, n_rows, off_time, code_time, off_time, code_time, -1, 0, off_qual, code_qual};
     LK_HIP_CHECK(hipMemcpyAsync(d_roff, roff, 16, hipMemcpyHostToDevice, stream));
@@ -443,13 +433,11 @@ int transit_mask_launch(lk_handle *h, int B, const int64_t *n_off_host, const do
     }
     for (int p = 0; p < np_tot; ++p) LK_REQUIRE(period_host[p] != 0.0, "period must be non-zero");
     if (nmax == 0) return LK_OK;
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(B + 1) * 12 + (size_t)np_tot * 24 + 8 * 256 + 4096);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    int *d_poff = (int *)h->ws.alloc((size_t)(B + 1) * 4);
-    double *d_par = (double *)h->ws.alloc((size_t)std::max(np_tot, 1) * 24);
     std::vector<double> par((size_t)std::max(np_tot, 1) * 3, 1.0);
+    int64_t *d_off;
+    int *d_poff;
+    double *d_par;
+    if (const int rc = Scratch(h, h->ws).buf(d_off, B + 1).buf(d_poff, B + 1).buf(d_par, par.size()).carve(stream)) return rc;
     for (int p = 0; p < np_tot; ++p) {
         par[p] = period_host[p];
         par[(size_t)np_tot + p] = duration_host[p];
@@ -571,12 +559,12 @@ int bin_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, 
         LK_REQUIRE(bin_off_host[b + 1] >= bin_off_host[b] && bin_off_host[b + 1] - bin_off_host[b] < n_edges,
                    "target %d needs more bin edges than were passed", b);
     if (nbins == 0) return LK_OK;
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(B + 1) * 16 + (size_t)B * 9 + (size_t)n_edges * 8 + 6 * 256 + 4096);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8), *d_boff = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    double *d_start = (double *)h->ws.alloc((size_t)B * 8), *d_edges = (double *)h->ws.alloc((size_t)n_edges * 8);
-    uint8_t *d_he = (uint8_t *)h->ws.alloc((size_t)B);
+    int64_t *d_off, *d_boff;
+    double *d_start, *d_edges;
+    uint8_t *d_he;
+    if (const int rc = Scratch(h, h->ws).buf(d_off, B + 1).buf(d_boff, B + 1).buf(d_start, B).buf(d_edges, n_edges)
+            .buf(d_he, B).carve(stream))
+        return rc;
     LK_HIP_CHECK(hipMemcpyAsync(d_off, n_off_host, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, stream));
     LK_HIP_CHECK(hipMemcpyAsync(d_boff, bin_off_host, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, stream));
     LK_HIP_CHECK(hipMemcpyAsync(d_start, start_host, (size_t)B * 8, hipMemcpyHostToDevice, stream));

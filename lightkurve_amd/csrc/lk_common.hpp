@@ -34,12 +34,15 @@ void set_error(const char *fmt, ...);
     } while (0)
 
 // Grow-only device scratch arena.  Sub-allocations are 256-byte aligned and valid until reset().
+// reserve() and alloc() are called only by Scratch (below), by capi.hip's StagedCall and by pld.hip: pld_design_launch and
+// dm_pca_launch use the arena as a stack (mark / rewind between phases, a maximum and not a sum), so they stay hand-carved.
 struct Arena {
+    static constexpr size_t round(size_t bytes) { return (bytes + 255) & ~size_t(255); }  // what one alloc() occupies
     char *base = nullptr;
     size_t cap = 0, used = 0;
     int reserve(size_t bytes);  // ensure capacity (may reallocate: only call before any alloc())
     void *alloc(size_t bytes) {
-        size_t a = (used + 255) & ~size_t(255);
+        size_t a = round(used);
         if (a + bytes > cap) return nullptr;
         used = a + bytes;
         return base + a;
@@ -66,9 +69,10 @@ struct lk_handle {
     int num_cu = 256;
     int host_chunk_mb = 64;  // MiB of spectra per chunk of the pinned host pipeline (LK_HOST_CHUNK_MB at lk_init, lk_set_host_chunk_mb)
     lk::HostStage stage;
-    lk::Arena ws;        // kernel scratch (prepped per-cadence records, per-target stats)
-    lk::Arena staging;   // device mirrors of host buffers for the *_batch (host pointer) entry points, carved per call by
-                         // capi.hip's StagedCall (the chunked LS 'fast' pipeline carves its own double buffers)
+    lk::Arena ws;        // kernel scratch (prepped per-cadence records, per-target stats), carved once per launch through a
+                         // lk::Scratch plan (pld.hip's two launchers carve it by hand)
+    lk::Arena staging;   // device mirrors of host buffers for the *_batch (host pointer) entry points only, carved per call by
+                         // capi.hip's StagedCall (the chunked LS 'fast' pipeline: a lk::Scratch plan of its double buffers)
     // host-pointer pipeline (lk_ls_fast_peaks_batch): copy-in, compute and copy-out streams + the events that order
     // the two halves of the double buffers; created on first use
     hipStream_t s_in = nullptr, s_comp = nullptr, s_out = nullptr;
@@ -117,6 +121,39 @@ inline int take_lds_error(lk_handle *h) {
     h->lds_attr_rc = 0;
     return rc;
 }
+
+// The device scratch of one launch, in one Arena (h->ws; h->staging for the chunked host pipeline).  The launcher declares
+// its buffers in carving order, counts in elements of the pointer's type: buf() is device-only, upload() is also filled from
+// host memory through h->stage at carve time; a false condition declares nothing and leaves the pointer null.  carve()
+// resets the arena, reserves exactly the declared buffers at Arena::alloc's alignment, sets every pointer (non-null, also
+// for a zero-length buffer) and queues the uploads on the stream in declaration order.  No heap allocation per call.
+class Scratch {
+  public:
+    static constexpr int MAX_BUFS = 32;
+    Scratch(lk_handle *h, Arena &arena) : h_(h), arena_(arena) {}
+    template <class T> Scratch &buf(T *&dev, size_t n, bool on = true) { return add(dev, nullptr, n, on); }
+    template <class T> Scratch &upload(T *&dev, const T *host, size_t n, bool on = true) { return add(dev, host, n, on); }
+    int carve(hipStream_t stream);  // a failed reserve or placement (LK_ENOMEM / LK_EHIP) leaves every declared pointer null
+
+  private:
+    struct Buf {
+        void *slot;  // the launcher's device-pointer variable, set through set()
+        void (*set)(void *slot, void *dev);
+        const void *src;  // upload: host source
+        size_t bytes;
+    };
+    template <class T> static void set_ptr(void *slot, void *dev) { *static_cast<T **>(slot) = static_cast<T *>(dev); }
+    template <class T> Scratch &add(T *&dev, const void *src, size_t n, bool on) {
+        dev = nullptr;
+        if (on && n_ < MAX_BUFS) bufs_[n_] = {&dev, set_ptr<T>, src, n * sizeof(T)};
+        if (on) ++n_;  // past MAX_BUFS: counted, carve() refuses
+        return *this;
+    }
+    lk_handle *h_;
+    Arena &arena_;
+    Buf bufs_[MAX_BUFS];
+    int n_ = 0;
+};
 }  // namespace lk
 
 // launchers implemented in the .hip files (device pointers, enqueue on stream, no sync)
@@ -217,10 +254,13 @@ int cube_threshold_mask_launch(lk_handle *h, int B, int ny, int nx, const double
                                hipStream_t stream);
 int pld_corrected_launch(lk_handle *h, int B, int N, const double *y, const double *model, const double *spline, double *out,
                          hipStream_t stream);
+// rebase: t holds absolute times, the launcher works on t - t[first cadence] per target (carved in its own plan)
 int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *y, const double *dy,
                   double f0, double df, int64_t M, int fit_mean, int center_data, int normalization,
                   const double *scale, int oversampling, double *power, hipStream_t stream, double *max_out = nullptr,
-                  int64_t *arg_out = nullptr);
+                  int64_t *arg_out = nullptr, bool rebase = false);
+// out = t - t[first cadence] per target, out of place (device.hip); d_off is the batch's offsets on the device
+int rebase_launch(int B, const int64_t *d_off, const double *t, double *out, hipStream_t stream);
 int lsfastchi2_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *y, const double *dy,
                       double f0, double df, int64_t M, int nterms, int fit_mean, int center_data, int normalization,
                       const double *scale, int oversampling, double *power, hipStream_t stream);

@@ -506,7 +506,6 @@ int ls_chi2_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
     for (int b = 0; b < B; ++b)
         LK_REQUIRE(n_off_host[b + 1] - n_off_host[b] < (int64_t)1 << 30, "target %d too long", b);
 
-    h->ws.reset();
     // irregular single-term grids with few (target, frequency) pairs: slices of the cadences fill the chip (ls_any_kernel)
     int any_slices = 1;
     if (freq && nterms == 1) {
@@ -515,29 +514,32 @@ int ls_chi2_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
         const int64_t threads = (int64_t)B * ((M + 255) / 256) * 256;
         any_slices = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(256, nmax / 64), ((int64_t)1 << 17) / threads));
     }
-    const size_t need = (size_t)(B + 1) * 8 + (size_t)B * sizeof(TargetStats) + ntot * (sizeof(CadHot) + sizeof(CadGen)) +
-                        (size_t)M * 8 + (any_slices > 1 ? (size_t)B * any_slices * 6 * (size_t)M * 8 + 256 : 0) + 4096;
-    int rc = h->ws.reserve(need);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    TargetStats *d_stats = (TargetStats *)h->ws.alloc((size_t)B * sizeof(TargetStats));
-    if (!freq && nterms > LK_FAST_NTERMS) {
-        // 5 .. LK_MAX_NTERMS terms: 6 nterms sums per frequency no longer fit four frequencies per lane — the grid becomes an
-        // explicit array and the one-thread-per-frequency kernel runs (exact sums, ~7 x the cost per pair: rare requests)
-        LK_REQUIRE(B <= 65535, "at most 65535 targets per call with nterms > %d (got %d)", LK_FAST_NTERMS, B);
-        double *d_freq = (double *)h->ws.alloc((size_t)M * 8);
-        LK_REQUIRE(d_freq != nullptr, "workspace exhausted (frequency grid)");
+    // 5 .. LK_MAX_NTERMS terms: 6 nterms sums per frequency no longer fit four frequencies per lane — the grid becomes an
+    // explicit array and the one-thread-per-frequency kernel runs (exact sums, ~7 x the cost per pair: rare requests)
+    const bool make_grid = !freq && nterms > LK_FAST_NTERMS;
+    const bool any_freq = freq || make_grid;
+    LK_REQUIRE(!make_grid || B <= 65535, "at most 65535 targets per call with nterms > %d (got %d)", LK_FAST_NTERMS, B);
+    int64_t *d_off;
+    TargetStats *d_stats;
+    double *d_freq, *d_part;
+    CadAny *d_any;
+    CadHot *d_hot;
+    CadGen *d_gen;
+    Scratch ws(h, h->ws);
+    ws.upload(d_off, n_off_host, B + 1)
+        .buf(d_stats, B)
+        .buf(d_freq, M, make_grid)
+        .buf(d_any, ntot, any_freq)
+        .buf(d_part, (size_t)B * any_slices * 6 * M, any_slices > 1)
+        .buf(d_hot, ntot, !any_freq).buf(d_gen, ntot, !any_freq);
+    if (const int rc = ws.carve(stream)) return rc;
+    if (make_grid) {
         hipLaunchKernelGGL(ls_freq_grid_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, f0, df, M, d_freq);
         freq = d_freq;
-    }
-    {
-        const int rcs = h->stage.copy(d_off, n_off_host, (size_t)(B + 1) * 8, stream);
-        if (rcs) return rcs;
     }
     const int center = (fit_mean || center_data) ? 1 : 0;
 
     if (freq) {
-        CadAny *d_any = (CadAny *)h->ws.alloc(ntot * sizeof(CadAny));
         hipLaunchKernelGGL(ls_prep_kernel, dim3(B), dim3(256), 0, stream, t, y, dy, d_off, center, 0.0, 1,
                            (CadHot *)nullptr, (CadGen *)nullptr, d_any, d_stats);
         dim3 grid((unsigned)((M + 255) / 256), (unsigned)B);
@@ -546,8 +548,6 @@ int ls_chi2_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
                        normalization, fit_mean, scale, power)
         switch (nterms) {
             case 1: {
-                double *d_part = any_slices > 1 ? (double *)h->ws.alloc((size_t)B * any_slices * 6 * (size_t)M * 8) : nullptr;
-                LK_REQUIRE(any_slices == 1 || d_part != nullptr, "workspace exhausted (partial sums)");
                 LK_REQUIRE(B <= 65535, "at most 65535 targets per call on an irregular frequency grid (got %d)", B);
                 hipLaunchKernelGGL(ls_any_kernel, dim3(grid.x, grid.y, (unsigned)any_slices), dim3(256), 0, stream, d_any, d_off,
                                    d_stats, freq, M, normalization, fit_mean, scale, power, any_slices, d_part);
@@ -566,8 +566,6 @@ int ls_chi2_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
         }
 #undef LK_CHI2_ANY
     } else if (nterms > 1) {
-        CadHot *d_hot = (CadHot *)h->ws.alloc(ntot * sizeof(CadHot));
-        CadGen *d_gen = (CadGen *)h->ws.alloc(ntot * sizeof(CadGen));
         const int F = LS_CHI2_F;
         hipLaunchKernelGGL(ls_prep_kernel, dim3(B), dim3(256), 0, stream, t, y, dy, d_off, center, df, F, d_hot,
                            d_gen, (CadAny *)nullptr, d_stats);
@@ -584,8 +582,6 @@ int ls_chi2_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
         }
 #undef LK_CHI2_GRID
     } else {
-        CadHot *d_hot = (CadHot *)h->ws.alloc(ntot * sizeof(CadHot));
-        CadGen *d_gen = (CadGen *)h->ws.alloc(ntot * sizeof(CadGen));
         const int F = LS_F;  // 16 frequencies per lane (8, 10, 12 measured slower; 32 would need 384 accumulator VGPRs)
         hipLaunchKernelGGL(ls_prep_kernel, dim3(B), dim3(256), 0, stream, t, y, dy, d_off, center, df, F, d_hot,
                            d_gen, (CadAny *)nullptr, d_stats);

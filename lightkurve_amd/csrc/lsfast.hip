@@ -1524,11 +1524,12 @@ static int ilog2_ceil(long long v) {
 }
 
 // max_out / arg_out (both or neither): per-target nanmax / nanargmax of the spectra, from the fused kernel's partials where
-// that kernel runs, by argmax_launch over `power` otherwise.
+// that kernel runs, by argmax_launch over `power` otherwise.  rebase: `t` holds absolute times; the launcher works on its own
+// copy, t - t[first cadence] per target.
 int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *y, const double *dy,
                   double f0, double df, int64_t M, int fit_mean, int center_data, int normalization,
                   const double *scale, int oversampling, double *power, hipStream_t stream, double *max_out,
-                  int64_t *arg_out) {
+                  int64_t *arg_out, bool rebase) {
     LK_REQUIRE(B >= 0 && n_off_host != nullptr, "bad batch description");
     LK_REQUIRE(M >= 0, "M must be >= 0");
     if (B == 0 || M == 0) return LK_OK;
@@ -1568,24 +1569,27 @@ int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *
     const int ntab256 = (nfft + SPREAD_WW - 1) / SPREAD_WW + 3;
     const int ntab16 = (m2 >= 8 && m2 <= 10) ? (int)((((size_t)256 << m2) >> 4) + 3) : 0;
     const int ntab_max = std::max(ntab256, ntab16);
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(B + 1) * 8 + (size_t)B * sizeof(FastStats) + 512 +
-                           (size_t)Bc * 3 * nfft * 16 * 2 + (size_t)Bc * 3 * M * 16 + (size_t)B * 16 +
-                           (size_t)B * 4 * ntab_max * 4 + (size_t)(B + 1) * nparts_max * sizeof(PeakPart) + 16384);
+    int64_t *d_off;
+    FastStats *d_stats;
+    double2 *d_grids, *d_spec, *d_grids2;
+    int *d_rows, *d_plan, *d_tab;
+    PeakPart *d_peaks;
+    double *d_trel;
+    Scratch ws(h, h->ws);
+    ws.upload(d_off, n_off_host, B + 1)
+        .buf(d_stats, B)
+        .buf(d_grids, (size_t)Bc * 3 * nfft)
+        .buf(d_spec, (size_t)Bc * 3 * M, !fused)
+        .buf(d_grids2, (size_t)Bc * 3 * nfft, fused)
+        .buf(d_rows, (size_t)B * 4).buf(d_plan, 16)
+        .buf(d_tab, (size_t)B * 4 * ntab_max, reg_path)
+        .buf(d_peaks, (size_t)B * nparts_max, fused && max_out)
+        .buf(d_trel, n_off_host[B], rebase);
+    int rc = ws.carve(stream);
+    if (!rc && rebase) rc = rebase_launch(B, d_off, t, d_trel, stream);
     if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    FastStats *d_stats = (FastStats *)h->ws.alloc((size_t)B * sizeof(FastStats));
-    double2 *d_grids = (double2 *)h->ws.alloc((size_t)Bc * 3 * nfft * 16);
-    double2 *d_spec = fused ? nullptr : (double2 *)h->ws.alloc((size_t)Bc * 3 * M * 16);
-    rc = h->stage.copy(d_off, n_off_host, (size_t)(B + 1) * 8, stream);
-    if (rc) return rc;
+    if (rebase) t = d_trel;
     const int tw = tile_width(m1, m2);
-    double2 *d_grids2 = fused ? (double2 *)h->ws.alloc((size_t)Bc * 3 * nfft * 16) : nullptr;
-    LK_REQUIRE(!fused || d_grids2 != nullptr, "workspace exhausted");
-    int *d_rows = (int *)h->ws.alloc((size_t)B * 4 * 4);
-    int *d_plan = (int *)h->ws.alloc(64);
-    int *d_tab = reg_path ? (int *)h->ws.alloc((size_t)B * 4 * ntab_max * 4) : nullptr;
-    PeakPart *d_peaks = (fused && max_out) ? (PeakPart *)h->ws.alloc((size_t)B * nparts_max * sizeof(PeakPart)) : nullptr;
     hipLaunchKernelGGL(lsf_prep_kernel, dim3(B), dim3(PREP_NT), 0, stream, t, y, dy, d_off, (fit_mean || center_data) ? 1 : 0,
                        d_stats, df, nfft, m2, d_rows);
     // ---- plan: the pruned column kernel applies when every grid of every target keeps its samples in the first
@@ -1744,16 +1748,12 @@ int lsfastchi2_launch(lk_handle *h, int B, const int64_t *n_off_host, const doub
     const int NG = 3 * nterms;
     const size_t per_target = (size_t)NG * nfft * 16;
     const int Bc = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, ((size_t)2 << 30) / per_target));
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(B + 1) * 8 + (size_t)B * sizeof(FastStats) + 512 +
-                           (size_t)Bc * per_target + (size_t)Bc * NG * M * 16 + 16384);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    FastStats *d_stats = (FastStats *)h->ws.alloc((size_t)B * sizeof(FastStats));
-    double2 *d_grids = (double2 *)h->ws.alloc((size_t)Bc * per_target);
-    double2 *d_spec = (double2 *)h->ws.alloc((size_t)Bc * NG * M * 16);
-    rc = h->stage.copy(d_off, n_off_host, (size_t)(B + 1) * 8, stream);
-    if (rc) return rc;
+    int64_t *d_off;
+    FastStats *d_stats;
+    double2 *d_grids, *d_spec;
+    if (const int rc = Scratch(h, h->ws).upload(d_off, n_off_host, B + 1).buf(d_stats, B).buf(d_grids, (size_t)Bc * NG * nfft)
+            .buf(d_spec, (size_t)Bc * NG * M).carve(stream))
+        return rc;
     hipLaunchKernelGGL(lsf_prep_kernel, dim3(B), dim3(PREP_NT), 0, stream, t, y, dy, d_off, (fit_mean || center_data) ? 1 : 0,
                        d_stats, df, nfft, m2, (int *)nullptr);
     const bool reg_path = m1 >= 4 && m1 <= 10 && m2 >= 4 && m2 <= 10;

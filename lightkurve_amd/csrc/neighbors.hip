@@ -197,12 +197,8 @@ int underfit_neighbors_launch(lk_handle *h, int B, int N, const double *flux, in
     LK_REQUIRE(flux && metric, "NULL buffer");
     LK_REQUIRE(M == 0 || neighbors != nullptr, "neighbors is NULL with M=%d", M);
     const int pitch = (n + UF_STEP - 1) / UF_STEP * UF_STEP;
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)B * pitch * 8 + (size_t)B * 8 + 1024);
-    if (rc) return rc;
-    double *d_z = (double *)h->ws.alloc((size_t)B * pitch * 8);
-    double *d_g = (double *)h->ws.alloc((size_t)B * 8);
-    LK_REQUIRE(d_z && d_g, "workspace exhausted");
+    double *d_z, *d_g;
+    if (const int rc = Scratch(h, h->ws).buf(d_z, (size_t)B * pitch).buf(d_g, B).carve(stream)) return rc;
     const double wgn = 0.0007 + 0.8083 * std::pow((double)n, -0.5023);
     const double scale = std::log(2.0 / 0.95 - 1.0) / wgn;
     if (M > 0)

@@ -105,12 +105,11 @@ int pg_logmedian_launch(lk_handle *h, int B, int64_t M, const double *power, int
     for (int64_t j = 0; j < M; ++j)
         LK_REQUIRE(klo_host[j] >= 0 && khi_host[j] < K + (K == 0) && klo_host[j] <= khi_host[j] + 1,
                    "frequency %lld lists windows [%d, %d] outside [0, K)", (long long)j, klo_host[j], khi_host[j]);
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(2 * K + 2 * M) * 4 + (size_t)B * (size_t)(K + 1) * 8 + 4096);
-    if (rc) return rc;
-    int *d_lo = (int *)h->ws.alloc((size_t)(K + 1) * 4), *d_hi = (int *)h->ws.alloc((size_t)(K + 1) * 4);
-    int *d_klo = (int *)h->ws.alloc((size_t)M * 4), *d_khi = (int *)h->ws.alloc((size_t)M * 4);
-    double *d_med = (double *)h->ws.alloc((size_t)B * (size_t)(K + 1) * 8);
+    int *d_lo, *d_hi, *d_klo, *d_khi;
+    double *d_med;
+    if (const int rc = Scratch(h, h->ws).buf(d_lo, K + 1).buf(d_hi, K + 1).buf(d_klo, M).buf(d_khi, M)
+            .buf(d_med, (size_t)B * (size_t)(K + 1)).carve(stream))
+        return rc;
     if (K) {
         LK_HIP_CHECK(hipMemcpyAsync(d_lo, win_lo_host, (size_t)K * 4, hipMemcpyHostToDevice, stream));
         LK_HIP_CHECK(hipMemcpyAsync(d_hi, win_hi_host, (size_t)K * 4, hipMemcpyHostToDevice, stream));
@@ -137,11 +136,9 @@ int pg_boxsmooth_launch(lk_handle *h, int B, int64_t M, const double *power, con
     double ksum = 0.0;
     for (int i = 0; i < nk; ++i) ksum += taps_host[i];
     LK_REQUIRE(ksum > 1e-8, "The kernel can't be normalized, because its sum is close to zero.");
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)nk * 8 + (size_t)B * 4 + 4096);
-    if (rc) return rc;
-    double *d_taps = (double *)h->ws.alloc((size_t)nk * 8);
-    int *d_flag = (int *)h->ws.alloc((size_t)B * 4);
+    double *d_taps;
+    int *d_flag;
+    if (const int rc = Scratch(h, h->ws).buf(d_taps, nk).buf(d_flag, B).carve(stream)) return rc;
     LK_HIP_CHECK(hipMemcpyAsync(d_taps, taps_host, (size_t)nk * 8, hipMemcpyHostToDevice, stream));
     LK_HIP_CHECK(hipStreamSynchronize(stream));
     hipLaunchKernelGGL(pg_has_nan_kernel, dim3(B), dim3(256), 0, stream, power, M, d_flag);
@@ -245,10 +242,8 @@ int pg_acf2d_launch(lk_handle *h, int B, int64_t M, const double *power, int n_w
     for (int k = 0; k < n_win; ++k)
         LK_REQUIRE(win_start_host[k] >= 0 && (int64_t)win_start_host[k] + W <= M, "window %d = [%d, %d) outside [0, M)", k,
                    win_start_host[k], win_start_host[k] + W);
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)n_win * 4 + 4096);
-    if (rc) return rc;
-    int *d_start = (int *)h->ws.alloc((size_t)n_win * 4);
+    int *d_start;
+    if (const int rc = Scratch(h, h->ws).buf(d_start, n_win).carve(stream)) return rc;
     LK_HIP_CHECK(hipMemcpyAsync(d_start, win_start_host, (size_t)n_win * 4, hipMemcpyHostToDevice, stream));
     LK_HIP_CHECK(hipStreamSynchronize(stream));
     {

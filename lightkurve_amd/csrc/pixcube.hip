@@ -406,10 +406,8 @@ int cube_aperture_launch(lk_handle *h, int B, int N, int npix, const float *flux
     LK_REQUIRE(flux && flux_err && mask && flux_out && err_out && keep_out && kept_host, "NULL buffer");
     LK_REQUIRE(mask_stride == 0 || mask_stride == npix, "mask_stride must be 0 (one mask for the batch) or npix");
     LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)2 * B * 8 + 4096);
-    if (rc) return rc;
-    unsigned long long *d_cnt = (unsigned long long *)h->ws.alloc((size_t)2 * B * 8);
+    unsigned long long *d_cnt;
+    if (const int rc = Scratch(h, h->ws).buf(d_cnt, (size_t)2 * B).carve(stream)) return rc;
     LK_HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t)2 * B * 8, stream));
     const int W = std::min(npix, AP_WMAX), pitch = W | 1;
     const size_t lds = (size_t)2 * AP_T * pitch * 4 + (size_t)((W + 15) & ~15);
@@ -494,18 +492,15 @@ int pld_gather_launch(lk_handle *h, int B, int N, int npix, int n, const float *
     for (size_t i = 0; i < n_bi; ++i)
         LK_REQUIRE(bkg_idx_host[i] >= 0 && bkg_idx_host[i] < npix, "bkg_idx[%zu] = %d is not a pixel of the cutout", i, bkg_idx_host[i]);
     const size_t nk = knots_out ? (size_t)n_inner : 0;
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)B * n * 4 + (n_pi + n_bi) * 4 + nk * 12 + 8 * 256 + 4096);
-    if (rc) return rc;
-    int *d_src = (int *)h->ws.alloc((size_t)B * n * 4);
-    int *d_pi = n_pi ? (int *)h->ws.alloc(n_pi * 4) : nullptr, *d_bi = n_bi ? (int *)h->ws.alloc(n_bi * 4) : nullptr;
-    int *d_klo = nk ? (int *)h->ws.alloc(nk * 4) : nullptr;
-    double *d_kg = nk ? (double *)h->ws.alloc(nk * 8) : nullptr;
-    int *d_flags = (int *)h->ws.alloc(4);
-    if (n_pi && (rc = h->stage.copy(d_pi, pld_idx_host, n_pi * 4, stream))) return rc;
-    if (n_bi && (rc = h->stage.copy(d_bi, bkg_idx_host, n_bi * 4, stream))) return rc;
-    if (nk && (rc = h->stage.copy(d_klo, knot_lo_host, nk * 4, stream))) return rc;
-    if (nk && (rc = h->stage.copy(d_kg, knot_g_host, nk * 8, stream))) return rc;
+    int *d_src, *d_pi, *d_bi, *d_klo, *d_flags;
+    double *d_kg;
+    Scratch ws(h, h->ws);
+    ws.buf(d_src, (size_t)B * n)
+        .upload(d_pi, pld_idx_host, n_pi, n_pi != 0)
+        .upload(d_bi, bkg_idx_host, n_bi, n_bi != 0)
+        .upload(d_klo, knot_lo_host, nk, nk != 0).upload(d_kg, knot_g_host, nk, nk != 0)
+        .buf(d_flags, 1);
+    if (const int rc = ws.carve(stream)) return rc;
     LK_HIP_CHECK(hipMemsetAsync(d_flags, 0, 4, stream));
     hipLaunchKernelGGL(cube_compact_kernel, dim3(B), dim3(256), 0, stream, keep, time, flux32, err32, N, n, d_src, t_out, y_out,
                        err_out, lcf_out, n_inner, d_klo, d_kg, knots_out, d_flags);

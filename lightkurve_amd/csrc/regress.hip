@@ -1074,16 +1074,10 @@ int sigma_clip_launch(lk_handle *h, int B, const int64_t *n_off_host, const doub
     LK_REQUIRE(y && outlier, "NULL buffer");
     LK_REQUIRE(maxiters >= 0, "maxiters must be >= 0");
     const size_t ntot = (size_t)n_off_host[B];
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(B + 1) * 8 + ntot * 9 + 3 * 256 + 4096);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    double *d_zero = (double *)h->ws.alloc(ntot * 8);
-    uint8_t *d_flag = (uint8_t *)h->ws.alloc(ntot);
-    {
-        const int rcs = h->stage.copy(d_off, n_off_host, (size_t)(B + 1) * 8, stream);
-        if (rcs) return rcs;
-    }
+    int64_t *d_off;
+    double *d_zero;
+    uint8_t *d_flag;
+    if (const int rc = Scratch(h, h->ws).upload(d_off, n_off_host, B + 1).buf(d_zero, ntot).buf(d_flag, ntot).carve(stream)) return rc;
     LK_HIP_CHECK(hipMemsetAsync(d_zero, 0, ntot * 8, stream));
     LK_HIP_CHECK(hipMemsetAsync(outlier, 0, ntot, stream));
     hipLaunchKernelGGL(clip_kernel, dim3(B), dim3(1024), 0, stream, y, d_zero, d_off, sigma, maxiters, d_flag, outlier);
@@ -1109,26 +1103,22 @@ int regress_launch(lk_handle *h, int B, const int64_t *n_off_host, int K, const 
     }
     const size_t ntot = (size_t)n_off_host[B];
     const int KB = (K + 1 + GR_BLK - 1) / GR_BLK, Kp = KB * GR_BLK;
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(B + 1) * 8 + (size_t)B * Kp * Kp * 8 + (size_t)B * K * (K + 1) * 8 * (w_cov ? 2 : 1) +
-                           ntot + (size_t)B * 4 + (size_t)B * 4 * (256 + 1) + 4096);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    double *d_G = (double *)h->ws.alloc((size_t)B * Kp * Kp * 8);
-    double *d_A = (double *)h->ws.alloc((size_t)B * K * (K + 1) * 8 * (w_cov ? 2 : 1));  // K x 2K per target for the inverse
-    uint8_t *d_flag = (uint8_t *)h->ws.alloc(ntot);
-    {
-        const int rcs = h->stage.copy(d_off, n_off_host, (size_t)(B + 1) * 8, stream);
-        if (rcs) return rcs;
-    }
-    LK_HIP_CHECK(hipMemsetAsync(outl, 0, ntot, stream));
-    // per-target convergence flags of the clip loop: a pass that adds no outlier ends the target's loop
-    int *d_done = (int *)h->ws.alloc((size_t)B * 4);
-    // the cadences each clip adds to the outlier set, for the DELTA Gram of the next pass
+    // d_done: per-target convergence flags of the clip loop, a pass that adds no outlier ends the target's loop;
+    // d_newcnt / d_newidx: the cadences each clip adds to the outlier set, for the DELTA Gram of the next pass
     constexpr int kNewCap = 256;
-    int *d_newcnt = (int *)h->ws.alloc((size_t)B * 4);
-    int *d_newidx = (int *)h->ws.alloc((size_t)B * kNewCap * 4);
-    LK_REQUIRE(d_done && d_newcnt && d_newidx, "workspace exhausted");
+    int64_t *d_off;
+    double *d_G, *d_A;
+    uint8_t *d_flag;
+    int *d_done, *d_newcnt, *d_newidx;
+    Scratch ws(h, h->ws);
+    ws.upload(d_off, n_off_host, B + 1)
+        .buf(d_G, (size_t)B * Kp * Kp)
+        .buf(d_A, (size_t)B * K * (K + 1) * (w_cov ? 2 : 1))  // K x 2K per target for the inverse
+        .buf(d_flag, ntot)
+        .buf(d_done, B)
+        .buf(d_newcnt, B).buf(d_newidx, (size_t)B * kNewCap);
+    if (const int rc = ws.carve(stream)) return rc;
+    LK_HIP_CHECK(hipMemsetAsync(outl, 0, ntot, stream));
     LK_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)B * 4, stream));
     const int nblk = KB * (KB + 1) / 2;
     for (int it = 0; it < niters; ++it) {
@@ -1435,19 +1425,20 @@ int regress_shared_launch(lk_handle *h, int B, int N, int K, const double *X, co
     int S = 1, slice = N;
     shared_split(N, &S, &slice);
     const int ntb = (B + SH_TB - 1) / SH_TB, npairs = K * (K + 1) / 2, T = (npairs + 15) / 16 + (K + 15) / 16, NC = 16 * T;
-    const size_t part_bytes = (size_t)ntb * SH_TB * S * NC * 8;
-    h->ws.reset();
-    int rc = h->ws.reserve((size_t)(B + 1) * 8 + (size_t)B * Kp * Kp * 8 + (size_t)B * K * (K + 1) * 8 * (w_cov ? 2 : 1) + ntot +
-                           (size_t)B * 4 + part_bytes + 4 + 8 * 256 + 4096);
-    if (rc) return rc;
-    int64_t *d_off = (int64_t *)h->ws.alloc((size_t)(B + 1) * 8);
-    double *d_G = (double *)h->ws.alloc((size_t)B * Kp * Kp * 8);
-    double *d_A = (double *)h->ws.alloc((size_t)B * K * (K + 1) * 8 * (w_cov ? 2 : 1));
-    uint8_t *d_flag = (uint8_t *)h->ws.alloc(ntot);
-    int *d_done = (int *)h->ws.alloc((size_t)B * 4);
-    double *d_part = (double *)h->ws.alloc(part_bytes);
-    int *d_bad = (int *)h->ws.alloc(4);
-    LK_REQUIRE(d_off && d_G && d_A && d_flag && d_done && d_part && d_bad, "workspace exhausted");
+    std::vector<int64_t> off((size_t)B + 1);
+    for (int b = 0; b <= B; ++b) off[b] = (int64_t)b * N;
+    int64_t *d_off;
+    double *d_G, *d_A, *d_part;
+    uint8_t *d_flag;
+    int *d_done, *d_bad;
+    Scratch ws(h, h->ws);
+    ws.upload(d_off, off.data(), B + 1)
+        .buf(d_G, (size_t)B * Kp * Kp)
+        .buf(d_A, (size_t)B * K * (K + 1) * (w_cov ? 2 : 1))
+        .buf(d_flag, ntot).buf(d_done, B)
+        .buf(d_part, (size_t)ntb * SH_TB * S * NC)
+        .buf(d_bad, 1);
+    if (const int rc = ws.carve(stream)) return rc;
     // the input check first: its answer is back before the fit is queued
     LK_HIP_CHECK(hipMemsetAsync(d_bad, 0, 4, stream));
     {
@@ -1459,12 +1450,6 @@ int regress_shared_launch(lk_handle *h, int B, int N, int K, const double *X, co
         LK_HIP_CHECK(hipStreamSynchronize(stream));
         LK_REQUIRE(!(bad & 1), "Input light curve has NaNs in the flux");
         LK_REQUIRE(!(bad & 2), "Input light curve has NaN, infinite, zero or negative flux errors");
-    }
-    {
-        std::vector<int64_t> off((size_t)B + 1);
-        for (int b = 0; b <= B; ++b) off[b] = (int64_t)b * N;
-        const int rcs = h->stage.copy(d_off, off.data(), (size_t)(B + 1) * 8, stream);
-        if (rcs) return rcs;
     }
     LK_HIP_CHECK(hipMemsetAsync(outl, 0, ntot, stream));
     LK_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)B * 4, stream));
