@@ -498,8 +498,9 @@ __host__ __device__ constexpr int brev_c(int x, int bits) {
 }
 
 // in-place radix-2 decimation-in-frequency FFT of 2^L points in registers, kernel e^{+2 pi i nk/2^L};
-// the result is left in bit-reversed order: v[p] = X[brev(p)]
-template <int L>
+// the result is left in bit-reversed order: v[p] = X[brev(p)].  UPPER_ZERO: the inputs v[2^(L-1) ..] are known zeros and are
+// not read — the first stage is a + 0 = a and (a - 0) w = a w (the same values; only an exact zero may change its sign)
+template <int L, bool UPPER_ZERO = false>
 __device__ __forceinline__ void reg_fft(double2 (&v)[1 << L]) {
 #pragma unroll
     for (int s = L; s >= 1; --s) {
@@ -508,9 +509,10 @@ __device__ __forceinline__ void reg_fft(double2 (&v)[1 << L]) {
         for (int g = 0; g < (1 << L); g += (1 << s)) {
 #pragma unroll
             for (int k = 0; k < half; ++k) {
-                const double2 a = v[g + k], b = v[g + k + half];
-                v[g + k] = make_double2(a.x + b.x, a.y + b.y);
-                const double dx = a.x - b.x, dy = a.y - b.y;
+                const bool bz = UPPER_ZERO && s == L;
+                const double2 a = v[g + k], b = bz ? make_double2(0.0, 0.0) : v[g + k + half];
+                if (!bz) v[g + k] = make_double2(a.x + b.x, a.y + b.y);
+                const double dx = bz ? a.x : a.x - b.x, dy = bz ? a.y : a.y - b.y;
                 const int ti = k * (32 >> s);  // e^{2 pi i k / 2^s} as a 32nd root
                 if (ti == 0)
                     v[g + k + half] = make_double2(dx, dy);
@@ -628,7 +630,9 @@ __global__ __launch_bounds__(256) void fft_cols_reg_kernel(double2 *__restrict__
 // holds 4.  That is what this kernel is for — 16-column tiles make the intermediate's [c / 16][k1][c % 16] layout
 // deliver 256-B runs per row to this kernel's loads and RT x 256-B runs to the row kernel (4 x the run length of the
 // full-length kernel above), and the workgroups are small enough for 2 waves per SIMD.  The input column is loaded
-// once and kept in registers over the Q passes; rows keep their natural order k1 = Q q + s.
+// once and kept in registers over the Q passes; rows keep their natural order k1 = Q q + s.  A grid with rows_used <= P / 2 (the
+// two df grids whenever the 2 df grid decided P) takes a second copy of the pass loop that neither pre-twiddles the zero half of
+// the input nor runs the first butterfly stage over it (reg_fft<LA, true>): 550 fp64 instructions per pass against 646 at LP = 8.
 constexpr int PRUNED_CT = 16;
 
 constexpr int LSF_CHUNK_HALF_GB = 3;  // bytes of grids per chunk, in units of 2^29 (1.5 GiB = 60 targets at Nfft = 2^19)
@@ -662,6 +666,10 @@ __global__ __launch_bounds__(PRUNED_CT * (1 << ((LP + 1) / 2)), 2) void fft_cols
     const int f = tid % CT, jk = tid / CT;  // column of the tile; j (phase 1) or ka (phase 2)
     const bool p1 = jk < Bq, p2 = jk < A;
     const double invN1 = 1.0 / (double)N1, invN = 1.0 / (double)((size_t)1 << (m1 + m2));
+    // ru <= P / 2 (the df grids of a batch whose 2 df grid picked P): rows i Bq + j, i >= A / 2, hold no samples — the upper half
+    // of xin is not loaded (r < ru fails) nor pre-twiddled, and the first butterfly stage knows it is zero.  One branch per
+    // workgroup.
+    const bool short_in = ru <= P / 2;
     double2 xin[A];
     if (tab16 != nullptr && rows_used[lbt * 4 + 3]) {
         double2 *acc = lds2;  // [ru][CT]: ru <= P rows of 256 B fit the exchange tile
@@ -766,49 +774,57 @@ __global__ __launch_bounds__(PRUNED_CT * (1 << ((LP + 1) / 2)), 2) void fft_cols
     const double2 wc = root((double)(c0 + f) * invN), stepc = root((double)((long long)(c0 + f) * Q * A) * invN);
     double2 wjs = make_double2(1.0, 0.0), wqs = wjs;                                  // (W_N1^j)^s, (W_N1^Bq)^s
     double2 wout = root((double)((long long)(c0 + f) * Q * jk) * invN);               // W_N^{c (Q ka + s)}
-    for (int s = 0; s < Q; ++s) {
-        if (p1) {
-            double2 v[A];
-            if (s == 0) {
+    auto passes = [&](auto short_c) {
+        constexpr bool SHORT = decltype(short_c)::value;
+        constexpr int AI = SHORT ? A / 2 : A;  // inputs that can be non-zero
+        for (int s = 0; s < Q; ++s) {
+            if (p1) {
+                double2 v[A];
+                if (s == 0) {
 #pragma unroll
-                for (int i = 0; i < A; ++i) v[i] = xin[i];
-            } else {
-                double2 w = wjs;
+                    for (int i = 0; i < AI; ++i) v[i] = xin[i];
+                } else {
+                    double2 w = wjs;
 #pragma unroll
-                for (int i = 0; i < A; ++i) {
-                    v[i] = cmul(xin[i], w);
-                    w = cmul(w, wqs);
+                    for (int i = 0; i < AI; ++i) {
+                        v[i] = cmul(xin[i], w);
+                        if (i + 1 < AI) w = cmul(w, wqs);
+                    }
+                }
+                reg_fft<LA, SHORT>(v);
+                double2 w = make_double2(1.0, 0.0);
+                double2 *row = lds2 + (size_t)f * FST + jk;
+#pragma unroll
+                for (int ka = 0; ka < A; ++ka) {
+                    row[ka * LDT] = cmul(v[brev_c(ka, LA)], w);
+                    w = cmul(w, tw_j);
                 }
             }
-            reg_fft<LA>(v);
-            double2 w = make_double2(1.0, 0.0);
-            double2 *row = lds2 + (size_t)f * FST + jk;
+            __syncthreads();
+            if (p2) {
+                const double2 *row = lds2 + (size_t)f * FST + (size_t)jk * LDT;
+                double2 u[Bq];
 #pragma unroll
-            for (int ka = 0; ka < A; ++ka) {
-                row[ka * LDT] = cmul(v[brev_c(ka, LA)], w);
-                w = cmul(w, tw_j);
+                for (int j = 0; j < Bq; ++j) u[j] = row[j];
+                reg_fft<LB>(u);
+                double2 w = wout;
+#pragma unroll
+                for (int kb = 0; kb < Bq; ++kb) {
+                    const int q = jk + A * kb;
+                    O[(size_t)(Q * q + s) * CT + f] = cmul(u[brev_c(kb, LB)], w);
+                    w = cmul(w, stepc);
+                }
             }
+            wjs = cmul(wjs, wj);
+            wqs = cmul(wqs, wq);
+            wout = cmul(wout, wc);
+            __syncthreads();
         }
-        __syncthreads();
-        if (p2) {
-            const double2 *row = lds2 + (size_t)f * FST + (size_t)jk * LDT;
-            double2 u[Bq];
-#pragma unroll
-            for (int j = 0; j < Bq; ++j) u[j] = row[j];
-            reg_fft<LB>(u);
-            double2 w = wout;
-#pragma unroll
-            for (int kb = 0; kb < Bq; ++kb) {
-                const int q = jk + A * kb;
-                O[(size_t)(Q * q + s) * CT + f] = cmul(u[brev_c(kb, LB)], w);
-                w = cmul(w, stepc);
-            }
-        }
-        wjs = cmul(wjs, wj);
-        wqs = cmul(wqs, wq);
-        wout = cmul(wout, wc);
-        __syncthreads();
-    }
+    };
+    if (short_in)
+        passes(std::true_type{});
+    else
+        passes(std::false_type{});
 }
 
 // step 2 (register version): RT rows r0..r0+RT-1, outputs k = k1 + N1 k2 < nkeep kept
@@ -949,7 +965,8 @@ __global__ __launch_bounds__(512) void fft_rows_power_kernel(const double2 *__re
 //   phase 2  X[ka + 16 kb] = sum_{j < 32} T[ka][j] W_32^{j kb} is needed for kb < 8 only (k2 < 128 covers M <= 128 N1):
 //            a PAIR of threads (ka, e) splits the sum by the parity of j — thread e runs two 8-point FFTs over
 //            j = j1 + 4 j2, j1 = e, e + 2, combines them with constant 32nd roots, and the two partial sums meet through
-//            one DPP row rotation (lane ^ 8); thread e keeps kb = 4 e .. 4 e + 3 of each grid for the closed form.
+//            one DPP row rotation (lane ^ 8); thread e keeps kb = e, e + 2, e + 4, e + 6 of each grid for the closed form,
+//            as far as M reaches (see nq below).
 // No thread ever holds more than 16 points, so the next grid's 64 KB are requested the moment a grid's points sit in LDS,
 // under phase 2.  Loads are non-temporal (each byte is read once), targets go last-written first (the tail of what step 1
 // has just written is still in the Infinity Cache).  Measured alone on an 85-target chunk: 430 us = 5.1 TB/s against 560-610 us for the generic kernel
@@ -1006,6 +1023,12 @@ __global__ __launch_bounds__(Rows512::NT, 2) void fft_rows512_power_kernel(
         step4 = make_double2(c, s);
     }
     double2 keep[3][4];
+    // kept outputs: thread (ka, e) owns kb = 2 q + e, q < 4, i.e. k2 = ka + 16 e + 32 q — the pair shares every q evenly.  Only
+    // k2 < ceil(M / N1) is wanted, and a wave holds four consecutive ka, so it needs the first nq values of q only (wave-uniform;
+    // at M = 1e5, N1 = 1024: 98 rows of k2 -> four q in wave 0 of a workgroup, three in the others): P[kb], the exchange and the
+    // closed form are skipped for the rest
+    const int k2need = (int)((M + ((int64_t)1 << m1) - 1) >> m1);
+    const int nq = __builtin_amdgcn_readfirstlane(min(4, (k2need - 4 * (tid >> 6) + 31) >> 5));
     double *row1 = tile512 + f1 * SF + j;
     const double *row2 = tile512 + f2 * SF + ka * SK + e;
     // one grid: the 16 loaded points of v -> keep[G]; `refill` runs once v's last LDS write has been issued (v is dead)
@@ -1077,9 +1100,11 @@ __global__ __launch_bounds__(Rows512::NT, 2) void fft_rows512_power_kernel(
         };
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const double2 plo = pval(q), phi = pval(q + 4);
-            const double2 mine = e ? phi : plo, send = e ? plo : phi;
-            keep[G][q] = make_double2(mine.x + dpp_ror8(send.x), mine.y + dpp_ror8(send.y));
+            if (q < nq) {  // (wave-uniform: nobody in this wave wants kb >= 2 nq)
+                const double2 pev = pval(2 * q), pod = pval(2 * q + 1);
+                const double2 mine = e ? pod : pev, send = e ? pev : pod;
+                keep[G][q] = make_double2(mine.x + dpp_ror8(send.x), mine.y + dpp_ror8(send.y));
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -1112,15 +1137,15 @@ __global__ __launch_bounds__(Rows512::NT, 2) void fft_rows512_power_kernel(
             double ph_c = 1.0, ph_s = 0.0, st_c = 1.0, st_s = 0.0;
             if (st.t0 != 0.0) {
                 // e^{2 pi i t0 f} for this thread's outputs: one sincos for the first and one for the step between consecutive
-                // ones (a rotation by 2 pi t0 df 16 N1), the 2f phase by the double-angle formulas
-                const long long kfirst = (long long)k1 + ((long long)(ka + 64 * e) << m1);
+                // ones (a rotation by 2 pi t0 df 32 N1), the 2f phase by the double-angle formulas
+                const long long kfirst = (long long)k1 + ((long long)(ka + 16 * e) << m1);
                 sincos(twopi * st.t0 * (f0 + df * (double)kfirst), &ph_s, &ph_c);
-                sincos(twopi * st.t0 * (df * (double)((long long)16 << m1)), &st_s, &st_c);
+                sincos(twopi * st.t0 * (df * (double)((long long)32 << m1)), &st_s, &st_c);
             }
             // a rolled loop (the closed form is ~350 instructions per output): the kept outputs rotate through slot 0
 #pragma unroll 1
-            for (int q = 0; q < 4; ++q) {
-                const long long k = (long long)k1 + ((long long)(ka + 16 * (4 * e + q)) << m1);
+            for (int q = 0; q < nq; ++q) {
+                const long long k = (long long)k1 + ((long long)(ka + 16 * (2 * q + e)) << m1);
                 if (k < M) {
                     double2 a = keep[0][0], bq = keep[1][0], c2 = keep[2][0];
                     if (st.t0 != 0.0) {

@@ -9,9 +9,9 @@ C=lightkurve_amd/csrc
 make -s -C $C
 mkdir -p build/ab build/obj
 base=$(basename $src .hip)
-fp=""; case $base in bls|pgsmooth) fp="-ffp-contract=off";; esac
+fp=""; case $base in bls|pgsmooth|pixcube) fp="-ffp-contract=off";; esac
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result $fp $extra -c $C/$base.hip -o build/obj/$name.$base.o
-objs=""; for o in capi ls lsfast bls regress flatten pld pgsmooth fold ingest device; do
+objs=""; for o in capi ls lsfast bls regress flatten pld pgsmooth fold ingest device pixcube neighbors overfit; do
   if [ $o = $base ]; then objs="$objs build/obj/$name.$base.o"; else objs="$objs $C/$o.o"; fi; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/ab/$name.so $objs
 echo build/ab/$name.so
