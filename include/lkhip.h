@@ -441,6 +441,11 @@ int lk_regress_shared_batch_dev(lk_handle *h, int B, int N, int K, const double 
  * numpy.median(flux_err[b]) / sqrt(|alpha|) (B x K each), alpha != 0.  Device pointers; nothing comes back to the host. */
 int lk_ridge_prior_batch_dev(lk_handle *h, int B, int N, int K, const double *flux_err, double alpha, double *prior_mu,
                              double *prior_sigma, void *stream);
+/* The same with one penalty per target: alpha = B doubles ON THE DEVICE, each finite and non-zero (the caller checks: nothing
+ * comes back), prior_sigma[b][:] = numpy.median(flux_err[b]) / sqrt(|alpha[b]|) by the same two operations: row b has the bits
+ * lk_ridge_prior_batch_dev gives at alpha[b]. */
+int lk_ridge_prior_alphas_batch_dev(lk_handle *h, int B, int N, int K, const double *flux_err, const double *alpha,
+                                    double *prior_mu, double *prior_sigma, void *stream);
 /* out[i] = a[i] - b[i] for n doubles on the device (flux - model: the corrected flux of RegressionCorrector.correct). */
 int lk_subtract_f64_dev(lk_handle *h, int64_t n, const double *a, const double *b, double *out, void *stream);
 
@@ -464,6 +469,21 @@ int lk_underfit_neighbors_batch(lk_handle *h, int B, int N, const double *flux, 
                                 const int32_t *neighbors, double *corr, double *metric);
 int lk_underfit_neighbors_batch_dev(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
                                     const int32_t *neighbors, double *corr, double *metric, void *stream);
+/* The same metric with the neighbours taken from ANOTHER array of Bn rows (flux_nb: Bn x N, NaN-free, the same cadences), prepared
+ * once and used by any number of calls (a ridge search scores many corrections of the targets against fixed neighbours).
+ * lk_underfit_rows_prepare_dev writes the Bn median-normalised rows z_j (pitch ceil(n / 128) x 128 doubles, zero tail) and then
+ * the Bn self-products G(j,j) into `rows`, a 16-byte aligned device block of the caller's of lk_underfit_rows_bytes(Bn, n) bytes.
+ * lk_underfit_against_rows_batch_dev prepares only the B target rows (B x ceil(n / 128) x 128 + B doubles of the handle's arena)
+ * and runs the pair pass against `rows`, which must have been prepared with the same n and keep_idx; neighbors: B x M int32
+ * indices into [0, Bn), anything else = padding; an index equal to the target's own row number is a neighbour like any other
+ * (it names a row of the other array).  G(a,b) is summed in the order given above: with flux_nb == flux the results are the bits
+ * of lk_underfit_neighbors_batch_dev.  Neither call synchronises anything. */
+int lk_underfit_rows_bytes(int Bn, int n, int64_t *bytes);
+int lk_underfit_rows_prepare_dev(lk_handle *h, int Bn, int N, const double *flux_nb, int n, const int32_t *keep_idx, void *rows,
+                                 int64_t rows_bytes, void *stream);
+int lk_underfit_against_rows_batch_dev(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int Bn,
+                                       const void *rows, int M, const int32_t *neighbors, double *corr, double *metric,
+                                       void *stream);
 
 /* ---- Over-fitting goodness metric of B targets (reference src/lightkurve/correctors/metrics.py:24-138
  * overfit_metric_lombscargle, as CBVCorrector.over_fitting_metric calls it on lc[cadence_mask]).  time, flux_orig, flux_corr,
@@ -502,6 +522,25 @@ int lk_overfit_metric_batch_dev(lk_handle *h, int B, int N, const double *time, 
                                 const double *err_corr, int n, const int32_t *keep_idx, double f0, double df, int64_t M,
                                 int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id, void *scratch,
                                 int64_t scratch_bytes, double *metric, void *stream);
+/* The metric as a SESSION, for scoring many corrections of one original batch with one noise stream (a ridge search: common
+ * random numbers).  `session` is a 256-byte aligned device block of the caller's with the size and the sample rounds of the
+ * unsplit call's scratch (lk_overfit_session_bytes: the arguments and answers of lk_overfit_scratch_bytes); it is caller-owned
+ * because the LS launcher resets the handle's arena.  begin does once what does not depend on the correction: z0, the rebased
+ * times, P0 and u_k[b] = nanmean(LS of the UNIT normals of sample k).  eval, any number of times with the shapes, keep_idx and
+ * grid of begin: z1, mean_unc, P1 (ONE LS launch of B rows), n_up and S against the kept P0, and the closed form with
+ * nanmean(Pn_k) = |mean_unc| * u_k (the amplitude-normalised periodogram is homogeneous of degree one in its input).  P0 and P1
+ * are the bits of the unsplit call, hence n_up and S too; the metric differs from it by the rounding of |mean_unc| * u_k against
+ * nanmean(LS(normal * mean_unc)) alone.  A NaN mean_unc gives NaN and a zero one per_k = inf (metric 0) when n_up > 0; n_up == 0
+ * gives per_k = 0.  eval allocates nothing, leaves everything begin wrote intact, and its result does not depend on the
+ * evaluations before it. */
+int lk_overfit_session_bytes(int B, int n, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes,
+                             int *samples_per_round);
+int lk_overfit_session_begin_dev(lk_handle *h, int B, int N, const double *time, const double *flux_orig, int n,
+                                 const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, uint64_t seed,
+                                 int64_t first_target, int64_t stream_id, void *session, int64_t session_bytes, void *stream);
+int lk_overfit_session_eval_dev(lk_handle *h, int B, int N, const double *flux_corr, const double *err_corr, int n,
+                                const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, void *session,
+                                int64_t session_bytes, double *metric, void *stream);
 /* out[b][c] = the standard normal of (target first_target + b, sample k, kept cadence c), B x n float64 on the device (16-byte
  * aligned): the generator of lk_overfit_metric_batch on its own. */
 int lk_overfit_noise_batch_dev(lk_handle *h, int B, int n, int k, uint64_t seed, int64_t first_target, int64_t stream_id,

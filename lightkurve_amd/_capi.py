@@ -162,11 +162,18 @@ SIGNATURES = [
       _vp, _vp, _vp, _vp]),
     ("lk_ridge_prior_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp]),
+    ("lk_ridge_prior_alphas_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     ("lk_subtract_f64_dev", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     ("lk_underfit_neighbors_batch", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, _c_i32p, ctypes.c_int, _c_i32p, _c_dp, _c_dp]),
     ("lk_underfit_neighbors_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    ("lk_underfit_rows_bytes", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    ("lk_underfit_rows_prepare_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int64, _vp]),
+    ("lk_underfit_against_rows_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     ("lk_overfit_scratch_bytes", ctypes.c_int,
      [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
       ctypes.POINTER(ctypes.c_int)]),
@@ -176,6 +183,15 @@ SIGNATURES = [
     ("lk_overfit_metric_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
       ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp]),
+    ("lk_overfit_session_bytes", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+      ctypes.POINTER(ctypes.c_int)]),
+    ("lk_overfit_session_begin_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
+      ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int64, _vp]),
+    ("lk_overfit_session_eval_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
+      ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp]),
     ("lk_overfit_noise_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp, _vp]),
     ("lk_savgol_trend_batch", ctypes.c_int,
@@ -831,19 +847,21 @@ def regress_shared_batch(X, y, err=None, cadence_mask=None, prior_mu=None, prior
 
 
 # --------------------------------------------------------------------------------------------- under-fitting metric
-def underfit_arguments(B, N, neighbors, cadence_mask=None):
-    """The checks of the under-fitting metric that need no device, shared by its three front ends: ``neighbors`` -> int32
+def underfit_arguments(B, N, neighbors, cadence_mask=None, Bn=None):
+    """The checks of the under-fitting metric that need no device, shared by its front ends: ``neighbors`` -> int32
     (B, M) C-contiguous (-1 = padding, else an index in [0, B) other than the row's own), ``cadence_mask`` (bool (N,), True
-    = used) -> ascending int32 indices of the kept cadences, or None for all of them.  Returns (neighbors, keep_idx, n)."""
+    = used) -> ascending int32 indices of the kept cadences, or None for all of them.  ``Bn``: the neighbours are the rows of
+    another array of Bn rows: indices in [0, Bn), the row's own number included.  Returns (neighbors, keep_idx, n)."""
     nb = np.asarray(neighbors)
     if nb.size == 0 and nb.ndim == 2:
         nb = nb.astype(np.int32)
     if nb.ndim != 2 or nb.shape[0] != B or not np.issubdtype(nb.dtype, np.integer):
         raise ValueError("neighbors must be an integer array of shape (B, M) = (%d, M) (got %s of shape %s)" % (B, nb.dtype, nb.shape))
     if nb.size:
-        if nb.min() < -1 or nb.max() >= B:
-            raise ValueError("a neighbour is -1 (padding) or an index in [0, %d): got values between %d and %d" % (B, nb.min(), nb.max()))
-        own = np.nonzero(nb == np.arange(B)[:, None])
+        rows = B if Bn is None else int(Bn)
+        if nb.min() < -1 or nb.max() >= rows:
+            raise ValueError("a neighbour is -1 (padding) or an index in [0, %d): got values between %d and %d" % (rows, nb.min(), nb.max()))
+        own = np.nonzero(nb == np.arange(B)[:, None]) if Bn is None else ((),)
         if len(own[0]):
             raise ValueError("a target cannot be its own neighbour: row %d lists %d" % (own[0][0], own[0][0]))
     nb = np.ascontiguousarray(nb, dtype=np.int32)

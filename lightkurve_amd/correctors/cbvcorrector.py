@@ -23,7 +23,7 @@ from .designmatrix import DesignMatrix, DesignMatrixCollection
 from .metrics import overfit_metric_lombscargle, overfit_metric_lombscargle_batch, underfit_metric_neighbors
 from .regressioncorrector import RegressionCorrector
 
-__all__ = ["CBVCorrector", "minimize_scalar_bounded"]
+__all__ = ["CBVCorrector", "minimize_scalar_bounded", "BoundedBrentBatch"]
 
 
 def minimize_scalar_bounded(func, bounds, xatol=1e-5, maxiter=500):
@@ -106,6 +106,124 @@ def minimize_scalar_bounded(func, bounds, xatol=1e-5, maxiter=500):
     if np.isnan(xf) or np.isnan(fx) or np.isnan(fu):
         flag = 2
     return dict(x=float(xf), fun=float(fx), nfev=num, status=flag)
+
+
+def _bounded_brent_steps(x1, x2, xatol, maxiter):
+    """``minimize_scalar_bounded`` turned inside out: a generator that yields each abscissa where the function would call
+    ``func`` and is sent the value; the same operations in the same order, statement for statement.  Its return value
+    (``StopIteration.value``) is the function's dict."""
+    flag = 0
+    sqrt_eps = np.sqrt(2.2e-16)
+    golden_mean = 0.5 * (3.0 - np.sqrt(5.0))
+    a, b = x1, x2
+    fulc = a + golden_mean * (b - a)
+    nfc, xf = fulc, fulc
+    rat = e = 0.0
+    x = xf
+    fx = yield x
+    num = 1
+    fu = np.inf
+    ffulc = fnfc = fx
+    xm = 0.5 * (a + b)
+    tol1 = sqrt_eps * np.abs(xf) + xatol / 3.0
+    tol2 = 2.0 * tol1
+    while np.abs(xf - xm) > (tol2 - 0.5 * (b - a)):
+        golden = 1
+        if np.abs(e) > tol1:
+            golden = 0
+            r = (xf - nfc) * (fx - ffulc)
+            q = (xf - fulc) * (fx - fnfc)
+            p = (xf - fulc) * q - (xf - nfc) * r
+            q = 2.0 * (q - r)
+            if q > 0.0:
+                p = -p
+            q = np.abs(q)
+            r = e
+            e = rat
+            if (np.abs(p) < np.abs(0.5 * q * r)) and (p > q * (a - xf)) and (p < q * (b - xf)):
+                rat = (p + 0.0) / q
+                x = xf + rat
+                if ((x - a) < tol2) or ((b - x) < tol2):
+                    si = np.sign(xm - xf) + ((xm - xf) == 0)
+                    rat = tol1 * si
+            else:
+                golden = 1
+        if golden:
+            e = a - xf if xf >= xm else b - xf
+            rat = golden_mean * e
+        si = np.sign(rat) + (rat == 0)
+        x = xf + si * np.maximum(np.abs(rat), tol1)
+        fu = yield x
+        num += 1
+        if fu <= fx:
+            if x >= xf:
+                a = xf
+            else:
+                b = xf
+            fulc, ffulc = nfc, fnfc
+            nfc, fnfc = xf, fx
+            xf, fx = x, fu
+        else:
+            if x < xf:
+                a = x
+            else:
+                b = x
+            if (fu <= fnfc) or (nfc == xf):
+                fulc, ffulc = nfc, fnfc
+                nfc, fnfc = x, fu
+            elif (fu <= ffulc) or (fulc == xf) or (fulc == nfc):
+                fulc, ffulc = x, fu
+        xm = 0.5 * (a + b)
+        tol1 = sqrt_eps * np.abs(xf) + xatol / 3.0
+        tol2 = 2.0 * tol1
+        if num >= maxiter:
+            flag = 1
+            break
+    if np.isnan(xf) or np.isnan(fx) or np.isnan(fu):
+        flag = 2
+    return dict(x=float(xf), fun=float(fx), nfev=num, status=flag)
+
+
+class BoundedBrentBatch(object):
+    """``minimize_scalar_bounded`` as a stepper for B independent searches on one interval, run in lockstep: ``.x`` is the
+    next abscissa of every search (float64[B]), ``.tell(f)`` takes the B objective values there, ``.done`` (bool[B]) says
+    which searches have ended and ``.result()`` gives the arrays x, fun, nfev, status.  Each search visits exactly the
+    abscissae the scalar function would, given the same values (B scalar states: the searches share nothing).  A finished
+    search keeps its final ``xf`` in ``.x``; whatever ``tell`` is given for it is ignored."""
+
+    def __init__(self, bounds, B, xatol=1e-5, maxiter=500):
+        x1, x2 = float(bounds[0]), float(bounds[1])
+        if not (np.isfinite(x1) and np.isfinite(x2)):
+            raise ValueError("Optimization bounds must be finite scalars.")
+        if x1 > x2:
+            raise ValueError("The lower bound exceeds the upper bound.")
+        if int(B) < 1:
+            raise ValueError("B must be >= 1 (got %r)" % (B,))
+        self._steps = [_bounded_brent_steps(x1, x2, xatol, maxiter) for _ in range(int(B))]
+        self._results = [None] * int(B)
+        self.x = np.array([float(next(g)) for g in self._steps], dtype=np.float64)
+        self.done = np.zeros(int(B), dtype=bool)
+
+    def tell(self, f):
+        f = np.asarray(f, dtype=np.float64)
+        if f.shape != self.x.shape:
+            raise ValueError("tell() takes one objective value per search, shape %s (got %s)" % (self.x.shape, f.shape))
+        for b, g in enumerate(self._steps):
+            if self.done[b]:
+                continue
+            try:
+                self.x[b] = g.send(f[b])
+            except StopIteration as stop:
+                self._results[b] = stop.value
+                self.done[b] = True
+                self.x[b] = stop.value["x"]
+
+    def result(self):
+        if not self.done.all():
+            raise ValueError("%d of the %d searches have not ended" % ((~self.done).sum(), len(self.done)))
+        r = self._results
+        return dict(x=np.array([v["x"] for v in r], dtype=np.float64), fun=np.array([v["fun"] for v in r], dtype=np.float64),
+                    nfev=np.array([v["nfev"] for v in r], dtype=np.int64), status=np.array([v["status"] for v in r], dtype=np.int64))
 
 
 def cbv_index_list(cbv_indices, n_vectors):

@@ -617,7 +617,15 @@ int lk_ridge_prior_batch_dev(lk_handle *h, int B, int N, int K, const double *fl
                              double *prior_sigma, void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    return lk::ridge_prior_launch(h, B, N, K, flux_err, alpha, prior_mu, prior_sigma, static_cast<hipStream_t>(stream));
+    return lk::ridge_prior_launch(h, B, N, K, flux_err, alpha, nullptr, prior_mu, prior_sigma, static_cast<hipStream_t>(stream));
+}
+
+int lk_ridge_prior_alphas_batch_dev(lk_handle *h, int B, int N, int K, const double *flux_err, const double *alpha,
+                                    double *prior_mu, double *prior_sigma, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(alpha != nullptr, "alpha is NULL (B doubles on the device)");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::ridge_prior_launch(h, B, N, K, flux_err, 0.0, alpha, prior_mu, prior_sigma, static_cast<hipStream_t>(stream));
 }
 
 int lk_subtract_f64_dev(lk_handle *h, int64_t n, const double *a, const double *b, double *out, void *stream) {
@@ -667,6 +675,24 @@ int lk_underfit_neighbors_batch(lk_handle *h, int B, int N, const double *flux, 
     return rc ? rc : io.finish();
 }
 
+int lk_underfit_rows_bytes(int Bn, int n, int64_t *bytes) { return lk::underfit_rows_bytes(Bn, n, bytes); }
+
+int lk_underfit_rows_prepare_dev(lk_handle *h, int Bn, int N, const double *flux_nb, int n, const int32_t *keep_idx, void *rows,
+                                 int64_t rows_bytes, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::underfit_rows_prepare_launch(h, Bn, N, flux_nb, n, keep_idx, rows, rows_bytes, static_cast<hipStream_t>(stream));
+}
+
+int lk_underfit_against_rows_batch_dev(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int Bn,
+                                       const void *rows, int M, const int32_t *neighbors, double *corr, double *metric,
+                                       void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::underfit_against_rows_launch(h, B, N, flux, n, keep_idx, Bn, rows, M, neighbors, corr, metric,
+                                            static_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------------------------ over-fitting metric
 int lk_overfit_scratch_bytes(int B, int n, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes,
                              int *samples_per_round) {
@@ -688,6 +714,29 @@ int lk_overfit_metric_batch_dev(lk_handle *h, int B, int N, const double *time, 
     LK_HIP_CHECK(hipSetDevice(h->device));
     return lk::overfit_metric_launch(h, B, N, time, flux_orig, flux_corr, err_corr, n, keep_idx, f0, df, M, n_samples, seed,
                                      first_target, stream_id, scratch, scratch_bytes, metric, static_cast<hipStream_t>(stream));
+}
+
+int lk_overfit_session_bytes(int B, int n, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes,
+                             int *samples_per_round) {
+    return lk::overfit_scratch_bytes(B, n, M, n_samples, max_scratch_bytes, bytes, samples_per_round);
+}
+
+int lk_overfit_session_begin_dev(lk_handle *h, int B, int N, const double *time, const double *flux_orig, int n,
+                                 const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, uint64_t seed,
+                                 int64_t first_target, int64_t stream_id, void *session, int64_t session_bytes, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::overfit_session_begin_launch(h, B, N, time, flux_orig, n, keep_idx, f0, df, M, n_samples, seed, first_target,
+                                            stream_id, session, session_bytes, static_cast<hipStream_t>(stream));
+}
+
+int lk_overfit_session_eval_dev(lk_handle *h, int B, int N, const double *flux_corr, const double *err_corr, int n,
+                                const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, void *session,
+                                int64_t session_bytes, double *metric, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::overfit_session_eval_launch(h, B, N, flux_corr, err_corr, n, keep_idx, f0, df, M, n_samples, session, session_bytes,
+                                           metric, static_cast<hipStream_t>(stream));
 }
 
 int lk_overfit_metric_batch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, const double *flux_corr,

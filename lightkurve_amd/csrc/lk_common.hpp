@@ -177,11 +177,17 @@ int regress_launch(lk_handle *h, int B, const int64_t *n_off_host, int K, const 
 int regress_shared_launch(lk_handle *h, int B, int N, int K, const double *X, const double *y, const double *err,
                           const uint8_t *cmask, const double *prior_mu, const double *prior_sigma, double clip_sigma, int niters,
                           double *w, double *model, uint8_t *outl, double *w_cov, hipStream_t stream);
-int ridge_prior_launch(lk_handle *h, int B, int N, int K, const double *err, double alpha, double *prior_mu, double *prior_sigma,
-                       hipStream_t stream);
+int ridge_prior_launch(lk_handle *h, int B, int N, int K, const double *err, double alpha, const double *alphas, double *prior_mu,
+                       double *prior_sigma, hipStream_t stream);
 int subtract_launch(lk_handle *h, int64_t n, const double *a, const double *b, double *out, hipStream_t stream);
 int underfit_neighbors_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
                               const int32_t *neighbors, double *corr, double *metric, hipStream_t stream);
+int underfit_rows_bytes(int Bn, int n, int64_t *bytes);
+int underfit_rows_prepare_launch(lk_handle *h, int Bn, int N, const double *flux_nb, int n, const int32_t *keep_idx, void *rows,
+                                 int64_t rows_bytes, hipStream_t stream);
+int underfit_against_rows_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int Bn,
+                                 const void *rows, int M, const int32_t *neighbors, double *corr, double *metric,
+                                 hipStream_t stream);
 int overfit_scratch_bytes(int B, int n, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes, int *samples_per_round);
 int overfit_noise_launch(lk_handle *h, int B, int n, int k, uint64_t seed, int64_t first_target, int64_t stream_id, double *out,
                          hipStream_t stream);
@@ -189,6 +195,12 @@ int overfit_metric_launch(lk_handle *h, int B, int N, const double *time, const 
                           const double *err_corr, int n, const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples,
                           uint64_t seed, int64_t first_target, int64_t stream_id, void *scratch, int64_t scratch_bytes,
                           double *metric, hipStream_t stream);
+int overfit_session_begin_launch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, int n,
+                                 const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, uint64_t seed,
+                                 int64_t first_target, int64_t stream_id, void *session, int64_t session_bytes, hipStream_t stream);
+int overfit_session_eval_launch(lk_handle *h, int B, int N, const double *flux_corr, const double *err_corr, int n,
+                                const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, void *session,
+                                int64_t session_bytes, double *metric, hipStream_t stream);
 int model_part_launch(lk_handle *h, int B, int N, int K, int c0, int c1, const double *X, const double *w, double *out,
                       hipStream_t stream);
 int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,

@@ -18,6 +18,10 @@
 // (distance 32 ... 1) finish the dot in every lane alike.  One wavefront computes one dot from start to end, so nothing
 // depends on B, M, the neighbour's position in the list or the workgroup: G(t,j) and G(j,t) are the same bits, and so is a
 // run on a sub-batch.  No atomics.
+//
+// The neighbours may also be the rows of ANOTHER array, prepared once into a caller-owned block (underfit_rows_*: Bn rows at the
+// same pitch, then their Bn self-products) and used by any number of pair passes: the pair kernel takes the target rows and the
+// neighbour rows as two arrays, which are one and the same in the call above.
 #include "block_select.hpp"
 #include "lk_common.hpp"
 
@@ -92,10 +96,13 @@ __global__ __launch_bounds__(1024) void underfit_prepare_kernel(const double *__
 // chunk's global loads are issued before the current chunk's arithmetic and land in the other buffer after it, one barrier
 // per chunk).  A trip handles UF_NW * UF_A = 32 list positions: wavefront w owns positions base + a * UF_NW + w, a < UF_A,
 // and streams those neighbours' rows with 16-byte loads; a list longer than a trip takes more trips (the row is staged again
-// from L2 each trip).  Padding (-1) and indices outside [0, B) read the target's own row and are discarded: correlation NaN,
+// from L2 each trip).  Padding (-1) and indices outside [0, Bn) read the target's own row and are discarded: correlation NaN,
 // not counted in m.  The cubes of a trip are added in position order by one thread, so the metric is reproducible too.
+// z / gself: the target rows and their self-products; zn / gn: the Bn neighbour rows and theirs (the same two arrays when the
+// neighbours are targets of the batch).  A neighbour's row base is formed once per trip, outside the dot loop.
 __global__ __launch_bounds__(UF_NT, 4) void underfit_pair_kernel(const double *__restrict__ z, const double *__restrict__ gself,
-                                                              int pitch, int B, int M, const int32_t *__restrict__ nbr,
+                                                              const double *__restrict__ zn, const double *__restrict__ gn,
+                                                              int pitch, int Bn, int M, const int32_t *__restrict__ nbr,
                                                               double scale, double *__restrict__ corr,
                                                               double *__restrict__ metric) {
     __shared__ __attribute__((aligned(16))) double2 s_row[2][UF_CHUNK / 2];
@@ -120,9 +127,9 @@ __global__ __launch_bounds__(UF_NT, 4) void underfit_pair_kernel(const double *_
                 na = a + 1;
                 j = __builtin_amdgcn_readfirstlane(nbr[(size_t)t * M + p]);
             }
-            ok[a] = j >= 0 && j < B;
-            jn[a] = ok[a] ? j : t;
-            rows[a] = z + (size_t)jn[a] * pitch;
+            ok[a] = j >= 0 && j < Bn;
+            jn[a] = j;
+            rows[a] = ok[a] ? zn + (size_t)j * pitch : zt;
         }
         double ax[UF_A] = {0.0, 0.0, 0.0, 0.0}, ay[UF_A] = {0.0, 0.0, 0.0, 0.0};
         auto row = [&](int a, int k) { return *reinterpret_cast<const double2 *>(rows[a] + (size_t)k * UF_STEP + 2 * lane); };
@@ -165,7 +172,7 @@ __global__ __launch_bounds__(UF_NT, 4) void underfit_pair_kernel(const double *_
                 const double g = uf_dot_finish(ax[a], ay[a]);
                 if (lane == 0) {
                     const int p = base + a * UF_NW + w;
-                    const double gjj = gself[jn[a]];
+                    const double gjj = ok[a] ? gn[jn[a]] : gtt;
                     const double c = (gtt == 0.0 || gjj == 0.0) ? 0.0 : g / sqrt(gtt * gjj);
                     const double ac = fabs(c);
                     if (corr) corr[(size_t)t * M + p] = ok[a] ? c : __longlong_as_double(0x7ff8000000000000ll);
@@ -186,25 +193,83 @@ __global__ __launch_bounds__(UF_NT, 4) void underfit_pair_kernel(const double *_
     if (tid == 0) metric[t] = 2.0 / (1.0 + exp(scale * sum / (double)(m + 1)));
 }
 
-// Workspace: B x pitch doubles of z rows (pitch = n rounded up to 128) + B self-products.
-int underfit_neighbors_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
-                              const int32_t *neighbors, double *corr, double *metric, hipStream_t stream) {
+static int underfit_shape_ok(int B, int N, int n, const int32_t *keep_idx) {
     LK_REQUIRE(B >= 1, "B must be >= 1 (got %d)", B);
     LK_REQUIRE(N >= 2 && n >= 2 && n <= N, "need 2 <= n <= N (got n=%d, N=%d): the metric needs at least two kept cadences", n, N);
     LK_REQUIRE(N < (1 << 30), "N=%d cadences outside 2..2^30", N);
     LK_REQUIRE(keep_idx != nullptr || n == N, "keep_idx is NULL (all cadences) but n=%d != N=%d", n, N);
+    return LK_OK;
+}
+
+static inline int uf_pitch(int n) { return (n + UF_STEP - 1) / UF_STEP * UF_STEP; }
+
+static double uf_scale(int n) {
+    const double wgn = 0.0007 + 0.8083 * std::pow((double)n, -0.5023);
+    return std::log(2.0 / 0.95 - 1.0) / wgn;
+}
+
+// Workspace: B x pitch doubles of z rows (pitch = n rounded up to 128) + B self-products.
+int underfit_neighbors_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
+                              const int32_t *neighbors, double *corr, double *metric, hipStream_t stream) {
+    if (const int rc = underfit_shape_ok(B, N, n, keep_idx)) return rc;
     LK_REQUIRE(M >= 0, "M must be >= 0 (got %d)", M);
     LK_REQUIRE(flux && metric, "NULL buffer");
     LK_REQUIRE(M == 0 || neighbors != nullptr, "neighbors is NULL with M=%d", M);
-    const int pitch = (n + UF_STEP - 1) / UF_STEP * UF_STEP;
+    const int pitch = uf_pitch(n);
     double *d_z, *d_g;
     if (const int rc = Scratch(h, h->ws).buf(d_z, (size_t)B * pitch).buf(d_g, B).carve(stream)) return rc;
-    const double wgn = 0.0007 + 0.8083 * std::pow((double)n, -0.5023);
-    const double scale = std::log(2.0 / 0.95 - 1.0) / wgn;
     if (M > 0)
         hipLaunchKernelGGL(underfit_prepare_kernel, dim3(B), dim3(1024), 0, stream, flux, N, n, keep_idx, pitch, d_z, d_g);
-    hipLaunchKernelGGL(underfit_pair_kernel, dim3(B), dim3(UF_NT), 0, stream, (const double *)d_z, (const double *)d_g, pitch, B,
-                       M, neighbors, scale, corr, metric);
+    hipLaunchKernelGGL(underfit_pair_kernel, dim3(B), dim3(UF_NT), 0, stream, (const double *)d_z, (const double *)d_g,
+                       (const double *)d_z, (const double *)d_g, pitch, B, M, neighbors, uf_scale(n), corr, metric);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ prepared neighbour rows
+// The block: Bn x pitch doubles of z rows, then Bn self-products (the row part is a multiple of 1 KiB: both 16-byte aligned).
+int underfit_rows_bytes(int Bn, int n, int64_t *bytes) {
+    LK_REQUIRE(Bn >= 1 && n >= 2 && n < (1 << 30), "need Bn >= 1 and 2 <= n < 2^30 (got Bn=%d, n=%d)", Bn, n);
+    LK_REQUIRE(bytes != nullptr, "bytes is NULL");
+    *bytes = ((int64_t)Bn * uf_pitch(n) + Bn) * 8;
+    return LK_OK;
+}
+
+int underfit_rows_prepare_launch(lk_handle *h, int Bn, int N, const double *flux_nb, int n, const int32_t *keep_idx, void *rows,
+                                 int64_t rows_bytes, hipStream_t stream) {
+    (void)h;
+    if (const int rc = underfit_shape_ok(Bn, N, n, keep_idx)) return rc;
+    LK_REQUIRE(flux_nb != nullptr, "NULL buffer");
+    LK_REQUIRE(rows != nullptr && ((uintptr_t)rows & 15) == 0, "rows must be a 16-byte aligned device buffer");
+    const int pitch = uf_pitch(n);
+    LK_REQUIRE(rows_bytes >= ((int64_t)Bn * pitch + Bn) * 8, "rows too small: %lld bytes given, %d rows of %d kept cadences need %lld "
+               "(lk_underfit_rows_bytes)", (long long)rows_bytes, Bn, n, (long long)(((int64_t)Bn * pitch + Bn) * 8));
+    double *z = static_cast<double *>(rows);
+    hipLaunchKernelGGL(underfit_prepare_kernel, dim3(Bn), dim3(1024), 0, stream, flux_nb, N, n, keep_idx, pitch, z,
+                       z + (size_t)Bn * pitch);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+// Only the B target rows are prepared (in the handle's arena); the neighbours are read from `rows` as prepared above with the
+// same n and keep_idx.  Here an index equal to the target's own row number names a row of the OTHER array: a neighbour.
+int underfit_against_rows_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int Bn,
+                                 const void *rows, int M, const int32_t *neighbors, double *corr, double *metric,
+                                 hipStream_t stream) {
+    if (const int rc = underfit_shape_ok(B, N, n, keep_idx)) return rc;
+    LK_REQUIRE(Bn >= 1, "Bn must be >= 1 (got %d)", Bn);
+    LK_REQUIRE(M >= 0, "M must be >= 0 (got %d)", M);
+    LK_REQUIRE(flux && metric, "NULL buffer");
+    LK_REQUIRE(M == 0 || neighbors != nullptr, "neighbors is NULL with M=%d", M);
+    LK_REQUIRE(rows != nullptr && ((uintptr_t)rows & 15) == 0, "rows must be a 16-byte aligned device buffer");
+    const int pitch = uf_pitch(n);
+    double *d_z, *d_g;
+    if (const int rc = Scratch(h, h->ws).buf(d_z, (size_t)B * pitch).buf(d_g, B).carve(stream)) return rc;
+    const double *zn = static_cast<const double *>(rows);
+    if (M > 0)
+        hipLaunchKernelGGL(underfit_prepare_kernel, dim3(B), dim3(1024), 0, stream, flux, N, n, keep_idx, pitch, d_z, d_g);
+    hipLaunchKernelGGL(underfit_pair_kernel, dim3(B), dim3(UF_NT), 0, stream, (const double *)d_z, (const double *)d_g, zn,
+                       zn + (size_t)Bn * pitch, pitch, Bn, M, neighbors, uf_scale(n), corr, metric);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }

@@ -69,7 +69,8 @@ __device__ __forceinline__ void philox_normal_pair(const Philox4 &p, double &a, 
 // ------------------------------------------------------------------------------------------------ prepare
 // One workgroup per target: exact medians of the kept cadences of both fluxes, the packed rows z0[b], z1[b], the rebased
 // times t - t[first kept] (written R times: rows (r, b) of the time block serve the R x B noise rows of a round, rows (0, b)
-// the two flux launches), and mean_unc[b].
+// the two flux launches), and mean_unc[b].  A session does it in two halves: y1 == NULL writes z0 and the times alone (begin),
+// y0 == NULL writes z1 and mean_unc alone (every evaluation); each half does what the whole does to its own outputs.
 __global__ __launch_bounds__(OF_PREP_NT) void overfit_prepare_kernel(const double *__restrict__ time, const double *__restrict__ y0,
                                                                     const double *__restrict__ y1, const double *__restrict__ e1,
                                                                     int N, int n, const int32_t *__restrict__ keep_idx, int B,
@@ -81,26 +82,36 @@ __global__ __launch_bounds__(OF_PREP_NT) void overfit_prepare_kernel(const doubl
     const size_t in = (size_t)b * N, out = (size_t)b * n;
     auto idx = [&](int i) { return keep_idx ? keep_idx[i] : i; };
     auto all = [&](int) { return true; };
-    const double med0 = block_median(n, (long long)n, [&](int i) { return y0[in + idx(i)]; }, all, sh);
-    __syncthreads();
-    const double med1 = block_median(n, (long long)n, [&](int i) { return y1[in + idx(i)]; }, all, sh);
-    __syncthreads();
-    const double t0 = time[in + idx(0)];
+    double med0 = 0.0, med1 = 0.0, t0 = 0.0;   // (y0, y1: uniform over the grid)
+    if (y0) {
+        med0 = block_median(n, (long long)n, [&](int i) { return y0[in + idx(i)]; }, all, sh);
+        __syncthreads();
+        t0 = time[in + idx(0)];
+    }
+    if (y1) {
+        med1 = block_median(n, (long long)n, [&](int i) { return y1[in + idx(i)]; }, all, sh);
+        __syncthreads();
+    }
     double s = 0.0;
     int cnt = 0;
     for (int i = tid; i < n; i += OF_PREP_NT) {
         const int j = idx(i);
         // y / med - 1.0 as two separately rounded operations (a zero median gives non-finite rows, as in the reference)
-        z0[out + i] = __dsub_rn(__ddiv_rn(y0[in + j], med0), 1.0);
-        z1[out + i] = __dsub_rn(__ddiv_rn(y1[in + j], med1), 1.0);
-        const double tr = __dsub_rn(time[in + j], t0);
-        for (int r = 0; r < R; ++r) trel[((size_t)r * B + b) * n + i] = tr;
-        const double u = __ddiv_rn(e1[in + j], med1);
-        if (u == u) {
-            s += u;
-            ++cnt;
+        if (y0) {
+            z0[out + i] = __dsub_rn(__ddiv_rn(y0[in + j], med0), 1.0);
+            const double tr = __dsub_rn(time[in + j], t0);
+            for (int r = 0; r < R; ++r) trel[((size_t)r * B + b) * n + i] = tr;
+        }
+        if (y1) {
+            z1[out + i] = __dsub_rn(__ddiv_rn(y1[in + j], med1), 1.0);
+            const double u = __ddiv_rn(e1[in + j], med1);
+            if (u == u) {
+                s += u;
+                ++cnt;
+            }
         }
     }
+    if (!y1) return;
     double *shd = reinterpret_cast<double *>(sh);
     shd[tid] = s;
     sh_cnt[tid] = cnt;
@@ -205,19 +216,23 @@ __global__ __launch_bounds__(OF_NT) void overfit_noise_mean_kernel(const double 
     if (tid == 0) mnp[row] = sc[0] ? sd[0] / (double)sc[0] : __longlong_as_double(0x7ff8000000000000ll);
 }
 
-// the closed form, one thread per target; the sample terms are added in order of k
+// the closed form, one thread per target; the sample terms are added in order of k.  mean_unc == NULL: mnp holds the noise
+// spectra's means themselves; else mnp holds those of the UNIT normals (a session's u_k) and the mean is |mean_unc[b]| * u_k:
+// the amplitude-normalised periodogram is homogeneous of degree one in its input.
 __global__ __launch_bounds__(OF_NT) void overfit_metric_kernel(int B, int n_samples, const int *__restrict__ n_up,
                                                               const double *__restrict__ S, const double *__restrict__ mnp,
-                                                              double *__restrict__ metric) {
+                                                              const double *__restrict__ mean_unc, double *__restrict__ metric) {
     const int b = blockIdx.x * OF_NT + threadIdx.x;
     if (b >= B) return;
     const int nu = n_up[b];
     const double s = S[b];
+    const double amp = mean_unc ? fabs(mean_unc[b]) : 1.0;
     double acc = 0.0;
     for (int k = 0; k < n_samples; ++k) {
         double per = 0.0;
         if (nu != 0) {
-            const double den = (double)nu * mnp[(size_t)k * B + b];
+            const double mk = mnp[(size_t)k * B + b];
+            const double den = (double)nu * (mean_unc ? amp * mk : mk);
             per = den == 0.0 ? __longlong_as_double(0x7ff0000000000000ll) : s / den;
         }
         acc += per;
@@ -324,53 +339,127 @@ int overfit_noise_launch(lk_handle *h, int B, int n, int k, uint64_t seed, int64
     return LK_OK;
 }
 
-int overfit_metric_launch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, const double *flux_corr,
-                          const double *err_corr, int n, const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples,
-                          uint64_t seed, int64_t first_target, int64_t stream_id, void *scratch, int64_t scratch_bytes,
-                          double *metric, hipStream_t stream) {
+namespace {
+// one call's view of the caller-owned block and the three steps the unsplit metric and a session share
+struct OverfitRun {
+    lk_handle *h;
+    int B, n, n_samples;
+    double f0, df;
+    int64_t M;
+    hipStream_t stream;
+    OverfitPlan p;
+    char *base;
+    std::vector<int64_t> off;   // row offsets of the largest launch (R B rows of n)
+
+    OverfitRun(lk_handle *h_, int B_, int n_, double f0_, double df_, int64_t M_, int n_samples_, void *block, size_t bytes,
+               hipStream_t st)
+        : h(h_), B(B_), n(n_), n_samples(n_samples_), f0(f0_), df(df_), M(M_), stream(st), p(of_plan(B_, n_, M_, n_samples_, bytes)),
+          base(static_cast<char *>(block)), off((size_t)p.R * B_ + 1) {
+        for (size_t r = 0; r < off.size(); ++r) off[r] = (int64_t)r * n;
+    }
+    double *at(size_t o) const { return reinterpret_cast<double *>(base + o); }
+    int *n_up() const { return reinterpret_cast<int *>(base + p.n_up); }
+
+    int prepare(const double *time, const double *y0, const double *y1, const double *e1, int N, const int32_t *keep_idx) const {
+        hipLaunchKernelGGL(overfit_prepare_kernel, dim3(B), dim3(OF_PREP_NT), 0, stream, time, y0, y1, e1, N, n, keep_idx, B, p.R,
+                           at(p.z0), at(p.z1), at(p.trel), at(p.mean_unc));
+        LK_HIP_CHECK(hipGetLastError());
+        return LK_OK;
+    }
+    int ls(int rows, const double *y, double *power) const {
+        return lsfast_launch(h, rows, off.data(), at(p.trel), y, nullptr, f0, df, M, 1, 1, LK_NORM_LK_AMPLITUDE, nullptr, 5, power, stream);
+    }
+    // P1, then n_up and S against P0
+    int change() const {
+        if (const int rc = ls(B, at(p.z1), at(p.p1))) return rc;
+        hipLaunchKernelGGL(overfit_change_kernel, dim3(B), dim3(OF_NT), 0, stream, (const double *)at(p.p0), (const double *)at(p.p1),
+                           (int)M, n_up(), at(p.S));
+        return LK_OK;
+    }
+    // mnp[k][b] = nanmean(LS of sample k's normals times scale[b]) (scale == NULL: the unit normals), in rounds of R samples
+    int noise_means(uint64_t seed, int64_t first_target, int64_t stream_id, const double *scale) const {
+        for (int k0 = 0; k0 < n_samples; k0 += p.R) {
+            const int nk = std::min(p.R, n_samples - k0);
+            overfit_noise_rows(B, n, nk, k0, seed, first_target, stream_id, scale, at(p.g), stream);
+            LK_HIP_CHECK(hipGetLastError());
+            if (const int rc = ls(nk * B, at(p.g), at(p.pn))) return rc;
+            hipLaunchKernelGGL(overfit_noise_mean_kernel, dim3((unsigned)(nk * B)), dim3(OF_NT), 0, stream, (const double *)at(p.pn),
+                               (int)M, at(p.mnp) + (size_t)k0 * B);
+        }
+        return LK_OK;
+    }
+    int metric(const double *amp, double *out) const {
+        hipLaunchKernelGGL(overfit_metric_kernel, dim3((B + OF_NT - 1) / OF_NT), dim3(OF_NT), 0, stream, B, n_samples,
+                           (const int *)n_up(), (const double *)at(p.S), (const double *)at(p.mnp), amp, out);
+        LK_HIP_CHECK(hipGetLastError());
+        return LK_OK;
+    }
+};
+}  // namespace
+
+static int overfit_block_ok(int B, int N, int n, const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples,
+                            const void *block, int64_t bytes) {
     int rc = overfit_shape_ok(B, n, M, n_samples);
     if (rc) return rc;
     LK_REQUIRE(N >= n && N < (1 << 30), "need n <= N < 2^30 (got n=%d, N=%d)", n, N);
     LK_REQUIRE(keep_idx != nullptr || n == N, "keep_idx is NULL (all cadences) but n=%d != N=%d", n, N);
-    LK_REQUIRE(time && flux_orig && flux_corr && err_corr && metric, "NULL buffer");
     LK_REQUIRE(f0 >= 0.0 && df > 0.0, "the grid needs f0 >= 0 and df > 0 (got f0=%g, df=%g)", f0, df);
-    if ((rc = overfit_rng_ok(B, first_target, stream_id))) return rc;
-    LK_REQUIRE(scratch != nullptr && ((uintptr_t)scratch & 255) == 0, "scratch must be a 256-byte aligned device buffer");
-    LK_REQUIRE(scratch_bytes >= 0, "scratch_bytes must be >= 0");
-    const OverfitPlan p = of_plan(B, n, M, n_samples, (size_t)scratch_bytes);
-    LK_REQUIRE(p.total <= (size_t)scratch_bytes, "scratch too small: %lld bytes given, one sample per round needs %lld "
-               "(lk_overfit_scratch_bytes)", (long long)scratch_bytes, (long long)p.total);
-    char *base = static_cast<char *>(scratch);
-    auto at = [&](size_t off) { return reinterpret_cast<double *>(base + off); };
-    double *d_z0 = at(p.z0), *d_z1 = at(p.z1), *d_t = at(p.trel), *d_g = at(p.g), *d_p0 = at(p.p0), *d_p1 = at(p.p1), *d_pn = at(p.pn);
-    double *d_mu = at(p.mean_unc), *d_mnp = at(p.mnp), *d_S = at(p.S);
-    int *d_nup = reinterpret_cast<int *>(base + p.n_up);
-    const int R = p.R;
-    std::vector<int64_t> off((size_t)R * B + 1);
-    for (size_t r = 0; r < off.size(); ++r) off[r] = (int64_t)r * n;
-
-    hipLaunchKernelGGL(overfit_prepare_kernel, dim3(B), dim3(OF_PREP_NT), 0, stream, time, flux_orig, flux_corr, err_corr, N, n,
-                       keep_idx, B, R, d_z0, d_z1, d_t, d_mu);
-    LK_HIP_CHECK(hipGetLastError());
-    auto ls = [&](int rows, const double *y, double *power) {
-        return lsfast_launch(h, rows, off.data(), d_t, y, nullptr, f0, df, M, 1, 1, LK_NORM_LK_AMPLITUDE, nullptr, 5, power, stream);
-    };
-    if ((rc = ls(B, d_z0, d_p0))) return rc;
-    if ((rc = ls(B, d_z1, d_p1))) return rc;
-    hipLaunchKernelGGL(overfit_change_kernel, dim3(B), dim3(OF_NT), 0, stream, (const double *)d_p0, (const double *)d_p1, (int)M,
-                       d_nup, d_S);
-    for (int k0 = 0; k0 < n_samples; k0 += R) {
-        const int nk = std::min(R, n_samples - k0);
-        overfit_noise_rows(B, n, nk, k0, seed, first_target, stream_id, d_mu, d_g, stream);
-        LK_HIP_CHECK(hipGetLastError());
-        if ((rc = ls(nk * B, d_g, d_pn))) return rc;
-        hipLaunchKernelGGL(overfit_noise_mean_kernel, dim3((unsigned)(nk * B)), dim3(OF_NT), 0, stream, (const double *)d_pn, (int)M,
-                           d_mnp + (size_t)k0 * B);
-    }
-    hipLaunchKernelGGL(overfit_metric_kernel, dim3((B + OF_NT - 1) / OF_NT), dim3(OF_NT), 0, stream, B, n_samples,
-                       (const int *)d_nup, (const double *)d_S, (const double *)d_mnp, metric);
-    LK_HIP_CHECK(hipGetLastError());
+    LK_REQUIRE(block != nullptr && ((uintptr_t)block & 255) == 0, "scratch must be a 256-byte aligned device buffer");
+    LK_REQUIRE(bytes >= 0, "scratch_bytes must be >= 0");
+    const OverfitPlan p = of_plan(B, n, M, n_samples, (size_t)bytes);
+    LK_REQUIRE(p.total <= (size_t)bytes, "scratch too small: %lld bytes given, one sample per round needs %lld "
+               "(lk_overfit_scratch_bytes)", (long long)bytes, (long long)p.total);
     return LK_OK;
+}
+
+int overfit_metric_launch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, const double *flux_corr,
+                          const double *err_corr, int n, const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples,
+                          uint64_t seed, int64_t first_target, int64_t stream_id, void *scratch, int64_t scratch_bytes,
+                          double *metric, hipStream_t stream) {
+    int rc = overfit_block_ok(B, N, n, keep_idx, f0, df, M, n_samples, scratch, scratch_bytes);
+    if (rc) return rc;
+    LK_REQUIRE(time && flux_orig && flux_corr && err_corr && metric, "NULL buffer");
+    if ((rc = overfit_rng_ok(B, first_target, stream_id))) return rc;
+    const OverfitRun run(h, B, n, f0, df, M, n_samples, scratch, (size_t)scratch_bytes, stream);
+    if ((rc = run.prepare(time, flux_orig, flux_corr, err_corr, N, keep_idx))) return rc;
+    if ((rc = run.ls(B, run.at(run.p.z0), run.at(run.p.p0)))) return rc;
+    if ((rc = run.change())) return rc;
+    if ((rc = run.noise_means(seed, first_target, stream_id, run.at(run.p.mean_unc)))) return rc;
+    return run.metric(nullptr, metric);
+}
+
+// ------------------------------------------------------------------------------------------------ session
+// The metric in two halves for a caller that scores MANY corrections of one original batch with one noise stream (the ridge
+// search): begin takes everything that does not depend on the correction (z0, the times, P0 and u_k = nanmean(LS of the unit
+// normals of sample k)); an evaluation packs z1 and mean_unc, takes P1 in ONE launch of B rows and closes the form with
+// mnp_k = |mean_unc| * u_k.  P0 and P1 are the bits of the unsplit call, so n_up and S are too; only mnp_k differs, by the
+// rounding of nanmean(LS(normal * mean_unc)) against |mean_unc| * nanmean(LS(normal)).  Edge rules: a NaN mean_unc gives a NaN
+// noise mean (a NaN metric) and a zero one a zero noise mean (per_k = inf, metric 0) when n_up > 0; n_up == 0 gives 0.  The
+// block has the layout of the unsplit call's scratch (same size, same rounds); an evaluation writes z1, P1, mean_unc, n_up and
+// S and nothing that begin wrote.
+int overfit_session_begin_launch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, int n,
+                                 const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, uint64_t seed,
+                                 int64_t first_target, int64_t stream_id, void *session, int64_t session_bytes, hipStream_t stream) {
+    int rc = overfit_block_ok(B, N, n, keep_idx, f0, df, M, n_samples, session, session_bytes);
+    if (rc) return rc;
+    LK_REQUIRE(time && flux_orig, "NULL buffer");
+    if ((rc = overfit_rng_ok(B, first_target, stream_id))) return rc;
+    const OverfitRun run(h, B, n, f0, df, M, n_samples, session, (size_t)session_bytes, stream);
+    if ((rc = run.prepare(time, flux_orig, nullptr, nullptr, N, keep_idx))) return rc;
+    if ((rc = run.ls(B, run.at(run.p.z0), run.at(run.p.p0)))) return rc;
+    return run.noise_means(seed, first_target, stream_id, nullptr);
+}
+
+int overfit_session_eval_launch(lk_handle *h, int B, int N, const double *flux_corr, const double *err_corr, int n,
+                                const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, void *session,
+                                int64_t session_bytes, double *metric, hipStream_t stream) {
+    int rc = overfit_block_ok(B, N, n, keep_idx, f0, df, M, n_samples, session, session_bytes);
+    if (rc) return rc;
+    LK_REQUIRE(flux_corr && err_corr && metric, "NULL buffer");
+    const OverfitRun run(h, B, n, f0, df, M, n_samples, session, (size_t)session_bytes, stream);
+    if ((rc = run.prepare(nullptr, nullptr, flux_corr, err_corr, N, keep_idx))) return rc;
+    if ((rc = run.change())) return rc;
+    return run.metric(run.at(run.p.mean_unc), metric);
 }
 
 }  // namespace lk

@@ -1490,29 +1490,32 @@ int regress_shared_launch(lk_handle *h, int B, int N, int K, const double *X, co
 }
 
 // CBVCorrector.correct_gaussian_prior's prior (reference cbvcorrector.py:333-395): mu = 0 and one ridge width per target,
-// sigma_b = numpy.median(flux_err_b) / sqrt(|alpha|), on every column.  One workgroup per target.
+// sigma_b = numpy.median(flux_err_b) / sqrt(|alpha_b|), on every column; alpha_b = alphas[b], or `alpha` for every target
+// when alphas == NULL (the same two operations either way: a row has the same bits).  One workgroup per target.
 __global__ __launch_bounds__(1024) void ridge_prior_kernel(const double *__restrict__ err, int N, int K, double alpha,
-                                                           double *__restrict__ mu, double *__restrict__ sg) {
+                                                           const double *__restrict__ alphas, double *__restrict__ mu,
+                                                           double *__restrict__ sg) {
     __shared__ unsigned long long sh[1024];
     const int b = blockIdx.x;
     const double *e = err + (size_t)b * N;
     auto val = [&](int i) { return e[i]; };
     auto keep = [&](int) { return true; };
     const double med = block_median(N, (long long)N, val, keep, sh);
-    const double s = med / sqrt(fabs(alpha));
+    const double s = med / sqrt(fabs(alphas ? alphas[b] : alpha));
     for (int k = threadIdx.x; k < K; k += 1024) {
         mu[(size_t)b * K + k] = 0.0;
         sg[(size_t)b * K + k] = s;
     }
 }
 
-int ridge_prior_launch(lk_handle *h, int B, int N, int K, const double *err, double alpha, double *prior_mu, double *prior_sigma,
-                       hipStream_t stream) {
+// alphas: B doubles on the device, or NULL = `alpha` for every target
+int ridge_prior_launch(lk_handle *h, int B, int N, int K, const double *err, double alpha, const double *alphas, double *prior_mu,
+                       double *prior_sigma, hipStream_t stream) {
     (void)h;
     LK_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && K >= 1, "bad shapes");
     LK_REQUIRE(err && prior_mu && prior_sigma, "NULL buffer");
-    LK_REQUIRE(alpha != 0.0 && alpha == alpha, "alpha must be non-zero (alpha == 0 means no prior: pass NULL priors)");
-    hipLaunchKernelGGL(ridge_prior_kernel, dim3(B), dim3(1024), 0, stream, err, N, K, alpha, prior_mu, prior_sigma);
+    LK_REQUIRE(alphas || (alpha != 0.0 && alpha == alpha), "alpha must be non-zero (alpha == 0 means no prior: pass NULL priors)");
+    hipLaunchKernelGGL(ridge_prior_kernel, dim3(B), dim3(1024), 0, stream, err, N, K, alpha, alphas, prior_mu, prior_sigma);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }

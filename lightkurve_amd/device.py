@@ -47,7 +47,9 @@ class _Pool(object):
     def __init__(self, handle):
         self.handle = handle
         self.free = []                  # (capacity, ptr)
-        self.lock = threading.Lock()
+        # re-entrant: a buffer that dies in a reference cycle is finalised by the cyclic collector, which may run at any
+        # allocation of this thread, also inside take() while the lock is held; give() then only appends
+        self.lock = threading.RLock()
 
     def take(self, nbytes):
         nbytes = max(int(nbytes), 1)
@@ -430,31 +432,51 @@ class DeviceLightCurveBatch(object):
         cbvcorrector.py:333-395) for every target of the batch: columns [cbvs[:, idx - 1] | ext_dm | 1] shared by all targets
         (``cbvs``: (N, n_vectors), column j = basis vector j + 1; indices 1-based, out-of-range ones dropped, "ALL" accepted),
         prior_mu = 0 and ONE ridge width per target, median(flux_err_b) / sqrt(|alpha|), taken on the device; ``alpha == 0``:
-        no prior.  Returns what ``regression_correct`` returns."""
+        no prior.  ``alpha`` may also be an array-like of B finite, non-zero penalties, one per target (8 bytes per target go
+        up; row b is what the scalar call at ``alpha[b]`` gives, bit for bit); a zero inside an array is a ``ValueError``:
+        "no prior" stays the scalar ``alpha == 0.0``.  Returns what ``regression_correct`` returns."""
         Xa = _cbv_columns(cbvs, cbv_indices, ext_dm)
         N = self._uniform_n(Xa.shape[0], "cbv_correct")
-        B, K = len(self), Xa.shape[1]
-        h = self.handle
-        d_mu = d_sg = None
-        if alpha != 0.0:
-            if self.d_flux_err is None:
-                raise ValueError("cbv_correct with alpha != 0 needs flux errors (the ridge width is median(flux_err) / sqrt(|alpha|))")
-            d_mu, d_sg = DeviceBuffer(h, B * K * 8), DeviceBuffer(h, B * K * 8)
-            _capi._check(_capi._lib.lk_ridge_prior_batch_dev(h._h, B, N, K, _vp(self.d_flux_err.ptr), float(alpha), _vp(d_mu.ptr),
-                                                             _vp(d_sg.ptr), _vp(self.stream or None)))
-        return self._regress_shared(Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, [])
+        alphas = None if np.ndim(alpha) == 0 else _alpha_per_target(alpha, len(self))
+        keep = []
+        d_mu, d_sg = self._ridge_prior(N, Xa.shape[1], alpha, alphas, keep)
+        return self._regress_shared(Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, keep)
 
-    def _regress_shared(self, Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, keep):
+    def _ridge_prior(self, N, K, alpha, alphas, keep):
+        """(prior_mu, prior_sigma) on the device for one scalar ``alpha`` (0: (None, None), no prior) or, when ``alphas`` is
+        not None, for one checked penalty per target."""
+        if alphas is None and alpha == 0.0:
+            return None, None
+        if getattr(self, "d_flux_err", None) is None:
+            raise ValueError("cbv_correct with alpha != 0 needs flux errors (the ridge width is median(flux_err) / sqrt(|alpha|))")
+        h, B, st = self.handle, len(self), _vp(self.stream or None)
+        d_mu, d_sg = DeviceBuffer(h, B * K * 8), DeviceBuffer(h, B * K * 8)
+        if alphas is None:
+            _capi._check(_capi._lib.lk_ridge_prior_batch_dev(h._h, B, N, K, _vp(self.d_flux_err.ptr), float(alpha), _vp(d_mu.ptr),
+                                                             _vp(d_sg.ptr), st))
+        else:
+            d_alpha, k = _upload(h, alphas, self.stream)
+            keep += [k, d_alpha]
+            _capi._check(_capi._lib.lk_ridge_prior_alphas_batch_dev(h._h, B, N, K, _vp(self.d_flux_err.ptr), _vp(d_alpha.ptr),
+                                                                    _vp(d_mu.ptr), _vp(d_sg.ptr), st))
+        return d_mu, d_sg
+
+    def _regress_shared(self, Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, keep, resident=None):
+        """``resident``: (d_X, d_cm) already in HBM (a search that fits the same matrix many times uploads them once); then
+        ``cadence_mask`` is not looked at."""
         h, B, K = self.handle, len(self), Xa.shape[1]
-        d_cm = None
-        if cadence_mask is not None:
-            cm = np.ascontiguousarray(cadence_mask, dtype=np.uint8)
-            if cm.shape != (B, N):
-                raise ValueError("cadence_mask must be (B, N) = %s (got %s)" % ((B, N), cm.shape))
-            d_cm, k = _upload(h, cm, self.stream, np.uint8)
+        if resident is not None:
+            d_X, d_cm = resident
+        else:
+            d_cm = None
+            if cadence_mask is not None:
+                cm = np.ascontiguousarray(cadence_mask, dtype=np.uint8)
+                if cm.shape != (B, N):
+                    raise ValueError("cadence_mask must be (B, N) = %s (got %s)" % ((B, N), cm.shape))
+                d_cm, k = _upload(h, cm, self.stream, np.uint8)
+                keep.append(k)
+            d_X, k = _upload(h, Xa, self.stream)
             keep.append(k)
-        d_X, k = _upload(h, Xa, self.stream)
-        keep.append(k)
         d_w, d_model, d_corr, d_outl = DeviceBuffer(h, B * K * 8), DeviceBuffer(h, B * N * 8), DeviceBuffer(h, B * N * 8), DeviceBuffer(h, B * N)
         _capi._check(_capi._lib.lk_regress_shared_batch_dev(
             h._h, B, N, K, _vp(d_X.ptr), _vp(self.d_flux.ptr), _vp(self.d_flux_err.ptr if self.d_flux_err is not None else None),
@@ -474,7 +496,7 @@ class DeviceLightCurveBatch(object):
         return out, d_outl, d_w
 
     # ---------------------------------------------------------------- under-fitting metric, neighbours by index
-    def under_fitting_metric(self, neighbors, cadence_mask=None, return_correlations=False, to_host=True):
+    def under_fitting_metric(self, neighbors, cadence_mask=None, return_correlations=False, to_host=True, neighbor_batch=None):
         """``underfit_metric_neighbors`` (reference correctors/metrics.py:141-257, 451-475) for every target of the batch, the
         neighbours being OTHER TARGETS OF THIS BATCH (the reference fetches them from MAST; after ``cbv_correct`` they are the
         corrected targets of the same field, already in HBM): ``neighbors`` int (B, M), row t = the indices of t's neighbours,
@@ -483,12 +505,17 @@ class DeviceLightCurveBatch(object):
         NaN-free batch (``remove_nans()``).  Zero-centred flux is fine (the correlation does not depend on the scale of
         flux / median - 1); a median of exactly zero gives a non-finite result, as in the reference.  Returns metric[B]
         (``to_host=True``; 8 bytes per target cross PCIe) or its ``DeviceBuffer`` (``to_host=False``: nothing synchronised);
-        ``return_correlations``: also correlations[B, M] (NaN at padding), host array or ``DeviceBuffer`` likewise."""
+        ``return_correlations``: also correlations[B, M] (NaN at padding), host array or ``DeviceBuffer`` likewise.
+        ``neighbor_batch``: a resident, NaN-free batch with the same cadence count whose ROWS are the neighbours instead
+        (``neighbors`` then holds indices into ``[0, len(neighbor_batch))``, and a target's own row number is a neighbour
+        like any other: it names a row of the other batch); its rows are prepared once and only the B targets after them.
+        With ``neighbor_batch`` = this batch the result is the same bits as without."""
         N = self._uniform_n(None, "under_fitting_metric")
-        if not self.nan_free:
+        if not getattr(self, "nan_free", False):
             raise ValueError("under_fitting_metric needs a NaN-free batch: call remove_nans() first (and cotrend after it)")
         B = len(self)
-        nb, keep_idx, n = _capi.underfit_arguments(B, N, neighbors, cadence_mask)
+        Bn = None if neighbor_batch is None else _neighbor_batch_rows(neighbor_batch, N, "under_fitting_metric")
+        nb, keep_idx, n = _capi.underfit_arguments(B, N, neighbors, cadence_mask, Bn)
         M = nb.shape[1]
         h, st = self.handle, _vp(self.stream or None)
         d_nb = d_keep = d_corr = None
@@ -500,10 +527,18 @@ class DeviceLightCurveBatch(object):
             self._keep.append(k)
         if return_correlations:
             d_corr = DeviceBuffer(h, max(B * M, 1) * 8)
-        d_metric = DeviceBuffer(h, B * 8)
-        _capi._check(_capi._lib.lk_underfit_neighbors_batch_dev(
-            h._h, B, N, _vp(self.d_flux.ptr), n, _vp(d_keep.ptr if d_keep is not None else None), M,
-            _vp(d_nb.ptr if d_nb is not None else None), _vp(d_corr.ptr if (d_corr is not None and M) else None), _vp(d_metric.ptr), st))
+        if neighbor_batch is None:
+            d_metric = DeviceBuffer(h, B * 8)
+            _capi._check(_capi._lib.lk_underfit_neighbors_batch_dev(
+                h._h, B, N, _vp(self.d_flux.ptr), n, _vp(d_keep.ptr if d_keep is not None else None), M,
+                _vp(d_nb.ptr if d_nb is not None else None), _vp(d_corr.ptr if (d_corr is not None and M) else None),
+                _vp(d_metric.ptr), st))
+        else:
+            d_rows = neighbor_batch._underfit_rows(N, n, d_keep, self.stream)
+            d_metric = self._underfit_against(N, n, d_keep, Bn, d_rows, M, d_nb, d_corr)
+            # (the neighbours' flux buffer, not the batch: a batch that holds a batch can close a reference cycle — with itself as
+            # its own neighbour batch it would — and a cycle's buffers come back only when the cyclic collector runs)
+            self._keep += [d_rows, neighbor_batch.d_flux]
         # inputs the stream may still be reading: held until the batch is synchronised or dropped
         self._keep += [d_nb, d_keep]
         if not to_host:
@@ -513,6 +548,29 @@ class DeviceLightCurveBatch(object):
             corr = d_corr.download(np.float64, B * M, stream=self.stream) if M else np.empty(0)
             return metric, corr.reshape(B, M)
         return metric
+
+    def _underfit_rows(self, N, n, d_keep, stream):
+        """This batch's rows prepared as the NEIGHBOURS of ``lk_underfit_against_rows_batch_dev`` -> their ``DeviceBuffer``
+        (queued on ``stream``, the stream of the batch that will read them)."""
+        h, Bn = self.handle, len(self)
+        nbytes = ctypes.c_int64(0)
+        _capi._check(_capi._lib.lk_underfit_rows_bytes(Bn, n, ctypes.byref(nbytes)))
+        d_rows = DeviceBuffer(h, nbytes.value)
+        _capi._check(_capi._lib.lk_underfit_rows_prepare_dev(h._h, Bn, N, _vp(self.d_flux.ptr), n,
+                                                             _vp(d_keep.ptr if d_keep is not None else None), _vp(d_rows.ptr),
+                                                             nbytes.value, _vp(stream or None)))
+        return d_rows
+
+    def _underfit_against(self, N, n, d_keep, Bn, d_rows, M, d_nb, d_corr=None, d_metric=None, metric_offset=0):
+        """The pair pass of this batch's targets against prepared neighbour rows -> the metric's ``DeviceBuffer``."""
+        h, B = self.handle, len(self)
+        if d_metric is None:
+            d_metric = DeviceBuffer(h, B * 8)
+        _capi._check(_capi._lib.lk_underfit_against_rows_batch_dev(
+            h._h, B, N, _vp(self.d_flux.ptr), n, _vp(d_keep.ptr if d_keep is not None else None), Bn, _vp(d_rows.ptr), M,
+            _vp(d_nb.ptr if d_nb is not None else None), _vp(d_corr.ptr if (d_corr is not None and M) else None),
+            _vp(d_metric.ptr + metric_offset), _vp(self.stream or None)))
+        return d_metric
 
     # ---------------------------------------------------------------- over-fitting metric, noise made on the device
     def _overfit_checks(self, original, n_samples, cadence_mask, frequency, seed, first_target, stream_id):
@@ -596,6 +654,143 @@ class DeviceLightCurveBatch(object):
                 under[a] = d_under.download(np.float64, B, stream=self.stream)
             cor.synchronize()
         return dict(alpha=alphas, over_fitting=over, under_fitting=under)
+
+    def cbv_correct_optimized(self, cbvs, neighbors=None, neighbor_batch=None, cbv_indices=np.arange(1, 9), ext_dm=None,
+                              cadence_mask=None, alpha_bounds=(1e-4, 1e4), target_over_score=0.5, target_under_score=0.5,
+                              max_iter=100, frequency=None, seed=0, first_target=0, stream_id=0, neighbor_alpha=1e-20, sigma=5,
+                              niters=5, max_scratch_bytes=None, return_trace=False):
+        """``CBVCorrector.correct`` (reference cbvcorrector.py:397-500) for every target of the batch: a bounded Brent search
+        of the ridge penalty alpha PER TARGET over ``-(leaky(over, target_over_score) + leaky(under, target_under_score))``
+        (``correctors.cbvcorrector.minimize_scalar_bounded`` is the search; every target visits the abscissae that function
+        would), one more fit at the optimum, then the over-fitting score with ``n_samples=10`` and the under-fitting score.
+        The B searches run in lockstep (``BoundedBrentBatch``): per step 8 bytes per target go up (its alpha) and 16 come back
+        (its two scores); a target whose search has ended is evaluated again at its optimum and the value ignored.  The
+        design matrix and the mask are uploaded once; what does not depend on alpha is taken once: the periodogram of the
+        uncorrected flux, the noise periodogram, the neighbours' normalised rows.  One evaluation is one regression, one
+        Lomb-Scargle pass of B rows and one pair pass.
+
+        NOISE: the reference draws fresh noise at every evaluation.  Here the search uses ``n_samples = 1`` and ONE fixed
+        stream ``(seed, first_target + b, stream_id)`` for all evaluations (common random numbers): the objective is a
+        deterministic function of alpha, and two runs give the same bits.  The final over-fitting score is
+        ``over_fitting_metric(n_samples=10)`` with the same seed and stream.
+
+        NEIGHBOURS: rows of the resident ``neighbor_batch`` named by ``neighbors`` (int (B, M), -1 = padding, indices into
+        ``[0, len(neighbor_batch))``); their flux is FIXED during the search (``CBVCorrector.set_neighbors``' semantics).
+        ``neighbor_batch=None``: this batch corrected at ``neighbor_alpha`` (1e-20: the plain least-squares fit).  A target's
+        result therefore depends on its own alpha alone and not on the other targets of the batch.
+
+        A score whose target is <= 0 is skipped (nothing is launched for it): it counts as 1.0 in the objective and is
+        reported as -1.0; ``target_under_score > 0`` needs ``neighbors``.  ``cadence_mask``: bool (N,), shared by the fit and
+        both metrics; ``frequency``: as in ``over_fitting_metric``.  Returns (corrected ``DeviceLightCurveBatch``, info):
+        info = dict(alpha[B], over_fitting_score[B], under_fitting_score[B], objective[B] (the search's best value), nfev[B],
+        status[B] (0, or 1 = ``max_iter`` reached)); ``return_trace`` adds trace = dict(alpha[I, B], over[I, B],
+        under[I, B]), the I lockstep evaluations (a skipped score is 1.0 there).  Every argument is checked before the first
+        device call."""
+        from .correctors.cbvcorrector import BoundedBrentBatch
+        Xa = _cbv_columns(cbvs, cbv_indices, ext_dm)
+        N = self._uniform_n(Xa.shape[0], "cbv_correct_optimized")
+        B, K = len(self), Xa.shape[1]
+        lo, hi = float(alpha_bounds[0]), float(alpha_bounds[1])
+        if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
+            raise ValueError("alpha_bounds must be two finite penalties, lower first (got %r)" % (tuple(alpha_bounds),))
+        if int(max_iter) < 1:
+            raise ValueError("max_iter must be >= 1 (got %r)" % (max_iter,))
+        t_over, t_under = float(target_over_score), float(target_under_score)
+        do_over, do_under = t_over > 0, t_under > 0
+        if do_under and neighbors is None:
+            raise ValueError("target_under_score > 0 needs `neighbors` (and `neighbor_batch`, or this batch's own targets corrected "
+                             "at neighbor_alpha): pass target_under_score=0 to search on the over-fitting metric alone")
+        if not np.isfinite(float(neighbor_alpha)):
+            raise ValueError("neighbor_alpha must be finite (got %r)" % (neighbor_alpha,))
+        if getattr(self, "d_flux_err", None) is None:
+            raise ValueError("cbv_correct_optimized needs flux errors (the ridge width is median(flux_err) / sqrt(|alpha|))")
+        _N, keep_idx, n, grid = self._overfit_checks(self, 10, cadence_mask, frequency, seed, first_target, stream_id)
+        nb = Bn = None
+        if do_under:
+            Bn = B if neighbor_batch is None else _neighbor_batch_rows(neighbor_batch, N, "cbv_correct_optimized")
+            nb = _capi.underfit_arguments(B, N, neighbors, cadence_mask, Bn)[0]
+        fit_mask = None if cadence_mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cadence_mask, dtype=bool), (B, N)),
+                                                                          dtype=np.uint8)
+        # ---- resident once: X, the masks, the neighbour rows, the over-fitting session
+        h, st = self.handle, _vp(self.stream or None)
+        keep = []
+        d_X, k = _upload(h, Xa, self.stream)
+        keep.append(k)
+        d_cm = d_keep = d_nb = d_rows = d_sess = None
+        if fit_mask is not None:
+            d_cm, k = _upload(h, fit_mask, self.stream, np.uint8)
+            keep.append(k)
+        if keep_idx is not None:
+            d_keep, k = _upload(h, keep_idx, self.stream, np.int32)
+            keep.append(k)
+        p_keep = _vp(d_keep.ptr if d_keep is not None else None)
+
+        def fit(alphas):
+            held = []
+            d_mu, d_sg = self._ridge_prior(N, K, None, alphas, held)
+            out = self._regress_shared(Xa, N, d_mu, d_sg, None, sigma, niters, False, held, resident=(d_X, d_cm))[0]
+            return out
+
+        if do_over:
+            if grid is None:
+                t0 = self.d_time.download(np.float64, N, stream=self.stream)
+                frequency = _capi.overfit_default_grid(t0 if keep_idx is None else t0[keep_idx])
+                grid = _capi.overfit_grid(frequency)
+            sess_bytes, _r = ctypes.c_int64(0), ctypes.c_int(0)
+            _capi._check(_capi._lib.lk_overfit_session_bytes(B, n, grid[2], 1, int(max_scratch_bytes or 0), ctypes.byref(sess_bytes),
+                                                             ctypes.byref(_r)))
+            sess_bytes = sess_bytes.value
+            d_sess = DeviceBuffer(h, sess_bytes)
+            _capi._check(_capi._lib.lk_overfit_session_begin_dev(
+                h._h, B, N, _vp(self.d_time.ptr), _vp(self.d_flux.ptr), n, p_keep, grid[0], grid[1], grid[2], 1, int(seed),
+                int(first_target), int(stream_id), _vp(d_sess.ptr), sess_bytes, st))
+        if do_under:
+            if neighbor_batch is None:
+                neighbor_batch = self.cbv_correct(cbvs, cbv_indices=cbv_indices, alpha=neighbor_alpha, ext_dm=ext_dm,
+                                                  cadence_mask=fit_mask, sigma=sigma, niters=niters)[0]
+            M = nb.shape[1]
+            if M:
+                d_nb, k = _upload(h, nb, self.stream, np.int32)
+                keep.append(k)
+            d_rows = neighbor_batch._underfit_rows(N, n, d_keep, self.stream)
+        # ---- the lockstep search
+        brent = BoundedBrentBatch((lo, hi), B, maxiter=int(max_iter))
+        d_scores = DeviceBuffer(h, 2 * B * 8)
+        scores = np.ones((2, B))
+        trace = dict(alpha=[], over=[], under=[])
+        while not brent.done.all():
+            alphas = brent.x.copy()
+            cor = fit(alphas)
+            if do_over:
+                _capi._check(_capi._lib.lk_overfit_session_eval_dev(
+                    h._h, B, N, _vp(cor.d_flux.ptr), _vp(cor.d_flux_err.ptr), n, p_keep, grid[0], grid[1], grid[2], 1,
+                    _vp(d_sess.ptr), sess_bytes, _vp(d_scores.ptr), st))
+            if do_under:
+                cor._underfit_against(N, n, d_keep, Bn, d_rows, M, d_nb, d_metric=d_scores, metric_offset=B * 8)
+            if do_over and do_under:
+                d_scores.download(np.float64, 2 * B, out=scores.reshape(-1), stream=self.stream)
+            elif do_over or do_under:
+                d_scores.download(np.float64, B, out=scores[0 if do_over else 1], stream=self.stream,
+                                  offset_bytes=0 if do_over else B * 8)
+            cor.synchronize()
+            brent.tell(-(_leaky_scores(scores[0], t_over) + _leaky_scores(scores[1], t_under)))
+            if return_trace:
+                trace["alpha"].append(alphas), trace["over"].append(scores[0].copy()), trace["under"].append(scores[1].copy())
+        res = brent.result()
+        # ---- the fit at the optimum and its scores
+        out = fit(res["x"])
+        over, under = np.full(B, -1.0), np.full(B, -1.0)
+        if do_over:
+            over = out.over_fitting_metric(self, frequency=frequency, n_samples=10, cadence_mask=cadence_mask, seed=seed,
+                                           first_target=first_target, stream_id=stream_id, max_scratch_bytes=max_scratch_bytes)
+        if do_under:
+            under = out._underfit_against(N, n, d_keep, Bn, d_rows, M, d_nb).download(np.float64, B, stream=self.stream)
+        out._keep += keep + [d_keep, d_nb, d_rows, None if neighbor_batch is None else neighbor_batch.d_flux]
+        info = dict(alpha=res["x"], over_fitting_score=over, under_fitting_score=under, objective=res["fun"], nfev=res["nfev"],
+                    status=res["status"])
+        if return_trace:
+            info["trace"] = {k: np.array(v, dtype=np.float64).reshape(len(v), B) for k, v in trace.items()}
+        return out, info
 
     # ---------------------------------------------------------------- Lomb-Scargle
     def _ls_ready(self):
@@ -1301,6 +1496,35 @@ def _design_arrays(X, prior_mu, prior_sigma):
     if prior_mu is not None:
         prior_mu, prior_sigma = np.asarray(prior_mu, dtype=np.float64), np.asarray(prior_sigma, dtype=np.float64)
     return Xa, prior_mu, prior_sigma
+
+
+def _alpha_per_target(alpha, B):
+    """One ridge penalty per target -> float64[B]; ``ValueError`` unless B finite, non-zero values."""
+    a = np.ascontiguousarray(alpha, dtype=np.float64)
+    if a.shape != (B,):
+        raise ValueError("alpha must be a scalar or one penalty per target, shape (%d,) (got shape %s)" % (B, a.shape))
+    if not np.all(np.isfinite(a)) or np.any(a == 0.0):
+        raise ValueError("every alpha of an array must be finite and non-zero (no prior is the scalar alpha == 0.0)")
+    return a
+
+
+def _leaky_scores(metric, target, leak=0.01):
+    """``correctors.cbvcorrector._leaky`` on an array of scores: above the target a score counts with 1 % of its excess."""
+    if target > 0:
+        return np.where(metric >= target, target + leak * (metric - target), metric)
+    return metric
+
+
+def _neighbor_batch_rows(neighbor_batch, N, what):
+    """The checks of a ``neighbor_batch`` that need no device -> its number of rows."""
+    if not isinstance(neighbor_batch, DeviceLightCurveBatch):
+        raise ValueError("%s: `neighbor_batch` must be a resident DeviceLightCurveBatch" % what)
+    Nn = neighbor_batch._uniform_n(None, "%s (neighbor_batch)" % what)
+    if Nn != N:
+        raise ValueError("%s: neighbor_batch has %d cadences per target, this batch has %d" % (what, Nn, N))
+    if not getattr(neighbor_batch, "nan_free", False):
+        raise ValueError("%s needs a NaN-free neighbor_batch: call remove_nans() first (and cotrend after it)" % what)
+    return len(neighbor_batch)
 
 
 def _cbv_columns(cbvs, cbv_indices, ext_dm):

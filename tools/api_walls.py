@@ -27,7 +27,16 @@ cadences on the default grid with `LK_WALLS_SAMPLES` (default 10) noise samples,
 a synchronise, H the host route (download both batches, then `overfit_metric_lombscargle` per target; its noise is numpy's, so H
 and R agree in distribution, not in value; the loop is sequential: every one of its calls launches on the one handle, which serves
 one call at a time, so the 16 threads of `underfit`'s host route, which is host arithmetic only, do not apply).  `overfit_trace`: only resident calls — the run to put under
-`rocprofv3 --kernel-trace --stats`, in a run of its own, for the split between the LS passes and the metric's own kernels."""
+`rocprofv3 --kernel-trace --stats`, in a run of its own, for the split between the LS passes and the metric's own kernels.
+
+`cbvopt`: the per-target ridge search (`DeviceLightCurveBatch.cbv_correct_optimized`) of `LK_WALLS_B` (default 1000) targets x
+`LK_WALLS_N` (default 20000) cadences on `LK_WALLS_K` (default 16) basis vectors + constant with `LK_WALLS_M` (default 50)
+neighbours each and the default bounds, in ONE process, alternating, `LK_WALLS_REPS` (default 3) times after one warm-up: O the
+whole call (the neighbours' own correction, the session's begin, the search, the final fit and its scores), S
+`cbv_goodness_scan(n_samples=1)` over as many penalties as the search took lockstep evaluations (what driving the resident calls
+one penalty at a time costs: three periodograms, the noise and the medians of all rows per penalty).  Prints the evaluation
+counts.  `cbvopt_trace`: one search cut at `LK_WALLS_ITERS` (default 6) evaluations — the run to put under
+`rocprofv3 --kernel-trace --stats`, in a run of its own, for what lies between two regressions."""
 import cProfile
 import io
 import os
@@ -278,6 +287,53 @@ def overfit(which):
     sys.stdout.flush()
 
 
+def cbvopt(which):
+    from lightkurve_amd import _capi
+    from lightkurve_amd.correctors import metrics
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    B, N, K, M = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000"), ("LK_WALLS_K", "16"),
+                                                         ("LK_WALLS_M", "50")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "3"))
+    rng = np.random.default_rng(7)
+    t = np.linspace(0, 27, N)
+    x = t / 27 - 0.5
+    S = np.column_stack([np.sin(2 * np.pi * t / p) for p in np.linspace(3.1, 41.0, K - 1)] + [x ** 2])
+    amp = rng.normal(0, 0.01, (B, K)) * (np.arange(K) < 4)          # four vectors carry systematics, the rest can only over-fit
+    y = 1000.0 * rng.uniform(0.5, 2, (B, 1)) * (1 + amp @ S.T + 1e-3 * rng.normal(0, 1, (B, N)))
+    nb = metrics.nearest_neighbors(rng.uniform(0, 1, B), rng.uniform(0, 1, B), M)
+    raw = DeviceLightCurveBatch.from_arrays(np.tile(t, B), y.reshape(-1), (1e-3 * y).reshape(-1), np.arange(B + 1) * N).remove_nans()
+    raw.synchronize()
+    sync = _capi.Handle.get(0).synchronize
+    kw = dict(neighbors=nb, cbv_indices=np.arange(1, K + 1))
+    shape = "%d targets x %d cadences, %d basis vectors + constant, %d neighbours, bounds (1e-4, 1e4)" % (B, N, K, nb.shape[1])
+    if "cbvopt_trace" in which:
+        iters = int(os.environ.get("LK_WALLS_ITERS", "6"))
+        _out, info = raw.cbv_correct_optimized(S, max_iter=iters, **kw)
+        sync()
+        print("cbvopt_trace: one search cut at %d evaluations (status %s) on %s" % (iters, sorted(set(info["status"].tolist())), shape))
+        return
+    _out, info = raw.cbv_correct_optimized(S, **kw)                          # warm-up; the search is deterministic
+    steps = int(info["nfev"].max())
+    alphas = np.logspace(-4, 4, steps)
+    raw.cbv_goodness_scan(S, alphas[:2], neighbors=nb, cbv_indices=np.arange(1, K + 1), n_samples=1)
+    sync()
+    O, Sc = [], []
+    for _ in range(reps):
+        O.append(timed(lambda: (raw.cbv_correct_optimized(S, **kw), sync()))[0])
+        Sc.append(timed(lambda: (raw.cbv_goodness_scan(S, alphas, neighbors=nb, cbv_indices=np.arange(1, K + 1), n_samples=1), sync()))[0])
+    print("per-target ridge search, %s" % shape)
+    print("  evaluations per target: min %d median %d max %d (= lockstep evaluations); status counts %s"
+          % (info["nfev"].min(), int(np.median(info["nfev"])), steps, np.bincount(info["status"], minlength=3).tolist()))
+    print("  alpha: min %.3g median %.3g max %.3g; over-fitting score median %.4f, under-fitting score median %.4f"
+          % (info["alpha"].min(), float(np.median(info["alpha"])), info["alpha"].max(), float(np.median(info["over_fitting_score"])),
+             float(np.median(info["under_fitting_score"]))))
+    print("  O  batch.cbv_correct_optimized(), the whole call                  %s" % spread(O))
+    print("  S  batch.cbv_goodness_scan(%d penalties, n_samples=1)             %s" % (steps, spread(Sc)))
+    print("  O per lockstep evaluation %.2f ms, S per penalty %.2f ms; S / O = %.2f"
+          % (1e3 * np.median(O) / steps, 1e3 * np.median(Sc) / steps, np.median(Sc) / np.median(O)))
+    sys.stdout.flush()
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -291,6 +347,8 @@ def main():
         underfit(which)
     if {"overfit", "overfit_trace"} & set(which):
         overfit(which)
+    if {"cbvopt", "cbvopt_trace"} & set(which):
+        cbvopt(which)
     if "flatten" in which:
         lcs = []
         for i in range(1000):
