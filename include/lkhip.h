@@ -356,6 +356,32 @@ int lk_transit_mask_batch(lk_handle *h, int B, const int64_t *n_off, const doubl
 int lk_transit_mask_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const int32_t *planet_off,
                               const double *period, const double *duration, const double *transit_time, uint8_t *mask,
                               void *stream);
+/* BoxLeastSquaresPeriodogram.compute_stats / get_transit_model (periodogram.py:1194-1269 over astropy
+ * BoxLeastSquares.compute_stats / .model, bls/core.py:332-570) of ONE box per target: period / duration / transit_time
+ * (absolute, like `time`) are HOST arrays of length B, positive and finite with duration < period.  time / flux / ivar: the
+ * packed batch WITHOUT NaN flux, times sorted per light curve (unsorted input stays in bounds, its per-transit results are
+ * unspecified); ivar NULL = ones.  stats[b][LK_BLS_NSTATS], in order:
+ *    0 depth             1 its error        2 depth_phased       3 its error        4 depth_half      5 its error
+ *    6 depth_odd         7 its error        8 depth_even         9 its error       10 harmonic_amplitude
+ *   11 harmonic_delta_log_likelihood       12 y_in (model level inside)            13 y_out (outside)
+ *   14 number of in-transit cadences       15 reserved, 0
+ * A depth whose mask is empty (or whose out-of-transit variance is not finite) is (0, inf) as in the reference; columns 10
+ * and 11 are NaN for a light curve of fewer than three cadences or a singular harmonic fit.
+ * Per transit: target b owns entries [tr_off[b], tr_off[b+1]) of tr_count / tr_ll; floor((t_last - t_first) / period) + 3
+ * entries always suffice.  tr_first[b] = the smallest transit id round((t - transit_time) / period) of an in-transit cadence
+ * (may be negative), tr_n[b] = the number of ids up to the largest; entry k of the slot = cadence count and log-likelihood
+ * gain of transit tr_first[b] + k (0 / 0.0 for a transit inside a data gap), the unused tail zeroed.  tr_n[b] = 0: no
+ * cadence in transit; tr_n[b] = -1: the ids do not fit the slot (the slot is zeroed, nothing beyond it is written).
+ * model: NULL, or [n] = y_in inside the transits and y_out outside.  Every sum's order depends on the target's own data
+ * alone: a target's outputs do not change with B or with its neighbours in the batch. */
+#define LK_BLS_NSTATS 16
+int lk_bls_stats_batch(lk_handle *h, int B, const int64_t *n_off, const double *time, const double *flux, const double *ivar,
+                       const double *period, const double *duration, const double *transit_time, const int64_t *tr_off,
+                       double *stats, int32_t *tr_first, int32_t *tr_n, int32_t *tr_count, double *tr_ll, double *model);
+int lk_bls_stats_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux,
+                           const double *ivar, const double *period, const double *duration, const double *transit_time,
+                           const int64_t *tr_off_host, double *stats, int32_t *tr_first, int32_t *tr_n, int32_t *tr_count,
+                           double *tr_ll, double *model, void *stream);
 /* LightCurve.bin (:1558-1763) over astropy aggregate_downsample (astropy@4.3.1 timeseries/downsample.py:12-125), times
  * sorted.  Target b gets bins [bin_off[b], bin_off[b+1]) of the outputs; its bins start at time_bin_start[b] [d] and their
  * edges, in seconds relative to it, are edges_sec[0 .. n_bins_b] (HOST; numpy's cumsum of the bin size, shared by all

@@ -90,6 +90,10 @@ SIGNATURES = [
     ("lk_compact_columns_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, _c_ip, _c_ip, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     ("lk_gather_f64_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _vp, _c_dp, _vp]),
+    ("lk_bls_stats_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_ip, _c_dp, _c_i32p, _c_i32p, _c_i32p, _c_dp, _c_dp]),
+    ("lk_bls_stats_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_ip, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("lk_shader_clock_mhz", ctypes.c_int, [_vp, ctypes.c_double, _c_dp]),
     ("lk_host_alloc", ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_size_t]),
     ("lk_host_free", ctypes.c_int, [_vp]),
@@ -1233,6 +1237,100 @@ def fits_unpack_cube(raw, off_time, code_time, off_quality, code_quality, bitmas
                                     cubes.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), _ptr(kept, _c_ip)))
     k = int(kept[0])
     return t[:k], q[:k], cubes[:, :k, :]
+
+
+BLS_NSTATS = 16                # LK_BLS_NSTATS (include/lkhip.h): columns of lk_bls_stats_batch's stats
+_BLS_STAT_PAIRS = (("depth", 0), ("depth_phased", 2), ("depth_half", 4), ("depth_odd", 6), ("depth_even", 8))
+
+
+def bls_stats_arguments(B, period, duration, transit_time):
+    """The per-target box of ``lk_bls_stats_batch``: each of ``period`` / ``duration`` / ``transit_time`` a scalar or one value
+    per target -> three float64[B]; positive finite periods and durations with duration < period, or ``ValueError``."""
+    out = []
+    for name, a in (("period", period), ("duration", duration), ("transit_time", transit_time)):
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.size != B):
+            raise ValueError("%s must be a scalar or one value per light curve (%d), got shape %r" % (name, B, a.shape))
+        out.append(np.ascontiguousarray(np.broadcast_to(a, (B,))))
+    period, duration, transit_time = out
+    if not (np.all(np.isfinite(period)) and np.all(np.isfinite(duration)) and np.all(np.isfinite(transit_time))):
+        raise ValueError("period, duration and transit_time must be finite")
+    if not (np.all(period > 0) and np.all(duration > 0)):
+        raise ValueError("period and duration must be positive")
+    return period, duration, transit_time
+
+
+def bls_stats_slots(t_first, t_last, period):
+    """tr_off[B + 1]: target b's per-transit slot holds floor((t_last - t_first) / period) + 3 entries, which covers every
+    transit id a box of that period can give to cadences between its first and last time."""
+    span = np.maximum(np.asarray(t_last, dtype=np.float64) - np.asarray(t_first, dtype=np.float64), 0.0)
+    cap = np.floor(span / period) + 3
+    if len(cap) and not cap.max() < 2 ** 31:
+        raise ValueError("a period of %g d gives more than 2^31 transits over the light curve" % float(period[np.argmax(cap)]))
+    tr_off = np.zeros(len(cap) + 1, dtype=np.int64)
+    tr_off[1:] = np.cumsum(cap.astype(np.int64))
+    return tr_off
+
+
+def bls_stats_dict(stats, tr_first, tr_n, tr_off, tr_count, tr_ll, period, transit_time, t_first):
+    """The raw outputs of ``lk_bls_stats_batch`` -> the dict of ``DeviceBLSResult.compute_stats``: the slots compacted into
+    packed per-transit arrays (``transit_off[B + 1]``), transit times absolute, formed like the reference's
+    (period * id + (transit_time - t[0])) + t[0]).  ``tr_n = -1`` (ids that do not fit their slot): ``RuntimeError``."""
+    B = len(tr_n)
+    if np.any(tr_n < 0):
+        raise RuntimeError("light curve %d: the transit ids do not fit the per-transit slot" % int(np.argmax(tr_n < 0)))
+    out = {k: np.ascontiguousarray(stats[:, c:c + 2]) for k, c in _BLS_STAT_PAIRS}
+    out["harmonic_amplitude"] = stats[:, 10].copy()
+    out["harmonic_delta_log_likelihood"] = stats[:, 11].copy()
+    n_tr = tr_n.astype(np.int64)
+    off = np.zeros(B + 1, dtype=np.int64)
+    off[1:] = np.cumsum(n_tr)
+    src = np.repeat(tr_off[:-1] - off[:-1], n_tr) + np.arange(off[-1])        # slot entry of every packed entry
+    ids = np.repeat(tr_first.astype(np.int64) - off[:-1], n_tr) + np.arange(off[-1])
+    rep = lambda v: np.repeat(v, n_tr)
+    out["n_transits"] = n_tr
+    out["transit_off"] = off
+    out["transit_times"] = (rep(period) * ids + rep(transit_time - t_first)) + rep(t_first)
+    out["per_transit_count"] = tr_count[src].astype(np.int64)
+    out["per_transit_log_likelihood"] = tr_ll[src]
+    return out
+
+
+def bls_stats_batch(t, flux, ivar, n_off, period, duration, transit_time, want_model=False, tr_off=None, raw=False, device=0):
+    """``BoxLeastSquaresPeriodogram.compute_stats`` of one box per light curve for B ragged, time-sorted, NaN-free light
+    curves on the host (``lk_bls_stats_batch``).  ``t`` / ``transit_time`` absolute; ``ivar`` None = ones; ``period`` /
+    ``duration`` / ``transit_time``: scalars or one value per target.  Returns the dict of ``DeviceBLSResult.compute_stats``
+    (``want_model``: plus ``model``, the box model per cadence).  ``tr_off``: per-transit slots other than
+    ``bls_stats_slots``'s; ``raw``: the C outputs as they are (stats, tr_first, tr_n, tr_off, tr_count, tr_ll, model)."""
+    h = Handle.get(device)
+    t, flux = _f64(t), _f64(flux)
+    n_off = _offsets(n_off, t.size)
+    if flux.shape != t.shape or (ivar is not None and np.shape(ivar) != t.shape):
+        raise ValueError("t, flux, ivar must be 1-D arrays of one length")
+    ivar = None if ivar is None else _f64(ivar)
+    B = n_off.size - 1
+    period, duration, transit_time = bls_stats_arguments(B, period, duration, transit_time)
+    counts = np.diff(n_off)
+    if B and counts.min() < 1:
+        raise ValueError("a light curve of the batch has no cadence")
+    t_first, t_last = t[n_off[:-1]], t[n_off[1:] - 1]
+    tr_off = bls_stats_slots(t_first, t_last, period) if tr_off is None else np.ascontiguousarray(tr_off, dtype=np.int64)
+    if tr_off.shape != (B + 1,) or tr_off[0] != 0 or np.any(np.diff(tr_off) < 0):
+        raise ValueError("tr_off must be B + 1 non-decreasing prefix offsets starting at 0")
+    ntr = int(tr_off[-1])
+    stats = np.zeros((B, BLS_NSTATS), dtype=np.float64)
+    tr_first, tr_n = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    tr_count, tr_ll = np.zeros(max(ntr, 1), dtype=np.int32), np.zeros(max(ntr, 1), dtype=np.float64)
+    model = np.empty(t.size, dtype=np.float64) if want_model else None
+    _check(_lib.lk_bls_stats_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(t), _ptr(flux), _ptr(ivar), _ptr(period), _ptr(duration),
+                                   _ptr(transit_time), _ptr(tr_off, _c_ip), _ptr(stats), _ptr(tr_first, _c_i32p),
+                                   _ptr(tr_n, _c_i32p), _ptr(tr_count, _c_i32p), _ptr(tr_ll), _ptr(model)))
+    if raw:
+        return stats, tr_first, tr_n, tr_off, tr_count[:ntr], tr_ll[:ntr], model
+    out = bls_stats_dict(stats, tr_first, tr_n, tr_off, tr_count, tr_ll, period, transit_time, t_first)
+    if want_model:
+        out["model"] = model
+    return out
 
 
 def transit_mask_batch(t, n_off, period, duration, transit_time, planet_off=None, device=0):

@@ -8,7 +8,7 @@ from . import _capi
 from .distributed import all_gather_rows, device_gather_available, shard_bounds, sharded_map, sharded_map_ragged
 from . import packed
 
-__all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "periodogram_peaks", "flatten_batch",
+__all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "periodogram_peaks", "flatten_batch",
            "estimate_cdpp_batch", "pld_correct_batch", "regression_correct_batch"]
 
 
@@ -204,6 +204,26 @@ def bls_batch(lcs, period, duration=None, objective="likelihood", oversample=10,
     out = np.stack([res[k] for k in _capi.BLS_FIELDS], axis=1)
     out[:, 4, :] += t_ref[:, None]
     return _finish(out, bounds, gather)
+
+
+def bls_stats_batch(lcs, period, duration, transit_time, device=0):
+    """``BoxLeastSquaresPeriodogram.compute_stats`` of one box per light curve (reference periodogram.py:1194-1229 over
+    astropy compute_stats) for host light curves: ``lcs`` a list of light curves or a ``LightCurveBatch``; ``period`` /
+    ``duration`` / ``transit_time`` (absolute) scalars or one value per light curve.  NaN-flux cadences are dropped and
+    ivar = 1 / flux_err^2 (ones where the errors are not all finite), as for ``bls_batch``; the light curves must be sorted
+    by time.  Returns the dict of ``DeviceBLSResult.compute_stats``.  Not sharded over ranks."""
+    from .ingest import LightCurveBatch
+    if isinstance(lcs, LightCurveBatch):
+        time, flux, err, n_off = lcs.time, lcs.flux, lcs.flux_err, lcs.n_off
+    else:
+        (time, flux, err), n_off = packed.pack_columns(list(lcs), ("time", "flux", "flux_err"), pinned="auto", pool_prefix="blsstats")
+    time, flux, n_off, err = packed.drop_nan_flux(time, flux, n_off, err)
+    counts = np.diff(n_off)
+    if len(counts) and counts.min() < 1:
+        raise ValueError("a light curve of the batch has no finite flux")
+    if not packed.check_sorted(time, n_off):
+        raise ValueError("bls_stats_batch needs every light curve sorted by time")
+    return _capi.bls_stats_batch(time, flux, packed.bls_ivar(flux, err, n_off), n_off, period, duration, transit_time, device=device)
 
 
 def periodogram_peaks(power, device=0):

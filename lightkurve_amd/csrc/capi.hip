@@ -1453,6 +1453,40 @@ int lk_transit_mask_batch(lk_handle *h, int B, const int64_t *n_off, const doubl
     return rc ? rc : io.finish();
 }
 
+int lk_bls_stats_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux,
+                           const double *ivar, const double *period, const double *duration, const double *transit_time,
+                           const int64_t *tr_off_host, double *stats, int32_t *tr_first, int32_t *tr_n, int32_t *tr_count,
+                           double *tr_ll, double *model, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::bls_stats_launch(h, B, n_off_host, time, flux, ivar, period, duration, transit_time, tr_off_host, stats, tr_first,
+                                tr_n, tr_count, tr_ll, model, static_cast<hipStream_t>(stream));
+}
+
+int lk_bls_stats_batch(lk_handle *h, int B, const int64_t *n_off, const double *time, const double *flux, const double *ivar,
+                       const double *period, const double *duration, const double *transit_time, const int64_t *tr_off,
+                       double *stats, int32_t *tr_first, int32_t *tr_n, int32_t *tr_count, double *tr_ll, double *model) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr && tr_off != nullptr, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(n_off[B] >= 0 && tr_off[B] >= 0, "bad batch description");
+    LK_REQUIRE(n_off[B] == 0 || (time && flux), "NULL time or flux");
+    LK_REQUIRE(stats && tr_first && tr_n && tr_count && tr_ll, "NULL output buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B], ntr = (size_t)tr_off[B];
+    const double *dt, *dy, *dw;
+    double *dstats, *dll, *dmodel;
+    int32_t *dfirst, *dn, *dcount;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, time, ntot).in(dy, flux, ntot).in(dw, ivar, ntot).out(dstats, stats, (size_t)B * LK_BLS_NSTATS)
+                 .out(dfirst, tr_first, (size_t)B).out(dn, tr_n, (size_t)B).out(dcount, tr_count, ntr).out(dll, tr_ll, ntr)
+                 .out(dmodel, model, ntot).stage();
+    if (rc) return rc;
+    rc = lk::bls_stats_launch(h, B, n_off, dt, dy, dw, period, duration, transit_time, tr_off, dstats, dfirst, dn, dcount, dll,
+                              dmodel, nullptr);
+    return rc ? rc : io.finish();
+}
+
 int lk_bin_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,
                      const double *flux_err, const int64_t *bin_off, const double *time_bin_start, const double *edges_sec,
                      int64_t n_edges, double bin_size_sec, const uint8_t *has_err, double *t_out, double *flux_out,

@@ -244,6 +244,10 @@ int fits_cube_launch(lk_handle *h, const uint8_t *raw, int row_bytes, int n_rows
 int transit_mask_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const int *p_off_host,
                         const double *period_host, const double *duration_host, const double *transit_time_host,
                         uint8_t *mask, hipStream_t stream);
+int bls_stats_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux, const double *ivar,
+                     const double *period_host, const double *duration_host, const double *transit_time_host,
+                     const int64_t *tr_off_host, double *stats, int32_t *tr_first, int32_t *tr_n, int32_t *tr_count, double *tr_ll,
+                     double *model, hipStream_t stream);
 int bin_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux, const double *err,
                const int64_t *bin_off_host, const double *start_host, const double *edges_host, int64_t n_edges,
                double bin_size_sec, const uint8_t *has_err_host, double *t_out, double *f_out, double *e_out,

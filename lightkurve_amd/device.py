@@ -906,7 +906,7 @@ class DeviceLightCurveBatch(object):
                                               period.ctypes.data_as(_dp), _vp(d_per.ptr), nP, duration.ctypes.data_as(_dp),
                                               len(duration), int(oversample), int(objective == "likelihood"), _vp(d_out.ptr), st))
             src._keep.append(k)
-        return DeviceBLSResult(src, d_out, d_ref, period, duration)
+        return DeviceBLSResult(src, d_out, d_ref, period, duration, d_ivar=d_w)
 
     # ---------------------------------------------------------------- fold / transit mask / bin
     def fold(self, period, epoch_time=None, epoch_phase=0.0, wrap_phase=None, normalize_phase=False):
@@ -1023,10 +1023,11 @@ class DeviceBLSResult(object):
     """out7[7, B, nP] in HBM (``_capi.BLS_FIELDS`` order; transit_time relative to ``t_ref``, the reference's
     ``min(t)`` per light curve) + what a pipeline keeps of it."""
 
-    def __init__(self, batch, d_out7, d_t_ref, period, duration):
+    def __init__(self, batch, d_out7, d_t_ref, period, duration, d_ivar=None):
         self.handle, self.stream, self.B = batch.handle, batch.stream, len(batch)
         self.d_out7, self.d_t_ref, self.period, self.duration = d_out7, d_t_ref, period, duration
-        self._batch = batch
+        self._batch = batch              # the NaN-free batch the search ran on
+        self.d_ivar = d_ivar             # its prepared ivar (lk_bls_prepare_batch_dev); None: ones
 
     def to_host(self):
         """float64[B, 7, nP] as ``batch.bls_batch`` returns it (transit_time absolute, like the reference)."""
@@ -1057,6 +1058,82 @@ class DeviceBLSResult(object):
         got = {k: vals[i * B:(i + 1) * B] for i, k in enumerate(rows)}
         return dict(max_power=mx, argmax=am, period=self.period[a], transit_time=got["transit_time"] + t_ref,
                     duration=got["duration"], depth=got["depth"])
+
+    # ---------------------------------------------------------------- vetting: compute_stats / model / mask
+    def _box(self, period, duration, transit_time):
+        """(period, duration, transit_time)[B]: each a scalar or one value per target; None = the value at the peak."""
+        if period is None or duration is None or transit_time is None:
+            pk = self.peaks()
+            period = pk["period"] if period is None else period
+            duration = pk["duration"] if duration is None else duration
+            transit_time = pk["transit_time"] if transit_time is None else transit_time
+        return _capi.bls_stats_arguments(self.B, period, duration, transit_time)
+
+    def _stats(self, period, duration, transit_time, want_model, tr_off=None):
+        src = self._batch
+        if not src._sorted():
+            raise ValueError("compute_stats / transit_model need every light curve sorted by time")
+        period, duration, transit_time = self._box(period, duration, transit_time)
+        h, B, n, st = self.handle, self.B, src.n_cadences, _vp(self.stream or None)
+        idx = np.concatenate([src.n_off[:-1], np.maximum(src.n_off[1:] - 1, 0)]).astype(np.int64)
+        ends = np.zeros(2 * B, dtype=np.float64)
+        if B and n:
+            _capi._check(_capi._lib.lk_gather_f64_dev(h._h, 2 * B, _off_ptr(np.minimum(idx, n - 1)), _vp(src.d_time.ptr),
+                                                      ends.ctypes.data_as(_dp), st))
+        t_first = ends[:B]
+        if tr_off is None:
+            tr_off = _capi.bls_stats_slots(t_first, ends[B:], period)
+        tr_off = np.ascontiguousarray(tr_off, dtype=np.int64)
+        ntr = int(tr_off[-1])
+        d_stats = DeviceBuffer(h, max(B, 1) * _capi.BLS_NSTATS * 8)
+        d_first, d_n = DeviceBuffer(h, max(B, 1) * 4), DeviceBuffer(h, max(B, 1) * 4)
+        d_cnt, d_ll = DeviceBuffer(h, max(ntr, 1) * 4), DeviceBuffer(h, max(ntr, 1) * 8)
+        d_model = DeviceBuffer(h, max(n, 1) * 8) if want_model else None
+        _capi._check(_capi._lib.lk_bls_stats_batch_dev(
+            h._h, B, _off_ptr(src.n_off), _vp(src.d_time.ptr), _vp(src.d_flux.ptr), _vp(self.d_ivar.ptr if self.d_ivar is not None else None),
+            period.ctypes.data_as(_dp), duration.ctypes.data_as(_dp), transit_time.ctypes.data_as(_dp), _off_ptr(tr_off),
+            _vp(d_stats.ptr), _vp(d_first.ptr), _vp(d_n.ptr), _vp(d_cnt.ptr), _vp(d_ll.ptr),
+            _vp(d_model.ptr if d_model is not None else None), st))
+        return dict(period=period, transit_time=transit_time, t_first=t_first, tr_off=tr_off, d_stats=d_stats, d_first=d_first,
+                    d_n=d_n, d_cnt=d_cnt, d_ll=d_ll, d_model=d_model)
+
+    def compute_stats(self, period=None, duration=None, transit_time=None):
+        """``BoxLeastSquaresPeriodogram.compute_stats`` (reference periodogram.py:1194-1229 over astropy compute_stats) of one
+        box per target, on the resident batch (``lk_bls_stats_batch_dev``).  ``period`` / ``duration`` / ``transit_time``
+        (absolute): a scalar or one value per target; None = the value at the target's maximum power (``peaks()``).
+        Returns a dict of host arrays: ``depth`` / ``depth_phased`` / ``depth_half`` / ``depth_odd`` / ``depth_even``
+        [B, 2] (value, error), ``harmonic_amplitude`` / ``harmonic_delta_log_likelihood`` [B], ``n_transits`` [B],
+        ``transit_off`` [B + 1] and the packed ``transit_times`` (absolute) / ``per_transit_count`` /
+        ``per_transit_log_likelihood``: target b's slice ``[transit_off[b]:transit_off[b + 1]]`` is the array astropy's dict
+        holds.  A target without an in-transit cadence has ``n_transits`` 0 (astropy raises).  The light curves must be sorted
+        by time (``ValueError``)."""
+        r = self._stats(period, duration, transit_time, False)
+        B, ntr = self.B, int(r["tr_off"][-1])
+        stats = r["d_stats"].download(np.float64, B * _capi.BLS_NSTATS, stream=self.stream).reshape(B, _capi.BLS_NSTATS)
+        tr_first = r["d_first"].download(np.int32, B, stream=self.stream)
+        tr_n = r["d_n"].download(np.int32, B, stream=self.stream)
+        tr_count = r["d_cnt"].download(np.int32, ntr, stream=self.stream)
+        tr_ll = r["d_ll"].download(np.float64, ntr, stream=self.stream)
+        return _capi.bls_stats_dict(stats, tr_first, tr_n, r["tr_off"], tr_count, tr_ll, r["period"], r["transit_time"], r["t_first"])
+
+    def transit_model(self, period=None, duration=None, transit_time=None):
+        """``BoxLeastSquaresPeriodogram.get_transit_model`` for every target (reference periodogram.py:1229-1269): a
+        ``DeviceLightCurveBatch`` with the times of the searched batch and the box model as flux (the weighted mean flux
+        inside / outside the transits), resident.  Arguments as in ``compute_stats``."""
+        r = self._stats(period, duration, transit_time, True)
+        src = self._batch
+        out = src._new(src.d_time, r["d_model"], None, src.n_off, nan_free=True, is_sorted=True)
+        for m in out.meta:
+            m["LABEL"] = "Transit Model Flux"
+        return out
+
+    def transit_mask(self, period=None, duration=None, transit_time=None, to_host=True):
+        """``BoxLeastSquaresPeriodogram.get_transit_mask`` for every target: ``create_transit_mask`` of the searched batch
+        with one planet per target (arguments as in ``compute_stats``) -> bool array over its cadences, or the ``DeviceBuffer``
+        of bytes (usable as ``flatten(mask=...)``) with ``to_host=False``."""
+        period, duration, transit_time = self._box(period, duration, transit_time)
+        return self._batch.create_transit_mask(period, transit_time, duration, planet_off=np.arange(self.B + 1, dtype=np.int32),
+                                               to_host=to_host)
 
 
 # ------------------------------------------------------------------------------------------------ pixel cubes

@@ -228,6 +228,18 @@ def _segment_medians(y, n_off):
     return np.array([np.median(y[a:b]) for a, b in zip(n_off[:-1], n_off[1:])])
 
 
+def bls_ivar(flux, flux_err, n_off):
+    """astropy BoxLeastSquares' weights for a packed batch WITHOUT empty light curves: ivar = 1 / err^2, ones for a light
+    curve whose errors are not all finite (or without errors)."""
+    if flux_err is None:
+        return np.ones_like(flux)
+    counts = np.diff(n_off)
+    fin = np.isfinite(flux_err)
+    all_fin = np.logical_and.reduceat(fin, n_off[:-1]) if len(counts) else np.zeros(0, bool)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(np.repeat(all_fin, counts), 1.0 / flux_err ** 2, 1.0)
+
+
 def bls_inputs(time, flux, flux_err, n_off):
     """What ``BoxLeastSquaresPeriodogram.from_lightcurve`` + astropy hand to ``bls_fast`` (reference periodogram.py:
     1093-1100, astropy bls/core.py:277-327), for the whole batch: NaN-flux cadences dropped, t - min(t), y - median(y),
@@ -242,11 +254,4 @@ def bls_inputs(time, flux, flux_err, n_off):
     tmin = np.minimum.reduceat(trel, n_off[:-1]) if len(counts) else np.zeros(0)
     t = trel - rep(tmin)
     y = flux - rep(_segment_medians(flux, n_off))
-    if flux_err is None:
-        ivar = np.ones_like(flux)
-    else:
-        fin = np.isfinite(flux_err)
-        all_fin = np.logical_and.reduceat(fin, n_off[:-1]) if len(counts) else np.zeros(0, bool)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            ivar = np.where(rep(all_fin), 1.0 / flux_err ** 2, 1.0)
-    return t, y, ivar, n_off, tmin + t0
+    return t, y, bls_ivar(flux, flux_err, n_off), n_off, tmin + t0

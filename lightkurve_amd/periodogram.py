@@ -512,6 +512,92 @@ def _bls_plan(lc, **kwargs):
                 duration=duration, oversample=oversample, objective=objective, time_unit=time_unit)
 
 
+def bls_transit_model_host(time, flux, ivar, period, duration, transit_time):
+    """The box model of ``BoxLeastSquaresPeriodogram.get_transit_model`` as a pure host function (astropy
+    BoxLeastSquares.model, bls/core.py:332-387): the ivar-weighted mean flux inside / outside the transit windows, one
+    value per cadence.  ``time`` and ``transit_time`` are absolute; the arithmetic runs on times relative to ``time[0]``,
+    like astropy's.  The reference of ``lk_bls_stats_batch``'s model output."""
+    t0 = float(time[0])                              # astropy works on times relative to the first cadence
+    t = np.asarray(time, dtype=np.float64) - t0
+    tt = float(transit_time) - t0
+    y, ivar = np.asarray(flux, dtype=np.float64), np.asarray(ivar, dtype=np.float64)
+    hp = 0.5 * period
+    m_in = np.abs((t - tt + hp) % period - hp) < 0.5 * duration
+    m_out = ~m_in
+    with np.errstate(invalid="ignore", divide="ignore"):
+        y_in = np.sum(y[m_in] * ivar[m_in]) / np.sum(ivar[m_in])
+        y_out = np.sum(y[m_out] * ivar[m_out]) / np.sum(ivar[m_out])
+    model = y_out + np.zeros_like(t)
+    model[m_in] = y_in
+    return model
+
+
+def bls_compute_stats_host(time, flux, ivar, period, duration, transit_time, singular_harmonic="raise"):
+    """The vetting statistics of ``BoxLeastSquaresPeriodogram.compute_stats`` as a pure host function (astropy
+    BoxLeastSquares.compute_stats, bls/core.py:389-570): same keys, same operations in the same order.  ``time`` and
+    ``transit_time`` are absolute; the arithmetic runs on times relative to ``time[0]``.  The reference of
+    ``lk_bls_stats_batch``.  Raises ``ValueError`` when no cadence is in transit, like astropy.
+    ``singular_harmonic``: ``"raise"`` lets ``numpy.linalg.solve`` raise on a singular harmonic fit (astropy's behaviour);
+    ``"nan"`` gives NaN for the two harmonic entries of a light curve of fewer than three cadences or a singular fit, which
+    is what the batch kernel reports per target."""
+    t0 = float(time[0])                              # astropy works on times relative to the first cadence
+    t = np.asarray(time, dtype=np.float64) - t0
+    tt = float(transit_time) - t0
+    y = np.asarray(flux, dtype=np.float64)
+    ivar = np.asarray(ivar, dtype=np.float64)
+
+    def _compute_depth(m, y_out=None, var_out=None):
+        if np.any(m) and (var_out is None or np.isfinite(var_out)):
+            var_m = 1.0 / np.sum(ivar[m])
+            y_m = np.sum(y[m] * ivar[m]) * var_m
+            if y_out is None:
+                return y_m, var_m
+            return y_out - y_m, np.sqrt(var_m + var_out)
+        return 0.0, np.inf
+
+    hp = 0.5 * period
+    m_in = np.abs((t - tt + hp) % period - hp) < 0.5 * duration
+    m_out = ~m_in
+    m_odd = np.abs((t - tt) % (2 * period) - period) < 0.5 * duration
+    m_even = np.abs((t - tt + period) % (2 * period) - period) < 0.5 * duration
+    y_out, var_out = _compute_depth(m_out)
+    depth = _compute_depth(m_in, y_out, var_out)
+    depth_odd = _compute_depth(m_odd, y_out, var_out)
+    depth_even = _compute_depth(m_even, y_out, var_out)
+    y_in = y_out - depth[0]
+    m_phase = np.abs((t - tt) % period - hp) < 0.5 * duration
+    depth_phase = _compute_depth(m_phase, *_compute_depth((~m_phase) & m_out))
+    m_half = np.abs((t - tt + 0.25 * period) % (0.5 * period) - 0.25 * period) < 0.5 * duration
+    depth_half = _compute_depth(m_half, *_compute_depth(~m_half))
+    transit_id = np.round((t[m_in] - tt) / period).astype(int)
+    transit_times = period * np.arange(transit_id.min(), transit_id.max() + 1) + tt
+    unique_ids, unique_counts = np.unique(transit_id, return_counts=True)
+    unique_ids -= np.min(transit_id)
+    transit_id -= np.min(transit_id)
+    counts = np.zeros(np.max(transit_id) + 1, dtype=int)
+    counts[unique_ids] = unique_counts
+    ll = -0.5 * ivar[m_in] * ((y[m_in] - y_in) ** 2 - (y[m_in] - y_out) ** 2)
+    lls = np.zeros(len(counts))
+    for i in unique_ids:
+        lls[i] = np.sum(ll[transit_id == i])
+    full_ll = -0.5 * np.sum(ivar[m_in] * (y[m_in] - y_in) ** 2)
+    full_ll -= 0.5 * np.sum(ivar[m_out] * (y[m_out] - y_out) ** 2)
+    A = np.vstack((np.sin(2 * np.pi * t / period), np.cos(2 * np.pi * t / period), np.ones_like(t))).T
+    try:
+        if singular_harmonic == "nan" and len(t) < 3:
+            raise np.linalg.LinAlgError("fewer than three cadences")
+        w = np.linalg.solve(np.dot(A.T, A * ivar[:, None]), np.dot(A.T, y * ivar))
+    except np.linalg.LinAlgError:
+        if singular_harmonic != "nan":
+            raise
+        w = np.full(3, np.nan)
+    sin_ll = -0.5 * np.sum((y - np.dot(A, w)) ** 2 * ivar)
+    return dict(transit_times=transit_times + t0, per_transit_count=counts, per_transit_log_likelihood=lls,
+                depth=depth, depth_phased=depth_phase, depth_half=depth_half, depth_odd=depth_odd,
+                depth_even=depth_even, harmonic_amplitude=np.sqrt(np.sum(w[:2] ** 2)),
+                harmonic_delta_log_likelihood=sin_ll - full_ll)
+
+
 class BoxLeastSquaresPeriodogram(Periodogram):
     """BLS periodogram computed by the bit-exact HIP kernel (reference periodogram.py:1021-1296)."""
 
@@ -576,18 +662,7 @@ class BoxLeastSquaresPeriodogram(Periodogram):
         if transit_time is None:
             transit_time = self.transit_time_at_max_power
             log.warning("No transit time specified. Using transit time at max power")
-        t0 = float(self.time[0])                         # astropy works on times relative to the first cadence
-        t = np.asarray(self.time, dtype=np.float64) - t0
-        tt = float(transit_time) - t0
-        y, ivar = np.asarray(self.flux, dtype=np.float64), self._BLS_inputs["ivar"]
-        hp = 0.5 * period
-        m_in = np.abs((t - tt + hp) % period - hp) < 0.5 * duration
-        m_out = ~m_in
-        with np.errstate(invalid="ignore", divide="ignore"):
-            y_in = np.sum(y[m_in] * ivar[m_in]) / np.sum(ivar[m_in])
-            y_out = np.sum(y[m_out] * ivar[m_out]) / np.sum(ivar[m_out])
-        model = y_out + np.zeros_like(t)
-        model[m_in] = y_in
+        model = bls_transit_model_host(self.time, self.flux, self._BLS_inputs["ivar"], period, duration, transit_time)
         return LightCurve(time=self.time, flux=model, label="Transit Model Flux")
 
     def compute_stats(self, period=None, duration=None, transit_time=None):
@@ -609,55 +684,7 @@ class BoxLeastSquaresPeriodogram(Periodogram):
             raise ValueError("period and duration must be positive")
         if duration >= period:
             raise ValueError("The maximum transit duration must be shorter than the minimum period")
-        t0 = float(self.time[0])                         # astropy works on times relative to the first cadence
-        t = np.asarray(self.time, dtype=np.float64) - t0
-        tt = float(transit_time) - t0
-        y = np.asarray(self.flux, dtype=np.float64)
-        ivar = np.asarray(self._BLS_inputs["ivar"], dtype=np.float64)
-
-        def _compute_depth(m, y_out=None, var_out=None):
-            if np.any(m) and (var_out is None or np.isfinite(var_out)):
-                var_m = 1.0 / np.sum(ivar[m])
-                y_m = np.sum(y[m] * ivar[m]) * var_m
-                if y_out is None:
-                    return y_m, var_m
-                return y_out - y_m, np.sqrt(var_m + var_out)
-            return 0.0, np.inf
-
-        hp = 0.5 * period
-        m_in = np.abs((t - tt + hp) % period - hp) < 0.5 * duration
-        m_out = ~m_in
-        m_odd = np.abs((t - tt) % (2 * period) - period) < 0.5 * duration
-        m_even = np.abs((t - tt + period) % (2 * period) - period) < 0.5 * duration
-        y_out, var_out = _compute_depth(m_out)
-        depth = _compute_depth(m_in, y_out, var_out)
-        depth_odd = _compute_depth(m_odd, y_out, var_out)
-        depth_even = _compute_depth(m_even, y_out, var_out)
-        y_in = y_out - depth[0]
-        m_phase = np.abs((t - tt) % period - hp) < 0.5 * duration
-        depth_phase = _compute_depth(m_phase, *_compute_depth((~m_phase) & m_out))
-        m_half = np.abs((t - tt + 0.25 * period) % (0.5 * period) - 0.25 * period) < 0.5 * duration
-        depth_half = _compute_depth(m_half, *_compute_depth(~m_half))
-        transit_id = np.round((t[m_in] - tt) / period).astype(int)
-        transit_times = period * np.arange(transit_id.min(), transit_id.max() + 1) + tt
-        unique_ids, unique_counts = np.unique(transit_id, return_counts=True)
-        unique_ids -= np.min(transit_id)
-        transit_id -= np.min(transit_id)
-        counts = np.zeros(np.max(transit_id) + 1, dtype=int)
-        counts[unique_ids] = unique_counts
-        ll = -0.5 * ivar[m_in] * ((y[m_in] - y_in) ** 2 - (y[m_in] - y_out) ** 2)
-        lls = np.zeros(len(counts))
-        for i in unique_ids:
-            lls[i] = np.sum(ll[transit_id == i])
-        full_ll = -0.5 * np.sum(ivar[m_in] * (y[m_in] - y_in) ** 2)
-        full_ll -= 0.5 * np.sum(ivar[m_out] * (y[m_out] - y_out) ** 2)
-        A = np.vstack((np.sin(2 * np.pi * t / period), np.cos(2 * np.pi * t / period), np.ones_like(t))).T
-        w = np.linalg.solve(np.dot(A.T, A * ivar[:, None]), np.dot(A.T, y * ivar))
-        sin_ll = -0.5 * np.sum((y - np.dot(A, w)) ** 2 * ivar)
-        return dict(transit_times=transit_times + t0, per_transit_count=counts, per_transit_log_likelihood=lls,
-                    depth=depth, depth_phased=depth_phase, depth_half=depth_half, depth_odd=depth_odd,
-                    depth_even=depth_even, harmonic_amplitude=np.sqrt(np.sum(w[:2] ** 2)),
-                    harmonic_delta_log_likelihood=sin_ll - full_ll)
+        return bls_compute_stats_host(self.time, self.flux, self._BLS_inputs["ivar"], period, duration, transit_time)
 
     def get_transit_mask(self, period=None, duration=None, transit_time=None):
         """True where the box model is in transit (reference periodogram.py:1271-1292)."""

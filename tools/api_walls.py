@@ -36,7 +36,12 @@ whole call (the neighbours' own correction, the session's begin, the search, the
 `cbv_goodness_scan(n_samples=1)` over as many penalties as the search took lockstep evaluations (what driving the resident calls
 one penalty at a time costs: three periodograms, the noise and the medians of all rows per penalty).  Prints the evaluation
 counts.  `cbvopt_trace`: one search cut at `LK_WALLS_ITERS` (default 6) evaluations — the run to put under
-`rocprofv3 --kernel-trace --stats`, in a run of its own, for what lies between two regressions."""
+`rocprofv3 --kernel-trace --stats`, in a run of its own, for what lies between two regressions.
+
+`blsstats`: the vetting tail of a resident BLS survey on `LK_WALLS_B` (default 1000) targets x `LK_WALLS_N` (default 20000)
+cadences after a search on `LK_WALLS_P` (default 256) periods x 3 durations (the search is not timed), with `wall()`'s
+repetitions: R the resident tail `result.compute_stats()` (peaks, the statistics kernel, the per-target numbers back), H the host
+route (download time, flux and ivar, then `bls_compute_stats_host` per target at the same boxes)."""
 import cProfile
 import io
 import os
@@ -334,6 +339,40 @@ def cbvopt(which):
     sys.stdout.flush()
 
 
+def blsstats():
+    from lightkurve_amd import _capi, synth
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    from lightkurve_amd.periodogram import bls_compute_stats_host
+    B, N, nP = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000"), ("LK_WALLS_P", "256")))
+    cols = [synth.bls_target(3, i, N)[:3] for i in range(B)]
+    n_off = np.arange(B + 1, dtype=np.int64) * N
+    raw = DeviceLightCurveBatch.from_arrays(*(np.concatenate([c[k] for c in cols]) for k in range(3)), n_off)
+    periods = 1.0 / np.linspace(1 / 13.0, 1 / 0.6, nP)[::-1]
+    res = raw.bls(periods, duration=[0.05, 0.1, 0.2])
+    pk = res.peaks()
+    sync = _capi.Handle.get(0).synchronize
+    sync()
+    src = res._batch
+
+    def host_route():
+        t, y = src.time_host(), src.flux_host()
+        w = res.d_ivar.download(np.float64, src.n_cadences, stream=src.stream)
+        out = []
+        for b in range(B):
+            a, z = int(src.n_off[b]), int(src.n_off[b + 1])
+            out.append(bls_compute_stats_host(t[a:z], y[a:z], w[a:z], pk["period"][b], pk["duration"][b], pk["transit_time"][b]))
+        return out
+
+    r_ms, r_prof = wall(lambda: (res.compute_stats(), sync()))
+    h_ms, h_prof = wall(host_route)
+    print("BLS vetting statistics after a resident search, %d targets x %d cadences (search: %d periods x 3 durations, not timed)"
+          % (B, N, nP))
+    print("  R  result.compute_stats(), resident tail                              %10.1f ms per call" % r_ms)
+    print("  H  download 3 columns + bls_compute_stats_host per target             %10.1f ms per call" % h_ms)
+    print("  H / R = %.1f\n%s\n%s\n" % (h_ms / r_ms, r_prof, h_prof))
+    sys.stdout.flush()
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -349,6 +388,8 @@ def main():
         overfit(which)
     if {"cbvopt", "cbvopt_trace"} & set(which):
         cbvopt(which)
+    if "blsstats" in which:
+        blsstats()
     if "flatten" in which:
         lcs = []
         for i in range(1000):
