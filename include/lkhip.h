@@ -315,6 +315,35 @@ int lk_sigma_clip_batch(lk_handle *h, int B, const int64_t *n_off, const double 
                         uint8_t *outlier);
 int lk_sigma_clip_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *y, double sigma, int maxiters,
                             uint8_t *outlier, void *stream);
+/* LightCurve.remove_outliers(sigma_lower=, sigma_upper=) (:1430-1556): astropy.stats.sigma_clip(y, sigma_lower=, sigma_upper=,
+ * maxiters=, cenfunc=median, stdfunc=std).mask (astropy@4.3.1 stats/sigma_clipping.py:_sigmaclip_noaxis) per ragged row.  From
+ * the finite values, each round keeps cen - std * sigma_lower <= x <= cen + std * sigma_upper (cen = median, std =
+ * sqrt(mean((x - mean)^2)) of what is kept; equality keeps) until a round removes nothing or maxiters rounds have run
+ * (maxiters < 0: no cap, astropy's maxiters=None).  outlier[i] = 1 where the value is not finite or outside the last bounds.
+ * Empty rows and rows without a finite value are fine (every cadence of the latter is flagged). */
+int lk_outlier_mask_batch(lk_handle *h, int B, const int64_t *n_off, const double *y, double sigma_lower, double sigma_upper,
+                          int maxiters, uint8_t *outlier);
+int lk_outlier_mask_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *y, double sigma_lower,
+                              double sigma_upper, int maxiters, uint8_t *outlier, void *stream);
+/* lc[mask] / lc[~mask] (boolean-array indexing of a LightCurve, as in the tutorial's second-planet search
+ * lc[~bls.get_transit_mask(...)]) for the columns of a resident batch: cadence i is kept where (mask[i] != 0) != invert, order
+ * preserved, cols_out[c][new_off[b] + k] = the k-th kept element of light curve b in cols_in[c].  ncols <= 8 device pointers
+ * in two HOST arrays, elem_bytes[c] (HOST) 4 or 8; every cols_out[c] holds as many elements as cols_in[c] and overlaps no
+ * input, no other output and not the mask (LK_EINVAL).  new_off_host (B + 1, HOST) is written before the call returns: the
+ * call synchronises `stream`, as lk_ingest_batch_dev does. */
+int lk_select_columns_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const uint8_t *mask, int invert, int ncols,
+                                const int *elem_bytes, const void *const *cols_in, void *const *cols_out,
+                                int64_t *new_off_host, void *stream);
+/* The tail of LightCurve.estimate_cdpp (:1764-1833) per ragged row of an already flattened flux, on the cadences with
+ * outlier[i] == 0 (outlier NULL: all of them) in their original order: ppm = kept / median(kept) * 1e6 (normalize("ppm"),
+ * :1216-1292); the n_kept - w + 1 running means of w = min(transit_duration, n_kept) consecutive values (running_mean,
+ * utils.py:374-386, as differences of a prefix sum); cdpp_out[b] = their population standard deviation (np.std, two passes).
+ * n_kept == 0 gives NaN; transit_duration < 1 is LK_EINVAL.  The order of every sum follows from the row's own values alone:
+ * a row's result has the same bits for any B, any position in the batch and any run.  cdpp_out: B doubles. */
+int lk_cdpp_batch(lk_handle *h, int B, const int64_t *n_off, const double *flat_flux, const uint8_t *outlier,
+                  int transit_duration, double *cdpp_out);
+int lk_cdpp_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *flat_flux, const uint8_t *outlier,
+                      int transit_duration, double *cdpp_out, void *stream);
 /* lk_fits_unpack_batch: what the reference's light-curve readers do per file through astropy — Table.read of the BINTABLE
  * (src/lightkurve/io/generic.py:21-207), drop the rows whose TIME is NaN (:98-101), drop the cadences whose quality flag
  * hits the bitmask (io/kepler.py:49-53, io/tess.py:45-48, utils.py:79-115) — for B files at once.  `raw`: the tables' bytes

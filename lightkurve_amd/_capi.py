@@ -118,6 +118,14 @@ SIGNATURES = [
      [_vp, ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _c_i32p, ctypes.c_int, _vp, _vp, _vp]),
     ("lk_sigma_clip_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _c_dp, ctypes.c_double, ctypes.c_int, _c_u8p]),
     ("lk_sigma_clip_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _vp, ctypes.c_double, ctypes.c_int, _vp, _vp]),
+    ("lk_outlier_mask_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, _c_u8p]),
+    ("lk_outlier_mask_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp]),
+    ("lk_select_columns_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, ctypes.c_int, ctypes.c_int, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_ip, _vp]),
+    ("lk_cdpp_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _c_dp, _c_u8p, ctypes.c_int, _c_dp]),
+    ("lk_cdpp_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _vp, _vp, ctypes.c_int, _vp, _vp]),
     ("lk_ingest_batch", ctypes.c_int,
      [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_ip, _c_dp]),
     ("lk_ingest_batch_dev", ctypes.c_int,
@@ -1172,6 +1180,55 @@ def sigma_clip_batch(y, n_off, sigma=5.0, maxiters=5, device=0):
     _check(_lib.lk_sigma_clip_batch(h._h, n_off.size - 1, _ptr(n_off, _c_ip), _ptr(y), float(sigma), int(maxiters),
                                     _ptr(out, _c_u8p)))
     return out.astype(bool)
+
+
+def clip_bounds(sigma=5.0, sigma_lower=None, sigma_upper=None, maxiters=5):
+    """(sigma_lower, sigma_upper, maxiters) as the C ABI takes them: ``None`` bounds fall back to ``sigma`` (astropy's
+    rule), ``maxiters=None`` ("until nothing changes") becomes -1."""
+    lo = float(sigma if sigma_lower is None else sigma_lower)
+    hi = float(sigma if sigma_upper is None else sigma_upper)
+    if np.isnan(lo) or np.isnan(hi):
+        raise ValueError("sigma, sigma_lower and sigma_upper must not be NaN")
+    if maxiters is None:
+        return lo, hi, -1
+    if int(maxiters) < 0:
+        raise ValueError("maxiters must be >= 0 or None (got %r)" % (maxiters,))
+    return lo, hi, int(maxiters)
+
+
+def outlier_mask_batch(y, n_off, sigma=5.0, sigma_lower=None, sigma_upper=None, maxiters=5, device=0):
+    """astropy.stats.sigma_clip(y_b, sigma, sigma_lower, sigma_upper, maxiters).mask for B ragged arrays -> bool[sum N]
+    (True = clipped / non-finite); ``maxiters=None``: until a round removes nothing."""
+    lo, hi, mi = clip_bounds(sigma, sigma_lower, sigma_upper, maxiters)
+    h = Handle.get(device)
+    y = _f64(y)
+    n_off = _offsets(n_off, y.size)
+    out = np.zeros(y.size, dtype=np.uint8)
+    _check(_lib.lk_outlier_mask_batch(h._h, n_off.size - 1, _ptr(n_off, _c_ip), _ptr(y), lo, hi, mi, _ptr(out, _c_u8p)))
+    return out.astype(bool)
+
+
+def cdpp_batch(flat_flux, n_off, outlier=None, transit_duration=13, device=0):
+    """The tail of ``LightCurve.estimate_cdpp`` (reference lightcurve.py:1764-1833) for B ragged, already flattened rows:
+    ppm of the cadences ``outlier`` (bool / uint8 over all cadences, None: none) leaves, running mean over
+    ``transit_duration`` cadences, np.std -> float64[B] (NaN for a row with nothing left)."""
+    if not isinstance(transit_duration, (int, np.integer)) or isinstance(transit_duration, bool):
+        raise ValueError("transit_duration must be an integer in units number of cadences, got {}.".format(transit_duration))
+    if transit_duration < 1:
+        raise ValueError("transit_duration must be >= 1 cadence (got %d)" % transit_duration)
+    y = _f64(flat_flux)
+    n_off = _offsets(n_off, y.size)
+    B = n_off.size - 1
+    m = None
+    if outlier is not None:
+        m = np.ascontiguousarray(outlier, dtype=np.uint8)
+        if m.shape != y.shape:
+            raise ValueError("outlier must have one entry per cadence (got shape %s, need %s)" % (m.shape, y.shape))
+    h = Handle.get(device)
+    out = np.empty(B, dtype=np.float64)
+    _check(_lib.lk_cdpp_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(y), None if m is None else _ptr(m, _c_u8p),
+                              int(transit_duration), _ptr(out)))
+    return out
 
 
 def ingest_batch(t, flux, n_off, flux_err=None, normalize=True, device=0):

@@ -1318,6 +1318,69 @@ int lk_sigma_clip_batch(lk_handle *h, int B, const int64_t *n_off, const double 
     return rc ? rc : io.finish();
 }
 
+// ------------------------------------------------------------------------------------------------ select.hip
+int lk_outlier_mask_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *y, double sigma_lower,
+                              double sigma_upper, int maxiters, uint8_t *outlier, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::outlier_mask_launch(h, B, n_off_host, y, sigma_lower, sigma_upper, maxiters, outlier,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int lk_outlier_mask_batch(lk_handle *h, int B, const int64_t *n_off, const double *y, double sigma_lower, double sigma_upper,
+                          int maxiters, uint8_t *outlier) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr, "bad batch description");
+    if (B == 0 || n_off[B] == 0) return LK_OK;
+    LK_REQUIRE(n_off[0] == 0 && n_off[B] > 0, "n_off must be prefix offsets starting at 0");
+    LK_REQUIRE(y && outlier, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B];
+    const double *dy;
+    uint8_t *dm;
+    lk::StagedCall io(h);
+    int rc = io.in(dy, y, ntot).out(dm, outlier, ntot).stage();
+    if (rc) return rc;
+    rc = lk::outlier_mask_launch(h, B, n_off, dy, sigma_lower, sigma_upper, maxiters, dm, nullptr);
+    return rc ? rc : io.finish();
+}
+
+int lk_select_columns_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const uint8_t *mask, int invert, int ncols,
+                                const int *elem_bytes, const void *const *cols_in, void *const *cols_out,
+                                int64_t *new_off_host, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::select_columns_launch(h, B, n_off_host, mask, invert, ncols, elem_bytes, cols_in, cols_out, new_off_host,
+                                     static_cast<hipStream_t>(stream));
+}
+
+int lk_cdpp_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *flat_flux, const uint8_t *outlier,
+                      int transit_duration, double *cdpp_out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cdpp_launch(h, B, n_off_host, flat_flux, outlier, transit_duration, cdpp_out, static_cast<hipStream_t>(stream));
+}
+
+int lk_cdpp_batch(lk_handle *h, int B, const int64_t *n_off, const double *flat_flux, const uint8_t *outlier,
+                  int transit_duration, double *cdpp_out) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr, "bad batch description");
+    LK_REQUIRE(transit_duration >= 1, "transit_duration must be >= 1 cadence (got %d)", transit_duration);
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(n_off[0] == 0 && n_off[B] >= 0, "n_off must be prefix offsets starting at 0");
+    LK_REQUIRE(cdpp_out != nullptr && (flat_flux != nullptr || n_off[B] == 0), "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B];
+    const double *df;
+    const uint8_t *dm;
+    double *dc;
+    lk::StagedCall io(h);
+    int rc = io.in(df, flat_flux, ntot).in(dm, outlier, ntot).out(dc, cdpp_out, (size_t)B).stage();
+    if (rc) return rc;
+    rc = lk::cdpp_launch(h, B, n_off, df, dm, transit_duration, dc, nullptr);
+    return rc ? rc : io.finish();
+}
+
 // ------------------------------------------------------------------------------------------------ batch ingest (N4)
 int lk_ingest_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,
                         const double *flux_err, int normalize, double *t_out, double *flux_out, double *flux_err_out,

@@ -70,6 +70,11 @@ __global__ __launch_bounds__(1024) void ingest_scan_kernel(const int64_t *__rest
     }
 }
 
+// new_off[0..B] = exclusive prefix sums of kept[0..B) (device arrays), queued on `stream`: shared with select.hip
+void exscan_i64_launch(const int64_t *kept, int B, int64_t *new_off, hipStream_t stream) {
+    hipLaunchKernelGGL(ingest_scan_kernel, dim3(1), dim3(1024), 0, stream, kept, B, new_off);
+}
+
 __global__ __launch_bounds__(512) void ingest_pack_kernel(const double *__restrict__ t, const double *__restrict__ flux,
                                                            const double *__restrict__ err, const int64_t *__restrict__ n_off,
                                                            const int64_t *__restrict__ new_off, int normalize,

@@ -235,6 +235,21 @@ int sigma_clip_launch(lk_handle *h, int B, const int64_t *n_off_host, const doub
 int ingest_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux, const double *err,
                   int normalize, double *t_out, double *f_out, double *e_out, int64_t *new_off_host, double *median_out,
                   hipStream_t stream);
+// new_off[0..B] = exclusive prefix sums of kept[0..B), both on the device (ingest.hip's one-workgroup scan)
+void exscan_i64_launch(const int64_t *kept, int B, int64_t *new_off, hipStream_t stream);
+// select.hip: astropy.stats.sigma_clip(y, sigma_lower=, sigma_upper=, maxiters=, cenfunc=median, stdfunc=std).mask per ragged
+// row (maxiters < 0: until nothing changes); nothing of the batch's size is carved
+int outlier_mask_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *y, double sigma_lower, double sigma_upper,
+                        int maxiters, uint8_t *outlier, hipStream_t stream);
+// select.hip: lc[mask] (invert: lc[~mask]) for up to 8 columns of 4- or 8-byte elements; new_off_host is valid on return
+// (synchronises `stream`)
+int select_columns_launch(lk_handle *h, int B, const int64_t *n_off_host, const uint8_t *mask, int invert, int ncols,
+                          const int *elem_bytes, const void *const *cols_in, void *const *cols_out, int64_t *new_off_host,
+                          hipStream_t stream);
+// select.hip: the tail of LightCurve.estimate_cdpp (lightcurve.py:1764-1833, utils.py:374-386) on the cadences outlier[]
+// leaves (nullable: all), cdpp_out[B] on the device
+int cdpp_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *flat_flux, const uint8_t *outlier,
+                int transit_duration, double *cdpp_out, hipStream_t stream);
 int fits_unpack_launch(lk_handle *h, int B, const uint8_t *raw, const int64_t *raw_off_host, const int32_t *desc_host,
                        const int64_t *bitmask_host, double *t_out, double *f_out, double *e_out, int32_t *q_out,
                        int64_t *new_off_host, hipStream_t stream);

@@ -386,6 +386,86 @@ class DeviceLightCurveBatch(object):
             return out, tr
         return out
 
+    # ---------------------------------------------------------------- outliers / select / CDPP
+    def outlier_mask(self, sigma=5.0, sigma_lower=None, sigma_upper=None, maxiters=5, to_host=False):
+        """``astropy.stats.sigma_clip(flux, sigma, sigma_lower, sigma_upper, maxiters).mask`` per light curve (what
+        ``LightCurve.remove_outliers`` removes, reference :1430-1556): 1 = clipped or not finite -> ``DeviceBuffer`` of bytes
+        over this batch's cadences (usable as ``select(mask, invert=True)`` / ``flatten(mask=...)``), or a host bool array
+        with ``to_host=True``.  ``None`` bounds fall back to ``sigma``; ``maxiters=None``: until a round removes nothing."""
+        lo, hi, mi = _capi.clip_bounds(sigma, sigma_lower, sigma_upper, maxiters)
+        h, n = self.handle, self.n_cadences
+        d_m = DeviceBuffer(h, max(n, 1))
+        _capi._check(_capi._lib.lk_outlier_mask_batch_dev(h._h, len(self), _off_ptr(self.n_off), _vp(self.d_flux.ptr), lo, hi, mi,
+                                                          _vp(d_m.ptr), _vp(self.stream or None)))
+        if not to_host:
+            return d_m
+        return d_m.download(np.uint8, n, stream=self.stream).astype(bool)
+
+    def select(self, mask, invert=False):
+        """``lc[mask]`` (``invert``: ``lc[~mask]``) for every light curve, resident: ``mask`` is a host bool / uint8 array over
+        the ``n_cadences`` of this batch or a ``DeviceBuffer`` of that many bytes (``outlier_mask`` /
+        ``DeviceBLSResult.transit_mask(to_host=False)`` / ``create_transit_mask(to_host=False)``).  time, flux, flux_err and
+        the quality flags are repacked in HBM, order kept (``lk_select_columns_batch_dev``; the call synchronises: the new
+        offsets come back).  ``median_flux`` does not carry over."""
+        h, B, n = self.handle, len(self), self.n_cadences
+        if isinstance(mask, DeviceBuffer):
+            if mask.nbytes != max(n, 1):
+                raise ValueError("mask holds %d bytes, the batch has %d cadences" % (mask.nbytes, n))
+            d_m = mask
+        else:
+            mk = np.asarray(mask)
+            if mk.dtype != np.bool_ and mk.dtype != np.uint8:
+                raise ValueError("mask must be a bool or uint8 array (got %s)" % mk.dtype)
+            if mk.shape != (n,):
+                raise ValueError("mask must have one entry per cadence (got shape %s, need (%d,))" % (mk.shape, n))
+            d_m, _k = _upload(h, mk, self.stream, np.uint8)
+        cols = [(self.d_time, 8), (self.d_flux, 8)]
+        if self.d_flux_err is not None:
+            cols.append((self.d_flux_err, 8))
+        if self.d_quality is not None:
+            cols.append((self.d_quality, 4))
+        outs = [DeviceBuffer(h, max(n, 1) * eb) for _c, eb in cols]
+        cin = (_vp * len(cols))(*[c.ptr for c, _eb in cols])
+        cout = (_vp * len(cols))(*[c.ptr for c in outs])
+        elem = np.ascontiguousarray([eb for _c, eb in cols], dtype=np.int32)
+        new_off = np.zeros(B + 1, dtype=np.int64)
+        _capi._check(_capi._lib.lk_select_columns_batch_dev(h._h, B, _off_ptr(self.n_off), _vp(d_m.ptr), int(bool(invert)), len(cols),
+                                                            elem.ctypes.data_as(_i32p), cin, cout, _off_ptr(new_off),
+                                                            _vp(self.stream or None)))      # (synchronises)
+        it = iter(outs[2:])
+        d_e = next(it) if self.d_flux_err is not None else None
+        out = self._new(outs[0], outs[1], d_e, new_off, nan_free=self.nan_free, is_sorted=self.is_sorted)
+        out.d_quality = next(it) if self.d_quality is not None else None
+        return out
+
+    def remove_outliers(self, sigma=5.0, sigma_lower=None, sigma_upper=None, return_mask=False, maxiters=5):
+        """``lc.remove_outliers(sigma, sigma_lower, sigma_upper)`` for every light curve (reference :1430-1556), resident:
+        ``select(outlier_mask(...), invert=True)``; a cadence whose flux is not finite goes too.  ``return_mask``: also the
+        mask's ``DeviceBuffer`` (bytes over the cadences of THIS batch, 1 = removed)."""
+        d_m = self.outlier_mask(sigma, sigma_lower, sigma_upper, maxiters)
+        out = self.select(d_m, invert=True)
+        out.nan_free = True
+        return (out, d_m) if return_mask else out
+
+    def estimate_cdpp(self, transit_duration=13, savgol_window=101, savgol_polyorder=2, sigma=5.0):
+        """``lc.estimate_cdpp(...)`` in ppm for every light curve (reference :1764-1833; ``lightcurve.estimate_cdpp_batch`` for
+        a resident batch): flatten -> sigma clip -> ppm -> std of the ``transit_duration``-cadence running mean, all in HBM
+        (``lk_savgol_trend_batch_dev``, ``lk_outlier_mask_batch_dev``, ``lk_cdpp_batch_dev``) -> float64[B] on the host: 8
+        bytes per target cross PCIe.  NaN for a light curve with no cadence left."""
+        if not isinstance(transit_duration, int):
+            raise ValueError("transit_duration must be an integer in units number of cadences, got {}.".format(transit_duration))
+        if transit_duration < 1:
+            raise ValueError("transit_duration must be >= 1 cadence (got %d)" % transit_duration)
+        d_tr = self.flatten_trend(savgol_window, savgol_polyorder)
+        h, B, n, st = self.handle, len(self), self.n_cadences, _vp(self.stream or None)
+        d_f, d_m, d_c = DeviceBuffer(h, max(n, 1) * 8), DeviceBuffer(h, max(n, 1)), DeviceBuffer(h, max(B, 1) * 8)
+        _capi._check(_capi._lib.lk_flatten_apply_batch_dev(h._h, n, _vp(self.d_flux.ptr), None, _vp(d_tr.ptr), _vp(d_f.ptr), None, st))
+        lo, hi, mi = _capi.clip_bounds(sigma, None, None, 5)
+        _capi._check(_capi._lib.lk_outlier_mask_batch_dev(h._h, B, _off_ptr(self.n_off), _vp(d_f.ptr), lo, hi, mi, _vp(d_m.ptr), st))
+        _capi._check(_capi._lib.lk_cdpp_batch_dev(h._h, B, _off_ptr(self.n_off), _vp(d_f.ptr), _vp(d_m.ptr), int(transit_duration),
+                                                  _vp(d_c.ptr), st))
+        return d_c.download(np.float64, B, stream=self.stream)
+
     # ---------------------------------------------------------------- cotrending on one shared design matrix
     def _uniform_n(self, rows, what):
         """The one cadence count of the batch, checked against the ``rows`` of the shared design matrix unless ``rows`` is None
@@ -907,6 +987,23 @@ class DeviceLightCurveBatch(object):
                                               len(duration), int(oversample), int(objective == "likelihood"), _vp(d_out.ptr), st))
             src._keep.append(k)
         return DeviceBLSResult(src, d_out, d_ref, period, duration, d_ivar=d_w)
+
+    def bls_search(self, period, n_signals=2, duration=None, objective="likelihood", oversample=10):
+        """The tutorial's planet-by-planet search (``lc[~bls.get_transit_mask(...)]`` then BLS again) for every light curve,
+        resident: ``n_signals`` times ``bls(...)`` -> ``peaks()`` -> ``transit_mask(to_host=False)`` at each target's own peak ->
+        ``select(mask, invert=True)``.  Returns (signals, residual): the list of the ``peaks()`` dicts, strongest signal
+        first, and the batch without the transits of every signal found.  Per round only the peaks cross PCIe.  A light curve
+        that has lost every cadence makes the next round's ``bls`` raise its ``ValueError``."""
+        if int(n_signals) < 1:
+            raise ValueError("n_signals must be >= 1 (got %r)" % (n_signals,))
+        cur, signals = self, []
+        for _ in range(int(n_signals)):
+            res = cur.bls(period, duration, objective, oversample)
+            pk = res.peaks()
+            d_m = res.transit_mask(pk["period"], pk["duration"], pk["transit_time"], to_host=False)
+            signals.append(pk)
+            cur = res._batch.select(d_m, invert=True)
+        return signals, cur
 
     # ---------------------------------------------------------------- fold / transit mask / bin
     def fold(self, period, epoch_time=None, epoch_phase=0.0, wrap_phase=None, normalize_phase=False):

@@ -107,6 +107,20 @@ class LightCurveBatch(object):
             m["NORMALIZED"] = True
         return out
 
+    def remove_outliers(self, sigma=5.0, sigma_lower=None, sigma_upper=None, return_mask=False, maxiters=5, device=0):
+        """``lc.remove_outliers(sigma, sigma_lower, sigma_upper)`` for every light curve (reference :1430-1556; astropy
+        sigma_clip with median / std, NaN flux counts as an outlier): ONE lk_outlier_mask_batch call, then the kept cadences
+        of every column.  ``maxiters=None``: until a round removes nothing.  ``return_mask``: also the bool mask over the
+        cadences of THIS batch (True = removed)."""
+        mask = _capi.outlier_mask_batch(self.flux, self.n_off, sigma=sigma, sigma_lower=sigma_lower, sigma_upper=sigma_upper,
+                                        maxiters=maxiters, device=device)
+        keep = ~mask
+        off = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)[self.n_off]      # kept cadences before each light curve
+        out = LightCurveBatch(self.time[keep], self.flux[keep], self.flux_err[keep], off, [dict(m) for m in self.meta])
+        if self.quality is not None:
+            out.quality = np.ascontiguousarray(np.asarray(self.quality)[keep])
+        return (out, mask) if return_mask else out
+
     def create_transit_mask(self, period, transit_time, duration, planet_off=None, device=0):
         """Boolean array over all cadences of the batch, True in transit (reference :2967-3037).  Scalars / 1-D arrays
         apply to every light curve; with ``planet_off`` each light curve gets its own planets."""

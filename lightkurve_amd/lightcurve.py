@@ -85,12 +85,18 @@ class LightCurve(object):
         lc.meta["NORMALIZED"] = True
         return lc
 
-    def remove_outliers(self, sigma=5.0, return_mask=False, maxiters=5, device=0):
+    def remove_outliers(self, sigma=5.0, sigma_lower=None, sigma_upper=None, return_mask=False, maxiters=5, device=0):
         """Light curve without the cadences astropy.stats.sigma_clip flags (median centre, std width, ``maxiters``
         rounds; NaN flux counts as an outlier) — reference :1430-1556, the default ``corrector_func`` of
-        ``TargetPixelFile.plot_pixels``; the clip runs on the GPU (lk_sigma_clip_batch)."""
+        ``TargetPixelFile.plot_pixels``; the clip runs on the GPU (lk_sigma_clip_batch).  ``sigma_lower`` / ``sigma_upper``:
+        separate bounds below / above the median (``None``: ``sigma``), e.g. ``sigma_upper=3, sigma_lower=20`` clips
+        flares and keeps transits; ``maxiters=None``: until a round removes nothing (lk_outlier_mask_batch)."""
         from . import _capi
-        mask = _capi.sigma_clip_batch(self.flux, [0, len(self)], sigma=sigma, maxiters=maxiters, device=device)
+        if sigma_lower is None and sigma_upper is None and maxiters is not None:
+            mask = _capi.sigma_clip_batch(self.flux, [0, len(self)], sigma=sigma, maxiters=maxiters, device=device)
+        else:
+            mask = _capi.outlier_mask_batch(self.flux, [0, len(self)], sigma=sigma, sigma_lower=sigma_lower,
+                                            sigma_upper=sigma_upper, maxiters=maxiters, device=device)
         return (self[~mask], mask) if return_mask else self[~mask]
 
     def bin(self, time_bin_size=0.5, time_bin_start=None, device=0):

@@ -41,7 +41,16 @@ counts.  `cbvopt_trace`: one search cut at `LK_WALLS_ITERS` (default 6) evaluati
 `blsstats`: the vetting tail of a resident BLS survey on `LK_WALLS_B` (default 1000) targets x `LK_WALLS_N` (default 20000)
 cadences after a search on `LK_WALLS_P` (default 256) periods x 3 durations (the search is not timed), with `wall()`'s
 repetitions: R the resident tail `result.compute_stats()` (peaks, the statistics kernel, the per-target numbers back), H the host
-route (download time, flux and ivar, then `bls_compute_stats_host` per target at the same boxes)."""
+route (download time, flux and ivar, then `bls_compute_stats_host` per target at the same boxes).
+
+`clean`: the transit-search front of `LK_WALLS_B` (default 1000) targets x `LK_WALLS_N` (default 20000) cadences with 0.5 % of
+up-going outliers, in ONE process, the routes alternating, `LK_WALLS_REPS` (default 3) times after one warm-up.  C the resident
+chain `normalize().flatten(401).remove_outliers().to_periodogram_peaks(f)` on `LK_WALLS_M` (default 4096) frequencies; C_H the
+same with the clip staged through the host, as it had to be without `remove_outliers`: `to_host()`, the sigma clip in numpy per
+target, boolean indexing, `from_arrays`.  S `bls_search(periods, n_signals=2)` on `LK_WALLS_P` (default 64) periods x 3
+durations of the flattened batch; S_H the same loop with `to_host()`, numpy `~mask` indexing and `from_arrays` between the
+rounds.  `cdpp`: R `batch.estimate_cdpp()`; H `to_host()` + `lightcurve.estimate_cdpp_batch` on the list of light curves
+(flatten and clip on the GPU from host arrays, the tail in numpy per target).  Results: profiles/clean_walls.txt."""
 import cProfile
 import io
 import os
@@ -373,6 +382,106 @@ def blsstats():
     sys.stdout.flush()
 
 
+def clean_field():
+    """(resident batch of B x N with transits, noise and 0.5 % up-going outliers, B, N)."""
+    from lightkurve_amd import synth
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    B, N = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000")))
+    rng = np.random.default_rng(11)
+    cols = [synth.bls_target(3, i, N)[:3] for i in range(B)]
+    t, f, e = (np.concatenate([c[k] for c in cols]) for k in range(3))
+    f = f + np.where(rng.random(f.size) < 0.005, 8.0 * np.median(e), 0.0)
+    return DeviceLightCurveBatch.from_arrays(t, f, e, np.arange(B + 1, dtype=np.int64) * N), B, N
+
+
+def clean():
+    from lightkurve_amd import _capi
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    from oracle import np_oracle as O
+    reps = int(os.environ.get("LK_WALLS_REPS", "3"))
+    M, nP = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_M", "4096"), ("LK_WALLS_P", "64")))
+    raw, B, N = clean_field()
+    sync = _capi.Handle.get(0).synchronize
+    freq = 0.02 + 0.002 * np.arange(M)
+    periods = 1.0 / np.linspace(1 / 13.0, 1 / 0.6, nP)[::-1]
+    durations = [0.05, 0.1, 0.2]
+
+    def without(batch, mask):
+        """``batch`` without the cadences of ``mask`` (host bool), through the host."""
+        host = batch.to_host()
+        keep = ~mask
+        off = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)[host.n_off]
+        return DeviceLightCurveBatch.from_arrays(host.time[keep], host.flux[keep], host.flux_err[keep], off)
+
+    def chain():
+        return raw.normalize().flatten(401).remove_outliers().to_periodogram_peaks(freq)
+
+    def chain_host():
+        flat = raw.normalize().flatten(401)
+        flux, off = flat.flux_host(), flat.n_off
+        with np.errstate(all="ignore"):
+            mask = np.concatenate([O.sigma_clip_mask(flux[off[b]:off[b + 1]]) for b in range(B)])
+        return without(flat, mask).to_periodogram_peaks(freq)
+
+    flat = raw.normalize().flatten(401)
+    flat.synchronize()
+
+    def search():
+        return flat.bls_search(periods, n_signals=2, duration=durations)
+
+    def search_host():
+        cur, signals = flat, []
+        for _ in range(2):
+            res = cur.bls(periods, duration=durations)
+            pk = res.peaks()
+            signals.append(pk)
+            cur = without(res._batch, res.transit_mask(pk["period"], pk["duration"], pk["transit_time"]))
+        return signals, cur
+
+    fns = {"C": chain, "C_H": chain_host, "S": search, "S_H": search_host}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    sync()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(lambda: (fn(), sync()))[0])
+    same_c = bool(np.array_equal(first["C"], first["C_H"]))
+    same_s = all(np.array_equal(a[k], b[k]) for a, b in zip(first["S"][0], first["S_H"][0]) for k in a) and bool(
+        np.array_equal(first["S"][1].flux_host(), first["S_H"][1].flux_host()))
+    print("transit-search front, %d targets x %d cadences (%.0f MB per float64 column)" % (B, N, B * N * 8 / 1e6))
+    print("  C    normalize().flatten(401).remove_outliers().to_periodogram_peaks(%d frequencies)   %s" % (M, spread(ts["C"])))
+    print("  C_H  the same, the clip through the host (to_host, numpy per target, from_arrays)       %s" % spread(ts["C_H"]))
+    print("  S    flattened.bls_search(%d periods x 3 durations, n_signals=2)                        %s" % (nP, spread(ts["S"])))
+    print("  S_H  the same loop, to_host / numpy ~mask / from_arrays between the rounds               %s" % spread(ts["S_H"]))
+    print("  C == C_H: %s; S == S_H: %s; C_H / C = %.2f; S_H / S = %.2f"
+          % (same_c, same_s, np.median(ts["C_H"]) / np.median(ts["C"]), np.median(ts["S_H"]) / np.median(ts["S"])))
+    sys.stdout.flush()
+
+
+def cdpp():
+    from lightkurve_amd import _capi
+    from lightkurve_amd.lightcurve import estimate_cdpp_batch
+    reps = int(os.environ.get("LK_WALLS_REPS", "3"))
+    raw, B, N = clean_field()
+    sync = _capi.Handle.get(0).synchronize
+
+    def host_route():
+        return estimate_cdpp_batch(raw.to_host().to_lightcurves())
+
+    got, ref = raw.estimate_cdpp(), host_route()                          # warm-up of both routes
+    sync()
+    R, H = [], []
+    for _ in range(reps):
+        R.append(timed(lambda: raw.estimate_cdpp())[0])                    # (the download synchronises)
+        H.append(timed(host_route)[0])
+    print("estimate_cdpp, %d targets x %d cadences" % (B, N))
+    print("  R  batch.estimate_cdpp() -> cdpp[B] on the host                               %s" % spread(R))
+    print("  H  to_host() + estimate_cdpp_batch(list of light curves)                      %s" % spread(H))
+    print("  max |R - H| / H = %.3e; median CDPP %.1f ppm; H / R = %.1f"
+          % (float(np.max(np.abs(got - ref) / ref)), float(np.median(got)), np.median(H) / np.median(R)))
+    sys.stdout.flush()
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -390,6 +499,10 @@ def main():
         cbvopt(which)
     if "blsstats" in which:
         blsstats()
+    if "clean" in which:
+        clean()
+    if "cdpp" in which:
+        cdpp()
     if "flatten" in which:
         lcs = []
         for i in range(1000):
