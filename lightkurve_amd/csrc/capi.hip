@@ -246,6 +246,7 @@ void lk_destroy(lk_handle *h) {
     if (h->ev_ls_fork) (void)hipEventDestroy(h->ev_ls_fork);
     if (h->clk_buf) (void)hipHostFree(h->clk_buf);
     if (h->flat_tab_dev) (void)hipFree(h->flat_tab_dev);
+    if (h->ls_roots) (void)hipFree(h->ls_roots);
     h->ws.release();
     h->staging.release();
     delete h;

@@ -97,6 +97,9 @@ struct lk_handle {
     // device.hip: lk_shader_clock_mhz's own stream and 16 pinned bytes (kept: freeing either would synchronise the device)
     hipStream_t s_probe = nullptr;
     unsigned long long *clk_buf = nullptr;
+    // lsfast.hip: the 1024th roots of unity (1024 x double2, cos | sin), filled once per handle: the column kernel's
+    // workgroup-uniform pre-twiddles are read from it through scalar loads
+    double *ls_roots = nullptr;
 };
 
 namespace lk {

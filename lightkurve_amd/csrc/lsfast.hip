@@ -632,8 +632,9 @@ __global__ __launch_bounds__(256) void fft_cols_reg_kernel(double2 *__restrict__
 // full-length kernel above), and the workgroups are small enough for 2 waves per SIMD.  The input column is loaded
 // once and kept in registers over the Q passes; rows keep their natural order k1 = Q q + s.  A grid with rows_used <= P / 2 (the
 // two df grids whenever the 2 df grid decided P) takes a second copy of the pass loop that neither pre-twiddles the zero half of
-// the input nor runs the first butterfly stage over it (reg_fft<LA, true>): 550 fp64 instructions per pass against 646 at LP = 8.
+// the input nor runs the first butterfly stage over it (reg_fft<LA, true>): 508 fp64 instructions per pass against 572 at LP = 8.
 constexpr int PRUNED_CT = 16;
+constexpr int LSF_LOG_NROOTS = 10, LSF_NROOTS = 1 << LSF_LOG_NROOTS;  // the handle's table of roots of unity (lsf_roots_kernel)
 
 constexpr int LSF_CHUNK_HALF_GB = 3;  // bytes of grids per chunk, in units of 2^29 (1.5 GiB = 60 targets at Nfft = 2^19)
 
@@ -651,7 +652,7 @@ __global__ __launch_bounds__(PRUNED_CT * (1 << ((LP + 1) / 2)), 2) void fft_cols
     const double2 *__restrict__ grids, int m1, int m2, const int *__restrict__ rows_used, double2 *__restrict__ gout,
     const double *__restrict__ t, const double *__restrict__ y, const double *__restrict__ dy,
     const int64_t *__restrict__ n_off, const FastStats *__restrict__ stats, int b0, double f0, double df, int fit_mean,
-    const int *__restrict__ tab16, int ntab16) {
+    const int *__restrict__ tab16, int ntab16, const double2 *__restrict__ roots) {
     extern __shared__ __attribute__((aligned(16))) double2 lds2[];
     constexpr int LA = (LP + 1) / 2, LB = LP / 2, A = 1 << LA, Bq = 1 << LB, P = 1 << LP, LDT = Bq + 1, FST = A * LDT + 1;
     constexpr int CT = PRUNED_CT, NT = CT * A;
@@ -665,7 +666,7 @@ __global__ __launch_bounds__(PRUNED_CT * (1 << ((LP + 1) / 2)), 2) void fft_cols
     const int tid = threadIdx.x;
     const int f = tid % CT, jk = tid / CT;  // column of the tile; j (phase 1) or ka (phase 2)
     const bool p1 = jk < Bq, p2 = jk < A;
-    const double invN1 = 1.0 / (double)N1, invN = 1.0 / (double)((size_t)1 << (m1 + m2));
+    const double invN = 1.0 / (double)((size_t)1 << (m1 + m2));
     // ru <= P / 2 (the df grids of a batch whose 2 df grid picked P): rows i Bq + j, i >= A / 2, hold no samples — the upper half
     // of xin is not loaded (r < ru fails) nor pre-twiddled, and the first butterfly stage knows it is zero.  One branch per
     // workgroup.
@@ -761,44 +762,54 @@ __global__ __launch_bounds__(PRUNED_CT * (1 << ((LP + 1) / 2)), 2) void fft_cols
             xin[i] = r < ru ? G[(size_t)r * N2 + c0 + f] : make_double2(0.0, 0.0);
         }
     }
-    // Every twiddle of the Q passes is a running product of a handful of roots taken once (the passes used to spend five
-    // sincospi each):   pre-twiddle W_N1^{(i Bq + j) s} = (W_N1^j)^s (W_N1^{Bq s})^i,   intra-transform W_P^{j ka},
-    // inter-step W_N^{c (Q (ka + A kb) + s)} = W_N^{c Q ka} (W_N^c)^s (W_N^{c Q A})^kb
+    // The twiddles of the Q passes.  Pass s, thread (f, j) of phase 1 with inputs x[i] at n = i Bq + j, column c = c0 + f:
+    //   pre-twiddle W_N1^{n s} = W_{A Q}^{s i} W_N1^{j s}: the first factor is the same for every lane of the workgroup — read
+    //   from the handle's table of roots through uniform addresses (scalar loads; no running product, none at s = 0) — and the
+    //   second does not depend on i, so it commutes with the A-point transform and moves behind it;
+    //   inter-step W_N^{c k1}, k1 = Q (ka + A kb) + s, = W_N^{c (s + Q ka)} (W_N^{c Q A})^kb: the first factor does not depend
+    //   on j, the index phase 2 sums over, so it moves in front of the exchange.
+    // Behind the A-point transform W_N1^{j s}, the intra-transform W_P^{j ka} = W_N1^{j Q ka} and W_N^{c (s + Q ka)} are one
+    // factor g^{s + Q ka}, g = e^{2 pi i (j N2 + c) / N}: a chain from g^s in steps of g^Q, g^s advanced by g per pass.  Phase 2
+    // multiplies by (W_N^{c Q A})^kb alone.  Three roots per thread.
     auto root = [](double x) {
         double sn, cs;
         sincospi(2.0 * x, &sn, &cs);
         return make_double2(cs, sn);
     };
-    const double2 wj = root((double)jk * invN1), wq = root((double)Bq * invN1);  // W_N1^j, W_N1^Bq
-    const double2 tw_j = root((double)jk / (double)P);
-    const double2 wc = root((double)(c0 + f) * invN), stepc = root((double)((long long)(c0 + f) * Q * A) * invN);
-    double2 wjs = make_double2(1.0, 0.0), wqs = wjs;                                  // (W_N1^j)^s, (W_N1^Bq)^s
-    double2 wout = root((double)((long long)(c0 + f) * Q * jk) * invN);               // W_N^{c (Q ka + s)}
+    const long long gi = (long long)jk * N2 + (c0 + f);
+    const double2 g1 = root((double)gi * invN), gq = root((double)(gi * Q) * invN);
+    const double2 stepc = root((double)((long long)(c0 + f) * Q * A) * invN);
+    double2 gs = make_double2(1.0, 0.0);  // g^s
+    const int rsh = LB + LSF_LOG_NROOTS - m1;  // W_{A Q}^{s i} = roots[(s i) << rsh]
     auto passes = [&](auto short_c) {
         constexpr bool SHORT = decltype(short_c)::value;
         constexpr int AI = SHORT ? A / 2 : A;  // inputs that can be non-zero
         for (int s = 0; s < Q; ++s) {
             if (p1) {
                 double2 v[A];
+                v[0] = xin[0];
                 if (s == 0) {
 #pragma unroll
-                    for (int i = 0; i < AI; ++i) v[i] = xin[i];
+                    for (int i = 1; i < AI; ++i) v[i] = xin[i];
                 } else {
-                    double2 w = wjs;
+                    // byte offsets as unsigned 32-bit scalars: one scalar add per load, the offset in a scalar register
+                    const unsigned ostep = (unsigned)s << (rsh + 4);
+                    unsigned off = 0;
 #pragma unroll
-                    for (int i = 0; i < AI; ++i) {
-                        v[i] = cmul(xin[i], w);
-                        if (i + 1 < AI) w = cmul(w, wqs);
+                    for (int i = 1; i < AI; ++i) {
+                        off += ostep;
+                        v[i] = cmul(xin[i], *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(roots) + off));
                     }
                 }
                 reg_fft<LA, SHORT>(v);
-                double2 w = make_double2(1.0, 0.0);
+                double2 w = gs;
                 double2 *row = lds2 + (size_t)f * FST + jk;
 #pragma unroll
                 for (int ka = 0; ka < A; ++ka) {
                     row[ka * LDT] = cmul(v[brev_c(ka, LA)], w);
-                    w = cmul(w, tw_j);
+                    if (ka + 1 < A) w = cmul(w, gq);
                 }
+                gs = cmul(gs, g1);
             }
             __syncthreads();
             if (p2) {
@@ -807,17 +818,15 @@ __global__ __launch_bounds__(PRUNED_CT * (1 << ((LP + 1) / 2)), 2) void fft_cols
 #pragma unroll
                 for (int j = 0; j < Bq; ++j) u[j] = row[j];
                 reg_fft<LB>(u);
-                double2 w = wout;
+                O[(size_t)(Q * jk + s) * CT + f] = u[0];
+                double2 w = stepc;
 #pragma unroll
-                for (int kb = 0; kb < Bq; ++kb) {
+                for (int kb = 1; kb < Bq; ++kb) {
                     const int q = jk + A * kb;
                     O[(size_t)(Q * q + s) * CT + f] = cmul(u[brev_c(kb, LB)], w);
-                    w = cmul(w, stepc);
+                    if (kb + 1 < Bq) w = cmul(w, stepc);
                 }
             }
-            wjs = cmul(wjs, wj);
-            wqs = cmul(wqs, wq);
-            wout = cmul(wout, wc);
             __syncthreads();
         }
     };
@@ -1509,6 +1518,14 @@ __global__ __launch_bounds__(256) void lsf_plan_kernel(const int *__restrict__ r
     }
 }
 
+// the 1024th roots of unity, e^{2 pi i k / 1024}: every N1 <= 1024 of the register path finds its N1-th roots among them
+__global__ __launch_bounds__(256) void lsf_roots_kernel(double2 *__restrict__ roots) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    double sn, cs;
+    sincospi((double)k * (2.0 / LSF_NROOTS), &sn, &cs);
+    roots[k] = make_double2(cs, sn);
+}
+
 // the cadence side of the fused extirpolation (tab16 == nullptr: every target's rows come from `grids`)
 struct SpreadArgs {
     const double *t, *y, *dy;
@@ -1528,7 +1545,8 @@ static void launch_cols_pruned_t(lk_handle *h, int m1, int m2, int ngrids, const
     (void)want_lds(h, reinterpret_cast<const void *>(fft_cols_pruned_kernel<LP>), 160 * 1024);
     hipLaunchKernelGGL((fft_cols_pruned_kernel<LP>), dim3((1 << m2) / PRUNED_CT, ngrids), dim3(PRUNED_CT * A),
                        (size_t)PRUNED_CT * FST * 16, stream, grids, m1, m2, rows_used, gout, sa.t, sa.y, sa.dy, sa.n_off,
-                       sa.stats, sa.b0, sa.f0, sa.df, sa.fit_mean, sa.tab16, sa.ntab16);
+                       sa.stats, sa.b0, sa.f0, sa.df, sa.fit_mean, sa.tab16, sa.ntab16,
+                       reinterpret_cast<const double2 *>(h->ls_roots));
 }
 
 static bool launch_cols_pruned(lk_handle *h, int lp, int m1, int m2, int ngrids, const double2 *grids, const int *rows_used,
@@ -1625,7 +1643,21 @@ int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *
         if (!h->h_plan) LK_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&h->h_plan), 64, hipHostMallocDefault));
         hipLaunchKernelGGL(lsf_plan_kernel, dim3(1), dim3(256), 0, stream, d_rows, B, d_plan);
         LK_HIP_CHECK(hipMemcpyAsync(h->h_plan, d_plan, 8, hipMemcpyDeviceToHost, stream));
-        LK_HIP_CHECK(hipStreamSynchronize(stream));
+        // the pruned column kernel's table of roots: filled once per handle, complete when the wait below returns
+        double *new_roots = nullptr;
+        if (!h->ls_roots) {
+            LK_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&new_roots), (size_t)LSF_NROOTS * 16));
+            hipLaunchKernelGGL(lsf_roots_kernel, dim3(LSF_NROOTS / 256), dim3(256), 0, stream,
+                               reinterpret_cast<double2 *>(new_roots));
+        }
+        const hipError_t sync_rc = hipStreamSynchronize(stream);
+        if (new_roots) {
+            if (sync_rc == hipSuccess)
+                h->ls_roots = new_roots;
+            else
+                (void)hipFree(new_roots);
+        }
+        LK_HIP_CHECK(sync_rc);
         n_unordered = h->h_plan[1];
         // the spreader's workgroups only need to cover the rows that can hold samples
         spread_blocks = std::min(spread_blocks, (int)((((size_t)std::max(1, h->h_plan[0]) << m2) + SPREAD_W - 1) / SPREAD_W));
