@@ -55,16 +55,23 @@ __device__ __forceinline__ void cadence_weights(const double *__restrict__ y, co
     wy = w * (y[i] - ybar);
 }
 
-// per target: weights, the mean about y[0], YY, t0 = min t, and the rows of each grid that can hold samples — ONE sweep over
-// the cadences (the kernel is a streaming reduction; round 3 swept four times): with u = 1 / dy^2, z = y - y[0],
+// per target: weights, the mean about y[0], YY, t0 = min t, and the rows of each grid that can hold samples.  What every call
+// needs comes from ONE sweep over the cadences (the kernel is a streaming reduction; round 3 swept four times): with
+// u = 1 / dy^2, z = y - y[0],
 //     A = sum u,  Bz = sum u z,  Cz = sum u z^2   ->   ybar = y[0] + Bz / A,   YY = (Cz - Bz^2 / A) / A
-// (the shifted-data form: y[0] sits within a few sigma of the mean, so the subtraction costs a digit at most, and a constant
-// light curve still centres to exactly 0).  Targets the owner-computes spreader cannot take (unsorted, wrapping) and the
-// multi-term path need the scales of the scatter kernels' quanta and the bias sum: a second sweep, for those only.
+// (the shifted-data form: a constant light curve still centres to exactly 0).  Two things take a further sweep each, only
+// where they are used:
+//  * want_yy (normalization 'standard', the one reader of YY): YY = sum w (y - ybar)^2 summed directly.  The shifted form is
+//    good to a digit only while y[0] sits within a few sigma of the mean; a first cadence D away from the others with an
+//    error bar to match leaves sum w (y - ybar)^2 ~ sigma^2 while Cz / A ~ D^2, and the subtraction costs
+//    log10(D^2 / sigma^2) digits (1e-5 of the power at D = 1e6 sigma).  The other normalisations never read YY; they store
+//    the shifted form's value as before.
+//  * targets the owner-computes spreader cannot take (unsorted, wrapping) and the multi-term path: the scales of the scatter
+//    kernels' quanta and the bias sum.
 constexpr int PREP_NT = 512;
 __global__ __launch_bounds__(PREP_NT) void lsf_prep_kernel(const double *__restrict__ t, const double *__restrict__ y,
                                                         const double *__restrict__ dy,
-                                                        const int64_t *__restrict__ n_off, int center,
+                                                        const int64_t *__restrict__ n_off, int center, int want_yy,
                                                         FastStats *__restrict__ stats, double df, int nfft, int m2,
                                                         int *__restrict__ rows_used) {
     constexpr int NT = PREP_NT;
@@ -125,12 +132,20 @@ __global__ __launch_bounds__(PREP_NT) void lsf_prep_kernel(const double *__restr
     }
     const double delta = center ? Bz / wsum : 0.0;
     const double ybar = center ? y0 + delta : 0.0;
-    // sum w (y - ybar)^2 with w = u / wsum: about y0 when centred (then ybar - y0 = delta), about 0 otherwise
+    // sum w (y - ybar)^2 with w = u / wsum (ybar = 0 when not centred)
     double YY;
-    if (center)
+    if (want_yy) {  // 'standard' divides by it: summed directly, residual by residual
+        double acc = 0.0;
+        for (int64_t i = tid; i < n; i += NT) {
+            const double d = dy ? dy[lo + i] : 1.0, r = y[lo + i] - ybar;
+            acc = fma((1.0 / (d * d)) * r, r, acc);
+        }
+        YY = bsum(acc) / wsum;
+    } else if (center) {  // not read by any other normalisation: the first sweep's sums about y0 (ybar - y0 = delta)
         YY = fmax(0.0, (Cz - Bz * delta) / wsum);
-    else
+    } else {
         YY = (Cz + y0 * (2.0 * Bz + y0 * wsum)) / wsum;  // sum u (z + y0)^2
+    }
     double yws = 0.0, wmx = 0.0, vmx = 0.0;
     if (!(rows_used && ordered)) {
         double acc2 = 0.0;
@@ -1634,18 +1649,21 @@ int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *
     if (rebase) t = d_trel;
     const int tw = tile_width(m1, m2);
     hipLaunchKernelGGL(lsf_prep_kernel, dim3(B), dim3(PREP_NT), 0, stream, t, y, dy, d_off, (fit_mean || center_data) ? 1 : 0,
-                       d_stats, df, nfft, m2, d_rows);
+                       normalization == LK_NORM_STANDARD ? 1 : 0, d_stats, df, nfft, m2, d_rows);
     // ---- plan: the pruned column kernel applies when every grid of every target keeps its samples in the first
     // P <= 256 rows (P < N1) and the row kernel can read 16-column tiles.  The decision needs two device words, so
-    // the call synchronises `stream` once here (20-30 us against a >= 1 ms step).
+    // the call synchronises `stream` once here (20-30 us against a >= 1 ms step, measured on the fused route).  The register
+    // path without the fused row kernel (oversampling 1 .. 3) needs the count of unordered targets all the same — the scatter,
+    // zero and unquantize kernels leave the ordered ones to the spreader — and pays the same wait; its cost against that
+    // route's step has not been measured.
     int lp = 0, n_unordered = B, spread_blocks = (nfft + SPREAD_W - 1) / SPREAD_W;
-    if (fused) {
+    if (reg_path) {
         if (!h->h_plan) LK_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&h->h_plan), 64, hipHostMallocDefault));
         hipLaunchKernelGGL(lsf_plan_kernel, dim3(1), dim3(256), 0, stream, d_rows, B, d_plan);
         LK_HIP_CHECK(hipMemcpyAsync(h->h_plan, d_plan, 8, hipMemcpyDeviceToHost, stream));
         // the pruned column kernel's table of roots: filled once per handle, complete when the wait below returns
         double *new_roots = nullptr;
-        if (!h->ls_roots) {
+        if (fused && !h->ls_roots) {
             LK_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&new_roots), (size_t)LSF_NROOTS * 16));
             hipLaunchKernelGGL(lsf_roots_kernel, dim3(LSF_NROOTS / 256), dim3(256), 0, stream,
                                reinterpret_cast<double2 *>(new_roots));
@@ -1661,7 +1679,7 @@ int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *
         n_unordered = h->h_plan[1];
         // the spreader's workgroups only need to cover the rows that can hold samples
         spread_blocks = std::min(spread_blocks, (int)((((size_t)std::max(1, h->h_plan[0]) << m2) + SPREAD_W - 1) / SPREAD_W));
-        if (m2 >= 8 && m2 <= 10 && N2 >= PRUNED_CT) {
+        if (fused && m2 >= 8 && m2 <= 10 && N2 >= PRUNED_CT) {
             const int want = std::max(5, ilog2_ceil(std::max(1, h->h_plan[0])));
             if (want <= 8 && want < m1) lp = want;
         }
@@ -1812,7 +1830,7 @@ int lsfastchi2_launch(lk_handle *h, int B, const int64_t *n_off_host, const doub
             .buf(d_spec, (size_t)Bc * NG * M).carve(stream))
         return rc;
     hipLaunchKernelGGL(lsf_prep_kernel, dim3(B), dim3(PREP_NT), 0, stream, t, y, dy, d_off, (fit_mean || center_data) ? 1 : 0,
-                       d_stats, df, nfft, m2, (int *)nullptr);
+                       normalization == LK_NORM_STANDARD ? 1 : 0, d_stats, df, nfft, m2, (int *)nullptr);
     const bool reg_path = m1 >= 4 && m1 <= 10 && m2 >= 4 && m2 <= 10;
     if (!reg_path) {
         (void)want_lds(h, reinterpret_cast<const void *>(fft_cols_kernel), 100 * 1024);

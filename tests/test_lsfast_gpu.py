@@ -58,10 +58,8 @@ def test_ragged_batch_fft_sizes_weights_vs_port():
                 for b in range(len(ns)):
                     if not fit_mean and f0 == 0.0:
                         continue   # C2 - ... singular at f = 0 without the mean term: NaN pattern is rounding noise
-                    ref = O.ls_power_fast(ts[b], ys[b], es[b] if use_dy else None, f0, df, M, normalization="psd") \
-                        if fit_mean else None
-                    if ref is None:
-                        continue
+                    ref = O.ls_power_fast(ts[b], ys[b], es[b] if use_dy else None, f0, df, M, normalization="psd",
+                                          fit_mean=fit_mean)
                     fr = f0 + df * np.arange(M)
                     # conditioned part only: below one cycle per baseline CC/SS cancel and rounding is amplified
                     ok = np.isfinite(ref) & (fr * (ts[b][-1] - ts[b][0]) >= 1.0)
