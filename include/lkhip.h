@@ -411,6 +411,38 @@ int lk_bls_stats_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const
                            const double *ivar, const double *period, const double *duration, const double *transit_time,
                            const int64_t *tr_off_host, double *stats, int32_t *tr_first, int32_t *tr_n, int32_t *tr_count,
                            double *tr_ll, double *model, void *stream);
+/* LombScarglePeriodogram.model (periodogram.py:991-1018 over astropy LombScargle.model -> mle.periodic_fit,
+ * implementations/mle.py:58-114) at ONE frequency per target: frequency is a HOST array of length B [1/d].  time / flux /
+ * dy: the packed batch WITHOUT NaN flux; the fit runs on t = time - time[first stored cadence of the target].  dy NULL = unit
+ * weights; a target whose dy are not all finite gets unit weights too (the rule of the other stages), else w = dy^-2.
+ * y_mean = sum w y / sum w (center_data) or 0; design columns [1 if fit_mean], sin(2 pi m f t), cos(2 pi m f t) for
+ * m = 1 .. nterms (nterms 1 .. 8, anything else is LK_EINVAL); theta solves the weighted normal equations of y - y_mean by
+ * LU with partial pivoting; model = y_mean + X theta.
+ * theta[b][2 * nterms + 1]: slot 0 = the bias (0 when !fit_mean), then sin 1, cos 1, sin 2, cos 2, ...
+ * stats[b][LK_LS_MODEL_NSTATS], in order:
+ *    0 y_mean        1 chi2_ref = sum w (y - y_mean)^2        2 chi2_model = sum w (y - model)^2        3 status
+ * status  1: fitted.   0: the frequency is NaN or <= 0, the target is skipped.   -1: fewer than 2 * nterms + fit_mean
+ * cadences (an empty light curve included; nothing of it is read), or a pivot / coefficient that is zero or not finite
+ * (astropy raises).  Where the status is not 1, theta and stats 0 .. 2 are NaN.
+ * model: NULL, or [n] = the model (NaN where the status is not 1).  residual: NULL, or [n] = flux minus the periodic part
+ * alone (keep_mean: the level y_mean + bias stays in the light curve) or flux - model (!keep_mean); where the status is not
+ * 1 it is the flux, bit for bit.  Every sum's order depends on the target's own data alone: a target's outputs do not
+ * change with B or with its neighbours in the batch.
+ * lk_ls_model_eval_batch: the fitted series at other times.  Target b owns entries [m_off[b], m_off[b+1]) of t_fit / out;
+ * out = y_mean + bias + series(t_fit - t_ref[b]) with t_ref (HOST, the target's first stored time) and frequency (HOST) as
+ * given to the fit, theta / stats as the fit wrote them; NaN where the status is not 1. */
+#define LK_LS_MODEL_NSTATS 4
+int lk_ls_model_batch(lk_handle *h, int B, const int64_t *n_off, const double *time, const double *flux, const double *dy,
+                      const double *frequency, int nterms, int fit_mean, int center_data, int keep_mean, double *theta,
+                      double *stats, double *model, double *residual);
+int lk_ls_model_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux,
+                          const double *dy, const double *frequency, int nterms, int fit_mean, int center_data, int keep_mean,
+                          double *theta, double *stats, double *model, double *residual, void *stream);
+int lk_ls_model_eval_batch(lk_handle *h, int B, const int64_t *m_off, const double *t_fit, const double *t_ref,
+                           const double *frequency, int nterms, const double *theta, const double *stats, double *out);
+int lk_ls_model_eval_batch_dev(lk_handle *h, int B, const int64_t *m_off_host, const double *t_fit, const double *t_ref,
+                               const double *frequency, int nterms, const double *theta, const double *stats, double *out,
+                               void *stream);
 /* LightCurve.bin (:1558-1763) over astropy aggregate_downsample (astropy@4.3.1 timeseries/downsample.py:12-125), times
  * sorted.  Target b gets bins [bin_off[b], bin_off[b+1]) of the outputs; its bins start at time_bin_start[b] [d] and their
  * edges, in seconds relative to it, are edges_sec[0 .. n_bins_b] (HOST; numpy's cumsum of the bin size, shared by all

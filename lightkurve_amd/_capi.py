@@ -94,6 +94,14 @@ SIGNATURES = [
      [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_ip, _c_dp, _c_i32p, _c_i32p, _c_i32p, _c_dp, _c_dp]),
     ("lk_bls_stats_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_ip, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_ls_model_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp,
+      _c_dp, _c_dp]),
+    ("lk_ls_model_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp,
+      _vp]),
+    ("lk_ls_model_eval_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp]),
+    ("lk_ls_model_eval_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _vp, _c_dp, _c_dp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     ("lk_shader_clock_mhz", ctypes.c_int, [_vp, ctypes.c_double, _c_dp]),
     ("lk_host_alloc", ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_size_t]),
     ("lk_host_free", ctypes.c_int, [_vp]),
@@ -1387,6 +1395,72 @@ def bls_stats_batch(t, flux, ivar, n_off, period, duration, transit_time, want_m
     out = bls_stats_dict(stats, tr_first, tr_n, tr_off, tr_count, tr_ll, period, transit_time, t_first)
     if want_model:
         out["model"] = model
+    return out
+
+
+LS_MODEL_NSTATS = 4            # LK_LS_MODEL_NSTATS (include/lkhip.h): y_mean, chi2_ref, chi2_model, status
+
+
+def ls_model_arguments(B, frequency, nterms):
+    """The per-target frequency of ``lk_ls_model_batch``: a scalar or one value per target -> float64[B] (NaN and values
+    <= 0 are kept: they mark a target to skip, status 0); ``nterms`` an integer 1 .. ``MAX_NTERMS``, or ``ValueError``."""
+    a = np.asarray(frequency, dtype=np.float64)
+    if a.ndim > 1 or (a.ndim == 1 and a.size != B):
+        raise ValueError("frequency must be a scalar or one value per light curve (%d), got shape %r" % (B, a.shape))
+    if int(nterms) != nterms or not 1 <= int(nterms) <= MAX_NTERMS:
+        raise ValueError("nterms must be an integer 1 .. %d (got %r)" % (MAX_NTERMS, nterms))
+    return np.ascontiguousarray(np.broadcast_to(a, (B,))), int(nterms)
+
+
+def ls_model_dict(frequency, theta, stats):
+    """The raw outputs of ``lk_ls_model_batch`` -> the dict of ``DeviceLightCurveBatch.ls_model``: ``frequency`` [B],
+    ``theta`` [B, 2 nterms + 1], ``amplitude`` / ``phase`` [B, nterms] (hypot and atan2(cos, sin) of each harmonic's pair:
+    the harmonic is amplitude * sin(2 pi m f t + phase)), ``offset`` = y_mean + bias, ``y_mean``, ``chi2_ref``,
+    ``chi2_model``, ``status`` (int: 1 fitted, 0 skipped, -1 not fitted)."""
+    th_s, th_c = theta[:, 1::2], theta[:, 2::2]
+    return dict(frequency=np.array(frequency, dtype=np.float64), theta=theta, amplitude=np.hypot(th_s, th_c),
+                phase=np.arctan2(th_c, th_s), offset=stats[:, 0] + theta[:, 0], y_mean=stats[:, 0].copy(),
+                chi2_ref=stats[:, 1].copy(), chi2_model=stats[:, 2].copy(), status=stats[:, 3].astype(np.int64))
+
+
+def ls_model_batch(t, flux, dy, n_off, frequency, nterms=1, fit_mean=True, center_data=True, keep_mean=True, want_model=True,
+                   want_residual=False, t_fit=None, m_off=None, device=0):
+    """``LombScargle.model`` at one frequency [1/d] per light curve for B ragged, NaN-free light curves on the host
+    (``lk_ls_model_batch``).  ``t`` absolute; ``dy`` None = unit weights (a light curve whose ``dy`` are not all finite gets
+    unit weights too); ``frequency``: a scalar or one value per target.  Returns the dict of ``ls_model_dict`` plus ``model``
+    (``want_model``) and ``residual`` (``want_residual``; ``keep_mean``: the level stays in it) per cadence, and with
+    ``t_fit`` / ``m_off`` (target b owns ``t_fit[m_off[b]:m_off[b + 1]]``, absolute) ``model_fit``, the series at those times
+    (``lk_ls_model_eval_batch``)."""
+    h = Handle.get(device)
+    t, flux = _f64(t), _f64(flux)
+    n_off = _offsets(n_off, t.size)
+    if flux.shape != t.shape or (dy is not None and np.shape(dy) != t.shape):
+        raise ValueError("t, flux, dy must be 1-D arrays of one length")
+    dy = None if dy is None else _f64(dy)
+    B = n_off.size - 1
+    frequency, nterms = ls_model_arguments(B, frequency, nterms)
+    theta = np.zeros((B, 2 * nterms + 1), dtype=np.float64)
+    stats = np.zeros((B, LS_MODEL_NSTATS), dtype=np.float64)
+    model = np.empty(t.size, dtype=np.float64) if want_model else None
+    residual = np.empty(t.size, dtype=np.float64) if want_residual else None
+    _check(_lib.lk_ls_model_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(t), _ptr(flux), _ptr(dy), _ptr(frequency), nterms,
+                                  int(bool(fit_mean)), int(bool(center_data)), int(bool(keep_mean)), _ptr(theta), _ptr(stats),
+                                  _ptr(model), _ptr(residual)))
+    out = ls_model_dict(frequency, theta, stats)
+    if want_model:
+        out["model"] = model
+    if want_residual:
+        out["residual"] = residual
+    if t_fit is not None:
+        t_fit = _f64(t_fit)
+        m_off = _offsets(m_off, t_fit.size)
+        if m_off.size != B + 1:
+            raise ValueError("m_off must hold B + 1 prefix offsets over t_fit")
+        t_ref = t[np.minimum(n_off[:-1], t.size - 1)] if t.size else np.zeros(B)     # (an empty light curve is not fitted)
+        fit = np.empty(t_fit.size, dtype=np.float64)
+        _check(_lib.lk_ls_model_eval_batch(h._h, B, _ptr(m_off, _c_ip), _ptr(t_fit), _ptr(_f64(t_ref)), _ptr(frequency), nterms,
+                                           _ptr(theta), _ptr(stats), _ptr(fit)))
+        out["model_fit"] = fit
     return out
 
 

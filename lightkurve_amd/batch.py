@@ -8,7 +8,7 @@ from . import _capi
 from .distributed import all_gather_rows, device_gather_available, shard_bounds, sharded_map, sharded_map_ragged
 from . import packed
 
-__all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "periodogram_peaks", "flatten_batch",
+__all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "periodogram_peaks", "flatten_batch",
            "estimate_cdpp_batch", "pld_correct_batch", "regression_correct_batch"]
 
 
@@ -224,6 +224,26 @@ def bls_stats_batch(lcs, period, duration, transit_time, device=0):
     if not packed.check_sorted(time, n_off):
         raise ValueError("bls_stats_batch needs every light curve sorted by time")
     return _capi.bls_stats_batch(time, flux, packed.bls_ivar(flux, err, n_off), n_off, period, duration, transit_time, device=device)
+
+
+def ls_model_batch(lcs, frequency, nterms=1, fit_mean=True, center_data=True, use_flux_err=False, keep_mean=True, want_model=True,
+                   want_residual=False, device=0):
+    """``LombScarglePeriodogram.model`` before its normalisation (reference periodogram.py:991-1018 over astropy
+    ``LombScargle.model``) at one frequency [1/d] per light curve, for host light curves: ``lcs`` a list of light curves or a
+    ``LightCurveBatch``; ``frequency`` a scalar or one value per light curve (NaN or <= 0: the light curve is skipped, status
+    0).  NaN-flux cadences are dropped, as ``LombScarglePeriodogram.from_lightcurve`` drops them; weights are uniform, as
+    lightkurve's, unless ``use_flux_err`` (then 1 / flux_err^2 where a light curve's errors are all finite).  Returns the dict
+    of ``_capi.ls_model_batch`` plus ``n_off``, the offsets of the per-cadence arrays.  Not sharded over ranks."""
+    from .ingest import LightCurveBatch
+    if isinstance(lcs, LightCurveBatch):
+        time, flux, err, n_off = lcs.time, lcs.flux, lcs.flux_err, lcs.n_off
+    else:
+        (time, flux, err), n_off = packed.pack_columns(list(lcs), ("time", "flux", "flux_err"), pinned="auto", pool_prefix="lsmodel")
+    time, flux, n_off, err = packed.drop_nan_flux(time, flux, n_off, err)
+    out = _capi.ls_model_batch(time, flux, err if use_flux_err else None, n_off, frequency, nterms, fit_mean, center_data, keep_mean,
+                               want_model, want_residual, device=device)
+    out["n_off"] = n_off
+    return out
 
 
 def periodogram_peaks(power, device=0):

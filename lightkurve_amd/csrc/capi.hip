@@ -1551,6 +1551,67 @@ int lk_bls_stats_batch(lk_handle *h, int B, const int64_t *n_off, const double *
     return rc ? rc : io.finish();
 }
 
+int lk_ls_model_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux,
+                          const double *dy, const double *frequency, int nterms, int fit_mean, int center_data, int keep_mean,
+                          double *theta, double *stats, double *model, double *residual, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::ls_model_launch(h, B, n_off_host, time, flux, dy, frequency, nterms, fit_mean, center_data, keep_mean, theta, stats,
+                               model, residual, static_cast<hipStream_t>(stream));
+}
+
+int lk_ls_model_batch(lk_handle *h, int B, const int64_t *n_off, const double *time, const double *flux, const double *dy,
+                      const double *frequency, int nterms, int fit_mean, int center_data, int keep_mean, double *theta,
+                      double *stats, double *model, double *residual) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr, "bad batch description");
+    LK_REQUIRE(nterms >= 1 && nterms <= 8, "nterms must be 1 .. 8 (got %d)", nterms);
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(n_off[B] >= 0, "bad batch description");
+    LK_REQUIRE(n_off[B] == 0 || (time && flux), "NULL time or flux");
+    LK_REQUIRE(theta && stats, "NULL output buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B];
+    const double *dt, *df, *de;
+    double *dtheta, *dstats, *dmodel, *dres;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, time, ntot).in(df, flux, ntot).in(de, dy, ntot).out(dtheta, theta, (size_t)B * (2 * nterms + 1))
+                 .out(dstats, stats, (size_t)B * LK_LS_MODEL_NSTATS).out(dmodel, model, ntot).out(dres, residual, ntot).stage();
+    if (rc) return rc;
+    rc = lk::ls_model_launch(h, B, n_off, dt, df, de, frequency, nterms, fit_mean, center_data, keep_mean, dtheta, dstats, dmodel,
+                             dres, nullptr);
+    return rc ? rc : io.finish();
+}
+
+int lk_ls_model_eval_batch_dev(lk_handle *h, int B, const int64_t *m_off_host, const double *t_fit, const double *t_ref,
+                               const double *frequency, int nterms, const double *theta, const double *stats, double *out,
+                               void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::ls_model_eval_launch(h, B, m_off_host, t_fit, t_ref, frequency, nterms, theta, stats, out,
+                                    static_cast<hipStream_t>(stream));
+}
+
+int lk_ls_model_eval_batch(lk_handle *h, int B, const int64_t *m_off, const double *t_fit, const double *t_ref,
+                           const double *frequency, int nterms, const double *theta, const double *stats, double *out) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && m_off != nullptr, "bad batch description");
+    LK_REQUIRE(nterms >= 1 && nterms <= 8, "nterms must be 1 .. 8 (got %d)", nterms);
+    if (B == 0 || m_off[B] == 0) return LK_OK;
+    LK_REQUIRE(m_off[B] > 0 && t_fit && out, "NULL t_fit or out");
+    LK_REQUIRE(theta && stats, "NULL fit parameters");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t mtot = (size_t)m_off[B];
+    const double *dt, *dtheta, *dstats;
+    double *dout;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t_fit, mtot).in(dtheta, theta, (size_t)B * (2 * nterms + 1)).in(dstats, stats, (size_t)B * LK_LS_MODEL_NSTATS)
+                 .out(dout, out, mtot).stage();
+    if (rc) return rc;
+    rc = lk::ls_model_eval_launch(h, B, m_off, dt, t_ref, frequency, nterms, dtheta, dstats, dout, nullptr);
+    return rc ? rc : io.finish();
+}
+
 int lk_bin_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,
                      const double *flux_err, const int64_t *bin_off, const double *time_bin_start, const double *edges_sec,
                      int64_t n_edges, double bin_size_sec, const uint8_t *has_err, double *t_out, double *flux_out,

@@ -266,6 +266,13 @@ int bls_stats_launch(lk_handle *h, int B, const int64_t *n_off_host, const doubl
                      const double *period_host, const double *duration_host, const double *transit_time_host,
                      const int64_t *tr_off_host, double *stats, int32_t *tr_first, int32_t *tr_n, int32_t *tr_count, double *tr_ll,
                      double *model, hipStream_t stream);
+// lsmodel.hip: LombScargle.model (mle.periodic_fit) of one frequency per target; model / residual nullable
+int ls_model_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux, const double *dy,
+                    const double *frequency_host, int nterms, int fit_mean, int center_data, int keep_mean, double *theta,
+                    double *stats, double *model, double *residual, hipStream_t stream);
+int ls_model_eval_launch(lk_handle *h, int B, const int64_t *m_off_host, const double *t_fit, const double *t_ref_host,
+                         const double *frequency_host, int nterms, const double *theta, const double *stats, double *out,
+                         hipStream_t stream);
 int bin_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux, const double *err,
                const int64_t *bin_off_host, const double *start_host, const double *edges_host, int64_t n_edges,
                double bin_size_sec, const uint8_t *has_err_host, double *t_out, double *f_out, double *e_out,

@@ -962,6 +962,98 @@ class DeviceLightCurveBatch(object):
                                                 to_host=False, want_peaks=True)
         return peaks
 
+    def ls_model(self, frequency, nterms=1, freq_unit=None, use_flux_err=False, fit_mean=True, center_data=True, want_model=True,
+                 want_residual=False, keep_mean=True, time=None):
+        """``LombScarglePeriodogram.model`` before its normalisation (reference periodogram.py:991-1018 over astropy
+        ``LombScargle.model``) for every light curve at its OWN frequency, resident (``lk_ls_model_batch_dev``).
+        ``frequency``: a scalar or one value per target in ``freq_unit`` (default 1/d); NaN or <= 0 skips the target (status
+        0).  Works on the batch the periodogram methods see (NaN flux dropped); weights are uniform, as lightkurve's, unless
+        ``use_flux_err`` (1 / flux_err^2 where a target's errors are all finite).  Returns the dict of
+        ``_capi.ls_model_dict`` (host arrays per target: ``frequency``, ``theta``, ``amplitude``, ``phase``, ``offset``,
+        ``y_mean``, ``chi2_ref``, ``chi2_model``, ``status``) plus, resident, ``model`` (``want_model``) and ``residual``
+        (``want_residual``): ``DeviceLightCurveBatch``es that share the time and flux_err buffers of the fitted batch.
+        ``residual`` keeps the level ``offset`` with ``keep_mean`` (the light curve stays positive and normalised), is the
+        flux bit for bit where ``status`` is not 1, and equals flux - model without ``keep_mean``.  ``time=(t_fit, m_off)``:
+        ``model`` is evaluated on other times instead (host array of absolute times, target b owns
+        ``t_fit[m_off[b]:m_off[b + 1]]``; ``lk_ls_model_eval_batch_dev``).  ``model``, divided by its median per target, is what
+        ``LombScarglePeriodogram.model(lc.time)`` returns."""
+        from .periodogram import _freq_unit_factor
+        src = self._ls_ready()
+        h, B, n, st = src.handle, len(src), src.n_cadences, _vp(src.stream or None)
+        freq, nterms = _capi.ls_model_arguments(B, frequency, nterms)
+        f_day = np.ascontiguousarray(freq / _freq_unit_factor(freq_unit if freq_unit is not None else "1/d"))
+        on_time = want_model and time is None
+        d_theta = DeviceBuffer(h, max(B, 1) * (2 * nterms + 1) * 8)
+        d_stats = DeviceBuffer(h, max(B, 1) * _capi.LS_MODEL_NSTATS * 8)
+        d_model = DeviceBuffer(h, max(n, 1) * 8) if on_time else None
+        d_res = DeviceBuffer(h, max(n, 1) * 8) if want_residual else None
+        d_err = src.d_flux_err if use_flux_err else None
+        lib = _capi._lib
+        _capi._check(lib.lk_ls_model_batch_dev(
+            h._h, B, _off_ptr(src.n_off), _vp(src.d_time.ptr), _vp(src.d_flux.ptr), _vp(d_err.ptr if d_err is not None else None),
+            f_day.ctypes.data_as(_dp), nterms, int(bool(fit_mean)), int(bool(center_data)), int(bool(keep_mean)), _vp(d_theta.ptr),
+            _vp(d_stats.ptr), _vp(d_model.ptr if d_model is not None else None), _vp(d_res.ptr if d_res is not None else None), st))
+        mdl = None
+        if on_time:
+            mdl = src._new(src.d_time, d_model, None, src.n_off, nan_free=True, is_sorted=src.is_sorted)
+        elif want_model:
+            t_fit, m_off = time
+            t_fit = np.ascontiguousarray(t_fit, dtype=np.float64)
+            m_off = _capi._offsets(m_off, t_fit.size)
+            if m_off.size != B + 1:
+                raise ValueError("time=(t_fit, m_off): m_off must hold B + 1 prefix offsets over t_fit")
+            t_ref = np.zeros(B, dtype=np.float64)
+            if B and n:
+                _capi._check(lib.lk_gather_f64_dev(h._h, B, _off_ptr(np.minimum(src.n_off[:-1], n - 1)), _vp(src.d_time.ptr),
+                                                   t_ref.ctypes.data_as(_dp), st))
+            d_tf, k = _upload(h, t_fit, src.stream)
+            src._keep.append(k)
+            d_fit = DeviceBuffer(h, max(t_fit.size, 1) * 8)
+            _capi._check(lib.lk_ls_model_eval_batch_dev(h._h, B, _off_ptr(m_off), _vp(d_tf.ptr), t_ref.ctypes.data_as(_dp),
+                                                        f_day.ctypes.data_as(_dp), nterms, _vp(d_theta.ptr), _vp(d_stats.ptr),
+                                                        _vp(d_fit.ptr), st))
+            mdl = src._new(d_tf, d_fit, None, m_off, nan_free=True)
+        theta = d_theta.download(np.float64, B * (2 * nterms + 1), stream=src.stream).reshape(B, 2 * nterms + 1)
+        stats = d_stats.download(np.float64, B * _capi.LS_MODEL_NSTATS, stream=src.stream).reshape(B, _capi.LS_MODEL_NSTATS)
+        src._keep = []
+        out = _capi.ls_model_dict(freq, theta, stats)
+        if mdl is not None:
+            for m in mdl.meta:
+                m["LABEL"] = "LS Model"
+            out["model"] = mdl
+        if want_residual:
+            out["residual"] = src._new(src.d_time, d_res, src.d_flux_err, src.n_off, nan_free=True, is_sorted=src.is_sorted)
+            out["residual"].d_quality = src.d_quality
+        return out
+
+    def prewhiten(self, frequency, n_signals=3, nterms=1, normalization="amplitude", freq_unit=None, oversample_factor=None,
+                  ls_method="fast", min_power=None, use_flux_err=False):
+        """Iterative prewhitening (``lc.to_periodogram()`` -> ``pg.model(lc.time)`` -> ``lc - model``, again) for every light
+        curve, resident: ``n_signals`` times ``to_periodogram_power(..., to_host=False, want_peaks=True)`` on the shared grid
+        ``frequency`` -> ``ls_model(frequency at each target's own peak, want_model=False, want_residual=True)``; the residual
+        (level kept) is the next round's batch.  Returns (signals, residual): per round the dict of ``ls_model`` plus ``power``,
+        the peak it was fitted at, strongest signal first, and the batch without every fitted signal.  A target whose peak is
+        below ``min_power`` (or NaN) gets frequency NaN in that round and every later one: status 0, its flux untouched.
+        ``nterms`` is the model's; the periodogram's follows ``ls_method`` as in ``to_periodogram_power``.  Per round the
+        peaks and the fit parameters come down and 8 B per target go up; no column crosses PCIe."""
+        if int(n_signals) < 1:
+            raise ValueError("n_signals must be >= 1 (got %r)" % (n_signals,))
+        plan = packed.ls_grid_plan(frequency, normalization, freq_unit, oversample_factor, ls_method, nterms)
+        cur, signals = self._ls_ready(), []
+        alive = np.ones(len(cur), dtype=bool)
+        for _ in range(int(n_signals)):
+            _pow, peaks = cur.to_periodogram_power(frequency, normalization, freq_unit, oversample_factor, ls_method, nterms,
+                                                   to_host=False, want_peaks=True)
+            power = peaks[:, 0]
+            alive &= np.isfinite(power) if min_power is None else power >= min_power
+            at = np.clip(peaks[:, 1].astype(np.int64), 0, len(plan.frequency) - 1)
+            res = cur.ls_model(np.where(alive, plan.frequency[at], np.nan), nterms=nterms, freq_unit=plan.freq_unit,
+                               use_flux_err=use_flux_err, want_model=False, want_residual=True)
+            cur = res.pop("residual")
+            res["power"] = power
+            signals.append(res)
+        return signals, cur
+
     # ---------------------------------------------------------------- BLS
     def bls(self, period, duration=None, objective="likelihood", oversample=10):
         """The seven BLS statistics of every light curve on one shared period grid, resident (``batch.bls_batch``:

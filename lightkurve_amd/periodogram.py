@@ -440,6 +440,65 @@ def _ls_model(self, time, frequency=None, device=0):
     return lc.normalize()
 
 
+def ls_model_host(time, flux, dy, frequency, nterms=1, fit_mean=True, center_data=True, t_fit=None, singular="raise"):
+    """``LombScargle.model`` as a pure host function (astropy 4.3.1 mle.periodic_fit, implementations/mle.py:58-114, what the
+    reference's periodogram.py:991-1018 calls): same operations in the same order.  ``time`` / ``t_fit`` are absolute; the
+    arithmetic runs on times relative to ``time[0]``, like ``LombScarglePeriodogram.from_lightcurve``'s.  ``frequency`` in 1/d;
+    ``dy`` None = unit weights.  Returns a dict: ``theta`` float64[2 nterms + 1] in the layout of ``lk_ls_model_batch`` (slot 0
+    the bias, 0 without ``fit_mean``; then sin 1, cos 1, sin 2, ...), ``y_mean``, ``model`` (at ``t_fit`` when given, else at
+    ``time``), ``chi2_ref`` = sum w (y - y_mean)^2 and ``chi2_model`` = sum w (y - model(time))^2.  The reference of
+    ``lk_ls_model_batch``.  ``singular``: ``"raise"`` lets ``numpy.linalg.solve`` raise (astropy's behaviour); ``"nan"`` gives
+    NaN everywhere for a light curve of fewer than 2 nterms + fit_mean cadences or a singular fit, which is what the batch
+    kernel reports per target (status -1)."""
+    time = np.asarray(time, dtype=np.float64)
+    y = np.asarray(flux, dtype=np.float64)
+    nterms = int(nterms)
+    if nterms < 1:
+        raise ValueError("nterms must be >= 1 (got %d)" % nterms)
+    if not float(frequency) > 0:
+        raise ValueError("frequency must be positive (got %r)" % (frequency,))
+    K = 2 * nterms + int(bool(fit_mean))
+    t0 = float(time[0]) if len(time) else 0.0
+    t = time - t0
+    tf = t if t_fit is None else np.asarray(t_fit, dtype=np.float64) - t0
+    dy = np.ones_like(y) if dy is None else np.broadcast_to(np.asarray(dy, dtype=np.float64), y.shape)
+
+    def design(tt, err=None):                        # mle.design_matrix
+        cols = [np.ones(len(tt))] if fit_mean else []
+        for i in range(1, nterms + 1):
+            cols.append(np.sin(2 * np.pi * i * frequency * tt))
+            cols.append(np.cos(2 * np.pi * i * frequency * tt))
+        XT = np.vstack(cols)
+        if err is not None:
+            XT = XT / err
+        return np.transpose(XT)
+
+    w = dy ** -2.0
+    try:
+        if singular == "nan" and len(t) < K:
+            raise np.linalg.LinAlgError("fewer cadences than columns")
+        if center_data:
+            y_mean = np.dot(y, w) / w.sum()
+            yc = y - y_mean
+        else:
+            y_mean, yc = 0.0, y
+        X = design(t, dy)
+        sol = np.linalg.solve(np.dot(X.T, X), np.dot(X.T, yc / dy))
+        if singular == "nan" and not np.all(np.isfinite(sol)):
+            raise np.linalg.LinAlgError("non-finite solution")
+    except np.linalg.LinAlgError:
+        if singular != "nan":
+            raise
+        nan = float("nan")
+        return dict(theta=np.full(2 * nterms + 1, nan), y_mean=nan, model=np.full(len(tf), nan), chi2_ref=nan, chi2_model=nan)
+    theta = np.zeros(2 * nterms + 1)
+    theta[1 - int(bool(fit_mean)):] = sol
+    at_time = y_mean + np.dot(design(t), sol)
+    model = at_time if t_fit is None else y_mean + np.dot(design(tf), sol)
+    return dict(theta=theta, y_mean=float(y_mean), model=model, chi2_ref=float(np.sum(w * (y - y_mean) ** 2)),
+                chi2_model=float(np.sum(w * (y - at_time) ** 2)))
+
+
 def _bls_plan(lc, **kwargs):
     """Everything BoxLeastSquaresPeriodogram.from_lightcurve decides before calling astropy (reference
     periodogram.py:1093-1168 + astropy bls/core.py:113-214, 277-327)."""

@@ -50,7 +50,14 @@ same with the clip staged through the host, as it had to be without `remove_outl
 target, boolean indexing, `from_arrays`.  S `bls_search(periods, n_signals=2)` on `LK_WALLS_P` (default 64) periods x 3
 durations of the flattened batch; S_H the same loop with `to_host()`, numpy `~mask` indexing and `from_arrays` between the
 rounds.  `cdpp`: R `batch.estimate_cdpp()`; H `to_host()` + `lightcurve.estimate_cdpp_batch` on the list of light curves
-(flatten and clip on the GPU from host arrays, the tail in numpy per target).  Results: profiles/clean_walls.txt."""
+(flatten and clip on the GPU from host arrays, the tail in numpy per target).  Results: profiles/clean_walls.txt.
+
+`prewhiten`: `batch.prewhiten(frequency, n_signals=3)` of `LK_WALLS_B` (default 1000) targets x `LK_WALLS_N` (default 20000)
+cadences on the benchmark's grid of `LK_WALLS_M` (default 100000) frequencies, in ONE process, the routes alternating,
+`LK_WALLS_REPS` (default 3) times after one warm-up.  W the resident loop; W_H the same loop through the host: the peaks from
+the resident periodogram, then `to_host()`, `ls_model_host` per target, `from_arrays` per round.  L one round's periodogram
+pass alone (`to_periodogram_power(to_host=False, want_peaks=True)`), F one round's fit alone
+(`ls_model(want_model=False, want_residual=True)`).  Results: profiles/prewhiten_walls.txt."""
 import cProfile
 import io
 import os
@@ -482,6 +489,71 @@ def cdpp():
     sys.stdout.flush()
 
 
+def prewhiten():
+    from lightkurve_amd import _capi, synth
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    from lightkurve_amd.periodogram import ls_model_host
+    B, N, M = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000"), ("LK_WALLS_M", "100000")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "3"))
+    cols = [synth.ls_target(1, i, N)[:3] for i in range(B)]
+    n_off = np.arange(B + 1, dtype=np.int64) * N
+    raw = DeviceLightCurveBatch.from_arrays(np.concatenate([c[0] for c in cols]), 1.0 + np.concatenate([c[1] for c in cols]),
+                                            np.concatenate([c[2] for c in cols]), n_off).remove_nans()
+    freq = synth.ls_frequency_grid(M)
+    sync = _capi.Handle.get(0).synchronize
+
+    def resident():
+        return raw.prewhiten(freq, n_signals=3)
+
+    def through_host():
+        cur, signals = raw, []
+        for _ in range(3):
+            _pow, peaks = cur.to_periodogram_power(freq, to_host=False, want_peaks=True)
+            f = freq[peaks[:, 1].astype(np.int64)]
+            host = cur.to_host()
+            flux, theta = host.flux.copy(), np.empty((B, 3))
+            for b in range(B):
+                a, z = int(host.n_off[b]), int(host.n_off[b + 1])
+                m = ls_model_host(host.time[a:z], host.flux[a:z], None, f[b])
+                flux[a:z] -= m["model"] - (m["y_mean"] + m["theta"][0])
+                theta[b] = m["theta"]
+            signals.append(dict(frequency=f, theta=theta, power=peaks[:, 0]))
+            cur = DeviceLightCurveBatch.from_arrays(host.time, flux, host.flux_err, host.n_off)
+            cur.nan_free = True
+        return signals, cur
+
+    def ls_pass():
+        return raw.to_periodogram_power(freq, to_host=False, want_peaks=True)
+
+    peaks = ls_pass()[1]
+    f_peak = freq[peaks[:, 1].astype(np.int64)]
+
+    def fit():
+        return raw.ls_model(f_peak, want_model=False, want_residual=True)
+
+    fns = {"W": resident, "W_H": through_host, "L": ls_pass, "F": fit}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    sync()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(lambda: (fn(), sync()))[0])
+    (sig_w, res_w), (sig_h, res_h) = first["W"], first["W_H"]
+    same_f = all(np.array_equal(a["frequency"], b["frequency"]) for a, b in zip(sig_w, sig_h))
+    d_theta = max(float(np.max(np.abs(a["theta"] - b["theta"]))) for a, b in zip(sig_w, sig_h))
+    d_res = float(np.max(np.abs(res_w.flux_host() - res_h.flux_host())))
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    print("prewhitening, %d targets x %d cadences (%.0f MB per float64 column), %d frequencies, n_signals = 3"
+          % (B, N, B * N * 8 / 1e6, M))
+    print("  W    batch.prewhiten(frequency, n_signals=3), resident                                  %s" % spread(ts["W"]))
+    print("  W_H  the same loop, to_host / ls_model_host per target / from_arrays between the rounds   %s" % spread(ts["W_H"]))
+    print("  L    one round's periodogram pass: to_periodogram_power(to_host=False, want_peaks=True)   %s" % spread(ts["L"]))
+    print("  F    one round's fit: ls_model(want_model=False, want_residual=True)                      %s" % spread(ts["F"]))
+    print("  same frequencies: %s; max |theta W - W_H| = %.3e; max |residual W - W_H| = %.3e" % (same_f, d_theta, d_res))
+    print("  W_H / W = %.1f; W per round / L = %.2f; F / L = %.3f" % (med["W_H"] / med["W"], med["W"] / 3 / med["L"], med["F"] / med["L"]))
+    sys.stdout.flush()
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -503,6 +575,8 @@ def main():
         clean()
     if "cdpp" in which:
         cdpp()
+    if "prewhiten" in which:
+        prewhiten()
     if "flatten" in which:
         lcs = []
         for i in range(1000):
