@@ -511,7 +511,8 @@ __global__ __launch_bounds__(256) void solve_kernel(const double *__restrict__ G
     for (int i = tid; i < K; i += 256) w[(size_t)target * K + i] = s_col[i];
 }
 
-// The same solve for K <= ~138 with the whole augmented system in LDS: no global round trips between the phases of a
+// The same solve for K <= 141 with the whole augmented system in LDS (regress_launch's plan, K (K + 1) + 2 K + 34 doubles, fits
+// the 160 KB = 20480 doubles up to there: 20338 at K = 141, 20624 at K = 142): no global round trips between the phases of a
 // column, the pivot found by a wave reduction + one 4-entry LDS exchange (2 barriers instead of 9), and a column-oriented
 // back substitution (1 barrier per unknown instead of 9).  Same pivot rule; the update order per element is unchanged.
 constexpr int SOLVE_NT = 1024, SOLVE_NW = SOLVE_NT / 64;  // sixteen waves: the trailing update of a column is rows / waves deep

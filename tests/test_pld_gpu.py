@@ -383,3 +383,59 @@ def test_wide_block_eigen_iteration_matches_the_oracle(order, comps, npix):
         r = O.pld_correct(c.time, c.flux, c.flux_err, allm, allm, allm, pld_order=order, pca_components=comps, spline_degree=5)
         assert np.array_equal(masks[i], r["outlier_mask"]), i
         assert np.max(np.abs(corr[i] - r["corrected"])) / np.median(r["corrected"]) < 1e-6, i
+
+
+# ------------------------------------------------------------------------------------------------ wide design matrices
+# PLDCorrector.correct builds K = 3 * 16 + 16 + spline_n_knots + 1 columns with a prior on every one; at the default knot count
+# (n / 50) no test above is wider than 135 columns, the side of the regression kernels where the system is solved in LDS
+# (K <= 141, regress.hip) and [X | y] takes the one-workgroup Gram (K + 1 <= 144).  The knot count sets the width, so the
+# global-memory LU and the 64 x 64-block Gram (full and delta) are reached with PLD's own matrices and priors at 1200 - 2000 cadences.
+_KNOT_CUBES = {}
+
+
+def _many_knot_cubes(n, npix):
+    """Two cutouts; in each, 25 random cadences are brighter by 1, 3 or 10 per cent in every pixel, so that the clip loop has
+    work (the oracle clips 15 - 21 per cutout).  Cached: the resident-path test shares the first case's cubes."""
+    from lightkurve_amd import synth
+    if (n, npix) not in _KNOT_CUBES:
+        rng = np.random.default_rng(n + npix)
+        cubes = []
+        for i in range(2):
+            t, flux, err, _ = synth.pld_cutout(4, 40 + i, n=n, npix=npix)
+            flux = flux.copy()
+            flux[rng.choice(n, 25, replace=False)] *= (1 + rng.choice([0.01, 0.03, 0.1], 25)).astype(np.float32)[:, None, None]
+            cubes.append(PixelCube(t, flux, err, mission="K2"))
+        _KNOT_CUBES[(n, npix)] = cubes
+    return _KNOT_CUBES[(n, npix)]
+
+
+@pytest.mark.parametrize("n,npix,spline_n_knots,K", [(1200, 9, 80, 145), (1500, 11, 100, 165), (2000, 11, 140, 205)])
+def test_many_spline_knots_take_the_wide_solver(n, npix, spline_n_knots, K):
+    """Design matrices of 145 / 165 / 205 columns (3 and 4 blocks of 64), a prior on every column, a clip loop that removes
+    cadences over several passes: identical outlier masks and corrected flux within the file's 1e-6 of the median.  (The
+    oracle's normal matrix has condition number about 2e5, 1e4 after diagonal scaling.)  Measured: 6e-9 .. 2.6e-8 of the median."""
+    from lightkurve_amd import _capi
+    assert _capi.pld_design_width(npix * npix, npix * npix, 3, 16, spline_n_knots) == K > 141
+    cubes = _many_knot_cubes(n, npix)
+    corrected, outl = pld_correct_batch(cubes, pld_order=3, pca_components=16, spline_n_knots=spline_n_knots)
+    allm = np.ones((npix, npix), bool)
+    for i, c in enumerate(cubes):
+        r = O.pld_correct(c.time, c.flux, c.flux_err, allm, allm, allm, pld_order=3, pca_components=16,
+                          spline_n_knots=spline_n_knots, spline_degree=5)
+        assert r["X"].shape[1] == K
+        d = np.max(np.abs(corrected[i] - r["corrected"])) / np.median(r["corrected"])
+        print("K=%d cutout %d: %d clipped, corrected flux within %.2e of the median" % (K, i, r["outlier_mask"].sum(), d))
+        assert r["outlier_mask"].sum() >= 10                        # the clip loop had work
+        assert np.array_equal(outl[i], r["outlier_mask"]), i
+        assert d < 1e-6, i
+
+
+def test_many_spline_knots_resident_path_same_bits():
+    """The first case above through DevicePixelCubeBatch: the resident path computes its knots on the device and must hand the
+    wide regression the same numbers — equality of bits with pld_correct_batch, as test_pixcube_gpu.py states at the default width."""
+    from lightkurve_amd.device import DevicePixelCubeBatch
+    cubes = _many_knot_cubes(1200, 9)
+    corrected, outl = DevicePixelCubeBatch.from_cubes(cubes).pld_correct(pld_order=3, pca_components=16, spline_n_knots=80)
+    ref_c, ref_o = pld_correct_batch(cubes, pld_order=3, pca_components=16, spline_n_knots=80)
+    assert corrected.shape == ref_c.shape == (2, 1200) and ref_o.sum() >= 20
+    assert np.array_equal(corrected, ref_c) and np.array_equal(outl, ref_o)

@@ -105,8 +105,10 @@ def test_clip_loop_delta_gram_and_its_overflow_vs_oracle():
 @pytest.mark.parametrize("K", [3, 16, 17, 33, 50, 70, 90, 110, 128, 141, 143, 145])
 def test_narrow_gram_kernel_every_tile_count(K):
     """[X | y] of K + 1 <= 144 columns takes the one-workgroup-per-matrix Gram kernel (T = 1 .. 9 tile columns, its waves'
-    tile runs differ with T); 145 is the first width on the 64 x 64-block kernel again.  Ragged N (partial last stage),
-    weights, a cadence mask: coefficients and model against the oracle."""
+    tile runs differ with T); 145 is the first width on the 64 x 64-block kernel again.  The solver changes earlier: up to
+    K = 141 the augmented system fits solve_lds_kernel's LDS plan (K (K + 1) + 2 K + 34 <= 20480 doubles), so 143 and 145 take
+    the global-memory solve_kernel (test_regress_wide_gpu.py covers that family).  Ragged N (partial last stage), weights,
+    a cadence mask: coefficients and model against the oracle."""
     rng = np.random.default_rng(100 + K)
     ns = [517, 1000, 33]
     if K >= 33:
