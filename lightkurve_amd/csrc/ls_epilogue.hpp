@@ -40,6 +40,69 @@ __device__ __forceinline__ double gls_power_sums(double Sh, double Ch, double S,
     return p;
 }
 
+// 1 / sqrt(x) to <= 2 ulp for normal x.  Device: v_rsq_f64 (2^-23 relative) and one third-order step, y (1 + e/2 + 3 e^2/8)
+// with e = 1 - x y^2 — six instructions, one of them at the transcendental rate, where 1.0 / sqrt(x) compiles to two IEEE
+// sequences of 11-16.  Host: the plain quotient.
+__host__ __device__ __forceinline__ double rsqrt_refined(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double y = __builtin_amdgcn_rsq(x);
+    const double e = fma(-(x * y), y, 1.0);
+    return fma(y * e, fma(0.375, e, 0.5), y);
+#else
+    return 1.0 / sqrt(x);
+#endif
+}
+
+// gls_power_sums() with the angle from two reciprocal square roots: per output five division / square-root sequences where
+// that has eight, two divisions and three square roots fewer (lsfast.hip's kernels: the closed form runs with nothing beside
+// it there; the exact kernels of ls.hip keep gls_power_sums() and their bits).  With tan 2w = num / den the reference takes
+// 2w in (-pi/2, pi/2):
+//   cos 2w = |den| / hypot(num, den),  sin 2w = sign(den) num / hypot(num, den)                      one rsqrt, no division
+//   u = cos^2 w = (1 + cos 2w) / 2 in [1/2, 1],  cos w = u / sqrt(u),  sin w = sin 2w / (2 cos w)    one rsqrt
+// Same NaNs as the reference: den == 0 (inf * 0 there, 0 / 0 when num is zero too), SS == 0 with YS == 0 (f = 0).  Where
+// num^2 + den^2 would underflow (both below 1e-150: no real light curve) the angle comes from the reference's expression.
+// (One division for both quotients of p, (YC^2 SS + YS^2 CC) / (CC SS), measured no gain: profiles/lsfast_closed_form_ab.txt.)
+__device__ __forceinline__ double gls_power_sums_lean(double Sh, double Ch, double S, double C, double S2, double C2,
+                                                      int fit_mean, int norm, double YY, double psd_factor, double nN,
+                                                      double scale) {
+    double num = S2, den = C2;
+    if (fit_mean) {
+        num = S2 - 2.0 * S * C;
+        den = C2 - (C * C - S * S);
+    }
+    double C2w, S2w;
+    if (fmax(fabs(num), fabs(den)) >= 1e-150) {
+        const double r = rsqrt_refined(num * num + den * den);
+        C2w = fabs(den) * r;
+        S2w = (den == 0.0) ? NAN : ((den < 0.0) ? -num : num) * r;
+    } else {
+        const double tan2 = num / den;
+        C2w = 1.0 / sqrt(1.0 + tan2 * tan2);
+        S2w = tan2 * C2w;
+    }
+    const double u = 0.5 + 0.5 * C2w;
+    const double rc = rsqrt_refined(u);
+    const double Cw = u * rc;
+    const double Sw = 0.5 * S2w * rc;
+    const double YC = Ch * Cw + Sh * Sw;
+    const double YS = Sh * Cw - Ch * Sw;
+    double CC = 0.5 * (1.0 + C2 * C2w + S2 * S2w);
+    double SS = 0.5 * (1.0 - C2 * C2w - S2 * S2w);
+    if (fit_mean) {
+        const double a = C * Cw + S * Sw, bq = S * Cw - C * Sw;
+        CC -= a * a;
+        SS -= bq * bq;
+    }
+    double p = YC * YC / CC + YS * YS / SS;
+    switch (norm) {
+        case LK_NORM_STANDARD: p /= YY; break;
+        case LK_NORM_PSD: p *= psd_factor; break;
+        case LK_NORM_LK_AMPLITUDE: p = sqrt(p * psd_factor) * sqrt(4.0 / nN); break;  // (the compiler hoists the second
+        default: p = p * psd_factor * scale; break;                                  //  root out of the callers' loops)
+    }
+    return p;
+}
+
 // ---- multi-term least-squares periodogram from the harmonic trig sums (astropy chi2_impl.py / fastchi2_impl.py)
 template <int NT>
 struct Chi2Sums {

@@ -951,7 +951,7 @@ __global__ __launch_bounds__(512) void fft_rows_power_kernel(const double2 *__re
                     const double cc = c * c - s * s, ss = 2.0 * s * c;
                     c2 = make_double2(c2.x * cc - c2.y * ss, c2.x * ss + c2.y * cc);
                 }
-                const double pw = gls_power_sums(a.y, a.x, bq.y, bq.x, c2.y, c2.x, fit_mean, norm, st.YY, 0.5 * st.wsum, nn, sc);
+                const double pw = gls_power_sums_lean(a.y, a.x, bq.y, bq.x, c2.y, c2.x, fit_mean, norm, st.YY, 0.5 * st.wsum, nn, sc);
                 power[(size_t)b * (size_t)M + k] = pw;
                 if (pw == pw && peak_better(pw, k, best_v, best_k)) {  // ascending k within the thread: strict > would do
                     best_v = pw;
@@ -1166,7 +1166,7 @@ __global__ __launch_bounds__(Rows512::NT, 2) void fft_rows512_power_kernel(
                 sincos(twopi * st.t0 * (f0 + df * (double)kfirst), &ph_s, &ph_c);
                 sincos(twopi * st.t0 * (df * (double)((long long)32 << m1)), &st_s, &st_c);
             }
-            // a rolled loop (the closed form is ~350 instructions per output): the kept outputs rotate through slot 0
+            // a rolled loop (the closed form is ~200 instructions per output): the kept outputs rotate through slot 0
 #pragma unroll 1
             for (int q = 0; q < nq; ++q) {
                 const long long k = (long long)k1 + ((long long)(ka + 16 * (2 * q + e)) << m1);
@@ -1179,7 +1179,7 @@ __global__ __launch_bounds__(Rows512::NT, 2) void fft_rows512_power_kernel(
                         const double cc = c * c - s * s, ss = 2.0 * s * c;
                         c2 = make_double2(c2.x * cc - c2.y * ss, c2.x * ss + c2.y * cc);
                     }
-                    const double pw = gls_power_sums(a.y, a.x, bq.y, bq.x, c2.y, c2.x, fit_mean, norm, st.YY, 0.5 * st.wsum, nn, sc);
+                    const double pw = gls_power_sums_lean(a.y, a.x, bq.y, bq.x, c2.y, c2.x, fit_mean, norm, st.YY, 0.5 * st.wsum, nn, sc);
                     power[(size_t)b * (size_t)M + k] = pw;
                     if (pw == pw && peak_better(pw, k, best_v, best_k)) {  // ascending k within the thread
                         best_v = pw;
@@ -1324,7 +1324,7 @@ __global__ __launch_bounds__(256) void lsf_power_kernel(const double2 *__restric
         c2 = make_double2(c2.x * c - c2.y * s, c2.x * s + c2.y * c);
     }
     const double n = (double)(n_off[b + 1] - n_off[b]);
-    power[(size_t)b * (size_t)M + j] = gls_power_sums(a.y, a.x, bq.y, bq.x, c2.y, c2.x, fit_mean, norm, st.YY,
+    power[(size_t)b * (size_t)M + j] = gls_power_sums_lean(a.y, a.x, bq.y, bq.x, c2.y, c2.x, fit_mean, norm, st.YY,
                                                       0.5 * st.wsum, n, scale ? scale[b] : 1.0);
 }
 
@@ -1648,8 +1648,11 @@ int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *
     if (rc) return rc;
     if (rebase) t = d_trel;
     const int tw = tile_width(m1, m2);
+    // (without the register path every target goes through lsf_scatter_kernel, time-ordered ones too: no rows_used, so that
+    // the prep kernel leaves the scales of the quanta for all of them — with the table it skips them for ordered targets,
+    // and the scatter then added plain doubles in no fixed order: two runs of one call differed in the last bits)
     hipLaunchKernelGGL(lsf_prep_kernel, dim3(B), dim3(PREP_NT), 0, stream, t, y, dy, d_off, (fit_mean || center_data) ? 1 : 0,
-                       normalization == LK_NORM_STANDARD ? 1 : 0, d_stats, df, nfft, m2, d_rows);
+                       normalization == LK_NORM_STANDARD ? 1 : 0, d_stats, df, nfft, m2, reg_path ? d_rows : (int *)nullptr);
     // ---- plan: the pruned column kernel applies when every grid of every target keeps its samples in the first
     // P <= 256 rows (P < N1) and the row kernel can read 16-column tiles.  The decision needs two device words, so
     // the call synchronises `stream` once here (20-30 us against a >= 1 ms step, measured on the fused route).  The register

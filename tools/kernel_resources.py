@@ -76,9 +76,42 @@ def short(name):
     return name[:cut].replace("lk::", "").replace("(anonymous namespace)::", "")
 
 
+CLOSED_FORM = ("fft_rows512_power_kernel", "fft_rows_power_kernel", "lsf_power_kernel")
+
+
+def closed_form_counts():
+    """Static counts of the fp64 reciprocal / reciprocal-square-root instructions (the ones that issue at the transcendental
+    rate; one per IEEE division or square root sequence) in the lsfast.hip kernels that hold the closed form, from -S."""
+    src = os.path.join(CSRC, "lsfast.hip")
+    cmd = [HIPCC] + flags_for(src) + ["--cuda-device-only", "-S", src, "-o", "-"]
+    p = subprocess.run(cmd, capture_output=True, text=True, cwd=CSRC)
+    if p.returncode != 0:
+        raise SystemExit("compile failed: %s\n%s" % (" ".join(cmd), p.stderr[-2000:]))
+    counts, cur = {}, None
+    for line in p.stdout.splitlines():
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            cur = counts.setdefault(m.group(1), [0, 0])
+        elif line.startswith(".Lfunc_end"):
+            cur = None
+        elif cur is not None:
+            op = line.split()[0] if line.split() else ""
+            cur[0] += op.startswith("v_rcp_f64")
+            cur[1] += op.startswith("v_rsq_f64")
+    names = demangle(list(counts))
+    rows = sorted((short(n), c) for n, c in zip(names, counts.values()) if short(n).split("<")[0] in CLOSED_FORM)
+    lines = ["### lsfast.hip: closed-form kernels, fp64 reciprocals and reciprocal square roots (whole kernel, static)", "",
+             "Every branch counts: all four normalisations, both `fit_mean` settings and the underflow fall-back of",
+             "`gls_power_sums_lean`; what one output executes is in `profiles/lsfast_closed_form_ab.txt`.", "",
+             "| kernel | v_rcp_f64 | v_rsq_f64 |", "|---|---:|---:|"]
+    lines += ["| `%s` | %d | %d |" % (n, c[0], c[1]) for n, c in rows]
+    return lines + [""]
+
+
 def table():
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
+        extra = ex.submit(closed_form_counts)
         results = list(ex.map(lambda f: analyse(os.path.join(CSRC, f)), srcs))
     lines = ["# Kernel resources (generated by tools/kernel_resources.py — do not edit)", "",
              "`hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage`, the flags of `lightkurve_amd/csrc/Makefile`.",
@@ -91,6 +124,8 @@ def table():
         for name, k in rows:
             lines.append("| `%s` | " % name + " | ".join(str(k.get(key, "")) for key, _ in FIELDS) + " |")
         lines.append("")
+        if f == "lsfast.hip":
+            lines += extra.result()
     return "\n".join(lines) + "\n"
 
 
