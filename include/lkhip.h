@@ -36,6 +36,8 @@
  *                           remain: one kept-cadence count per call, every count >= pca_components.
  *   lk_fold_batch*       <- LightCurve.fold, src/lightkurve/lightcurve.py:1089-1214 (astropy TimeSeries.fold + sort).
  *   lk_pg_logmedian_batch* / lk_pg_boxsmooth_batch* <- Periodogram.smooth, periodogram.py:182-284.
+ *   lk_pg_snr_batch_dev / lk_pg_acf_metric_batch_dev / lk_pg_numax_pick_batch_dev / lk_pg_deltanu_batch* <- flatten,
+ *                           estimate_numax and estimate_deltanu (seismology/) on spectra that stay in device memory.
  *
  * Conventions
  *   - Every function returns an int status: LK_OK, LK_EINVAL (-> ValueError), LK_ENOMEM (-> MemoryError),
@@ -196,6 +198,52 @@ int lk_pg_acf2d_batch(lk_handle *h, int B, int64_t M, const double *power, int n
                       double *acf2d, double *metric);
 int lk_pg_acf2d_batch_dev(lk_handle *h, int B, int64_t M, const double *power, int n_win, const int32_t *win_start,
                           int W, double *acf2d, double *metric, void *stream);
+
+/* ---- the seismology chain on spectra that stay in HBM (flatten -> estimate_numax -> estimate_deltanu of
+ * src/lightkurve/seismology/; device.DevicePeriodogramBatch).  B periodograms on one grid of M points, row-major [B][M].
+ *
+ * lk_pg_snr_batch_dev: out = power / bkg, element by element in IEEE double (Periodogram.flatten's division,
+ * periodogram.py:381-429, after lk_pg_logmedian_batch_dev or lk_pg_boxsmooth_batch_dev made bkg).
+ *
+ * lk_pg_acf_metric_batch_dev: the `metric` of lk_pg_acf2d_batch_dev, bit for bit, without its acf2d output (the numax
+ * estimator reads nothing else; B x n_win doubles leave the chip instead of B x n_win x W).
+ *
+ * lk_pg_numax_pick_batch_dev: the tail of estimate_numax_acf2d (numax_estimators.py:181-186), one workgroup per target:
+ * metric_smooth[b] = metric[b] convolved with the n_taps taps (HOST array: the normalised Gaussian1DKernel, n_taps odd;
+ * boundary='extend', i.e. the end values replicated; products summed in tap order), or a copy of metric[b] when
+ * n_taps == 0 (metric_smooth may then be metric itself); argmax_out[b] = np.argmax(metric_smooth[b]): the first maximum,
+ * a NaN counts as the maximum.  metric, metric_smooth: B x n_win; argmax_out: int64[B].
+ *
+ * lk_pg_deltanu_batch(_dev): estimate_deltanu_acf2d (deltanu_estimators.py:18-153) for B targets, each with its OWN
+ * window, one workgroup per target.  HOST tables, one entry per target, which the caller derives from the target's numax
+ * with the reference's scalar arithmetic (lightkurve_amd/seismology.py::_deltanu_plan): start / width = first sample and
+ * number W of samples of the window (numax -+ one envelope FWHM); deltanu_emp = 0.294 numax^0.772 (NaN: skip the target);
+ * distance = floor(deltanu_emp / 2 / fs); step, stop = the reference's lags np.linspace(0, W fs, W): lag i = i * step,
+ * the last one = stop (the grid spacing fs enters through these three only).  Per target: the window minus its nanmean,
+ * C[0] and C[lag] for the lags with `lag > emp - 0.25 emp and lag < emp + 0.25 emp` alone (the same bits as
+ * lk_pg_acf2d_batch gives that window), acf = (|C^2| / |C[0]^2|) / (3 / (2 W)), scipy.signal.find_peaks(acf[sel],
+ * distance=distance) (plateau midpoints, no peak at either end of the slice, highest peak first and its neighbours
+ * closer than ceil(distance) dropped; the order of peaks of exactly equal height is unspecified, as in scipy), and
+ * deltanu = the lag of the surviving peak closest to deltanu_emp (the first of equally close ones).
+ * Outputs [B]: deltanu (NaN unless status 0), n_peaks (surviving peaks), sel_lo / sel_len (the selected lags), status:
+ * 0 ok; 1 skipped (deltanu_emp NaN); 2 the window is not inside [0, M), has fewer than 2 or more than 16384 samples, or
+ * does not fit the 160 KB of LDS together with its selection; 3 nothing to pick (no local maximum inside the
+ * selection, or distance < 1, where scipy raises).  No error is raised for a target.  acf (nullable): B x max_sel, row b =
+ * the rescaled ACF on the selection (sel_len[b] values, at most max_sel are written), NaN behind it. */
+int lk_pg_snr_batch_dev(lk_handle *h, int B, int64_t M, const double *power, const double *bkg, double *out,
+                        void *stream);
+int lk_pg_acf_metric_batch_dev(lk_handle *h, int B, int64_t M, const double *power, int n_win, const int32_t *win_start,
+                               int W, double *metric, void *stream);
+int lk_pg_numax_pick_batch_dev(lk_handle *h, int B, int n_win, const double *metric, const double *taps, int n_taps,
+                               double *metric_smooth, int64_t *argmax_out, void *stream);
+int lk_pg_deltanu_batch(lk_handle *h, int B, int64_t M, const double *power, const int32_t *start, const int32_t *width,
+                        const double *deltanu_emp, const double *distance, const double *step, const double *stop,
+                        int max_sel, double *deltanu, int32_t *n_peaks, int32_t *status, int32_t *sel_lo,
+                        int32_t *sel_len, double *acf);
+int lk_pg_deltanu_batch_dev(lk_handle *h, int B, int64_t M, const double *power, const int32_t *start,
+                            const int32_t *width, const double *deltanu_emp, const double *distance, const double *step,
+                            const double *stop, int max_sel, double *deltanu, int32_t *n_peaks, int32_t *status,
+                            int32_t *sel_lo, int32_t *sel_len, double *acf, void *stream);
 
 /* ---- Lomb-Scargle, lightkurve's DEFAULT method ls_method="fast" (periodogram.py:650): Press & Rybicki extirpolation
  * + FFT evaluation of the trig sums (astropy fast_impl.py / utils.py trig_sum, extirpolate), regular grid only.

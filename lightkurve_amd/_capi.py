@@ -124,7 +124,17 @@ SIGNATURES = [
      [_vp, ctypes.c_int, ctypes.c_int64, _c_dp, ctypes.c_int, _c_i32p, ctypes.c_int, _c_dp, _c_dp]),
     ("lk_pg_acf2d_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _c_i32p, ctypes.c_int, _vp, _vp, _vp]),
-    ("lk_sigma_clip_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _c_dp, ctypes.c_double, ctypes.c_int, _c_u8p]),
+    ("lk_pg_snr_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    ("lk_pg_acf_metric_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _c_i32p, ctypes.c_int, _vp, _vp]),
+    ("lk_pg_numax_pick_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _c_dp, ctypes.c_int, _vp, _vp, _vp]),
+    ("lk_pg_deltanu_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int64, _c_dp, _c_i32p, _c_i32p, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_dp, _c_i32p,
+      _c_i32p, _c_i32p, _c_i32p, _c_dp]),
+    ("lk_pg_deltanu_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int64, _vp, _c_i32p, _c_i32p, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int, _vp, _vp, _vp, _vp,
+      _vp, _vp, _vp]),
+    ("lk_sigma_clip_batch",ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _c_dp, ctypes.c_double, ctypes.c_int, _c_u8p]),
     ("lk_sigma_clip_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _vp, ctypes.c_double, ctypes.c_int, _vp, _vp]),
     ("lk_outlier_mask_batch", ctypes.c_int,
      [_vp, ctypes.c_int, _c_ip, _c_dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, _c_u8p]),
@@ -701,6 +711,35 @@ def pg_acf2d_batch(power, win_start, W, device=0):
     met = np.empty((B, ws.size), dtype=np.float64)
     _check(_lib.lk_pg_acf2d_batch(h._h, B, M, _ptr(power), int(ws.size), _ptr(ws, _c_i32p), W, _ptr(acf), _ptr(met)))
     return acf, met
+
+
+def _deltanu_tables(plan, B):
+    """The six per-target HOST tables of ``lk_pg_deltanu_batch`` from ``seismology._deltanu_plan``'s dict (kept alive by the
+    caller for the call) and the widest selection."""
+    tabs = [np.ascontiguousarray(plan[k], dtype=np.int32) for k in ("start", "width")]
+    tabs += [np.ascontiguousarray(plan[k], dtype=np.float64) for k in ("deltanu_emp", "distance", "step", "stop")]
+    if any(t.shape != (B,) for t in tabs):
+        raise ValueError("the deltanu plan does not match the batch")
+    return tabs, int(np.max(plan["sel_len"], initial=0))
+
+
+def pg_deltanu_batch(power, plan, want_acf=False, device=0):
+    """``estimate_deltanu_acf2d`` for B periodograms on one grid (power float64[B, M]), each with its own window from
+    ``seismology._deltanu_plan`` -> dict of ``deltanu`` float64[B], ``n_peaks`` / ``status`` / ``sel_lo`` / ``sel_len`` int32[B]
+    and, with ``want_acf``, ``acf`` float64[B, max_sel] (the rescaled ACF on the selected lags, NaN behind them)."""
+    h = Handle.get(device)
+    power = np.ascontiguousarray(np.atleast_2d(power), dtype=np.float64)
+    B, M = power.shape
+    tabs, max_sel = _deltanu_tables(plan, B)
+    out = dict(deltanu=np.empty(B), n_peaks=np.empty(B, dtype=np.int32), status=np.empty(B, dtype=np.int32),
+               sel_lo=np.empty(B, dtype=np.int32), sel_len=np.empty(B, dtype=np.int32))
+    if want_acf:
+        out["acf"] = np.empty((B, max_sel))
+    _check(_lib.lk_pg_deltanu_batch(h._h, B, M, _ptr(power), _ptr(tabs[0], _c_i32p), _ptr(tabs[1], _c_i32p), _ptr(tabs[2]),
+                                    _ptr(tabs[3]), _ptr(tabs[4]), _ptr(tabs[5]), max_sel, _ptr(out["deltanu"]),
+                                    _ptr(out["n_peaks"], _c_i32p), _ptr(out["status"], _c_i32p), _ptr(out["sel_lo"], _c_i32p),
+                                    _ptr(out["sel_len"], _c_i32p), _ptr(out.get("acf"))))
+    return out
 
 
 def argmax_batch(x, device=0):

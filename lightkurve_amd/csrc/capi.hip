@@ -419,6 +419,61 @@ int lk_pg_acf2d_batch(lk_handle *h, int B, int64_t M, const double *power, int n
     return rc ? rc : io.finish();
 }
 
+// ------------------------------------------------------------------------------------------------ resident seismology
+int lk_pg_snr_batch_dev(lk_handle *h, int B, int64_t M, const double *power, const double *bkg, double *out,
+                        void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::pg_snr_launch(h, B, M, power, bkg, out, static_cast<hipStream_t>(stream));
+}
+
+int lk_pg_acf_metric_batch_dev(lk_handle *h, int B, int64_t M, const double *power, int n_win, const int32_t *win_start,
+                               int W, double *metric, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::pg_acf_metric_launch(h, B, M, power, n_win, win_start, W, metric, static_cast<hipStream_t>(stream));
+}
+
+int lk_pg_numax_pick_batch_dev(lk_handle *h, int B, int n_win, const double *metric, const double *taps, int n_taps,
+                               double *metric_smooth, int64_t *argmax_out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::pg_numax_pick_launch(h, B, n_win, metric, taps, n_taps, metric_smooth, argmax_out,
+                                    static_cast<hipStream_t>(stream));
+}
+
+int lk_pg_deltanu_batch_dev(lk_handle *h, int B, int64_t M, const double *power, const int32_t *start,
+                            const int32_t *width, const double *deltanu_emp, const double *distance, const double *step,
+                            const double *stop, int max_sel, double *deltanu, int32_t *n_peaks, int32_t *status,
+                            int32_t *sel_lo, int32_t *sel_len, double *acf, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::pg_deltanu_launch(h, B, M, power, start, width, deltanu_emp, distance, step, stop, max_sel, deltanu,
+                                 n_peaks, status, sel_lo, sel_len, acf, static_cast<hipStream_t>(stream));
+}
+
+int lk_pg_deltanu_batch(lk_handle *h, int B, int64_t M, const double *power, const int32_t *start, const int32_t *width,
+                        const double *deltanu_emp, const double *distance, const double *step, const double *stop,
+                        int max_sel, double *deltanu, int32_t *n_peaks, int32_t *status, int32_t *sel_lo,
+                        int32_t *sel_len, double *acf) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && M >= 1 && max_sel >= 0, "need B >= 0, M >= 1, max_sel >= 0");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(power && deltanu && n_peaks && status && sel_lo && sel_len, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const double *dp;
+    double *dd, *da;
+    int32_t *dn, *ds, *dlo, *dlen;
+    lk::StagedCall io(h);
+    int rc = io.in(dp, power, (size_t)B * (size_t)M).out(dd, deltanu, (size_t)B).out(dn, n_peaks, (size_t)B)
+                 .out(ds, status, (size_t)B).out(dlo, sel_lo, (size_t)B).out(dlen, sel_len, (size_t)B)
+                 .out(da, acf, (size_t)B * (size_t)max_sel).stage();
+    if (rc) return rc;
+    rc = lk::pg_deltanu_launch(h, B, M, dp, start, width, deltanu_emp, distance, step, stop, max_sel, dd, dn, ds, dlo,
+                               dlen, da, nullptr);
+    return rc ? rc : io.finish();
+}
+
 // ------------------------------------------------------------------------------------------------ LS 'fast'
 int lk_ls_fast_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *y,
                          const double *dy, double f0, double df, int64_t M, int fit_mean, int center_data,

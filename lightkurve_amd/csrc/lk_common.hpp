@@ -279,6 +279,18 @@ int bin_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, 
                hipStream_t stream);
 int pg_acf2d_launch(lk_handle *h, int B, int64_t M, const double *power, int n_win, const int *win_start_host, int W,
                     double *acf2d, double *metric, hipStream_t stream);
+// pgsmooth.hip, the resident seismology chain: metric of the 2-D ACF alone; power / background; Gaussian smoothing and
+// argmax of the metric (taps_host nullable: no smoothing); deltanu of B targets with their own windows (acf nullable)
+int pg_acf_metric_launch(lk_handle *h, int B, int64_t M, const double *power, int n_win, const int *win_start_host, int W,
+                         double *metric, hipStream_t stream);
+int pg_snr_launch(lk_handle *h, int B, int64_t M, const double *power, const double *bkg, double *out,
+                  hipStream_t stream);
+int pg_numax_pick_launch(lk_handle *h, int B, int n_win, const double *metric, const double *taps_host, int nk,
+                         double *metric_smooth, int64_t *argmax_out, hipStream_t stream);
+int pg_deltanu_launch(lk_handle *h, int B, int64_t M, const double *power, const int *start_host, const int *width_host,
+                      const double *emp_host, const double *distance_host, const double *step_host,
+                      const double *stop_host, int max_sel, double *deltanu, int *n_peaks, int *status, int *sel_lo,
+                      int *sel_len, double *acf, hipStream_t stream);
 int cube_aperture_launch(lk_handle *h, int B, int N, int npix, const float *flux, const float *flux_err, const uint8_t *mask,
                          int mask_stride, float *flux_out, float *err_out, uint8_t *keep_out, int64_t *kept_host,
                          int64_t *nonfinite_host, hipStream_t stream);

@@ -20,6 +20,7 @@ No torch: device memory, copies and the stream come from liblkhip.so itself (``l
 ``lk_stream_*``).  Results are bit-identical to the staged host path — the same kernels run on the same numbers.
 """
 import ctypes
+import math
 import threading
 import weakref
 
@@ -27,9 +28,11 @@ import numpy as np
 
 from . import _capi
 from . import packed
+from . import periodogram as _pg
+from . import seismology as _seis
 
-__all__ = ["DeviceBuffer", "DeviceLightCurveBatch", "DeviceFoldedBatch", "DeviceBLSResult", "DevicePixelCubeBatch",
-           "release_device_pool"]
+__all__ = ["DeviceBuffer", "DeviceLightCurveBatch", "DeviceFoldedBatch", "DeviceBLSResult", "DevicePeriodogramBatch",
+           "DevicePixelCubeBatch", "release_device_pool"]
 
 _vp = ctypes.c_void_p
 _ip = ctypes.POINTER(ctypes.c_int64)
@@ -962,6 +965,16 @@ class DeviceLightCurveBatch(object):
                                                 to_host=False, want_peaks=True)
         return peaks
 
+    def to_periodogram(self, frequency, normalization="psd", freq_unit=None, oversample_factor=None, ls_method="fast", nterms=1):
+        """``lc.to_periodogram(frequency=..., normalization=...)`` for every light curve, the spectra left in HBM: a
+        ``DevicePeriodogramBatch`` over ``to_periodogram_power(..., to_host=False)`` on the grid ``frequency`` (in
+        ``freq_unit``: microhertz for 'psd', 1/d for 'amplitude' unless given) — the head of the resident chain
+        ``batch.to_periodogram(f).flatten().estimate_numax()`` / ``.estimate_seismology()``."""
+        plan = packed.ls_grid_plan(frequency, normalization, freq_unit, oversample_factor, ls_method, nterms)
+        d_pow = self.to_periodogram_power(frequency, normalization, freq_unit, oversample_factor, ls_method, nterms, to_host=False)
+        return DevicePeriodogramBatch(plan.frequency, d_pow, len(self), frequency_unit=plan.freq_unit, power_unit=plan.power_unit,
+                                      device=self.device, stream=self.stream)
+
     def ls_model(self, frequency, nterms=1, freq_unit=None, use_flux_err=False, fit_mean=True, center_data=True, want_model=True,
                  want_residual=False, keep_mean=True, time=None):
         """``LombScarglePeriodogram.model`` before its normalisation (reference periodogram.py:991-1018 over astropy
@@ -1326,6 +1339,196 @@ class DeviceBLSResult(object):
 
 
 # ------------------------------------------------------------------------------------------------ pixel cubes
+class DevicePeriodogramBatch(object):
+    """B power spectra on ONE frequency grid, in HBM: ``frequency`` (host float64[M], in ``frequency_unit``) and ``power``
+    (``DeviceBuffer``, row-major B x M) — what ``DeviceLightCurveBatch.to_periodogram`` returns and the seismology chain of
+    the reference consumes one object at a time:
+
+        pg = lc.to_periodogram(normalization="psd"); snr = pg.flatten()          # periodogram.py:381-429
+        seis = snr.to_seismology(); seis.estimate_numax(); seis.estimate_deltanu()   # seismology/*_estimators.py
+
+        pgs = batch.to_periodogram(f, normalization="psd")
+        res = pgs.estimate_seismology()               # numax, deltanu, status per target; 8 + 16 B per target cross PCIe
+
+    Every method enqueues on the batch's stream; nothing of the size of a spectrum leaves the device unless asked for."""
+
+    def __init__(self, frequency, d_power, B, frequency_unit="uHz", power_unit="", device=0, stream=0):
+        self.handle = _capi.Handle.get(device)
+        self.device, self.stream = int(device), int(stream or 0)
+        self.frequency = np.ascontiguousarray(frequency, dtype=np.float64)
+        _pg._freq_unit_factor(frequency_unit)
+        if self.frequency.ndim != 1 or self.frequency.size <= 1:
+            raise ValueError("frequency and power must have a length greater than 1.")
+        self.frequency_unit, self.power_unit = frequency_unit, power_unit
+        self.B, self.M = int(B), int(self.frequency.size)
+        if d_power.capacity < self.B * self.M * 8:
+            raise ValueError("device buffer smaller than the batch it is said to hold")
+        self.power = d_power
+        self.numax = None                # float64[B] of the last estimate_numax
+        self._keep = []                  # host staging the stream may still be reading
+
+    @classmethod
+    def from_arrays(cls, frequency, power, frequency_unit="uHz", device=0, stream=0):
+        """H2D once: ``frequency`` float64[M] shared by the batch, ``power`` float64[B, M] (one row: [M])."""
+        power = np.ascontiguousarray(np.atleast_2d(power), dtype=np.float64)
+        frequency = np.asarray(frequency, dtype=np.float64)
+        if power.ndim != 2 or frequency.ndim != 1 or power.shape[1] != frequency.size:
+            raise ValueError("frequency and power must have the same length.")
+        h = _capi.Handle.get(device)
+        d_pow, keep = _upload(h, power, stream)
+        out = cls(frequency, d_pow, power.shape[0], frequency_unit=frequency_unit, device=device, stream=stream)
+        out._keep = [keep]
+        return out
+
+    def __len__(self):
+        return self.B
+
+    def synchronize(self):
+        _capi._check(_capi._lib.lk_stream_synchronize(self.handle._h, _vp(self.stream or None)))
+        self._keep = []
+
+    def _is_evenly_spaced(self):
+        freqdiff = np.diff(self.frequency)
+        return bool(np.allclose(freqdiff[0], freqdiff))
+
+    def _like(self, d_power, power_unit=None):
+        out = DevicePeriodogramBatch(self.frequency, d_power, self.B, frequency_unit=self.frequency_unit,
+                                     power_unit=self.power_unit if power_unit is None else power_unit, device=self.device,
+                                     stream=self.stream)
+        out._keep = list(self._keep)
+        return out
+
+    def to_host(self):
+        """float64[B, M]."""
+        out = self.power.download(np.float64, self.B * self.M, stream=self.stream).reshape(self.B, self.M)
+        self._keep = []
+        return out
+
+    def to_periodograms(self):
+        """One host ``Periodogram`` per target."""
+        return [_pg.Periodogram(self.frequency, row, frequency_unit=self.frequency_unit, power_unit=self.power_unit)
+                for row in self.to_host()]
+
+    def peaks(self):
+        """``Periodogram.max_power`` / ``frequency_at_max_power`` (reference periodogram.py:127-140) per target: dict of
+        ``max_power``, ``argmax`` (-1 for an all-NaN row) and ``frequency``; 16 B per target cross PCIe."""
+        h, B, st = self.handle, self.B, _vp(self.stream or None)
+        d_max, d_arg = DeviceBuffer(h, max(B, 1) * 8), DeviceBuffer(h, max(B, 1) * 8)
+        if B:
+            _capi._check(_capi._lib.lk_argmax_batch_dev(h._h, B, self.M, _vp(self.power.ptr), _vp(d_max.ptr), _vp(d_arg.ptr), st))
+        mx = d_max.download(np.float64, B, stream=self.stream)
+        am = d_arg.download(np.int64, B, stream=self.stream)
+        return dict(max_power=mx, argmax=am, frequency=np.where(am >= 0, self.frequency[np.clip(am, 0, self.M - 1)], np.nan))
+
+    # ---------------------------------------------------------------- Periodogram.smooth / flatten
+    def smooth(self, method="boxkernel", filter_width=0.1):
+        """``Periodogram.smooth`` (reference periodogram.py:182-284) of every spectrum -> a new batch; the same planning,
+        checks and kernels as the host class (``lk_pg_boxsmooth_batch_dev`` / ``lk_pg_logmedian_batch_dev``)."""
+        method = _pg.validate_method(method, ["boxkernel", "logmedian"])
+        h, B, M, st, lib = self.handle, self.B, self.M, _vp(self.stream or None), _capi._lib
+        if method == "boxkernel":
+            if filter_width <= 0.0:
+                raise ValueError("the `filter_width` parameter must be larger than 0 for the 'boxkernel' method.")
+            if not self._is_evenly_spaced():
+                raise ValueError("the 'boxkernel' method requires the periodogram to have a grid of evenly spaced "
+                                 "frequencies.")
+            fs = np.mean(np.diff(self.frequency))
+            taps = np.ascontiguousarray(_pg._box1d_kernel(math.ceil(filter_width / fs))[::-1])
+            d_out = DeviceBuffer(h, max(B * M, 1) * 8)
+            _capi._check(lib.lk_pg_boxsmooth_batch_dev(h._h, B, M, _vp(self.power.ptr), taps.ctypes.data_as(_dp), int(taps.size),
+                                                       _vp(d_out.ptr), st))
+            return self._like(d_out)
+        tabs = [np.ascontiguousarray(a, dtype=np.int32) for a in _pg._logmedian_windows(self.frequency, filter_width)]
+        d_out = DeviceBuffer(h, max(B * M, 1) * 8)
+        _capi._check(lib.lk_pg_logmedian_batch_dev(h._h, B, M, _vp(self.power.ptr), int(tabs[0].size), tabs[0].ctypes.data_as(_i32p),
+                                                   tabs[1].ctypes.data_as(_i32p), tabs[2].ctypes.data_as(_i32p),
+                                                   tabs[3].ctypes.data_as(_i32p), (8.0 / 9.0) ** 3, _vp(d_out.ptr), st))
+        return self._like(d_out)
+
+    def flatten(self, method="logmedian", filter_width=0.01, return_trend=False):
+        """``Periodogram.flatten`` (reference periodogram.py:381-429): power / smooth, unitless, as a new batch (and the
+        background batch with ``return_trend``); the division is ``lk_pg_snr_batch_dev``."""
+        bkg = self.smooth(method=method, filter_width=filter_width)
+        d_snr = DeviceBuffer(self.handle, max(self.B * self.M, 1) * 8)
+        _capi._check(_capi._lib.lk_pg_snr_batch_dev(self.handle._h, self.B, self.M, _vp(self.power.ptr), _vp(bkg.power.ptr),
+                                                    _vp(d_snr.ptr), _vp(self.stream or None)))
+        snr = self._like(d_snr, power_unit="")
+        return (snr, bkg) if return_trend else snr
+
+    # ---------------------------------------------------------------- seismology
+    def estimate_numax(self, numaxs=None, window_width=None, spacing=None, return_metric=False):
+        """``estimate_numax_acf2d`` (reference seismology/numax_estimators.py:15-205) per target, resident: the plan and its
+        ``ValueError``s are ``seismology._plan``'s on the shared grid; ``lk_pg_acf_metric_batch_dev`` forms the metric of
+        every window without storing the 2-D ACF, ``lk_pg_numax_pick_batch_dev`` smooths it and takes the argmax; 8 B per
+        target come back.  Returns a dict: ``numax`` float64[B] (also kept as ``self.numax``), ``numaxs``, ``window_width``
+        and, with ``return_metric``, ``metric`` and ``metric_smooth`` (float64[B, len(numaxs)])."""
+        numaxs, window_width, starts, W = _seis._plan(self, numaxs, window_width, spacing)
+        h, B, M, st, lib = self.handle, self.B, self.M, _vp(self.stream or None), _capi._lib
+        n_win = int(numaxs.size)
+        if n_win == 0:
+            raise ValueError("attempt to get argmax of an empty sequence")
+        if starts.min() < 0 or int(starts.max()) + W > M:
+            raise ValueError("a window reaches outside the spectrum")
+        ws = np.ascontiguousarray(starts, dtype=np.int32)
+        d_met, d_smooth = DeviceBuffer(h, max(B * n_win, 1) * 8), DeviceBuffer(h, max(B * n_win, 1) * 8)
+        d_arg = DeviceBuffer(h, max(B, 1) * 8)
+        taps = np.ascontiguousarray(_seis._gaussian_taps(np.sqrt(n_win))) if n_win > 10 else None
+        _capi._check(lib.lk_pg_acf_metric_batch_dev(h._h, B, M, _vp(self.power.ptr), n_win, ws.ctypes.data_as(_i32p), W,
+                                                    _vp(d_met.ptr), st))
+        _capi._check(lib.lk_pg_numax_pick_batch_dev(h._h, B, n_win, _vp(d_met.ptr), None if taps is None else taps.ctypes.data_as(_dp),
+                                                    0 if taps is None else int(taps.size), _vp(d_smooth.ptr), _vp(d_arg.ptr), st))
+        arg = d_arg.download(np.int64, B, stream=self.stream)
+        self.numax = numaxs[arg]
+        out = dict(numax=self.numax, numaxs=numaxs, window_width=window_width)
+        if return_metric:
+            out["metric"] = d_met.download(np.float64, B * n_win, stream=self.stream).reshape(B, n_win)
+            out["metric_smooth"] = d_smooth.download(np.float64, B * n_win, stream=self.stream).reshape(B, n_win)
+        return out
+
+    def estimate_deltanu(self, numax=None, return_acf=False):
+        """``estimate_deltanu_acf2d`` (reference seismology/deltanu_estimators.py:18-153) per target, each around its own
+        ``numax``: a scalar, one value per target, or None for the last ``estimate_numax`` result.  The windows are planned
+        on the host from those B numbers (``seismology._deltanu_plan``), ``lk_pg_deltanu_batch_dev`` does the rest.  Returns a
+        dict of arrays [B]: ``deltanu`` (NaN unless ``status`` is 0), ``deltanu_emp``, ``n_peaks``, ``status`` (0 ok, 1 skipped:
+        numax NaN or <= 0, 2 no usable window, 3 no peak in the selection; no target raises) and ``numax``; with
+        ``return_acf`` also ``acf`` float64[B, max_sel] (the rescaled ACF on the selected lags, NaN behind them), ``sel_lo``
+        and ``sel_len``."""
+        if numax is None:
+            if self.numax is None:
+                raise ValueError("pass numax or call estimate_numax first")
+            numax = self.numax
+        if not self._is_evenly_spaced():
+            raise ValueError("the ACF 2D method requires that the periodogram has a grid of uniformly spaced frequencies.")
+        h, B, M, st = self.handle, self.B, self.M, _vp(self.stream or None)
+        numax = np.ascontiguousarray(np.broadcast_to(np.asarray(numax, dtype=np.float64), (B,)))
+        plan = _seis._deltanu_plan(self.frequency, self.frequency_unit, numax)
+        tabs, max_sel = _capi._deltanu_tables(plan, B)
+        d_dnu = DeviceBuffer(h, max(B, 1) * 8)
+        d_int = DeviceBuffer(h, max(B, 1) * 16)                     # n_peaks | status | sel_lo | sel_len, int32[B] each
+        d_acf = DeviceBuffer(h, max(B * max_sel, 1) * 8) if return_acf else None
+        _capi._check(_capi._lib.lk_pg_deltanu_batch_dev(
+            h._h, B, M, _vp(self.power.ptr), tabs[0].ctypes.data_as(_i32p), tabs[1].ctypes.data_as(_i32p), tabs[2].ctypes.data_as(_dp),
+            tabs[3].ctypes.data_as(_dp), tabs[4].ctypes.data_as(_dp), tabs[5].ctypes.data_as(_dp), max_sel, _vp(d_dnu.ptr),
+            _vp(d_int.ptr), _vp(d_int.ptr + 4 * B), _vp(d_int.ptr + 8 * B), _vp(d_int.ptr + 12 * B),
+            _vp(d_acf.ptr if d_acf is not None else None), st))
+        ints = d_int.download(np.int32, 4 * B, stream=self.stream).reshape(4, B)
+        out = dict(deltanu=d_dnu.download(np.float64, B, stream=self.stream), deltanu_emp=plan["deltanu_emp"], n_peaks=ints[0],
+                   status=ints[1], numax=numax)
+        if return_acf:
+            out.update(acf=d_acf.download(np.float64, B * max_sel, stream=self.stream).reshape(B, max_sel), sel_lo=ints[2],
+                       sel_len=ints[3])
+        return out
+
+    def estimate_seismology(self, method="logmedian", filter_width=0.01, numaxs=None, window_width=None, spacing=None):
+        """The reference's chain ``pg.flatten().to_seismology()``, ``estimate_numax()``, ``estimate_deltanu()`` for the batch:
+        dict of ``numax``, ``deltanu``, ``deltanu_emp``, ``n_peaks`` and ``status`` (of the deltanu step) per target."""
+        snr = self.flatten(method=method, filter_width=filter_width)
+        numax = snr.estimate_numax(numaxs=numaxs, window_width=window_width, spacing=spacing)["numax"]
+        self.numax = numax
+        res = snr.estimate_deltanu(numax)
+        return dict(numax=numax, deltanu=res["deltanu"], deltanu_emp=res["deltanu_emp"], n_peaks=res["n_peaks"], status=res["status"])
+
+
 class DevicePixelCubeBatch(object):
     """B same-shaped target-pixel cutouts IN HBM — the input of ``PLDCorrector`` as ``DeviceLightCurveBatch`` is the input of
     the light-curve chain: ``d_flux`` / ``d_flux_err`` float32 [B][N][npix] (npix = ny * nx, row-major pixels: the layout

@@ -12,7 +12,8 @@ import numpy as np
 from . import _capi
 from .periodogram import UHZ_PER_CPD, _freq_unit_factor
 
-__all__ = ["autocorrelate", "estimate_numax_acf2d", "estimate_numax_acf2d_batch", "estimate_deltanu_acf2d", "get_fwhm"]
+__all__ = ["autocorrelate", "estimate_numax_acf2d", "estimate_numax_acf2d_batch", "estimate_deltanu_acf2d",
+           "estimate_deltanu_acf2d_batch", "get_fwhm"]
 
 
 def _to_uhz(value, unit):
@@ -41,16 +42,23 @@ def autocorrelate(periodogram, numax, window_width=25.0, frequency_spacing=None,
     return acf[0, 0]
 
 
-def _gaussian_smooth_extend(metric, stddev):
-    """astropy.convolution.convolve(metric, Gaussian1DKernel(stddev), boundary='extend') (numax_estimators.py:181-183):
-    kernel of _round_up_to_odd_integer(8 stddev) taps sampled at the integers, normalised by its sum, edges replicated."""
+def _gaussian_taps(stddev):
+    """astropy ``Gaussian1DKernel(stddev)`` as convolve() applies it: _round_up_to_odd_integer(8 stddev) taps sampled at the
+    integers, normalised by their sum."""
     size = int(np.ceil(8 * stddev))
     if size % 2 == 0:
         size += 1
     half = size // 2
     xk = np.arange(-half, half + 1, dtype=np.float64)
     g = np.exp(-0.5 * (xk / stddev) ** 2) / (np.sqrt(2 * np.pi) * stddev)
-    g = g / g.sum()
+    return g / g.sum()
+
+
+def _gaussian_smooth_extend(metric, stddev):
+    """astropy.convolution.convolve(metric, Gaussian1DKernel(stddev), boundary='extend') (numax_estimators.py:181-183):
+    the taps of ``_gaussian_taps``, edges replicated."""
+    g = _gaussian_taps(stddev)
+    half = len(g) // 2
     padded = np.concatenate([np.full(half, metric[0]), metric, np.full(half, metric[-1])])
     return np.correlate(padded, g, mode="valid")
 
@@ -201,3 +209,93 @@ def estimate_deltanu_acf2d(periodogram, numax, device=0):
     peaks = _find_peaks(acf[sel], distance=np.floor(deltanu_emp / 2.0 / fs))
     best = lags[sel][peaks][np.argmin(np.abs(lags[sel][peaks] - deltanu_emp))]
     return dict(deltanu=float(best), lags=lags, acf=acf, peaks=peaks, sel=sel, numax=numax, deltanu_emp=deltanu_emp)
+
+
+# ------------------------------------------------------------------------------------------------ deltanu, batched
+DELTANU_MAX_WINDOW = 16384      # samples per window of lk_pg_deltanu_batch (include/lkhip.h)
+
+
+def _deltanu_plan(frequency, frequency_unit, numaxs):
+    """What ``estimate_deltanu_acf2d`` derives from ``numax`` before it touches the spectrum, for every target of a batch on one
+    grid — with the reference's own scalar arithmetic, one target at a time (python ``int()`` truncation, python ``**``), so a
+    target gets the window it gets from the single call.  Returns a dict of arrays [B]: ``start`` / ``width`` (int32: the window,
+    ``_window_start`` of ``2 * int(floor(fwhm))``), ``deltanu_emp`` (NaN marks a target to skip: numax not finite or <= 0),
+    ``distance`` (``floor(deltanu_emp / 2 / fs)``), ``step`` / ``stop`` (``np.linspace(0, width fs, width)`` = i * step, the last
+    lag = stop) and ``sel_lo`` / ``sel_len`` (int32): the run of lags with ``lag > emp - 0.25 emp`` and ``lag < emp + 0.25 emp``,
+    found from the two bounds by the predicate itself on the lags next to them, not from a mask of all ``width`` lags."""
+    freq = np.asarray(frequency, dtype=np.float64)
+    fs = np.median(np.diff(freq))
+    high = _to_uhz(freq[-1], frequency_unit) > 500.0
+    B = len(numaxs)
+    plan = dict(start=np.full(B, -1, dtype=np.int32), width=np.zeros(B, dtype=np.int32), deltanu_emp=np.full(B, np.nan),
+                distance=np.zeros(B), step=np.zeros(B), stop=np.zeros(B), sel_lo=np.zeros(B, dtype=np.int32),
+                sel_len=np.zeros(B, dtype=np.int32), fs=fs)
+    for b in range(B):
+        numax = float(numaxs[b])
+        if not (numax > 0 and numax < np.inf):
+            continue
+        emp = _from_uhz(0.294 * _to_uhz(numax, frequency_unit) ** 0.772, frequency_unit)
+        fwhm = 0.25 * numax if high else 0.66 * numax ** 0.88
+        start, W = _window_start(freq, numax, 2 * int(np.floor(fwhm)), fs)
+        plan["deltanu_emp"][b] = emp
+        plan["distance"][b] = np.floor(emp / 2.0 / fs)
+        if W < 2 or W > DELTANU_MAX_WINDOW or abs(start) >= 2 ** 31:
+            continue                                   # start = -1, width = 0: no such window (status 2)
+        stop = W * fs
+        step = stop / (W - 1)                          # np.linspace: step = (stop - start) / (num - 1)
+        lo_t, hi_t = emp - 0.25 * emp, emp + 0.25 * emp
+
+        def lag(i):
+            return stop if i == W - 1 else i * step
+
+        lo = min(max(int(lo_t / step), 0), W)
+        while lo > 0 and lag(lo - 1) > lo_t:
+            lo -= 1
+        while lo < W and not lag(lo) > lo_t:
+            lo += 1
+        hi = min(max(int(hi_t / step), lo), W)
+        while hi > lo and not lag(hi - 1) < hi_t:
+            hi -= 1
+        while hi < W and lag(hi) < hi_t:
+            hi += 1
+        plan["start"][b], plan["width"][b], plan["step"][b], plan["stop"][b] = start, W, step, stop
+        plan["sel_lo"][b], plan["sel_len"][b] = (lo, hi - lo) if hi > lo else (0, 0)
+    return plan
+
+
+def estimate_deltanu_acf2d_batch(periodograms, numaxs, device=0):
+    """``estimate_deltanu_acf2d`` for a list of periodograms on one shared frequency grid, each with its own ``numax`` (a scalar
+    serves all): every target's window in ONE launch (``lk_pg_deltanu_batch``), which forms lag 0 and the lags within 25 % of
+    the empirical deltanu and nothing else.  Returns one dict per target: ``deltanu`` (NaN unless ``status`` is 0), ``status``
+    (0 ok, 1 skipped: numax NaN or <= 0, 2 no usable window, 3 no peak in the selection — a batch raises for no single target),
+    ``n_peaks``, ``numax``, ``deltanu_emp`` and the reference's diagnostics ``lags``, ``sel``, ``peaks`` and ``acf``; ``acf``
+    holds the rescaled ACF on ``sel`` and NaN elsewhere (the other lags are never computed)."""
+    if not periodograms:
+        return []
+    pg0 = periodograms[0]
+    f0 = np.asarray(pg0.frequency)
+    for pg in periodograms[1:]:
+        if not np.array_equal(np.asarray(pg.frequency), f0) or pg.frequency_unit != pg0.frequency_unit:
+            raise ValueError("estimate_deltanu_acf2d_batch needs periodograms on one shared frequency grid")
+    if not pg0._is_evenly_spaced():
+        raise ValueError("the ACF 2D method requires that the periodogram has a grid of uniformly spaced frequencies.")
+    B = len(periodograms)
+    numaxs = np.ascontiguousarray(np.broadcast_to(np.asarray(numaxs, dtype=np.float64), (B,)))
+    plan = _deltanu_plan(f0, pg0.frequency_unit, numaxs)
+    power = np.stack([np.asarray(pg.power, dtype=np.float64) for pg in periodograms])
+    res = _capi.pg_deltanu_batch(power, plan, want_acf=True, device=device)
+    out = []
+    for b in range(B):
+        W, lo, n = int(plan["width"][b]), int(res["sel_lo"][b]), int(res["sel_len"][b])
+        ok = res["status"][b] == 0
+        lags = np.linspace(0.0, W * plan["fs"], W) if W >= 2 else np.zeros(0)
+        sel = np.zeros(len(lags), dtype=bool)
+        acf = np.full(len(lags), np.nan)
+        if len(lags):
+            sel[lo:lo + n] = True
+            acf[lo:lo + n] = res["acf"][b, :n]
+        peaks = _find_peaks(acf[sel], distance=plan["distance"][b]) if ok else np.zeros(0, dtype=np.intp)
+        out.append(dict(deltanu=float(res["deltanu"][b]), status=int(res["status"][b]), n_peaks=int(res["n_peaks"][b]),
+                        lags=lags, acf=acf, peaks=peaks, sel=sel, numax=float(numaxs[b]),
+                        deltanu_emp=float(plan["deltanu_emp"][b])))
+    return out

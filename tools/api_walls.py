@@ -57,7 +57,13 @@ cadences on the benchmark's grid of `LK_WALLS_M` (default 100000) frequencies, i
 `LK_WALLS_REPS` (default 3) times after one warm-up.  W the resident loop; W_H the same loop through the host: the peaks from
 the resident periodogram, then `to_host()`, `ls_model_host` per target, `from_arrays` per round.  L one round's periodogram
 pass alone (`to_periodogram_power(to_host=False, want_peaks=True)`), F one round's fit alone
-(`ls_model(want_model=False, want_residual=True)`).  Results: profiles/prewhiten_walls.txt."""
+(`ls_model(want_model=False, want_residual=True)`).  Results: profiles/prewhiten_walls.txt.
+
+`seismology`: numax and deltanu of `LK_WALLS_B` (default 1000) targets x `LK_WALLS_N` (default 20000) two-minute cadences on
+the natural grid (oversample_factor 1, up to the Nyquist frequency), in ONE process, the routes alternating, `LK_WALLS_REPS`
+(default 3) times after one warm-up.  S the resident chain `batch.to_periodogram(f, "psd").estimate_seismology()`; S_H the
+spectra brought to the host, then per target `Periodogram.flatten`, `estimate_numax_acf2d`, `estimate_deltanu_acf2d`; L the
+periodogram pass alone.  Results: profiles/seismology_walls.txt."""
 import cProfile
 import io
 import os
@@ -554,6 +560,68 @@ def prewhiten():
     sys.stdout.flush()
 
 
+def seismology():
+    from lightkurve_amd import _capi
+    from lightkurve_amd import seismology as seis
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    from lightkurve_amd.periodogram import Periodogram
+    B, N = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "3"))
+    rng = np.random.default_rng(11)
+    t = np.arange(N) * (2.0 / 1440.0)
+    fs = 1e6 / 86400.0 / (t[-1] - t[0])                      # microhertz: oversample_factor = 1
+    M = int(1e6 / 240.0 / fs)                                # up to the Nyquist frequency of two-minute cadences
+    freq = fs * np.arange(1, M + 1)
+    flux = np.empty((B, N))
+    for b in range(B):
+        numax = rng.uniform(800.0, 3000.0)
+        dnu = 0.294 * numax ** 0.772
+        y = 1.0 + 2e-4 * rng.standard_normal(N)
+        for n in range(-4, 5):
+            y += 1e-4 * np.exp(-0.5 * (n / 2.5) ** 2) * np.sin(2 * np.pi * (numax + n * dnu) * 0.0864 * t + rng.uniform(0, 6.28))
+        flux[b] = y
+    n_off = np.arange(B + 1, dtype=np.int64) * N
+    raw = DeviceLightCurveBatch.from_arrays(np.tile(t, B), flux.ravel(), None, n_off).remove_nans()
+    sync = _capi.Handle.get(0).synchronize
+
+    def resident():
+        return raw.to_periodogram(freq, normalization="psd").estimate_seismology()
+
+    def through_host():
+        power = raw.to_periodogram_power(freq, normalization="psd", to_host=True)
+        numax, deltanu = np.empty(B), np.full(B, np.nan)
+        for b in range(B):
+            snr = Periodogram(freq, power[b], frequency_unit="uHz").flatten()
+            numax[b] = seis.estimate_numax_acf2d(snr)["numax"]
+            try:
+                deltanu[b] = seis.estimate_deltanu_acf2d(snr, numax[b])["deltanu"]
+            except ValueError:                              # no peak in the selection: the resident route's status 3
+                pass
+        return dict(numax=numax, deltanu=deltanu)
+
+    def ls_pass():
+        return raw.to_periodogram_power(freq, normalization="psd", to_host=False)
+
+    fns = {"S": resident, "S_H": through_host, "L": ls_pass}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    sync()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(lambda: (fn(), sync()))[0])
+    r, hst = first["S"], first["S_H"]
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    print("seismology chain, %d targets x %d two-minute cadences, %d frequencies of %.3f uHz (oversample_factor 1)" % (B, N, M, fs))
+    print("  S    batch.to_periodogram(f, 'psd').estimate_seismology(), resident                         %s" % spread(ts["S"]))
+    print("  S_H  to_periodogram_power(to_host=True), then per target flatten / numax / deltanu          %s" % spread(ts["S_H"]))
+    print("  L    the periodogram pass alone: to_periodogram_power(to_host=False)                        %s" % spread(ts["L"]))
+    print("  same numax: %s; same deltanu: %s; status counts 0..3: %s"
+          % (np.array_equal(r["numax"], hst["numax"]), np.array_equal(r["deltanu"], hst["deltanu"], equal_nan=True),
+             np.bincount(r["status"], minlength=4).tolist()))
+    print("  S_H / S = %.1f; (S - L) = %.2f ms for flatten, numax and deltanu" % (med["S_H"] / med["S"], 1e3 * (med["S"] - med["L"])))
+    sys.stdout.flush()
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -577,6 +645,8 @@ def main():
         cdpp()
     if "prewhiten" in which:
         prewhiten()
+    if "seismology" in which:
+        seismology()
     if "flatten" in which:
         lcs = []
         for i in range(1000):
