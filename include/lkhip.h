@@ -38,6 +38,9 @@
  *   lk_pg_logmedian_batch* / lk_pg_boxsmooth_batch* <- Periodogram.smooth, periodogram.py:182-284.
  *   lk_pg_snr_batch_dev / lk_pg_acf_metric_batch_dev / lk_pg_numax_pick_batch_dev / lk_pg_deltanu_batch* <- flatten,
  *                           estimate_numax and estimate_deltanu (seismology/) on spectra that stay in device memory.
+ *   lk_sff_correct_batch* / lk_sff_arclength_batch* / lk_cube_centroids_batch_dev <- SFFCorrector.correct (correctors/
+ *                           sffcorrector.py, lightkurve 2.x) and TargetPixelFile.estimate_centroids(method='moments') for a resident
+ *                           batch: arclength, percentile knots, the block-structured design matrix, the fit, the components.
  *
  * Conventions
  *   - Every function returns an int status: LK_OK, LK_EINVAL (-> ValueError), LK_ENOMEM (-> MemoryError),
@@ -822,6 +825,77 @@ int lk_pld_gather_ragged_batch_dev(lk_handle *h, int B, int N, int npix, int n, 
                                    const int32_t *knot_lo_host, const double *knot_g_host, double *t_out, double *y_out,
                                    double *err_out, float *lcf_out, float *pld_out, float *bkg_out, double *knots_out,
                                    int *nonfinite_host, void *stream);
+
+/* lk_cube_centroids_batch_dev <- TargetPixelFile.estimate_centroids(aperture_mask, method='moments') for the same resident
+ *   cubes: col[b][i] = sum_p (column0 + x_p) m_p flux_p / sum_p m_p flux_p and row likewise with (row0 + y_p), pixel p at
+ *   x_p = p % nx, y_p = p / nx; sums in float64, NaN pixels count as 0 (nansum), a zero or NaN total gives NaN.  mask /
+ *   mask_stride as lk_cube_aperture_batch_dev.  col_out / row_out: B x N float64.  One wavefront per cadence; the order of
+ *   its sums depends on npix alone.  Enqueued, no synchronisation. */
+int lk_cube_centroids_batch_dev(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask,
+                                int mask_stride, double column0, double row0, double *col_out, double *row_out, void *stream);
+
+/* ---- SFFCorrector.correct (self-flat-fielding, the K2 roll-motion correction; reference lightkurve 2.x
+ * src/lightkurve/correctors/sffcorrector.py) for B ragged light curves.  Per target, all float64, inputs finite:
+ *   f = flux / median(flux), e = flux_err / median(flux); raw_mean = mean(flux);
+ *   arclength (_estimate_arclength): c = col - min(col), r = row - min(row); c = max(c) - c if the least-squares slope of r on
+ *     c is negative (the sign of sum (c - mean c)(r - mean r)); arc = sqrt(c c + r r);
+ *   windows: window_points are ascending cut indices in (0, N); window j = [lo_j, up_j), lo = [0, wp...], up = [wp..., N],
+ *     W = number of points + 1;
+ *   design matrix, K = n_knots + W (bins + degree) columns [ spline | window 1 | ... | window W ]:
+ *     spline   = create_spline_matrix(time, n_knots), n_knots = int((time[-1] - time[0]) / timescale): the clamped cubic
+ *                B-spline basis with n_knots - 4 interior knots at equally spaced percentiles of time; prior_mu[k] = mean of
+ *                the k-th chunk of np.array_split(f, n_knots), prior_sigma = 1000 std(f) + 1e-6 (np.std);
+ *     window j = the clamped B-spline basis (degree `degree`, intercept kept) of x = arc inside the window and -1 outside, with
+ *                bins - 1 interior knots np.percentile(arc[lo_j:up_j], linspace(0, 100, bins + 1)[1:-1]) and boundary knots
+ *                min(x), max(x): a cadence outside the window has [1, 0, ..., 0] there (the 1 as the basis itself evaluates at
+ *                its lower boundary knot: 1 up to the rounding of the recursion); prior_mu = 0, prior_sigma = 10000
+ *                std(f) + 1e-6.  "Outside" is decided BY INDEX; the reference decides it by value (~np.in1d(ar, ar[a:b])): the
+ *                two differ only when an arclength outside the window is bit-equal to one inside it;
+ *   fit = lk_regress_batch_dev on that matrix (clip_sigma, niters; cadence_mask nullable, 1 = used);
+ *   corrected = f - model; spline / sff = the two column groups' shares of the model, each minus its median;
+ *   restore_trend: corrected += spline - nanmedian(spline); finally corrected and e are multiplied by raw_mean.
+ * status (HOST int32[B], valid on return: the _dev call synchronises `stream` once, to learn every target's n_knots):
+ *   0 corrected; 1 too short (n_knots < 4); 2 a non-finite time, flux, flux_err or centroid; 3 K > 4095.  A target whose status
+ *   is not 0 gets NaN flux / flux_err / spline / sff / w and outlier 0; no error is raised for it.
+ * Outputs: flux_out, err_out (sum N), outlier (sum N bytes); nullable arclength, spline, sff (sum N) and w (B x w_pitch, row b
+ *   = its K coefficients, NaN behind them; w_pitch >= the widest K).
+ * win_off (B + 1) / window_points (int32, ragged): HOST arrays, target b owns [win_off[b], win_off[b+1]).
+ * GROUPS AND SCRATCH.  K must be uniform per regression, so targets are grouped by (n_knots, W) and each group runs in chunks
+ *   of targets; nothing is padded.  The regression launcher owns the handle's arena, so the design matrices (N K 8 bytes per
+ *   target: ~6 GB for 1000 x 3500 x 213) and the other per-chunk arrays live in `scratch`, a 256-byte aligned device block of
+ *   the caller's.  lk_sff_scratch_bytes(n_knots per target, as above) returns the block size whose chunks are the largest that
+ *   fit max_scratch_bytes (0: LK_SFF_SCRATCH_DEFAULT) and their number; a budget below one target's own need is LK_EINVAL.
+ *   A target's result has the same bits in any batch, at any position and for any chunk size; two runs give the same bits
+ *   (every sum's order depends on the target's own sizes; no atomics).
+ * lk_sff_correct_batch: host pointers; stages everything and its scratch (max_scratch_bytes) in the handle's staging arena.
+ * lk_sff_arclength_batch(_dev): the arclength alone (the host needs it to choose windows); flipped (nullable) int32[B].
+ * lk_sff_design_batch_dev: stops after the design matrix, for B targets of ONE group (n_knots given, the same W): X (sum N x
+ *   K), prior_mu / prior_sigma (B x K), knots_time (B x (n_knots - 2): [min, interior..., max]), knots_win (B x W x (bins + 1)),
+ *   f_out / e_out (sum N: the normalised flux and errors).  Its spline blocks are what lk_spline_basis_batch_dev gives for the
+ *   same x and knots, bit for bit (one shared device function).  Enqueued, no synchronisation. */
+#define LK_SFF_SCRATCH_DEFAULT ((int64_t)4 << 30)
+int lk_sff_scratch_bytes(int B, const int64_t *n_off, const int32_t *n_knots, const int32_t *win_off, int bins, int degree,
+                         int64_t max_scratch_bytes, int64_t *bytes, int *n_chunks);
+int lk_sff_arclength_batch(lk_handle *h, int B, const int64_t *n_off, const double *centroid_col, const double *centroid_row,
+                           double *arclength, int32_t *flipped);
+int lk_sff_arclength_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *centroid_col,
+                               const double *centroid_row, double *arclength, int32_t *flipped, void *stream);
+int lk_sff_design_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux,
+                            const double *flux_err, const double *arclength, const int32_t *win_off, const int32_t *window_points,
+                            int bins, int degree, int n_knots, double *X, double *prior_mu, double *prior_sigma,
+                            double *knots_time, double *knots_win, double *f_out, double *e_out, void *stream);
+int lk_sff_correct_batch(lk_handle *h, int B, const int64_t *n_off, const double *time, const double *flux, const double *flux_err,
+                         const double *centroid_col, const double *centroid_row, const uint8_t *cadence_mask,
+                         const int32_t *win_off, const int32_t *window_points, int bins, int degree, double timescale,
+                         int restore_trend, double clip_sigma, int niters, int64_t max_scratch_bytes, double *flux_out,
+                         double *err_out, uint8_t *outlier, int32_t *status, double *arclength, double *spline, double *sff,
+                         double *w, int w_pitch);
+int lk_sff_correct_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux,
+                             const double *flux_err, const double *centroid_col, const double *centroid_row,
+                             const uint8_t *cadence_mask, const int32_t *win_off, const int32_t *window_points, int bins,
+                             int degree, double timescale, int restore_trend, double clip_sigma, int niters, void *scratch,
+                             int64_t scratch_bytes, double *flux_out, double *err_out, uint8_t *outlier, int32_t *status_host,
+                             double *arclength, double *spline, double *sff, double *w, int w_pitch, void *stream);
 
 /* ---- Standalone design-matrix operations (correctors/designmatrix.py) for B same-shaped matrices ----------------
  * lk_pca_batch          <- DesignMatrix.pca(nterms), designmatrix.py:252-282 (fbpca.pca(values, nterms) -> U): the first

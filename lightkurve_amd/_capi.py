@@ -276,6 +276,25 @@ SIGNATURES = [
      [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     ("lk_standardize_batch", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
     ("lk_standardize_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    ("lk_cube_centroids_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+      _vp, _vp, _vp]),
+    ("lk_sff_scratch_bytes", ctypes.c_int,
+     [ctypes.c_int, _c_ip, _c_i32p, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+      ctypes.POINTER(ctypes.c_int)]),
+    ("lk_sff_arclength_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_i32p]),
+    ("lk_sff_arclength_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_sff_design_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _vp, _c_i32p, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
+      _vp, _vp, _vp, _vp, _vp]),
+    ("lk_sff_correct_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_u8p, _c_i32p, _c_i32p, ctypes.c_int, ctypes.c_int,
+      ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp, _c_u8p, _c_i32p, _c_dp, _c_dp,
+      _c_dp, _c_dp, ctypes.c_int]),
+    ("lk_sff_correct_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _vp, _vp, _vp, _c_i32p, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+      ctypes.c_int, ctypes.c_double, ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp, _vp, _c_i32p, _vp, _vp, _vp, _vp, ctypes.c_int,
+      _vp]),
 ]
 
 _lib = None
@@ -1560,3 +1579,96 @@ def bin_batch(t, flux, n_off, flux_err=None, time_bin_size=0.5, time_bin_start=N
     _check(_lib.lk_bin_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(t), _ptr(flux), _ptr(err), _ptr(bin_off, _c_ip), _ptr(start),
                              _ptr(edges), int(edges.size), size_sec, _ptr(has_err, _c_u8p), _ptr(to), _ptr(fo), _ptr(eo)))
     return to, fo, eo, bin_off
+
+
+# --------------------------------------------------------------------------------------------- SFF
+SFF_SCRATCH_DEFAULT = 4 << 30       # LK_SFF_SCRATCH_DEFAULT in include/lkhip.h
+SFF_STATUS = {0: "ok", 1: "too short", 2: "non-finite input", 3: "too wide"}      # lk_sff_correct_batch's per-target status
+
+
+def sff_n_knots(t_first, t_last, timescale):
+    """Columns of the long-term spline per target, the reference's ``int((time[-1] - time[0]) / timescale)`` (0 where that is
+    not a number a spline can have: the library reports such a target by its status)."""
+    span = (np.asarray(t_last, dtype=np.float64) - np.asarray(t_first, dtype=np.float64)) / float(timescale)
+    ok = np.isfinite(span) & (span >= 0) & (span < 1e6)
+    return np.where(ok, np.trunc(np.where(ok, span, 0.0)), 0).astype(np.int32)
+
+
+def sff_window_arrays(window_points, n_off):
+    """One list of cut indices per target -> (win_off int32[B + 1], window_points int32) as lk_sff_correct_batch takes them;
+    ascending indices inside (0, N) are required."""
+    n_off = np.asarray(n_off, dtype=np.int64)
+    B = n_off.size - 1
+    if len(window_points) != B:
+        raise ValueError("window_points needs one list of cut indices per target (got %d for %d targets)" % (len(window_points), B))
+    wps = [np.asarray(w, dtype=np.int64).reshape(-1) for w in window_points]
+    for b, w in enumerate(wps):
+        N = int(n_off[b + 1] - n_off[b])
+        if w.size and (w[0] <= 0 or w[-1] >= N or np.any(np.diff(w) <= 0)):
+            raise ValueError("target %d: window_points must be ascending cut indices inside (0, %d)" % (b, N))
+    win_off = np.zeros(B + 1, dtype=np.int32)
+    win_off[1:] = np.cumsum([w.size for w in wps])
+    wp = np.ascontiguousarray(np.concatenate(wps) if wps else np.zeros(0), dtype=np.int32)
+    return win_off, wp
+
+
+def sff_scratch_bytes(n_off, n_knots, win_off, bins=5, degree=3, max_scratch_bytes=None):
+    """(bytes, chunks) of the device block ``lk_sff_correct_batch_dev`` needs: the design matrices of the largest chunk of
+    targets that fits ``max_scratch_bytes`` (None: 4 GiB) plus the batch's arclength.  Host arithmetic only."""
+    load_library()
+    n_off = np.ascontiguousarray(n_off, dtype=np.int64)
+    n_knots = np.ascontiguousarray(n_knots, dtype=np.int32)
+    win_off = np.ascontiguousarray(win_off, dtype=np.int32)
+    B = n_off.size - 1
+    if n_knots.shape != (B,) or win_off.shape != (B + 1,):
+        raise ValueError("n_knots needs B entries and win_off B + 1")
+    nbytes, chunks = ctypes.c_int64(0), ctypes.c_int(0)
+    _check(_lib.lk_sff_scratch_bytes(B, _ptr(n_off, _c_ip), _ptr(n_knots, _c_i32p), _ptr(win_off, _c_i32p), int(bins), int(degree),
+                                     int(max_scratch_bytes or 0), ctypes.byref(nbytes), ctypes.byref(chunks)))
+    return int(nbytes.value), int(chunks.value)
+
+
+def sff_arclength_batch(centroid_col, centroid_row, n_off, device=0):
+    """``SFFCorrector._estimate_arclength`` for B ragged targets -> (arclength[sum N], flipped bool[B])."""
+    h = Handle.get(device)
+    col, row = _f64(centroid_col), _f64(centroid_row)
+    n_off = _offsets(n_off, col.size)
+    if col.ndim != 1 or row.shape != col.shape:
+        raise ValueError("centroid_col and centroid_row must be 1-D arrays of one length")
+    B = n_off.size - 1
+    arc = np.empty(col.size, dtype=np.float64)
+    flipped = np.zeros(max(B, 1), dtype=np.int32)
+    _check(_lib.lk_sff_arclength_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(col), _ptr(row), _ptr(arc), _ptr(flipped, _c_i32p)))
+    return arc, flipped[:B].astype(bool)
+
+
+def sff_correct_batch(time, flux, flux_err, centroid_col, centroid_row, n_off, window_points, bins=5, degree=3, timescale=1.5,
+                      restore_trend=False, cadence_mask=None, sigma=5.0, niters=5, max_scratch_bytes=None, device=0):
+    """``SFFCorrector.correct`` numerics for B ragged targets (include/lkhip.h: lk_sff_correct_batch).  ``window_points``: one
+    list of cut indices per target.  Returns dict(flux, flux_err, outlier_mask, status int32[B], arclength, spline, sff — all
+    packed like the inputs — and coefficients: a list of B arrays, K_b each)."""
+    h = Handle.get(device)
+    time = _f64(time)
+    n_off = _offsets(n_off, time.size)
+    cols = [_f64(a) for a in (flux, flux_err, centroid_col, centroid_row)]
+    if time.ndim != 1 or any(a.shape != time.shape for a in cols):
+        raise ValueError("time, flux, flux_err and the centroids must be 1-D arrays of one length")
+    B, ntot = n_off.size - 1, time.size
+    win_off, wp = sff_window_arrays(window_points, n_off)
+    cm = None if cadence_mask is None else np.ascontiguousarray(cadence_mask, dtype=np.uint8)
+    if cm is not None and cm.shape != (ntot,):
+        raise ValueError("cadence_mask must have one entry per cadence")
+    nk = sff_n_knots(time[n_off[:-1]], time[n_off[1:] - 1], timescale)
+    widths = nk + (np.diff(win_off) + 1) * (int(bins) + int(degree))
+    pitch = int(max(widths.max(), 1))
+    out_f, out_e, arc, spl, sff = (np.empty(ntot, dtype=np.float64) for _ in range(5))
+    outl = np.empty(ntot, dtype=np.uint8)
+    status = np.zeros(B, dtype=np.int32)
+    w = np.empty((B, pitch), dtype=np.float64)
+    _check(_lib.lk_sff_correct_batch(
+        h._h, B, _ptr(n_off, _c_ip), _ptr(time), _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), _ptr(cm, _c_u8p),
+        _ptr(win_off, _c_i32p), _ptr(wp, _c_i32p), int(bins), int(degree), float(timescale), int(bool(restore_trend)), float(sigma),
+        int(niters), int(max_scratch_bytes or 0), _ptr(out_f), _ptr(out_e), _ptr(outl, _c_u8p), _ptr(status, _c_i32p), _ptr(arc),
+        _ptr(spl), _ptr(sff), _ptr(w), pitch))
+    return dict(flux=out_f, flux_err=out_e, outlier_mask=outl.astype(bool), status=status, arclength=arc, spline=spl, sff=sff,
+                coefficients=[w[b, :widths[b]].copy() if status[b] == 0 else np.full(0, np.nan) for b in range(B)])

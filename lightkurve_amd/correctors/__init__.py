@@ -5,3 +5,4 @@ from .pldcorrector import PixelCube, PLDCorrector, pld_correct_batch  # noqa: F4
 from .regressioncorrector import RegressionCorrector  # noqa: F401
 from .metrics import overfit_metric_lombscargle  # noqa: F401
 from .cbvcorrector import CBVCorrector  # noqa: F401
+from .sffcorrector import SFFCorrector, sff_correct_batch, sff_thruster_firings, sff_window_points  # noqa: F401

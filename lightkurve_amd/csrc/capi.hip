@@ -1697,4 +1697,108 @@ int lk_bin_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, con
     return rc ? rc : io.finish();
 }
 
+// ------------------------------------------------------------------------------------------------ SFF
+int lk_cube_centroids_batch_dev(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask,
+                                int mask_stride, double column0, double row0, double *col_out, double *row_out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_centroids_launch(h, B, N, npix, nx, flux, mask, mask_stride, column0, row0, col_out, row_out,
+                                     static_cast<hipStream_t>(stream));
+}
+
+int lk_sff_scratch_bytes(int B, const int64_t *n_off, const int32_t *n_knots, const int32_t *win_off, int bins, int degree,
+                         int64_t max_scratch_bytes, int64_t *bytes, int *n_chunks) {
+    return lk::sff_scratch_bytes(B, n_off, n_knots, win_off, bins, degree, max_scratch_bytes, bytes, n_chunks);
+}
+
+int lk_sff_arclength_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *centroid_col,
+                               const double *centroid_row, double *arclength, int32_t *flipped, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::sff_arclength_launch(h, B, n_off_host, centroid_col, centroid_row, arclength, flipped,
+                                    static_cast<hipStream_t>(stream));
+}
+
+int lk_sff_arclength_batch(lk_handle *h, int B, const int64_t *n_off, const double *centroid_col, const double *centroid_row,
+                           double *arclength, int32_t *flipped) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr, "bad batch description");
+    if (B == 0 || n_off[B] == 0) return LK_OK;
+    LK_REQUIRE(centroid_col && centroid_row && arclength, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B];
+    const double *dc, *dr;
+    double *da;
+    int32_t *dfl;
+    lk::StagedCall io(h);
+    int rc = io.in(dc, centroid_col, ntot).in(dr, centroid_row, ntot).out(da, arclength, ntot).out(dfl, flipped, (size_t)B).stage();
+    if (rc) return rc;
+    rc = lk::sff_arclength_launch(h, B, n_off, dc, dr, da, dfl, nullptr);
+    return rc ? rc : io.finish();
+}
+
+int lk_sff_design_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux,
+                            const double *flux_err, const double *arclength, const int32_t *win_off, const int32_t *window_points,
+                            int bins, int degree, int n_knots, double *X, double *prior_mu, double *prior_sigma,
+                            double *knots_time, double *knots_win, double *f_out, double *e_out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::sff_design_launch(h, B, n_off_host, time, flux, flux_err, arclength, win_off, window_points, bins, degree, n_knots, X,
+                                 prior_mu, prior_sigma, knots_time, knots_win, f_out, e_out, static_cast<hipStream_t>(stream));
+}
+
+int lk_sff_correct_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux,
+                             const double *flux_err, const double *centroid_col, const double *centroid_row,
+                             const uint8_t *cadence_mask, const int32_t *win_off, const int32_t *window_points, int bins,
+                             int degree, double timescale, int restore_trend, double clip_sigma, int niters, void *scratch,
+                             int64_t scratch_bytes, double *flux_out, double *err_out, uint8_t *outlier, int32_t *status_host,
+                             double *arclength, double *spline, double *sff, double *w, int w_pitch, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::sff_correct_launch(h, B, n_off_host, time, flux, flux_err, centroid_col, centroid_row, cadence_mask, win_off,
+                                  window_points, bins, degree, timescale, restore_trend, clip_sigma, niters, scratch, scratch_bytes,
+                                  flux_out, err_out, outlier, status_host, arclength, spline, sff, w, w_pitch,
+                                  static_cast<hipStream_t>(stream));
+}
+
+int lk_sff_correct_batch(lk_handle *h, int B, const int64_t *n_off, const double *time, const double *flux, const double *flux_err,
+                         const double *centroid_col, const double *centroid_row, const uint8_t *cadence_mask,
+                         const int32_t *win_off, const int32_t *window_points, int bins, int degree, double timescale,
+                         int restore_trend, double clip_sigma, int niters, int64_t max_scratch_bytes, double *flux_out,
+                         double *err_out, uint8_t *outlier, int32_t *status, double *arclength, double *spline, double *sff,
+                         double *w, int w_pitch) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 1 && n_off != nullptr && win_off != nullptr, "bad batch description");
+    LK_REQUIRE(time && flux && flux_err && centroid_col && centroid_row && flux_out && err_out && outlier && status, "NULL buffer");
+    LK_REQUIRE(timescale > 0.0, "timescale must be positive");
+    LK_REQUIRE(!w || w_pitch >= 1, "w needs its row pitch");
+    // the block is sized for the widths the times imply (the launcher derives the same widths from the device's copy; a target
+    // it then finds non-finite is simply not fitted)
+    std::vector<int32_t> nk((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        LK_REQUIRE(n_off[b + 1] - n_off[b] >= 2, "target %d has fewer than 2 cadences", b);
+        const double span = (time[n_off[b + 1] - 1] - time[n_off[b]]) / timescale;
+        nk[b] = span >= 0.0 && span < 1e6 ? (int)span : 0;
+    }
+    int64_t bytes = 0;
+    int rc = lk::sff_scratch_bytes(B, n_off, nk.data(), win_off, bins, degree, max_scratch_bytes, &bytes, nullptr);
+    if (rc) return rc;
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B];
+    const double *dt, *df, *de, *dc, *dr;
+    const uint8_t *dcm;
+    double *dfo, *deo, *da, *dsp, *dsf, *dw;
+    uint8_t *dout;
+    char *dscr;
+    lk::StagedCall io(h);
+    rc = io.in(dt, time, ntot).in(df, flux, ntot).in(de, flux_err, ntot).in(dc, centroid_col, ntot).in(dr, centroid_row, ntot)
+             .in(dcm, cadence_mask, ntot).out(dfo, flux_out, ntot).out(deo, err_out, ntot).out(dout, outlier, ntot)
+             .out(da, arclength, ntot).out(dsp, spline, ntot).out(dsf, sff, ntot).out(dw, w, (size_t)B * (w ? w_pitch : 0))
+             .scratch(dscr, (size_t)bytes).stage();
+    if (rc) return rc;
+    rc = lk::sff_correct_launch(h, B, n_off, dt, df, de, dc, dr, dcm, win_off, window_points, bins, degree, timescale, restore_trend,
+                                clip_sigma, niters, dscr, bytes, dfo, deo, dout, status, da, dsp, dsf, dw, w_pitch, nullptr);
+    return rc ? rc : io.finish();
+}
+
 }  // extern "C"

@@ -307,6 +307,26 @@ int cube_threshold_mask_launch(lk_handle *h, int B, int ny, int nx, const double
                                hipStream_t stream);
 int pld_corrected_launch(lk_handle *h, int B, int N, const double *y, const double *model, const double *spline, double *out,
                          hipStream_t stream);
+// pixcube.hip: TargetPixelFile.estimate_centroids(method='moments') per cadence of every cutout
+int cube_centroids_launch(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask, int mask_stride,
+                          double column0, double row0, double *col_out, double *row_out, hipStream_t stream);
+// sff.hip: SFFCorrector for a ragged resident batch.  The regression launcher owns h->ws, so the design matrices and everything
+// else that lives across it sit in `scratch`, a device block of the caller's (sff_scratch_bytes); status_host is valid on
+// return (the call synchronises once, to group the targets by their design width)
+int sff_scratch_bytes(int B, const int64_t *n_off, const int32_t *n_knots, const int32_t *win_off, int bins, int degree,
+                      int64_t max_scratch_bytes, int64_t *bytes, int *n_chunks);
+int sff_arclength_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *col, const double *row, double *arc,
+                         int32_t *flipped, hipStream_t stream);
+int sff_design_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux, const double *err,
+                      const double *arc, const int32_t *win_off_host, const int32_t *wp_host, int bins, int degree, int n_knots,
+                      double *X, double *prior_mu, double *prior_sigma, double *knots_time, double *knots_win, double *f_out,
+                      double *e_out, hipStream_t stream);
+int sff_correct_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux, const double *err,
+                       const double *col, const double *row, const uint8_t *cmask, const int32_t *win_off_host,
+                       const int32_t *wp_host, int bins, int degree, double timescale, int restore_trend, double clip_sigma,
+                       int niters, void *scratch, int64_t scratch_bytes, double *flux_out, double *err_out, uint8_t *outl_out,
+                       int32_t *status_host, double *arclength, double *spline, double *sff, double *w, int w_pitch,
+                       hipStream_t stream);
 // rebase: t holds absolute times, the launcher works on t - t[first cadence] per target (carved in its own plan)
 int lsfast_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *y, const double *dy,
                   double f0, double df, int64_t M, int fit_mean, int center_data, int normalization,

@@ -3,6 +3,7 @@
 //   cube_aperture   simple aperture photometry (TargetPixelFile.to_lightcurve, flux_method='sum',
 //                   src/lightkurve/targetpixelfile.py:868-923) + the NaN-cadence flags of PLDCorrector.__init__
 //                   (correctors/pldcorrector.py:109-120);
+//   cube_centroids  the moment centroids of TargetPixelFile.estimate_centroids (what SFFCorrector's arclength is made from);
 //   cube_median     the per-pixel nanmedian image behind create_threshold_mask (targetpixelfile.py:680-742);
 //   cube_compact / cube_gather   the compaction tpf[~nan_mask], the pixel series of the PLD / background apertures
 //                   (pldcorrector.py:203-227) and the spline's percentile knots;
@@ -134,6 +135,44 @@ __global__ __launch_bounds__(256) void cube_aperture_kernel(const float *__restr
             if (kept) atomicAdd(&counts[b], (unsigned long long)__popcll(kept));
             if (dirty) atomicAdd(&counts[B + b], (unsigned long long)__popcll(dirty));
         }
+    }
+}
+
+// TargetPixelFile.estimate_centroids(aperture_mask, method='moments') (src/lightkurve/targetpixelfile.py): per cadence the flux-
+// weighted mean pixel position inside the aperture, col = sum_p (column0 + x_p) m_p flux_p / sum_p m_p flux_p and likewise
+// for row, summed in float64 with NaN pixels counting as 0 (nansum); a total that is zero or NaN gives NaN.  One wavefront
+// per cadence: lane l adds the pixels l, l + 64, ... in that order and the 64 lane sums are added in a butterfly, so the
+// order of every sum depends on npix alone.  Pixel p sits at x_p = p % nx, y_p = p / nx.
+__global__ __launch_bounds__(256) void cube_centroids_kernel(const float *__restrict__ flux, const uint8_t *__restrict__ mask,
+                                                             int mask_stride, int N, int npix, int nx, double column0,
+                                                             double row0, double *__restrict__ col_out,
+                                                             double *__restrict__ row_out) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= N) return;
+    const float *img = flux + ((size_t)b * N + i) * npix;
+    const uint8_t *m = mask + (size_t)b * mask_stride;
+    double tot = 0.0, sx = 0.0, sy = 0.0;
+    for (int p = lane; p < npix; p += 64) {
+        const float v = img[p];
+        if (m[p] && !isnan(v)) {
+            const int y = p / nx, x = p - y * nx;
+            const double d = (double)v;
+            tot = tot + d;
+            sx = sx + (column0 + (double)x) * d;
+            sy = sy + (row0 + (double)y) * d;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        tot = tot + __shfl_xor(tot, o);
+        sx = sx + __shfl_xor(sx, o);
+        sy = sy + __shfl_xor(sy, o);
+    }
+    if (lane == 0) {
+        const bool ok = tot == tot && tot != 0.0;
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        col_out[(size_t)b * N + i] = ok ? sx / tot : nan;
+        row_out[(size_t)b * N + i] = ok ? sy / tot : nan;
     }
 }
 
@@ -421,6 +460,20 @@ int cube_aperture_launch(lk_handle *h, int B, int N, int npix, const float *flux
         kept_host[b] = cnt[b];
         if (nonfinite_host) nonfinite_host[b] = cnt[(size_t)B + b];
     }
+    return LK_OK;
+}
+
+int cube_centroids_launch(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask, int mask_stride,
+                          double column0, double row0, double *col_out, double *row_out, hipStream_t stream) {
+    (void)h;
+    LK_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && npix >= 1, "need 1 <= B <= 65535, N >= 1, npix >= 1");
+    LK_REQUIRE(nx >= 1 && npix % nx == 0, "npix = %d is not a whole number of rows of nx = %d pixels", npix, nx);
+    LK_REQUIRE(flux && mask && col_out && row_out, "NULL buffer");
+    LK_REQUIRE(mask_stride == 0 || mask_stride == npix, "mask_stride must be 0 (one mask for the batch) or npix");
+    LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
+    hipLaunchKernelGGL(cube_centroids_kernel, dim3((N + 3) / 4, B), dim3(256), 0, stream, flux, mask, mask_stride, N, npix, nx,
+                       column0, row0, col_out, row_out);
+    LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }
 

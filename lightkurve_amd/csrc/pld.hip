@@ -33,6 +33,7 @@
 
 #include "block_select.hpp"
 #include "lk_common.hpp"
+#include "spline_basis.hpp"
 
 namespace lk {
 
@@ -748,30 +749,8 @@ __global__ __launch_bounds__(256) void pld_spline_kernel(const double *__restric
     const int order = degree + 1, nb = n_inner + order;
     if (n < N) {
         const double x = t[n], lo = kn[0], hi = kn[n_inner + 1];
-        auto T = [&](int i) -> double {  // full knot vector: order copies of lo, inner, order copies of hi
-            if (i < order) return lo;
-            if (i >= order + n_inner) return hi;
-            return kn[1 + i - order];
-        };
-        // knot span: largest mu with T(mu) <= x < T(mu+1), the right end belongs to the last non-empty span
-        int mu = order - 1;
-        const int last = order + n_inner - 1;
-        while (mu < last && !(x < T(mu + 1))) ++mu;
-        while (mu > order - 1 && T(mu) == T(mu + 1)) --mu;  // skip empty spans at repeated interior knots
-        double Nv[8] = {1.0, 0, 0, 0, 0, 0, 0, 0}, left[8], right[8];
-        for (int j = 1; j <= degree; ++j) {
-            left[j] = x - T(mu + 1 - j);
-            right[j] = T(mu + j) - x;
-            double saved = 0.0;
-            for (int r = 0; r < j; ++r) {
-                const double den = right[r + 1] + left[j - r];
-                const double tmp = den != 0.0 ? Nv[r] / den : 0.0;
-                Nv[r] = saved + right[r + 1] * tmp;
-                saved = left[j - r] * tmp;
-            }
-            Nv[j] = saved;
-        }
-        s_mu[tid] = mu - degree;  // column of Nv[0]
+        double Nv[8];
+        s_mu[tid] = bspline_row(x, lo, hi, [&](int i) { return kn[1 + i]; }, n_inner, degree, Nv);  // column of Nv[0]
 #pragma unroll
         for (int j = 0; j < 8; ++j) s_nv[tid][j] = Nv[j];
     }

@@ -875,6 +875,112 @@ class DeviceLightCurveBatch(object):
             info["trace"] = {k: np.array(v, dtype=np.float64).reshape(len(v), B) for k, v in trace.items()}
         return out, info
 
+    # ---------------------------------------------------------------- SFF
+    def _centroid_buffer(self, c, what):
+        """Centroids as a ``DeviceBuffer`` of the batch's packed layout: one as given, or a host (B, N) array / list of B
+        arrays / packed array uploaded."""
+        n = self.n_cadences
+        if isinstance(c, DeviceBuffer):
+            if c.capacity < n * 8:
+                raise ValueError("%s: device buffer smaller than the batch's %d cadences" % (what, n))
+            return c
+        if isinstance(c, (list, tuple)):
+            c = np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1) for a in c]) if len(c) else np.zeros(0)
+        c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
+        if c.size != n:
+            raise ValueError("%s needs one value per cadence of the batch (%d), got %d" % (what, n, c.size))
+        buf, k = _upload(self.handle, c, self.stream)
+        self._keep.append(k)
+        return buf
+
+    def sff_arclength(self, centroid_col, centroid_row, to_host=True):
+        """``SFFCorrector._estimate_arclength`` per target on the device (``lk_sff_arclength_batch_dev``) -> float64[sum N] on
+        the host (8 B per cadence come back), or the ``DeviceBuffer``."""
+        h, B, n = self.handle, len(self), self.n_cadences
+        d_c, d_r = self._centroid_buffer(centroid_col, "centroid_col"), self._centroid_buffer(centroid_row, "centroid_row")
+        d_arc = DeviceBuffer(h, n * 8)
+        _capi._check(_capi._lib.lk_sff_arclength_batch_dev(h._h, B, _off_ptr(self.n_off), _vp(d_c.ptr), _vp(d_r.ptr), _vp(d_arc.ptr),
+                                                           None, _vp(self.stream or None)))
+        return d_arc.download(np.float64, n, stream=self.stream) if to_host else d_arc
+
+    def sff_correct(self, centroid_col, centroid_row, windows=20, bins=5, timescale=1.5, breakindex=None, degree=3,
+                    restore_trend=False, window_points=None, cadence_mask=None, sigma=5, niters=5, to_host=False,
+                    max_scratch_bytes=None, diagnostics=True):
+        """``SFFCorrector(lc).correct(centroid_col, centroid_row, windows, bins, timescale, breakindex, degree, restore_trend)``
+        (reference correctors/sffcorrector.py) for every target of a ragged resident batch in one call of
+        ``lk_sff_correct_batch_dev``: arclength, percentile knots, the block-structured design matrices and their priors, the
+        regression and the component models never leave HBM.  The batch must be NaN-free with finite errors and centroids (a
+        target that is not gets status 2 and NaN results; 1 = baseline shorter than 4 ``timescale``).  Centroids: host (B, N) /
+        ragged lists / packed arrays, or ``DeviceBuffer``s (``DevicePixelCubeBatch.estimate_centroids(to_host=False)``).
+        ``window_points``: one list of cut indices per target; None: the arclength is downloaded (8 B per cadence) and
+        ``sff_window_points`` runs per target on the host — otherwise nothing but the B statuses crosses PCIe.
+        ``cadence_mask``: bool over the packed cadences, True = used in the fit.  ``max_scratch_bytes``: cap of the device block
+        that holds the design matrices (None: 4 GiB); groups of equal width run in chunks under it, bit-identically.
+        Windows are cut BY INDEX (the reference's by-value ``np.in1d`` differs only for bit-equal arclengths in and outside a
+        window).
+        Returns a dict: ``lc`` (corrected ``DeviceLightCurveBatch`` sharing this batch's times), ``outlier_mask``, ``status``
+        (int32[B], host), ``window_points`` and — with ``diagnostics`` — ``arclength`` / ``spline`` / ``sff``: ``DeviceBuffer``s
+        (``spline`` / ``sff`` also as batches ``spline_lc`` / ``sff_lc``); ``to_host=True`` downloads them all as packed
+        numpy arrays (``flux``, ``flux_err`` instead of ``lc``)."""
+        from .correctors.sffcorrector import sff_window_points
+        h, B, n = self.handle, len(self), self.n_cadences
+        if B < 1:
+            raise ValueError("sff_correct needs at least one light curve")
+        if self.d_flux_err is None:
+            raise ValueError("sff_correct needs flux errors")
+        d_c, d_r = self._centroid_buffer(centroid_col, "centroid_col"), self._centroid_buffer(centroid_row, "centroid_row")
+        if window_points is None:
+            arc = self.sff_arclength(d_c, d_r)
+            window_points = [sff_window_points(int(self.n_off[b + 1] - self.n_off[b]), windows, arc[self.n_off[b]:self.n_off[b + 1]],
+                                               breakindex) for b in range(B)]
+        win_off, wp = _capi.sff_window_arrays(window_points, self.n_off)
+        idx = np.concatenate([self.n_off[:-1], self.n_off[1:] - 1]).astype(np.int64)
+        ends = np.empty(2 * B, dtype=np.float64)
+        _capi._check(_capi._lib.lk_gather_f64_dev(h._h, 2 * B, _off_ptr(idx), _vp(self.d_time.ptr), ends.ctypes.data_as(_dp),
+                                                  _vp(self.stream or None)))
+        nk = _capi.sff_n_knots(ends[:B], ends[B:], timescale)
+        nbytes, _ = _capi.sff_scratch_bytes(self.n_off, nk, win_off, bins, degree, max_scratch_bytes)
+        d_scr = DeviceBuffer(h, nbytes)
+        d_cm = None
+        if cadence_mask is not None:
+            if isinstance(cadence_mask, DeviceBuffer):
+                d_cm = cadence_mask
+            else:
+                cm = np.ascontiguousarray(cadence_mask).reshape(-1).astype(np.uint8)
+                if cm.size != n:
+                    raise ValueError("cadence_mask needs one entry per cadence of the batch (%d), got %d" % (n, cm.size))
+                d_cm, k = _upload(h, cm, self.stream, np.uint8)
+                self._keep.append(k)
+        d_f, d_e, d_o = DeviceBuffer(h, n * 8), DeviceBuffer(h, n * 8), DeviceBuffer(h, n)
+        d_arc = d_sp = d_sf = None
+        if diagnostics:
+            d_arc, d_sp, d_sf = (DeviceBuffer(h, n * 8) for _ in range(3))
+        status = np.zeros(B, dtype=np.int32)
+
+        def p(buf):
+            return _vp(buf.ptr if buf is not None else None)
+
+        _capi._check(_capi._lib.lk_sff_correct_batch_dev(
+            h._h, B, _off_ptr(self.n_off), p(self.d_time), p(self.d_flux), p(self.d_flux_err), p(d_c), p(d_r), p(d_cm),
+            win_off.ctypes.data_as(_i32p), wp.ctypes.data_as(_i32p), int(bins), int(degree), float(timescale),
+            int(bool(restore_trend)), float(sigma), int(niters), p(d_scr), int(d_scr.capacity), p(d_f), p(d_e), p(d_o),
+            status.ctypes.data_as(_i32p), p(d_arc), p(d_sp), p(d_sf), None, 0, _vp(self.stream or None)))
+        wps = [np.asarray(w, dtype=np.int64) for w in window_points]
+        if to_host:
+            out = dict(flux=d_f.download(np.float64, n, stream=self.stream), flux_err=d_e.download(np.float64, n, stream=self.stream),
+                       outlier_mask=d_o.download(np.uint8, n, stream=self.stream).astype(bool), status=status, window_points=wps)
+            if diagnostics:
+                for key, buf in (("arclength", d_arc), ("spline", d_sp), ("sff", d_sf)):
+                    out[key] = buf.download(np.float64, n, stream=self.stream)
+            return out
+        lc = self._new(self.d_time, d_f, d_e, self.n_off.copy(), nan_free=bool(np.all(status == 0)), is_sorted=self.is_sorted)
+        out = dict(lc=lc, outlier_mask=d_o, status=status, window_points=wps)
+        if diagnostics:
+            out.update(arclength=d_arc, spline=d_sp, sff=d_sf,
+                       spline_lc=self._new(self.d_time, d_sp, None, self.n_off.copy(), is_sorted=self.is_sorted),
+                       sff_lc=self._new(self.d_time, d_sf, None, self.n_off.copy(), is_sorted=self.is_sorted))
+        return out
+
     # ---------------------------------------------------------------- Lomb-Scargle
     def _ls_ready(self):
         """The batch the periodogram kernels see: NaN-flux cadences dropped (LombScarglePeriodogram.from_lightcurve,
@@ -1841,6 +1947,26 @@ class DevicePixelCubeBatch(object):
         return DeviceLightCurveBatch(g["time"], g["y"], g["err"], np.arange(B + 1, dtype=np.int64) * n,
                                      [dict(m) for m in self.meta], self.device, self.stream, nan_free=True,
                                      is_sorted=self.is_sorted)
+
+    def estimate_centroids(self, aperture_mask="all", column=0, row=0, to_host=False):
+        """``TargetPixelFile.estimate_centroids(aperture_mask, method='moments')`` of every cadence of every cutout
+        (``lk_cube_centroids_batch_dev``): the flux-weighted mean pixel position inside the aperture, ``column`` / ``row`` = the
+        cutout's corner (``tpf.column`` / ``tpf.row``); float64 sums, NaN pixels count as 0, a zero or NaN total gives NaN.
+        All N cadences, in the cube's order (``to_lightcurves`` drops NaN cadences: where it dropped any, select the same ones
+        here).  -> (col, row): ``DeviceBuffer``s of B x N float64, what ``DeviceLightCurveBatch.sff_correct`` takes; or (B, N)
+        numpy arrays with ``to_host=True``."""
+        h, (B, N, ny, nx) = self.handle, self.shape
+        ap = self._masks(aperture_mask, True, None, {})
+        d_mask, k = _upload(h, ap.reshape(-1, ny * nx), self.stream, np.uint8)
+        d_c, d_r = DeviceBuffer(h, B * N * 8), DeviceBuffer(h, B * N * 8)
+        _capi._check(_capi._lib.lk_cube_centroids_batch_dev(h._h, B, N, ny * nx, nx, _vp(self.d_flux.ptr), _vp(d_mask.ptr),
+                                                            ny * nx if ap.ndim == 3 else 0, float(column), float(row),
+                                                            _vp(d_c.ptr), _vp(d_r.ptr), _vp(self.stream or None)))
+        self._keep.append(k)
+        if not to_host:
+            return d_c, d_r
+        return (d_c.download(np.float64, B * N, stream=self.stream).reshape(B, N),
+                d_r.download(np.float64, B * N, stream=self.stream).reshape(B, N))
 
     # ---------------------------------------------------------------- PLD
     def pld_correct(self, aperture_mask="all", pld_aperture_mask="all", background_aperture_mask="all", pld_order=3,

@@ -63,7 +63,12 @@ pass alone (`to_periodogram_power(to_host=False, want_peaks=True)`), F one round
 the natural grid (oversample_factor 1, up to the Nyquist frequency), in ONE process, the routes alternating, `LK_WALLS_REPS`
 (default 3) times after one warm-up.  S the resident chain `batch.to_periodogram(f, "psd").estimate_seismology()`; S_H the
 spectra brought to the host, then per target `Periodogram.flatten`, `estimate_numax_acf2d`, `estimate_deltanu_acf2d`; L the
-periodogram pass alone.  Results: profiles/seismology_walls.txt."""
+periodogram pass alone.  Results: profiles/seismology_walls.txt.
+
+`sff`: the SFF correction of `LK_WALLS_B` (default 1000) targets x `LK_WALLS_N` (default 3500) cadences with windows = 20 (one set
+of window points, chosen once, for both routes), in ONE process, the routes alternating, `LK_WALLS_REPS` (default 2) times after
+one warm-up.  R the resident call `batch.sff_correct(...)`; H the host route: `to_host()`, `SFFCorrector(lc).correct(...)` per
+target, `from_arrays`.  Written to profiles/sff_walls.txt."""
 import cProfile
 import io
 import os
@@ -622,6 +627,68 @@ def seismology():
     sys.stdout.flush()
 
 
+def sff():
+    from lightkurve_amd import _capi
+    from lightkurve_amd.correctors import SFFCorrector, sff_window_points
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    from lightkurve_amd.lightcurve import LightCurve
+    B, N = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "3500")))
+    reps, windows = int(os.environ.get("LK_WALLS_REPS", "2")), 20
+    rng = np.random.default_rng(17)
+    i = np.arange(N)
+    t = 2000.0 + 0.0204 * i
+    roll = (i % 12) / 12.0
+    col = 10.3 + roll[None] * 0.8 + 2e-5 * i[None] + 1e-3 * rng.standard_normal((B, N))
+    row = 20.7 + roll[None] * 0.55 + 1e-5 * i[None] + 1e-3 * rng.standard_normal((B, N))
+    flux = 1000.0 * (1.0 + 0.003 * np.sin(2 * np.pi * (t - t[0]) / rng.uniform(4.0, 9.0, (B, 1))) + 0.006 * (roll[None] - 0.4) ** 2
+                     + 3e-4 * rng.standard_normal((B, N)))
+    err = np.full((B, N), 0.3)
+    n_off = np.arange(B + 1, dtype=np.int64) * N
+    wp = sff_window_points(N, windows, thrusters=np.arange(11, N, 12))        # the same windows for both routes, chosen once
+    wps = [wp] * B
+    raw = DeviceLightCurveBatch.from_arrays(np.tile(t, B), flux.ravel(), err.ravel(), n_off)
+    raw.nan_free = True
+    d_col, d_row = raw._centroid_buffer(col, "centroid_col"), raw._centroid_buffer(row, "centroid_row")
+    sync = _capi.Handle.get(0).synchronize
+
+    def resident():
+        return raw.sff_correct(d_col, d_row, windows=windows, window_points=wps, diagnostics=False)["lc"]
+
+    def through_host():
+        host = raw.to_host()
+        c, r = d_col.download(np.float64, B * N), d_row.download(np.float64, B * N)
+        out = np.empty(B * N)
+        for b in range(B):
+            a, z = int(host.n_off[b]), int(host.n_off[b + 1])
+            lc = LightCurve(time=host.time[a:z], flux=host.flux[a:z], flux_err=host.flux_err[a:z])
+            out[a:z] = SFFCorrector(lc).correct(c[a:z], r[a:z], windows=windows, window_points=wp).flux
+        return DeviceLightCurveBatch.from_arrays(host.time, out, host.flux_err, host.n_off)
+
+    fns = {"R": resident, "H": through_host}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    sync()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(lambda: (fn(), sync()))[0])
+    same = np.array_equal(first["R"].flux_host(), first["H"].flux_host())
+    K = int((t[-1] - t[0]) / 1.5) + (len(wp) + 1) * 8
+    nbytes, chunks = _capi.sff_scratch_bytes(n_off, np.full(B, int((t[-1] - t[0]) / 1.5), np.int32),
+                                             np.arange(B + 1, dtype=np.int32) * len(wp), 5, 3)
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    lines = ["SFF correction, %d targets x %d cadences, windows = %d (%d window points), bins = 5: K = %d columns per target, "
+             "design matrices %.2f GB in %d chunk(s) of a %.2f GB scratch block" % (B, N, windows, len(wp), K, B * N * K * 8 / 1e9,
+                                                                                  chunks, nbytes / 1e9),
+             "  R    batch.sff_correct(d_col, d_row, window_points=...), resident                         %s" % spread(ts["R"]),
+             "  H    to_host(), SFFCorrector(lc).correct(...) per target, from_arrays                      %s" % spread(ts["H"]),
+             "  same corrected flux, bit for bit: %s" % same,
+             "  H / R = %.1f" % (med["H"] / med["R"])]
+    print("\n".join(lines))
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sff_walls.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    sys.stdout.flush()
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -647,6 +714,8 @@ def main():
         prewhiten()
     if "seismology" in which:
         seismology()
+    if "sff" in which:
+        sff()
     if "flatten" in which:
         lcs = []
         for i in range(1000):
