@@ -15,6 +15,8 @@
  *   lk_regress_batch*    <- RegressionCorrector._fit_coefficients + the sigma-clip loop of .correct,
  *                           src/lightkurve/correctors/regressioncorrector.py:127-189, 243-279.
  *   lk_regress_shared_batch*  the same for B targets on ONE shared design matrix (CBVCorrector.correct_gaussian_prior).
+ *   lk_regress_shared_rows_batch* / lk_align_rows_batch*  the same for RAGGED targets, each cadence on its own row of the
+ *                           shared matrix (CotrendingBasisVectors.align(lc) by CADENCENO before the correction).
  *   lk_underfit_neighbors_batch* <- correctors.metrics.underfit_metric_neighbors + _compute_correlation,
  *                           src/lightkurve/correctors/metrics.py:141-257, 451-475, neighbours = other targets of the batch.
  *   lk_overfit_metric_batch* <- correctors.metrics.overfit_metric_lombscargle, src/lightkurve/correctors/metrics.py:24-138,
@@ -411,6 +413,16 @@ int lk_fits_unpack_batch(lk_handle *h, int B, const uint8_t *raw, const int64_t 
 int lk_fits_unpack_batch_dev(lk_handle *h, int B, const uint8_t *raw, const int64_t *raw_off_host, const int32_t *desc_host,
                              const int64_t *bitmask_host, double *t_out, double *flux_out, double *flux_err_out,
                              int32_t *quality_out, int64_t *new_off_host, void *stream);
+/* The CADENCENO column of the same tables for the rows lk_fits_unpack_batch kept (what CotrendingBasisVectors.align matches):
+ * raw / raw_off / desc / bitmask as above (the keep rule is evaluated again from the same bytes; the flux columns of desc
+ * are not read), col: B x 2 int32 = {byte offset, TFORM code 2..5} of the integer column, new_off: the B + 1 offsets the
+ * unpack call returned (HOST), cadenceno_out: int32, new_off[B] entries, packed like the other columns.  No padding after a
+ * table is needed.  The _dev call does not synchronise. */
+int lk_fits_cadenceno_batch(lk_handle *h, int B, const uint8_t *raw, const int64_t *raw_off, const int32_t *desc,
+                            const int32_t *col, const int64_t *bitmask, const int64_t *new_off, int32_t *cadenceno_out);
+int lk_fits_cadenceno_batch_dev(lk_handle *h, int B, const uint8_t *raw, const int64_t *raw_off_host, const int32_t *desc_host,
+                                const int32_t *col_host, const int64_t *bitmask_host, const int64_t *new_off_host,
+                                int32_t *cadenceno_out, void *stream);
 
 /* lk_fits_unpack_cube: one target-pixel file -> what PLDCorrector reads from a TargetPixelFile: time, quality and the
  * float32 pixel cubes FLUX / FLUX_ERR / FLUX_BKG / ... of the cadences the reference keeps
@@ -584,6 +596,42 @@ int lk_ridge_prior_batch_dev(lk_handle *h, int B, int N, int K, const double *fl
  * lk_ridge_prior_batch_dev gives at alpha[b]. */
 int lk_ridge_prior_alphas_batch_dev(lk_handle *h, int B, int N, int K, const double *flux_err, const double *alpha,
                                     double *prior_mu, double *prior_sigma, void *stream);
+/* ---- The shared-matrix regression for a RAGGED batch: target b has n_off[b + 1] - n_off[b] >= 1 cadences and its cadence i
+ * uses row rows[n_off[b] + i] of the ONE matrix X (Nx x K, K <= 64).  rows: int32 (sum n), per target strictly increasing and
+ * in [0, Nx) (checked: LK_EINVAL names the first offending target); y, err (nullable), cadence_mask (nullable), model and
+ * outlier: (sum n), packed by n_off; priors, w and w_cov as lk_regress_shared_batch.  Per target the numerics are
+ * RegressionCorrector.correct on X[rows_b]: the clip's median / std and the model's median are over the target's own cadences.
+ * Rows of X that a target does not have add +0 to its sums, so its result has the bits its own rows alone give and, when
+ * every target has every row, the bits of lk_regress_shared_batch.  The results of a target do not depend on the other
+ * targets of the batch; the order of its partial sums depends on Nx alone.  Scratch: B x Nx int32 more than the uniform call.
+ * Synchronisation as lk_regress_shared_batch_dev (one wait, for the rows and the input check). */
+int lk_regress_shared_rows_batch(lk_handle *h, int B, const int64_t *n_off, const int32_t *rows, int Nx, int K, const double *X,
+                                 const double *y, const double *err, const uint8_t *cadence_mask, const double *prior_mu,
+                                 const double *prior_sigma, double clip_sigma, int niters, double *w, double *model,
+                                 uint8_t *outlier, double *w_cov);
+int lk_regress_shared_rows_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx, int K,
+                                     const double *X, const double *y, const double *err, const uint8_t *cadence_mask,
+                                     const double *prior_mu, const double *prior_sigma, double clip_sigma, int niters, double *w,
+                                     double *model, uint8_t *outlier, double *w_cov, void *stream);
+/* CotrendingBasisVectors.align for B targets: cadenceno (int32, (sum n), per target strictly increasing) against the grid's
+ * cadence numbers (int32, Nx, strictly increasing) -> rows (int32 (sum n): the index into the grid, binary search per
+ * cadence) and pos (int32 B x Nx, nullable: the target-relative cadence index at a grid row, -1 where the target has none).
+ * A cadence that is not on the grid is LK_EINVAL with the first such target's index in lk_last_error (rows is then still
+ * written, -1 at such cadences): drop those cadences first.  The call synchronises. */
+int lk_align_rows_batch(lk_handle *h, int B, const int64_t *n_off, const int32_t *cadenceno, int Nx, const int32_t *grid_cadenceno,
+                        int32_t *rows, int32_t *pos);
+int lk_align_rows_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *cadenceno, int Nx,
+                            const int32_t *grid_cadenceno, int32_t *rows, int32_t *pos, void *stream);
+/* lk_ridge_prior_batch_dev / lk_ridge_prior_alphas_batch_dev for a ragged batch: the median is over target b's own
+ * flux_err[n_off[b] .. n_off[b + 1]), by the same two operations (a uniform batch gets the same bits). */
+int lk_ridge_prior_rows_batch(lk_handle *h, int B, const int64_t *n_off, int K, const double *flux_err, double alpha,
+                              double *prior_mu, double *prior_sigma);
+int lk_ridge_prior_rows_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, int K, const double *flux_err, double alpha,
+                                  double *prior_mu, double *prior_sigma, void *stream);
+int lk_ridge_prior_rows_alphas_batch(lk_handle *h, int B, const int64_t *n_off, int K, const double *flux_err, const double *alpha,
+                                     double *prior_mu, double *prior_sigma);
+int lk_ridge_prior_rows_alphas_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, int K, const double *flux_err,
+                                         const double *alpha, double *prior_mu, double *prior_sigma, void *stream);
 /* out[i] = a[i] - b[i] for n doubles on the device (flux - model: the corrected flux of RegressionCorrector.correct). */
 int lk_subtract_f64_dev(lk_handle *h, int64_t n, const double *a, const double *b, double *out, void *stream);
 

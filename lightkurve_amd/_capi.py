@@ -194,6 +194,20 @@ SIGNATURES = [
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp]),
     ("lk_ridge_prior_alphas_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_regress_shared_rows_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_i32p, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_u8p, _c_dp, _c_dp, ctypes.c_double,
+      ctypes.c_int, _c_dp, _c_dp, _c_u8p, _c_dp]),
+    ("lk_regress_shared_rows_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_int,
+      _vp, _vp, _vp, _vp, _vp]),
+    ("lk_align_rows_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _c_i32p, ctypes.c_int, _c_i32p, _c_i32p, _c_i32p]),
+    ("lk_align_rows_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    ("lk_ridge_prior_rows_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, ctypes.c_int, _c_dp, ctypes.c_double, _c_dp, _c_dp]),
+    ("lk_ridge_prior_rows_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp]),
+    ("lk_ridge_prior_rows_alphas_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
+    ("lk_ridge_prior_rows_alphas_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_fits_cadenceno_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_u8p, _c_ip, _c_i32p, _c_i32p, _c_ip, _c_ip, _c_i32p]),
+    ("lk_fits_cadenceno_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _vp, _c_ip, _c_i32p, _c_i32p, _c_ip, _c_ip, _vp, _vp]),
     ("lk_subtract_f64_dev", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     ("lk_underfit_neighbors_batch", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, _c_i32p, ctypes.c_int, _c_i32p, _c_dp, _c_dp]),
@@ -922,6 +936,90 @@ def regress_shared_batch(X, y, err=None, cadence_mask=None, prior_mu=None, prior
     if want_cov:
         res["coefficients_cov"] = cov
     return res
+
+
+def _i32(a, n, name):
+    a = np.asarray(a)
+    if a.shape != (n,) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("%s must be an integer array of shape (%d,) (got %s of shape %s)" % (name, n, a.dtype, a.shape))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def align_rows_batch(cadenceno, n_off, grid_cadenceno, want_pos=False, device=0):
+    """``CotrendingBasisVectors.align`` as indices: per target sorted ``cadenceno`` (packed, (sum n,)) against the grid's
+    strictly increasing ``grid_cadenceno`` (Nx,) -> rows int32 (sum n,); ``want_pos``: also pos int32 (B, Nx), the
+    target-relative cadence index at each grid row or -1.  ``ValueError`` naming the target when a cadence is not on the grid."""
+    h = Handle.get(device)
+    cad = np.asarray(cadenceno)
+    n_off = _offsets(n_off, cad.size)
+    cad = _i32(cad, cad.size, "cadenceno")
+    grid = np.asarray(grid_cadenceno)
+    grid = _i32(grid, grid.size, "grid_cadenceno")
+    B, Nx = n_off.size - 1, grid.size
+    rows = np.empty(cad.size, dtype=np.int32)
+    pos = np.empty((B, Nx), dtype=np.int32) if want_pos else None
+    _check(_lib.lk_align_rows_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(cad, _c_i32p), Nx, _ptr(grid, _c_i32p), _ptr(rows, _c_i32p),
+                                    _ptr(pos, _c_i32p)))
+    return (rows, pos) if want_pos else rows
+
+
+def regress_shared_rows_batch(X, y, n_off, rows, err=None, cadence_mask=None, prior_mu=None, prior_sigma=None, sigma=5.0, niters=5,
+                              device=0, want_cov=False):
+    """``regress_shared_batch`` for B RAGGED targets on ONE design matrix ``X`` (Nx, K), K <= 64: ``y`` / ``err`` /
+    ``cadence_mask`` packed (sum n,) by ``n_off``, ``rows`` int (sum n,) = the row of ``X`` each cadence uses, per target
+    strictly increasing.  Per target the numerics are ``RegressionCorrector.correct`` on ``X[rows_b]``.  Returns
+    dict(coefficients[B,K], model[sum n] (median-subtracted per target), outlier_mask[sum n] bool); ``want_cov``: also
+    coefficients_cov[B,K,K]."""
+    h = Handle.get(device)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("X must be 2-D (grid rows x regressors)")
+    Nx, K = X.shape
+    y = _f64(y)
+    if y.ndim != 1:
+        raise ValueError("y must be packed 1-D (sum n,) (got shape %s)" % (y.shape,))
+    ntot = y.size
+    n_off = _offsets(n_off, ntot)
+    B = n_off.size - 1
+    rows = _i32(rows, ntot, "rows")
+    err = None if err is None else _f64(np.broadcast_to(err, (ntot,)))
+    cm = None if cadence_mask is None else np.ascontiguousarray(cadence_mask, dtype=np.uint8)
+    if cm is not None and cm.shape != (ntot,):
+        raise ValueError("cadence_mask must have one entry per cadence (got shape %s, need (%d,))" % (cm.shape, ntot))
+    if (prior_mu is None) != (prior_sigma is None):
+        raise ValueError("Please specify both `prior_mu` and `prior_sigma`")
+    if prior_mu is not None:
+        prior_mu = _f64(np.broadcast_to(np.asarray(prior_mu, dtype=np.float64), (B, K)))
+        prior_sigma = _f64(np.broadcast_to(np.asarray(prior_sigma, dtype=np.float64), (B, K)))
+    w = np.empty((B, K), dtype=np.float64)
+    model = np.empty(ntot, dtype=np.float64)
+    outl = np.empty(ntot, dtype=np.uint8)
+    cov = np.empty((B, K, K), dtype=np.float64) if want_cov else None
+    _check(_lib.lk_regress_shared_rows_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(rows, _c_i32p), Nx, K, _ptr(X), _ptr(y), _ptr(err),
+                                             _ptr(cm, _c_u8p), _ptr(prior_mu), _ptr(prior_sigma), float(sigma), int(niters),
+                                             _ptr(w), _ptr(model), _ptr(outl, _c_u8p), _ptr(cov)))
+    res = dict(coefficients=w, model=model, outlier_mask=outl.astype(bool))
+    if want_cov:
+        res["coefficients_cov"] = cov
+    return res
+
+
+def ridge_prior_rows_batch(flux_err, n_off, K, alpha, device=0):
+    """(prior_mu, prior_sigma), each (B, K), of ``CBVCorrector.correct_gaussian_prior`` for ragged targets: mu = 0 and
+    sigma_b = median(flux_err_b) / sqrt(|alpha_b|); ``alpha``: a non-zero scalar or B non-zero penalties."""
+    h = Handle.get(device)
+    e = _f64(flux_err)
+    n_off = _offsets(n_off, e.size)
+    B = n_off.size - 1
+    mu, sg = np.empty((B, int(K)), dtype=np.float64), np.empty((B, int(K)), dtype=np.float64)
+    if np.ndim(alpha) == 0:
+        _check(_lib.lk_ridge_prior_rows_batch(h._h, B, _ptr(n_off, _c_ip), int(K), _ptr(e), float(alpha), _ptr(mu), _ptr(sg)))
+    else:
+        a = _f64(alpha)
+        if a.shape != (B,) or not np.all(np.isfinite(a)) or np.any(a == 0.0):
+            raise ValueError("alpha must be a scalar or B finite, non-zero penalties")
+        _check(_lib.lk_ridge_prior_rows_alphas_batch(h._h, B, _ptr(n_off, _c_ip), int(K), _ptr(e), _ptr(a), _ptr(mu), _ptr(sg)))
+    return mu, sg
 
 
 # --------------------------------------------------------------------------------------------- under-fitting metric

@@ -9,7 +9,7 @@ from .distributed import all_gather_rows, device_gather_available, shard_bounds,
 from . import packed
 
 __all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "periodogram_peaks", "flatten_batch",
-           "estimate_cdpp_batch", "pld_correct_batch", "regression_correct_batch"]
+           "estimate_cdpp_batch", "pld_correct_batch", "regression_correct_batch", "cbv_correct_batch"]
 
 
 def _resolve_device(device):
@@ -398,3 +398,49 @@ def regression_correct_batch(lcs, design_matrices, cadence_masks=None, sigma=5, 
     outl = [r[n:2 * n] != 0.0 for r, n in zip(rows, lens)]
     coef = np.stack([r[2 * n:2 * n + K] for r, n in zip(rows, lens)]) if rows else np.zeros((0, K))
     return flux, coef, outl
+
+
+def cbv_correct_batch(lcs, cbvs, cadenceno, cbv_indices=np.arange(1, 9), alpha=1e-20, ext_dm=None, cadence_masks=None, sigma=5,
+                      niters=5, device=0):
+    """``CBVCorrector(lc, cbvs.align(lc)).correct_gaussian_prior(cbv_indices, alpha, ext_dm, cadence_mask)`` for many host
+    light curves that share the basis vectors of one channel but keep different cadences: ``cbvs`` (Nx, n_vectors) lives on
+    the cadence grid ``cadenceno`` (Nx, strictly increasing) and every light curve carries its own ``cadenceno`` column.
+    Cadences that are not on the grid are dropped, as ``align`` drops them; X goes to the device ONCE
+    (``lk_regress_shared_rows_batch``), no stacked copy per target exists.  ``alpha``: scalar (0: no prior) or one
+    penalty per target.  Returns (corrected_flux list, coefficients[B, K], outlier_mask list, kept list): ``kept[b]`` is the
+    bool mask over light curve b's cadences of those that are on the grid (the others have no corrected flux).  One
+    process, one device: a resident ``DeviceLightCurveBatch.cbv_correct(cadenceno=)`` is the route that scales."""
+    from .device import _alpha_per_target, _cbv_columns
+    lcs = list(lcs)
+    B = len(lcs)
+    X = _cbv_columns(cbvs, cbv_indices, ext_dm)
+    grid = np.asarray(cadenceno)
+    if grid.shape != (X.shape[0],) or not np.issubdtype(grid.dtype, np.integer) or np.any(np.diff(grid) <= 0):
+        raise ValueError("cadenceno must be %d strictly increasing integers, one per row of cbvs" % X.shape[0])
+    alphas = None if np.ndim(alpha) == 0 else _alpha_per_target(alpha, B)
+    cms = [None] * B if cadence_masks is None else list(cadence_masks)
+    rows, ys, errs, cmk, kept = [], [], [], [], []
+    for lc, c in zip(lcs, cms):
+        cad = np.asarray(getattr(lc, "cadenceno"))
+        cad = np.asarray(getattr(cad, "value", cad))
+        if not np.issubdtype(cad.dtype, np.integer) or cad.shape != (len(lc.time),):
+            raise ValueError("every light curve needs an integer cadenceno column, one entry per cadence")
+        if np.any(np.diff(cad) <= 0):
+            raise ValueError("every light curve's cadence numbers must be strictly increasing")
+        r = np.searchsorted(grid, cad)
+        ok = (r < grid.size) & (grid[np.minimum(r, grid.size - 1)] == cad)
+        kept.append(ok), rows.append(r[ok])
+        ys.append(np.asarray(getattr(lc.flux, "value", lc.flux), dtype=np.float64)[ok])
+        errs.append(np.asarray(getattr(lc.flux_err, "value", lc.flux_err), dtype=np.float64)[ok])
+        cmk.append(np.ones(int(ok.sum()), bool) if c is None else np.asarray(c, dtype=bool)[ok])
+    off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    if B == 0:
+        return [], np.zeros((0, X.shape[1])), [], []
+    y, err = np.concatenate(ys), np.concatenate(errs)
+    mu = sg = None
+    if alphas is not None or alpha != 0.0:
+        mu, sg = _capi.ridge_prior_rows_batch(err, off, X.shape[1], alpha if alphas is None else alphas, device=device)
+    res = _capi.regress_shared_rows_batch(X, y, off, np.concatenate(rows), err=err, cadence_mask=np.concatenate(cmk), prior_mu=mu,
+                                          prior_sigma=sg, sigma=sigma, niters=niters, device=device)
+    cut = off[1:-1]
+    return np.split(y - res["model"], cut), res["coefficients"], np.split(res["outlier_mask"], cut), kept

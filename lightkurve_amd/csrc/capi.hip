@@ -684,6 +684,113 @@ int lk_ridge_prior_alphas_batch_dev(lk_handle *h, int B, int N, int K, const dou
     return lk::ridge_prior_launch(h, B, N, K, flux_err, 0.0, alpha, prior_mu, prior_sigma, static_cast<hipStream_t>(stream));
 }
 
+// one design matrix, ragged targets aligned by cadence number
+int lk_align_rows_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *cadenceno, int Nx,
+                            const int32_t *grid_cadenceno, int32_t *rows, int32_t *pos, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::align_rows_launch(h, B, n_off_host, cadenceno, Nx, grid_cadenceno, rows, pos, static_cast<hipStream_t>(stream));
+}
+
+int lk_align_rows_batch(lk_handle *h, int B, const int64_t *n_off, const int32_t *cadenceno, int Nx, const int32_t *grid_cadenceno,
+                        int32_t *rows, int32_t *pos) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(Nx >= 1 && n_off[B] >= 0, "bad shapes");
+    LK_REQUIRE(cadenceno && grid_cadenceno && rows, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B];
+    const int32_t *dc, *dg;
+    int32_t *dr, *dp;
+    lk::StagedCall io(h);
+    int rc = io.in(dc, cadenceno, ntot).in(dg, grid_cadenceno, (size_t)Nx).out(dr, rows, ntot).out(dp, pos, (size_t)B * Nx).stage();
+    if (rc) return rc;
+    rc = lk::align_rows_launch(h, B, n_off, dc, Nx, dg, dr, dp, nullptr);
+    return rc ? rc : io.finish();
+}
+
+int lk_regress_shared_rows_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx, int K,
+                                     const double *X, const double *y, const double *err, const uint8_t *cadence_mask,
+                                     const double *prior_mu, const double *prior_sigma, double clip_sigma, int niters, double *w,
+                                     double *model, uint8_t *outlier, double *w_cov, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::regress_shared_rows_launch(h, B, n_off_host, rows, Nx, K, X, y, err, cadence_mask, prior_mu, prior_sigma, clip_sigma,
+                                          niters, w, model, outlier, w_cov, static_cast<hipStream_t>(stream));
+}
+
+int lk_regress_shared_rows_batch(lk_handle *h, int B, const int64_t *n_off, const int32_t *rows, int Nx, int K, const double *X,
+                                 const double *y, const double *err, const uint8_t *cadence_mask, const double *prior_mu,
+                                 const double *prior_sigma, double clip_sigma, int niters, double *w, double *model,
+                                 uint8_t *outlier, double *w_cov) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(K >= 1 && Nx >= 1 && n_off[B] >= 0, "K and Nx must be >= 1");
+    LK_REQUIRE(rows && X && y && w && model && outlier, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B], nk = (size_t)B * K;
+    const int32_t *drows;
+    const double *dX, *dy, *derr, *dmu, *dsg;
+    const uint8_t *dcm;
+    double *dmodel, *dw, *dcov;
+    uint8_t *dout;
+    lk::StagedCall io(h);
+    int rc = io.in(drows, rows, ntot).in(dX, X, (size_t)Nx * K).in(dy, y, ntot).in(derr, err, ntot).out(dmodel, model, ntot)
+                 .in(dcm, cadence_mask, ntot).out(dout, outlier, ntot).in(dmu, prior_mu, nk).in(dsg, prior_sigma, nk)
+                 .out(dw, w, nk).out(dcov, w_cov, nk * K).stage();
+    if (rc) return rc;
+    rc = lk::regress_shared_rows_launch(h, B, n_off, drows, Nx, K, dX, dy, derr, dcm, dmu, dsg, clip_sigma, niters, dw, dmodel, dout,
+                                        dcov, nullptr);
+    return rc ? rc : io.finish();
+}
+
+int lk_ridge_prior_rows_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, int K, const double *flux_err, double alpha,
+                                  double *prior_mu, double *prior_sigma, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::ridge_prior_rows_launch(h, B, n_off_host, K, flux_err, alpha, nullptr, prior_mu, prior_sigma,
+                                       static_cast<hipStream_t>(stream));
+}
+
+int lk_ridge_prior_rows_alphas_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, int K, const double *flux_err,
+                                         const double *alpha, double *prior_mu, double *prior_sigma, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(alpha != nullptr, "alpha is NULL (B doubles on the device)");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::ridge_prior_rows_launch(h, B, n_off_host, K, flux_err, 0.0, alpha, prior_mu, prior_sigma,
+                                       static_cast<hipStream_t>(stream));
+}
+
+// host pointers; alphas nullable (then `alpha` for every target)
+static int ridge_prior_rows_host(lk_handle *h, int B, const int64_t *n_off, int K, const double *flux_err, double alpha,
+                                 const double *alphas, double *prior_mu, double *prior_sigma) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 1 && K >= 1 && n_off != nullptr && n_off[B] >= 0, "bad shapes");
+    LK_REQUIRE(flux_err && prior_mu && prior_sigma, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t nk = (size_t)B * K;
+    const double *de, *da;
+    double *dmu, *dsg;
+    lk::StagedCall io(h);
+    int rc = io.in(de, flux_err, (size_t)n_off[B]).in(da, alphas, (size_t)B).out(dmu, prior_mu, nk).out(dsg, prior_sigma, nk).stage();
+    if (rc) return rc;
+    rc = lk::ridge_prior_rows_launch(h, B, n_off, K, de, alpha, da, dmu, dsg, nullptr);
+    return rc ? rc : io.finish();
+}
+
+int lk_ridge_prior_rows_batch(lk_handle *h, int B, const int64_t *n_off, int K, const double *flux_err, double alpha,
+                              double *prior_mu, double *prior_sigma) {
+    return ridge_prior_rows_host(h, B, n_off, K, flux_err, alpha, nullptr, prior_mu, prior_sigma);
+}
+
+int lk_ridge_prior_rows_alphas_batch(lk_handle *h, int B, const int64_t *n_off, int K, const double *flux_err, const double *alpha,
+                                     double *prior_mu, double *prior_sigma) {
+    LK_REQUIRE(alpha != nullptr, "alpha is NULL (B doubles)");
+    return ridge_prior_rows_host(h, B, n_off, K, flux_err, 0.0, alpha, prior_mu, prior_sigma);
+}
+
 int lk_subtract_f64_dev(lk_handle *h, int64_t n, const double *a, const double *b, double *out, void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
@@ -1502,6 +1609,32 @@ int lk_fits_unpack_batch(lk_handle *h, int B, const uint8_t *raw, const int64_t 
                  .out(deo, flux_err_out, rows, kept).out(dqo, quality_out, rows, kept).stage();
     if (rc) return rc;
     rc = lk::fits_unpack_launch(h, B, draw, raw_off, desc, bitmask, dto, dfo, deo, dqo, new_off, nullptr);
+    return rc ? rc : io.finish();
+}
+
+int lk_fits_cadenceno_batch_dev(lk_handle *h, int B, const uint8_t *raw, const int64_t *raw_off_host, const int32_t *desc_host,
+                                const int32_t *col_host, const int64_t *bitmask_host, const int64_t *new_off_host,
+                                int32_t *cadenceno_out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::fits_int_column_launch(h, B, raw, raw_off_host, desc_host, col_host, bitmask_host, new_off_host, cadenceno_out,
+                                      static_cast<hipStream_t>(stream));
+}
+
+int lk_fits_cadenceno_batch(lk_handle *h, int B, const uint8_t *raw, const int64_t *raw_off, const int32_t *desc,
+                            const int32_t *col, const int64_t *bitmask, const int64_t *new_off, int32_t *cadenceno_out) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && raw_off != nullptr && desc != nullptr && col != nullptr && new_off != nullptr, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(raw && bitmask && cadenceno_out, "NULL buffer");
+    LK_REQUIRE(raw_off[0] == 0 && raw_off[B] >= 0 && new_off[B] >= 0, "raw_off[0] must be 0");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const uint8_t *draw;
+    int32_t *dco;
+    lk::StagedCall io(h);
+    int rc = io.in(draw, raw, (size_t)raw_off[B]).out(dco, cadenceno_out, (size_t)new_off[B]).stage();
+    if (rc) return rc;
+    rc = lk::fits_int_column_launch(h, B, draw, raw_off, desc, col, bitmask, new_off, dco, nullptr);
     return rc ? rc : io.finish();
 }
 

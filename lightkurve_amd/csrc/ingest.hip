@@ -326,6 +326,80 @@ int fits_unpack_launch(lk_handle *h, int B, const uint8_t *raw, const int64_t *r
     return LK_OK;
 }
 
+// One more integer column of the same tables (CADENCENO: what CotrendingBasisVectors.align matches), for the rows
+// fits_unpack_kernel keeps: the keep rule is evaluated again from the same bytes, the column's value goes to
+// c_out[new_off[b] + rank of the row among the kept].  Three fields per record, read straight from global memory.
+__global__ __launch_bounds__(256) void fits_int_column_kernel(const uint8_t *__restrict__ raw, const int64_t *__restrict__ raw_off,
+                                                               const FitsDesc *__restrict__ desc, const int *__restrict__ col,
+                                                               const int64_t *__restrict__ bitmask,
+                                                               const int64_t *__restrict__ new_off, int *__restrict__ c_out) {
+    __shared__ int s_cnt[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const FitsDesc d = desc[b];
+    const int off_c = col[2 * b], code_c = col[2 * b + 1];
+    const uint8_t *tab = raw + raw_off[b];
+    const long long mask = bitmask[b];
+    long long base = new_off[b];
+    const long long end = new_off[b + 1];
+    for (long long r0 = 0; r0 < d.n_rows; r0 += FITS_ROWS) {
+        const int nr = (int)min((long long)FITS_ROWS, (long long)d.n_rows - r0);
+        __syncthreads();
+        const uint8_t *rec = tab + (size_t)(r0 + min(tid, nr - 1)) * d.row_bytes;
+        bool keep = false;
+        if (tid < nr) {
+            const double tv = fits_real(rec, d.off_t, d.code_t);
+            const long long qv = d.off_q >= 0 ? fits_int(rec, d.off_q, d.code_q) : 0;
+            keep = !isnan(tv) && (qv & mask) == 0;
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) s_cnt[wv] = __popcll(bal);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wv) before += s_cnt[w];
+            all += s_cnt[w];
+        }
+        if (keep) {
+            const long long p = base + before + __popcll(bal & ((1ull << lane) - 1ull));
+            if (p < end) c_out[p] = (int)fits_int(rec, off_c, code_c);  // (new_off from another call: never past the target)
+        }
+        base += all;
+    }
+}
+
+// new_off_host: what fits_unpack_launch returned for the same raw / desc / bitmask; col_host: B x (offset, TFORM code 2..5)
+int fits_int_column_launch(lk_handle *h, int B, const uint8_t *raw, const int64_t *raw_off_host, const int32_t *desc_host,
+                           const int32_t *col_host, const int64_t *bitmask_host, const int64_t *new_off_host, int32_t *c_out,
+                           hipStream_t stream) {
+    LK_REQUIRE(B >= 0 && raw_off_host && desc_host && col_host && new_off_host, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(raw && bitmask_host && c_out, "NULL buffer");
+    LK_REQUIRE(new_off_host[0] == 0, "new_off must start at 0");
+    const int widths[6] = {8, 4, 4, 8, 2, 1};
+    for (int b = 0; b < B; ++b) {
+        const int32_t *d = desc_host + (size_t)b * 10, *c = col_host + (size_t)b * 2;
+        LK_REQUIRE(d[0] >= 1 && d[1] >= 0, "file %d: bad record length or row count", b);
+        LK_REQUIRE(raw_off_host[b + 1] - raw_off_host[b] >= (int64_t)d[0] * d[1], "file %d: `raw` holds fewer bytes than rows x record length", b);
+        LK_REQUIRE(d[3] >= 0 && d[3] <= 1 && d[2] >= 0 && d[2] + widths[d[3]] <= d[0], "file %d: TIME does not fit the record", b);
+        LK_REQUIRE(d[8] < 0 || (d[9] >= 2 && d[9] <= 5 && d[8] + widths[d[9]] <= d[0]), "file %d: QUALITY does not fit the record", b);
+        LK_REQUIRE(c[1] >= 2 && c[1] <= 5 && c[0] >= 0 && c[0] + widths[c[1]] <= d[0],
+                   "file %d: the integer column (offset %d, type %d) does not fit the %d-byte record", b, c[0], c[1], d[0]);
+        LK_REQUIRE(new_off_host[b + 1] >= new_off_host[b] && new_off_host[b + 1] - new_off_host[b] <= d[1],
+                   "file %d: new_off keeps more rows than the table has", b);
+    }
+    int64_t *d_roff, *d_mask, *d_new;
+    FitsDesc *d_desc;
+    int *d_col;
+    Scratch ws(h, h->ws);
+    ws.upload(d_roff, raw_off_host, (size_t)B + 1).upload(d_mask, bitmask_host, B).upload(d_new, new_off_host, (size_t)B + 1)
+        .upload(d_desc, reinterpret_cast<const FitsDesc *>(desc_host), B).upload(d_col, col_host, (size_t)2 * B);
+    if (const int rc = ws.carve(stream)) return rc;
+    hipLaunchKernelGGL(fits_int_column_kernel, dim3(B), dim3(256), 0, stream, raw, (const int64_t *)d_roff, (const FitsDesc *)d_desc,
+                       (const int *)d_col, (const int64_t *)d_mask, (const int64_t *)d_new, c_out);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
 // Target-pixel files (the input of PLDCorrector): every kept cadence's pixel vectors (FLUX, FLUX_ERR, FLUX_BKG ...: `npix`
 // big-endian float32 per column and record) -> float32 cubes [column][kept cadence][pixel].  One workgroup per kept
 // cadence; the pixels of a record are contiguous, so the loads are coalesced 4-byte words when the column is aligned.

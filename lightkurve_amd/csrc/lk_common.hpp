@@ -182,6 +182,16 @@ int regress_shared_launch(lk_handle *h, int B, int N, int K, const double *X, co
                           double *w, double *model, uint8_t *outl, double *w_cov, hipStream_t stream);
 int ridge_prior_launch(lk_handle *h, int B, int N, int K, const double *err, double alpha, const double *alphas, double *prior_mu,
                        double *prior_sigma, hipStream_t stream);
+// regress.hip, ragged targets on one shared matrix: cadence numbers -> rows of the grid (pos nullable: the inverse map, B x Nx);
+// the fit with target b's cadence i on row rows[n_off[b] + i] of X; the ridge prior over each target's own errors
+int align_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *cadenceno, int Nx, const int32_t *grid,
+                      int32_t *rows, int32_t *pos, hipStream_t stream);
+int regress_shared_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx, int K, const double *X,
+                               const double *y, const double *err, const uint8_t *cmask, const double *prior_mu,
+                               const double *prior_sigma, double clip_sigma, int niters, double *w, double *model, uint8_t *outl,
+                               double *w_cov, hipStream_t stream);
+int ridge_prior_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, int K, const double *err, double alpha,
+                            const double *alphas, double *prior_mu, double *prior_sigma, hipStream_t stream);
 int subtract_launch(lk_handle *h, int64_t n, const double *a, const double *b, double *out, hipStream_t stream);
 int underfit_neighbors_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
                               const int32_t *neighbors, double *corr, double *metric, hipStream_t stream);
@@ -256,6 +266,9 @@ int cdpp_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *fl
 int fits_unpack_launch(lk_handle *h, int B, const uint8_t *raw, const int64_t *raw_off_host, const int32_t *desc_host,
                        const int64_t *bitmask_host, double *t_out, double *f_out, double *e_out, int32_t *q_out,
                        int64_t *new_off_host, hipStream_t stream);
+int fits_int_column_launch(lk_handle *h, int B, const uint8_t *raw, const int64_t *raw_off_host, const int32_t *desc_host,
+                           const int32_t *col_host, const int64_t *bitmask_host, const int64_t *new_off_host, int32_t *c_out,
+                           hipStream_t stream);
 int fits_cube_launch(lk_handle *h, const uint8_t *raw, int row_bytes, int n_rows, int off_time, int code_time, int off_qual,
                      int code_qual, int64_t bitmask, int keep_nan_time, int ncols, const int32_t *col_off_host, int npix,
                      double *t_out, int32_t *q_out, float *cubes_out, int64_t *kept_host, hipStream_t stream);

@@ -14,6 +14,7 @@
 // Final: model = X w - median(X w).
 // Targets that share ONE design matrix (cotrending on a channel's basis vectors) take gram_shared_kernel / model_shared_kernel
 // below instead of the first and third step: see "one design matrix for all targets".
+#include <climits>
 #include <cstdlib>
 
 #include "block_select.hpp"
@@ -1181,12 +1182,19 @@ static void shared_split(int N, int *nslice, int *len) {
 }
 
 // part[(16 tile + row) * S + slice][NC]: the slice's share of row `row` of [W | W o Y] times the pair / plain columns
-template <int NS>
+// ROWS: a ragged batch on a grid of N rows (regress_shared_rows_launch).  Target b holds n_off[b + 1] - n_off[b] cadences and
+// pos[b][r] is the target-relative index of its cadence at grid row r, or -1: y / err / cmask / outl are then read at
+// n_off[b] + pos[b][r] and a row the target does not have gets weight 0.  It adds 0 x = +0 to every accumulator, so a target's
+// sums are the bits that its own rows alone give in row order; with every row present they are the bits of ROWS = false.
+// The two extra arguments come last, so the kernel arguments of ROWS = false sit where they sat before the flavour existed.
+template <int NS, bool ROWS = false>
 __global__ __launch_bounds__(SH_NT) void gram_shared_kernel(const double *__restrict__ X, const double *__restrict__ y,
                                                             const double *__restrict__ err,
                                                             const uint8_t *__restrict__ cmask,
                                                             const uint8_t *__restrict__ outl, int B, int N, int K, int slice,
-                                                            double *__restrict__ part, const int *__restrict__ done) {
+                                                            double *__restrict__ part, const int *__restrict__ done,
+                                                            const int *__restrict__ pos = nullptr,
+                                                            const int64_t *__restrict__ n_off = nullptr) {
     __shared__ __attribute__((aligned(16))) double sx[2][(SH_KMAX + 2) * SH_LD];  // [buf][column | ones | zeros][cadence]
     __shared__ __attribute__((aligned(16))) double sw[2][2][SH_TB * SH_LD];       // [buf][w | w y][target][cadence]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1254,10 +1262,20 @@ __global__ __launch_bounds__(SH_NT) void gram_shared_kernel(const double *__rest
     const uint8_t *cp = cmask ? cmask : outl;
     double xv[SH_NXF], yv = 0.0, ev = 1.0;
     uint8_t cv = 1, ov = 0;
+    int pv = 0;                                      // ROWS: the cadence at this grid row, -1 = the target has none
+    int64_t tlo = 0, tlast = 0;                      // ROWS: the target's first cadence, the batch's last one
+    if (ROWS) {
+        tlo = n_off[min(b0 + lt, B - 1)];
+        tlast = n_off[B] - 1;
+    }
     auto fetch = [&](int n0) {
 #pragma unroll
         for (int u = 0; u < SH_NXF; ++u) xv[u] = xs[min(n0 * K + tid + SH_NT * u, xlast)];  // (past the slice: weight 0)
-        const size_t g = trow + min(nlo + n0 + lc, nhi - 1);
+        size_t g = trow + min(nlo + n0 + lc, nhi - 1);
+        if (ROWS) {
+            pv = pos[g];
+            g = (size_t)min(tlo + max(pv, 0), tlast);
+        }
         yv = y[g];
         ev = ep[g];
         cv = cp[g];
@@ -1267,7 +1285,7 @@ __global__ __launch_bounds__(SH_NT) void gram_shared_kernel(const double *__rest
 #pragma unroll
         for (int u = 0; u < SH_NXF; ++u)
             if (tid + SH_NT * u < SH_RC * K) sx[buf][xdst[u]] = xv[u];
-        const bool live = tlive && n0 + lc < n && (cmask == nullptr || cv != 0) && ov == 0;
+        const bool live = tlive && n0 + lc < n && (cmask == nullptr || cv != 0) && ov == 0 && (!ROWS || pv >= 0);
         const double e1 = err ? ev : 1.0;
         const double w = live ? 1.0 / (e1 * e1) : 0.0;
         sw[buf][0][lt * SH_LD + lc] = w;
@@ -1509,6 +1527,25 @@ __global__ __launch_bounds__(1024) void ridge_prior_kernel(const double *__restr
     }
 }
 
+// The same for a ragged batch: target b's errors are err[n_off[b] .. n_off[b + 1]) and the median is over its own cadences, by
+// the same select and the same two operations (a uniform batch gets the bits of ridge_prior_kernel).
+__global__ __launch_bounds__(1024) void ridge_prior_rows_kernel(const double *__restrict__ err, const int64_t *__restrict__ n_off,
+                                                                int K, double alpha, const double *__restrict__ alphas,
+                                                                double *__restrict__ mu, double *__restrict__ sg) {
+    __shared__ unsigned long long sh[1024];
+    const int b = blockIdx.x;
+    const double *e = err + n_off[b];
+    const int N = (int)(n_off[b + 1] - n_off[b]);
+    auto val = [&](int i) { return e[i]; };
+    auto keep = [&](int) { return true; };
+    const double med = block_median(N, (long long)N, val, keep, sh);
+    const double s = med / sqrt(fabs(alphas ? alphas[b] : alpha));
+    for (int k = threadIdx.x; k < K; k += 1024) {
+        mu[(size_t)b * K + k] = 0.0;
+        sg[(size_t)b * K + k] = s;
+    }
+}
+
 // alphas: B doubles on the device, or NULL = `alpha` for every target
 int ridge_prior_launch(lk_handle *h, int B, int N, int K, const double *err, double alpha, const double *alphas, double *prior_mu,
                        double *prior_sigma, hipStream_t stream) {
@@ -1517,6 +1554,238 @@ int ridge_prior_launch(lk_handle *h, int B, int N, int K, const double *err, dou
     LK_REQUIRE(err && prior_mu && prior_sigma, "NULL buffer");
     LK_REQUIRE(alphas || (alpha != 0.0 && alpha == alpha), "alpha must be non-zero (alpha == 0 means no prior: pass NULL priors)");
     hipLaunchKernelGGL(ridge_prior_kernel, dim3(B), dim3(1024), 0, stream, err, N, K, alpha, alphas, prior_mu, prior_sigma);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ one design matrix, ragged targets
+// A batch made from real files is ragged: every target keeps its own subset of the sector's cadences, and the channel's basis
+// vectors live on the sector's cadence grid (CotrendingBasisVectors.align matches CADENCENO before the fit).  Target b has
+// n_b cadences and its cadence i uses row rows_b[i] of the ONE matrix X (Nx rows); rows_b is strictly increasing.  The fit per
+// target is RegressionCorrector.correct on X[rows_b]: the clip's median / std, the model's median and the ridge width are over
+// the target's own cadences.  The Gram kernel walks the GRID's rows (the decomposition and shared_split(Nx) of the uniform
+// path) and finds a target's cadence at a row through the inverse map pos[b][r]; everything else is per cadence.
+static int ragged_offsets(int B, const int64_t *n_off_host, int64_t *nmax) {
+    LK_REQUIRE(n_off_host[0] == 0, "n_off must start at 0");
+    *nmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t nb = n_off_host[b + 1] - n_off_host[b];
+        LK_REQUIRE(nb >= 1, "target %d has no cadence (n_off not increasing): every target needs at least one", b);
+        LK_REQUIRE(nb < (1 << 30), "target %d: %lld cadences outside 1..2^30", b, (long long)nb);
+        *nmax = std::max(*nmax, nb);
+    }
+    return LK_OK;
+}
+
+// rows[n_off[b] + i] = the index of cad[n_off[b] + i] in grid[0..Nx) (binary search), -1 when it is not there;
+// pos[b][that index] = i (pos is -1 everywhere before the launch).  bad[0]: the first target with a cadence off the grid,
+// bad[1]: the first target whose cadence numbers are not strictly increasing (its scatter would collide).
+__global__ __launch_bounds__(256) void align_rows_kernel(const int *__restrict__ cad, const int64_t *__restrict__ n_off,
+                                                         const int *__restrict__ grid, int Nx, int *__restrict__ rows,
+                                                         int *__restrict__ pos, int *__restrict__ bad) {
+    const int b = blockIdx.y;
+    const int64_t lo = n_off[b];
+    const int n = (int)(n_off[b + 1] - lo), i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = cad[lo + i];
+    if (i > 0 && cad[lo + i - 1] >= c) atomicMin(bad + 1, b);
+    int a = 0, e = Nx;  // first grid entry >= c
+    while (a < e) {
+        const int mid = (a + e) >> 1;
+        if (grid[mid] < c)
+            a = mid + 1;
+        else
+            e = mid;
+    }
+    const bool hit = a < Nx && grid[a] == c;
+    rows[lo + i] = hit ? a : -1;
+    if (!hit)
+        atomicMin(bad, b);
+    else if (pos)
+        pos[(size_t)b * Nx + a] = i;
+}
+
+__global__ __launch_bounds__(256) void increasing_check_kernel(const int *__restrict__ v, int n, int *__restrict__ flag) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > 0 && i < n && v[i - 1] >= v[i]) atomicOr(flag, 1);
+}
+
+// rows given by the caller: in range and strictly increasing per target, else bad[0] = the first offending target; pos as above
+__global__ __launch_bounds__(256) void rows_pos_kernel(const int *__restrict__ rows, const int64_t *__restrict__ n_off, int Nx,
+                                                       int *__restrict__ pos, int *__restrict__ bad) {
+    const int b = blockIdx.y;
+    const int64_t lo = n_off[b];
+    const int n = (int)(n_off[b + 1] - lo), i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int r = rows[lo + i];
+    const bool ok = r >= 0 && r < Nx && (i == 0 || rows[lo + i - 1] < r);
+    if (ok)
+        pos[(size_t)b * Nx + r] = i;
+    else
+        atomicMin(bad, b);
+}
+
+int align_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *cadenceno, int Nx, const int32_t *grid,
+                      int32_t *rows, int32_t *pos, hipStream_t stream) {
+    LK_REQUIRE(B >= 0 && n_off_host, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(B <= 65535, "at most 65535 targets per call on this path (got %d): split the batch", B);
+    LK_REQUIRE(Nx >= 1 && Nx < (1 << 30), "Nx=%d grid rows outside 1..2^30", Nx);
+    LK_REQUIRE(cadenceno && grid && rows, "NULL buffer");
+    int64_t nmax = 0;
+    if (const int rc = ragged_offsets(B, n_off_host, &nmax)) return rc;
+    const int init[3] = {INT_MAX, INT_MAX, 0};
+    int64_t *d_off;
+    int *d_bad;
+    Scratch ws(h, h->ws);
+    ws.upload(d_off, n_off_host, (size_t)B + 1).upload(d_bad, init, 3);
+    if (const int rc = ws.carve(stream)) return rc;
+    if (pos) LK_HIP_CHECK(hipMemsetAsync(pos, 0xff, (size_t)B * Nx * 4, stream));  // -1
+    hipLaunchKernelGGL(increasing_check_kernel, dim3((Nx + 255) / 256), dim3(256), 0, stream, grid, Nx, d_bad + 2);
+    hipLaunchKernelGGL(align_rows_kernel, dim3((unsigned)((nmax + 255) / 256), B), dim3(256), 0, stream, cadenceno,
+                       (const int64_t *)d_off, grid, Nx, rows, pos, d_bad);
+    LK_HIP_CHECK(hipGetLastError());
+    int bad[3] = {0, 0, 0};
+    LK_HIP_CHECK(hipMemcpyAsync(bad, d_bad, 12, hipMemcpyDeviceToHost, stream));
+    LK_HIP_CHECK(hipStreamSynchronize(stream));
+    LK_REQUIRE(!bad[2], "the grid's cadence numbers must be strictly increasing");
+    LK_REQUIRE(bad[1] == INT_MAX, "target %d: its cadence numbers must be strictly increasing", bad[1]);
+    LK_REQUIRE(bad[0] == INT_MAX, "target %d has a cadence that is not on the grid (drop it first, as CotrendingBasisVectors.align does)",
+               bad[0]);
+    return LK_OK;
+}
+
+// model[n_off[b] + i] = sum_k X[rows[n_off[b] + i]][k] w[b][k], k ascending from 0.0 (the bits of model_shared_kernel): a workgroup
+// stages the coefficients of 8 targets in LDS and walks one 256-cadence tile of each; a thread reads its own row of X, which
+// neighbours in the wave mostly follow (rows_b is increasing and nearly dense), from the cache.
+constexpr int MR_TB = 8;
+__global__ __launch_bounds__(256) void model_rows_kernel(const double *__restrict__ X, const double *__restrict__ w,
+                                                         const int *__restrict__ rows, const int64_t *__restrict__ n_off, int B,
+                                                         int K, double *__restrict__ model, const int *__restrict__ done) {
+    __shared__ double s_w[MR_TB * SH_KMAX];
+    const int tid = threadIdx.x, b0 = blockIdx.y * MR_TB;
+    for (int e = tid; e < MR_TB * K; e += 256) {
+        const int t = e / K, k = e - t * K;
+        s_w[t * SH_KMAX + k] = w[(size_t)min(b0 + t, B - 1) * K + k];
+    }
+    __syncthreads();
+    const int i = blockIdx.x * 256 + tid;
+    for (int t = 0; t < MR_TB && b0 + t < B; ++t) {
+        const int b = b0 + t;
+        const int64_t lo = n_off[b];
+        if (i >= (int)(n_off[b + 1] - lo) || (done && done[b])) continue;
+        const double *xr = X + (size_t)rows[lo + i] * K;
+        const double *wt = s_w + t * SH_KMAX;
+        double a = 0.0;
+        for (int k = 0; k < K; ++k) a = fma(xr[k], wt[k], a);
+        model[lo + i] = a;
+    }
+}
+
+// Workspace: regress_shared_launch's with sum n in place of B N, plus the inverse map pos (B Nx int32: 80 MB for 1000 targets
+// on 20 000 rows).
+int regress_shared_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx, int K, const double *X,
+                               const double *y, const double *err, const uint8_t *cmask, const double *prior_mu,
+                               const double *prior_sigma, double clip_sigma, int niters, double *w, double *model, uint8_t *outl,
+                               double *w_cov, hipStream_t stream) {
+    LK_REQUIRE(B >= 0 && n_off_host, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(K >= 1, "K must be >= 1 (got %d)", K);
+    LK_REQUIRE(K <= SH_KMAX,
+               "K=%d: the shared-matrix regression takes at most %d columns; wider matrices go through lk_regress_batch "
+               "(one design matrix per target)", K, SH_KMAX);
+    LK_REQUIRE(B <= 65535, "at most 65535 targets per call on this path (got %d): split the batch", B);
+    LK_REQUIRE(Nx >= 1 && Nx < (1 << 30), "Nx=%d grid rows outside 1..2^30", Nx);
+    LK_REQUIRE(rows && X && y && w && model && outl, "NULL buffer");
+    LK_REQUIRE((prior_mu == nullptr) == (prior_sigma == nullptr), "Please specify both `prior_mu` and `prior_sigma`");
+    LK_REQUIRE(niters >= 1, "niters must be >= 1");
+    int64_t nmax = 0;
+    if (const int rc = ragged_offsets(B, n_off_host, &nmax)) return rc;
+    const size_t ntot = (size_t)n_off_host[B];
+    const int KB = (K + 1 + GR_BLK - 1) / GR_BLK, Kp = KB * GR_BLK;
+    int S = 1, slice = Nx;
+    shared_split(Nx, &S, &slice);
+    const int ntb = (B + SH_TB - 1) / SH_TB, npairs = K * (K + 1) / 2, T = (npairs + 15) / 16 + (K + 15) / 16, NC = 16 * T;
+    const int init[2] = {0, INT_MAX};  // input-check flags | first target with bad rows
+    int64_t *d_off;
+    double *d_G, *d_A, *d_part;
+    uint8_t *d_flag;
+    int *d_done, *d_bad, *d_pos;
+    Scratch ws(h, h->ws);
+    ws.upload(d_off, n_off_host, (size_t)B + 1)
+        .buf(d_G, (size_t)B * Kp * Kp)
+        .buf(d_A, (size_t)B * K * (K + 1) * (w_cov ? 2 : 1))
+        .buf(d_flag, ntot).buf(d_done, B)
+        .buf(d_part, (size_t)ntb * SH_TB * S * NC)
+        .buf(d_pos, (size_t)B * Nx)
+        .upload(d_bad, init, 2);
+    if (const int rc = ws.carve(stream)) return rc;
+    // the rows and the input check first: their answers are back before the fit is queued
+    LK_HIP_CHECK(hipMemsetAsync(d_pos, 0xff, (size_t)B * Nx * 4, stream));  // -1: the target has no cadence at that row
+    {
+        hipLaunchKernelGGL(rows_pos_kernel, dim3((unsigned)((nmax + 255) / 256), B), dim3(256), 0, stream, rows,
+                           (const int64_t *)d_off, Nx, d_pos, d_bad + 1);
+        const int gx = (int)std::min<size_t>((ntot + 1023) / 1024, 2048);
+        hipLaunchKernelGGL(shared_check_kernel, dim3(gx), dim3(256), 0, stream, y, err, ntot, d_bad);
+        LK_HIP_CHECK(hipGetLastError());
+        int bad[2] = {0, 0};
+        LK_HIP_CHECK(hipMemcpyAsync(bad, d_bad, 8, hipMemcpyDeviceToHost, stream));
+        LK_HIP_CHECK(hipStreamSynchronize(stream));
+        LK_REQUIRE(bad[1] == INT_MAX, "target %d: rows must be strictly increasing indices into the %d rows of X", bad[1], Nx);
+        LK_REQUIRE(!(bad[0] & 1), "Input light curve has NaNs in the flux");
+        LK_REQUIRE(!(bad[0] & 2), "Input light curve has NaN, infinite, zero or negative flux errors");
+    }
+    LK_HIP_CHECK(hipMemsetAsync(outl, 0, ntot, stream));
+    LK_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)B * 4, stream));
+    const int ns = (T + 7) / 8;
+    const size_t solve_lds = ((size_t)K * (K + 1) + 2 * K + 2 * SOLVE_NW + 2) * 8;  // (<= 35 KB for K <= 64)
+    {
+        const int rc_ = want_lds(h, reinterpret_cast<const void *>(solve_lds_kernel), 160 * 1024);
+        if (rc_) return rc_;
+    }
+    for (int it = 0; it < niters; ++it) {
+#define SHR_GO(NS_)                                                                                                            \
+    hipLaunchKernelGGL((gram_shared_kernel<NS_, true>), dim3(ntb, S), dim3(SH_NT), 0, stream, X, y, err, cmask,                 \
+                       (const uint8_t *)outl, B, Nx, K, slice, d_part, (const int *)d_done, (const int *)d_pos,               \
+                       (const int64_t *)d_off)
+        if (ns <= 1) SHR_GO(1);
+        else if (ns <= 2) SHR_GO(2);
+        else if (ns <= 3) SHR_GO(3);
+        else if (ns <= 4) SHR_GO(4);
+        else if (ns <= 6) SHR_GO(6);
+        else if (ns <= 8) SHR_GO(8);
+        else if (ns <= 12) SHR_GO(12);
+        else SHR_GO(17);
+#undef SHR_GO
+        hipLaunchKernelGGL(gram_shared_reduce_kernel, dim3(B), dim3(256), 0, stream, (const double *)d_part, S, K, Kp, d_G,
+                           (const int *)d_done);
+        hipLaunchKernelGGL(solve_lds_kernel, dim3(B), dim3(SOLVE_NT), solve_lds, stream, d_G, K, Kp, prior_mu, prior_sigma, w,
+                           (const int *)d_done);
+        hipLaunchKernelGGL(model_rows_kernel, dim3((unsigned)((nmax + 255) / 256), (B + MR_TB - 1) / MR_TB), dim3(256), 0, stream, X,
+                           (const double *)w, rows, (const int64_t *)d_off, B, K, model, (const int *)d_done);
+        hipLaunchKernelGGL(clip_kernel, dim3(B), dim3(1024), 0, stream, y, model, d_off, clip_sigma, 5, d_flag, outl, d_done,
+                           (int *)nullptr, (int *)nullptr, 0);
+    }
+    hipLaunchKernelGGL(demedian_kernel, dim3(B), dim3(1024), 0, stream, d_off, model);
+    if (w_cov) hipLaunchKernelGGL(invert_kernel, dim3(B), dim3(256), 0, stream, d_G, K, Kp, prior_sigma, d_A, w_cov);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+// alphas: B doubles on the device, or NULL = `alpha` for every target; a uniform batch gets the bits of ridge_prior_launch
+int ridge_prior_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, int K, const double *err, double alpha,
+                            const double *alphas, double *prior_mu, double *prior_sigma, hipStream_t stream) {
+    LK_REQUIRE(B >= 1 && B <= 65535 && K >= 1 && n_off_host, "bad shapes");
+    LK_REQUIRE(err && prior_mu && prior_sigma, "NULL buffer");
+    LK_REQUIRE(alphas || (alpha != 0.0 && alpha == alpha), "alpha must be non-zero (alpha == 0 means no prior: pass NULL priors)");
+    int64_t nmax = 0;
+    if (const int rc = ragged_offsets(B, n_off_host, &nmax)) return rc;
+    int64_t *d_off;
+    Scratch ws(h, h->ws);
+    ws.upload(d_off, n_off_host, (size_t)B + 1);
+    if (const int rc = ws.carve(stream)) return rc;
+    hipLaunchKernelGGL(ridge_prior_rows_kernel, dim3(B), dim3(1024), 0, stream, err, (const int64_t *)d_off, K, alpha, alphas,
+                       prior_mu, prior_sigma);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }

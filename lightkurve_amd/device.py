@@ -162,13 +162,15 @@ class DeviceLightCurveBatch(object):
         self.nan_free = bool(nan_free)          # no NaN flux: the periodogram front ends need not compact first
         self.is_sorted = is_sorted              # times non-decreasing per light curve (None: not checked yet)
         self.d_quality = None                   # int32 flags (from_fits), carried through remove_nans / normalize
+        self.d_cadenceno = None                 # int32 cadence numbers (from_fits / from_arrays(cadenceno=)), carried likewise
         self.median_flux = None                 # DeviceBuffer float64[B] after remove_nans / normalize
         self._keep = []                         # host staging the stream may still be reading
 
     # ---------------------------------------------------------------- construction
     @classmethod
-    def from_arrays(cls, time, flux, flux_err, n_off, meta=None, device=0, stream=0):
-        """H2D once: packed host arrays (page-locked ones from ``_capi.pinned_empty`` / the staging pool go by DMA)."""
+    def from_arrays(cls, time, flux, flux_err, n_off, meta=None, device=0, stream=0, cadenceno=None):
+        """H2D once: packed host arrays (page-locked ones from ``_capi.pinned_empty`` / the staging pool go by DMA).
+        ``cadenceno``: integer cadence numbers, one per cadence (what ``cbv_correct(cadenceno=)`` aligns by)."""
         time = np.ascontiguousarray(time, dtype=np.float64)
         n_off = _capi._offsets(n_off, time.size)
         h = _capi.Handle.get(device)
@@ -182,7 +184,12 @@ class DeviceLightCurveBatch(object):
                 raise ValueError("time, flux, flux_err must be 1-D arrays of one length")
             b, k = _upload(h, a, stream)
             bufs.append(b), keep.append(k)
+        if cadenceno is not None:
+            cad = _cadenceno_array(cadenceno, time.size, "cadenceno")
         out = cls(bufs[0], bufs[1], bufs[2], n_off, meta, device, stream, is_sorted=srt)
+        if cadenceno is not None:
+            out.d_cadenceno, k = _upload(h, cad, stream, np.int32)
+            keep.append(k)
         out._keep = keep
         return out
 
@@ -201,7 +208,8 @@ class DeviceLightCurveBatch(object):
     @classmethod
     def from_batch(cls, batch, device=0, stream=0):
         """From a host ``LightCurveBatch``."""
-        out = cls.from_arrays(batch.time, batch.flux, batch.flux_err, batch.n_off, [dict(m) for m in batch.meta], device, stream)
+        out = cls.from_arrays(batch.time, batch.flux, batch.flux_err, batch.n_off, [dict(m) for m in batch.meta], device, stream,
+                              cadenceno=getattr(batch, "cadenceno", None))
         if getattr(batch, "quality", None) is not None:
             out.d_quality, k = _upload(out.handle, batch.quality, stream, np.int32)
             out._keep.append(k)
@@ -211,14 +219,15 @@ class DeviceLightCurveBatch(object):
     def from_fits(cls, paths, flux_column=None, quality_bitmask="default", ext=1, device=0, stream=0):
         """Light-curve FITS files -> a device-resident batch (``LightCurveBatch.from_fits`` without the way back: reference
         ``lk.read(path)`` per file, src/lightkurve/io/generic.py:21-207, io/kepler.py, io/tess.py).  The host parses the
-        headers; the tables' bytes go to HBM as they are and ``lk_fits_unpack_batch_dev`` turns them into the arrays."""
+        headers; the tables' bytes go to HBM as they are and ``lk_fits_unpack_batch_dev`` turns them into the arrays.  When
+        every table has a CADENCENO column the kept cadences' numbers become ``d_cadenceno`` (``lk_fits_cadenceno_batch_dev``)."""
         from . import fitsio
         h = _capi.Handle.get(device)
-        raws, descs, masks, meta = [], [], [], []
+        raws, descs, masks, meta, cadcols = [], [], [], [], []
         for path in paths:
             tab = fitsio.read_fits_table(path, ext=ext)
             desc, bitmask, mission = fitsio.lightcurve_columns(tab, flux_column=flux_column, quality_bitmask=quality_bitmask)
-            raws.append(tab.raw), descs.append(desc), masks.append(bitmask)
+            raws.append(tab.raw), descs.append(desc), masks.append(bitmask), cadcols.append(fitsio.int_column(tab, "cadenceno"))
             meta.append({"FILENAME": str(path), "LABEL": tab.primary.get("OBJECT"),
                          "MISSION": tab.primary.get("MISSION", tab.primary.get("TELESCOP")), "RA": tab.primary.get("RA_OBJ"),
                          "DEC": tab.primary.get("DEC_OBJ"), "QUALITY_BITMASK": quality_bitmask,
@@ -252,6 +261,14 @@ class DeviceLightCurveBatch(object):
                                                          _off_ptr(new_off), _vp(stream or None)))     # (synchronises)
         out = cls(d_t, d_f, d_e, new_off, meta, device, stream)
         out.d_quality = d_q
+        if B and all(c is not None for c in cadcols):      # every table has CADENCENO: decoded from the same bytes
+            col = np.ascontiguousarray(cadcols, dtype=np.int32).reshape(B, 2)
+            d_c = DeviceBuffer(h, max(int(new_off[-1]), 1) * 4)
+            _capi._check(_capi._lib.lk_fits_cadenceno_batch_dev(h._h, B, _vp(d_raw.ptr), _off_ptr(raw_off), desc.ctypes.data_as(_i32p),
+                                                                col.ctypes.data_as(_i32p), _off_ptr(mask), _off_ptr(new_off),
+                                                                _vp(d_c.ptr), _vp(stream or None)))
+            out.d_cadenceno = d_c
+            out._keep = [d_raw]          # the decode may still be reading the tables' bytes
         return out
 
     # ---------------------------------------------------------------- plumbing
@@ -287,6 +304,15 @@ class DeviceLightCurveBatch(object):
     def quality_host(self):
         return self._host(self.d_quality, np.int32)
 
+    def cadenceno_host(self):
+        """The cadence numbers of all cadences of the batch (int32), or None when the batch carries none."""
+        return self._host(self.d_cadenceno, np.int32)
+
+    def _carry(self, out):
+        """The per-cadence integer columns onto a batch with the same cadences."""
+        out.d_quality, out.d_cadenceno = self.d_quality, self.d_cadenceno
+        return out
+
     def to_host(self):
         """D2H of the three columns -> ``LightCurveBatch`` (what a caller asks back at the END of a chain)."""
         from .ingest import LightCurveBatch
@@ -295,6 +321,8 @@ class DeviceLightCurveBatch(object):
         out = LightCurveBatch(self.time_host(), self.flux_host(), e, self.n_off.copy(), [dict(m) for m in self.meta])
         if self.d_quality is not None:
             out.quality = self.quality_host()
+        if self.d_cadenceno is not None:
+            out.cadenceno = self.cadenceno_host()
         return out
 
     def _sorted(self):
@@ -319,12 +347,14 @@ class DeviceLightCurveBatch(object):
             _vp(d_e.ptr if d_e is not None else None), _off_ptr(new_off), _vp(d_med.ptr), _vp(self.stream or None)))
         out = self._new(d_t, d_f, d_e, new_off, nan_free=True, is_sorted=self.is_sorted)
         out.median_flux = d_med
-        if self.d_quality is not None:
-            d_q = DeviceBuffer(h, n * 4)
-            cin, cout = (_vp * 1)(self.d_quality.ptr), (_vp * 1)(d_q.ptr)
-            _capi._check(_capi._lib.lk_compact_columns_batch_dev(h._h, B, _off_ptr(self.n_off), _off_ptr(new_off), _vp(self.d_flux.ptr),
-                                                                 1, 4, cin, cout, _vp(self.stream or None)))
-            out.d_quality = d_q
+        for name in ("d_quality", "d_cadenceno"):
+            src = getattr(self, name)
+            if src is not None:
+                d_q = DeviceBuffer(h, n * 4)
+                cin, cout = (_vp * 1)(src.ptr), (_vp * 1)(d_q.ptr)
+                _capi._check(_capi._lib.lk_compact_columns_batch_dev(h._h, B, _off_ptr(self.n_off), _off_ptr(new_off),
+                                                                     _vp(self.d_flux.ptr), 1, 4, cin, cout, _vp(self.stream or None)))
+                setattr(out, name, d_q)
         return out
 
     def remove_nans(self):
@@ -380,8 +410,7 @@ class DeviceLightCurveBatch(object):
                                                            _vp(self.d_flux_err.ptr if self.d_flux_err is not None else None),
                                                            _vp(d_tr.ptr), _vp(d_f.ptr), _vp(d_e.ptr if d_e is not None else None),
                                                            _vp(self.stream or None)))
-        out = self._new(self.d_time, d_f, d_e, self.n_off, nan_free=False, is_sorted=self.is_sorted)
-        out.d_quality = self.d_quality
+        out = self._carry(self._new(self.d_time, d_f, d_e, self.n_off, nan_free=False, is_sorted=self.is_sorted))
         for m in out.meta:
             m["NORMALIZED"] = True
         if return_trend:
@@ -427,6 +456,8 @@ class DeviceLightCurveBatch(object):
             cols.append((self.d_flux_err, 8))
         if self.d_quality is not None:
             cols.append((self.d_quality, 4))
+        if self.d_cadenceno is not None:
+            cols.append((self.d_cadenceno, 4))
         outs = [DeviceBuffer(h, max(n, 1) * eb) for _c, eb in cols]
         cin = (_vp * len(cols))(*[c.ptr for c, _eb in cols])
         cout = (_vp * len(cols))(*[c.ptr for c in outs])
@@ -439,6 +470,7 @@ class DeviceLightCurveBatch(object):
         d_e = next(it) if self.d_flux_err is not None else None
         out = self._new(outs[0], outs[1], d_e, new_off, nan_free=self.nan_free, is_sorted=self.is_sorted)
         out.d_quality = next(it) if self.d_quality is not None else None
+        out.d_cadenceno = next(it) if self.d_cadenceno is not None else None
         return out
 
     def remove_outliers(self, sigma=5.0, sigma_lower=None, sigma_upper=None, return_mask=False, maxiters=5):
@@ -488,7 +520,8 @@ class DeviceLightCurveBatch(object):
             raise ValueError("%s: the design matrix has %d rows, the light curves have %d cadences" % (what, rows, N))
         return N
 
-    def regression_correct(self, X, prior_mu=None, prior_sigma=None, cadence_mask=None, sigma=5, niters=5, to_host=False):
+    def regression_correct(self, X, prior_mu=None, prior_sigma=None, cadence_mask=None, sigma=5, niters=5, to_host=False, rows=None,
+                           cadenceno=None):
         """``RegressionCorrector(lc).correct(X, cadence_mask, sigma, niters)`` (reference regressioncorrector.py:191-279,
         ``propagate_errors=False``) for every target of the batch on ONE shared design matrix: ``X`` is a host array (N, K),
         K <= 64, or a ``DesignMatrix`` / ``DesignMatrixCollection`` (its own priors go to every target unless ``prior_mu`` /
@@ -496,8 +529,27 @@ class DeviceLightCurveBatch(object):
         flux is flux - model, formed on the device; flux_err is unchanged.  ``cadence_mask``: bool (B, N), True = used in the
         fit.  ``to_host=False`` -> (``DeviceLightCurveBatch``, ``DeviceBuffer`` of the B x N outlier bytes, ``DeviceBuffer``
         of the B x K coefficients), nothing synchronised after the input check; ``to_host=True`` -> (corrected[B, N],
-        outlier[B, N] bool, coefficients[B, K])."""
+        outlier[B, N] bool, coefficients[B, K]).
+
+        A RAGGED batch (``from_fits``, ``remove_nans``, ``remove_outliers``, ``select``) is fitted on the same one matrix when
+        the call says which row of ``X`` each cadence uses: ``cadenceno`` = the integer cadence numbers of the Nx rows of ``X``,
+        strictly increasing, matched against the batch's own ``d_cadenceno`` column (``CotrendingBasisVectors.align``: a
+        cadence of a target that is not on the grid is dropped first, the count per target goes to
+        ``meta[b]["CADENCES_NOT_ON_GRID"]`` of the result; a grid row that no target has carries no weight), or ``rows`` =
+        int (sum n,), per target strictly increasing indices into the rows of ``X``.  Per target the numerics are
+        ``RegressionCorrector.correct`` on ``X[rows_b]``.  ``cadence_mask`` is then ragged: bool (sum n,) over the cadences of
+        this batch, or a ``DeviceBuffer`` of that many bytes.  The result is the same triple on the batch's own offsets
+        (outlier bytes (sum n,)); ``to_host=True`` -> (list of corrected[n_b], list of outlier[n_b] bool, coefficients[B, K])."""
         Xa, mu, sg = _design_arrays(X, prior_mu, prior_sigma)
+        if rows is not None or cadenceno is not None:
+            src, d_rows, d_cm, keep = self._aligned(Xa.shape[0], rows, cadenceno, cadence_mask, "regression_correct")
+            B, K = len(src), Xa.shape[1]
+            d_mu = d_sg = None
+            if mu is not None:
+                d_mu, k1 = _upload(src.handle, np.broadcast_to(mu, (B, K)), src.stream)
+                d_sg, k2 = _upload(src.handle, np.broadcast_to(sg, (B, K)), src.stream)
+                keep += [k1, k2]
+            return src._regress_shared_rows(Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, to_host, keep)
         N = self._uniform_n(Xa.shape[0], "regression_correct")
         B, K = len(self), Xa.shape[1]
         d_mu = d_sg = None
@@ -509,16 +561,110 @@ class DeviceLightCurveBatch(object):
             keep += [k1, k2]
         return self._regress_shared(Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, keep)
 
+    def _aligned(self, Nx, rows, cadenceno, cadence_mask, what):
+        """The ragged route's front end -> (batch to fit, d_rows, d_cm, keep).  Every check that needs no device comes first.
+        With ``cadenceno`` the rows come from ``lk_align_rows_batch_dev``; when a target has cadences that are not on the grid
+        the batch (and a ragged ``cadence_mask``) is ``select``-ed down to the matched cadences and aligned again."""
+        n, B = self.n_cadences, len(self)
+        if rows is not None and cadenceno is not None:
+            raise ValueError("%s: pass `rows` or `cadenceno`, not both" % what)
+        if B == 0 or n == 0:
+            raise ValueError("%s needs at least one light curve with cadences" % what)
+        cm = None
+        if cadence_mask is not None and not isinstance(cadence_mask, DeviceBuffer):
+            cm = np.ascontiguousarray(cadence_mask, dtype=np.uint8)
+            if cm.shape != (n,):
+                raise ValueError("%s: with `rows` / `cadenceno` cadence_mask is ragged, one entry per cadence of the batch: "
+                                 "shape (%d,) (got %s)" % (what, n, cm.shape))
+        elif cadence_mask is not None and cadence_mask.nbytes != n:
+            raise ValueError("%s: cadence_mask holds %d bytes, the batch has %d cadences" % (what, cadence_mask.nbytes, n))
+        if rows is not None:
+            r = _cadenceno_array(rows, n, "rows")
+            if r.size and (r.min() < 0 or r.max() >= Nx):
+                raise ValueError("%s: rows must be indices into the %d rows of the design matrix" % (what, Nx))
+        else:
+            grid = _cadenceno_array(cadenceno, Nx, "cadenceno (one per row of the design matrix)")
+            if np.any(np.diff(grid) <= 0):
+                raise ValueError("%s: the grid's cadence numbers must be strictly increasing" % what)
+            if getattr(self, "d_cadenceno", None) is None:
+                raise ValueError("%s(cadenceno=) needs a batch that carries cadence numbers: from_fits of files with a CADENCENO "
+                                 "column, or from_arrays(..., cadenceno=)" % what)
+        h, st, keep = self.handle, _vp(self.stream or None), []
+        if rows is not None:
+            d_rows, k = _upload(h, r, self.stream, np.int32)
+            keep.append(k)
+            src = self
+        else:
+            d_grid, k = _upload(h, grid, self.stream, np.int32)
+            keep += [k, d_grid]
+            src, dropped = self, np.zeros(B, dtype=np.int64)
+            d_rows = DeviceBuffer(h, n * 4)
+            try:
+                _capi._check(_capi._lib.lk_align_rows_batch_dev(h._h, B, _off_ptr(self.n_off), _vp(self.d_cadenceno.ptr), Nx,
+                                                                _vp(d_grid.ptr), _vp(d_rows.ptr), None, st))
+            except ValueError as exc:
+                if "not on the grid" not in str(exc):
+                    raise
+                off_grid = d_rows.download(np.int32, n, stream=self.stream) < 0       # (rows is written before the call fails)
+                dropped = np.diff(np.concatenate([[0], np.cumsum(off_grid, dtype=np.int64)])[self.n_off])
+                src = self.select(off_grid, invert=True)
+                if cm is not None:
+                    cm = np.ascontiguousarray(cm[~off_grid])
+                elif cadence_mask is not None:
+                    cm = np.ascontiguousarray(cadence_mask.download(np.uint8, n, stream=self.stream)[~off_grid])
+                    cadence_mask = None
+                d_rows = DeviceBuffer(h, max(src.n_cadences, 1) * 4)
+                _capi._check(_capi._lib.lk_align_rows_batch_dev(h._h, B, _off_ptr(src.n_off), _vp(src.d_cadenceno.ptr), Nx,
+                                                                _vp(d_grid.ptr), _vp(d_rows.ptr), None, st))
+            if src is self:
+                src = self._carry(self._new(self.d_time, self.d_flux, self.d_flux_err, self.n_off, nan_free=self.nan_free,
+                                            is_sorted=self.is_sorted))
+            for m, c in zip(src.meta, dropped):
+                m["CADENCES_NOT_ON_GRID"] = int(c)
+        d_cm = cadence_mask if isinstance(cadence_mask, DeviceBuffer) else None
+        if cm is not None:
+            d_cm, k = _upload(h, cm, self.stream, np.uint8)
+            keep.append(k)
+        return src, d_rows, d_cm, keep
+
+    def _regress_shared_rows(self, Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, to_host, keep):
+        h, B, K, n = self.handle, len(self), Xa.shape[1], self.n_cadences
+        d_X, k = _upload(h, Xa, self.stream)
+        keep.append(k)
+        d_w, d_model, d_corr, d_outl = DeviceBuffer(h, B * K * 8), DeviceBuffer(h, n * 8), DeviceBuffer(h, n * 8), DeviceBuffer(h, n)
+        _capi._check(_capi._lib.lk_regress_shared_rows_batch_dev(
+            h._h, B, _off_ptr(self.n_off), _vp(d_rows.ptr), Xa.shape[0], K, _vp(d_X.ptr), _vp(self.d_flux.ptr),
+            _vp(self.d_flux_err.ptr if self.d_flux_err is not None else None), _vp(d_cm.ptr if d_cm is not None else None),
+            _vp(d_mu.ptr if d_mu is not None else None), _vp(d_sg.ptr if d_sg is not None else None), float(sigma), int(niters),
+            _vp(d_w.ptr), _vp(d_model.ptr), _vp(d_outl.ptr), None, _vp(self.stream or None)))
+        _capi._check(_capi._lib.lk_subtract_f64_dev(h._h, n, _vp(self.d_flux.ptr), _vp(d_model.ptr), _vp(d_corr.ptr),
+                                                    _vp(self.stream or None)))
+        if to_host:
+            cut = self.n_off[1:-1]
+            corrected = np.split(d_corr.download(np.float64, n, stream=self.stream), cut)
+            outl = np.split(d_outl.download(np.uint8, n, stream=self.stream).astype(bool), cut)
+            return corrected, outl, d_w.download(np.float64, B * K, stream=self.stream).reshape(B, K)
+        out = self._carry(self._new(self.d_time, d_corr, self.d_flux_err, self.n_off, nan_free=self.nan_free, is_sorted=self.is_sorted))
+        out._keep = keep + [d_X, d_rows, d_cm, d_mu, d_sg, d_model, self]
+        return out, d_outl, d_w
+
     def cbv_correct(self, cbvs, cbv_indices=np.arange(1, 9), alpha=1e-20, ext_dm=None, cadence_mask=None, sigma=5, niters=5,
-                    to_host=False):
+                    to_host=False, cadenceno=None):
         """``CBVCorrector(lc, cbvs).correct_gaussian_prior(cbv_indices, alpha, ext_dm, cadence_mask)`` (reference
         cbvcorrector.py:333-395) for every target of the batch: columns [cbvs[:, idx - 1] | ext_dm | 1] shared by all targets
         (``cbvs``: (N, n_vectors), column j = basis vector j + 1; indices 1-based, out-of-range ones dropped, "ALL" accepted),
         prior_mu = 0 and ONE ridge width per target, median(flux_err_b) / sqrt(|alpha|), taken on the device; ``alpha == 0``:
         no prior.  ``alpha`` may also be an array-like of B finite, non-zero penalties, one per target (8 bytes per target go
         up; row b is what the scalar call at ``alpha[b]`` gives, bit for bit); a zero inside an array is a ``ValueError``:
-        "no prior" stays the scalar ``alpha == 0.0``.  Returns what ``regression_correct`` returns."""
+        "no prior" stays the scalar ``alpha == 0.0``.  Returns what ``regression_correct`` returns.  ``cadenceno``: the cadence
+        numbers of the rows of ``cbvs``; the batch may then be ragged and is matched by its own cadence numbers, exactly as
+        ``regression_correct(cadenceno=)`` (the ridge width is the median over the target's own matched cadences)."""
         Xa = _cbv_columns(cbvs, cbv_indices, ext_dm)
+        if cadenceno is not None:
+            alphas = None if np.ndim(alpha) == 0 else _alpha_per_target(alpha, len(self))
+            src, d_rows, d_cm, keep = self._aligned(Xa.shape[0], None, cadenceno, cadence_mask, "cbv_correct")
+            d_mu, d_sg = src._ridge_prior(None, Xa.shape[1], alpha, alphas, keep)
+            return src._regress_shared_rows(Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, to_host, keep)
         N = self._uniform_n(Xa.shape[0], "cbv_correct")
         alphas = None if np.ndim(alpha) == 0 else _alpha_per_target(alpha, len(self))
         keep = []
@@ -534,14 +680,23 @@ class DeviceLightCurveBatch(object):
             raise ValueError("cbv_correct with alpha != 0 needs flux errors (the ridge width is median(flux_err) / sqrt(|alpha|))")
         h, B, st = self.handle, len(self), _vp(self.stream or None)
         d_mu, d_sg = DeviceBuffer(h, B * K * 8), DeviceBuffer(h, B * K * 8)
-        if alphas is None:
-            _capi._check(_capi._lib.lk_ridge_prior_batch_dev(h._h, B, N, K, _vp(self.d_flux_err.ptr), float(alpha), _vp(d_mu.ptr),
-                                                             _vp(d_sg.ptr), st))
-        else:
+        lib = _capi._lib
+        if alphas is not None:
             d_alpha, k = _upload(h, alphas, self.stream)
             keep += [k, d_alpha]
-            _capi._check(_capi._lib.lk_ridge_prior_alphas_batch_dev(h._h, B, N, K, _vp(self.d_flux_err.ptr), _vp(d_alpha.ptr),
-                                                                    _vp(d_mu.ptr), _vp(d_sg.ptr), st))
+        if N is None:       # ragged: the median over each target's own cadences
+            if alphas is None:
+                _capi._check(lib.lk_ridge_prior_rows_batch_dev(h._h, B, _off_ptr(self.n_off), K, _vp(self.d_flux_err.ptr), float(alpha),
+                                                               _vp(d_mu.ptr), _vp(d_sg.ptr), st))
+            else:
+                _capi._check(lib.lk_ridge_prior_rows_alphas_batch_dev(h._h, B, _off_ptr(self.n_off), K, _vp(self.d_flux_err.ptr),
+                                                                      _vp(d_alpha.ptr), _vp(d_mu.ptr), _vp(d_sg.ptr), st))
+        elif alphas is None:
+            _capi._check(lib.lk_ridge_prior_batch_dev(h._h, B, N, K, _vp(self.d_flux_err.ptr), float(alpha), _vp(d_mu.ptr),
+                                                      _vp(d_sg.ptr), st))
+        else:
+            _capi._check(lib.lk_ridge_prior_alphas_batch_dev(h._h, B, N, K, _vp(self.d_flux_err.ptr), _vp(d_alpha.ptr),
+                                                             _vp(d_mu.ptr), _vp(d_sg.ptr), st))
         return d_mu, d_sg
 
     def _regress_shared(self, Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, keep, resident=None):
@@ -572,8 +727,7 @@ class DeviceLightCurveBatch(object):
             corrected = d_corr.download(np.float64, B * N, stream=self.stream).reshape(B, N)
             outl = d_outl.download(np.uint8, B * N, stream=self.stream).reshape(B, N).astype(bool)
             return corrected, outl, d_w.download(np.float64, B * K, stream=self.stream).reshape(B, K)
-        out = self._new(self.d_time, d_corr, self.d_flux_err, self.n_off, nan_free=self.nan_free, is_sorted=self.is_sorted)
-        out.d_quality = self.d_quality
+        out = self._carry(self._new(self.d_time, d_corr, self.d_flux_err, self.n_off, nan_free=self.nan_free, is_sorted=self.is_sorted))
         # scratch and inputs the stream may still be reading: held until the batch is synchronised or dropped
         out._keep = keep + [d_X, d_cm, d_mu, d_sg, d_model, self]
         return out, d_outl, d_w
@@ -1142,7 +1296,7 @@ class DeviceLightCurveBatch(object):
             out["model"] = mdl
         if want_residual:
             out["residual"] = src._new(src.d_time, d_res, src.d_flux_err, src.n_off, nan_free=True, is_sorted=src.is_sorted)
-            out["residual"].d_quality = src.d_quality
+            src._carry(out["residual"])
         return out
 
     def prewhiten(self, frequency, n_signals=3, nterms=1, normalization="amplitude", freq_unit=None, oversample_factor=None,
@@ -2091,6 +2245,16 @@ def _design_arrays(X, prior_mu, prior_sigma):
     if prior_mu is not None:
         prior_mu, prior_sigma = np.asarray(prior_mu, dtype=np.float64), np.asarray(prior_sigma, dtype=np.float64)
     return Xa, prior_mu, prior_sigma
+
+
+def _cadenceno_array(a, n, name):
+    """Integer cadence numbers / row indices -> int32 (n,), C-contiguous; ``ValueError`` for another shape, kind or range."""
+    a = np.asarray(a)
+    if a.shape != (n,) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("%s must be an integer array of shape (%d,) (got %s of shape %s)" % (name, n, a.dtype, a.shape))
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError("%s must fit int32" % name)
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def _alpha_per_target(alpha, B):

@@ -225,6 +225,17 @@ def lightcurve_columns(tab, flux_column=None, quality_bitmask="default", mission
     return desc, int(bitmask), mission
 
 
+def int_column(tab, name="cadenceno"):
+    """(byte offset, TFORM code) of a plain integer column of the table (CADENCENO: what ``CotrendingBasisVectors.align``
+    matches), or None when the table has no such column or it is not a scalar, unscaled J / K / I / B."""
+    if name not in tab.columns:
+        return None
+    off, letter, repeat, scaled = tab.columns[name]
+    if letter not in "JKIB" or repeat != 1 or scaled:
+        return None
+    return int(off), _CODES[letter]
+
+
 def pixel_columns(tab, columns=("flux", "flux_err", "flux_bkg"), quality_bitmask="default", mission=None):
     """Where a target-pixel file keeps TIME, QUALITY and its pixel cubes, and which cadences the reference keeps:
     quality_mask = (QUALITY & bitmask) == 0 (targetpixelfile.py:2120-2122 Kepler / K2, :2794-2797 TESS), TESS also drops

@@ -35,6 +35,7 @@ class LightCurveBatch(object):
             raise ValueError("n_off must be non-decreasing prefix offsets over the arrays")
         self.meta = list(meta) if meta is not None else [{} for _ in range(len(self))]
         self.quality = None   # per-cadence quality flags (set by from_fits; carried through remove_nans / normalize)
+        self.cadenceno = None  # per-cadence cadence numbers (DeviceLightCurveBatch.to_host; carried like the flags)
 
     @classmethod
     def from_lightcurves(cls, lcs, pinned=False):
@@ -92,6 +93,8 @@ class LightCurveBatch(object):
                 raise RuntimeError("quality flags out of step with the ingest kernel (kept %d of %d cadences, expected %d)"
                                    % (len(t), len(self.flux), int(keep.sum())))
             out.quality = np.ascontiguousarray(np.asarray(self.quality)[keep])
+        if self.cadenceno is not None:
+            out.cadenceno = np.ascontiguousarray(np.asarray(self.cadenceno)[~np.isnan(self.flux)])
         return out
 
     def remove_nans(self, device=0):
@@ -119,6 +122,8 @@ class LightCurveBatch(object):
         out = LightCurveBatch(self.time[keep], self.flux[keep], self.flux_err[keep], off, [dict(m) for m in self.meta])
         if self.quality is not None:
             out.quality = np.ascontiguousarray(np.asarray(self.quality)[keep])
+        if self.cadenceno is not None:
+            out.cadenceno = np.ascontiguousarray(np.asarray(self.cadenceno)[keep])
         return (out, mask) if return_mask else out
 
     def create_transit_mask(self, period, transit_time, duration, planet_off=None, device=0):

@@ -68,7 +68,13 @@ periodogram pass alone.  Results: profiles/seismology_walls.txt.
 `sff`: the SFF correction of `LK_WALLS_B` (default 1000) targets x `LK_WALLS_N` (default 3500) cadences with windows = 20 (one set
 of window points, chosen once, for both routes), in ONE process, the routes alternating, `LK_WALLS_REPS` (default 2) times after
 one warm-up.  R the resident call `batch.sff_correct(...)`; H the host route: `to_host()`, `SFFCorrector(lc).correct(...)` per
-target, `from_arrays`.  Written to profiles/sff_walls.txt."""
+target, `from_arrays`.  Written to profiles/sff_walls.txt.
+
+`cbvragged`: the CBV correction of a RAGGED batch, `LK_WALLS_B` (default 1000) targets on a grid of `LK_WALLS_N` (default
+20000) cadences with about 3 % of them missing per target, `LK_WALLS_K` (default 17) columns, in ONE process, the routes
+alternating, `LK_WALLS_REPS` (default 2) times after one warm-up.  S `from_arrays(cadenceno=)` ->
+`cbv_correct(cadenceno=grid)`: one shared matrix; T the route a ragged batch had before: `X[rows_b]` per target ->
+`regression_correct_batch` on the stacked copies.  Written to profiles/cbvragged_walls.txt."""
 import cProfile
 import io
 import os
@@ -689,6 +695,63 @@ def sff():
     sys.stdout.flush()
 
 
+def cbvragged():
+    from lightkurve_amd import _capi, batch
+    from lightkurve_amd.correctors import DesignMatrix
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    from lightkurve_amd.lightcurve import LightCurve
+    B, N, K = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000"), ("LK_WALLS_K", "17")))
+    reps, alpha = int(os.environ.get("LK_WALLS_REPS", "2")), 1e-4
+    rng = np.random.default_rng(23)
+    t = np.linspace(0.0, 27.0, N)
+    cbvs = np.column_stack([np.sin(2 * np.pi * t * rng.uniform(0.05, 3.0) + rng.uniform(0, 6)) for _ in range(K - 1)])
+    grid = 100000 + np.arange(N, dtype=np.int32)
+    rows = [np.flatnonzero(rng.random(N) >= 0.03).astype(np.int32) for _ in range(B)]      # ~3 % of the cadences missing per target
+    n_off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    allrows = np.concatenate(rows)
+    ntot = int(n_off[-1])
+    err = rng.uniform(0.5, 2.0, ntot) * 2e-4
+    w = rng.normal(0, 1e-3, (B, K - 1))
+    flux = np.concatenate([1.0 + cbvs[r] @ w[b] for b, r in enumerate(rows)]) + rng.standard_normal(ntot) * err
+    time_, cad = t[allrows], grid[allrows]
+    sync = _capi.Handle.get(0).synchronize
+
+    def shared():
+        dev = DeviceLightCurveBatch.from_arrays(time_, flux, err, n_off, cadenceno=cad)
+        return dev.cbv_correct(cbvs, cbv_indices="ALL", alpha=alpha, cadenceno=grid)[0]
+
+    def stacked():
+        X = np.column_stack([cbvs, np.ones(N)])
+        lcs, dms = [], []
+        for b, r in enumerate(rows):
+            a, z = int(n_off[b]), int(n_off[b + 1])
+            lcs.append(LightCurve(time=time_[a:z], flux=flux[a:z], flux_err=err[a:z]))
+            dms.append(DesignMatrix(X[r], name="cbv", prior_mu=np.zeros(K), prior_sigma=np.full(K, np.median(err[a:z]) / np.sqrt(alpha))))
+        return batch.regression_correct_batch(lcs, dms)[0]
+
+    fns = {"S": shared, "T": stacked}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    sync()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(lambda: (fn(), sync()))[0])
+    a, b = first["S"].flux_host(), np.concatenate(first["T"])
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    lines = ["CBV correction of a ragged batch: %d targets on a grid of %d cadences (%d kept in all, %.1f %% missing), K = %d columns, "
+             "alpha = %g" % (B, N, ntot, 100.0 * (1 - ntot / (B * N)), K, alpha),
+             "  S    from_arrays(cadenceno=) -> cbv_correct(cadenceno=grid): ONE %.1f MB matrix goes up              %s"
+             % (N * K * 8 / 1e6, spread(ts["S"])),
+             "  T    X[rows_b] per target -> regression_correct_batch: %.2f GB of stacked copies go up             %s"
+             % (ntot * K * 8 / 1e9, spread(ts["T"])),
+             "  max |S - T| / median flux: %.2e" % (np.max(np.abs(a - b)) / np.median(flux)),
+             "  T / S = %.1f" % (med["T"] / med["S"])]
+    print("\n".join(lines))
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "cbvragged_walls.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    sys.stdout.flush()
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -716,6 +779,8 @@ def main():
         seismology()
     if "sff" in which:
         sff()
+    if "cbvragged" in which:
+        cbvragged()
     if "flatten" in which:
         lcs = []
         for i in range(1000):
