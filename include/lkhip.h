@@ -670,6 +670,49 @@ int lk_underfit_rows_prepare_dev(lk_handle *h, int Bn, int N, const double *flux
 int lk_underfit_against_rows_batch_dev(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int Bn,
                                        const void *rows, int M, const int32_t *neighbors, double *corr, double *metric,
                                        void *stream);
+/* The same metric for a RAGGED batch on a grid of Nx cadences.  Light curve b holds n_off[b + 1] - n_off[b] cadences (0 .. Nx),
+ * its cadence i on grid row rows[n_off[b] + i]: int32 (sum n), per light curve strictly increasing indices into [0, Nx), what
+ * lk_align_rows_batch returns.  flux: (sum n), NaN-free.  cadence_mask: (sum n) bytes, non-zero = used, or NULL = all.  A light
+ * curve is PRESENT at a grid row when it has that cadence and its own mask entry there is set.  med_b = numpy.median of its flux
+ * over its present cadences and z_b[r] = flux / med_b - 1.0 there.  Per target t, C_t = the grid rows where t and every valid
+ * neighbour of t are present (the reference drops a cadence any column lacks), n_t = |C_t|, and with G_t(a,b) = the sum of
+ * z_a[r] z_b[r] over r in C_t:
+ *   corr[t][p]  = G_t(t,j) / sqrt(G_t(t,t) G_t(j,j)) for j = neighbors[t][p] (0 when either self-product is 0; NaN at padding),
+ *                 B x M or NULL;
+ *   n_common[t] = n_t, int32 B or NULL;
+ *   metric[t]   = 2 / (1 + exp(scale(n_t) * sum_p |corr[t][p]|^3 / (m + 1))) with the scale above at n = n_t; 1.0 when m == 0.
+ * n_t < 2 (with m > 0): metric[t] and every corr[t][p] are NaN; that is no error, since with a mask in device memory the count is
+ * not known to the host.  G_t is summed in the order given above with i = the grid row (step r / 128, lane (r / 2) % 64, component
+ * r % 2), the elements outside C_t replaced by 0.0: when every light curve has every grid row and cadence_mask is NULL, metric and
+ * corr are the bits of lk_underfit_neighbors_batch_dev on the same flux; a target's result does not depend on B, on rows it does
+ * not list, on a neighbour's position in its list or on the run; no atomics.  B >= 1, B <= 65535, 1 <= Nx <= 245760, M >= 0
+ * (LK_EINVAL otherwise).  The host flavour checks rows and every neighbour index on the host (as lk_regress_shared_rows_batch and
+ * lk_underfit_neighbors_batch do).  The _dev flavours treat any index outside [0, B) (or [0, Bn)) as padding; they check rows on
+ * the device and wait on `stream` ONCE, for the 4 bytes of that check (LK_EINVAL names the first offending light curve), before
+ * the prepare pass is queued; nothing else is waited for, and the results are ordered on `stream` like any kernel's.  n_off_host
+ * is read before the call returns.  Scratch in the handle's arena: B x Nx int32 (the inverse map) + B x P doubles + B x P / 64
+ * words + Nx + 1 doubles, P = ceil(Nx / 128) x 128.
+ * lk_underfit_grid_rows_prepare_dev writes Bn light curves of ANOTHER ragged array (their own n_off_host / rows on the same grid;
+ * cadence_mask usually NULL) into `block`, a 16-byte aligned device block of the caller's of lk_underfit_grid_rows_bytes(Bn, Nx)
+ * bytes: the Bn z rows on the grid layout (P doubles each, 0.0 at absent rows), then their presence bitmasks (P / 64 64-bit words
+ * each, bit r % 64 of word r / 64 = present at grid row r).  lk_underfit_grid_against_rows_batch_dev prepares only the B targets
+ * and runs the pair pass against `block` (prepared with the same Nx); neighbors then index [0, Bn) and a target's own row number
+ * is a neighbour like any other.  With the block prepared from the batch itself the results are the bits of
+ * lk_underfit_grid_neighbors_batch_dev.  Both wait once for their own check of rows, as above. */
+int lk_underfit_grid_neighbors_batch(lk_handle *h, int B, const int64_t *n_off, const int32_t *rows, int Nx, const double *flux,
+                                     const uint8_t *cadence_mask, int M, const int32_t *neighbors, double *corr, int32_t *n_common,
+                                     double *metric);
+int lk_underfit_grid_neighbors_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx,
+                                         const double *flux, const uint8_t *cadence_mask, int M, const int32_t *neighbors,
+                                         double *corr, int32_t *n_common, double *metric, void *stream);
+int lk_underfit_grid_rows_bytes(int Bn, int Nx, int64_t *bytes);
+int lk_underfit_grid_rows_prepare_dev(lk_handle *h, int Bn, const int64_t *n_off_host, const int32_t *rows, int Nx,
+                                      const double *flux_nb, const uint8_t *cadence_mask, void *block, int64_t block_bytes,
+                                      void *stream);
+int lk_underfit_grid_against_rows_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx,
+                                            const double *flux, const uint8_t *cadence_mask, int Bn, const void *block, int M,
+                                            const int32_t *neighbors, double *corr, int32_t *n_common, double *metric,
+                                            void *stream);
 
 /* ---- Over-fitting goodness metric of B targets (reference src/lightkurve/correctors/metrics.py:24-138
  * overfit_metric_lombscargle, as CBVCorrector.over_fitting_metric calls it on lc[cadence_mask]).  time, flux_orig, flux_corr,
@@ -727,6 +770,41 @@ int lk_overfit_session_begin_dev(lk_handle *h, int B, int N, const double *time,
 int lk_overfit_session_eval_dev(lk_handle *h, int B, int N, const double *flux_corr, const double *err_corr, int n,
                                 const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, void *session,
                                 int64_t session_bytes, double *metric, void *stream);
+/* The over-fitting metric and its session for a RAGGED batch, on the batch's own offsets.  Each call is its uniform namesake with
+ * (N, n, keep_idx) replaced by
+ *   n_off_host: B + 1 int64, target b holds cadences [n_off[b], n_off[b + 1]) of time / flux_orig / flux_corr / err_corr (sum n);
+ *   keep_idx:   int32 (sum kept), target-relative ascending indices of the kept cadences of every target, packed by k_off_host;
+ *               NULL = all cadences;
+ *   k_off_host: the B + 1 offsets into keep_idx (NULL, or n_off_host itself, when keep_idx is NULL).
+ * lk_overfit_scratch_rows_bytes / lk_overfit_session_rows_bytes take k_off_host alone (the batch's own offsets when all cadences
+ * are kept).  Per target the arithmetic, every summation order and the Philox counter (pair of kept cadences OF THAT TARGET,
+ * sample, first_target + b, stream_id) are the uniform call's: target b gives the bits of the uniform call on a one-target batch
+ * that holds its kept cadences with first_target + b as first_target, and a uniform batch gives the bits of the uniform entry
+ * points.  The block holds what the uniform block holds with sum kept in place of B n, then the two offset tables (2 (B + 1)
+ * int64).  Every target needs at least three kept cadences: LK_EINVAL names the first that has fewer.  The host flavour also
+ * checks keep_idx.  Both offset tables are read before a call returns; session_begin_rows puts them into the block and
+ * session_eval_rows reads them there, so an evaluation must be given begin's offsets (they size its plan and its periodogram
+ * launch).  The _dev calls enqueue on `stream` and add no synchronisation to the LS launcher's own. */
+int lk_overfit_scratch_rows_bytes(int B, const int64_t *k_off_host, int64_t M, int n_samples, int64_t max_scratch_bytes,
+                                  int64_t *bytes, int *samples_per_round);
+int lk_overfit_metric_rows_batch(lk_handle *h, int B, const int64_t *n_off, const double *time, const double *flux_orig,
+                                 const double *flux_corr, const double *err_corr, const int32_t *keep_idx, const int64_t *k_off,
+                                 double f0, double df, int64_t M, int n_samples, uint64_t seed, int64_t first_target,
+                                 int64_t stream_id, int64_t max_scratch_bytes, double *metric);
+int lk_overfit_metric_rows_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
+                                     const double *flux_corr, const double *err_corr, const int32_t *keep_idx,
+                                     const int64_t *k_off_host, double f0, double df, int64_t M, int n_samples, uint64_t seed,
+                                     int64_t first_target, int64_t stream_id, void *scratch, int64_t scratch_bytes, double *metric,
+                                     void *stream);
+int lk_overfit_session_rows_bytes(int B, const int64_t *k_off_host, int64_t M, int n_samples, int64_t max_scratch_bytes,
+                                  int64_t *bytes, int *samples_per_round);
+int lk_overfit_session_begin_rows_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
+                                      const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
+                                      int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id, void *session,
+                                      int64_t session_bytes, void *stream);
+int lk_overfit_session_eval_rows_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *flux_corr, const double *err_corr,
+                                     const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
+                                     int n_samples, void *session, int64_t session_bytes, double *metric, void *stream);
 /* out[b][c] = the standard normal of (target first_target + b, sample k, kept cadence c), B x n float64 on the device (16-byte
  * aligned): the generator of lk_overfit_metric_batch on its own. */
 int lk_overfit_noise_batch_dev(lk_handle *h, int B, int n, int k, uint64_t seed, int64_t first_target, int64_t stream_id,

@@ -218,6 +218,15 @@ SIGNATURES = [
      [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int64, _vp]),
     ("lk_underfit_against_rows_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    ("lk_underfit_grid_neighbors_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_i32p, ctypes.c_int, _c_dp, _c_u8p, ctypes.c_int, _c_i32p, _c_dp, _c_i32p, _c_dp]),
+    ("lk_underfit_grid_neighbors_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_underfit_grid_rows_bytes", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    ("lk_underfit_grid_rows_prepare_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int64, _vp]),
+    ("lk_underfit_grid_against_rows_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     ("lk_overfit_scratch_bytes", ctypes.c_int,
      [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
       ctypes.POINTER(ctypes.c_int)]),
@@ -227,6 +236,22 @@ SIGNATURES = [
     ("lk_overfit_metric_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
       ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp]),
+    ("lk_overfit_scratch_rows_bytes", ctypes.c_int,
+     [ctypes.c_int, _c_ip, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]),
+    ("lk_overfit_metric_rows_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_dp, _c_i32p, _c_ip, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
+      ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _c_dp]),
+    ("lk_overfit_metric_rows_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _vp, _vp, _c_ip, ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.c_int,
+      ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp]),
+    ("lk_overfit_session_rows_bytes", ctypes.c_int,
+     [ctypes.c_int, _c_ip, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]),
+    ("lk_overfit_session_begin_rows_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _c_ip, ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.c_int,
+      ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int64, _vp]),
+    ("lk_overfit_session_eval_rows_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _c_ip, ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.c_int, _vp,
+      ctypes.c_int64, _vp, _vp]),
     ("lk_overfit_session_bytes", ctypes.c_int,
      [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
       ctypes.POINTER(ctypes.c_int)]),
@@ -1073,6 +1098,41 @@ def underfit_neighbors_batch(flux, neighbors, cadence_mask=None, device=0):
     return dict(metric=metric, correlations=corr)
 
 
+UNDERFIT_GRID_MAX_NX = 245760   # the largest cadence grid of lk_underfit_grid_* (include/lkhip.h)
+
+
+def underfit_grid_neighbors_batch(flux, n_off, rows, Nx, neighbors, cadence_mask=None, device=0):
+    """The under-fitting metric of B RAGGED light curves on a grid of ``Nx`` cadences (``lk_underfit_grid_neighbors_batch``):
+    ``flux`` packed (sum n,) by ``n_off``, NaN-free; ``rows`` int (sum n,) = the grid row of each cadence, per target strictly
+    increasing (``align_rows_batch``); ``neighbors`` int (B, M), -1 = padding; ``cadence_mask`` (sum n,) bool, True = used.
+    Per target the dots run over the grid rows the target and all of its neighbours have.  Returns dict(metric[B],
+    correlations[B, M] (NaN at padding), n_common[B]); fewer than two common cadences: NaN."""
+    flux = _f64(flux)
+    if flux.ndim != 1:
+        raise ValueError("flux must be packed 1-D (sum n,) (got shape %s)" % (flux.shape,))
+    ntot = flux.size
+    n_off = _offsets(n_off, ntot)
+    B, Nx = n_off.size - 1, int(Nx)
+    if B < 1 or Nx < 1:
+        raise ValueError("need at least one light curve and one grid row (got B=%d, Nx=%d)" % (B, Nx))
+    rows = _i32(rows, ntot, "rows")
+    nb = underfit_arguments(B, max(Nx, 2), neighbors)[0]
+    cm = None if cadence_mask is None else np.ascontiguousarray(cadence_mask, dtype=np.uint8)
+    if cm is not None and cm.shape != (ntot,):
+        raise ValueError("cadence_mask must have one entry per cadence (got shape %s, need (%d,))" % (cm.shape, ntot))
+    if np.isnan(flux).any():
+        raise ValueError("the under-fitting metric needs NaN-free flux: drop the NaN cadences of every target first (remove_nans())")
+    M = nb.shape[1]
+    h = Handle.get(device)
+    metric = np.empty(B, dtype=np.float64)
+    corr = np.empty((B, M), dtype=np.float64)
+    n_common = np.empty(B, dtype=np.int32)
+    _check(_lib.lk_underfit_grid_neighbors_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(rows, _c_i32p), Nx, _ptr(flux), _ptr(cm, _c_u8p), M,
+                                                 _ptr(nb if M else None, _c_i32p), _ptr(corr if M else None),
+                                                 _ptr(n_common, _c_i32p), _ptr(metric)))
+    return dict(metric=metric, correlations=corr, n_common=n_common)
+
+
 # --------------------------------------------------------------------------------------------- over-fitting metric
 OVERFIT_SCRATCH_DEFAULT = 4 << 30   # LK_OVERFIT_SCRATCH_DEFAULT in include/lkhip.h
 
@@ -1160,6 +1220,73 @@ def overfit_metric_batch(time, flux, flux_corrected, flux_err_corrected, frequen
     _check(_lib.lk_overfit_metric_batch(h._h, B, N, _ptr(t), _ptr(y0), _ptr(y1), _ptr(e1), n, _ptr(keep_idx, _c_i32p), grid[0],
                                         grid[1], grid[2], int(n_samples), int(seed), int(first_target), int(stream_id),
                                         int(max_scratch_bytes or 0), _ptr(metric)))
+    return metric
+
+
+def overfit_rows_arguments(n_off, n_samples=10, cadence_mask=None, frequency=None, seed=0, first_target=0, stream_id=0):
+    """``overfit_arguments`` for a ragged batch with offsets ``n_off``: ``cadence_mask`` (bool (sum n,), True = used) ->
+    (keep_idx: target-relative ascending int32 indices packed by k_off, or None for all cadences; k_off int64 (B + 1,); grid or
+    None).  ``ValueError`` naming the first target with fewer than three kept cadences."""
+    n_off = np.ascontiguousarray(n_off, dtype=np.int64)
+    B, ntot = n_off.size - 1, int(n_off[-1])
+    overfit_arguments(3, n_samples, None, None, seed, first_target, stream_id, B)
+    keep_idx, k_off = None, n_off
+    if cadence_mask is not None:
+        cm = np.asarray(cadence_mask)
+        if cm.shape != (ntot,):
+            raise ValueError("cadence_mask of a ragged batch must be one bool per cadence of the batch, shape (%d,) (got shape %s)"
+                             % (ntot, cm.shape))
+        idx = np.nonzero(cm.astype(bool))[0]
+        tgt = np.searchsorted(n_off, idx, side="right") - 1
+        keep_idx = np.ascontiguousarray(idx - n_off[tgt], dtype=np.int32)
+        k_off = np.concatenate([[0], np.cumsum(np.bincount(tgt, minlength=B)[:B])]).astype(np.int64)
+    few = np.nonzero(np.diff(k_off) < 3)[0]
+    if len(few):
+        raise ValueError("target %d: the over-fitting metric needs at least three kept cadences (got %d)"
+                         % (few[0], np.diff(k_off)[few[0]]))
+    return keep_idx, k_off, (None if frequency is None else overfit_grid(frequency))
+
+
+def overfit_scratch_rows_bytes(k_off, M, n_samples, max_scratch_bytes=None):
+    """(bytes, samples per round) of the caller-owned block of ``lk_overfit_metric_rows_batch_dev`` / of a rows session."""
+    load_library()
+    k_off = np.ascontiguousarray(k_off, dtype=np.int64)
+    nbytes, rounds = ctypes.c_int64(0), ctypes.c_int(0)
+    _check(_lib.lk_overfit_scratch_rows_bytes(k_off.size - 1, _ptr(k_off, _c_ip), int(M), int(n_samples), int(max_scratch_bytes or 0),
+                                              ctypes.byref(nbytes), ctypes.byref(rounds)))
+    return nbytes.value, rounds.value
+
+
+def overfit_metric_rows_batch(time, flux, flux_corrected, flux_err_corrected, n_off, frequency=None, n_samples=10, cadence_mask=None,
+                              seed=0, first_target=0, stream_id=0, device=0, max_scratch_bytes=None):
+    """The over-fitting goodness metric of B RAGGED light curves packed by ``n_off`` (``lk_overfit_metric_rows_batch``): ``time``,
+    ``flux``, ``flux_corrected``, ``flux_err_corrected`` (sum n,), NaN-free flux; ``cadence_mask`` bool (sum n,), True = used;
+    ``frequency`` None = the default grid of target 0's kept times -> metric[B]."""
+    t = _f64(time)
+    if t.ndim != 1:
+        raise ValueError("time must be packed 1-D (sum n,) (got shape %s)" % (t.shape,))
+    n_off = _offsets(n_off, t.size)
+    if n_off.size < 2:
+        raise ValueError("need at least one light curve")
+    y0, y1 = _f64(flux), _f64(flux_corrected)
+    if flux_err_corrected is None:
+        raise ValueError("the over-fitting metric needs the flux errors of the corrected light curves")
+    e1 = _f64(np.broadcast_to(np.asarray(flux_err_corrected, dtype=np.float64), t.shape))
+    if y0.shape != t.shape or y1.shape != t.shape:
+        raise ValueError("time, flux and flux_corrected must have one shape (got %s, %s and %s)" % (t.shape, y0.shape, y1.shape))
+    keep_idx, k_off, grid = overfit_rows_arguments(n_off, n_samples, cadence_mask, frequency, seed, first_target, stream_id)
+    if np.isnan(y0).any() or np.isnan(y1).any():
+        raise ValueError("the over-fitting metric needs NaN-free flux: drop the NaN cadences of every target first (remove_nans())")
+    if grid is None:
+        t0 = t[:n_off[1]]
+        grid = overfit_grid(overfit_default_grid(t0 if keep_idx is None else t0[keep_idx[:k_off[1]]]))
+    h = Handle.get(device)
+    B = n_off.size - 1
+    metric = np.empty(B, dtype=np.float64)
+    _check(_lib.lk_overfit_metric_rows_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(t), _ptr(y0), _ptr(y1), _ptr(e1), _ptr(keep_idx, _c_i32p),
+                                             _ptr(k_off if keep_idx is not None else None, _c_ip), grid[0], grid[1], grid[2],
+                                             int(n_samples), int(seed), int(first_target), int(stream_id),
+                                             int(max_scratch_bytes or 0), _ptr(metric)))
     return metric
 
 

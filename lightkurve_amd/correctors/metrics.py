@@ -13,7 +13,8 @@ from ..batch import lombscargle_batch
 from ..lightcurve import LightCurve
 
 __all__ = ["overfit_metric_lombscargle", "overfit_metric_lombscargle_batch", "underfit_metric_neighbors",
-           "underfit_metric_batch", "nearest_neighbors", "overfit_metric_batch"]
+           "underfit_metric_batch", "nearest_neighbors", "overfit_metric_batch", "underfit_metric_ragged_batch",
+           "overfit_metric_ragged_batch"]
 
 
 def _prepared(lc):
@@ -165,6 +166,78 @@ def underfit_metric_batch(flux, neighbors, cadence_mask=None, device=0, return_c
     from .. import _capi
     r = _capi.underfit_neighbors_batch(flux, neighbors, cadence_mask=cadence_mask, device=device)
     return (r["metric"], r["correlations"]) if return_correlations else r["metric"]
+
+
+def underfit_metric_ragged_batch(flux_list, cadenceno_list, grid, neighbors, cadence_mask_list=None, device=0,
+                                 return_correlations=False, return_common=False):
+    """``underfit_metric_neighbors`` for B host light curves that do NOT share all their cadences, in ONE GPU call
+    (``lk_underfit_grid_neighbors_batch``): ``flux_list[b]`` (n_b,; NaN-free) at the integer cadence numbers
+    ``cadenceno_list[b]`` (strictly increasing), ``grid`` the strictly increasing cadence numbers of the field (a cadence that is
+    not on it is dropped, as ``CotrendingBasisVectors.align`` does); ``neighbors`` int (B, M) as in ``underfit_metric_batch``;
+    ``cadence_mask_list[b]`` bool (n_b,), True = used.  As in the reference, a target is compared with its neighbours on the
+    cadences that it and ALL of them have (``n_common``); fewer than two: NaN.  Returns metric[B], then correlations[B, M]
+    (``return_correlations``) and n_common[B] (``return_common``).  A resident batch has the same call as
+    ``DeviceLightCurveBatch.under_fitting_metric(cadenceno=)``: the same kernels, the same bits."""
+    from .. import _capi
+    grid = np.asarray(grid)
+    if grid.ndim != 1 or grid.size < 1 or not np.issubdtype(grid.dtype, np.integer) or np.any(np.diff(grid) <= 0):
+        raise ValueError("grid must be a 1-D array of strictly increasing integer cadence numbers")
+    B = len(flux_list)
+    if B < 1 or len(cadenceno_list) != B or (cadence_mask_list is not None and len(cadence_mask_list) != B):
+        raise ValueError("flux_list, cadenceno_list (and cadence_mask_list) must hold one entry per light curve, at least one")
+    flux, rows, masks, n_off = [], [], [], [0]
+    for b in range(B):
+        f = np.asarray(flux_list[b], dtype=np.float64)
+        c = np.asarray(cadenceno_list[b])
+        if f.ndim != 1 or c.shape != f.shape or not np.issubdtype(c.dtype, np.integer):
+            raise ValueError("light curve %d: flux (n,) and integer cadenceno (n,) must match (got %s and %s)" % (b, f.shape, c.shape))
+        if np.any(np.diff(c) <= 0):
+            raise ValueError("light curve %d: its cadence numbers must be strictly increasing" % b)
+        m = np.ones(f.size, dtype=bool) if cadence_mask_list is None else np.asarray(cadence_mask_list[b], dtype=bool)
+        if m.shape != f.shape:
+            raise ValueError("light curve %d: cadence_mask must have one entry per cadence (got %s)" % (b, m.shape))
+        r = np.searchsorted(grid, c)
+        on = (r < grid.size) & (grid[np.minimum(r, grid.size - 1)] == c)
+        flux.append(f[on])
+        rows.append(r[on])
+        masks.append(m[on])
+        n_off.append(n_off[-1] + int(on.sum()))
+    res = _capi.underfit_grid_neighbors_batch(np.concatenate(flux), n_off, np.concatenate(rows).astype(np.int32), grid.size, neighbors,
+                                              cadence_mask=None if cadence_mask_list is None else np.concatenate(masks),
+                                              device=device)
+    out = (res["metric"],)
+    if return_correlations:
+        out += (res["correlations"],)
+    if return_common:
+        out += (res["n_common"],)
+    return out if len(out) > 1 else out[0]
+
+
+def overfit_metric_ragged_batch(time_list, flux_list, flux_corrected_list, flux_err_corrected_list, frequency=None, n_samples=10,
+                                cadence_mask_list=None, seed=0, first_target=0, stream_id=0, device=0, max_scratch_bytes=None):
+    """``overfit_metric_batch`` for B host light curves of DIFFERENT lengths in ONE GPU call (``lk_overfit_metric_rows_batch``):
+    per target ``time_list[b]``, ``flux_list[b]`` (the original), ``flux_corrected_list[b]``, ``flux_err_corrected_list[b]``
+    (n_b,; NaN-free flux) and ``cadence_mask_list[b]`` bool (n_b,), True = used; ``frequency`` [1/d]: a regular grid shared by the
+    targets, None = the default grid of target 0's kept times.  The noise of target b is that of the uniform call with
+    ``first_target + b``.  Returns metric[B].  A resident batch has the same call as
+    ``DeviceLightCurveBatch.over_fitting_metric``: the same kernels, the same bits."""
+    from .. import _capi
+    B = len(time_list)
+    lists = (flux_list, flux_corrected_list, flux_err_corrected_list) + (() if cadence_mask_list is None else (cadence_mask_list,))
+    if B < 1 or any(len(x) != B for x in lists):
+        raise ValueError("every list must hold one entry per light curve, at least one")
+    t = [np.asarray(a, dtype=np.float64).reshape(-1) for a in time_list]
+    for b in range(B):
+        for x in lists:
+            if np.shape(x[b]) != t[b].shape:
+                raise ValueError("light curve %d: every array must have its %d cadences (got shape %s)" % (b, t[b].size, np.shape(x[b])))
+    n_off = np.concatenate([[0], np.cumsum([a.size for a in t])]).astype(np.int64)
+    cat = lambda x: np.concatenate([np.asarray(a).reshape(-1) for a in x])
+    return _capi.overfit_metric_rows_batch(cat(t), cat(flux_list), cat(flux_corrected_list), cat(flux_err_corrected_list), n_off,
+                                           frequency=frequency, n_samples=n_samples,
+                                           cadence_mask=None if cadence_mask_list is None else cat(cadence_mask_list), seed=seed,
+                                           first_target=first_target, stream_id=stream_id, device=device,
+                                           max_scratch_bytes=max_scratch_bytes)
 
 
 def nearest_neighbors(x, y, n_neighbors=50, chunk=1024):

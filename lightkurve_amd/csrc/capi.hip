@@ -856,6 +856,73 @@ int lk_underfit_against_rows_batch_dev(lk_handle *h, int B, int N, const double 
                                             static_cast<hipStream_t>(stream));
 }
 
+// ragged targets on a cadence grid
+int lk_underfit_grid_neighbors_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx,
+                                         const double *flux, const uint8_t *cadence_mask, int M, const int32_t *neighbors,
+                                         double *corr, int32_t *n_common, double *metric, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::underfit_grid_neighbors_launch(h, B, n_off_host, rows, Nx, flux, cadence_mask, M, neighbors, corr, n_common, metric,
+                                              static_cast<hipStream_t>(stream));
+}
+
+int lk_underfit_grid_neighbors_batch(lk_handle *h, int B, const int64_t *n_off, const int32_t *rows, int Nx, const double *flux,
+                                     const uint8_t *cadence_mask, int M, const int32_t *neighbors, double *corr, int32_t *n_common,
+                                     double *metric) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 1 && n_off != nullptr, "B must be >= 1 (got %d) and n_off given", B);
+    LK_REQUIRE(Nx >= 1 && n_off[0] == 0 && n_off[B] >= 0, "bad shapes");
+    LK_REQUIRE(M >= 0, "M must be >= 0 (got %d)", M);
+    LK_REQUIRE(rows && flux && metric, "NULL buffer");
+    LK_REQUIRE(M == 0 || neighbors != nullptr, "neighbors is NULL with M=%d", M);
+    for (int b = 0; b < B; ++b) {
+        LK_REQUIRE(n_off[b + 1] >= n_off[b], "n_off must not decrease (target %d)", b);
+        for (int64_t i = n_off[b]; i < n_off[b + 1]; ++i)
+            LK_REQUIRE(rows[i] >= 0 && rows[i] < Nx && (i == n_off[b] || rows[i] > rows[i - 1]),
+                       "target %d: rows must be strictly increasing indices into the %d rows of the grid", b, Nx);
+        for (int p = 0; p < M; ++p) {
+            const int32_t j = neighbors[(size_t)b * M + p];
+            LK_REQUIRE(j == -1 || (j >= 0 && j < B), "neighbors[%d][%d]=%d: a neighbour is -1 (padding) or an index in [0, %d)", b, p,
+                       (int)j, B);
+            LK_REQUIRE(j != b, "neighbors[%d][%d]=%d: a target cannot be its own neighbour", b, p, (int)j);
+        }
+    }
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B], nm = (size_t)B * M;
+    const int32_t *drows, *dnbr;
+    const double *dflux;
+    const uint8_t *dcm;
+    double *dcorr, *dmetric;
+    int32_t *dnc;
+    lk::StagedCall io(h);
+    int rc = io.in(drows, rows, ntot).in(dflux, flux, ntot).in(dcm, cadence_mask, ntot).in(dnbr, M ? neighbors : nullptr, nm)
+                 .out(dcorr, M ? corr : nullptr, nm).out(dnc, n_common, (size_t)B).out(dmetric, metric, (size_t)B).stage();
+    if (rc) return rc;
+    rc = lk::underfit_grid_neighbors_launch(h, B, n_off, drows, Nx, dflux, dcm, M, dnbr, dcorr, dnc, dmetric, nullptr);
+    return rc ? rc : io.finish();
+}
+
+int lk_underfit_grid_rows_bytes(int Bn, int Nx, int64_t *bytes) { return lk::underfit_grid_rows_bytes(Bn, Nx, bytes); }
+
+int lk_underfit_grid_rows_prepare_dev(lk_handle *h, int Bn, const int64_t *n_off_host, const int32_t *rows, int Nx,
+                                      const double *flux_nb, const uint8_t *cadence_mask, void *block, int64_t block_bytes,
+                                      void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::underfit_grid_rows_prepare_launch(h, Bn, n_off_host, rows, Nx, flux_nb, cadence_mask, block, block_bytes,
+                                                 static_cast<hipStream_t>(stream));
+}
+
+int lk_underfit_grid_against_rows_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx,
+                                            const double *flux, const uint8_t *cadence_mask, int Bn, const void *block, int M,
+                                            const int32_t *neighbors, double *corr, int32_t *n_common, double *metric,
+                                            void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::underfit_grid_against_rows_launch(h, B, n_off_host, rows, Nx, flux, cadence_mask, Bn, block, M, neighbors, corr,
+                                                 n_common, metric, static_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------------------------ over-fitting metric
 int lk_overfit_scratch_bytes(int B, int n, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes,
                              int *samples_per_round) {
@@ -928,6 +995,83 @@ int lk_overfit_metric_batch(lk_handle *h, int B, int N, const double *time, cons
     if (rc) return rc;
     rc = lk::overfit_metric_launch(h, B, N, dt, dy0, dy1, de1, n, dkeep, f0, df, M, n_samples, seed, first_target, stream_id, dscr,
                                    bytes, dmetric, nullptr);
+    return rc ? rc : io.finish();
+}
+
+// the batch's own offsets
+int lk_overfit_scratch_rows_bytes(int B, const int64_t *k_off_host, int64_t M, int n_samples, int64_t max_scratch_bytes,
+                                  int64_t *bytes, int *samples_per_round) {
+    return lk::overfit_scratch_rows_bytes(B, k_off_host, M, n_samples, max_scratch_bytes, bytes, samples_per_round);
+}
+
+int lk_overfit_session_rows_bytes(int B, const int64_t *k_off_host, int64_t M, int n_samples, int64_t max_scratch_bytes,
+                                  int64_t *bytes, int *samples_per_round) {
+    return lk::overfit_scratch_rows_bytes(B, k_off_host, M, n_samples, max_scratch_bytes, bytes, samples_per_round);
+}
+
+int lk_overfit_metric_rows_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
+                                     const double *flux_corr, const double *err_corr, const int32_t *keep_idx,
+                                     const int64_t *k_off_host, double f0, double df, int64_t M, int n_samples, uint64_t seed,
+                                     int64_t first_target, int64_t stream_id, void *scratch, int64_t scratch_bytes, double *metric,
+                                     void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::overfit_metric_rows_launch(h, B, n_off_host, time, flux_orig, flux_corr, err_corr, keep_idx, k_off_host, f0, df, M,
+                                          n_samples, seed, first_target, stream_id, scratch, scratch_bytes, metric,
+                                          static_cast<hipStream_t>(stream));
+}
+
+int lk_overfit_session_begin_rows_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
+                                      const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
+                                      int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id, void *session,
+                                      int64_t session_bytes, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::overfit_session_begin_rows_launch(h, B, n_off_host, time, flux_orig, keep_idx, k_off_host, f0, df, M, n_samples, seed,
+                                                 first_target, stream_id, session, session_bytes, static_cast<hipStream_t>(stream));
+}
+
+int lk_overfit_session_eval_rows_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *flux_corr, const double *err_corr,
+                                     const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
+                                     int n_samples, void *session, int64_t session_bytes, double *metric, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::overfit_session_eval_rows_launch(h, B, n_off_host, flux_corr, err_corr, keep_idx, k_off_host, f0, df, M, n_samples,
+                                                session, session_bytes, metric, static_cast<hipStream_t>(stream));
+}
+
+int lk_overfit_metric_rows_batch(lk_handle *h, int B, const int64_t *n_off, const double *time, const double *flux_orig,
+                                 const double *flux_corr, const double *err_corr, const int32_t *keep_idx, const int64_t *k_off,
+                                 double f0, double df, int64_t M, int n_samples, uint64_t seed, int64_t first_target,
+                                 int64_t stream_id, int64_t max_scratch_bytes, double *metric) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 1 && n_off != nullptr && n_off[0] == 0, "B must be >= 1 (got %d) and n_off given, starting at 0", B);
+    LK_REQUIRE((keep_idx == nullptr) == (k_off == nullptr || k_off == n_off), "keep_idx and k_off go together");
+    LK_REQUIRE(time && flux_orig && flux_corr && err_corr && metric, "NULL buffer");
+    const int64_t *ko = k_off ? k_off : n_off;
+    int64_t bytes = 0;
+    int rc = lk::overfit_scratch_rows_bytes(B, ko, M, n_samples, max_scratch_bytes, &bytes, nullptr);
+    if (rc) return rc;
+    for (int b = 0; b < B; ++b) {
+        const int64_t N = n_off[b + 1] - n_off[b];
+        LK_REQUIRE(N >= 3 && N < (1 << 30), "target %d: %lld cadences outside 3..2^30", b, (long long)N);
+        if (keep_idx)
+            for (int64_t i = ko[b]; i < ko[b + 1]; ++i)
+                LK_REQUIRE(keep_idx[i] >= 0 && keep_idx[i] < N && (i == ko[b] || keep_idx[i] > keep_idx[i - 1]),
+                           "target %d: the kept cadences must be ascending indices in [0, %lld)", b, (long long)N);
+    }
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B];
+    const double *dt, *dy0, *dy1, *de1;
+    const int32_t *dkeep;
+    double *dmetric;
+    char *dscr;
+    lk::StagedCall io(h);
+    rc = io.in(dt, time, ntot).in(dy0, flux_orig, ntot).in(dy1, flux_corr, ntot).in(de1, err_corr, ntot)
+             .in(dkeep, keep_idx, (size_t)ko[B]).out(dmetric, metric, (size_t)B).scratch(dscr, (size_t)bytes).stage();
+    if (rc) return rc;
+    rc = lk::overfit_metric_rows_launch(h, B, n_off, dt, dy0, dy1, de1, dkeep, keep_idx ? ko : nullptr, f0, df, M, n_samples, seed,
+                                        first_target, stream_id, dscr, bytes, dmetric, nullptr);
     return rc ? rc : io.finish();
 }
 

@@ -100,6 +100,9 @@ struct lk_handle {
     // lsfast.hip: the 1024th roots of unity (1024 x double2, cos | sin), filled once per handle: the column kernel's
     // workgroup-uniform pre-twiddles are read from it through scalar loads
     double *ls_roots = nullptr;
+    // neighbors.hip, the metric on a cadence grid: uf_scale(n) for n = 0 .. size - 1, grown on the host as larger grids come (the
+    // number of common cadences is known on the device only, and the scale must be the host's bits)
+    std::vector<double> uf_scale_tab;
 };
 
 namespace lk {
@@ -201,6 +204,21 @@ int underfit_rows_prepare_launch(lk_handle *h, int Bn, int N, const double *flux
 int underfit_against_rows_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int Bn,
                                  const void *rows, int M, const int32_t *neighbors, double *corr, double *metric,
                                  hipStream_t stream);
+// regress.hip's rows_pos_kernel: pos[b][rows[n_off[b] + i]] = i, -1 elsewhere (B x Nx); bad[0] (INT_MAX before) = the first target
+// whose rows are not strictly increasing indices into [0, Nx).  d_off: the offsets on the device, nmax: the longest target
+int rows_pos_launch(int B, const int64_t *d_off, int64_t nmax, const int32_t *rows, int Nx, int32_t *pos, int *bad,
+                    hipStream_t stream);
+// neighbors.hip, the same metric for ragged targets on a grid of Nx cadences (rows: lk_align_rows_batch's)
+int underfit_grid_neighbors_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx, const double *flux,
+                                   const uint8_t *cmask, int M, const int32_t *neighbors, double *corr, int32_t *n_common,
+                                   double *metric, hipStream_t stream);
+int underfit_grid_rows_bytes(int Bn, int Nx, int64_t *bytes);
+int underfit_grid_rows_prepare_launch(lk_handle *h, int Bn, const int64_t *n_off_host, const int32_t *rows, int Nx,
+                                      const double *flux_nb, const uint8_t *cmask, void *block, int64_t block_bytes,
+                                      hipStream_t stream);
+int underfit_grid_against_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx, const double *flux,
+                                      const uint8_t *cmask, int Bn, const void *block, int M, const int32_t *neighbors, double *corr,
+                                      int32_t *n_common, double *metric, hipStream_t stream);
 int overfit_scratch_bytes(int B, int n, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes, int *samples_per_round);
 int overfit_noise_launch(lk_handle *h, int B, int n, int k, uint64_t seed, int64_t first_target, int64_t stream_id, double *out,
                          hipStream_t stream);
@@ -214,6 +232,21 @@ int overfit_session_begin_launch(lk_handle *h, int B, int N, const double *time,
 int overfit_session_eval_launch(lk_handle *h, int B, int N, const double *flux_corr, const double *err_corr, int n,
                                 const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, void *session,
                                 int64_t session_bytes, double *metric, hipStream_t stream);
+// overfit.hip on the batch's own offsets: (N, n, keep_idx) become n_off_host (B + 1), keep_idx (target-relative, packed by k_off_host;
+// NULL: all cadences) and k_off_host (B + 1 offsets of the kept cadences; NULL with keep_idx == NULL)
+int overfit_scratch_rows_bytes(int B, const int64_t *k_off_host, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes,
+                               int *samples_per_round);
+int overfit_metric_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
+                               const double *flux_corr, const double *err_corr, const int32_t *keep_idx, const int64_t *k_off_host,
+                               double f0, double df, int64_t M, int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id,
+                               void *scratch, int64_t scratch_bytes, double *metric, hipStream_t stream);
+int overfit_session_begin_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
+                                      const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
+                                      int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id, void *session,
+                                      int64_t session_bytes, hipStream_t stream);
+int overfit_session_eval_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *flux_corr, const double *err_corr,
+                                     const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
+                                     int n_samples, void *session, int64_t session_bytes, double *metric, hipStream_t stream);
 int model_part_launch(lk_handle *h, int B, int N, int K, int c0, int c1, const double *X, const double *w, double *out,
                       hipStream_t stream);
 int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,

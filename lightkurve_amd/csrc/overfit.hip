@@ -155,6 +155,97 @@ __global__ __launch_bounds__(OF_NT) void overfit_noise_kernel(int B, int n, int 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ ragged targets
+// The two kernels above for a batch on its own offsets: target b's cadences are [n_off[b], n_off[b + 1]) of the inputs, its kept
+// ones keep_idx[k_off[b] .. k_off[b + 1]) (target-relative, ascending; keep_idx == NULL: all, and k_off is n_off), and its packed
+// row starts at element k_off[b] of a block of cad = k_off[B] elements (round r of the times and of the noise: r cad + k_off[b]).
+// Per target they do what the uniform kernels do to a target of that length: the same operations in the same order, and the same
+// Philox counter (pair of kept cadences of that target, sample, first_target + b, stream_id).
+__global__ __launch_bounds__(OF_PREP_NT) void overfit_prepare_rows_kernel(const double *__restrict__ time, const double *__restrict__ y0,
+                                                                         const double *__restrict__ y1, const double *__restrict__ e1,
+                                                                         const int64_t *__restrict__ n_off,
+                                                                         const int32_t *__restrict__ keep_idx,
+                                                                         const int64_t *__restrict__ k_off, int64_t cad, int R,
+                                                                         double *__restrict__ z0, double *__restrict__ z1,
+                                                                         double *__restrict__ trel, double *__restrict__ mean_unc) {
+    __shared__ unsigned long long sh[OF_PREP_NT];
+    __shared__ int sh_cnt[OF_PREP_NT];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const size_t in = (size_t)n_off[b], out = (size_t)k_off[b];
+    const int n = (int)(k_off[b + 1] - k_off[b]);
+    const int32_t *kb = keep_idx ? keep_idx + out : nullptr;
+    auto idx = [&](int i) { return kb ? kb[i] : i; };
+    auto all = [&](int) { return true; };
+    double med0 = 0.0, med1 = 0.0, t0 = 0.0;   // (y0, y1: uniform over the grid)
+    if (y0) {
+        med0 = block_median(n, (long long)n, [&](int i) { return y0[in + idx(i)]; }, all, sh);
+        __syncthreads();
+        t0 = time[in + idx(0)];
+    }
+    if (y1) {
+        med1 = block_median(n, (long long)n, [&](int i) { return y1[in + idx(i)]; }, all, sh);
+        __syncthreads();
+    }
+    double s = 0.0;
+    int cnt = 0;
+    for (int i = tid; i < n; i += OF_PREP_NT) {
+        const int j = idx(i);
+        if (y0) {
+            z0[out + i] = __dsub_rn(__ddiv_rn(y0[in + j], med0), 1.0);
+            const double tr = __dsub_rn(time[in + j], t0);
+            for (int r = 0; r < R; ++r) trel[(size_t)r * (size_t)cad + out + i] = tr;
+        }
+        if (y1) {
+            z1[out + i] = __dsub_rn(__ddiv_rn(y1[in + j], med1), 1.0);
+            const double u = __ddiv_rn(e1[in + j], med1);
+            if (u == u) {
+                s += u;
+                ++cnt;
+            }
+        }
+    }
+    if (!y1) return;
+    double *shd = reinterpret_cast<double *>(sh);
+    shd[tid] = s;
+    sh_cnt[tid] = cnt;
+    __syncthreads();
+    for (int h = OF_PREP_NT / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+            shd[tid] += shd[tid + h];
+            sh_cnt[tid] += sh_cnt[tid + h];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) mean_unc[b] = sh_cnt[0] ? shd[0] / (double)sh_cnt[0] : __longlong_as_double(0x7ff8000000000000ll);
+}
+
+// bpr workgroups per row, sized by the longest row: the ones past a shorter row's end leave at once
+__global__ __launch_bounds__(OF_NT) void overfit_noise_rows_kernel(int B, const int64_t *__restrict__ k_off, int64_t cad, int bpr, int k0,
+                                                                  uint32_t key0, uint32_t key1, uint32_t first_target,
+                                                                  uint32_t stream_id, const double *__restrict__ mean_unc,
+                                                                  double *__restrict__ g) {
+    const int row = blockIdx.x / bpr, i = (blockIdx.x - row * bpr) * OF_NT + threadIdx.x;
+    const int kk = row / B, b = row - kk * B;
+    const int n = (int)(k_off[b + 1] - k_off[b]), c = 2 * i;
+    if (c >= n) return;
+    double a, s;
+    philox_normal_pair(philox4x32_10((uint32_t)i, (uint32_t)(k0 + kk), first_target + (uint32_t)b, stream_id, key0, key1), a, s);
+    const double mu = mean_unc ? mean_unc[b] : 1.0;
+    a *= mu;
+    s *= mu;
+    const size_t base = (size_t)kk * (size_t)cad + (size_t)k_off[b];
+    if (c + 1 < n) {
+        if ((base & 1) == 0) {
+            *reinterpret_cast<double2 *>(g + base + c) = make_double2(a, s);
+        } else {
+            g[base + c] = a;
+            g[base + c + 1] = s;
+        }
+    } else {
+        g[base + c] = a;   // the last pair of an odd count: its second normal is discarded
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ spectra
 // The workgroup's fixed-order sum: thread j holds the partial sum of elements j, j + 256, ...; a halving tree finishes it.
 __device__ __forceinline__ void of_tree(double *sd, int *sc, int tid) {
@@ -248,7 +339,7 @@ inline int of_blocks_per_row(int n) { return ((n + 1) / 2 + OF_NT - 1) / OF_NT; 
 
 struct OverfitPlan {
     int R;   // samples per round
-    size_t z0, z1, trel, g, p0, p1, pn, mean_unc, mnp, n_up, S, total;
+    size_t z0, z1, trel, g, p0, p1, pn, mean_unc, mnp, n_up, S, offs, total;
 };
 
 inline size_t of_carve(size_t &used, size_t bytes) {
@@ -257,9 +348,11 @@ inline size_t of_carve(size_t &used, size_t bytes) {
     return at;
 }
 
-OverfitPlan of_layout(int B, int n, int64_t M, int n_samples, int R) {
+// cad: the kept cadences of all B targets together (B n for a uniform batch); offs: the ragged flavours also keep the batch's
+// two offset tables (2 (B + 1) int64) in the block, after everything else
+OverfitPlan of_layout(int B, size_t cad, int64_t M, int n_samples, int R, bool offs) {
     OverfitPlan p;
-    const size_t rows = (size_t)B * n * 8, spec = (size_t)B * M * 8;
+    const size_t rows = cad * 8, spec = (size_t)B * M * 8;
     size_t used = 0;
     p.R = R;
     p.z0 = of_carve(used, rows);
@@ -273,21 +366,26 @@ OverfitPlan of_layout(int B, int n, int64_t M, int n_samples, int R) {
     p.mnp = of_carve(used, (size_t)B * n_samples * 8);
     p.n_up = of_carve(used, (size_t)B * 4);
     p.S = of_carve(used, (size_t)B * 8);
+    p.offs = offs ? of_carve(used, 2 * ((size_t)B + 1) * 8) : used;
     p.total = used;
     return p;
 }
 
 // the largest round that fits `budget` (and one launch: R B rows as an int); one sample per round when none fits
-OverfitPlan of_plan(int B, int n, int64_t M, int n_samples, size_t budget) {
-    const int64_t wg_per_sample = (int64_t)B * of_blocks_per_row(n);   // (the noise pass: one launch per round, 1-D grid)
+// nmax: the longest row (n for a uniform batch)
+OverfitPlan of_plan(int B, size_t cad, int nmax, int64_t M, int n_samples, size_t budget, bool offs) {
+    const int64_t wg_per_sample = (int64_t)B * of_blocks_per_row(nmax);   // (the noise pass: one launch per round, 1-D grid)
     const int rmax = (int)std::min<int64_t>(n_samples, std::min<int64_t>(((int64_t)1 << 30) / B, (((int64_t)1 << 31) - 1) / wg_per_sample));
     int R = 1;
     for (int r = std::max(1, rmax); r > 1; --r)
-        if (of_layout(B, n, M, n_samples, r).total <= budget) {
+        if (of_layout(B, cad, M, n_samples, r, offs).total <= budget) {
             R = r;
             break;
         }
-    return of_layout(B, n, M, n_samples, R);
+    return of_layout(B, cad, M, n_samples, R, offs);
+}
+OverfitPlan of_plan(int B, int n, int64_t M, int n_samples, size_t budget) {
+    return of_plan(B, (size_t)B * n, n, M, n_samples, budget, false);
 }
 }  // namespace
 
@@ -343,22 +441,48 @@ namespace {
 // one call's view of the caller-owned block and the three steps the unsplit metric and a session share
 struct OverfitRun {
     lk_handle *h;
-    int B, n, n_samples;
+    int B, n, n_samples;   // n: the kept cadences of every target; of the longest one when the batch is ragged
     double f0, df;
     int64_t M;
     hipStream_t stream;
+    bool ragged;
+    size_t cad;            // the kept cadences of all targets together
     OverfitPlan p;
     char *base;
-    std::vector<int64_t> off;   // row offsets of the largest launch (R B rows of n)
+    std::vector<int64_t> off;   // row offsets of the largest launch (R B rows: row (r, b) starts at r cad + the kept offset of b)
 
     OverfitRun(lk_handle *h_, int B_, int n_, double f0_, double df_, int64_t M_, int n_samples_, void *block, size_t bytes,
                hipStream_t st)
-        : h(h_), B(B_), n(n_), n_samples(n_samples_), f0(f0_), df(df_), M(M_), stream(st), p(of_plan(B_, n_, M_, n_samples_, bytes)),
-          base(static_cast<char *>(block)), off((size_t)p.R * B_ + 1) {
+        : h(h_), B(B_), n(n_), n_samples(n_samples_), f0(f0_), df(df_), M(M_), stream(st), ragged(false), cad((size_t)B_ * n_),
+          p(of_plan(B_, n_, M_, n_samples_, bytes)), base(static_cast<char *>(block)), off((size_t)p.R * B_ + 1) {
         for (size_t r = 0; r < off.size(); ++r) off[r] = (int64_t)r * n;
+    }
+    // ragged: k_off = the B + 1 offsets of the kept cadences, nmax the longest row
+    OverfitRun(lk_handle *h_, int B_, const int64_t *k_off, int nmax, double f0_, double df_, int64_t M_, int n_samples_, void *block,
+               size_t bytes, hipStream_t st)
+        : h(h_), B(B_), n(nmax), n_samples(n_samples_), f0(f0_), df(df_), M(M_), stream(st), ragged(true), cad((size_t)k_off[B_]),
+          p(of_plan(B_, cad, nmax, M_, n_samples_, bytes, true)), base(static_cast<char *>(block)), off((size_t)p.R * B_ + 1) {
+        for (int r = 0; r < p.R; ++r)
+            for (int b = 0; b < B_; ++b) off[(size_t)r * B_ + b] = (int64_t)r * (int64_t)cad + k_off[b];
+        off.back() = (int64_t)p.R * (int64_t)cad;
     }
     double *at(size_t o) const { return reinterpret_cast<double *>(base + o); }
     int *n_up() const { return reinterpret_cast<int *>(base + p.n_up); }
+    int64_t *d_noff() const { return reinterpret_cast<int64_t *>(base + p.offs); }   // ragged: the batch's offsets on the device,
+    int64_t *d_koff() const { return d_noff() + B + 1; }                             // then the kept cadences' offsets
+
+    // ragged: both offset tables into the block (captured before the call returns), once per block
+    int upload_offsets(const int64_t *n_off_host, const int64_t *k_off_host) const {
+        if (const int rc = h->stage.copy(d_noff(), n_off_host, ((size_t)B + 1) * 8, stream)) return rc;
+        return h->stage.copy(d_koff(), k_off_host, ((size_t)B + 1) * 8, stream);
+    }
+    int prepare_rows(const double *time, const double *y0, const double *y1, const double *e1, const int32_t *keep_idx) const {
+        hipLaunchKernelGGL(overfit_prepare_rows_kernel, dim3(B), dim3(OF_PREP_NT), 0, stream, time, y0, y1, e1,
+                           (const int64_t *)d_noff(), keep_idx, (const int64_t *)d_koff(), (int64_t)cad, p.R, at(p.z0), at(p.z1),
+                           at(p.trel), at(p.mean_unc));
+        LK_HIP_CHECK(hipGetLastError());
+        return LK_OK;
+    }
 
     int prepare(const double *time, const double *y0, const double *y1, const double *e1, int N, const int32_t *keep_idx) const {
         hipLaunchKernelGGL(overfit_prepare_kernel, dim3(B), dim3(OF_PREP_NT), 0, stream, time, y0, y1, e1, N, n, keep_idx, B, p.R,
@@ -380,7 +504,14 @@ struct OverfitRun {
     int noise_means(uint64_t seed, int64_t first_target, int64_t stream_id, const double *scale) const {
         for (int k0 = 0; k0 < n_samples; k0 += p.R) {
             const int nk = std::min(p.R, n_samples - k0);
-            overfit_noise_rows(B, n, nk, k0, seed, first_target, stream_id, scale, at(p.g), stream);
+            if (ragged) {
+                const int bpr = of_blocks_per_row(n);
+                hipLaunchKernelGGL(overfit_noise_rows_kernel, dim3((unsigned)((size_t)nk * B * bpr)), dim3(OF_NT), 0, stream, B,
+                                   (const int64_t *)d_koff(), (int64_t)cad, bpr, k0, (uint32_t)(seed & 0xffffffffu),
+                                   (uint32_t)(seed >> 32), (uint32_t)first_target, (uint32_t)stream_id, scale, at(p.g));
+            } else {
+                overfit_noise_rows(B, n, nk, k0, seed, first_target, stream_id, scale, at(p.g), stream);
+            }
             LK_HIP_CHECK(hipGetLastError());
             if (const int rc = ls(nk * B, at(p.g), at(p.pn))) return rc;
             hipLaunchKernelGGL(overfit_noise_mean_kernel, dim3((unsigned)(nk * B)), dim3(OF_NT), 0, stream, (const double *)at(p.pn),
@@ -458,6 +589,112 @@ int overfit_session_eval_launch(lk_handle *h, int B, int N, const double *flux_c
     LK_REQUIRE(flux_corr && err_corr && metric, "NULL buffer");
     const OverfitRun run(h, B, n, f0, df, M, n_samples, session, (size_t)session_bytes, stream);
     if ((rc = run.prepare(nullptr, nullptr, flux_corr, err_corr, N, keep_idx))) return rc;
+    if ((rc = run.change())) return rc;
+    return run.metric(run.at(run.p.mean_unc), metric);
+}
+
+// ------------------------------------------------------------------------------------------------ ragged entry points
+// k_off_host: the B + 1 offsets of the kept cadences; keep_idx == NULL keeps all and k_off_host may be NULL or n_off_host.
+static int overfit_rows_ok(int B, const int64_t *n_off_host, const int32_t *keep_idx, const int64_t *&k_off_host, int64_t M,
+                           int n_samples, int *nmax) {
+    LK_REQUIRE(B >= 1 && B < (1 << 24), "B must be in [1, 2^24) (got %d)", B);
+    LK_REQUIRE(n_off_host != nullptr && n_off_host[0] == 0, "n_off must be given and start at 0");
+    if (k_off_host == nullptr) {
+        LK_REQUIRE(keep_idx == nullptr, "keep_idx is given without k_off");
+        k_off_host = n_off_host;
+    }
+    LK_REQUIRE(k_off_host[0] == 0, "k_off must start at 0");
+    *nmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t N = n_off_host[b + 1] - n_off_host[b], n = k_off_host[b + 1] - k_off_host[b];
+        LK_REQUIRE(N >= 0 && N < (1 << 30), "target %d: %lld cadences outside 0..2^30", b, (long long)N);
+        LK_REQUIRE(n >= 3, "target %d: the over-fitting metric needs at least 3 kept cadences (got %lld)", b, (long long)n);
+        LK_REQUIRE(n <= N && (keep_idx != nullptr || n == N), "target %d keeps %lld of %lld cadences%s", b, (long long)n, (long long)N,
+                   keep_idx ? "" : " but keep_idx is NULL (all cadences)");
+        *nmax = std::max(*nmax, (int)n);
+    }
+    LK_REQUIRE(M >= 2 && M < ((int64_t)1 << 24), "the frequency grid needs 2 <= M < 2^24 points (got %lld)", (long long)M);
+    LK_REQUIRE(n_samples >= 1 && n_samples <= (1 << 20), "n_samples must be in [1, 2^20] (got %d)", n_samples);
+    LK_REQUIRE((int64_t)B * of_blocks_per_row(*nmax) < ((int64_t)1 << 31), "B x n = %d x %d is more than one noise launch covers", B,
+               *nmax);
+    return LK_OK;
+}
+
+int overfit_scratch_rows_bytes(int B, const int64_t *k_off_host, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes,
+                               int *samples_per_round) {
+    int nmax = 0;
+    LK_REQUIRE(k_off_host != nullptr, "k_off is NULL (the offsets of the kept cadences; the batch's own when all are kept)");
+    const int64_t *k = k_off_host;
+    int rc = overfit_rows_ok(B, k_off_host, nullptr, k, M, n_samples, &nmax);
+    if (rc) return rc;
+    LK_REQUIRE(bytes != nullptr, "bytes is NULL");
+    LK_REQUIRE(max_scratch_bytes >= 0, "max_scratch_bytes must be >= 0 (0: the default of %lld)", (long long)LK_OVERFIT_SCRATCH_DEFAULT);
+    const OverfitPlan p = of_plan(B, (size_t)k_off_host[B], nmax, M, n_samples,
+                                  (size_t)(max_scratch_bytes ? max_scratch_bytes : LK_OVERFIT_SCRATCH_DEFAULT), true);
+    *bytes = (int64_t)p.total;
+    if (samples_per_round) *samples_per_round = p.R;
+    return LK_OK;
+}
+
+static int overfit_rows_block_ok(int B, const int64_t *k_off_host, int nmax, double f0, double df, int64_t M, int n_samples,
+                                 const void *block, int64_t bytes) {
+    LK_REQUIRE(f0 >= 0.0 && df > 0.0, "the grid needs f0 >= 0 and df > 0 (got f0=%g, df=%g)", f0, df);
+    LK_REQUIRE(block != nullptr && ((uintptr_t)block & 255) == 0, "scratch must be a 256-byte aligned device buffer");
+    LK_REQUIRE(bytes >= 0, "scratch_bytes must be >= 0");
+    const OverfitPlan p = of_plan(B, (size_t)k_off_host[B], nmax, M, n_samples, (size_t)bytes, true);
+    LK_REQUIRE(p.total <= (size_t)bytes, "scratch too small: %lld bytes given, one sample per round needs %lld "
+               "(lk_overfit_scratch_rows_bytes)", (long long)bytes, (long long)p.total);
+    return LK_OK;
+}
+
+int overfit_metric_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
+                               const double *flux_corr, const double *err_corr, const int32_t *keep_idx, const int64_t *k_off_host,
+                               double f0, double df, int64_t M, int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id,
+                               void *scratch, int64_t scratch_bytes, double *metric, hipStream_t stream) {
+    int nmax = 0;
+    int rc = overfit_rows_ok(B, n_off_host, keep_idx, k_off_host, M, n_samples, &nmax);
+    if (rc) return rc;
+    if ((rc = overfit_rows_block_ok(B, k_off_host, nmax, f0, df, M, n_samples, scratch, scratch_bytes))) return rc;
+    LK_REQUIRE(time && flux_orig && flux_corr && err_corr && metric, "NULL buffer");
+    if ((rc = overfit_rng_ok(B, first_target, stream_id))) return rc;
+    const OverfitRun run(h, B, k_off_host, nmax, f0, df, M, n_samples, scratch, (size_t)scratch_bytes, stream);
+    if ((rc = run.upload_offsets(n_off_host, k_off_host))) return rc;
+    if ((rc = run.prepare_rows(time, flux_orig, flux_corr, err_corr, keep_idx))) return rc;
+    if ((rc = run.ls(B, run.at(run.p.z0), run.at(run.p.p0)))) return rc;
+    if ((rc = run.change())) return rc;
+    if ((rc = run.noise_means(seed, first_target, stream_id, run.at(run.p.mean_unc)))) return rc;
+    return run.metric(nullptr, metric);
+}
+
+// The session of a ragged batch: begin also puts the two offset tables into the block, and an evaluation reads them there (its
+// own n_off_host / k_off_host must be begin's: they size the plan and the periodogram launch).
+int overfit_session_begin_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
+                                      const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
+                                      int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id, void *session,
+                                      int64_t session_bytes, hipStream_t stream) {
+    int nmax = 0;
+    int rc = overfit_rows_ok(B, n_off_host, keep_idx, k_off_host, M, n_samples, &nmax);
+    if (rc) return rc;
+    if ((rc = overfit_rows_block_ok(B, k_off_host, nmax, f0, df, M, n_samples, session, session_bytes))) return rc;
+    LK_REQUIRE(time && flux_orig, "NULL buffer");
+    if ((rc = overfit_rng_ok(B, first_target, stream_id))) return rc;
+    const OverfitRun run(h, B, k_off_host, nmax, f0, df, M, n_samples, session, (size_t)session_bytes, stream);
+    if ((rc = run.upload_offsets(n_off_host, k_off_host))) return rc;
+    if ((rc = run.prepare_rows(time, flux_orig, nullptr, nullptr, keep_idx))) return rc;
+    if ((rc = run.ls(B, run.at(run.p.z0), run.at(run.p.p0)))) return rc;
+    return run.noise_means(seed, first_target, stream_id, nullptr);
+}
+
+int overfit_session_eval_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *flux_corr, const double *err_corr,
+                                     const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
+                                     int n_samples, void *session, int64_t session_bytes, double *metric, hipStream_t stream) {
+    int nmax = 0;
+    int rc = overfit_rows_ok(B, n_off_host, keep_idx, k_off_host, M, n_samples, &nmax);
+    if (rc) return rc;
+    if ((rc = overfit_rows_block_ok(B, k_off_host, nmax, f0, df, M, n_samples, session, session_bytes))) return rc;
+    LK_REQUIRE(flux_corr && err_corr && metric, "NULL buffer");
+    const OverfitRun run(h, B, k_off_host, nmax, f0, df, M, n_samples, session, (size_t)session_bytes, stream);
+    if ((rc = run.prepare_rows(nullptr, nullptr, flux_corr, err_corr, keep_idx))) return rc;
     if ((rc = run.change())) return rc;
     return run.metric(run.at(run.p.mean_unc), metric);
 }

@@ -1625,6 +1625,16 @@ __global__ __launch_bounds__(256) void rows_pos_kernel(const int *__restrict__ r
         atomicMin(bad, b);
 }
 
+// rows_pos_kernel for the other translation units (neighbors.hip): pos is set to -1 first; nothing is waited for
+int rows_pos_launch(int B, const int64_t *d_off, int64_t nmax, const int32_t *rows, int Nx, int32_t *pos, int *bad,
+                    hipStream_t stream) {
+    LK_HIP_CHECK(hipMemsetAsync(pos, 0xff, (size_t)B * Nx * 4, stream));  // -1: the target has no cadence at that row
+    if (nmax > 0)
+        hipLaunchKernelGGL(rows_pos_kernel, dim3((unsigned)((nmax + 255) / 256), B), dim3(256), 0, stream, rows, d_off, Nx, pos, bad);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
 int align_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *cadenceno, int Nx, const int32_t *grid,
                       int32_t *rows, int32_t *pos, hipStream_t stream) {
     LK_REQUIRE(B >= 0 && n_off_host, "bad batch description");

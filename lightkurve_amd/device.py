@@ -627,10 +627,14 @@ class DeviceLightCurveBatch(object):
             keep.append(k)
         return src, d_rows, d_cm, keep
 
-    def _regress_shared_rows(self, Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, to_host, keep):
+    def _regress_shared_rows(self, Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, to_host, keep, resident=None):
+        """``resident``: d_X already in HBM (a search that fits the same matrix many times uploads it once)."""
         h, B, K, n = self.handle, len(self), Xa.shape[1], self.n_cadences
-        d_X, k = _upload(h, Xa, self.stream)
-        keep.append(k)
+        if resident is not None:
+            d_X = resident
+        else:
+            d_X, k = _upload(h, Xa, self.stream)
+            keep.append(k)
         d_w, d_model, d_corr, d_outl = DeviceBuffer(h, B * K * 8), DeviceBuffer(h, n * 8), DeviceBuffer(h, n * 8), DeviceBuffer(h, n)
         _capi._check(_capi._lib.lk_regress_shared_rows_batch_dev(
             h._h, B, _off_ptr(self.n_off), _vp(d_rows.ptr), Xa.shape[0], K, _vp(d_X.ptr), _vp(self.d_flux.ptr),
@@ -733,7 +737,8 @@ class DeviceLightCurveBatch(object):
         return out, d_outl, d_w
 
     # ---------------------------------------------------------------- under-fitting metric, neighbours by index
-    def under_fitting_metric(self, neighbors, cadence_mask=None, return_correlations=False, to_host=True, neighbor_batch=None):
+    def under_fitting_metric(self, neighbors, cadence_mask=None, return_correlations=False, to_host=True, neighbor_batch=None,
+                             cadenceno=None, return_common=False):
         """``underfit_metric_neighbors`` (reference correctors/metrics.py:141-257, 451-475) for every target of the batch, the
         neighbours being OTHER TARGETS OF THIS BATCH (the reference fetches them from MAST; after ``cbv_correct`` they are the
         corrected targets of the same field, already in HBM): ``neighbors`` int (B, M), row t = the indices of t's neighbours,
@@ -746,7 +751,22 @@ class DeviceLightCurveBatch(object):
         ``neighbor_batch``: a resident, NaN-free batch with the same cadence count whose ROWS are the neighbours instead
         (``neighbors`` then holds indices into ``[0, len(neighbor_batch))``, and a target's own row number is a neighbour
         like any other: it names a row of the other batch); its rows are prepared once and only the B targets after them.
-        With ``neighbor_batch`` = this batch the result is the same bits as without."""
+        With ``neighbor_batch`` = this batch the result is the same bits as without.
+
+        ``cadenceno``: the strictly increasing integer cadence numbers of the field's grid.  The batch may then be RAGGED
+        (``from_fits``, ``remove_nans``, ``remove_outliers``, ``select``) and is matched by its own ``d_cadenceno`` column, as in
+        ``regression_correct(cadenceno=)`` (a cadence that is not on the grid is dropped first); ``cadence_mask`` is then ragged:
+        bool (sum n,) over the cadences of this batch, or a ``DeviceBuffer`` of that many bytes.  As in the reference, target t
+        is compared with its neighbours on the cadences that t (under its mask) and ALL of them have; ``return_common`` adds
+        that count, n_common[B] int32, to the result (after the correlations, when both are asked for); fewer than two common
+        cadences give NaN, not an error.  A ``neighbor_batch`` is matched to the same grid by its own cadence numbers and its
+        rows are not masked (the common cadences are bounded by the target's mask anyway)."""
+        if cadenceno is not None:
+            return self._under_fitting_grid(neighbors, cadence_mask, return_correlations, to_host, neighbor_batch, cadenceno,
+                                            return_common)
+        if return_common:
+            raise ValueError("under_fitting_metric: return_common goes with cadenceno= (without it every target keeps the same "
+                             "cadences)")
         N = self._uniform_n(None, "under_fitting_metric")
         if not getattr(self, "nan_free", False):
             raise ValueError("under_fitting_metric needs a NaN-free batch: call remove_nans() first (and cotrend after it)")
@@ -785,6 +805,77 @@ class DeviceLightCurveBatch(object):
             corr = d_corr.download(np.float64, B * M, stream=self.stream) if M else np.empty(0)
             return metric, corr.reshape(B, M)
         return metric
+
+    def _under_fitting_grid(self, neighbors, cadence_mask, return_correlations, to_host, neighbor_batch, cadenceno, return_common):
+        """``under_fitting_metric(cadenceno=)``: every check that needs no device, the alignment(s), then the grid kernels."""
+        what = "under_fitting_metric"
+        if not getattr(self, "nan_free", False):
+            raise ValueError("under_fitting_metric needs a NaN-free batch: call remove_nans() first (and cotrend after it)")
+        B, Nx = len(self), int(np.asarray(cadenceno).size)
+        if Nx > _capi.UNDERFIT_GRID_MAX_NX:
+            raise ValueError("under_fitting_metric: the grid has %d cadences, at most %d are taken" % (Nx, _capi.UNDERFIT_GRID_MAX_NX))
+        Bn = None
+        if neighbor_batch is not None:
+            if not isinstance(neighbor_batch, DeviceLightCurveBatch):
+                raise ValueError("%s: `neighbor_batch` must be a resident DeviceLightCurveBatch" % what)
+            if not getattr(neighbor_batch, "nan_free", False):
+                raise ValueError("%s needs a NaN-free neighbor_batch: call remove_nans() first (and cotrend after it)" % what)
+            if getattr(neighbor_batch, "d_cadenceno", None) is None:
+                raise ValueError("%s(cadenceno=) needs a neighbor_batch that carries cadence numbers" % what)
+            Bn = len(neighbor_batch)
+        nb = _capi.underfit_arguments(B, max(Nx, 2), neighbors, None, Bn)[0]
+        M = nb.shape[1]
+        src, d_rows, d_cm, keep = self._aligned(Nx, None, cadenceno, cadence_mask, what)
+        h, st = self.handle, _vp(self.stream or None)
+        d_nb = None
+        if M:
+            d_nb, k = _upload(h, nb, self.stream, np.int32)
+            keep.append(k)
+        d_corr = DeviceBuffer(h, max(B * M, 1) * 8) if return_correlations else None
+        d_nc = DeviceBuffer(h, B * 4) if return_common else None
+        d_metric = DeviceBuffer(h, B * 8)
+        p = lambda buf: _vp(buf.ptr if buf is not None else None)
+        if neighbor_batch is None:
+            _capi._check(_capi._lib.lk_underfit_grid_neighbors_batch_dev(
+                h._h, B, _off_ptr(src.n_off), _vp(d_rows.ptr), Nx, _vp(src.d_flux.ptr), p(d_cm), M, p(d_nb),
+                p(d_corr if M else None), p(d_nc), _vp(d_metric.ptr), st))
+        else:
+            d_block, nkeep = neighbor_batch._underfit_grid_rows(Nx, cadenceno, self.stream)
+            src._underfit_grid_against(Nx, d_rows, d_cm, Bn, d_block, M, d_nb, d_corr, d_nc, d_metric)
+            keep += nkeep + [d_block]
+        # inputs the stream may still be reading: held until the batch is synchronised or dropped (the flux buffer, not the
+        # aligned batch: see under_fitting_metric)
+        self._keep += keep + [d_rows, d_cm, d_nb, src.d_flux]
+        if not to_host:
+            out = (d_metric,) + ((d_corr,) if return_correlations else ()) + ((d_nc,) if return_common else ())
+        else:
+            out = (d_metric.download(np.float64, B, stream=self.stream),)
+            if return_correlations:
+                out += ((d_corr.download(np.float64, B * M, stream=self.stream) if M else np.empty(0)).reshape(B, M),)
+            if return_common:
+                out += (d_nc.download(np.int32, B, stream=self.stream),)
+        return out if len(out) > 1 else out[0]
+
+    def _underfit_grid_rows(self, Nx, cadenceno, stream):
+        """This batch's light curves, matched to the grid by their own cadence numbers and unmasked, prepared as the NEIGHBOURS
+        of ``lk_underfit_grid_against_rows_batch_dev`` -> (their ``DeviceBuffer``, buffers to keep until ``stream`` is done)."""
+        src, d_rows, _, keep = self._aligned(Nx, None, cadenceno, None, "under_fitting_metric (neighbor_batch)")
+        h = self.handle
+        nbytes = ctypes.c_int64(0)
+        _capi._check(_capi._lib.lk_underfit_grid_rows_bytes(len(src), Nx, ctypes.byref(nbytes)))
+        d_block = DeviceBuffer(h, nbytes.value)
+        _capi._check(_capi._lib.lk_underfit_grid_rows_prepare_dev(h._h, len(src), _off_ptr(src.n_off), _vp(d_rows.ptr), Nx,
+                                                                  _vp(src.d_flux.ptr), None, _vp(d_block.ptr), nbytes.value,
+                                                                  _vp(stream or None)))
+        return d_block, keep + [d_rows, src.d_flux]
+
+    def _underfit_grid_against(self, Nx, d_rows, d_cm, Bn, d_block, M, d_nb, d_corr, d_nc, d_metric, metric_offset=0):
+        """The grid pair pass of this (aligned) batch's targets against prepared neighbour rows, into ``d_metric``."""
+        p = lambda buf: _vp(buf.ptr if buf is not None else None)
+        _capi._check(_capi._lib.lk_underfit_grid_against_rows_batch_dev(
+            self.handle._h, len(self), _off_ptr(self.n_off), _vp(d_rows.ptr), Nx, _vp(self.d_flux.ptr), p(d_cm), Bn, _vp(d_block.ptr),
+            M, p(d_nb), p(d_corr if M else None), p(d_nc), _vp(d_metric.ptr + metric_offset), _vp(self.stream or None)))
+        return d_metric
 
     def _underfit_rows(self, N, n, d_keep, stream):
         """This batch's rows prepared as the NEIGHBOURS of ``lk_underfit_against_rows_batch_dev`` -> their ``DeviceBuffer``
@@ -839,7 +930,21 @@ class DeviceLightCurveBatch(object):
         samples are taken in rounds that keep the scratch block under it; default 4 GiB) or on the run.  Returns metric[B]
         (``to_host=True``) or its ``DeviceBuffer`` (``to_host=False``: nothing synchronised after the periodograms' own
         planning).  Needs one cadence count per batch, NaN-free batches, flux errors on the corrected batch, ``n_samples`` >= 1,
-        a regular grid of at least two frequencies and at least three kept cadences: ``ValueError`` before any device call."""
+        a regular grid of at least two frequencies and at least three kept cadences: ``ValueError`` before any device call.
+
+        RAGGED batches (``from_fits``, ``remove_nans``, ``remove_outliers``, ``select``; what ``cbv_correct(cadenceno=)`` returns)
+        are taken on their own offsets when ``original.n_off`` equals this batch's (``ValueError`` otherwise); ``cadence_mask`` is
+        then ragged, bool (sum n,) over the cadences of the batch, or a ``DeviceBuffer`` of that many bytes (downloaded once, to
+        list the kept cadences; a ``DeviceBuffer`` is always read as this ragged mask, also on a uniform batch, and for one target the
+        two shapes are the same mask); every target needs at least three kept cadences.  A ragged mask also takes a uniform batch this
+        way, with the same bits.  ``frequency=None`` stays the grid of target 0's kept times.  Target b's value is the uniform
+        call's on a batch that holds its kept cadences alone, with ``first_target + b``."""
+        ragged_mask = isinstance(cadence_mask, DeviceBuffer) or (
+            cadence_mask is not None and len(self) > 1 and np.shape(cadence_mask) == (self.n_cadences,))
+        if isinstance(original, DeviceLightCurveBatch) and (self._is_ragged() or original._is_ragged() or ragged_mask):
+            keep_idx, k_off, grid = self._overfit_rows_checks(original, n_samples, cadence_mask, frequency, seed, first_target, stream_id)
+            return self._over_fitting_rows(original, grid, n_samples, keep_idx, k_off, None, seed, first_target, stream_id, to_host,
+                                           max_scratch_bytes)
         N, keep_idx, n, grid = self._overfit_checks(original, n_samples, cadence_mask, frequency, seed, first_target, stream_id)
         B, h, st = len(self), self.handle, _vp(self.stream or None)
         if grid is None:
@@ -861,17 +966,77 @@ class DeviceLightCurveBatch(object):
             return d_metric
         return d_metric.download(np.float64, B, stream=self.stream)
 
+    def _is_ragged(self):
+        counts = np.diff(self.n_off)
+        return bool(len(counts)) and counts.min() != counts.max()
+
+    def _overfit_rows_checks(self, original, n_samples, cadence_mask, frequency, seed, first_target, stream_id):
+        """The checks of the ragged ``over_fitting_metric`` -> (keep_idx or None, k_off, grid or None).  Only a mask given as a
+        ``DeviceBuffer`` needs the device (one download), after every check that does not."""
+        if not isinstance(original, DeviceLightCurveBatch):
+            raise ValueError("over_fitting_metric: `original` must be the resident batch before the correction")
+        if len(self) < 1:
+            raise ValueError("over_fitting_metric needs at least one light curve")
+        if len(original) != len(self) or not np.array_equal(original.n_off, self.n_off):
+            rag, name = (self, "corrected") if self._is_ragged() else (original, "original")
+            counts = np.diff(rag.n_off)
+            raise ValueError("over_fitting_metric: the original batch must have the offsets (n_off) of the corrected one, target by "
+                             "target; the %s batch has between %d and %d cadences per target" % (name, counts.min(), counts.max()))
+        if not (self.nan_free and original.nan_free):
+            raise ValueError("over_fitting_metric needs NaN-free batches: call remove_nans() first (and cotrend after it)")
+        if getattr(self, "d_flux_err", None) is None:
+            raise ValueError("over_fitting_metric needs the flux errors of the corrected batch (the noise level is their mean)")
+        if isinstance(cadence_mask, DeviceBuffer):
+            if cadence_mask.nbytes != self.n_cadences:
+                raise ValueError("over_fitting_metric: cadence_mask holds %d bytes, the batch has %d cadences"
+                                 % (cadence_mask.nbytes, self.n_cadences))
+            _capi.overfit_rows_arguments(self.n_off, n_samples, None, frequency, seed, first_target, stream_id)
+            cadence_mask = cadence_mask.download(np.uint8, self.n_cadences, stream=self.stream)
+        return _capi.overfit_rows_arguments(self.n_off, n_samples, cadence_mask, frequency, seed, first_target, stream_id)
+
+    def _overfit_rows_default_grid(self, keep_idx, k_off):
+        """The default frequency grid of target 0's kept times (its times are downloaded once)."""
+        t0 = self.d_time.download(np.float64, int(self.n_off[1]), stream=self.stream)
+        return _capi.overfit_default_grid(t0 if keep_idx is None else t0[keep_idx[:int(k_off[1])]])
+
+    def _over_fitting_rows(self, original, grid, n_samples, keep_idx, k_off, d_keep, seed, first_target, stream_id, to_host,
+                           max_scratch_bytes):
+        """``lk_overfit_metric_rows_batch_dev`` on this (corrected) batch; ``d_keep``: keep_idx already in HBM."""
+        B, h, st = len(self), self.handle, _vp(self.stream or None)
+        if grid is None:
+            grid = _capi.overfit_grid(self._overfit_rows_default_grid(keep_idx, k_off))
+        nbytes, _rounds = _capi.overfit_scratch_rows_bytes(k_off, grid[2], n_samples, max_scratch_bytes)
+        if keep_idx is not None and d_keep is None:
+            d_keep, k = _upload(h, keep_idx, self.stream, np.int32)
+            self._keep.append(k)
+        d_scr, d_metric = DeviceBuffer(h, nbytes), DeviceBuffer(h, B * 8)
+        _capi._check(_capi._lib.lk_overfit_metric_rows_batch_dev(
+            h._h, B, _off_ptr(self.n_off), _vp(self.d_time.ptr), _vp(original.d_flux.ptr), _vp(self.d_flux.ptr), _vp(self.d_flux_err.ptr),
+            _vp(d_keep.ptr if d_keep is not None else None), _off_ptr(k_off) if keep_idx is not None else None, grid[0], grid[1],
+            grid[2], int(n_samples), int(seed), int(first_target), int(stream_id), _vp(d_scr.ptr), nbytes, _vp(d_metric.ptr), st))
+        self._keep += [d_keep, original.d_flux]
+        if not to_host:
+            return d_metric
+        return d_metric.download(np.float64, B, stream=self.stream)
+
     def cbv_goodness_scan(self, cbvs, alphas, neighbors=None, cbv_indices=np.arange(1, 9), cadence_mask=None, n_samples=1, seed=0,
-                          frequency=None, first_target=0, ext_dm=None, sigma=5, niters=5, max_scratch_bytes=None):
+                          frequency=None, first_target=0, ext_dm=None, sigma=5, niters=5, max_scratch_bytes=None, cadenceno=None):
         """Both goodness metrics of ``cbv_correct`` over a list of ridge penalties, for the whole batch (what
         ``correctors.CBVCorrector.goodness_scan`` does for one target, here for a whole channel): for each
         ``alphas[a]`` the batch is corrected (``cbv_correct(cbvs, cbv_indices, alpha, ext_dm, cadence_mask, sigma, niters)``),
         scored with ``over_fitting_metric(self, ..., stream_id=a)`` and, when ``neighbors`` (int (B, M), see
         ``under_fitting_metric``) is given, with ``under_fitting_metric``.  ``cadence_mask``: bool (N,), shared by the fit and
         both metrics.  A plain loop of resident calls; 8 or 16 bytes per target and penalty come back.  Returns
-        dict(alpha[A], over_fitting[A, B], under_fitting[A, B] or None)."""
+        dict(alpha[A], over_fitting[A, B], under_fitting[A, B] or None).  ``cadenceno``: the cadence numbers of the rows of
+        ``cbvs``; the batch may then be ragged, ``cadence_mask`` is ragged (bool (sum n,) or a ``DeviceBuffer``), and the fit and
+        both metrics are ``cbv_correct(cadenceno=)``, the ragged ``over_fitting_metric`` and ``under_fitting_metric(cadenceno=)``:
+        the batch is aligned once and the matrix, the mask, the rows and the kept cadences are uploaded once; the result gains
+        n_common[A, B] (or None)."""
         alphas = np.atleast_1d(np.asarray(alphas, dtype=np.float64))
         B = len(self)
+        if cadenceno is not None:
+            return self._cbv_goodness_scan_rows(_cbv_columns(cbvs, cbv_indices, ext_dm), alphas, neighbors, cadenceno, cadence_mask,
+                                                n_samples, seed, frequency, first_target, sigma, niters, max_scratch_bytes)
         N, keep_idx, _n, grid = self._overfit_checks(self, n_samples, cadence_mask, frequency, seed, first_target, 0)
         if grid is None:      # the default grid depends on the times alone: taken once for the whole scan
             t0 = self.d_time.download(np.float64, N, stream=self.stream)
@@ -895,7 +1060,7 @@ class DeviceLightCurveBatch(object):
     def cbv_correct_optimized(self, cbvs, neighbors=None, neighbor_batch=None, cbv_indices=np.arange(1, 9), ext_dm=None,
                               cadence_mask=None, alpha_bounds=(1e-4, 1e4), target_over_score=0.5, target_under_score=0.5,
                               max_iter=100, frequency=None, seed=0, first_target=0, stream_id=0, neighbor_alpha=1e-20, sigma=5,
-                              niters=5, max_scratch_bytes=None, return_trace=False):
+                              niters=5, max_scratch_bytes=None, return_trace=False, cadenceno=None):
         """``CBVCorrector.correct`` (reference cbvcorrector.py:397-500) for every target of the batch: a bounded Brent search
         of the ridge penalty alpha PER TARGET over ``-(leaky(over, target_over_score) + leaky(under, target_under_score))``
         (``correctors.cbvcorrector.minimize_scalar_bounded`` is the search; every target visits the abscissae that function
@@ -922,9 +1087,23 @@ class DeviceLightCurveBatch(object):
         info = dict(alpha[B], over_fitting_score[B], under_fitting_score[B], objective[B] (the search's best value), nfev[B],
         status[B] (0, or 1 = ``max_iter`` reached)); ``return_trace`` adds trace = dict(alpha[I, B], over[I, B],
         under[I, B]), the I lockstep evaluations (a skipped score is 1.0 there).  Every argument is checked before the first
-        device call."""
+        device call.
+
+        ``cadenceno``: the cadence numbers of the rows of ``cbvs``.  The batch may then be RAGGED and is matched by its own cadence
+        numbers once (``cbv_correct(cadenceno=)``); ``cadence_mask`` is ragged (bool (sum n,) or a ``DeviceBuffer``); the fit, the
+        over-fitting session and the under-fitting pair pass run on the batch's own offsets and on the grid
+        (``under_fitting_metric(cadenceno=)``: a target meets its neighbours on the cadences it and all of them have); a
+        ``neighbor_batch`` is matched to the grid by its own cadence numbers.  The matrix, the mask, the rows and the kept cadences
+        are uploaded once; per step still 8 bytes per target go up and 16 come back.  info gains n_common[B] (-1 when the
+        under-fitting score is skipped).  A batch in which every target has every grid row gives, without a mask, the bits of the
+        call without ``cadenceno`` (under a mask the under-fitting sums run in grid order, not in kept order: equal within
+        rounding, the over-fitting scores still bit for bit)."""
         from .correctors.cbvcorrector import BoundedBrentBatch
         Xa = _cbv_columns(cbvs, cbv_indices, ext_dm)
+        if cadenceno is not None:
+            return self._cbv_correct_optimized_rows(Xa, neighbors, neighbor_batch, cadence_mask, alpha_bounds, target_over_score,
+                                                    target_under_score, max_iter, frequency, seed, first_target, stream_id,
+                                                    neighbor_alpha, sigma, niters, max_scratch_bytes, return_trace, cadenceno)
         N = self._uniform_n(Xa.shape[0], "cbv_correct_optimized")
         B, K = len(self), Xa.shape[1]
         lo, hi = float(alpha_bounds[0]), float(alpha_bounds[1])
@@ -1028,6 +1207,203 @@ class DeviceLightCurveBatch(object):
         if return_trace:
             info["trace"] = {k: np.array(v, dtype=np.float64).reshape(len(v), B) for k, v in trace.items()}
         return out, info
+
+    # ---------------------------------------------------------------- the goodness metrics and the search, ragged
+    def _goodness_rows_setup(self, Nx, cadenceno, cadence_mask, n_samples, frequency, seed, first_target, stream_id, what):
+        """The front end the ragged scan and search share: the checks that need no device, ONE alignment, then the kept cadences
+        of the aligned batch -> (src, d_rows, d_cm, keep, keep_idx, k_off, d_keep, grid or None)."""
+        if not getattr(self, "nan_free", False):
+            raise ValueError("%s needs a NaN-free batch: call remove_nans() first" % what)
+        if getattr(self, "d_flux_err", None) is None:
+            raise ValueError("%s needs flux errors (the ridge width is median(flux_err) / sqrt(|alpha|))" % what)
+        if Nx > _capi.UNDERFIT_GRID_MAX_NX:
+            raise ValueError("%s: the grid has %d cadences, at most %d are taken" % (what, Nx, _capi.UNDERFIT_GRID_MAX_NX))
+        host_mask = None if isinstance(cadence_mask, DeviceBuffer) else cadence_mask
+        if host_mask is not None and np.shape(host_mask) != (self.n_cadences,):
+            raise ValueError("%s: with `cadenceno` cadence_mask is ragged, one entry per cadence of the batch: shape (%d,) (got %s)"
+                             % (what, self.n_cadences, np.shape(host_mask)))
+        _capi.overfit_rows_arguments(self.n_off, n_samples, host_mask, frequency, seed, first_target, stream_id)
+        src, d_rows, d_cm, keep = self._aligned(Nx, None, cadenceno, cadence_mask, what)
+        if d_cm is not None and (host_mask is None or src.n_cadences != self.n_cadences):
+            host_mask = d_cm.download(np.uint8, src.n_cadences, stream=self.stream)     # once: it lists the kept cadences
+        keep_idx, k_off, grid = _capi.overfit_rows_arguments(src.n_off, n_samples, host_mask, frequency, seed, first_target, stream_id)
+        d_keep = None
+        if keep_idx is not None:
+            d_keep, k = _upload(self.handle, keep_idx, self.stream, np.int32)
+            keep.append(k)
+        return src, d_rows, d_cm, keep, keep_idx, k_off, d_keep, grid
+
+    def _underfit_grid_direct(self, Nx, d_rows, d_cm, M, d_nb, d_nc, d_metric):
+        """``lk_underfit_grid_neighbors_batch_dev`` of this aligned batch against its own targets, into ``d_metric``."""
+        p = lambda buf: _vp(buf.ptr if buf is not None else None)
+        _capi._check(_capi._lib.lk_underfit_grid_neighbors_batch_dev(
+            self.handle._h, len(self), _off_ptr(self.n_off), _vp(d_rows.ptr), Nx, _vp(self.d_flux.ptr), p(d_cm), M, p(d_nb), None,
+            p(d_nc), _vp(d_metric.ptr), _vp(self.stream or None)))
+
+    def _cbv_goodness_scan_rows(self, Xa, alphas, neighbors, cadenceno, cadence_mask, n_samples, seed, frequency, first_target,
+                                sigma, niters, max_scratch_bytes):
+        what = "cbv_goodness_scan"
+        B, (Nx, K) = len(self), Xa.shape
+        nb = None if neighbors is None else _capi.underfit_arguments(B, max(Nx, 2), neighbors)[0]
+        src, d_rows, d_cm, keep, keep_idx, k_off, d_keep, grid = self._goodness_rows_setup(
+            Nx, cadenceno, cadence_mask, n_samples, frequency, seed, first_target, 0, what)
+        h = self.handle
+        if grid is None:      # the default grid depends on the times alone: taken once for the whole scan
+            grid = _capi.overfit_grid(src._overfit_rows_default_grid(keep_idx, k_off))
+        d_X, k = _upload(h, Xa, self.stream)
+        keep.append(k)
+        d_nb = None
+        if nb is not None and nb.shape[1]:
+            d_nb, k = _upload(h, nb, self.stream, np.int32)
+            keep.append(k)
+        over = np.empty((len(alphas), B))
+        under = np.empty((len(alphas), B)) if nb is not None else None
+        n_common = np.empty((len(alphas), B), dtype=np.int32) if nb is not None else None
+        d_under, d_nc = DeviceBuffer(h, B * 8), DeviceBuffer(h, B * 4)
+        for a, alpha in enumerate(alphas):
+            held = []
+            d_mu, d_sg = src._ridge_prior(None, K, float(alpha), None, held)
+            cor = src._regress_shared_rows(Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, False, held, resident=d_X)[0]
+            d_over = cor._over_fitting_rows(src, grid, n_samples, keep_idx, k_off, d_keep, seed, first_target, a, False,
+                                            max_scratch_bytes)
+            if nb is not None:
+                cor._underfit_grid_direct(Nx, d_rows, d_cm, nb.shape[1], d_nb, d_nc, d_under)
+            over[a] = d_over.download(np.float64, B, stream=self.stream)
+            if nb is not None:
+                under[a] = d_under.download(np.float64, B, stream=self.stream)
+                n_common[a] = d_nc.download(np.int32, B, stream=self.stream)
+            cor.synchronize()
+        self.synchronize()
+        return dict(alpha=alphas, over_fitting=over, under_fitting=under, n_common=n_common)
+
+    def _cbv_correct_optimized_rows(self, Xa, neighbors, neighbor_batch, cadence_mask, alpha_bounds, target_over_score,
+                                    target_under_score, max_iter, frequency, seed, first_target, stream_id, neighbor_alpha, sigma,
+                                    niters, max_scratch_bytes, return_trace, cadenceno):
+        """``cbv_correct_optimized(cadenceno=)``: the uniform method's steps on the batch's own offsets and on the grid."""
+        from .correctors.cbvcorrector import BoundedBrentBatch
+        what = "cbv_correct_optimized"
+        B, (Nx, K) = len(self), Xa.shape
+        lo, hi = float(alpha_bounds[0]), float(alpha_bounds[1])
+        if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
+            raise ValueError("alpha_bounds must be two finite penalties, lower first (got %r)" % (tuple(alpha_bounds),))
+        if int(max_iter) < 1:
+            raise ValueError("max_iter must be >= 1 (got %r)" % (max_iter,))
+        t_over, t_under = float(target_over_score), float(target_under_score)
+        do_over, do_under = t_over > 0, t_under > 0
+        if do_under and neighbors is None:
+            raise ValueError("target_under_score > 0 needs `neighbors` (and `neighbor_batch`, or this batch's own targets corrected "
+                             "at neighbor_alpha): pass target_under_score=0 to search on the over-fitting metric alone")
+        if not np.isfinite(float(neighbor_alpha)):
+            raise ValueError("neighbor_alpha must be finite (got %r)" % (neighbor_alpha,))
+        nb = Bn = None
+        if do_under:
+            Bn = B
+            if neighbor_batch is not None:
+                if not isinstance(neighbor_batch, DeviceLightCurveBatch):
+                    raise ValueError("%s: `neighbor_batch` must be a resident DeviceLightCurveBatch" % what)
+                if not getattr(neighbor_batch, "nan_free", False):
+                    raise ValueError("%s needs a NaN-free neighbor_batch: call remove_nans() first (and cotrend after it)" % what)
+                if getattr(neighbor_batch, "d_cadenceno", None) is None:
+                    raise ValueError("%s(cadenceno=) needs a neighbor_batch that carries cadence numbers" % what)
+                Bn = len(neighbor_batch)
+            nb = _capi.underfit_arguments(B, max(Nx, 2), neighbors, None, Bn)[0]
+        src, d_rows, d_cm, keep, keep_idx, k_off, d_keep, grid = self._goodness_rows_setup(
+            Nx, cadenceno, cadence_mask, 10, frequency, seed, first_target, stream_id, what)
+        # ---- resident once: X, the neighbour rows, the over-fitting session (the mask, the rows and keep_idx already are)
+        h, st = self.handle, _vp(self.stream or None)
+        d_X, k = _upload(h, Xa, self.stream)
+        keep.append(k)
+        d_nb = d_block = d_sess = None
+        p_keep = _vp(d_keep.ptr if d_keep is not None else None)
+        p_koff = _off_ptr(k_off) if keep_idx is not None else None
+
+        def fit(alphas, alpha=None):
+            held = []
+            d_mu, d_sg = src._ridge_prior(None, K, alpha, alphas, held)
+            return src._regress_shared_rows(Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, False, held, resident=d_X)[0]
+
+        if do_over:
+            if grid is None:
+                grid = _capi.overfit_grid(src._overfit_rows_default_grid(keep_idx, k_off))
+            sess_bytes, _r = ctypes.c_int64(0), ctypes.c_int(0)
+            _capi._check(_capi._lib.lk_overfit_session_rows_bytes(B, _off_ptr(k_off), grid[2], 1, int(max_scratch_bytes or 0),
+                                                                  ctypes.byref(sess_bytes), ctypes.byref(_r)))
+            sess_bytes = sess_bytes.value
+            d_sess = DeviceBuffer(h, sess_bytes)
+            _capi._check(_capi._lib.lk_overfit_session_begin_rows_dev(
+                h._h, B, _off_ptr(src.n_off), _vp(src.d_time.ptr), _vp(src.d_flux.ptr), p_keep, p_koff, grid[0], grid[1], grid[2], 1,
+                int(seed), int(first_target), int(stream_id), _vp(d_sess.ptr), sess_bytes, st))
+        M = 0
+        if do_under:
+            M = nb.shape[1]
+            if M:
+                d_nb, k = _upload(h, nb, self.stream, np.int32)
+                keep.append(k)
+            if neighbor_batch is None:
+                # this batch's own targets at neighbor_alpha: the same cadences, so the same rows and the same mask
+                nbr = fit(None, float(neighbor_alpha))
+                d_block = nbr._underfit_grid_block(Nx, d_rows, d_cm, self.stream)
+                keep += [nbr.d_flux]
+            else:
+                d_block, nkeep = neighbor_batch._underfit_grid_rows(Nx, cadenceno, self.stream)
+                keep += nkeep
+        # ---- the lockstep search
+        brent = BoundedBrentBatch((lo, hi), B, maxiter=int(max_iter))
+        d_scores = DeviceBuffer(h, 2 * B * 8)
+        d_nc = DeviceBuffer(h, B * 4)
+        scores = np.ones((2, B))
+        trace = dict(alpha=[], over=[], under=[])
+
+        def under_eval(cor, d_metric, offset):
+            cor._underfit_grid_against(Nx, d_rows, d_cm, Bn, d_block, M, d_nb, None, d_nc, d_metric, metric_offset=offset)
+
+        while not brent.done.all():
+            alphas = brent.x.copy()
+            cor = fit(alphas)
+            if do_over:
+                _capi._check(_capi._lib.lk_overfit_session_eval_rows_dev(
+                    h._h, B, _off_ptr(src.n_off), _vp(cor.d_flux.ptr), _vp(cor.d_flux_err.ptr), p_keep, p_koff, grid[0], grid[1],
+                    grid[2], 1, _vp(d_sess.ptr), sess_bytes, _vp(d_scores.ptr), st))
+            if do_under:
+                under_eval(cor, d_scores, B * 8)
+            if do_over and do_under:
+                d_scores.download(np.float64, 2 * B, out=scores.reshape(-1), stream=self.stream)
+            elif do_over or do_under:
+                d_scores.download(np.float64, B, out=scores[0 if do_over else 1], stream=self.stream,
+                                  offset_bytes=0 if do_over else B * 8)
+            cor.synchronize()
+            brent.tell(-(_leaky_scores(scores[0], t_over) + _leaky_scores(scores[1], t_under)))
+            if return_trace:
+                trace["alpha"].append(alphas), trace["over"].append(scores[0].copy()), trace["under"].append(scores[1].copy())
+        res = brent.result()
+        # ---- the fit at the optimum and its scores
+        out = fit(res["x"])
+        over, under, n_common = np.full(B, -1.0), np.full(B, -1.0), np.full(B, -1, dtype=np.int32)
+        if do_over:
+            over = out._over_fitting_rows(src, grid, 10, keep_idx, k_off, d_keep, seed, first_target, stream_id, True, max_scratch_bytes)
+        if do_under:
+            d_under = DeviceBuffer(h, B * 8)
+            under_eval(out, d_under, 0)
+            under = d_under.download(np.float64, B, stream=self.stream)
+            n_common = d_nc.download(np.int32, B, stream=self.stream)
+        out._keep += keep + [d_X, d_rows, d_cm, d_keep, d_nb, d_block, d_sess, src.d_flux, src.d_time]
+        info = dict(alpha=res["x"], over_fitting_score=over, under_fitting_score=under, objective=res["fun"], nfev=res["nfev"],
+                    status=res["status"], n_common=n_common)
+        if return_trace:
+            info["trace"] = {k: np.array(v, dtype=np.float64).reshape(len(v), B) for k, v in trace.items()}
+        return out, info
+
+    def _underfit_grid_block(self, Nx, d_rows, d_cm, stream):
+        """This ALIGNED batch's light curves (rows ``d_rows``, mask ``d_cm``) prepared as grid neighbour rows -> their
+        ``DeviceBuffer`` (queued on ``stream``)."""
+        h = self.handle
+        nbytes = ctypes.c_int64(0)
+        _capi._check(_capi._lib.lk_underfit_grid_rows_bytes(len(self), Nx, ctypes.byref(nbytes)))
+        d_block = DeviceBuffer(h, nbytes.value)
+        _capi._check(_capi._lib.lk_underfit_grid_rows_prepare_dev(h._h, len(self), _off_ptr(self.n_off), _vp(d_rows.ptr), Nx,
+                                                                  _vp(self.d_flux.ptr), _vp(d_cm.ptr if d_cm is not None else None),
+                                                                  _vp(d_block.ptr), nbytes.value, _vp(stream or None)))
+        return d_block
 
     # ---------------------------------------------------------------- SFF
     def _centroid_buffer(self, c, what):

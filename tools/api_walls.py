@@ -74,7 +74,19 @@ target, `from_arrays`.  Written to profiles/sff_walls.txt.
 20000) cadences with about 3 % of them missing per target, `LK_WALLS_K` (default 17) columns, in ONE process, the routes
 alternating, `LK_WALLS_REPS` (default 2) times after one warm-up.  S `from_arrays(cadenceno=)` ->
 `cbv_correct(cadenceno=grid)`: one shared matrix; T the route a ragged batch had before: `X[rows_b]` per target ->
-`regression_correct_batch` on the stacked copies.  Written to profiles/cbvragged_walls.txt."""
+`regression_correct_batch` on the stacked copies.  Written to profiles/cbvragged_walls.txt.
+
+`underfit_ragged`: the under-fitting metric of a RAGGED batch of that shape (`LK_WALLS_M`, default 50, nearest neighbours), in ONE
+process, the routes alternating, `LK_WALLS_REPS` (default 3) times after one warm-up.  R the resident call
+`under_fitting_metric(neighbors, cadenceno=grid)`; H the route a ragged batch had before: `to_host()`, the neighbours brought onto
+each target's cadences (NaN where a neighbour lacks one) and `underfit_metric_neighbors` per target, 16 threads.  Written to
+profiles/underfit_ragged_walls.txt.
+
+`cbvopt_ragged`: the per-target ridge search of a ragged batch of that shape (`LK_WALLS_K`, default 16, basis vectors; `LK_WALLS_M`
+neighbours), `LK_WALLS_REPS` (default 2) times after one warm-up.  O `cbv_correct_optimized(cadenceno=grid)`, the whole search; H
+ONE evaluation of its objective the way a ragged batch had it: the resident ragged fit, `to_host()`, then
+`underfit_metric_neighbors` (16 threads) and `overfit_metric_lombscargle` (sequential) per target on the host, over the first
+`LK_WALLS_HOST_TARGETS` (default: all) targets.  Written to profiles/cbvopt_ragged_walls.txt."""
 import cProfile
 import io
 import os
@@ -752,6 +764,152 @@ def cbvragged():
     sys.stdout.flush()
 
 
+def ragged_field_for_walls(B, N, M, K):
+    """B targets on a grid of N cadences, ~3 % of them missing per target (the shape of `cbvragged`), K basis vectors of which four
+    carry systematics, M nearest neighbours -> dict of packed host arrays."""
+    from lightkurve_amd.correctors import metrics
+    rng = np.random.default_rng(23)
+    t = np.linspace(0.0, 27.0, N)
+    x = t / 27 - 0.5
+    S = np.column_stack([np.sin(2 * np.pi * t / p) for p in np.linspace(3.1, 41.0, K - 1)] + [x ** 2])
+    amp = rng.normal(0, 0.01, (B, K)) * (np.arange(K) < 4)
+    scale = 1000.0 * rng.uniform(0.5, 2, B)
+    grid = 100000 + np.arange(N, dtype=np.int32)
+    rows = [np.flatnonzero(rng.random(N) >= 0.03).astype(np.int32) for _ in range(B)]
+    n_off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    flux = np.concatenate([scale[b] * (1 + S[r] @ amp[b] + 1e-3 * rng.standard_normal(len(r))) for b, r in enumerate(rows)])
+    allrows = np.concatenate(rows)
+    nb = metrics.nearest_neighbors(rng.uniform(0, 1, B), rng.uniform(0, 1, B), M)
+    return dict(t=t, S=S, grid=grid, rows=rows, n_off=n_off, flux=flux, err=1e-3 * flux, time=t[allrows], cad=grid[allrows], nb=nb)
+
+
+def host_underfit_ragged(lcb, rows, nb, t, Nx, targets):
+    """The route a ragged batch had before: the downloaded batch (``to_host()``), the neighbours brought onto each target's cadences
+    (NaN where a neighbour lacks one) and ``underfit_metric_neighbors`` per target, 16 threads -> metric[len(targets)]."""
+    from concurrent.futures import ThreadPoolExecutor
+    from lightkurve_amd.correctors import metrics
+    from lightkurve_amd.lightcurve import LightCurve
+    B = len(rows)
+    z = np.full((B, Nx), np.nan)
+    for b in range(B):
+        f = lcb.flux[lcb.n_off[b]:lcb.n_off[b + 1]]
+        z[b, rows[b]] = f / np.median(f) - 1.0
+
+    def one(b):
+        r = rows[b]
+        f = lcb.flux[lcb.n_off[b]:lcb.n_off[b + 1]]
+        return metrics.underfit_metric_neighbors(LightCurve(t[r], f), z[nb[b][nb[b] >= 0]][:, r].T)
+
+    with ThreadPoolExecutor(max_workers=16) as ex:
+        return np.array(list(ex.map(one, targets)))
+
+
+def write_walls(name, lines):
+    print("\n".join(lines))
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", name), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    sys.stdout.flush()
+
+
+def underfit_ragged():
+    from lightkurve_amd import _capi
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    B, N, M = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000"), ("LK_WALLS_M", "50")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "3"))
+    f = ragged_field_for_walls(B, N, M, 3)
+    nb, grid, M = f["nb"], f["grid"], f["nb"].shape[1]
+    raw = DeviceLightCurveBatch.from_arrays(f["time"], f["flux"], f["err"], f["n_off"], cadenceno=f["cad"]).remove_nans()
+    cor = raw.cbv_correct(f["S"], cbv_indices=[1, 2], cadenceno=grid)[0]
+    cor.synchronize()
+    sync = _capi.Handle.get(0).synchronize
+    pitch = -(-N // 128) * 128
+
+    def host_route():
+        return host_underfit_ragged(cor.to_host(), f["rows"], nb, f["t"], N, range(B))
+
+    got, n_common = cor.under_fitting_metric(nb, cadenceno=grid, return_common=True)          # warm-up of both routes
+    cor.under_fitting_metric(nb, cadenceno=grid, to_host=False)
+    sync()
+    ref = host_route()
+    R, R2, H = [], [], []
+    for _ in range(reps):
+        R.append(timed(lambda: cor.under_fitting_metric(nb, cadenceno=grid))[0])              # (the download synchronises)
+        R2.append(timed(lambda: (cor.under_fitting_metric(nb, cadenceno=grid, to_host=False), sync()))[0])
+        H.append(timed(host_route)[0])
+    write_walls("underfit_ragged_walls.txt", [
+        "under-fitting metric of a ragged batch: %d cotrended targets on a grid of %d cadences (%d kept in all, %.1f %% missing), "
+        "%d neighbours each; common cadences per target %d..%d" % (B, N, int(f["n_off"][-1]), 100.0 * (1 - f["n_off"][-1] / (B * N)), M,
+                                                                   n_common.min(), n_common.max()),
+        "  the pair pass reads %.2f GB of z rows (B M pitch 8) and %.1f MB of presence words; scratch %.1f MB (rows + words + the "
+        "inverse map)" % (B * M * pitch * 8 / 1e9, B * M * pitch / 8 / 1e6, (B * pitch * 8 + B * pitch / 8 + B * N * 4) / 1e6),
+        "  R  batch.under_fitting_metric(cadenceno=grid) -> metric[B] on the host (aligns, prepares, pairs)   %s" % spread(R),
+        "  R' the same, to_host=False + synchronise                                                          %s" % spread(R2),
+        "  H  to_host() + neighbours onto each target's cadences + underfit_metric_neighbors, 16 threads     %s" % spread(H),
+        "  max |R - H| = %.3e; metric min %.4f median %.4f; H / R = %.0f"
+        % (float(np.max(np.abs(got - ref))), got.min(), float(np.median(got)), np.median(H) / np.median(R))])
+
+
+def cbvopt_ragged():
+    from lightkurve_amd import _capi
+    from lightkurve_amd.correctors import metrics
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    from lightkurve_amd.lightcurve import LightCurve
+    B, N, K, M = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000"), ("LK_WALLS_K", "16"),
+                                                         ("LK_WALLS_M", "50")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "2"))
+    Hn = min(B, int(os.environ.get("LK_WALLS_HOST_TARGETS", str(B))))       # the host route's over-fitting loop is sequential
+    f = ragged_field_for_walls(B, N, M, K)
+    nb, grid, S = f["nb"], f["grid"], f["S"]
+    raw = DeviceLightCurveBatch.from_arrays(f["time"], f["flux"], f["err"], f["n_off"], cadenceno=f["cad"]).remove_nans()
+    raw.synchronize()
+    sync = _capi.Handle.get(0).synchronize
+    kw = dict(neighbors=nb, cbv_indices=np.arange(1, K + 1), cadenceno=grid)
+    out, info = raw.cbv_correct_optimized(S, **kw)                                       # warm-up; the search is deterministic
+    steps = int(info["nfev"].max())
+    alpha = float(np.median(info["alpha"]))
+
+    def host_evaluation():
+        """ONE evaluation of the objective the way a ragged batch had it: the resident ragged fit, then both metrics per target on
+        the host (the under-fitting metric against the other targets of the same correction)."""
+        cor = raw.cbv_correct(S, cbv_indices=np.arange(1, K + 1), alpha=alpha, cadenceno=grid)[0]
+        lcb, lc0 = cor.to_host(), raw.to_host()
+        under = host_underfit_ragged(lcb, f["rows"], nb, f["t"], N, range(Hn))
+        over = np.empty(Hn)
+        for b in range(Hn):
+            a, z = int(lcb.n_off[b]), int(lcb.n_off[b + 1])
+            over[b] = metrics.overfit_metric_lombscargle(LightCurve(lcb.time[a:z], lc0.flux[a:z], lcb.flux_err[a:z]),
+                                                         LightCurve(lcb.time[a:z], lcb.flux[a:z], lcb.flux_err[a:z]), n_samples=1)
+        return over, under
+
+    scan = raw.cbv_goodness_scan(S, [alpha], neighbors=nb, cbv_indices=np.arange(1, K + 1), n_samples=1, cadenceno=grid)
+    sync()
+    h_over, h_under = host_evaluation()
+    O, H = [], []
+    for _ in range(reps):
+        O.append(timed(lambda: (raw.cbv_correct_optimized(S, **kw), sync()))[0])
+        H.append(timed(host_evaluation)[0])
+    write_walls("cbvopt_ragged_walls.txt", [
+        "per-target ridge search of a ragged batch: %d targets on a grid of %d cadences (%d kept in all, %.1f %% missing), %d basis "
+        "vectors + constant, %d neighbours, bounds (1e-4, 1e4)" % (B, N, int(f["n_off"][-1]), 100.0 * (1 - f["n_off"][-1] / (B * N)), K,
+                                                                    nb.shape[1]),
+        "  evaluations per target: min %d median %d max %d (= lockstep evaluations); status counts %s; common cadences %d..%d"
+        % (info["nfev"].min(), int(np.median(info["nfev"])), steps, np.bincount(info["status"], minlength=3).tolist(),
+           info["n_common"].min(), info["n_common"].max()),
+        "  alpha: min %.3g median %.3g max %.3g; over-fitting score median %.4f, under-fitting score median %.4f"
+        % (info["alpha"].min(), float(np.median(info["alpha"])), info["alpha"].max(), float(np.median(info["over_fitting_score"])),
+           float(np.median(info["under_fitting_score"]))),
+        "  O  batch.cbv_correct_optimized(cadenceno=grid), the whole call (%d lockstep evaluations)                  %s"
+        % (steps, spread(O)),
+        "  H  ONE evaluation at alpha = %.3g the way it was: cbv_correct(cadenceno=) + to_host() + both metrics per target on the "
+        "host, %d of %d targets (under-fitting 16 threads, over-fitting sequential)   %s" % (alpha, Hn, B, spread(H)),
+        "  O per lockstep evaluation %.2f ms; H per evaluation / O per evaluation = %.0f (H over %d targets, O over %d)"
+        % (1e3 * np.median(O) / steps, np.median(H) / (np.median(O) / steps), Hn, B),
+        "  at that alpha, resident scan against the host route: max |under-fitting R - H| = %.3e; over-fitting median R %.4f, H %.4f "
+        "(different noise: equal in distribution), max |R - H| = %.3e"
+        % (float(np.max(np.abs(scan["under_fitting"][0][:Hn] - h_under))), float(np.median(scan["over_fitting"][0][:Hn])),
+           float(np.median(h_over)), float(np.max(np.abs(scan["over_fitting"][0][:Hn] - h_over))))])
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -781,6 +939,10 @@ def main():
         sff()
     if "cbvragged" in which:
         cbvragged()
+    if "underfit_ragged" in which:
+        underfit_ragged()
+    if "cbvopt_ragged" in which:
+        cbvopt_ragged()
     if "flatten" in which:
         lcs = []
         for i in range(1000):
