@@ -37,6 +37,8 @@
  *                           'background'): zero-padded pixel blocks of one row pitch plus per-cutout counts.  Limits that
  *                           remain: one kept-cadence count per call, every count >= pca_components.
  *   lk_fold_batch*       <- LightCurve.fold, src/lightkurve/lightcurve.py:1089-1214 (astropy TimeSeries.fold + sort).
+ *   lk_fold_bin_plan_batch* / lk_fold_bin_batch* / lk_phase_bin_batch_dev / lk_fold_cycle_batch_dev <- lc.fold(...).bin(...),
+ *                           optionally of the odd or even cycles only: fused without a sort, or on a folded batch (also nanmedian).
  *   lk_pg_logmedian_batch* / lk_pg_boxsmooth_batch* <- Periodogram.smooth, periodogram.py:182-284.
  *   lk_pg_snr_batch_dev / lk_pg_acf_metric_batch_dev / lk_pg_numax_pick_batch_dev / lk_pg_deltanu_batch* <- flatten,
  *                           estimate_numax and estimate_deltanu (seismology/) on spectra that stay in device memory.
@@ -520,6 +522,59 @@ int lk_bin_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const doubl
                      const double *flux_err, const int64_t *bin_off, const double *time_bin_start, const double *edges_sec,
                      int64_t n_edges, double bin_size_sec, const uint8_t *has_err, double *t_out, double *flux_out,
                      double *flux_err_out, void *stream);
+
+/* ---- lc.fold(period, epoch_time).bin(...) (and FoldedLightCurve.cycle / odd_mask / even_mask, lightcurve.py:3213-3250) for
+ * B ragged targets: LightCurve.bin's semantics above applied to the PHASE column, with the edges formed per target.
+ *
+ * Layout of the bins, shared by lk_phase_bin_batch_dev and lk_fold_bin_batch*: target b owns bins [bin_off[b], bin_off[b+1])
+ * of the outputs; its bins start at phase start[b] and are size_sec[b] seconds wide; its n_bins_b + 1 edges, in seconds
+ * relative to start[b] (numpy's cumsum of the bin size, beginning with 0 and strictly increasing), are
+ * edges[bin_off[b] + b ...] (so edges holds bin_off[B] + B values).  All of these are HOST arrays.
+ *
+ * lk_fold_bin_plan_batch*: what the caller needs to form that layout, from ONE pass over the cadences and no sort.  period /
+ * epoch_time / wrap_phase as in lk_fold_batch; plan (HOST, valid on return: the _dev form synchronises `stream`) receives
+ * LK_FOLD_BIN_NPLAN doubles per target: [0] smallest phase (+inf: none), [1] largest phase, [2] number of phases >=
+ * count_from[b] (count_from NULL: all that are not NaN), [3] 1 when a flux_err is finite (flux_err nullable), [4] the smallest
+ * cycle, floor((t - (e - P/2)) / P) with e = epoch_time[b] when epoch_given and the smallest phase otherwise, [5] the largest
+ * finite |flux|, [6] the largest finite |flux_err|, [7] largest minus smallest finite flux. */
+#define LK_FOLD_BIN_NPLAN 8
+int lk_fold_bin_plan_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, const double *flux, const double *flux_err,
+                           const double *period, const double *epoch_time, int epoch_given, double epoch_phase,
+                           const double *wrap_phase, int normalize_phase, const double *count_from, double *plan);
+int lk_fold_bin_plan_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,
+                               const double *flux_err, const double *period, const double *epoch_time, int epoch_given,
+                               double epoch_phase, const double *wrap_phase, int normalize_phase, const double *count_from,
+                               double *plan, void *stream);
+/* cycle[i] = floor((t[order[i]] - (cycle_epoch[b] - P/2)) / P) - cycle_min[b] for every slot of a folded batch (t: the unfolded
+ * times, order: lk_fold_batch's), odd[i] = cycle % 2 == 1, even[i] = cycle % 2 == 0 (bytes, the layout lk_select_batch_dev
+ * takes); each of the three outputs may be NULL.  cycle_epoch / cycle_min (HOST): plan[0] (or epoch_time) and plan[4]. */
+int lk_fold_cycle_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const int64_t *order,
+                            const double *period, const double *cycle_epoch, const double *cycle_min, int64_t *cycle, uint8_t *odd,
+                            uint8_t *even, void *stream);
+/* Bins of a folded batch (phase sorted; flux / flux_err in phase order).  sel (nullable): only the slots with sel[i] ==
+ * sel_value take part.  phase_out = start + (edges[k] + size_sec / 2) / 86400, flux_out = nanmean (median != 0: np.nanmedian),
+ * flux_err_out = sqrt(nansum(err^2) / #finite) where has_err[b], else nanstd of the flux in the bin (for both aggregates),
+ * count_out = slots of the bin that take part; a bin with none holds NaN. */
+int lk_phase_bin_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *phase, const double *flux,
+                           const double *flux_err, const uint8_t *sel, int sel_value, const int64_t *bin_off, const double *start,
+                           const double *size_sec, const double *edges, const uint8_t *has_err, int median, double *phase_out,
+                           double *flux_out, double *flux_err_out, int32_t *count_out, void *stream);
+/* The fused form on the UNFOLDED batch: no sort, no n-sized intermediate, one workgroup per target (foldbin.hip).  plan: what
+ * lk_fold_bin_plan_batch* wrote for the same arguments; cycle_epoch: as in lk_fold_cycle_batch_dev; which: 0 all cadences, 1 /
+ * 2 only those of odd / even cycles.  Outputs as lk_phase_bin_batch_dev's with median == 0: the same layout, counts and NaN
+ * pattern, values within rounding (sums of addends rounded to 2^-63 n max|x|, accumulated as integers: bitwise reproducible and
+ * independent of B).  Up to LK_FOLD_BIN_LDS_BINS bins per target are accumulated in LDS, more in a slab of device scratch. */
+#define LK_FOLD_BIN_LDS_BINS 1024
+int lk_fold_bin_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, const double *flux, const double *flux_err,
+                      const double *period, const double *epoch_time, double epoch_phase, const double *wrap_phase,
+                      int normalize_phase, const double *cycle_epoch, const double *plan, int which, const int64_t *bin_off,
+                      const double *start, const double *size_sec, const double *edges, double *phase_out, double *flux_out,
+                      double *flux_err_out, int32_t *count_out);
+int lk_fold_bin_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,
+                          const double *flux_err, const double *period, const double *epoch_time, double epoch_phase,
+                          const double *wrap_phase, int normalize_phase, const double *cycle_epoch, const double *plan, int which,
+                          const int64_t *bin_off, const double *start, const double *size_sec, const double *edges,
+                          double *phase_out, double *flux_out, double *flux_err_out, int32_t *count_out, void *stream);
 
 /* ---- nanmax / nanargmax over each row of a B x M float64 matrix (first maximum wins) ---------------- */
 int lk_argmax_batch(lk_handle *h, int B, int64_t M, const double *x, double *max_out, int64_t *argmax_out);

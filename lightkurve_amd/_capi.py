@@ -164,6 +164,22 @@ SIGNATURES = [
     ("lk_bin_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _c_ip, _c_dp, _c_dp, ctypes.c_int64, ctypes.c_double, _c_u8p, _vp, _vp, _vp,
       _vp]),
+    ("lk_fold_bin_plan_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int, ctypes.c_double, _c_dp, ctypes.c_int, _c_dp,
+      _c_dp]),
+    ("lk_fold_bin_plan_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _c_dp, _c_dp, ctypes.c_int, ctypes.c_double, _c_dp, ctypes.c_int, _c_dp, _c_dp,
+      _vp]),
+    ("lk_fold_cycle_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _vp, _vp, _c_dp, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
+    ("lk_phase_bin_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_u8p, ctypes.c_int, _vp, _vp,
+      _vp, _vp, _vp]),
+    ("lk_fold_bin_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_double, _c_dp, ctypes.c_int, _c_dp, _c_dp,
+      ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_i32p]),
+    ("lk_fold_bin_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _c_dp, _c_dp, ctypes.c_double, _c_dp, ctypes.c_int, _c_dp, _c_dp, ctypes.c_int,
+      _c_ip, _c_dp, _c_dp, _c_dp, _vp, _vp, _vp, _vp, _vp]),
     ("lk_argmax_batch", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp, _c_ip]),
     ("lk_argmax_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     ("lk_bls_batch", ctypes.c_int,
@@ -849,6 +865,48 @@ def fold_batch(t, n_off, period, epoch_time, epoch_phase=0.0, wrap_phase=None, n
                               _ptr(wrap_phase), int(bool(normalize_phase)), len(cols), cin, cout, _ptr(phase),
                               _ptr(order, _c_ip)))
     return phase, order, outs
+
+
+def fold_bin_batch(t, flux, n_off, period, flux_err=None, epoch_time=None, epoch_phase=0.0, wrap_phase=None,
+                   normalize_phase=False, time_bin_size=None, time_bin_start=None, n_bins=None, bins=None,
+                   aggregate_func="mean", which="all", device=0):
+    """``lc.fold(period, epoch_time, ...).bin(...)`` for B ragged targets on host arrays, fused: no sort and no folded copy
+    (``lk_fold_bin_plan_batch`` + ``lk_fold_bin_batch``).  Arguments as ``DeviceLightCurveBatch.fold_bin``.  Returns
+    dict(phase, flux, flux_err, count, bin_off): target b's bins are ``[bin_off[b]:bin_off[b + 1]]``."""
+    from . import foldbin
+    aggregate_func, which_code = foldbin.check_bin_arguments(time_bin_size, n_bins, bins, aggregate_func, which)
+    if aggregate_func != "mean":
+        raise ValueError("the fused fold_bin supports aggregate_func='mean' only: use fold(...).bin(aggregate_func='median')")
+    h = Handle.get(device)
+    t, flux = _f64(t), _f64(flux)
+    n_off = _offsets(n_off, t.size)
+    B = n_off.size - 1
+    err = None if flux_err is None else _f64(np.broadcast_to(flux_err, t.shape))
+    period = _f64(np.broadcast_to(np.asarray(period, dtype=np.float64), (B,)))
+    if not np.all(np.isfinite(period)) or np.any(period == 0):
+        raise ValueError("period must be finite and non-zero")
+    epoch_given = epoch_time is not None
+    if epoch_time is None:
+        epoch_time = t[np.minimum(n_off[:-1], max(t.size - 1, 0))] if t.size else np.zeros(B)
+    epoch_time = _f64(np.broadcast_to(np.asarray(epoch_time, dtype=np.float64), (B,)))
+    if wrap_phase is None:
+        wrap_phase = np.full(B, 0.5) if normalize_phase else period / 2.0
+    wrap_phase = _f64(np.broadcast_to(np.asarray(wrap_phase, dtype=np.float64), (B,)))
+    cfrom = foldbin.count_from(time_bin_start, bins, B)
+    plan = np.zeros(max(B, 1) * foldbin.NPLAN, dtype=np.float64)
+    _check(_lib.lk_fold_bin_plan_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(t), _ptr(flux), _ptr(err), _ptr(period), _ptr(epoch_time),
+                                       int(epoch_given), float(epoch_phase), _ptr(wrap_phase), int(bool(normalize_phase)),
+                                       _ptr(cfrom), _ptr(plan)))
+    lay = foldbin.phase_bin_layout(np.diff(n_off), plan[:B * foldbin.NPLAN], time_bin_size, time_bin_start, n_bins, bins)
+    cyc_epoch = epoch_time if epoch_given else _f64(plan[:B * foldbin.NPLAN].reshape(B, foldbin.NPLAN)[:, 0])
+    nbt = int(lay["bin_off"][-1])
+    po, fo, eo = (np.full(nbt, np.nan, dtype=np.float64) for _ in range(3))
+    co = np.zeros(nbt, dtype=np.int32)
+    _check(_lib.lk_fold_bin_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(t), _ptr(flux), _ptr(err), _ptr(period), _ptr(epoch_time),
+                                  float(epoch_phase), _ptr(wrap_phase), int(bool(normalize_phase)), _ptr(cyc_epoch), _ptr(plan),
+                                  which_code, _ptr(lay["bin_off"], _c_ip), _ptr(lay["start"]), _ptr(lay["size_sec"]),
+                                  _ptr(lay["edges"]), _ptr(po), _ptr(fo), _ptr(eo), _ptr(co, _c_i32p)))
+    return dict(phase=po, flux=fo, flux_err=eo, count=co, bin_off=lay["bin_off"])
 
 
 # --------------------------------------------------------------------------------------------- BLS

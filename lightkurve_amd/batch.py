@@ -8,7 +8,8 @@ from . import _capi
 from .distributed import all_gather_rows, device_gather_available, shard_bounds, sharded_map, sharded_map_ragged
 from . import packed
 
-__all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "periodogram_peaks", "flatten_batch",
+__all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch",
+           "periodogram_peaks", "flatten_batch",
            "estimate_cdpp_batch", "pld_correct_batch", "regression_correct_batch", "cbv_correct_batch"]
 
 
@@ -244,6 +245,25 @@ def ls_model_batch(lcs, frequency, nterms=1, fit_mean=True, center_data=True, us
                                want_model, want_residual, device=device)
     out["n_off"] = n_off
     return out
+
+
+def fold_bin_batch(lcs, period, epoch_time=None, epoch_phase=0.0, wrap_phase=None, normalize_phase=False, time_bin_size=None,
+                   time_bin_start=None, n_bins=None, bins=None, aggregate_func="mean", which="all", device=0):
+    """``lc.fold(period, epoch_time, ...).bin(...)`` per light curve (reference lightcurve.py:1089-1214, 1558-1763), optionally
+    of the odd or even cycles only, for host light curves: ``lcs`` a list of light curves or a ``LightCurveBatch``; ``period``
+    / ``epoch_time`` / ``wrap_phase`` / ``time_bin_size`` / ``time_bin_start`` / ``n_bins`` scalars or one value per light
+    curve.  The fused kernel (``lk_fold_bin_batch``: no sort, no folded copy) with the arguments and semantics of
+    ``DeviceLightCurveBatch.fold_bin``; ``aggregate_func="mean"`` only.  Returns dict(phase, flux, flux_err, count, bin_off):
+    light curve b's bins are ``[bin_off[b]:bin_off[b + 1]]``.  Not sharded over ranks."""
+    from .ingest import LightCurveBatch
+    if isinstance(lcs, LightCurveBatch):
+        time, flux, err, n_off = lcs.time, lcs.flux, lcs.flux_err, lcs.n_off
+    else:
+        (time, flux, err), n_off = packed.pack_columns(list(lcs), ("time", "flux", "flux_err"), pinned="auto", pool_prefix="foldbin")
+    return _capi.fold_bin_batch(time, flux, n_off, period, flux_err=err, epoch_time=epoch_time, epoch_phase=epoch_phase,
+                                wrap_phase=wrap_phase, normalize_phase=normalize_phase, time_bin_size=time_bin_size,
+                                time_bin_start=time_bin_start, n_bins=n_bins, bins=bins, aggregate_func=aggregate_func,
+                                which=which, device=device)
 
 
 def periodogram_peaks(power, device=0):

@@ -1974,6 +1974,88 @@ int lk_bin_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, con
     return rc ? rc : io.finish();
 }
 
+// ------------------------------------------------------------------------------------------------ fold + bin by phase
+int lk_fold_bin_plan_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,
+                               const double *flux_err, const double *period, const double *epoch_time, int epoch_given,
+                               double epoch_phase, const double *wrap_phase, int normalize_phase, const double *count_from,
+                               double *plan, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::fold_bin_plan_launch(h, B, n_off_host, t, flux, flux_err, period, epoch_time, epoch_given, epoch_phase, wrap_phase,
+                                    normalize_phase, count_from, plan, static_cast<hipStream_t>(stream));
+}
+
+int lk_fold_bin_plan_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, const double *flux, const double *flux_err,
+                           const double *period, const double *epoch_time, int epoch_given, double epoch_phase,
+                           const double *wrap_phase, int normalize_phase, const double *count_from, double *plan) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(t && flux && plan, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B];
+    const double *dt, *df, *de;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).in(df, flux, ntot).in(de, flux_err, ntot).stage();
+    if (rc) return rc;
+    return lk::fold_bin_plan_launch(h, B, n_off, dt, df, de, period, epoch_time, epoch_given, epoch_phase, wrap_phase,
+                                    normalize_phase, count_from, plan, nullptr);
+}
+
+int lk_fold_cycle_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const int64_t *order,
+                            const double *period, const double *cycle_epoch, const double *cycle_min, int64_t *cycle, uint8_t *odd,
+                            uint8_t *even, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::fold_cycle_launch(h, B, n_off_host, t, order, period, cycle_epoch, cycle_min, cycle, odd, even,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int lk_phase_bin_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *phase, const double *flux,
+                           const double *flux_err, const uint8_t *sel, int sel_value, const int64_t *bin_off, const double *start,
+                           const double *size_sec, const double *edges, const uint8_t *has_err, int median, double *phase_out,
+                           double *flux_out, double *flux_err_out, int32_t *count_out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::phase_bin_launch(h, B, n_off_host, phase, flux, flux_err, sel, sel_value, bin_off, start, size_sec, edges, has_err,
+                                median, phase_out, flux_out, flux_err_out, count_out, static_cast<hipStream_t>(stream));
+}
+
+int lk_fold_bin_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,
+                          const double *flux_err, const double *period, const double *epoch_time, double epoch_phase,
+                          const double *wrap_phase, int normalize_phase, const double *cycle_epoch, const double *plan, int which,
+                          const int64_t *bin_off, const double *start, const double *size_sec, const double *edges,
+                          double *phase_out, double *flux_out, double *flux_err_out, int32_t *count_out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::fold_bin_launch(h, B, n_off_host, t, flux, flux_err, period, epoch_time, epoch_phase, wrap_phase, normalize_phase,
+                               cycle_epoch, plan, which, bin_off, start, size_sec, edges, phase_out, flux_out, flux_err_out,
+                               count_out, static_cast<hipStream_t>(stream));
+}
+
+int lk_fold_bin_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, const double *flux, const double *flux_err,
+                      const double *period, const double *epoch_time, double epoch_phase, const double *wrap_phase,
+                      int normalize_phase, const double *cycle_epoch, const double *plan, int which, const int64_t *bin_off,
+                      const double *start, const double *size_sec, const double *edges, double *phase_out, double *flux_out,
+                      double *flux_err_out, int32_t *count_out) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr && bin_off != nullptr, "bad batch description");
+    if (B == 0 || bin_off[B] == 0) return LK_OK;
+    LK_REQUIRE(t && flux && phase_out && flux_out && flux_err_out && count_out, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B], nbin = (size_t)bin_off[B];
+    const double *dt, *df, *de;
+    double *dpo, *dfo, *deo;
+    int32_t *dco;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).in(df, flux, ntot).in(de, flux_err, ntot).out(dpo, phase_out, nbin).out(dfo, flux_out, nbin)
+                 .out(deo, flux_err_out, nbin).out(dco, count_out, nbin).stage();
+    if (rc) return rc;
+    rc = lk::fold_bin_launch(h, B, n_off, dt, df, de, period, epoch_time, epoch_phase, wrap_phase, normalize_phase, cycle_epoch,
+                             plan, which, bin_off, start, size_sec, edges, dpo, dfo, deo, dco, nullptr);
+    return rc ? rc : io.finish();
+}
+
 // ------------------------------------------------------------------------------------------------ SFF
 int lk_cube_centroids_batch_dev(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask,
                                 int mask_stride, double column0, double row0, double *col_out, double *row_out, void *stream) {

@@ -12,19 +12,10 @@
 #include <vector>
 
 #include "block_select.hpp"  // f64_sortable
+#include "fold_phase.hpp"    // np_mod, fold_par, fold_phase (shared with foldbin.hip)
 #include "lk_common.hpp"
 
 namespace lk {
-
-__device__ __forceinline__ double np_mod(double a, double b) {
-    double m = fmod(a, b);
-    if (m != 0.0) {
-        if ((b < 0.0) != (m < 0.0)) m += b;
-    } else {
-        m = copysign(0.0, b);
-    }
-    return m;
-}
 
 struct FoldKey {
     unsigned long long k;  // order-preserving bits of the phase (NaN sorts last, like numpy)
@@ -54,17 +45,11 @@ __global__ __launch_bounds__(1024) void fold_kernel(const double *__restrict__ t
     FoldKey *keys = scratch + scratch_off[b];
     int npad = 1;
     while (npad < n) npad <<= 1;
-    const double P = period[b], ep = epoch_time[b];
-    // astropy: wrap_phase defaults to P/2 (or 0.5 when normalising); in phase units it is multiplied by P
-    const double wrap = normalize_phase ? wrap_phase[b] * P : wrap_phase[b];
-    const double eph = normalize_phase ? epoch_phase * P : epoch_phase;
-    const double shift = P - wrap;
+    const FoldPar fp = fold_par(period[b], epoch_time[b], epoch_phase, wrap_phase[b], normalize_phase);
     for (int i = tid; i < npad; i += nt) {
         FoldKey kk;
         if (i < n) {
-            const double rel = ((t[i] - ep) + eph) + shift;
-            double ph = np_mod(rel, P) - shift;
-            if (normalize_phase) ph = ph / P;
+            const double ph = fold_phase(fp, t[i]);
             phase_out[lo + i] = ph;  // cadence order for now; permuted below
             kk.k = isnan(ph) ? 0xfffffffffffffffeull : f64_sortable(ph == 0.0 ? 0.0 : ph);  // -0.0 == +0.0 for the sort
             kk.i = (unsigned int)i;

@@ -323,6 +323,24 @@ int bin_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, 
                const int64_t *bin_off_host, const double *start_host, const double *edges_host, int64_t n_edges,
                double bin_size_sec, const uint8_t *has_err_host, double *t_out, double *f_out, double *e_out,
                hipStream_t stream);
+// foldbin.hip: fold + bin by phase.  The plan (one pass, no sort; plan_host is valid on return), cycle / odd / even of a folded
+// batch, the bins of a folded batch (median: nanmedian flux) and the fused form on the unfolded batch (include/lkhip.h)
+int fold_bin_plan_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux, const double *err,
+                         const double *period_host, const double *epoch_time_host, int epoch_given, double epoch_phase,
+                         const double *wrap_phase_host, int normalize_phase, const double *count_from_host, double *plan_host,
+                         hipStream_t stream);
+int fold_cycle_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const int64_t *order,
+                      const double *period_host, const double *cycle_epoch_host, const double *cycle_min_host, int64_t *cycle,
+                      uint8_t *odd, uint8_t *even, hipStream_t stream);
+int phase_bin_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *phase, const double *flux, const double *err,
+                     const uint8_t *sel, int sel_value, const int64_t *bin_off_host, const double *start_host,
+                     const double *size_sec_host, const double *edges_host, const uint8_t *has_err_host, int median,
+                     double *phase_out, double *flux_out, double *err_out, int32_t *count_out, hipStream_t stream);
+int fold_bin_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux, const double *err,
+                    const double *period_host, const double *epoch_time_host, double epoch_phase, const double *wrap_phase_host,
+                    int normalize_phase, const double *cycle_epoch_host, const double *plan_host, int which,
+                    const int64_t *bin_off_host, const double *start_host, const double *size_sec_host, const double *edges_host,
+                    double *phase_out, double *flux_out, double *err_out, int32_t *count_out, hipStream_t stream);
 int pg_acf2d_launch(lk_handle *h, int B, int64_t M, const double *power, int n_win, const int *win_start_host, int W,
                     double *acf2d, double *metric, hipStream_t stream);
 // pgsmooth.hip, the resident seismology chain: metric of the 2-D ACF alone; power / background; Gaussian smoothing and

@@ -192,6 +192,16 @@ class FoldedLightCurve(LightCurve):
     def phase(self):
         return self.time
 
+    @property
+    def odd_mask(self):
+        """True for the cadences of odd cycles (``cycle % 2 == 1``), in phase order, as the reference's."""
+        return self.cycle % 2 == 1
+
+    @property
+    def even_mask(self):
+        """True for the cadences of even cycles (``cycle % 2 == 0``)."""
+        return self.cycle % 2 == 0
+
 
 def running_mean(data, window_size):
     """Moving average by differences of the cumulative sum (reference utils.py:374-386)."""

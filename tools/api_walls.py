@@ -86,7 +86,13 @@ profiles/underfit_ragged_walls.txt.
 neighbours), `LK_WALLS_REPS` (default 2) times after one warm-up.  O `cbv_correct_optimized(cadenceno=grid)`, the whole search; H
 ONE evaluation of its objective the way a ragged batch had it: the resident ragged fit, `to_host()`, then
 `underfit_metric_neighbors` (16 threads) and `overfit_metric_lombscargle` (sequential) per target on the host, over the first
-`LK_WALLS_HOST_TARGETS` (default: all) targets.  Written to profiles/cbvopt_ragged_walls.txt."""
+`LK_WALLS_HOST_TARGETS` (default: all) targets.  Written to profiles/cbvopt_ragged_walls.txt.
+
+`foldbin`: the phase-binned folded light curve of `LK_WALLS_B` (default 1000) targets x `LK_WALLS_N` (default 20000) cadences, one
+period per target, `bins=LK_WALLS_BINS` (default 201), in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5) times
+after one warm-up.  F the fused `batch.fold_bin(period, bins=)`; S `batch.fold(period).bin(bins=)` (sort, gathers, bins); H the host
+route: `to_host()`, then numpy fold + bin per target on 16 threads.  Every timed region ends with the binned curves on the host.
+Written to profiles/foldbin_walls.txt."""
 import cProfile
 import io
 import os
@@ -910,6 +916,72 @@ def cbvopt_ragged():
            float(np.median(h_over)), float(np.max(np.abs(scan["over_fitting"][0][:Hn] - h_over))))])
 
 
+def foldbin():
+    from concurrent.futures import ThreadPoolExecutor
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    B, N, bins = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000"), ("LK_WALLS_BINS", "201")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "5"))
+    rng = np.random.default_rng(23)
+    t = 1000.0 + 0.0204 * np.arange(N)
+    period = rng.uniform(0.7, 12.0, B)
+    flux = 1.0 + 3e-4 * rng.standard_normal((B, N)) - 0.005 * (np.abs((t[None] - t[0]) / period[:, None] % 1.0 - 0.5) > 0.49)
+    err = np.full((B, N), 3e-4)
+    n_off = np.arange(B + 1, dtype=np.int64) * N
+    raw = DeviceLightCurveBatch.from_arrays(np.tile(t, B), flux.ravel(), err.ravel(), n_off)
+
+    def fused():
+        return raw.fold_bin(period, bins=bins).to_host()
+
+    def sorted_then_binned():
+        return raw.fold(period).bin(bins=bins).to_host()
+
+    def one(host, b):
+        a, z = int(host.n_off[b]), int(host.n_off[b + 1])
+        tt, ff, ee, P = host.time[a:z], host.flux[a:z], host.flux_err[a:z], period[b]
+        ph = np.mod((tt - tt[0]) + P / 2.0, P) - P / 2.0
+        o = np.argsort(ph, kind="stable")
+        ph, ff, ee = ph[o], ff[o], ee[o]
+        size = (ph[-1] - ph[0]) * ph.size / ((ph.size - 1) * bins) * 86400.0
+        rel = (ph - ph[0]) * 86400.0
+        nb = int(np.ceil(rel[-1] / size))
+        edges = np.cumsum(np.hstack([0.0, np.repeat(size, nb)]))
+        keep = rel < edges[-1]
+        idx = np.searchsorted(edges, rel[keep]) - 1
+        idx[rel[keep] == 0.0] = 0
+        cnt = np.bincount(idx, minlength=nb)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (np.bincount(idx, ff[keep], minlength=nb) / cnt, np.sqrt(np.bincount(idx, ee[keep] ** 2, minlength=nb) / cnt), cnt)
+
+    def through_host():
+        host = raw.to_host()
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            return list(ex.map(lambda b: one(host, b), range(B)))
+
+    fns = {"F": fused, "S": sorted_then_binned, "H": through_host}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    f, s2 = first["F"], first["S"]
+    same_layout = np.array_equal(f["bin_off"], s2["bin_off"]) and np.array_equal(f["count"], s2["count"]) \
+        and np.array_equal(f["phase"], s2["phase"])
+    rel = float(np.nanmax(np.abs(f["flux"] - s2["flux"]) / np.abs(s2["flux"])))
+    hf = np.concatenate([h[0] for h in first["H"]])
+    hc = np.concatenate([h[2] for h in first["H"]])
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    write_walls("foldbin_walls.txt", [
+        "phase-binned folded light curves, %d targets x %d cadences, one period per target, bins = %d (%.1f MB of input columns, "
+        "%.2f MB of result)" % (B, N, bins, 3 * B * N * 8 / 1e6, f["flux"].size * 28 / 1e6),
+        "  F    batch.fold_bin(period, bins=).to_host(): plan kernel + fused kernel, no sort                %s" % spread(ts["F"]),
+        "  S    batch.fold(period).bin(bins=).to_host(): bitonic sort, two gathers, plan, bin kernel        %s" % spread(ts["S"]),
+        "  H    to_host(), numpy fold + argsort + bin per target on 16 threads                              %s" % spread(ts["H"]),
+        "  F and S: same layout, counts and bin centres: %s; max relative difference of the binned flux %.2e" % (same_layout, rel),
+        "  F and H: same counts: %s; max relative difference of the binned flux %.2e"
+        % (np.array_equal(hc, f["count"]), float(np.nanmax(np.abs(hf - f["flux"]) / np.abs(f["flux"]))) if hf.size == f["flux"].size else np.nan),
+        "  S / F = %.2f; H / F = %.1f" % (med["S"] / med["F"], med["H"] / med["F"])])
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -943,6 +1015,8 @@ def main():
         underfit_ragged()
     if "cbvopt_ragged" in which:
         cbvopt_ragged()
+    if "foldbin" in which:
+        foldbin()
     if "flatten" in which:
         lcs = []
         for i in range(1000):
