@@ -399,6 +399,60 @@ int lk_cdpp_batch(lk_handle *h, int B, const int64_t *n_off, const double *flat_
                   int transit_duration, double *cdpp_out);
 int lk_cdpp_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *flat_flux, const uint8_t *outlier,
                       int transit_duration, double *cdpp_out, void *stream);
+/* ---- fill_gaps and stitch ------------------------------------------------------------------------------------------
+ * LightCurve.fill_gaps(method="gaussian_noise") of lightkurve 2.x (lightcurve.py) for B ragged light curves whose NaN-flux
+ * cadences are already removed, in two calls.  cadenceno == NULL is the reference's time path, cadenceno != NULL its cadence
+ * path; built with -ffp-contract=off, every product and sum below rounds on its own.
+ *
+ * lk_fill_gaps_plan_batch: per light curve m = np.median(np.diff(time)) (exact; even count: mean of the two middle values),
+ * mu = np.nanmean(flux), sd = np.nanstd(flux) and the number of inserted cadences -> stats[4 b + 0..3] (n_inserted as a double);
+ * pos[n_off[b] + i] = index of original cadence i inside the filled light curve; new_off (B + 1, HOST) = offsets of the filled
+ * batch, written before the call returns: the call synchronises `stream`, as lk_select_columns_batch_dev does.  A light curve
+ * with fewer than 2 cadences comes back unchanged (m = NaN).
+ *   time path   times must be non-decreasing.  prev = t[0]; for every next original t: while (t - prev) > 1.2 * m: insert
+ *               prev + m, prev = that; then take t.  The inserted times are that chain of additions (one lane per gap).
+ *   cadence path  cadence numbers must be strictly increasing; the filled light curve holds every c of [c_first, c_last],
+ *               pos = c - c_first.
+ * LK_EINVAL names the first light curve whose order is wrong, or whose median step is not positive / so small against a gap
+ * that one gap would take more than 2^20 or the light curve 2^30 cadences (the reference does not return there).
+ *
+ * lk_fill_gaps_batch: the filled columns.  Originals keep flux, flux_err, quality, cadenceno; their time is t on the time path
+ * and d + m * cf with cf = (double)c, d = t - m * cf on the cadence path (the reference recomputes them).  A cadence inserted
+ * between originals j and j + 1:
+ *   time      time path: its link of the chain.  Cadence path: slope = (d[j+1] - d[j]) / (cf[j+1] - cf[j]),
+ *             nd = slope * (cf - cf[j]) + d[j], time = nd + m * cf  (np.interp's expression, plus m * cf)
+ *   flux_err  slope = (e[j+1] - e[j]) / (t[j+1] - t[j]), slope * (time - t[j]) + e[j] with t the ORIGINAL times (np.interp)
+ *   quality   65536;  cadenceno  c[j] + its place in the gap
+ *   flux      noise_mean[b] + noise_std[b] * g.  g: the generator of lk_overfit_metric_batch, Philox4x32-10 with key (seed &
+ *             0xffffffff, seed >> 32) and counter (i, 0, first_target + b, stream_id), i = the pair index over the inserted
+ *             cadences of THAT light curve: inserted cadence 2 i takes the cosine normal, 2 i + 1 the sine normal.  (The
+ *             reference draws from numpy's global generator: inserted fluxes match it in distribution only.)
+ *   inserted  1 (0 for originals): out[~inserted] are the originals.
+ * flux_err, quality (nullable) go with their outputs; the cadence-path outputs include cadenceno_out (the full range), the
+ * time path takes cadenceno == cadenceno_out == NULL.  stats, pos, new_off: the plan's for the same batch and path (indices are
+ * checked against the new lengths; a foreign plan leaves cadences unwritten).  noise_mean / noise_std: B doubles.  No
+ * floating-point atomics; the order of every sum follows from the light curve's own length: a light curve's output has the
+ * same bits for any B, any neighbours and any run.  Outputs hold new_off[B] elements. */
+int lk_fill_gaps_plan_batch(lk_handle *h, int B, const int64_t *n_off, const double *time, const double *flux, const int32_t *cadenceno,
+                            double *stats, int32_t *pos, int64_t *new_off);
+int lk_fill_gaps_plan_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux,
+                                const int32_t *cadenceno, double *stats, int32_t *pos, int64_t *new_off_host, void *stream);
+int lk_fill_gaps_batch(lk_handle *h, int B, const int64_t *n_off, const int64_t *new_off, const double *time, const double *flux,
+                       const double *flux_err, const int32_t *quality, const int32_t *cadenceno, const double *stats,
+                       const int32_t *pos, const double *noise_mean, const double *noise_std, uint64_t seed, int64_t first_target,
+                       int64_t stream_id, double *time_out, double *flux_out, double *flux_err_out, int32_t *quality_out,
+                       int32_t *cadenceno_out, uint8_t *inserted);
+int lk_fill_gaps_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const int64_t *new_off_host, const double *time,
+                           const double *flux, const double *flux_err, const int32_t *quality, const int32_t *cadenceno,
+                           const double *stats, const int32_t *pos, const double *noise_mean, const double *noise_std, uint64_t seed,
+                           int64_t first_target, int64_t stream_id, double *time_out, double *flux_out, double *flux_err_out,
+                           int32_t *quality_out, int32_t *cadenceno_out, uint8_t *inserted, void *stream);
+/* LightCurveCollection.stitch's vstack for a resident batch: segment s, dst_off[s + 1] - dst_off[s] elements long, of every
+ * column goes from cols_in[c][src_start[s] ..] to cols_out[c][dst_off[s] ..] in ONE launch.  src_start (S), dst_off (S + 1,
+ * prefix offsets from 0) are HOST tables; n_src = elements per input column (every segment is checked against it); ncols <= 8
+ * device pointers in two HOST arrays, elem_bytes[c] (HOST) 4 or 8; out of place. */
+int lk_gather_segments_batch_dev(lk_handle *h, int S, const int64_t *src_start_host, const int64_t *dst_off_host, int64_t n_src,
+                                 int ncols, const int *elem_bytes, const void *const *cols_in, void *const *cols_out, void *stream);
 /* lk_fits_unpack_batch: what the reference's light-curve readers do per file through astropy — Table.read of the BINTABLE
  * (src/lightkurve/io/generic.py:21-207), drop the rows whose TIME is NaN (:98-101), drop the cadences whose quality flag
  * hits the bitmask (io/kepler.py:49-53, io/tess.py:45-48, utils.py:79-115) — for B files at once.  `raw`: the tables' bytes

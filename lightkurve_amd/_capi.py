@@ -144,6 +144,16 @@ SIGNATURES = [
      [_vp, ctypes.c_int, _c_ip, _vp, ctypes.c_int, ctypes.c_int, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_ip, _vp]),
     ("lk_cdpp_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _c_dp, _c_u8p, ctypes.c_int, _c_dp]),
     ("lk_cdpp_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    ("lk_fill_gaps_plan_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_i32p, _c_dp, _c_i32p, _c_ip]),
+    ("lk_fill_gaps_plan_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _vp, _vp, _c_ip, _vp]),
+    ("lk_fill_gaps_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_ip, _c_dp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_dp, _c_i32p, _c_dp, _c_dp, ctypes.c_uint64,
+      ctypes.c_int64, ctypes.c_int64, _c_dp, _c_dp, _c_dp, _c_i32p, _c_i32p, _c_u8p]),
+    ("lk_fill_gaps_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_ip, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int64,
+      ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_gather_segments_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_ip, ctypes.c_int64, ctypes.c_int, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     ("lk_ingest_batch", ctypes.c_int,
      [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_ip, _c_dp]),
     ("lk_ingest_batch_dev", ctypes.c_int,
@@ -1577,6 +1587,69 @@ def cdpp_batch(flat_flux, n_off, outlier=None, transit_duration=13, device=0):
     out = np.empty(B, dtype=np.float64)
     _check(_lib.lk_cdpp_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(y), None if m is None else _ptr(m, _c_u8p),
                               int(transit_duration), _ptr(out)))
+    return out
+
+
+def _i32_column(a, n, name):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if a.shape != (n,):
+        raise ValueError("%s must have one entry per cadence (got shape %s, need (%d,))" % (name, a.shape, n))
+    return a
+
+
+def fill_gaps_plan_batch(time, flux, n_off, cadenceno=None, device=0):
+    """The plan of ``LightCurve.fill_gaps`` for B ragged light curves without NaN flux (``lk_fill_gaps_plan_batch``):
+    -> (stats float64[B, 4] = m, mu, sd, n_inserted; pos int32[sum n] = where every original lands in its filled light curve;
+    new_off int64[B + 1]).  ``cadenceno`` (int32 per cadence) selects the reference's cadence path, None its time path."""
+    h = Handle.get(device)
+    time, flux = _f64(time), _f64(flux)
+    n_off = _offsets(n_off, time.size)
+    if flux.shape != time.shape:
+        raise ValueError("time and flux must have the same length")
+    cad = _i32_column(cadenceno, time.size, "cadenceno")
+    B = n_off.size - 1
+    stats, pos, new_off = np.zeros((B, 4)), np.zeros(time.size, dtype=np.int32), np.zeros(B + 1, dtype=np.int64)
+    _check(_lib.lk_fill_gaps_plan_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(time), _ptr(flux),
+                                        None if cad is None else _ptr(cad, _c_i32p), _ptr(stats), _ptr(pos, _c_i32p),
+                                        _ptr(new_off, _c_ip)))
+    return stats, pos, new_off
+
+
+def fill_gaps_batch(time, flux, n_off, stats, pos, new_off, noise_mean, noise_std, flux_err=None, quality=None, cadenceno=None,
+                    seed=0, first_target=0, stream_id=0, device=0):
+    """The filled columns of ``LightCurve.fill_gaps`` from ``fill_gaps_plan_batch``'s results (``lk_fill_gaps_batch``): inserted
+    cadence j of light curve b gets flux ``noise_mean[b] + noise_std[b] * normal_j`` (Philox stream (seed, first_target + b,
+    stream_id)), flux_err linear in time, quality 65536.  -> dict(time, flux, flux_err, quality, cadenceno (None where the input
+    has none), inserted bool, n_off)."""
+    h = Handle.get(device)
+    time, flux = _f64(time), _f64(flux)
+    n_off = _offsets(n_off, time.size)
+    B, n = n_off.size - 1, time.size
+    new_off = np.ascontiguousarray(new_off, dtype=np.int64)
+    stats, pos = _f64(stats), np.ascontiguousarray(pos, dtype=np.int32)
+    nm, ns = _f64(noise_mean), _f64(noise_std)
+    if flux.shape != time.shape or pos.shape != time.shape or new_off.shape != (B + 1,) or stats.size != 4 * B:
+        raise ValueError("time, flux, pos must have one length and stats / new_off one row per light curve")
+    if nm.shape != (B,) or ns.shape != (B,):
+        raise ValueError("noise_mean and noise_std must hold one value per light curve")
+    err = None if flux_err is None else _f64(flux_err)
+    if err is not None and err.shape != time.shape:
+        raise ValueError("flux_err must have the length of time")
+    q, cad = _i32_column(quality, n, "quality"), _i32_column(cadenceno, n, "cadenceno")
+    nn = int(new_off[-1]) if B else 0
+    out = {"time": np.empty(nn), "flux": np.empty(nn), "flux_err": None if err is None else np.empty(nn),
+           "quality": None if q is None else np.empty(nn, dtype=np.int32),
+           "cadenceno": None if cad is None else np.empty(nn, dtype=np.int32), "inserted": np.zeros(nn, dtype=np.uint8)}
+    opt = lambda a, typ=_c_dp: None if a is None else _ptr(a, typ)     # noqa: E731
+    _check(_lib.lk_fill_gaps_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(new_off, _c_ip), _ptr(time), _ptr(flux), opt(err),
+                                   opt(q, _c_i32p), opt(cad, _c_i32p), _ptr(stats), _ptr(pos, _c_i32p), _ptr(nm), _ptr(ns),
+                                   int(seed), int(first_target), int(stream_id), _ptr(out["time"]), _ptr(out["flux"]),
+                                   opt(out["flux_err"]), opt(out["quality"], _c_i32p), opt(out["cadenceno"], _c_i32p),
+                                   _ptr(out["inserted"], _c_u8p)))
+    out["inserted"] = out["inserted"].astype(bool)
+    out["n_off"] = new_off
     return out
 
 

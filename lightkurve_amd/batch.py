@@ -8,7 +8,7 @@ from . import _capi
 from .distributed import all_gather_rows, device_gather_available, shard_bounds, sharded_map, sharded_map_ragged
 from . import packed
 
-__all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch",
+__all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch", "fill_gaps_batch",
            "periodogram_peaks", "flatten_batch",
            "estimate_cdpp_batch", "pld_correct_batch", "regression_correct_batch", "cbv_correct_batch"]
 
@@ -264,6 +264,18 @@ def fold_bin_batch(lcs, period, epoch_time=None, epoch_phase=0.0, wrap_phase=Non
                                 wrap_phase=wrap_phase, normalize_phase=normalize_phase, time_bin_size=time_bin_size,
                                 time_bin_start=time_bin_start, n_bins=n_bins, bins=bins, aggregate_func=aggregate_func,
                                 which=which, device=device)
+
+
+def fill_gaps_batch(lcs, method="gaussian_noise", noise_std="auto", seed=0, first_target=0, stream_id=0, return_mask=False, device=0):
+    """``lc.fill_gaps(method="gaussian_noise")`` of lightkurve 2.x per light curve, for host light curves: ``lcs`` a list of light
+    curves (the reference's time path) or a ``LightCurveBatch`` (by cadence number when it carries them).  The arguments and
+    semantics of ``DeviceLightCurveBatch.fill_gaps``, through ``lk_fill_gaps_plan_batch`` / ``lk_fill_gaps_batch``.  Returns the
+    filled ``LightCurveBatch`` (with ``return_mask`` also the bool mask of its inserted cadences).  Not sharded over ranks."""
+    from .ingest import LightCurveBatch
+    if not isinstance(lcs, LightCurveBatch):
+        lcs = LightCurveBatch.from_lightcurves(list(lcs))
+    return lcs.fill_gaps(method=method, noise_std=noise_std, seed=seed, first_target=first_target, stream_id=stream_id,
+                         return_mask=return_mask, device=device)
 
 
 def periodogram_peaks(power, device=0):

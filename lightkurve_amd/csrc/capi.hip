@@ -1688,6 +1688,86 @@ int lk_cdpp_batch(lk_handle *h, int B, const int64_t *n_off, const double *flat_
     return rc ? rc : io.finish();
 }
 
+// ------------------------------------------------------------------------------------------------ fillgaps.hip
+int lk_fill_gaps_plan_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux,
+                                const int32_t *cadenceno, double *stats, int32_t *pos, int64_t *new_off_host, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::fill_gaps_plan_launch(h, B, n_off_host, time, flux, cadenceno, stats, pos, new_off_host, static_cast<hipStream_t>(stream));
+}
+
+int lk_fill_gaps_plan_batch(lk_handle *h, int B, const int64_t *n_off, const double *time, const double *flux, const int32_t *cadenceno,
+                            double *stats, int32_t *pos, int64_t *new_off) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr && new_off != nullptr, "bad batch description");
+    if (B == 0) {
+        new_off[0] = 0;
+        return LK_OK;
+    }
+    LK_REQUIRE(n_off[0] == 0 && n_off[B] >= 0, "n_off must be prefix offsets starting at 0");
+    LK_REQUIRE(stats != nullptr && ((time && flux && pos) || n_off[B] == 0), "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B];
+    const double *dt, *df;
+    const int32_t *dc;
+    double *ds;
+    int32_t *dp;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, time, ntot).in(df, flux, ntot).in(dc, cadenceno, ntot).out(ds, stats, (size_t)B * 4).out(dp, pos, ntot).stage();
+    if (rc) return rc;
+    rc = lk::fill_gaps_plan_launch(h, B, n_off, dt, df, dc, ds, dp, new_off, nullptr);
+    return rc ? rc : io.finish();
+}
+
+int lk_fill_gaps_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const int64_t *new_off_host, const double *time,
+                           const double *flux, const double *flux_err, const int32_t *quality, const int32_t *cadenceno,
+                           const double *stats, const int32_t *pos, const double *noise_mean, const double *noise_std, uint64_t seed,
+                           int64_t first_target, int64_t stream_id, double *time_out, double *flux_out, double *flux_err_out,
+                           int32_t *quality_out, int32_t *cadenceno_out, uint8_t *inserted, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::fill_gaps_launch(h, B, n_off_host, new_off_host, time, flux, flux_err, quality, cadenceno, stats, pos, noise_mean,
+                                noise_std, seed, first_target, stream_id, time_out, flux_out, flux_err_out, quality_out,
+                                cadenceno_out, inserted, static_cast<hipStream_t>(stream));
+}
+
+int lk_fill_gaps_batch(lk_handle *h, int B, const int64_t *n_off, const int64_t *new_off, const double *time, const double *flux,
+                       const double *flux_err, const int32_t *quality, const int32_t *cadenceno, const double *stats,
+                       const int32_t *pos, const double *noise_mean, const double *noise_std, uint64_t seed, int64_t first_target,
+                       int64_t stream_id, double *time_out, double *flux_out, double *flux_err_out, int32_t *quality_out,
+                       int32_t *cadenceno_out, uint8_t *inserted) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr && new_off != nullptr, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(n_off[0] == 0 && n_off[B] >= 0 && new_off[0] == 0 && new_off[B] >= n_off[B], "n_off / new_off must be prefix offsets starting at 0");
+    if (new_off[B] == 0) return LK_OK;
+    LK_REQUIRE(stats && noise_mean && noise_std && time && flux && pos && time_out && flux_out && inserted, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B], nnew = (size_t)new_off[B];
+    const double *dt, *df, *de, *ds, *dm, *dn;
+    const int32_t *dq, *dc, *dp;
+    double *ot, *of, *oe;
+    int32_t *oq, *oc;
+    uint8_t *om;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, time, ntot).in(df, flux, ntot).in(de, flux_err, ntot).in(dq, quality, ntot).in(dc, cadenceno, ntot)
+                 .in(ds, stats, (size_t)B * 4).in(dp, pos, ntot).in(dm, noise_mean, (size_t)B).in(dn, noise_std, (size_t)B)
+                 .out(ot, time_out, nnew).out(of, flux_out, nnew).out(oe, flux_err_out, nnew).out(oq, quality_out, nnew)
+                 .out(oc, cadenceno_out, nnew).out(om, inserted, nnew).stage();
+    if (rc) return rc;
+    rc = lk::fill_gaps_launch(h, B, n_off, new_off, dt, df, de, dq, dc, ds, dp, dm, dn, seed, first_target, stream_id, ot, of, oe, oq,
+                              oc, om, nullptr);
+    return rc ? rc : io.finish();
+}
+
+int lk_gather_segments_batch_dev(lk_handle *h, int S, const int64_t *src_start_host, const int64_t *dst_off_host, int64_t n_src,
+                                 int ncols, const int *elem_bytes, const void *const *cols_in, void *const *cols_out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::gather_segments_launch(h, S, src_start_host, dst_off_host, n_src, ncols, elem_bytes, cols_in, cols_out,
+                                      static_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------------------------ batch ingest (N4)
 int lk_ingest_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,
                         const double *flux_err, int normalize, double *t_out, double *flux_out, double *flux_err_out,

@@ -296,6 +296,17 @@ int select_columns_launch(lk_handle *h, int B, const int64_t *n_off_host, const 
 // leaves (nullable: all), cdpp_out[B] on the device
 int cdpp_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *flat_flux, const uint8_t *outlier,
                 int transit_duration, double *cdpp_out, hipStream_t stream);
+// fillgaps.hip: LightCurve.fill_gaps for a ragged batch in two calls (the plan synchronises: new_off_host is valid on return) and
+// the segment gather of DeviceLightCurveBatch.stitch (include/lkhip.h)
+int fill_gaps_plan_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux,
+                          const int32_t *cadenceno, double *stats, int32_t *pos, int64_t *new_off_host, hipStream_t stream);
+int fill_gaps_launch(lk_handle *h, int B, const int64_t *n_off_host, const int64_t *new_off_host, const double *time,
+                     const double *flux, const double *flux_err, const int32_t *quality, const int32_t *cadenceno, const double *stats,
+                     const int32_t *pos, const double *noise_mean, const double *noise_std, uint64_t seed, int64_t first_target,
+                     int64_t stream_id, double *time_out, double *flux_out, double *flux_err_out, int32_t *quality_out,
+                     int32_t *cadenceno_out, uint8_t *inserted, hipStream_t stream);
+int gather_segments_launch(lk_handle *h, int S, const int64_t *src_start_host, const int64_t *dst_off_host, int64_t n_src, int ncols,
+                           const int *elem_bytes, const void *const *cols_in, void *const *cols_out, hipStream_t stream);
 int fits_unpack_launch(lk_handle *h, int B, const uint8_t *raw, const int64_t *raw_off_host, const int32_t *desc_host,
                        const int64_t *bitmask_host, double *t_out, double *f_out, double *e_out, int32_t *q_out,
                        int64_t *new_off_host, hipStream_t stream);

@@ -27,6 +27,7 @@ import weakref
 import numpy as np
 
 from . import _capi
+from . import fillgaps as _fg
 from . import foldbin as _fb
 from . import packed
 from . import periodogram as _pg
@@ -501,6 +502,115 @@ class DeviceLightCurveBatch(object):
         _capi._check(_capi._lib.lk_cdpp_batch_dev(h._h, B, _off_ptr(self.n_off), _vp(d_f.ptr), _vp(d_m.ptr), int(transit_duration),
                                                   _vp(d_c.ptr), st))
         return d_c.download(np.float64, B, stream=self.stream)
+
+    # ---------------------------------------------------------------- fill_gaps / stitch
+    def fill_gaps(self, method="gaussian_noise", by="auto", noise_std="auto", seed=0, first_target=0, stream_id=0, return_mask=False,
+                  noise_mean=None):
+        """``lc.fill_gaps(method="gaussian_noise")`` of lightkurve 2.x for every light curve, resident: the batch on an even grid,
+        missing cadences inserted with ``quality`` 65536, ``flux_err`` linear in time between the gap's two originals and flux
+        drawn from a normal distribution.  NaN-flux cadences are removed first, as the reference does; a light curve with fewer
+        than 2 cadences comes back unchanged.
+
+        ``by="time"``: the reference's loop over the sorted times, with m = median(diff(time)): a step of more than 1.2 m gets
+        prev + m, prev + m + m, ... (that chain of additions: the reference's bits); the result carries no cadence numbers.
+        ``by="cadenceno"``: every cadence number of [c_first, c_last], times interpolated on t - m c as the reference does
+        (the originals' times are recomputed, so they may move by an ulp); this is what makes a ragged batch uniform again
+        when all targets span the same cadence numbers.  ``"auto"``: by cadence number when the batch carries them.
+
+        The flux of inserted cadence j of light curve b is ``noise_mean + noise_std * g``, g = normal j of the Philox stream
+        (``seed``, target ``first_target + b``, ``stream_id``) that ``over_fitting_metric`` draws from — the reference draws
+        from numpy's global generator, so the match is in distribution.  ``noise_mean``: None = nanmean(flux), or one value per
+        light curve.  ``noise_std``: "std" = nanstd(flux); "cdpp" = ``estimate_cdpp() * 1e-6`` (NaN: nanstd), what the
+        reference takes for a dimensionless light curve; "auto" = "cdpp" when every ``meta["NORMALIZED"]`` is true, else
+        "std"; or one value per light curve.
+
+        ``lk_fill_gaps_plan_batch_dev`` (synchronises: the new offsets come back) and ``lk_fill_gaps_batch_dev``; 32 B of
+        statistics per target come to the host and 16 B go back.  ``return_mask``: also the ``DeviceBuffer`` of bytes over the
+        cadences of the RESULT, 1 = inserted: ``out.select(mask, invert=True)`` gives the originals back."""
+        by_cad, mode, std, mean = _fg.check_fill_gaps(method, by, self.d_cadenceno is not None, noise_std, noise_mean, self.meta)
+        src = self if self.nan_free else self.remove_nans()
+        if not by_cad and not src._sorted():
+            raise ValueError("fill_gaps needs the light curve sorted by time")
+        h, B, n, st = src.handle, len(src), src.n_cadences, _vp(src.stream or None)
+        d_cad = src.d_cadenceno if by_cad else None
+        d_stats, d_pos = DeviceBuffer(h, max(B, 1) * 32), DeviceBuffer(h, max(n, 1) * 4)
+        new_off = np.zeros(B + 1, dtype=np.int64)
+        _capi._check(_capi._lib.lk_fill_gaps_plan_batch_dev(h._h, B, _off_ptr(src.n_off), _vp(src.d_time.ptr), _vp(src.d_flux.ptr),
+                                                            _vp(d_cad.ptr if d_cad is not None else None), _vp(d_stats.ptr),
+                                                            _vp(d_pos.ptr), _off_ptr(new_off), st))       # (synchronises)
+        stats = d_stats.download(np.float64, 4 * B, stream=src.stream).reshape(B, 4)
+        nm, ns = _fg.noise_arrays(stats, mode, std, mean, src.estimate_cdpp)
+        d_nm, k1 = _upload(h, nm, src.stream)
+        d_ns, k2 = _upload(h, ns, src.stream)
+        nn = int(new_off[-1])
+        d_t, d_f, d_m = DeviceBuffer(h, max(nn, 1) * 8), DeviceBuffer(h, max(nn, 1) * 8), DeviceBuffer(h, max(nn, 1))
+        d_e = DeviceBuffer(h, max(nn, 1) * 8) if src.d_flux_err is not None else None
+        d_q = DeviceBuffer(h, max(nn, 1) * 4) if src.d_quality is not None else None
+        d_c = DeviceBuffer(h, max(nn, 1) * 4) if by_cad else None
+        opt = lambda buf: _vp(buf.ptr if buf is not None else None)     # noqa: E731
+        _capi._check(_capi._lib.lk_fill_gaps_batch_dev(
+            h._h, B, _off_ptr(src.n_off), _off_ptr(new_off), _vp(src.d_time.ptr), _vp(src.d_flux.ptr), opt(src.d_flux_err),
+            opt(src.d_quality), opt(d_cad), _vp(d_stats.ptr), _vp(d_pos.ptr), _vp(d_nm.ptr), _vp(d_ns.ptr), int(seed),
+            int(first_target), int(stream_id), _vp(d_t.ptr), _vp(d_f.ptr), opt(d_e), opt(d_q), opt(d_c), _vp(d_m.ptr), st))
+        finite = bool(np.all(np.isfinite(nm)) and np.all(np.isfinite(ns)))
+        out = src._new(d_t, d_f, d_e, new_off, nan_free=finite, is_sorted=None if by_cad else True)
+        out.d_quality, out.d_cadenceno = d_q, d_c
+        out._keep = [k1, k2]
+        out.fill_stats = stats          # m, mu, sd, n_inserted per light curve, as planned
+        return (out, d_m) if return_mask else out
+
+    def stitch(self, group=None, corrector="normalize", order="given"):
+        """``LightCurveCollection(segments).stitch()`` for the light curves of this batch, resident: the light curves that
+        share a value of ``group`` (int, one per light curve) become ONE target, targets numbered by first appearance;
+        ``group=None``: the whole batch is one target, as a collection is.  ``corrector="normalize"`` (the reference's default
+        ``corrector_func``) applies ``normalize()`` to every segment first, ``None`` leaves them as they are.  A target's
+        segments are concatenated in batch order (``order="given"``: the reference's vstack, no sort) or by the time of their
+        first cadence (``"start_time"``: B doubles come back through ``lk_gather_f64_dev``).  A column survives when the batch
+        has it (join_type="inner").  ONE launch of ``lk_gather_segments_batch_dev`` moves every column; when the segments of
+        every target already lie together in the wanted order nothing moves: the columns are shared and only the offsets
+        merge.  ``meta`` is the first segment's plus ``STITCHED_FROM`` (the indices of the target's segments, in order);
+        ``median_flux`` does not carry over."""
+        labels = _fg.check_stitch(group, len(self), corrector, order)
+        src = self.normalize() if corrector == "normalize" else self
+        h, B, n, st = src.handle, len(src), src.n_cadences, _vp(src.stream or None)
+        counts = np.diff(src.n_off)
+        start = None
+        if order == "start_time" and B:
+            start = np.zeros(B)
+            if n:
+                _capi._check(_capi._lib.lk_gather_f64_dev(h._h, B, _off_ptr(np.minimum(src.n_off[:-1], n - 1)), _vp(src.d_time.ptr),
+                                                          start.ctypes.data_as(_dp), st))
+        perm, seg_off, n_off = _fg.stitch_plan(labels, counts, start)
+        cols = [(src.d_time, 8), (src.d_flux, 8)]
+        for buf, eb in ((src.d_flux_err, 8), (src.d_quality, 4), (src.d_cadenceno, 4)):
+            if buf is not None:
+                cols.append((buf, eb))
+        if np.array_equal(perm, np.arange(B)):
+            outs = [c for c, _eb in cols]
+        else:
+            outs = [DeviceBuffer(h, max(n, 1) * eb) for _c, eb in cols]
+            src_start = np.ascontiguousarray(src.n_off[:-1][perm])
+            dst_off = np.zeros(B + 1, dtype=np.int64)
+            dst_off[1:] = np.cumsum(counts[perm])
+            cin = (_vp * len(cols))(*[c.ptr for c, _eb in cols])
+            cout = (_vp * len(cols))(*[c.ptr for c in outs])
+            elem = np.ascontiguousarray([eb for _c, eb in cols], dtype=np.int32)
+            _capi._check(_capi._lib.lk_gather_segments_batch_dev(h._h, B, _off_ptr(src_start), _off_ptr(dst_off), n, len(cols),
+                                                                 elem.ctypes.data_as(_i32p), cin, cout, st))
+        meta = []
+        for g in range(len(seg_off) - 1):
+            segs = [int(s) for s in perm[seg_off[g]:seg_off[g + 1]]]
+            m = dict(src.meta[segs[0]]) if segs else {}
+            m["STITCHED_FROM"] = segs
+            meta.append(m)
+        it = iter(outs[2:])
+        d_e = next(it) if src.d_flux_err is not None else None
+        out = DeviceLightCurveBatch(outs[0], outs[1], d_e, n_off, meta, src.device, src.stream, nan_free=src.nan_free)
+        out.d_quality = next(it) if src.d_quality is not None else None
+        out.d_cadenceno = next(it) if src.d_cadenceno is not None else None
+        out._keep = list(src._keep)
+        out._sorted()
+        return out
 
     # ---------------------------------------------------------------- cotrending on one shared design matrix
     def _uniform_n(self, rows, what):

@@ -126,6 +126,41 @@ class LightCurveBatch(object):
             out.cadenceno = np.ascontiguousarray(np.asarray(self.cadenceno)[keep])
         return (out, mask) if return_mask else out
 
+    def fill_gaps(self, method="gaussian_noise", by="auto", noise_std="auto", seed=0, first_target=0, stream_id=0, return_mask=False,
+                  noise_mean=None, device=0):
+        """``lc.fill_gaps(method="gaussian_noise")`` of lightkurve 2.x for every light curve (``DeviceLightCurveBatch.fill_gaps``
+        has the semantics and the arguments): NaN-flux cadences removed, then ``lk_fill_gaps_plan_batch`` and
+        ``lk_fill_gaps_batch`` on the host arrays; ``noise_std="cdpp"`` takes the CDPP from the resident ``estimate_cdpp``,
+        so both classes insert the same numbers.  ``return_mask``: also the bool mask over the cadences of the RESULT
+        (True = inserted)."""
+        from . import fillgaps as _fg, packed
+        by_cad, mode, std, mean = _fg.check_fill_gaps(method, by, self.cadenceno is not None, noise_std, noise_mean, self.meta)
+        src = self.remove_nans(device=device)
+        if not by_cad and not packed.check_sorted(src.time, src.n_off):
+            raise ValueError("fill_gaps needs the light curve sorted by time")
+        cad = src.cadenceno if by_cad else None
+        stats, pos, new_off = _capi.fill_gaps_plan_batch(src.time, src.flux, src.n_off, cadenceno=cad, device=device)
+
+        def cdpp():
+            from .device import DeviceLightCurveBatch
+            return DeviceLightCurveBatch.from_arrays(src.time, src.flux, None, src.n_off, device=device).estimate_cdpp()
+
+        nm, ns = _fg.noise_arrays(stats, mode, std, mean, cdpp)
+        r = _capi.fill_gaps_batch(src.time, src.flux, src.n_off, stats, pos, new_off, nm, ns, flux_err=src.flux_err,
+                                  quality=src.quality, cadenceno=cad, seed=seed, first_target=first_target, stream_id=stream_id,
+                                  device=device)
+        out = LightCurveBatch(r["time"], r["flux"], r["flux_err"], r["n_off"], [dict(m) for m in src.meta])
+        out.quality, out.cadenceno = r["quality"], r["cadenceno"]
+        return (out, r["inserted"]) if return_mask else out
+
+    def stitch(self, group=None, corrector="normalize", order="given", device=0):
+        """``LightCurveCollection(segments).stitch()``: the light curves that share a value of ``group`` become one target
+        (``DeviceLightCurveBatch.stitch`` has the semantics; this is that call on an uploaded copy, brought back)."""
+        from . import fillgaps as _fg
+        from .device import DeviceLightCurveBatch
+        _fg.check_stitch(group, len(self), corrector, order)
+        return DeviceLightCurveBatch.from_batch(self, device=device).stitch(group, corrector, order).to_host()
+
     def create_transit_mask(self, period, transit_time, duration, planet_off=None, device=0):
         """Boolean array over all cadences of the batch, True in transit (reference :2967-3037).  Scalars / 1-D arrays
         apply to every light curve; with ``planet_off`` each light curve gets its own planets."""

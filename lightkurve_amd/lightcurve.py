@@ -159,6 +159,17 @@ class LightCurve(object):
         return float(estimate_cdpp_batch([self], transit_duration=transit_duration, savgol_window=savgol_window,
                                          savgol_polyorder=savgol_polyorder, sigma=sigma, device=device)[0])
 
+    def fill_gaps(self, method="gaussian_noise", seed=0, device=0):
+        """The light curve on an even time grid (lightkurve 2.x ``LightCurve.fill_gaps``, its time path): NaN-flux cadences
+        removed, then wherever the time steps by more than 1.2 median steps cadences are inserted at prev + median step, with
+        flux_err linear in time and flux drawn from N(nanmean(flux), noise): the CDPP for a normalised light curve, else
+        nanstd(flux).  The draw is the library's Philox stream of ``seed`` (the reference draws from numpy's global
+        generator); ``lk_fill_gaps_plan_batch`` + ``lk_fill_gaps_batch`` on the GPU."""
+        from .ingest import LightCurveBatch
+        b = LightCurveBatch(self.time, self.flux, self.flux_err, [0, len(self)], [dict(self.meta)])
+        out = b.fill_gaps(method=method, by="time", seed=seed, device=device)
+        return LightCurve(time=out.time, flux=out.flux, flux_err=out.flux_err, meta=self.meta)
+
     def fold(self, period=None, epoch_time=None, epoch_phase=0, wrap_phase=None, normalize_phase=False, device=0):
         """Phase-fold (reference :1089-1214 over astropy TimeSeries.fold, timeseries/sampled.py:230-233):
         phase = ((t - epoch) + epoch_phase + (P - wrap)) % P - (P - wrap), then a stable sort by phase — both on

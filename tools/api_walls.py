@@ -92,7 +92,17 @@ ONE evaluation of its objective the way a ragged batch had it: the resident ragg
 period per target, `bins=LK_WALLS_BINS` (default 201), in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5) times
 after one warm-up.  F the fused `batch.fold_bin(period, bins=)`; S `batch.fold(period).bin(bins=)` (sort, gathers, bins); H the host
 route: `to_host()`, then numpy fold + bin per target on 16 threads.  Every timed region ends with the binned curves on the host.
-Written to profiles/foldbin_walls.txt."""
+Written to profiles/foldbin_walls.txt.
+
+`stitch`: `LK_WALLS_B` (default 1000) targets observed in `LK_WALLS_SEGMENTS` (default 4) sectors of `LK_WALLS_N` (default 5000)
+cadences each, TESS-like cadence numbers that continue across a one-day gap between sectors, 3 % of the cadences missing inside
+them, in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5) times after one warm-up.  R `from_arrays(cadenceno=)`
+-> `stitch(group)` -> `fill_gaps()` (the default noise: the resident CDPP of the stitched targets); R' the same with
+`fill_gaps(noise_std="std")`; G as R' on the segments in sector-major order (the gather route of `stitch`); H the host route: `to_host()` of the resident segments, numpy normalize + concatenate + fill_gaps
+by cadence number per target on 16 threads (noise of nanstd width from numpy's generator), then `from_arrays`.  Every timed
+region ends with a synchronise.  Written to profiles/stitch_walls.txt.  `stitch_trace`: resident calls only (four with
+`noise_std="std"`, then one with the CDPP), the run to put under `rocprofv3 --kernel-trace --stats`
+(`profiles/stitch_kernel_stats.txt`)."""
 import cProfile
 import io
 import os
@@ -982,6 +992,123 @@ def foldbin():
         "  S / F = %.2f; H / F = %.1f" % (med["S"] / med["F"], med["H"] / med["F"])])
 
 
+def stitch(which=("stitch",)):
+    from concurrent.futures import ThreadPoolExecutor
+    from lightkurve_amd import _capi
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    B, S, N = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_SEGMENTS", "4"), ("LK_WALLS_N", "5000")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "5"))
+    rng = np.random.default_rng(31)
+    step = 2.0 / 1440.0 * 10.0                       # a 20-minute-like cadence [d]; one day between sectors
+    day = int(round(1.0 / step))
+    keep = rng.random((B * S, N)) >= 0.03
+    keep[:, 0] = keep[:, -1] = True
+    c_seg = (np.arange(S)[:, None] * (N + day) + np.arange(N)[None, :]).astype(np.int64)          # (S, N): continuing numbers
+    cad = (100000 + np.tile(c_seg, (B, 1)))[keep].astype(np.int32)
+    time = 1325.0 + step * cad * (1.0 + 1e-6 * np.sin(cad / 900.0))
+    level = np.repeat(rng.uniform(800.0, 1200.0, B * S), keep.sum(axis=1))
+    flux = level * (1.0 + 1e-3 * rng.standard_normal(cad.size))
+    err = level * 1e-3
+    n_off = np.concatenate([[0], np.cumsum(keep.sum(axis=1))]).astype(np.int64)
+    group = np.repeat(np.arange(B), S)
+    sync = _capi.Handle.get(0).synchronize
+
+    def resident(noise_std="auto"):
+        out = DeviceLightCurveBatch.from_arrays(time, flux, err, n_off, cadenceno=cad).stitch(group).fill_gaps(noise_std=noise_std)
+        sync()
+        return out
+
+    # the same segments sector by sector (all targets' first sector, then their second, ...), as a survey delivers them: the groups
+    # interleave, so the gather kernel moves every column
+    order = np.arange(B * S).reshape(B, S).T.ravel()
+    counts = np.diff(n_off)
+    idx = np.concatenate([np.arange(n_off[s], n_off[s + 1]) for s in order])
+    time_s, flux_s, err_s, cad_s = time[idx], flux[idx], err[idx], cad[idx]
+    n_off_s = np.concatenate([[0], np.cumsum(counts[order])]).astype(np.int64)
+    group_s = group[order]
+
+    def resident_gather():
+        out = DeviceLightCurveBatch.from_arrays(time_s, flux_s, err_s, n_off_s, cadenceno=cad_s).stitch(group_s).fill_gaps(noise_std="std")
+        sync()
+        return out
+
+    def one(host, b, gen):
+        ts, fs, es, cs = [], [], [], []
+        for s in range(b * S, (b + 1) * S):                              # LightCurveCollection.stitch: normalize, then vstack
+            a, z = int(host.n_off[s]), int(host.n_off[s + 1])
+            f = host.flux[a:z]
+            ok = ~np.isnan(f)
+            med = np.median(f[ok])
+            ts.append(host.time[a:z][ok]), fs.append(f[ok] / med), es.append(host.flux_err[a:z][ok] / med), cs.append(host.cadenceno[a:z][ok])
+        t, f, e, c = (np.concatenate(x) for x in (ts, fs, es, cs))
+        m = np.median(np.diff(t))                                        # LightCurve.fill_gaps, the cadence path
+        cf = c.astype(np.float64)
+        nc = np.arange(c[0], c[-1] + 1)
+        ncf = nc.astype(np.float64)
+        nt = np.interp(ncf, cf, t - m * cf) + m * ncf
+        ins = np.ones(nc.size, dtype=bool)
+        ins[c - c[0]] = False
+        nf, ne = np.empty(nc.size), np.empty(nc.size)
+        nf[~ins], ne[~ins] = f, e
+        nf[ins] = gen.normal(np.nanmean(f), np.nanstd(f), int(ins.sum()))
+        ne[ins] = np.interp(nt[ins], t, e)
+        return nt, nf, ne, nc.astype(np.int32), ins
+
+    def through_host(src):
+        host = src.to_host()
+        gens = [np.random.default_rng(1000 + b) for b in range(B)]
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            parts = list(ex.map(lambda b: one(host, b, gens[b]), range(B)))
+        off = np.concatenate([[0], np.cumsum([p[0].size for p in parts])]).astype(np.int64)
+        out = DeviceLightCurveBatch.from_arrays(*(np.concatenate([p[k] for p in parts]) for k in range(3)), off,
+                                                cadenceno=np.concatenate([p[3] for p in parts]))
+        sync()
+        return out, np.concatenate([p[4] for p in parts])
+
+    if "stitch_trace" in which:
+        for _ in range(4):
+            resident("std")
+        resident_gather()
+        resident()
+        print("stitch_trace: 4 resident from_arrays -> stitch -> fill_gaps(noise_std='std') calls, one on sector-major segments (gather) and one "
+              "with the CDPP on %d x %d x %d"
+              % (B, S, N))
+        return
+    src = DeviceLightCurveBatch.from_arrays(time, flux, err, n_off, cadenceno=cad)     # the resident segments the host route starts from
+    src.synchronize()
+    r, r2, g = resident(), resident("std"), resident_gather()           # warm-up of every route
+    (h, h_ins) = through_host(src)
+    R, R2, G, H = [], [], [], []
+    for _ in range(reps):
+        R.append(timed(resident)[0])
+        R2.append(timed(lambda: resident("std"))[0])
+        G.append(timed(resident_gather)[0])
+        H.append(timed(lambda: through_host(src))[0])
+    gather_same = all(np.array_equal(a, b) for a, b in ((g.n_off, r2.n_off), (g.time_host(), r2.time_host()),
+                                                       (g.flux_host(), r2.flux_host()), (g.flux_err_host(), r2.flux_err_host()),
+                                                       (g.cadenceno_host(), r2.cadenceno_host())))
+    same_layout = np.array_equal(r.n_off, h.n_off) and np.array_equal(r.cadenceno_host(), h.cadenceno_host())
+    rt, ht, re_, he, rf, hf = r.time_host(), h.time_host(), r.flux_err_host(), h.flux_err_host(), r2.flux_host(), h.flux_host()
+    dt = float(np.max(np.abs(rt - ht) / np.spacing(np.abs(ht)))) if same_layout else np.nan
+    de = float(np.nanmax(np.abs(re_ - he) / np.abs(he))) if same_layout else np.nan
+    df = float(np.max(np.abs(rf[~h_ins] - hf[~h_ins]) / np.abs(hf[~h_ins]))) if same_layout else np.nan
+    med = {k: float(np.median(v)) for k, v in (("R", R), ("R2", R2), ("H", H))}
+    n_in, n_out = int(n_off[-1]), int(r.n_off[-1])
+    write_walls("stitch_walls.txt", [
+        "stitch + fill_gaps: %d targets x %d sectors x %d cadences, one day (%d cadences) between sectors, 3 %% missing inside: %d "
+        "cadences in (%.0f MB of columns), %d out, %d inserted" % (B, S, N, day, n_in, n_in * 28 / 1e6, n_out, n_out - n_in),
+        "  R   from_arrays(cadenceno=) -> stitch(group) -> fill_gaps() + synchronise (noise: resident CDPP)        %s" % spread(R),
+        "  R'  the same with fill_gaps(noise_std='std')                                                            %s" % spread(R2),
+        "  G   R' on the segments in sector-major order: the groups interleave, the gather kernel moves 5 columns   %s" % spread(G),
+        "  H   to_host(), numpy normalize + concatenate + fill_gaps per target on 16 threads, from_arrays          %s" % spread(H),
+        "  G and R': every column and offset bitwise equal: %s" % gather_same,
+        "  R and H: same offsets and cadence numbers: %s; largest difference of the times %.2f ulp, of flux_err %.2e relative, of "
+        "the originals' flux %.2e relative (R'); inserted flux: different generators, equal in distribution (std of the inserted "
+        "flux R' %.3e, H %.3e)" % (same_layout, dt, de, df, float(np.std(rf[h_ins])) if same_layout else np.nan, float(np.std(hf[h_ins]))),
+        "  H / R = %.2f; H / R' = %.2f; R / R' = %.2f (the CDPP: flatten + clip of every stitched target); kernels alone not measured"
+        % (med["H"] / med["R"], med["H"] / med["R2"], med["R"] / med["R2"])])
+
+
 def main():
     import torch  # noqa: F401  (before liblkhip.so)
     from lightkurve_amd import batch, synth
@@ -1017,6 +1144,8 @@ def main():
         cbvopt_ragged()
     if "foldbin" in which:
         foldbin()
+    if {"stitch", "stitch_trace"} & set(which):
+        stitch(which)
     if "flatten" in which:
         lcs = []
         for i in range(1000):
