@@ -741,6 +741,24 @@ int lk_ridge_prior_rows_alphas_batch(lk_handle *h, int B, const int64_t *n_off, 
                                      double *prior_mu, double *prior_sigma);
 int lk_ridge_prior_rows_alphas_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, int K, const double *flux_err,
                                          const double *alpha, double *prior_mu, double *prior_sigma, void *stream);
+/* ---- CotrendingBasisVectors.interpolate for a ragged batch: K columns Y (Nx x K row-major) given at the knot times knot_time
+ * (Nx) are interpolated to the times t ((sum n), packed by n_off; a target may have no cadence) with
+ * scipy.interpolate.PchipInterpolator's piecewise cubic, and written as the targets' design matrices X_out, (sum n) x Kout
+ * row-major, Kout = K + (append_constant != 0): the layout lk_regress_batch takes; the optional last column is all ones.
+ * knot_keep (Nx bytes, nullable = all): the reference's ~gap_indicators, knots with 0 are left out (compacted on the device).
+ * The LK_EINVAL cases: kept knot times not finite or not strictly increasing, fewer than 2 kept knots, a kept Y that is not
+ * finite, K < 1.  A time outside [first kept knot, last kept knot], or not finite, gives NaN in the K columns when
+ * extrapolate == 0, and the first / last cubic continued, as scipy does, otherwise (NaN for a NaN time).  A time bit-equal
+ * to a kept knot gives that knot's values bit for bit.  inside ((sum n) bytes, nullable): 1 = the time lies in the kept knots'
+ * span.  X_out may be NULL when inside is not: only the bytes are written.  Every element depends on its own time alone: a
+ * target's rows have the same bits whatever else is in the batch.  The call waits once, for the check of the knots, before
+ * it queues the interpolation; the _dev form returns without further synchronisation.  Nx K < 2^31, B <= 65535. */
+int lk_pchip_interp_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, int Nx, int K, const double *knot_time,
+                          const double *Y, const uint8_t *knot_keep, int extrapolate, int append_constant, double *X_out,
+                          uint8_t *inside);
+int lk_pchip_interp_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, int Nx, int K,
+                              const double *knot_time, const double *Y, const uint8_t *knot_keep, int extrapolate,
+                              int append_constant, double *X_out, uint8_t *inside, void *stream);
 /* out[i] = a[i] - b[i] for n doubles on the device (flux - model: the corrected flux of RegressionCorrector.correct). */
 int lk_subtract_f64_dev(lk_handle *h, int64_t n, const double *a, const double *b, double *out, void *stream);
 

@@ -235,6 +235,10 @@ SIGNATURES = [
     ("lk_fits_cadenceno_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_u8p, _c_ip, _c_i32p, _c_i32p, _c_ip, _c_ip, _c_i32p]),
     ("lk_fits_cadenceno_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _vp, _c_ip, _c_i32p, _c_i32p, _c_ip, _c_ip, _vp, _vp]),
     ("lk_subtract_f64_dev", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    ("lk_pchip_interp_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_dp, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_u8p, ctypes.c_int, ctypes.c_int, _c_dp, _c_u8p]),
+    ("lk_pchip_interp_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
     ("lk_underfit_neighbors_batch", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, _c_i32p, ctypes.c_int, _c_i32p, _c_dp, _c_dp]),
     ("lk_underfit_neighbors_batch_dev", ctypes.c_int,
@@ -1113,6 +1117,31 @@ def ridge_prior_rows_batch(flux_err, n_off, K, alpha, device=0):
             raise ValueError("alpha must be a scalar or B finite, non-zero penalties")
         _check(_lib.lk_ridge_prior_rows_alphas_batch(h._h, B, _ptr(n_off, _c_ip), int(K), _ptr(e), _ptr(a), _ptr(mu), _ptr(sg)))
     return mu, sg
+
+
+def pchip_interp_batch(time, n_off, knot_time, Y, knot_keep=None, extrapolate=False, append_constant=False, device=0):
+    """``CotrendingBasisVectors.interpolate`` for a ragged batch: the K columns ``Y`` (Nx, K) at ``knot_time`` (Nx,) ->
+    (X (sum n, K + append_constant), inside bool (sum n,)) at the packed ``time``; ``knot_keep`` (bool (Nx,), None = all):
+    the reference's ``~gap_indicators``.  Outside the kept knots' span: NaN, or scipy's extrapolation with ``extrapolate``.
+    The device form of ``correctors.cbvcorrector.interpolate_cbvs``."""
+    h = Handle.get(device)
+    t = _f64(time)
+    if t.ndim != 1:
+        raise ValueError("time must be packed 1-D (sum n,) (got shape %s)" % (t.shape,))
+    n_off = _offsets(n_off, t.size)
+    x = _f64(knot_time)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    if x.ndim != 1 or Y.ndim != 2 or Y.shape[0] != x.size:
+        raise ValueError("knot_time must be 1-D and Y 2-D with one row per knot (got %s and %s)" % (x.shape, Y.shape))
+    keep = None if knot_keep is None else np.ascontiguousarray(knot_keep, dtype=np.uint8)
+    if keep is not None and keep.shape != x.shape:
+        raise ValueError("knot_keep must have one entry per knot (got shape %s, need %s)" % (keep.shape, x.shape))
+    Nx, K = Y.shape
+    X = np.empty((t.size, K + int(bool(append_constant))), dtype=np.float64)
+    inside = np.empty(t.size, dtype=np.uint8)
+    _check(_lib.lk_pchip_interp_batch(h._h, n_off.size - 1, _ptr(n_off, _c_ip), _ptr(t), Nx, K, _ptr(x), _ptr(Y), _ptr(keep, _c_u8p),
+                                      int(bool(extrapolate)), int(bool(append_constant)), _ptr(X), _ptr(inside, _c_u8p)))
+    return X, inside.astype(bool)
 
 
 # --------------------------------------------------------------------------------------------- under-fitting metric

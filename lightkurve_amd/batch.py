@@ -432,8 +432,8 @@ def regression_correct_batch(lcs, design_matrices, cadence_masks=None, sigma=5, 
     return flux, coef, outl
 
 
-def cbv_correct_batch(lcs, cbvs, cadenceno, cbv_indices=np.arange(1, 9), alpha=1e-20, ext_dm=None, cadence_masks=None, sigma=5,
-                      niters=5, device=0):
+def cbv_correct_batch(lcs, cbvs, cadenceno=None, cbv_indices=np.arange(1, 9), alpha=1e-20, ext_dm=None, cadence_masks=None, sigma=5,
+                      niters=5, device=0, cbv_time=None, gap_indicators=None, extrapolate=False):
     """``CBVCorrector(lc, cbvs.align(lc)).correct_gaussian_prior(cbv_indices, alpha, ext_dm, cadence_mask)`` for many host
     light curves that share the basis vectors of one channel but keep different cadences: ``cbvs`` (Nx, n_vectors) lives on
     the cadence grid ``cadenceno`` (Nx, strictly increasing) and every light curve carries its own ``cadenceno`` column.
@@ -441,10 +441,35 @@ def cbv_correct_batch(lcs, cbvs, cadenceno, cbv_indices=np.arange(1, 9), alpha=1
     (``lk_regress_shared_rows_batch``), no stacked copy per target exists.  ``alpha``: scalar (0: no prior) or one
     penalty per target.  Returns (corrected_flux list, coefficients[B, K], outlier_mask list, kept list): ``kept[b]`` is the
     bool mask over light curve b's cadences of those that are on the grid (the others have no corrected flux).  One
-    process, one device: a resident ``DeviceLightCurveBatch.cbv_correct(cadenceno=)`` is the route that scales."""
-    from .device import _alpha_per_target, _cbv_columns
+    process, one device: a resident ``DeviceLightCurveBatch.cbv_correct(cadenceno=)`` is the route that scales.
+
+    ``cbv_time`` (Nx,) instead of ``cadenceno``: ``CBVCorrector(lc, interpolate_cbvs=True, extrapolate_cbvs=extrapolate)`` —
+    the light curves need no cadence numbers, the basis vectors are interpolated to each one's times on the device
+    (``DeviceLightCurveBatch.cbv_correct(cbv_time=, gap_indicators=, extrapolate=)``, which this call goes through);
+    ``kept[b]`` marks the cadences inside the CBVs' span (all of them with ``extrapolate``)."""
+    from .device import DeviceLightCurveBatch, _alpha_per_target, _cbv_columns
     lcs = list(lcs)
     B = len(lcs)
+    if (cadenceno is None) == (cbv_time is None):
+        raise ValueError("cbv_correct_batch: pass `cadenceno` (the cadence numbers of the rows of cbvs) or `cbv_time` (their times)")
+    if cbv_time is not None:
+        if B == 0:
+            return [], np.zeros((0, _cbv_columns(cbvs, cbv_indices, None).shape[1])), [], []
+        col = lambda lc, name: np.asarray(getattr(getattr(lc, name), "value", getattr(lc, name)), dtype=np.float64)
+        ts, ys, es = ([col(lc, name) for lc in lcs] for name in ("time", "flux", "flux_err"))
+        off = np.concatenate([[0], np.cumsum([len(t) for t in ts])]).astype(np.int64)
+        cms = None
+        if cadence_masks is not None:
+            cms = np.concatenate([np.ones(len(t), bool) if c is None else np.asarray(c, dtype=bool)
+                                  for c, t in zip(cadence_masks, ts)])
+        dev = DeviceLightCurveBatch.from_arrays(np.concatenate(ts), np.concatenate(ys), np.concatenate(es), off, device=device)
+        flux, outl, coef = dev.cbv_correct(cbvs, cbv_indices=cbv_indices, alpha=alpha, ext_dm=ext_dm, cadence_mask=cms, sigma=sigma,
+                                           niters=niters, to_host=True, cbv_time=cbv_time, gap_indicators=gap_indicators,
+                                           extrapolate=extrapolate)
+        x = np.asarray(cbv_time, dtype=np.float64)
+        knots = x if gap_indicators is None else x[np.asarray(gap_indicators) == 0]
+        kept = [np.ones(len(t), bool) if extrapolate else (t >= knots[0]) & (t <= knots[-1]) for t in ts]
+        return flux, coef, outl, kept
     X = _cbv_columns(cbvs, cbv_indices, ext_dm)
     grid = np.asarray(cadenceno)
     if grid.shape != (X.shape[0],) or not np.issubdtype(grid.dtype, np.integer) or np.any(np.diff(grid) <= 0):

@@ -23,7 +23,7 @@ from .designmatrix import DesignMatrix, DesignMatrixCollection
 from .metrics import overfit_metric_lombscargle, overfit_metric_lombscargle_batch, underfit_metric_neighbors
 from .regressioncorrector import RegressionCorrector
 
-__all__ = ["CBVCorrector", "minimize_scalar_bounded", "BoundedBrentBatch"]
+__all__ = ["CBVCorrector", "minimize_scalar_bounded", "BoundedBrentBatch", "interpolate_cbvs", "pchip_slopes"]
 
 
 def minimize_scalar_bounded(func, bounds, xatol=1e-5, maxiter=500):
@@ -182,6 +182,81 @@ def _bounded_brent_steps(x1, x2, xatol, maxiter):
     if np.isnan(xf) or np.isnan(fx) or np.isnan(fu):
         flag = 2
     return dict(x=float(xf), fun=float(fx), nfev=num, status=flag)
+
+
+def _kept_knots(cbv_time, cbvs, gap_indicators):
+    """The checks of ``interpolate_cbvs`` -> (knot times, knot values (Nk, K)) without the gap-flagged cadences."""
+    x = np.asarray(cbv_time, dtype=np.float64)
+    y = np.asarray(cbvs, dtype=np.float64)
+    if x.ndim != 1 or y.ndim != 2 or y.shape[0] != x.size:
+        raise ValueError("cbv_time must be 1-D and cbvs 2-D with one row per CBV cadence (got %s and %s)" % (x.shape, y.shape))
+    if y.shape[1] < 1:
+        raise ValueError("cbvs needs at least one column")
+    if gap_indicators is not None:
+        gap = np.asarray(gap_indicators)
+        if gap.shape != x.shape or (gap.dtype != np.bool_ and gap.dtype != np.uint8):
+            raise ValueError("gap_indicators must be a bool array with one entry per CBV cadence")
+        x, y = x[gap == 0], y[gap == 0]
+    if x.size < 2:
+        raise ValueError("interpolation needs at least 2 CBV cadences that are not gap-flagged (got %d)" % x.size)
+    if not np.all(np.isfinite(x)) or np.any(np.diff(x) <= 0):
+        raise ValueError("the times of the CBV cadences that are not gap-flagged must be finite and strictly increasing")
+    if not np.all(np.isfinite(y)):
+        raise ValueError("the basis vectors must be finite at every cadence that is not gap-flagged")
+    return x, y
+
+
+def pchip_slopes(x, y):
+    """The derivatives ``scipy.interpolate.PchipInterpolator(x, y, axis=0)`` uses at its knots (scipy
+    interpolate/_cubic.py ``_find_derivatives`` / ``_edge_case``): x (Nx,) strictly increasing, y (Nx, K) -> (Nx, K)."""
+    h = np.diff(x)[:, None]
+    m = np.diff(y, axis=0) / h
+    d = np.zeros_like(y)
+    if x.size == 2:
+        d[0] = d[1] = m[0]
+        return d
+    flat = (np.sign(m[1:]) != np.sign(m[:-1])) | (m[1:] == 0) | (m[:-1] == 0)
+    w1, w2 = 2 * h[1:] + h[:-1], h[1:] + 2 * h[:-1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        whmean = (w1 / m[:-1] + w2 / m[1:]) / (w1 + w2)
+        d[1:-1] = np.where(flat, 0.0, 1.0 / whmean)
+
+    def edge(h0, h1, m0, m1):
+        e = ((2 * h0 + h1) * m0 - h0 * m1) / (h0 + h1)
+        steep = (np.sign(m0) != np.sign(m1)) & (np.abs(e) > 3.0 * np.abs(m0))
+        return np.where(np.sign(e) != np.sign(m0), 0.0, np.where(steep, 3.0 * m0, e))
+
+    d[0] = edge(h[0], h[1], m[0], m[1])
+    d[-1] = edge(h[-1], h[-2], m[-1], m[-2])
+    return d
+
+
+def interpolate_cbvs(cbv_time, cbvs, time, gap_indicators=None, extrapolate=False):
+    """``CotrendingBasisVectors.interpolate(lc, extrapolate)`` on arrays (reference cbvcorrector.py: every basis vector
+    through ``scipy.interpolate.PchipInterpolator`` with the cadences that are not gap-flagged as knots, evaluated at the
+    light curve's times), restated in numpy so the product interpreter needs no scipy: ``cbvs`` (Nx, K) at ``cbv_time``
+    (Nx,) -> (len(time), K).  A time outside the knots' span (or not finite) gives NaN unless ``extrapolate``, which
+    continues the first / last cubic as scipy does.  A time bit-equal to a knot returns that knot's values bit for bit.
+    This is the host mirror of ``lk_pchip_interp_batch`` (csrc/interp.hip): same interval, same coefficients, same Horner
+    form."""
+    x, y = _kept_knots(cbv_time, cbvs, gap_indicators)
+    t = np.asarray(time, dtype=np.float64)
+    if t.ndim != 1:
+        raise ValueError("time must be 1-D")
+    d = pchip_slopes(x, y)
+    i = np.clip(np.searchsorted(x, t, side="right") - 1, 0, x.size - 2)
+    dx = (x[i + 1] - x[i])[:, None]
+    s = (t - x[i])[:, None]
+    sl = (y[i + 1] - y[i]) / dx
+    tt = (d[i] + d[i + 1] - 2 * sl) / dx
+    c0, c1 = tt / dx, (sl - d[i]) / dx - tt
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = y[i] + s * (d[i] + s * (c1 + s * c0))
+    last = t == x[-1]
+    out[last] = y[-1]
+    if not extrapolate:
+        out[~((t >= x[0]) & (t <= x[-1]))] = np.nan
+    return out
 
 
 class BoundedBrentBatch(object):

@@ -791,6 +791,37 @@ int lk_ridge_prior_rows_alphas_batch(lk_handle *h, int B, const int64_t *n_off, 
     return ridge_prior_rows_host(h, B, n_off, K, flux_err, 0.0, alpha, prior_mu, prior_sigma);
 }
 
+// shared columns on knots -> per-target design matrices by PCHIP (interp.hip)
+int lk_pchip_interp_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, int Nx, int K,
+                              const double *knot_time, const double *Y, const uint8_t *knot_keep, int extrapolate,
+                              int append_constant, double *X_out, uint8_t *inside, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::pchip_interp_launch(h, B, n_off_host, t, Nx, K, knot_time, Y, knot_keep, extrapolate, append_constant, X_out, inside,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int lk_pchip_interp_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, int Nx, int K, const double *knot_time,
+                          const double *Y, const uint8_t *knot_keep, int extrapolate, int append_constant, double *X_out,
+                          uint8_t *inside) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr && n_off[B] >= 0, "bad batch description");
+    LK_REQUIRE(K >= 1 && Nx >= 2, "K must be >= 1 and Nx >= 2");
+    LK_REQUIRE(knot_time && Y && (n_off[B] == 0 || (t && (X_out || inside))), "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B], kout = (size_t)K + (append_constant ? 1 : 0);
+    const double *dt, *dx, *dY;
+    const uint8_t *dkeep;
+    double *dX;
+    uint8_t *din;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).in(dx, knot_time, (size_t)Nx).in(dY, Y, (size_t)Nx * K).in(dkeep, knot_keep, (size_t)Nx)
+                 .out(dX, X_out, ntot * kout).out(din, inside, ntot).stage();
+    if (rc) return rc;
+    rc = lk::pchip_interp_launch(h, B, n_off, dt, Nx, K, dx, dY, dkeep, extrapolate, append_constant, dX, din, nullptr);
+    return rc ? rc : io.finish();
+}
+
 int lk_subtract_f64_dev(lk_handle *h, int64_t n, const double *a, const double *b, double *out, void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));

@@ -196,6 +196,11 @@ int regress_shared_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, c
 int ridge_prior_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, int K, const double *err, double alpha,
                             const double *alphas, double *prior_mu, double *prior_sigma, hipStream_t stream);
 int subtract_launch(lk_handle *h, int64_t n, const double *a, const double *b, double *out, hipStream_t stream);
+// interp.hip: K shared columns on Nx knots -> every target's own design matrix by PCHIP (include/lkhip.h); synchronises once, for
+// the check of the knots.  X_out nullable: the inside bytes alone
+int pchip_interp_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, int Nx, int K, const double *knot_time,
+                        const double *Y, const uint8_t *knot_keep, int extrapolate, int append_constant, double *X_out,
+                        uint8_t *inside, hipStream_t stream);
 int underfit_neighbors_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
                               const int32_t *neighbors, double *corr, double *metric, hipStream_t stream);
 int underfit_rows_bytes(int Bn, int n, int64_t *bytes);

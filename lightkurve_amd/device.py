@@ -632,7 +632,7 @@ class DeviceLightCurveBatch(object):
         return N
 
     def regression_correct(self, X, prior_mu=None, prior_sigma=None, cadence_mask=None, sigma=5, niters=5, to_host=False, rows=None,
-                           cadenceno=None):
+                           cadenceno=None, knot_time=None, extrapolate=False, knot_keep=None, design_slab_mb=4096):
         """``RegressionCorrector(lc).correct(X, cadence_mask, sigma, niters)`` (reference regressioncorrector.py:191-279,
         ``propagate_errors=False``) for every target of the batch on ONE shared design matrix: ``X`` is a host array (N, K),
         K <= 64, or a ``DesignMatrix`` / ``DesignMatrixCollection`` (its own priors go to every target unless ``prior_mu`` /
@@ -650,8 +650,36 @@ class DeviceLightCurveBatch(object):
         int (sum n,), per target strictly increasing indices into the rows of ``X``.  Per target the numerics are
         ``RegressionCorrector.correct`` on ``X[rows_b]``.  ``cadence_mask`` is then ragged: bool (sum n,) over the cadences of
         this batch, or a ``DeviceBuffer`` of that many bytes.  The result is the same triple on the batch's own offsets
-        (outlier bytes (sum n,)); ``to_host=True`` -> (list of corrected[n_b], list of outlier[n_b] bool, coefficients[B, K])."""
+        (outlier bytes (sum n,)); ``to_host=True`` -> (list of corrected[n_b], list of outlier[n_b] bool, coefficients[B, K]).
+
+        The third route, for light curves whose cadences are NOT rows of ``X`` (another cadence length, binned light curves,
+        times that differ by seconds, no cadence numbers): ``knot_time`` = the times of the Nx rows of ``X``, float (Nx,),
+        strictly increasing where ``knot_keep`` (bool (Nx,), None = everywhere; the reference's ``~gap_indicators``) is
+        true.  Every column of ``X`` is then interpolated to each target's own times as ``CotrendingBasisVectors.interpolate``
+        does (``scipy.interpolate.PchipInterpolator`` on the kept rows; ``lk_pchip_interp_batch_dev``) and every target is
+        fitted on its own interpolated matrix (``lk_regress_batch_dev``; any K that call takes).  Not to be combined with
+        ``rows`` / ``cadenceno``.  ``extrapolate=False``: a cadence outside the kept knots' span (or with a time that is not
+        finite) is dropped before the fit, exactly as an off-grid cadence is, and counted in
+        ``meta[b]["CADENCES_OUTSIDE_CBVS"]`` of the result; a target left with no cadence is a ``ValueError`` naming it.
+        ``extrapolate=True``: nothing is dropped, the first / last cubic is continued as scipy does.  ``cadence_mask`` and
+        the results are ragged as above.  The interpolated matrices are 8 K (sum n) bytes: whole targets are fitted in
+        groups whose matrices stay under ``design_slab_mb`` MiB (a target's result does not depend on the grouping, bit
+        for bit)."""
         Xa, mu, sg = _design_arrays(X, prior_mu, prior_sigma)
+        if knot_time is not None:
+            if rows is not None or cadenceno is not None:
+                raise ValueError("regression_correct: `knot_time` interpolates X to the targets' own times; it cannot be combined "
+                                 "with `rows` / `cadenceno`")
+            src, d_cm, keep, knots = self._interp_front(Xa, knot_time, knot_keep, extrapolate, cadence_mask, "regression_correct")
+            B, K = len(src), Xa.shape[1]
+            d_mu = d_sg = None
+            if mu is not None:
+                d_mu, k1 = _upload(src.handle, np.broadcast_to(mu, (B, K)), src.stream)
+                d_sg, k2 = _upload(src.handle, np.broadcast_to(sg, (B, K)), src.stream)
+                keep += [k1, k2]
+            return src._regress_interp(knots, False, extrapolate, d_mu, d_sg, d_cm, sigma, niters, to_host, keep, design_slab_mb)
+        if knot_keep is not None or extrapolate:
+            raise ValueError("regression_correct: `knot_keep` / `extrapolate` belong to the interpolated route: pass `knot_time`")
         if rows is not None or cadenceno is not None:
             src, d_rows, d_cm, keep = self._aligned(Xa.shape[0], rows, cadenceno, cadence_mask, "regression_correct")
             B, K = len(src), Xa.shape[1]
@@ -738,6 +766,119 @@ class DeviceLightCurveBatch(object):
             keep.append(k)
         return src, d_rows, d_cm, keep
 
+    def _interp_front(self, Ya, knot_time, knot_keep, extrapolate, cadence_mask, what):
+        """The interpolated route's front end -> (batch to fit, d_cm, keep, (d_x, d_Y, d_keep, Nx, K)).  Every check that
+        needs no device comes first.  Without ``extrapolate`` the inside bytes come from ``lk_pchip_interp_batch_dev`` (which
+        also checks the knots) and the batch (and ``cadence_mask``) is ``select``-ed down to the cadences inside the span."""
+        n, B = self.n_cadences, len(self)
+        x = np.asarray(knot_time)
+        if x.ndim != 1 or x.shape[0] != Ya.shape[0] or not (np.issubdtype(x.dtype, np.floating) or np.issubdtype(x.dtype, np.integer)):
+            raise ValueError("%s: the knot times must be a real array of shape (%d,), one per row of the matrix (got %s of shape %s)"
+                             % (what, Ya.shape[0], x.dtype, x.shape))
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        kk = None
+        if knot_keep is not None:
+            kk = np.asarray(knot_keep)
+            if kk.shape != x.shape or (kk.dtype != np.bool_ and kk.dtype != np.uint8):
+                raise ValueError("%s: the knot mask must be a bool array of shape (%d,) (got %s of shape %s)"
+                                 % (what, x.size, kk.dtype, kk.shape))
+            kk = np.ascontiguousarray(kk != 0, dtype=np.uint8)
+        if int(x.size if kk is None else kk.sum()) < 2:
+            raise ValueError("%s: interpolation needs at least 2 knots that are kept" % what)
+        if B == 0 or n == 0:
+            raise ValueError("%s needs at least one light curve with cadences" % what)
+        cm = None
+        if cadence_mask is not None and not isinstance(cadence_mask, DeviceBuffer):
+            cm = np.ascontiguousarray(cadence_mask, dtype=np.uint8)
+            if cm.shape != (n,):
+                raise ValueError("%s: on the interpolated route cadence_mask is ragged, one entry per cadence of the batch: "
+                                 "shape (%d,) (got %s)" % (what, n, cm.shape))
+        elif cadence_mask is not None and cadence_mask.nbytes != n:
+            raise ValueError("%s: cadence_mask holds %d bytes, the batch has %d cadences" % (what, cadence_mask.nbytes, n))
+        h, st, keep = self.handle, _vp(self.stream or None), []
+        d_x, k1 = _upload(h, x, self.stream)
+        d_Y, k2 = _upload(h, Ya, self.stream)
+        keep += [k1, k2]
+        d_keep = None
+        if kk is not None:
+            d_keep, k3 = _upload(h, kk, self.stream, np.uint8)
+            keep.append(k3)
+        knots = (d_x, d_Y, d_keep, Ya.shape[0], Ya.shape[1])
+        src, dropped = self, np.zeros(B, dtype=np.int64)
+        if not extrapolate:
+            d_in = DeviceBuffer(h, n)
+            _capi._check(_capi._lib.lk_pchip_interp_batch_dev(h._h, B, _off_ptr(self.n_off), _vp(self.d_time.ptr), Ya.shape[0],
+                                                              Ya.shape[1], _vp(d_x.ptr), _vp(d_Y.ptr),
+                                                              _vp(d_keep.ptr if d_keep is not None else None), 0, 0, None,
+                                                              _vp(d_in.ptr), st))
+            outside = d_in.download(np.uint8, n, stream=self.stream) == 0
+            if outside.any():
+                dropped = np.diff(np.concatenate([[0], np.cumsum(outside, dtype=np.int64)])[self.n_off])
+                empty = np.flatnonzero(dropped == np.diff(self.n_off))
+                if empty.size:
+                    raise ValueError("%s: target %d has no cadence inside the span of the knots (extrapolate=True keeps them)"
+                                     % (what, int(empty[0])))
+                src = self.select(d_in)
+                if cm is not None:
+                    cm = np.ascontiguousarray(cm[~outside])
+                elif cadence_mask is not None:
+                    cm = np.ascontiguousarray(cadence_mask.download(np.uint8, n, stream=self.stream)[~outside])
+                    cadence_mask = None
+        if np.any(np.diff(src.n_off) == 0):
+            raise ValueError("%s: target %d has no cadence" % (what, int(np.flatnonzero(np.diff(src.n_off) == 0)[0])))
+        if src is self:
+            src = self._carry(self._new(self.d_time, self.d_flux, self.d_flux_err, self.n_off, nan_free=self.nan_free,
+                                        is_sorted=self.is_sorted))
+        for m, c in zip(src.meta, dropped):
+            m["CADENCES_OUTSIDE_CBVS"] = int(c)
+        d_cm = cadence_mask if isinstance(cadence_mask, DeviceBuffer) else None
+        if cm is not None:
+            d_cm, k = _upload(h, cm, self.stream, np.uint8)
+            keep.append(k)
+        return src, d_cm, keep, knots
+
+    def _regress_interp(self, knots, append_constant, extrapolate, d_mu, d_sg, d_cm, sigma, niters, to_host, keep, design_slab_mb):
+        """Interpolate and fit, whole targets in groups whose design matrices fit ``design_slab_mb``; one slab, reused."""
+        d_x, d_Y, d_keep, Nx, K = knots
+        h, B, n, st = self.handle, len(self), self.n_cadences, _vp(self.stream or None)
+        Kout = K + int(bool(append_constant))
+        budget = int(float(design_slab_mb) * (1 << 20)) // (8 * Kout)        # cadences per group
+        if budget < 1:
+            raise ValueError("design_slab_mb=%r holds not one row of the design matrix" % (design_slab_mb,))
+        groups, b0 = [], 0
+        while b0 < B:
+            b1 = b0 + 1
+            while b1 < B and self.n_off[b1 + 1] - self.n_off[b0] <= budget and b1 - b0 < 65535:
+                b1 += 1
+            groups.append((b0, b1))
+            b0 = b1
+        d_slab = DeviceBuffer(h, 8 * Kout * int(max(self.n_off[b1] - self.n_off[b0] for b0, b1 in groups)))
+        d_w, d_model, d_corr, d_outl = DeviceBuffer(h, B * Kout * 8), DeviceBuffer(h, n * 8), DeviceBuffer(h, n * 8), DeviceBuffer(h, n)
+        lib = _capi._lib
+
+        def at(buf, nbytes):
+            return _vp(buf.ptr + int(nbytes)) if buf is not None else _vp(None)
+
+        for b0, b1 in groups:
+            o = int(self.n_off[b0])
+            off = np.ascontiguousarray(self.n_off[b0:b1 + 1] - o)
+            _capi._check(lib.lk_pchip_interp_batch_dev(h._h, b1 - b0, _off_ptr(off), at(self.d_time, 8 * o), Nx, K, _vp(d_x.ptr),
+                                                       _vp(d_Y.ptr), at(d_keep, 0), int(bool(extrapolate)), int(bool(append_constant)),
+                                                       _vp(d_slab.ptr), None, st))
+            _capi._check(lib.lk_regress_batch_dev(h._h, b1 - b0, _off_ptr(off), Kout, _vp(d_slab.ptr), at(self.d_flux, 8 * o),
+                                                  at(self.d_flux_err, 8 * o), at(d_cm, o), at(d_mu, 8 * Kout * b0),
+                                                  at(d_sg, 8 * Kout * b0), float(sigma), int(niters), at(d_w, 8 * Kout * b0),
+                                                  at(d_model, 8 * o), at(d_outl, o), st))
+        _capi._check(lib.lk_subtract_f64_dev(h._h, n, _vp(self.d_flux.ptr), _vp(d_model.ptr), _vp(d_corr.ptr), st))
+        if to_host:
+            cut = self.n_off[1:-1]
+            corrected = np.split(d_corr.download(np.float64, n, stream=self.stream), cut)
+            outl = np.split(d_outl.download(np.uint8, n, stream=self.stream).astype(bool), cut)
+            return corrected, outl, d_w.download(np.float64, B * Kout, stream=self.stream).reshape(B, Kout)
+        out = self._carry(self._new(self.d_time, d_corr, self.d_flux_err, self.n_off, nan_free=self.nan_free, is_sorted=self.is_sorted))
+        out._keep = keep + [d_x, d_Y, d_keep, d_slab, d_cm, d_mu, d_sg, d_model, self]
+        return out, d_outl, d_w
+
     def _regress_shared_rows(self, Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, to_host, keep, resident=None):
         """``resident``: d_X already in HBM (a search that fits the same matrix many times uploads it once)."""
         h, B, K, n = self.handle, len(self), Xa.shape[1], self.n_cadences
@@ -764,7 +905,7 @@ class DeviceLightCurveBatch(object):
         return out, d_outl, d_w
 
     def cbv_correct(self, cbvs, cbv_indices=np.arange(1, 9), alpha=1e-20, ext_dm=None, cadence_mask=None, sigma=5, niters=5,
-                    to_host=False, cadenceno=None):
+                    to_host=False, cadenceno=None, cbv_time=None, gap_indicators=None, extrapolate=False, design_slab_mb=4096):
         """``CBVCorrector(lc, cbvs).correct_gaussian_prior(cbv_indices, alpha, ext_dm, cadence_mask)`` (reference
         cbvcorrector.py:333-395) for every target of the batch: columns [cbvs[:, idx - 1] | ext_dm | 1] shared by all targets
         (``cbvs``: (N, n_vectors), column j = basis vector j + 1; indices 1-based, out-of-range ones dropped, "ALL" accepted),
@@ -773,7 +914,38 @@ class DeviceLightCurveBatch(object):
         up; row b is what the scalar call at ``alpha[b]`` gives, bit for bit); a zero inside an array is a ``ValueError``:
         "no prior" stays the scalar ``alpha == 0.0``.  Returns what ``regression_correct`` returns.  ``cadenceno``: the cadence
         numbers of the rows of ``cbvs``; the batch may then be ragged and is matched by its own cadence numbers, exactly as
-        ``regression_correct(cadenceno=)`` (the ridge width is the median over the target's own matched cadences)."""
+        ``regression_correct(cadenceno=)`` (the ridge width is the median over the target's own matched cadences).
+
+        ``cbv_time``: the times of the rows of ``cbvs`` -> ``CBVCorrector(lc, interpolate_cbvs=True, extrapolate_cbvs=
+        extrapolate)``: the selected vectors are interpolated to every target's own times (``regression_correct(knot_time=)``;
+        ``gap_indicators``: bool (Nx,), True = a CBV cadence that is no knot, the reference's ``cbvs.gap_indicators``), the
+        constant column is written with them, and the batch needs neither one cadence count nor cadence numbers.  Not to be
+        combined with ``cadenceno``; ``ext_dm`` lives on the CBV cadences and is not interpolated: a ``ValueError``.  The
+        ridge width is the median over the target's own cadences that are fitted (inside the CBVs' span unless ``extrapolate``);
+        the dropped ones are counted in ``meta[b]["CADENCES_OUTSIDE_CBVS"]``."""
+        if cbv_time is not None:
+            if cadenceno is not None:
+                raise ValueError("cbv_correct: `cbv_time` interpolates the basis vectors to the targets' own times; it cannot be "
+                                 "combined with `cadenceno`")
+            if ext_dm is not None:
+                raise ValueError("cbv_correct(cbv_time=): `ext_dm` is not interpolated; put its columns on the targets' own "
+                                 "cadences and use regression_correct_batch, or fit it on the cadence grid (cadenceno=)")
+            if cbv_indices is None:
+                raise ValueError("nothing to fit: pass cbv_indices")
+            Ya = np.ascontiguousarray(_cbv_columns(cbvs, cbv_indices, None)[:, :-1])
+            alphas = None if np.ndim(alpha) == 0 else _alpha_per_target(alpha, len(self))
+            kk = None
+            if gap_indicators is not None:
+                gap = np.asarray(gap_indicators)
+                if gap.shape != (Ya.shape[0],) or (gap.dtype != np.bool_ and gap.dtype != np.uint8):
+                    raise ValueError("cbv_correct: gap_indicators must be a bool array of shape (%d,) (got %s of shape %s)"
+                                     % (Ya.shape[0], gap.dtype, gap.shape))
+                kk = gap == 0
+            src, d_cm, keep, knots = self._interp_front(Ya, cbv_time, kk, extrapolate, cadence_mask, "cbv_correct")
+            d_mu, d_sg = src._ridge_prior(None, Ya.shape[1] + 1, alpha, alphas, keep)
+            return src._regress_interp(knots, True, extrapolate, d_mu, d_sg, d_cm, sigma, niters, to_host, keep, design_slab_mb)
+        if gap_indicators is not None or extrapolate:
+            raise ValueError("cbv_correct: `gap_indicators` / `extrapolate` belong to the interpolated route: pass `cbv_time`")
         Xa = _cbv_columns(cbvs, cbv_indices, ext_dm)
         if cadenceno is not None:
             alphas = None if np.ndim(alpha) == 0 else _alpha_per_target(alpha, len(self))

@@ -102,7 +102,17 @@ them, in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5) times 
 by cadence number per target on 16 threads (noise of nanstd width from numpy's generator), then `from_arrays`.  Every timed
 region ends with a synchronise.  Written to profiles/stitch_walls.txt.  `stitch_trace`: resident calls only (four with
 `noise_std="std"`, then one with the CDPP), the run to put under `rocprofv3 --kernel-trace --stats`
-(`profiles/stitch_kernel_stats.txt`)."""
+(`profiles/stitch_kernel_stats.txt`).
+
+`cbvinterp`: the CBV correction of a batch whose cadences are NOT rows of the CBV table, two shapes in ONE process: `LK_WALLS_B`
+(default 1000) targets of about 3600 ten-minute cadences, each offset by a few seconds, on 18000 two-minute knots; and the same
+number of two-minute targets (about 18000 cadences) on 1200 thirty-minute knots; `LK_WALLS_K` (default 16) basis vectors +
+constant, the routes alternating, `LK_WALLS_REPS` (default 5) times after one warm-up.  I `from_arrays` ->
+`cbv_correct(cbv_time=)`; H the route such a batch had before: `to_host()` of the resident batch,
+`scipy.interpolate.PchipInterpolator` per target on 16 threads, `regression_correct_batch` on the per-target matrices.  Every timed
+region ends with a synchronise.  Written to profiles/cbvinterp_walls.txt.  `cbvroutes`: the two older routes, U uniform
+`cbv_correct` and C `cbv_correct(cadenceno=)` of `LK_WALLS_B` x `LK_WALLS_N` (default 1000 x 20000), printed only (run on a commit
+and on its parent to show they did not move)."""
 import cProfile
 import io
 import os
@@ -780,6 +790,107 @@ def cbvragged():
     sys.stdout.flush()
 
 
+def cbvinterp():
+    from concurrent.futures import ThreadPoolExecutor
+    from scipy.interpolate import PchipInterpolator
+    from lightkurve_amd import _capi, batch
+    from lightkurve_amd.correctors import DesignMatrix
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    from lightkurve_amd.lightcurve import LightCurve
+    B, K = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_K", "16")))
+    reps, alpha = int(os.environ.get("LK_WALLS_REPS", "5")), 1e-4
+    sync = _capi.Handle.get(0).synchronize
+    lines = []
+    # (name, knots, knot step [two-minute cadences], cadences per target, target step)
+    for name, Nx, kstep, n0, tstep in (("ten-minute targets on two-minute knots", 18000, 1, 3590, 5),
+                                       ("two-minute targets on thirty-minute knots", 1200, 15, 17900, 1)):
+        rng = np.random.default_rng(29)
+        x = 2000.0 + kstep * np.arange(Nx) / 720.0
+        cbvs = np.column_stack([np.sin(2 * np.pi * (x - x[0]) * rng.uniform(0.05, 1.0) + rng.uniform(0, 6)) for _ in range(K)])
+        ns = rng.integers(n0 - 90, n0 + 1, B)
+        n_off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        ntot = int(n_off[-1])
+        time_ = np.concatenate([x[0] + (rng.integers(1, 6) + tstep * np.arange(n)) / 720.0 + rng.uniform(-30, 30) / 86400.0 for n in ns])
+        assert time_.min() >= x[0] and time_.max() <= x[-1]
+        err = rng.uniform(0.5, 2.0, ntot) * 2e-4
+        w = rng.normal(0, 1e-3, (B, K))
+        true = PchipInterpolator(x, cbvs, axis=0)
+        flux = np.concatenate([1.0 + true(time_[n_off[b]:n_off[b + 1]]) @ w[b] for b in range(B)]) + rng.standard_normal(ntot) * err
+        resident = DeviceLightCurveBatch.from_arrays(time_, flux, err, n_off)
+        resident.synchronize()
+
+        def interpolated():
+            dev = DeviceLightCurveBatch.from_arrays(time_, flux, err, n_off)
+            return dev.cbv_correct(cbvs, cbv_indices="ALL", alpha=alpha, cbv_time=x)[0]
+
+        def through_host():
+            host = resident.to_host()
+
+            def one(b):
+                a, z = int(host.n_off[b]), int(host.n_off[b + 1])
+                Xb = np.column_stack([PchipInterpolator(x, cbvs, axis=0, extrapolate=False)(host.time[a:z]), np.ones(z - a)])
+                sg = np.full(K + 1, np.median(host.flux_err[a:z]) / np.sqrt(alpha))
+                return (LightCurve(time=host.time[a:z], flux=host.flux[a:z], flux_err=host.flux_err[a:z]),
+                        DesignMatrix(Xb, name="cbv", prior_mu=np.zeros(K + 1), prior_sigma=sg))
+
+            with ThreadPoolExecutor(max_workers=16) as ex:
+                pairs = list(ex.map(one, range(B)))
+            return batch.regression_correct_batch([p[0] for p in pairs], [p[1] for p in pairs])[0]
+
+        fns = {"I": interpolated, "H": through_host}
+        first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+        sync()
+        ts = {k: [] for k in fns}
+        for _ in range(reps):
+            for k, fn in fns.items():
+                ts[k].append(timed(lambda: (fn(), sync()))[0])
+        a, b = first["I"].flux_host(), np.concatenate(first["H"])
+        med = {k: float(np.median(v)) for k, v in ts.items()}
+        lines += ["CBV correction on interpolated CBVs, %s: %d targets, %d cadences in all, %d knots, K = %d + constant, alpha = %g"
+                  % (name, B, ntot, Nx, K, alpha),
+                  "  I    from_arrays -> cbv_correct(cbv_time=): the %.2f GB of interpolated matrices are written and read in HBM   %s"
+                  % (ntot * (K + 1) * 8 / 1e9, spread(ts["I"])),
+                  "  H    to_host() -> PchipInterpolator per target, 16 threads -> regression_correct_batch (%.2f GB go up)      %s"
+                  % (ntot * (K + 1) * 8 / 1e9, spread(ts["H"])),
+                  "  max |I - H| / median flux: %.2e" % (np.max(np.abs(a - b)) / np.median(flux)),
+                  "  H / I = %.1f" % (med["H"] / med["I"]), "  kernels alone: not measured", ""]
+        print("\n".join(lines[-7:]))
+        sys.stdout.flush()
+        del resident, first
+    write_walls("cbvinterp_walls.txt", lines[:-1])
+
+
+def cbvroutes():
+    from lightkurve_amd import _capi
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    B, N, K = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000"), ("LK_WALLS_K", "16")))
+    reps, alpha = int(os.environ.get("LK_WALLS_REPS", "5")), 1e-4
+    label = os.environ.get("LK_WALLS_LABEL", "this commit")
+    rng = np.random.default_rng(31)
+    t = np.linspace(0.0, 27.0, N)
+    cbvs = np.column_stack([np.sin(2 * np.pi * t * rng.uniform(0.05, 3.0) + rng.uniform(0, 6)) for _ in range(K)])
+    grid = 100000 + np.arange(N, dtype=np.int32)
+    err = rng.uniform(0.5, 2.0, B * N) * 2e-4
+    flux = (1.0 + rng.normal(0, 1e-3, (B, K)) @ cbvs.T).reshape(-1) + rng.standard_normal(B * N) * err
+    time_, cad = np.tile(t, B), np.tile(grid, B)
+    n_off = N * np.arange(B + 1, dtype=np.int64)
+    sync = _capi.Handle.get(0).synchronize
+    uni = DeviceLightCurveBatch.from_arrays(time_, flux, err, n_off)
+    rag = DeviceLightCurveBatch.from_arrays(time_, flux, err, n_off, cadenceno=cad)
+    fns = {"U": lambda: uni.cbv_correct(cbvs, cbv_indices="ALL", alpha=alpha),
+           "C": lambda: rag.cbv_correct(cbvs, cbv_indices="ALL", alpha=alpha, cadenceno=grid)}
+    for fn in fns.values():
+        fn()
+    sync()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(lambda: (fn(), sync()))[0])
+    print("cbvroutes  %-11s  U  resident cbv_correct(), uniform, %d x %d x %d + constant          %s" % (label, B, N, K, spread(ts["U"])))
+    print("cbvroutes  %-11s  C  resident cbv_correct(cadenceno=grid), every cadence on the grid    %s" % (label, spread(ts["C"])))
+    sys.stdout.flush()
+
+
 def ragged_field_for_walls(B, N, M, K):
     """B targets on a grid of N cadences, ~3 % of them missing per target (the shape of `cbvragged`), K basis vectors of which four
     carry systematics, M nearest neighbours -> dict of packed host arrays."""
@@ -1138,6 +1249,10 @@ def main():
         sff()
     if "cbvragged" in which:
         cbvragged()
+    if "cbvinterp" in which:
+        cbvinterp()
+    if "cbvroutes" in which:
+        cbvroutes()
     if "underfit_ragged" in which:
         underfit_ragged()
     if "cbvopt_ragged" in which:

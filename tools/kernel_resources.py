@@ -28,7 +28,7 @@ FIELDS = (("VGPRs", "VGPRs"), ("AGPRs", "AGPRs"), ("VGPRs Spill", "VGPR spill"),
 
 
 def flags_for(src):
-    extra = ["-ffp-contract=off"] if os.path.basename(src) in ("bls.hip", "blsstats.hip", "pgsmooth.hip", "pixcube.hip", "select.hip", "fillgaps.hip") else []    # as the Makefile
+    extra = ["-ffp-contract=off"] if os.path.basename(src) in ("bls.hip", "blsstats.hip", "pgsmooth.hip", "pixcube.hip", "select.hip", "fillgaps.hip", "interp.hip") else []    # as the Makefile
     return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra
 
 
