@@ -483,7 +483,7 @@ int lk_fits_cadenceno_batch_dev(lk_handle *h, int B, const uint8_t *raw, const i
 /* lk_fits_unpack_cube: one target-pixel file -> what PLDCorrector reads from a TargetPixelFile: time, quality and the
  * float32 pixel cubes FLUX / FLUX_ERR / FLUX_BKG / ... of the cadences the reference keeps
  * (src/lightkurve/targetpixelfile.py:332, 372, 380, 386, 398: hdu[1].data[col][quality_mask]; quality_mask =
- * (QUALITY & bitmask) == 0, :2120-2122 for Kepler / K2; TESS additionally drops NaN times when a bitmask is set,
+ * (QUALITY & bitmask) == 0, :2120-2122 for Kepler / K2; TESS additionally drops non-finite times when a bitmask is set,
  * :2794-2801 — pass keep_nan_time = 1 for Kepler files and for bitmask 0; a kept cadence without a finite TIME is
  * returned as 0.0 like TargetPixelFile.time does, :333-335).  raw: the BINTABLE's bytes as in the file;
  * ncols <= 4 pixel columns of npix big-endian float32 each at byte offsets col_off[]; cubes_out: ncols x n_rows x npix

@@ -1728,6 +1728,33 @@ def fits_unpack_batch(raws, descs, bitmasks, device=0):
     return t[:k], f[:k], e[:k], q[:k], new_off
 
 
+def fits_cadenceno_batch(raws, descs, cols, bitmasks, new_off, device=0):
+    """One integer column (CADENCENO) of the tables ``fits_unpack_batch`` decoded, for the rows it kept -> int32[new_off[-1]].
+    ``raws`` / ``descs`` / ``bitmasks`` as there; ``cols``: B x (byte offset, TFORM code 2..5) (fitsio.int_column); ``new_off``:
+    the offsets ``fits_unpack_batch`` returned.  The tables are packed back to back: this call needs no padding."""
+    h = Handle.get(device)
+    B = len(raws)
+    desc = np.ascontiguousarray(descs, dtype=np.int32).reshape(B, 10)
+    col = np.ascontiguousarray(cols, dtype=np.int32).reshape(B, 2)
+    mask = np.ascontiguousarray(bitmasks, dtype=np.int64).reshape(B)
+    new_off = np.ascontiguousarray(new_off, dtype=np.int64)
+    if new_off.shape != (B + 1,):
+        raise ValueError("new_off must be the B + 1 offsets fits_unpack_batch returned")
+    flat = [np.asarray(r, dtype=np.uint8).reshape(-1) for r in raws]
+    for b, r in enumerate(flat):
+        if r.size != int(desc[b, 0]) * int(desc[b, 1]):
+            raise ValueError("file %d: %d bytes of table data, descriptor says %d rows x %d bytes" % (b, r.size, desc[b, 1], desc[b, 0]))
+    raw_off = np.zeros(B + 1, dtype=np.int64)
+    raw_off[1:] = np.cumsum([r.size for r in flat])
+    raw = np.concatenate(flat) if B else np.zeros(0, dtype=np.uint8)
+    if raw.size == 0:
+        raw = np.zeros(1, dtype=np.uint8)       # (a non-NULL pointer for a batch of empty tables)
+    c = np.empty(max(int(new_off[-1]), 1) if B else 1, dtype=np.int32)
+    _check(_lib.lk_fits_cadenceno_batch(h._h, B, _ptr(raw, _c_u8p), _ptr(raw_off, _c_ip), _ptr(desc, _c_i32p), _ptr(col, _c_i32p),
+                                        _ptr(mask, _c_ip), _ptr(new_off, _c_ip), _ptr(c, _c_i32p)))
+    return c[:int(new_off[-1])] if B else c[:0]
+
+
 def fits_unpack_cube(raw, off_time, code_time, off_quality, code_quality, bitmask, keep_nan_time, col_offsets, npix, device=0):
     """One target-pixel file's table -> (time[k], quality[k], cubes[ncols, k, npix] float32) for the kept cadences."""
     h = Handle.get(device)

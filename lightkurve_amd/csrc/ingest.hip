@@ -207,15 +207,20 @@ __device__ __forceinline__ void fits_stage(const uint8_t *__restrict__ tab, long
 }
 
 // STAGE = false: records too long for the LDS stage (target-pixel files: kilobytes per cadence) — the few scalar fields
-// are read straight from global memory.  keep_nan_time: Kepler target-pixel files keep cadences whose TIME is NaN
-// (targetpixelfile.py:2120-2122), every other reader drops them.  row_out (nullable): source row of every kept record.
+// are read straight from global memory.  time_rule: which rows a reader drops for their TIME alone (TimeRule below).
+// row_out (nullable): source row of every kept record.
+enum TimeRule : int {
+    TIME_DROP_NAN = 0,        // light-curve readers: rows whose TIME is NaN go (generic.py:98-101), +-inf stays as it is
+    TIME_DROP_NONFINITE = 1,  // TessTargetPixelFile with a bitmask: quality_mask &= np.isfinite(TIME) (targetpixelfile.py:2798-2801)
+    TIME_KEEP_ALL = 2,        // Kepler / K2 target-pixel files and bitmask 0 (:2120-2122): every row; a time that is not finite reads 0
+};
 template <bool PACK, bool STAGE>
 __global__ __launch_bounds__(256) void fits_unpack_kernel(const uint8_t *__restrict__ raw, const int64_t *__restrict__ raw_off,
                                                            const FitsDesc *__restrict__ desc,
                                                            const int64_t *__restrict__ bitmask, int64_t *__restrict__ kept,
                                                            const int64_t *__restrict__ new_off, double *__restrict__ t_out,
                                                            double *__restrict__ f_out, double *__restrict__ e_out,
-                                                           int *__restrict__ q_out, int keep_nan_time,
+                                                           int *__restrict__ q_out, int time_rule,
                                                            int *__restrict__ row_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char fits_lds[];
     __shared__ int s_cnt[4];
@@ -232,8 +237,10 @@ __global__ __launch_bounds__(256) void fits_unpack_kernel(const uint8_t *__restr
         if (STAGE) {
             fits_stage(tab, r0, nr, d.row_bytes, fits_lds);
             __syncthreads();
-            const int skew = (int)((r0 * d.row_bytes) & 3);  // the staged words start at a 4-byte boundary
-            rec = fits_lds + skew + (size_t)tid * d.row_bytes;
+            // r0 is a multiple of FITS_ROWS = 256, so the trip's first byte r0 * row_bytes is a multiple of 4 for every
+            // record length: the staged words start exactly at record r0
+            static_assert(FITS_ROWS % 4 == 0, "a trip must start at a 4-byte boundary of the table");
+            rec = fits_lds + (size_t)tid * d.row_bytes;
         } else {
             rec = tab + (size_t)(r0 + min(tid, nr - 1)) * d.row_bytes;
         }
@@ -243,7 +250,8 @@ __global__ __launch_bounds__(256) void fits_unpack_kernel(const uint8_t *__restr
         if (tid < nr) {
             tv = fits_real(rec, d.off_t, d.code_t);
             if (d.off_q >= 0) qv = fits_int(rec, d.off_q, d.code_q);
-            keep = (keep_nan_time || !isnan(tv)) && (qv & mask) == 0;
+            const bool has_time = time_rule == TIME_KEEP_ALL || (time_rule == TIME_DROP_NAN ? !isnan(tv) : isfinite(tv));
+            keep = has_time && (qv & mask) == 0;
             if (PACK && keep) {
                 fv = fits_real(rec, d.off_f, d.code_f);
                 if (d.off_e >= 0) ev = fits_real(rec, d.off_e, d.code_e);
@@ -260,7 +268,7 @@ __global__ __launch_bounds__(256) void fits_unpack_kernel(const uint8_t *__restr
         if (PACK && keep) {
             const long long pos = base + before + __popcll(bal & ((1ull << lane) - 1ull));
             // a kept cadence without a time reads 0, as TargetPixelFile.time makes it (targetpixelfile.py:333-335)
-            t_out[pos] = (keep_nan_time && !isfinite(tv)) ? 0.0 : tv;
+            t_out[pos] = (time_rule == TIME_KEEP_ALL && !isfinite(tv)) ? 0.0 : tv;
             f_out[pos] = fv;
             if (e_out) e_out[pos] = ev;
             if (q_out) q_out[pos] = (int)qv;
@@ -315,11 +323,11 @@ int fits_unpack_launch(lk_handle *h, int B, const uint8_t *raw, const int64_t *r
         if (rc_) return rc_;
     }
     hipLaunchKernelGGL((fits_unpack_kernel<false, true>), dim3(B), dim3(256), lds, stream, raw, d_roff, d_desc, d_mask, d_kept,
-                       (const int64_t *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr, (int *)nullptr, 0,
-                       (int *)nullptr);
+                       (const int64_t *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr, (int *)nullptr,
+                       (int)TIME_DROP_NAN, (int *)nullptr);
     hipLaunchKernelGGL(ingest_scan_kernel, dim3(1), dim3(1024), 0, stream, d_kept, B, d_new);
     hipLaunchKernelGGL((fits_unpack_kernel<true, true>), dim3(B), dim3(256), lds, stream, raw, d_roff, d_desc, d_mask,
-                       (int64_t *)nullptr, d_new, t_out, f_out, e_out, q_out, 0, (int *)nullptr);
+                       (int64_t *)nullptr, d_new, t_out, f_out, e_out, q_out, (int)TIME_DROP_NAN, (int *)nullptr);
     LK_HIP_CHECK(hipMemcpyAsync(new_off_host, d_new, (size_t)(B + 1) * 8, hipMemcpyDeviceToHost, stream));
     LK_HIP_CHECK(hipStreamSynchronize(stream));
     LK_HIP_CHECK(hipGetLastError());
@@ -453,12 +461,13 @@ int fits_cube_launch(lk_handle *h, const uint8_t *raw, int row_bytes, int n_rows
     LK_HIP_CHECK(hipMemcpyAsync(d_mask, &bitmask, 8, hipMemcpyHostToDevice, stream));
     LK_HIP_CHECK(hipMemcpyAsync(d_desc, &desc, sizeof(FitsDesc), hipMemcpyHostToDevice, stream));
     LK_HIP_CHECK(hipStreamSynchronize(stream));  // the sources are on this function's stack
+    const int time_rule = keep_nan_time ? TIME_KEEP_ALL : TIME_DROP_NONFINITE;
     hipLaunchKernelGGL((fits_unpack_kernel<false, false>), dim3(1), dim3(256), 16, stream, raw, d_roff, d_desc, d_mask, d_kept,
                        (const int64_t *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr, (int *)nullptr,
-                       keep_nan_time, (int *)nullptr);
+                       time_rule, (int *)nullptr);
     hipLaunchKernelGGL(ingest_scan_kernel, dim3(1), dim3(1024), 0, stream, d_kept, 1, d_new);
     hipLaunchKernelGGL((fits_unpack_kernel<true, false>), dim3(1), dim3(256), 16, stream, raw, d_roff, d_desc, d_mask,
-                       (int64_t *)nullptr, d_new, t_out, d_dummy, (double *)nullptr, q_out, keep_nan_time, d_rows);
+                       (int64_t *)nullptr, d_new, t_out, d_dummy, (double *)nullptr, q_out, time_rule, d_rows);
     int64_t newoff[2];
     LK_HIP_CHECK(hipMemcpyAsync(newoff, d_new, 16, hipMemcpyDeviceToHost, stream));
     LK_HIP_CHECK(hipStreamSynchronize(stream));

@@ -239,7 +239,7 @@ def int_column(tab, name="cadenceno"):
 def pixel_columns(tab, columns=("flux", "flux_err", "flux_bkg"), quality_bitmask="default", mission=None):
     """Where a target-pixel file keeps TIME, QUALITY and its pixel cubes, and which cadences the reference keeps:
     quality_mask = (QUALITY & bitmask) == 0 (targetpixelfile.py:2120-2122 Kepler / K2, :2794-2797 TESS), TESS also drops
-    NaN times unless the bitmask is 0 / 'none' (:2798-2801).  Returns a dict for ``_capi.fits_unpack_cube``."""
+    the cadences without a finite time unless the bitmask is 0 / 'none' (:2798-2801).  Returns a dict for ``_capi.fits_unpack_cube``."""
     if mission is None:
         tel = str(tab.primary.get("TELESCOP", tab.header.get("TELESCOP", ""))).strip().lower()
         mission = "tess" if tel == "tess" else "kepler"
