@@ -21,8 +21,6 @@ No torch: device memory, copies and the stream come from liblkhip.so itself (``l
 """
 import ctypes
 import math
-import threading
-import weakref
 
 import numpy as np
 
@@ -32,117 +30,18 @@ from . import foldbin as _fb
 from . import packed
 from . import periodogram as _pg
 from . import seismology as _seis
+from .cotrend import CotrendMixin, _alpha_per_target, _cadenceno_array, _cbv_columns  # noqa: F401  (names others import from here)
+from .devmem import DeviceBuffer, _Pool, _ip, _off_ptr, _pool, _upload, _vp, release_device_pool  # noqa: F401
 
 __all__ = ["DeviceBuffer", "DeviceLightCurveBatch", "DeviceFoldedBatch", "DevicePhaseCurveBatch", "DeviceBLSResult",
            "DevicePeriodogramBatch", "DevicePixelCubeBatch", "release_device_pool"]
 
-_vp = ctypes.c_void_p
-_ip = ctypes.POINTER(ctypes.c_int64)
 _dp = ctypes.POINTER(ctypes.c_double)
 _i32p = ctypes.POINTER(ctypes.c_int32)
 
 
-# ------------------------------------------------------------------------------------------------ device memory
-class _Pool(object):
-    """Free list of device allocations per handle.  ``lk_dev_free`` (hipFree) synchronises the whole device, and a pipeline
-    drops an intermediate batch at every stage: a dropped buffer goes back to this list instead and is handed out again
-    to the next request it fits (work on one handle is stream-ordered — include/lkhip.h "Conventions" — so a kernel still
-    reading the old contents finishes before the new owner's kernels start).  ``release_device_pool()`` really frees."""
-
-    def __init__(self, handle):
-        self.handle = handle
-        self.free = []                  # (capacity, ptr)
-        # re-entrant: a buffer that dies in a reference cycle is finalised by the cyclic collector, which may run at any
-        # allocation of this thread, also inside take() while the lock is held; give() then only appends
-        self.lock = threading.RLock()
-
-    def take(self, nbytes):
-        nbytes = max(int(nbytes), 1)
-        with self.lock:
-            fit = [i for i, (cap, _) in enumerate(self.free) if nbytes <= cap <= 2 * nbytes + (1 << 16)]
-            if fit:
-                return self.free.pop(min(fit, key=lambda i: self.free[i][0]))
-        cap = (nbytes + 255) & ~255
-        ptr = _vp()
-        _capi._check(_capi._lib.lk_dev_alloc(self.handle._h, ctypes.byref(ptr), cap))
-        return cap, ptr.value
-
-    def give(self, cap, ptr):
-        with self.lock:
-            self.free.append((cap, ptr))
-
-    def release(self):
-        with self.lock:
-            items, self.free = self.free, []
-        for _cap, ptr in items:
-            _capi._lib.lk_dev_free(self.handle._h, _vp(ptr))
-
-
-_POOLS = {}
-
-
-def _pool(handle):
-    p = _POOLS.get(handle.device)
-    if p is None or p.handle is not handle:
-        p = _POOLS[handle.device] = _Pool(handle)
-    return p
-
-
-def release_device_pool():
-    """hipFree every idle buffer of the device free lists (buffers still owned by live objects are not touched)."""
-    for p in list(_POOLS.values()):
-        p.release()
-
-
-class DeviceBuffer(object):
-    """``nbytes`` of HBM owned by this object (returned to the free list when it is garbage collected)."""
-    __slots__ = ("ptr", "nbytes", "capacity", "handle", "__weakref__")
-
-    def __init__(self, handle, nbytes):
-        pool = _pool(handle)
-        self.capacity, self.ptr = pool.take(nbytes)
-        self.nbytes = int(nbytes)
-        self.handle = handle
-        weakref.finalize(self, pool.give, self.capacity, self.ptr)
-
-    def upload(self, host, stream=0):
-        host = np.ascontiguousarray(host)
-        if host.nbytes > self.capacity:
-            raise ValueError("host array of %d bytes into a device buffer of %d" % (host.nbytes, self.capacity))
-        _capi._check(_capi._lib.lk_memcpy_h2d(self.handle._h, _vp(self.ptr), _vp(host.ctypes.data), host.nbytes,
-                                             _vp(stream or None)))
-        return host          # (the caller keeps it alive until the stream has consumed it)
-
-    def download(self, dtype, count, out=None, stream=0, offset_bytes=0):
-        """``count`` elements of ``dtype`` starting ``offset_bytes`` into the buffer -> host array (synchronises ``stream``)."""
-        dtype = np.dtype(dtype)
-        count = int(count)
-        if out is None:
-            out = np.empty(count, dtype=dtype)
-        if out.dtype != dtype or out.size != count or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous %s array of %d elements" % (dtype, count))
-        if offset_bytes + count * dtype.itemsize > self.capacity:
-            raise ValueError("read past the end of the device buffer")
-        h = self.handle
-        _capi._check(_capi._lib.lk_memcpy_d2h(h._h, _vp(out.ctypes.data), _vp(self.ptr + offset_bytes), out.nbytes,
-                                             _vp(stream or None)))
-        _capi._check(_capi._lib.lk_stream_synchronize(h._h, _vp(stream or None)))
-        return out
-
-
-def _upload(handle, host, stream, dtype=np.float64):
-    host = np.ascontiguousarray(host, dtype=dtype)
-    buf = DeviceBuffer(handle, host.nbytes)
-    keep = buf.upload(host, stream)
-    return buf, keep
-
-
-def _off_ptr(n_off):
-    return n_off.ctypes.data_as(_ip)
-
-
 # ------------------------------------------------------------------------------------------------ the batch
-class DeviceLightCurveBatch(object):
+class DeviceLightCurveBatch(CotrendMixin):
     """B light curves as packed float64 arrays IN HBM (``d_time`` / ``d_flux`` / ``d_flux_err``: ``DeviceBuffer``) plus the
     prefix offsets ``n_off`` on the host (every launcher sizes its grid from them).  All work goes to ``stream`` (an opaque
     stream handle: ``0`` = the null stream, ``lk_stream_create``'s, or e.g. ``torch.cuda.current_stream().cuda_stream``) of
@@ -611,1082 +510,6 @@ class DeviceLightCurveBatch(object):
         out._keep = list(src._keep)
         out._sorted()
         return out
-
-    # ---------------------------------------------------------------- cotrending on one shared design matrix
-    def _uniform_n(self, rows, what):
-        """The one cadence count of the batch, checked against the ``rows`` of the shared design matrix unless ``rows`` is None
-        (no device call)."""
-        counts = np.diff(self.n_off)
-        if len(counts) == 0:
-            raise ValueError("%s needs at least one light curve" % what)
-        if counts.min() != counts.max():
-            if rows is None:
-                raise ValueError("%s needs one cadence count for every target: this batch has between %d and %d cadences per target"
-                                 % (what, counts.min(), counts.max()))
-            raise ValueError("%s needs one cadence count for every target: this batch has between %d and %d cadences per target "
-                             "and the design matrix has %d rows (regression_correct_batch takes ragged batches)"
-                             % (what, counts.min(), counts.max(), rows))
-        N = int(counts[0])
-        if rows is not None and rows != N:
-            raise ValueError("%s: the design matrix has %d rows, the light curves have %d cadences" % (what, rows, N))
-        return N
-
-    def regression_correct(self, X, prior_mu=None, prior_sigma=None, cadence_mask=None, sigma=5, niters=5, to_host=False, rows=None,
-                           cadenceno=None, knot_time=None, extrapolate=False, knot_keep=None, design_slab_mb=4096):
-        """``RegressionCorrector(lc).correct(X, cadence_mask, sigma, niters)`` (reference regressioncorrector.py:191-279,
-        ``propagate_errors=False``) for every target of the batch on ONE shared design matrix: ``X`` is a host array (N, K),
-        K <= 64, or a ``DesignMatrix`` / ``DesignMatrixCollection`` (its own priors go to every target unless ``prior_mu`` /
-        ``prior_sigma``, broadcastable to (B, K), are given).  X is uploaded once; no (B N) x K matrix exists.  The corrected
-        flux is flux - model, formed on the device; flux_err is unchanged.  ``cadence_mask``: bool (B, N), True = used in the
-        fit.  ``to_host=False`` -> (``DeviceLightCurveBatch``, ``DeviceBuffer`` of the B x N outlier bytes, ``DeviceBuffer``
-        of the B x K coefficients), nothing synchronised after the input check; ``to_host=True`` -> (corrected[B, N],
-        outlier[B, N] bool, coefficients[B, K]).
-
-        A RAGGED batch (``from_fits``, ``remove_nans``, ``remove_outliers``, ``select``) is fitted on the same one matrix when
-        the call says which row of ``X`` each cadence uses: ``cadenceno`` = the integer cadence numbers of the Nx rows of ``X``,
-        strictly increasing, matched against the batch's own ``d_cadenceno`` column (``CotrendingBasisVectors.align``: a
-        cadence of a target that is not on the grid is dropped first, the count per target goes to
-        ``meta[b]["CADENCES_NOT_ON_GRID"]`` of the result; a grid row that no target has carries no weight), or ``rows`` =
-        int (sum n,), per target strictly increasing indices into the rows of ``X``.  Per target the numerics are
-        ``RegressionCorrector.correct`` on ``X[rows_b]``.  ``cadence_mask`` is then ragged: bool (sum n,) over the cadences of
-        this batch, or a ``DeviceBuffer`` of that many bytes.  The result is the same triple on the batch's own offsets
-        (outlier bytes (sum n,)); ``to_host=True`` -> (list of corrected[n_b], list of outlier[n_b] bool, coefficients[B, K]).
-
-        The third route, for light curves whose cadences are NOT rows of ``X`` (another cadence length, binned light curves,
-        times that differ by seconds, no cadence numbers): ``knot_time`` = the times of the Nx rows of ``X``, float (Nx,),
-        strictly increasing where ``knot_keep`` (bool (Nx,), None = everywhere; the reference's ``~gap_indicators``) is
-        true.  Every column of ``X`` is then interpolated to each target's own times as ``CotrendingBasisVectors.interpolate``
-        does (``scipy.interpolate.PchipInterpolator`` on the kept rows; ``lk_pchip_interp_batch_dev``) and every target is
-        fitted on its own interpolated matrix (``lk_regress_batch_dev``; any K that call takes).  Not to be combined with
-        ``rows`` / ``cadenceno``.  ``extrapolate=False``: a cadence outside the kept knots' span (or with a time that is not
-        finite) is dropped before the fit, exactly as an off-grid cadence is, and counted in
-        ``meta[b]["CADENCES_OUTSIDE_CBVS"]`` of the result; a target left with no cadence is a ``ValueError`` naming it.
-        ``extrapolate=True``: nothing is dropped, the first / last cubic is continued as scipy does.  ``cadence_mask`` and
-        the results are ragged as above.  The interpolated matrices are 8 K (sum n) bytes: whole targets are fitted in
-        groups whose matrices stay under ``design_slab_mb`` MiB (a target's result does not depend on the grouping, bit
-        for bit)."""
-        Xa, mu, sg = _design_arrays(X, prior_mu, prior_sigma)
-        if knot_time is not None:
-            if rows is not None or cadenceno is not None:
-                raise ValueError("regression_correct: `knot_time` interpolates X to the targets' own times; it cannot be combined "
-                                 "with `rows` / `cadenceno`")
-            src, d_cm, keep, knots = self._interp_front(Xa, knot_time, knot_keep, extrapolate, cadence_mask, "regression_correct")
-            B, K = len(src), Xa.shape[1]
-            d_mu = d_sg = None
-            if mu is not None:
-                d_mu, k1 = _upload(src.handle, np.broadcast_to(mu, (B, K)), src.stream)
-                d_sg, k2 = _upload(src.handle, np.broadcast_to(sg, (B, K)), src.stream)
-                keep += [k1, k2]
-            return src._regress_interp(knots, False, extrapolate, d_mu, d_sg, d_cm, sigma, niters, to_host, keep, design_slab_mb)
-        if knot_keep is not None or extrapolate:
-            raise ValueError("regression_correct: `knot_keep` / `extrapolate` belong to the interpolated route: pass `knot_time`")
-        if rows is not None or cadenceno is not None:
-            src, d_rows, d_cm, keep = self._aligned(Xa.shape[0], rows, cadenceno, cadence_mask, "regression_correct")
-            B, K = len(src), Xa.shape[1]
-            d_mu = d_sg = None
-            if mu is not None:
-                d_mu, k1 = _upload(src.handle, np.broadcast_to(mu, (B, K)), src.stream)
-                d_sg, k2 = _upload(src.handle, np.broadcast_to(sg, (B, K)), src.stream)
-                keep += [k1, k2]
-            return src._regress_shared_rows(Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, to_host, keep)
-        N = self._uniform_n(Xa.shape[0], "regression_correct")
-        B, K = len(self), Xa.shape[1]
-        d_mu = d_sg = None
-        keep = []
-        h = self.handle
-        if mu is not None:
-            d_mu, k1 = _upload(h, np.broadcast_to(mu, (B, K)), self.stream)
-            d_sg, k2 = _upload(h, np.broadcast_to(sg, (B, K)), self.stream)
-            keep += [k1, k2]
-        return self._regress_shared(Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, keep)
-
-    def _aligned(self, Nx, rows, cadenceno, cadence_mask, what):
-        """The ragged route's front end -> (batch to fit, d_rows, d_cm, keep).  Every check that needs no device comes first.
-        With ``cadenceno`` the rows come from ``lk_align_rows_batch_dev``; when a target has cadences that are not on the grid
-        the batch (and a ragged ``cadence_mask``) is ``select``-ed down to the matched cadences and aligned again."""
-        n, B = self.n_cadences, len(self)
-        if rows is not None and cadenceno is not None:
-            raise ValueError("%s: pass `rows` or `cadenceno`, not both" % what)
-        if B == 0 or n == 0:
-            raise ValueError("%s needs at least one light curve with cadences" % what)
-        cm = None
-        if cadence_mask is not None and not isinstance(cadence_mask, DeviceBuffer):
-            cm = np.ascontiguousarray(cadence_mask, dtype=np.uint8)
-            if cm.shape != (n,):
-                raise ValueError("%s: with `rows` / `cadenceno` cadence_mask is ragged, one entry per cadence of the batch: "
-                                 "shape (%d,) (got %s)" % (what, n, cm.shape))
-        elif cadence_mask is not None and cadence_mask.nbytes != n:
-            raise ValueError("%s: cadence_mask holds %d bytes, the batch has %d cadences" % (what, cadence_mask.nbytes, n))
-        if rows is not None:
-            r = _cadenceno_array(rows, n, "rows")
-            if r.size and (r.min() < 0 or r.max() >= Nx):
-                raise ValueError("%s: rows must be indices into the %d rows of the design matrix" % (what, Nx))
-        else:
-            grid = _cadenceno_array(cadenceno, Nx, "cadenceno (one per row of the design matrix)")
-            if np.any(np.diff(grid) <= 0):
-                raise ValueError("%s: the grid's cadence numbers must be strictly increasing" % what)
-            if getattr(self, "d_cadenceno", None) is None:
-                raise ValueError("%s(cadenceno=) needs a batch that carries cadence numbers: from_fits of files with a CADENCENO "
-                                 "column, or from_arrays(..., cadenceno=)" % what)
-        h, st, keep = self.handle, _vp(self.stream or None), []
-        if rows is not None:
-            d_rows, k = _upload(h, r, self.stream, np.int32)
-            keep.append(k)
-            src = self
-        else:
-            d_grid, k = _upload(h, grid, self.stream, np.int32)
-            keep += [k, d_grid]
-            src, dropped = self, np.zeros(B, dtype=np.int64)
-            d_rows = DeviceBuffer(h, n * 4)
-            try:
-                _capi._check(_capi._lib.lk_align_rows_batch_dev(h._h, B, _off_ptr(self.n_off), _vp(self.d_cadenceno.ptr), Nx,
-                                                                _vp(d_grid.ptr), _vp(d_rows.ptr), None, st))
-            except ValueError as exc:
-                if "not on the grid" not in str(exc):
-                    raise
-                off_grid = d_rows.download(np.int32, n, stream=self.stream) < 0       # (rows is written before the call fails)
-                dropped = np.diff(np.concatenate([[0], np.cumsum(off_grid, dtype=np.int64)])[self.n_off])
-                src = self.select(off_grid, invert=True)
-                if cm is not None:
-                    cm = np.ascontiguousarray(cm[~off_grid])
-                elif cadence_mask is not None:
-                    cm = np.ascontiguousarray(cadence_mask.download(np.uint8, n, stream=self.stream)[~off_grid])
-                    cadence_mask = None
-                d_rows = DeviceBuffer(h, max(src.n_cadences, 1) * 4)
-                _capi._check(_capi._lib.lk_align_rows_batch_dev(h._h, B, _off_ptr(src.n_off), _vp(src.d_cadenceno.ptr), Nx,
-                                                                _vp(d_grid.ptr), _vp(d_rows.ptr), None, st))
-            if src is self:
-                src = self._carry(self._new(self.d_time, self.d_flux, self.d_flux_err, self.n_off, nan_free=self.nan_free,
-                                            is_sorted=self.is_sorted))
-            for m, c in zip(src.meta, dropped):
-                m["CADENCES_NOT_ON_GRID"] = int(c)
-        d_cm = cadence_mask if isinstance(cadence_mask, DeviceBuffer) else None
-        if cm is not None:
-            d_cm, k = _upload(h, cm, self.stream, np.uint8)
-            keep.append(k)
-        return src, d_rows, d_cm, keep
-
-    def _interp_front(self, Ya, knot_time, knot_keep, extrapolate, cadence_mask, what):
-        """The interpolated route's front end -> (batch to fit, d_cm, keep, (d_x, d_Y, d_keep, Nx, K)).  Every check that
-        needs no device comes first.  Without ``extrapolate`` the inside bytes come from ``lk_pchip_interp_batch_dev`` (which
-        also checks the knots) and the batch (and ``cadence_mask``) is ``select``-ed down to the cadences inside the span."""
-        n, B = self.n_cadences, len(self)
-        x = np.asarray(knot_time)
-        if x.ndim != 1 or x.shape[0] != Ya.shape[0] or not (np.issubdtype(x.dtype, np.floating) or np.issubdtype(x.dtype, np.integer)):
-            raise ValueError("%s: the knot times must be a real array of shape (%d,), one per row of the matrix (got %s of shape %s)"
-                             % (what, Ya.shape[0], x.dtype, x.shape))
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        kk = None
-        if knot_keep is not None:
-            kk = np.asarray(knot_keep)
-            if kk.shape != x.shape or (kk.dtype != np.bool_ and kk.dtype != np.uint8):
-                raise ValueError("%s: the knot mask must be a bool array of shape (%d,) (got %s of shape %s)"
-                                 % (what, x.size, kk.dtype, kk.shape))
-            kk = np.ascontiguousarray(kk != 0, dtype=np.uint8)
-        if int(x.size if kk is None else kk.sum()) < 2:
-            raise ValueError("%s: interpolation needs at least 2 knots that are kept" % what)
-        if B == 0 or n == 0:
-            raise ValueError("%s needs at least one light curve with cadences" % what)
-        cm = None
-        if cadence_mask is not None and not isinstance(cadence_mask, DeviceBuffer):
-            cm = np.ascontiguousarray(cadence_mask, dtype=np.uint8)
-            if cm.shape != (n,):
-                raise ValueError("%s: on the interpolated route cadence_mask is ragged, one entry per cadence of the batch: "
-                                 "shape (%d,) (got %s)" % (what, n, cm.shape))
-        elif cadence_mask is not None and cadence_mask.nbytes != n:
-            raise ValueError("%s: cadence_mask holds %d bytes, the batch has %d cadences" % (what, cadence_mask.nbytes, n))
-        h, st, keep = self.handle, _vp(self.stream or None), []
-        d_x, k1 = _upload(h, x, self.stream)
-        d_Y, k2 = _upload(h, Ya, self.stream)
-        keep += [k1, k2]
-        d_keep = None
-        if kk is not None:
-            d_keep, k3 = _upload(h, kk, self.stream, np.uint8)
-            keep.append(k3)
-        knots = (d_x, d_Y, d_keep, Ya.shape[0], Ya.shape[1])
-        src, dropped = self, np.zeros(B, dtype=np.int64)
-        if not extrapolate:
-            d_in = DeviceBuffer(h, n)
-            _capi._check(_capi._lib.lk_pchip_interp_batch_dev(h._h, B, _off_ptr(self.n_off), _vp(self.d_time.ptr), Ya.shape[0],
-                                                              Ya.shape[1], _vp(d_x.ptr), _vp(d_Y.ptr),
-                                                              _vp(d_keep.ptr if d_keep is not None else None), 0, 0, None,
-                                                              _vp(d_in.ptr), st))
-            outside = d_in.download(np.uint8, n, stream=self.stream) == 0
-            if outside.any():
-                dropped = np.diff(np.concatenate([[0], np.cumsum(outside, dtype=np.int64)])[self.n_off])
-                empty = np.flatnonzero(dropped == np.diff(self.n_off))
-                if empty.size:
-                    raise ValueError("%s: target %d has no cadence inside the span of the knots (extrapolate=True keeps them)"
-                                     % (what, int(empty[0])))
-                src = self.select(d_in)
-                if cm is not None:
-                    cm = np.ascontiguousarray(cm[~outside])
-                elif cadence_mask is not None:
-                    cm = np.ascontiguousarray(cadence_mask.download(np.uint8, n, stream=self.stream)[~outside])
-                    cadence_mask = None
-        if np.any(np.diff(src.n_off) == 0):
-            raise ValueError("%s: target %d has no cadence" % (what, int(np.flatnonzero(np.diff(src.n_off) == 0)[0])))
-        if src is self:
-            src = self._carry(self._new(self.d_time, self.d_flux, self.d_flux_err, self.n_off, nan_free=self.nan_free,
-                                        is_sorted=self.is_sorted))
-        for m, c in zip(src.meta, dropped):
-            m["CADENCES_OUTSIDE_CBVS"] = int(c)
-        d_cm = cadence_mask if isinstance(cadence_mask, DeviceBuffer) else None
-        if cm is not None:
-            d_cm, k = _upload(h, cm, self.stream, np.uint8)
-            keep.append(k)
-        return src, d_cm, keep, knots
-
-    def _regress_interp(self, knots, append_constant, extrapolate, d_mu, d_sg, d_cm, sigma, niters, to_host, keep, design_slab_mb):
-        """Interpolate and fit, whole targets in groups whose design matrices fit ``design_slab_mb``; one slab, reused."""
-        d_x, d_Y, d_keep, Nx, K = knots
-        h, B, n, st = self.handle, len(self), self.n_cadences, _vp(self.stream or None)
-        Kout = K + int(bool(append_constant))
-        budget = int(float(design_slab_mb) * (1 << 20)) // (8 * Kout)        # cadences per group
-        if budget < 1:
-            raise ValueError("design_slab_mb=%r holds not one row of the design matrix" % (design_slab_mb,))
-        groups, b0 = [], 0
-        while b0 < B:
-            b1 = b0 + 1
-            while b1 < B and self.n_off[b1 + 1] - self.n_off[b0] <= budget and b1 - b0 < 65535:
-                b1 += 1
-            groups.append((b0, b1))
-            b0 = b1
-        d_slab = DeviceBuffer(h, 8 * Kout * int(max(self.n_off[b1] - self.n_off[b0] for b0, b1 in groups)))
-        d_w, d_model, d_corr, d_outl = DeviceBuffer(h, B * Kout * 8), DeviceBuffer(h, n * 8), DeviceBuffer(h, n * 8), DeviceBuffer(h, n)
-        lib = _capi._lib
-
-        def at(buf, nbytes):
-            return _vp(buf.ptr + int(nbytes)) if buf is not None else _vp(None)
-
-        for b0, b1 in groups:
-            o = int(self.n_off[b0])
-            off = np.ascontiguousarray(self.n_off[b0:b1 + 1] - o)
-            _capi._check(lib.lk_pchip_interp_batch_dev(h._h, b1 - b0, _off_ptr(off), at(self.d_time, 8 * o), Nx, K, _vp(d_x.ptr),
-                                                       _vp(d_Y.ptr), at(d_keep, 0), int(bool(extrapolate)), int(bool(append_constant)),
-                                                       _vp(d_slab.ptr), None, st))
-            _capi._check(lib.lk_regress_batch_dev(h._h, b1 - b0, _off_ptr(off), Kout, _vp(d_slab.ptr), at(self.d_flux, 8 * o),
-                                                  at(self.d_flux_err, 8 * o), at(d_cm, o), at(d_mu, 8 * Kout * b0),
-                                                  at(d_sg, 8 * Kout * b0), float(sigma), int(niters), at(d_w, 8 * Kout * b0),
-                                                  at(d_model, 8 * o), at(d_outl, o), st))
-        _capi._check(lib.lk_subtract_f64_dev(h._h, n, _vp(self.d_flux.ptr), _vp(d_model.ptr), _vp(d_corr.ptr), st))
-        if to_host:
-            cut = self.n_off[1:-1]
-            corrected = np.split(d_corr.download(np.float64, n, stream=self.stream), cut)
-            outl = np.split(d_outl.download(np.uint8, n, stream=self.stream).astype(bool), cut)
-            return corrected, outl, d_w.download(np.float64, B * Kout, stream=self.stream).reshape(B, Kout)
-        out = self._carry(self._new(self.d_time, d_corr, self.d_flux_err, self.n_off, nan_free=self.nan_free, is_sorted=self.is_sorted))
-        out._keep = keep + [d_x, d_Y, d_keep, d_slab, d_cm, d_mu, d_sg, d_model, self]
-        return out, d_outl, d_w
-
-    def _regress_shared_rows(self, Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, to_host, keep, resident=None):
-        """``resident``: d_X already in HBM (a search that fits the same matrix many times uploads it once)."""
-        h, B, K, n = self.handle, len(self), Xa.shape[1], self.n_cadences
-        if resident is not None:
-            d_X = resident
-        else:
-            d_X, k = _upload(h, Xa, self.stream)
-            keep.append(k)
-        d_w, d_model, d_corr, d_outl = DeviceBuffer(h, B * K * 8), DeviceBuffer(h, n * 8), DeviceBuffer(h, n * 8), DeviceBuffer(h, n)
-        _capi._check(_capi._lib.lk_regress_shared_rows_batch_dev(
-            h._h, B, _off_ptr(self.n_off), _vp(d_rows.ptr), Xa.shape[0], K, _vp(d_X.ptr), _vp(self.d_flux.ptr),
-            _vp(self.d_flux_err.ptr if self.d_flux_err is not None else None), _vp(d_cm.ptr if d_cm is not None else None),
-            _vp(d_mu.ptr if d_mu is not None else None), _vp(d_sg.ptr if d_sg is not None else None), float(sigma), int(niters),
-            _vp(d_w.ptr), _vp(d_model.ptr), _vp(d_outl.ptr), None, _vp(self.stream or None)))
-        _capi._check(_capi._lib.lk_subtract_f64_dev(h._h, n, _vp(self.d_flux.ptr), _vp(d_model.ptr), _vp(d_corr.ptr),
-                                                    _vp(self.stream or None)))
-        if to_host:
-            cut = self.n_off[1:-1]
-            corrected = np.split(d_corr.download(np.float64, n, stream=self.stream), cut)
-            outl = np.split(d_outl.download(np.uint8, n, stream=self.stream).astype(bool), cut)
-            return corrected, outl, d_w.download(np.float64, B * K, stream=self.stream).reshape(B, K)
-        out = self._carry(self._new(self.d_time, d_corr, self.d_flux_err, self.n_off, nan_free=self.nan_free, is_sorted=self.is_sorted))
-        out._keep = keep + [d_X, d_rows, d_cm, d_mu, d_sg, d_model, self]
-        return out, d_outl, d_w
-
-    def cbv_correct(self, cbvs, cbv_indices=np.arange(1, 9), alpha=1e-20, ext_dm=None, cadence_mask=None, sigma=5, niters=5,
-                    to_host=False, cadenceno=None, cbv_time=None, gap_indicators=None, extrapolate=False, design_slab_mb=4096):
-        """``CBVCorrector(lc, cbvs).correct_gaussian_prior(cbv_indices, alpha, ext_dm, cadence_mask)`` (reference
-        cbvcorrector.py:333-395) for every target of the batch: columns [cbvs[:, idx - 1] | ext_dm | 1] shared by all targets
-        (``cbvs``: (N, n_vectors), column j = basis vector j + 1; indices 1-based, out-of-range ones dropped, "ALL" accepted),
-        prior_mu = 0 and ONE ridge width per target, median(flux_err_b) / sqrt(|alpha|), taken on the device; ``alpha == 0``:
-        no prior.  ``alpha`` may also be an array-like of B finite, non-zero penalties, one per target (8 bytes per target go
-        up; row b is what the scalar call at ``alpha[b]`` gives, bit for bit); a zero inside an array is a ``ValueError``:
-        "no prior" stays the scalar ``alpha == 0.0``.  Returns what ``regression_correct`` returns.  ``cadenceno``: the cadence
-        numbers of the rows of ``cbvs``; the batch may then be ragged and is matched by its own cadence numbers, exactly as
-        ``regression_correct(cadenceno=)`` (the ridge width is the median over the target's own matched cadences).
-
-        ``cbv_time``: the times of the rows of ``cbvs`` -> ``CBVCorrector(lc, interpolate_cbvs=True, extrapolate_cbvs=
-        extrapolate)``: the selected vectors are interpolated to every target's own times (``regression_correct(knot_time=)``;
-        ``gap_indicators``: bool (Nx,), True = a CBV cadence that is no knot, the reference's ``cbvs.gap_indicators``), the
-        constant column is written with them, and the batch needs neither one cadence count nor cadence numbers.  Not to be
-        combined with ``cadenceno``; ``ext_dm`` lives on the CBV cadences and is not interpolated: a ``ValueError``.  The
-        ridge width is the median over the target's own cadences that are fitted (inside the CBVs' span unless ``extrapolate``);
-        the dropped ones are counted in ``meta[b]["CADENCES_OUTSIDE_CBVS"]``."""
-        if cbv_time is not None:
-            if cadenceno is not None:
-                raise ValueError("cbv_correct: `cbv_time` interpolates the basis vectors to the targets' own times; it cannot be "
-                                 "combined with `cadenceno`")
-            if ext_dm is not None:
-                raise ValueError("cbv_correct(cbv_time=): `ext_dm` is not interpolated; put its columns on the targets' own "
-                                 "cadences and use regression_correct_batch, or fit it on the cadence grid (cadenceno=)")
-            if cbv_indices is None:
-                raise ValueError("nothing to fit: pass cbv_indices")
-            Ya = np.ascontiguousarray(_cbv_columns(cbvs, cbv_indices, None)[:, :-1])
-            alphas = None if np.ndim(alpha) == 0 else _alpha_per_target(alpha, len(self))
-            kk = None
-            if gap_indicators is not None:
-                gap = np.asarray(gap_indicators)
-                if gap.shape != (Ya.shape[0],) or (gap.dtype != np.bool_ and gap.dtype != np.uint8):
-                    raise ValueError("cbv_correct: gap_indicators must be a bool array of shape (%d,) (got %s of shape %s)"
-                                     % (Ya.shape[0], gap.dtype, gap.shape))
-                kk = gap == 0
-            src, d_cm, keep, knots = self._interp_front(Ya, cbv_time, kk, extrapolate, cadence_mask, "cbv_correct")
-            d_mu, d_sg = src._ridge_prior(None, Ya.shape[1] + 1, alpha, alphas, keep)
-            return src._regress_interp(knots, True, extrapolate, d_mu, d_sg, d_cm, sigma, niters, to_host, keep, design_slab_mb)
-        if gap_indicators is not None or extrapolate:
-            raise ValueError("cbv_correct: `gap_indicators` / `extrapolate` belong to the interpolated route: pass `cbv_time`")
-        Xa = _cbv_columns(cbvs, cbv_indices, ext_dm)
-        if cadenceno is not None:
-            alphas = None if np.ndim(alpha) == 0 else _alpha_per_target(alpha, len(self))
-            src, d_rows, d_cm, keep = self._aligned(Xa.shape[0], None, cadenceno, cadence_mask, "cbv_correct")
-            d_mu, d_sg = src._ridge_prior(None, Xa.shape[1], alpha, alphas, keep)
-            return src._regress_shared_rows(Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, to_host, keep)
-        N = self._uniform_n(Xa.shape[0], "cbv_correct")
-        alphas = None if np.ndim(alpha) == 0 else _alpha_per_target(alpha, len(self))
-        keep = []
-        d_mu, d_sg = self._ridge_prior(N, Xa.shape[1], alpha, alphas, keep)
-        return self._regress_shared(Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, keep)
-
-    def _ridge_prior(self, N, K, alpha, alphas, keep):
-        """(prior_mu, prior_sigma) on the device for one scalar ``alpha`` (0: (None, None), no prior) or, when ``alphas`` is
-        not None, for one checked penalty per target."""
-        if alphas is None and alpha == 0.0:
-            return None, None
-        if getattr(self, "d_flux_err", None) is None:
-            raise ValueError("cbv_correct with alpha != 0 needs flux errors (the ridge width is median(flux_err) / sqrt(|alpha|))")
-        h, B, st = self.handle, len(self), _vp(self.stream or None)
-        d_mu, d_sg = DeviceBuffer(h, B * K * 8), DeviceBuffer(h, B * K * 8)
-        lib = _capi._lib
-        if alphas is not None:
-            d_alpha, k = _upload(h, alphas, self.stream)
-            keep += [k, d_alpha]
-        if N is None:       # ragged: the median over each target's own cadences
-            if alphas is None:
-                _capi._check(lib.lk_ridge_prior_rows_batch_dev(h._h, B, _off_ptr(self.n_off), K, _vp(self.d_flux_err.ptr), float(alpha),
-                                                               _vp(d_mu.ptr), _vp(d_sg.ptr), st))
-            else:
-                _capi._check(lib.lk_ridge_prior_rows_alphas_batch_dev(h._h, B, _off_ptr(self.n_off), K, _vp(self.d_flux_err.ptr),
-                                                                      _vp(d_alpha.ptr), _vp(d_mu.ptr), _vp(d_sg.ptr), st))
-        elif alphas is None:
-            _capi._check(lib.lk_ridge_prior_batch_dev(h._h, B, N, K, _vp(self.d_flux_err.ptr), float(alpha), _vp(d_mu.ptr),
-                                                      _vp(d_sg.ptr), st))
-        else:
-            _capi._check(lib.lk_ridge_prior_alphas_batch_dev(h._h, B, N, K, _vp(self.d_flux_err.ptr), _vp(d_alpha.ptr),
-                                                             _vp(d_mu.ptr), _vp(d_sg.ptr), st))
-        return d_mu, d_sg
-
-    def _regress_shared(self, Xa, N, d_mu, d_sg, cadence_mask, sigma, niters, to_host, keep, resident=None):
-        """``resident``: (d_X, d_cm) already in HBM (a search that fits the same matrix many times uploads them once); then
-        ``cadence_mask`` is not looked at."""
-        h, B, K = self.handle, len(self), Xa.shape[1]
-        if resident is not None:
-            d_X, d_cm = resident
-        else:
-            d_cm = None
-            if cadence_mask is not None:
-                cm = np.ascontiguousarray(cadence_mask, dtype=np.uint8)
-                if cm.shape != (B, N):
-                    raise ValueError("cadence_mask must be (B, N) = %s (got %s)" % ((B, N), cm.shape))
-                d_cm, k = _upload(h, cm, self.stream, np.uint8)
-                keep.append(k)
-            d_X, k = _upload(h, Xa, self.stream)
-            keep.append(k)
-        d_w, d_model, d_corr, d_outl = DeviceBuffer(h, B * K * 8), DeviceBuffer(h, B * N * 8), DeviceBuffer(h, B * N * 8), DeviceBuffer(h, B * N)
-        _capi._check(_capi._lib.lk_regress_shared_batch_dev(
-            h._h, B, N, K, _vp(d_X.ptr), _vp(self.d_flux.ptr), _vp(self.d_flux_err.ptr if self.d_flux_err is not None else None),
-            _vp(d_cm.ptr if d_cm is not None else None), _vp(d_mu.ptr if d_mu is not None else None),
-            _vp(d_sg.ptr if d_sg is not None else None), float(sigma), int(niters), _vp(d_w.ptr), _vp(d_model.ptr), _vp(d_outl.ptr),
-            None, _vp(self.stream or None)))
-        _capi._check(_capi._lib.lk_subtract_f64_dev(h._h, B * N, _vp(self.d_flux.ptr), _vp(d_model.ptr), _vp(d_corr.ptr),
-                                                    _vp(self.stream or None)))
-        if to_host:
-            corrected = d_corr.download(np.float64, B * N, stream=self.stream).reshape(B, N)
-            outl = d_outl.download(np.uint8, B * N, stream=self.stream).reshape(B, N).astype(bool)
-            return corrected, outl, d_w.download(np.float64, B * K, stream=self.stream).reshape(B, K)
-        out = self._carry(self._new(self.d_time, d_corr, self.d_flux_err, self.n_off, nan_free=self.nan_free, is_sorted=self.is_sorted))
-        # scratch and inputs the stream may still be reading: held until the batch is synchronised or dropped
-        out._keep = keep + [d_X, d_cm, d_mu, d_sg, d_model, self]
-        return out, d_outl, d_w
-
-    # ---------------------------------------------------------------- under-fitting metric, neighbours by index
-    def under_fitting_metric(self, neighbors, cadence_mask=None, return_correlations=False, to_host=True, neighbor_batch=None,
-                             cadenceno=None, return_common=False):
-        """``underfit_metric_neighbors`` (reference correctors/metrics.py:141-257, 451-475) for every target of the batch, the
-        neighbours being OTHER TARGETS OF THIS BATCH (the reference fetches them from MAST; after ``cbv_correct`` they are the
-        corrected targets of the same field, already in HBM): ``neighbors`` int (B, M), row t = the indices of t's neighbours,
-        padded with -1 (``correctors.metrics.nearest_neighbors`` builds it from positions); ``cadence_mask`` bool (N,), shared
-        by every target, True = used (the reference's ``lc[cadence_mask]``).  Needs one cadence count for every target and a
-        NaN-free batch (``remove_nans()``).  Zero-centred flux is fine (the correlation does not depend on the scale of
-        flux / median - 1); a median of exactly zero gives a non-finite result, as in the reference.  Returns metric[B]
-        (``to_host=True``; 8 bytes per target cross PCIe) or its ``DeviceBuffer`` (``to_host=False``: nothing synchronised);
-        ``return_correlations``: also correlations[B, M] (NaN at padding), host array or ``DeviceBuffer`` likewise.
-        ``neighbor_batch``: a resident, NaN-free batch with the same cadence count whose ROWS are the neighbours instead
-        (``neighbors`` then holds indices into ``[0, len(neighbor_batch))``, and a target's own row number is a neighbour
-        like any other: it names a row of the other batch); its rows are prepared once and only the B targets after them.
-        With ``neighbor_batch`` = this batch the result is the same bits as without.
-
-        ``cadenceno``: the strictly increasing integer cadence numbers of the field's grid.  The batch may then be RAGGED
-        (``from_fits``, ``remove_nans``, ``remove_outliers``, ``select``) and is matched by its own ``d_cadenceno`` column, as in
-        ``regression_correct(cadenceno=)`` (a cadence that is not on the grid is dropped first); ``cadence_mask`` is then ragged:
-        bool (sum n,) over the cadences of this batch, or a ``DeviceBuffer`` of that many bytes.  As in the reference, target t
-        is compared with its neighbours on the cadences that t (under its mask) and ALL of them have; ``return_common`` adds
-        that count, n_common[B] int32, to the result (after the correlations, when both are asked for); fewer than two common
-        cadences give NaN, not an error.  A ``neighbor_batch`` is matched to the same grid by its own cadence numbers and its
-        rows are not masked (the common cadences are bounded by the target's mask anyway)."""
-        if cadenceno is not None:
-            return self._under_fitting_grid(neighbors, cadence_mask, return_correlations, to_host, neighbor_batch, cadenceno,
-                                            return_common)
-        if return_common:
-            raise ValueError("under_fitting_metric: return_common goes with cadenceno= (without it every target keeps the same "
-                             "cadences)")
-        N = self._uniform_n(None, "under_fitting_metric")
-        if not getattr(self, "nan_free", False):
-            raise ValueError("under_fitting_metric needs a NaN-free batch: call remove_nans() first (and cotrend after it)")
-        B = len(self)
-        Bn = None if neighbor_batch is None else _neighbor_batch_rows(neighbor_batch, N, "under_fitting_metric")
-        nb, keep_idx, n = _capi.underfit_arguments(B, N, neighbors, cadence_mask, Bn)
-        M = nb.shape[1]
-        h, st = self.handle, _vp(self.stream or None)
-        d_nb = d_keep = d_corr = None
-        if M:
-            d_nb, k = _upload(h, nb, self.stream, np.int32)
-            self._keep.append(k)
-        if keep_idx is not None:
-            d_keep, k = _upload(h, keep_idx, self.stream, np.int32)
-            self._keep.append(k)
-        if return_correlations:
-            d_corr = DeviceBuffer(h, max(B * M, 1) * 8)
-        if neighbor_batch is None:
-            d_metric = DeviceBuffer(h, B * 8)
-            _capi._check(_capi._lib.lk_underfit_neighbors_batch_dev(
-                h._h, B, N, _vp(self.d_flux.ptr), n, _vp(d_keep.ptr if d_keep is not None else None), M,
-                _vp(d_nb.ptr if d_nb is not None else None), _vp(d_corr.ptr if (d_corr is not None and M) else None),
-                _vp(d_metric.ptr), st))
-        else:
-            d_rows = neighbor_batch._underfit_rows(N, n, d_keep, self.stream)
-            d_metric = self._underfit_against(N, n, d_keep, Bn, d_rows, M, d_nb, d_corr)
-            # (the neighbours' flux buffer, not the batch: a batch that holds a batch can close a reference cycle — with itself as
-            # its own neighbour batch it would — and a cycle's buffers come back only when the cyclic collector runs)
-            self._keep += [d_rows, neighbor_batch.d_flux]
-        # inputs the stream may still be reading: held until the batch is synchronised or dropped
-        self._keep += [d_nb, d_keep]
-        if not to_host:
-            return (d_metric, d_corr) if return_correlations else d_metric
-        metric = d_metric.download(np.float64, B, stream=self.stream)
-        if return_correlations:
-            corr = d_corr.download(np.float64, B * M, stream=self.stream) if M else np.empty(0)
-            return metric, corr.reshape(B, M)
-        return metric
-
-    def _under_fitting_grid(self, neighbors, cadence_mask, return_correlations, to_host, neighbor_batch, cadenceno, return_common):
-        """``under_fitting_metric(cadenceno=)``: every check that needs no device, the alignment(s), then the grid kernels."""
-        what = "under_fitting_metric"
-        if not getattr(self, "nan_free", False):
-            raise ValueError("under_fitting_metric needs a NaN-free batch: call remove_nans() first (and cotrend after it)")
-        B, Nx = len(self), int(np.asarray(cadenceno).size)
-        if Nx > _capi.UNDERFIT_GRID_MAX_NX:
-            raise ValueError("under_fitting_metric: the grid has %d cadences, at most %d are taken" % (Nx, _capi.UNDERFIT_GRID_MAX_NX))
-        Bn = None
-        if neighbor_batch is not None:
-            if not isinstance(neighbor_batch, DeviceLightCurveBatch):
-                raise ValueError("%s: `neighbor_batch` must be a resident DeviceLightCurveBatch" % what)
-            if not getattr(neighbor_batch, "nan_free", False):
-                raise ValueError("%s needs a NaN-free neighbor_batch: call remove_nans() first (and cotrend after it)" % what)
-            if getattr(neighbor_batch, "d_cadenceno", None) is None:
-                raise ValueError("%s(cadenceno=) needs a neighbor_batch that carries cadence numbers" % what)
-            Bn = len(neighbor_batch)
-        nb = _capi.underfit_arguments(B, max(Nx, 2), neighbors, None, Bn)[0]
-        M = nb.shape[1]
-        src, d_rows, d_cm, keep = self._aligned(Nx, None, cadenceno, cadence_mask, what)
-        h, st = self.handle, _vp(self.stream or None)
-        d_nb = None
-        if M:
-            d_nb, k = _upload(h, nb, self.stream, np.int32)
-            keep.append(k)
-        d_corr = DeviceBuffer(h, max(B * M, 1) * 8) if return_correlations else None
-        d_nc = DeviceBuffer(h, B * 4) if return_common else None
-        d_metric = DeviceBuffer(h, B * 8)
-        p = lambda buf: _vp(buf.ptr if buf is not None else None)
-        if neighbor_batch is None:
-            _capi._check(_capi._lib.lk_underfit_grid_neighbors_batch_dev(
-                h._h, B, _off_ptr(src.n_off), _vp(d_rows.ptr), Nx, _vp(src.d_flux.ptr), p(d_cm), M, p(d_nb),
-                p(d_corr if M else None), p(d_nc), _vp(d_metric.ptr), st))
-        else:
-            d_block, nkeep = neighbor_batch._underfit_grid_rows(Nx, cadenceno, self.stream)
-            src._underfit_grid_against(Nx, d_rows, d_cm, Bn, d_block, M, d_nb, d_corr, d_nc, d_metric)
-            keep += nkeep + [d_block]
-        # inputs the stream may still be reading: held until the batch is synchronised or dropped (the flux buffer, not the
-        # aligned batch: see under_fitting_metric)
-        self._keep += keep + [d_rows, d_cm, d_nb, src.d_flux]
-        if not to_host:
-            out = (d_metric,) + ((d_corr,) if return_correlations else ()) + ((d_nc,) if return_common else ())
-        else:
-            out = (d_metric.download(np.float64, B, stream=self.stream),)
-            if return_correlations:
-                out += ((d_corr.download(np.float64, B * M, stream=self.stream) if M else np.empty(0)).reshape(B, M),)
-            if return_common:
-                out += (d_nc.download(np.int32, B, stream=self.stream),)
-        return out if len(out) > 1 else out[0]
-
-    def _underfit_grid_rows(self, Nx, cadenceno, stream):
-        """This batch's light curves, matched to the grid by their own cadence numbers and unmasked, prepared as the NEIGHBOURS
-        of ``lk_underfit_grid_against_rows_batch_dev`` -> (their ``DeviceBuffer``, buffers to keep until ``stream`` is done)."""
-        src, d_rows, _, keep = self._aligned(Nx, None, cadenceno, None, "under_fitting_metric (neighbor_batch)")
-        h = self.handle
-        nbytes = ctypes.c_int64(0)
-        _capi._check(_capi._lib.lk_underfit_grid_rows_bytes(len(src), Nx, ctypes.byref(nbytes)))
-        d_block = DeviceBuffer(h, nbytes.value)
-        _capi._check(_capi._lib.lk_underfit_grid_rows_prepare_dev(h._h, len(src), _off_ptr(src.n_off), _vp(d_rows.ptr), Nx,
-                                                                  _vp(src.d_flux.ptr), None, _vp(d_block.ptr), nbytes.value,
-                                                                  _vp(stream or None)))
-        return d_block, keep + [d_rows, src.d_flux]
-
-    def _underfit_grid_against(self, Nx, d_rows, d_cm, Bn, d_block, M, d_nb, d_corr, d_nc, d_metric, metric_offset=0):
-        """The grid pair pass of this (aligned) batch's targets against prepared neighbour rows, into ``d_metric``."""
-        p = lambda buf: _vp(buf.ptr if buf is not None else None)
-        _capi._check(_capi._lib.lk_underfit_grid_against_rows_batch_dev(
-            self.handle._h, len(self), _off_ptr(self.n_off), _vp(d_rows.ptr), Nx, _vp(self.d_flux.ptr), p(d_cm), Bn, _vp(d_block.ptr),
-            M, p(d_nb), p(d_corr if M else None), p(d_nc), _vp(d_metric.ptr + metric_offset), _vp(self.stream or None)))
-        return d_metric
-
-    def _underfit_rows(self, N, n, d_keep, stream):
-        """This batch's rows prepared as the NEIGHBOURS of ``lk_underfit_against_rows_batch_dev`` -> their ``DeviceBuffer``
-        (queued on ``stream``, the stream of the batch that will read them)."""
-        h, Bn = self.handle, len(self)
-        nbytes = ctypes.c_int64(0)
-        _capi._check(_capi._lib.lk_underfit_rows_bytes(Bn, n, ctypes.byref(nbytes)))
-        d_rows = DeviceBuffer(h, nbytes.value)
-        _capi._check(_capi._lib.lk_underfit_rows_prepare_dev(h._h, Bn, N, _vp(self.d_flux.ptr), n,
-                                                             _vp(d_keep.ptr if d_keep is not None else None), _vp(d_rows.ptr),
-                                                             nbytes.value, _vp(stream or None)))
-        return d_rows
-
-    def _underfit_against(self, N, n, d_keep, Bn, d_rows, M, d_nb, d_corr=None, d_metric=None, metric_offset=0):
-        """The pair pass of this batch's targets against prepared neighbour rows -> the metric's ``DeviceBuffer``."""
-        h, B = self.handle, len(self)
-        if d_metric is None:
-            d_metric = DeviceBuffer(h, B * 8)
-        _capi._check(_capi._lib.lk_underfit_against_rows_batch_dev(
-            h._h, B, N, _vp(self.d_flux.ptr), n, _vp(d_keep.ptr if d_keep is not None else None), Bn, _vp(d_rows.ptr), M,
-            _vp(d_nb.ptr if d_nb is not None else None), _vp(d_corr.ptr if (d_corr is not None and M) else None),
-            _vp(d_metric.ptr + metric_offset), _vp(self.stream or None)))
-        return d_metric
-
-    # ---------------------------------------------------------------- over-fitting metric, noise made on the device
-    def _overfit_checks(self, original, n_samples, cadence_mask, frequency, seed, first_target, stream_id):
-        """Every check of ``over_fitting_metric`` that needs no device -> (N, keep_idx, n, grid or None)."""
-        N = self._uniform_n(None, "over_fitting_metric")
-        if not isinstance(original, DeviceLightCurveBatch):
-            raise ValueError("over_fitting_metric: `original` must be the resident batch before the correction")
-        if len(original) != len(self) or original._uniform_n(None, "over_fitting_metric (original)") != N:
-            raise ValueError("over_fitting_metric: the original batch must have the targets and cadences of the corrected one "
-                             "(%d x %d)" % (len(self), N))
-        if not (self.nan_free and original.nan_free):
-            raise ValueError("over_fitting_metric needs NaN-free batches: call remove_nans() first (and cotrend after it)")
-        if getattr(self, "d_flux_err", None) is None:
-            raise ValueError("over_fitting_metric needs the flux errors of the corrected batch (the noise level is their mean)")
-        return (N,) + _capi.overfit_arguments(N, n_samples, cadence_mask, frequency, seed, first_target, stream_id, len(self))
-
-    def over_fitting_metric(self, original, frequency=None, n_samples=10, cadence_mask=None, seed=0, first_target=0, stream_id=0,
-                            to_host=True, max_scratch_bytes=None):
-        """``overfit_metric_lombscargle(original_lc[cadence_mask], corrected_lc[cadence_mask], n_samples)`` (reference
-        correctors/metrics.py:24-138, as ``CBVCorrector.over_fitting_metric`` calls it) for every target, called ON THE
-        CORRECTED batch; ``original``: the resident batch before the correction (same targets, same cadences).  Both stay in
-        HBM: the two periodograms per target, the ``n_samples`` white-noise periodograms and their reduction to one float run
-        on the device; 8 bytes per target come back.  ``frequency`` [1/d]: a regular grid shared by the targets; None = the
-        grid ``LombScarglePeriodogram.from_lightcurve`` builds (amplitude normalisation, oversample factor 5) for target 0's
-        kept cadences (its N times are downloaded once: the targets of a cotrending channel share their cadences; a batch whose
-        targets have different times passes ``frequency``).  ``cadence_mask``: bool (N,), True = used.  The noise is not
-        ``numpy.random``'s but a counter-based generator's (Philox4x32-10 keyed by ``seed``; counter = (cadence pair, sample,
-        ``first_target`` + row, ``stream_id``)): a target's value does not depend on the batch, on ``max_scratch_bytes`` (the
-        samples are taken in rounds that keep the scratch block under it; default 4 GiB) or on the run.  Returns metric[B]
-        (``to_host=True``) or its ``DeviceBuffer`` (``to_host=False``: nothing synchronised after the periodograms' own
-        planning).  Needs one cadence count per batch, NaN-free batches, flux errors on the corrected batch, ``n_samples`` >= 1,
-        a regular grid of at least two frequencies and at least three kept cadences: ``ValueError`` before any device call.
-
-        RAGGED batches (``from_fits``, ``remove_nans``, ``remove_outliers``, ``select``; what ``cbv_correct(cadenceno=)`` returns)
-        are taken on their own offsets when ``original.n_off`` equals this batch's (``ValueError`` otherwise); ``cadence_mask`` is
-        then ragged, bool (sum n,) over the cadences of the batch, or a ``DeviceBuffer`` of that many bytes (downloaded once, to
-        list the kept cadences; a ``DeviceBuffer`` is always read as this ragged mask, also on a uniform batch, and for one target the
-        two shapes are the same mask); every target needs at least three kept cadences.  A ragged mask also takes a uniform batch this
-        way, with the same bits.  ``frequency=None`` stays the grid of target 0's kept times.  Target b's value is the uniform
-        call's on a batch that holds its kept cadences alone, with ``first_target + b``."""
-        ragged_mask = isinstance(cadence_mask, DeviceBuffer) or (
-            cadence_mask is not None and len(self) > 1 and np.shape(cadence_mask) == (self.n_cadences,))
-        if isinstance(original, DeviceLightCurveBatch) and (self._is_ragged() or original._is_ragged() or ragged_mask):
-            keep_idx, k_off, grid = self._overfit_rows_checks(original, n_samples, cadence_mask, frequency, seed, first_target, stream_id)
-            return self._over_fitting_rows(original, grid, n_samples, keep_idx, k_off, None, seed, first_target, stream_id, to_host,
-                                           max_scratch_bytes)
-        N, keep_idx, n, grid = self._overfit_checks(original, n_samples, cadence_mask, frequency, seed, first_target, stream_id)
-        B, h, st = len(self), self.handle, _vp(self.stream or None)
-        if grid is None:
-            t0 = self.d_time.download(np.float64, N, stream=self.stream)
-            grid = _capi.overfit_grid(_capi.overfit_default_grid(t0 if keep_idx is None else t0[keep_idx]))
-        nbytes, _rounds = _capi.overfit_scratch_bytes(B, n, grid[2], n_samples, max_scratch_bytes)
-        d_keep = None
-        if keep_idx is not None:
-            d_keep, k = _upload(h, keep_idx, self.stream, np.int32)
-            self._keep.append(k)
-        # (the scratch block goes back to the free list when this call returns: work on one handle is stream-ordered)
-        d_scr, d_metric = DeviceBuffer(h, nbytes), DeviceBuffer(h, B * 8)
-        _capi._check(_capi._lib.lk_overfit_metric_batch_dev(
-            h._h, B, N, _vp(self.d_time.ptr), _vp(original.d_flux.ptr), _vp(self.d_flux.ptr), _vp(self.d_flux_err.ptr), n,
-            _vp(d_keep.ptr if d_keep is not None else None), grid[0], grid[1], grid[2], int(n_samples), int(seed), int(first_target),
-            int(stream_id), _vp(d_scr.ptr), nbytes, _vp(d_metric.ptr), st))
-        self._keep += [d_keep, original]
-        if not to_host:
-            return d_metric
-        return d_metric.download(np.float64, B, stream=self.stream)
-
-    def _is_ragged(self):
-        counts = np.diff(self.n_off)
-        return bool(len(counts)) and counts.min() != counts.max()
-
-    def _overfit_rows_checks(self, original, n_samples, cadence_mask, frequency, seed, first_target, stream_id):
-        """The checks of the ragged ``over_fitting_metric`` -> (keep_idx or None, k_off, grid or None).  Only a mask given as a
-        ``DeviceBuffer`` needs the device (one download), after every check that does not."""
-        if not isinstance(original, DeviceLightCurveBatch):
-            raise ValueError("over_fitting_metric: `original` must be the resident batch before the correction")
-        if len(self) < 1:
-            raise ValueError("over_fitting_metric needs at least one light curve")
-        if len(original) != len(self) or not np.array_equal(original.n_off, self.n_off):
-            rag, name = (self, "corrected") if self._is_ragged() else (original, "original")
-            counts = np.diff(rag.n_off)
-            raise ValueError("over_fitting_metric: the original batch must have the offsets (n_off) of the corrected one, target by "
-                             "target; the %s batch has between %d and %d cadences per target" % (name, counts.min(), counts.max()))
-        if not (self.nan_free and original.nan_free):
-            raise ValueError("over_fitting_metric needs NaN-free batches: call remove_nans() first (and cotrend after it)")
-        if getattr(self, "d_flux_err", None) is None:
-            raise ValueError("over_fitting_metric needs the flux errors of the corrected batch (the noise level is their mean)")
-        if isinstance(cadence_mask, DeviceBuffer):
-            if cadence_mask.nbytes != self.n_cadences:
-                raise ValueError("over_fitting_metric: cadence_mask holds %d bytes, the batch has %d cadences"
-                                 % (cadence_mask.nbytes, self.n_cadences))
-            _capi.overfit_rows_arguments(self.n_off, n_samples, None, frequency, seed, first_target, stream_id)
-            cadence_mask = cadence_mask.download(np.uint8, self.n_cadences, stream=self.stream)
-        return _capi.overfit_rows_arguments(self.n_off, n_samples, cadence_mask, frequency, seed, first_target, stream_id)
-
-    def _overfit_rows_default_grid(self, keep_idx, k_off):
-        """The default frequency grid of target 0's kept times (its times are downloaded once)."""
-        t0 = self.d_time.download(np.float64, int(self.n_off[1]), stream=self.stream)
-        return _capi.overfit_default_grid(t0 if keep_idx is None else t0[keep_idx[:int(k_off[1])]])
-
-    def _over_fitting_rows(self, original, grid, n_samples, keep_idx, k_off, d_keep, seed, first_target, stream_id, to_host,
-                           max_scratch_bytes):
-        """``lk_overfit_metric_rows_batch_dev`` on this (corrected) batch; ``d_keep``: keep_idx already in HBM."""
-        B, h, st = len(self), self.handle, _vp(self.stream or None)
-        if grid is None:
-            grid = _capi.overfit_grid(self._overfit_rows_default_grid(keep_idx, k_off))
-        nbytes, _rounds = _capi.overfit_scratch_rows_bytes(k_off, grid[2], n_samples, max_scratch_bytes)
-        if keep_idx is not None and d_keep is None:
-            d_keep, k = _upload(h, keep_idx, self.stream, np.int32)
-            self._keep.append(k)
-        d_scr, d_metric = DeviceBuffer(h, nbytes), DeviceBuffer(h, B * 8)
-        _capi._check(_capi._lib.lk_overfit_metric_rows_batch_dev(
-            h._h, B, _off_ptr(self.n_off), _vp(self.d_time.ptr), _vp(original.d_flux.ptr), _vp(self.d_flux.ptr), _vp(self.d_flux_err.ptr),
-            _vp(d_keep.ptr if d_keep is not None else None), _off_ptr(k_off) if keep_idx is not None else None, grid[0], grid[1],
-            grid[2], int(n_samples), int(seed), int(first_target), int(stream_id), _vp(d_scr.ptr), nbytes, _vp(d_metric.ptr), st))
-        self._keep += [d_keep, original.d_flux]
-        if not to_host:
-            return d_metric
-        return d_metric.download(np.float64, B, stream=self.stream)
-
-    def cbv_goodness_scan(self, cbvs, alphas, neighbors=None, cbv_indices=np.arange(1, 9), cadence_mask=None, n_samples=1, seed=0,
-                          frequency=None, first_target=0, ext_dm=None, sigma=5, niters=5, max_scratch_bytes=None, cadenceno=None):
-        """Both goodness metrics of ``cbv_correct`` over a list of ridge penalties, for the whole batch (what
-        ``correctors.CBVCorrector.goodness_scan`` does for one target, here for a whole channel): for each
-        ``alphas[a]`` the batch is corrected (``cbv_correct(cbvs, cbv_indices, alpha, ext_dm, cadence_mask, sigma, niters)``),
-        scored with ``over_fitting_metric(self, ..., stream_id=a)`` and, when ``neighbors`` (int (B, M), see
-        ``under_fitting_metric``) is given, with ``under_fitting_metric``.  ``cadence_mask``: bool (N,), shared by the fit and
-        both metrics.  A plain loop of resident calls; 8 or 16 bytes per target and penalty come back.  Returns
-        dict(alpha[A], over_fitting[A, B], under_fitting[A, B] or None).  ``cadenceno``: the cadence numbers of the rows of
-        ``cbvs``; the batch may then be ragged, ``cadence_mask`` is ragged (bool (sum n,) or a ``DeviceBuffer``), and the fit and
-        both metrics are ``cbv_correct(cadenceno=)``, the ragged ``over_fitting_metric`` and ``under_fitting_metric(cadenceno=)``:
-        the batch is aligned once and the matrix, the mask, the rows and the kept cadences are uploaded once; the result gains
-        n_common[A, B] (or None)."""
-        alphas = np.atleast_1d(np.asarray(alphas, dtype=np.float64))
-        B = len(self)
-        if cadenceno is not None:
-            return self._cbv_goodness_scan_rows(_cbv_columns(cbvs, cbv_indices, ext_dm), alphas, neighbors, cadenceno, cadence_mask,
-                                                n_samples, seed, frequency, first_target, sigma, niters, max_scratch_bytes)
-        N, keep_idx, _n, grid = self._overfit_checks(self, n_samples, cadence_mask, frequency, seed, first_target, 0)
-        if grid is None:      # the default grid depends on the times alone: taken once for the whole scan
-            t0 = self.d_time.download(np.float64, N, stream=self.stream)
-            frequency = _capi.overfit_default_grid(t0 if keep_idx is None else t0[keep_idx])
-        fit_mask = None if cadence_mask is None else np.broadcast_to(np.asarray(cadence_mask, dtype=bool), (B, N))
-        over = np.empty((len(alphas), B))
-        under = np.empty((len(alphas), B)) if neighbors is not None else None
-        for a, alpha in enumerate(alphas):
-            cor = self.cbv_correct(cbvs, cbv_indices=cbv_indices, alpha=float(alpha), ext_dm=ext_dm, cadence_mask=fit_mask, sigma=sigma,
-                                   niters=niters)[0]
-            d_over = cor.over_fitting_metric(self, frequency=frequency, n_samples=n_samples, cadence_mask=cadence_mask, seed=seed,
-                                             first_target=first_target, stream_id=a, to_host=False,
-                                             max_scratch_bytes=max_scratch_bytes)
-            d_under = cor.under_fitting_metric(neighbors, cadence_mask=cadence_mask, to_host=False) if neighbors is not None else None
-            over[a] = d_over.download(np.float64, B, stream=self.stream)
-            if d_under is not None:
-                under[a] = d_under.download(np.float64, B, stream=self.stream)
-            cor.synchronize()
-        return dict(alpha=alphas, over_fitting=over, under_fitting=under)
-
-    def cbv_correct_optimized(self, cbvs, neighbors=None, neighbor_batch=None, cbv_indices=np.arange(1, 9), ext_dm=None,
-                              cadence_mask=None, alpha_bounds=(1e-4, 1e4), target_over_score=0.5, target_under_score=0.5,
-                              max_iter=100, frequency=None, seed=0, first_target=0, stream_id=0, neighbor_alpha=1e-20, sigma=5,
-                              niters=5, max_scratch_bytes=None, return_trace=False, cadenceno=None):
-        """``CBVCorrector.correct`` (reference cbvcorrector.py:397-500) for every target of the batch: a bounded Brent search
-        of the ridge penalty alpha PER TARGET over ``-(leaky(over, target_over_score) + leaky(under, target_under_score))``
-        (``correctors.cbvcorrector.minimize_scalar_bounded`` is the search; every target visits the abscissae that function
-        would), one more fit at the optimum, then the over-fitting score with ``n_samples=10`` and the under-fitting score.
-        The B searches run in lockstep (``BoundedBrentBatch``): per step 8 bytes per target go up (its alpha) and 16 come back
-        (its two scores); a target whose search has ended is evaluated again at its optimum and the value ignored.  The
-        design matrix and the mask are uploaded once; what does not depend on alpha is taken once: the periodogram of the
-        uncorrected flux, the noise periodogram, the neighbours' normalised rows.  One evaluation is one regression, one
-        Lomb-Scargle pass of B rows and one pair pass.
-
-        NOISE: the reference draws fresh noise at every evaluation.  Here the search uses ``n_samples = 1`` and ONE fixed
-        stream ``(seed, first_target + b, stream_id)`` for all evaluations (common random numbers): the objective is a
-        deterministic function of alpha, and two runs give the same bits.  The final over-fitting score is
-        ``over_fitting_metric(n_samples=10)`` with the same seed and stream.
-
-        NEIGHBOURS: rows of the resident ``neighbor_batch`` named by ``neighbors`` (int (B, M), -1 = padding, indices into
-        ``[0, len(neighbor_batch))``); their flux is FIXED during the search (``CBVCorrector.set_neighbors``' semantics).
-        ``neighbor_batch=None``: this batch corrected at ``neighbor_alpha`` (1e-20: the plain least-squares fit).  A target's
-        result therefore depends on its own alpha alone and not on the other targets of the batch.
-
-        A score whose target is <= 0 is skipped (nothing is launched for it): it counts as 1.0 in the objective and is
-        reported as -1.0; ``target_under_score > 0`` needs ``neighbors``.  ``cadence_mask``: bool (N,), shared by the fit and
-        both metrics; ``frequency``: as in ``over_fitting_metric``.  Returns (corrected ``DeviceLightCurveBatch``, info):
-        info = dict(alpha[B], over_fitting_score[B], under_fitting_score[B], objective[B] (the search's best value), nfev[B],
-        status[B] (0, or 1 = ``max_iter`` reached)); ``return_trace`` adds trace = dict(alpha[I, B], over[I, B],
-        under[I, B]), the I lockstep evaluations (a skipped score is 1.0 there).  Every argument is checked before the first
-        device call.
-
-        ``cadenceno``: the cadence numbers of the rows of ``cbvs``.  The batch may then be RAGGED and is matched by its own cadence
-        numbers once (``cbv_correct(cadenceno=)``); ``cadence_mask`` is ragged (bool (sum n,) or a ``DeviceBuffer``); the fit, the
-        over-fitting session and the under-fitting pair pass run on the batch's own offsets and on the grid
-        (``under_fitting_metric(cadenceno=)``: a target meets its neighbours on the cadences it and all of them have); a
-        ``neighbor_batch`` is matched to the grid by its own cadence numbers.  The matrix, the mask, the rows and the kept cadences
-        are uploaded once; per step still 8 bytes per target go up and 16 come back.  info gains n_common[B] (-1 when the
-        under-fitting score is skipped).  A batch in which every target has every grid row gives, without a mask, the bits of the
-        call without ``cadenceno`` (under a mask the under-fitting sums run in grid order, not in kept order: equal within
-        rounding, the over-fitting scores still bit for bit)."""
-        from .correctors.cbvcorrector import BoundedBrentBatch
-        Xa = _cbv_columns(cbvs, cbv_indices, ext_dm)
-        if cadenceno is not None:
-            return self._cbv_correct_optimized_rows(Xa, neighbors, neighbor_batch, cadence_mask, alpha_bounds, target_over_score,
-                                                    target_under_score, max_iter, frequency, seed, first_target, stream_id,
-                                                    neighbor_alpha, sigma, niters, max_scratch_bytes, return_trace, cadenceno)
-        N = self._uniform_n(Xa.shape[0], "cbv_correct_optimized")
-        B, K = len(self), Xa.shape[1]
-        lo, hi = float(alpha_bounds[0]), float(alpha_bounds[1])
-        if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
-            raise ValueError("alpha_bounds must be two finite penalties, lower first (got %r)" % (tuple(alpha_bounds),))
-        if int(max_iter) < 1:
-            raise ValueError("max_iter must be >= 1 (got %r)" % (max_iter,))
-        t_over, t_under = float(target_over_score), float(target_under_score)
-        do_over, do_under = t_over > 0, t_under > 0
-        if do_under and neighbors is None:
-            raise ValueError("target_under_score > 0 needs `neighbors` (and `neighbor_batch`, or this batch's own targets corrected "
-                             "at neighbor_alpha): pass target_under_score=0 to search on the over-fitting metric alone")
-        if not np.isfinite(float(neighbor_alpha)):
-            raise ValueError("neighbor_alpha must be finite (got %r)" % (neighbor_alpha,))
-        if getattr(self, "d_flux_err", None) is None:
-            raise ValueError("cbv_correct_optimized needs flux errors (the ridge width is median(flux_err) / sqrt(|alpha|))")
-        _N, keep_idx, n, grid = self._overfit_checks(self, 10, cadence_mask, frequency, seed, first_target, stream_id)
-        nb = Bn = None
-        if do_under:
-            Bn = B if neighbor_batch is None else _neighbor_batch_rows(neighbor_batch, N, "cbv_correct_optimized")
-            nb = _capi.underfit_arguments(B, N, neighbors, cadence_mask, Bn)[0]
-        fit_mask = None if cadence_mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(cadence_mask, dtype=bool), (B, N)),
-                                                                          dtype=np.uint8)
-        # ---- resident once: X, the masks, the neighbour rows, the over-fitting session
-        h, st = self.handle, _vp(self.stream or None)
-        keep = []
-        d_X, k = _upload(h, Xa, self.stream)
-        keep.append(k)
-        d_cm = d_keep = d_nb = d_rows = d_sess = None
-        if fit_mask is not None:
-            d_cm, k = _upload(h, fit_mask, self.stream, np.uint8)
-            keep.append(k)
-        if keep_idx is not None:
-            d_keep, k = _upload(h, keep_idx, self.stream, np.int32)
-            keep.append(k)
-        p_keep = _vp(d_keep.ptr if d_keep is not None else None)
-
-        def fit(alphas):
-            held = []
-            d_mu, d_sg = self._ridge_prior(N, K, None, alphas, held)
-            out = self._regress_shared(Xa, N, d_mu, d_sg, None, sigma, niters, False, held, resident=(d_X, d_cm))[0]
-            return out
-
-        if do_over:
-            if grid is None:
-                t0 = self.d_time.download(np.float64, N, stream=self.stream)
-                frequency = _capi.overfit_default_grid(t0 if keep_idx is None else t0[keep_idx])
-                grid = _capi.overfit_grid(frequency)
-            sess_bytes, _r = ctypes.c_int64(0), ctypes.c_int(0)
-            _capi._check(_capi._lib.lk_overfit_session_bytes(B, n, grid[2], 1, int(max_scratch_bytes or 0), ctypes.byref(sess_bytes),
-                                                             ctypes.byref(_r)))
-            sess_bytes = sess_bytes.value
-            d_sess = DeviceBuffer(h, sess_bytes)
-            _capi._check(_capi._lib.lk_overfit_session_begin_dev(
-                h._h, B, N, _vp(self.d_time.ptr), _vp(self.d_flux.ptr), n, p_keep, grid[0], grid[1], grid[2], 1, int(seed),
-                int(first_target), int(stream_id), _vp(d_sess.ptr), sess_bytes, st))
-        if do_under:
-            if neighbor_batch is None:
-                neighbor_batch = self.cbv_correct(cbvs, cbv_indices=cbv_indices, alpha=neighbor_alpha, ext_dm=ext_dm,
-                                                  cadence_mask=fit_mask, sigma=sigma, niters=niters)[0]
-            M = nb.shape[1]
-            if M:
-                d_nb, k = _upload(h, nb, self.stream, np.int32)
-                keep.append(k)
-            d_rows = neighbor_batch._underfit_rows(N, n, d_keep, self.stream)
-        # ---- the lockstep search
-        brent = BoundedBrentBatch((lo, hi), B, maxiter=int(max_iter))
-        d_scores = DeviceBuffer(h, 2 * B * 8)
-        scores = np.ones((2, B))
-        trace = dict(alpha=[], over=[], under=[])
-        while not brent.done.all():
-            alphas = brent.x.copy()
-            cor = fit(alphas)
-            if do_over:
-                _capi._check(_capi._lib.lk_overfit_session_eval_dev(
-                    h._h, B, N, _vp(cor.d_flux.ptr), _vp(cor.d_flux_err.ptr), n, p_keep, grid[0], grid[1], grid[2], 1,
-                    _vp(d_sess.ptr), sess_bytes, _vp(d_scores.ptr), st))
-            if do_under:
-                cor._underfit_against(N, n, d_keep, Bn, d_rows, M, d_nb, d_metric=d_scores, metric_offset=B * 8)
-            if do_over and do_under:
-                d_scores.download(np.float64, 2 * B, out=scores.reshape(-1), stream=self.stream)
-            elif do_over or do_under:
-                d_scores.download(np.float64, B, out=scores[0 if do_over else 1], stream=self.stream,
-                                  offset_bytes=0 if do_over else B * 8)
-            cor.synchronize()
-            brent.tell(-(_leaky_scores(scores[0], t_over) + _leaky_scores(scores[1], t_under)))
-            if return_trace:
-                trace["alpha"].append(alphas), trace["over"].append(scores[0].copy()), trace["under"].append(scores[1].copy())
-        res = brent.result()
-        # ---- the fit at the optimum and its scores
-        out = fit(res["x"])
-        over, under = np.full(B, -1.0), np.full(B, -1.0)
-        if do_over:
-            over = out.over_fitting_metric(self, frequency=frequency, n_samples=10, cadence_mask=cadence_mask, seed=seed,
-                                           first_target=first_target, stream_id=stream_id, max_scratch_bytes=max_scratch_bytes)
-        if do_under:
-            under = out._underfit_against(N, n, d_keep, Bn, d_rows, M, d_nb).download(np.float64, B, stream=self.stream)
-        out._keep += keep + [d_keep, d_nb, d_rows, None if neighbor_batch is None else neighbor_batch.d_flux]
-        info = dict(alpha=res["x"], over_fitting_score=over, under_fitting_score=under, objective=res["fun"], nfev=res["nfev"],
-                    status=res["status"])
-        if return_trace:
-            info["trace"] = {k: np.array(v, dtype=np.float64).reshape(len(v), B) for k, v in trace.items()}
-        return out, info
-
-    # ---------------------------------------------------------------- the goodness metrics and the search, ragged
-    def _goodness_rows_setup(self, Nx, cadenceno, cadence_mask, n_samples, frequency, seed, first_target, stream_id, what):
-        """The front end the ragged scan and search share: the checks that need no device, ONE alignment, then the kept cadences
-        of the aligned batch -> (src, d_rows, d_cm, keep, keep_idx, k_off, d_keep, grid or None)."""
-        if not getattr(self, "nan_free", False):
-            raise ValueError("%s needs a NaN-free batch: call remove_nans() first" % what)
-        if getattr(self, "d_flux_err", None) is None:
-            raise ValueError("%s needs flux errors (the ridge width is median(flux_err) / sqrt(|alpha|))" % what)
-        if Nx > _capi.UNDERFIT_GRID_MAX_NX:
-            raise ValueError("%s: the grid has %d cadences, at most %d are taken" % (what, Nx, _capi.UNDERFIT_GRID_MAX_NX))
-        host_mask = None if isinstance(cadence_mask, DeviceBuffer) else cadence_mask
-        if host_mask is not None and np.shape(host_mask) != (self.n_cadences,):
-            raise ValueError("%s: with `cadenceno` cadence_mask is ragged, one entry per cadence of the batch: shape (%d,) (got %s)"
-                             % (what, self.n_cadences, np.shape(host_mask)))
-        _capi.overfit_rows_arguments(self.n_off, n_samples, host_mask, frequency, seed, first_target, stream_id)
-        src, d_rows, d_cm, keep = self._aligned(Nx, None, cadenceno, cadence_mask, what)
-        if d_cm is not None and (host_mask is None or src.n_cadences != self.n_cadences):
-            host_mask = d_cm.download(np.uint8, src.n_cadences, stream=self.stream)     # once: it lists the kept cadences
-        keep_idx, k_off, grid = _capi.overfit_rows_arguments(src.n_off, n_samples, host_mask, frequency, seed, first_target, stream_id)
-        d_keep = None
-        if keep_idx is not None:
-            d_keep, k = _upload(self.handle, keep_idx, self.stream, np.int32)
-            keep.append(k)
-        return src, d_rows, d_cm, keep, keep_idx, k_off, d_keep, grid
-
-    def _underfit_grid_direct(self, Nx, d_rows, d_cm, M, d_nb, d_nc, d_metric):
-        """``lk_underfit_grid_neighbors_batch_dev`` of this aligned batch against its own targets, into ``d_metric``."""
-        p = lambda buf: _vp(buf.ptr if buf is not None else None)
-        _capi._check(_capi._lib.lk_underfit_grid_neighbors_batch_dev(
-            self.handle._h, len(self), _off_ptr(self.n_off), _vp(d_rows.ptr), Nx, _vp(self.d_flux.ptr), p(d_cm), M, p(d_nb), None,
-            p(d_nc), _vp(d_metric.ptr), _vp(self.stream or None)))
-
-    def _cbv_goodness_scan_rows(self, Xa, alphas, neighbors, cadenceno, cadence_mask, n_samples, seed, frequency, first_target,
-                                sigma, niters, max_scratch_bytes):
-        what = "cbv_goodness_scan"
-        B, (Nx, K) = len(self), Xa.shape
-        nb = None if neighbors is None else _capi.underfit_arguments(B, max(Nx, 2), neighbors)[0]
-        src, d_rows, d_cm, keep, keep_idx, k_off, d_keep, grid = self._goodness_rows_setup(
-            Nx, cadenceno, cadence_mask, n_samples, frequency, seed, first_target, 0, what)
-        h = self.handle
-        if grid is None:      # the default grid depends on the times alone: taken once for the whole scan
-            grid = _capi.overfit_grid(src._overfit_rows_default_grid(keep_idx, k_off))
-        d_X, k = _upload(h, Xa, self.stream)
-        keep.append(k)
-        d_nb = None
-        if nb is not None and nb.shape[1]:
-            d_nb, k = _upload(h, nb, self.stream, np.int32)
-            keep.append(k)
-        over = np.empty((len(alphas), B))
-        under = np.empty((len(alphas), B)) if nb is not None else None
-        n_common = np.empty((len(alphas), B), dtype=np.int32) if nb is not None else None
-        d_under, d_nc = DeviceBuffer(h, B * 8), DeviceBuffer(h, B * 4)
-        for a, alpha in enumerate(alphas):
-            held = []
-            d_mu, d_sg = src._ridge_prior(None, K, float(alpha), None, held)
-            cor = src._regress_shared_rows(Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, False, held, resident=d_X)[0]
-            d_over = cor._over_fitting_rows(src, grid, n_samples, keep_idx, k_off, d_keep, seed, first_target, a, False,
-                                            max_scratch_bytes)
-            if nb is not None:
-                cor._underfit_grid_direct(Nx, d_rows, d_cm, nb.shape[1], d_nb, d_nc, d_under)
-            over[a] = d_over.download(np.float64, B, stream=self.stream)
-            if nb is not None:
-                under[a] = d_under.download(np.float64, B, stream=self.stream)
-                n_common[a] = d_nc.download(np.int32, B, stream=self.stream)
-            cor.synchronize()
-        self.synchronize()
-        return dict(alpha=alphas, over_fitting=over, under_fitting=under, n_common=n_common)
-
-    def _cbv_correct_optimized_rows(self, Xa, neighbors, neighbor_batch, cadence_mask, alpha_bounds, target_over_score,
-                                    target_under_score, max_iter, frequency, seed, first_target, stream_id, neighbor_alpha, sigma,
-                                    niters, max_scratch_bytes, return_trace, cadenceno):
-        """``cbv_correct_optimized(cadenceno=)``: the uniform method's steps on the batch's own offsets and on the grid."""
-        from .correctors.cbvcorrector import BoundedBrentBatch
-        what = "cbv_correct_optimized"
-        B, (Nx, K) = len(self), Xa.shape
-        lo, hi = float(alpha_bounds[0]), float(alpha_bounds[1])
-        if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
-            raise ValueError("alpha_bounds must be two finite penalties, lower first (got %r)" % (tuple(alpha_bounds),))
-        if int(max_iter) < 1:
-            raise ValueError("max_iter must be >= 1 (got %r)" % (max_iter,))
-        t_over, t_under = float(target_over_score), float(target_under_score)
-        do_over, do_under = t_over > 0, t_under > 0
-        if do_under and neighbors is None:
-            raise ValueError("target_under_score > 0 needs `neighbors` (and `neighbor_batch`, or this batch's own targets corrected "
-                             "at neighbor_alpha): pass target_under_score=0 to search on the over-fitting metric alone")
-        if not np.isfinite(float(neighbor_alpha)):
-            raise ValueError("neighbor_alpha must be finite (got %r)" % (neighbor_alpha,))
-        nb = Bn = None
-        if do_under:
-            Bn = B
-            if neighbor_batch is not None:
-                if not isinstance(neighbor_batch, DeviceLightCurveBatch):
-                    raise ValueError("%s: `neighbor_batch` must be a resident DeviceLightCurveBatch" % what)
-                if not getattr(neighbor_batch, "nan_free", False):
-                    raise ValueError("%s needs a NaN-free neighbor_batch: call remove_nans() first (and cotrend after it)" % what)
-                if getattr(neighbor_batch, "d_cadenceno", None) is None:
-                    raise ValueError("%s(cadenceno=) needs a neighbor_batch that carries cadence numbers" % what)
-                Bn = len(neighbor_batch)
-            nb = _capi.underfit_arguments(B, max(Nx, 2), neighbors, None, Bn)[0]
-        src, d_rows, d_cm, keep, keep_idx, k_off, d_keep, grid = self._goodness_rows_setup(
-            Nx, cadenceno, cadence_mask, 10, frequency, seed, first_target, stream_id, what)
-        # ---- resident once: X, the neighbour rows, the over-fitting session (the mask, the rows and keep_idx already are)
-        h, st = self.handle, _vp(self.stream or None)
-        d_X, k = _upload(h, Xa, self.stream)
-        keep.append(k)
-        d_nb = d_block = d_sess = None
-        p_keep = _vp(d_keep.ptr if d_keep is not None else None)
-        p_koff = _off_ptr(k_off) if keep_idx is not None else None
-
-        def fit(alphas, alpha=None):
-            held = []
-            d_mu, d_sg = src._ridge_prior(None, K, alpha, alphas, held)
-            return src._regress_shared_rows(Xa, d_rows, d_mu, d_sg, d_cm, sigma, niters, False, held, resident=d_X)[0]
-
-        if do_over:
-            if grid is None:
-                grid = _capi.overfit_grid(src._overfit_rows_default_grid(keep_idx, k_off))
-            sess_bytes, _r = ctypes.c_int64(0), ctypes.c_int(0)
-            _capi._check(_capi._lib.lk_overfit_session_rows_bytes(B, _off_ptr(k_off), grid[2], 1, int(max_scratch_bytes or 0),
-                                                                  ctypes.byref(sess_bytes), ctypes.byref(_r)))
-            sess_bytes = sess_bytes.value
-            d_sess = DeviceBuffer(h, sess_bytes)
-            _capi._check(_capi._lib.lk_overfit_session_begin_rows_dev(
-                h._h, B, _off_ptr(src.n_off), _vp(src.d_time.ptr), _vp(src.d_flux.ptr), p_keep, p_koff, grid[0], grid[1], grid[2], 1,
-                int(seed), int(first_target), int(stream_id), _vp(d_sess.ptr), sess_bytes, st))
-        M = 0
-        if do_under:
-            M = nb.shape[1]
-            if M:
-                d_nb, k = _upload(h, nb, self.stream, np.int32)
-                keep.append(k)
-            if neighbor_batch is None:
-                # this batch's own targets at neighbor_alpha: the same cadences, so the same rows and the same mask
-                nbr = fit(None, float(neighbor_alpha))
-                d_block = nbr._underfit_grid_block(Nx, d_rows, d_cm, self.stream)
-                keep += [nbr.d_flux]
-            else:
-                d_block, nkeep = neighbor_batch._underfit_grid_rows(Nx, cadenceno, self.stream)
-                keep += nkeep
-        # ---- the lockstep search
-        brent = BoundedBrentBatch((lo, hi), B, maxiter=int(max_iter))
-        d_scores = DeviceBuffer(h, 2 * B * 8)
-        d_nc = DeviceBuffer(h, B * 4)
-        scores = np.ones((2, B))
-        trace = dict(alpha=[], over=[], under=[])
-
-        def under_eval(cor, d_metric, offset):
-            cor._underfit_grid_against(Nx, d_rows, d_cm, Bn, d_block, M, d_nb, None, d_nc, d_metric, metric_offset=offset)
-
-        while not brent.done.all():
-            alphas = brent.x.copy()
-            cor = fit(alphas)
-            if do_over:
-                _capi._check(_capi._lib.lk_overfit_session_eval_rows_dev(
-                    h._h, B, _off_ptr(src.n_off), _vp(cor.d_flux.ptr), _vp(cor.d_flux_err.ptr), p_keep, p_koff, grid[0], grid[1],
-                    grid[2], 1, _vp(d_sess.ptr), sess_bytes, _vp(d_scores.ptr), st))
-            if do_under:
-                under_eval(cor, d_scores, B * 8)
-            if do_over and do_under:
-                d_scores.download(np.float64, 2 * B, out=scores.reshape(-1), stream=self.stream)
-            elif do_over or do_under:
-                d_scores.download(np.float64, B, out=scores[0 if do_over else 1], stream=self.stream,
-                                  offset_bytes=0 if do_over else B * 8)
-            cor.synchronize()
-            brent.tell(-(_leaky_scores(scores[0], t_over) + _leaky_scores(scores[1], t_under)))
-            if return_trace:
-                trace["alpha"].append(alphas), trace["over"].append(scores[0].copy()), trace["under"].append(scores[1].copy())
-        res = brent.result()
-        # ---- the fit at the optimum and its scores
-        out = fit(res["x"])
-        over, under, n_common = np.full(B, -1.0), np.full(B, -1.0), np.full(B, -1, dtype=np.int32)
-        if do_over:
-            over = out._over_fitting_rows(src, grid, 10, keep_idx, k_off, d_keep, seed, first_target, stream_id, True, max_scratch_bytes)
-        if do_under:
-            d_under = DeviceBuffer(h, B * 8)
-            under_eval(out, d_under, 0)
-            under = d_under.download(np.float64, B, stream=self.stream)
-            n_common = d_nc.download(np.int32, B, stream=self.stream)
-        out._keep += keep + [d_X, d_rows, d_cm, d_keep, d_nb, d_block, d_sess, src.d_flux, src.d_time]
-        info = dict(alpha=res["x"], over_fitting_score=over, under_fitting_score=under, objective=res["fun"], nfev=res["nfev"],
-                    status=res["status"], n_common=n_common)
-        if return_trace:
-            info["trace"] = {k: np.array(v, dtype=np.float64).reshape(len(v), B) for k, v in trace.items()}
-        return out, info
-
-    def _underfit_grid_block(self, Nx, d_rows, d_cm, stream):
-        """This ALIGNED batch's light curves (rows ``d_rows``, mask ``d_cm``) prepared as grid neighbour rows -> their
-        ``DeviceBuffer`` (queued on ``stream``)."""
-        h = self.handle
-        nbytes = ctypes.c_int64(0)
-        _capi._check(_capi._lib.lk_underfit_grid_rows_bytes(len(self), Nx, ctypes.byref(nbytes)))
-        d_block = DeviceBuffer(h, nbytes.value)
-        _capi._check(_capi._lib.lk_underfit_grid_rows_prepare_dev(h._h, len(self), _off_ptr(self.n_off), _vp(d_rows.ptr), Nx,
-                                                                  _vp(self.d_flux.ptr), _vp(d_cm.ptr if d_cm is not None else None),
-                                                                  _vp(d_block.ptr), nbytes.value, _vp(stream or None)))
-        return d_block
 
     # ---------------------------------------------------------------- SFF
     def _centroid_buffer(self, c, what):
@@ -3096,83 +1919,6 @@ class DevicePixelCubeBatch(object):
         # scratch and inputs the stream may still be reading: held until the batch is synchronised or dropped
         out._keep = keep + [d_X, d_ps, d_mu, d_w, d_model, d_sp, d_pld, d_bkg, g, d_f, d_e, d_k, pld_idx, bkg_idx, d_pc, d_bc, self]
         return out, d_outl
-
-
-def _design_arrays(X, prior_mu, prior_sigma):
-    """(X float64 (N, K), prior_mu, prior_sigma) of a shared design matrix: a host array, a ``DesignMatrix`` or a
-    ``DesignMatrixCollection`` (whose own priors stand in when none are given)."""
-    if hasattr(X, "prior_sigma") and hasattr(X, "X"):
-        if prior_mu is None and prior_sigma is None:
-            prior_mu, prior_sigma = np.asarray(X.prior_mu, dtype=np.float64), np.asarray(X.prior_sigma, dtype=np.float64)
-        X = X.X
-    Xa = np.ascontiguousarray(X, dtype=np.float64)
-    if Xa.ndim != 2 or Xa.shape[1] < 1:
-        raise ValueError("the design matrix must be 2-D (cadences x regressors), got shape %s" % (Xa.shape,))
-    if (prior_mu is None) != (prior_sigma is None):
-        raise ValueError("Please specify both `prior_mu` and `prior_sigma`")
-    if prior_mu is not None:
-        prior_mu, prior_sigma = np.asarray(prior_mu, dtype=np.float64), np.asarray(prior_sigma, dtype=np.float64)
-    return Xa, prior_mu, prior_sigma
-
-
-def _cadenceno_array(a, n, name):
-    """Integer cadence numbers / row indices -> int32 (n,), C-contiguous; ``ValueError`` for another shape, kind or range."""
-    a = np.asarray(a)
-    if a.shape != (n,) or not np.issubdtype(a.dtype, np.integer):
-        raise ValueError("%s must be an integer array of shape (%d,) (got %s of shape %s)" % (name, n, a.dtype, a.shape))
-    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-        raise ValueError("%s must fit int32" % name)
-    return np.ascontiguousarray(a, dtype=np.int32)
-
-
-def _alpha_per_target(alpha, B):
-    """One ridge penalty per target -> float64[B]; ``ValueError`` unless B finite, non-zero values."""
-    a = np.ascontiguousarray(alpha, dtype=np.float64)
-    if a.shape != (B,):
-        raise ValueError("alpha must be a scalar or one penalty per target, shape (%d,) (got shape %s)" % (B, a.shape))
-    if not np.all(np.isfinite(a)) or np.any(a == 0.0):
-        raise ValueError("every alpha of an array must be finite and non-zero (no prior is the scalar alpha == 0.0)")
-    return a
-
-
-def _leaky_scores(metric, target, leak=0.01):
-    """``correctors.cbvcorrector._leaky`` on an array of scores: above the target a score counts with 1 % of its excess."""
-    if target > 0:
-        return np.where(metric >= target, target + leak * (metric - target), metric)
-    return metric
-
-
-def _neighbor_batch_rows(neighbor_batch, N, what):
-    """The checks of a ``neighbor_batch`` that need no device -> its number of rows."""
-    if not isinstance(neighbor_batch, DeviceLightCurveBatch):
-        raise ValueError("%s: `neighbor_batch` must be a resident DeviceLightCurveBatch" % what)
-    Nn = neighbor_batch._uniform_n(None, "%s (neighbor_batch)" % what)
-    if Nn != N:
-        raise ValueError("%s: neighbor_batch has %d cadences per target, this batch has %d" % (what, Nn, N))
-    if not getattr(neighbor_batch, "nan_free", False):
-        raise ValueError("%s needs a NaN-free neighbor_batch: call remove_nans() first (and cotrend after it)" % what)
-    return len(neighbor_batch)
-
-
-def _cbv_columns(cbvs, cbv_indices, ext_dm):
-    """The columns ``CBVCorrector._collection`` builds — [cbvs[:, idx - 1] | ext_dm | 1] — as one float64 (N, K) array."""
-    from .correctors.cbvcorrector import cbv_index_list
-    cbvs = np.asarray(cbvs, dtype=np.float64)
-    if cbvs.ndim != 2:
-        raise ValueError("cbvs must be 2-D (cadences x vectors)")
-    mats = []
-    if cbv_indices is not None:
-        mats.append(cbvs[:, cbv_index_list(cbv_indices, cbvs.shape[1]) - 1])
-    if ext_dm is not None:
-        if not (hasattr(ext_dm, "X") and hasattr(ext_dm, "prior_sigma")):
-            raise ValueError("ext_dm must be a DesignMatrix")
-        if ext_dm.shape[0] != cbvs.shape[0]:
-            raise ValueError("ext_dm must contain the same number of cadences as the basis vectors")
-        mats.append(np.asarray(ext_dm.X, dtype=np.float64))
-    if not mats:
-        raise ValueError("nothing to fit: pass cbv_indices and/or ext_dm")
-    mats.append(np.ones((cbvs.shape[0], 1)))
-    return np.ascontiguousarray(np.hstack(mats))
 
 
 def _cube_times_sorted(time):
