@@ -973,8 +973,9 @@ int lk_overfit_metric_batch_dev(lk_handle *h, int B, int N, const double *time, 
                                 int64_t scratch_bytes, double *metric, void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    return lk::overfit_metric_launch(h, B, N, time, flux_orig, flux_corr, err_corr, n, keep_idx, f0, df, M, n_samples, seed,
-                                     first_target, stream_id, scratch, scratch_bytes, metric, static_cast<hipStream_t>(stream));
+    return lk::overfit_metric_launch(h, lk::OverfitBatch::uniform(B, N, n, keep_idx), time, flux_orig, flux_corr, err_corr, f0, df, M,
+                                     n_samples, seed, first_target, stream_id, scratch, scratch_bytes, metric,
+                                     static_cast<hipStream_t>(stream));
 }
 
 int lk_overfit_session_bytes(int B, int n, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes,
@@ -987,8 +988,8 @@ int lk_overfit_session_begin_dev(lk_handle *h, int B, int N, const double *time,
                                  int64_t first_target, int64_t stream_id, void *session, int64_t session_bytes, void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    return lk::overfit_session_begin_launch(h, B, N, time, flux_orig, n, keep_idx, f0, df, M, n_samples, seed, first_target,
-                                            stream_id, session, session_bytes, static_cast<hipStream_t>(stream));
+    return lk::overfit_session_begin_launch(h, lk::OverfitBatch::uniform(B, N, n, keep_idx), time, flux_orig, f0, df, M, n_samples, seed,
+                                            first_target, stream_id, session, session_bytes, static_cast<hipStream_t>(stream));
 }
 
 int lk_overfit_session_eval_dev(lk_handle *h, int B, int N, const double *flux_corr, const double *err_corr, int n,
@@ -996,8 +997,8 @@ int lk_overfit_session_eval_dev(lk_handle *h, int B, int N, const double *flux_c
                                 int64_t session_bytes, double *metric, void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    return lk::overfit_session_eval_launch(h, B, N, flux_corr, err_corr, n, keep_idx, f0, df, M, n_samples, session, session_bytes,
-                                           metric, static_cast<hipStream_t>(stream));
+    return lk::overfit_session_eval_launch(h, lk::OverfitBatch::uniform(B, N, n, keep_idx), flux_corr, err_corr, f0, df, M, n_samples,
+                                           session, session_bytes, metric, static_cast<hipStream_t>(stream));
 }
 
 int lk_overfit_metric_batch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, const double *flux_corr,
@@ -1024,8 +1025,8 @@ int lk_overfit_metric_batch(lk_handle *h, int B, int N, const double *time, cons
     rc = io.in(dt, time, bn).in(dy0, flux_orig, bn).in(dy1, flux_corr, bn).in(de1, err_corr, bn).in(dkeep, keep_idx, (size_t)n)
              .out(dmetric, metric, (size_t)B).scratch(dscr, (size_t)bytes).stage();
     if (rc) return rc;
-    rc = lk::overfit_metric_launch(h, B, N, dt, dy0, dy1, de1, n, dkeep, f0, df, M, n_samples, seed, first_target, stream_id, dscr,
-                                   bytes, dmetric, nullptr);
+    rc = lk::overfit_metric_launch(h, lk::OverfitBatch::uniform(B, N, n, dkeep), dt, dy0, dy1, de1, f0, df, M, n_samples, seed, first_target,
+                                   stream_id, dscr, bytes, dmetric, nullptr);
     return rc ? rc : io.finish();
 }
 
@@ -1047,9 +1048,9 @@ int lk_overfit_metric_rows_batch_dev(lk_handle *h, int B, const int64_t *n_off_h
                                      void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    return lk::overfit_metric_rows_launch(h, B, n_off_host, time, flux_orig, flux_corr, err_corr, keep_idx, k_off_host, f0, df, M,
-                                          n_samples, seed, first_target, stream_id, scratch, scratch_bytes, metric,
-                                          static_cast<hipStream_t>(stream));
+    return lk::overfit_metric_launch(h, lk::OverfitBatch::rows(B, n_off_host, keep_idx, k_off_host), time, flux_orig, flux_corr, err_corr, f0,
+                                     df, M, n_samples, seed, first_target, stream_id, scratch, scratch_bytes, metric,
+                                     static_cast<hipStream_t>(stream));
 }
 
 int lk_overfit_session_begin_rows_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
@@ -1058,8 +1059,9 @@ int lk_overfit_session_begin_rows_dev(lk_handle *h, int B, const int64_t *n_off_
                                       int64_t session_bytes, void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    return lk::overfit_session_begin_rows_launch(h, B, n_off_host, time, flux_orig, keep_idx, k_off_host, f0, df, M, n_samples, seed,
-                                                 first_target, stream_id, session, session_bytes, static_cast<hipStream_t>(stream));
+    return lk::overfit_session_begin_launch(h, lk::OverfitBatch::rows(B, n_off_host, keep_idx, k_off_host), time, flux_orig, f0, df, M,
+                                            n_samples, seed, first_target, stream_id, session, session_bytes,
+                                            static_cast<hipStream_t>(stream));
 }
 
 int lk_overfit_session_eval_rows_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *flux_corr, const double *err_corr,
@@ -1067,8 +1069,8 @@ int lk_overfit_session_eval_rows_dev(lk_handle *h, int B, const int64_t *n_off_h
                                      int n_samples, void *session, int64_t session_bytes, double *metric, void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    return lk::overfit_session_eval_rows_launch(h, B, n_off_host, flux_corr, err_corr, keep_idx, k_off_host, f0, df, M, n_samples,
-                                                session, session_bytes, metric, static_cast<hipStream_t>(stream));
+    return lk::overfit_session_eval_launch(h, lk::OverfitBatch::rows(B, n_off_host, keep_idx, k_off_host), flux_corr, err_corr, f0, df, M,
+                                           n_samples, session, session_bytes, metric, static_cast<hipStream_t>(stream));
 }
 
 int lk_overfit_metric_rows_batch(lk_handle *h, int B, const int64_t *n_off, const double *time, const double *flux_orig,
@@ -1101,8 +1103,8 @@ int lk_overfit_metric_rows_batch(lk_handle *h, int B, const int64_t *n_off, cons
     rc = io.in(dt, time, ntot).in(dy0, flux_orig, ntot).in(dy1, flux_corr, ntot).in(de1, err_corr, ntot)
              .in(dkeep, keep_idx, (size_t)ko[B]).out(dmetric, metric, (size_t)B).scratch(dscr, (size_t)bytes).stage();
     if (rc) return rc;
-    rc = lk::overfit_metric_rows_launch(h, B, n_off, dt, dy0, dy1, de1, dkeep, keep_idx ? ko : nullptr, f0, df, M, n_samples, seed,
-                                        first_target, stream_id, dscr, bytes, dmetric, nullptr);
+    rc = lk::overfit_metric_launch(h, lk::OverfitBatch::rows(B, n_off, dkeep, keep_idx ? ko : nullptr), dt, dy0, dy1, de1, f0, df, M,
+                                   n_samples, seed, first_target, stream_id, dscr, bytes, dmetric, nullptr);
     return rc ? rc : io.finish();
 }
 

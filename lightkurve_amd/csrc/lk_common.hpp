@@ -227,31 +227,30 @@ int underfit_grid_against_rows_launch(lk_handle *h, int B, const int64_t *n_off_
 int overfit_scratch_bytes(int B, int n, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes, int *samples_per_round);
 int overfit_noise_launch(lk_handle *h, int B, int n, int k, uint64_t seed, int64_t first_target, int64_t stream_id, double *out,
                          hipStream_t stream);
-int overfit_metric_launch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, const double *flux_corr,
-                          const double *err_corr, int n, const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples,
-                          uint64_t seed, int64_t first_target, int64_t stream_id, void *scratch, int64_t scratch_bytes,
-                          double *metric, hipStream_t stream);
-int overfit_session_begin_launch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, int n,
-                                 const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, uint64_t seed,
-                                 int64_t first_target, int64_t stream_id, void *session, int64_t session_bytes, hipStream_t stream);
-int overfit_session_eval_launch(lk_handle *h, int B, int N, const double *flux_corr, const double *err_corr, int n,
-                                const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, void *session,
-                                int64_t session_bytes, double *metric, hipStream_t stream);
-// overfit.hip on the batch's own offsets: (N, n, keep_idx) become n_off_host (B + 1), keep_idx (target-relative, packed by k_off_host;
-// NULL: all cadences) and k_off_host (B + 1 offsets of the kept cadences; NULL with keep_idx == NULL)
+// overfit.hip's batch, two layouts.  uniform: every target has N cadences and keeps the n that ONE keep_idx names (NULL: all, n == N).
+// rows: the batch's own offsets, n_off_host (B + 1), keep_idx (target-relative, packed by k_off_host; NULL: all cadences) and
+// k_off_host (B + 1 offsets of the kept cadences; NULL with keep_idx == NULL).  The launchers check it.
+struct OverfitBatch {
+    bool ragged;
+    int B, N, n;
+    const int64_t *n_off_host, *k_off_host;
+    const int32_t *keep_idx;
+    static OverfitBatch uniform(int B, int N, int n, const int32_t *keep_idx) { return {false, B, N, n, nullptr, nullptr, keep_idx}; }
+    static OverfitBatch rows(int B, const int64_t *n_off_host, const int32_t *keep_idx, const int64_t *k_off_host) {
+        return {true, B, 0, 0, n_off_host, k_off_host, keep_idx};
+    }
+    size_t cad() const { return ragged ? (size_t)k_off_host[B] : (size_t)B * n; }   // the kept cadences of all targets (once checked)
+};
+int overfit_metric_launch(lk_handle *h, OverfitBatch bt, const double *time, const double *flux_orig, const double *flux_corr,
+                          const double *err_corr, double f0, double df, int64_t M, int n_samples, uint64_t seed, int64_t first_target,
+                          int64_t stream_id, void *scratch, int64_t scratch_bytes, double *metric, hipStream_t stream);
+int overfit_session_begin_launch(lk_handle *h, OverfitBatch bt, const double *time, const double *flux_orig, double f0, double df,
+                                 int64_t M, int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id, void *session,
+                                 int64_t session_bytes, hipStream_t stream);
+int overfit_session_eval_launch(lk_handle *h, OverfitBatch bt, const double *flux_corr, const double *err_corr, double f0, double df,
+                                int64_t M, int n_samples, void *session, int64_t session_bytes, double *metric, hipStream_t stream);
 int overfit_scratch_rows_bytes(int B, const int64_t *k_off_host, int64_t M, int n_samples, int64_t max_scratch_bytes, int64_t *bytes,
                                int *samples_per_round);
-int overfit_metric_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
-                               const double *flux_corr, const double *err_corr, const int32_t *keep_idx, const int64_t *k_off_host,
-                               double f0, double df, int64_t M, int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id,
-                               void *scratch, int64_t scratch_bytes, double *metric, hipStream_t stream);
-int overfit_session_begin_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
-                                      const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
-                                      int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id, void *session,
-                                      int64_t session_bytes, hipStream_t stream);
-int overfit_session_eval_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *flux_corr, const double *err_corr,
-                                     const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
-                                     int n_samples, void *session, int64_t session_bytes, double *metric, hipStream_t stream);
 int model_part_launch(lk_handle *h, int B, int N, int K, int c0, int c1, const double *X, const double *w, double *out,
                       hipStream_t stream);
 int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,

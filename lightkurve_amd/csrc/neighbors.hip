@@ -212,22 +212,34 @@ static double uf_scale(int n) {
     return std::log(2.0 / 0.95 - 1.0) / wgn;
 }
 
-// Workspace: B x pitch doubles of z rows (pitch = n rounded up to 128) + B self-products.
-int underfit_neighbors_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
-                              const int32_t *neighbors, double *corr, double *metric, hipStream_t stream) {
+// The B target rows are prepared in the handle's arena (workspace: B x pitch doubles of z rows, pitch = n rounded up to 128, + B
+// self-products).  against == false: the neighbours are the batch itself.  against: they are read from `rows` (Bn of them, as
+// underfit_rows_prepare_launch leaves them for the same n and keep_idx); then an index equal to the target's own row number names a
+// row of the OTHER array: a neighbour.
+static int underfit_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, bool against, int Bn,
+                           const void *rows, int M, const int32_t *neighbors, double *corr, double *metric, hipStream_t stream) {
     if (const int rc = underfit_shape_ok(B, N, n, keep_idx)) return rc;
+    if (against) LK_REQUIRE(Bn >= 1, "Bn must be >= 1 (got %d)", Bn);
     LK_REQUIRE(M >= 0, "M must be >= 0 (got %d)", M);
     LK_REQUIRE(flux && metric, "NULL buffer");
     LK_REQUIRE(M == 0 || neighbors != nullptr, "neighbors is NULL with M=%d", M);
+    if (against) LK_REQUIRE(rows != nullptr && ((uintptr_t)rows & 15) == 0, "rows must be a 16-byte aligned device buffer");
     const int pitch = uf_pitch(n);
     double *d_z, *d_g;
     if (const int rc = Scratch(h, h->ws).buf(d_z, (size_t)B * pitch).buf(d_g, B).carve(stream)) return rc;
+    if (!against) Bn = B;
+    const double *zn = against ? static_cast<const double *>(rows) : d_z, *gn = against ? zn + (size_t)Bn * pitch : d_g;
     if (M > 0)
         hipLaunchKernelGGL(underfit_prepare_kernel, dim3(B), dim3(1024), 0, stream, flux, N, n, keep_idx, pitch, d_z, d_g);
-    hipLaunchKernelGGL(underfit_pair_kernel, dim3(B), dim3(UF_NT), 0, stream, (const double *)d_z, (const double *)d_g,
-                       (const double *)d_z, (const double *)d_g, pitch, B, M, neighbors, uf_scale(n), corr, metric);
+    hipLaunchKernelGGL(underfit_pair_kernel, dim3(B), dim3(UF_NT), 0, stream, (const double *)d_z, (const double *)d_g, zn, gn, pitch,
+                       Bn, M, neighbors, uf_scale(n), corr, metric);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
+}
+
+int underfit_neighbors_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int M,
+                              const int32_t *neighbors, double *corr, double *metric, hipStream_t stream) {
+    return underfit_launch(h, B, N, flux, n, keep_idx, false, 0, nullptr, M, neighbors, corr, metric, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ prepared neighbour rows
@@ -255,27 +267,10 @@ int underfit_rows_prepare_launch(lk_handle *h, int Bn, int N, const double *flux
     return LK_OK;
 }
 
-// Only the B target rows are prepared (in the handle's arena); the neighbours are read from `rows` as prepared above with the
-// same n and keep_idx.  Here an index equal to the target's own row number names a row of the OTHER array: a neighbour.
 int underfit_against_rows_launch(lk_handle *h, int B, int N, const double *flux, int n, const int32_t *keep_idx, int Bn,
                                  const void *rows, int M, const int32_t *neighbors, double *corr, double *metric,
                                  hipStream_t stream) {
-    if (const int rc = underfit_shape_ok(B, N, n, keep_idx)) return rc;
-    LK_REQUIRE(Bn >= 1, "Bn must be >= 1 (got %d)", Bn);
-    LK_REQUIRE(M >= 0, "M must be >= 0 (got %d)", M);
-    LK_REQUIRE(flux && metric, "NULL buffer");
-    LK_REQUIRE(M == 0 || neighbors != nullptr, "neighbors is NULL with M=%d", M);
-    LK_REQUIRE(rows != nullptr && ((uintptr_t)rows & 15) == 0, "rows must be a 16-byte aligned device buffer");
-    const int pitch = uf_pitch(n);
-    double *d_z, *d_g;
-    if (const int rc = Scratch(h, h->ws).buf(d_z, (size_t)B * pitch).buf(d_g, B).carve(stream)) return rc;
-    const double *zn = static_cast<const double *>(rows);
-    if (M > 0)
-        hipLaunchKernelGGL(underfit_prepare_kernel, dim3(B), dim3(1024), 0, stream, flux, N, n, keep_idx, pitch, d_z, d_g);
-    hipLaunchKernelGGL(underfit_pair_kernel, dim3(B), dim3(UF_NT), 0, stream, (const double *)d_z, (const double *)d_g, zn,
-                       zn + (size_t)Bn * pitch, pitch, Bn, M, neighbors, uf_scale(n), corr, metric);
-    LK_HIP_CHECK(hipGetLastError());
-    return LK_OK;
+    return underfit_launch(h, B, N, flux, n, keep_idx, true, Bn, rows, M, neighbors, corr, metric, stream);
 }
 
 // ================================================================================================ the metric on a cadence grid
@@ -539,15 +534,20 @@ static void ufg_pair(int B, const double *z, const unsigned long long *mk, const
                        neighbors, d_tab, corr, n_common, metric);
 }
 
-// Workspace: B x pitch doubles of z rows + B x pitch / 64 presence words + the inverse map pos (B x Nx int32) + Nx + 1 scales.
-int underfit_grid_neighbors_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx, const double *flux,
-                                   const uint8_t *cmask, int M, const int32_t *neighbors, double *corr, int32_t *n_common,
-                                   double *metric, hipStream_t stream) {
+// The B target rows are prepared in the handle's arena (workspace: B x pitch doubles of z rows + B x pitch / 64 presence words + the
+// inverse map pos (B x Nx int32) + Nx + 1 scales).  against == false: the neighbours are the batch itself.  against: they are read
+// from `block` (Bn of them, as underfit_grid_rows_prepare_launch leaves them on the same grid); then an index equal to the target's
+// own row number names a row of the OTHER array: a neighbour.
+static int underfit_grid_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx, const double *flux,
+                                const uint8_t *cmask, bool against, int Bn, const void *block, int M, const int32_t *neighbors,
+                                double *corr, int32_t *n_common, double *metric, hipStream_t stream) {
     int64_t nmax = 0;
     if (const int rc = ufg_shape_ok(B, n_off_host, Nx, &nmax)) return rc;
+    if (against) LK_REQUIRE(Bn >= 1, "Bn must be >= 1 (got %d)", Bn);
     LK_REQUIRE(M >= 0, "M must be >= 0 (got %d)", M);
     LK_REQUIRE(rows && flux && metric, "NULL buffer");
     LK_REQUIRE(M == 0 || neighbors != nullptr, "neighbors is NULL with M=%d", M);
+    if (against) LK_REQUIRE(block != nullptr && ((uintptr_t)block & 15) == 0, "block must be a 16-byte aligned device buffer");
     const int pitch = uf_pitch(Nx), init = INT_MAX;
     int64_t *d_off;
     int32_t *d_pos;
@@ -559,9 +559,18 @@ int underfit_grid_neighbors_launch(lk_handle *h, int B, const int64_t *n_off_hos
         .buf(d_z, (size_t)B * pitch).buf(d_mk, (size_t)B * ufg_words(Nx)).upload(d_tab, ufg_scale_table(h, Nx), (size_t)Nx + 1);
     if (const int rc = ws.carve(stream)) return rc;
     if (const int rc = ufg_prepare(B, d_off, nmax, rows, Nx, flux, cmask, d_pos, d_bad, d_z, d_mk, stream)) return rc;
-    ufg_pair(B, d_z, d_mk, d_z, d_mk, Nx, B, M, neighbors, d_tab, corr, n_common, metric, stream);
+    if (!against) Bn = B;
+    const double *zn = against ? static_cast<const double *>(block) : d_z;
+    const unsigned long long *mkn = against ? reinterpret_cast<const unsigned long long *>(zn + (size_t)Bn * pitch) : d_mk;
+    ufg_pair(B, d_z, d_mk, zn, mkn, Nx, Bn, M, neighbors, d_tab, corr, n_common, metric, stream);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
+}
+
+int underfit_grid_neighbors_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx, const double *flux,
+                                   const uint8_t *cmask, int M, const int32_t *neighbors, double *corr, int32_t *n_common,
+                                   double *metric, hipStream_t stream) {
+    return underfit_grid_launch(h, B, n_off_host, rows, Nx, flux, cmask, false, 0, nullptr, M, neighbors, corr, n_common, metric, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ prepared neighbour rows, on a grid
@@ -596,34 +605,10 @@ int underfit_grid_rows_prepare_launch(lk_handle *h, int Bn, const int64_t *n_off
                        reinterpret_cast<unsigned long long *>(z + (size_t)Bn * uf_pitch(Nx)), stream);
 }
 
-// Only the B target rows are prepared (in the handle's arena); the neighbours are read from `block` as prepared above on the same
-// grid.  Here an index equal to the target's own row number names a row of the OTHER array: a neighbour.
 int underfit_grid_against_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx, const double *flux,
                                       const uint8_t *cmask, int Bn, const void *block, int M, const int32_t *neighbors, double *corr,
                                       int32_t *n_common, double *metric, hipStream_t stream) {
-    int64_t nmax = 0;
-    if (const int rc = ufg_shape_ok(B, n_off_host, Nx, &nmax)) return rc;
-    LK_REQUIRE(Bn >= 1, "Bn must be >= 1 (got %d)", Bn);
-    LK_REQUIRE(M >= 0, "M must be >= 0 (got %d)", M);
-    LK_REQUIRE(rows && flux && metric, "NULL buffer");
-    LK_REQUIRE(M == 0 || neighbors != nullptr, "neighbors is NULL with M=%d", M);
-    LK_REQUIRE(block != nullptr && ((uintptr_t)block & 15) == 0, "block must be a 16-byte aligned device buffer");
-    const int pitch = uf_pitch(Nx), init = INT_MAX;
-    int64_t *d_off;
-    int32_t *d_pos;
-    int *d_bad;
-    double *d_z, *d_tab;
-    unsigned long long *d_mk;
-    Scratch ws(h, h->ws);
-    ws.upload(d_off, n_off_host, (size_t)B + 1).upload(d_bad, &init, 1).buf(d_pos, (size_t)B * Nx)
-        .buf(d_z, (size_t)B * pitch).buf(d_mk, (size_t)B * ufg_words(Nx)).upload(d_tab, ufg_scale_table(h, Nx), (size_t)Nx + 1);
-    if (const int rc = ws.carve(stream)) return rc;
-    if (const int rc = ufg_prepare(B, d_off, nmax, rows, Nx, flux, cmask, d_pos, d_bad, d_z, d_mk, stream)) return rc;
-    const double *zn = static_cast<const double *>(block);
-    ufg_pair(B, d_z, d_mk, zn, reinterpret_cast<const unsigned long long *>(zn + (size_t)Bn * pitch), Nx, Bn, M, neighbors, d_tab,
-             corr, n_common, metric, stream);
-    LK_HIP_CHECK(hipGetLastError());
-    return LK_OK;
+    return underfit_grid_launch(h, B, n_off_host, rows, Nx, flux, cmask, true, Bn, block, M, neighbors, corr, n_common, metric, stream);
 }
 
 }  // namespace lk

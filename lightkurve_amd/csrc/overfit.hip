@@ -39,109 +39,26 @@ constexpr int OF_NT = 256;         // noise and spectra passes
 // times t - t[first kept] (written R times: rows (r, b) of the time block serve the R x B noise rows of a round, rows (0, b)
 // the two flux launches), and mean_unc[b].  A session does it in two halves: y1 == NULL writes z0 and the times alone (begin),
 // y0 == NULL writes z1 and mean_unc alone (every evaluation); each half does what the whole does to its own outputs.
+//
+// Where a target's rows start is the one thing a batch's layout decides.  Target b's cadences are [n_off[b], n_off[b + 1]) of the
+// inputs, its kept ones keep_idx[k_off[b] .. k_off[b + 1]) (target-relative, ascending; keep_idx == NULL: all), and its packed row
+// starts at element k_off[b] of a block of cad = k_off[B] elements (round r of the times and of the noise: r cad + k_off[b]).
+// n_off == NULL is the uniform batch: n_off[b] = b N, k_off[b] = b n, cad = B n and ONE keep_idx serves every target; it reads no
+// table.  b is uniform over the workgroup, so the choice is a scalar branch.
 __global__ __launch_bounds__(OF_PREP_NT) void overfit_prepare_kernel(const double *__restrict__ time, const double *__restrict__ y0,
                                                                     const double *__restrict__ y1, const double *__restrict__ e1,
-                                                                    int N, int n, const int32_t *__restrict__ keep_idx, int B,
-                                                                    int R, double *__restrict__ z0, double *__restrict__ z1,
+                                                                    int N, int n, const int64_t *__restrict__ n_off,
+                                                                    const int32_t *__restrict__ keep_idx,
+                                                                    const int64_t *__restrict__ k_off, int64_t cad, int R,
+                                                                    double *__restrict__ z0, double *__restrict__ z1,
                                                                     double *__restrict__ trel, double *__restrict__ mean_unc) {
     __shared__ unsigned long long sh[OF_PREP_NT];
     __shared__ int sh_cnt[OF_PREP_NT];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const size_t in = (size_t)b * N, out = (size_t)b * n;
-    auto idx = [&](int i) { return keep_idx ? keep_idx[i] : i; };
-    auto all = [&](int) { return true; };
-    double med0 = 0.0, med1 = 0.0, t0 = 0.0;   // (y0, y1: uniform over the grid)
-    if (y0) {
-        med0 = block_median(n, (long long)n, [&](int i) { return y0[in + idx(i)]; }, all, sh);
-        __syncthreads();
-        t0 = time[in + idx(0)];
-    }
-    if (y1) {
-        med1 = block_median(n, (long long)n, [&](int i) { return y1[in + idx(i)]; }, all, sh);
-        __syncthreads();
-    }
-    double s = 0.0;
-    int cnt = 0;
-    for (int i = tid; i < n; i += OF_PREP_NT) {
-        const int j = idx(i);
-        // y / med - 1.0 as two separately rounded operations (a zero median gives non-finite rows, as in the reference)
-        if (y0) {
-            z0[out + i] = __dsub_rn(__ddiv_rn(y0[in + j], med0), 1.0);
-            const double tr = __dsub_rn(time[in + j], t0);
-            for (int r = 0; r < R; ++r) trel[((size_t)r * B + b) * n + i] = tr;
-        }
-        if (y1) {
-            z1[out + i] = __dsub_rn(__ddiv_rn(y1[in + j], med1), 1.0);
-            const double u = __ddiv_rn(e1[in + j], med1);
-            if (u == u) {
-                s += u;
-                ++cnt;
-            }
-        }
-    }
-    if (!y1) return;
-    double *shd = reinterpret_cast<double *>(sh);
-    shd[tid] = s;
-    sh_cnt[tid] = cnt;
-    __syncthreads();
-    for (int h = OF_PREP_NT / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-            shd[tid] += shd[tid + h];
-            sh_cnt[tid] += sh_cnt[tid + h];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) mean_unc[b] = sh_cnt[0] ? shd[0] / (double)sh_cnt[0] : __longlong_as_double(0x7ff8000000000000ll);
-}
-
-// ------------------------------------------------------------------------------------------------ noise
-// Rows (kk, b), kk < nk: g[(kk B + b) n + c] = normal(target first_target + b, sample k0 + kk, cadence c) * mean_unc[b]
-// (mean_unc == NULL: the normals themselves).  One thread = one Philox call = cadences 2i and 2i + 1; bpr workgroups per row.
-// A row starts 16-byte aligned when its first element index is even: then the pair goes out as one 16-byte store.
-__global__ __launch_bounds__(OF_NT) void overfit_noise_kernel(int B, int n, int bpr, int k0, uint32_t key0, uint32_t key1,
-                                                             uint32_t first_target, uint32_t stream_id,
-                                                             const double *__restrict__ mean_unc, double *__restrict__ g) {
-    const int row = blockIdx.x / bpr, i = (blockIdx.x - row * bpr) * OF_NT + threadIdx.x;
-    const int c = 2 * i;
-    if (c >= n) return;
-    const int kk = row / B, b = row - kk * B;
-    double a, s;
-    philox_normal_pair(philox4x32_10((uint32_t)i, (uint32_t)(k0 + kk), first_target + (uint32_t)b, stream_id, key0, key1), a, s);
-    const double mu = mean_unc ? mean_unc[b] : 1.0;
-    a *= mu;
-    s *= mu;
-    const size_t base = (size_t)row * n;
-    if (c + 1 < n) {
-        if ((base & 1) == 0) {
-            *reinterpret_cast<double2 *>(g + base + c) = make_double2(a, s);
-        } else {
-            g[base + c] = a;
-            g[base + c + 1] = s;
-        }
-    } else {
-        g[base + c] = a;   // the last pair of an odd count: its second normal is discarded
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ ragged targets
-// The two kernels above for a batch on its own offsets: target b's cadences are [n_off[b], n_off[b + 1]) of the inputs, its kept
-// ones keep_idx[k_off[b] .. k_off[b + 1]) (target-relative, ascending; keep_idx == NULL: all, and k_off is n_off), and its packed
-// row starts at element k_off[b] of a block of cad = k_off[B] elements (round r of the times and of the noise: r cad + k_off[b]).
-// Per target they do what the uniform kernels do to a target of that length: the same operations in the same order, and the same
-// Philox counter (pair of kept cadences of that target, sample, first_target + b, stream_id).
-__global__ __launch_bounds__(OF_PREP_NT) void overfit_prepare_rows_kernel(const double *__restrict__ time, const double *__restrict__ y0,
-                                                                         const double *__restrict__ y1, const double *__restrict__ e1,
-                                                                         const int64_t *__restrict__ n_off,
-                                                                         const int32_t *__restrict__ keep_idx,
-                                                                         const int64_t *__restrict__ k_off, int64_t cad, int R,
-                                                                         double *__restrict__ z0, double *__restrict__ z1,
-                                                                         double *__restrict__ trel, double *__restrict__ mean_unc) {
-    __shared__ unsigned long long sh[OF_PREP_NT];
-    __shared__ int sh_cnt[OF_PREP_NT];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const size_t in = (size_t)n_off[b], out = (size_t)k_off[b];
-    const int n = (int)(k_off[b + 1] - k_off[b]);
-    const int32_t *kb = keep_idx ? keep_idx + out : nullptr;
+    const bool ragged = n_off != nullptr;
+    const size_t in = ragged ? (size_t)n_off[b] : (size_t)b * N, out = ragged ? (size_t)k_off[b] : (size_t)b * n;
+    if (ragged) n = (int)(k_off[b + 1] - k_off[b]);
+    const int32_t *kb = keep_idx ? keep_idx + (ragged ? out : 0) : nullptr;
     auto idx = [&](int i) { return kb ? kb[i] : i; };
     auto all = [&](int) { return true; };
     double med0 = 0.0, med1 = 0.0, t0 = 0.0;   // (y0, y1: uniform over the grid)
@@ -158,6 +75,7 @@ __global__ __launch_bounds__(OF_PREP_NT) void overfit_prepare_rows_kernel(const 
     int cnt = 0;
     for (int i = tid; i < n; i += OF_PREP_NT) {
         const int j = idx(i);
+        // y / med - 1.0 as two separately rounded operations (a zero median gives non-finite rows, as in the reference)
         if (y0) {
             z0[out + i] = __dsub_rn(__ddiv_rn(y0[in + j], med0), 1.0);
             const double tr = __dsub_rn(time[in + j], t0);
@@ -187,21 +105,27 @@ __global__ __launch_bounds__(OF_PREP_NT) void overfit_prepare_rows_kernel(const 
     if (tid == 0) mean_unc[b] = sh_cnt[0] ? shd[0] / (double)sh_cnt[0] : __longlong_as_double(0x7ff8000000000000ll);
 }
 
-// bpr workgroups per row, sized by the longest row: the ones past a shorter row's end leave at once
-__global__ __launch_bounds__(OF_NT) void overfit_noise_rows_kernel(int B, const int64_t *__restrict__ k_off, int64_t cad, int bpr, int k0,
-                                                                  uint32_t key0, uint32_t key1, uint32_t first_target,
-                                                                  uint32_t stream_id, const double *__restrict__ mean_unc,
-                                                                  double *__restrict__ g) {
+// ------------------------------------------------------------------------------------------------ noise
+// Rows (kk, b), kk < nk: g[kk cad + k_off[b] + c] = normal(target first_target + b, sample k0 + kk, kept cadence c of that target)
+// * mean_unc[b] (mean_unc == NULL: the normals themselves); k_off == NULL: the uniform batch, k_off[b] = b n.  One thread = one
+// Philox call = cadences 2i and 2i + 1, so any (target, sample, cadence) gets the same number on either layout; bpr workgroups
+// per row, sized by the longest row: the ones past a shorter row's end leave at once.
+// A row starts 16-byte aligned when its first element index is even: then the pair goes out as one 16-byte store.
+__global__ __launch_bounds__(OF_NT) void overfit_noise_kernel(int B, int n, const int64_t *__restrict__ k_off, int64_t cad, int bpr,
+                                                             int k0, uint32_t key0, uint32_t key1, uint32_t first_target,
+                                                             uint32_t stream_id, const double *__restrict__ mean_unc,
+                                                             double *__restrict__ g) {
     const int row = blockIdx.x / bpr, i = (blockIdx.x - row * bpr) * OF_NT + threadIdx.x;
     const int kk = row / B, b = row - kk * B;
-    const int n = (int)(k_off[b + 1] - k_off[b]), c = 2 * i;
+    if (k_off) n = (int)(k_off[b + 1] - k_off[b]);
+    const int c = 2 * i;
     if (c >= n) return;
     double a, s;
     philox_normal_pair(philox4x32_10((uint32_t)i, (uint32_t)(k0 + kk), first_target + (uint32_t)b, stream_id, key0, key1), a, s);
     const double mu = mean_unc ? mean_unc[b] : 1.0;
     a *= mu;
     s *= mu;
-    const size_t base = (size_t)kk * (size_t)cad + (size_t)k_off[b];
+    const size_t base = (size_t)kk * (size_t)cad + (k_off ? (size_t)k_off[b] : (size_t)b * n);
     if (c + 1 < n) {
         if ((base & 1) == 0) {
             *reinterpret_cast<double2 *>(g + base + c) = make_double2(a, s);
@@ -352,9 +276,6 @@ OverfitPlan of_plan(int B, size_t cad, int nmax, int64_t M, int n_samples, size_
         }
     return of_layout(B, cad, M, n_samples, R, offs);
 }
-OverfitPlan of_plan(int B, int n, int64_t M, int n_samples, size_t budget) {
-    return of_plan(B, (size_t)B * n, n, M, n_samples, budget, false);
-}
 }  // namespace
 
 static int overfit_shape_ok(int B, int n, int64_t M, int n_samples) {
@@ -371,7 +292,8 @@ int overfit_scratch_bytes(int B, int n, int64_t M, int n_samples, int64_t max_sc
     if (rc) return rc;
     LK_REQUIRE(bytes != nullptr, "bytes is NULL");
     LK_REQUIRE(max_scratch_bytes >= 0, "max_scratch_bytes must be >= 0 (0: the default of %lld)", (long long)LK_OVERFIT_SCRATCH_DEFAULT);
-    const OverfitPlan p = of_plan(B, n, M, n_samples, (size_t)(max_scratch_bytes ? max_scratch_bytes : LK_OVERFIT_SCRATCH_DEFAULT));
+    const OverfitPlan p = of_plan(B, (size_t)B * n, n, M, n_samples,
+                                  (size_t)(max_scratch_bytes ? max_scratch_bytes : LK_OVERFIT_SCRATCH_DEFAULT), false);
     *bytes = (int64_t)p.total;
     if (samples_per_round) *samples_per_round = p.R;
     return LK_OK;
@@ -384,11 +306,13 @@ static int overfit_rng_ok(int B, int64_t first_target, int64_t stream_id) {
     return LK_OK;
 }
 
-static void overfit_noise_rows(int B, int n, int nk, int k0, uint64_t seed, int64_t first_target, int64_t stream_id,
-                               const double *mean_unc, double *g, hipStream_t stream) {
+// nk samples from k0 on, one launch.  n: the longest row; d_koff: the kept offsets on the device, NULL for a uniform batch
+static void overfit_noise_rows(int B, int n, const int64_t *d_koff, size_t cad, int nk, int k0, uint64_t seed, int64_t first_target,
+                               int64_t stream_id, const double *mean_unc, double *g, hipStream_t stream) {
     const int bpr = of_blocks_per_row(n);
-    hipLaunchKernelGGL(overfit_noise_kernel, dim3((unsigned)((size_t)nk * B * bpr)), dim3(OF_NT), 0, stream, B, n, bpr, k0,
-                       (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), (uint32_t)first_target, (uint32_t)stream_id, mean_unc, g);
+    hipLaunchKernelGGL(overfit_noise_kernel, dim3((unsigned)((size_t)nk * B * bpr)), dim3(OF_NT), 0, stream, B, n, d_koff, (int64_t)cad,
+                       bpr, k0, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), (uint32_t)first_target, (uint32_t)stream_id,
+                       mean_unc, g);
 }
 
 int overfit_noise_launch(lk_handle *h, int B, int n, int k, uint64_t seed, int64_t first_target, int64_t stream_id, double *out,
@@ -400,168 +324,12 @@ int overfit_noise_launch(lk_handle *h, int B, int n, int k, uint64_t seed, int64
     LK_REQUIRE((int64_t)B * of_blocks_per_row(n) < ((int64_t)1 << 31), "B x n = %d x %d is more than one noise launch covers", B, n);
     int rc = overfit_rng_ok(B, first_target, stream_id);
     if (rc) return rc;
-    overfit_noise_rows(B, n, 1, k, seed, first_target, stream_id, nullptr, out, stream);
+    overfit_noise_rows(B, n, nullptr, (size_t)B * n, 1, k, seed, first_target, stream_id, nullptr, out, stream);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }
 
-namespace {
-// one call's view of the caller-owned block and the three steps the unsplit metric and a session share
-struct OverfitRun {
-    lk_handle *h;
-    int B, n, n_samples;   // n: the kept cadences of every target; of the longest one when the batch is ragged
-    double f0, df;
-    int64_t M;
-    hipStream_t stream;
-    bool ragged;
-    size_t cad;            // the kept cadences of all targets together
-    OverfitPlan p;
-    char *base;
-    std::vector<int64_t> off;   // row offsets of the largest launch (R B rows: row (r, b) starts at r cad + the kept offset of b)
-
-    OverfitRun(lk_handle *h_, int B_, int n_, double f0_, double df_, int64_t M_, int n_samples_, void *block, size_t bytes,
-               hipStream_t st)
-        : h(h_), B(B_), n(n_), n_samples(n_samples_), f0(f0_), df(df_), M(M_), stream(st), ragged(false), cad((size_t)B_ * n_),
-          p(of_plan(B_, n_, M_, n_samples_, bytes)), base(static_cast<char *>(block)), off((size_t)p.R * B_ + 1) {
-        for (size_t r = 0; r < off.size(); ++r) off[r] = (int64_t)r * n;
-    }
-    // ragged: k_off = the B + 1 offsets of the kept cadences, nmax the longest row
-    OverfitRun(lk_handle *h_, int B_, const int64_t *k_off, int nmax, double f0_, double df_, int64_t M_, int n_samples_, void *block,
-               size_t bytes, hipStream_t st)
-        : h(h_), B(B_), n(nmax), n_samples(n_samples_), f0(f0_), df(df_), M(M_), stream(st), ragged(true), cad((size_t)k_off[B_]),
-          p(of_plan(B_, cad, nmax, M_, n_samples_, bytes, true)), base(static_cast<char *>(block)), off((size_t)p.R * B_ + 1) {
-        for (int r = 0; r < p.R; ++r)
-            for (int b = 0; b < B_; ++b) off[(size_t)r * B_ + b] = (int64_t)r * (int64_t)cad + k_off[b];
-        off.back() = (int64_t)p.R * (int64_t)cad;
-    }
-    double *at(size_t o) const { return reinterpret_cast<double *>(base + o); }
-    int *n_up() const { return reinterpret_cast<int *>(base + p.n_up); }
-    int64_t *d_noff() const { return reinterpret_cast<int64_t *>(base + p.offs); }   // ragged: the batch's offsets on the device,
-    int64_t *d_koff() const { return d_noff() + B + 1; }                             // then the kept cadences' offsets
-
-    // ragged: both offset tables into the block (captured before the call returns), once per block
-    int upload_offsets(const int64_t *n_off_host, const int64_t *k_off_host) const {
-        if (const int rc = h->stage.copy(d_noff(), n_off_host, ((size_t)B + 1) * 8, stream)) return rc;
-        return h->stage.copy(d_koff(), k_off_host, ((size_t)B + 1) * 8, stream);
-    }
-    int prepare_rows(const double *time, const double *y0, const double *y1, const double *e1, const int32_t *keep_idx) const {
-        hipLaunchKernelGGL(overfit_prepare_rows_kernel, dim3(B), dim3(OF_PREP_NT), 0, stream, time, y0, y1, e1,
-                           (const int64_t *)d_noff(), keep_idx, (const int64_t *)d_koff(), (int64_t)cad, p.R, at(p.z0), at(p.z1),
-                           at(p.trel), at(p.mean_unc));
-        LK_HIP_CHECK(hipGetLastError());
-        return LK_OK;
-    }
-
-    int prepare(const double *time, const double *y0, const double *y1, const double *e1, int N, const int32_t *keep_idx) const {
-        hipLaunchKernelGGL(overfit_prepare_kernel, dim3(B), dim3(OF_PREP_NT), 0, stream, time, y0, y1, e1, N, n, keep_idx, B, p.R,
-                           at(p.z0), at(p.z1), at(p.trel), at(p.mean_unc));
-        LK_HIP_CHECK(hipGetLastError());
-        return LK_OK;
-    }
-    int ls(int rows, const double *y, double *power) const {
-        return lsfast_launch(h, rows, off.data(), at(p.trel), y, nullptr, f0, df, M, 1, 1, LK_NORM_LK_AMPLITUDE, nullptr, 5, power, stream);
-    }
-    // P1, then n_up and S against P0
-    int change() const {
-        if (const int rc = ls(B, at(p.z1), at(p.p1))) return rc;
-        hipLaunchKernelGGL(overfit_change_kernel, dim3(B), dim3(OF_NT), 0, stream, (const double *)at(p.p0), (const double *)at(p.p1),
-                           (int)M, n_up(), at(p.S));
-        return LK_OK;
-    }
-    // mnp[k][b] = nanmean(LS of sample k's normals times scale[b]) (scale == NULL: the unit normals), in rounds of R samples
-    int noise_means(uint64_t seed, int64_t first_target, int64_t stream_id, const double *scale) const {
-        for (int k0 = 0; k0 < n_samples; k0 += p.R) {
-            const int nk = std::min(p.R, n_samples - k0);
-            if (ragged) {
-                const int bpr = of_blocks_per_row(n);
-                hipLaunchKernelGGL(overfit_noise_rows_kernel, dim3((unsigned)((size_t)nk * B * bpr)), dim3(OF_NT), 0, stream, B,
-                                   (const int64_t *)d_koff(), (int64_t)cad, bpr, k0, (uint32_t)(seed & 0xffffffffu),
-                                   (uint32_t)(seed >> 32), (uint32_t)first_target, (uint32_t)stream_id, scale, at(p.g));
-            } else {
-                overfit_noise_rows(B, n, nk, k0, seed, first_target, stream_id, scale, at(p.g), stream);
-            }
-            LK_HIP_CHECK(hipGetLastError());
-            if (const int rc = ls(nk * B, at(p.g), at(p.pn))) return rc;
-            hipLaunchKernelGGL(overfit_noise_mean_kernel, dim3((unsigned)(nk * B)), dim3(OF_NT), 0, stream, (const double *)at(p.pn),
-                               (int)M, at(p.mnp) + (size_t)k0 * B);
-        }
-        return LK_OK;
-    }
-    int metric(const double *amp, double *out) const {
-        hipLaunchKernelGGL(overfit_metric_kernel, dim3((B + OF_NT - 1) / OF_NT), dim3(OF_NT), 0, stream, B, n_samples,
-                           (const int *)n_up(), (const double *)at(p.S), (const double *)at(p.mnp), amp, out);
-        LK_HIP_CHECK(hipGetLastError());
-        return LK_OK;
-    }
-};
-}  // namespace
-
-static int overfit_block_ok(int B, int N, int n, const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples,
-                            const void *block, int64_t bytes) {
-    int rc = overfit_shape_ok(B, n, M, n_samples);
-    if (rc) return rc;
-    LK_REQUIRE(N >= n && N < (1 << 30), "need n <= N < 2^30 (got n=%d, N=%d)", n, N);
-    LK_REQUIRE(keep_idx != nullptr || n == N, "keep_idx is NULL (all cadences) but n=%d != N=%d", n, N);
-    LK_REQUIRE(f0 >= 0.0 && df > 0.0, "the grid needs f0 >= 0 and df > 0 (got f0=%g, df=%g)", f0, df);
-    LK_REQUIRE(block != nullptr && ((uintptr_t)block & 255) == 0, "scratch must be a 256-byte aligned device buffer");
-    LK_REQUIRE(bytes >= 0, "scratch_bytes must be >= 0");
-    const OverfitPlan p = of_plan(B, n, M, n_samples, (size_t)bytes);
-    LK_REQUIRE(p.total <= (size_t)bytes, "scratch too small: %lld bytes given, one sample per round needs %lld "
-               "(lk_overfit_scratch_bytes)", (long long)bytes, (long long)p.total);
-    return LK_OK;
-}
-
-int overfit_metric_launch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, const double *flux_corr,
-                          const double *err_corr, int n, const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples,
-                          uint64_t seed, int64_t first_target, int64_t stream_id, void *scratch, int64_t scratch_bytes,
-                          double *metric, hipStream_t stream) {
-    int rc = overfit_block_ok(B, N, n, keep_idx, f0, df, M, n_samples, scratch, scratch_bytes);
-    if (rc) return rc;
-    LK_REQUIRE(time && flux_orig && flux_corr && err_corr && metric, "NULL buffer");
-    if ((rc = overfit_rng_ok(B, first_target, stream_id))) return rc;
-    const OverfitRun run(h, B, n, f0, df, M, n_samples, scratch, (size_t)scratch_bytes, stream);
-    if ((rc = run.prepare(time, flux_orig, flux_corr, err_corr, N, keep_idx))) return rc;
-    if ((rc = run.ls(B, run.at(run.p.z0), run.at(run.p.p0)))) return rc;
-    if ((rc = run.change())) return rc;
-    if ((rc = run.noise_means(seed, first_target, stream_id, run.at(run.p.mean_unc)))) return rc;
-    return run.metric(nullptr, metric);
-}
-
-// ------------------------------------------------------------------------------------------------ session
-// The metric in two halves for a caller that scores MANY corrections of one original batch with one noise stream (the ridge
-// search): begin takes everything that does not depend on the correction (z0, the times, P0 and u_k = nanmean(LS of the unit
-// normals of sample k)); an evaluation packs z1 and mean_unc, takes P1 in ONE launch of B rows and closes the form with
-// mnp_k = |mean_unc| * u_k.  P0 and P1 are the bits of the unsplit call, so n_up and S are too; only mnp_k differs, by the
-// rounding of nanmean(LS(normal * mean_unc)) against |mean_unc| * nanmean(LS(normal)).  Edge rules: a NaN mean_unc gives a NaN
-// noise mean (a NaN metric) and a zero one a zero noise mean (per_k = inf, metric 0) when n_up > 0; n_up == 0 gives 0.  The
-// block has the layout of the unsplit call's scratch (same size, same rounds); an evaluation writes z1, P1, mean_unc, n_up and
-// S and nothing that begin wrote.
-int overfit_session_begin_launch(lk_handle *h, int B, int N, const double *time, const double *flux_orig, int n,
-                                 const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, uint64_t seed,
-                                 int64_t first_target, int64_t stream_id, void *session, int64_t session_bytes, hipStream_t stream) {
-    int rc = overfit_block_ok(B, N, n, keep_idx, f0, df, M, n_samples, session, session_bytes);
-    if (rc) return rc;
-    LK_REQUIRE(time && flux_orig, "NULL buffer");
-    if ((rc = overfit_rng_ok(B, first_target, stream_id))) return rc;
-    const OverfitRun run(h, B, n, f0, df, M, n_samples, session, (size_t)session_bytes, stream);
-    if ((rc = run.prepare(time, flux_orig, nullptr, nullptr, N, keep_idx))) return rc;
-    if ((rc = run.ls(B, run.at(run.p.z0), run.at(run.p.p0)))) return rc;
-    return run.noise_means(seed, first_target, stream_id, nullptr);
-}
-
-int overfit_session_eval_launch(lk_handle *h, int B, int N, const double *flux_corr, const double *err_corr, int n,
-                                const int32_t *keep_idx, double f0, double df, int64_t M, int n_samples, void *session,
-                                int64_t session_bytes, double *metric, hipStream_t stream) {
-    int rc = overfit_block_ok(B, N, n, keep_idx, f0, df, M, n_samples, session, session_bytes);
-    if (rc) return rc;
-    LK_REQUIRE(flux_corr && err_corr && metric, "NULL buffer");
-    const OverfitRun run(h, B, n, f0, df, M, n_samples, session, (size_t)session_bytes, stream);
-    if ((rc = run.prepare(nullptr, nullptr, flux_corr, err_corr, N, keep_idx))) return rc;
-    if ((rc = run.change())) return rc;
-    return run.metric(run.at(run.p.mean_unc), metric);
-}
-
-// ------------------------------------------------------------------------------------------------ ragged entry points
+// ------------------------------------------------------------------------------------------------ the batch's own offsets
 // k_off_host: the B + 1 offsets of the kept cadences; keep_idx == NULL keeps all and k_off_host may be NULL or n_off_host.
 static int overfit_rows_ok(int B, const int64_t *n_off_host, const int32_t *keep_idx, const int64_t *&k_off_host, int64_t M,
                            int n_samples, int *nmax) {
@@ -604,65 +372,147 @@ int overfit_scratch_rows_bytes(int B, const int64_t *k_off_host, int64_t M, int 
     return LK_OK;
 }
 
-static int overfit_rows_block_ok(int B, const int64_t *k_off_host, int nmax, double f0, double df, int64_t M, int n_samples,
-                                 const void *block, int64_t bytes) {
+// ------------------------------------------------------------------------------------------------ one call
+// The checks every launcher below starts with, each flavour's own first and in its own order.  A ragged batch comes out with
+// k_off_host set (n_off_host when all cadences are kept) and n = its longest row.
+static int overfit_batch_ok(OverfitBatch &bt, double f0, double df, int64_t M, int n_samples, const void *block, int64_t bytes) {
+    if (bt.ragged) {
+        if (const int rc = overfit_rows_ok(bt.B, bt.n_off_host, bt.keep_idx, bt.k_off_host, M, n_samples, &bt.n)) return rc;
+    } else {
+        if (const int rc = overfit_shape_ok(bt.B, bt.n, M, n_samples)) return rc;
+        LK_REQUIRE(bt.N >= bt.n && bt.N < (1 << 30), "need n <= N < 2^30 (got n=%d, N=%d)", bt.n, bt.N);
+        LK_REQUIRE(bt.keep_idx != nullptr || bt.n == bt.N, "keep_idx is NULL (all cadences) but n=%d != N=%d", bt.n, bt.N);
+    }
     LK_REQUIRE(f0 >= 0.0 && df > 0.0, "the grid needs f0 >= 0 and df > 0 (got f0=%g, df=%g)", f0, df);
     LK_REQUIRE(block != nullptr && ((uintptr_t)block & 255) == 0, "scratch must be a 256-byte aligned device buffer");
     LK_REQUIRE(bytes >= 0, "scratch_bytes must be >= 0");
-    const OverfitPlan p = of_plan(B, (size_t)k_off_host[B], nmax, M, n_samples, (size_t)bytes, true);
-    LK_REQUIRE(p.total <= (size_t)bytes, "scratch too small: %lld bytes given, one sample per round needs %lld "
-               "(lk_overfit_scratch_rows_bytes)", (long long)bytes, (long long)p.total);
+    const OverfitPlan p = of_plan(bt.B, bt.cad(), bt.n, M, n_samples, (size_t)bytes, bt.ragged);
+    LK_REQUIRE(p.total <= (size_t)bytes, "scratch too small: %lld bytes given, one sample per round needs %lld (%s)", (long long)bytes,
+               (long long)p.total, bt.ragged ? "lk_overfit_scratch_rows_bytes" : "lk_overfit_scratch_bytes");
     return LK_OK;
 }
 
-int overfit_metric_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
-                               const double *flux_corr, const double *err_corr, const int32_t *keep_idx, const int64_t *k_off_host,
-                               double f0, double df, int64_t M, int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id,
-                               void *scratch, int64_t scratch_bytes, double *metric, hipStream_t stream) {
-    int nmax = 0;
-    int rc = overfit_rows_ok(B, n_off_host, keep_idx, k_off_host, M, n_samples, &nmax);
+namespace {
+// one call's view of the caller-owned block and the steps the unsplit metric and a session share
+struct OverfitRun {
+    lk_handle *h;
+    OverfitBatch bt;       // as overfit_batch_ok left it
+    int B, n, n_samples;   // n: the kept cadences of every target; of the longest one when the batch is ragged
+    double f0, df;
+    int64_t M;
+    hipStream_t stream;
+    size_t cad;            // the kept cadences of all targets together
+    OverfitPlan p;
+    char *base;
+    std::vector<int64_t> off;   // row offsets of the largest launch (R B rows: row (r, b) starts at r cad + the kept offset of b)
+
+    OverfitRun(lk_handle *h_, const OverfitBatch &bt_, double f0_, double df_, int64_t M_, int n_samples_, void *block, size_t bytes,
+               hipStream_t st)
+        : h(h_), bt(bt_), B(bt_.B), n(bt_.n), n_samples(n_samples_), f0(f0_), df(df_), M(M_), stream(st), cad(bt_.cad()),
+          p(of_plan(B, cad, n, M_, n_samples_, bytes, bt_.ragged)), base(static_cast<char *>(block)), off((size_t)p.R * B + 1) {
+        for (int r = 0; r < p.R; ++r)
+            for (int b = 0; b < B; ++b)
+                off[(size_t)r * B + b] = (int64_t)r * (int64_t)cad + (bt.ragged ? bt.k_off_host[b] : (int64_t)b * n);
+        off.back() = (int64_t)p.R * (int64_t)cad;
+    }
+    double *at(size_t o) const { return reinterpret_cast<double *>(base + o); }
+    int *n_up() const { return reinterpret_cast<int *>(base + p.n_up); }
+    // ragged: the batch's offsets on the device, then the kept cadences' offsets; a uniform block has neither (NULL: the kernels
+    // compute them)
+    const int64_t *d_noff() const { return bt.ragged ? reinterpret_cast<const int64_t *>(base + p.offs) : nullptr; }
+    const int64_t *d_koff() const { return bt.ragged ? d_noff() + B + 1 : nullptr; }
+
+    // ragged: both offset tables into the block (captured before the call returns), once per block
+    int upload_offsets() const {
+        if (!bt.ragged) return LK_OK;
+        int64_t *d = reinterpret_cast<int64_t *>(base + p.offs);
+        if (const int rc = h->stage.copy(d, bt.n_off_host, ((size_t)B + 1) * 8, stream)) return rc;
+        return h->stage.copy(d + B + 1, bt.k_off_host, ((size_t)B + 1) * 8, stream);
+    }
+    int prepare(const double *time, const double *y0, const double *y1, const double *e1) const {
+        hipLaunchKernelGGL(overfit_prepare_kernel, dim3(B), dim3(OF_PREP_NT), 0, stream, time, y0, y1, e1, bt.N, n, d_noff(), bt.keep_idx,
+                           d_koff(), (int64_t)cad, p.R, at(p.z0), at(p.z1), at(p.trel), at(p.mean_unc));
+        LK_HIP_CHECK(hipGetLastError());
+        return LK_OK;
+    }
+    int ls(int rows, const double *y, double *power) const {
+        return lsfast_launch(h, rows, off.data(), at(p.trel), y, nullptr, f0, df, M, 1, 1, LK_NORM_LK_AMPLITUDE, nullptr, 5, power, stream);
+    }
+    // P1, then n_up and S against P0
+    int change() const {
+        if (const int rc = ls(B, at(p.z1), at(p.p1))) return rc;
+        hipLaunchKernelGGL(overfit_change_kernel, dim3(B), dim3(OF_NT), 0, stream, (const double *)at(p.p0), (const double *)at(p.p1),
+                           (int)M, n_up(), at(p.S));
+        return LK_OK;
+    }
+    // mnp[k][b] = nanmean(LS of sample k's normals times scale[b]) (scale == NULL: the unit normals), in rounds of R samples
+    int noise_means(uint64_t seed, int64_t first_target, int64_t stream_id, const double *scale) const {
+        for (int k0 = 0; k0 < n_samples; k0 += p.R) {
+            const int nk = std::min(p.R, n_samples - k0);
+            overfit_noise_rows(B, n, d_koff(), cad, nk, k0, seed, first_target, stream_id, scale, at(p.g), stream);
+            LK_HIP_CHECK(hipGetLastError());
+            if (const int rc = ls(nk * B, at(p.g), at(p.pn))) return rc;
+            hipLaunchKernelGGL(overfit_noise_mean_kernel, dim3((unsigned)(nk * B)), dim3(OF_NT), 0, stream, (const double *)at(p.pn),
+                               (int)M, at(p.mnp) + (size_t)k0 * B);
+        }
+        return LK_OK;
+    }
+    int metric(const double *amp, double *out) const {
+        hipLaunchKernelGGL(overfit_metric_kernel, dim3((B + OF_NT - 1) / OF_NT), dim3(OF_NT), 0, stream, B, n_samples,
+                           (const int *)n_up(), (const double *)at(p.S), (const double *)at(p.mnp), amp, out);
+        LK_HIP_CHECK(hipGetLastError());
+        return LK_OK;
+    }
+};
+}  // namespace
+
+int overfit_metric_launch(lk_handle *h, OverfitBatch bt, const double *time, const double *flux_orig, const double *flux_corr,
+                          const double *err_corr, double f0, double df, int64_t M, int n_samples, uint64_t seed, int64_t first_target,
+                          int64_t stream_id, void *scratch, int64_t scratch_bytes, double *metric, hipStream_t stream) {
+    int rc = overfit_batch_ok(bt, f0, df, M, n_samples, scratch, scratch_bytes);
     if (rc) return rc;
-    if ((rc = overfit_rows_block_ok(B, k_off_host, nmax, f0, df, M, n_samples, scratch, scratch_bytes))) return rc;
     LK_REQUIRE(time && flux_orig && flux_corr && err_corr && metric, "NULL buffer");
-    if ((rc = overfit_rng_ok(B, first_target, stream_id))) return rc;
-    const OverfitRun run(h, B, k_off_host, nmax, f0, df, M, n_samples, scratch, (size_t)scratch_bytes, stream);
-    if ((rc = run.upload_offsets(n_off_host, k_off_host))) return rc;
-    if ((rc = run.prepare_rows(time, flux_orig, flux_corr, err_corr, keep_idx))) return rc;
-    if ((rc = run.ls(B, run.at(run.p.z0), run.at(run.p.p0)))) return rc;
+    if ((rc = overfit_rng_ok(bt.B, first_target, stream_id))) return rc;
+    const OverfitRun run(h, bt, f0, df, M, n_samples, scratch, (size_t)scratch_bytes, stream);
+    if ((rc = run.upload_offsets())) return rc;
+    if ((rc = run.prepare(time, flux_orig, flux_corr, err_corr))) return rc;
+    if ((rc = run.ls(bt.B, run.at(run.p.z0), run.at(run.p.p0)))) return rc;
     if ((rc = run.change())) return rc;
     if ((rc = run.noise_means(seed, first_target, stream_id, run.at(run.p.mean_unc)))) return rc;
     return run.metric(nullptr, metric);
 }
 
-// The session of a ragged batch: begin also puts the two offset tables into the block, and an evaluation reads them there (its
-// own n_off_host / k_off_host must be begin's: they size the plan and the periodogram launch).
-int overfit_session_begin_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *time, const double *flux_orig,
-                                      const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
-                                      int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id, void *session,
-                                      int64_t session_bytes, hipStream_t stream) {
-    int nmax = 0;
-    int rc = overfit_rows_ok(B, n_off_host, keep_idx, k_off_host, M, n_samples, &nmax);
+// ------------------------------------------------------------------------------------------------ session
+// The metric in two halves for a caller that scores MANY corrections of one original batch with one noise stream (the ridge
+// search): begin takes everything that does not depend on the correction (z0, the times, P0 and u_k = nanmean(LS of the unit
+// normals of sample k)); an evaluation packs z1 and mean_unc, takes P1 in ONE launch of B rows and closes the form with
+// mnp_k = |mean_unc| * u_k.  P0 and P1 are the bits of the unsplit call, so n_up and S are too; only mnp_k differs, by the
+// rounding of nanmean(LS(normal * mean_unc)) against |mean_unc| * nanmean(LS(normal)).  Edge rules: a NaN mean_unc gives a NaN
+// noise mean (a NaN metric) and a zero one a zero noise mean (per_k = inf, metric 0) when n_up > 0; n_up == 0 gives 0.  The
+// block has the layout of the unsplit call's scratch (same size, same rounds); an evaluation writes z1, P1, mean_unc, n_up and
+// S and nothing that begin wrote.  Ragged: begin also puts the two offset tables into the block, and an evaluation reads them
+// there (its own n_off_host / k_off_host must be begin's: they size the plan and the periodogram launch).
+int overfit_session_begin_launch(lk_handle *h, OverfitBatch bt, const double *time, const double *flux_orig, double f0, double df,
+                                 int64_t M, int n_samples, uint64_t seed, int64_t first_target, int64_t stream_id, void *session,
+                                 int64_t session_bytes, hipStream_t stream) {
+    int rc = overfit_batch_ok(bt, f0, df, M, n_samples, session, session_bytes);
     if (rc) return rc;
-    if ((rc = overfit_rows_block_ok(B, k_off_host, nmax, f0, df, M, n_samples, session, session_bytes))) return rc;
     LK_REQUIRE(time && flux_orig, "NULL buffer");
-    if ((rc = overfit_rng_ok(B, first_target, stream_id))) return rc;
-    const OverfitRun run(h, B, k_off_host, nmax, f0, df, M, n_samples, session, (size_t)session_bytes, stream);
-    if ((rc = run.upload_offsets(n_off_host, k_off_host))) return rc;
-    if ((rc = run.prepare_rows(time, flux_orig, nullptr, nullptr, keep_idx))) return rc;
-    if ((rc = run.ls(B, run.at(run.p.z0), run.at(run.p.p0)))) return rc;
+    if ((rc = overfit_rng_ok(bt.B, first_target, stream_id))) return rc;
+    const OverfitRun run(h, bt, f0, df, M, n_samples, session, (size_t)session_bytes, stream);
+    if ((rc = run.upload_offsets())) return rc;
+    if ((rc = run.prepare(time, flux_orig, nullptr, nullptr))) return rc;
+    if ((rc = run.ls(bt.B, run.at(run.p.z0), run.at(run.p.p0)))) return rc;
     return run.noise_means(seed, first_target, stream_id, nullptr);
 }
 
-int overfit_session_eval_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *flux_corr, const double *err_corr,
-                                     const int32_t *keep_idx, const int64_t *k_off_host, double f0, double df, int64_t M,
-                                     int n_samples, void *session, int64_t session_bytes, double *metric, hipStream_t stream) {
-    int nmax = 0;
-    int rc = overfit_rows_ok(B, n_off_host, keep_idx, k_off_host, M, n_samples, &nmax);
+int overfit_session_eval_launch(lk_handle *h, OverfitBatch bt, const double *flux_corr, const double *err_corr, double f0, double df,
+                                int64_t M, int n_samples, void *session, int64_t session_bytes, double *metric, hipStream_t stream) {
+    int rc = overfit_batch_ok(bt, f0, df, M, n_samples, session, session_bytes);
     if (rc) return rc;
-    if ((rc = overfit_rows_block_ok(B, k_off_host, nmax, f0, df, M, n_samples, session, session_bytes))) return rc;
     LK_REQUIRE(flux_corr && err_corr && metric, "NULL buffer");
-    const OverfitRun run(h, B, k_off_host, nmax, f0, df, M, n_samples, session, (size_t)session_bytes, stream);
-    if ((rc = run.prepare_rows(nullptr, nullptr, flux_corr, err_corr, keep_idx))) return rc;
+    const OverfitRun run(h, bt, f0, df, M, n_samples, session, (size_t)session_bytes, stream);
+    if ((rc = run.prepare(nullptr, nullptr, flux_corr, err_corr))) return rc;
     if ((rc = run.change())) return rc;
     return run.metric(run.at(run.p.mean_unc), metric);
 }

@@ -1422,120 +1422,17 @@ __global__ __launch_bounds__(256) void shared_check_kernel(const double *__restr
     if (bad) atomicOr(flag, bad);
 }
 
-// Workspace: (B + 1) offsets + B Kp^2 normal matrices + B K (K + 1) solver scratch (twice that with w_cov) + B N clip flags +
-// B done words + the partial sums, 16 ceil(B / 16) x S x NC doubles (S <= 16 cadence slices, NC = 16 (ceil(K (K + 1) / 32) +
-// ceil(K / 16)) product columns: 25 MB for 1000 targets at K = 17).  Nothing here has B N K elements.
-int regress_shared_launch(lk_handle *h, int B, int N, int K, const double *X, const double *y, const double *err,
-                          const uint8_t *cmask, const double *prior_mu, const double *prior_sigma, double clip_sigma, int niters,
-                          double *w, double *model, uint8_t *outl, double *w_cov, hipStream_t stream) {
-    LK_REQUIRE(B >= 0, "bad batch description");
-    if (B == 0) return LK_OK;
-    LK_REQUIRE(K >= 1, "K must be >= 1 (got %d)", K);
-    LK_REQUIRE(K <= SH_KMAX,
-               "K=%d: the shared-matrix regression takes at most %d columns; wider matrices go through lk_regress_batch "
-               "(one design matrix per target)", K, SH_KMAX);
-    LK_REQUIRE(B <= 65535, "at most 65535 targets per call on this path (got %d): split the batch", B);
-    LK_REQUIRE(N >= 1 && N < (1 << 30), "N=%d cadences outside 1..2^30", N);
-    LK_REQUIRE(X && y && w && model && outl, "NULL buffer");
-    LK_REQUIRE((prior_mu == nullptr) == (prior_sigma == nullptr), "Please specify both `prior_mu` and `prior_sigma`");
-    LK_REQUIRE(niters >= 1, "niters must be >= 1");
-    const size_t ntot = (size_t)B * N;
-    const int KB = (K + 1 + GR_BLK - 1) / GR_BLK, Kp = KB * GR_BLK;
-    int S = 1, slice = N;
-    shared_split(N, &S, &slice);
-    const int ntb = (B + SH_TB - 1) / SH_TB, npairs = K * (K + 1) / 2, T = (npairs + 15) / 16 + (K + 15) / 16, NC = 16 * T;
-    std::vector<int64_t> off((size_t)B + 1);
-    for (int b = 0; b <= B; ++b) off[b] = (int64_t)b * N;
-    int64_t *d_off;
-    double *d_G, *d_A, *d_part;
-    uint8_t *d_flag;
-    int *d_done, *d_bad;
-    Scratch ws(h, h->ws);
-    ws.upload(d_off, off.data(), B + 1)
-        .buf(d_G, (size_t)B * Kp * Kp)
-        .buf(d_A, (size_t)B * K * (K + 1) * (w_cov ? 2 : 1))
-        .buf(d_flag, ntot).buf(d_done, B)
-        .buf(d_part, (size_t)ntb * SH_TB * S * NC)
-        .buf(d_bad, 1);
-    if (const int rc = ws.carve(stream)) return rc;
-    // the input check first: its answer is back before the fit is queued
-    LK_HIP_CHECK(hipMemsetAsync(d_bad, 0, 4, stream));
-    {
-        const int gx = (int)std::min<size_t>((ntot + 1023) / 1024, 2048);
-        hipLaunchKernelGGL(shared_check_kernel, dim3(gx), dim3(256), 0, stream, y, err, ntot, d_bad);
-        LK_HIP_CHECK(hipGetLastError());
-        int bad = 0;
-        LK_HIP_CHECK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, stream));
-        LK_HIP_CHECK(hipStreamSynchronize(stream));
-        LK_REQUIRE(!(bad & 1), "Input light curve has NaNs in the flux");
-        LK_REQUIRE(!(bad & 2), "Input light curve has NaN, infinite, zero or negative flux errors");
-    }
-    LK_HIP_CHECK(hipMemsetAsync(outl, 0, ntot, stream));
-    LK_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)B * 4, stream));
-    const int ns = (T + 7) / 8;
-    const size_t solve_lds = ((size_t)K * (K + 1) + 2 * K + 2 * SOLVE_NW + 2) * 8;  // (<= 35 KB for K <= 64)
-    {
-        const int rc_ = want_lds(h, reinterpret_cast<const void *>(solve_lds_kernel), 160 * 1024);
-        if (rc_) return rc_;
-    }
-    const size_t model_lds = ((size_t)MS_CB * (K + 1) + (size_t)K * MS_TB) * 8;
-    for (int it = 0; it < niters; ++it) {
-        // every pass recomputes the Gram in full: it re-reads only the targets' own arrays (18 bytes per cadence)
-#define SH_GO(NS_)                                                                                                        \
-    hipLaunchKernelGGL(gram_shared_kernel<NS_>, dim3(ntb, S), dim3(SH_NT), 0, stream, X, y, err, cmask, (const uint8_t *)outl, B, \
-                       N, K, slice, d_part, (const int *)d_done)
-        if (ns <= 1) SH_GO(1);
-        else if (ns <= 2) SH_GO(2);
-        else if (ns <= 3) SH_GO(3);
-        else if (ns <= 4) SH_GO(4);
-        else if (ns <= 6) SH_GO(6);
-        else if (ns <= 8) SH_GO(8);
-        else if (ns <= 12) SH_GO(12);
-        else SH_GO(17);
-#undef SH_GO
-        hipLaunchKernelGGL(gram_shared_reduce_kernel, dim3(B), dim3(256), 0, stream, (const double *)d_part, S, K, Kp, d_G,
-                           (const int *)d_done);
-        hipLaunchKernelGGL(solve_lds_kernel, dim3(B), dim3(SOLVE_NT), solve_lds, stream, d_G, K, Kp, prior_mu, prior_sigma, w,
-                           (const int *)d_done);
-        hipLaunchKernelGGL(model_shared_kernel, dim3((N + MS_CB - 1) / MS_CB, (B + MS_TB - 1) / MS_TB), dim3(256), model_lds, stream,
-                           X, (const double *)w, B, N, K, model, (const int *)d_done);
-        hipLaunchKernelGGL(clip_kernel, dim3(B), dim3(1024), 0, stream, y, model, d_off, clip_sigma, 5, d_flag, outl, d_done,
-                           (int *)nullptr, (int *)nullptr, 0);
-    }
-    hipLaunchKernelGGL(demedian_kernel, dim3(B), dim3(1024), 0, stream, d_off, model);
-    if (w_cov) hipLaunchKernelGGL(invert_kernel, dim3(B), dim3(256), 0, stream, d_G, K, Kp, prior_sigma, d_A, w_cov);
-    LK_HIP_CHECK(hipGetLastError());
-    return LK_OK;
-}
-
 // CBVCorrector.correct_gaussian_prior's prior (reference cbvcorrector.py:333-395): mu = 0 and one ridge width per target,
 // sigma_b = numpy.median(flux_err_b) / sqrt(|alpha_b|), on every column; alpha_b = alphas[b], or `alpha` for every target
-// when alphas == NULL (the same two operations either way: a row has the same bits).  One workgroup per target.
-__global__ __launch_bounds__(1024) void ridge_prior_kernel(const double *__restrict__ err, int N, int K, double alpha,
-                                                           const double *__restrict__ alphas, double *__restrict__ mu,
-                                                           double *__restrict__ sg) {
+// when alphas == NULL (the same two operations either way: a row has the same bits).  One workgroup per target.  Target b's errors
+// are err[n_off[b] .. n_off[b + 1]) and the median is over its own cadences; n_off == NULL: a uniform batch, err[b N .. (b + 1) N).
+__global__ __launch_bounds__(1024) void ridge_prior_kernel(const double *__restrict__ err, const int64_t *__restrict__ n_off, int N,
+                                                           int K, double alpha, const double *__restrict__ alphas,
+                                                           double *__restrict__ mu, double *__restrict__ sg) {
     __shared__ unsigned long long sh[1024];
     const int b = blockIdx.x;
-    const double *e = err + (size_t)b * N;
-    auto val = [&](int i) { return e[i]; };
-    auto keep = [&](int) { return true; };
-    const double med = block_median(N, (long long)N, val, keep, sh);
-    const double s = med / sqrt(fabs(alphas ? alphas[b] : alpha));
-    for (int k = threadIdx.x; k < K; k += 1024) {
-        mu[(size_t)b * K + k] = 0.0;
-        sg[(size_t)b * K + k] = s;
-    }
-}
-
-// The same for a ragged batch: target b's errors are err[n_off[b] .. n_off[b + 1]) and the median is over its own cadences, by
-// the same select and the same two operations (a uniform batch gets the bits of ridge_prior_kernel).
-__global__ __launch_bounds__(1024) void ridge_prior_rows_kernel(const double *__restrict__ err, const int64_t *__restrict__ n_off,
-                                                                int K, double alpha, const double *__restrict__ alphas,
-                                                                double *__restrict__ mu, double *__restrict__ sg) {
-    __shared__ unsigned long long sh[1024];
-    const int b = blockIdx.x;
-    const double *e = err + n_off[b];
-    const int N = (int)(n_off[b + 1] - n_off[b]);
+    const double *e = err + (n_off ? (size_t)n_off[b] : (size_t)b * N);
+    if (n_off) N = (int)(n_off[b + 1] - n_off[b]);
     auto val = [&](int i) { return e[i]; };
     auto keep = [&](int) { return true; };
     const double med = block_median(N, (long long)N, val, keep, sh);
@@ -1553,7 +1450,8 @@ int ridge_prior_launch(lk_handle *h, int B, int N, int K, const double *err, dou
     LK_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && K >= 1, "bad shapes");
     LK_REQUIRE(err && prior_mu && prior_sigma, "NULL buffer");
     LK_REQUIRE(alphas || (alpha != 0.0 && alpha == alpha), "alpha must be non-zero (alpha == 0 means no prior: pass NULL priors)");
-    hipLaunchKernelGGL(ridge_prior_kernel, dim3(B), dim3(1024), 0, stream, err, N, K, alpha, alphas, prior_mu, prior_sigma);
+    hipLaunchKernelGGL(ridge_prior_kernel, dim3(B), dim3(1024), 0, stream, err, (const int64_t *)nullptr, N, K, alpha, alphas, prior_mu,
+                       prior_sigma);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }
@@ -1692,6 +1590,126 @@ __global__ __launch_bounds__(256) void model_rows_kernel(const double *__restric
     }
 }
 
+// What both launchers below size their workspace by, and the workspace itself.
+struct SharedShape {
+    int Kp, S, slice, ntb, T, NC;   // padded normal matrix | cadence slices and their length | target tiles | product tiles, columns
+    SharedShape(int B, int N, int K) : Kp((K + 1 + GR_BLK - 1) / GR_BLK * GR_BLK), S(1), slice(N), ntb((B + SH_TB - 1) / SH_TB) {
+        shared_split(N, &S, &slice);
+        T = (K * (K + 1) / 2 + 15) / 16 + (K + 15) / 16;
+        NC = 16 * T;
+    }
+};
+struct SharedWs {
+    int64_t *off;
+    double *G, *A, *part;
+    uint8_t *flag;
+    int *done, *bad, *pos = nullptr;
+};
+
+template <bool ROWS>
+static void gram_shared_go(const SharedShape &sh, hipStream_t stream, const double *X, const double *y, const double *err,
+                           const uint8_t *cmask, const uint8_t *outl, int B, int N, int K, const SharedWs &d) {
+#define SH_GO(NS_)                                                                                                              \
+    hipLaunchKernelGGL((gram_shared_kernel<NS_, ROWS>), dim3(sh.ntb, sh.S), dim3(SH_NT), 0, stream, X, y, err, cmask, outl, B, N, K, \
+                       sh.slice, d.part, (const int *)d.done, (const int *)d.pos, ROWS ? (const int64_t *)d.off : nullptr)
+    const int ns = (sh.T + 7) / 8;
+    if (ns <= 1) SH_GO(1);
+    else if (ns <= 2) SH_GO(2);
+    else if (ns <= 3) SH_GO(3);
+    else if (ns <= 4) SH_GO(4);
+    else if (ns <= 6) SH_GO(6);
+    else if (ns <= 8) SH_GO(8);
+    else if (ns <= 12) SH_GO(12);
+    else SH_GO(17);
+#undef SH_GO
+}
+
+// The fit, once a launcher has checked its inputs: B targets of ntot cadences together on the N rows of X.  rows == NULL: every
+// target has all N rows (d.off[b] = b N).  Else target b's cadence i is on row rows[d.off[b] + i], d.pos is the inverse map and
+// nmax the longest target.
+static int shared_fit(lk_handle *h, const SharedShape &sh, const SharedWs &d, int B, int N, int K, size_t ntot, const int32_t *rows,
+                      int64_t nmax, const double *X, const double *y, const double *err, const uint8_t *cmask, const double *prior_mu,
+                      const double *prior_sigma, double clip_sigma, int niters, double *w, double *model, uint8_t *outl, double *w_cov,
+                      hipStream_t stream) {
+    LK_HIP_CHECK(hipMemsetAsync(outl, 0, ntot, stream));
+    LK_HIP_CHECK(hipMemsetAsync(d.done, 0, (size_t)B * 4, stream));
+    const size_t solve_lds = ((size_t)K * (K + 1) + 2 * K + 2 * SOLVE_NW + 2) * 8;  // (<= 35 KB for K <= 64)
+    {
+        const int rc_ = want_lds(h, reinterpret_cast<const void *>(solve_lds_kernel), 160 * 1024);
+        if (rc_) return rc_;
+    }
+    const size_t model_lds = ((size_t)MS_CB * (K + 1) + (size_t)K * MS_TB) * 8;
+    for (int it = 0; it < niters; ++it) {
+        // every pass recomputes the Gram in full: it re-reads only the targets' own arrays (18 bytes per cadence)
+        if (rows)
+            gram_shared_go<true>(sh, stream, X, y, err, cmask, outl, B, N, K, d);
+        else
+            gram_shared_go<false>(sh, stream, X, y, err, cmask, outl, B, N, K, d);
+        hipLaunchKernelGGL(gram_shared_reduce_kernel, dim3(B), dim3(256), 0, stream, (const double *)d.part, sh.S, K, sh.Kp, d.G,
+                           (const int *)d.done);
+        hipLaunchKernelGGL(solve_lds_kernel, dim3(B), dim3(SOLVE_NT), solve_lds, stream, d.G, K, sh.Kp, prior_mu, prior_sigma, w,
+                           (const int *)d.done);
+        if (rows)
+            hipLaunchKernelGGL(model_rows_kernel, dim3((unsigned)((nmax + 255) / 256), (B + MR_TB - 1) / MR_TB), dim3(256), 0, stream, X,
+                               (const double *)w, rows, (const int64_t *)d.off, B, K, model, (const int *)d.done);
+        else
+            hipLaunchKernelGGL(model_shared_kernel, dim3((N + MS_CB - 1) / MS_CB, (B + MS_TB - 1) / MS_TB), dim3(256), model_lds,
+                               stream, X, (const double *)w, B, N, K, model, (const int *)d.done);
+        hipLaunchKernelGGL(clip_kernel, dim3(B), dim3(1024), 0, stream, y, model, d.off, clip_sigma, 5, d.flag, outl, d.done,
+                           (int *)nullptr, (int *)nullptr, 0);
+    }
+    hipLaunchKernelGGL(demedian_kernel, dim3(B), dim3(1024), 0, stream, d.off, model);
+    if (w_cov) hipLaunchKernelGGL(invert_kernel, dim3(B), dim3(256), 0, stream, d.G, K, sh.Kp, prior_sigma, d.A, w_cov);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+// Workspace: (B + 1) offsets + B Kp^2 normal matrices + B K (K + 1) solver scratch (twice that with w_cov) + B N clip flags +
+// B done words + the partial sums, 16 ceil(B / 16) x S x NC doubles (S <= 16 cadence slices, NC = 16 (ceil(K (K + 1) / 32) +
+// ceil(K / 16)) product columns: 25 MB for 1000 targets at K = 17).  Nothing here has B N K elements.
+int regress_shared_launch(lk_handle *h, int B, int N, int K, const double *X, const double *y, const double *err,
+                          const uint8_t *cmask, const double *prior_mu, const double *prior_sigma, double clip_sigma, int niters,
+                          double *w, double *model, uint8_t *outl, double *w_cov, hipStream_t stream) {
+    LK_REQUIRE(B >= 0, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(K >= 1, "K must be >= 1 (got %d)", K);
+    LK_REQUIRE(K <= SH_KMAX,
+               "K=%d: the shared-matrix regression takes at most %d columns; wider matrices go through lk_regress_batch "
+               "(one design matrix per target)", K, SH_KMAX);
+    LK_REQUIRE(B <= 65535, "at most 65535 targets per call on this path (got %d): split the batch", B);
+    LK_REQUIRE(N >= 1 && N < (1 << 30), "N=%d cadences outside 1..2^30", N);
+    LK_REQUIRE(X && y && w && model && outl, "NULL buffer");
+    LK_REQUIRE((prior_mu == nullptr) == (prior_sigma == nullptr), "Please specify both `prior_mu` and `prior_sigma`");
+    LK_REQUIRE(niters >= 1, "niters must be >= 1");
+    const size_t ntot = (size_t)B * N;
+    const SharedShape sh(B, N, K);
+    std::vector<int64_t> off((size_t)B + 1);
+    for (int b = 0; b <= B; ++b) off[b] = (int64_t)b * N;
+    SharedWs d;
+    Scratch ws(h, h->ws);
+    ws.upload(d.off, off.data(), B + 1)
+        .buf(d.G, (size_t)B * sh.Kp * sh.Kp)
+        .buf(d.A, (size_t)B * K * (K + 1) * (w_cov ? 2 : 1))
+        .buf(d.flag, ntot).buf(d.done, B)
+        .buf(d.part, (size_t)sh.ntb * SH_TB * sh.S * sh.NC)
+        .buf(d.bad, 1);
+    if (const int rc = ws.carve(stream)) return rc;
+    // the input check first: its answer is back before the fit is queued
+    LK_HIP_CHECK(hipMemsetAsync(d.bad, 0, 4, stream));
+    {
+        const int gx = (int)std::min<size_t>((ntot + 1023) / 1024, 2048);
+        hipLaunchKernelGGL(shared_check_kernel, dim3(gx), dim3(256), 0, stream, y, err, ntot, d.bad);
+        LK_HIP_CHECK(hipGetLastError());
+        int bad = 0;
+        LK_HIP_CHECK(hipMemcpyAsync(&bad, d.bad, 4, hipMemcpyDeviceToHost, stream));
+        LK_HIP_CHECK(hipStreamSynchronize(stream));
+        LK_REQUIRE(!(bad & 1), "Input light curve has NaNs in the flux");
+        LK_REQUIRE(!(bad & 2), "Input light curve has NaN, infinite, zero or negative flux errors");
+    }
+    return shared_fit(h, sh, d, B, N, K, ntot, nullptr, 0, X, y, err, cmask, prior_mu, prior_sigma, clip_sigma, niters, w, model, outl,
+                      w_cov, stream);
+}
+
 // Workspace: regress_shared_launch's with sum n in place of B N, plus the inverse map pos (B Nx int32: 80 MB for 1000 targets
 // on 20 000 rows).
 int regress_shared_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, const int32_t *rows, int Nx, int K, const double *X,
@@ -1712,74 +1730,35 @@ int regress_shared_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, c
     int64_t nmax = 0;
     if (const int rc = ragged_offsets(B, n_off_host, &nmax)) return rc;
     const size_t ntot = (size_t)n_off_host[B];
-    const int KB = (K + 1 + GR_BLK - 1) / GR_BLK, Kp = KB * GR_BLK;
-    int S = 1, slice = Nx;
-    shared_split(Nx, &S, &slice);
-    const int ntb = (B + SH_TB - 1) / SH_TB, npairs = K * (K + 1) / 2, T = (npairs + 15) / 16 + (K + 15) / 16, NC = 16 * T;
+    const SharedShape sh(B, Nx, K);
     const int init[2] = {0, INT_MAX};  // input-check flags | first target with bad rows
-    int64_t *d_off;
-    double *d_G, *d_A, *d_part;
-    uint8_t *d_flag;
-    int *d_done, *d_bad, *d_pos;
+    SharedWs d;
     Scratch ws(h, h->ws);
-    ws.upload(d_off, n_off_host, (size_t)B + 1)
-        .buf(d_G, (size_t)B * Kp * Kp)
-        .buf(d_A, (size_t)B * K * (K + 1) * (w_cov ? 2 : 1))
-        .buf(d_flag, ntot).buf(d_done, B)
-        .buf(d_part, (size_t)ntb * SH_TB * S * NC)
-        .buf(d_pos, (size_t)B * Nx)
-        .upload(d_bad, init, 2);
+    ws.upload(d.off, n_off_host, (size_t)B + 1)
+        .buf(d.G, (size_t)B * sh.Kp * sh.Kp)
+        .buf(d.A, (size_t)B * K * (K + 1) * (w_cov ? 2 : 1))
+        .buf(d.flag, ntot).buf(d.done, B)
+        .buf(d.part, (size_t)sh.ntb * SH_TB * sh.S * sh.NC)
+        .buf(d.pos, (size_t)B * Nx)
+        .upload(d.bad, init, 2);
     if (const int rc = ws.carve(stream)) return rc;
     // the rows and the input check first: their answers are back before the fit is queued
-    LK_HIP_CHECK(hipMemsetAsync(d_pos, 0xff, (size_t)B * Nx * 4, stream));  // -1: the target has no cadence at that row
+    LK_HIP_CHECK(hipMemsetAsync(d.pos, 0xff, (size_t)B * Nx * 4, stream));  // -1: the target has no cadence at that row
     {
         hipLaunchKernelGGL(rows_pos_kernel, dim3((unsigned)((nmax + 255) / 256), B), dim3(256), 0, stream, rows,
-                           (const int64_t *)d_off, Nx, d_pos, d_bad + 1);
+                           (const int64_t *)d.off, Nx, d.pos, d.bad + 1);
         const int gx = (int)std::min<size_t>((ntot + 1023) / 1024, 2048);
-        hipLaunchKernelGGL(shared_check_kernel, dim3(gx), dim3(256), 0, stream, y, err, ntot, d_bad);
+        hipLaunchKernelGGL(shared_check_kernel, dim3(gx), dim3(256), 0, stream, y, err, ntot, d.bad);
         LK_HIP_CHECK(hipGetLastError());
         int bad[2] = {0, 0};
-        LK_HIP_CHECK(hipMemcpyAsync(bad, d_bad, 8, hipMemcpyDeviceToHost, stream));
+        LK_HIP_CHECK(hipMemcpyAsync(bad, d.bad, 8, hipMemcpyDeviceToHost, stream));
         LK_HIP_CHECK(hipStreamSynchronize(stream));
         LK_REQUIRE(bad[1] == INT_MAX, "target %d: rows must be strictly increasing indices into the %d rows of X", bad[1], Nx);
         LK_REQUIRE(!(bad[0] & 1), "Input light curve has NaNs in the flux");
         LK_REQUIRE(!(bad[0] & 2), "Input light curve has NaN, infinite, zero or negative flux errors");
     }
-    LK_HIP_CHECK(hipMemsetAsync(outl, 0, ntot, stream));
-    LK_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)B * 4, stream));
-    const int ns = (T + 7) / 8;
-    const size_t solve_lds = ((size_t)K * (K + 1) + 2 * K + 2 * SOLVE_NW + 2) * 8;  // (<= 35 KB for K <= 64)
-    {
-        const int rc_ = want_lds(h, reinterpret_cast<const void *>(solve_lds_kernel), 160 * 1024);
-        if (rc_) return rc_;
-    }
-    for (int it = 0; it < niters; ++it) {
-#define SHR_GO(NS_)                                                                                                            \
-    hipLaunchKernelGGL((gram_shared_kernel<NS_, true>), dim3(ntb, S), dim3(SH_NT), 0, stream, X, y, err, cmask,                 \
-                       (const uint8_t *)outl, B, Nx, K, slice, d_part, (const int *)d_done, (const int *)d_pos,               \
-                       (const int64_t *)d_off)
-        if (ns <= 1) SHR_GO(1);
-        else if (ns <= 2) SHR_GO(2);
-        else if (ns <= 3) SHR_GO(3);
-        else if (ns <= 4) SHR_GO(4);
-        else if (ns <= 6) SHR_GO(6);
-        else if (ns <= 8) SHR_GO(8);
-        else if (ns <= 12) SHR_GO(12);
-        else SHR_GO(17);
-#undef SHR_GO
-        hipLaunchKernelGGL(gram_shared_reduce_kernel, dim3(B), dim3(256), 0, stream, (const double *)d_part, S, K, Kp, d_G,
-                           (const int *)d_done);
-        hipLaunchKernelGGL(solve_lds_kernel, dim3(B), dim3(SOLVE_NT), solve_lds, stream, d_G, K, Kp, prior_mu, prior_sigma, w,
-                           (const int *)d_done);
-        hipLaunchKernelGGL(model_rows_kernel, dim3((unsigned)((nmax + 255) / 256), (B + MR_TB - 1) / MR_TB), dim3(256), 0, stream, X,
-                           (const double *)w, rows, (const int64_t *)d_off, B, K, model, (const int *)d_done);
-        hipLaunchKernelGGL(clip_kernel, dim3(B), dim3(1024), 0, stream, y, model, d_off, clip_sigma, 5, d_flag, outl, d_done,
-                           (int *)nullptr, (int *)nullptr, 0);
-    }
-    hipLaunchKernelGGL(demedian_kernel, dim3(B), dim3(1024), 0, stream, d_off, model);
-    if (w_cov) hipLaunchKernelGGL(invert_kernel, dim3(B), dim3(256), 0, stream, d_G, K, Kp, prior_sigma, d_A, w_cov);
-    LK_HIP_CHECK(hipGetLastError());
-    return LK_OK;
+    return shared_fit(h, sh, d, B, Nx, K, ntot, rows, nmax, X, y, err, cmask, prior_mu, prior_sigma, clip_sigma, niters, w, model, outl,
+                      w_cov, stream);
 }
 
 // alphas: B doubles on the device, or NULL = `alpha` for every target; a uniform batch gets the bits of ridge_prior_launch
@@ -1794,8 +1773,8 @@ int ridge_prior_rows_launch(lk_handle *h, int B, const int64_t *n_off_host, int 
     Scratch ws(h, h->ws);
     ws.upload(d_off, n_off_host, (size_t)B + 1);
     if (const int rc = ws.carve(stream)) return rc;
-    hipLaunchKernelGGL(ridge_prior_rows_kernel, dim3(B), dim3(1024), 0, stream, err, (const int64_t *)d_off, K, alpha, alphas,
-                       prior_mu, prior_sigma);
+    hipLaunchKernelGGL(ridge_prior_kernel, dim3(B), dim3(1024), 0, stream, err, (const int64_t *)d_off, 0, K, alpha, alphas, prior_mu,
+                       prior_sigma);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }
