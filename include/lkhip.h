@@ -1087,6 +1087,50 @@ int lk_pld_gather_ragged_batch_dev(lk_handle *h, int B, int N, int npix, int n, 
 int lk_cube_centroids_batch_dev(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask,
                                 int mask_stride, double column0, double row0, double *col_out, double *row_out, void *stream);
 
+/* lk_cube_centroids_quadratic_batch_dev <- TargetPixelFile.estimate_centroids(aperture_mask, method='quadratic'), i.e.
+ *   lightkurve.utils.centroid_quadratic(data, mask) per cadence of the same resident cubes (ny = npix / nx >= 3, nx >= 3, else
+ *   LK_EINVAL):  z = data * mask (a masked-out finite pixel is 0, a masked-out NaN or inf pixel NaN);  k = nanargmax(z), the first
+ *   flat index of the largest value that is not NaN;  (yy, xx) = divmod(k, nx) clamped into [1, ny - 2] x [1, nx - 2];  the 3 x 3
+ *   patch of z around (yy, xx), row-major;  the least-squares quadratic P = a + b x + c y + d x^2 + e x y + f y^2 over x, y in
+ *   {0, 1, 2} ((A^T A)^-1 A^T is an integer matrix over 36, hard-coded);  det = 4 d f - e^2, |det| < 1e-6 -> NaN, otherwise
+ *   xm = -(2 f b - c e) / det, ym = -(2 d c - b e) / det and col = column0 + xx - 1 + xm, row = row0 + yy - 1 + ym: the pixel-
+ *   index convention of lk_cube_centroids_batch_dev (a symmetric source centred on pixel (i, j) gives (i, j)).  A NaN inside the
+ *   patch gives NaN; a cadence without any value gives NaN and peak -1 (nothing is raised).  All float64 after the float32 load.
+ *   mask / mask_stride as lk_cube_aperture_batch_dev.  col_out / row_out: B x N float64; peak_out (nullable): B x N int32, k
+ *   before the clamp or -1.  One wavefront per cadence, the cube is read once.  Enqueued, no synchronisation.
+ * lk_image_centroids_batch_dev <- the same two estimators (method = LK_CENTROID_MOMENTS: the formula of
+ *   lk_cube_centroids_batch_dev; LK_CENTROID_QUADRATIC: the one above) on B float64 images [B][npix], one wavefront per image.
+ *   col_out / row_out: B float64; peak_out (nullable, B int32): the quadratic's k, -1 for the moments.  Enqueued.
+ * lk_cube_diffimage_batch_dev <- the transit difference image of every cutout, one box (period, transit_time, duration: HOST
+ *   arrays of B) per cutout.  Cadence i of cutout b with time t has x = np_mod(t - t0 + P/2, P) - P/2 (the expression of
+ *   lk_transit_mask_batch) and the class 1 (in) where |x| < in_width D, 2 (out) where out_inner D <= |x| < out_outer D, 0
+ *   otherwise and for a NaN time.  0 < in_width <= out_inner < out_outer and P != 0, else LK_EINVAL.  Per pixel p, summing the
+ *   float32 values in float64: mean_in / mean_out = the mean of flux[p] over the in / out cadences where it is not NaN (n_in[p],
+ *   n_out[p] of them); diff = mean_out - mean_in; diff_err = sqrt(sum_in e^2 / n_in[p]^2 + sum_out e^2 / n_out[p]^2) with e =
+ *   flux_err[p] at the same cadences (a NaN error there gives NaN).  A pixel with n_in[p] == 0 or n_out[p] == 0 is NaN in every
+ *   image that needs the missing count.  Outputs on the device: cadence_class B x N bytes; mean_in, mean_out, diff, diff_err
+ *   B x npix float64; n_in, n_out B int32 = the CADENCES of each class.  A workgroup sums a chunk of 128 cadences of one cutout
+ *   (lanes = pixels), a second kernel adds the chunks in index order: no floating-point atomics, the order of every sum depends
+ *   on N alone, so a cutout's images have the same bits alone, in any batch and from run to run.  Cadences without a class are
+ *   not read.  Scratch: B x ceil(N / 128) x npix x 40 bytes of the handle's arena.  Enqueued, no synchronisation.
+ * lk_diffimage_offsets_batch_dev <- offset[b] = (diff_col - out_col, diff_row - out_row) (B x 2), offset_pix[b] = its norm and
+ *   status[b] (all on the device): 1 n_in[b] == 0, 2 n_out[b] == 0, 3 a centroid that is NaN, else 0.  Enqueued. */
+#define LK_CENTROID_MOMENTS 0
+#define LK_CENTROID_QUADRATIC 1
+int lk_cube_centroids_quadratic_batch_dev(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask,
+                                          int mask_stride, double column0, double row0, double *col_out, double *row_out,
+                                          int32_t *peak_out, void *stream);
+int lk_image_centroids_batch_dev(lk_handle *h, int B, int npix, int nx, const double *image, const uint8_t *mask, int mask_stride,
+                                 double column0, double row0, int method, double *col_out, double *row_out, int32_t *peak_out,
+                                 void *stream);
+int lk_cube_diffimage_batch_dev(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const float *flux_err,
+                                const double *period, const double *transit_time, const double *duration, double in_width,
+                                double out_inner, double out_outer, uint8_t *cadence_class, double *mean_in, double *mean_out,
+                                double *diff, double *diff_err, int32_t *n_in, int32_t *n_out, void *stream);
+int lk_diffimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *n_in, const int32_t *n_out, const double *diff_col,
+                                   const double *diff_row, const double *out_col, const double *out_row, double *offset,
+                                   double *offset_pix, int32_t *status, void *stream);
+
 /* ---- SFFCorrector.correct (self-flat-fielding, the K2 roll-motion correction; reference lightkurve 2.x
  * src/lightkurve/correctors/sffcorrector.py) for B ragged light curves.  Per target, all float64, inputs finite:
  *   f = flux / median(flux), e = flux_err / median(flux); raw_mean = mean(flux);

@@ -10,7 +10,7 @@ from . import packed
 
 __all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch", "fill_gaps_batch",
            "periodogram_peaks", "flatten_batch",
-           "estimate_cdpp_batch", "pld_correct_batch", "regression_correct_batch", "cbv_correct_batch"]
+           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "regression_correct_batch", "cbv_correct_batch"]
 
 
 def _resolve_device(device):
@@ -367,6 +367,14 @@ def pld_correct_batch(cubes, gather=True, device=0, ragged_masks=False, **kwargs
     else:
         out = sharded_map(cubes, compute, gather=gather)
     return out[:, 0], out[:, 1] != 0.0
+
+
+def difference_images_batch(cubes, period, transit_time, duration, device=0, **kwargs):
+    """``PixelCube.difference_image`` of every cutout, for host cutouts: ``cubes`` a list of same-shaped float32 ``PixelCube``s,
+    ``period`` / ``transit_time`` / ``duration`` scalars or one value per cutout.  One upload (``DevicePixelCubeBatch.from_cubes``),
+    then ``DevicePixelCubeBatch.difference_images`` with its keywords and its dict of host arrays.  Not sharded over ranks."""
+    from .device import DevicePixelCubeBatch
+    return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).difference_images(period, transit_time, duration, **kwargs)
 
 
 def regression_correct_batch(lcs, design_matrices, cadence_masks=None, sigma=5, niters=5, device=0, gather=True):

@@ -17,7 +17,73 @@ from .regressioncorrector import RegressionCorrector
 
 log = logging.getLogger(__name__)
 
-__all__ = ["PixelCube", "PLDCorrector", "pld_correct_batch", "threshold_mask_from_median_image"]
+__all__ = ["PixelCube", "PLDCorrector", "pld_correct_batch", "threshold_mask_from_median_image", "centroid_quadratic"]
+
+# (A^T A)^-1 A^T of the 3 x 3 quadratic fit P = a + b x + c y + d x^2 + e x y + f y^2, x fastest, x, y in {0, 1, 2}: these
+# integers over 36, exactly (the table csrc/pixcube.hip carries)
+_QUADRATIC_FIT_36 = np.array([[29, 8, -1, 8, -4, -4, -1, -4, 5], [-27, 24, 3, -18, 24, -6, -9, 24, -15],
+                              [-27, -18, -9, 24, 24, 24, 3, -6, -15], [6, -12, 6, 6, -12, 6, 6, -12, 6],
+                              [9, 0, -9, 0, 0, 0, -9, 0, 9], [6, 6, 6, -12, -12, -12, 6, 6, 6]], dtype=np.float64)
+
+
+def centroid_quadratic(data, mask=None, return_peak=False):
+    """``lightkurve.utils.centroid_quadratic``: the extremum of the quadratic fitted to the 3 x 3 patch around the brightest
+    pixel of ``data * mask`` -> (column, row) in pixel indices (a symmetric source centred on pixel (i, j) gives (i, j)).  The
+    patch is clamped into the image; a NaN inside it, a flat patch (``|det| < 1e-6``) or an image without any value gives
+    (nan, nan) — the reference raises on the last.  ``return_peak`` adds the flat index of the brightest pixel (before the
+    clamp; -1 without one).  The host mirror of ``lk_cube_centroids_quadratic_batch_dev``."""
+    z = np.asarray(data, dtype=np.float64)
+    if z.ndim != 2 or z.shape[0] < 3 or z.shape[1] < 3:
+        raise ValueError("centroid_quadratic needs an image of at least 3 x 3 pixels (got shape {})".format(z.shape))
+    with np.errstate(all="ignore"):
+        if mask is not None:
+            mask = np.asarray(mask, dtype=bool)
+            if mask.shape != z.shape:
+                raise ValueError("`mask` has shape {}, but the image has shape {}".format(mask.shape, z.shape))
+            z = z * mask
+        col = row = np.nan
+        valid = ~np.isnan(z)
+        if not valid.any():
+            return (col, row, -1) if return_peak else (col, row)
+        k = int(np.argmax(np.where(valid, z, -np.inf)))
+        if np.isnan(z.flat[k]):                      # (every value is -inf: argmax may sit on a NaN before the first of them)
+            k = int(np.flatnonzero(valid.ravel())[0])
+        ny, nx = z.shape
+        yy, xx = min(max(k // nx, 1), ny - 2), min(max(k % nx, 1), nx - 2)
+        a, b, c, d, e, f = _QUADRATIC_FIT_36.dot(z[yy - 1:yy + 2, xx - 1:xx + 2].ravel()) / 36.0
+        det = 4 * d * f - e ** 2
+        if not abs(det) < 1e-6:
+            col = xx - 1 + (-(2 * f * b - c * e) / det)
+            row = yy - 1 + (-(2 * d * c - b * e) / det)
+    return (float(col), float(row), k) if return_peak else (float(col), float(row))
+
+
+def _moment_centroids(flux, ap, column=0, row=0):
+    """The moment centroids of the images flux[..., ny, nx] inside the boolean aperture ``ap`` -> (col, row): float64 nansums,
+    a zero or NaN total gives NaN."""
+    yy, xx = np.indices(ap.shape)
+    with np.errstate(all="ignore"):
+        f = np.where(ap, np.asarray(flux, dtype=np.float64), np.nan)
+        tot = np.nansum(f, axis=(-2, -1))
+        tot = np.where(tot == 0, np.nan, tot)
+        return np.nansum((column + xx) * f, axis=(-2, -1)) / tot, np.nansum((row + yy) * f, axis=(-2, -1)) / tot
+
+
+def _transit_classes(time, period, transit_time, duration, in_width=0.5, out_inner=1.0, out_outer=2.0):
+    """uint8 per cadence: 1 in transit (``|x| < in_width * duration``), 2 out of transit (``out_inner * duration <= |x| <
+    out_outer * duration``), 0 otherwise and for a NaN time; x = the phase of ``create_transit_mask``."""
+    if not (0 < in_width <= out_inner < out_outer):
+        raise ValueError("need 0 < in_width <= out_inner < out_outer (got %r, %r, %r)" % (in_width, out_inner, out_outer))
+    period, transit_time, duration = float(period), float(transit_time), float(duration)
+    if not (period != 0 and np.isfinite(period) and np.isfinite(transit_time) and np.isfinite(duration)):
+        raise ValueError("period, transit_time and duration must be finite and the period non-zero")
+    with np.errstate(all="ignore"):
+        hp = period / 2.0
+        x = np.abs(np.mod(np.asarray(time, dtype=np.float64) - transit_time + hp, period) - hp)
+        cls = np.zeros(x.shape, dtype=np.uint8)
+        cls[x < in_width * duration] = 1
+        cls[(x >= out_inner * duration) & (x < out_outer * duration)] = 2
+    return cls
 
 
 def threshold_mask_from_median_image(median_image, threshold=3, reference_pixel="center"):
@@ -133,6 +199,53 @@ class PixelCube(object):
         lc = LightCurve(time=self.time, flux=flux, flux_err=flux_err, meta=dict(self.meta))
         lc._flux_f32 = np.asarray(flux, dtype=np.float32)   # the value the reference carries (float32 for FITS cubes)
         return lc
+
+    def estimate_centroids(self, aperture_mask="all", method="moments", column=0, row=0):
+        """``TargetPixelFile.estimate_centroids(aperture_mask, method)`` -> (col[N], row[N]) float64, ``column`` / ``row`` = the
+        cutout's corner.  'moments': the flux-weighted mean pixel position inside the aperture (nansum; a zero or NaN total
+        gives NaN).  'quadratic': ``centroid_quadratic`` of every cadence (NaN where the reference would raise).  The host
+        mirror of ``DevicePixelCubeBatch.estimate_centroids``."""
+        ap = self._parse_aperture_mask(aperture_mask)
+        if method == "moments":
+            return _moment_centroids(self.flux, ap, column, row)
+        if method != "quadratic":
+            raise ValueError("method must be 'moments' or 'quadratic' (got {!r})".format(method))
+        cr = np.array([centroid_quadratic(im, ap) for im in self.flux], dtype=np.float64).reshape(-1, 2)
+        return column + cr[:, 0], row + cr[:, 1]
+
+    def difference_image(self, period, transit_time, duration, in_width=0.5, out_inner=1.0, out_outer=2.0,
+                         aperture_mask="all", column=0, row=0):
+        """The transit difference image of this cutout and where it sits (the host mirror of
+        ``DevicePixelCubeBatch.difference_images``, in numpy; same keys without the batch axis).  Cadences are classed by the
+        phase of ``create_transit_mask``: in transit where ``|x| < in_width * duration``, out of transit where ``out_inner *
+        duration <= |x| < out_outer * duration``.  ``mean_in`` / ``mean_out``: per-pixel nanmean over each class; ``diff`` =
+        mean_out - mean_in (positive where the dimming is); ``diff_err`` from ``flux_err`` over the same values.
+        ``centroid_diff`` / ``centroid_out`` (quadratic) and ``..._moments``: (col, row) inside ``aperture_mask``; ``offset`` =
+        centroid_diff - centroid_out, ``offset_pix`` its norm.  ``status``: 0 ok, 1 no in-transit cadence, 2 no out-of-transit
+        cadence, 3 centroid undefined."""
+        ap = self._parse_aperture_mask(aperture_mask)
+        cls = _transit_classes(self.time, period, transit_time, duration, in_width, out_inner, out_outer)
+        flux = np.asarray(self.flux, dtype=np.float64)
+        err2 = np.asarray(self.flux_err, dtype=np.float64) ** 2
+        out = {"cadence_class": cls, "n_in": int(np.sum(cls == 1)), "n_out": int(np.sum(cls == 2))}
+        with np.errstate(all="ignore"):
+            part = {}
+            for name, sel in (("in", cls == 1), ("out", cls == 2)):
+                f = flux[sel]
+                ok = ~np.isnan(f)
+                n = ok.sum(axis=0).astype(np.float64)
+                part[name] = (np.where(ok, f, 0.0).sum(axis=0) / n, np.where(ok, err2[sel], 0.0).sum(axis=0) / (n * n))
+            out["mean_in"], out["mean_out"] = part["in"][0], part["out"][0]
+            out["diff"] = out["mean_out"] - out["mean_in"]
+            out["diff_err"] = np.sqrt(part["in"][1] + part["out"][1])
+        for key, im in (("diff", out["diff"]), ("out", out["mean_out"])):
+            c, r = centroid_quadratic(im, ap)
+            out["centroid_" + key] = np.array([column + c, row + r])
+            out["centroid_%s_moments" % key] = np.array([v[0] for v in _moment_centroids(im[None], ap, column, row)])
+        out["offset"] = out["centroid_diff"] - out["centroid_out"]
+        out["offset_pix"] = float(np.sqrt(np.sum(out["offset"] ** 2)))
+        out["status"] = 1 if out["n_in"] == 0 else 2 if out["n_out"] == 0 else 3 if np.isnan(out["offset_pix"]) else 0
+        return out
 
 
     def _aperture_sums(self, ap):

@@ -2178,6 +2178,45 @@ int lk_cube_centroids_batch_dev(lk_handle *h, int B, int N, int npix, int nx, co
                                      static_cast<hipStream_t>(stream));
 }
 
+// ------------------------------------------------------------------------------------------------ quadratic centroids, difference images
+int lk_cube_centroids_quadratic_batch_dev(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask,
+                                          int mask_stride, double column0, double row0, double *col_out, double *row_out,
+                                          int32_t *peak_out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_centroids_quadratic_launch(h, B, N, npix, nx, flux, mask, mask_stride, column0, row0, col_out, row_out,
+                                               peak_out, static_cast<hipStream_t>(stream));
+}
+
+int lk_image_centroids_batch_dev(lk_handle *h, int B, int npix, int nx, const double *image, const uint8_t *mask, int mask_stride,
+                                 double column0, double row0, int method, double *col_out, double *row_out, int32_t *peak_out,
+                                 void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::image_centroids_launch(h, B, npix, nx, image, mask, mask_stride, column0, row0, method, col_out, row_out, peak_out,
+                                      static_cast<hipStream_t>(stream));
+}
+
+int lk_cube_diffimage_batch_dev(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const float *flux_err,
+                                const double *period, const double *transit_time, const double *duration, double in_width,
+                                double out_inner, double out_outer, uint8_t *cadence_class, double *mean_in, double *mean_out,
+                                double *diff, double *diff_err, int32_t *n_in, int32_t *n_out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_diffimage_launch(h, B, N, npix, time, flux, flux_err, period, transit_time, duration, in_width, out_inner,
+                                     out_outer, cadence_class, mean_in, mean_out, diff, diff_err, n_in, n_out,
+                                     static_cast<hipStream_t>(stream));
+}
+
+int lk_diffimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *n_in, const int32_t *n_out, const double *diff_col,
+                                   const double *diff_row, const double *out_col, const double *out_row, double *offset,
+                                   double *offset_pix, int32_t *status, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::diffimage_offsets_launch(h, B, n_in, n_out, diff_col, diff_row, out_col, out_row, offset, offset_pix, status,
+                                        static_cast<hipStream_t>(stream));
+}
+
 int lk_sff_scratch_bytes(int B, const int64_t *n_off, const int32_t *n_knots, const int32_t *win_off, int bins, int degree,
                          int64_t max_scratch_bytes, int64_t *bytes, int *n_chunks) {
     return lk::sff_scratch_bytes(B, n_off, n_knots, win_off, bins, degree, max_scratch_bytes, bytes, n_chunks);

@@ -389,6 +389,22 @@ int pld_corrected_launch(lk_handle *h, int B, int N, const double *y, const doub
 // pixcube.hip: TargetPixelFile.estimate_centroids(method='moments') per cadence of every cutout
 int cube_centroids_launch(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask, int mask_stride,
                           double column0, double row0, double *col_out, double *row_out, hipStream_t stream);
+// pixcube.hip: estimate_centroids(method='quadratic') per cadence (peak_out nullable); either estimator on B float64 images
+int cube_centroids_quadratic_launch(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask,
+                                    int mask_stride, double column0, double row0, double *col_out, double *row_out,
+                                    int32_t *peak_out, hipStream_t stream);
+int image_centroids_launch(lk_handle *h, int B, int npix, int nx, const double *image, const uint8_t *mask, int mask_stride,
+                           double column0, double row0, int method, double *col_out, double *row_out, int32_t *peak_out,
+                           hipStream_t stream);
+// pixcube.hip: the transit difference images of B resident cutouts, one box per cutout (host arrays); then the centroid offsets
+// and statuses.  Everything else on the device; enqueued, no synchronisation
+int cube_diffimage_launch(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const float *flux_err,
+                          const double *period_host, const double *transit_time_host, const double *duration_host, double in_width,
+                          double out_inner, double out_outer, uint8_t *cls, double *mean_in, double *mean_out, double *diff,
+                          double *diff_err, int32_t *n_in, int32_t *n_out, hipStream_t stream);
+int diffimage_offsets_launch(lk_handle *h, int B, const int32_t *n_in, const int32_t *n_out, const double *diff_col,
+                             const double *diff_row, const double *out_col, const double *out_row, double *offset,
+                             double *offset_pix, int32_t *status, hipStream_t stream);
 // sff.hip: SFFCorrector for a ragged resident batch.  The regression launcher owns h->ws, so the design matrices and everything
 // else that lives across it sit in `scratch`, a device block of the caller's (sff_scratch_bytes); status_host is valid on
 // return (the call synchronises once, to group the targets by their design width)

@@ -4,6 +4,9 @@
 //                   src/lightkurve/targetpixelfile.py:868-923) + the NaN-cadence flags of PLDCorrector.__init__
 //                   (correctors/pldcorrector.py:109-120);
 //   cube_centroids  the moment centroids of TargetPixelFile.estimate_centroids (what SFFCorrector's arclength is made from);
+//   cube_centroids_quadratic   the same method's 'quadratic' estimator (lightkurve.utils.centroid_quadratic) per cadence;
+//   cube_diffimage  the transit difference image of every cutout (mean out-of-transit minus mean in-transit image, with its
+//                   error image) and image_centroids, both estimators on such float64 images;
 //   cube_median     the per-pixel nanmedian image behind create_threshold_mask (targetpixelfile.py:680-742);
 //   cube_compact / cube_gather   the compaction tpf[~nan_mask], the pixel series of the PLD / background apertures
 //                   (pldcorrector.py:203-227) and the spline's percentile knots;
@@ -15,6 +18,7 @@
 #include <algorithm>
 
 #include "block_select.hpp"
+#include "fold_phase.hpp"  // np_mod: the difference image classes its cadences by create_transit_mask's phase
 
 namespace lk {
 
@@ -142,19 +146,14 @@ __global__ __launch_bounds__(256) void cube_aperture_kernel(const float *__restr
 // weighted mean pixel position inside the aperture, col = sum_p (column0 + x_p) m_p flux_p / sum_p m_p flux_p and likewise
 // for row, summed in float64 with NaN pixels counting as 0 (nansum); a total that is zero or NaN gives NaN.  One wavefront
 // per cadence: lane l adds the pixels l, l + 64, ... in that order and the 64 lane sums are added in a butterfly, so the
-// order of every sum depends on npix alone.  Pixel p sits at x_p = p % nx, y_p = p / nx.
-__global__ __launch_bounds__(256) void cube_centroids_kernel(const float *__restrict__ flux, const uint8_t *__restrict__ mask,
-                                                             int mask_stride, int N, int npix, int nx, double column0,
-                                                             double row0, double *__restrict__ col_out,
-                                                             double *__restrict__ row_out) {
-    const int b = blockIdx.y, lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= N) return;
-    const float *img = flux + ((size_t)b * N + i) * npix;
-    const uint8_t *m = mask + (size_t)b * mask_stride;
+// order of every sum depends on npix alone.  Pixel p sits at x_p = p % nx, y_p = p / nx.  T: float (a cadence of a cube) or
+// double (a difference image); every lane of the wavefront returns the result.
+template <class T>
+__device__ __forceinline__ void wave_centroid_moments(const T *__restrict__ img, const uint8_t *__restrict__ m, int npix, int nx,
+                                                      double column0, double row0, int lane, double &col, double &row) {
     double tot = 0.0, sx = 0.0, sy = 0.0;
     for (int p = lane; p < npix; p += 64) {
-        const float v = img[p];
+        const T v = img[p];
         if (m[p] && !isnan(v)) {
             const int y = p / nx, x = p - y * nx;
             const double d = (double)v;
@@ -168,12 +167,245 @@ __global__ __launch_bounds__(256) void cube_centroids_kernel(const float *__rest
         sx = sx + __shfl_xor(sx, o);
         sy = sy + __shfl_xor(sy, o);
     }
+    const bool ok = tot == tot && tot != 0.0;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    col = ok ? sx / tot : nan;
+    row = ok ? sy / tot : nan;
+}
+
+__global__ __launch_bounds__(256) void cube_centroids_kernel(const float *__restrict__ flux, const uint8_t *__restrict__ mask,
+                                                             int mask_stride, int N, int npix, int nx, double column0,
+                                                             double row0, double *__restrict__ col_out,
+                                                             double *__restrict__ row_out) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= N) return;
+    double col, row;
+    wave_centroid_moments(flux + ((size_t)b * N + i) * npix, mask + (size_t)b * mask_stride, npix, nx, column0, row0, lane, col,
+                          row);
     if (lane == 0) {
-        const bool ok = tot == tot && tot != 0.0;
-        const double nan = __longlong_as_double(0x7ff8000000000000ll);
-        col_out[(size_t)b * N + i] = ok ? sx / tot : nan;
-        row_out[(size_t)b * N + i] = ok ? sy / tot : nan;
+        col_out[(size_t)b * N + i] = col;
+        row_out[(size_t)b * N + i] = row;
     }
+}
+
+// lightkurve.utils.centroid_quadratic(data, mask) (TargetPixelFile.estimate_centroids(method='quadratic')) of one (ny, nx) image
+// by one wavefront.  z = data * mask (a masked-out finite pixel is 0, a masked-out NaN / inf pixel NaN); k = nanargmax(z), the
+// FIRST flat index of the largest value that is not NaN: lane l scans the pixels l, l + 64, ... and keeps (value, first index),
+// and the 64 pairs meet in a butterfly whose order is (larger value, then smaller index), so k does not depend on how the pixels
+// fell on the lanes.  (yy, xx) = divmod(k, nx) clamped into [1, ny - 2] x [1, nx - 2]; nine lanes fetch the 3 x 3 patch of z
+// around it (row-major, x fastest) and every lane fits P = a + b x + c y + d x^2 + e x y + f y^2 through (A^T A)^-1 A^T, which
+// for x, y in {0, 1, 2} is exactly the integer table below over 36; det = 4 d f - e^2, |det| < 1e-6 -> NaN, else the extremum
+// xm = -(2 f b - c e) / det, ym = -(2 d c - b e) / det and col = column0 + xx - 1 + xm, row = row0 + yy - 1 + ym (the pixel-index
+// convention of the moments: a symmetric source centred on pixel (i, j) gives (i, j)).  A NaN in the patch gives NaN through
+// the arithmetic; no pixel that is not NaN gives NaN and peak = -1.  peak = k, before the clamp.  All float64, no contraction.
+template <class T>
+__device__ __forceinline__ void wave_centroid_quadratic(const T *__restrict__ img, const uint8_t *__restrict__ m, int npix, int nx,
+                                                        double column0, double row0, int lane, double &col, double &row,
+                                                        int &peak) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double best = 0.0;
+    int bi = -1;
+    for (int p = lane; p < npix; p += 64) {
+        const double z = (double)img[p] * (m[p] ? 1.0 : 0.0);
+        if (z == z && (bi < 0 || z > best)) {
+            best = z;
+            bi = p;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bi, o);
+        if (oi >= 0 && (bi < 0 || ob > best || (ob == best && oi < bi))) {
+            best = ob;
+            bi = oi;
+        }
+    }
+    peak = bi;
+    col = row = nan;
+    if (bi < 0) return;  // (the whole wavefront)
+    const int ny = npix / nx;
+    const int yy = min(max(bi / nx, 1), ny - 2), xx = min(max(bi % nx, 1), nx - 2);
+    double zl = 0.0;
+    if (lane < 9) {
+        const int q = (yy - 1 + lane / 3) * nx + xx - 1 + lane % 3;
+        zl = (double)img[q] * (m[q] ? 1.0 : 0.0);
+    }
+    const double w[6][9] = {{29, 8, -1, 8, -4, -4, -1, -4, 5},      {-27, 24, 3, -18, 24, -6, -9, 24, -15},
+                            {-27, -18, -9, 24, 24, 24, 3, -6, -15}, {6, -12, 6, 6, -12, 6, 6, -12, 6},
+                            {9, 0, -9, 0, 0, 0, -9, 0, 9},          {6, 6, 6, -12, -12, -12, 6, 6, 6}};
+    double c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        const double z = __shfl(zl, j);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) c[k] = c[k] + w[k][j] * z;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c[k] = c[k] / 36.0;
+    const double b1 = c[1], c1 = c[2], d = c[3], e = c[4], f = c[5];
+    const double det = 4.0 * d * f - e * e;
+    if (fabs(det) < 1e-6) return;
+    const double xm = -(2.0 * f * b1 - c1 * e) / det, ym = -(2.0 * d * c1 - b1 * e) / det;
+    col = ((column0 + (double)xx) - 1.0) + xm;
+    row = ((row0 + (double)yy) - 1.0) + ym;
+}
+
+// One wavefront per cadence, the mapping of cube_centroids_kernel: the cube is read once, coalesced; peak_out is nullable.
+__global__ __launch_bounds__(256) void cube_centroids_quadratic_kernel(const float *__restrict__ flux,
+                                                                       const uint8_t *__restrict__ mask, int mask_stride, int N,
+                                                                       int npix, int nx, double column0, double row0,
+                                                                       double *__restrict__ col_out, double *__restrict__ row_out,
+                                                                       int *__restrict__ peak_out) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= N) return;
+    double col, row;
+    int peak;
+    wave_centroid_quadratic(flux + ((size_t)b * N + i) * npix, mask + (size_t)b * mask_stride, npix, nx, column0, row0, lane, col,
+                            row, peak);
+    if (lane == 0) {
+        col_out[(size_t)b * N + i] = col;
+        row_out[(size_t)b * N + i] = row;
+        if (peak_out) peak_out[(size_t)b * N + i] = peak;
+    }
+}
+
+// Either estimator on B float64 images [B][npix] (the difference images below), one wavefront per image
+__global__ __launch_bounds__(256) void image_centroids_kernel(const double *__restrict__ image, const uint8_t *__restrict__ mask,
+                                                              int mask_stride, int B, int npix, int nx, double column0,
+                                                              double row0, int quadratic, double *__restrict__ col_out,
+                                                              double *__restrict__ row_out, int *__restrict__ peak_out) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= B) return;
+    const double *img = image + (size_t)b * npix;
+    const uint8_t *m = mask + (size_t)b * mask_stride;
+    double col, row;
+    int peak = -1;
+    if (quadratic) wave_centroid_quadratic(img, m, npix, nx, column0, row0, lane, col, row, peak);
+    else wave_centroid_moments(img, m, npix, nx, column0, row0, lane, col, row);
+    if (lane == 0) {
+        col_out[b] = col;
+        row_out[b] = row;
+        if (peak_out) peak_out[b] = peak;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ difference images
+// Per cutout b one box (P, t0, D); par = [P[B] | t0[B] | D[B]].  Cadence i with time t has the phase
+// x = np_mod(t - t0 + P/2, P) - P/2 (create_transit_mask's expression) and the class
+//   1 (in)   |x| < in_width D,      2 (out)  out_inner D <= |x| < out_outer D,      0 (none) otherwise and for a NaN time.
+// n_in[b] / n_out[b] (zeroed by the launcher) count the cadences of the two classes: integer atomics, one per wavefront.
+constexpr int DI_CHUNK = 128;  // cadences per workgroup of the accumulation: the order of every sum depends on N alone
+constexpr int DI_T = 128;      // its lanes: adjacent pixels of one cadence row per load
+
+__global__ __launch_bounds__(256) void cube_diffimage_class_kernel(const double *__restrict__ time, const double *__restrict__ par,
+                                                                   int B, int N, double in_width, double out_inner,
+                                                                   double out_outer, uint8_t *__restrict__ cls,
+                                                                   int *__restrict__ n_in, int *__restrict__ n_out) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    int c = 0;
+    if (i < N) {
+        const double P = par[b], t0 = par[B + b], D = par[2 * B + b], hp = P / 2.0;
+        const double x = fabs(np_mod(time[(size_t)b * N + i] - t0 + hp, P) - hp);
+        c = x < in_width * D ? 1 : (x >= out_inner * D && x < out_outer * D ? 2 : 0);
+        cls[(size_t)b * N + i] = (uint8_t)c;
+    }
+    const unsigned long long bal_in = __ballot(c == 1), bal_out = __ballot(c == 2);
+    if ((threadIdx.x & 63) == 0) {
+        if (bal_in) atomicAdd(&n_in[b], __popcll(bal_in));
+        if (bal_out) atomicAdd(&n_out[b], __popcll(bal_out));
+    }
+}
+
+// Workgroup (chunk, b): the cadences [chunk DI_CHUNK, +DI_CHUNK) of cutout b, lane = pixel (cutouts of more than DI_T pixels
+// take them in groups).  A lane walks its pixel down the chunk's cadences in order and keeps, for the in and the out class,
+// the float64 sum of the float32 flux values that are not NaN, the sum of flux_err^2 over the same cadences and their number:
+// psum[b][chunk][s_in | s_out | e_in | e_out][npix], pcnt[b][chunk][n_in | n_out][npix].  The class is uniform over the
+// workgroup, so the rows of a cadence without a class are not loaded at all; every other row of both cubes is loaded once, as
+// runs of adjacent floats.  No atomics: cube_diffimage_finish_kernel adds the chunks in index order.
+__global__ __launch_bounds__(DI_T) void cube_diffimage_accum_kernel(const float *__restrict__ flux, const float *__restrict__ ferr,
+                                                                    const uint8_t *__restrict__ cls, int N, int npix, int chunks,
+                                                                    double *__restrict__ psum, int *__restrict__ pcnt) {
+    const int b = blockIdx.y, ch = blockIdx.x, c0 = ch * DI_CHUNK, rows = min(DI_CHUNK, N - c0);
+    const uint8_t *cl = cls + (size_t)b * N + c0;
+    const size_t base = ((size_t)b * N + c0) * npix;
+    double *ps = psum + ((size_t)b * chunks + ch) * 4 * npix;
+    int *pc = pcnt + ((size_t)b * chunks + ch) * 2 * npix;
+    for (int p = threadIdx.x; p < npix; p += DI_T) {
+        double s_in = 0.0, s_out = 0.0, e_in = 0.0, e_out = 0.0;
+        int k_in = 0, k_out = 0;
+        for (int j = 0; j < rows; ++j) {
+            const int c = cl[j];
+            if (c == 0) continue;
+            const float v = flux[base + (size_t)j * npix + p], e = ferr[base + (size_t)j * npix + p];
+            if (isnan(v)) continue;
+            const double d = (double)v, q = (double)e * (double)e;
+            if (c == 1) {
+                s_in = s_in + d;
+                e_in = e_in + q;
+                ++k_in;
+            } else {
+                s_out = s_out + d;
+                e_out = e_out + q;
+                ++k_out;
+            }
+        }
+        ps[p] = s_in;
+        ps[npix + p] = s_out;
+        ps[2 * npix + p] = e_in;
+        ps[3 * npix + p] = e_out;
+        pc[p] = k_in;
+        pc[npix + p] = k_out;
+    }
+}
+
+// One thread per pixel: the chunks' partials added in index order, then mean_in = s_in / n_in, mean_out = s_out / n_out,
+// diff = mean_out - mean_in (positive where the dimming is) and diff_err = sqrt(e_in / n_in^2 + e_out / n_out^2).  A pixel
+// without a value in a class has 0 / 0 = NaN in every image that needs that class.
+__global__ __launch_bounds__(256) void cube_diffimage_finish_kernel(const double *__restrict__ psum, const int *__restrict__ pcnt,
+                                                                    int npix, int chunks, double *__restrict__ mean_in,
+                                                                    double *__restrict__ mean_out, double *__restrict__ diff,
+                                                                    double *__restrict__ diff_err) {
+    const int b = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npix) return;
+    double s_in = 0.0, s_out = 0.0, e_in = 0.0, e_out = 0.0;
+    long long k_in = 0, k_out = 0;
+    for (int ch = 0; ch < chunks; ++ch) {
+        const double *ps = psum + ((size_t)b * chunks + ch) * 4 * npix;
+        const int *pc = pcnt + ((size_t)b * chunks + ch) * 2 * npix;
+        s_in = s_in + ps[p];
+        s_out = s_out + ps[npix + p];
+        e_in = e_in + ps[2 * npix + p];
+        e_out = e_out + ps[3 * npix + p];
+        k_in += pc[p];
+        k_out += pc[npix + p];
+    }
+    const double ni = (double)k_in, no = (double)k_out;
+    const double mi = s_in / ni, mo = s_out / no;
+    const size_t o = (size_t)b * npix + p;
+    mean_in[o] = mi;
+    mean_out[o] = mo;
+    diff[o] = mo - mi;
+    diff_err[o] = sqrt(e_in / (ni * ni) + e_out / (no * no));
+}
+
+// offset[b] = centroid_diff - centroid_out as (col, row), offset_pix[b] its norm, and the status of cutout b: 1 no in-transit
+// cadence, 2 no out-of-transit cadence, 3 a centroid that is not defined (NaN), else 0
+__global__ __launch_bounds__(256) void diffimage_offsets_kernel(int B, const int *__restrict__ n_in, const int *__restrict__ n_out,
+                                                                const double *__restrict__ diff_col,
+                                                                const double *__restrict__ diff_row,
+                                                                const double *__restrict__ out_col,
+                                                                const double *__restrict__ out_row, double *__restrict__ offset,
+                                                                double *__restrict__ offset_pix, int *__restrict__ status) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const double dx = diff_col[b] - out_col[b], dy = diff_row[b] - out_row[b];
+    const double r = sqrt(dx * dx + dy * dy);
+    offset[2 * (size_t)b] = dx;
+    offset[2 * (size_t)b + 1] = dy;
+    offset_pix[b] = r;
+    status[b] = n_in[b] == 0 ? 1 : n_out[b] == 0 ? 2 : r != r ? 3 : 0;
 }
 
 // np.nanmedian(cube.astype(float64), axis=0) of the cadences with keep != 0 (all of them when keep is NULL): exact order
@@ -473,6 +705,92 @@ int cube_centroids_launch(lk_handle *h, int B, int N, int npix, int nx, const fl
     LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
     hipLaunchKernelGGL(cube_centroids_kernel, dim3((N + 3) / 4, B), dim3(256), 0, stream, flux, mask, mask_stride, N, npix, nx,
                        column0, row0, col_out, row_out);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+int cube_centroids_quadratic_launch(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask,
+                                    int mask_stride, double column0, double row0, double *col_out, double *row_out,
+                                    int32_t *peak_out, hipStream_t stream) {
+    (void)h;
+    LK_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && npix >= 1, "need 1 <= B <= 65535, N >= 1, npix >= 1");
+    LK_REQUIRE(nx >= 1 && npix % nx == 0, "npix = %d is not a whole number of rows of nx = %d pixels", npix, nx);
+    LK_REQUIRE(nx >= 3 && npix / nx >= 3, "the quadratic centroid fits a 3 x 3 patch: a %d x %d cutout is too small", npix / nx, nx);
+    LK_REQUIRE(flux && mask && col_out && row_out, "NULL buffer");
+    LK_REQUIRE(mask_stride == 0 || mask_stride == npix, "mask_stride must be 0 (one mask for the batch) or npix");
+    LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
+    hipLaunchKernelGGL(cube_centroids_quadratic_kernel, dim3((N + 3) / 4, B), dim3(256), 0, stream, flux, mask, mask_stride, N,
+                       npix, nx, column0, row0, col_out, row_out, (int *)peak_out);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+int image_centroids_launch(lk_handle *h, int B, int npix, int nx, const double *image, const uint8_t *mask, int mask_stride,
+                           double column0, double row0, int method, double *col_out, double *row_out, int32_t *peak_out,
+                           hipStream_t stream) {
+    (void)h;
+    LK_REQUIRE(B >= 1 && npix >= 1, "need B >= 1 images of at least one pixel");
+    LK_REQUIRE(nx >= 1 && npix % nx == 0, "npix = %d is not a whole number of rows of nx = %d pixels", npix, nx);
+    LK_REQUIRE(method == LK_CENTROID_MOMENTS || method == LK_CENTROID_QUADRATIC, "method must be LK_CENTROID_MOMENTS or LK_CENTROID_QUADRATIC");
+    LK_REQUIRE(method == LK_CENTROID_MOMENTS || (nx >= 3 && npix / nx >= 3),
+               "the quadratic centroid fits a 3 x 3 patch: a %d x %d image is too small", npix / nx, nx);
+    LK_REQUIRE(image && mask && col_out && row_out, "NULL buffer");
+    LK_REQUIRE(mask_stride == 0 || mask_stride == npix, "mask_stride must be 0 (one mask for the batch) or npix");
+    hipLaunchKernelGGL(image_centroids_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, image, mask, mask_stride, B, npix, nx,
+                       column0, row0, method == LK_CENTROID_QUADRATIC ? 1 : 0, col_out, row_out, (int *)peak_out);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+int cube_diffimage_launch(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const float *flux_err,
+                          const double *period_host, const double *transit_time_host, const double *duration_host, double in_width,
+                          double out_inner, double out_outer, uint8_t *cls, double *mean_in, double *mean_out, double *diff,
+                          double *diff_err, int32_t *n_in, int32_t *n_out, hipStream_t stream) {
+    LK_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && npix >= 1, "need 1 <= B <= 65535, N >= 1, npix >= 1");
+    LK_REQUIRE(time && flux && flux_err && cls && mean_in && mean_out && diff && diff_err && n_in && n_out, "NULL buffer");
+    LK_REQUIRE(period_host && transit_time_host && duration_host, "NULL box parameters");
+    LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
+    LK_REQUIRE(in_width > 0.0 && in_width <= out_inner && out_inner < out_outer,
+               "need 0 < in_width <= out_inner < out_outer (got %g, %g, %g)", in_width, out_inner, out_outer);
+    for (int b = 0; b < B; ++b)
+        LK_REQUIRE(period_host[b] != 0.0 && period_host[b] == period_host[b], "cutout %d: the period must be a non-zero number", b);
+    const int chunks = (N + DI_CHUNK - 1) / DI_CHUNK;
+    std::vector<double> par((size_t)3 * B);
+    for (int b = 0; b < B; ++b) {
+        par[b] = period_host[b];
+        par[(size_t)B + b] = transit_time_host[b];
+        par[2 * (size_t)B + b] = duration_host[b];
+    }
+    double *d_par, *d_psum;
+    int *d_pcnt;
+    if (const int rc = Scratch(h, h->ws)
+                           .upload(d_par, (const double *)par.data(), par.size())
+                           .buf(d_psum, (size_t)B * chunks * 4 * npix)
+                           .buf(d_pcnt, (size_t)B * chunks * 2 * npix)
+                           .carve(stream))
+        return rc;
+    LK_HIP_CHECK(hipMemsetAsync(n_in, 0, (size_t)B * 4, stream));
+    LK_HIP_CHECK(hipMemsetAsync(n_out, 0, (size_t)B * 4, stream));
+    hipLaunchKernelGGL(cube_diffimage_class_kernel, dim3((N + 255) / 256, B), dim3(256), 0, stream, time, (const double *)d_par, B, N,
+                       in_width, out_inner, out_outer, cls, (int *)n_in, (int *)n_out);
+    LK_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(cube_diffimage_accum_kernel, dim3(chunks, B), dim3(DI_T), 0, stream, flux, flux_err, (const uint8_t *)cls, N,
+                       npix, chunks, d_psum, d_pcnt);
+    LK_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(cube_diffimage_finish_kernel, dim3((npix + 255) / 256, B), dim3(256), 0, stream, (const double *)d_psum,
+                       (const int *)d_pcnt, npix, chunks, mean_in, mean_out, diff, diff_err);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+int diffimage_offsets_launch(lk_handle *h, int B, const int32_t *n_in, const int32_t *n_out, const double *diff_col,
+                             const double *diff_row, const double *out_col, const double *out_row, double *offset,
+                             double *offset_pix, int32_t *status, hipStream_t stream) {
+    (void)h;
+    LK_REQUIRE(B >= 1, "need B >= 1 cutouts");
+    LK_REQUIRE(n_in && n_out && diff_col && diff_row && out_col && out_row && offset && offset_pix && status, "NULL buffer");
+    hipLaunchKernelGGL(diffimage_offsets_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, (const int *)n_in,
+                       (const int *)n_out, diff_col, diff_row, out_col, out_row, offset, offset_pix, (int *)status);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }

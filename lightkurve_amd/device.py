@@ -1288,6 +1288,15 @@ class DeviceBLSResult(object):
         return self._batch.create_transit_mask(period, transit_time, duration, planet_off=np.arange(self.B + 1, dtype=np.int32),
                                                to_host=to_host)
 
+    def difference_images(self, cubes, period=None, duration=None, transit_time=None, **kwargs):
+        """Is each detection on its target's pixels?  ``cubes.difference_images`` (a ``DevicePixelCubeBatch`` holding the
+        cutout of every searched target, in the batch's order) at one box per target (arguments as in ``compute_stats``: None =
+        the value at the target's maximum power); the other keywords are ``DevicePixelCubeBatch.difference_images``'s."""
+        if len(cubes) != self.B:
+            raise ValueError("difference_images needs one cutout per searched light curve (%d), got %d" % (self.B, len(cubes)))
+        period, duration, transit_time = self._box(period, duration, transit_time)
+        return cubes.difference_images(period, transit_time, duration, **kwargs)
+
 
 # ------------------------------------------------------------------------------------------------ pixel cubes
 class DevicePeriodogramBatch(object):
@@ -1793,25 +1802,113 @@ class DevicePixelCubeBatch(object):
                                      [dict(m) for m in self.meta], self.device, self.stream, nan_free=True,
                                      is_sorted=self.is_sorted)
 
-    def estimate_centroids(self, aperture_mask="all", column=0, row=0, to_host=False):
-        """``TargetPixelFile.estimate_centroids(aperture_mask, method='moments')`` of every cadence of every cutout
-        (``lk_cube_centroids_batch_dev``): the flux-weighted mean pixel position inside the aperture, ``column`` / ``row`` = the
-        cutout's corner (``tpf.column`` / ``tpf.row``); float64 sums, NaN pixels count as 0, a zero or NaN total gives NaN.
+    def estimate_centroids(self, aperture_mask="all", column=0, row=0, to_host=False, method="moments", return_peak=False):
+        """``TargetPixelFile.estimate_centroids(aperture_mask, method)`` of every cadence of every cutout, ``column`` / ``row`` =
+        the cutout's corner (``tpf.column`` / ``tpf.row``).  ``method="moments"`` (``lk_cube_centroids_batch_dev``): the flux-
+        weighted mean pixel position inside the aperture; float64 sums, NaN pixels count as 0, a zero or NaN total gives NaN.
+        ``method="quadratic"`` (``lk_cube_centroids_quadratic_batch_dev``): ``lightkurve.utils.centroid_quadratic``, the extremum
+        of the quadratic through the 3 x 3 patch around the brightest pixel of ``flux * mask``; NaN for a NaN in the patch, a
+        flat patch or a cadence without a value (nothing is raised); cutouts of at least 3 x 3 pixels.
         All N cadences, in the cube's order (``to_lightcurves`` drops NaN cadences: where it dropped any, select the same ones
         here).  -> (col, row): ``DeviceBuffer``s of B x N float64, what ``DeviceLightCurveBatch.sff_correct`` takes; or (B, N)
-        numpy arrays with ``to_host=True``."""
+        numpy arrays with ``to_host=True``.  ``return_peak=True`` (quadratic only) adds a third item: B x N int32, the flat pixel
+        index of the brightest pixel before the patch is clamped into the image, -1 for a cadence without a value."""
+        if method not in ("moments", "quadratic"):
+            raise ValueError("method must be 'moments' or 'quadratic' (got {!r})".format(method))
+        if return_peak and method != "quadratic":
+            raise ValueError("return_peak needs method='quadratic'")
         h, (B, N, ny, nx) = self.handle, self.shape
         ap = self._masks(aperture_mask, True, None, {})
         d_mask, k = _upload(h, ap.reshape(-1, ny * nx), self.stream, np.uint8)
         d_c, d_r = DeviceBuffer(h, B * N * 8), DeviceBuffer(h, B * N * 8)
-        _capi._check(_capi._lib.lk_cube_centroids_batch_dev(h._h, B, N, ny * nx, nx, _vp(self.d_flux.ptr), _vp(d_mask.ptr),
-                                                            ny * nx if ap.ndim == 3 else 0, float(column), float(row),
-                                                            _vp(d_c.ptr), _vp(d_r.ptr), _vp(self.stream or None)))
+        d_p = DeviceBuffer(h, B * N * 4) if return_peak else None
+        args = (h._h, B, N, ny * nx, nx, _vp(self.d_flux.ptr), _vp(d_mask.ptr), ny * nx if ap.ndim == 3 else 0, float(column),
+                float(row), _vp(d_c.ptr), _vp(d_r.ptr))
+        if method == "quadratic":
+            _capi._check(_capi._lib.lk_cube_centroids_quadratic_batch_dev(*args, _vp(d_p.ptr if return_peak else None),
+                                                                          _vp(self.stream or None)))
+        else:
+            _capi._check(_capi._lib.lk_cube_centroids_batch_dev(*args, _vp(self.stream or None)))
         self._keep.append(k)
         if not to_host:
-            return d_c, d_r
-        return (d_c.download(np.float64, B * N, stream=self.stream).reshape(B, N),
-                d_r.download(np.float64, B * N, stream=self.stream).reshape(B, N))
+            return (d_c, d_r, d_p) if return_peak else (d_c, d_r)
+        out = (d_c.download(np.float64, B * N, stream=self.stream).reshape(B, N),
+               d_r.download(np.float64, B * N, stream=self.stream).reshape(B, N))
+        return out + (d_p.download(np.int32, B * N, stream=self.stream).reshape(B, N),) if return_peak else out
+
+    # ---------------------------------------------------------------- difference images
+    def difference_images(self, period, transit_time, duration, in_width=0.5, out_inner=1.0, out_outer=2.0, aperture_mask="all",
+                          column=0, row=0, to_host=True):
+        """The transit difference image of every cutout and where it sits: is the dimming on the target's pixels or on a
+        neighbour's?  ``period`` / ``transit_time`` / ``duration``: a scalar or one value per cutout (one box each).  Cadence i
+        with time t has the phase x = (t - transit_time + period / 2) % period - period / 2 of ``create_transit_mask`` and is in
+        transit where ``|x| < in_width * duration``, out of transit where ``out_inner * duration <= |x| < out_outer *
+        duration``, neither elsewhere or for a NaN time (``0 < in_width <= out_inner < out_outer``, ``period != 0``).  Per pixel,
+        float64 sums of the float32 values that are not NaN (``lk_cube_diffimage_batch_dev``): ``mean_in``, ``mean_out``,
+        ``diff`` = mean_out - mean_in (positive where the dimming is) and ``diff_err`` = sqrt(sum_in e^2 / n_in^2 + sum_out e^2
+        / n_out^2) from ``flux_err`` at the same values; a pixel without a value in a class is NaN where that class is needed.
+        Then both centroid estimators of ``estimate_centroids`` on ``diff`` and ``mean_out`` inside ``aperture_mask``
+        (``lk_image_centroids_batch_dev``).  Returns a dict: ``mean_in`` / ``mean_out`` / ``diff`` / ``diff_err`` (B, ny, nx);
+        ``n_in`` / ``n_out`` (B,) int32, the cadences of each class; ``centroid_diff`` / ``centroid_out`` (B, 2) as (col, row),
+        quadratic, and ``centroid_diff_moments`` / ``centroid_out_moments``; ``offset`` (B, 2) = centroid_diff - centroid_out and
+        ``offset_pix`` (B,), its norm; ``status`` (B,) int32: 0 ok, 1 no in-transit cadence, 2 no out-of-transit cadence, 3 a
+        quadratic centroid is undefined (nothing is raised for a cutout); ``cadence_class`` (B, N) uint8: 1 in, 2 out, 0 neither.
+        ``to_host=False``: the images, ``offset``, ``offset_pix`` and ``cadence_class`` are ``DeviceBuffer``s and every centroid a
+        pair (col, row) of ``DeviceBuffer``s of B float64, enqueued on the batch's stream; only the counts and the statuses come
+        back.  A cutout's images have the same bits alone, in any batch and from run to run."""
+        h, (B, N, ny, nx) = self.handle, self.shape
+        npix = ny * nx
+        if not (0 < in_width <= out_inner < out_outer):
+            raise ValueError("need 0 < in_width <= out_inner < out_outer (got %r, %r, %r)" % (in_width, out_inner, out_outer))
+        box = []
+        for name, a in (("period", period), ("transit_time", transit_time), ("duration", duration)):
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim > 1 or (a.ndim == 1 and a.size != B):
+                raise ValueError("%s must be a scalar or one value per cutout (%d), got shape %r" % (name, B, a.shape))
+            if not np.all(np.isfinite(a)):
+                raise ValueError("%s must be finite" % name)
+            box.append(np.ascontiguousarray(np.broadcast_to(a, (B,))))
+        if np.any(box[0] == 0):
+            raise ValueError("period must be non-zero")
+        if ny < 3 or nx < 3:
+            raise ValueError("the quadratic centroid needs cutouts of at least 3 x 3 pixels (got %d x %d)" % (ny, nx))
+        ap = self._masks(aperture_mask, True, None, {})
+        d_mask, k = _upload(h, ap.reshape(-1, npix), self.stream, np.uint8)
+        mask_stride = npix if ap.ndim == 3 else 0
+        st = _vp(self.stream or None)
+        img = {key: DeviceBuffer(h, B * npix * 8) for key in ("mean_in", "mean_out", "diff", "diff_err")}
+        d_cls, d_nin, d_nout = DeviceBuffer(h, B * N), DeviceBuffer(h, B * 4), DeviceBuffer(h, B * 4)
+        _capi._check(_capi._lib.lk_cube_diffimage_batch_dev(
+            h._h, B, N, npix, _vp(self.d_time.ptr), _vp(self.d_flux.ptr), _vp(self.d_flux_err.ptr), box[0].ctypes.data_as(_dp),
+            box[1].ctypes.data_as(_dp), box[2].ctypes.data_as(_dp), float(in_width), float(out_inner), float(out_outer),
+            _vp(d_cls.ptr), _vp(img["mean_in"].ptr), _vp(img["mean_out"].ptr), _vp(img["diff"].ptr), _vp(img["diff_err"].ptr),
+            _vp(d_nin.ptr), _vp(d_nout.ptr), st))
+        cen = {}
+        for key, src, method in (("centroid_diff", "diff", 1), ("centroid_out", "mean_out", 1),
+                                 ("centroid_diff_moments", "diff", 0), ("centroid_out_moments", "mean_out", 0)):
+            cen[key] = (DeviceBuffer(h, B * 8), DeviceBuffer(h, B * 8))
+            _capi._check(_capi._lib.lk_image_centroids_batch_dev(
+                h._h, B, npix, nx, _vp(img[src].ptr), _vp(d_mask.ptr), mask_stride, float(column), float(row), method,
+                _vp(cen[key][0].ptr), _vp(cen[key][1].ptr), _vp(None), st))
+        d_off, d_pix, d_status = DeviceBuffer(h, B * 16), DeviceBuffer(h, B * 8), DeviceBuffer(h, B * 4)
+        _capi._check(_capi._lib.lk_diffimage_offsets_batch_dev(
+            h._h, B, _vp(d_nin.ptr), _vp(d_nout.ptr), _vp(cen["centroid_diff"][0].ptr), _vp(cen["centroid_diff"][1].ptr),
+            _vp(cen["centroid_out"][0].ptr), _vp(cen["centroid_out"][1].ptr), _vp(d_off.ptr), _vp(d_pix.ptr), _vp(d_status.ptr), st))
+        out = dict(n_in=d_nin.download(np.int32, B, stream=self.stream), n_out=d_nout.download(np.int32, B, stream=self.stream),
+                   status=d_status.download(np.int32, B, stream=self.stream))       # (synchronises: the staged mask may go)
+        del k
+        if not to_host:
+            out.update(img, offset=d_off, offset_pix=d_pix, cadence_class=d_cls, **cen)
+            return out
+        for key, buf in img.items():
+            out[key] = buf.download(np.float64, B * npix, stream=self.stream).reshape(B, ny, nx)
+        for key, (d_c, d_r) in cen.items():
+            out[key] = np.stack([d_c.download(np.float64, B, stream=self.stream), d_r.download(np.float64, B, stream=self.stream)],
+                                axis=1)
+        out["offset"] = d_off.download(np.float64, 2 * B, stream=self.stream).reshape(B, 2)
+        out["offset_pix"] = d_pix.download(np.float64, B, stream=self.stream)
+        out["cadence_class"] = d_cls.download(np.uint8, B * N, stream=self.stream).reshape(B, N)
+        return out
 
     # ---------------------------------------------------------------- PLD
     def pld_correct(self, aperture_mask="all", pld_aperture_mask="all", background_aperture_mask="all", pld_order=3,

@@ -112,7 +112,13 @@ constant, the routes alternating, `LK_WALLS_REPS` (default 5) times after one wa
 `scipy.interpolate.PchipInterpolator` per target on 16 threads, `regression_correct_batch` on the per-target matrices.  Every timed
 region ends with a synchronise.  Written to profiles/cbvinterp_walls.txt.  `cbvroutes`: the two older routes, U uniform
 `cbv_correct` and C `cbv_correct(cadenceno=)` of `LK_WALLS_B` x `LK_WALLS_N` (default 1000 x 20000), printed only (run on a commit
-and on its parent to show they did not move)."""
+and on its parent to show they did not move).
+
+`diffimage`: the transit difference images of `LK_WALLS_B` (default 500) resident cutouts x `LK_WALLS_N` (default 4000) cadences x
+`LK_WALLS_SIDE`^2 (default 11 x 11) pixels, one box per cutout, in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5)
+times after one warm-up.  R `cubes.difference_images(period, transit_time, duration)`; H the host route: `to_host()`, then
+`PixelCube.difference_image` per cutout on 16 threads.  Every timed region ends with a synchronise.  Written to
+profiles/diffimage_walls.txt."""
 import cProfile
 import io
 import os
@@ -1103,6 +1109,61 @@ def foldbin():
         "  S / F = %.2f; H / F = %.1f" % (med["S"] / med["F"], med["H"] / med["F"])])
 
 
+def diffimage():
+    from concurrent.futures import ThreadPoolExecutor
+    from lightkurve_amd.device import DevicePixelCubeBatch
+    B, N, side = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "500"), ("LK_WALLS_N", "4000"), ("LK_WALLS_SIDE", "11")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "5"))
+    rng = np.random.default_rng(29)
+    t = 1000.0 + np.arange(N) / 48.0
+    period, duration = rng.uniform(1.5, 9.0, B), rng.uniform(0.1, 0.3, B)
+    t0 = t[0] + rng.uniform(0.0, 1.0, B) * period
+    yy, xx = np.indices((side, side))
+    c = side // 2
+    star = 1000.0 * np.exp(-((xx - c) ** 2 + (yy - c) ** 2) / 1.62) + 300.0 * np.exp(-((xx - c - 2) ** 2 + (yy - c) ** 2) / 1.62)
+    flux = np.empty((B, N, side, side), dtype=np.float32)
+    for b in range(B):                                                  # (drawn per cutout: 1.9 GB of cubes in all)
+        flux[b] = star + 20.0 + rng.standard_normal((N, side, side), dtype=np.float32)
+    err = np.ones_like(flux)
+    cubes = DevicePixelCubeBatch.from_arrays(np.tile(t, (B, 1)), flux, err)
+    cubes.synchronize()
+    del flux, err
+
+    def resident():
+        out = cubes.difference_images(period, t0, duration)
+        cubes.synchronize()
+        return out
+
+    def through_host():
+        host = cubes.to_host()
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            out = list(ex.map(lambda b: host[b].difference_image(period[b], t0[b], duration[b]), range(B)))
+        cubes.synchronize()
+        return out
+
+    fns = {"R": resident, "H": through_host}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    r, h = first["R"], first["H"]
+    scale = np.nanmax(np.abs(r["diff"]), axis=(1, 2))
+    rel = max(float(np.nanmax(np.abs(h[b]["diff"] - r["diff"][b])) / scale[b]) for b in range(B) if scale[b] == scale[b])
+    pix = np.array([h[b]["offset_pix"] for b in range(B)])
+    ok = ~np.isnan(pix)
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    write_walls("diffimage_walls.txt", [
+        "transit difference images, %d cutouts x %d cadences x %d x %d float32, one box per cutout (%.1f MB of cubes resident, "
+        "%.2f MB of images)" % (B, N, side, side, 2 * B * N * side * side * 4 / 1e6, 4 * B * side * side * 8 / 1e6),
+        "  R    cubes.difference_images(period, transit_time, duration): classes, chunk sums, images, 4 centroids   %s" % spread(ts["R"]),
+        "  H    to_host(), PixelCube.difference_image per cutout on 16 threads                                      %s" % spread(ts["H"]),
+        "  R and H: same counts and statuses: %s; max |diff_R - diff_H| / max |diff| %.2e; max |offset_pix_R - offset_pix_H| %.2e px"
+        % (all(np.array_equal(r[k], [h[b][k] for b in range(B)]) for k in ("n_in", "n_out", "status")), rel,
+           float(np.max(np.abs(pix[ok] - r["offset_pix"][ok]))) if ok.any() else np.nan),
+        "  H / R = %.1f" % (med["H"] / med["R"])])
+
+
 def stitch(which=("stitch",)):
     from concurrent.futures import ThreadPoolExecutor
     from lightkurve_amd import _capi
@@ -1259,6 +1320,8 @@ def main():
         cbvopt_ragged()
     if "foldbin" in which:
         foldbin()
+    if "diffimage" in which:
+        diffimage()
     if {"stitch", "stitch_trace"} & set(which):
         stitch(which)
     if "flatten" in which:
