@@ -230,7 +230,8 @@ int lk_pg_acf2d_batch_dev(lk_handle *h, int B, int64_t M, const double *power, i
  * C[0] and C[lag] for the lags with `lag > emp - 0.25 emp and lag < emp + 0.25 emp` alone (the same bits as
  * lk_pg_acf2d_batch gives that window), acf = (|C^2| / |C[0]^2|) / (3 / (2 W)), scipy.signal.find_peaks(acf[sel],
  * distance=distance) (plateau midpoints, no peak at either end of the slice, highest peak first and its neighbours
- * closer than ceil(distance) dropped; the order of peaks of exactly equal height is unspecified, as in scipy), and
+ * closer than ceil(distance) dropped; of peaks of exactly equal height the later one is served first, as a stable
+ * argsort orders them -- scipy's own argsort is unstable and agrees with that on short peak lists), and
  * deltanu = the lag of the surviving peak closest to deltanu_emp (the first of equally close ones).
  * Outputs [B]: deltanu (NaN unless status 0), n_peaks (surviving peaks), sel_lo / sel_len (the selected lags), status:
  * 0 ok; 1 skipped (deltanu_emp NaN); 2 the window is not inside [0, M), has fewer than 2 or more than 16384 samples, or

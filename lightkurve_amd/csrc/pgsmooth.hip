@@ -428,11 +428,13 @@ int pg_numax_pick_launch(lk_handle *h, int B, int n_win, const double *metric, c
 //           the slice), then _select_by_peak_distance with ceil(distance): the highest peak first, its neighbours
 //           closer than that dropped
 //   deltanu = the lag of the surviving peak closest to emp, the first of equally close ones.
-// scipy orders peaks of EXACTLY equal height by an unstable argsort; here the later one goes first.  That case is not
-// specified by the reference and not tested.
+// scipy orders peaks of EXACTLY equal height by an unstable argsort; here the later one goes first, which is what a
+// stable argsort gives and what scipy itself does on short peak lists (tests/test_seismology_exact_gpu.py, the
+// equal-heights cases of tests/seismology_cases.py: two and three equal maxima closer than the distance).
 // status: 0 ok; 1 skipped (emp is NaN: the caller's mark for a numax that is NaN or <= 0); 2 the window is not inside
 // [0, M), is shorter than 2 or longer than 16384 samples, or does not fit the workgroup's LDS together with its
-// selection; 3 nothing to pick: no local maximum inside the selection, or distance < 1 (where scipy raises).
+// selection; 3 nothing to pick: no local maximum inside the selection (fewer than 3 lags, a constant window or a NaN in
+// it among the causes), or distance < 1 or NaN (where scipy raises).
 // LDS (doubles): W + 8 window | 8 scratch | the selected slice.  The window's space holds the peak list afterwards.
 __device__ __forceinline__ void block_min_sum(int &mn, int &sum, int *scratch) {
     for (int o = 32; o > 0; o >>= 1) {
