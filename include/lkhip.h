@@ -1132,6 +1132,43 @@ int lk_diffimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *n_in, con
                                    const double *diff_row, const double *out_col, const double *out_row, double *offset,
                                    double *offset_pix, int32_t *status, void *stream);
 
+/* lk_cube_ampimage_batch_dev <- the amplitude images of every cutout (PixelCube.amplitude_image is the numpy mirror): a truncated
+ *   Fourier series of ONE frequency per cutout (frequency: HOST array of B, 1/d) fitted to every pixel's time series, the
+ *   periodic twin of lk_cube_diffimage_batch_dev.  nterms in 1 .. 3, K = 2 nterms + 1; nterms outside that, a NULL buffer or
+ *   N * npix >= 2^31 give LK_EINVAL.  flux_err is not read.
+ *   Cadences: t_ref (HOST array of B) is the reference time of each cutout, by convention its first finite time.  Cadences with
+ *   a non-finite time are dropped (their rows are not loaded); pixel p is fitted on the remaining cadences where its own flux is
+ *   not NaN, n_used[p] of them, unweighted.
+ *   Design: that of lk_ls_model_batch with fit_mean, center_data and unit weights — columns [1, sin(2 pi m f (t - t_ref)),
+ *   cos(2 pi m f (t - t_ref))], m = 1 .. nterms, y centred on the pixel's own mean y_mean; pixel p equals
+ *   ls_model_host(t[ok], y[ok, p], None, f, nterms, singular="nan") on its own cadences (with that function's phases referred
+ *   to t_ref).  All float64 after the float32 load.
+ *   Images, coefficient- or harmonic-major so that each is one block of B images (what lk_image_centroids_batch_dev takes):
+ *   theta [K][B][npix] (slot 0 the bias, then sin 1, cos 1, ...); level [B][npix] = y_mean + bias, the mean image under the
+ *   signal; amplitude [nterms][B][npix] = hypot(s_m, c_m); phase = atan2(c_m, s_m), of the periodic part A sin(w t + phase);
+ *   chi2 [B][npix] = sum (y - model)^2, from the residuals of a second pass over the cube; with sigma2 = chi2 / (n_used - K) and C
+ *   the inverse of the pixel's normal matrix, amplitude_err [nterms][B][npix] = sqrt(sigma2 (s^2 C_ss + 2 s c C_sc + c^2 C_cc)) /
+ *   amplitude and snr = amplitude / amplitude_err; n_used [B][npix] int32.
+ *   Degenerate pixels: n_used < K, or a pivot or coefficient that is zero / not finite -> NaN in every float image; n_used == K
+ *   -> NaN amplitude_err and snr.  Nothing is raised per pixel.
+ *   fit_status [B] int32: 0 fitted; 1 the frequency is NaN or <= 0; 2 fewer than K + 1 cadences with a finite time.  Where it is
+ *   not 0 the cutout is skipped: its float images are NaN, its n_used 0.
+ *   A workgroup sums a chunk of 128 cadences of one cutout (lanes = pixels, the chunk's sines and cosines staged in LDS, float64
+ *   partials against a per-pixel pivot), further kernels add the chunks in index order and solve per pixel: no floating-point
+ *   atomics, the order of every sum depends on N alone, so a cutout's images have the same bits alone, in any batch position
+ *   and from run to run.  Scratch: about B x ceil(N / 128) x npix x (K + (K + 1) K / 2 + 2) x 8 bytes plus B x N x (16 nterms + 1)
+ *   of the handle's arena.  Enqueued, no synchronisation.
+ * lk_ampimage_offsets_batch_dev <- offset[b] = (amp_col - level_col, amp_row - level_row) (B x 2), offset_pix[b] = its norm and
+ *   status[b] (all on the device): fit_status[b] where that is not 0, 3 a centroid that is NaN, else 0.  The centroids are
+ *   lk_image_centroids_batch_dev's of amplitude[0] and level.  Enqueued. */
+int lk_cube_ampimage_batch_dev(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const double *frequency,
+                               int nterms, const double *t_ref, double *theta, double *level, double *amplitude, double *phase,
+                               double *amplitude_err, double *snr, double *chi2, int32_t *n_used, int32_t *fit_status,
+                               void *stream);
+int lk_ampimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *fit_status, const double *amp_col, const double *amp_row,
+                                  const double *level_col, const double *level_row, double *offset, double *offset_pix,
+                                  int32_t *status, void *stream);
+
 /* ---- SFFCorrector.correct (self-flat-fielding, the K2 roll-motion correction; reference lightkurve 2.x
  * src/lightkurve/correctors/sffcorrector.py) for B ragged light curves.  Per target, all float64, inputs finite:
  *   f = flux / median(flux), e = flux_err / median(flux); raw_mean = mean(flux);

@@ -10,7 +10,7 @@ from . import packed
 
 __all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch", "fill_gaps_batch",
            "periodogram_peaks", "flatten_batch",
-           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "regression_correct_batch", "cbv_correct_batch"]
+           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "regression_correct_batch", "cbv_correct_batch"]
 
 
 def _resolve_device(device):
@@ -375,6 +375,14 @@ def difference_images_batch(cubes, period, transit_time, duration, device=0, **k
     then ``DevicePixelCubeBatch.difference_images`` with its keywords and its dict of host arrays.  Not sharded over ranks."""
     from .device import DevicePixelCubeBatch
     return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).difference_images(period, transit_time, duration, **kwargs)
+
+
+def amplitude_images_batch(cubes, frequency, device=0, **kwargs):
+    """``PixelCube.amplitude_image`` of every cutout, for host cutouts: ``cubes`` a list of same-shaped float32 ``PixelCube``s,
+    ``frequency`` a scalar or one value per cutout.  One upload (``DevicePixelCubeBatch.from_cubes``), then
+    ``DevicePixelCubeBatch.amplitude_images`` with its keywords and its dict of host arrays.  Not sharded over ranks."""
+    from .device import DevicePixelCubeBatch
+    return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).amplitude_images(frequency, **kwargs)
 
 
 def regression_correct_batch(lcs, design_matrices, cadence_masks=None, sigma=5, niters=5, device=0, gather=True):

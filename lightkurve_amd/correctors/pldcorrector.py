@@ -247,6 +247,84 @@ class PixelCube(object):
         out["status"] = 1 if out["n_in"] == 0 else 2 if out["n_out"] == 0 else 3 if np.isnan(out["offset_pix"]) else 0
         return out
 
+    def amplitude_image(self, frequency, nterms=1, aperture_mask="all", column=0, row=0):
+        """The amplitude image of this cutout at one ``frequency`` [1/d] and where it sits: the periodic twin of
+        ``difference_image`` (the host mirror of ``DevicePixelCubeBatch.amplitude_images``, in float64 numpy after the float32
+        load; same keys without the batch axis).  ``t_ref`` is the first finite time; cadences with a non-finite time are
+        dropped and pixel p is fitted, unweighted, on the cadences where its own flux is not NaN (``n_used[p]`` of them) by the
+        design of ``ls_model_host(t[ok], y[ok, p], None, frequency, nterms, singular="nan")``: columns [1, sin(2 pi m f (t -
+        t_ref)), cos(2 pi m f (t - t_ref))], m = 1 .. ``nterms`` (1 .. 3), K = 2 nterms + 1, y centred on its mean.
+        ``theta`` (K, ny, nx): the bias, then sin 1, cos 1, ...; ``level`` = y_mean + bias, the mean image under the signal;
+        ``amplitude`` (nterms, ny, nx) = hypot(s_m, c_m); ``phase`` = atan2(c_m, s_m), of A sin(w (t - t_ref) + phase);
+        ``chi2`` = sum (y - model)^2; with sigma2 = chi2 / (n_used - K) and C the inverse of the pixel's normal matrix,
+        ``amplitude_err`` = sqrt(sigma2 (s^2 C_ss + 2 s c C_sc + c^2 C_cc)) / amplitude and ``snr`` = amplitude /
+        amplitude_err.  A pixel with n_used < K or a singular or non-finite fit is NaN in every float image, one with n_used
+        == K has NaN ``amplitude_err`` and ``snr``; nothing is raised per pixel.  ``centroid_amp`` / ``centroid_level``
+        (quadratic) and ``..._moments``: (col, row) of ``amplitude[0]`` and ``level`` inside ``aperture_mask``; ``offset`` =
+        centroid_amp - centroid_level, ``offset_pix`` its norm.  ``status``: 0 ok; 1 the frequency is NaN or <= 0, 2 fewer than
+        K + 1 cadences with a finite time (the cutout is skipped: NaN images, ``n_used`` 0); 3 a quadratic centroid is NaN."""
+        if int(nterms) != nterms or not 1 <= int(nterms) <= 3:
+            raise ValueError("nterms must be an integer 1 .. 3 (got %r)" % (nterms,))
+        if np.ndim(frequency) != 0:
+            raise ValueError("frequency must be one number per cutout (got shape %r)" % (np.shape(frequency),))
+        ny, nx = self.shape[1:]
+        if ny < 3 or nx < 3:
+            raise ValueError("the quadratic centroid needs cutouts of at least 3 x 3 pixels (got %d x %d)" % (ny, nx))
+        ap = self._parse_aperture_mask(aperture_mask)
+        nterms, f = int(nterms), float(frequency)
+        K = 2 * nterms + 1
+        fin = np.isfinite(self.time)
+        t_ref = float(self.time[fin][0]) if fin.any() else np.nan
+        status = 1 if not (f > 0 and np.isfinite(f)) else 2 if fin.sum() < K + 1 else 0
+        out = {"frequency": f, "t_ref": t_ref, "theta": np.full((K, ny, nx), np.nan), "n_used": np.zeros((ny, nx), dtype=np.int32)}
+        for key in ("level", "chi2"):
+            out[key] = np.full((ny, nx), np.nan)
+        for key in ("amplitude", "phase", "amplitude_err", "snr"):
+            out[key] = np.full((nterms, ny, nx), np.nan)
+        if status == 0:
+            t = self.time[fin] - t_ref
+            y = np.asarray(self.flux, dtype=np.float64)[fin].reshape(len(t), ny * nx)
+            cols = [np.ones(len(t))]
+            for m in range(1, nterms + 1):
+                cols += [np.sin(2 * np.pi * m * f * t), np.cos(2 * np.pi * m * f * t)]
+            X_all = np.column_stack(cols)
+            with np.errstate(all="ignore"):
+                for p in range(ny * nx):
+                    iy, ix = divmod(p, nx)
+                    ok = ~np.isnan(y[:, p])
+                    n = int(ok.sum())
+                    out["n_used"][iy, ix] = n
+                    if n < K:
+                        continue
+                    X, yp = (X_all, y[:, p]) if n == len(t) else (X_all[ok], y[ok, p])
+                    y_mean = yp.sum() / n
+                    G = X.T.dot(X)
+                    try:
+                        sol = np.linalg.solve(G, X.T.dot(yp - y_mean))
+                        C = np.linalg.inv(G)
+                    except np.linalg.LinAlgError:
+                        continue
+                    level = y_mean + sol[0]
+                    if not (np.all(np.isfinite(sol)) and np.isfinite(level)):
+                        continue
+                    chi2 = float(np.sum((yp - (y_mean + X.dot(sol))) ** 2))
+                    s, c = sol[1::2], sol[2::2]
+                    amp = np.hypot(s, c)
+                    sigma2 = chi2 / (n - K) if n > K else np.nan
+                    i = np.arange(1, K, 2)
+                    err = np.sqrt(sigma2 * (s * s * C[i, i] + 2 * s * c * C[i, i + 1] + c * c * C[i + 1, i + 1])) / amp
+                    out["theta"][:, iy, ix], out["level"][iy, ix], out["chi2"][iy, ix] = sol, level, chi2
+                    out["amplitude"][:, iy, ix], out["phase"][:, iy, ix] = amp, np.arctan2(c, s)
+                    out["amplitude_err"][:, iy, ix], out["snr"][:, iy, ix] = err, amp / err
+        for key, im in (("amp", out["amplitude"][0]), ("level", out["level"])):
+            c, r = centroid_quadratic(im, ap)
+            out["centroid_" + key] = np.array([column + c, row + r])
+            out["centroid_%s_moments" % key] = np.array([v[0] for v in _moment_centroids(im[None], ap, column, row)])
+        out["offset"] = out["centroid_amp"] - out["centroid_level"]
+        out["offset_pix"] = float(np.sqrt(np.sum(out["offset"] ** 2)))
+        out["status"] = status if status else 3 if np.isnan(out["offset_pix"]) else 0
+        return out
+
 
     def _aperture_sums(self, ap):
         """(flux, flux_err) of the aperture `ap` (boolean image) per cadence, in the cube's dtype.  The gather `cube[:, ap]`

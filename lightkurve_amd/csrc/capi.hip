@@ -2217,6 +2217,26 @@ int lk_diffimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *n_in, con
                                         static_cast<hipStream_t>(stream));
 }
 
+// ------------------------------------------------------------------------------------------------ amplitude images
+int lk_cube_ampimage_batch_dev(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const double *frequency,
+                               int nterms, const double *t_ref, double *theta, double *level, double *amplitude, double *phase,
+                               double *amplitude_err, double *snr, double *chi2, int32_t *n_used, int32_t *fit_status,
+                               void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_ampimage_launch(h, B, N, npix, time, flux, frequency, nterms, t_ref, theta, level, amplitude, phase,
+                                    amplitude_err, snr, chi2, n_used, fit_status, static_cast<hipStream_t>(stream));
+}
+
+int lk_ampimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *fit_status, const double *amp_col, const double *amp_row,
+                                  const double *level_col, const double *level_row, double *offset, double *offset_pix,
+                                  int32_t *status, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::ampimage_offsets_launch(h, B, fit_status, amp_col, amp_row, level_col, level_row, offset, offset_pix, status,
+                                       static_cast<hipStream_t>(stream));
+}
+
 int lk_sff_scratch_bytes(int B, const int64_t *n_off, const int32_t *n_knots, const int32_t *win_off, int bins, int degree,
                          int64_t max_scratch_bytes, int64_t *bytes, int *n_chunks) {
     return lk::sff_scratch_bytes(B, n_off, n_knots, win_off, bins, degree, max_scratch_bytes, bytes, n_chunks);

@@ -405,6 +405,15 @@ int cube_diffimage_launch(lk_handle *h, int B, int N, int npix, const double *ti
 int diffimage_offsets_launch(lk_handle *h, int B, const int32_t *n_in, const int32_t *n_out, const double *diff_col,
                              const double *diff_row, const double *out_col, const double *out_row, double *offset,
                              double *offset_pix, int32_t *status, hipStream_t stream);
+// ampimage.hip: the per-pixel sinusoid fit of B resident cutouts at one frequency each (host arrays), coefficient- and harmonic-
+// major images; then the centroid offsets and statuses.  Everything else on the device; enqueued, no synchronisation
+int cube_ampimage_launch(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const double *frequency_host,
+                         int nterms, const double *t_ref_host, double *theta, double *level, double *amplitude, double *phase,
+                         double *amplitude_err, double *snr, double *chi2, int32_t *n_used, int32_t *fit_status,
+                         hipStream_t stream);
+int ampimage_offsets_launch(lk_handle *h, int B, const int32_t *fit_status, const double *amp_col, const double *amp_row,
+                            const double *level_col, const double *level_row, double *offset, double *offset_pix, int32_t *status,
+                            hipStream_t stream);
 // sff.hip: SFFCorrector for a ragged resident batch.  The regression launcher owns h->ws, so the design matrices and everything
 // else that lives across it sit in `scratch`, a device block of the caller's (sff_scratch_bytes); status_host is valid on
 // return (the call synchronises once, to group the targets by their design width)

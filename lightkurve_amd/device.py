@@ -1380,6 +1380,14 @@ class DevicePeriodogramBatch(object):
         am = d_arg.download(np.int64, B, stream=self.stream)
         return dict(max_power=mx, argmax=am, frequency=np.where(am >= 0, self.frequency[np.clip(am, 0, self.M - 1)], np.nan))
 
+    def amplitude_images(self, cubes, **kwargs):
+        """Is each spectrum's strongest signal on its target's pixels?  ``cubes.amplitude_images`` (a ``DevicePixelCubeBatch``
+        holding the cutout of every target, in the batch's order) at every target's ``peaks()["frequency"]``, in this batch's
+        frequency unit; the other keywords are ``DevicePixelCubeBatch.amplitude_images``'s."""
+        if len(cubes) != self.B:
+            raise ValueError("amplitude_images needs one cutout per spectrum (%d), got %d" % (self.B, len(cubes)))
+        return cubes.amplitude_images(self.peaks()["frequency"], freq_unit=self.frequency_unit, **kwargs)
+
     # ---------------------------------------------------------------- Periodogram.smooth / flatten
     def smooth(self, method="boxkernel", filter_width=0.1):
         """``Periodogram.smooth`` (reference periodogram.py:182-284) of every spectrum -> a new batch; the same planning,
@@ -1908,6 +1916,90 @@ class DevicePixelCubeBatch(object):
         out["offset"] = d_off.download(np.float64, 2 * B, stream=self.stream).reshape(B, 2)
         out["offset_pix"] = d_pix.download(np.float64, B, stream=self.stream)
         out["cadence_class"] = d_cls.download(np.uint8, B * N, stream=self.stream).reshape(B, N)
+        return out
+
+    # ---------------------------------------------------------------- amplitude images
+    def amplitude_images(self, frequency, nterms=1, aperture_mask="all", column=0, row=0, to_host=True, freq_unit=None, peaks=None):
+        """The amplitude image of every cutout and where it sits: is a periodic signal (a pulsation, a rotation signal, a
+        contact binary) on the target's pixels or on a neighbour's?  The periodic twin of ``difference_images``; the numpy
+        mirror is ``PixelCube.amplitude_image``.  ``frequency``: a scalar or one value per cutout in ``freq_unit`` (default
+        1/d, the units of ``ls_model``); NaN or <= 0 skips the cutout (status 1).  With ``peaks`` (the float64[B, 2] array of
+        ``to_periodogram_peaks(frequency, ...)`` of the cutouts' light curves) ``frequency`` is the grid that was searched and
+        every cutout takes the frequency at its own maximum.  Per pixel (``lk_cube_ampimage_batch_dev``): an unweighted fit of
+        [1, sin(2 pi m f (t - t_ref)), cos(2 pi m f (t - t_ref))], m = 1 .. ``nterms`` (1 .. 3), to the values that are not
+        NaN at the cadences with a finite time; ``t_ref`` is each cutout's first finite time; float64 sums of the float32
+        values, ``flux_err`` is not read.  Then both centroid estimators of ``estimate_centroids`` on ``amplitude[:, 0]`` and
+        ``level`` inside ``aperture_mask`` (``lk_image_centroids_batch_dev``).  Returns a dict: ``theta`` (B, K, ny, nx), K = 2
+        nterms + 1 (the bias, then sin 1, cos 1, ...); ``level`` (B, ny, nx) = y_mean + bias; ``amplitude`` / ``phase`` /
+        ``amplitude_err`` / ``snr`` (B, nterms, ny, nx); ``chi2`` (B, ny, nx); ``n_used`` (B, ny, nx) int32; ``centroid_amp`` /
+        ``centroid_level`` (B, 2) as (col, row), quadratic, and ``centroid_amp_moments`` / ``centroid_level_moments``;
+        ``offset`` (B, 2) = centroid_amp - centroid_level and ``offset_pix`` (B,); ``frequency`` [1/d] and ``t_ref`` (B,);
+        ``status`` (B,) int32: 0 ok, 1 skipped, 2 fewer than K + 1 cadences with a finite time, 3 a quadratic centroid is
+        undefined (nothing is raised for a cutout or a pixel).  ``to_host=False``: the images, ``offset`` and ``offset_pix``
+        are ``DeviceBuffer``s — ``theta`` laid out [K][B][npix] and the per-harmonic images [nterms][B][npix], every
+        coefficient one block of B images — and every centroid a pair (col, row) of ``DeviceBuffer``s of B float64, enqueued
+        on the batch's stream; only ``status`` comes back.  A cutout's images have the same bits alone, in any batch position
+        and from run to run."""
+        from .periodogram import _freq_unit_factor
+        h, (B, N, ny, nx) = self.handle, self.shape
+        npix = ny * nx
+        if int(nterms) != nterms or not 1 <= int(nterms) <= 3:
+            raise ValueError("nterms must be an integer 1 .. 3 (got %r)" % (nterms,))
+        nterms = int(nterms)
+        K = 2 * nterms + 1
+        freq = np.asarray(frequency, dtype=np.float64)
+        if peaks is not None:
+            peaks = np.asarray(peaks, dtype=np.float64)
+            if peaks.shape != (B, 2) or freq.ndim != 1 or freq.size < 2:
+                raise ValueError("peaks must be the (%d, 2) array of to_periodogram_peaks(frequency) and frequency its grid" % B)
+            at = np.where(np.isfinite(peaks[:, 1]), peaks[:, 1], -1).astype(np.int64)
+            freq = np.where((at >= 0) & (at < freq.size), freq[np.clip(at, 0, freq.size - 1)], np.nan)
+        if freq.ndim > 1 or (freq.ndim == 1 and freq.size != B):
+            raise ValueError("frequency must be a scalar or one value per cutout (%d), got shape %r" % (B, freq.shape))
+        f_day = np.ascontiguousarray(np.broadcast_to(freq, (B,)) / _freq_unit_factor(freq_unit if freq_unit is not None else "1/d"))
+        if ny < 3 or nx < 3:
+            raise ValueError("the quadratic centroid needs cutouts of at least 3 x 3 pixels (got %d x %d)" % (ny, nx))
+        fin = np.isfinite(self.time)
+        first = np.argmax(fin, axis=1)
+        t_ref = np.ascontiguousarray(np.where(fin.any(axis=1), self.time[np.arange(B), first], np.nan))
+        ap = self._masks(aperture_mask, True, None, {})
+        d_mask, k = _upload(h, ap.reshape(-1, npix), self.stream, np.uint8)
+        mask_stride = npix if ap.ndim == 3 else 0
+        st = _vp(self.stream or None)
+        img = {key: DeviceBuffer(h, n * B * npix * 8) for key, n in (("theta", K), ("level", 1), ("amplitude", nterms), ("phase", nterms),
+                                                                   ("amplitude_err", nterms), ("snr", nterms), ("chi2", 1))}
+        d_used, d_fit = DeviceBuffer(h, B * npix * 4), DeviceBuffer(h, B * 4)
+        _capi._check(_capi._lib.lk_cube_ampimage_batch_dev(
+            h._h, B, N, npix, _vp(self.d_time.ptr), _vp(self.d_flux.ptr), f_day.ctypes.data_as(_dp), nterms, t_ref.ctypes.data_as(_dp),
+            _vp(img["theta"].ptr), _vp(img["level"].ptr), _vp(img["amplitude"].ptr), _vp(img["phase"].ptr),
+            _vp(img["amplitude_err"].ptr), _vp(img["snr"].ptr), _vp(img["chi2"].ptr), _vp(d_used.ptr), _vp(d_fit.ptr), st))
+        cen = {}
+        for key, src, method in (("centroid_amp", "amplitude", 1), ("centroid_level", "level", 1),
+                                 ("centroid_amp_moments", "amplitude", 0), ("centroid_level_moments", "level", 0)):
+            cen[key] = (DeviceBuffer(h, B * 8), DeviceBuffer(h, B * 8))       # (amplitude's first block is harmonic 1 of the batch)
+            _capi._check(_capi._lib.lk_image_centroids_batch_dev(
+                h._h, B, npix, nx, _vp(img[src].ptr), _vp(d_mask.ptr), mask_stride, float(column), float(row), method,
+                _vp(cen[key][0].ptr), _vp(cen[key][1].ptr), _vp(None), st))
+        d_off, d_pix, d_status = DeviceBuffer(h, B * 16), DeviceBuffer(h, B * 8), DeviceBuffer(h, B * 4)
+        _capi._check(_capi._lib.lk_ampimage_offsets_batch_dev(
+            h._h, B, _vp(d_fit.ptr), _vp(cen["centroid_amp"][0].ptr), _vp(cen["centroid_amp"][1].ptr),
+            _vp(cen["centroid_level"][0].ptr), _vp(cen["centroid_level"][1].ptr), _vp(d_off.ptr), _vp(d_pix.ptr), _vp(d_status.ptr), st))
+        out = dict(status=d_status.download(np.int32, B, stream=self.stream), frequency=f_day, t_ref=t_ref)   # (synchronises)
+        del k
+        if not to_host:
+            out.update(img, n_used=d_used, offset=d_off, offset_pix=d_pix, **cen)
+            return out
+        for key, n in (("theta", K), ("amplitude", nterms), ("phase", nterms), ("amplitude_err", nterms), ("snr", nterms)):
+            a = img[key].download(np.float64, n * B * npix, stream=self.stream).reshape(n, B, ny, nx)
+            out[key] = np.ascontiguousarray(a.transpose(1, 0, 2, 3))
+        for key in ("level", "chi2"):
+            out[key] = img[key].download(np.float64, B * npix, stream=self.stream).reshape(B, ny, nx)
+        out["n_used"] = d_used.download(np.int32, B * npix, stream=self.stream).reshape(B, ny, nx)
+        for key, (d_c, d_r) in cen.items():
+            out[key] = np.stack([d_c.download(np.float64, B, stream=self.stream), d_r.download(np.float64, B, stream=self.stream)],
+                                axis=1)
+        out["offset"] = d_off.download(np.float64, 2 * B, stream=self.stream).reshape(B, 2)
+        out["offset_pix"] = d_pix.download(np.float64, B, stream=self.stream)
         return out
 
     # ---------------------------------------------------------------- PLD

@@ -118,7 +118,14 @@ and on its parent to show they did not move).
 `LK_WALLS_SIDE`^2 (default 11 x 11) pixels, one box per cutout, in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5)
 times after one warm-up.  R `cubes.difference_images(period, transit_time, duration)`; H the host route: `to_host()`, then
 `PixelCube.difference_image` per cutout on 16 threads.  Every timed region ends with a synchronise.  Written to
-profiles/diffimage_walls.txt."""
+profiles/diffimage_walls.txt.
+
+`ampimage`: the amplitude images of the same batch shape (`LK_WALLS_B` x `LK_WALLS_N` x `LK_WALLS_SIDE`^2, defaults 500 x 4000 x
+11 x 11), one frequency per cutout, in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5) times after one warm-up.
+R `cubes.amplitude_images(frequency, nterms=1)` and R3 the same with `nterms=3`, images on the host at the end; D
+`cubes.difference_images(...)` of the same cubes, the other kernel family with this chunking (it reads the rows of the in- and
+out-of-transit cadences of two cubes; the floor of R is two reads of every row of the flux cube); H the host route: `to_host()`, then `PixelCube.amplitude_image` per cutout on 16 threads.  Every
+timed region ends with a synchronise.  Written to profiles/ampimage_walls.txt."""
 import cProfile
 import io
 import os
@@ -1164,6 +1171,72 @@ def diffimage():
         "  H / R = %.1f" % (med["H"] / med["R"])])
 
 
+def ampimage():
+    from concurrent.futures import ThreadPoolExecutor
+    from lightkurve_amd.device import DevicePixelCubeBatch
+    B, N, side = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "500"), ("LK_WALLS_N", "4000"), ("LK_WALLS_SIDE", "11")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "5"))
+    rng = np.random.default_rng(37)
+    t = 1000.0 + np.arange(N) / 720.0                                    # two-minute cadences
+    freq = rng.uniform(5.0, 60.0, B)                                     # [1/d]: 28 to 330 cycles in the baseline
+    period, duration = rng.uniform(1.5, 5.0, B), rng.uniform(0.1, 0.3, B)
+    t0 = t[0] + rng.uniform(0.0, 1.0, B) * period
+    yy, xx = np.indices((side, side))
+    c = side // 2
+    star = (1e4 + 3000.0 * np.exp(-((xx - c) ** 2 + (yy - c) ** 2) / 1.62)).astype(np.float32)
+    neighbour = (800.0 * np.exp(-((xx - c - 3) ** 2 + (yy - c) ** 2) / 1.62)).astype(np.float32)
+    flux = np.empty((B, N, side, side), dtype=np.float32)
+    for b in range(B):                                                  # (drawn per cutout: 1.9 GB of cubes in all)
+        signal = (1.0 + 0.05 * np.sin(2 * np.pi * freq[b] * (t - t[0]) + 0.7)).astype(np.float32)
+        flux[b] = star + neighbour * signal[:, None, None] + 2.0 * rng.standard_normal((N, side, side), dtype=np.float32)
+    err = np.full_like(flux, 2.0)
+    cubes = DevicePixelCubeBatch.from_arrays(np.tile(t, (B, 1)), flux, err)
+    cubes.synchronize()
+    del flux, err
+
+    def resident(nterms=1):
+        out = cubes.amplitude_images(freq, nterms)
+        cubes.synchronize()
+        return out
+
+    def difference():
+        out = cubes.difference_images(period, t0, duration)
+        cubes.synchronize()
+        return out
+
+    def through_host():
+        host = cubes.to_host()
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            out = list(ex.map(lambda b: host[b].amplitude_image(freq[b]), range(B)))
+        cubes.synchronize()
+        return out
+
+    fns = {"R": resident, "R3": lambda: resident(3), "D": difference, "H": through_host}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    r, h = first["R"], first["H"]
+    rel = {}
+    for key in ("theta", "level", "amplitude", "amplitude_err", "chi2"):
+        rel[key] = max(float(np.nanmax(np.abs(h[b][key] - r[key][b])) / np.nanmax(np.abs(h[b][key]))) for b in range(B))
+    pix = np.array([h[b]["offset_pix"] for b in range(B)])
+    ok = ~np.isnan(pix)
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    write_walls("ampimage_walls.txt", [
+        "amplitude images, %d cutouts x %d cadences x %d x %d float32, one frequency per cutout (%.1f MB of flux resident, read twice; "
+        "%.2f MB of images at nterms = 1)" % (B, N, side, side, B * N * side * side * 4 / 1e6, 10.5 * B * side * side * 8 / 1e6),
+        "  R    cubes.amplitude_images(frequency, nterms=1): trig, pivots, chunk sums, solve, residual pass, 4 centroids  %s" % spread(ts["R"]),
+        "  R3   the same with nterms=3 (K = 7)                                                                           %s" % spread(ts["R3"]),
+        "  D    cubes.difference_images(period, transit_time, duration) of the same cubes: classed rows of two cubes     %s" % spread(ts["D"]),
+        "  H    to_host(), PixelCube.amplitude_image per cutout on 16 threads                                            %s" % spread(ts["H"]),
+        "  R and H: same counts and statuses: %s; max |R - H| / max |image|: %s; max |offset_pix_R - offset_pix_H| %.2e px"
+        % (all(np.array_equal(r[k], [h[b][k] for b in range(B)]) for k in ("n_used", "status")),
+           ", ".join("%s %.2e" % kv for kv in rel.items()), float(np.max(np.abs(pix[ok] - r["offset_pix"][ok]))) if ok.any() else np.nan),
+        "  R / D = %.2f; R3 / D = %.2f; H / R = %.1f; kernel times alone: profiles/ampimage_kernels.txt" % (med["R"] / med["D"], med["R3"] / med["D"], med["H"] / med["R"])])
+
+
 def stitch(which=("stitch",)):
     from concurrent.futures import ThreadPoolExecutor
     from lightkurve_amd import _capi
@@ -1322,6 +1395,8 @@ def main():
         foldbin()
     if "diffimage" in which:
         diffimage()
+    if "ampimage" in which:
+        ampimage()
     if {"stitch", "stitch_trace"} & set(which):
         stitch(which)
     if "flatten" in which:
