@@ -959,7 +959,11 @@ int lk_savgol_design(int window, int polyorder, double *coeffs, double *edge);
  * knots: B x (n_inner + 2) = [min(t), interior knots (percentiles of t, as patsy's bs()), max(t)];
  * n_knots = n_inner + spline_degree + 1 spline columns (+1 constant).  normalize_bkg: divide background pixels
  * by their row sum.  X: B x N x K row-major with K = lk_pld_design_width(...):
- *   [ PCA(pixels/flux) | PCA(2-fold products) | ... | PCA(background) | B-splines | 1 ];  prior_sigma: B x K. */
+ *   [ PCA(pixels/flux) | PCA(2-fold products) | ... | PCA(background) | B-splines | 1 ];  prior_sigma: B x K.
+ * A block wider than 4096 columns before PCA (e.g. 29 components at order 3: 4495 products) is refused with LK_EINVAL.
+ * normalize_bkg with Pb <= pca_components: the rows of the normalised block sum to 1, so the centred block has rank Pb - 1
+ * and the last of its min(pca_components, Pb) columns is a quotient of rounding errors, as in the reference; the leading
+ * Pb - 1 columns are the block's basis (tests/test_pld_blocks_gpu.py asserts on those). */
 int lk_pld_design_width(int P, int Pb, int pld_order, int pca_components, int n_knots);
 int lk_pld_design_batch(lk_handle *h, int B, int N, int P, int Pb, const float *pld_pix, const float *bkg_pix,
                         const float *lc_flux, const double *time, const double *knots, int n_inner, int pld_order,
