@@ -1173,6 +1173,26 @@ int lk_ampimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *fit_status
                                   const double *level_col, const double *level_row, double *offset, double *offset_pix,
                                   int32_t *status, void *stream);
 
+/* lk_cube_background_batch_dev <- TargetPixelFile.estimate_background(aperture_mask) per cadence of the same resident cubes,
+ *   and the subtraction of that background, in one pass (PixelCube.estimate_background / subtract_background are the numpy
+ *   mirror).  mask / mask_stride as lk_cube_aperture_batch_dev; sel = the masked pixels of cadence i of cutout b.
+ *   bkg[b][i] (B x N float32) = np.nanmedian(sel) in float32: NaN is the only excluded value, +-inf are values, an even count
+ *   gives float32(a + b) / 2 of the two middle values, no value (or an empty mask) gives NaN.  n_pixels[b][i] (B x N int32) =
+ *   the values of sel that are not NaN.  want_scatter != 0: scatter[b][i] (B x N float32) = np.nanmedian(|sel - bkg|), all in
+ *   float32, NaN differences excluded; otherwise scatter is not touched and may be NULL.  cube_out (nullable, B x N x npix
+ *   float32, not the cube itself): cube[b][i][p] - bkg[b][i] for ALL npix pixels of the cadence.  Selection is exact: every
+ *   output equals numpy's value for value, and a cutout's outputs have the same bits alone, at any position of a batch and
+ *   from run to run.  Two routes, chosen from npix alone: npix <= 224 stages 64 cadences per workgroup in LDS, one wavefront
+ *   per cadence ranks the selected pixels by counting; wider cutouts take one workgroup per cadence and a radix select.  The
+ *   cube is read once (and written once).  No scratch.  Enqueued, no synchronisation.
+ * lk_cube_subtract_rows_batch_dev <- cube_out[b][i][p] = cube[b][i][p] - rows[b][i] for rows (B x N float32) of the caller's.
+ *   Enqueued, no synchronisation.
+ * Both: B, N, npix >= 1, B <= 65535 and N * npix < 2^31, no NULL buffer but the nullable ones, else LK_EINVAL. */
+int lk_cube_background_batch_dev(lk_handle *h, int B, int N, int npix, const float *cube, const uint8_t *mask, int mask_stride,
+                                 int want_scatter, float *bkg, int32_t *n_pixels, float *scatter, float *cube_out, void *stream);
+int lk_cube_subtract_rows_batch_dev(lk_handle *h, int B, int N, int npix, const float *cube, const float *rows, float *cube_out,
+                                    void *stream);
+
 /* ---- SFFCorrector.correct (self-flat-fielding, the K2 roll-motion correction; reference lightkurve 2.x
  * src/lightkurve/correctors/sffcorrector.py) for B ragged light curves.  Per target, all float64, inputs finite:
  *   f = flux / median(flux), e = flux_err / median(flux); raw_mean = mean(flux);

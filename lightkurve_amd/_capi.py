@@ -362,6 +362,9 @@ SIGNATURES = [
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _c_dp, ctypes.c_int, _c_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
       _vp, _vp]),
     ("lk_ampimage_offsets_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_cube_background_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_cube_subtract_rows_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
     ("lk_sff_scratch_bytes", ctypes.c_int,
      [ctypes.c_int, _c_ip, _c_i32p, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
       ctypes.POINTER(ctypes.c_int)]),

@@ -10,7 +10,7 @@ from . import packed
 
 __all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch", "fill_gaps_batch",
            "periodogram_peaks", "flatten_batch",
-           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "regression_correct_batch", "cbv_correct_batch"]
+           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "subtract_background_batch", "regression_correct_batch", "cbv_correct_batch"]
 
 
 def _resolve_device(device):
@@ -383,6 +383,16 @@ def amplitude_images_batch(cubes, frequency, device=0, **kwargs):
     ``DevicePixelCubeBatch.amplitude_images`` with its keywords and its dict of host arrays.  Not sharded over ranks."""
     from .device import DevicePixelCubeBatch
     return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).amplitude_images(frequency, **kwargs)
+
+
+def subtract_background_batch(cubes, background=None, aperture_mask="background", device=0, to_host=True):
+    """``PixelCube.subtract_background`` of every cutout, for host cutouts: ``cubes`` a list of same-shaped float32
+    ``PixelCube``s, ``background`` None (each cutout's own estimate over ``aperture_mask``) or a (B, N) array.  One upload
+    (``DevicePixelCubeBatch.from_cubes``), then ``DevicePixelCubeBatch.subtract_background``; returns the subtracted
+    ``PixelCube``s, or the resident batch with ``to_host=False``.  Not sharded over ranks."""
+    from .device import DevicePixelCubeBatch
+    out = DevicePixelCubeBatch.from_cubes(list(cubes), device=device).subtract_background(background, aperture_mask)
+    return out.to_host() if to_host else out
 
 
 def regression_correct_batch(lcs, design_matrices, cadence_masks=None, sigma=5, niters=5, device=0, gather=True):

@@ -121,6 +121,11 @@ def threshold_mask_from_median_image(median_image, threshold=3, reference_pixel=
     return labels == labels[closest[0], closest[1]]
 
 
+def _background_meta(npix, bkg):
+    """The meta keys a background subtraction leaves: ``npix`` mask pixels (-1: unknown), ``bkg`` the subtracted [N] values."""
+    return {"BKG_SUBTRACTED": True, "BKG_NPIX": int(npix), "BKG_NAN_CADENCES": int(np.sum(np.isnan(bkg)))}
+
+
 class PixelCube(object):
     """Minimal stand-in for the slice of TargetPixelFile that PLDCorrector touches."""
 
@@ -212,6 +217,54 @@ class PixelCube(object):
             raise ValueError("method must be 'moments' or 'quadratic' (got {!r})".format(method))
         cr = np.array([centroid_quadratic(im, ap) for im in self.flux], dtype=np.float64).reshape(-1, 2)
         return column + cr[:, 0], row + cr[:, 1]
+
+    def estimate_background(self, aperture_mask="background", return_scatter=False):
+        """``TargetPixelFile.estimate_background(aperture_mask)``: the per-pixel background of every cadence as the median of
+        the pixels in ``aperture_mask`` (default 'background', the complement of ``create_threshold_mask(0, None)``, made from
+        the cube as it is).  The host mirror of ``DevicePixelCubeBatch.estimate_background``, and its definition.  With ``sel =
+        flux[:, mask]`` in float32 (pixels in ascending flat index), a dict of ``flux`` float32[N] = ``np.nanmedian(sel,
+        axis=1)`` (NaN is the only excluded value, +-inf are values; an even count gives float32(a + b) / 2; no value, or an empty
+        mask, gives NaN and no warning), ``n_pixels`` int32[N] = the values of ``sel`` that are not NaN, ``mask`` bool (ny, nx) and,
+        with ``return_scatter``, ``scatter`` float32[N] = ``np.nanmedian(|sel - flux[:, None]|, axis=1)`` in float32.  No error
+        column: the reference's estimate has none."""
+        import warnings
+        m = self._parse_aperture_mask(aperture_mask)
+        sel = np.asarray(self.flux, dtype=np.float32)[:, m]
+
+        def nanmedian_rows(a):
+            if a.shape[1] == 0:
+                return np.full(a.shape[0], np.nan, dtype=np.float32)
+            with warnings.catch_warnings(), np.errstate(all="ignore"):
+                warnings.simplefilter("ignore", RuntimeWarning)
+                return np.asarray(np.nanmedian(a, axis=1), dtype=np.float32)
+
+        out = {"flux": nanmedian_rows(sel), "n_pixels": np.sum(~np.isnan(sel), axis=1).astype(np.int32), "mask": m}
+        if return_scatter:
+            with np.errstate(all="ignore"):
+                out["scatter"] = nanmedian_rows(np.abs(sel - out["flux"][:, None]))
+        return out
+
+    def subtract_background(self, background=None, aperture_mask="background"):
+        """A new ``PixelCube`` with ``flux - bkg[:, None, None]`` in float32.  ``bkg``: ``estimate_background(aperture_mask)
+        ["flux"]`` when ``background`` is None, else the given float32-castable [N] array or the dict ``estimate_background``
+        returned.  ``flux_err`` and ``time`` are carried unchanged (the estimate has no error).  ``meta`` gains ``BKG_SUBTRACTED``
+        = True, ``BKG_NPIX`` = the pixels of the mask (-1 for a bare array) and ``BKG_NAN_CADENCES`` = the cadences whose
+        background is NaN.  The host mirror of ``DevicePixelCubeBatch.subtract_background``."""
+        if background is None:
+            background = self.estimate_background(aperture_mask)
+        npix = -1
+        if isinstance(background, dict):
+            npix = int(np.sum(background["mask"]))
+            background = background["flux"]
+        bkg = np.asarray(background, dtype=np.float32)
+        if bkg.shape != (len(self.time),):
+            raise ValueError("background must hold one value per cadence (%d), got shape %r" % (len(self.time), bkg.shape))
+        with np.errstate(all="ignore"):
+            flux = np.asarray(self.flux, dtype=np.float32) - bkg[:, None, None]
+        out = PixelCube(self.time, flux, self.flux_err)
+        out.meta = dict(self.meta)
+        out.meta.update(_background_meta(npix, bkg))
+        return out
 
     def difference_image(self, period, transit_time, duration, in_width=0.5, out_inner=1.0, out_outer=2.0,
                          aperture_mask="all", column=0, row=0):

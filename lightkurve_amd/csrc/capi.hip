@@ -2217,6 +2217,22 @@ int lk_diffimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *n_in, con
                                         static_cast<hipStream_t>(stream));
 }
 
+// ------------------------------------------------------------------------------------------------ background
+int lk_cube_background_batch_dev(lk_handle *h, int B, int N, int npix, const float *cube, const uint8_t *mask, int mask_stride,
+                                 int want_scatter, float *bkg, int32_t *n_pixels, float *scatter, float *cube_out, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_background_launch(h, B, N, npix, cube, mask, mask_stride, want_scatter, bkg, n_pixels, scatter, cube_out,
+                                      static_cast<hipStream_t>(stream));
+}
+
+int lk_cube_subtract_rows_batch_dev(lk_handle *h, int B, int N, int npix, const float *cube, const float *rows, float *cube_out,
+                                    void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_subtract_rows_launch(h, B, N, npix, cube, rows, cube_out, static_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------------------------ amplitude images
 int lk_cube_ampimage_batch_dev(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const double *frequency,
                                int nterms, const double *t_ref, double *theta, double *level, double *amplitude, double *phase,

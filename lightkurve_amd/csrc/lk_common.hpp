@@ -405,6 +405,13 @@ int cube_diffimage_launch(lk_handle *h, int B, int N, int npix, const double *ti
 int diffimage_offsets_launch(lk_handle *h, int B, const int32_t *n_in, const int32_t *n_out, const double *diff_col,
                              const double *diff_row, const double *out_col, const double *out_row, double *offset,
                              double *offset_pix, int32_t *status, hipStream_t stream);
+// pixcube.hip: TargetPixelFile.estimate_background per cadence (nanmedian of the masked pixels, their count, optionally the
+// median absolute deviation) and, with cube_out, the subtracted cube from the same pass; cube - rows[b][i] for given rows.
+// Enqueued, no synchronisation, no scratch
+int cube_background_launch(lk_handle *h, int B, int N, int npix, const float *cube, const uint8_t *mask, int mask_stride,
+                           int want_scatter, float *bkg, int32_t *n_pixels, float *scatter, float *cube_out, hipStream_t stream);
+int cube_subtract_rows_launch(lk_handle *h, int B, int N, int npix, const float *cube, const float *rows, float *cube_out,
+                              hipStream_t stream);
 // ampimage.hip: the per-pixel sinusoid fit of B resident cutouts at one frequency each (host arrays), coefficient- and harmonic-
 // major images; then the centroid offsets and statuses.  Everything else on the device; enqueued, no synchronisation
 int cube_ampimage_launch(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const double *frequency_host,

@@ -433,6 +433,242 @@ __global__ __launch_bounds__(256) void cube_median_image_kernel(const float *__r
     }
 }
 
+// ------------------------------------------------------------------------------------------------ background
+// TargetPixelFile.estimate_background per cadence: bkg[b][i] = np.nanmedian(cube[b][i][mask_b]) in float32 (the mirror is
+// PixelCube.estimate_background), n_pixels = the selected pixels that are not NaN, scatter = nanmedian(|sel - bkg|) in
+// float32, and cube_out = cube - bkg over ALL pixels of the cadence.  NaN is the only excluded value, +-inf are values; an
+// even count gives (a + b) * 0.5f of the two middle values, rounded once in float32 (this file has no contraction); no value
+// gives NaN.  Selection is exact, so every output has the same bits wherever the cutout sits in a batch.
+//
+// float32 -> a key whose unsigned order is the order of the values (-0.0 below +0.0); every NaN becomes the largest key,
+// which no other value has, so the NaNs of a row sort behind its n values.
+constexpr int BG_T = 64;                 // cadences per workgroup of the small route (16 per wavefront)
+constexpr int BG_SMALL_MAX_NPIX = 224;   // the route cut: 64 rows x 225 dwords + the key lists stay below 64 KB of LDS
+constexpr unsigned BG_NAN_KEY = 0xffffffffu;
+
+__device__ __forceinline__ unsigned f32_sortable(float x) {
+    if (isnan(x)) return BG_NAN_KEY;
+    const unsigned u = (unsigned)__float_as_int(x);
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float f32_from_sortable(unsigned u) {
+    u = (u >> 31) ? (u & 0x7fffffffu) : ~u;
+    return __int_as_float((int)u);  // (BG_NAN_KEY -> 0x7fffffff, a NaN)
+}
+
+// LDS written by some lanes of a wavefront and read by others of the same one
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Median of the n keys of keys[0 .. S) that are not BG_NAN_KEY, by one wavefront: every entry is ranked by counting the
+// entries below it, (key, index) in lexicographic order, so the ranks are a permutation of 0 .. S - 1 whatever the ties and
+// the entries of rank (n - 1) / 2 and n / 2 are the middle ones.  Lane l ranks the entries l, l + 64, ...; the list is read
+// four keys per ds_read_b128 (every lane the same address: a broadcast) and is padded with BG_NAN_KEY up to a multiple of
+// four — a padding entry sits behind every real one in that order and adds to no rank.  S^2 / 64 comparisons per lane.
+__device__ __forceinline__ float wave_median_keys(const unsigned *__restrict__ keys, int S, int n, int lane) {
+    if (n <= 0) return __int_as_float(0x7fc00000);  // (n is the same in every lane)
+    const int k1 = (n - 1) >> 1, k2 = n >> 1, S4 = (S + 3) >> 2;
+    const uint4 *kv = reinterpret_cast<const uint4 *>(keys);
+    float a = 0.0f, b = 0.0f;
+    for (int j0 = 0; j0 < S; j0 += 64) {
+        const int j = j0 + lane;
+        const bool valid = j < S;
+        const unsigned k = valid ? keys[j] : BG_NAN_KEY;
+        int rank = 0;
+        for (int q = 0; q < S4; ++q) {
+            const uint4 w = kv[q];
+            const int i = 4 * q;
+            rank += (w.x < k || (w.x == k && i < j)) ? 1 : 0;
+            rank += (w.y < k || (w.y == k && i + 1 < j)) ? 1 : 0;
+            rank += (w.z < k || (w.z == k && i + 2 < j)) ? 1 : 0;
+            rank += (w.w < k || (w.w == k && i + 3 < j)) ? 1 : 0;
+        }
+        const float v = f32_from_sortable(k);
+        const unsigned long long ha = __ballot(valid && rank == k1), hb = __ballot(valid && rank == k2);
+        if (ha) a = __shfl(v, __ffsll((long long)ha) - 1);
+        if (hb) b = __shfl(v, __ffsll((long long)hb) - 1);
+    }
+    return k1 == k2 ? a : (a + b) * 0.5f;
+}
+
+// tile[row * pitch + column] - sub[row] -> rows x npix floats that are CONTIGUOUS in global memory: stage_contiguous backwards
+__device__ __forceinline__ void unstage_contiguous_minus(const float *__restrict__ tile, const float *__restrict__ sub,
+                                                         float *__restrict__ g, int total, int npix, int pitch) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int mis = (int)((reinterpret_cast<uintptr_t>(g) >> 2) & 3);
+    const int head = min(total, (4 - mis) & 3);
+    if (tid < head) g[tid] = tile[(tid / npix) * pitch + tid % npix] - sub[tid / npix];
+    const int nvec = (total - head) >> 2;
+    float4 *gv = reinterpret_cast<float4 *>(g + head);
+#pragma unroll 4
+    for (int v = tid; v < nvec; v += nt) {
+        const int i = head + 4 * v;
+        int r = i / npix, c = i - r * npix;
+        float e[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            e[k] = tile[r * pitch + c] - sub[r];
+            if (++c == npix) {
+                c = 0;
+                ++r;
+            }
+        }
+        gv[v] = make_float4(e[0], e[1], e[2], e[3]);
+    }
+    const int i = head + 4 * nvec + tid;
+    if (i < total) g[i] = tile[(i / npix) * pitch + i % npix] - sub[i / npix];
+}
+
+// Small route (npix <= BG_SMALL_MAX_NPIX): a workgroup stages BG_T consecutive cadences of one cutout (contiguous in memory)
+// in LDS with 16-byte loads, lists the selected pixel numbers of the cutout's mask in ascending order once, and every
+// wavefront takes the cadences wave, wave + 4, ... of the tile: the keys of its selected pixels go to the wavefront's own
+// list, wave_median_keys finds the median, the keys of |v - bkg| replace them for the scatter.  The subtracted tile leaves
+// with 16-byte stores.  The cube is read once and written once.
+__global__ __launch_bounds__(256) void cube_background_kernel(const float *__restrict__ cube, const uint8_t *__restrict__ mask,
+                                                              int mask_stride, int N, int npix, int pitch, int want_scatter,
+                                                              float *__restrict__ bkg_out, int *__restrict__ npix_out,
+                                                              float *__restrict__ scatter_out, float *__restrict__ cube_out) {
+    extern __shared__ __align__(16) float bg_tile[];
+    __shared__ __align__(16) unsigned s_keys[4][BG_SMALL_MAX_NPIX];
+    __shared__ int s_sel[BG_SMALL_MAX_NPIX];
+    __shared__ float s_bkg[BG_T];
+    __shared__ int s_wcnt[4];
+    const int b = blockIdx.y, c0 = blockIdx.x * BG_T, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int rows = min(BG_T, N - c0);
+    const size_t off = ((size_t)b * N + c0) * npix;
+    stage_contiguous(cube + off, bg_tile, rows * npix, npix, pitch);
+    // the selected pixels in ascending order (npix <= 256 threads: one ballot per wavefront, offsets from the four counts)
+    const bool on = tid < npix && mask[(size_t)b * mask_stride + tid] != 0;
+    const unsigned long long bal = __ballot(on);
+    if (lane == 0) s_wcnt[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0, S = 0;
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) before += s_wcnt[w];
+        S += s_wcnt[w];
+    }
+    if (on) s_sel[before + __popcll(bal & ((1ull << lane) - 1ull))] = tid;
+    __syncthreads();
+    unsigned *keys = s_keys[wave];
+    const int S4 = (S + 3) & ~3;
+    for (int r = wave; r < rows; r += 4) {
+        const float *row = bg_tile + r * pitch;
+        int n = 0;
+        for (int j = lane; j < S4; j += 64) {
+            const unsigned k = j < S ? f32_sortable(row[s_sel[j]]) : BG_NAN_KEY;
+            keys[j] = k;
+            n += k != BG_NAN_KEY ? 1 : 0;
+        }
+        for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+        wave_lds_sync();
+        const float med = wave_median_keys(keys, S, n, lane);
+        float sc = 0.0f;
+        if (want_scatter) {
+            wave_lds_sync();  // every lane has read the keys
+            int n2 = 0;
+            for (int j = lane; j < S; j += 64) {
+                const unsigned k = f32_sortable(fabsf(f32_from_sortable(keys[j]) - med));
+                keys[j] = k;
+                n2 += k != BG_NAN_KEY ? 1 : 0;
+            }
+            for (int o = 32; o > 0; o >>= 1) n2 += __shfl_xor(n2, o);
+            wave_lds_sync();
+            sc = wave_median_keys(keys, S, n2, lane);
+        }
+        wave_lds_sync();  // ... before the next cadence's keys overwrite them
+        if (lane == 0) {
+            const size_t o = (size_t)b * N + c0 + r;
+            bkg_out[o] = med;
+            npix_out[o] = n;
+            if (want_scatter) scatter_out[o] = sc;
+            s_bkg[r] = med;
+        }
+    }
+    if (!cube_out) return;  // (the whole workgroup)
+    __syncthreads();
+    unstage_contiguous_minus(bg_tile, s_bkg, cube_out + off, rows * npix, npix, pitch);
+}
+
+// Large route: one workgroup per cadence over global memory (the row stays in the caches between the passes), the radix
+// select of block_select.hpp on the values widened to float64 — exact and order-preserving; the two middle values come back
+// as they are and meet in float32.
+__global__ __launch_bounds__(256) void cube_background_wide_kernel(const float *__restrict__ cube, const uint8_t *__restrict__ mask,
+                                                                   int mask_stride, int N, int npix, int want_scatter,
+                                                                   float *__restrict__ bkg_out, int *__restrict__ npix_out,
+                                                                   float *__restrict__ scatter_out, float *__restrict__ cube_out) {
+    __shared__ unsigned long long sh[264];
+    const int b = blockIdx.y, i = blockIdx.x, tid = threadIdx.x;
+    const size_t off = ((size_t)b * N + i) * npix;
+    const float *row = cube + off;
+    const uint8_t *m = mask + (size_t)b * mask_stride;
+    const float nan = __int_as_float(0x7fc00000);
+    auto median = [&](auto val, auto keep, long long &cnt) -> float {
+        long long c = 0;
+        for (int p = tid; p < npix; p += 256) c += keep(p) ? 1 : 0;
+        cnt = block_count_dyn(c, reinterpret_cast<long long *>(sh));
+        if (cnt <= 0) return nan;  // (the whole workgroup)
+        const float a = (float)block_select_kth(npix, (cnt - 1) / 2, val, keep, sh);
+        if (cnt & 1) return a;
+        const float hi = (float)block_select_kth(npix, cnt / 2, val, keep, sh);
+        return (a + hi) * 0.5f;
+    };
+    long long n = 0, n2 = 0;
+    const float med = median([&](int p) { return (double)row[p]; }, [&](int p) { return m[p] != 0 && !isnan(row[p]); }, n);
+    float sc = 0.0f;
+    if (want_scatter)
+        sc = median([&](int p) { return (double)fabsf(row[p] - med); },
+                    [&](int p) { return m[p] != 0 && !isnan(row[p] - med); }, n2);
+    if (tid == 0) {
+        const size_t o = (size_t)b * N + i;
+        bkg_out[o] = med;
+        npix_out[o] = (int)n;
+        if (want_scatter) scatter_out[o] = sc;
+    }
+    if (cube_out)
+        for (int p = tid; p < npix; p += 256) cube_out[off + p] = row[p] - med;
+}
+
+// cube_out = cube - rows[b][i] for rows given by the caller.  A workgroup walks a share of one cutout (N * npix < 2^31
+// values): 16-byte loads and stores where source and destination are misaligned alike, else value by value.
+__global__ __launch_bounds__(256) void cube_subtract_rows_kernel(const float *__restrict__ cube, const float *__restrict__ rows,
+                                                                 int N, int npix, float *__restrict__ cube_out) {
+    const int b = blockIdx.y, total = N * npix;
+    const int t = blockIdx.x * 256 + threadIdx.x, nt = gridDim.x * 256;
+    const float *g = cube + (size_t)b * total;
+    const float *sub = rows + (size_t)b * N;
+    float *o = cube_out + (size_t)b * total;
+    if (((reinterpret_cast<uintptr_t>(g) ^ reinterpret_cast<uintptr_t>(o)) & 15) != 0) {
+        for (long long i = t; i < total; i += nt) o[i] = g[i] - sub[(int)i / npix];
+        return;
+    }
+    const int mis = (int)((reinterpret_cast<uintptr_t>(g) >> 2) & 3);
+    const int head = min(total, (4 - mis) & 3);
+    if (t < head) o[t] = g[t] - sub[t / npix];
+    const int nvec = (total - head) >> 2;
+    const float4 *gv = reinterpret_cast<const float4 *>(g + head);
+    float4 *ov = reinterpret_cast<float4 *>(o + head);
+    for (int v = t; v < nvec; v += nt) {
+        const float4 x = gv[v];
+        const int i = head + 4 * v;
+        int r = i / npix, c = i - r * npix;
+        float e[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            e[k] = e[k] - sub[r];
+            if (++c == npix) {
+                c = 0;
+                ++r;
+            }
+        }
+        ov[v] = make_float4(e[0], e[1], e[2], e[3]);
+    }
+    const int tail = head + 4 * nvec;
+    if (t < total - tail) o[tail + t] = g[tail + t] - sub[(tail + t) / npix];
+}
+
 // One workgroup per cutout: exclusive scan of keep -> src[j] = cadence of the j-th kept one, the compacted time / SAP flux
 // / error columns (float64 = the float32 sums widened; lcf = the float32 flux itself) and the spline knots
 // [t[0], lerp(t[lo], t[lo + 1], g) per interior knot, t[n - 1]] (np.percentile of non-decreasing times: numpy's _lerp,
@@ -803,6 +1039,41 @@ int cube_median_image_launch(lk_handle *h, int B, int N, int npix, const float *
     LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
     hipLaunchKernelGGL(cube_median_image_kernel, dim3((npix + MED_G - 1) / MED_G, B), dim3(256), 0, stream, cube, keep, N, npix,
                        median);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+int cube_background_launch(lk_handle *h, int B, int N, int npix, const float *cube, const uint8_t *mask, int mask_stride,
+                           int want_scatter, float *bkg, int32_t *n_pixels, float *scatter, float *cube_out, hipStream_t stream) {
+    (void)h;
+    LK_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && npix >= 1, "need 1 <= B <= 65535, N >= 1, npix >= 1");
+    LK_REQUIRE(cube && mask && bkg && n_pixels, "NULL buffer");
+    LK_REQUIRE(!want_scatter || scatter, "want_scatter needs the scatter buffer");
+    LK_REQUIRE(cube_out != cube, "cube_out must not be the cube itself");
+    LK_REQUIRE(mask_stride == 0 || mask_stride == npix, "mask_stride must be 0 (one mask for the batch) or npix");
+    LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
+    // the route depends on npix alone: a cutout's bits are the same in any batch
+    if (npix <= BG_SMALL_MAX_NPIX) {
+        const int pitch = npix | 1;
+        hipLaunchKernelGGL(cube_background_kernel, dim3((N + BG_T - 1) / BG_T, B), dim3(256), (size_t)BG_T * pitch * 4, stream, cube,
+                           mask, mask_stride, N, npix, pitch, want_scatter ? 1 : 0, bkg, (int *)n_pixels, scatter, cube_out);
+    } else {
+        hipLaunchKernelGGL(cube_background_wide_kernel, dim3(N, B), dim3(256), 0, stream, cube, mask, mask_stride, N, npix,
+                           want_scatter ? 1 : 0, bkg, (int *)n_pixels, scatter, cube_out);
+    }
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
+int cube_subtract_rows_launch(lk_handle *h, int B, int N, int npix, const float *cube, const float *rows, float *cube_out,
+                              hipStream_t stream) {
+    (void)h;
+    LK_REQUIRE(B >= 1 && B <= 65535 && N >= 1 && npix >= 1, "need 1 <= B <= 65535, N >= 1, npix >= 1");
+    LK_REQUIRE(cube && rows && cube_out, "NULL buffer");
+    LK_REQUIRE((int64_t)N * npix < (int64_t)1 << 31, "a cutout of %d x %d values is too large", N, npix);
+    // 4 values per thread and 4 trips: enough workgroups in flight per cutout to stream, few enough to amortise their start
+    const int gx = (int)std::min<int64_t>(((int64_t)N * npix + 4095) / 4096, 1024);
+    hipLaunchKernelGGL(cube_subtract_rows_kernel, dim3(gx, B), dim3(256), 0, stream, cube, rows, N, npix, cube_out);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }

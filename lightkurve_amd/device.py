@@ -1513,7 +1513,7 @@ class DevicePixelCubeBatch(object):
     finite and non-decreasing per cutout (the knots are gathered from sorted times) — ``pld_correct_batch`` takes what does
     not fit."""
 
-    def __init__(self, d_time, d_flux, d_flux_err, time, shape, meta=None, device=0, stream=0):
+    def __init__(self, d_time, d_flux, d_flux_err, time, shape, meta=None, device=0, stream=0, is_sorted=None):
         self.handle = _capi.Handle.get(device)
         self.device = int(device)
         self.stream = int(stream or 0)
@@ -1525,7 +1525,8 @@ class DevicePixelCubeBatch(object):
         self.time = np.ascontiguousarray(time, dtype=np.float64).reshape(B, N)      # host copy (B x N doubles)
         # checked here, on the host's copy; raised by pld_correct — a file whose kept cadences lack a TIME (read as 0.0 like
         # TargetPixelFile.time does) still round-trips and still has aperture photometry
-        self.is_sorted = _cube_times_sorted(self.time)
+        # (is_sorted: what a batch that shares its parent's times already knows)
+        self.is_sorted = _cube_times_sorted(self.time) if is_sorted is None else bool(is_sorted)
         self.meta = list(meta) if meta is not None else [{} for _ in range(B)]
         self._keep = []                                              # host staging the stream may still be reading
 
@@ -1843,6 +1844,100 @@ class DevicePixelCubeBatch(object):
         out = (d_c.download(np.float64, B * N, stream=self.stream).reshape(B, N),
                d_r.download(np.float64, B * N, stream=self.stream).reshape(B, N))
         return out + (d_p.download(np.int32, B * N, stream=self.stream).reshape(B, N),) if return_peak else out
+
+    # ---------------------------------------------------------------- background
+    def _background(self, aperture_mask, want_scatter, subtract):
+        """One launch of ``lk_cube_background_batch_dev`` -> (masks bool (B, ny, nx), d_bkg, d_n_pixels, d_scatter or None,
+        d_cube_out or None), enqueued on the batch's stream."""
+        h, (B, N, ny, nx) = self.handle, self.shape
+        npix = ny * nx
+        m = self._masks(aperture_mask, False, None, {})
+        d_mask, k = _upload(h, m.reshape(-1, npix), self.stream, np.uint8)
+        d_bkg, d_n = DeviceBuffer(h, B * N * 4), DeviceBuffer(h, B * N * 4)
+        d_sc = DeviceBuffer(h, B * N * 4) if want_scatter else None
+        d_out = DeviceBuffer(h, B * N * npix * 4) if subtract else None
+        _capi._check(_capi._lib.lk_cube_background_batch_dev(
+            h._h, B, N, npix, _vp(self.d_flux.ptr), _vp(d_mask.ptr), npix if m.ndim == 3 else 0, int(bool(want_scatter)),
+            _vp(d_bkg.ptr), _vp(d_n.ptr), _vp(d_sc.ptr if want_scatter else None), _vp(d_out.ptr if subtract else None),
+            _vp(self.stream or None)))
+        self._keep.extend([k, d_mask])
+        return np.ascontiguousarray(np.broadcast_to(m, (B, ny, nx))), d_bkg, d_n, d_sc, d_out
+
+    def estimate_background(self, aperture_mask="background", return_scatter=False, to_host=True):
+        """``PixelCube.estimate_background(aperture_mask, return_scatter)`` of every cutout, value for value
+        (``lk_cube_background_batch_dev``; ``TargetPixelFile.estimate_background``): per cadence the float32 ``np.nanmedian`` of the
+        pixels in ``aperture_mask`` — 'background' (default: each cutout's own complement of ``threshold_masks(0, None)``, made on
+        the device from the cube as it is), 'all', 'threshold', a bool (ny, nx) mask or one per cutout (B, ny, nx).  Returns a dict:
+        ``flux`` float32 (B, N); ``n_pixels`` int32 (B, N), the masked pixels that are not NaN; ``mask`` bool (B, ny, nx);
+        with ``return_scatter`` also ``scatter`` float32 (B, N), the median absolute deviation from ``flux``.  A cadence without a
+        value is NaN.  ``to_host=False``: ``flux`` / ``n_pixels`` / ``scatter`` are ``DeviceBuffer``s enqueued on the batch's
+        stream (``mask`` stays a host array: it is B x npix bytes and was made to be uploaded).  The cube does not move."""
+        B, N = self.shape[:2]
+        m, d_bkg, d_n, d_sc, _ = self._background(aperture_mask, return_scatter, False)
+        out = {"flux": d_bkg, "n_pixels": d_n, "mask": m}
+        if return_scatter:
+            out["scatter"] = d_sc
+        if to_host:
+            for key, dt in (("flux", np.float32), ("n_pixels", np.int32), ("scatter", np.float32)):
+                if key in out:
+                    out[key] = out[key].download(dt, B * N, stream=self.stream).reshape(B, N)
+            self._keep = []
+        return out
+
+    def subtract_background(self, background=None, aperture_mask="background", return_background=False):
+        """``PixelCube.subtract_background`` of every cutout -> a new ``DevicePixelCubeBatch`` whose ``d_flux`` is ``flux -
+        bkg[:, :, None, None]`` in float32.  ``background=None``: the estimate over ``aperture_mask`` (see
+        ``estimate_background``) and the subtraction in ONE launch — the cube is read once and written once.  Otherwise
+        ``background`` is a host (B, N) array, a ``DeviceBuffer`` of B x N float32, or the dict ``estimate_background`` returned
+        (either flavour), subtracted by ``lk_cube_subtract_rows_batch_dev``.  The result shares this batch's ``d_time`` and
+        ``d_flux_err`` buffers (no method of the class writes them) and its host ``time``; ``meta`` is copied and gains, per
+        cutout, ``BKG_SUBTRACTED`` = True, ``BKG_NPIX`` = the pixels of its mask (-1 when only values were given) and
+        ``BKG_NAN_CADENCES``.  The B x N background values come to the host for that count (the call synchronises);
+        ``return_background=True`` returns (batch, dict of ``flux`` (B, N) and, when a mask was used, ``n_pixels`` and ``mask``)."""
+        h, (B, N, ny, nx) = self.handle, self.shape
+        npix = ny * nx
+        info = {}
+        if background is None:
+            m, d_bkg, d_n, _, d_out = self._background(aperture_mask, False, True)
+            bkg = d_bkg.download(np.float32, B * N, stream=self.stream).reshape(B, N)
+            info = {"flux": bkg, "mask": m}
+            if return_background:
+                info["n_pixels"] = d_n.download(np.int32, B * N, stream=self.stream).reshape(B, N)
+            counts = m.reshape(B, npix).sum(axis=1)
+        else:
+            counts = np.full(B, -1)
+            if isinstance(background, dict):
+                if np.shape(background["mask"]) != (B, ny, nx):
+                    raise ValueError("the background's masks have shape %r, this batch needs %r"
+                                     % (np.shape(background["mask"]), (B, ny, nx)))
+                counts = np.asarray(background["mask"], dtype=bool).reshape(B, npix).sum(axis=1)
+                info = {key: background[key] for key in ("mask", "n_pixels") if key in background}
+                background = background["flux"]
+            keep = None
+            if isinstance(background, DeviceBuffer):
+                if background.nbytes != B * N * 4:
+                    raise ValueError("a background of %d bytes for %d x %d float32 cadences" % (background.nbytes, B, N))
+                d_rows = background
+                bkg = d_rows.download(np.float32, B * N, stream=self.stream).reshape(B, N)
+            else:
+                bkg = np.asarray(background, dtype=np.float32)
+                if bkg.shape != (B, N):
+                    raise ValueError("background must be (B, N) = %r, one value per cadence (got %r)" % ((B, N), bkg.shape))
+                d_rows, keep = _upload(h, bkg, self.stream, np.float32)
+            if isinstance(info.get("n_pixels"), DeviceBuffer):
+                info["n_pixels"] = info["n_pixels"].download(np.int32, B * N, stream=self.stream).reshape(B, N)
+            info["flux"] = bkg
+            d_out = DeviceBuffer(h, B * N * npix * 4)
+            _capi._check(_capi._lib.lk_cube_subtract_rows_batch_dev(h._h, B, N, npix, _vp(self.d_flux.ptr), _vp(d_rows.ptr),
+                                                                    _vp(d_out.ptr), _vp(self.stream or None)))
+        nan_cadences = np.isnan(bkg).sum(axis=1)
+        meta = [dict(mb, BKG_SUBTRACTED=True, BKG_NPIX=int(counts[b]), BKG_NAN_CADENCES=int(nan_cadences[b]))
+                for b, mb in enumerate(self.meta)]          # (the keys of PixelCube.subtract_background)
+        out = DevicePixelCubeBatch(self.d_time, d_out, self.d_flux_err, self.time, self.shape, meta, self.device, self.stream,
+                                   is_sorted=self.is_sorted)
+        if background is not None:
+            out._keep = [keep, d_rows]          # what the enqueued subtraction still reads
+        return (out, info) if return_background else out
 
     # ---------------------------------------------------------------- difference images
     def difference_images(self, period, transit_time, duration, in_width=0.5, out_inner=1.0, out_outer=2.0, aperture_mask="all",

@@ -125,7 +125,14 @@ profiles/diffimage_walls.txt.
 R `cubes.amplitude_images(frequency, nterms=1)` and R3 the same with `nterms=3`, images on the host at the end; D
 `cubes.difference_images(...)` of the same cubes, the other kernel family with this chunking (it reads the rows of the in- and
 out-of-transit cadences of two cubes; the floor of R is two reads of every row of the flux cube); H the host route: `to_host()`, then `PixelCube.amplitude_image` per cutout on 16 threads.  Every
-timed region ends with a synchronise.  Written to profiles/ampimage_walls.txt."""
+timed region ends with a synchronise.  Written to profiles/ampimage_walls.txt.
+
+`background`: the per-cadence background of the same batch shape with 'background' masks, in ONE process, the routes alternating,
+`LK_WALLS_REPS` (default 5) times after one warm-up.  F `cubes.subtract_background()` (median images, masks, the fused estimate +
+subtraction) and Fm the same with the masks given; E `cubes.estimate_background()`, Em with the masks given, Es with the scatter
+too; S `cubes.subtract_background(background=DeviceBuffer)`, the streaming subtraction alone; H the host route: `to_host()`,
+`PixelCube.subtract_background` per cutout on 16 threads, `from_cubes`.  Every timed region ends with a synchronise.  Written to
+profiles/background_walls.txt."""
 import cProfile
 import io
 import os
@@ -1237,6 +1244,76 @@ def ampimage():
         "  R / D = %.2f; R3 / D = %.2f; H / R = %.1f; kernel times alone: profiles/ampimage_kernels.txt" % (med["R"] / med["D"], med["R3"] / med["D"], med["H"] / med["R"])])
 
 
+def background():
+    from concurrent.futures import ThreadPoolExecutor
+    from lightkurve_amd.device import DevicePixelCubeBatch
+    B, N, side = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "500"), ("LK_WALLS_N", "4000"), ("LK_WALLS_SIDE", "11")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "5"))
+    rng = np.random.default_rng(43)
+    t = 1000.0 + np.arange(N) / 48.0
+    yy, xx = np.indices((side, side))
+    c = side // 2
+    star = (1000.0 * np.exp(-((xx - c) ** 2 + (yy - c) ** 2) / 1.62)).astype(np.float32)
+    flux = np.empty((B, N, side, side), dtype=np.float32)
+    for b in range(B):                                                  # (drawn per cutout: 1.9 GB of cubes in all)
+        sky = (150.0 + 60.0 * np.sin(2 * np.pi * (t - t[0]) / 13.7 + b)).astype(np.float32)     # scattered light, per cadence
+        flux[b] = star * np.float32(0.5 + rng.random()) + sky[:, None, None] + 3.0 * rng.standard_normal((N, side, side), dtype=np.float32)
+    err = np.full_like(flux, 3.0)
+    cubes = DevicePixelCubeBatch.from_arrays(np.tile(t, (B, 1)), flux, err)
+    cubes.synchronize()
+    del flux, err
+    masks = cubes.estimate_background()["mask"]                          # the 'background' masks, made once for Fm / Em
+    given = cubes.estimate_background(to_host=False)["flux"]             # a resident background for S
+
+    def synced(fn):
+        def run():
+            out = fn()
+            cubes.synchronize()
+            return out
+        return run
+
+    def through_host():
+        host = cubes.to_host()
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            sub = list(ex.map(lambda c: c.subtract_background(), host))
+        out = DevicePixelCubeBatch.from_cubes(sub)
+        out.synchronize()
+        return out
+
+    fns = {"F": synced(lambda: cubes.subtract_background()), "Fm": synced(lambda: cubes.subtract_background(aperture_mask=masks)),
+           "E": synced(lambda: cubes.estimate_background()), "Em": synced(lambda: cubes.estimate_background(masks)),
+           "Es": synced(lambda: cubes.estimate_background(masks, return_scatter=True)),
+           "S": synced(lambda: cubes.subtract_background(background=given)), "H": through_host}
+    first = {}
+    for k, fn in fns.items():                                            # warm-up of every route; F and H are compared below
+        out = fn()
+        if k in ("F", "H"):
+            first[k] = [np.array(c.flux) for c in out.to_host()[::max(B // 8, 1)]]
+        del out
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    cube_mb = B * N * side * side * 4 / 1e6
+    same = all(np.array_equal(a, b, equal_nan=True) for a, b in zip(first["F"], first["H"]))
+    write_walls("background_walls.txt", [
+        "per-cadence background, %d cutouts x %d cadences x %d x %d float32, 'background' masks of %d .. %d pixels (%.1f MB of flux; "
+        "a fused call reads it once and writes it once)" % (B, N, side, side, masks.reshape(B, -1).sum(axis=1).min(),
+                                                         masks.reshape(B, -1).sum(axis=1).max(), cube_mb),
+        "  F    cubes.subtract_background(): median images, masks, estimate + subtraction in one launch, B x N values back  %s" % spread(ts["F"]),
+        "  Fm   the same with the masks given (B, ny, nx): the fused launch and the B x N values back                      %s" % spread(ts["Fm"]),
+        "  E    cubes.estimate_background(): median images, masks, estimate; flux and n_pixels on the host                 %s" % spread(ts["E"]),
+        "  Em   the same with the masks given                                                                              %s" % spread(ts["Em"]),
+        "  Es   Em with return_scatter=True                                                                                %s" % spread(ts["Es"]),
+        "  S    cubes.subtract_background(background=DeviceBuffer): the streaming subtraction, B x N values back           %s" % spread(ts["S"]),
+        "  H    to_host(), PixelCube.subtract_background per cutout on 16 threads, from_cubes                              %s" % spread(ts["H"]),
+        "  F and H: the same subtracted pixels in every 1 of 8 cutouts compared: %s" % same,
+        "  bytes / wall: Fm %.0f GB/s of %.1f MB, S %.0f GB/s of %.1f MB, Em %.0f GB/s of %.1f MB; H / F = %.1f; F - Fm = %.2f ms of masks"
+        % (2 * cube_mb / 1e3 / med["Fm"], 2 * cube_mb, 2 * cube_mb / 1e3 / med["S"], 2 * cube_mb, cube_mb / 1e3 / med["Em"], cube_mb,
+           med["H"] / med["F"], 1e3 * (med["F"] - med["Fm"]))])
+
+
 def stitch(which=("stitch",)):
     from concurrent.futures import ThreadPoolExecutor
     from lightkurve_amd import _capi
@@ -1397,6 +1474,8 @@ def main():
         diffimage()
     if "ampimage" in which:
         ampimage()
+    if "background" in which:
+        background()
     if {"stitch", "stitch_trace"} & set(which):
         stitch(which)
     if "flatten" in which:
