@@ -950,7 +950,9 @@ int lk_savgol_trend_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, co
                               const uint8_t *mask, int window, int polyorder, double break_tol, int niters,
                               double sigma, double *trend, uint8_t *fit_mask, void *stream);
 /* Host-only helper (no GPU): the FIR taps (window doubles) and the two edge-refit operators
- * (2 x (window/2) x window doubles, left then right) the kernel uses == scipy savgol_coeffs / mode='interp'. */
+ * (2 x (window/2) x window doubles, left then right) the kernel uses == scipy savgol_coeffs / mode='interp' in exact
+ * arithmetic: rows of the least-squares hat matrix, each entry within one ulp of the row's largest weight of the exact value
+ * for every polyorder 0..15 (scipy's own taps lose all digits towards polyorder 15). */
 int lk_savgol_design(int window, int polyorder, double *coeffs, double *edge);
 
 /* ---- PLDCorrector.create_design_matrix (correctors/pldcorrector.py:186-287) for B same-shaped cutouts --------
@@ -1266,7 +1268,9 @@ int lk_sff_correct_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, con
  *                          x: B x N; knots: B x (n_inner + 2) = [lower bound, interior knots, upper bound];
  *                          out: B x N x (n_inner + degree + 1).  (include_intercept=False drops column 0.)
  * lk_standardize_batch  <- DesignMatrix.standardize, designmatrix.py:215-250: per column, zeros are missing values;
- *                          (x - nanmedian) / nanstd of the rest, missing -> 0, constant columns unchanged. */
+ *                          (x - nanmedian) / nanstd of the rest, missing -> 0.  A column whose remaining values are all equal
+ *                          (min == max, whether the value is representable or not) is left unchanged; a column holding
+ *                          +-inf (no finite median or deviation) comes back as zeros. */
 int lk_pca_batch(lk_handle *h, int B, int N, int P, int k, const double *A, double *U);
 int lk_pca_batch_dev(lk_handle *h, int B, int N, int P, int k, const double *A, double *U, void *stream);
 int lk_spline_basis_batch(lk_handle *h, int B, int N, const double *x, const double *knots, int n_inner, int degree,

@@ -86,8 +86,9 @@ class DesignMatrix(object):
         return dm
 
     def standardize(self, inplace=False, device=0):
-        """Columns median-subtracted and sigma-divided, zeros treated as missing, constant columns unchanged (reference
-        :215-250) — on the GPU (lk_standardize_batch: one radix-select median per column)."""
+        """Columns median-subtracted and sigma-divided, zeros treated as missing, constant columns (all remaining values
+        equal, whether representable or not) unchanged, columns holding +-inf zeroed (reference :215-250) — on the GPU
+        (lk_standardize_batch: one radix-select median per column)."""
         from .. import _capi
         dm = self if inplace else self.copy()
         dm.values = _capi.standardize_batch(self.values, device=device)
@@ -227,12 +228,18 @@ def create_spline_matrix(x, n_knots=20, knots=None, degree=3, name="spline", inc
     """DesignMatrix of B-splines as ``patsy.dmatrix("bs(x, df|knots, degree, include_intercept) - 1")`` builds it (reference
     designmatrix.py:952-997): with ``knots`` the given interior knots, otherwise ``n_knots`` = df columns whose interior
     knots are equally spaced quantiles of x (numpy's linear-interpolation percentiles, as patsy takes them); the boundary
-    knots are min(x) and max(x).  The basis itself is evaluated on the GPU (lk_spline_basis_batch, de Boor)."""
+    knots are min(x) and max(x), and a given knot outside them is a ValueError, as in patsy.  The basis itself is evaluated on
+    the GPU (lk_spline_basis_batch, de Boor)."""
     from .. import _capi
     x = np.asarray(x, dtype=np.float64)
     order = int(degree) + 1
     if knots is not None:
         inner = np.sort(np.asarray(knots, dtype=np.float64))
+        # patsy's bs() raises for a knot outside the bounds too (one equal to a bound is accepted): the knot vector would not
+        # be monotone and the basis meaningless
+        if inner.size and not (np.min(x) <= inner[0] and inner[-1] <= np.max(x)):
+            raise ValueError("interior knots {} outside the data range [{}, {}]".format(
+                inner[(inner < np.min(x)) | (inner > np.max(x))], np.min(x), np.max(x)))
     else:
         n_inner = int(n_knots) - order + (0 if include_intercept else 1)
         if n_inner < 0:

@@ -46,10 +46,49 @@ static bool solve_small(std::vector<long double> &M, std::vector<long double> &b
 
 // coeffs[w]: FIR taps (scipy savgol_coeffs(w, p): min-norm solution of sum_j c_j x_j^i = delta_i0 with
 // x = h..-h; symmetric for deriv=0).  edge[2][half][w]: rows of E for outputs 0..half-1 from the first w samples
-// and outputs w-half..w-1 from the last w samples.  Abscissae are scaled to [-1, 1] for conditioning.
-static bool savgol_design(int w, int p, std::vector<double> &coeffs, std::vector<double> &edge,
-                          long double *tap_poly = nullptr,  // tap_poly[a]: c_j = sum_a tap_poly[a] ((half - j) / half)^a
-                          std::vector<double> *edge_minv = nullptr) {  // (p+1)^2: inverse moment matrix of the edge fit
+// and outputs w-half..w-1 from the last w samples.
+// Both are rows of the hat matrix H = V (V^T V)^-1 V^T of the polynomial fit over w equally spaced points, built from the
+// orthonormal discrete (Gram) polynomials q_0..q_p of those points: H[i][j] = sum_k q_k(i) q_k(j), with
+// x q_k = b_{k+1} q_{k+1} + b_k q_{k-1}, b_k = (k / 2) sqrt((w^2 - k^2) / (4 k^2 - 1)), x = i - (w - 1) / 2.  No system is
+// solved, so every entry is the exact one rounded to double (at most one ulp of the row's largest weight off, checked against
+// rational arithmetic for every polyorder up to 15); the monomial normal equations lose six digits at polyorder 15.
+static void savgol_design(int w, int p, std::vector<double> &coeffs, std::vector<double> &edge) {
+    const int half = w / 2, np1 = p + 1;
+    std::vector<long double> q((size_t)np1 * w);
+    const long double c0 = (long double)(w - 1) / 2.0L;
+    for (int i = 0; i < w; ++i) q[i] = 1.0L / sqrtl((long double)w);
+    long double b_prev = 0.0L;
+    for (int k = 1; k < np1; ++k) {
+        const long double kk = (long double)k;
+        const long double bk = kk / 2.0L * sqrtl(((long double)w * w - kk * kk) / (4.0L * kk * kk - 1.0L));
+        for (int i = 0; i < w; ++i) {
+            const long double x = (long double)i - c0;
+            const long double below = k > 1 ? b_prev * q[(size_t)(k - 2) * w + i] : 0.0L;
+            q[(size_t)k * w + i] = (x * q[(size_t)(k - 1) * w + i] - below) / bk;
+        }
+        b_prev = bk;
+    }
+    auto hat = [&](int i, int j) {
+        long double s = 0.0L;
+        for (int k = 0; k < np1; ++k) s += q[(size_t)k * w + i] * q[(size_t)k * w + j];
+        return (double)s;
+    };
+    coeffs.assign(w, 0.0);
+    for (int j = 0; j < w; ++j) coeffs[j] = hat(half, w - 1 - j);  // x = arange(-half, w-half)[::-1]
+    edge.assign((size_t)2 * half * w, 0.0);
+    for (int side = 0; side < 2; ++side)
+        for (int r = 0; r < half; ++r) {
+            const int pos = side == 0 ? r : (w - half + r);
+            for (int j = 0; j < w; ++j) edge[((size_t)side * half + r) * w + j] = hat(pos, j);
+        }
+}
+
+// The moment form of the same design for polyorder <= 5 (the kernels' long-window interior and edge paths): the taps as a
+// polynomial in the scaled abscissa, and the inverse moment matrix of the edge fit.  Monomial normal equations in long double,
+// abscissae scaled to [-1, 1] for conditioning.
+static bool savgol_moment_form(int w, int p,
+                               long double *tap_poly,            // tap_poly[a]: c_j = sum_a tap_poly[a] ((half - j) / half)^a
+                               std::vector<double> *edge_minv) {  // (p+1)^2: inverse moment matrix of the edge fit
     const int half = w / 2, np1 = p + 1;
     std::vector<long double> z(w);
     const long double hs = half > 0 ? (long double)half : 1.0L;
@@ -66,15 +105,8 @@ static bool savgol_design(int w, int p, std::vector<double> &coeffs, std::vector
         std::vector<long double> Mc = M;
         if (!solve_small(Mc, rhs, np1)) return false;
     }
-    if (tap_poly)
-        for (int a = 0; a < np1; ++a) tap_poly[a] = rhs[a];
-    coeffs.assign(w, 0.0);
-    for (int j = 0; j < w; ++j) {
-        long double s = 0.0L;
-        for (int a = 0; a < np1; ++a) s += rhs[a] * powl(z[j], a);
-        coeffs[j] = (double)s;
-    }
-    // edge operators: polyfit over positions 0..w-1 (scaled u), evaluated at r
+    for (int a = 0; a < np1; ++a) tap_poly[a] = rhs[a];
+    // edge fit: polyfit over positions 0..w-1 (scaled u)
     std::vector<long double> u(w);
     const long double c0 = (long double)(w - 1) / 2.0L, sc = c0 > 0 ? c0 : 1.0L;
     for (int j = 0; j < w; ++j) u[j] = ((long double)j - c0) / sc;
@@ -84,28 +116,13 @@ static bool savgol_design(int w, int p, std::vector<double> &coeffs, std::vector
             for (int j = 0; j < w; ++j) s += powl(u[j], a + b);
             M[a * np1 + b] = s;
         }
-    if (edge_minv) {
-        edge_minv->assign((size_t)np1 * np1, 0.0);
-        for (int b = 0; b < np1; ++b) {
-            std::vector<long double> Mc = M, g(np1, 0.0L);
-            g[b] = 1.0L;
-            if (!solve_small(Mc, g, np1)) return false;
-            for (int a = 0; a < np1; ++a) (*edge_minv)[(size_t)a * np1 + b] = (double)g[a];
-        }
+    edge_minv->assign((size_t)np1 * np1, 0.0);
+    for (int b = 0; b < np1; ++b) {
+        std::vector<long double> Mc = M, g(np1, 0.0L);
+        g[b] = 1.0L;
+        if (!solve_small(Mc, g, np1)) return false;
+        for (int a = 0; a < np1; ++a) (*edge_minv)[(size_t)a * np1 + b] = (double)g[a];
     }
-    edge.assign((size_t)2 * half * w, 0.0);
-    for (int side = 0; side < 2; ++side)
-        for (int r = 0; r < half; ++r) {
-            const int pos = side == 0 ? r : (w - half + r);
-            std::vector<long double> Mc = M, g(np1);
-            for (int a = 0; a < np1; ++a) g[a] = powl(u[pos], a);
-            if (!solve_small(Mc, g, np1)) return false;  // g = M^-1 v(pos)  (M symmetric)
-            for (int j = 0; j < w; ++j) {
-                long double s = 0.0L;
-                for (int a = 0; a < np1; ++a) s += g[a] * powl(u[j], a);
-                edge[((size_t)side * half + r) * w + j] = (double)s;
-            }
-        }
     return true;
 }
 
@@ -114,7 +131,7 @@ int savgol_design_host(int window, int polyorder, double *coeffs, double *edge) 
     LK_REQUIRE(polyorder >= 0 && polyorder < window && polyorder <= 15, "polyorder must be less than window_length");
     LK_REQUIRE(coeffs && edge, "NULL buffer");
     std::vector<double> c, e;
-    LK_REQUIRE(savgol_design(window, polyorder, c, e), "singular Savitzky-Golay design");
+    savgol_design(window, polyorder, c, e);
     std::copy(c.begin(), c.end(), coeffs);
     std::copy(e.begin(), e.end(), edge);
     return LK_OK;
@@ -1030,8 +1047,10 @@ int flatten_launch(lk_handle *h, int B, const int64_t *n_off_host, const double 
         std::vector<double> coeffs, edge;
         long double tap_poly[16] = {0};
         std::vector<double> minv;
-        LK_REQUIRE(savgol_design(window, polyorder, coeffs, edge, tap_poly, &minv),
-                   "singular Savitzky-Golay design (window %d, order %d)", window, polyorder);
+        savgol_design(window, polyorder, coeffs, edge);
+        if (polyorder <= 5)  // the moment form is used up to there only
+            LK_REQUIRE(savgol_moment_form(window, polyorder, tap_poly, &minv),
+                       "singular Savitzky-Golay design (window %d, order %d)", window, polyorder);
         Design d{h->device, window, polyorder, nullptr, nullptr, nullptr, 0.0, 0.0};
         if (polyorder <= 5 && window >= 3) {
             LK_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d.d_minv), minv.size() * 8));

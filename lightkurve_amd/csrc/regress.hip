@@ -1826,8 +1826,22 @@ int model_part_launch(lk_handle *h, int B, int N, int K, int c0, int c1, const d
 
 // ------------------------------------------------------------------------------------------------ DesignMatrix.standardize
 // correctors/designmatrix.py:215-250: per column, zeros count as missing; subtract the nanmedian and divide by the nanstd of
-// the remaining values, missing values come back as 0; a column whose values are all equal (nanstd == 0) is left unchanged.
+// the remaining values, missing values come back as 0; a column whose remaining values are all equal is left unchanged; a
+// column whose median or deviation is not finite (it holds +-inf) comes back as zeros.
 // One workgroup per (column, matrix); the column is read through a strided view (no staging copy).
+__device__ __forceinline__ double block_max_dyn(double x, double *shd) {  // workgroup maximum, the tree of block_sum_dyn
+    const int tid = threadIdx.x, nt = blockDim.x;
+    shd[tid] = x;
+    __syncthreads();
+    for (int s = nt >> 1; s > 0; s >>= 1) {
+        if (tid < s) shd[tid] = fmax(shd[tid], shd[tid + s]);
+        __syncthreads();
+    }
+    const double r = shd[0];
+    __syncthreads();
+    return r;
+}
+
 __global__ __launch_bounds__(256) void dm_standardize_kernel(const double *__restrict__ A, int N, int P, double *__restrict__ out) {
     __shared__ unsigned long long sh[264];
     const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -1838,16 +1852,34 @@ __global__ __launch_bounds__(256) void dm_standardize_kernel(const double *__res
         const double v = col[(size_t)i * P];
         return v == v && v != 0.0;
     };
+    auto zero_column = [&]() {
+        for (int i = tid; i < N; i += 256) oc[(size_t)i * P] = 0.0;
+    };
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
     long long cnt = 0;
-    double sum = 0.0;
+    double sum = 0.0, lo = inf, hi = -inf;
     for (int i = tid; i < N; i += 256)
         if (keep(i)) {
+            const double v = val(i);
             ++cnt;
-            sum += val(i);
+            sum += v;
+            lo = fmin(lo, v);
+            hi = fmax(hi, v);
         }
     const long long count = block_count_dyn(cnt, reinterpret_cast<long long *>(sh));
     if (count == 0) {  // nothing but zeros / NaN: every entry is "missing" -> 0
-        for (int i = tid; i < N; i += 256) oc[(size_t)i * P] = 0.0;
+        zero_column();
+        return;
+    }
+    // "all equal" is min == max of the kept values, not sd == 0: the mean of equal values that are not representable (0.1,
+    // 3.3) can be an ulp off them, whatever the order of the sum, and sd then comes out as 1e-17, not 0
+    const double vmin = -block_max_dyn(-lo, reinterpret_cast<double *>(sh));
+    const double vmax = block_max_dyn(hi, reinterpret_cast<double *>(sh));
+    if (vmin == vmax) {  // constant column: unchanged (its zeros were "missing" and come back as zeros)
+        for (int i = tid; i < N; i += 256) {
+            const double v = val(i);
+            oc[(size_t)i * P] = v == v ? v : 0.0;
+        }
         return;
     }
     const double mean = block_sum_dyn(sum, reinterpret_cast<double *>(sh)) / (double)count;
@@ -1858,14 +1890,11 @@ __global__ __launch_bounds__(256) void dm_standardize_kernel(const double *__res
             ss = fma(d, d, ss);
         }
     const double sd = sqrt(block_sum_dyn(ss, reinterpret_cast<double *>(sh)) / (double)count);  // numpy nanstd (ddof = 0)
-    if (sd == 0.0) {  // constant column: unchanged (its zeros were "missing" and come back as zeros)
-        for (int i = tid; i < N; i += 256) {
-            const double v = val(i);
-            oc[(size_t)i * P] = v == v ? v : 0.0;
-        }
+    const double med = block_median(N, count, val, keep, sh);
+    if (!isfinite(sd) || !isfinite(med)) {  // a +-inf value: every entry would be NaN or +-inf, the reference's fillna(0) -> 0
+        zero_column();
         return;
     }
-    const double med = block_median(N, count, val, keep, sh);
     for (int i = tid; i < N; i += 256) oc[(size_t)i * P] = keep(i) ? (val(i) - med) / sd : 0.0;
 }
 

@@ -422,6 +422,9 @@ def _make_spline_builders(lk_dm_mod):
         order = int(degree) + 1
         if knots is not None:
             inner = np.sort(np.asarray(knots, dtype=np.float64))
+            if inner.size and not (np.min(xx) <= inner[0] and inner[-1] <= np.max(xx)):     # patsy's own error message for this
+                return orig_dense(x, n_knots=n_knots, knots=knots, degree=degree, name=name,
+                                  include_intercept=include_intercept)
         else:
             n_inner = int(n_knots) - order + (0 if include_intercept else 1)
             if n_inner < 0:     # patsy's own error message for this

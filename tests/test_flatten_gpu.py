@@ -4,6 +4,7 @@ sums taps in order, so last-bit differences are expected); clip decisions identi
 import numpy as np
 import pytest
 
+import designmatrix_cases
 from lightkurve_amd import LightCurve, _capi, synth
 from lightkurve_amd.flatten import flatten_trend_batch
 from oracle import np_oracle as O
@@ -311,3 +312,24 @@ def test_segment_cuts_when_the_time_step_sample_misses_the_median():
     got = _capi.savgol_trend_batch(t, y, np.array([0, n], dtype=np.int64), window_length=51)
     ref = O.flatten_trend(t, y, window_length=51)[0]
     assert np.nanmedian(np.diff(t)) < 1.5 * u and np.allclose(got, ref, rtol=RTOL, atol=0)
+
+
+@pytest.mark.parametrize("window,polyorder", [(31, 8), (51, 10), (31, 15), (17, 15)])
+def test_high_polyorder_trend_is_the_exact_design_applied(window, polyorder):
+    """The operator-row edge path (polyorder > 5) beyond polyorder 6, where no scipy-based oracle can follow (scipy's own taps
+    are off by 100 % at (31, 15)): one unbroken segment on a regular grid, one iteration, nothing clipped, so the trend is the
+    filter itself — the exact rational design of tests/designmatrix_cases.py applied in numpy, interior by convolution with the
+    taps, ends by the edge rows.  The device applies what the host designed, and the host design is exact (the monomial
+    normal equations it used to solve lose up to six digits here, tests/test_savgol_design_cpu.py).  Measured: 6.7e-16 relative
+    in all four cases."""
+    n = 300
+    rng = np.random.default_rng(window * 100 + polyorder)
+    t = np.arange(n) * (30.0 / 1440.0)
+    y = 1.0 + 0.01 * np.sin(2 * np.pi * t / 1.7) + 2e-3 * np.cos(2 * np.pi * t / 0.31) + 1e-3 * rng.standard_normal(n)
+    got, fit = _capi.savgol_trend_batch(t, y, np.array([0, n], dtype=np.int64), window_length=window, polyorder=polyorder,
+                                        break_tolerance=None, niters=1, sigma=1e6, return_fit_mask=True)
+    assert fit.all()
+    taps, edge = designmatrix_cases.savgol_reference_of(window, polyorder)
+    ref = designmatrix_cases.savgol_apply(y, taps, edge)
+    print("flatten (%d, %d): max rel err %.3g" % (window, polyorder, np.max(np.abs(got - ref) / np.abs(ref))))
+    assert np.allclose(got, ref, rtol=RTOL, atol=0)
