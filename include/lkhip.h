@@ -39,6 +39,7 @@
  *   lk_fold_batch*       <- LightCurve.fold, src/lightkurve/lightcurve.py:1089-1214 (astropy TimeSeries.fold + sort).
  *   lk_fold_bin_plan_batch* / lk_fold_bin_batch* / lk_phase_bin_batch_dev / lk_fold_cycle_batch_dev <- lc.fold(...).bin(...),
  *                           optionally of the odd or even cycles only: fused without a sort, or on a folded batch (also nanmedian).
+ *   lk_river_plan_batch* / lk_river_batch* <- the image behind LightCurve.plot_river (lightkurve 2.x): cycles x phase bins per target.
  *   lk_pg_logmedian_batch* / lk_pg_boxsmooth_batch* <- Periodogram.smooth, periodogram.py:182-284.
  *   lk_pg_snr_batch_dev / lk_pg_acf_metric_batch_dev / lk_pg_numax_pick_batch_dev / lk_pg_deltanu_batch* <- flatten,
  *                           estimate_numax and estimate_deltanu (seismology/) on spectra that stay in device memory.
@@ -630,6 +631,53 @@ int lk_fold_bin_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const 
                           const double *wrap_phase, int normalize_phase, const double *cycle_epoch, const double *plan, int which,
                           const int64_t *bin_off, const double *start, const double *size_sec, const double *edges,
                           double *phase_out, double *flux_out, double *flux_err_out, int32_t *count_out, void *stream);
+
+/* ---- River diagrams: per target an image (cycles x phase bins) of the UNFOLDED batch, the data behind LightCurve.plot_river
+ * (lightkurve 2.x lightcurve.py).  y = flux / nanmedian(flux), u = flux_err / nanmedian(flux); phase = lk_fold_batch's with
+ * epoch_phase 0, wrap_phase 0.5, normalize_phase 1 (the same bits); row = floor((t - (e - P/2)) / P) minus its minimum over the
+ * target; a cadence is in column j when edges[j] < phase <= edges[j+1] (a phase equal to edges[0] is in none) and takes part
+ * when its y is finite.  river = mean of the cell's y (method 0), np.median of it (1) or (mean - 1) / sqrt(nansum(u^2)) (2,
+ * needs flux_err); count = cadences that take part; a cell with none holds NaN / 0.  Times must be non-decreasing per target.
+ *
+ * lk_river_plan_batch*: ONE workgroup per target streams time and flux once; plan (HOST, valid on return: the _dev form
+ * synchronises `stream`) receives LK_RIVER_NPLAN doubles per target: [0] nanmedian(flux), [1] nanmedian(diff(t)) (both exact
+ * order statistics), [2] / [3] smallest / largest cycle before the minimum is taken off (0 / -1: no finite time), [4] number of
+ * finite fluxes, [5] 1 when every time is finite and none decreases, [6] the first time (NaN: no cadence), [7] / [8] the largest
+ * finite |flux| / |flux_err|.  period (> 0) / epoch_time: HOST, B each; with epoch_given == 0 the epoch is the target's first time.
+ *
+ * lk_river_batch*: target b owns cells [cell_off[b], cell_off[b+1]) of river (float64) and count (int32), row-major as
+ * (n_cycles[b], n_bins[b]); its n_bins[b] + 1 edges (strictly increasing phases) are edges[sum of n_bins[a < b] + b ...]; a
+ * target with n_bins[b] == 0 or n_cycles[b] == 0 owns no cell and is not read.  plan: what lk_river_plan_batch* wrote for the
+ * same period and epoch (its median, smallest and largest cycle and maxima are used); epoch_time: the epoch of every target (its
+ * first time where none was given).  All of these are HOST arrays.  Every cell is written.  The rows of a target are cut into tiles
+ * of at most LK_RIVER_LDS_CELLS cells (a row wider than that into column chunks), one workgroup each; sums are exact integer sums
+ * of the addends rounded to a per-target quantum (lk_fold_bin_batch's scheme), medians exact: a target's cells have the same bits
+ * alone, at any place in a batch and from run to run.  Median: a tile's values are collected in LDS, or in device scratch when more
+ * than LK_RIVER_LDS_VALS take part; a cell of up to LK_RIVER_CELL_THREAD values is ranked by one thread, a larger one by the
+ * workgroup.  route (DEVICE, int32[B], nullable) receives per target the OR of its tiles' LK_RIVER_ROUTE_* bits. */
+#define LK_RIVER_NPLAN 9
+#define LK_RIVER_LDS_CELLS 3072
+#define LK_RIVER_LDS_VALS 4096
+#define LK_RIVER_CELL_THREAD 32
+#define LK_RIVER_ROUTE_ROWS 1         /* a tile of whole rows */
+#define LK_RIVER_ROUTE_COLUMNS 2      /* a column chunk of one row (n_bins > LK_RIVER_LDS_CELLS) */
+#define LK_RIVER_ROUTE_VALS_LDS 4     /* median: the tile's values collected in LDS */
+#define LK_RIVER_ROUTE_VALS_SCRATCH 8 /* median: ... in device scratch */
+#define LK_RIVER_ROUTE_CELL_THREAD 16 /* median: a cell ranked by one thread */
+#define LK_RIVER_ROUTE_CELL_GROUP 32  /* median: a cell ranked by the workgroup */
+int lk_river_plan_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, const double *flux, const double *flux_err,
+                        const double *period, const double *epoch_time, int epoch_given, double *plan);
+int lk_river_plan_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,
+                            const double *flux_err, const double *period, const double *epoch_time, int epoch_given, double *plan,
+                            void *stream);
+int lk_river_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, const double *flux, const double *flux_err,
+                   const double *period, const double *epoch_time, const double *plan, int method, const int32_t *n_bins,
+                   const int32_t *n_cycles, const int64_t *cell_off, const double *edges, double *river, int32_t *count,
+                   int32_t *route);
+int lk_river_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux, const double *flux_err,
+                       const double *period, const double *epoch_time, const double *plan, int method, const int32_t *n_bins,
+                       const int32_t *n_cycles, const int64_t *cell_off, const double *edges, double *river, int32_t *count,
+                       int32_t *route, void *stream);
 
 /* ---- nanmax / nanargmax over each row of a B x M float64 matrix (first maximum wins) ---------------- */
 int lk_argmax_batch(lk_handle *h, int B, int64_t M, const double *x, double *max_out, int64_t *argmax_out);

@@ -190,6 +190,15 @@ SIGNATURES = [
     ("lk_fold_bin_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _c_dp, _c_dp, ctypes.c_double, _c_dp, ctypes.c_int, _c_dp, _c_dp, ctypes.c_int,
       _c_ip, _c_dp, _c_dp, _c_dp, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_river_plan_batch", ctypes.c_int, [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_dp]),
+    ("lk_river_plan_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _c_dp, _c_dp, ctypes.c_int, _c_dp, _vp]),
+    ("lk_river_batch", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_i32p, _c_i32p, _c_ip, _c_dp, _c_dp,
+      _c_i32p, _c_i32p]),
+    ("lk_river_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, _c_ip, _vp, _vp, _vp, _c_dp, _c_dp, _c_dp, ctypes.c_int, _c_i32p, _c_i32p, _c_ip, _c_dp, _vp, _vp, _vp,
+      _vp]),
     ("lk_argmax_batch", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp, _c_ip]),
     ("lk_argmax_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     ("lk_bls_batch", ctypes.c_int,
@@ -938,6 +947,39 @@ def fold_bin_batch(t, flux, n_off, period, flux_err=None, epoch_time=None, epoch
                                   which_code, _ptr(lay["bin_off"], _c_ip), _ptr(lay["start"]), _ptr(lay["size_sec"]),
                                   _ptr(lay["edges"]), _ptr(po), _ptr(fo), _ptr(eo), _ptr(co, _c_i32p)))
     return dict(phase=po, flux=fo, flux_err=eo, count=co, bin_off=lay["bin_off"])
+
+
+def river_batch(t, flux, n_off, period, flux_err=None, epoch_time=None, bin_points=1, minimum_phase=-0.5, maximum_phase=0.5,
+                method="mean", bins=None, max_output_mb=4096, device=0):
+    """River diagrams (cycle x phase images) of B ragged targets on host arrays (``lk_river_plan_batch`` + ``lk_river_batch``).
+    Arguments and definition as ``DeviceLightCurveBatch.river``.  Returns dict(river, count: lists of per-target
+    (n_cycles_b, n_bins_b) arrays; n_cycles, n_bins, status, cell_off, edges, edge_off, cycle_min, route)."""
+    from . import river as rv
+    h = Handle.get(device)
+    t, flux = _f64(t), _f64(flux)
+    n_off = _offsets(n_off, t.size)
+    B = n_off.size - 1
+    err = None if flux_err is None else _f64(np.broadcast_to(flux_err, t.shape))
+    period, bins, code = rv.check_arguments(B, period, bin_points, minimum_phase, maximum_phase, method, bins, has_err=err is not None)
+    epoch_given = epoch_time is not None
+    epoch = _f64(np.broadcast_to(np.asarray(epoch_time if epoch_given else 0.0, dtype=np.float64), (B,)))
+    plan = np.zeros((max(B, 1), rv.NPLAN), dtype=np.float64)
+    _check(_lib.lk_river_plan_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(t), _ptr(flux), _ptr(err), _ptr(period), _ptr(epoch),
+                                    int(epoch_given), _ptr(plan)))
+    plan = plan[:B]
+    lay = rv.layout(np.diff(n_off), plan, period, bin_points, minimum_phase, maximum_phase, bins, max_output_mb)
+    if not epoch_given:
+        epoch = _f64(plan[:, 6])
+    ncell = int(lay["cell_off"][-1])
+    river, count = np.full(max(ncell, 1), np.nan, dtype=np.float64), np.zeros(max(ncell, 1), dtype=np.int32)
+    route = np.zeros(max(B, 1), dtype=np.int32)
+    _check(_lib.lk_river_batch(h._h, B, _ptr(n_off, _c_ip), _ptr(t), _ptr(flux), _ptr(err), _ptr(period), _ptr(epoch),
+                               _ptr(np.ascontiguousarray(plan)), code, _ptr(lay["n_bins"], _c_i32p), _ptr(lay["n_cycles"], _c_i32p),
+                               _ptr(lay["cell_off"], _c_ip), _ptr(lay["edges"]), _ptr(river), _ptr(count, _c_i32p),
+                               _ptr(route, _c_i32p)))
+    out = dict(lay)
+    out.update(river=rv.split(river[:ncell], lay), count=rv.split(count[:ncell], lay), route=route[:B])
+    return out
 
 
 # --------------------------------------------------------------------------------------------- BLS

@@ -8,7 +8,7 @@ from . import _capi
 from .distributed import all_gather_rows, device_gather_available, shard_bounds, sharded_map, sharded_map_ragged
 from . import packed
 
-__all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch", "fill_gaps_batch",
+__all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch", "river_batch", "fill_gaps_batch",
            "periodogram_peaks", "flatten_batch",
            "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "subtract_background_batch", "regression_correct_batch", "cbv_correct_batch"]
 
@@ -264,6 +264,24 @@ def fold_bin_batch(lcs, period, epoch_time=None, epoch_phase=0.0, wrap_phase=Non
                                 wrap_phase=wrap_phase, normalize_phase=normalize_phase, time_bin_size=time_bin_size,
                                 time_bin_start=time_bin_start, n_bins=n_bins, bins=bins, aggregate_func=aggregate_func,
                                 which=which, device=device)
+
+
+def river_batch(lcs, period, epoch_time=None, bin_points=1, minimum_phase=-0.5, maximum_phase=0.5, method="mean", bins=None,
+                max_output_mb=4096, device=0):
+    """River diagrams (cycle x phase images, the data behind ``plot_river`` of lightkurve 2.x) per light curve, for host light
+    curves: ``lcs`` a list of light curves or a ``LightCurveBatch``; ``period`` / ``epoch_time`` / ``bins`` scalars or one value
+    per light curve.  The arguments, definition and statuses of ``DeviceLightCurveBatch.river``, through ``lk_river_plan_batch`` /
+    ``lk_river_batch``.  Returns the dict of ``_capi.river_batch``: ``river`` / ``count`` are lists of per-light-curve
+    (n_cycles, n_bins) arrays.  ``method="sigma"`` needs errors: light curves without them carry NaN errors, which ``nansum``
+    skips.  Not sharded over ranks."""
+    from .ingest import LightCurveBatch
+    if isinstance(lcs, LightCurveBatch):
+        time, flux, err, n_off = lcs.time, lcs.flux, lcs.flux_err, lcs.n_off
+    else:
+        (time, flux, err), n_off = packed.pack_columns(list(lcs), ("time", "flux", "flux_err"), pinned="auto", pool_prefix="river")
+    return _capi.river_batch(time, flux, n_off, period, flux_err=err, epoch_time=epoch_time, bin_points=bin_points,
+                             minimum_phase=minimum_phase, maximum_phase=maximum_phase, method=method, bins=bins,
+                             max_output_mb=max_output_mb, device=device)
 
 
 def fill_gaps_batch(lcs, method="gaussian_noise", noise_std="auto", seed=0, first_target=0, stream_id=0, return_mask=False, device=0):

@@ -2169,6 +2169,63 @@ int lk_fold_bin_batch(lk_handle *h, int B, const int64_t *n_off, const double *t
     return rc ? rc : io.finish();
 }
 
+// ------------------------------------------------------------------------------------------------ river diagrams
+int lk_river_plan_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux,
+                            const double *flux_err, const double *period, const double *epoch_time, int epoch_given, double *plan,
+                            void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::river_plan_launch(h, B, n_off_host, t, flux, flux_err, period, epoch_time, epoch_given, plan,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int lk_river_plan_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, const double *flux, const double *flux_err,
+                        const double *period, const double *epoch_time, int epoch_given, double *plan) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(t && flux && plan, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B];
+    const double *dt, *df, *de;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).in(df, flux, ntot).in(de, flux_err, ntot).stage();
+    if (rc) return rc;
+    return lk::river_plan_launch(h, B, n_off, dt, df, de, period, epoch_time, epoch_given, plan, nullptr);
+}
+
+int lk_river_batch_dev(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux, const double *flux_err,
+                       const double *period, const double *epoch_time, const double *plan, int method, const int32_t *n_bins,
+                       const int32_t *n_cycles, const int64_t *cell_off, const double *edges, double *river, int32_t *count,
+                       int32_t *route, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::river_launch(h, B, n_off_host, t, flux, flux_err, period, epoch_time, plan, method, n_bins, n_cycles, cell_off, edges,
+                            river, count, route, static_cast<hipStream_t>(stream));
+}
+
+int lk_river_batch(lk_handle *h, int B, const int64_t *n_off, const double *t, const double *flux, const double *flux_err,
+                   const double *period, const double *epoch_time, const double *plan, int method, const int32_t *n_bins,
+                   const int32_t *n_cycles, const int64_t *cell_off, const double *edges, double *river, int32_t *count,
+                   int32_t *route) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_REQUIRE(B >= 0 && n_off != nullptr && cell_off != nullptr, "bad batch description");
+    if (B == 0) return LK_OK;
+    LK_REQUIRE(t && flux && river && count, "NULL buffer");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    const size_t ntot = (size_t)n_off[B], ncell = (size_t)cell_off[B];
+    const double *dt, *df, *de;
+    double *dro;
+    int32_t *dco, *drt;
+    lk::StagedCall io(h);
+    int rc = io.in(dt, t, ntot).in(df, flux, ntot).in(de, flux_err, ntot).out(dro, river, ncell).out(dco, count, ncell)
+                 .out(drt, route, (size_t)B).stage();
+    if (rc) return rc;
+    rc = lk::river_launch(h, B, n_off, dt, df, de, period, epoch_time, plan, method, n_bins, n_cycles, cell_off, edges, dro, dco,
+                          drt, nullptr);
+    return rc ? rc : io.finish();
+}
+
 // ------------------------------------------------------------------------------------------------ SFF
 int lk_cube_centroids_batch_dev(lk_handle *h, int B, int N, int npix, int nx, const float *flux, const uint8_t *mask,
                                 int mask_stride, double column0, double row0, double *col_out, double *row_out, void *stream) {

@@ -1,6 +1,6 @@
-// fold_phase.hpp — the phase of one cadence, shared by fold.hip (fold + sort) and foldbin.hip (fold + bin, no sort).
-// Both translation units are compiled with the same flags, so the expression below rounds the same way in both and the
-// fused kernel sees the bits fold_kernel writes.
+// fold_phase.hpp — the phase and the cycle of one cadence, shared by fold.hip (fold + sort), foldbin.hip (fold + bin, no sort)
+// and river.hip (cycle x phase images).  The translation units are compiled with the same flags, so the expressions below round
+// the same way in all of them and the fused kernels see the bits fold_kernel writes.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -42,5 +42,8 @@ __device__ __forceinline__ double fold_phase(const FoldPar &f, double t) {
     if (f.normalize) ph = ph / f.P;
     return ph;
 }
+
+// FoldedLightCurve.cycle before the minimum is taken off (foldbin.hip's odd / even cycles, river.hip's rows)
+__device__ __forceinline__ double fb_cycle(double t, double e, double P) { return floor((t - (e - P / 2.0)) / P); }
 
 }  // namespace lk

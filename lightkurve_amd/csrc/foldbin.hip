@@ -38,9 +38,6 @@ constexpr int FB_LDS_BINS = LK_FOLD_BIN_LDS_BINS;  // bins per target accumulate
 __device__ __forceinline__ double fb_qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
 __device__ __forceinline__ double fb_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
 
-// FoldedLightCurve.cycle before the minimum is taken off
-__device__ __forceinline__ double fb_cycle(double t, double e, double P) { return floor((t - (e - P / 2.0)) / P); }
-
 // relative time of a phase [s] and the centre of bin k (downsample.py:85-97, ingest.hip's bin_kernel)
 __device__ __forceinline__ double fb_rel(double ph, double start) { return (ph - start) * 86400.0; }
 __device__ __forceinline__ double fb_centre(double start, double edge, double size_sec) {

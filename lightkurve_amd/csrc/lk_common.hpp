@@ -356,6 +356,15 @@ int fold_bin_launch(lk_handle *h, int B, const int64_t *n_off_host, const double
                     int normalize_phase, const double *cycle_epoch_host, const double *plan_host, int which,
                     const int64_t *bin_off_host, const double *start_host, const double *size_sec_host, const double *edges_host,
                     double *phase_out, double *flux_out, double *err_out, int32_t *count_out, hipStream_t stream);
+// river.hip: river diagrams (cycle x phase images) of the unfolded batch.  The plan (one pass; plan_host is valid on return) and
+// the images on the layout the caller formed from it (include/lkhip.h); route nullable
+int river_plan_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux, const double *err,
+                      const double *period_host, const double *epoch_time_host, int epoch_given, double *plan_host,
+                      hipStream_t stream);
+int river_launch(lk_handle *h, int B, const int64_t *n_off_host, const double *t, const double *flux, const double *err,
+                 const double *period_host, const double *epoch_time_host, const double *plan_host, int method,
+                 const int32_t *n_bins_host, const int32_t *n_cycles_host, const int64_t *cell_off_host, const double *edges_host,
+                 double *river, int32_t *count, int32_t *route, hipStream_t stream);
 int pg_acf2d_launch(lk_handle *h, int B, int64_t M, const double *power, int n_win, const int *win_start_host, int W,
                     double *acf2d, double *metric, hipStream_t stream);
 // pgsmooth.hip, the resident seismology chain: metric of the 2-D ACF alone; power / background; Gaussian smoothing and

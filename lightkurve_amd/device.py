@@ -29,6 +29,7 @@ from . import fillgaps as _fg
 from . import foldbin as _fb
 from . import packed
 from . import periodogram as _pg
+from . import river as _rv
 from . import seismology as _seis
 from .cotrend import CotrendMixin, _alpha_per_target, _cadenceno_array, _cbv_columns  # noqa: F401  (names others import from here)
 from .devmem import DeviceBuffer, _Pool, _ip, _off_ptr, _pool, _upload, _vp, release_device_pool  # noqa: F401
@@ -938,6 +939,57 @@ class DeviceLightCurveBatch(CotrendMixin):
         out._parent = self
         return out
 
+    def river(self, period, epoch_time=None, bin_points=1, minimum_phase=-0.5, maximum_phase=0.5, method="mean", bins=None,
+              max_output_mb=4096):
+        """River diagrams: per light curve an image of shape (cycles, phase bins), the data behind ``LightCurve.plot_river`` of
+        lightkurve 2.x -> ``DeviceRiverBatch`` (plotting itself stays out of scope).  The one view that keeps the cycles apart:
+        is the signal in every transit, does it drift in phase, does one stretch of data carry the detection.
+
+        ``y = flux / nanmedian(flux)``; the phase is ``fold(period, epoch_time, normalize_phase=True)``'s (the same bits), the
+        row ``FoldedLightCurve.cycle`` (rows of cycles without a cadence exist and are empty); ``n_bins = bins`` or
+        ``int(period / nanmedian(diff(time)) * (maximum_phase - minimum_phase) / bin_points)``; edges
+        ``np.linspace(minimum_phase, maximum_phase, n_bins + 1)``, a cadence is in column j when ``edges[j] < phase <=
+        edges[j+1]`` (a phase equal to ``edges[0]``, -0.5 in particular, is in none) and takes part when its y is finite.
+        ``method``: ``"mean"`` / ``"median"`` of the cell's y, or ``"sigma"`` = ``(mean - 1) / sqrt(nansum((flux_err /
+        nanmedian(flux))^2))`` (needs ``flux_err``).  A cell nobody takes part in holds NaN, count 0.  ``period`` / ``epoch_time``
+        (default: each light curve's first time) / ``bins``: a scalar or one value per light curve.
+
+        Deviations from the reference, on purpose: rows are this project's cycles, cut at phase +-0.5 of the given epoch (the
+        reference cuts at ``time % period``, so a row boundary can fall inside a transit); with ``bin_points == 1`` every cell
+        is still aggregated (the reference takes the cell's first cadence; equal when a cell holds one); ``sigma`` is the
+        reference's expression, not divided by the count.
+
+        No exception per light curve: ``status`` 1 fewer than two cadences or no finite flux, 2 times decreasing or not finite,
+        3 median flux not finite or zero or median time step not positive, 4 ``n_bins < 1``; such a light curve has no cell.
+        ``ValueError`` for bad arguments and when the images exceed ``max_output_mb`` MiB.  Two launches: a plan kernel (72 B
+        per target to the host) and the image kernel, one workgroup per tile of rows; medians are exact, means within
+        n 2^-63 max|y| (exact integer sums): a light curve's image has the same bits alone and in any batch."""
+        h, B = self.handle, len(self)
+        period, bins, code = _rv.check_arguments(B, period, bin_points, minimum_phase, maximum_phase, method, bins,
+                                                 has_err=self.d_flux_err is not None)
+        epoch_given = epoch_time is not None
+        epoch = np.ascontiguousarray(np.broadcast_to(np.asarray(epoch_time if epoch_given else 0.0, dtype=np.float64), (B,)))
+        d_err = _vp(self.d_flux_err.ptr if self.d_flux_err is not None else None)
+        plan = np.zeros((max(B, 1), _rv.NPLAN), dtype=np.float64)
+        _capi._check(_capi._lib.lk_river_plan_batch_dev(
+            h._h, B, _off_ptr(self.n_off), _vp(self.d_time.ptr), _vp(self.d_flux.ptr), d_err, period.ctypes.data_as(_dp),
+            epoch.ctypes.data_as(_dp), int(epoch_given), plan.ctypes.data_as(_dp), _vp(self.stream or None)))
+        plan = plan[:B]
+        lay = _rv.layout(np.diff(self.n_off), plan, period, bin_points, minimum_phase, maximum_phase, bins, max_output_mb)
+        if not epoch_given:
+            epoch = np.ascontiguousarray(plan[:, 6])
+        ncell = int(lay["cell_off"][-1])
+        d_river, d_count = DeviceBuffer(h, max(ncell, 1) * 8), DeviceBuffer(h, max(ncell, 1) * 4)
+        d_route = DeviceBuffer(h, max(B, 1) * 4)
+        _capi._check(_capi._lib.lk_river_batch_dev(
+            h._h, B, _off_ptr(self.n_off), _vp(self.d_time.ptr), _vp(self.d_flux.ptr), d_err, period.ctypes.data_as(_dp),
+            epoch.ctypes.data_as(_dp), np.ascontiguousarray(plan).ctypes.data_as(_dp), code, lay["n_bins"].ctypes.data_as(_i32p),
+            lay["n_cycles"].ctypes.data_as(_i32p), _off_ptr(lay["cell_off"]), lay["edges"].ctypes.data_as(_dp), _vp(d_river.ptr),
+            _vp(d_count.ptr), _vp(d_route.ptr), _vp(self.stream or None)))
+        out = DeviceRiverBatch(h, self.stream, d_river, d_count, d_route, lay, period, epoch, method, self.meta)
+        out._parent = self
+        return out
+
     def create_transit_mask(self, period, transit_time, duration, planet_off=None, to_host=True):
         """In-transit flags over all cadences of the batch (reference :2967-3037) -> bool array on the host, or the
         ``DeviceBuffer`` of bytes (usable as ``flatten(mask=...)``) with ``to_host=False``."""
@@ -1152,6 +1204,44 @@ class DevicePhaseCurveBatch(object):
                     count=self.d_count.download(np.int32, nbt, stream=self.stream), bin_off=self.bin_off.copy())
 
 
+class DeviceRiverBatch(object):
+    """River diagrams in HBM: ``d_river`` (float64) and ``d_count`` (int32 cadences per cell), target b's cells at
+    ``[cell_off[b], cell_off[b + 1])``, row-major as ``(n_cycles[b], n_bins[b])``.  Host arrays per target: ``status`` (0 ok; a
+    non-zero status has no cell), ``n_cycles``, ``n_bins``, ``cycle_min`` (the cycle number of row 0) and ``edges`` (target b's
+    ``n_bins[b] + 1`` phase edges at ``edge_off[b]``: ``edges_of(b)``); ``cell_off`` (B + 1)."""
+
+    def __init__(self, handle, stream, d_river, d_count, d_route, lay, period, epoch_time, method, meta=None):
+        self.handle, self.stream = handle, stream
+        self.d_river, self.d_count, self._d_route = d_river, d_count, d_route
+        self.cell_off, self.n_cycles, self.n_bins = lay["cell_off"], lay["n_cycles"], lay["n_bins"]
+        self.status, self.edges, self.edge_off, self.cycle_min = lay["status"], lay["edges"], lay["edge_off"], lay["cycle_min"]
+        self.period, self.epoch_time, self.method = period, epoch_time, method
+        self.meta = meta
+        self._parent = None              # (keeps the inputs alive while the kernels may still read them)
+
+    def __len__(self):
+        return len(self.cell_off) - 1
+
+    def edges_of(self, b):
+        """The ``n_bins[b] + 1`` phase edges of target b (empty for a non-zero status)."""
+        return self.edges[self.edge_off[b]:self.edge_off[b + 1]] if self.status[b] == 0 else np.zeros(0)
+
+    def routes(self):
+        """int32[B]: per target the OR of its tiles' ``river.ROUTE_*`` bits (which kernel routes served it)."""
+        return self._d_route.download(np.int32, len(self), stream=self.stream)
+
+    def to_host(self):
+        """-> dict(river, count: lists of per-target (n_cycles_b, n_bins_b) arrays; n_cycles, n_bins, status, cell_off, edges,
+        edge_off, cycle_min)."""
+        ncell = int(self.cell_off[-1])
+        lay = dict(cell_off=self.cell_off, n_cycles=self.n_cycles, n_bins=self.n_bins)
+        river = self.d_river.download(np.float64, ncell, stream=self.stream)
+        count = self.d_count.download(np.int32, ncell, stream=self.stream)
+        return dict(river=_rv.split(river, lay), count=_rv.split(count, lay), n_cycles=self.n_cycles.copy(), n_bins=self.n_bins.copy(),
+                    status=self.status.copy(), cell_off=self.cell_off.copy(), edges=self.edges.copy(), edge_off=self.edge_off.copy(),
+                    cycle_min=self.cycle_min.copy())
+
+
 class DeviceBLSResult(object):
     """out7[7, B, nP] in HBM (``_capi.BLS_FIELDS`` order; transit_time relative to ``t_ref``, the reference's
     ``min(t)`` per light curve) + what a pipeline keeps of it."""
@@ -1279,6 +1369,13 @@ class DeviceBLSResult(object):
         ``DevicePhaseCurveBatch``."""
         period, transit_time = self._fold_box(period, transit_time)
         return self._batch.fold_bin(period, epoch_time=transit_time, **kwargs)
+
+    def river(self, period=None, transit_time=None, **kwargs):
+        """The river diagrams of the searched batch on each target's box: ``self._batch.river(period, epoch_time=transit_time,
+        ...)`` -> ``DeviceRiverBatch`` (the other keywords are ``DeviceLightCurveBatch.river``'s).  The transit sits at phase 0
+        of every row."""
+        period, transit_time = self._fold_box(period, transit_time)
+        return self._batch.river(period, epoch_time=transit_time, **kwargs)
 
     def transit_mask(self, period=None, duration=None, transit_time=None, to_host=True):
         """``BoxLeastSquaresPeriodogram.get_transit_mask`` for every target: ``create_transit_mask`` of the searched batch

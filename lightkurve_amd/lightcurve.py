@@ -195,6 +195,17 @@ class LightCurve(object):
         out.normalize_phase = normalize_phase
         return out
 
+    def river(self, period, epoch_time=None, bin_points=1, minimum_phase=-0.5, maximum_phase=0.5, method="mean", bins=None,
+              max_output_mb=4096):
+        """The data behind ``plot_river`` of lightkurve 2.x: an image of shape (cycles, phase bins), in numpy (the mirror of
+        ``DeviceLightCurveBatch.river``, whose docstring holds the definition and the deviations from the reference; no plot is
+        drawn).  Returns dict(river, count: (n_cycles, n_bins) arrays; n_cycles, n_bins, status, edges, cycle_min); a non-zero
+        status (as on the device) gives empty arrays; bad arguments raise ``ValueError``."""
+        from . import river as _rv
+        return _rv.river_numpy(self.time, self.flux, self.flux_err, period, epoch_time=epoch_time, bin_points=bin_points,
+                               minimum_phase=minimum_phase, maximum_phase=maximum_phase, method=method, bins=bins,
+                               max_output_mb=max_output_mb)
+
 
 class FoldedLightCurve(LightCurve):
     """Folded light curve: ``time`` holds the phase; ``time_original`` and ``cycle`` as in the reference."""

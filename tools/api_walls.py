@@ -94,6 +94,11 @@ after one warm-up.  F the fused `batch.fold_bin(period, bins=)`; S `batch.fold(p
 route: `to_host()`, then numpy fold + bin per target on 16 threads.  Every timed region ends with the binned curves on the host.
 Written to profiles/foldbin_walls.txt.
 
+`river`: the river diagrams (cycle x phase images) of `LK_WALLS_B` (default 1000) targets x `LK_WALLS_N` (default 20000) cadences,
+one period per target, default arguments (`LK_WALLS_METHOD`, default mean), in ONE process, the routes alternating, `LK_WALLS_REPS`
+(default 5) times after one warm-up.  D `batch.river(period)` and a synchronise (images resident); T the same with `to_host()`; H
+the host route: `to_host()` of the batch, then the numpy mirror per target on 16 threads.  Written to profiles/river_walls.txt.
+
 `stitch`: `LK_WALLS_B` (default 1000) targets observed in `LK_WALLS_SEGMENTS` (default 4) sectors of `LK_WALLS_N` (default 5000)
 cadences each, TESS-like cadence numbers that continue across a one-day gap between sectors, 3 % of the cadences missing inside
 them, in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5) times after one warm-up.  R `from_arrays(cadenceno=)`
@@ -1123,6 +1128,65 @@ def foldbin():
         "  S / F = %.2f; H / F = %.1f" % (med["S"] / med["F"], med["H"] / med["F"])])
 
 
+def river():
+    from concurrent.futures import ThreadPoolExecutor
+    from lightkurve_amd import _capi, river as rv
+    from lightkurve_amd.device import DeviceLightCurveBatch
+    B, N = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "1000"), ("LK_WALLS_N", "20000")))
+    reps = int(os.environ.get("LK_WALLS_REPS", "5"))
+    method = os.environ.get("LK_WALLS_METHOD", "mean")
+    rng = np.random.default_rng(29)
+    t = 1000.0 + 0.0204 * np.arange(N)
+    period = rng.uniform(0.7, 12.0, B)
+    flux = 1.0 + 3e-4 * rng.standard_normal((B, N)) - 0.005 * (np.abs((t[None] - t[0]) / period[:, None] % 1.0 - 0.5) > 0.49)
+    err = np.full((B, N), 3e-4)
+    n_off = np.arange(B + 1, dtype=np.int64) * N
+    raw = DeviceLightCurveBatch.from_arrays(np.tile(t, B), flux.ravel(), err.ravel(), n_off)
+    raw.synchronize()
+    sync = _capi.Handle.get(0).synchronize
+
+    def resident():
+        out = raw.river(period, method=method)
+        sync()
+        return out
+
+    def to_host():
+        return raw.river(period, method=method).to_host()
+
+    def through_host():
+        host = raw.to_host()
+
+        def one(b):
+            a, z = int(host.n_off[b]), int(host.n_off[b + 1])
+            return rv.river_numpy(host.time[a:z], host.flux[a:z], host.flux_err[a:z], period[b], method=method)
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            return list(ex.map(one, range(B)))
+
+    fns = {"D": resident, "T": to_host, "H": through_host}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    d, h = first["T"], first["H"]
+    same = all(np.array_equal(d["count"][b], h[b]["count"]) for b in range(B)) and all(int(s) == 0 for s in d["status"])
+    worst = 0.0
+    for b in range(B):
+        fin = np.isfinite(h[b]["river"])
+        if fin.any():
+            worst = max(worst, float(np.max(np.abs(d["river"][b][fin] - h[b]["river"][fin]) / np.maximum(1.0, np.abs(h[b]["river"][fin])))))
+    cells = int(d["cell_off"][-1])
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    write_walls("river_walls.txt", [
+        "river diagrams, %d targets x %d cadences, one period per target, default arguments, method = %s (%.1f MB of input columns, "
+        "%d cells = %.1f MB of images)" % (B, N, method, 3 * B * N * 8 / 1e6, cells, cells * 12 / 1e6),
+        "  D    batch.river(period) + synchronise: plan kernel + image kernel, images resident              %s" % spread(ts["D"]),
+        "  T    batch.river(period).to_host(): the same and the images copied to the host                   %s" % spread(ts["T"]),
+        "  H    to_host(), LightCurve.river's numpy mirror per target on 16 threads                         %s" % spread(ts["H"]),
+        "  D and H: same shapes, statuses and counts: %s; max |difference| / max(1, |H|) of the images %.2e" % (same, worst),
+        "  H / D = %.1f; H / T = %.1f" % (med["H"] / med["D"], med["H"] / med["T"])])
+
+
 def diffimage():
     from concurrent.futures import ThreadPoolExecutor
     from lightkurve_amd.device import DevicePixelCubeBatch
@@ -1470,6 +1534,8 @@ def main():
         cbvopt_ragged()
     if "foldbin" in which:
         foldbin()
+    if "river" in which:
+        river()
     if "diffimage" in which:
         diffimage()
     if "ampimage" in which:
