@@ -1223,6 +1223,36 @@ int lk_ampimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *fit_status
                                   const double *level_col, const double *level_row, double *offset, double *offset_pix,
                                   int32_t *status, void *stream);
 
+/* lk_cube_pixel_ls_batch_dev <- one Lomb-Scargle spectrum per pixel of every cutout on ONE shared grid, and its peak (PixelCube.
+ *   pixel_periodogram is the numpy mirror): which pixels vary and at which frequency, what TargetPixelFile.plot_pixels(
+ *   periodogram=True) loops for.  frequency: HOST array of F, 1/d, every entry finite and > 0.  normalization: LK_NORM_LK_AMPLITUDE
+ *   or LK_NORM_LK_PSD.  A NULL non-nullable buffer, B, N, npix or F < 1, B > 65535, N * npix >= 2^31, F * npix >= 2^31, a bad
+ *   frequency, another normalization or an oversample_factor that is not finite and > 0 give LK_EINVAL.  flux_err is not read.
+ *   Cadences: t_ref (HOST array of B) is the reference time of each cutout, by convention its first finite time (NaN where it
+ *   has none).  Cadences with a non-finite time are dropped (their rows are not loaded); pixel p is taken on the remaining
+ *   cadences where its own flux is not NaN, n_used[p] of them, with unit weights.
+ *   Spectrum: astropy's floating-mean GLS (fit_mean, center_data) from the exact sums with weights 1 / n_used[p], then
+ *   P_psd = P * n_used / 2 and LK_NORM_LK_AMPLITUDE: sqrt(P_psd) sqrt(4 / n_used); LK_NORM_LK_PSD: P_psd * 2 / (n_used *
+ *   oversample_factor * fs), fs = 1 / (t_last - t_first) / oversample_factor * 1e6 / 86400 from the pixel's own first and last
+ *   used time — what lk_ls_batch gives for that light curve with the same normalization.  S, C, S2, C2 are summed once per
+ *   (cutout, frequency) and shared by the pixels; only sum y sin and sum y cos are per pixel, taken against a per-pixel pivot
+ *   (its first value), the mean put back through S and C; what a pixel's missing cadences added to the shared sums is
+ *   accumulated on the NaN branch and taken off.  Phases from (t - t_ref) with the product f (t - t_ref) reduced exactly, one
+ *   sine / cosine pair per (cadence, frequency), no recurrence.  All float64 after the float32 load.
+ *   Outputs on the device: power (nullable) [B][F][npix] float64, pixel fastest; peak_index [B][npix] int32, the first index of
+ *   the largest non-NaN power, -1 without one; peak_power [B][npix] float64, the bits of power there, NaN without one; n_used
+ *   [B][npix] int32; status [B] int32.  With power == NULL nothing of the size F * npix is written.
+ *   Degenerate cases: a pixel with n_used < 4 has a NaN spectrum; a cutout with fewer than 4 finite times has status 2, every
+ *   spectrum NaN and n_used 0 (status 0 otherwise).  Nothing is raised per pixel.
+ *   One wavefront owns (cutout, 16 frequencies, up to 128 adjacent pixels, two per lane) and walks all N cadences in chunks of 32
+ *   whose sines and cosines it stages in LDS; pixel groups in which a pixel lacks cadences take a second instantiation with one
+ *   pixel per lane.  No floating-point atomics, the order of every sum depends on N alone, so a cutout's outputs have the same
+ *   bits alone, at any batch position, with or without power and from run to run.  Scratch: B x npix x (24 + 12 ceil(F / 16))
+ *   bytes plus 8 F of the handle's arena.  Enqueued, no synchronisation. */
+int lk_cube_pixel_ls_batch_dev(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const double *frequency,
+                               int F, int normalization, double oversample_factor, const double *t_ref, double *power,
+                               double *peak_power, int32_t *peak_index, int32_t *n_used, int32_t *status, void *stream);
+
 /* lk_cube_background_batch_dev <- TargetPixelFile.estimate_background(aperture_mask) per cadence of the same resident cubes,
  *   and the subtraction of that background, in one pass (PixelCube.estimate_background / subtract_background are the numpy
  *   mirror).  mask / mask_stride as lk_cube_aperture_batch_dev; sel = the masked pixels of cadence i of cutout b.

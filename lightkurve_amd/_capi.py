@@ -371,6 +371,9 @@ SIGNATURES = [
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _c_dp, ctypes.c_int, _c_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
       _vp, _vp]),
     ("lk_ampimage_offsets_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_cube_pixel_ls_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_dp, _vp, _vp,
+      _vp, _vp, _vp, _vp]),
     ("lk_cube_background_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     ("lk_cube_subtract_rows_batch_dev", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),

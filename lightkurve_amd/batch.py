@@ -10,7 +10,7 @@ from . import packed
 
 __all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch", "river_batch", "fill_gaps_batch",
            "periodogram_peaks", "flatten_batch",
-           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "subtract_background_batch", "regression_correct_batch", "cbv_correct_batch"]
+           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "pixel_periodograms_batch", "subtract_background_batch", "regression_correct_batch", "cbv_correct_batch"]
 
 
 def _resolve_device(device):
@@ -401,6 +401,14 @@ def amplitude_images_batch(cubes, frequency, device=0, **kwargs):
     ``DevicePixelCubeBatch.amplitude_images`` with its keywords and its dict of host arrays.  Not sharded over ranks."""
     from .device import DevicePixelCubeBatch
     return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).amplitude_images(frequency, **kwargs)
+
+
+def pixel_periodograms_batch(cubes, frequency, device=0, **kwargs):
+    """``PixelCube.pixel_periodogram`` of every cutout, for host cutouts: ``cubes`` a list of same-shaped float32 ``PixelCube``s,
+    ``frequency`` one grid shared by all.  One upload (``DevicePixelCubeBatch.from_cubes``), then
+    ``DevicePixelCubeBatch.pixel_periodograms`` with its keywords and its dict of host arrays.  Not sharded over ranks."""
+    from .device import DevicePixelCubeBatch
+    return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).pixel_periodograms(frequency, **kwargs)
 
 
 def subtract_background_batch(cubes, background=None, aperture_mask="background", device=0, to_host=True):

@@ -378,6 +378,87 @@ class PixelCube(object):
         out["status"] = status if status else 3 if np.isnan(out["offset_pix"]) else 0
         return out
 
+    def pixel_periodogram(self, frequency, normalization="amplitude", freq_unit=None, oversample_factor=None):
+        """One Lomb-Scargle spectrum per pixel on ONE shared ``frequency`` grid, and where each peaks: which pixels vary, and at
+        which frequency (what ``TargetPixelFile.plot_pixels(periodogram=True)`` loops for; the host mirror of
+        ``DevicePixelCubeBatch.pixel_periodograms`` and its definition, float64 numpy after the float32 load; same keys without
+        the batch axis).  Cadences with a non-finite time are dropped for the whole cutout, ``t_ref`` is the first finite time;
+        pixel p is taken on the remaining cadences where its own flux is not NaN, ``n_used[p]`` of them, with unit weights
+        (``flux_err`` is not read).  Its spectrum is what ``LombScarglePeriodogram.from_lightcurve`` returns for that light
+        curve with an exact ``ls_method``: astropy's floating-mean GLS from the exact trigonometric sums, then
+        ``normalization`` 'amplitude': ``sqrt(P_psd) * sqrt(4 / n_used)``, ``frequency`` in 1/d by default; 'psd': ``P_psd * 2 /
+        (n_used * oversample_factor * fs)`` with ``fs = 1 / (t_last - t_first) / oversample_factor`` in microhertz from the
+        pixel's own first and last used time, ``frequency`` in microhertz by default, ``oversample_factor`` 1 by default.
+        ``frequency``: F values in ``freq_unit``, each finite and > 0 (``ValueError`` otherwise).  A pixel with ``n_used`` < 4
+        has a NaN spectrum; a cutout with fewer than 4 finite times has ``status`` 2, every spectrum NaN and ``n_used`` 0
+        (``status`` 0 otherwise).  Returns a dict: ``power`` (F, ny, nx); ``peak_index`` (ny, nx) int32, the first index of the
+        largest non-NaN power, -1 without one; ``peak_power`` and ``peak_frequency`` [1/d] (ny, nx), NaN where ``peak_index`` is
+        -1; ``n_used`` (ny, nx) int32; ``status``; ``t_ref``; ``frequency`` in 1/d.  Unlike the reference no ``corrector_func``
+        runs per pixel (its default removes outliers): clean the cube first, for instance with ``subtract_background``."""
+        from ..periodogram import UHZ_PER_CPD, _freq_unit_factor
+        if normalization not in ("amplitude", "psd"):
+            raise ValueError("normalization must be 'amplitude' or 'psd' (got %r)" % (normalization,))
+        unit = freq_unit if freq_unit is not None else ("1/d" if normalization == "amplitude" else "uHz")
+        freq = np.atleast_1d(np.asarray(frequency, dtype=np.float64))
+        if freq.ndim != 1 or freq.size < 1 or not (np.all(np.isfinite(freq)) and np.all(freq > 0)):
+            raise ValueError("frequency must be a 1-D grid of finite values > 0")
+        if oversample_factor is None:
+            oversample_factor = 5.0 if normalization == "amplitude" else 1.0
+        osf = float(oversample_factor)
+        if not (osf > 0 and np.isfinite(osf)):
+            raise ValueError("oversample_factor must be finite and > 0 (got %r)" % (oversample_factor,))
+        f_day = freq / _freq_unit_factor(unit)
+        F = len(f_day)
+        ny, nx = self.shape[1:]
+        fin = np.isfinite(self.time)
+        t_ref = float(self.time[fin][0]) if fin.any() else np.nan
+        status = 2 if fin.sum() < 4 else 0
+        power = np.full((F, ny * nx), np.nan)
+        n_used = np.zeros(ny * nx, dtype=np.int32)
+        if status == 0:
+            t_abs = self.time[fin]
+            t = t_abs - t_ref
+            y = np.asarray(self.flux, dtype=np.float64)[fin].reshape(len(t), ny * nx)
+            with np.errstate(all="ignore"):
+                ph = (2 * np.pi * f_day)[None, :] * t[:, None]
+                s_all, c_all, s2_all, c2_all = np.sin(ph), np.cos(ph), np.sin(2 * ph), np.cos(2 * ph)
+                for p in range(ny * nx):
+                    ok = ~np.isnan(y[:, p])
+                    n = int(ok.sum())
+                    n_used[p] = n
+                    if n < 4:
+                        continue
+                    full = n == len(t)
+                    s, c, s2, c2 = (a if full else a[ok] for a in (s_all, c_all, s2_all, c2_all))
+                    yp, tp = (y[:, p], t_abs) if full else (y[ok, p], t_abs[ok])
+                    w = 1.0 / n
+                    yc = yp - (yp[0] + np.sum(yp - yp[0]) * w)
+                    Sh, Ch = yc.dot(s) * w, yc.dot(c) * w
+                    S, C, S2, C2 = s.sum(axis=0) * w, c.sum(axis=0) * w, s2.sum(axis=0) * w, c2.sum(axis=0) * w
+                    tan2 = (S2 - 2 * S * C) / (C2 - (C * C - S * S))
+                    C2w = 1 / np.sqrt(1 + tan2 * tan2)
+                    S2w = tan2 * C2w
+                    Cw = np.sqrt(0.5) * np.sqrt(1 + C2w)
+                    Sw = np.sqrt(0.5) * np.sign(S2w) * np.sqrt(1 - C2w)
+                    YC, YS = Ch * Cw + Sh * Sw, Sh * Cw - Ch * Sw
+                    CC = 0.5 * (1 + C2 * C2w + S2 * S2w) - (C * Cw + S * Sw) ** 2
+                    SS = 0.5 * (1 - C2 * C2w - S2 * S2w) - (S * Cw - C * Sw) ** 2
+                    psd = (YC * YC / CC + YS * YS / SS) * (0.5 * n)
+                    if normalization == "amplitude":
+                        power[:, p] = np.sqrt(psd) * np.sqrt(4.0 / n)
+                    else:
+                        fs = (1.0 / (tp[-1] - tp[0])) / osf * UHZ_PER_CPD
+                        power[:, p] = psd * (2.0 / (n * osf * fs))
+        has = ~np.isnan(power)
+        peak_index = np.where(has.any(axis=0), np.argmax(np.where(has, power, -np.inf), axis=0), -1).astype(np.int32)
+        at = np.clip(peak_index, 0, F - 1)
+        found = peak_index >= 0
+        peak_power = np.where(found, power[at, np.arange(ny * nx)], np.nan)
+        peak_frequency = np.where(found, f_day[at], np.nan)
+        return {"power": power.reshape(F, ny, nx), "peak_index": peak_index.reshape(ny, nx),
+                "peak_power": peak_power.reshape(ny, nx), "peak_frequency": peak_frequency.reshape(ny, nx),
+                "n_used": n_used.reshape(ny, nx), "status": status, "t_ref": t_ref, "frequency": f_day}
+
 
     def _aperture_sums(self, ap):
         """(flux, flux_err) of the aperture `ap` (boolean image) per cadence, in the cube's dtype.  The gather `cube[:, ap]`

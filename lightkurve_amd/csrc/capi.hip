@@ -2310,6 +2310,16 @@ int lk_ampimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *fit_status
                                        static_cast<hipStream_t>(stream));
 }
 
+// ------------------------------------------------------------------------------------------------ pixel periodograms
+int lk_cube_pixel_ls_batch_dev(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const double *frequency,
+                               int F, int normalization, double oversample_factor, const double *t_ref, double *power,
+                               double *peak_power, int32_t *peak_index, int32_t *n_used, int32_t *status, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_pixelpg_launch(h, B, N, npix, time, flux, frequency, F, normalization, oversample_factor, t_ref, power,
+                                   peak_power, peak_index, n_used, status, static_cast<hipStream_t>(stream));
+}
+
 int lk_sff_scratch_bytes(int B, const int64_t *n_off, const int32_t *n_knots, const int32_t *win_off, int bins, int degree,
                          int64_t max_scratch_bytes, int64_t *bytes, int *n_chunks) {
     return lk::sff_scratch_bytes(B, n_off, n_knots, win_off, bins, degree, max_scratch_bytes, bytes, n_chunks);

@@ -430,6 +430,11 @@ int cube_ampimage_launch(lk_handle *h, int B, int N, int npix, const double *tim
 int ampimage_offsets_launch(lk_handle *h, int B, const int32_t *fit_status, const double *amp_col, const double *amp_row,
                             const double *level_col, const double *level_row, double *offset, double *offset_pix, int32_t *status,
                             hipStream_t stream);
+// pixelpg.hip: the per-pixel Lomb-Scargle periodograms of B resident cutouts on one shared grid (host array, 1/d), their peak
+// images and, where power is not NULL, the power cube [B][F][npix].  Everything else on the device; enqueued, no synchronisation
+int cube_pixelpg_launch(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const double *frequency_host,
+                        int F, int normalization, double oversample_factor, const double *t_ref_host, double *power,
+                        double *peak_power, int32_t *peak_index, int32_t *n_used, int32_t *status, hipStream_t stream);
 // sff.hip: SFFCorrector for a ragged resident batch.  The regression launcher owns h->ws, so the design matrices and everything
 // else that lives across it sit in `scratch`, a device block of the caller's (sff_scratch_bytes); status_host is valid on
 // return (the call synchronises once, to group the targets by their design width)

@@ -2194,6 +2194,79 @@ class DevicePixelCubeBatch(object):
         out["offset_pix"] = d_pix.download(np.float64, B, stream=self.stream)
         return out
 
+    # ---------------------------------------------------------------- pixel periodograms
+    def pixel_periodograms(self, frequency, normalization="amplitude", freq_unit=None, oversample_factor=None, return_power=True,
+                           to_host=True, max_output_mb=4096):
+        """One Lomb-Scargle spectrum per pixel of every cutout on ONE shared ``frequency`` grid, and where each peaks: which
+        pixels vary, and at which frequency (what ``TargetPixelFile.plot_pixels(periodogram=True)`` loops for).  The numpy
+        mirror and the definition is ``PixelCube.pixel_periodogram``: cadences with a non-finite time are dropped per cutout,
+        pixel p is taken where its own flux is not NaN (``n_used[p]`` values, unit weights, ``flux_err`` is not read), its
+        spectrum is the exact floating-mean GLS with lightkurve's ``normalization`` ('amplitude', ``frequency`` in 1/d by
+        default; 'psd', microhertz by default, ``oversample_factor`` 1 by default).  Every grid value must be finite and > 0.
+        The pixels of a cutout share the cadences, so four of the closed form's six sums are formed once per (cutout,
+        frequency) and only two per pixel (``lk_cube_pixel_ls_batch_dev``); no transpose, no second copy of the cube.
+        Returns a dict: ``power`` (B, F, ny, nx); ``peak_index`` (B, ny, nx) int32, the first index of the largest non-NaN
+        power, -1 without one; ``peak_power`` and ``peak_frequency`` [1/d] (B, ny, nx), NaN there; ``n_used`` (B, ny, nx) int32;
+        ``status`` (B,) int32: 0, or 2 for a cutout with fewer than 4 finite times (NaN spectra, ``n_used`` 0); ``t_ref`` (B,);
+        ``frequency`` (F,) in 1/d.  ``return_power=False`` computes the peak images alone: nothing of the size of the power
+        cube is written and the key is omitted; the peak images have the same bits either way.  ``ValueError`` when the power
+        cube would exceed ``max_output_mb``.  ``to_host=False``: ``power`` ([B][F][npix]), ``peak_power``, ``peak_index`` and
+        ``n_used`` are ``DeviceBuffer``s enqueued on the batch's stream, ``peak_frequency`` is omitted (``frequency[peak_index]``);
+        only ``status`` comes back.  A cutout's outputs have the same bits alone, at any batch position and from run to run.
+        No ``corrector_func`` runs per pixel (the reference's default removes outliers): clean the cube first, for instance
+        with ``subtract_background``.  The hand-off to the fit at one frequency per cutout, for the pixel (row, col)::
+
+            res = cubes.pixel_periodograms(grid)
+            images = cubes.amplitude_images(res["peak_frequency"][:, row, col])"""
+        from .periodogram import _freq_unit_factor
+        h, (B, N, ny, nx) = self.handle, self.shape
+        npix = ny * nx
+        norms = {"amplitude": 2, "psd": 3}                          # LK_NORM_LK_AMPLITUDE, LK_NORM_LK_PSD
+        if normalization not in norms:
+            raise ValueError("normalization must be 'amplitude' or 'psd' (got %r)" % (normalization,))
+        unit = freq_unit if freq_unit is not None else ("1/d" if normalization == "amplitude" else "uHz")
+        freq = np.atleast_1d(np.asarray(frequency, dtype=np.float64))
+        if freq.ndim != 1 or freq.size < 1 or not (np.all(np.isfinite(freq)) and np.all(freq > 0)):
+            raise ValueError("frequency must be a 1-D grid of finite values > 0")
+        if oversample_factor is None:
+            oversample_factor = 5.0 if normalization == "amplitude" else 1.0
+        osf = float(oversample_factor)
+        if not (osf > 0 and np.isfinite(osf)):
+            raise ValueError("oversample_factor must be finite and > 0 (got %r)" % (oversample_factor,))
+        f_day = np.ascontiguousarray(freq / _freq_unit_factor(unit))
+        F = int(f_day.size)
+        if F * npix >= 2 ** 31:
+            raise ValueError("a power cube of %d x %d values per cutout is too large" % (F, npix))
+        power_bytes = B * F * npix * 8
+        if return_power and power_bytes > max_output_mb * 2 ** 20:
+            raise ValueError("the power cube of %d x %d x %d x %d float64 is %.0f MiB, more than max_output_mb = %r; raise it, pass "
+                             "fewer cutouts or frequencies per call, or pass return_power=False for the peak images alone"
+                             % (B, F, ny, nx, power_bytes / 2.0 ** 20, max_output_mb))
+        fin = np.isfinite(self.time)
+        first = np.argmax(fin, axis=1)
+        t_ref = np.ascontiguousarray(np.where(fin.any(axis=1), self.time[np.arange(B), first], np.nan))
+        st = _vp(self.stream or None)
+        d_power = DeviceBuffer(h, power_bytes) if return_power else None
+        d_peak, d_idx = DeviceBuffer(h, B * npix * 8), DeviceBuffer(h, B * npix * 4)
+        d_used, d_status = DeviceBuffer(h, B * npix * 4), DeviceBuffer(h, B * 4)
+        _capi._check(_capi._lib.lk_cube_pixel_ls_batch_dev(
+            h._h, B, N, npix, _vp(self.d_time.ptr), _vp(self.d_flux.ptr), f_day.ctypes.data_as(_dp), F, norms[normalization], osf,
+            t_ref.ctypes.data_as(_dp), _vp(d_power.ptr if return_power else None), _vp(d_peak.ptr), _vp(d_idx.ptr), _vp(d_used.ptr),
+            _vp(d_status.ptr), st))
+        out = dict(status=d_status.download(np.int32, B, stream=self.stream), t_ref=t_ref, frequency=f_day)    # (synchronises)
+        if not to_host:
+            out.update(peak_power=d_peak, peak_index=d_idx, n_used=d_used)
+            if return_power:
+                out["power"] = d_power
+            return out
+        if return_power:
+            out["power"] = d_power.download(np.float64, B * F * npix, stream=self.stream).reshape(B, F, ny, nx)
+        out["peak_power"] = d_peak.download(np.float64, B * npix, stream=self.stream).reshape(B, ny, nx)
+        out["peak_index"] = d_idx.download(np.int32, B * npix, stream=self.stream).reshape(B, ny, nx)
+        out["peak_frequency"] = np.where(out["peak_index"] >= 0, f_day[np.clip(out["peak_index"], 0, F - 1)], np.nan)
+        out["n_used"] = d_used.download(np.int32, B * npix, stream=self.stream).reshape(B, ny, nx)
+        return out
+
     # ---------------------------------------------------------------- PLD
     def pld_correct(self, aperture_mask="all", pld_aperture_mask="all", background_aperture_mask="all", pld_order=3,
                     pca_components=16, spline_n_knots=None, spline_degree=5, normalize_background_pixels=True,

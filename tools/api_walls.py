@@ -137,7 +137,16 @@ timed region ends with a synchronise.  Written to profiles/ampimage_walls.txt.
 subtraction) and Fm the same with the masks given; E `cubes.estimate_background()`, Em with the masks given, Es with the scatter
 too; S `cubes.subtract_background(background=DeviceBuffer)`, the streaming subtraction alone; H the host route: `to_host()`,
 `PixelCube.subtract_background` per cutout on 16 threads, `from_cubes`.  Every timed region ends with a synchronise.  Written to
-profiles/background_walls.txt."""
+profiles/background_walls.txt.
+
+`pixelpg`: the per-pixel Lomb-Scargle periodograms of the same batch shape on one grid of `LK_WALLS_F` (default 2000) frequencies,
+in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5) times after one warm-up.  R
+`cubes.pixel_periodograms(grid, to_host=False)`, the power cube resident; P the same with `return_power=False`; L the route
+without the kernel: `to_host()`, the host transpose into B x npix light curves, `DeviceLightCurveBatch.from_arrays`, then
+`to_periodogram_power(grid, ls_method="slow", to_host=False)`; H the mirror `PixelCube.pixel_periodogram` on 16 threads for the
+first `LK_WALLS_MIRROR_B` (default 16) cutouts only (a cutout takes seconds), scaled to the batch in the report.  Every timed
+region ends with a synchronise.  Written to profiles/pixelpg_walls.txt.  `pixelpg_trace`: R and P once each after a warm-up, for a
+`rocprofv3 --kernel-trace --stats` run of its own (profiles/pixelpg_kernel_stats.txt)."""
 import cProfile
 import io
 import os
@@ -1308,6 +1317,87 @@ def ampimage():
         "  R / D = %.2f; R3 / D = %.2f; H / R = %.1f; kernel times alone: profiles/ampimage_kernels.txt" % (med["R"] / med["D"], med["R3"] / med["D"], med["H"] / med["R"])])
 
 
+def pixelpg(which):
+    from concurrent.futures import ThreadPoolExecutor
+    from lightkurve_amd.device import DeviceLightCurveBatch, DevicePixelCubeBatch
+    B, N, side, F = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "500"), ("LK_WALLS_N", "4000"), ("LK_WALLS_SIDE", "11"),
+                                                            ("LK_WALLS_F", "2000")))
+    reps, Bm = int(os.environ.get("LK_WALLS_REPS", "5")), min(B, int(os.environ.get("LK_WALLS_MIRROR_B", "16")))
+    rng = np.random.default_rng(53)
+    npix = side * side
+    t = 1000.0 + np.arange(N) / 720.0                                    # two-minute cadences
+    grid = np.linspace(1.5 / (t[-1] - t[0]), 0.25 * 720.0, F)            # [1/d]: 1.5 cycles per baseline to a quarter of the sampling rate
+    freq = rng.uniform(5.0, 60.0, B)
+    yy, xx = np.indices((side, side))
+    c = side // 2
+    star = (1e4 + 3000.0 * np.exp(-((xx - c) ** 2 + (yy - c) ** 2) / 1.62)).astype(np.float32)
+    neighbour = (800.0 * np.exp(-((xx - c - 3) ** 2 + (yy - c) ** 2) / 1.62)).astype(np.float32)
+    flux = np.empty((B, N, side, side), dtype=np.float32)
+    for b in range(B):                                                  # (drawn per cutout: 1.9 GB of cubes in all)
+        signal = (1.0 + 0.05 * np.sin(2 * np.pi * freq[b] * (t - t[0]) + 0.7)).astype(np.float32)
+        flux[b] = star + neighbour * signal[:, None, None] + 2.0 * rng.standard_normal((N, side, side), dtype=np.float32)
+    err = np.full_like(flux, 2.0)
+    cubes = DevicePixelCubeBatch.from_arrays(np.tile(t, (B, 1)), flux, err)
+    cubes.synchronize()
+    del flux, err
+
+    def resident(return_power=True):
+        out = cubes.pixel_periodograms(grid, return_power=return_power, to_host=False)
+        cubes.synchronize()
+        return out
+
+    if "pixelpg_trace" in which:
+        resident()
+        resident()
+        resident(False)
+        return
+
+    def per_light_curve():
+        host = cubes.to_host()
+        y = np.empty((B, npix, N), dtype=np.float64)
+        for b in range(B):                                              # the transpose: every pixel becomes a light curve
+            y[b] = host[b].flux.reshape(N, npix).T
+        lcs = DeviceLightCurveBatch.from_arrays(np.tile(t, B * npix), y.reshape(-1), np.ones(B * npix * N),
+                                                np.arange(B * npix + 1, dtype=np.int64) * N)
+        out = lcs.to_periodogram_power(grid, ls_method="slow", to_host=False)
+        lcs.synchronize()
+        return out
+
+    host_m = cubes.to_host()[:Bm]
+
+    def mirror():
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            return list(ex.map(lambda cube: cube.pixel_periodogram(grid), host_m))
+
+    fns = {"R": resident, "P": lambda: resident(False), "L": per_light_curve, "H": mirror}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    r = first["R"]["power"].download(np.float64, Bm * F * npix, stream=cubes.stream).reshape(Bm, F, npix)
+    l = first["L"].download(np.float64, Bm * npix * F).reshape(Bm, npix, F).transpose(0, 2, 1)
+    h = np.stack([o["power"].reshape(F, npix) for o in first["H"]])
+    top = np.max(h, axis=1, keepdims=True)
+    rel = {"R - H": float(np.max(np.abs(r - h) / top)), "L - H": float(np.max(np.abs(l - h) / top)), "R - L": float(np.max(np.abs(r - l) / top))}
+    pk = first["P"]["peak_index"].download(np.int32, B * npix, stream=cubes.stream)
+    same_peaks = np.array_equal(pk, first["R"]["peak_index"].download(np.int32, B * npix, stream=cubes.stream))
+    peaks_h = np.array_equal(pk[:Bm * npix].reshape(Bm, npix), np.stack([o["peak_index"].reshape(npix) for o in first["H"]]))
+    first.clear()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    write_walls("pixelpg_walls.txt", [
+        "per-pixel Lomb-Scargle periodograms, %d cutouts x %d cadences x %d x %d float32, one grid of %d frequencies (%.1f MB of flux "
+        "resident, %.1f MB of power)" % (B, N, side, side, F, B * N * npix * 4 / 1e6, B * F * npix * 8 / 1e6),
+        "  R    cubes.pixel_periodograms(grid, to_host=False): stats, spectra, peaks; the power cube resident            %s" % spread(ts["R"]),
+        "  P    the same with return_power=False: the peak images alone                                                   %s" % spread(ts["P"]),
+        "  L    to_host(), host transpose, DeviceLightCurveBatch.from_arrays, to_periodogram_power(ls_method='slow')    %s" % spread(ts["L"]),
+        "  H    PixelCube.pixel_periodogram on 16 threads, the first %d cutouts only                                      %s" % (Bm, spread(ts["H"])),
+        "  max |difference| / max of the pixel's spectrum over the first %d cutouts: %s" % (Bm, ", ".join("%s %.2e" % kv for kv in rel.items())),
+        "  P and R: the same peak_index: %s; P and H (first %d cutouts): the same peak_index: %s" % (same_peaks, Bm, peaks_h),
+        "  L / R = %.2f; L / P = %.2f; H scaled to %d cutouts / R = %.0f; kernel times alone: profiles/pixelpg_kernel_stats.txt"
+        % (med["L"] / med["R"], med["L"] / med["P"], B, med["H"] * B / Bm / med["R"])])
+
+
 def background():
     from concurrent.futures import ThreadPoolExecutor
     from lightkurve_amd.device import DevicePixelCubeBatch
@@ -1542,6 +1632,8 @@ def main():
         ampimage()
     if "background" in which:
         background()
+    if {"pixelpg", "pixelpg_trace"} & set(which):
+        pixelpg(which)
     if {"stitch", "stitch_trace"} & set(which):
         stitch(which)
     if "flatten" in which:
