@@ -1253,6 +1253,50 @@ int lk_cube_pixel_ls_batch_dev(lk_handle *h, int B, int N, int npix, const doubl
                                int F, int normalization, double oversample_factor, const double *t_ref, double *power,
                                double *peak_power, int32_t *peak_index, int32_t *n_used, int32_t *status, void *stream);
 
+/* lk_cube_psf_photometry_batch_dev <- deblended PSF photometry per cadence of every cutout (PixelCube.psf_photometry is the numpy
+ *   mirror and the definition): the fluxes of up to 8 stars at KNOWN positions and one constant background, by weighted linear
+ *   least squares on every cadence's image.  What TargetPixelFile.to_lightcurve(method="prf") is used for, in its linear form: no
+ *   position or width is fitted, the PSF is a pixel-integrated Gaussian and not a tabulated PRF.
+ *   Stars: star_col / star_row are HOST arrays [B][S_max], 1 <= S_max <= 8, in the coordinates of lk_cube_centroids_batch_dev
+ *   (pixel (iy, ix) covers [column0 + ix - 1/2, column0 + ix + 1/2] x [row0 + iy - 1/2, row0 + iy + 1/2]).  A star with a NaN
+ *   coordinate is not part of its cutout; the others keep their order: cutout b has S_b of them and owns the output rows
+ *   star_off[b] .. star_off[b] + S_b - 1, star_off the prefix sums of S_b (written to the HOST array star_off of B + 1 int32 when
+ *   that is not NULL).  sigma: HOST array [B][2] = (sigma_col, sigma_row) in pixels.  shift_col / shift_row (nullable, both or
+ *   neither): DEVICE arrays [B][N] added to every star's position at that cadence.
+ *   PSF of star s at cadence n: with c = star_col[s] + shift_col[n] - column0 and E_c(k) = erf((k - 1/2 - c) / (sqrt(2)
+ *   sigma_col)), k = 0 .. nx, the column factor is (E_c(ix + 1) - E_c(ix)) / 2; the row factor likewise from r and sigma_row;
+ *   g[iy][ix] = their product.  Without shifts the nx + ny factors of a star are formed once per cutout, with shifts once per
+ *   cadence.
+ *   Fit: the design of a cadence is A = [g_0 ... g_{S-1}, 1] over its used pixels: those in the mask (mask / mask_stride as
+ *   lk_cube_aperture_batch_dev) whose flux is finite and, with use_flux_err != 0, whose flux_err is finite and > 0.  Weights
+ *   w = 1 / flux_err^2 in float64 from the float32 value, or 1 (flux_err is then not read).  G = A^T W A and rhs = A^T W y are
+ *   summed over the used pixels, G is factored by Cholesky without pivoting in index order; the cadence is SINGULAR
+ *   when a pivot d_k is not finite or d_k <= 1e-12 G_kk.  flux[s] = theta_s, flux_err[s] = sqrt((G^-1)_ss), background =
+ *   theta_S, chi2 = sum w (y - A theta)^2 from the residuals, n_used = the used pixels.  All float64 after the float32 load.
+ *   Outputs on the device: flux_out / flux_err_out [star_off[B]][N] float64 (row-major: every star is one light curve of N
+ *   cadences); time_out (nullable) [star_off[B]][N] float64: every row's times, those of its cutout; background, chi2 [B][N]
+ *   float64; n_used [B][N] int32; cadence_status [B][N] int8: 0 ok, 1 the time or a shift is not finite, 2 n_used < S + 2, 3
+ *   singular (in that order of precedence) — a cadence that is not ok has NaN in flux, flux_err, background and chi2, nothing
+ *   is raised; status [B] int32: 0, or 1 when no cadence of the cutout is ok.
+ *   LK_EINVAL: a NULL required buffer, B < 1 or > 65535, N, ny or nx < 1, N * npix >= 2^31, S_max outside 1 .. 8, a cutout
+ *   without a star, an infinite star coordinate, a sigma that is not finite and > 0, one shift array without the other, a
+ *   mask_stride that is neither 0 nor npix, or a cutout too large for the LDS tile: 16 x 8 pitch + npix + 8 S_max (nx + ny) x
+ *   (16 with shifts, else 1) bytes must not exceed 160 KiB, pitch = npix rounded up to 4 x an odd number (4 pitch instead of
+ *   8 with use_flux_err == 0).
+ *   Four lanes per cadence: a workgroup of one wavefront stages 16 consecutive cadences of flux and flux_err in LDS; lane k of
+ *   a cadence walks the pixel rows k, k + 4, ... in index order with the (S + 1)(S + 2) / 2 + S + 1 sums in registers (the
+ *   kernel is instantiated on S; the cutouts of a batch are grouped by their star count), the four partial sums are added in
+ *   a fixed order, every lane solves, and chi2 is taken from the same tile: flux and flux_err are read from HBM once.  No
+ *   atomics; the order of every sum depends on the cutout's own data alone, so a cutout's outputs have the same bits alone,
+ *   at any batch position and from run to run.  Scratch: B x (S_max (nx + ny + 2) + 2) x 8 + 12 B bytes of the handle's
+ *   arena.  Enqueued, no synchronisation. */
+int lk_cube_psf_photometry_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
+                                     const float *flux_err, const uint8_t *mask, int mask_stride, int S_max,
+                                     const double *star_col, const double *star_row, const double *sigma, const double *shift_col,
+                                     const double *shift_row, double column0, double row0, int use_flux_err, int32_t *star_off,
+                                     double *time_out, double *flux_out, double *flux_err_out, double *background, double *chi2,
+                                     int32_t *n_used, int8_t *cadence_status, int32_t *status, void *stream);
+
 /* lk_cube_background_batch_dev <- TargetPixelFile.estimate_background(aperture_mask) per cadence of the same resident cubes,
  *   and the subtraction of that background, in one pass (PixelCube.estimate_background / subtract_background are the numpy
  *   mirror).  mask / mask_stride as lk_cube_aperture_batch_dev; sel = the masked pixels of cadence i of cutout b.

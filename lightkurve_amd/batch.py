@@ -10,7 +10,7 @@ from . import packed
 
 __all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch", "river_batch", "fill_gaps_batch",
            "periodogram_peaks", "flatten_batch",
-           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "pixel_periodograms_batch", "subtract_background_batch", "regression_correct_batch", "cbv_correct_batch"]
+           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "psf_photometry_batch", "pixel_periodograms_batch", "subtract_background_batch", "regression_correct_batch", "cbv_correct_batch"]
 
 
 def _resolve_device(device):
@@ -401,6 +401,17 @@ def amplitude_images_batch(cubes, frequency, device=0, **kwargs):
     ``DevicePixelCubeBatch.amplitude_images`` with its keywords and its dict of host arrays.  Not sharded over ranks."""
     from .device import DevicePixelCubeBatch
     return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).amplitude_images(frequency, **kwargs)
+
+
+def psf_photometry_batch(cubes, star_col, star_row, sigma, device=0, **kwargs):
+    """``PixelCube.psf_photometry`` of every cutout, for host cutouts: ``cubes`` a list of same-shaped float32 ``PixelCube``s,
+    ``star_col`` / ``star_row`` [S] or [B, S] (NaN = no star), ``sigma`` a scalar, a pair or [B, 2].  One upload
+    (``DevicePixelCubeBatch.from_cubes``), then ``DevicePixelCubeBatch.psf_photometry`` with its keywords; returns its
+    ``(lcs, info)``: the resident light curves, one per star, and ``info`` as host arrays unless ``to_host=False`` is passed.
+    Not sharded over ranks."""
+    from .device import DevicePixelCubeBatch
+    kwargs.setdefault("to_host", True)
+    return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).psf_photometry(star_col, star_row, sigma, **kwargs)
 
 
 def pixel_periodograms_batch(cubes, frequency, device=0, **kwargs):

@@ -126,6 +126,17 @@ def _background_meta(npix, bkg):
     return {"BKG_SUBTRACTED": True, "BKG_NPIX": int(npix), "BKG_NAN_CADENCES": int(np.sum(np.isnan(bkg)))}
 
 
+def _psf_sigma(sigma):
+    """``sigma`` of ``psf_photometry``: a scalar or (sigma_col, sigma_row) -> the pair, finite and > 0."""
+    sg = np.asarray(sigma, dtype=np.float64)
+    if sg.shape not in ((), (2,)):
+        raise ValueError("sigma must be a scalar or (sigma_col, sigma_row) (got shape %r)" % (sg.shape,))
+    sg = np.broadcast_to(sg, (2,))
+    if not (np.all(np.isfinite(sg)) and np.all(sg > 0)):
+        raise ValueError("sigma must be finite and > 0 (got %r)" % (sigma,))
+    return float(sg[0]), float(sg[1])
+
+
 class PixelCube(object):
     """Minimal stand-in for the slice of TargetPixelFile that PLDCorrector touches."""
 
@@ -377,6 +388,119 @@ class PixelCube(object):
         out["offset_pix"] = float(np.sqrt(np.sum(out["offset"] ** 2)))
         out["status"] = status if status else 3 if np.isnan(out["offset_pix"]) else 0
         return out
+
+    def psf_photometry(self, star_col, star_row, sigma, shifts=None, aperture_mask="all", column=0, row=0, use_flux_err=True):
+        """Deblended PSF photometry per cadence: the fluxes of up to 8 stars at KNOWN positions and one constant background, by
+        weighted linear least squares on every cadence's image (the host mirror of ``DevicePixelCubeBatch.psf_photometry`` and
+        its definition, float64 numpy after the float32 load).  The linear form of ``TargetPixelFile.to_lightcurve(method=
+        "prf")``: nothing about the PSF is fitted, and it is a pixel-integrated Gaussian, not a tabulated PRF.
+        ``star_col`` / ``star_row`` [S]: positions in the coordinates of ``estimate_centroids`` — pixel (iy, ix) covers
+        [column + ix - 1/2, column + ix + 1/2] x [row + iy - 1/2, row + iy + 1/2]; a star with a NaN coordinate is left out.
+        ``sigma``: a scalar or (sigma_col, sigma_row), pixels.  ``shifts``: None or (shift_col[N], shift_row[N]), added to every
+        star's position at that cadence.  With c = star_col[s] + shift_col[n] - column and E(k) = erf((k - 1/2 - c) / (sqrt(2)
+        sigma_col)), star s has the column factors (E(ix + 1) - E(ix)) / 2, the row factors likewise, and g[iy, ix] = their
+        product.  Per cadence the design is A = [g_0 ... g_{S-1}, 1] over the used pixels: those of ``aperture_mask`` whose flux
+        is finite and, with ``use_flux_err``, whose flux_err is finite and > 0; weights w = 1 / flux_err^2, or 1.  G = A^T W A
+        is factored by Cholesky without pivoting, in index order; the cadence is singular when a pivot d_k is not finite or d_k
+        <= 1e-12 G_kk.  Returns a dict: ``flux`` / ``flux_err`` (S, N) = theta_s and sqrt((G^-1)_ss); ``background`` (N,) =
+        theta_S; ``chi2`` (N,) = sum w (y - A theta)^2; ``n_used`` (N,) int32, the used pixels; ``cadence_status`` (N,) int8: 0
+        ok, 1 the time or a shift is not finite, 2 n_used < S + 2, 3 singular (a cadence that is not ok is NaN in the four float
+        outputs; nothing is raised); ``status``: 0, or 1 when no cadence is ok; ``star_index`` (S,): the stars that took part;
+        ``min_pivot_ratio`` (N,): the smallest d_k / G_kk of the factorisation (0 for a pivot that is not finite)."""
+        import math
+        col, rw = np.atleast_1d(np.asarray(star_col, dtype=np.float64)), np.atleast_1d(np.asarray(star_row, dtype=np.float64))
+        if col.ndim != 1 or col.shape != rw.shape:
+            raise ValueError("star_col and star_row must be 1-D arrays of one length (got %r and %r)" % (col.shape, rw.shape))
+        star_index = np.flatnonzero(~(np.isnan(col) | np.isnan(rw)))
+        col, rw = col[star_index], rw[star_index]
+        S = len(star_index)
+        if not 1 <= S <= 8:
+            raise ValueError("psf_photometry fits 1 .. 8 stars per cutout (got %d)" % S)
+        if not (np.all(np.isfinite(col)) and np.all(np.isfinite(rw))):
+            raise ValueError("a star position is infinite")
+        sig_c, sig_r = _psf_sigma(sigma)
+        N, ny, nx = self.shape
+        npix, K = ny * nx, S + 1
+        if shifts is None:
+            dc = dr = np.zeros(1)
+        else:
+            dc, dr = (np.asarray(a, dtype=np.float64) for a in shifts)
+            if dc.shape != (N,) or dr.shape != (N,):
+                raise ValueError("shifts must be a pair of arrays of one value per cadence (%d)" % N)
+        ap = self._parse_aperture_mask(aperture_mask).reshape(npix)
+        erf = np.vectorize(math.erf, otypes=[np.float64])
+
+        def factors(c, sg, n):                                   # c: (S, N or 1) -> (S, N or 1, n)
+            E = erf((np.arange(n + 1) - 0.5 - c[..., None]) / (np.sqrt(2.0) * sg))
+            return 0.5 * (E[..., 1:] - E[..., :-1])
+
+        with np.errstate(all="ignore"):
+            g_col = factors(col[:, None] + dc[None, :] - column, sig_c, nx)
+            g_row = factors(rw[:, None] + dr[None, :] - row, sig_r, ny)
+            A = np.empty((N, npix, K))
+            for s in range(S):
+                A[:, :, s] = (g_col[s][:, None, :] * g_row[s][:, :, None]).reshape(-1, npix)
+            A[:, :, S] = 1.0
+            y32 = np.asarray(self.flux).reshape(N, npix)
+            used = ap[None, :] & np.isfinite(y32)
+            if use_flux_err:
+                e32 = np.asarray(self.flux_err).reshape(N, npix)
+                used &= np.isfinite(e32) & (e32 > 0)
+                e = np.where(used, e32, 1).astype(np.float64)
+                w = np.where(used, 1.0 / (e * e), 0.0)
+            else:
+                w = used.astype(np.float64)
+            y = np.where(used, y32, 0).astype(np.float64)
+            A = np.where(used[:, :, None], A, 0.0)
+            WA = A * w[:, :, None]
+            G = np.einsum("npi,npj->nij", WA, A)
+            rhs = np.einsum("npi,np->ni", WA, y)
+            L = np.zeros((N, K, K))
+            singular = np.zeros(N, dtype=bool)
+            ratio = np.full(N, np.inf)
+            for k in range(K):
+                d = G[:, k, k].copy()
+                for j in range(k):
+                    d -= L[:, k, j] * L[:, k, j]
+                singular |= ~(np.isfinite(d) & (d > 1e-12 * G[:, k, k]))
+                ratio = np.minimum(ratio, np.where(np.isfinite(d) & (G[:, k, k] > 0), d / G[:, k, k], 0.0))
+                L[:, k, k] = np.sqrt(d)
+                for i in range(k + 1, K):
+                    s_ = G[:, k, i].copy()
+                    for j in range(k):
+                        s_ -= L[:, i, j] * L[:, k, j]
+                    L[:, i, k] = s_ / L[:, k, k]
+            z, theta, var = np.zeros((N, K)), np.zeros((N, K)), np.zeros((N, K))
+            for i in range(K):
+                s_ = rhs[:, i].copy()
+                for j in range(i):
+                    s_ -= L[:, i, j] * z[:, j]
+                z[:, i] = s_ / L[:, i, i]
+            for i in range(K - 1, -1, -1):
+                s_ = z[:, i].copy()
+                for j in range(i + 1, K):
+                    s_ -= L[:, j, i] * theta[:, j]
+                theta[:, i] = s_ / L[:, i, i]
+            for k in range(K):                                   # column k of L^-1; (G^-1)_kk = the sum of its squares
+                M = np.zeros((N, K))
+                M[:, k] = 1.0 / L[:, k, k]
+                for i in range(k + 1, K):
+                    s_ = np.zeros(N)
+                    for j in range(k, i):
+                        s_ -= L[:, i, j] * M[:, j]
+                    M[:, i] = s_ / L[:, i, i]
+                var[:, k] = np.sum(M[:, k:] ** 2, axis=1)
+            res = y - np.einsum("npi,ni->np", A, theta)
+            chi2 = np.sum(w * res * res, axis=1)
+        n_used = used.sum(axis=1).astype(np.int32)
+        fin = np.isfinite(self.time) & np.isfinite(dc) & np.isfinite(dr)
+        cst = np.where(~fin, 1, np.where(n_used < S + 2, 2, np.where(singular, 3, 0))).astype(np.int8)
+        bad = cst != 0
+        with np.errstate(all="ignore"):
+            err = np.sqrt(var[:, :S]).T
+        return {"flux": np.where(bad[None, :], np.nan, theta[:, :S].T), "flux_err": np.where(bad[None, :], np.nan, err),
+                "background": np.where(bad, np.nan, theta[:, S]), "chi2": np.where(bad, np.nan, chi2), "n_used": n_used,
+                "cadence_status": cst, "status": 0 if np.any(cst == 0) else 1, "star_index": star_index, "min_pivot_ratio": ratio}
 
     def pixel_periodogram(self, frequency, normalization="amplitude", freq_unit=None, oversample_factor=None):
         """One Lomb-Scargle spectrum per pixel on ONE shared ``frequency`` grid, and where each peaks: which pixels vary, and at

@@ -435,6 +435,14 @@ int ampimage_offsets_launch(lk_handle *h, int B, const int32_t *fit_status, cons
 int cube_pixelpg_launch(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const double *frequency_host,
                         int F, int normalization, double oversample_factor, const double *t_ref_host, double *power,
                         double *peak_power, int32_t *peak_index, int32_t *n_used, int32_t *status, hipStream_t stream);
+// psfphot.hip: deblended PSF photometry per cadence of B resident cutouts — the fluxes of up to 8 stars at known positions (host
+// arrays, NaN = no star) and a constant background by weighted least squares; star_off_host (nullable) receives the row
+// offsets.  Everything else on the device; enqueued, no synchronisation
+int cube_psfphot_launch(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux, const float *flux_err,
+                        const uint8_t *mask, int mask_stride, int S_max, const double *star_col_host, const double *star_row_host,
+                        const double *sigma_host, const double *shift_col, const double *shift_row, double column0, double row0,
+                        int use_flux_err, int32_t *star_off_host, double *time_out, double *flux_out, double *flux_err_out, double *background,
+                        double *chi2, int32_t *n_used, int8_t *cadence_status, int32_t *status, hipStream_t stream);
 // sff.hip: SFFCorrector for a ragged resident batch.  The regression launcher owns h->ws, so the design matrices and everything
 // else that lives across it sit in `scratch`, a device block of the caller's (sff_scratch_bytes); status_host is valid on
 // return (the call synchronises once, to group the targets by their design width)

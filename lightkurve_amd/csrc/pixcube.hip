@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "block_select.hpp"
+#include "stage_tile.hpp"  // stage_contiguous, shared with psfphot.hip
 #include "fold_phase.hpp"  // np_mod: the difference image classes its cadences by create_transit_mask's phase
 
 namespace lk {
@@ -25,35 +26,6 @@ namespace lk {
 constexpr int AP_T = 64;       // cadences per workgroup: one lane of wave 0 (flux) and of wave 1 (flux_err) each
 constexpr int AP_WMAX = 127;   // pixel columns per LDS chunk: 2 tiles x 64 rows x 127 dwords + the mask < 64 KB
 constexpr int MED_G = 16;      // adjacent pixels per workgroup of the median image: one 64-byte segment of every cadence row
-
-// rows x npix floats that are CONTIGUOUS in global memory -> tile[row * pitch + column]: 16-byte loads once the
-// address is aligned, scalar head and tail.
-__device__ __forceinline__ void stage_contiguous(const float *__restrict__ g, float *__restrict__ tile, int total, int npix,
-                                                 int pitch) {
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int mis = (int)((reinterpret_cast<uintptr_t>(g) >> 2) & 3);
-    const int head = min(total, (4 - mis) & 3);
-    if (tid < head) tile[(tid / npix) * pitch + tid % npix] = g[tid];
-    const int nvec = (total - head) >> 2;
-    const float4 *gv = reinterpret_cast<const float4 *>(g + head);
-#pragma unroll 4
-    for (int v = tid; v < nvec; v += nt) {
-        const float4 x = gv[v];
-        const int i = head + 4 * v;
-        int r = i / npix, c = i - r * npix;
-        const float e[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            tile[r * pitch + c] = e[k];
-            if (++c == npix) {
-                c = 0;
-                ++r;
-            }
-        }
-    }
-    const int i = head + 4 * nvec + tid;
-    if (i < total) tile[(i / npix) * pitch + i % npix] = g[i];
-}
 
 // columns [p0, p0 + w) of rows x npix floats -> tile[row * pitch + column - p0] (cutouts wider than one chunk)
 __device__ __forceinline__ void stage_columns(const float *__restrict__ g, float *__restrict__ tile, int rows, int npix, int p0,

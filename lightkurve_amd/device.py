@@ -2267,6 +2267,103 @@ class DevicePixelCubeBatch(object):
         out["n_used"] = d_used.download(np.int32, B * npix, stream=self.stream).reshape(B, ny, nx)
         return out
 
+    # ---------------------------------------------------------------- PSF photometry
+    def psf_photometry(self, star_col, star_row, sigma, shifts=None, aperture_mask="all", column=0, row=0, use_flux_err=True,
+                       to_host=False):
+        """Deblended PSF photometry per cadence of every cutout: the light curves of up to 8 blended stars at KNOWN positions,
+        each without its neighbours, and a constant background — a weighted linear least-squares fit of pixel-integrated
+        Gaussians to every cadence's image (``lk_cube_psf_photometry_batch_dev``; the numpy mirror and the definition is
+        ``PixelCube.psf_photometry``).  The linear form of ``TargetPixelFile.to_lightcurve(method="prf")``: no position or
+        width is fitted and no PRF file is read.  ``star_col`` / ``star_row``: [S] (the same stars in every cutout) or [B, S],
+        S <= 8, in the coordinates of ``estimate_centroids`` with the same ``column`` / ``row`` (pixel (iy, ix) is centred on
+        (column + ix, row + iy)); a star with a NaN coordinate is not part of its cutout, so cutouts with fewer stars are padded
+        with NaN.  ``sigma``: a scalar, (sigma_col, sigma_row), or [B, 2], pixels.  ``shifts``: None, or a pair (shift_col,
+        shift_row) of host arrays [B, N] or of ``DeviceBuffer``s of B x N float64, added to every star's position at that
+        cadence.  ``estimate_centroids(to_host=False)`` returns that layout; offsets from centroids, on the host::
+
+            c, r = cubes.estimate_centroids(to_host=True)
+            shifts = (c - np.nanmedian(c, axis=1, keepdims=True), r - np.nanmedian(r, axis=1, keepdims=True))
+            lcs, info = cubes.psf_photometry(star_col, star_row, 1.1, shifts=shifts)
+
+        A cadence uses the pixels of ``aperture_mask`` whose flux is finite and, with ``use_flux_err``, whose flux_err is finite
+        and > 0, weighted by 1 / flux_err^2 (else by 1).  Returns ``(lcs, info)``.  ``lcs``: a ``DeviceLightCurveBatch`` with
+        one light curve per star, cutout-major (cutout b owns the rows ``star_off[b] : star_off[b + 1]``), N cadences each on
+        its cutout's times, flux = the star's fitted flux and flux_err = sqrt((G^-1)_ss); a cadence that failed is NaN, so
+        ``remove_nans()`` and the rest of the chain follow; ``meta`` is the cutout's plus ``STAR_INDEX``, ``STAR_COL``,
+        ``STAR_ROW``.  ``info``: ``background`` and ``chi2`` (B x N float64), ``n_used`` (B x N int32, the used pixels),
+        ``cadence_status`` (B x N int8: 0 ok, 1 the time or a shift is not finite, 2 n_used < S + 2, 3 singular), ``status`` (B
+        int32: 1 when no cadence is ok) and ``star_off`` (B + 1 int32) — ``DeviceBuffer``s enqueued on the batch's stream, or
+        host arrays with ``to_host=True``.  Nothing is raised per cadence.  A cutout's outputs have the same bits alone, at any
+        batch position and from run to run."""
+        from .correctors.pldcorrector import _psf_sigma
+        h, (B, N, ny, nx) = self.handle, self.shape
+        npix = ny * nx
+        pos = []
+        for name, a in (("star_col", star_col), ("star_row", star_row)):
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim == 1:
+                a = np.broadcast_to(a, (B, a.size))
+            if a.ndim != 2 or a.shape[0] != B:
+                raise ValueError("%s must be [S] or [B, S] with B = %d (got shape %r)" % (name, B, a.shape))
+            pos.append(np.ascontiguousarray(a))
+        if pos[0].shape != pos[1].shape or not 1 <= pos[0].shape[1] <= 8:
+            raise ValueError("star_col and star_row must have one shape with 1 .. 8 stars per cutout (got %r and %r)"
+                             % (pos[0].shape, pos[1].shape))
+        S_max = pos[0].shape[1]
+        part = ~(np.isnan(pos[0]) | np.isnan(pos[1]))
+        if not np.all(np.isfinite(pos[0][part]) & np.isfinite(pos[1][part])):
+            raise ValueError("a star position is infinite")
+        if not np.all(part.any(axis=1)):
+            raise ValueError("cutouts %s have no star" % np.flatnonzero(~part.any(axis=1)).tolist())
+        sg = np.asarray(sigma, dtype=np.float64)
+        sg = np.array([_psf_sigma(s) for s in sg]) if sg.shape == (B, 2) else np.tile(_psf_sigma(sg), (B, 1))
+        sg = np.ascontiguousarray(sg, dtype=np.float64)
+        keep = []
+        d_shift = [None, None]
+        if shifts is not None:
+            if len(shifts) != 2:
+                raise ValueError("shifts must be a pair (shift_col, shift_row)")
+            for i, a in enumerate(shifts):
+                if isinstance(a, DeviceBuffer):
+                    if a.nbytes != B * N * 8:
+                        raise ValueError("a shift buffer of %d bytes for %d x %d float64 cadences" % (a.nbytes, B, N))
+                    d_shift[i] = a
+                else:
+                    a = np.asarray(a, dtype=np.float64)
+                    if a.shape != (B, N):
+                        raise ValueError("shifts must be (B, N) = %r arrays (got %r)" % ((B, N), a.shape))
+                    d_shift[i], k = _upload(h, a, self.stream, np.float64)
+                    keep.append(k)
+        m = self._masks(aperture_mask, False, None, {})
+        d_mask, k = _upload(h, m.reshape(-1, npix), self.stream, np.uint8)
+        keep.append(k)
+        rows = int(part.sum())
+        d_t, d_f, d_e = (DeviceBuffer(h, rows * N * 8) for _ in range(3))
+        d_bkg, d_chi = DeviceBuffer(h, B * N * 8), DeviceBuffer(h, B * N * 8)
+        d_n, d_cs, d_st = DeviceBuffer(h, B * N * 4), DeviceBuffer(h, B * N), DeviceBuffer(h, B * 4)
+        star_off = np.zeros(B + 1, dtype=np.int32)
+        _capi._check(_capi._lib.lk_cube_psf_photometry_batch_dev(
+            h._h, B, N, ny, nx, _vp(self.d_time.ptr), _vp(self.d_flux.ptr), _vp(self.d_flux_err.ptr), _vp(d_mask.ptr),
+            npix if m.ndim == 3 else 0, S_max, pos[0].ctypes.data_as(_dp), pos[1].ctypes.data_as(_dp), sg.ctypes.data_as(_dp),
+            _vp(d_shift[0].ptr if shifts is not None else None), _vp(d_shift[1].ptr if shifts is not None else None),
+            float(column), float(row), int(bool(use_flux_err)), star_off.ctypes.data_as(_i32p), _vp(d_t.ptr), _vp(d_f.ptr),
+            _vp(d_e.ptr), _vp(d_bkg.ptr), _vp(d_chi.ptr), _vp(d_n.ptr), _vp(d_cs.ptr), _vp(d_st.ptr), _vp(self.stream or None)))
+        meta = [dict(self.meta[b], STAR_INDEX=int(s), STAR_COL=float(pos[0][b, s]), STAR_ROW=float(pos[1][b, s]))
+                for b in range(B) for s in np.flatnonzero(part[b])]
+        lcs = DeviceLightCurveBatch(d_t, d_f, d_e, np.arange(rows + 1, dtype=np.int64) * N, meta, self.device, self.stream,
+                                    is_sorted=True if self.is_sorted else None)
+        lcs._keep = keep + [d_mask] + [d for d in d_shift if d is not None]       # what the enqueued fit still reads
+        info = {"background": d_bkg, "chi2": d_chi, "n_used": d_n, "cadence_status": d_cs, "status": d_st}
+        if not to_host:
+            info["star_off"], k = _upload(h, star_off, self.stream, np.int32)
+            lcs._keep.append(k)
+            return lcs, info
+        for key, dt, shp in (("background", np.float64, (B, N)), ("chi2", np.float64, (B, N)), ("n_used", np.int32, (B, N)),
+                             ("cadence_status", np.int8, (B, N)), ("status", np.int32, (B,))):
+            info[key] = info[key].download(dt, int(np.prod(shp)), stream=self.stream).reshape(shp)
+        info["star_off"] = star_off
+        return lcs, info
+
     # ---------------------------------------------------------------- PLD
     def pld_correct(self, aperture_mask="all", pld_aperture_mask="all", background_aperture_mask="all", pld_order=3,
                     pca_components=16, spline_n_knots=None, spline_degree=5, normalize_background_pixels=True,

@@ -132,6 +132,13 @@ R `cubes.amplitude_images(frequency, nterms=1)` and R3 the same with `nterms=3`,
 out-of-transit cadences of two cubes; the floor of R is two reads of every row of the flux cube); H the host route: `to_host()`, then `PixelCube.amplitude_image` per cutout on 16 threads.  Every
 timed region ends with a synchronise.  Written to profiles/ampimage_walls.txt.
 
+`psfphot`: deblended PSF photometry of the same batch shape with `LK_WALLS_STARS` (default 4) stars per cutout, in ONE process, the
+routes alternating, `LK_WALLS_REPS` (default 5) times after one warm-up.  R `cubes.psf_photometry(star_col, star_row, sigma)`, Rs
+the same with resident shifts, everything left in HBM; H / Hs the host route: `PixelCube.psf_photometry` per cutout on 16
+threads over the first `LK_WALLS_MIRROR_B` (default 16) cutouts, scaled to the batch in the ratios.  Every timed region ends with
+a synchronise.  Written to profiles/psfphot_walls.txt.  `psfphot_trace`: R and Rs twice and nothing else, for `rocprofv3
+--kernel-trace --stats` (profiles/psfphot_kernel_stats.txt).
+
 `background`: the per-cadence background of the same batch shape with 'background' masks, in ONE process, the routes alternating,
 `LK_WALLS_REPS` (default 5) times after one warm-up.  F `cubes.subtract_background()` (median images, masks, the fused estimate +
 subtraction) and Fm the same with the masks given; E `cubes.estimate_background()`, Em with the masks given, Es with the scatter
@@ -1398,6 +1405,91 @@ def pixelpg(which):
         % (med["L"] / med["R"], med["L"] / med["P"], B, med["H"] * B / Bm / med["R"])])
 
 
+def psfphot(which):
+    from concurrent.futures import ThreadPoolExecutor
+    from lightkurve_amd.device import DevicePixelCubeBatch
+    B, N, side, S = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "500"), ("LK_WALLS_N", "4000"), ("LK_WALLS_SIDE", "11"),
+                                                            ("LK_WALLS_STARS", "4")))
+    reps, Bm = int(os.environ.get("LK_WALLS_REPS", "5")), min(B, int(os.environ.get("LK_WALLS_MIRROR_B", "16")))
+    rng = np.random.default_rng(61)
+    npix = side * side
+    t = 1000.0 + np.arange(N) / 720.0                                    # two-minute cadences
+    sigma = 1.1
+    cells = int(np.ceil(np.sqrt(S)))
+    lattice = np.array([((i + 0.5) * side / cells - 0.5, (j + 0.5) * side / cells - 0.5) for j in range(cells) for i in range(cells)][:S])
+    col = lattice[None, :, 0] + rng.uniform(-0.3, 0.3, (B, S))
+    row = lattice[None, :, 1] + rng.uniform(-0.3, 0.3, (B, S))
+    shifts = (0.2 * np.sin(2 * np.pi * (t - t[0]) / 3.1)[None, :] * rng.uniform(0.5, 1.0, (B, 1)),
+              0.2 * np.cos(2 * np.pi * (t - t[0]) / 3.1)[None, :] * rng.uniform(0.5, 1.0, (B, 1)))
+    edges = np.arange(side + 1) - 0.5
+    from scipy.special import erf
+    flux = np.empty((B, N, side, side), dtype=np.float32)
+    for b in range(B):                                                  # (drawn per cutout: 1.9 GB of flux in all; the stars do not move)
+        img = np.full((side, side), 100.0)
+        for s in range(S):
+            gx = np.diff(erf((edges - col[b, s]) / (np.sqrt(2) * sigma))) / 2
+            gy = np.diff(erf((edges - row[b, s]) / (np.sqrt(2) * sigma))) / 2
+            img += rng.uniform(2000.0, 20000.0) * gy[:, None] * gx[None, :]
+        flux[b] = img.astype(np.float32) + 3.0 * rng.standard_normal((N, side, side), dtype=np.float32)
+    err = np.full_like(flux, 3.0)
+    cubes = DevicePixelCubeBatch.from_arrays(np.tile(t, (B, 1)), flux, err)
+    cubes.synchronize()
+    del flux, err
+    d_shifts = tuple(_upload_f64(cubes, a) for a in shifts)
+
+    def resident(sh=None):
+        out = cubes.psf_photometry(col, row, sigma, shifts=sh)
+        cubes.synchronize()
+        return out
+
+    if "psfphot_trace" in which:
+        for _ in range(2):
+            resident()
+            resident(d_shifts)
+        return
+
+    host_m = cubes.to_host()[:Bm]
+
+    def mirror(with_shifts=False):
+        def one(b):
+            return host_m[b].psf_photometry(col[b], row[b], sigma, shifts=(shifts[0][b], shifts[1][b]) if with_shifts else None)
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            return list(ex.map(one, range(Bm)))
+
+    fns = {"R": resident, "Rs": lambda: resident(d_shifts), "H": mirror, "Hs": lambda: mirror(True)}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    rel = {}
+    for k, hk in (("R", "H"), ("Rs", "Hs")):
+        f = first[k][0].flux_host().reshape(B * S, N)[:Bm * S].reshape(Bm, S, N)
+        h = np.stack([o["flux"] for o in first[hk]])
+        rel[k + " - " + hk] = float(np.max(np.abs(f - h) / np.max(np.abs(h), axis=(1, 2), keepdims=True)))
+    first.clear()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    floor = B * N * npix * 8 + B * N * (3 * S * 8 + 8 + 8 + 4 + 1)
+    write_walls("psfphot_walls.txt", [
+        "PSF photometry, %d cutouts x %d cadences x %d x %d float32, %d stars per cutout, sigma %.1f px (%.1f MB of flux and flux_err "
+        "resident, read once; %.1f MB of outputs)" % (B, N, side, side, S, sigma, B * N * npix * 8 / 1e6, (floor - B * N * npix * 8) / 1e6),
+        "  R    cubes.psf_photometry(star_col, star_row, sigma): tables per cutout, fit, statuses; everything resident     %s" % spread(ts["R"]),
+        "  Rs   the same with shifts=(DeviceBuffer, DeviceBuffer): tables per cadence                                      %s" % spread(ts["Rs"]),
+        "  H    PixelCube.psf_photometry on 16 threads, the first %d cutouts only                                          %s" % (Bm, spread(ts["H"])),
+        "  Hs   the same with shifts                                                                                        %s" % spread(ts["Hs"]),
+        "  max |flux difference| / max |flux| of the cutout over the first %d cutouts: %s" % (Bm, ", ".join("%s %.2e" % kv for kv in rel.items())),
+        "  H scaled to %d cutouts / R = %.0f; Hs scaled / Rs = %.0f; floor bytes of the fit kernel %.1f MB; kernel times alone: "
+        "profiles/psfphot_kernel_stats.txt" % (B, med["H"] * B / Bm / med["R"], med["Hs"] * B / Bm / med["Rs"], floor / 1e6)])
+
+
+def _upload_f64(cubes, a):
+    from lightkurve_amd.devmem import _upload
+    buf, keep = _upload(cubes.handle, np.ascontiguousarray(a, dtype=np.float64), cubes.stream, np.float64)
+    cubes.synchronize()
+    del keep
+    return buf
+
+
 def background():
     from concurrent.futures import ThreadPoolExecutor
     from lightkurve_amd.device import DevicePixelCubeBatch
@@ -1632,6 +1724,8 @@ def main():
         ampimage()
     if "background" in which:
         background()
+    if {"psfphot", "psfphot_trace"} & set(which):
+        psfphot(which)
     if {"pixelpg", "pixelpg_trace"} & set(which):
         pixelpg(which)
     if {"stitch", "stitch_trace"} & set(which):
