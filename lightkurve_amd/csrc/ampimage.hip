@@ -383,23 +383,6 @@ __global__ __launch_bounds__(AI_T) void cube_ampimage_images_kernel(const double
     }
 }
 
-// offset[b] = centroid_amp - centroid_level as (col, row), offset_pix[b] its norm; status[b] = fit_status[b] where that is not
-// 0, else 3 for a centroid that is not defined (NaN), else 0
-__global__ __launch_bounds__(256) void ampimage_offsets_kernel(int B, const int *__restrict__ fit_status,
-                                                               const double *__restrict__ amp_col, const double *__restrict__ amp_row,
-                                                               const double *__restrict__ level_col,
-                                                               const double *__restrict__ level_row, double *__restrict__ offset,
-                                                               double *__restrict__ offset_pix, int *__restrict__ status) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    const double dx = amp_col[b] - level_col[b], dy = amp_row[b] - level_row[b];
-    const double r = sqrt(dx * dx + dy * dy);
-    offset[2 * (size_t)b] = dx;
-    offset[2 * (size_t)b + 1] = dy;
-    offset_pix[b] = r;
-    status[b] = fit_status[b] != 0 ? fit_status[b] : r != r ? 3 : 0;
-}
-
 namespace {
 
 struct AiBuffers {
@@ -484,18 +467,6 @@ int cube_ampimage_launch(lk_handle *h, int B, int N, int npix, const double *tim
                      (int *)fit_status, stream);
         break;
     }
-    LK_HIP_CHECK(hipGetLastError());
-    return LK_OK;
-}
-
-int ampimage_offsets_launch(lk_handle *h, int B, const int32_t *fit_status, const double *amp_col, const double *amp_row,
-                            const double *level_col, const double *level_row, double *offset, double *offset_pix, int32_t *status,
-                            hipStream_t stream) {
-    (void)h;
-    LK_REQUIRE(B >= 1, "need B >= 1 cutouts");
-    LK_REQUIRE(fit_status && amp_col && amp_row && level_col && level_row && offset && offset_pix && status, "NULL buffer");
-    hipLaunchKernelGGL(ampimage_offsets_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, (const int *)fit_status, amp_col,
-                       amp_row, level_col, level_row, offset, offset_pix, (int *)status);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }

@@ -2270,8 +2270,8 @@ int lk_diffimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *n_in, con
                                    double *offset_pix, int32_t *status, void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    return lk::diffimage_offsets_launch(h, B, n_in, n_out, diff_col, diff_row, out_col, out_row, offset, offset_pix, status,
-                                        static_cast<hipStream_t>(stream));
+    return lk::centroid_offsets_launch(h, B, nullptr, n_in, n_out, diff_col, diff_row, out_col, out_row, offset, offset_pix, status,
+                                       static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ background
@@ -2306,8 +2306,8 @@ int lk_ampimage_offsets_batch_dev(lk_handle *h, int B, const int32_t *fit_status
                                   int32_t *status, void *stream) {
     LK_REQUIRE(h != nullptr, "handle is NULL");
     LK_HIP_CHECK(hipSetDevice(h->device));
-    return lk::ampimage_offsets_launch(h, B, fit_status, amp_col, amp_row, level_col, level_row, offset, offset_pix, status,
-                                       static_cast<hipStream_t>(stream));
+    return lk::centroid_offsets_launch(h, B, fit_status, nullptr, nullptr, amp_col, amp_row, level_col, level_row, offset, offset_pix,
+                                       status, static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ pixel periodograms

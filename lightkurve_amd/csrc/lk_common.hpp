@@ -406,14 +406,15 @@ int image_centroids_launch(lk_handle *h, int B, int npix, int nx, const double *
                            double column0, double row0, int method, double *col_out, double *row_out, int32_t *peak_out,
                            hipStream_t stream);
 // pixcube.hip: the transit difference images of B resident cutouts, one box per cutout (host arrays); then the centroid offsets
-// and statuses.  Everything else on the device; enqueued, no synchronisation
+// and statuses of these (n_in / n_out, fit_status NULL) or of the amplitude images (fit_status, n_in / n_out NULL).  Everything
+// else on the device; enqueued, no synchronisation
 int cube_diffimage_launch(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const float *flux_err,
                           const double *period_host, const double *transit_time_host, const double *duration_host, double in_width,
                           double out_inner, double out_outer, uint8_t *cls, double *mean_in, double *mean_out, double *diff,
                           double *diff_err, int32_t *n_in, int32_t *n_out, hipStream_t stream);
-int diffimage_offsets_launch(lk_handle *h, int B, const int32_t *n_in, const int32_t *n_out, const double *diff_col,
-                             const double *diff_row, const double *out_col, const double *out_row, double *offset,
-                             double *offset_pix, int32_t *status, hipStream_t stream);
+int centroid_offsets_launch(lk_handle *h, int B, const int32_t *fit_status, const int32_t *n_in, const int32_t *n_out,
+                            const double *a_col, const double *a_row, const double *b_col, const double *b_row, double *offset,
+                            double *offset_pix, int32_t *status, hipStream_t stream);
 // pixcube.hip: TargetPixelFile.estimate_background per cadence (nanmedian of the masked pixels, their count, optionally the
 // median absolute deviation) and, with cube_out, the subtracted cube from the same pass; cube - rows[b][i] for given rows.
 // Enqueued, no synchronisation, no scratch
@@ -422,14 +423,11 @@ int cube_background_launch(lk_handle *h, int B, int N, int npix, const float *cu
 int cube_subtract_rows_launch(lk_handle *h, int B, int N, int npix, const float *cube, const float *rows, float *cube_out,
                               hipStream_t stream);
 // ampimage.hip: the per-pixel sinusoid fit of B resident cutouts at one frequency each (host arrays), coefficient- and harmonic-
-// major images; then the centroid offsets and statuses.  Everything else on the device; enqueued, no synchronisation
+// major images (offsets and statuses: centroid_offsets_launch).  Everything else on the device; enqueued, no synchronisation
 int cube_ampimage_launch(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const double *frequency_host,
                          int nterms, const double *t_ref_host, double *theta, double *level, double *amplitude, double *phase,
                          double *amplitude_err, double *snr, double *chi2, int32_t *n_used, int32_t *fit_status,
                          hipStream_t stream);
-int ampimage_offsets_launch(lk_handle *h, int B, const int32_t *fit_status, const double *amp_col, const double *amp_row,
-                            const double *level_col, const double *level_row, double *offset, double *offset_pix, int32_t *status,
-                            hipStream_t stream);
 // pixelpg.hip: the per-pixel Lomb-Scargle periodograms of B resident cutouts on one shared grid (host array, 1/d), their peak
 // images and, where power is not NULL, the power cube [B][F][npix].  Everything else on the device; enqueued, no synchronisation
 int cube_pixelpg_launch(lk_handle *h, int B, int N, int npix, const double *time, const float *flux, const double *frequency_host,

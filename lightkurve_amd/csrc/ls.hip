@@ -50,15 +50,6 @@ struct TargetStats {
     double yws;   // sum w (y-ybar)
 };
 
-// sin/cos of 2*pi*(f*t) with the product reduced exactly: p = f*t rounded, e its exact error (fma),
-// r = (p - rint(p)) + e in [-0.5, 0.5]: phase error ~1e-17 cycles even for f*t ~ 1e4.
-__device__ __forceinline__ void sincos2pi_prod(double f, double t, double *s, double *c) {
-    double p = f * t;
-    double e = fma(f, t, -p);
-    double r = (p - rint(p)) + e;
-    sincospi(2.0 * r, s, c);
-}
-
 // ------------------------------------------------------------------------------------------------ prep
 // One 256-thread workgroup per target: weights, weighted mean (about y[0] so that a constant curve centres
 // to exactly 0 — tests/test_periodogram.py:445-457), YY, and the per-cadence records.

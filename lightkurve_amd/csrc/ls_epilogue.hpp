@@ -8,6 +8,15 @@
 
 namespace lk {
 
+// sin/cos of 2*pi*(f*t) with the product reduced exactly: p = f*t rounded, e its exact error (fma),
+// r = (p - rint(p)) + e in [-0.5, 0.5]: phase error ~1e-17 cycles even for f*t ~ 1e4.
+__device__ __forceinline__ void sincos2pi_prod(double f, double t, double *s, double *c) {
+    double p = f * t;
+    double e = fma(f, t, -p);
+    double r = (p - rint(p)) + e;
+    sincospi(2.0 * r, s, c);
+}
+
 __device__ __forceinline__ double gls_power_sums(double Sh, double Ch, double S, double C, double S2, double C2,
                                                  int fit_mean, int norm, double YY, double psd_factor, double nN,
                                                  double scale) {

@@ -1,5 +1,5 @@
 // pixcube.hip — what PLDCorrector does to a target-pixel cutout BEFORE the design matrix, for B same-shaped float32 cubes
-// [B][N][npix] resident in HBM (lightkurve_amd/device.py: DevicePixelCubeBatch):
+// [B][N][npix] resident in HBM (lightkurve_amd/cubes.py: DevicePixelCubeBatch):
 //   cube_aperture   simple aperture photometry (TargetPixelFile.to_lightcurve, flux_method='sum',
 //                   src/lightkurve/targetpixelfile.py:868-923) + the NaN-cadence flags of PLDCorrector.__init__
 //                   (correctors/pldcorrector.py:109-120);
@@ -362,22 +362,26 @@ __global__ __launch_bounds__(256) void cube_diffimage_finish_kernel(const double
     diff_err[o] = sqrt(e_in / (ni * ni) + e_out / (no * no));
 }
 
-// offset[b] = centroid_diff - centroid_out as (col, row), offset_pix[b] its norm, and the status of cutout b: 1 no in-transit
-// cadence, 2 no out-of-transit cadence, 3 a centroid that is not defined (NaN), else 0
-__global__ __launch_bounds__(256) void diffimage_offsets_kernel(int B, const int *__restrict__ n_in, const int *__restrict__ n_out,
-                                                                const double *__restrict__ diff_col,
-                                                                const double *__restrict__ diff_row,
-                                                                const double *__restrict__ out_col,
-                                                                const double *__restrict__ out_row, double *__restrict__ offset,
-                                                                double *__restrict__ offset_pix, int *__restrict__ status) {
+// offset[b] = centroid_a - centroid_b as (col, row), offset_pix[b] its norm, and the status of cutout b.  The leading status is
+// fit_status[b] where fit_status is given (amplitude images), else 1 for no in-transit cadence, 2 for no out-of-transit cadence
+// (difference images); where that is 0: 3 for a centroid that is not defined (NaN), else 0.  The norm is numpy's
+// sqrt(dx * dx + dy * dy), every product and the sum rounded on its own: this file is built with -ffp-contract=off, and in a
+// file built with contraction the sum fuses and offset_pix moves in the last place
+__global__ __launch_bounds__(256) void centroid_offsets_kernel(int B, const int *__restrict__ fit_status,
+                                                               const int *__restrict__ n_in, const int *__restrict__ n_out,
+                                                               const double *__restrict__ a_col, const double *__restrict__ a_row,
+                                                               const double *__restrict__ b_col, const double *__restrict__ b_row,
+                                                               double *__restrict__ offset, double *__restrict__ offset_pix,
+                                                               int *__restrict__ status) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
-    const double dx = diff_col[b] - out_col[b], dy = diff_row[b] - out_row[b];
+    const double dx = a_col[b] - b_col[b], dy = a_row[b] - b_row[b];
     const double r = sqrt(dx * dx + dy * dy);
     offset[2 * (size_t)b] = dx;
     offset[2 * (size_t)b + 1] = dy;
     offset_pix[b] = r;
-    status[b] = n_in[b] == 0 ? 1 : n_out[b] == 0 ? 2 : r != r ? 3 : 0;
+    const int lead = fit_status ? fit_status[b] : n_in[b] == 0 ? 1 : n_out[b] == 0 ? 2 : 0;
+    status[b] = lead != 0 ? lead : r != r ? 3 : 0;
 }
 
 // np.nanmedian(cube.astype(float64), axis=0) of the cadences with keep != 0 (all of them when keep is NULL): exact order
@@ -991,14 +995,14 @@ int cube_diffimage_launch(lk_handle *h, int B, int N, int npix, const double *ti
     return LK_OK;
 }
 
-int diffimage_offsets_launch(lk_handle *h, int B, const int32_t *n_in, const int32_t *n_out, const double *diff_col,
-                             const double *diff_row, const double *out_col, const double *out_row, double *offset,
-                             double *offset_pix, int32_t *status, hipStream_t stream) {
+int centroid_offsets_launch(lk_handle *h, int B, const int32_t *fit_status, const int32_t *n_in, const int32_t *n_out,
+                            const double *a_col, const double *a_row, const double *b_col, const double *b_row, double *offset,
+                            double *offset_pix, int32_t *status, hipStream_t stream) {
     (void)h;
     LK_REQUIRE(B >= 1, "need B >= 1 cutouts");
-    LK_REQUIRE(n_in && n_out && diff_col && diff_row && out_col && out_row && offset && offset_pix && status, "NULL buffer");
-    hipLaunchKernelGGL(diffimage_offsets_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, (const int *)n_in,
-                       (const int *)n_out, diff_col, diff_row, out_col, out_row, offset, offset_pix, (int *)status);
+    LK_REQUIRE((fit_status || (n_in && n_out)) && a_col && a_row && b_col && b_row && offset && offset_pix && status, "NULL buffer");
+    hipLaunchKernelGGL(centroid_offsets_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, (const int *)fit_status,
+                       (const int *)n_in, (const int *)n_out, a_col, a_row, b_col, b_row, offset, offset_pix, (int *)status);
     LK_HIP_CHECK(hipGetLastError());
     return LK_OK;
 }

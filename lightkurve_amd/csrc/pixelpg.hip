@@ -13,7 +13,7 @@
 //            n_valid[b] and status[b]; whether any pixel of a group of PP_T pixels lacks cadences that the cutout has.
 //   spectra  workgroup (cutout, tile of PP_FT frequencies, group of PP_T adjacent pixels), lanes = pixels.  It walks all N
 //            cadences in chunks of PP_CH.  For a chunk every lane generates the sine and cosine of a different (cadence,
-//            frequency) — (t - t_ref) and the exactly reduced product of ls.hip's sincos2pi_prod, no recurrence — into LDS and
+//            frequency) — (t - t_ref) and the exactly reduced product of sincos2pi_prod (ls_epilogue.hpp), no recurrence — into LDS and
 //            keeps, for the cadences IT generated, the shared sums of its frequency; then every lane walks its pixel down the
 //            chunk (coalesced float32 row loads, PP_ROWS in flight) and folds y' into its 2 PP_FT register accumulators, the
 //            trig values read as LDS broadcasts.  At the end the shared sums are added across the generating lanes in lane
@@ -47,14 +47,6 @@ constexpr int PP_CH = 32;    // cadences per staged chunk: PP_CH x PP_FT (sin, c
 constexpr int PP_ROWS = 8;   // cadence rows whose loads a lane issues before it uses them
 constexpr int PP_GJ = PP_W / PP_FT;  // lanes that generate one frequency's values of a chunk (cadences r = gj, gj + PP_GJ, ...)
 static_assert(PP_CH % PP_GJ == 0 && PP_CH % PP_ROWS == 0 && PP_W >= 4 * PP_FT, "tile constants");
-
-// ls.hip's sincos2pi_prod: sin/cos of 2 pi (f t) with the product reduced exactly (p = f t rounded, e its exact error)
-__device__ __forceinline__ void pp_sincos2pi_prod(double f, double t, double *s, double *c) {
-    const double p = f * t;
-    const double e = fma(f, t, -p);
-    const double r = (p - rint(p)) + e;
-    sincospi(2.0 * r, s, c);
-}
 
 }  // namespace
 
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(PP_W) void cube_pixelpg_spectra_kernel(
             if (r < rows) {
                 const double t = tm[c0 + r];
                 ok = isfinite(t);
-                if (ok) pp_sincos2pi_prod(fg, t - tr, &s, &c);
+                if (ok) sincos2pi_prod(fg, t - tr, &s, &c);
             }
             sh_tr[r][gk] = make_double2(s, c);
             if (gk == 0) sh_valid[r] = ok ? 1 : 0;

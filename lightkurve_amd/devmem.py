@@ -1,5 +1,5 @@
 """Device memory of the resident classes: the per-handle free list, ``DeviceBuffer`` and the upload / pointer helpers that
-device.py and cotrend.py share (no torch: memory and copies come from liblkhip.so itself)."""
+device.py, cubes.py and cotrend.py share (no torch: memory and copies come from liblkhip.so itself)."""
 import ctypes
 import threading
 import weakref
@@ -10,6 +10,8 @@ from . import _capi
 
 _vp = ctypes.c_void_p
 _ip = ctypes.POINTER(ctypes.c_int64)
+_dp = ctypes.POINTER(ctypes.c_double)
+_i32p = ctypes.POINTER(ctypes.c_int32)
 
 
 # ------------------------------------------------------------------------------------------------ device memory

@@ -4,9 +4,9 @@
     python tools/compare_device_code.py OLD.so NEW.so
 
 Dumps the .hip_fatbin section of both libraries, unbundles every gfx950 code object (one per .hip file), disassembles each
-with llvm-objdump and compares function by function: instruction text only (addresses, encodings and branch-target comments
-dropped, so a function that merely moved is not reported).  Prints the kernels / device functions that differ, or "identical".
-Needs no GPU.  LLVM_BIN (default /opt/rocm/llvm/bin) names the directory of llvm-objcopy and llvm-objdump."""
+with llvm-objdump and compares function by function: instruction text only (addresses, encodings, branch-target comments and
+the padding behind a function dropped, so a function that merely moved, or became its file's last, is not reported).  Prints
+the kernels / device functions that differ, or "identical".  Needs no GPU.  LLVM_BIN (default /opt/rocm/llvm/bin) names the directory of llvm-objcopy and llvm-objdump."""
 import os
 import re
 import struct
@@ -51,6 +51,9 @@ def functions(elf_bytes, tmp):
             cur = funcs.setdefault(m.group(1), [])
         elif cur is not None and line.strip():
             cur.append(re.sub(r"\s*//.*", "", line).strip())
+    for body in funcs.values():     # the padding behind a function's last instruction (s_nop up to the alignment, and the
+        while body and body[-1] in ("s_nop 0", "..."):  # prefetch guard behind the code object's last function) is not its code
+            body.pop()
     return funcs
 
 
