@@ -1297,6 +1297,51 @@ int lk_cube_psf_photometry_batch_dev(lk_handle *h, int B, int N, int ny, int nx,
                                      double *time_out, double *flux_out, double *flux_err_out, double *background, double *chi2,
                                      int32_t *n_used, int8_t *cadence_status, int32_t *status, void *stream);
 
+/* lk_cube_psf_fit_batch_dev <- PSF photometry that fits each cadence's pointing shift (PixelCube.psf_fit is the numpy mirror and the
+ *   definition): per cadence the fluxes of up to 8 stars, one constant background and ONE common (column, row) shift u = (dc, dr)
+ *   of all stars, by variable projection in Kaufman's form.  The per-cadence motion shift of TargetPixelFile.to_lightcurve(method=
+ *   "prf"); per-star positions, the PSF width, tabulated PRFs, rotation and a background gradient are not fitted.
+ *   Inputs, stars, sigma, mask, PSF, used pixels, weights, design A(u) = [g_0 ... g_{S-1}, 1], K = S + 1, and the output rows are
+ *   those of lk_cube_psf_photometry_batch_dev.  shift0_col / shift0_row (nullable, both or neither): DEVICE arrays [B][N], the
+ *   initial shift u0 of every cadence (0 without them).  The used pixels do not depend on u.
+ *   Per cadence, from u = u0, for it = 1 .. max_iter:
+ *     1. G = A^T W A, rhs = A^T W y at u; G = L L^T by the unpivoted Cholesky of lk_cube_psf_photometry_batch_dev with its pivot
+ *        cut 1e-12 G_kk (a failed pivot: status 3); theta = G^-1 rhs.
+ *     2. r = y - A theta; D = [sum_s theta_s dg_s/ddc, sum_s theta_s dg_s/ddr] over the used pixels, where the derivative of a
+ *        column factor (E(ix + 1) - E(ix)) / 2 by the centre is -(P(ix + 1) - P(ix)), P(k) = exp(-z_k^2) / (sqrt(2 pi) sigma_col),
+ *        z_k = (k - 1/2 - c) / (sqrt(2) sigma_col), rows likewise.  C = A^T W D (K x 2), E = D^T W D (2 x 2), g = D^T W r,
+ *        S2 = E - (L^-1 C)^T (L^-1 C), factored by the same Cholesky with the pivot cut 1e-12 E_kk (a failed pivot: status 3);
+ *        du = S2^-1 g.
+ *     3. each component of du is clamped to +-max_step; u += du; n_iter = it; last_step = max |du| after the clamp.  If
+ *        max |u - u0| > max_shift: status 5, stop.  If tol > 0 and last_step < tol: converged, stop.
+ *   After max_iter iterations a cadence that has not converged has status 4 when tol > 0; tol == 0 means "take exactly max_iter
+ *   steps" and is status 0.  A status 0 cadence is evaluated once more at the final u: flux, flux_err = sqrt((G^-1)_ss),
+ *   background and chi2 are those of lk_cube_psf_photometry_batch_dev at shifts = u (errors conditional on the shift), and
+ *   shift_col_err / shift_row_err = sqrt((S2^-1)_kk) of that evaluation (a failed pivot there: status 3).
+ *   cadence_status [B][N] int8: 0 ok, 1 the time or u0 is not finite, 2 n_used < S + 4, 3 singular, 4 not converged, 5 left
+ *   max_shift.  A cadence that is not ok is NaN in flux, flux_err, background, chi2, shift_col, shift_row and their errors;
+ *   n_iter [B][N] int32 (the shift updates made) and last_step [B][N] float64 are written for every cadence (0 / NaN for
+ *   statuses 1 and 2, and NaN before the first update); n_used [B][N] int32; status [B] int32: 0, or 1 when no cadence of the
+ *   cutout is ok.  shift_col, shift_row, shift_col_err, shift_row_err: [B][N] float64, the layout the shifts of
+ *   lk_cube_psf_photometry_batch_dev take.  Nothing is raised per cadence.
+ *   LK_EINVAL: as lk_cube_psf_photometry_batch_dev, and max_iter outside 1 .. 64, tol not finite or < 0, max_step or max_shift
+ *   not > 0, or a cutout too large for the LDS tile: 16 x 8 pitch + npix + 2 x 16 x 8 S_max (nx + ny) bytes (factor and
+ *   derivative tables) must not exceed 160 KiB (4 pitch instead of 8 with use_flux_err == 0); nothing is launched then.
+ *   One wavefront per tile of 16 cadences, four lanes per cadence, instantiated on S: flux, flux_err and the mask are staged in
+ *   LDS once and every iteration reads LDS alone; per evaluation the lanes of a cadence rebuild its factor and derivative
+ *   tables (every edge's erf and exp serve both pixels it separates), walk the tile for G and rhs, solve, and walk it again
+ *   for C, E, g and chi2; the loop runs until every cadence of the tile has stopped.  No atomics; a cutout's outputs have the
+ *   same bits alone, at any batch position and from run to run.  Scratch: B x (2 S_max + 2) x 8 + 12 B bytes of the handle's
+ *   arena.  Enqueued, no synchronisation. */
+int lk_cube_psf_fit_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
+                              const float *flux_err, const uint8_t *mask, int mask_stride, int S_max, const double *star_col,
+                              const double *star_row, const double *sigma, const double *shift0_col, const double *shift0_row,
+                              int max_iter, double tol, double max_step, double max_shift, double column0, double row0,
+                              int use_flux_err, int32_t *star_off, double *time_out, double *flux_out, double *flux_err_out,
+                              double *background, double *chi2, double *shift_col, double *shift_row, double *shift_col_err,
+                              double *shift_row_err, double *last_step, int32_t *n_iter, int32_t *n_used, int8_t *cadence_status,
+                              int32_t *status, void *stream);
+
 /* lk_cube_background_batch_dev <- TargetPixelFile.estimate_background(aperture_mask) per cadence of the same resident cubes,
  *   and the subtraction of that background, in one pass (PixelCube.estimate_background / subtract_background are the numpy
  *   mirror).  mask / mask_stride as lk_cube_aperture_batch_dev; sel = the masked pixels of cadence i of cutout b.

@@ -10,7 +10,7 @@ from . import packed
 
 __all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch", "river_batch", "fill_gaps_batch",
            "periodogram_peaks", "flatten_batch",
-           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "psf_photometry_batch", "pixel_periodograms_batch", "subtract_background_batch", "regression_correct_batch", "cbv_correct_batch"]
+           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "psf_photometry_batch", "psf_fit_batch", "pixel_periodograms_batch", "subtract_background_batch", "regression_correct_batch", "cbv_correct_batch"]
 
 
 def _resolve_device(device):
@@ -412,6 +412,16 @@ def psf_photometry_batch(cubes, star_col, star_row, sigma, device=0, **kwargs):
     from .device import DevicePixelCubeBatch
     kwargs.setdefault("to_host", True)
     return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).psf_photometry(star_col, star_row, sigma, **kwargs)
+
+
+def psf_fit_batch(cubes, star_col, star_row, sigma, device=0, **kwargs):
+    """``PixelCube.psf_fit`` of every cutout, for host cutouts: PSF photometry with one common pointing shift per cadence fitted
+    next to the fluxes.  ``cubes``, ``star_col`` / ``star_row`` and ``sigma`` as in ``psf_photometry_batch``.  One upload
+    (``DevicePixelCubeBatch.from_cubes``), then ``DevicePixelCubeBatch.psf_fit`` with its keywords; returns its ``(lcs,
+    info)``, ``info`` as host arrays unless ``to_host=False`` is passed.  Not sharded over ranks."""
+    from .device import DevicePixelCubeBatch
+    kwargs.setdefault("to_host", True)
+    return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).psf_fit(star_col, star_row, sigma, **kwargs)
 
 
 def pixel_periodograms_batch(cubes, frequency, device=0, **kwargs):

@@ -137,6 +137,19 @@ def _psf_sigma(sigma):
     return float(sg[0]), float(sg[1])
 
 
+def _psf_fit_parameters(max_iter, tol, max_step, max_shift):
+    """The iteration's parameters of ``psf_fit``, checked: max_iter an integer 1 .. 64, tol finite and >= 0, max_step and
+    max_shift > 0."""
+    if int(max_iter) != max_iter or not 1 <= int(max_iter) <= 64:
+        raise ValueError("max_iter must be an integer 1 .. 64 (got %r)" % (max_iter,))
+    tol, max_step, max_shift = float(tol), float(max_step), float(max_shift)
+    if not (np.isfinite(tol) and tol >= 0):
+        raise ValueError("tol must be finite and >= 0 (got %r)" % (tol,))
+    if not (max_step > 0 and max_shift > 0):
+        raise ValueError("max_step and max_shift must be > 0 (got %r and %r)" % (max_step, max_shift))
+    return int(max_iter), tol, max_step, max_shift
+
+
 class PixelCube(object):
     """Minimal stand-in for the slice of TargetPixelFile that PLDCorrector touches."""
 
@@ -501,6 +514,201 @@ class PixelCube(object):
         return {"flux": np.where(bad[None, :], np.nan, theta[:, :S].T), "flux_err": np.where(bad[None, :], np.nan, err),
                 "background": np.where(bad, np.nan, theta[:, S]), "chi2": np.where(bad, np.nan, chi2), "n_used": n_used,
                 "cadence_status": cst, "status": 0 if np.any(cst == 0) else 1, "star_index": star_index, "min_pivot_ratio": ratio}
+
+    def psf_fit(self, star_col, star_row, sigma, shifts0=None, max_iter=10, tol=1e-7, max_step=0.5, max_shift=2.0,
+                aperture_mask="all", column=0, row=0, use_flux_err=True):
+        """PSF photometry that fits each cadence's pointing shift: per cadence the fluxes of up to 8 stars, one constant
+        background and ONE common (column, row) shift u = (dc, dr) of all stars, by variable projection in Kaufman's form (the
+        host mirror of ``DevicePixelCubeBatch.psf_fit`` and its definition, float64 numpy after the float32 load).  The
+        per-cadence motion shift of ``TargetPixelFile.to_lightcurve(method="prf")``; per-star positions, the PSF width,
+        tabulated PRFs, rotation and a background gradient are not fitted.  Stars, ``sigma``, ``aperture_mask``, ``column`` /
+        ``row``, the used pixels, the weights w, the star factors g_s at shift u and the design A(u) = [g_0 ... g_{S-1}, 1], K =
+        S + 1, are those of ``psf_photometry``; the used pixels do not depend on u.  ``shifts0``: None or (shift_col[N],
+        shift_row[N]), the initial shift u0 of every cadence (0 without).  Per cadence, from u = u0, for it = 1 .. ``max_iter``:
+
+        1. G = A^T W A, rhs = A^T W y at u; G = L L^T by the unpivoted Cholesky of ``psf_photometry`` with its pivot cut 1e-12
+           G_kk (a failed pivot: status 3); theta = G^-1 rhs.
+        2. r = y - A theta; D = [sum_s theta_s dg_s/ddc, sum_s theta_s dg_s/ddr] over the used pixels: the derivative of a
+           column factor (E(ix + 1) - E(ix)) / 2 by the centre is -(P(ix + 1) - P(ix)), P(k) = exp(-z_k^2) / (sqrt(2 pi)
+           sigma_col), z_k = (k - 1/2 - c) / (sqrt(2) sigma_col); rows likewise.  C = A^T W D (K x 2), E = D^T W D (2 x 2), g =
+           D^T W r, S2 = E - (L^-1 C)^T (L^-1 C), factored by the same Cholesky with the pivot cut 1e-12 E_kk (a failed pivot:
+           status 3); du = S2^-1 g.
+        3. each component of du is clamped to +-``max_step``; u += du; n_iter = it; last_step = max |du| after the clamp.  If
+           max |u - u0| > ``max_shift``: status 5, stop.  If ``tol`` > 0 and last_step < ``tol``: converged, stop.
+
+        After ``max_iter`` iterations a cadence that has not converged has status 4 when ``tol`` > 0; ``tol`` = 0 means "take
+        exactly ``max_iter`` steps" and is status 0.  A status 0 cadence is evaluated once more at the final u: ``flux``,
+        ``flux_err`` = sqrt((G^-1)_ss), ``background`` and ``chi2`` are ``psf_photometry``'s at shifts = u (errors conditional
+        on the shift) and ``shift_col_err`` / ``shift_row_err`` = sqrt((S2^-1)_kk) of that evaluation (a failed pivot there:
+        status 3).  ``cadence_status`` (N,) int8: 0 ok, 1 the time or u0 is not finite, 2 n_used < S + 4, 3 singular, 4 not
+        converged, 5 left ``max_shift``; a cadence that is not ok is NaN in every float output, the shifts included; nothing is
+        raised.  Returns the dict of ``psf_photometry`` plus ``shift_col``, ``shift_row``, ``shift_col_err``, ``shift_row_err``
+        (N,); ``n_iter`` (N,) int32, the shift updates made, and ``last_step`` (N,), for every cadence (0 / NaN for statuses 1
+        and 2); and what the tests' preconditions read: ``steps`` (N, max_iter), the last_step of every iteration, NaN
+        afterwards; ``raw_steps`` (N, max_iter, 2), du before the clamp; ``excursion`` (N, max_iter), max |u - u0| after every
+        update; ``min_pivot_ratio`` (N,), the smallest d_k / G_kk or d_k / E_kk of every factorisation made (0 for a pivot that
+        is not finite).  ``max_iter`` 1 .. 64, ``tol`` finite and >= 0, ``max_step`` and ``max_shift`` > 0 (``ValueError``)."""
+        import math
+        col, rw = np.atleast_1d(np.asarray(star_col, dtype=np.float64)), np.atleast_1d(np.asarray(star_row, dtype=np.float64))
+        if col.ndim != 1 or col.shape != rw.shape:
+            raise ValueError("star_col and star_row must be 1-D arrays of one length (got %r and %r)" % (col.shape, rw.shape))
+        star_index = np.flatnonzero(~(np.isnan(col) | np.isnan(rw)))
+        col, rw = col[star_index], rw[star_index]
+        S = len(star_index)
+        if not 1 <= S <= 8:
+            raise ValueError("psf_fit fits 1 .. 8 stars per cutout (got %d)" % S)
+        if not (np.all(np.isfinite(col)) and np.all(np.isfinite(rw))):
+            raise ValueError("a star position is infinite")
+        sig_c, sig_r = _psf_sigma(sigma)
+        max_iter, tol, max_step, max_shift = _psf_fit_parameters(max_iter, tol, max_step, max_shift)
+        N, ny, nx = self.shape
+        npix, K = ny * nx, S + 1
+        if shifts0 is None:
+            u0 = np.zeros((N, 2))
+        else:
+            u0 = np.stack([np.asarray(a, dtype=np.float64) for a in shifts0], axis=-1)
+            if len(shifts0) != 2 or u0.shape != (N, 2):
+                raise ValueError("shifts0 must be a pair of arrays of one value per cadence (%d)" % N)
+        ap = self._parse_aperture_mask(aperture_mask).reshape(npix)
+        erf = np.vectorize(math.erf, otypes=[np.float64])
+        y32 = np.asarray(self.flux).reshape(N, npix)
+        used = ap[None, :] & np.isfinite(y32)
+        with np.errstate(all="ignore"):
+            if use_flux_err:
+                e32 = np.asarray(self.flux_err).reshape(N, npix)
+                used &= np.isfinite(e32) & (e32 > 0)
+                e = np.where(used, e32, 1).astype(np.float64)
+                w_all = np.where(used, 1.0 / (e * e), 0.0)
+            else:
+                w_all = used.astype(np.float64)
+        y_all = np.where(used, y32, 0).astype(np.float64)
+        n_used = used.sum(axis=1).astype(np.int32)
+
+        def tables(c, sg, n):                                    # c: (S, M) -> factors and their derivatives by c, (S, M, n)
+            z = (np.arange(n + 1) - 0.5 - c[..., None]) / (np.sqrt(2.0) * sg)
+            E, P = erf(z), np.exp(-z * z) / (np.sqrt(2.0 * np.pi) * sg)
+            return 0.5 * (E[..., 1:] - E[..., :-1]), -(P[..., 1:] - P[..., :-1])
+
+        def cholesky(G, scale):                                  # (M, k, k), pivot cut on scale (M, k) -> L, singular, ratio
+            M, k = G.shape[:2]
+            L, singular, ratio = np.zeros((M, k, k)), np.zeros(M, dtype=bool), np.full(M, np.inf)
+            for q in range(k):
+                d = G[:, q, q].copy()
+                for j in range(q):
+                    d -= L[:, q, j] * L[:, q, j]
+                singular |= ~(np.isfinite(d) & (d > 1e-12 * scale[:, q]))
+                ratio = np.minimum(ratio, np.where(np.isfinite(d) & (scale[:, q] > 0), d / scale[:, q], 0.0))
+                L[:, q, q] = np.sqrt(d)
+                for i in range(q + 1, k):
+                    s_ = G[:, q, i].copy()
+                    for j in range(q):
+                        s_ -= L[:, i, j] * L[:, q, j]
+                    L[:, i, q] = s_ / L[:, q, q]
+            return L, singular, ratio
+
+        def forward(L, B):                                       # L^-1 B, B (M, k, m)
+            Y = np.zeros_like(B)
+            for i in range(L.shape[1]):
+                s_ = B[:, i].copy()
+                for j in range(i):
+                    s_ -= L[:, i, j, None] * Y[:, j]
+                Y[:, i] = s_ / L[:, i, i, None]
+            return Y
+
+        def backward(L, Y):                                      # L^-T Y
+            X = np.zeros_like(Y)
+            for i in range(L.shape[1] - 1, -1, -1):
+                s_ = Y[:, i].copy()
+                for j in range(i + 1, L.shape[1]):
+                    s_ -= L[:, j, i, None] * X[:, j]
+                X[:, i] = s_ / L[:, i, i, None]
+            return X
+
+        def evaluate(idx, u):
+            """The cadences idx at the shifts u (M, 2) -> theta (M, K), L, L2, g (M, 2), chi2, singular, pivot ratio."""
+            M = len(idx)
+            g_col, d_col = tables(col[:, None] + u[None, :, 0] - column, sig_c, nx)
+            g_row, d_row = tables(rw[:, None] + u[None, :, 1] - row, sig_r, ny)
+            w, y, keep = w_all[idx], y_all[idx], used[idx]
+            A, Ac, Ar = np.empty((M, npix, K)), np.empty((M, npix, S)), np.empty((M, npix, S))
+            for s in range(S):
+                A[:, :, s] = (g_col[s][:, None, :] * g_row[s][:, :, None]).reshape(M, npix)
+                Ac[:, :, s] = (d_col[s][:, None, :] * g_row[s][:, :, None]).reshape(M, npix)
+                Ar[:, :, s] = (g_col[s][:, None, :] * d_row[s][:, :, None]).reshape(M, npix)
+            A[:, :, S] = 1.0
+            A = np.where(keep[:, :, None], A, 0.0)
+            WA = A * w[:, :, None]
+            G = np.einsum("npi,npj->nij", WA, A)
+            rhs = np.einsum("npi,np->ni", WA, y)
+            L, singular, ratio = cholesky(G, np.einsum("nii->ni", G))
+            theta = backward(L, forward(L, rhs[:, :, None]))[:, :, 0]
+            res = y - np.einsum("npi,ni->np", A, theta)
+            D = np.stack([np.einsum("nps,ns->np", Ac, theta[:, :S]), np.einsum("nps,ns->np", Ar, theta[:, :S])], axis=2)
+            D = np.where(keep[:, :, None], D, 0.0)
+            WD = D * w[:, :, None]
+            Y = forward(L, np.einsum("npi,npj->nij", A, WD))
+            E = np.einsum("npi,npj->nij", WD, D)
+            L2, singular2, ratio2 = cholesky(E - np.einsum("nki,nkj->nij", Y, Y), np.einsum("nii->ni", E))
+            return dict(theta=theta, L=L, L2=L2, g=np.einsum("npi,np->ni", WD, res), chi2=np.sum(w * res * res, axis=1),
+                        singular=singular | singular2, ratio=np.minimum(ratio, ratio2))
+
+        fin = np.isfinite(self.time) & np.all(np.isfinite(u0), axis=1)
+        cst = np.where(~fin, 1, np.where(n_used < S + 4, 2, 0)).astype(np.int8)
+        u = u0.copy()
+        n_iter, last_step = np.zeros(N, dtype=np.int32), np.full(N, np.nan)
+        steps, raw_steps, excursion = np.full((N, max_iter), np.nan), np.full((N, max_iter, 2), np.nan), np.full((N, max_iter), np.nan)
+        ratio = np.full(N, np.inf)
+        running = cst == 0
+        final = np.zeros(N, dtype=bool)                          # stopped and ok: the evaluation at the final u is to come
+        with np.errstate(all="ignore"):
+            for it in range(1, max_iter + 1):
+                idx = np.flatnonzero(running)
+                if not len(idx):
+                    break
+                ev = evaluate(idx, u[idx])
+                ratio[idx] = np.minimum(ratio[idx], ev["ratio"])
+                du = backward(ev["L2"], forward(ev["L2"], ev["g"][:, :, None]))[:, :, 0]
+                go = ~ev["singular"]
+                cst[idx[~go]] = 3
+                running[idx[~go]] = False
+                idx, du = idx[go], du[go]
+                raw_steps[idx, it - 1] = du
+                du = np.where(du > max_step, max_step, np.where(du < -max_step, -max_step, du))
+                u[idx] += du
+                n_iter[idx] = it
+                a0, a1 = np.abs(du[:, 0]), np.abs(du[:, 1])
+                last_step[idx] = steps[idx, it - 1] = np.where(a0 > a1, a0, a1)
+                a0, a1 = np.abs(u[idx, 0] - u0[idx, 0]), np.abs(u[idx, 1] - u0[idx, 1])
+                exc = excursion[idx, it - 1] = np.where(a0 > a1, a0, a1)
+                left = exc > max_shift
+                conv = ~left & (tol > 0) & (last_step[idx] < tol)
+                cst[idx[left]] = 5
+                running[idx[left | conv]] = False
+                final[idx[conv]] = True
+            if tol > 0:
+                cst[running] = 4
+            else:
+                final |= running
+            flux, err = np.full((S, N), np.nan), np.full((S, N), np.nan)
+            out = {k: np.full(N, np.nan) for k in ("background", "chi2", "shift_col", "shift_row", "shift_col_err", "shift_row_err")}
+            idx = np.flatnonzero(final)
+            if len(idx):
+                ev = evaluate(idx, u[idx])
+                ratio[idx] = np.minimum(ratio[idx], ev["ratio"])
+                cst[idx[ev["singular"]]] = 3
+                eye = np.broadcast_to(np.eye(K)[None], (len(idx), K, K))
+                var = np.sum(forward(ev["L"], eye.copy()) ** 2, axis=1)          # (G^-1)_kk = the squares of column k of L^-1
+                var2 = np.sum(forward(ev["L2"], np.broadcast_to(np.eye(2)[None], (len(idx), 2, 2)).copy()) ** 2, axis=1)
+                ok = ~ev["singular"]
+                at = idx[ok]
+                flux[:, at], err[:, at] = ev["theta"][ok, :S].T, np.sqrt(var[ok, :S]).T
+                out["background"][at], out["chi2"][at] = ev["theta"][ok, S], ev["chi2"][ok]
+                out["shift_col"][at], out["shift_row"][at] = u[at, 0], u[at, 1]
+                out["shift_col_err"][at], out["shift_row_err"][at] = np.sqrt(var2[ok, 0]), np.sqrt(var2[ok, 1])
+        out.update(flux=flux, flux_err=err, n_used=n_used, cadence_status=cst, status=0 if np.any(cst == 0) else 1,
+                   star_index=star_index, min_pivot_ratio=ratio, n_iter=n_iter, last_step=last_step, steps=steps,
+                   raw_steps=raw_steps, excursion=excursion)
+        return out
 
     def pixel_periodogram(self, frequency, normalization="amplitude", freq_unit=None, oversample_factor=None):
         """One Lomb-Scargle spectrum per pixel on ONE shared ``frequency`` grid, and where each peaks: which pixels vary, and at

@@ -441,6 +441,16 @@ int cube_psfphot_launch(lk_handle *h, int B, int N, int ny, int nx, const double
                         const double *sigma_host, const double *shift_col, const double *shift_row, double column0, double row0,
                         int use_flux_err, int32_t *star_off_host, double *time_out, double *flux_out, double *flux_err_out, double *background,
                         double *chi2, int32_t *n_used, int8_t *cadence_status, int32_t *status, hipStream_t stream);
+// psffit.hip: the same fit with one common (column, row) shift per cadence fitted next to the fluxes, by variable projection from
+// shift0 (nullable device arrays): fluxes, background and chi2 at the fitted shift, the shifts, their errors, the iterations
+// taken and the last step.  Everything but the stars on the device; enqueued, no synchronisation
+int cube_psffit_launch(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux, const float *flux_err,
+                       const uint8_t *mask, int mask_stride, int S_max, const double *star_col_host, const double *star_row_host,
+                       const double *sigma_host, const double *shift0_col, const double *shift0_row, int max_iter, double tol,
+                       double max_step, double max_shift, double column0, double row0, int use_flux_err, int32_t *star_off_host,
+                       double *time_out, double *flux_out, double *flux_err_out, double *background, double *chi2, double *shift_col,
+                       double *shift_row, double *shift_col_err, double *shift_row_err, double *last_step, int32_t *n_iter,
+                       int32_t *n_used, int8_t *cadence_status, int32_t *status, hipStream_t stream);
 // sff.hip: SFFCorrector for a ragged resident batch.  The regression launcher owns h->ws, so the design matrices and everything
 // else that lives across it sit in `scratch`, a device block of the caller's (sff_scratch_bytes); status_host is valid on
 // return (the call synchronises once, to group the targets by their design width)

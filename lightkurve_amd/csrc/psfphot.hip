@@ -26,24 +26,12 @@
 //
 // No atomics; the order of every sum depends on the cutout's own data alone, so a cutout's outputs have the same bits alone,
 // at any batch position and from run to run.
-#include <cmath>
-#include <vector>
-
-#include "lk_common.hpp"
+#include "psf_common.hpp"  // the lane mapping, psf_edge, the cadence sum, the Cholesky and the star grouping, shared with psffit.hip
 #include "stage_tile.hpp"
 
 namespace lk {
 
 namespace {
-
-constexpr int PSF_LPC = 4;          // lanes per cadence: lane sub of a cadence takes the pixel rows sub, sub + 4, ...
-constexpr int PSF_T = 64 / PSF_LPC; // cadences per workgroup of one wavefront
-constexpr int PSF_MAX_STARS = 8;
-constexpr int PSF_MAX_LDS = 160 * 1024;
-constexpr double PSF_PIVOT_CUT = 1e-12;  // singular: a pivot d_k <= PSF_PIVOT_CUT * G_kk
-
-// E(k) of the header: the Gaussian's integral up to the lower edge of pixel k (upper edge of pixel k - 1), as erf
-__device__ __forceinline__ double psf_edge(int k, double c, double den) { return erf(((double)k - 0.5 - c) / den); }
 
 // factor k of star s of a cutout (p: its row of par): k < nx the column factor of pixel column k, else the row factor of pixel
 // row k - nx, with the star moved by (dc, dr)
@@ -53,14 +41,6 @@ __device__ __forceinline__ double psf_factor(const double *__restrict__ p, int S
     const double c = col ? p[s] + dc - column0 : p[S_max + s] + dr - row0, den = M_SQRT2 * p[2 * S_max + (col ? 0 : 1)];
     const int e = col ? k : k - nx;
     return 0.5 * (psf_edge(e + 1, c, den) - psf_edge(e, c, den));
-}
-
-// the sum of v over the PSF_LPC lanes of a cadence (adjacent lanes), the same bits in each of them: a + b is commutative, so
-// the two lanes of a pair — and then the two pairs — hold the same sum
-template <class T> __device__ __forceinline__ T psf_cadence_sum(T v) {
-#pragma unroll
-    for (int o = 1; o < PSF_LPC; o <<= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 }  // namespace
@@ -175,55 +155,11 @@ template <int S> __global__ __launch_bounds__(64) void cube_psfphot_kernel(const
         for (int j = i; j < K; ++j) G[i][j] = psf_cadence_sum(G[i][j]);
     }
 
-    // every lane of the cadence: G = L L^T in index order, no pivoting
-    double L[K][K];
-    bool singular = false;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double d = G[k][k];
-#pragma unroll
-        for (int j = 0; j < k; ++j) d -= L[k][j] * L[k][j];
-        singular = singular || !(isfinite(d) && d > PSF_PIVOT_CUT * G[k][k]);
-        L[k][k] = sqrt(d);
-#pragma unroll
-        for (int i = k + 1; i < K; ++i) {
-            double s = G[k][i];
-#pragma unroll
-            for (int j = 0; j < k; ++j) s -= L[i][j] * L[k][j];
-            L[i][k] = s / L[k][k];
-        }
-    }
-    double z[K], theta[K], var[K];
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        double s = rhs[i];
-#pragma unroll
-        for (int j = 0; j < i; ++j) s -= L[i][j] * z[j];
-        z[i] = s / L[i][i];
-    }
-#pragma unroll
-    for (int i = K - 1; i >= 0; --i) {
-        double s = z[i];
-#pragma unroll
-        for (int j = i + 1; j < K; ++j) s -= L[j][i] * theta[j];
-        theta[i] = s / L[i][i];
-    }
-    // M = L^-1 column by column; (G^-1)_kk = sum_i M_ik^2, i >= k
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double M[K];
-        M[k] = 1.0 / L[k][k];
-        double v = M[k] * M[k];
-#pragma unroll
-        for (int i = k + 1; i < K; ++i) {
-            double s = 0.0;
-#pragma unroll
-            for (int j = k; j < i; ++j) s -= L[i][j] * M[j];
-            M[i] = s / L[i][i];
-            v += M[i] * M[i];
-        }
-        var[k] = v;
-    }
+    // every lane of the cadence: G = L L^T in index order, no pivoting; solve; (G^-1)_kk for the variances
+    double L[K][K], theta[K], var[K];
+    const bool singular = psf_cholesky<K>(G, L);
+    psf_solve<K>(L, rhs, theta);
+    psf_variances<K>(L, var);
     const int st = !fin ? 1 : n < S + 2 ? 2 : singular ? 3 : 0;
 
     // chi2 from the residuals, over the tile the lanes have just walked (st is the same in the lanes of a cadence)
@@ -273,6 +209,12 @@ __global__ __launch_bounds__(256) void cube_psfphot_status_kernel(const int8_t *
     if (threadIdx.x == 0) status[b] = any ? 0 : 1;
 }
 
+int psf_status_launch(int B, int N, const int8_t *cadence_status, int32_t *status, hipStream_t stream) {
+    hipLaunchKernelGGL(cube_psfphot_status_kernel, dim3(B), dim3(256), 0, stream, cadence_status, N, (int *)status);
+    LK_HIP_CHECK(hipGetLastError());
+    return LK_OK;
+}
+
 namespace {
 
 template <int S> int psf_launch(lk_handle *h, const PsfArgs &a, int chunks, int count, size_t lds, hipStream_t stream) {
@@ -300,7 +242,7 @@ int cube_psfphot_launch(lk_handle *h, int B, int N, int ny, int nx, const double
     const int64_t npix64 = (int64_t)ny * nx;
     LK_REQUIRE((int64_t)N * npix64 < (int64_t)1 << 31, "a cutout of %d x %d x %d values is too large", N, ny, nx);
     // row pitch of the tile: 4 x an odd number, so the 8 cadences x 4 pixel rows of a ds_read_b32 half spread over the banks
-    const int npix = (int)npix64, nt = nx + ny, pitch = 4 * (((npix + 3) / 4) | 1), PAR = 2 * S_max + 2;
+    const int npix = (int)npix64, nt = nx + ny, pitch = 4 * (((npix + 3) / 4) | 1);
     LK_REQUIRE(mask_stride == 0 || mask_stride == npix, "mask_stride must be 0 (one mask for the batch) or npix");
     const bool shifted = shift_col != nullptr;
     const size_t tile_bytes = (size_t)PSF_T * pitch * 4 * (use_flux_err ? 2 : 1) + npix;
@@ -309,43 +251,11 @@ int cube_psfphot_launch(lk_handle *h, int B, int N, int ny, int nx, const double
                S_max, shifted ? " and shifts" : "", lds_bytes(S_max), PSF_MAX_LDS);
 
     // the cutout's stars (no NaN coordinate) first and in order; the cutouts grouped by their star count
-    std::vector<double> par((size_t)B * PAR, NAN);
-    std::vector<int> ints((size_t)3 * B);  // order | n_stars | star_off
-    int *order = ints.data(), *n_stars = order + B, *star_off = n_stars + B;
-    int first[PSF_MAX_STARS + 2] = {0};
-    int total = 0;
-    for (int b = 0; b < B; ++b) {
-        double *p = par.data() + (size_t)b * PAR;
-        int S = 0;
-        for (int s = 0; s < S_max; ++s) {
-            const double c = star_col_host[(size_t)b * S_max + s], r = star_row_host[(size_t)b * S_max + s];
-            if (std::isnan(c) || std::isnan(r)) continue;
-            LK_REQUIRE(std::isfinite(c) && std::isfinite(r), "cutout %d: star %d has an infinite coordinate", b, s);
-            p[S] = c;
-            p[S_max + S] = r;
-            ++S;
-        }
-        LK_REQUIRE(S >= 1, "cutout %d has no star", b);
-        for (int k = 0; k < 2; ++k) {
-            const double sg = sigma_host[2 * (size_t)b + k];
-            LK_REQUIRE(std::isfinite(sg) && sg > 0.0, "cutout %d: sigma must be finite and > 0 (got %g)", b, sg);
-            p[2 * S_max + k] = sg;
-        }
-        n_stars[b] = S;
-        star_off[b] = total;
-        total += S;
-        ++first[S + 1];
-    }
-    for (int S = 1; S <= PSF_MAX_STARS + 1; ++S) first[S] += first[S - 1];  // first[S]: where the cutouts of S stars begin
-    {
-        int at[PSF_MAX_STARS + 1];
-        for (int S = 0; S <= PSF_MAX_STARS; ++S) at[S] = first[S];
-        for (int b = 0; b < B; ++b) order[at[n_stars[b]]++] = b;
-    }
-    if (star_off_host) {
-        for (int b = 0; b < B; ++b) star_off_host[b] = star_off[b];
-        star_off_host[B] = total;
-    }
+    PsfStars stars;
+    if (const int rc = psf_group_stars(B, S_max, star_col_host, star_row_host, sigma_host, star_off_host, stars)) return rc;
+    const std::vector<double> &par = stars.par;
+    const std::vector<int> &ints = stars.ints;
+    const int *first = stars.first;
 
     double *d_par, *d_tab;
     int *d_ints;
@@ -386,9 +296,7 @@ int cube_psfphot_launch(lk_handle *h, int B, int N, int ny, int nx, const double
         }
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(cube_psfphot_status_kernel, dim3(B), dim3(256), 0, stream, (const int8_t *)cadence_status, N, (int *)status);
-    LK_HIP_CHECK(hipGetLastError());
-    return LK_OK;
+    return psf_status_launch(B, N, cadence_status, status, stream);
 }
 
 }  // namespace lk

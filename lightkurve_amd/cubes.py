@@ -27,6 +27,42 @@ def _first_finite_times(time):
     return np.ascontiguousarray(np.where(fin.any(axis=1), time[np.arange(len(time)), np.argmax(fin, axis=1)], np.nan))
 
 
+def _psf_stars(B, star_col, star_row, sigma):
+    """The stars and widths of the PSF calls, checked -> ((star_col, star_row) as C-contiguous float64 [B, S_max], the bool [B,
+    S_max] of the stars that take part (no NaN coordinate), sigma float64 [B, 2], S_max)."""
+    from .correctors.pldcorrector import _psf_sigma
+    pos = []
+    for name, a in (("star_col", star_col), ("star_row", star_row)):
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim == 1:
+            a = np.broadcast_to(a, (B, a.size))
+        if a.ndim != 2 or a.shape[0] != B:
+            raise ValueError("%s must be [S] or [B, S] with B = %d (got shape %r)" % (name, B, a.shape))
+        pos.append(np.ascontiguousarray(a))
+    if pos[0].shape != pos[1].shape or not 1 <= pos[0].shape[1] <= 8:
+        raise ValueError("star_col and star_row must have one shape with 1 .. 8 stars per cutout (got %r and %r)"
+                         % (pos[0].shape, pos[1].shape))
+    part = ~(np.isnan(pos[0]) | np.isnan(pos[1]))
+    if not np.all(np.isfinite(pos[0][part]) & np.isfinite(pos[1][part])):
+        raise ValueError("a star position is infinite")
+    if not np.all(part.any(axis=1)):
+        raise ValueError("cutouts %s have no star" % np.flatnonzero(~part.any(axis=1)).tolist())
+    sg = np.asarray(sigma, dtype=np.float64)
+    sg = np.array([_psf_sigma(s) for s in sg]) if sg.shape == (B, 2) else np.tile(_psf_sigma(sg), (B, 1))
+    return pos, part, np.ascontiguousarray(sg, dtype=np.float64), pos[0].shape[1]
+
+
+# ``info`` of the PSF calls: (key, dtype), B x N values each but ``status`` (B)
+_PSF_INFO = (("background", np.float64), ("chi2", np.float64), ("n_used", np.int32), ("cadence_status", np.int8), ("status", np.int32))
+_PSF_FIT_INFO = _PSF_INFO + (("shift_col", np.float64), ("shift_row", np.float64), ("shift_col_err", np.float64),
+                             ("shift_row_err", np.float64), ("last_step", np.float64), ("n_iter", np.int32))
+
+
+def _psf_info_spec(B, N, spec):
+    """(key, dtype, bytes) of every ``info`` buffer of a PSF call."""
+    return [(key, dt, (B if key == "status" else B * N) * np.dtype(dt).itemsize) for key, dt in spec]
+
+
 class DevicePixelCubeBatch(object):
     """B same-shaped target-pixel cutouts IN HBM — the input of ``PLDCorrector`` as ``DeviceLightCurveBatch`` is the input of
     the light-curve chain: ``d_flux`` / ``d_flux_err`` float32 [B][N][npix] (npix = ny * nx, row-major pixels: the layout
@@ -716,35 +752,80 @@ class DevicePixelCubeBatch(object):
         int32: 1 when no cadence is ok) and ``star_off`` (B + 1 int32) — ``DeviceBuffer``s enqueued on the batch's stream, or
         host arrays with ``to_host=True``.  Nothing is raised per cadence.  A cutout's outputs have the same bits alone, at any
         batch position and from run to run."""
-        from .correctors.pldcorrector import _psf_sigma
-        from .device import DeviceLightCurveBatch
         h, (B, N, ny, nx) = self.handle, self.shape
-        npix = ny * nx
-        pos = []
-        for name, a in (("star_col", star_col), ("star_row", star_row)):
-            a = np.asarray(a, dtype=np.float64)
-            if a.ndim == 1:
-                a = np.broadcast_to(a, (B, a.size))
-            if a.ndim != 2 or a.shape[0] != B:
-                raise ValueError("%s must be [S] or [B, S] with B = %d (got shape %r)" % (name, B, a.shape))
-            pos.append(np.ascontiguousarray(a))
-        if pos[0].shape != pos[1].shape or not 1 <= pos[0].shape[1] <= 8:
-            raise ValueError("star_col and star_row must have one shape with 1 .. 8 stars per cutout (got %r and %r)"
-                             % (pos[0].shape, pos[1].shape))
-        S_max = pos[0].shape[1]
-        part = ~(np.isnan(pos[0]) | np.isnan(pos[1]))
-        if not np.all(np.isfinite(pos[0][part]) & np.isfinite(pos[1][part])):
-            raise ValueError("a star position is infinite")
-        if not np.all(part.any(axis=1)):
-            raise ValueError("cutouts %s have no star" % np.flatnonzero(~part.any(axis=1)).tolist())
-        sg = np.asarray(sigma, dtype=np.float64)
-        sg = np.array([_psf_sigma(s) for s in sg]) if sg.shape == (B, 2) else np.tile(_psf_sigma(sg), (B, 1))
-        sg = np.ascontiguousarray(sg, dtype=np.float64)
+        pos, part, sg, S_max = _psf_stars(B, star_col, star_row, sigma)
         keep = []
+        d_shift = self._psf_shift_buffers(shifts, "shifts", keep)
+        _, d_mask, stride, k = self._stage_mask(aperture_mask, False)
+        keep += [k, d_mask]
+        rows = int(part.sum())
+        d_t, d_f, d_e = (DeviceBuffer(h, rows * N * 8) for _ in range(3))
+        info = {key: DeviceBuffer(h, size) for key, _, size in _psf_info_spec(B, N, _PSF_INFO)}
+        star_off = np.zeros(B + 1, dtype=np.int32)
+        _capi._check(_capi._lib.lk_cube_psf_photometry_batch_dev(
+            h._h, B, N, ny, nx, _p(self.d_time), _p(self.d_flux), _p(self.d_flux_err), _p(d_mask), stride, S_max,
+            pos[0].ctypes.data_as(_dp), pos[1].ctypes.data_as(_dp), sg.ctypes.data_as(_dp), _p(d_shift[0]), _p(d_shift[1]),
+            float(column), float(row), int(bool(use_flux_err)), star_off.ctypes.data_as(_i32p), _p(d_t), _p(d_f), _p(d_e),
+            _p(info["background"]), _p(info["chi2"]), _p(info["n_used"]), _p(info["cadence_status"]), _p(info["status"]),
+            _vp(self.stream or None)))
+        return self._psf_results(pos, part, (d_t, d_f, d_e), keep + [d for d in d_shift if d is not None], info, _PSF_INFO,
+                                 star_off, to_host)
+
+    def psf_fit(self, star_col, star_row, sigma, shifts0=None, max_iter=10, tol=1e-7, max_step=0.5, max_shift=2.0,
+                aperture_mask="all", column=0, row=0, use_flux_err=True, to_host=False):
+        """PSF photometry that fits each cadence's pointing shift: ``psf_photometry`` with ONE common (column, row) shift of all
+        stars per cadence fitted next to the fluxes and the background, by variable projection (``lk_cube_psf_fit_batch_dev``;
+        the numpy mirror and the definition is ``PixelCube.psf_fit``).  The per-cadence motion shift of
+        ``TargetPixelFile.to_lightcurve(method="prf")``: unlike the centroid of the whole blend (``estimate_centroids``) it is
+        not biased by the blending and does not move when one star varies.  Per-star positions, the PSF width, tabulated PRFs,
+        rotation and a background gradient are not fitted.  Stars, ``sigma``, ``aperture_mask``, ``column`` / ``row`` and
+        ``use_flux_err`` as in ``psf_photometry``.  ``shifts0``: None (start at 0) or a pair (shift_col, shift_row) of host
+        arrays [B, N] or of ``DeviceBuffer``s of B x N float64, the initial shifts.  Up to ``max_iter`` (1 .. 64) Gauss-Newton
+        steps per cadence, each component clamped to +-``max_step``; a cadence stops when its step is below ``tol`` (``tol`` =
+        0: exactly ``max_iter`` steps), and fails when it moves more than ``max_shift`` from its start.  Returns ``(lcs,
+        info)`` shaped like ``psf_photometry``'s, the fluxes, errors (conditional on the shift), ``background`` and ``chi2``
+        being ``psf_photometry``'s at the fitted shifts.  ``info`` gains ``shift_col``, ``shift_row``, ``shift_col_err``,
+        ``shift_row_err``, ``last_step`` (B x N float64) and ``n_iter`` (B x N int32); ``cadence_status``: 0 ok, 1 the time or
+        an initial shift is not finite, 2 n_used < S + 4, 3 singular, 4 not converged, 5 left ``max_shift`` — a cadence that is
+        not ok is NaN in every float output, the shifts included, while ``n_iter`` and ``last_step`` are reported for every
+        cadence.  The shift buffers have the layout ``psf_photometry(shifts=)`` takes and feed ``sff_correct`` as a pointing
+        history that no single star's variability biases::
+
+            lcs, info = cubes.psf_fit(star_col, star_row, 1.1)
+            again, _ = cubes.psf_photometry(star_col, star_row, 1.1, shifts=(info["shift_col"], info["shift_row"]))
+
+        Nothing is raised per cadence.  A cutout's outputs have the same bits alone, at any batch position and from run to
+        run."""
+        from .correctors.pldcorrector import _psf_fit_parameters
+        h, (B, N, ny, nx) = self.handle, self.shape
+        pos, part, sg, S_max = _psf_stars(B, star_col, star_row, sigma)
+        max_iter, tol, max_step, max_shift = _psf_fit_parameters(max_iter, tol, max_step, max_shift)
+        keep = []
+        d_shift = self._psf_shift_buffers(shifts0, "shifts0", keep)
+        _, d_mask, stride, k = self._stage_mask(aperture_mask, False)
+        keep += [k, d_mask]
+        rows = int(part.sum())
+        d_t, d_f, d_e = (DeviceBuffer(h, rows * N * 8) for _ in range(3))
+        info = {key: DeviceBuffer(h, size) for key, _, size in _psf_info_spec(B, N, _PSF_FIT_INFO)}
+        star_off = np.zeros(B + 1, dtype=np.int32)
+        _capi._check(_capi._lib.lk_cube_psf_fit_batch_dev(
+            h._h, B, N, ny, nx, _p(self.d_time), _p(self.d_flux), _p(self.d_flux_err), _p(d_mask), stride, S_max,
+            pos[0].ctypes.data_as(_dp), pos[1].ctypes.data_as(_dp), sg.ctypes.data_as(_dp), _p(d_shift[0]), _p(d_shift[1]),
+            max_iter, tol, max_step, max_shift, float(column), float(row), int(bool(use_flux_err)), star_off.ctypes.data_as(_i32p),
+            _p(d_t), _p(d_f), _p(d_e), _p(info["background"]), _p(info["chi2"]), _p(info["shift_col"]), _p(info["shift_row"]),
+            _p(info["shift_col_err"]), _p(info["shift_row_err"]), _p(info["last_step"]), _p(info["n_iter"]), _p(info["n_used"]),
+            _p(info["cadence_status"]), _p(info["status"]), _vp(self.stream or None)))
+        return self._psf_results(pos, part, (d_t, d_f, d_e), keep + [d for d in d_shift if d is not None], info, _PSF_FIT_INFO,
+                                 star_off, to_host)
+
+    def _psf_shift_buffers(self, shifts, name, keep):
+        """``shifts`` / ``shifts0`` of the PSF calls -> [shift_col, shift_row] on the device (None, None without): a pair of
+        host arrays [B, N], uploaded (what must outlive the upload is appended to ``keep``), or of ``DeviceBuffer``s."""
+        h, (B, N) = self.handle, self.shape[:2]
         d_shift = [None, None]
         if shifts is not None:
             if len(shifts) != 2:
-                raise ValueError("shifts must be a pair (shift_col, shift_row)")
+                raise ValueError("%s must be a pair (shift_col, shift_row)" % name)
             for i, a in enumerate(shifts):
                 if isinstance(a, DeviceBuffer):
                     if a.nbytes != B * N * 8:
@@ -753,34 +834,28 @@ class DevicePixelCubeBatch(object):
                 else:
                     a = np.asarray(a, dtype=np.float64)
                     if a.shape != (B, N):
-                        raise ValueError("shifts must be (B, N) = %r arrays (got %r)" % ((B, N), a.shape))
+                        raise ValueError("%s must be (B, N) = %r arrays (got %r)" % (name, (B, N), a.shape))
                     d_shift[i], k = _upload(h, a, self.stream, np.float64)
                     keep.append(k)
-        _, d_mask, stride, k = self._stage_mask(aperture_mask, False)
-        keep += [k, d_mask]
+        return d_shift
+
+    def _psf_results(self, pos, part, curves, keep, info, spec, star_off, to_host):
+        """The return value of the PSF calls: the light curves (one per star that took part, N cadences each) and ``info``
+        (``DeviceBuffer``s, or host arrays with ``to_host``) with ``star_off``."""
+        from .device import DeviceLightCurveBatch
+        h, (B, N) = self.handle, self.shape[:2]
         rows = int(part.sum())
-        d_t, d_f, d_e = (DeviceBuffer(h, rows * N * 8) for _ in range(3))
-        d_bkg, d_chi = DeviceBuffer(h, B * N * 8), DeviceBuffer(h, B * N * 8)
-        d_n, d_cs, d_st = DeviceBuffer(h, B * N * 4), DeviceBuffer(h, B * N), DeviceBuffer(h, B * 4)
-        star_off = np.zeros(B + 1, dtype=np.int32)
-        _capi._check(_capi._lib.lk_cube_psf_photometry_batch_dev(
-            h._h, B, N, ny, nx, _p(self.d_time), _p(self.d_flux), _p(self.d_flux_err), _p(d_mask), stride, S_max,
-            pos[0].ctypes.data_as(_dp), pos[1].ctypes.data_as(_dp), sg.ctypes.data_as(_dp), _p(d_shift[0]), _p(d_shift[1]),
-            float(column), float(row), int(bool(use_flux_err)), star_off.ctypes.data_as(_i32p), _p(d_t), _p(d_f), _p(d_e), _p(d_bkg),
-            _p(d_chi), _p(d_n), _p(d_cs), _p(d_st), _vp(self.stream or None)))
         meta = [dict(self.meta[b], STAR_INDEX=int(s), STAR_COL=float(pos[0][b, s]), STAR_ROW=float(pos[1][b, s]))
                 for b in range(B) for s in np.flatnonzero(part[b])]
-        lcs = DeviceLightCurveBatch(d_t, d_f, d_e, np.arange(rows + 1, dtype=np.int64) * N, meta, self.device, self.stream,
-                                    is_sorted=True if self.is_sorted else None)
-        lcs._keep = keep + [d for d in d_shift if d is not None]       # what the enqueued fit still reads
-        info = {"background": d_bkg, "chi2": d_chi, "n_used": d_n, "cadence_status": d_cs, "status": d_st}
+        lcs = DeviceLightCurveBatch(curves[0], curves[1], curves[2], np.arange(rows + 1, dtype=np.int64) * N, meta, self.device,
+                                    self.stream, is_sorted=True if self.is_sorted else None)
+        lcs._keep = list(keep)                                         # what the enqueued fit still reads
         if not to_host:
             info["star_off"], k = _upload(h, star_off, self.stream, np.int32)
             lcs._keep.append(k)
             return lcs, info
-        for key, dt, shp in (("background", np.float64, (B, N)), ("chi2", np.float64, (B, N)), ("n_used", np.int32, (B, N)),
-                             ("cadence_status", np.int8, (B, N)), ("status", np.int32, (B,))):
-            info[key] = self._get(info[key], dt, shp)
+        for key, dt, _ in _psf_info_spec(B, N, spec):
+            info[key] = self._get(info[key], dt, (B,) if key == "status" else (B, N))
         self._keep = []
         info["star_off"] = star_off
         return lcs, info

@@ -139,6 +139,13 @@ threads over the first `LK_WALLS_MIRROR_B` (default 16) cutouts, scaled to the b
 a synchronise.  Written to profiles/psfphot_walls.txt.  `psfphot_trace`: R and Rs twice and nothing else, for `rocprofv3
 --kernel-trace --stats` (profiles/psfphot_kernel_stats.txt).
 
+`psffit`: the PSF fit with a pointing shift per cadence on the same batch shape and star count, the cubes rendered with true
+shifts uniform in +-0.3 px, in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5) times after one warm-up.  F
+`cubes.psf_fit(star_col, star_row, sigma)` with the defaults; Rs `cubes.psf_photometry` of the same cubes at the true shifts
+(resident); H the mirror `PixelCube.psf_fit` per cutout on 16 threads over the first `LK_WALLS_MIRROR_B` (default 16) cutouts.
+Every timed region ends with a synchronise.  Written to profiles/psffit_walls.txt.  `psffit_trace`: F and Rs twice and nothing
+else, for `rocprofv3 --kernel-trace --stats` (profiles/psffit_kernel_stats.txt).
+
 `background`: the per-cadence background of the same batch shape with 'background' masks, in ONE process, the routes alternating,
 `LK_WALLS_REPS` (default 5) times after one warm-up.  F `cubes.subtract_background()` (median images, masks, the fused estimate +
 subtraction) and Fm the same with the masks given; E `cubes.estimate_background()`, Em with the masks given, Es with the scatter
@@ -1482,6 +1489,91 @@ def psfphot(which):
         "profiles/psfphot_kernel_stats.txt" % (B, med["H"] * B / Bm / med["R"], med["Hs"] * B / Bm / med["Rs"], floor / 1e6)])
 
 
+def psffit(which):
+    from concurrent.futures import ThreadPoolExecutor
+    from scipy.special import erf
+    from lightkurve_amd.device import DevicePixelCubeBatch
+    B, N, side, S = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "500"), ("LK_WALLS_N", "4000"), ("LK_WALLS_SIDE", "11"),
+                                                            ("LK_WALLS_STARS", "4")))
+    reps, Bm = int(os.environ.get("LK_WALLS_REPS", "5")), min(B, int(os.environ.get("LK_WALLS_MIRROR_B", "16")))
+    rng = np.random.default_rng(67)
+    npix = side * side
+    t = 1000.0 + np.arange(N) / 720.0                                    # two-minute cadences
+    sigma = 1.1
+    cells = int(np.ceil(np.sqrt(S)))
+    lattice = np.array([((i + 0.5) * side / cells - 0.5, (j + 0.5) * side / cells - 0.5) for j in range(cells) for i in range(cells)][:S])
+    col = lattice[None, :, 0] + rng.uniform(-0.3, 0.3, (B, S))
+    row = lattice[None, :, 1] + rng.uniform(-0.3, 0.3, (B, S))
+    shifts = (rng.uniform(-0.3, 0.3, (B, N)), rng.uniform(-0.3, 0.3, (B, N)))     # the true pointing of every cadence
+    edges = np.arange(side + 1) - 0.5
+    flux = np.empty((B, N, side, side), dtype=np.float32)
+    for b in range(B):                                                  # every cadence rendered at its own shift
+        gx = np.diff(erf((edges[None, None, :] - col[b][None, :, None] - shifts[0][b][:, None, None]) / (np.sqrt(2) * sigma)), axis=2) / 2
+        gy = np.diff(erf((edges[None, None, :] - row[b][None, :, None] - shifts[1][b][:, None, None]) / (np.sqrt(2) * sigma)), axis=2) / 2
+        img = 100.0 + np.einsum("s,nsy,nsx->nyx", rng.uniform(2000.0, 20000.0, S), gy, gx)
+        flux[b] = img.astype(np.float32) + 3.0 * rng.standard_normal((N, side, side), dtype=np.float32)
+    err = np.full_like(flux, 3.0)
+    cubes = DevicePixelCubeBatch.from_arrays(np.tile(t, (B, 1)), flux, err)
+    cubes.synchronize()
+    del flux, err
+    d_shifts = tuple(_upload_f64(cubes, a) for a in shifts)
+
+    def fit():
+        out = cubes.psf_fit(col, row, sigma)
+        cubes.synchronize()
+        return out
+
+    def given():
+        out = cubes.psf_photometry(col, row, sigma, shifts=d_shifts)
+        cubes.synchronize()
+        return out
+
+    if "psffit_trace" in which:
+        for _ in range(2):
+            fit()
+            given()
+        return
+
+    host_m = cubes.to_host()[:Bm]
+
+    def mirror():
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            return list(ex.map(lambda b: host_m[b].psf_fit(col[b], row[b], sigma), range(Bm)))
+
+    fns = {"F": fit, "Rs": given, "H": mirror}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    lcs, info = first["F"]
+    n_iter = info["n_iter"].download(np.int32, B * N, stream=lcs.stream).reshape(B, N)
+    cstat = info["cadence_status"].download(np.int8, B * N, stream=lcs.stream).reshape(B, N)
+    got = tuple(info[k].download(np.float64, B * N, stream=lcs.stream).reshape(B, N) for k in ("shift_col", "shift_row"))
+    off = float(max(np.nanmax(np.abs(g - s)) for g, s in zip(got, shifts)))
+    f = lcs.flux_host().reshape(B * S, N)[:Bm * S].reshape(Bm, S, N)
+    h = np.stack([o["flux"] for o in first["H"]])
+    rel = float(np.max(np.abs(f - h) / np.max(np.abs(h), axis=(1, 2), keepdims=True)))
+    rel_u = float(max(np.max(np.abs(g[:Bm] - np.stack([o[k] for o in first["H"]]))) for g, k in zip(got, ("shift_col", "shift_row"))))
+    same_iter = bool(np.array_equal(n_iter[:Bm], np.stack([o["n_iter"] for o in first["H"]])))
+    first.clear()
+    del lcs, info
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    evals = float(np.mean(np.max(np.pad(n_iter, ((0, 0), (0, -N % 16))).reshape(B, -1, 16), axis=2))) + 1
+    write_walls("psffit_walls.txt", [
+        "PSF fit with a pointing shift per cadence, %d cutouts x %d cadences x %d x %d float32, %d stars per cutout, sigma %.1f px, true "
+        "shifts uniform in +-0.3 px (%.1f MB of flux and flux_err resident, read once)" % (B, N, side, side, S, sigma, B * N * npix * 8 / 1e6),
+        "  F    cubes.psf_fit(star_col, star_row, sigma), defaults, from shifts 0; everything resident                     %s" % spread(ts["F"]),
+        "  Rs   cubes.psf_photometry(..., shifts=(DeviceBuffer, DeviceBuffer)) at the TRUE shifts, the same run            %s" % spread(ts["Rs"]),
+        "  H    PixelCube.psf_fit on 16 threads, the first %d cutouts only                                                 %s" % (Bm, spread(ts["H"])),
+        "  cadence statuses: %s; iterations per cadence: mean %.2f, max %d; evaluations per tile of 16 cadences (its slowest cadence + 1): "
+        "mean %.2f" % (dict(zip(*(a.tolist() for a in np.unique(cstat, return_counts=True)))), float(n_iter.mean()), int(n_iter.max()), evals),
+        "  largest |fitted - true shift| %.4f px; first %d cutouts against the mirror: max |flux difference| / max |flux| %.2e, max |shift "
+        "difference| %.2e px, the same n_iter: %s" % (off, Bm, rel, rel_u, same_iter),
+        "  F / Rs = %.2f (%.2f per evaluation of a tile); H scaled to %d cutouts / F = %.0f; kernel times alone: "
+        "profiles/psffit_kernel_stats.txt" % (med["F"] / med["Rs"], med["F"] / med["Rs"] / evals, B, med["H"] * B / Bm / med["F"])])
+
+
 def _upload_f64(cubes, a):
     from lightkurve_amd.devmem import _upload
     buf, keep = _upload(cubes.handle, np.ascontiguousarray(a, dtype=np.float64), cubes.stream, np.float64)
@@ -1726,6 +1818,8 @@ def main():
         background()
     if {"psfphot", "psfphot_trace"} & set(which):
         psfphot(which)
+    if {"psffit", "psffit_trace"} & set(which):
+        psffit(which)
     if {"pixelpg", "pixelpg_trace"} & set(which):
         pixelpg(which)
     if {"stitch", "stitch_trace"} & set(which):
