@@ -1342,6 +1342,64 @@ int lk_cube_psf_fit_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const 
                               double *shift_row_err, double *last_step, int32_t *n_iter, int32_t *n_used, int8_t *cadence_status,
                               int32_t *status, void *stream);
 
+/* lk_cube_psf_width_batch_dev <- the PSF width of every cutout, fitted (PixelCube.psf_width is the numpy mirror and the definition):
+ *   ONE pair v = (sigma_col, sigma_row) per cutout, shared by all its cadences, by variable projection in Kaufman's form with the
+ *   linear unknowns (the fluxes of up to 8 stars and one background PER CADENCE) projected out.  The PSF scale of
+ *   TargetPixelFile.to_lightcurve(method="prf"); the chain is lk_cube_psf_fit_batch_dev(a guess of sigma) -> this call at the
+ *   fitted shifts -> lk_cube_psf_fit_batch_dev or lk_cube_psf_photometry_batch_dev at the fitted sigma.  Per-star positions, a
+ *   width that varies with time or across the cutout, tabulated PRFs, rotation and a background gradient are not fitted.
+ *   Inputs, stars, mask, PSF, used pixels, weights, design A = [g_0 ... g_{S-1}, 1], K = S + 1, the Cholesky and its pivot cut
+ *   1e-12 G_kk are those of lk_cube_psf_photometry_batch_dev.  sigma0: HOST array [B][2], the start.  shift_col / shift_row
+ *   (nullable, both or neither): DEVICE arrays [B][N] added to every star's position at that cadence.  cadence_mask (nullable):
+ *   DEVICE array [B][N] uint8, non-zero = the width is fitted on this cadence.
+ *   A cadence is ELIGIBLE when cadence_mask selects it, its time and its shift are finite and n_used >= S + 2; that does not
+ *   depend on v.  One EVALUATION at v, per eligible cadence n: G = A^T W A, rhs = A^T W y, G = L L^T, theta = G^-1 rhs, r = y - A
+ *   theta; D = [sum_s theta_s dg_s/dsigma_col, sum_s theta_s dg_s/dsigma_row] over the used pixels, where the derivative of a
+ *   column factor (erf(z_{k+1}) - erf(z_k)) / 2, z_k = (k - 1/2 - c) / (sqrt(2) sigma_col), by sigma_col is -(Q(k + 1) - Q(k)),
+ *   Q(k) = (k - 1/2 - c) exp(-z_k^2) / (sqrt(2 pi) sigma_col^2), rows likewise; C = A^T W D (K x 2), E = D^T W D, g_n = D^T W r,
+ *   S2_n = E - (L^-1 C)^T (L^-1 C), chi2_n = sum w r^2.  A cadence whose G fails a pivot is singular at this evaluation and
+ *   contributes nothing.  The cutout's sums g = sum g_n, H = sum S2_n, chi2 = sum chi2_n, n_cadences and n_pixels = sum n_used
+ *   run over the contributing cadences in an order fixed by N alone.
+ *   Per cutout, from v = sigma0, for it = 1 .. max_iter:
+ *     1. evaluate at v;
+ *     2. n_cadences == 0: status 1, stop;
+ *     3. H = L2 L2^T by the 2 x 2 Cholesky without pivoting; singular when H_00 is not finite and > 0 or d_11 is not finite and
+ *        > 1e-12 H_11: status 3, stop;
+ *     4. dv = H^-1 g, each component clamped to +-max_step;
+ *     5. v += dv, n_iter = it, last_step = max |dv| after the clamp;
+ *     6. a component of v not in [min_sigma, max_sigma]: status 5, stop;
+ *     7. tol > 0 and last_step < tol: converged, stop.
+ *   After max_iter steps without convergence the status is 4; tol == 0 means "take exactly max_iter steps" and is status 0.  A
+ *   status 0 cutout is evaluated once more at its final v (no cadence there: status 1; H singular: status 3): sigma [B][2] = v,
+ *   sigma_err [B][2] = sqrt((H^-1)_kk) (not scaled by chi2 and conditional on the shifts, the convention of flux_err),
+ *   sigma_cov [B] = (H^-1)_01 and chi2 [B] are those of that evaluation.  A failed cutout is NaN in these four; nothing is raised.
+ *   Written for every cutout: status [B] int32; n_iter [B] int32 (the updates made); last_step [B] float64 (NaN before the first
+ *   update); n_cadences [B] int32 and n_pixels [B] int64 of the last evaluation made; trace [B][max_iter + 1][2] float64: row k
+ *   is the v of evaluation k + 1, NaN beyond the evaluations made — the final evaluation is made at, and rewrites, row n_iter,
+ *   so a status 0 cutout has n_iter + 1 rows that are not NaN, a failed one the points it evaluated, and a v that left the bounds
+ *   (status 5) is not in it; cadence_status [B][N] int8 from the last evaluation made, in this order of precedence: 6 not
+ *   selected by cadence_mask, 1 the time or a shift is not finite, 2 n_used < S + 2, 3 singular, 0 contributed.
+ *   LK_EINVAL: where lk_cube_psf_fit_batch_dev returns it (its LDS bound included: 16 x 8 pitch + npix + 2 x 16 x 8 S_max (nx +
+ *   ny) bytes, a factor and a derivative table per cadence, must not exceed 160 KiB), and max_iter outside 1 .. 64, tol not
+ *   finite or < 0, max_step not > 0, min_sigma or max_sigma not finite, or not 0 < min_sigma <= sigma0 <= max_sigma; nothing is
+ *   launched then.
+ *   Two kernels per evaluation, enqueued max_iter + 1 times with no synchronisation and no host read in between.  Evaluate: one
+ *   wavefront per tile of 16 cadences, four lanes per cadence, instantiated on S, the staging, the tables and the two walks of
+ *   lk_cube_psf_fit_batch_dev with the derivatives by the width; it reads v from the cutout's state record and returns at once
+ *   when the cutout has stopped, and a tile that cadence_mask leaves out entirely is not read; the tile's 16 cadences are added by a fixed butterfly (a cadence that does not contribute
+ *   enters as +0) into one 64-byte record per tile.  Step: one wavefront per cutout adds the tile records lane-strided in index
+ *   order and then by the butterfly, factors H, applies the rules above and advances the state.  No atomics; a cutout's outputs
+ *   have the same bits alone, at any batch position, with any other cutouts in the batch and from run to run.  Scratch: B x
+ *   ceil(N / 16) x 64 bytes of tile records, 40 B of state, B x (2 S_max + 2) x 8 + 12 B of the stars, of the handle's arena.
+ *   Enqueued, no synchronisation. */
+int lk_cube_psf_width_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
+                                const float *flux_err, const uint8_t *mask, int mask_stride, int S_max, const double *star_col,
+                                const double *star_row, const double *sigma0, const double *shift_col, const double *shift_row,
+                                const uint8_t *cadence_mask, int max_iter, double tol, double max_step, double min_sigma,
+                                double max_sigma, double column0, double row0, int use_flux_err, double *sigma, double *sigma_err,
+                                double *sigma_cov, double *chi2, double *last_step, double *trace, int32_t *n_iter,
+                                int32_t *n_cadences, int64_t *n_pixels, int8_t *cadence_status, int32_t *status, void *stream);
+
 /* lk_cube_background_batch_dev <- TargetPixelFile.estimate_background(aperture_mask) per cadence of the same resident cubes,
  *   and the subtraction of that background, in one pass (PixelCube.estimate_background / subtract_background are the numpy
  *   mirror).  mask / mask_stride as lk_cube_aperture_batch_dev; sel = the masked pixels of cadence i of cutout b.

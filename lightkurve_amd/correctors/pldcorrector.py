@@ -150,6 +150,73 @@ def _psf_fit_parameters(max_iter, tol, max_step, max_shift):
     return int(max_iter), tol, max_step, max_shift
 
 
+def _psf_width_parameters(max_iter, tol, max_step, min_sigma, max_sigma, sigma0):
+    """The iteration's parameters of ``psf_width``, checked: max_iter an integer 1 .. 64, tol finite and >= 0, max_step > 0,
+    0 < min_sigma <= sigma0 <= max_sigma with both bounds finite; ``sigma0``: (sigma_col, sigma_row) or [B, 2]."""
+    max_iter, tol, _, _ = _psf_fit_parameters(max_iter, tol, 1.0, 1.0)
+    max_step, min_sigma, max_sigma = float(max_step), float(min_sigma), float(max_sigma)
+    if not max_step > 0:
+        raise ValueError("max_step must be > 0 (got %r)" % (max_step,))
+    if not (np.isfinite(min_sigma) and np.isfinite(max_sigma) and min_sigma > 0):
+        raise ValueError("min_sigma and max_sigma must be finite, min_sigma > 0 (got %r and %r)" % (min_sigma, max_sigma))
+    s0 = np.asarray(sigma0, dtype=np.float64)
+    if not (np.all(s0 >= min_sigma) and np.all(s0 <= max_sigma)):
+        raise ValueError("need min_sigma <= sigma0 <= max_sigma (got %r, %r, %r)" % (min_sigma, sigma0, max_sigma))
+    return max_iter, tol, max_step, min_sigma, max_sigma
+
+
+def _psf_width_tables(c, sg, n):
+    """The n pixel factors of ``psf_width`` along one axis at the centres ``c`` (any shape) and the width ``sg``, and their
+    derivatives by ``sg`` -> two arrays c.shape + (n,): (erf(z_{k+1}) - erf(z_k)) / 2 and -(Q(k + 1) - Q(k)), z_k = (k - 1/2 - c) /
+    (sqrt(2) sg), Q(k) = (k - 1/2 - c) exp(-z_k^2) / (sqrt(2 pi) sg^2)."""
+    import math
+    x = np.arange(n + 1) - 0.5 - np.asarray(c, dtype=np.float64)[..., None]
+    z = x / (np.sqrt(2.0) * sg)
+    E, Q = np.vectorize(math.erf, otypes=[np.float64])(z), x * np.exp(-z * z) / (np.sqrt(2.0 * np.pi) * sg * sg)
+    return 0.5 * (E[..., 1:] - E[..., :-1]), -(Q[..., 1:] - Q[..., :-1])
+
+
+def _psf_cholesky(G, scale):
+    """The unpivoted Cholesky of the PSF fits: G (M, k, k), pivot cut 1e-12 scale (M, k) -> L, singular, smallest pivot ratio."""
+    M, k = G.shape[:2]
+    L, singular, ratio = np.zeros((M, k, k)), np.zeros(M, dtype=bool), np.full(M, np.inf)
+    for q in range(k):
+        d = G[:, q, q].copy()
+        for j in range(q):
+            d -= L[:, q, j] * L[:, q, j]
+        singular |= ~(np.isfinite(d) & (d > 1e-12 * scale[:, q]))
+        ratio = np.minimum(ratio, np.where(np.isfinite(d) & (scale[:, q] > 0), d / scale[:, q], 0.0))
+        L[:, q, q] = np.sqrt(d)
+        for i in range(q + 1, k):
+            s_ = G[:, q, i].copy()
+            for j in range(q):
+                s_ -= L[:, i, j] * L[:, q, j]
+            L[:, i, q] = s_ / L[:, q, q]
+    return L, singular, ratio
+
+
+def _psf_forward(L, B):
+    """L^-1 B, B (M, k, m)."""
+    Y = np.zeros_like(B)
+    for i in range(L.shape[1]):
+        s_ = B[:, i].copy()
+        for j in range(i):
+            s_ -= L[:, i, j, None] * Y[:, j]
+        Y[:, i] = s_ / L[:, i, i, None]
+    return Y
+
+
+def _psf_backward(L, Y):
+    """L^-T Y."""
+    X = np.zeros_like(Y)
+    for i in range(L.shape[1] - 1, -1, -1):
+        s_ = Y[:, i].copy()
+        for j in range(i + 1, L.shape[1]):
+            s_ -= L[:, j, i, None] * X[:, j]
+        X[:, i] = s_ / L[:, i, i, None]
+    return X
+
+
 class PixelCube(object):
     """Minimal stand-in for the slice of TargetPixelFile that PLDCorrector touches."""
 
@@ -589,40 +656,7 @@ class PixelCube(object):
             E, P = erf(z), np.exp(-z * z) / (np.sqrt(2.0 * np.pi) * sg)
             return 0.5 * (E[..., 1:] - E[..., :-1]), -(P[..., 1:] - P[..., :-1])
 
-        def cholesky(G, scale):                                  # (M, k, k), pivot cut on scale (M, k) -> L, singular, ratio
-            M, k = G.shape[:2]
-            L, singular, ratio = np.zeros((M, k, k)), np.zeros(M, dtype=bool), np.full(M, np.inf)
-            for q in range(k):
-                d = G[:, q, q].copy()
-                for j in range(q):
-                    d -= L[:, q, j] * L[:, q, j]
-                singular |= ~(np.isfinite(d) & (d > 1e-12 * scale[:, q]))
-                ratio = np.minimum(ratio, np.where(np.isfinite(d) & (scale[:, q] > 0), d / scale[:, q], 0.0))
-                L[:, q, q] = np.sqrt(d)
-                for i in range(q + 1, k):
-                    s_ = G[:, q, i].copy()
-                    for j in range(q):
-                        s_ -= L[:, i, j] * L[:, q, j]
-                    L[:, i, q] = s_ / L[:, q, q]
-            return L, singular, ratio
-
-        def forward(L, B):                                       # L^-1 B, B (M, k, m)
-            Y = np.zeros_like(B)
-            for i in range(L.shape[1]):
-                s_ = B[:, i].copy()
-                for j in range(i):
-                    s_ -= L[:, i, j, None] * Y[:, j]
-                Y[:, i] = s_ / L[:, i, i, None]
-            return Y
-
-        def backward(L, Y):                                      # L^-T Y
-            X = np.zeros_like(Y)
-            for i in range(L.shape[1] - 1, -1, -1):
-                s_ = Y[:, i].copy()
-                for j in range(i + 1, L.shape[1]):
-                    s_ -= L[:, j, i, None] * X[:, j]
-                X[:, i] = s_ / L[:, i, i, None]
-            return X
+        cholesky, forward, backward = _psf_cholesky, _psf_forward, _psf_backward
 
         def evaluate(idx, u):
             """The cadences idx at the shifts u (M, 2) -> theta (M, K), L, L2, g (M, 2), chi2, singular, pivot ratio."""
@@ -708,6 +742,185 @@ class PixelCube(object):
         out.update(flux=flux, flux_err=err, n_used=n_used, cadence_status=cst, status=0 if np.any(cst == 0) else 1,
                    star_index=star_index, min_pivot_ratio=ratio, n_iter=n_iter, last_step=last_step, steps=steps,
                    raw_steps=raw_steps, excursion=excursion)
+        return out
+
+    def psf_width(self, star_col, star_row, sigma0, shifts=None, cadence_mask=None, max_iter=20, tol=1e-6, max_step=0.25,
+                  min_sigma=0.2, max_sigma=5.0, aperture_mask="all", column=0, row=0, use_flux_err=True):
+        """The PSF width of the cutout, fitted: ONE pair v = (sigma_col, sigma_row) shared by every cadence, by variable
+        projection in Kaufman's form with the linear unknowns (the fluxes of up to 8 stars and a background PER CADENCE)
+        projected out (the host mirror of ``DevicePixelCubeBatch.psf_width`` and its definition, float64 numpy after the float32
+        load).  The PSF scale of ``TargetPixelFile.to_lightcurve(method="prf")``; the third step of the chain ``psf_fit(sigma
+        guess)`` -> ``psf_width(shifts=)`` -> ``psf_fit(sigma)`` / ``psf_photometry(sigma, shifts)``.  Stars, ``aperture_mask``,
+        ``column`` / ``row``, the PSF, the used pixels, the weights w, the design A = [g_0 ... g_{S-1}, 1], K = S + 1, the
+        Cholesky and its pivot cut 1e-12 G_kk are those of ``psf_photometry``.  ``shifts``: None or (shift_col[N], shift_row[N]),
+        added to every star's position as in ``psf_photometry``.  ``cadence_mask``: None or bool (N,), the cadences the width
+        is fitted on.  ``sigma0``: a scalar or (sigma_col, sigma_row), the start.
+
+        A cadence is ELIGIBLE when ``cadence_mask`` selects it, its time and its shift are finite and n_used >= S + 2; that
+        does not depend on v.  One EVALUATION at v, per eligible cadence: G = A^T W A, rhs = A^T W y, G = L L^T, theta = G^-1
+        rhs, r = y - A theta; D = [sum_s theta_s dg_s/dsigma_col, sum_s theta_s dg_s/dsigma_row] over the used pixels, where the
+        derivative of a column factor (erf(z_{k+1}) - erf(z_k)) / 2, z_k = (k - 1/2 - c) / (sqrt(2) sigma_col), by sigma_col is
+        -(Q(k + 1) - Q(k)), Q(k) = (k - 1/2 - c) exp(-z_k^2) / (sqrt(2 pi) sigma_col^2), rows likewise; C = A^T W D, E = D^T W
+        D, g_n = D^T W r, S2_n = E - (L^-1 C)^T (L^-1 C), chi2_n = sum w r^2.  A cadence whose G fails a pivot is singular at
+        this evaluation and contributes nothing.  The cutout's sums g = sum g_n, H = sum S2_n, chi2, n_cadences and n_pixels =
+        sum n_used run over the contributing cadences in an order fixed by N alone.
+
+        From v = ``sigma0``, for it = 1 .. ``max_iter``: (1) evaluate at v; (2) n_cadences == 0: status 1, stop; (3) H = L2
+        L2^T by the 2 x 2 unpivoted Cholesky, singular when H_00 is not finite and > 0 or d_11 is not finite and > 1e-12 H_11:
+        status 3, stop; (4) dv = H^-1 g, each component clamped to +-``max_step``; (5) v += dv, n_iter = it, last_step = max
+        |dv|; (6) a component of v not in [``min_sigma``, ``max_sigma``]: status 5, stop; (7) ``tol`` > 0 and last_step <
+        ``tol``: converged.  After ``max_iter`` steps without convergence the status is 4, but ``tol`` = 0 means "exactly
+        ``max_iter`` steps" and is status 0.  A status 0 cutout is evaluated once more at its final v (no cadence there: status
+        1; H singular: status 3), which gives ``sigma`` (2,) = v, ``sigma_err`` (2,) = sqrt((H^-1)_kk) (not scaled by chi2,
+        conditional on the shifts), ``sigma_cov`` = (H^-1)_01, ``chi2``.  A failed cutout is NaN in those four; nothing is
+        raised.  Always returned: ``status``; ``n_cadences`` and ``n_pixels`` (int64) of the last evaluation made; ``n_iter``
+        and ``last_step`` (NaN before the first update); ``trace`` (max_iter + 1, 2): row k is the v of evaluation k + 1, NaN
+        beyond the evaluations made — the final evaluation is made at row n_iter, so a status 0 cutout has n_iter + 1 rows
+        and a v that left the bounds (status 5) is not in it; ``cadence_status`` (N,) int8 from the last evaluation made, in
+        this order of precedence: 6 not selected by ``cadence_mask``, 1 the time or a shift is not finite, 2 n_used < S + 2, 3
+        singular, 0 contributed; ``n_used`` (N,) int32; ``star_index``; and what the tests' preconditions read: ``steps``
+        (max_iter,), ``raw_steps`` (max_iter, 2) before the clamp, ``visited`` (max_iter, 2), v after every update, and
+        ``min_pivot_ratio``, the smallest d_k / G_kk (eligible cadences) or d_k / H_kk of every factorisation made.
+        ``ValueError``: ``max_iter`` outside 1 .. 64, ``tol`` not finite or < 0, ``max_step`` not > 0, not 0 < ``min_sigma`` <=
+        ``sigma0`` <= ``max_sigma`` or a bound not finite."""
+        col, rw = np.atleast_1d(np.asarray(star_col, dtype=np.float64)), np.atleast_1d(np.asarray(star_row, dtype=np.float64))
+        if col.ndim != 1 or col.shape != rw.shape:
+            raise ValueError("star_col and star_row must be 1-D arrays of one length (got %r and %r)" % (col.shape, rw.shape))
+        star_index = np.flatnonzero(~(np.isnan(col) | np.isnan(rw)))
+        col, rw = col[star_index], rw[star_index]
+        S = len(star_index)
+        if not 1 <= S <= 8:
+            raise ValueError("psf_width fits 1 .. 8 stars per cutout (got %d)" % S)
+        if not (np.all(np.isfinite(col)) and np.all(np.isfinite(rw))):
+            raise ValueError("a star position is infinite")
+        v = np.array(_psf_sigma(sigma0))
+        max_iter, tol, max_step, min_sigma, max_sigma = _psf_width_parameters(max_iter, tol, max_step, min_sigma, max_sigma, v)
+        N, ny, nx = self.shape
+        npix, K = ny * nx, S + 1
+        if shifts is None:
+            dc = dr = np.zeros(N)
+        else:
+            if len(shifts) != 2:
+                raise ValueError("shifts must be a pair (shift_col, shift_row)")
+            dc, dr = (np.asarray(a, dtype=np.float64) for a in shifts)
+            if dc.shape != (N,) or dr.shape != (N,):
+                raise ValueError("shifts must be a pair of arrays of one value per cadence (%d)" % N)
+        if cadence_mask is None:
+            selected = np.ones(N, dtype=bool)
+        else:
+            selected = np.asarray(cadence_mask)
+            if selected.dtype != bool or selected.shape != (N,):
+                raise ValueError("cadence_mask must be a bool array of one value per cadence (%d)" % N)
+        ap = self._parse_aperture_mask(aperture_mask).reshape(npix)
+        y32 = np.asarray(self.flux).reshape(N, npix)
+        used = ap[None, :] & np.isfinite(y32)
+        with np.errstate(all="ignore"):
+            if use_flux_err:
+                e32 = np.asarray(self.flux_err).reshape(N, npix)
+                used &= np.isfinite(e32) & (e32 > 0)
+                e = np.where(used, e32, 1).astype(np.float64)
+                w_all = np.where(used, 1.0 / (e * e), 0.0)
+            else:
+                w_all = used.astype(np.float64)
+        y_all = np.where(used, y32, 0).astype(np.float64)
+        n_used = used.sum(axis=1).astype(np.int32)
+        base = np.where(~selected, 6, np.where(~(np.isfinite(self.time) & np.isfinite(dc) & np.isfinite(dr)), 1,
+                                               np.where(n_used < S + 2, 2, 0))).astype(np.int8)
+        idx = np.flatnonzero(base == 0)                         # the eligible cadences
+        w, y, keep = w_all[idx], y_all[idx], used[idx]
+        M = len(idx)
+
+        def evaluate(v):
+            """-> g (2,), H (2, 2), chi2, n_cadences, n_pixels, cadence_status (N,), the smallest pivot ratio of G."""
+            g_col, d_col = _psf_width_tables(col[:, None] + dc[None, idx] - column, v[0], nx)
+            g_row, d_row = _psf_width_tables(rw[:, None] + dr[None, idx] - row, v[1], ny)
+            A, Ac, Ar = np.empty((M, npix, K)), np.empty((M, npix, S)), np.empty((M, npix, S))
+            for s in range(S):
+                A[:, :, s] = (g_col[s][:, None, :] * g_row[s][:, :, None]).reshape(M, npix)
+                Ac[:, :, s] = (d_col[s][:, None, :] * g_row[s][:, :, None]).reshape(M, npix)
+                Ar[:, :, s] = (g_col[s][:, None, :] * d_row[s][:, :, None]).reshape(M, npix)
+            A[:, :, S] = 1.0
+            A = np.where(keep[:, :, None], A, 0.0)
+            WA = A * w[:, :, None]
+            G = np.einsum("npi,npj->nij", WA, A)
+            L, singular, ratio = _psf_cholesky(G, np.einsum("nii->ni", G))
+            theta = _psf_backward(L, _psf_forward(L, np.einsum("npi,np->ni", WA, y)[:, :, None]))[:, :, 0]
+            res = y - np.einsum("npi,ni->np", A, theta)
+            D = np.stack([np.einsum("nps,ns->np", Ac, theta[:, :S]), np.einsum("nps,ns->np", Ar, theta[:, :S])], axis=2)
+            D = np.where(keep[:, :, None], D, 0.0)
+            WD = D * w[:, :, None]
+            Y = _psf_forward(L, np.einsum("npi,npj->nij", A, WD))
+            S2 = np.einsum("npi,npj->nij", WD, D) - np.einsum("nki,nkj->nij", Y, Y)
+            ok = ~singular
+            cst = base.copy()
+            cst[idx[singular]] = 3
+            return dict(g=np.where(ok[:, None], np.einsum("npi,np->ni", WD, res), 0.0).sum(axis=0),
+                        H=np.where(ok[:, None, None], S2, 0.0).sum(axis=0), chi2=np.where(ok, np.sum(w * res * res, axis=1), 0.0).sum(),
+                        n_cadences=int(ok.sum()), n_pixels=int(n_used[idx][ok].sum()), cadence_status=cst,
+                        ratio=ratio.min() if M else np.inf)
+
+        def factor(H):                                           # the 2 x 2 Cholesky -> l00, l10, l11, singular, pivot ratio
+            singular = not (np.isfinite(H[0, 0]) and H[0, 0] > 0)
+            l00 = np.sqrt(H[0, 0])
+            l10 = H[0, 1] / l00
+            d11 = H[1, 1] - l10 * l10
+            singular = singular or not (np.isfinite(d11) and d11 > 1e-12 * H[1, 1])
+            return l00, l10, np.sqrt(d11), singular, d11 / H[1, 1] if np.isfinite(d11) and H[1, 1] > 0 else 0.0
+
+        n_iter, last_step, status = 0, np.nan, 4
+        trace = np.full((max_iter + 1, 2), np.nan)
+        steps, raw_steps, visited = np.full(max_iter, np.nan), np.full((max_iter, 2), np.nan), np.full((max_iter, 2), np.nan)
+        ratio = np.inf
+        out = dict(sigma=np.full(2, np.nan), sigma_err=np.full(2, np.nan), sigma_cov=np.nan, chi2=np.nan)
+        with np.errstate(all="ignore"):
+            for it in range(1, max_iter + 1):
+                ev = evaluate(v)
+                trace[it - 1] = v
+                ratio = min(ratio, ev["ratio"])
+                if ev["n_cadences"] == 0:
+                    status = 1
+                    break
+                l00, l10, l11, singular, r2 = factor(ev["H"])
+                ratio = min(ratio, r2)
+                if singular:
+                    status = 3
+                    break
+                z0 = ev["g"][0] / l00
+                z1 = (ev["g"][1] - l10 * z0) / l11
+                dv1 = z1 / l11
+                dv = np.array([(z0 - l10 * dv1) / l00, dv1])
+                raw_steps[it - 1] = dv
+                dv = np.where(dv > max_step, max_step, np.where(dv < -max_step, -max_step, dv))
+                v = v + dv
+                n_iter, visited[it - 1] = it, v
+                last_step = steps[it - 1] = abs(dv[0]) if abs(dv[0]) > abs(dv[1]) else abs(dv[1])
+                if not (np.all(v >= min_sigma) and np.all(v <= max_sigma)):
+                    status = 5
+                    break
+                if tol > 0 and last_step < tol:
+                    status = 0
+                    break
+            if status == 4 and tol == 0:
+                status = 0
+            if status == 0:
+                ev = evaluate(v)
+                trace[n_iter] = v
+                ratio = min(ratio, ev["ratio"])
+                if ev["n_cadences"] == 0:
+                    status = 1
+                else:
+                    l00, l10, l11, singular, r2 = factor(ev["H"])
+                    ratio = min(ratio, r2)
+                    if singular:
+                        status = 3
+                    else:
+                        m00, m11 = 1.0 / l00, 1.0 / l11
+                        m10 = -l10 * m00 * m11
+                        out = dict(sigma=v.copy(), sigma_err=np.array([np.sqrt(m00 * m00 + m10 * m10), m11]), sigma_cov=m10 * m11,
+                                   chi2=float(ev["chi2"]))
+        out.update(status=status, n_cadences=ev["n_cadences"], n_pixels=ev["n_pixels"], n_iter=n_iter, last_step=float(last_step),
+                   trace=trace, cadence_status=ev["cadence_status"], n_used=n_used, star_index=star_index, steps=steps,
+                   raw_steps=raw_steps, visited=visited, min_pivot_ratio=float(ratio))
         return out
 
     def pixel_periodogram(self, frequency, normalization="amplitude", freq_unit=None, oversample_factor=None):

@@ -2350,6 +2350,21 @@ int lk_cube_psf_fit_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const 
                                   shift_row_err, last_step, n_iter, n_used, cadence_status, status, static_cast<hipStream_t>(stream));
 }
 
+int lk_cube_psf_width_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
+                                const float *flux_err, const uint8_t *mask, int mask_stride, int S_max, const double *star_col,
+                                const double *star_row, const double *sigma0, const double *shift_col, const double *shift_row,
+                                const uint8_t *cadence_mask, int max_iter, double tol, double max_step, double min_sigma,
+                                double max_sigma, double column0, double row0, int use_flux_err, double *sigma, double *sigma_err,
+                                double *sigma_cov, double *chi2, double *last_step, double *trace, int32_t *n_iter,
+                                int32_t *n_cadences, int64_t *n_pixels, int8_t *cadence_status, int32_t *status, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_psfwidth_launch(h, B, N, ny, nx, time, flux, flux_err, mask, mask_stride, S_max, star_col, star_row, sigma0,
+                                    shift_col, shift_row, cadence_mask, max_iter, tol, max_step, min_sigma, max_sigma, column0, row0,
+                                    use_flux_err, sigma, sigma_err, sigma_cov, chi2, last_step, trace, n_iter, n_cadences, n_pixels,
+                                    cadence_status, status, static_cast<hipStream_t>(stream));
+}
+
 int lk_sff_scratch_bytes(int B, const int64_t *n_off, const int32_t *n_knots, const int32_t *win_off, int bins, int degree,
                          int64_t max_scratch_bytes, int64_t *bytes, int *n_chunks) {
     return lk::sff_scratch_bytes(B, n_off, n_knots, win_off, bins, degree, max_scratch_bytes, bytes, n_chunks);

@@ -451,6 +451,16 @@ int cube_psffit_launch(lk_handle *h, int B, int N, int ny, int nx, const double 
                        double *time_out, double *flux_out, double *flux_err_out, double *background, double *chi2, double *shift_col,
                        double *shift_row, double *shift_col_err, double *shift_row_err, double *last_step, int32_t *n_iter,
                        int32_t *n_used, int8_t *cadence_status, int32_t *status, hipStream_t stream);
+// psfwidth.hip: the PSF width (sigma_col, sigma_row) of every cutout, shared by its cadences, by variable projection from sigma0
+// (host array) at given shifts (nullable device arrays) on the cadences of cadence_mask (nullable device bytes): max_iter + 1
+// pairs of an evaluate and a step kernel.  Everything but the stars and sigma0 on the device; enqueued, no synchronisation
+int cube_psfwidth_launch(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux, const float *flux_err,
+                         const uint8_t *mask, int mask_stride, int S_max, const double *star_col_host, const double *star_row_host,
+                         const double *sigma0_host, const double *shift_col, const double *shift_row, const uint8_t *cadence_mask,
+                         int max_iter, double tol, double max_step, double min_sigma, double max_sigma, double column0, double row0,
+                         int use_flux_err, double *sigma, double *sigma_err, double *sigma_cov, double *chi2, double *last_step,
+                         double *trace, int32_t *n_iter, int32_t *n_cadences, int64_t *n_pixels, int8_t *cadence_status,
+                         int32_t *status, hipStream_t stream);
 // sff.hip: SFFCorrector for a ragged resident batch.  The regression launcher owns h->ws, so the design matrices and everything
 // else that lives across it sit in `scratch`, a device block of the caller's (sff_scratch_bytes); status_host is valid on
 // return (the call synchronises once, to group the targets by their design width)

@@ -1,6 +1,7 @@
-// psf_common.hpp — what psfphot.hip (fluxes at given positions) and psffit.hip (fluxes and a common shift per cadence) share:
-// the cadence-per-four-lanes mapping, the Gaussian's edge integral, the sum over a cadence's lanes, the Cholesky without
-// pivoting with its singularity test, and the host-side grouping of a batch's cutouts by their star count.
+// psf_common.hpp — what psfphot.hip (fluxes at given positions), psffit.hip (fluxes and a common shift per cadence) and
+// psfwidth.hip (the width of a cutout) share: the cadence-per-four-lanes mapping, the Gaussian's edge integral, the sums over a
+// cadence's lanes, a tile's cadences and a wavefront, the Cholesky without pivoting with its singularity test, and the host-side
+// grouping of a batch's cutouts by their star count.
 #pragma once
 #include <cmath>
 #include <vector>
@@ -23,6 +24,21 @@ __device__ __forceinline__ double psf_edge(int k, double c, double den) { return
 template <class T> __device__ __forceinline__ T psf_cadence_sum(T v) {
 #pragma unroll
     for (int o = 1; o < PSF_LPC; o <<= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// the sum over the PSF_T cadences of a tile of a value that the PSF_LPC lanes of each cadence already share (psf_cadence_sum):
+// the butterfly across the cadences, the same bits in every lane and an order that depends on nothing
+template <class T> __device__ __forceinline__ T psf_tile_sum(T v) {
+#pragma unroll
+    for (int o = PSF_LPC; o < 64; o <<= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// the sum of v over the 64 lanes of a wavefront by the same butterfly
+template <class T> __device__ __forceinline__ T psf_wave_sum(T v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
     return v;
 }
 

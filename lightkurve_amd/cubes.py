@@ -63,6 +63,14 @@ def _psf_info_spec(B, N, spec):
     return [(key, dt, (B if key == "status" else B * N) * np.dtype(dt).itemsize) for key, dt in spec]
 
 
+def _psf_width_spec(B, N, max_iter):
+    """(key, dtype, shape) of every output of ``psf_width``."""
+    return [("sigma", np.float64, (B, 2)), ("sigma_err", np.float64, (B, 2)), ("sigma_cov", np.float64, (B,)),
+            ("chi2", np.float64, (B,)), ("last_step", np.float64, (B,)), ("trace", np.float64, (B, max_iter + 1, 2)),
+            ("n_iter", np.int32, (B,)), ("n_cadences", np.int32, (B,)), ("n_pixels", np.int64, (B,)),
+            ("cadence_status", np.int8, (B, N)), ("status", np.int32, (B,))]
+
+
 class DevicePixelCubeBatch(object):
     """B same-shaped target-pixel cutouts IN HBM — the input of ``PLDCorrector`` as ``DeviceLightCurveBatch`` is the input of
     the light-curve chain: ``d_flux`` / ``d_flux_err`` float32 [B][N][npix] (npix = ny * nx, row-major pixels: the layout
@@ -817,6 +825,67 @@ class DevicePixelCubeBatch(object):
             _p(info["cadence_status"]), _p(info["status"]), _vp(self.stream or None)))
         return self._psf_results(pos, part, (d_t, d_f, d_e), keep + [d for d in d_shift if d is not None], info, _PSF_FIT_INFO,
                                  star_off, to_host)
+
+    def psf_width(self, star_col, star_row, sigma0, shifts=None, cadence_mask=None, max_iter=20, tol=1e-6, max_step=0.25,
+                  min_sigma=0.2, max_sigma=5.0, aperture_mask="all", column=0, row=0, use_flux_err=True, to_host=True):
+        """The PSF width of every cutout, fitted: ONE pair (sigma_col, sigma_row) per cutout, shared by all its cadences, by
+        variable projection with every cadence's fluxes and background projected out (``lk_cube_psf_width_batch_dev``; the numpy
+        mirror and the definition is ``PixelCube.psf_width``) — the ``sigma`` that ``psf_photometry`` and ``psf_fit`` take as
+        given, the PSF scale of ``TargetPixelFile.to_lightcurve(method="prf")``.  The chain that calibrates itself::
+
+            _, fit = cubes.psf_fit(star_col, star_row, sigma_guess)
+            info = cubes.psf_width(star_col, star_row, sigma_guess, shifts=(fit["shift_col"], fit["shift_row"]))
+            lcs, fit = cubes.psf_fit(star_col, star_row, info["sigma"])
+
+        Stars, ``aperture_mask``, ``column`` / ``row`` and ``use_flux_err`` as in ``psf_photometry``.  ``sigma0``: a scalar,
+        (sigma_col, sigma_row) or [B, 2], the start.  ``shifts``: None or a pair (shift_col, shift_row) of host arrays [B, N]
+        or of ``DeviceBuffer``s of B x N float64 (what ``psf_fit`` returns; a cadence with a NaN shift is left out).
+        ``cadence_mask``: None, a bool host array [B, N] or a ``DeviceBuffer`` of B x N bytes, the cadences to fit on — every
+        tenth, say.  Up to ``max_iter`` (1 .. 64) Gauss-Newton steps per cutout, each component clamped to +-``max_step``; a
+        cutout stops when its step is below ``tol`` (``tol`` = 0: exactly ``max_iter`` steps) and fails when a width leaves
+        [``min_sigma``, ``max_sigma``].  Returns a dict: ``sigma`` and ``sigma_err`` (B, 2), ``sigma_cov``, ``chi2`` and
+        ``last_step`` (B,) float64; ``trace`` (B, max_iter + 1, 2), the widths of every evaluation made, NaN beyond; ``n_iter``
+        and ``n_cadences`` (B,) int32, ``n_pixels`` (B,) int64; ``cadence_status`` (B, N) int8: 0 contributed, 1 the time or a
+        shift is not finite, 2 n_used < S + 2, 3 singular, 6 not selected; ``status`` (B,) int32: 0 ok, 1 no cadence
+        contributed, 3 singular, 4 not converged, 5 left the bounds — a cutout that is not ok is NaN in ``sigma``,
+        ``sigma_err``, ``sigma_cov`` and ``chi2``; nothing is raised per cutout.  Numpy arrays with ``to_host=True`` (16 bytes
+        of widths per cutout), ``DeviceBuffer``s enqueued on the batch's stream with ``to_host=False``.  A cutout's outputs
+        have the same bits alone, at any batch position and from run to run."""
+        from .correctors.pldcorrector import _psf_width_parameters
+        h, (B, N, ny, nx) = self.handle, self.shape
+        pos, part, sg, S_max = _psf_stars(B, star_col, star_row, sigma0)
+        max_iter, tol, max_step, min_sigma, max_sigma = _psf_width_parameters(max_iter, tol, max_step, min_sigma, max_sigma, sg)
+        keep = []
+        d_shift = self._psf_shift_buffers(shifts, "shifts", keep)
+        d_cmask = None
+        if isinstance(cadence_mask, DeviceBuffer):
+            if cadence_mask.nbytes != B * N:
+                raise ValueError("a cadence_mask buffer of %d bytes for %d x %d cadences" % (cadence_mask.nbytes, B, N))
+            d_cmask = cadence_mask
+        elif cadence_mask is not None:
+            cm = np.asarray(cadence_mask)
+            if cm.dtype != bool or cm.shape != (B, N):
+                raise ValueError("cadence_mask must be a bool (B, N) = %r array (got %s %r)" % ((B, N), cm.dtype, cm.shape))
+            d_cmask, k = _upload(h, cm.astype(np.uint8), self.stream, np.uint8)
+            keep.append(k)
+        _, d_mask, stride, _ = self._stage_mask(aperture_mask, False)           # kept in self._keep
+        spec = _psf_width_spec(B, N, max_iter)
+        out = {key: DeviceBuffer(h, int(np.prod(shape)) * np.dtype(dt).itemsize) for key, dt, shape in spec}
+        _capi._check(_capi._lib.lk_cube_psf_width_batch_dev(
+            h._h, B, N, ny, nx, _p(self.d_time), _p(self.d_flux), _p(self.d_flux_err), _p(d_mask), stride, S_max,
+            pos[0].ctypes.data_as(_dp), pos[1].ctypes.data_as(_dp), sg.ctypes.data_as(_dp), _p(d_shift[0]), _p(d_shift[1]),
+            _p(d_cmask), max_iter, tol, max_step, min_sigma, max_sigma, float(column), float(row), int(bool(use_flux_err)),
+            _p(out["sigma"]), _p(out["sigma_err"]), _p(out["sigma_cov"]), _p(out["chi2"]), _p(out["last_step"]), _p(out["trace"]),
+            _p(out["n_iter"]), _p(out["n_cadences"]), _p(out["n_pixels"]), _p(out["cadence_status"]), _p(out["status"]),
+            _vp(self.stream or None)))
+        keep += [d for d in d_shift if d is not None] + ([d_cmask] if d_cmask is not None else [])
+        if not to_host:
+            self._keep = self._keep + keep                              # what the enqueued fit still reads
+            return out
+        for key, dt, shape in spec:
+            out[key] = self._get(out[key], dt, shape)
+        self._keep = []
+        return out
 
     def _psf_shift_buffers(self, shifts, name, keep):
         """``shifts`` / ``shifts0`` of the PSF calls -> [shift_col, shift_row] on the device (None, None without): a pair of

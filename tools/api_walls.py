@@ -146,6 +146,15 @@ shifts uniform in +-0.3 px, in ONE process, the routes alternating, `LK_WALLS_RE
 Every timed region ends with a synchronise.  Written to profiles/psffit_walls.txt.  `psffit_trace`: F and Rs twice and nothing
 else, for `rocprofv3 --kernel-trace --stats` (profiles/psffit_kernel_stats.txt).
 
+`psfwidth`: the fit of the PSF width per cutout on the same batch shape and star count, the cubes rendered with true shifts uniform
+in +-0.3 px (given to the fit) and a true width of 1.1 px, `sigma0` 15 % off (1.15 x the truth in columns, 0.85 x in rows), in ONE
+process, the routes alternating, `LK_WALLS_REPS` (default 5) times after one warm-up.  W `cubes.psf_width(star_col, star_row,
+sigma0, shifts=)` with the defaults; Wm the same with a `cadence_mask` that selects every tenth cadence; Rs
+`cubes.psf_photometry` of the same cubes at the same shifts (one evaluation pass should cost about one such call); H the mirror
+`PixelCube.psf_width` per cutout on 16 threads over the first `LK_WALLS_MIRROR_B` (default 16) cutouts.  Every timed region ends
+with a synchronise.  Written to profiles/psfwidth_walls.txt.  `psfwidth_trace`: W, Wm, Wb and Rs twice and nothing else, for `rocprofv3
+--kernel-trace --stats` (profiles/psfwidth_kernel_stats.txt).
+
 `background`: the per-cadence background of the same batch shape with 'background' masks, in ONE process, the routes alternating,
 `LK_WALLS_REPS` (default 5) times after one warm-up.  F `cubes.subtract_background()` (median images, masks, the fused estimate +
 subtraction) and Fm the same with the masks given; E `cubes.estimate_background()`, Em with the masks given, Es with the scatter
@@ -1574,6 +1583,110 @@ def psffit(which):
         "profiles/psffit_kernel_stats.txt" % (med["F"] / med["Rs"], med["F"] / med["Rs"] / evals, B, med["H"] * B / Bm / med["F"])])
 
 
+def psfwidth(which):
+    from concurrent.futures import ThreadPoolExecutor
+    from scipy.special import erf
+    from lightkurve_amd.device import DevicePixelCubeBatch
+    B, N, side, S = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "500"), ("LK_WALLS_N", "4000"), ("LK_WALLS_SIDE", "11"),
+                                                            ("LK_WALLS_STARS", "4")))
+    reps, Bm = int(os.environ.get("LK_WALLS_REPS", "5")), min(B, int(os.environ.get("LK_WALLS_MIRROR_B", "16")))
+    rng = np.random.default_rng(71)
+    npix = side * side
+    t = 1000.0 + np.arange(N) / 720.0                                    # two-minute cadences
+    sigma, sigma0 = 1.1, (1.1 * 1.15, 1.1 * 0.85)                        # the truth; the start, 15 % off on either side
+    cells = int(np.ceil(np.sqrt(S)))
+    lattice = np.array([((i + 0.5) * side / cells - 0.5, (j + 0.5) * side / cells - 0.5) for j in range(cells) for i in range(cells)][:S])
+    col = lattice[None, :, 0] + rng.uniform(-0.3, 0.3, (B, S))
+    row = lattice[None, :, 1] + rng.uniform(-0.3, 0.3, (B, S))
+    shifts = (rng.uniform(-0.3, 0.3, (B, N)), rng.uniform(-0.3, 0.3, (B, N)))     # the true pointing of every cadence, given
+    edges = np.arange(side + 1) - 0.5
+    flux = np.empty((B, N, side, side), dtype=np.float32)
+    for b in range(B):                                                  # every cadence rendered at its own shift
+        gx = np.diff(erf((edges[None, None, :] - col[b][None, :, None] - shifts[0][b][:, None, None]) / (np.sqrt(2) * sigma)), axis=2) / 2
+        gy = np.diff(erf((edges[None, None, :] - row[b][None, :, None] - shifts[1][b][:, None, None]) / (np.sqrt(2) * sigma)), axis=2) / 2
+        img = 100.0 + np.einsum("s,nsy,nsx->nyx", rng.uniform(2000.0, 20000.0, S), gy, gx)
+        flux[b] = img.astype(np.float32) + 3.0 * rng.standard_normal((N, side, side), dtype=np.float32)
+    err = np.full_like(flux, 3.0)
+    cubes = DevicePixelCubeBatch.from_arrays(np.tile(t, (B, 1)), flux, err)
+    cubes.synchronize()
+    del flux, err
+    d_shifts = tuple(_upload_f64(cubes, a) for a in shifts)
+    tenth = np.zeros((B, N), dtype=bool)
+    tenth[:, ::10] = True
+    from lightkurve_amd.devmem import _upload
+    d_tenth, keep = _upload(cubes.handle, tenth.astype(np.uint8), cubes.stream, np.uint8)
+    block = np.zeros((B, N), dtype=bool)
+    block[:, :N // 10] = True                                            # as many cadences, in whole tiles
+    d_block, keep2 = _upload(cubes.handle, block.astype(np.uint8), cubes.stream, np.uint8)
+    cubes.synchronize()
+    del keep, keep2
+
+    def width(mask=None):
+        out = cubes.psf_width(col, row, sigma0, shifts=d_shifts, cadence_mask=mask, to_host=False)
+        cubes.synchronize()
+        return out
+
+    def given():
+        out = cubes.psf_photometry(col, row, sigma0, shifts=d_shifts)
+        cubes.synchronize()
+        return out
+
+    if "psfwidth_trace" in which:
+        for _ in range(2):
+            width()
+            width(d_tenth)
+            width(d_block)
+            given()
+        return
+
+    host_m = cubes.to_host()[:Bm]
+
+    def mirror():
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            return list(ex.map(lambda b: host_m[b].psf_width(col[b], row[b], sigma0, shifts=(shifts[0][b], shifts[1][b])), range(Bm)))
+
+    fns = {"W": width, "Wm": lambda: width(d_tenth), "Wb": lambda: width(d_block), "Rs": given, "H": mirror}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    get = lambda out, k, dt, shape: out[k].download(dt, int(np.prod(shape)), stream=cubes.stream).reshape(shape)
+    res = {k: (get(first[k], "status", np.int32, (B,)), get(first[k], "n_iter", np.int32, (B,)), get(first[k], "sigma", np.float64, (B, 2)),
+               get(first[k], "sigma_err", np.float64, (B, 2))) for k in ("W", "Wm", "Wb")}
+    status, n_iter, sg, sg_err = res["W"]
+    h_sigma = np.stack([o["sigma"] for o in first["H"]])
+    rel = float(np.max(np.abs(sg[:Bm] - h_sigma)))
+    same_iter = bool(np.array_equal(n_iter[:Bm], [o["n_iter"] for o in first["H"]]))
+    first.clear()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    evals = int(n_iter.max()) + 1                                        # passes in which a tile of the batch still works
+    evals_m = int(res["Wm"][1].max()) + 1
+    write_walls("psfwidth_walls.txt", [
+        "PSF width per cutout, %d cutouts x %d cadences x %d x %d float32, %d stars per cutout, true sigma %.1f px, sigma0 (%.3f, %.3f), "
+        "true shifts uniform in +-0.3 px given (%.1f MB of flux and flux_err resident, read once per evaluation)"
+        % (B, N, side, side, S, sigma, sigma0[0], sigma0[1], B * N * npix * 8 / 1e6),
+        "  W    cubes.psf_width(star_col, star_row, sigma0, shifts=(DeviceBuffer, DeviceBuffer)), defaults; everything resident  %s" % spread(ts["W"]),
+        "  Wm   the same with cadence_mask = every tenth cadence (DeviceBuffer)                                                 %s" % spread(ts["Wm"]),
+        "  Wb   the same with cadence_mask = the first tenth of the cadences: the other tiles are left out entirely             %s" % spread(ts["Wb"]),
+        "  Rs   cubes.psf_photometry(star_col, star_row, sigma0, shifts=) at the same shifts, the same run                      %s" % spread(ts["Rs"]),
+        "  H    PixelCube.psf_width on 16 threads, the first %d cutouts only                                                    %s" % (Bm, spread(ts["H"])),
+        "  W: statuses %s; updates per cutout: mean %.2f, max %d; evaluations made by the slowest cutout (updates + the final one): %d of "
+        "the %d passes enqueued" % (dict(zip(*(a.tolist() for a in np.unique(status, return_counts=True)))), float(n_iter.mean()),
+                                    int(n_iter.max()), evals, 21),
+        "  Wm: statuses %s; evaluations made by the slowest cutout: %d"
+        % (dict(zip(*(a.tolist() for a in np.unique(res["Wm"][0], return_counts=True)))), evals_m),
+        "  largest |fitted - true sigma| %.5f px (W), %.5f px (Wm); mean sigma_err %.5f px (W), %.5f px (Wm); first %d cutouts against the "
+        "mirror: max |sigma difference| %.2e px, the same n_iter: %s"
+        % (float(np.nanmax(np.abs(sg - sigma))), float(np.nanmax(np.abs(res["Wm"][2] - sigma))), float(np.nanmean(sg_err)),
+           float(np.nanmean(res["Wm"][3])), Bm, rel, same_iter),
+        "  Wb: statuses %s; evaluations made by the slowest cutout: %d; W / Wb = %.2f"
+        % (dict(zip(*(a.tolist() for a in np.unique(res["Wb"][0], return_counts=True)))), int(res["Wb"][1].max()) + 1, med["W"] / med["Wb"]),
+        "  W / Rs = %.2f (%.2f per evaluation made); Wm / Rs = %.2f; H scaled to %d cutouts / W = %.0f; kernel times alone: "
+        "profiles/psfwidth_kernel_stats.txt" % (med["W"] / med["Rs"], med["W"] / med["Rs"] / evals, med["Wm"] / med["Rs"], B,
+                                                med["H"] * B / Bm / med["W"])])
+
+
 def _upload_f64(cubes, a):
     from lightkurve_amd.devmem import _upload
     buf, keep = _upload(cubes.handle, np.ascontiguousarray(a, dtype=np.float64), cubes.stream, np.float64)
@@ -1820,6 +1933,8 @@ def main():
         psfphot(which)
     if {"psffit", "psffit_trace"} & set(which):
         psffit(which)
+    if {"psfwidth", "psfwidth_trace"} & set(which):
+        psfwidth(which)
     if {"pixelpg", "pixelpg_trace"} & set(which):
         pixelpg(which)
     if {"stitch", "stitch_trace"} & set(which):
