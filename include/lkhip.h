@@ -1400,6 +1400,76 @@ int lk_cube_psf_width_batch_dev(lk_handle *h, int B, int N, int ny, int nx, cons
                                 double *sigma_cov, double *chi2, double *last_step, double *trace, int32_t *n_iter,
                                 int32_t *n_cadences, int64_t *n_pixels, int8_t *cadence_status, int32_t *status, void *stream);
 
+/* lk_cube_psf_positions_batch_dev <- the positions of every cutout's stars, fitted (PixelCube.psf_positions is the numpy mirror and
+ *   the definition): ONE (column, row) per fitted star, shared by all the cutout's cadences, by variable projection in Kaufman's
+ *   form with the linear unknowns (the fluxes of up to 8 stars and one background PER CADENCE) projected out.  The last unknown of
+ *   TargetPixelFile.to_lightcurve(method="prf") that the calls above take as given; the chain is lk_cube_psf_fit_batch_dev(a
+ *   guess) -> this call at the fitted shifts -> lk_cube_psf_width_batch_dev at the same shifts -> lk_cube_psf_fit_batch_dev or
+ *   lk_cube_psf_photometry_batch_dev.  THE FIT IS CONDITIONAL ON THE SHIFTS (and the width): a translation common to all stars
+ *   is the same model as a constant added to every shift; the call never frees both, and fit_star can pin an anchor star.
+ *   Inputs, stars (NaN = an empty slot), mask, sigma (HOST [B][2], given and not fitted), PSF, used pixels, weights, design A =
+ *   [g_0 ... g_{S-1}, 1], K = S + 1, the Cholesky and its pivot cut 1e-12 G_kk are those of lk_cube_psf_photometry_batch_dev;
+ *   shift_col / shift_row and cadence_mask those of lk_cube_psf_width_batch_dev.  fit_star (nullable): HOST array [B][S_max]
+ *   uint8 in the caller's slot layout, non-zero = the star of that slot is fitted; NULL = every star present is fitted.  A star
+ *   that is not fitted stays at its given position.
+ *   The unknowns v are (column, row) of the fitted stars in slot order, v[2j] the column and v[2j + 1] the row of the j-th
+ *   fitted star, P = 2 x their number <= 16; v starts at the given positions.  A cadence is ELIGIBLE when cadence_mask selects
+ *   it, its time and its shift are finite and n_used >= S + 2; that does not depend on v.  One EVALUATION at v, per eligible
+ *   cadence n: G = A^T W A, rhs = A^T W y, G = L L^T, theta = G^-1 rhs, r = y - A theta; D has one column per unknown, for star s
+ *   theta_s (dg_s^col/dc) g_s^row and theta_s g_s^col (dg_s^row/dc) over the used pixels, the derivative of a factor (erf(z_{k+1})
+ *   - erf(z_k)) / 2, z_k = (k - 1/2 - c) / (sqrt(2) sigma), by its centre c being -(P(k + 1) - P(k)), P(k) = exp(-z_k^2) /
+ *   (sqrt(2 pi) sigma) (lk_cube_psf_fit_batch_dev's derivative by the shift: a shift and a centre enter as one sum); C = A^T W D
+ *   (K x P), E = D^T W D, g_n = D^T W r, S2_n = E - (L^-1 C)^T (L^-1 C), chi2_n = sum w r^2.  A cadence whose G fails a pivot is
+ *   singular at this evaluation and contributes nothing.  The cutout's sums g = sum g_n, H = sum S2_n, chi2 = sum chi2_n,
+ *   n_cadences and n_pixels = sum n_used run over the contributing cadences in an order fixed by N alone.
+ *   Per cutout, for it = 1 .. max_iter:
+ *     1. evaluate at v;
+ *     2. n_cadences == 0: status 1, stop;
+ *     3. H = L2 L2^T by the P x P Cholesky without pivoting; singular when a pivot d_k is not finite and > 1e-12 H_kk: status 3,
+ *        stop;
+ *     4. dv = H^-1 g, each component clamped to +-max_step;
+ *     5. v += dv, n_iter = it, last_step = max |dv| after the clamp;
+ *     6. a component of v farther than max_offset from its start: status 5, stop;
+ *     7. tol > 0 and last_step < tol: converged, stop.
+ *   After max_iter steps without convergence the status is 4; tol == 0 means "take exactly max_iter steps" and is status 0.  A
+ *   status 0 cutout is evaluated once more at its final v (no cadence there: status 1; H singular: status 3) for the outputs,
+ *   all in the caller's slot layout: star_col_out / star_row_out [B][S_max]: the fitted values, the given value bit for bit for
+ *   a star that is not fitted, NaN in an empty slot; star_col_err / star_row_err [B][S_max] = sqrt((H^-1)_kk) (not scaled by
+ *   chi2, conditional on the shifts and the width), NaN where the star is not fitted; position_cov [B][2 S_max][2 S_max] = H^-1
+ *   at index 2 slot + axis, NaN rows and columns where the star is not fitted; chi2 [B].  A failed cutout is NaN in the fitted
+ *   stars' positions, their errors, position_cov and chi2; nothing is raised.
+ *   Written for every cutout: status [B] int32; n_iter [B] int32 (the updates made); last_step [B] float64 (NaN before the first
+ *   update); n_cadences [B] int32 and n_pixels [B] int64 of the last evaluation made; trace [B][max_iter + 1][2 S_max] float64:
+ *   row k holds the positions of evaluation k + 1 at index 2 slot + axis (a star that is not fitted at its given value, NaN in an
+ *   empty slot), NaN beyond the evaluations made — the final evaluation is made at, and rewrites, row n_iter, so a status 0
+ *   cutout has n_iter + 1 rows that are not NaN, a failed one the points it evaluated, and a v that left max_offset (status 5)
+ *   is not in it; cadence_status [B][N] int8 from the last evaluation made, in this order of precedence: 6 not selected by
+ *   cadence_mask, 1 the time or a shift is not finite, 2 n_used < S + 2, 3 singular, 0 contributed.
+ *   LK_EINVAL: where lk_cube_psf_width_batch_dev returns it for the arguments they share, with this call's LDS bound: 16 x 8
+ *   pitch + npix + 2 x 16 x 8 S_max (nx + ny) + 16 x 8 (S_max + 1) 2 S_max bytes (the tile, a factor and a derivative table per
+ *   cadence, and the parked L^-1 C) must not exceed 160 KiB; max_offset not > 0; a cutout without a fitted star; nothing is
+ *   launched then.
+ *   Two kernels per evaluation, enqueued max_iter + 1 times with no synchronisation and no host read in between.  Evaluate: one
+ *   wavefront per tile of 16 cadences, four lanes per cadence, instantiated on S, the staging, the tables and walk 1 of
+ *   lk_cube_psf_fit_batch_dev; it reads v from the cutout's state record and returns at once when the cutout has stopped, and
+ *   a tile that cadence_mask leaves out entirely is not read; all 2 S columns are evaluated (the Schur complement over the fitted
+ *   subset is the submatrix of S2), walk 2 once per star in panels of two rows of E with L^-1 C parked in LDS; the tile's 16
+ *   cadences are added entry by entry by a fixed butterfly (a cadence that does not contribute enters as +0) into one record per
+ *   tile, P + P (P + 1) / 2 + 1 doubles (P = 2 S) stored entry-major, and two 64-bit counts.  Step: one wavefront per cutout adds
+ *   every entry lane-strided over the tile records in index order and then by the butterfly, selects the fitted rows and columns,
+ *   factors H, applies the rules above and advances the state.  No atomics; a cutout's outputs have the same bits alone, at any
+ *   batch position, with any other cutouts in the batch and from run to run.  Scratch: B x ceil(N / 16) x (8 (2 S_max + S_max (2
+ *   S_max + 1) + 1) + 16) bytes of tile records, 152 B of state, B x ((2 S_max + 2) x 8 + 12 + 4 S_max) of the stars, of the
+ *   handle's arena.  Enqueued, no synchronisation. */
+int lk_cube_psf_positions_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
+                                    const float *flux_err, const uint8_t *mask, int mask_stride, int S_max, const double *star_col,
+                                    const double *star_row, const double *sigma, const uint8_t *fit_star, const double *shift_col,
+                                    const double *shift_row, const uint8_t *cadence_mask, int max_iter, double tol, double max_step,
+                                    double max_offset, double column0, double row0, int use_flux_err, double *star_col_out,
+                                    double *star_row_out, double *star_col_err, double *star_row_err, double *position_cov,
+                                    double *chi2, double *last_step, double *trace, int32_t *n_iter, int32_t *n_cadences,
+                                    int64_t *n_pixels, int8_t *cadence_status, int32_t *status, void *stream);
+
 /* lk_cube_background_batch_dev <- TargetPixelFile.estimate_background(aperture_mask) per cadence of the same resident cubes,
  *   and the subtraction of that background, in one pass (PixelCube.estimate_background / subtract_background are the numpy
  *   mirror).  mask / mask_stride as lk_cube_aperture_batch_dev; sel = the masked pixels of cadence i of cutout b.

@@ -10,7 +10,7 @@ from . import packed
 
 __all__ = ["lombscargle_batch", "lombscargle_peaks_batch", "bls_batch", "bls_stats_batch", "ls_model_batch", "fold_bin_batch", "river_batch", "fill_gaps_batch",
            "periodogram_peaks", "flatten_batch",
-           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "psf_photometry_batch", "psf_fit_batch", "psf_width_batch", "pixel_periodograms_batch", "subtract_background_batch", "regression_correct_batch", "cbv_correct_batch"]
+           "estimate_cdpp_batch", "pld_correct_batch", "difference_images_batch", "amplitude_images_batch", "psf_photometry_batch", "psf_fit_batch", "psf_width_batch", "psf_positions_batch", "pixel_periodograms_batch", "subtract_background_batch", "regression_correct_batch", "cbv_correct_batch"]
 
 
 def _resolve_device(device):
@@ -430,6 +430,15 @@ def psf_width_batch(cubes, star_col, star_row, sigma0, device=0, **kwargs):
     (``DevicePixelCubeBatch.from_cubes``), then ``DevicePixelCubeBatch.psf_width`` with its keywords; returns its dict."""
     from .device import DevicePixelCubeBatch
     return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).psf_width(star_col, star_row, sigma0, **kwargs)
+
+
+def psf_positions_batch(cubes, star_col, star_row, sigma, device=0, **kwargs):
+    """``PixelCube.psf_positions`` of every cutout, for host cutouts: the (column, row) of each fitted star of each cutout, fitted
+    on all its cadences at given shifts and width (``DESIGN.md`` §5i).  ``cubes``: ``PixelCube``s of one (N, ny, nx) with float32
+    flux; they go up once (``DevicePixelCubeBatch.from_cubes``), then ``DevicePixelCubeBatch.psf_positions`` with its keywords;
+    returns its dict."""
+    from .device import DevicePixelCubeBatch
+    return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).psf_positions(star_col, star_row, sigma, **kwargs)
 
 
 def pixel_periodograms_batch(cubes, frequency, device=0, **kwargs):

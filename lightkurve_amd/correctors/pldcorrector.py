@@ -176,6 +176,29 @@ def _psf_width_tables(c, sg, n):
     return 0.5 * (E[..., 1:] - E[..., :-1]), -(Q[..., 1:] - Q[..., :-1])
 
 
+def _psf_positions_parameters(max_iter, tol, max_step, max_offset):
+    """The iteration's parameters of ``psf_positions``, checked: max_iter an integer 1 .. 64, tol finite and >= 0, max_step > 0,
+    max_offset > 0."""
+    max_iter, tol, _, _ = _psf_fit_parameters(max_iter, tol, 1.0, 1.0)
+    max_step, max_offset = float(max_step), float(max_offset)
+    if not max_step > 0:
+        raise ValueError("max_step must be > 0 (got %r)" % (max_step,))
+    if not max_offset > 0:
+        raise ValueError("max_offset must be > 0 (got %r)" % (max_offset,))
+    return max_iter, tol, max_step, max_offset
+
+
+def _psf_centre_tables(c, sg, n):
+    """The n pixel factors of the PSF calls along one axis at the centres ``c`` (any shape) and the width ``sg``, and their
+    derivatives by the centre -> two arrays c.shape + (n,): (erf(z_{k+1}) - erf(z_k)) / 2 and -(P(k + 1) - P(k)), z_k = (k - 1/2
+    - c) / (sqrt(2) sg), P(k) = exp(-z_k^2) / (sqrt(2 pi) sg): the tables of ``psf_fit``, where a shift and a centre enter as
+    one sum."""
+    import math
+    z = (np.arange(n + 1) - 0.5 - np.asarray(c, dtype=np.float64)[..., None]) / (np.sqrt(2.0) * sg)
+    E, P = np.vectorize(math.erf, otypes=[np.float64])(z), np.exp(-z * z) / (np.sqrt(2.0 * np.pi) * sg)
+    return 0.5 * (E[..., 1:] - E[..., :-1]), -(P[..., 1:] - P[..., :-1])
+
+
 def _psf_cholesky(G, scale):
     """The unpivoted Cholesky of the PSF fits: G (M, k, k), pivot cut 1e-12 scale (M, k) -> L, singular, smallest pivot ratio."""
     M, k = G.shape[:2]
@@ -921,6 +944,223 @@ class PixelCube(object):
         out.update(status=status, n_cadences=ev["n_cadences"], n_pixels=ev["n_pixels"], n_iter=n_iter, last_step=float(last_step),
                    trace=trace, cadence_status=ev["cadence_status"], n_used=n_used, star_index=star_index, steps=steps,
                    raw_steps=raw_steps, visited=visited, min_pivot_ratio=float(ratio))
+        return out
+
+    def psf_positions(self, star_col, star_row, sigma, shifts=None, cadence_mask=None, fit_star=None, max_iter=20, tol=1e-6,
+                      max_step=0.25, max_offset=1.0, aperture_mask="all", column=0, row=0, use_flux_err=True):
+        """The positions of the cutout's stars, fitted: ONE (column, row) per fitted star, shared by every cadence, by variable
+        projection in Kaufman's form with the linear unknowns (the fluxes of up to 8 stars and a background PER CADENCE)
+        projected out (the host mirror of ``DevicePixelCubeBatch.psf_positions`` and its definition, float64 numpy after the
+        float32 load).  The last unknown of ``TargetPixelFile.to_lightcurve(method="prf")`` that the PSF calls took as given; the
+        chain is ``psf_fit(guess)`` -> ``psf_positions(shifts=)`` -> ``psf_width(shifts=)`` -> ``psf_fit`` / ``psf_photometry``.
+        Stars (NaN = an empty slot), ``aperture_mask``, ``column`` / ``row``, ``sigma`` (given, not fitted), the PSF, the used
+        pixels, the weights w, the design A = [g_0 ... g_{S-1}, 1], K = S + 1, the Cholesky and its pivot cut 1e-12 G_kk are
+        those of ``psf_photometry``; ``shifts`` and ``cadence_mask`` those of ``psf_width``.  ``fit_star``: None (every star
+        present is fitted) or a bool array over the slots; a star that is not fitted stays at its given position (a faint
+        neighbour left at its catalogue value); no fitted star is a ``ValueError``.
+
+        THE FIT IS CONDITIONAL ON THE SHIFTS (and on the width): a translation common to all stars is the same model as a
+        constant added to every shift, the call never frees both, and ``fit_star`` can pin an anchor star.
+
+        The unknowns v are (column, row) of the fitted stars in slot order, v[2j] the column and v[2j + 1] the row of the j-th
+        fitted star, P = 2 x their number <= 16; v starts at the given positions.  A cadence is ELIGIBLE when ``cadence_mask``
+        selects it, its time and its shift are finite and n_used >= S + 2; that does not depend on v.  One EVALUATION at v, per
+        eligible cadence: G = A^T W A, rhs = A^T W y, G = L L^T, theta = G^-1 rhs, r = y - A theta; D has one column per
+        unknown, for star s theta_s (dg_s^col/dc) g_s^row and theta_s g_s^col (dg_s^row/dc) over the used pixels, where the
+        derivative of a factor (erf(z_{k+1}) - erf(z_k)) / 2, z_k = (k - 1/2 - c) / (sqrt(2) sigma), by its centre c is -(P(k +
+        1) - P(k)), P(k) = exp(-z_k^2) / (sqrt(2 pi) sigma) (``psf_fit``'s derivative by the shift); C = A^T W D (K x P), E =
+        D^T W D, g_n = D^T W r, S2_n = E - (L^-1 C)^T (L^-1 C), chi2_n = sum w r^2.  The columns of every star are formed; the
+        Schur complement over the fitted subset is exactly the submatrix of S2_n.  A cadence whose G fails a pivot is singular
+        at this evaluation and contributes nothing.  The cutout's sums g = sum g_n, H = sum S2_n, chi2, n_cadences and
+        n_pixels = sum n_used run over the contributing cadences in an order fixed by N alone.
+
+        For it = 1 .. ``max_iter``: (1) evaluate at v; (2) n_cadences == 0: status 1, stop; (3) H (the fitted rows and
+        columns) = L2 L2^T by the P x P unpivoted Cholesky, singular when a pivot d_k is not finite and > 1e-12 H_kk: status 3,
+        stop; (4) dv = H^-1 g, each component clamped to +-``max_step``; (5) v += dv, n_iter = it, last_step = max |dv|; (6) a
+        component of v farther than ``max_offset`` from its start: status 5, stop; (7) ``tol`` > 0 and last_step < ``tol``:
+        converged.  After ``max_iter`` steps without convergence the status is 4, but ``tol`` = 0 means "exactly ``max_iter``
+        steps" and is status 0.  A status 0 cutout is evaluated once more at its final v (no cadence there: status 1; H
+        singular: status 3) for the outputs, all in the caller's slot layout (S_max slots): ``star_col`` / ``star_row`` (S_max,):
+        the fitted values, the given value bit for bit for a star that is not fitted, NaN in an empty slot; ``star_col_err`` /
+        ``star_row_err`` = sqrt((H^-1)_kk), not scaled by chi2 and conditional on shifts and width, NaN where the star is not
+        fitted; ``position_cov`` (2 S_max, 2 S_max) = H^-1 at index 2 slot + axis, NaN rows and columns where the star is not
+        fitted; ``chi2``.  A failed cutout is NaN in the fitted stars' positions, their errors, ``position_cov`` and ``chi2``;
+        nothing is raised.  Always returned: ``status``; ``n_cadences`` and ``n_pixels`` (int64) of the last evaluation made;
+        ``n_iter`` and ``last_step`` (NaN before the first update); ``trace`` (max_iter + 1, 2 S_max): row k holds the
+        positions of evaluation k + 1 at index 2 slot + axis (a star that is not fitted at its given value, NaN in an empty
+        slot), NaN beyond the evaluations made — the final evaluation is made at row n_iter, so a status 0 cutout has n_iter +
+        1 rows and a v that left ``max_offset`` (status 5) is not in it; ``cadence_status`` (N,) int8 from the last evaluation
+        made, in this order of precedence: 6 not selected by ``cadence_mask``, 1 the time or a shift is not finite, 2 n_used <
+        S + 2, 3 singular, 0 contributed; ``n_used`` (N,) int32; ``star_index`` and ``fitted_index`` (the slots of the stars
+        and of the fitted stars); and what the tests' preconditions read: ``steps`` (max_iter,), ``raw_steps`` (max_iter, P)
+        before the clamp, ``visited`` (max_iter, P), v after every update, ``start`` (P,), ``min_pivot_ratio``, the smallest
+        d_k / G_kk (eligible cadences) or d_k / H_kk of every factorisation made, and ``first_gradient`` (2 S,) and
+        ``first_hessian`` (2 S, 2 S), g and H of the first evaluation over ALL the stars' columns (index 2 star + axis).
+        ``ValueError``: the argument errors of ``psf_width``, ``max_offset`` not > 0, a ``fit_star`` of another shape or
+        dtype, or no fitted star."""
+        col_in, rw_in = np.atleast_1d(np.asarray(star_col, dtype=np.float64)), np.atleast_1d(np.asarray(star_row, dtype=np.float64))
+        if col_in.ndim != 1 or col_in.shape != rw_in.shape:
+            raise ValueError("star_col and star_row must be 1-D arrays of one length (got %r and %r)" % (col_in.shape, rw_in.shape))
+        S_max = len(col_in)
+        star_index = np.flatnonzero(~(np.isnan(col_in) | np.isnan(rw_in)))
+        col, rw = col_in[star_index], rw_in[star_index]
+        S = len(star_index)
+        if not 1 <= S <= 8:
+            raise ValueError("psf_positions fits 1 .. 8 stars per cutout (got %d)" % S)
+        if not (np.all(np.isfinite(col)) and np.all(np.isfinite(rw))):
+            raise ValueError("a star position is infinite")
+        if fit_star is None:
+            fit = np.ones(S_max, dtype=bool)
+        else:
+            fit = np.asarray(fit_star)
+            if fit.dtype != bool or fit.shape != (S_max,):
+                raise ValueError("fit_star must be a bool array of one value per slot (%d)" % S_max)
+        fitted = np.flatnonzero(fit[star_index])                # among the stars present
+        if len(fitted) == 0:
+            raise ValueError("no star of the cutout is fitted")
+        fitted_index = star_index[fitted]
+        sg = _psf_sigma(sigma)
+        max_iter, tol, max_step, max_offset = _psf_positions_parameters(max_iter, tol, max_step, max_offset)
+        N, ny, nx = self.shape
+        npix, K, P = ny * nx, S + 1, 2 * len(fitted)
+        sel = np.stack([2 * fitted, 2 * fitted + 1], axis=1).reshape(-1)       # the fitted columns among the 2 S
+        if shifts is None:
+            dc = dr = np.zeros(N)
+        else:
+            if len(shifts) != 2:
+                raise ValueError("shifts must be a pair (shift_col, shift_row)")
+            dc, dr = (np.asarray(a, dtype=np.float64) for a in shifts)
+            if dc.shape != (N,) or dr.shape != (N,):
+                raise ValueError("shifts must be a pair of arrays of one value per cadence (%d)" % N)
+        if cadence_mask is None:
+            selected = np.ones(N, dtype=bool)
+        else:
+            selected = np.asarray(cadence_mask)
+            if selected.dtype != bool or selected.shape != (N,):
+                raise ValueError("cadence_mask must be a bool array of one value per cadence (%d)" % N)
+        ap = self._parse_aperture_mask(aperture_mask).reshape(npix)
+        y32 = np.asarray(self.flux).reshape(N, npix)
+        used = ap[None, :] & np.isfinite(y32)
+        with np.errstate(all="ignore"):
+            if use_flux_err:
+                e32 = np.asarray(self.flux_err).reshape(N, npix)
+                used &= np.isfinite(e32) & (e32 > 0)
+                e = np.where(used, e32, 1).astype(np.float64)
+                w_all = np.where(used, 1.0 / (e * e), 0.0)
+            else:
+                w_all = used.astype(np.float64)
+        y_all = np.where(used, y32, 0).astype(np.float64)
+        n_used = used.sum(axis=1).astype(np.int32)
+        base = np.where(~selected, 6, np.where(~(np.isfinite(self.time) & np.isfinite(dc) & np.isfinite(dr)), 1,
+                                               np.where(n_used < S + 2, 2, 0))).astype(np.int8)
+        idx = np.flatnonzero(base == 0)                         # the eligible cadences
+        w, y, keep = w_all[idx], y_all[idx], used[idx]
+        M = len(idx)
+
+        def evaluate(pos):
+            """pos (2 S,): every star's (column, row) -> g (2 S,), H (2 S, 2 S), chi2, the counts, cadence_status, pivot ratio."""
+            g_col, d_col = _psf_centre_tables(pos[0::2, None] + dc[None, idx] - column, sg[0], nx)
+            g_row, d_row = _psf_centre_tables(pos[1::2, None] + dr[None, idx] - row, sg[1], ny)
+            A, Dp = np.empty((M, npix, K)), np.empty((M, npix, 2 * S))
+            for s in range(S):
+                A[:, :, s] = (g_col[s][:, None, :] * g_row[s][:, :, None]).reshape(M, npix)
+                Dp[:, :, 2 * s] = (d_col[s][:, None, :] * g_row[s][:, :, None]).reshape(M, npix)
+                Dp[:, :, 2 * s + 1] = (g_col[s][:, None, :] * d_row[s][:, :, None]).reshape(M, npix)
+            A[:, :, S] = 1.0
+            A = np.where(keep[:, :, None], A, 0.0)
+            WA = A * w[:, :, None]
+            G = np.einsum("npi,npj->nij", WA, A)
+            L, singular, ratio = _psf_cholesky(G, np.einsum("nii->ni", G))
+            theta = _psf_backward(L, _psf_forward(L, np.einsum("npi,np->ni", WA, y)[:, :, None]))[:, :, 0]
+            res = y - np.einsum("npi,ni->np", A, theta)
+            D = np.where(keep[:, :, None], Dp * np.repeat(theta[:, :S], 2, axis=1)[:, None, :], 0.0)
+            WD = D * w[:, :, None]
+            Y = _psf_forward(L, np.einsum("npi,npj->nij", A, WD))
+            S2 = np.einsum("npi,npj->nij", WD, D) - np.einsum("nki,nkj->nij", Y, Y)
+            ok = ~singular
+            cst = base.copy()
+            cst[idx[singular]] = 3
+            return dict(g=np.where(ok[:, None], np.einsum("npi,np->ni", WD, res), 0.0).sum(axis=0),
+                        H=np.where(ok[:, None, None], S2, 0.0).sum(axis=0), chi2=np.where(ok, np.sum(w * res * res, axis=1), 0.0).sum(),
+                        n_cadences=int(ok.sum()), n_pixels=int(n_used[idx][ok].sum()), cadence_status=cst,
+                        ratio=ratio.min() if M else np.inf)
+
+        def factor(H):                                           # the fitted rows and columns -> L2, singular, pivot ratio
+            Hf = H[np.ix_(sel, sel)]
+            L2, singular, r2 = _psf_cholesky(Hf[None], np.diag(Hf)[None])
+            return L2, bool(singular[0]), float(r2[0])
+
+        def slots(pos):                                          # (2 S,) -> (2 S_max,) at index 2 slot + axis, NaN in empty slots
+            out = np.full(2 * S_max, np.nan)
+            out[2 * star_index], out[2 * star_index + 1] = pos[0::2], pos[1::2]
+            return out
+
+        pos = np.stack([col, rw], axis=1).reshape(-1)            # every star's position; the fitted ones move
+        start = pos[sel].copy()
+        n_iter, last_step, status = 0, np.nan, 4
+        trace = np.full((max_iter + 1, 2 * S_max), np.nan)
+        steps, raw_steps, visited = np.full(max_iter, np.nan), np.full((max_iter, P), np.nan), np.full((max_iter, P), np.nan)
+        ratio, first = np.inf, None
+        out = dict(star_col=np.where(fit, np.nan, col_in), star_row=np.where(fit, np.nan, rw_in), star_col_err=np.full(S_max, np.nan),
+                   star_row_err=np.full(S_max, np.nan), position_cov=np.full((2 * S_max, 2 * S_max), np.nan), chi2=np.nan)
+        with np.errstate(all="ignore"):
+            for it in range(1, max_iter + 1):
+                ev = evaluate(pos)
+                if first is None:
+                    first = ev
+                trace[it - 1] = slots(pos)
+                ratio = min(ratio, ev["ratio"])
+                if ev["n_cadences"] == 0:
+                    status = 1
+                    break
+                L2, singular, r2 = factor(ev["H"])
+                ratio = min(ratio, r2)
+                if singular:
+                    status = 3
+                    break
+                dv = _psf_backward(L2, _psf_forward(L2, ev["g"][sel][None, :, None]))[0, :, 0]
+                raw_steps[it - 1] = dv
+                dv = np.where(dv > max_step, max_step, np.where(dv < -max_step, -max_step, dv))
+                pos = pos.copy()
+                pos[sel] = pos[sel] + dv
+                n_iter, visited[it - 1] = it, pos[sel]
+                last_step = steps[it - 1] = np.max(np.abs(dv))
+                if np.any(np.abs(pos[sel] - start) > max_offset):
+                    status = 5
+                    break
+                if tol > 0 and last_step < tol:
+                    status = 0
+                    break
+            if status == 4 and tol == 0:
+                status = 0
+            if status == 0:
+                ev = evaluate(pos)
+                trace[n_iter] = slots(pos)
+                ratio = min(ratio, ev["ratio"])
+                if ev["n_cadences"] == 0:
+                    status = 1
+                else:
+                    L2, singular, r2 = factor(ev["H"])
+                    ratio = min(ratio, r2)
+                    if singular:
+                        status = 3
+                    else:
+                        Minv = _psf_forward(L2, np.eye(P)[None])[0]                # L2^-1
+                        cov = Minv.T @ Minv
+                        full = slots(pos)
+                        out["star_col"], out["star_row"] = np.where(fit, full[0::2], col_in), np.where(fit, full[1::2], rw_in)
+                        at = np.stack([2 * fitted_index, 2 * fitted_index + 1], axis=1).reshape(-1)
+                        out["position_cov"][np.ix_(at, at)] = cov
+                        err = np.sqrt(np.diag(cov))
+                        out["star_col_err"][fitted_index], out["star_row_err"][fitted_index] = err[0::2], err[1::2]
+                        out["chi2"] = float(ev["chi2"])
+        # an empty slot is NaN whether or not fit_star names it
+        empty = np.isnan(col_in) | np.isnan(rw_in)
+        out["star_col"], out["star_row"] = np.where(empty, np.nan, out["star_col"]), np.where(empty, np.nan, out["star_row"])
+        out.update(status=status, n_cadences=ev["n_cadences"], n_pixels=ev["n_pixels"], n_iter=n_iter, last_step=float(last_step),
+                   trace=trace, cadence_status=ev["cadence_status"], n_used=n_used, star_index=star_index, fitted_index=fitted_index,
+                   steps=steps, raw_steps=raw_steps, visited=visited, start=start, min_pivot_ratio=float(ratio),
+                   first_gradient=first["g"], first_hessian=first["H"])
         return out
 
     def pixel_periodogram(self, frequency, normalization="amplitude", freq_unit=None, oversample_factor=None):

@@ -2365,6 +2365,22 @@ int lk_cube_psf_width_batch_dev(lk_handle *h, int B, int N, int ny, int nx, cons
                                     cadence_status, status, static_cast<hipStream_t>(stream));
 }
 
+int lk_cube_psf_positions_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
+                                    const float *flux_err, const uint8_t *mask, int mask_stride, int S_max, const double *star_col,
+                                    const double *star_row, const double *sigma, const uint8_t *fit_star, const double *shift_col,
+                                    const double *shift_row, const uint8_t *cadence_mask, int max_iter, double tol, double max_step,
+                                    double max_offset, double column0, double row0, int use_flux_err, double *star_col_out,
+                                    double *star_row_out, double *star_col_err, double *star_row_err, double *position_cov,
+                                    double *chi2, double *last_step, double *trace, int32_t *n_iter, int32_t *n_cadences,
+                                    int64_t *n_pixels, int8_t *cadence_status, int32_t *status, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_psfpos_launch(h, B, N, ny, nx, time, flux, flux_err, mask, mask_stride, S_max, star_col, star_row, sigma, fit_star,
+                                  shift_col, shift_row, cadence_mask, max_iter, tol, max_step, max_offset, column0, row0, use_flux_err,
+                                  star_col_out, star_row_out, star_col_err, star_row_err, position_cov, chi2, last_step, trace, n_iter,
+                                  n_cadences, n_pixels, cadence_status, status, static_cast<hipStream_t>(stream));
+}
+
 int lk_sff_scratch_bytes(int B, const int64_t *n_off, const int32_t *n_knots, const int32_t *win_off, int bins, int degree,
                          int64_t max_scratch_bytes, int64_t *bytes, int *n_chunks) {
     return lk::sff_scratch_bytes(B, n_off, n_knots, win_off, bins, degree, max_scratch_bytes, bytes, n_chunks);

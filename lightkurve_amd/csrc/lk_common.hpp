@@ -461,6 +461,17 @@ int cube_psfwidth_launch(lk_handle *h, int B, int N, int ny, int nx, const doubl
                          int use_flux_err, double *sigma, double *sigma_err, double *sigma_cov, double *chi2, double *last_step,
                          double *trace, int32_t *n_iter, int32_t *n_cadences, int64_t *n_pixels, int8_t *cadence_status,
                          int32_t *status, hipStream_t stream);
+// psfpos.hip: the (column, row) of every fitted star of every cutout, shared by its cadences, by variable projection from the given
+// positions (host arrays; fit_star_host nullable host bytes [B][S_max], non-zero = fitted) at given shifts (nullable device
+// arrays) on the cadences of cadence_mask (nullable device bytes): max_iter + 1 pairs of an evaluate and a step kernel.
+// Everything but the stars, sigma and fit_star on the device; enqueued, no synchronisation
+int cube_psfpos_launch(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux, const float *flux_err,
+                       const uint8_t *mask, int mask_stride, int S_max, const double *star_col_host, const double *star_row_host,
+                       const double *sigma_host, const uint8_t *fit_star_host, const double *shift_col, const double *shift_row,
+                       const uint8_t *cadence_mask, int max_iter, double tol, double max_step, double max_offset, double column0,
+                       double row0, int use_flux_err, double *star_col, double *star_row, double *star_col_err, double *star_row_err,
+                       double *position_cov, double *chi2, double *last_step, double *trace, int32_t *n_iter, int32_t *n_cadences,
+                       int64_t *n_pixels, int8_t *cadence_status, int32_t *status, hipStream_t stream);
 // sff.hip: SFFCorrector for a ragged resident batch.  The regression launcher owns h->ws, so the design matrices and everything
 // else that lives across it sit in `scratch`, a device block of the caller's (sff_scratch_bytes); status_host is valid on
 // return (the call synchronises once, to group the targets by their design width)

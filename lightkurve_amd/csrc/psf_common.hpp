@@ -1,7 +1,8 @@
-// psf_common.hpp — what psfphot.hip (fluxes at given positions), psffit.hip (fluxes and a common shift per cadence) and
-// psfwidth.hip (the width of a cutout) share: the cadence-per-four-lanes mapping, the Gaussian's edge integral, the sums over a
-// cadence's lanes, a tile's cadences and a wavefront, the Cholesky without pivoting with its singularity test, and the host-side
-// grouping of a batch's cutouts by their star count.
+// psf_common.hpp — what psfphot.hip (fluxes at given positions), psffit.hip (fluxes and a common shift per cadence), psfwidth.hip
+// (the width of a cutout) and psfpos.hip (the positions of a cutout's stars) share: the cadence-per-four-lanes mapping, the
+// Gaussian's edge integral, the table of factors and their derivatives by the centre (psffit.hip and psfpos.hip), the sums over
+// a cadence's lanes, a tile's cadences and a wavefront, the Cholesky without pivoting with its singularity test, and the
+// host-side grouping of a batch's cutouts by their star count.
 #pragma once
 #include <cmath>
 #include <vector>
@@ -40,6 +41,23 @@ template <class T> __device__ __forceinline__ T psf_wave_sum(T v) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
     return v;
+}
+
+// One run of tables (a star's len column or row factors at centre c, width sg) for cadence slot cl: val[k][cl] = (E(k + 1) -
+// E(k)) / 2 and der[k][cl] = its derivative by c, -(P(k + 1) - P(k)); every edge's erf and exp serve the two pixels it
+// separates, len + 1 evaluations for len factors.
+__device__ __forceinline__ void fit_table_run(double *__restrict__ val, double *__restrict__ der, int len, double c, double sg) {
+    constexpr double INV_SQRT_2PI = 0.3989422804014327;
+    const double den = M_SQRT2 * sg, pn = INV_SQRT_2PI / sg;
+    double z = (-0.5 - c) / den;
+    double lo = psf_edge(0, c, den), plo = exp(-z * z) * pn;
+    for (int k = 0; k < len; ++k) {
+        z = ((double)(k + 1) - 0.5 - c) / den;
+        const double hi = psf_edge(k + 1, c, den), phi = exp(-z * z) * pn;
+        val[k * PSF_T] = 0.5 * (hi - lo);
+        der[k * PSF_T] = plo - phi;
+        lo = hi, plo = phi;
+    }
 }
 
 // G = L L^T in index order, no pivoting (G: upper triangle read); true when a pivot is not finite or <= PSF_PIVOT_CUT * G_kk

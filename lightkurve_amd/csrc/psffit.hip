@@ -61,23 +61,6 @@ struct FitArgs {
     int8_t *cstat;
 };
 
-// One run of tables (a star's len column or row factors at centre c, width sg) for cadence slot cl: val[k][cl] = (E(k + 1) -
-// E(k)) / 2 and der[k][cl] = its derivative by c, -(P(k + 1) - P(k)); every edge's erf and exp serve the two pixels it
-// separates, len + 1 evaluations for len factors.
-__device__ __forceinline__ void fit_table_run(double *__restrict__ val, double *__restrict__ der, int len, double c, double sg) {
-    constexpr double INV_SQRT_2PI = 0.3989422804014327;
-    const double den = M_SQRT2 * sg, pn = INV_SQRT_2PI / sg;
-    double z = (-0.5 - c) / den;
-    double lo = psf_edge(0, c, den), plo = exp(-z * z) * pn;
-    for (int k = 0; k < len; ++k) {
-        z = ((double)(k + 1) - 0.5 - c) / den;
-        const double hi = psf_edge(k + 1, c, den), phi = exp(-z * z) * pn;
-        val[k * PSF_T] = 0.5 * (hi - lo);
-        der[k * PSF_T] = plo - phi;
-        lo = hi, plo = phi;
-    }
-}
-
 template <int S> __global__ __launch_bounds__(64) void cube_psffit_kernel(const FitArgs a) {
     constexpr int K = S + 1;
     extern __shared__ __align__(16) double fit_lds[];

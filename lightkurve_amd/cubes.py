@@ -71,6 +71,15 @@ def _psf_width_spec(B, N, max_iter):
             ("cadence_status", np.int8, (B, N)), ("status", np.int32, (B,))]
 
 
+def _psf_positions_spec(B, N, S_max, max_iter):
+    """(key, dtype, shape) of every output of ``psf_positions``."""
+    return [("star_col", np.float64, (B, S_max)), ("star_row", np.float64, (B, S_max)), ("star_col_err", np.float64, (B, S_max)),
+            ("star_row_err", np.float64, (B, S_max)), ("position_cov", np.float64, (B, 2 * S_max, 2 * S_max)),
+            ("chi2", np.float64, (B,)), ("last_step", np.float64, (B,)), ("trace", np.float64, (B, max_iter + 1, 2 * S_max)),
+            ("n_iter", np.int32, (B,)), ("n_cadences", np.int32, (B,)), ("n_pixels", np.int64, (B,)),
+            ("cadence_status", np.int8, (B, N)), ("status", np.int32, (B,))]
+
+
 class DevicePixelCubeBatch(object):
     """B same-shaped target-pixel cutouts IN HBM — the input of ``PLDCorrector`` as ``DeviceLightCurveBatch`` is the input of
     the light-curve chain: ``d_flux`` / ``d_flux_err`` float32 [B][N][npix] (npix = ny * nx, row-major pixels: the layout
@@ -857,17 +866,7 @@ class DevicePixelCubeBatch(object):
         max_iter, tol, max_step, min_sigma, max_sigma = _psf_width_parameters(max_iter, tol, max_step, min_sigma, max_sigma, sg)
         keep = []
         d_shift = self._psf_shift_buffers(shifts, "shifts", keep)
-        d_cmask = None
-        if isinstance(cadence_mask, DeviceBuffer):
-            if cadence_mask.nbytes != B * N:
-                raise ValueError("a cadence_mask buffer of %d bytes for %d x %d cadences" % (cadence_mask.nbytes, B, N))
-            d_cmask = cadence_mask
-        elif cadence_mask is not None:
-            cm = np.asarray(cadence_mask)
-            if cm.dtype != bool or cm.shape != (B, N):
-                raise ValueError("cadence_mask must be a bool (B, N) = %r array (got %s %r)" % ((B, N), cm.dtype, cm.shape))
-            d_cmask, k = _upload(h, cm.astype(np.uint8), self.stream, np.uint8)
-            keep.append(k)
+        d_cmask = self._psf_cadence_mask(cadence_mask, keep)
         _, d_mask, stride, _ = self._stage_mask(aperture_mask, False)           # kept in self._keep
         spec = _psf_width_spec(B, N, max_iter)
         out = {key: DeviceBuffer(h, int(np.prod(shape)) * np.dtype(dt).itemsize) for key, dt, shape in spec}
@@ -878,6 +877,92 @@ class DevicePixelCubeBatch(object):
             _p(out["sigma"]), _p(out["sigma_err"]), _p(out["sigma_cov"]), _p(out["chi2"]), _p(out["last_step"]), _p(out["trace"]),
             _p(out["n_iter"]), _p(out["n_cadences"]), _p(out["n_pixels"]), _p(out["cadence_status"]), _p(out["status"]),
             _vp(self.stream or None)))
+        keep += [d for d in d_shift if d is not None] + ([d_cmask] if d_cmask is not None else [])
+        if not to_host:
+            self._keep = self._keep + keep                              # what the enqueued fit still reads
+            return out
+        for key, dt, shape in spec:
+            out[key] = self._get(out[key], dt, shape)
+        self._keep = []
+        return out
+
+    def _psf_cadence_mask(self, cadence_mask, keep):
+        """``cadence_mask`` of the PSF calls -> its bytes on the device or None: a bool host array [B, N], uploaded (what must
+        outlive the upload is appended to ``keep``), or a ``DeviceBuffer`` of B x N bytes."""
+        h, (B, N, _, _) = self.handle, self.shape
+        if isinstance(cadence_mask, DeviceBuffer):
+            if cadence_mask.nbytes != B * N:
+                raise ValueError("a cadence_mask buffer of %d bytes for %d x %d cadences" % (cadence_mask.nbytes, B, N))
+            return cadence_mask
+        if cadence_mask is None:
+            return None
+        cm = np.asarray(cadence_mask)
+        if cm.dtype != bool or cm.shape != (B, N):
+            raise ValueError("cadence_mask must be a bool (B, N) = %r array (got %s %r)" % ((B, N), cm.dtype, cm.shape))
+        d_cmask, k = _upload(h, cm.astype(np.uint8), self.stream, np.uint8)
+        keep.append(k)
+        return d_cmask
+
+    def psf_positions(self, star_col, star_row, sigma, shifts=None, cadence_mask=None, fit_star=None, max_iter=20, tol=1e-6,
+                      max_step=0.25, max_offset=1.0, aperture_mask="all", column=0, row=0, use_flux_err=True, to_host=True):
+        """The positions of every cutout's stars, fitted: ONE (column, row) per fitted star, shared by all the cutout's cadences,
+        by variable projection with every cadence's fluxes and background projected out (``lk_cube_psf_positions_batch_dev``;
+        the numpy mirror and the definition is ``PixelCube.psf_positions``) — the ``star_col`` / ``star_row`` that
+        ``psf_photometry``, ``psf_fit`` and ``psf_width`` take as given (a catalogue at another epoch, ``estimate_centroids`` of
+        a blend, the peak images).  The chain that calibrates itself::
+
+            _, fit = cubes.psf_fit(col, row, sigma_guess)
+            shifts = (fit["shift_col"], fit["shift_row"])
+            pos = cubes.psf_positions(col, row, sigma_guess, shifts=shifts)
+            width = cubes.psf_width(pos["star_col"], pos["star_row"], sigma_guess, shifts=shifts)
+            lcs, fit = cubes.psf_fit(pos["star_col"], pos["star_row"], width["sigma"])
+
+        THE FIT IS CONDITIONAL ON THE SHIFTS (and on the width): a translation common to all stars is the same model as a
+        constant added to every shift, the call never frees both, and ``fit_star`` can pin an anchor star.
+
+        Stars (NaN = an empty slot), ``sigma`` (given, not fitted), ``aperture_mask``, ``column`` / ``row`` and ``use_flux_err``
+        as in ``psf_photometry``; ``shifts`` and ``cadence_mask`` as in ``psf_width`` (host arrays or ``DeviceBuffer``s).
+        ``fit_star``: None (every star present is fitted) or a bool array (S_max,) or (B, S_max); a star that is not fitted
+        stays at its given position; a cutout with no fitted star is a ``ValueError``.  Up to ``max_iter`` (1 .. 64)
+        Gauss-Newton steps per cutout, each component clamped to +-``max_step``; a cutout stops when its step is below ``tol``
+        (``tol`` = 0: exactly ``max_iter`` steps) and fails when a position moves farther than ``max_offset`` from its start.
+        Returns a dict, everything in the caller's slot layout: ``star_col`` / ``star_row`` (B, S_max): the fitted values, the
+        given value bit for bit for a star that is not fitted, NaN in an empty slot; ``star_col_err`` / ``star_row_err`` (B,
+        S_max) = sqrt((H^-1)_kk), NaN where the star is not fitted; ``position_cov`` (B, 2 S_max, 2 S_max) = H^-1 at index 2
+        slot + axis; ``chi2`` and ``last_step`` (B,); ``trace`` (B, max_iter + 1, 2 S_max), the positions of every evaluation
+        made, NaN beyond; ``n_iter`` and ``n_cadences`` (B,) int32, ``n_pixels`` (B,) int64; ``cadence_status`` (B, N) int8: 0
+        contributed, 1 the time or a shift is not finite, 2 n_used < S + 2, 3 singular, 6 not selected; ``status`` (B,) int32: 0
+        ok, 1 no cadence contributed, 3 singular, 4 not converged, 5 left ``max_offset`` — a cutout that is not ok is NaN in the
+        fitted stars' positions, their errors, ``position_cov`` and ``chi2``; nothing is raised per cutout.  Numpy arrays with
+        ``to_host=True``, ``DeviceBuffer``s enqueued on the batch's stream with ``to_host=False``.  A cutout's outputs have the
+        same bits alone, at any batch position and from run to run."""
+        from .correctors.pldcorrector import _psf_positions_parameters
+        h, (B, N, ny, nx) = self.handle, self.shape
+        pos, part, sg, S_max = _psf_stars(B, star_col, star_row, sigma)
+        max_iter, tol, max_step, max_offset = _psf_positions_parameters(max_iter, tol, max_step, max_offset)
+        if fit_star is None:
+            fit = np.ones((B, S_max), dtype=bool)
+        else:
+            fit = np.asarray(fit_star)
+            if fit.dtype != bool or fit.shape not in ((S_max,), (B, S_max)):
+                raise ValueError("fit_star must be a bool array (S_max,) or (B, S_max) = %r (got %s %r)" % ((B, S_max), fit.dtype, fit.shape))
+            fit = np.broadcast_to(fit, (B, S_max))
+        if not np.all((fit & part).any(axis=1)):
+            raise ValueError("cutouts %s have no fitted star" % np.flatnonzero(~(fit & part).any(axis=1)).tolist())
+        fit8 = np.ascontiguousarray(fit, dtype=np.uint8)
+        keep = []
+        d_shift = self._psf_shift_buffers(shifts, "shifts", keep)
+        d_cmask = self._psf_cadence_mask(cadence_mask, keep)
+        _, d_mask, stride, _ = self._stage_mask(aperture_mask, False)           # kept in self._keep
+        spec = _psf_positions_spec(B, N, S_max, max_iter)
+        out = {key: DeviceBuffer(h, int(np.prod(shape)) * np.dtype(dt).itemsize) for key, dt, shape in spec}
+        _capi._check(_capi._lib.lk_cube_psf_positions_batch_dev(
+            h._h, B, N, ny, nx, _p(self.d_time), _p(self.d_flux), _p(self.d_flux_err), _p(d_mask), stride, S_max,
+            pos[0].ctypes.data_as(_dp), pos[1].ctypes.data_as(_dp), sg.ctypes.data_as(_dp), _vp(fit8.ctypes.data), _p(d_shift[0]),
+            _p(d_shift[1]), _p(d_cmask), max_iter, tol, max_step, max_offset, float(column), float(row), int(bool(use_flux_err)),
+            _p(out["star_col"]), _p(out["star_row"]), _p(out["star_col_err"]), _p(out["star_row_err"]), _p(out["position_cov"]),
+            _p(out["chi2"]), _p(out["last_step"]), _p(out["trace"]), _p(out["n_iter"]), _p(out["n_cadences"]), _p(out["n_pixels"]),
+            _p(out["cadence_status"]), _p(out["status"]), _vp(self.stream or None)))
         keep += [d for d in d_shift if d is not None] + ([d_cmask] if d_cmask is not None else [])
         if not to_host:
             self._keep = self._keep + keep                              # what the enqueued fit still reads

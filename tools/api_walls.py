@@ -155,6 +155,15 @@ sigma0, shifts=)` with the defaults; Wm the same with a `cadence_mask` that sele
 with a synchronise.  Written to profiles/psfwidth_walls.txt.  `psfwidth_trace`: W, Wm, Wb and Rs twice and nothing else, for `rocprofv3
 --kernel-trace --stats` (profiles/psfwidth_kernel_stats.txt).
 
+`psfpos`: the fit of the stars' positions per cutout on the same batch shape and star count, the cubes rendered at the true positions
+with true shifts uniform in +-0.3 px (given to the fit as `DeviceBuffer`s) and the true width 1.1 px (given), the starts 0.2 px off
+per star and axis with either sign, in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5) times after one warm-up.  P
+`cubes.psf_positions(star_col, star_row, sigma, shifts=)` with the defaults; W `cubes.psf_width` and Rs `cubes.psf_photometry` of
+the same cubes at the same shifts and the same (offset) positions; H the mirror `PixelCube.psf_positions` per cutout on 16 threads
+over the first `LK_WALLS_MIRROR_B` (default 16) cutouts, scaled to the batch in the report.  Every timed region ends with a
+synchronise.  Written to profiles/psfpos_walls.txt.  `psfpos_trace`: P and W twice and nothing else, for `rocprofv3 --kernel-trace
+--stats` (profiles/psfpos_kernel_stats.txt).
+
 `background`: the per-cadence background of the same batch shape with 'background' masks, in ONE process, the routes alternating,
 `LK_WALLS_REPS` (default 5) times after one warm-up.  F `cubes.subtract_background()` (median images, masks, the fused estimate +
 subtraction) and Fm the same with the masks given; E `cubes.estimate_background()`, Em with the masks given, Es with the scatter
@@ -1687,6 +1696,100 @@ def psfwidth(which):
                                                 med["H"] * B / Bm / med["W"])])
 
 
+def psfpos(which):
+    from concurrent.futures import ThreadPoolExecutor
+    from scipy.special import erf
+    from lightkurve_amd.device import DevicePixelCubeBatch
+    B, N, side, S = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "500"), ("LK_WALLS_N", "4000"), ("LK_WALLS_SIDE", "11"),
+                                                            ("LK_WALLS_STARS", "4")))
+    reps, Bm = int(os.environ.get("LK_WALLS_REPS", "5")), min(B, int(os.environ.get("LK_WALLS_MIRROR_B", "16")))
+    rng = np.random.default_rng(73)
+    npix = side * side
+    t = 1000.0 + np.arange(N) / 720.0                                    # two-minute cadences
+    sigma, off = 1.1, 0.2                                                # the true width, given; the starts' distance from the truth
+    cells = int(np.ceil(np.sqrt(S)))
+    lattice = np.array([((i + 0.5) * side / cells - 0.5, (j + 0.5) * side / cells - 0.5) for j in range(cells) for i in range(cells)][:S])
+    col = lattice[None, :, 0] + rng.uniform(-0.3, 0.3, (B, S))           # the truth
+    row = lattice[None, :, 1] + rng.uniform(-0.3, 0.3, (B, S))
+    col0, row0 = col + off * rng.choice([-1.0, 1.0], (B, S)), row + off * rng.choice([-1.0, 1.0], (B, S))
+    shifts = (rng.uniform(-0.3, 0.3, (B, N)), rng.uniform(-0.3, 0.3, (B, N)))     # the true pointing of every cadence, given
+    edges = np.arange(side + 1) - 0.5
+    flux = np.empty((B, N, side, side), dtype=np.float32)
+    for b in range(B):                                                  # every cadence rendered at its own shift
+        gx = np.diff(erf((edges[None, None, :] - col[b][None, :, None] - shifts[0][b][:, None, None]) / (np.sqrt(2) * sigma)), axis=2) / 2
+        gy = np.diff(erf((edges[None, None, :] - row[b][None, :, None] - shifts[1][b][:, None, None]) / (np.sqrt(2) * sigma)), axis=2) / 2
+        img = 100.0 + np.einsum("s,nsy,nsx->nyx", rng.uniform(2000.0, 20000.0, S), gy, gx)
+        flux[b] = img.astype(np.float32) + 3.0 * rng.standard_normal((N, side, side), dtype=np.float32)
+    err = np.full_like(flux, 3.0)
+    cubes = DevicePixelCubeBatch.from_arrays(np.tile(t, (B, 1)), flux, err)
+    cubes.synchronize()
+    del flux, err
+    d_shifts = tuple(_upload_f64(cubes, a) for a in shifts)
+
+    def positions():
+        out = cubes.psf_positions(col0, row0, sigma, shifts=d_shifts, to_host=False)
+        cubes.synchronize()
+        return out
+
+    def width():
+        out = cubes.psf_width(col0, row0, sigma, shifts=d_shifts, to_host=False)
+        cubes.synchronize()
+        return out
+
+    def given():
+        out = cubes.psf_photometry(col0, row0, sigma, shifts=d_shifts)
+        cubes.synchronize()
+        return out
+
+    if "psfpos_trace" in which:
+        for _ in range(2):
+            positions()
+            width()
+        return
+
+    host_m = cubes.to_host()[:Bm]
+
+    def mirror():
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            return list(ex.map(lambda b: host_m[b].psf_positions(col0[b], row0[b], sigma, shifts=(shifts[0][b], shifts[1][b])), range(Bm)))
+
+    fns = {"P": positions, "W": width, "Rs": given, "H": mirror}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    get = lambda out, k, dt, shape: out[k].download(dt, int(np.prod(shape)), stream=cubes.stream).reshape(shape)
+    status, n_iter = get(first["P"], "status", np.int32, (B,)), get(first["P"], "n_iter", np.int32, (B,))
+    pc, pr = get(first["P"], "star_col", np.float64, (B, S)), get(first["P"], "star_row", np.float64, (B, S))
+    pe = get(first["P"], "star_col_err", np.float64, (B, S))
+    w_iter = get(first["W"], "n_iter", np.int32, (B,))
+    rel = float(max(np.max(np.abs(pc[:Bm] - np.stack([o["star_col"] for o in first["H"]]))),
+                    np.max(np.abs(pr[:Bm] - np.stack([o["star_row"] for o in first["H"]])))))
+    same_iter = bool(np.array_equal(n_iter[:Bm], [o["n_iter"] for o in first["H"]]))
+    first.clear()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    evals, evals_w = int(n_iter.max()) + 1, int(w_iter.max()) + 1        # passes in which a tile of the batch still works
+    write_walls("psfpos_walls.txt", [
+        "Star positions per cutout, %d cutouts x %d cadences x %d x %d float32, %d stars per cutout (%d unknowns), sigma %.1f px given, "
+        "starts %.1f px off per star and axis, true shifts uniform in +-0.3 px given (%.1f MB of flux and flux_err resident, read once "
+        "per evaluation)" % (B, N, side, side, S, 2 * S, sigma, off, B * N * npix * 8 / 1e6),
+        "  P    cubes.psf_positions(star_col, star_row, sigma, shifts=(DeviceBuffer, DeviceBuffer)), defaults; everything resident  %s" % spread(ts["P"]),
+        "  W    cubes.psf_width(star_col, star_row, sigma, shifts=) on the same cubes at the same (offset) positions, the same run     %s" % spread(ts["W"]),
+        "  Rs   cubes.psf_photometry(star_col, star_row, sigma, shifts=) likewise                                                     %s" % spread(ts["Rs"]),
+        "  H    PixelCube.psf_positions on 16 threads, the first %d cutouts only                                                      %s" % (Bm, spread(ts["H"])),
+        "  P: statuses %s; updates per cutout: mean %.2f, max %d; evaluations made by the slowest cutout (updates + the final one): %d of "
+        "the %d passes enqueued; W: %d" % (dict(zip(*(a.tolist() for a in np.unique(status, return_counts=True)))), float(n_iter.mean()),
+                                           int(n_iter.max()), evals, 21, evals_w),
+        "  largest |fitted - true position| %.5f px; mean star_col_err %.5f px; first %d cutouts against the mirror: max |position "
+        "difference| %.2e px, the same n_iter: %s" % (float(max(np.nanmax(np.abs(pc - col)), np.nanmax(np.abs(pr - row)))),
+                                                      float(np.nanmean(pe)), Bm, rel, same_iter),
+        "  P / Rs = %.2f (%.2f per evaluation made); W / Rs = %.2f (%.2f per evaluation made); P per evaluation / W per evaluation = %.2f "
+        "(S = %d); H scaled to %d cutouts (measured on %d, not run on all) / P = %.0f; kernel times alone: profiles/psfpos_kernel_stats.txt"
+        % (med["P"] / med["Rs"], med["P"] / med["Rs"] / evals, med["W"] / med["Rs"], med["W"] / med["Rs"] / evals_w,
+           (med["P"] / evals) / (med["W"] / evals_w), S, B, Bm, med["H"] * B / Bm / med["P"])])
+
+
 def _upload_f64(cubes, a):
     from lightkurve_amd.devmem import _upload
     buf, keep = _upload(cubes.handle, np.ascontiguousarray(a, dtype=np.float64), cubes.stream, np.float64)
@@ -1935,6 +2038,8 @@ def main():
         psffit(which)
     if {"psfwidth", "psfwidth_trace"} & set(which):
         psfwidth(which)
+    if {"psfpos", "psfpos_trace"} & set(which):
+        psfpos(which)
     if {"pixelpg", "pixelpg_trace"} & set(which):
         pixelpg(which)
     if {"stitch", "stitch_trace"} & set(which):
