@@ -1297,6 +1297,45 @@ int lk_cube_psf_photometry_batch_dev(lk_handle *h, int B, int N, int ny, int nx,
                                      double *time_out, double *flux_out, double *flux_err_out, double *background, double *chi2,
                                      int32_t *n_used, int8_t *cadence_status, int32_t *status, void *stream);
 
+/* lk_cube_prf_photometry_batch_dev <- lk_cube_psf_photometry_batch_dev with a TABULATED PRF in place of the Gaussian
+ *   (TabulatedPRF.evaluate and PixelCube.psf_photometry(prf=) are the numpy mirror and the definition): what
+ *   TargetPixelFile.to_lightcurve(method="prf") evaluates through KeplerPRF, in its linear form.  No position, shift or width is
+ *   fitted, no mission file is read and the corner tables of a channel are not blended: the caller passes the blended array.
+ *   Inputs, stars, shifts, mask, used pixels, weights, the design A = [g_0 ... g_{S-1}, 1], the Cholesky with its pivot cut
+ *   1e-12 G_kk, the outputs, star_off and the statuses 0 .. 3 are those of lk_cube_psf_photometry_batch_dev; sigma is not taken.
+ *   prf_table: DEVICE float32 [n_prf][Ty][Tx], row-major, every value finite (not checked here); oversample = os >= 1, an
+ *   integer; Ty, Tx >= 1 of any parity.  prf_index: HOST int32 [B], the table of every cutout, or NULL: table 0 for all.
+ *   Sample (j, i) is the fraction of a star's flux collected by a pixel whose centre lies ((i - (Tx - 1) / 2) / os, (j - (Ty - 1)
+ *   / 2) / os) px from the star's centre — already pixel-integrated; nothing is normalised.
+ *   Model of star s at cadence n: Keys' cubic convolution (a = -1/2, Catmull-Rom) on the table continued by zeros, float64.  With
+ *   c = star_col[s] + shift_col[n] - column0, u = (0 - c) os + (Tx - 1) / 2, i0 = floor(u), f = u - i0 (likewise r, v, j0, g from
+ *   star_row, shift_row, row0 and Ty):
+ *     w_-1 = ((-f + 2) f - 1) f / 2   w_0 = ((3 f - 5) f f + 2) / 2   w_1 = ((-3 f + 4) f + 1) f / 2   w_2 = (f - 1) f f / 2
+ *     g[iy][ix] = sum_{jj = -1 .. 2} w_jj(g) (sum_{ii = -1 .. 2} w_ii(f) T[j0 + iy os + jj][i0 + ix os + ii]),  T = 0 outside,
+ *   both sums in that order.  os is an integer, so the pixels of a cutout share f and g: they are formed once per (star,
+ *   cadence), at pixel 0.  A star with |u| or |v| >= 1e9, or a NaN shift, has no tap on the table.  A star whose model is zero on
+ *   every used pixel makes the cadence singular (status 3) through the pivot cut; there is no status of its own.
+ *   LK_EINVAL: as lk_cube_psf_photometry_batch_dev without the sigma case, and n_prf, Ty, Tx or oversample < 1, a prf_index
+ *   outside 0 .. n_prf - 1, n_prf os^2 ceil(Ty / os) ceil(Tx / os) >= 2^30, max(ny, nx) os >= 2^30, or a cutout too large for
+ *   the LDS of one workgroup: tile + images must not exceed 160 KiB, where tile = 16 x 8 pitch + npix (4 pitch instead of 8 with
+ *   use_flux_err == 0), pitch = npix rounded up to 4 x an odd number, and images = 8 S_max npix without shifts, 16 x (8 mpitch +
+ *   128 S_max) with them, mpitch = S_max npix rounded up to 4 x an odd number.
+ *   The table is first re-laid in polyphase order, Tp[table][py][px][Y][X] = T[table][Y os + py][X os + px], so that each of
+ *   the 16 taps of a cutout's pixels is one contiguous sub-image.  Without shifts a star's image is the same at every cadence:
+ *   one workgroup per cutout forms the S images once, and the fit kernel — the four-lanes-per-cadence workgroup of
+ *   lk_cube_psf_photometry_batch_dev, instantiated on S — copies them to LDS.  With shifts the fit kernel forms the images of
+ *   its 16 cadences itself, lane = pixel, and parks them in LDS for both walks.  No atomics; the order of every sum depends on
+ *   the cutout's own data alone, so a cutout's outputs have the same bits alone, at any batch position, with prf_index NULL,
+ *   shared or per cutout, and from run to run.  Scratch: B x (2 S_max + 2) x 8 + 16 B + 4 n_prf os^2 ceil(Ty / os) ceil(Tx / os)
+ *   bytes of the handle's arena, and 8 B S_max npix more without shifts.  Enqueued, no synchronisation. */
+int lk_cube_prf_photometry_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
+                                     const float *flux_err, const uint8_t *mask, int mask_stride, int S_max,
+                                     const double *star_col, const double *star_row, const float *prf_table, int n_prf, int Ty,
+                                     int Tx, int oversample, const int32_t *prf_index, const double *shift_col,
+                                     const double *shift_row, double column0, double row0, int use_flux_err, int32_t *star_off,
+                                     double *time_out, double *flux_out, double *flux_err_out, double *background, double *chi2,
+                                     int32_t *n_used, int8_t *cadence_status, int32_t *status, void *stream);
+
 /* lk_cube_psf_fit_batch_dev <- PSF photometry that fits each cadence's pointing shift (PixelCube.psf_fit is the numpy mirror and the
  *   definition): per cadence the fluxes of up to 8 stars, one constant background and ONE common (column, row) shift u = (dc, dr)
  *   of all stars, by variable projection in Kaufman's form.  The per-cadence motion shift of TargetPixelFile.to_lightcurve(method=

@@ -403,9 +403,10 @@ def amplitude_images_batch(cubes, frequency, device=0, **kwargs):
     return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).amplitude_images(frequency, **kwargs)
 
 
-def psf_photometry_batch(cubes, star_col, star_row, sigma, device=0, **kwargs):
+def psf_photometry_batch(cubes, star_col, star_row, sigma=None, device=0, **kwargs):
     """``PixelCube.psf_photometry`` of every cutout, for host cutouts: ``cubes`` a list of same-shaped float32 ``PixelCube``s,
-    ``star_col`` / ``star_row`` [S] or [B, S] (NaN = no star), ``sigma`` a scalar, a pair or [B, 2].  One upload
+    ``star_col`` / ``star_row`` [S] or [B, S] (NaN = no star), ``sigma`` a scalar, a pair or [B, 2] — or ``prf=`` a
+    ``TabulatedPRF`` (and ``prf_index=``) in its place.  One upload
     (``DevicePixelCubeBatch.from_cubes``), then ``DevicePixelCubeBatch.psf_photometry`` with its keywords; returns its
     ``(lcs, info)``: the resident light curves, one per star, and ``info`` as host arrays unless ``to_host=False`` is passed.
     Not sharded over ranks."""

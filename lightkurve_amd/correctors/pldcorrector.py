@@ -240,6 +240,94 @@ def _psf_backward(L, Y):
     return X
 
 
+class TabulatedPRF(object):
+    """A tabulated, pixel-integrated PRF and its interpolation — the model of ``psf_photometry(prf=)``, plain numpy, and the
+    definition of what ``lk_cube_prf_photometry_batch_dev`` evaluates on the device.  ``samples``: [Ty, Tx] or [n_prf, Ty, Tx],
+    kept as float32 (as the mission files are); every value finite; Ty, Tx >= 1, no parity requirement.  ``oversample``: an
+    integer os >= 1.  Sample (j, i) is the fraction of a star's flux collected by a pixel whose centre lies ((i - (Tx - 1) / 2) /
+    os, (j - (Ty - 1) / 2) / os) px from the star's centre.  Nothing is normalised.  The value at an offset (dx, dy) is Keys' cubic
+    convolution (a = -1/2, Catmull-Rom) on the table continued by zeros, all in float64: u = dx os + (Tx - 1) / 2, i0 = floor(u),
+    f = u - i0 (likewise v, j0, g), w_-1 = ((-f + 2) f - 1) f / 2, w_0 = ((3 f - 5) f f + 2) / 2, w_1 = ((-3 f + 4) f + 1) f / 2,
+    w_2 = (f - 1) f f / 2, P = sum_jj w_jj(g) (sum_ii w_ii(f) T[j0 + jj][i0 + ii]), ii and jj from -1 to 2 in that order, T = 0
+    outside the table.  os is an integer, so the pixels of an image share f and g: i0 and f are formed ONCE per axis, at pixel 0
+    (dx = 0 - col), and pixel ix reads the taps i0 + ix os + ii.  A centre with |u| >= 1e9 or NaN has no tap on the table (f = 0).
+    No file is read and the five corner tables of a channel are not blended: the caller passes the blended array."""
+
+    FAR = 1e9
+
+    def __init__(self, samples, oversample):
+        s = np.asarray(samples)
+        if s.ndim == 2:
+            s = s[None]
+        if s.ndim != 3 or min(s.shape) < 1:
+            raise ValueError("samples must be [Ty, Tx] or [n_prf, Ty, Tx] with every size >= 1 (got shape %r)" % (np.shape(samples),))
+        with np.errstate(all="ignore"):
+            s = np.array(s, dtype=np.float32, order="C")
+        if not np.all(np.isfinite(s)):
+            raise ValueError("every sample of a PRF table must be finite (as float32)")
+        if isinstance(oversample, bool) or int(oversample) != oversample or int(oversample) < 1:
+            raise ValueError("oversample must be an integer >= 1 (got %r)" % (oversample,))
+        s.setflags(write=False)
+        self.samples, self.oversample = s, int(oversample)
+
+    @property
+    def n_prf(self):
+        return self.samples.shape[0]
+
+    @classmethod
+    def from_gaussian(cls, sigma_col, sigma_row, oversample, half_width):
+        """The pixel-integrated Gaussian of ``psf_photometry(sigma=)`` sampled on a table that reaches ``half_width`` px to every
+        side of the centre: 2 round(half_width os) + 1 samples per axis."""
+        import math
+        sig_c, sig_r = _psf_sigma((sigma_col, sigma_row))
+        os_ = int(oversample)
+        if os_ != oversample or os_ < 1 or not half_width * os_ >= 0.5:
+            raise ValueError("need an integer oversample >= 1 and half_width * oversample >= 1/2")
+        d = np.arange(-int(round(half_width * os_)), int(round(half_width * os_)) + 1) / float(os_)
+        erf = np.vectorize(math.erf, otypes=[np.float64])
+        gx = 0.5 * (erf((d + 0.5) / (np.sqrt(2.0) * sig_c)) - erf((d - 0.5) / (np.sqrt(2.0) * sig_c)))
+        gy = 0.5 * (erf((d + 0.5) / (np.sqrt(2.0) * sig_r)) - erf((d - 0.5) / (np.sqrt(2.0) * sig_r)))
+        return cls(gy[:, None] * gx[None, :], os_)
+
+    def _check_index(self, index):
+        if isinstance(index, (bool, np.bool_)) or np.ndim(index) != 0 or int(index) != index or not 0 <= int(index) < self.n_prf:
+            raise ValueError("prf_index must be an integer 0 .. %d (got %r)" % (self.n_prf - 1, index))
+        return int(index)
+
+    def _axis(self, c, n, size):
+        """One axis: centres ``c`` (any shape, px from the centre of pixel 0), ``n`` pixels, ``size`` samples -> the table
+        indices c.shape + (n, 4) of the four taps of every pixel (``size`` = the zero beyond the table) and the weights
+        c.shape + (4,)."""
+        os_ = self.oversample
+        u = (0.0 - np.asarray(c, dtype=np.float64)) * os_ + 0.5 * (size - 1)
+        far = ~(np.abs(u) < self.FAR)
+        fl = np.floor(np.where(far, 0.0, u))
+        f = np.where(far, 0.0, u - fl)
+        w = np.stack([((-f + 2.0) * f - 1.0) * f * 0.5, ((3.0 * f - 5.0) * f * f + 2.0) * 0.5,
+                      ((-3.0 * f + 4.0) * f + 1.0) * f * 0.5, (f - 1.0) * f * f * 0.5], axis=-1)
+        idx = fl.astype(np.int64)[..., None, None] - 1 + np.arange(4) + (np.arange(n) * os_)[:, None]
+        return np.where(far[..., None, None] | (idx < 0) | (idx >= size), size, idx), w
+
+    def evaluate(self, shape, col, row, index=0):
+        """The model image(s) of a star of unit flux centred (``col``, ``row``) px from the centre of pixel (0, 0) of a (ny, nx)
+        image: float64 of shape broadcast(col, row).shape + (ny, nx)."""
+        ny, nx = (int(v) for v in shape)
+        _, Ty, Tx = self.samples.shape
+        T = np.zeros((Ty + 1, Tx + 1))
+        T[:Ty, :Tx] = self.samples[self._check_index(index)]
+        col, row = np.broadcast_arrays(np.asarray(col, dtype=np.float64), np.asarray(row, dtype=np.float64))
+        with np.errstate(all="ignore"):
+            jx, wx = self._axis(col, nx, Tx)
+            jy, wy = self._axis(row, ny, Ty)
+            acc = np.zeros(col.shape + (ny, nx))
+            for jj in range(4):
+                r = np.zeros(col.shape + (ny, nx))
+                for ii in range(4):
+                    r = r + wx[..., None, None, ii] * T[jy[..., :, None, jj], jx[..., None, :, ii]]
+                acc = acc + wy[..., None, None, jj] * r
+        return acc
+
+
 class PixelCube(object):
     """Minimal stand-in for the slice of TargetPixelFile that PLDCorrector touches."""
 
@@ -492,11 +580,12 @@ class PixelCube(object):
         out["status"] = status if status else 3 if np.isnan(out["offset_pix"]) else 0
         return out
 
-    def psf_photometry(self, star_col, star_row, sigma, shifts=None, aperture_mask="all", column=0, row=0, use_flux_err=True):
+    def psf_photometry(self, star_col, star_row, sigma=None, shifts=None, aperture_mask="all", column=0, row=0, use_flux_err=True,
+                       prf=None, prf_index=0):
         """Deblended PSF photometry per cadence: the fluxes of up to 8 stars at KNOWN positions and one constant background, by
         weighted linear least squares on every cadence's image (the host mirror of ``DevicePixelCubeBatch.psf_photometry`` and
         its definition, float64 numpy after the float32 load).  The linear form of ``TargetPixelFile.to_lightcurve(method=
-        "prf")``: nothing about the PSF is fitted, and it is a pixel-integrated Gaussian, not a tabulated PRF.
+        "prf")``: nothing about the PSF is fitted; it is a pixel-integrated Gaussian (``sigma``) or a tabulated PRF (``prf``, below).
         ``star_col`` / ``star_row`` [S]: positions in the coordinates of ``estimate_centroids`` — pixel (iy, ix) covers
         [column + ix - 1/2, column + ix + 1/2] x [row + iy - 1/2, row + iy + 1/2]; a star with a NaN coordinate is left out.
         ``sigma``: a scalar or (sigma_col, sigma_row), pixels.  ``shifts``: None or (shift_col[N], shift_row[N]), added to every
@@ -509,8 +598,17 @@ class PixelCube(object):
         theta_S; ``chi2`` (N,) = sum w (y - A theta)^2; ``n_used`` (N,) int32, the used pixels; ``cadence_status`` (N,) int8: 0
         ok, 1 the time or a shift is not finite, 2 n_used < S + 2, 3 singular (a cadence that is not ok is NaN in the four float
         outputs; nothing is raised); ``status``: 0, or 1 when no cadence is ok; ``star_index`` (S,): the stars that took part;
-        ``min_pivot_ratio`` (N,): the smallest d_k / G_kk of the factorisation (0 for a pivot that is not finite)."""
+        ``min_pivot_ratio`` (N,): the smallest d_k / G_kk of the factorisation (0 for a pivot that is not finite).
+        ``prf``: a ``TabulatedPRF`` in place of ``sigma`` (exactly one of the two, else ``ValueError``), ``prf_index`` its table:
+        g[iy, ix] = ``prf.evaluate`` at the star's position (column + ix - star_col[s] - shift_col[n] from the pixel's centre);
+        everything else is the same.  A star whose model is zero on every used pixel makes its cadences singular (status 3)."""
         import math
+        if (sigma is None) == (prf is None):
+            raise ValueError("psf_photometry takes exactly one of sigma and prf")
+        if prf is not None:
+            if not isinstance(prf, TabulatedPRF):
+                raise ValueError("prf must be a TabulatedPRF (got %r)" % (type(prf),))
+            prf_index = prf._check_index(prf_index)
         col, rw = np.atleast_1d(np.asarray(star_col, dtype=np.float64)), np.atleast_1d(np.asarray(star_row, dtype=np.float64))
         if col.ndim != 1 or col.shape != rw.shape:
             raise ValueError("star_col and star_row must be 1-D arrays of one length (got %r and %r)" % (col.shape, rw.shape))
@@ -521,7 +619,8 @@ class PixelCube(object):
             raise ValueError("psf_photometry fits 1 .. 8 stars per cutout (got %d)" % S)
         if not (np.all(np.isfinite(col)) and np.all(np.isfinite(rw))):
             raise ValueError("a star position is infinite")
-        sig_c, sig_r = _psf_sigma(sigma)
+        if prf is None:
+            sig_c, sig_r = _psf_sigma(sigma)
         N, ny, nx = self.shape
         npix, K = ny * nx, S + 1
         if shifts is None:
@@ -538,11 +637,15 @@ class PixelCube(object):
             return 0.5 * (E[..., 1:] - E[..., :-1])
 
         with np.errstate(all="ignore"):
-            g_col = factors(col[:, None] + dc[None, :] - column, sig_c, nx)
-            g_row = factors(rw[:, None] + dr[None, :] - row, sig_r, ny)
             A = np.empty((N, npix, K))
-            for s in range(S):
-                A[:, :, s] = (g_col[s][:, None, :] * g_row[s][:, :, None]).reshape(-1, npix)
+            if prf is None:
+                g_col = factors(col[:, None] + dc[None, :] - column, sig_c, nx)
+                g_row = factors(rw[:, None] + dr[None, :] - row, sig_r, ny)
+                for s in range(S):
+                    A[:, :, s] = (g_col[s][:, None, :] * g_row[s][:, :, None]).reshape(-1, npix)
+            else:
+                g = prf.evaluate((ny, nx), col[:, None] + dc[None, :] - column, rw[:, None] + dr[None, :] - row, prf_index)
+                A[:, :, :S] = g.reshape(S, -1, npix).transpose(1, 2, 0)
             A[:, :, S] = 1.0
             y32 = np.asarray(self.flux).reshape(N, npix)
             used = ap[None, :] & np.isfinite(y32)

@@ -2334,6 +2334,21 @@ int lk_cube_psf_photometry_batch_dev(lk_handle *h, int B, int N, int ny, int nx,
                                    chi2, n_used, cadence_status, status, static_cast<hipStream_t>(stream));
 }
 
+int lk_cube_prf_photometry_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
+                                     const float *flux_err, const uint8_t *mask, int mask_stride, int S_max,
+                                     const double *star_col, const double *star_row, const float *prf_table, int n_prf, int Ty,
+                                     int Tx, int oversample, const int32_t *prf_index, const double *shift_col,
+                                     const double *shift_row, double column0, double row0, int use_flux_err, int32_t *star_off,
+                                     double *time_out, double *flux_out, double *flux_err_out, double *background, double *chi2,
+                                     int32_t *n_used, int8_t *cadence_status, int32_t *status, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_prfphot_launch(h, B, N, ny, nx, time, flux, flux_err, mask, mask_stride, S_max, star_col, star_row, prf_table,
+                                   n_prf, Ty, Tx, oversample, prf_index, shift_col, shift_row, column0, row0, use_flux_err, star_off,
+                                   time_out, flux_out, flux_err_out, background, chi2, n_used, cadence_status, status,
+                                   static_cast<hipStream_t>(stream));
+}
+
 int lk_cube_psf_fit_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
                               const float *flux_err, const uint8_t *mask, int mask_stride, int S_max, const double *star_col,
                               const double *star_row, const double *sigma, const double *shift0_col, const double *shift0_row,

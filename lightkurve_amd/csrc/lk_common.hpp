@@ -441,6 +441,14 @@ int cube_psfphot_launch(lk_handle *h, int B, int N, int ny, int nx, const double
                         const double *sigma_host, const double *shift_col, const double *shift_row, double column0, double row0,
                         int use_flux_err, int32_t *star_off_host, double *time_out, double *flux_out, double *flux_err_out, double *background,
                         double *chi2, int32_t *n_used, int8_t *cadence_status, int32_t *status, hipStream_t stream);
+// prfphot.hip: cube_psfphot_launch with a tabulated PRF in place of the widths — prf_table DEVICE float32 [n_prf][Ty][Tx],
+// prf_index_host HOST [B] or NULL (table 0); Keys' cubic convolution on the table continued by zeros (lkhip.h)
+int cube_prfphot_launch(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux, const float *flux_err,
+                        const uint8_t *mask, int mask_stride, int S_max, const double *star_col_host, const double *star_row_host,
+                        const float *prf_table, int n_prf, int Ty, int Tx, int oversample, const int32_t *prf_index_host,
+                        const double *shift_col, const double *shift_row, double column0, double row0, int use_flux_err,
+                        int32_t *star_off_host, double *time_out, double *flux_out, double *flux_err_out, double *background,
+                        double *chi2, int32_t *n_used, int8_t *cadence_status, int32_t *status, hipStream_t stream);
 // psffit.hip: the same fit with one common (column, row) shift per cadence fitted next to the fluxes, by variable projection from
 // shift0 (nullable device arrays): fluxes, background and chi2 at the fitted shift, the shifts, their errors, the iterations
 // taken and the last step.  Everything but the stars on the device; enqueued, no synchronisation

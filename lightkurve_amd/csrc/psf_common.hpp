@@ -1,4 +1,4 @@
-// psf_common.hpp — what psfphot.hip (fluxes at given positions), psffit.hip (fluxes and a common shift per cadence), psfwidth.hip
+// psf_common.hpp — what psfphot.hip (fluxes at given positions), prfphot.hip (the same with a tabulated PRF), psffit.hip (fluxes and a common shift per cadence), psfwidth.hip
 // (the width of a cutout) and psfpos.hip (the positions of a cutout's stars) share: the cadence-per-four-lanes mapping, the
 // Gaussian's edge integral, the table of factors and their derivatives by the centre (psffit.hip and psfpos.hip), the sums over
 // a cadence's lanes, a tile's cadences and a wavefront, the Cholesky without pivoting with its singularity test, and the
@@ -120,7 +120,7 @@ template <int K> __device__ __forceinline__ void psf_variances(const double (&L)
 }
 
 // The stars of a batch as the kernels read them.  par [B][2 S_max + 2]: star columns, star rows (the cutout's stars — no NaN
-// coordinate — first and in order), sigma_col, sigma_row.  ints = order | n_stars | star_off, B each: order lists the cutouts
+// coordinate — first and in order), sigma_col, sigma_row (NaN for a NULL sigma_host: prfphot.hip's model has no width).  ints = order | n_stars | star_off, B each: order lists the cutouts
 // grouped by their star count, those of S stars at order[first[S] .. first[S + 1]); star_off the first output row of a cutout.
 struct PsfStars {
     std::vector<double> par;
@@ -147,7 +147,7 @@ inline int psf_group_stars(int B, int S_max, const double *star_col_host, const 
             ++S;
         }
         LK_REQUIRE(S >= 1, "cutout %d has no star", b);
-        for (int k = 0; k < 2; ++k) {
+        for (int k = 0; sigma_host && k < 2; ++k) {
             const double sg = sigma_host[2 * (size_t)b + k];
             LK_REQUIRE(std::isfinite(sg) && sg > 0.0, "cutout %d: sigma must be finite and > 0 (got %g)", b, sg);
             p[2 * S_max + k] = sg;

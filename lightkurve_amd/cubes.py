@@ -29,7 +29,8 @@ def _first_finite_times(time):
 
 def _psf_stars(B, star_col, star_row, sigma):
     """The stars and widths of the PSF calls, checked -> ((star_col, star_row) as C-contiguous float64 [B, S_max], the bool [B,
-    S_max] of the stars that take part (no NaN coordinate), sigma float64 [B, 2], S_max)."""
+    S_max] of the stars that take part (no NaN coordinate), sigma float64 [B, 2] (None for ``sigma`` None: a call with a
+    tabulated PRF), S_max)."""
     from .correctors.pldcorrector import _psf_sigma
     pos = []
     for name, a in (("star_col", star_col), ("star_row", star_row)):
@@ -47,9 +48,23 @@ def _psf_stars(B, star_col, star_row, sigma):
         raise ValueError("a star position is infinite")
     if not np.all(part.any(axis=1)):
         raise ValueError("cutouts %s have no star" % np.flatnonzero(~part.any(axis=1)).tolist())
+    if sigma is None:
+        return pos, part, None, pos[0].shape[1]
     sg = np.asarray(sigma, dtype=np.float64)
     sg = np.array([_psf_sigma(s) for s in sg]) if sg.shape == (B, 2) else np.tile(_psf_sigma(sg), (B, 1))
     return pos, part, np.ascontiguousarray(sg, dtype=np.float64), pos[0].shape[1]
+
+
+def _prf_device_table(prf, handle, stream):
+    """``prf.samples`` in HBM: uploaded once per handle and kept on the ``TabulatedPRF`` (synchronised, so that later calls on
+    any stream of the handle may read it)."""
+    cache = prf.__dict__.setdefault("_device", {})
+    hit = cache.get(handle.device)
+    if hit is None or hit[0] is not handle:
+        buf, _ = _upload(handle, prf.samples, stream, np.float32)
+        _capi._check(_capi._lib.lk_stream_synchronize(handle._h, _vp(stream or None)))
+        hit = cache[handle.device] = (handle, buf)
+    return hit[1]
 
 
 # ``info`` of the PSF calls: (key, dtype), B x N values each but ``status`` (B)
@@ -742,8 +757,8 @@ class DevicePixelCubeBatch(object):
         return out
 
     # ---------------------------------------------------------------- PSF photometry
-    def psf_photometry(self, star_col, star_row, sigma, shifts=None, aperture_mask="all", column=0, row=0, use_flux_err=True,
-                       to_host=False):
+    def psf_photometry(self, star_col, star_row, sigma=None, shifts=None, aperture_mask="all", column=0, row=0, use_flux_err=True,
+                       to_host=False, prf=None, prf_index=None):
         """Deblended PSF photometry per cadence of every cutout: the light curves of up to 8 blended stars at KNOWN positions,
         each without its neighbours, and a constant background — a weighted linear least-squares fit of pixel-integrated
         Gaussians to every cadence's image (``lk_cube_psf_photometry_batch_dev``; the numpy mirror and the definition is
@@ -768,8 +783,28 @@ class DevicePixelCubeBatch(object):
         ``cadence_status`` (B x N int8: 0 ok, 1 the time or a shift is not finite, 2 n_used < S + 2, 3 singular), ``status`` (B
         int32: 1 when no cadence is ok) and ``star_off`` (B + 1 int32) — ``DeviceBuffer``s enqueued on the batch's stream, or
         host arrays with ``to_host=True``.  Nothing is raised per cadence.  A cutout's outputs have the same bits alone, at any
-        batch position and from run to run."""
+        batch position and from run to run.
+        ``prf``: a ``TabulatedPRF`` in place of ``sigma`` (exactly one of the two, else ``ValueError``) — the model of every star
+        is then interpolated from the table by Keys' cubic convolution (``lk_cube_prf_photometry_batch_dev``; the definition is
+        ``TabulatedPRF``), which carries the wings and asymmetries of a mission PRF that no Gaussian width reproduces.  The
+        table goes up once and stays on the ``TabulatedPRF``.  ``prf_index``: None (table 0), a scalar or [B], the table of every
+        cutout.  Everything else, the return value included, is the same; ``psf_fit``, ``psf_width`` and ``psf_positions`` do
+        not take a table."""
+        from .correctors.pldcorrector import TabulatedPRF
         h, (B, N, ny, nx) = self.handle, self.shape
+        if (sigma is None) == (prf is None):
+            raise ValueError("psf_photometry takes exactly one of sigma and prf")
+        if prf is not None:
+            if not isinstance(prf, TabulatedPRF):
+                raise ValueError("prf must be a TabulatedPRF (got %r)" % (type(prf),))
+            pidx = np.zeros(B, dtype=np.int32) if prf_index is None else np.asarray(prf_index)
+            if pidx.ndim > 1 or (pidx.ndim == 1 and pidx.size != B) or pidx.dtype.kind not in "iu":
+                raise ValueError("prf_index must be an integer or one integer per cutout (%d)" % B)
+            if np.any(pidx < 0) or np.any(pidx >= prf.n_prf):
+                raise ValueError("prf_index must be 0 .. %d" % (prf.n_prf - 1))
+            pidx = np.ascontiguousarray(np.broadcast_to(pidx, (B,)), dtype=np.int32)
+        elif prf_index is not None:
+            raise ValueError("prf_index needs prf")
         pos, part, sg, S_max = _psf_stars(B, star_col, star_row, sigma)
         keep = []
         d_shift = self._psf_shift_buffers(shifts, "shifts", keep)
@@ -779,12 +814,21 @@ class DevicePixelCubeBatch(object):
         d_t, d_f, d_e = (DeviceBuffer(h, rows * N * 8) for _ in range(3))
         info = {key: DeviceBuffer(h, size) for key, _, size in _psf_info_spec(B, N, _PSF_INFO)}
         star_off = np.zeros(B + 1, dtype=np.int32)
-        _capi._check(_capi._lib.lk_cube_psf_photometry_batch_dev(
-            h._h, B, N, ny, nx, _p(self.d_time), _p(self.d_flux), _p(self.d_flux_err), _p(d_mask), stride, S_max,
-            pos[0].ctypes.data_as(_dp), pos[1].ctypes.data_as(_dp), sg.ctypes.data_as(_dp), _p(d_shift[0]), _p(d_shift[1]),
-            float(column), float(row), int(bool(use_flux_err)), star_off.ctypes.data_as(_i32p), _p(d_t), _p(d_f), _p(d_e),
-            _p(info["background"]), _p(info["chi2"]), _p(info["n_used"]), _p(info["cadence_status"]), _p(info["status"]),
-            _vp(self.stream or None)))
+        if prf is None:
+            _capi._check(_capi._lib.lk_cube_psf_photometry_batch_dev(
+                h._h, B, N, ny, nx, _p(self.d_time), _p(self.d_flux), _p(self.d_flux_err), _p(d_mask), stride, S_max,
+                pos[0].ctypes.data_as(_dp), pos[1].ctypes.data_as(_dp), sg.ctypes.data_as(_dp), _p(d_shift[0]), _p(d_shift[1]),
+                float(column), float(row), int(bool(use_flux_err)), star_off.ctypes.data_as(_i32p), _p(d_t), _p(d_f), _p(d_e),
+                _p(info["background"]), _p(info["chi2"]), _p(info["n_used"]), _p(info["cadence_status"]), _p(info["status"]),
+                _vp(self.stream or None)))
+        else:
+            n_prf, Ty, Tx = prf.samples.shape
+            _capi._check(_capi._lib.lk_cube_prf_photometry_batch_dev(
+                h._h, B, N, ny, nx, _p(self.d_time), _p(self.d_flux), _p(self.d_flux_err), _p(d_mask), stride, S_max,
+                pos[0].ctypes.data_as(_dp), pos[1].ctypes.data_as(_dp), _p(_prf_device_table(prf, h, self.stream)), n_prf, Ty, Tx,
+                prf.oversample, pidx.ctypes.data_as(_i32p), _p(d_shift[0]), _p(d_shift[1]), float(column), float(row),
+                int(bool(use_flux_err)), star_off.ctypes.data_as(_i32p), _p(d_t), _p(d_f), _p(d_e), _p(info["background"]),
+                _p(info["chi2"]), _p(info["n_used"]), _p(info["cadence_status"]), _p(info["status"]), _vp(self.stream or None)))
         return self._psf_results(pos, part, (d_t, d_f, d_e), keep + [d for d in d_shift if d is not None], info, _PSF_INFO,
                                  star_off, to_host)
 

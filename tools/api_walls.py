@@ -164,6 +164,14 @@ over the first `LK_WALLS_MIRROR_B` (default 16) cutouts, scaled to the batch in 
 synchronise.  Written to profiles/psfpos_walls.txt.  `psfpos_trace`: P and W twice and nothing else, for `rocprofv3 --kernel-trace
 --stats` (profiles/psfpos_kernel_stats.txt).
 
+`prfphot`: PSF photometry with a tabulated PRF on the same batch shape and star count, the cubes rendered by the Gaussian of width
+1.1 px with true shifts uniform in +-0.3 px, the table `TabulatedPRF.from_gaussian(1.1, 1.1, 50, 5.5)` (os = 50, 551 x 551), in ONE
+process, the routes alternating, `LK_WALLS_REPS` (default 5) times after one warm-up.  P `cubes.psf_photometry(star_col, star_row,
+prf=)`, Ps the same with resident shifts; G / Gs `cubes.psf_photometry(star_col, star_row, sigma)` of the same cubes, the yardstick;
+H / Hs the mirror `PixelCube.psf_photometry(prf=)` per cutout on 16 threads over the first `LK_WALLS_MIRROR_B` (default 16) cutouts,
+scaled to the batch in the report.  Every timed region ends with a synchronise.  Written to profiles/prfphot_walls.txt.
+`prfphot_trace`: P and Ps twice and nothing else, for `rocprofv3 --kernel-trace --stats` (profiles/prfphot_kernel_stats.txt).
+
 `background`: the per-cadence background of the same batch shape with 'background' masks, in ONE process, the routes alternating,
 `LK_WALLS_REPS` (default 5) times after one warm-up.  F `cubes.subtract_background()` (median images, masks, the fused estimate +
 subtraction) and Fm the same with the masks given; E `cubes.estimate_background()`, Em with the masks given, Es with the scatter
@@ -1507,6 +1515,87 @@ def psfphot(which):
         "profiles/psfphot_kernel_stats.txt" % (B, med["H"] * B / Bm / med["R"], med["Hs"] * B / Bm / med["Rs"], floor / 1e6)])
 
 
+def prfphot(which):
+    from concurrent.futures import ThreadPoolExecutor
+    from scipy.special import erf
+    from lightkurve_amd.correctors import TabulatedPRF
+    from lightkurve_amd.device import DevicePixelCubeBatch
+    B, N, side, S = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "500"), ("LK_WALLS_N", "4000"), ("LK_WALLS_SIDE", "11"),
+                                                            ("LK_WALLS_STARS", "4")))
+    reps, Bm = int(os.environ.get("LK_WALLS_REPS", "5")), min(B, int(os.environ.get("LK_WALLS_MIRROR_B", "16")))
+    rng = np.random.default_rng(71)
+    npix = side * side
+    t = 1000.0 + np.arange(N) / 720.0                                    # two-minute cadences
+    sigma = 1.1
+    prf = TabulatedPRF.from_gaussian(sigma, sigma, 50, 5.5)
+    cells = int(np.ceil(np.sqrt(S)))
+    lattice = np.array([((i + 0.5) * side / cells - 0.5, (j + 0.5) * side / cells - 0.5) for j in range(cells) for i in range(cells)][:S])
+    col = lattice[None, :, 0] + rng.uniform(-0.3, 0.3, (B, S))
+    row = lattice[None, :, 1] + rng.uniform(-0.3, 0.3, (B, S))
+    shifts = (rng.uniform(-0.3, 0.3, (B, N)), rng.uniform(-0.3, 0.3, (B, N)))     # the true pointing of every cadence
+    edges = np.arange(side + 1) - 0.5
+    flux = np.empty((B, N, side, side), dtype=np.float32)
+    for b in range(B):                                                  # every cadence rendered at its own shift
+        gx = np.diff(erf((edges[None, None, :] - col[b][None, :, None] - shifts[0][b][:, None, None]) / (np.sqrt(2) * sigma)), axis=2) / 2
+        gy = np.diff(erf((edges[None, None, :] - row[b][None, :, None] - shifts[1][b][:, None, None]) / (np.sqrt(2) * sigma)), axis=2) / 2
+        img = 100.0 + np.einsum("s,nsy,nsx->nyx", rng.uniform(2000.0, 20000.0, S), gy, gx)
+        flux[b] = img.astype(np.float32) + 3.0 * rng.standard_normal((N, side, side), dtype=np.float32)
+    err = np.full_like(flux, 3.0)
+    cubes = DevicePixelCubeBatch.from_arrays(np.tile(t, (B, 1)), flux, err)
+    cubes.synchronize()
+    del flux, err
+    d_shifts = tuple(_upload_f64(cubes, a) for a in shifts)
+
+    def resident(sh=None, table=True):
+        out = cubes.psf_photometry(col, row, shifts=sh, prf=prf) if table else cubes.psf_photometry(col, row, sigma, shifts=sh)
+        cubes.synchronize()
+        return out
+
+    if "prfphot_trace" in which:
+        for _ in range(2):
+            resident()
+            resident(d_shifts)
+        return
+
+    host_m = cubes.to_host()[:Bm]
+
+    def mirror(with_shifts=False):
+        def one(b):
+            return host_m[b].psf_photometry(col[b], row[b], prf=prf, shifts=(shifts[0][b], shifts[1][b]) if with_shifts else None)
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            return list(ex.map(one, range(Bm)))
+
+    fns = {"P": resident, "Ps": lambda: resident(d_shifts), "G": lambda: resident(None, False), "Gs": lambda: resident(d_shifts, False),
+           "H": mirror, "Hs": lambda: mirror(True)}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    dev = {k: first[k][0].flux_host().reshape(B * S, N)[:Bm * S].reshape(Bm, S, N) for k in ("P", "Ps", "G", "Gs")}
+    rel = {}
+    for k, other in (("P", "H"), ("Ps", "Hs"), ("Ps", "Gs")):
+        h = dev[other] if other in dev else np.stack([o["flux"] for o in first[other]])
+        rel[k + " - " + other] = float(np.max(np.abs(dev[k] - h) / np.max(np.abs(h), axis=(1, 2), keepdims=True)))
+    first.clear()
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    floor = B * N * npix * 8 + B * N * (3 * S * 8 + 8 + 8 + 4 + 1)
+    write_walls("prfphot_walls.txt", [
+        "PSF photometry with a tabulated PRF, %d cutouts x %d cadences x %d x %d float32, %d stars per cutout, table %d x %d at os = %d "
+        "from the Gaussian of %.1f px (%.1f MB of flux and flux_err resident, read once; %.1f MB of outputs)"
+        % ((B, N, side, side, S) + prf.samples.shape[1:] + (prf.oversample, sigma, B * N * npix * 8 / 1e6, (floor - B * N * npix * 8) / 1e6)),
+        "  P    cubes.psf_photometry(star_col, star_row, prf=): polyphase table, images per cutout, fit, statuses; resident  %s" % spread(ts["P"]),
+        "  Ps   the same with shifts=(DeviceBuffer, DeviceBuffer): images per cadence, formed in the fit kernel               %s" % spread(ts["Ps"]),
+        "  G    cubes.psf_photometry(star_col, star_row, sigma) of the same cubes, the same run                               %s" % spread(ts["G"]),
+        "  Gs   the same with the same shifts                                                                                 %s" % spread(ts["Gs"]),
+        "  H    PixelCube.psf_photometry(prf=) on 16 threads, the first %d cutouts only                                       %s" % (Bm, spread(ts["H"])),
+        "  Hs   the same with shifts                                                                                          %s" % spread(ts["Hs"]),
+        "  max |flux difference| / max |flux| of the cutout over the first %d cutouts: %s" % (Bm, ", ".join("%s %.2e" % kv for kv in rel.items())),
+        "  P / G = %.2f; Ps / Gs = %.2f; H scaled to %d cutouts / P = %.0f; Hs scaled / Ps = %.0f; floor bytes of the fit kernel %.1f MB; "
+        "kernel times alone: profiles/prfphot_kernel_stats.txt"
+        % (med["P"] / med["G"], med["Ps"] / med["Gs"], B, med["H"] * B / Bm / med["P"], med["Hs"] * B / Bm / med["Ps"], floor / 1e6)])
+
+
 def psffit(which):
     from concurrent.futures import ThreadPoolExecutor
     from scipy.special import erf
@@ -2034,6 +2123,8 @@ def main():
         background()
     if {"psfphot", "psfphot_trace"} & set(which):
         psfphot(which)
+    if {"prfphot", "prfphot_trace"} & set(which):
+        prfphot(which)
     if {"psffit", "psffit_trace"} & set(which):
         psffit(which)
     if {"psfwidth", "psfwidth_trace"} & set(which):
