@@ -1339,7 +1339,8 @@ int lk_cube_prf_photometry_batch_dev(lk_handle *h, int B, int N, int ny, int nx,
 /* lk_cube_psf_fit_batch_dev <- PSF photometry that fits each cadence's pointing shift (PixelCube.psf_fit is the numpy mirror and the
  *   definition): per cadence the fluxes of up to 8 stars, one constant background and ONE common (column, row) shift u = (dc, dr)
  *   of all stars, by variable projection in Kaufman's form.  The per-cadence motion shift of TargetPixelFile.to_lightcurve(method=
- *   "prf"); per-star positions, the PSF width, tabulated PRFs, rotation and a background gradient are not fitted.
+ *   "prf"); per-star positions, the PSF width, rotation and a background gradient are not fitted; with a tabulated PRF in place
+ *   of the Gaussian the call is lk_cube_prf_fit_batch_dev.
  *   Inputs, stars, sigma, mask, PSF, used pixels, weights, design A(u) = [g_0 ... g_{S-1}, 1], K = S + 1, and the output rows are
  *   those of lk_cube_psf_photometry_batch_dev.  shift0_col / shift0_row (nullable, both or neither): DEVICE arrays [B][N], the
  *   initial shift u0 of every cadence (0 without them).  The used pixels do not depend on u.
@@ -1380,6 +1381,44 @@ int lk_cube_psf_fit_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const 
                               double *background, double *chi2, double *shift_col, double *shift_row, double *shift_col_err,
                               double *shift_row_err, double *last_step, int32_t *n_iter, int32_t *n_used, int8_t *cadence_status,
                               int32_t *status, void *stream);
+
+/* lk_cube_prf_fit_batch_dev <- lk_cube_psf_fit_batch_dev with a TABULATED PRF in place of the Gaussian (PixelCube.psf_fit(prf=) and
+ *   TabulatedPRF.evaluate_with_gradient are the numpy mirror and the definition): the per-cadence shift fitted with the model
+ *   that lk_cube_prf_photometry_batch_dev then takes at shifts = (shift_col, shift_row).  The argument list is
+ *   lk_cube_psf_fit_batch_dev's with sigma replaced by the table arguments of lk_cube_prf_photometry_batch_dev (prf_table DEVICE
+ *   float32 [n_prf][Ty][Tx], oversample, prf_index HOST int32 [B] or NULL).  Steps 1 to 3 of lk_cube_psf_fit_batch_dev, the used
+ *   pixels, the weights, both pivot cuts, the clamp, tol, max_shift, the evaluation at the final u, the statuses 0 .. 5 (2: n_used <
+ *   S + 4) and every output hold word for word, with
+ *     A_s = g_s of lk_cube_prf_photometry_batch_dev at c = star_col[s] + dc - column0, r = star_row[s] + dr - row0, and
+ *     D = [sum_s theta_s dg_s/dc, sum_s theta_s dg_s/dr], s in index order — a shift and a centre enter as one sum, so the
+ *     derivative by the shift is the derivative by the centre: the same 16 taps with the derivative weights of the same f,
+ *       w'_-1 = ((-3 f + 4) f - 1) / 2   w'_0 = (9 f - 10) f / 2   w'_1 = ((-9 f + 8) f + 1) / 2   w'_2 = (3 f - 2) f / 2,
+ *     each times du/dc = -os; dg/dc = sum_jj w_jj(g) (sum_ii w'_ii(f) T), dg/dr = sum_jj w'_jj(g) (sum_ii w_ii(f) T), in the order
+ *     of g.  Keys' interpolant is C1: the derivative is continuous, which is what Gauss-Newton needs.
+ *   A cadence whose stars all have a zero model or a zero derivative on the used pixels fails a pivot cut: status 3.
+ *   LK_EINVAL: where either parent returns it (max_iter outside 1 .. 64, a prf_index outside 0 .. n_prf - 1, max(ny, nx) os >=
+ *   2^30, ...), or a cutout too large for the LDS of one workgroup.  A workgroup holds a tile of 16 cadences, or of 8 where 16 do
+ *   not fit; per cadence 8 (mpitch + dpitch + S + 3) + 192 S + 8 pitch bytes (4 pitch with use_flux_err == 0), plus 8 + npix per
+ *   workgroup, where pitch, mpitch and dpitch are npix, S npix and 2 npix rounded up to 4 x an odd number.  The launch of S stars
+ *   takes 16 cadences when they fit 160 KiB and 8 otherwise; the call is refused, before anything is launched or written, only
+ *   when 8 cadences at S_max do not fit.  At 11 x 11 with flux_err: 16 cadences up to 6 stars (160 513 bytes), 8 cadences at 7
+ *   and 8 (89 601 and 98 881).  A cadence's outputs do not depend on the tile length.
+ *   One workgroup per tile, instantiated on S: 512 threads (eight wavefronts) up to 6 stars, 256 threads (four wavefronts) at 7
+ *   and 8 stars, where the fit's registers leave no room for eight; the polyphase copy of the table is made once per call.  Per
+ *   evaluation all wavefronts form the S model images of every cadence in LDS, wavefront 0 — the four-lanes-per-cadence
+ *   wavefront of lk_cube_psf_fit_batch_dev — solves for theta, all wavefronts form the two theta-weighted derivative images (2
+ *   npix doubles per cadence, not 2 S npix), and wavefront 0 walks again for C, E, g and chi2 and takes the step; the loop runs
+ *   until every cadence of the tile has stopped.  No atomics; a cutout's outputs have the same bits alone, at any batch position,
+ *   with prf_index NULL, shared or per cutout, and from run to run.  Scratch: B x (2 S_max + 2) x 8 + 16 B + 4 n_prf os^2 ceil(Ty /
+ *   os) ceil(Tx / os) bytes of the handle's arena.  Enqueued, no synchronisation. */
+int lk_cube_prf_fit_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
+                              const float *flux_err, const uint8_t *mask, int mask_stride, int S_max, const double *star_col,
+                              const double *star_row, const float *prf_table, int n_prf, int Ty, int Tx, int oversample,
+                              const int32_t *prf_index, const double *shift0_col, const double *shift0_row, int max_iter, double tol,
+                              double max_step, double max_shift, double column0, double row0, int use_flux_err, int32_t *star_off,
+                              double *time_out, double *flux_out, double *flux_err_out, double *background, double *chi2,
+                              double *shift_col, double *shift_row, double *shift_col_err, double *shift_row_err, double *last_step,
+                              int32_t *n_iter, int32_t *n_used, int8_t *cadence_status, int32_t *status, void *stream);
 
 /* lk_cube_psf_width_batch_dev <- the PSF width of every cutout, fitted (PixelCube.psf_width is the numpy mirror and the definition):
  *   ONE pair v = (sigma_col, sigma_row) per cutout, shared by all its cadences, by variable projection in Kaufman's form with the

@@ -385,6 +385,11 @@ SIGNATURES = [
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp,
       _c_dp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
       ctypes.c_int, _c_i32p, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("lk_cube_prf_fit_batch_dev", ctypes.c_int,
+     [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp,
+      _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32p, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+      ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, _c_i32p, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+      _vp, _vp, _vp, _vp, _vp]),
     ("lk_cube_psf_width_batch_dev", ctypes.c_int,
      [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp,
       _c_dp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,

@@ -415,9 +415,10 @@ def psf_photometry_batch(cubes, star_col, star_row, sigma=None, device=0, **kwar
     return DevicePixelCubeBatch.from_cubes(list(cubes), device=device).psf_photometry(star_col, star_row, sigma, **kwargs)
 
 
-def psf_fit_batch(cubes, star_col, star_row, sigma, device=0, **kwargs):
+def psf_fit_batch(cubes, star_col, star_row, sigma=None, device=0, **kwargs):
     """``PixelCube.psf_fit`` of every cutout, for host cutouts: PSF photometry with one common pointing shift per cadence fitted
-    next to the fluxes.  ``cubes``, ``star_col`` / ``star_row`` and ``sigma`` as in ``psf_photometry_batch``.  One upload
+    next to the fluxes.  ``cubes``, ``star_col`` / ``star_row`` and ``sigma`` — or ``prf=`` a ``TabulatedPRF`` (and
+    ``prf_index=``) in its place — as in ``psf_photometry_batch``.  One upload
     (``DevicePixelCubeBatch.from_cubes``), then ``DevicePixelCubeBatch.psf_fit`` with its keywords; returns its ``(lcs,
     info)``, ``info`` as host arrays unless ``to_host=False`` is passed.  Not sharded over ranks."""
     from .device import DevicePixelCubeBatch

@@ -327,6 +327,45 @@ class TabulatedPRF(object):
                 acc = acc + wy[..., None, None, jj] * r
         return acc
 
+    def evaluate_with_gradient(self, shape, col, row, index=0):
+        """``evaluate`` and its derivatives by the star's centre -> (P, dP/dcol, dP/drow), each of ``evaluate``'s shape; P has
+        ``evaluate``'s bits.  The gradients use the same taps with the derivative weights of the same f: w'_-1 = ((-3 f + 4) f -
+        1) / 2, w'_0 = (9 f - 10) f / 2, w'_1 = ((-9 f + 8) f + 1) / 2, w'_2 = (3 f - 2) f / 2, each multiplied by du/dc = -os
+        (u = (0 - c) os + (T - 1) / 2 falls as the centre rises): dP/dcol = sum_jj w_jj(g) (sum_ii w'_ii(f) T), dP/drow = sum_jj
+        w'_jj(g) (sum_ii w_ii(f) T), in ``evaluate``'s order.  Keys' interpolant is C1, so the gradients are continuous; a far or
+        NaN centre gives zero for all three.  The model of ``psf_fit(prf=)``."""
+        ny, nx = (int(v) for v in shape)
+        _, Ty, Tx = self.samples.shape
+        T = np.zeros((Ty + 1, Tx + 1))
+        T[:Ty, :Tx] = self.samples[self._check_index(index)]
+        col, row = np.broadcast_arrays(np.asarray(col, dtype=np.float64), np.asarray(row, dtype=np.float64))
+        with np.errstate(all="ignore"):
+            jx, wx = self._axis(col, nx, Tx)
+            jy, wy = self._axis(row, ny, Ty)
+            dx, dy = self._axis_derivative(col, Tx), self._axis_derivative(row, Ty)
+            acc, acc_c, acc_r = (np.zeros(col.shape + (ny, nx)) for _ in range(3))
+            for jj in range(4):
+                r, rc = np.zeros(col.shape + (ny, nx)), np.zeros(col.shape + (ny, nx))
+                for ii in range(4):
+                    t = T[jy[..., :, None, jj], jx[..., None, :, ii]]
+                    r = r + wx[..., None, None, ii] * t
+                    rc = rc + dx[..., None, None, ii] * t
+                acc = acc + wy[..., None, None, jj] * r
+                acc_c = acc_c + wy[..., None, None, jj] * rc
+                acc_r = acc_r + dy[..., None, None, jj] * r
+        return acc, acc_c, acc_r
+
+    def _axis_derivative(self, c, size):
+        """One axis: the derivatives of ``_axis``'s weights by the centre c, c.shape + (4,): w'(f) x (-os); zeros for a far
+        centre."""
+        os_ = self.oversample
+        u = (0.0 - np.asarray(c, dtype=np.float64)) * os_ + 0.5 * (size - 1)
+        far = ~(np.abs(u) < self.FAR)
+        f = np.where(far, 0.0, u - np.floor(np.where(far, 0.0, u)))
+        d = np.stack([((-3.0 * f + 4.0) * f - 1.0) * 0.5, (9.0 * f - 10.0) * f * 0.5, ((-9.0 * f + 8.0) * f + 1.0) * 0.5,
+                      (3.0 * f - 2.0) * f * 0.5], axis=-1) * (-float(os_))
+        return np.where(far[..., None], 0.0, d)
+
 
 class PixelCube(object):
     """Minimal stand-in for the slice of TargetPixelFile that PLDCorrector touches."""
@@ -708,13 +747,13 @@ class PixelCube(object):
                 "background": np.where(bad, np.nan, theta[:, S]), "chi2": np.where(bad, np.nan, chi2), "n_used": n_used,
                 "cadence_status": cst, "status": 0 if np.any(cst == 0) else 1, "star_index": star_index, "min_pivot_ratio": ratio}
 
-    def psf_fit(self, star_col, star_row, sigma, shifts0=None, max_iter=10, tol=1e-7, max_step=0.5, max_shift=2.0,
-                aperture_mask="all", column=0, row=0, use_flux_err=True):
+    def psf_fit(self, star_col, star_row, sigma=None, shifts0=None, max_iter=10, tol=1e-7, max_step=0.5, max_shift=2.0,
+                aperture_mask="all", column=0, row=0, use_flux_err=True, prf=None, prf_index=0):
         """PSF photometry that fits each cadence's pointing shift: per cadence the fluxes of up to 8 stars, one constant
         background and ONE common (column, row) shift u = (dc, dr) of all stars, by variable projection in Kaufman's form (the
         host mirror of ``DevicePixelCubeBatch.psf_fit`` and its definition, float64 numpy after the float32 load).  The
         per-cadence motion shift of ``TargetPixelFile.to_lightcurve(method="prf")``; per-star positions, the PSF width,
-        tabulated PRFs, rotation and a background gradient are not fitted.  Stars, ``sigma``, ``aperture_mask``, ``column`` /
+        rotation and a background gradient are not fitted.  Stars, ``sigma``, ``aperture_mask``, ``column`` /
         ``row``, the used pixels, the weights w, the star factors g_s at shift u and the design A(u) = [g_0 ... g_{S-1}, 1], K =
         S + 1, are those of ``psf_photometry``; the used pixels do not depend on u.  ``shifts0``: None or (shift_col[N],
         shift_row[N]), the initial shift u0 of every cadence (0 without).  Per cadence, from u = u0, for it = 1 .. ``max_iter``:
@@ -740,8 +779,23 @@ class PixelCube(object):
         and 2); and what the tests' preconditions read: ``steps`` (N, max_iter), the last_step of every iteration, NaN
         afterwards; ``raw_steps`` (N, max_iter, 2), du before the clamp; ``excursion`` (N, max_iter), max |u - u0| after every
         update; ``min_pivot_ratio`` (N,), the smallest d_k / G_kk or d_k / E_kk of every factorisation made (0 for a pivot that
-        is not finite).  ``max_iter`` 1 .. 64, ``tol`` finite and >= 0, ``max_step`` and ``max_shift`` > 0 (``ValueError``)."""
+        is not finite).  ``max_iter`` 1 .. 64, ``tol`` finite and >= 0, ``max_step`` and ``max_shift`` > 0 (``ValueError``).
+        ``prf``: a ``TabulatedPRF`` in place of ``sigma`` (exactly one of the two, else ``ValueError``; ``prf_index`` its table,
+        ``ValueError`` without ``prf``).  Steps 1 to 3 hold word for word with the design columns A_s = P_s, ``prf.evaluate`` at
+        (col_s + dc - column, row_s + dr - row), and D = [sum_s theta_s dP_s/dc, sum_s theta_s dP_s/dr], s in index order,
+        from ``prf.evaluate_with_gradient``: a shift and a centre enter as one sum, so the derivative by the shift is the
+        derivative by the centre.  Everything else is the same; a cadence whose stars all have a zero model or a zero
+        derivative on the used pixels fails a pivot cut (status 3)."""
         import math
+        if (sigma is None) == (prf is None):
+            raise ValueError("psf_fit takes exactly one of sigma and prf")
+        if prf is None:
+            if prf_index is not None and not (np.ndim(prf_index) == 0 and prf_index == 0):
+                raise ValueError("prf_index needs prf")
+        else:
+            if not isinstance(prf, TabulatedPRF):
+                raise ValueError("prf must be a TabulatedPRF (got %r)" % (type(prf),))
+            prf_index = prf._check_index(prf_index)
         col, rw = np.atleast_1d(np.asarray(star_col, dtype=np.float64)), np.atleast_1d(np.asarray(star_row, dtype=np.float64))
         if col.ndim != 1 or col.shape != rw.shape:
             raise ValueError("star_col and star_row must be 1-D arrays of one length (got %r and %r)" % (col.shape, rw.shape))
@@ -752,7 +806,8 @@ class PixelCube(object):
             raise ValueError("psf_fit fits 1 .. 8 stars per cutout (got %d)" % S)
         if not (np.all(np.isfinite(col)) and np.all(np.isfinite(rw))):
             raise ValueError("a star position is infinite")
-        sig_c, sig_r = _psf_sigma(sigma)
+        if prf is None:
+            sig_c, sig_r = _psf_sigma(sigma)
         max_iter, tol, max_step, max_shift = _psf_fit_parameters(max_iter, tol, max_step, max_shift)
         N, ny, nx = self.shape
         npix, K = ny * nx, S + 1
@@ -784,17 +839,31 @@ class PixelCube(object):
 
         cholesky, forward, backward = _psf_cholesky, _psf_forward, _psf_backward
 
-        def evaluate(idx, u):
-            """The cadences idx at the shifts u (M, 2) -> theta (M, K), L, L2, g (M, 2), chi2, singular, pivot ratio."""
-            M = len(idx)
+        def gaussian_model(u, A, Ac, Ar):
+            """The star columns of A (M, npix, K) and their derivatives by (dc, dr), (M, npix, S) each, at the shifts u."""
+            M = len(u)
             g_col, d_col = tables(col[:, None] + u[None, :, 0] - column, sig_c, nx)
             g_row, d_row = tables(rw[:, None] + u[None, :, 1] - row, sig_r, ny)
-            w, y, keep = w_all[idx], y_all[idx], used[idx]
-            A, Ac, Ar = np.empty((M, npix, K)), np.empty((M, npix, S)), np.empty((M, npix, S))
             for s in range(S):
                 A[:, :, s] = (g_col[s][:, None, :] * g_row[s][:, :, None]).reshape(M, npix)
                 Ac[:, :, s] = (d_col[s][:, None, :] * g_row[s][:, :, None]).reshape(M, npix)
                 Ar[:, :, s] = (g_col[s][:, None, :] * d_row[s][:, :, None]).reshape(M, npix)
+
+        def tabulated_model(u, A, Ac, Ar):
+            M = len(u)
+            P, Pc, Pr = prf.evaluate_with_gradient((ny, nx), col[:, None] + u[None, :, 0] - column,
+                                                   rw[:, None] + u[None, :, 1] - row, prf_index)
+            for dst, src in ((A, P), (Ac, Pc), (Ar, Pr)):
+                dst[:, :, :S] = src.reshape(S, M, npix).transpose(1, 2, 0)
+
+        model = gaussian_model if prf is None else tabulated_model
+
+        def evaluate(idx, u):
+            """The cadences idx at the shifts u (M, 2) -> theta (M, K), L, L2, g (M, 2), chi2, singular, pivot ratio."""
+            M = len(idx)
+            w, y, keep = w_all[idx], y_all[idx], used[idx]
+            A, Ac, Ar = np.empty((M, npix, K)), np.empty((M, npix, S)), np.empty((M, npix, S))
+            model(u, A, Ac, Ar)
             A[:, :, S] = 1.0
             A = np.where(keep[:, :, None], A, 0.0)
             WA = A * w[:, :, None]

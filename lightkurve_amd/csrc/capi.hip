@@ -2365,6 +2365,23 @@ int lk_cube_psf_fit_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const 
                                   shift_row_err, last_step, n_iter, n_used, cadence_status, status, static_cast<hipStream_t>(stream));
 }
 
+int lk_cube_prf_fit_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
+                              const float *flux_err, const uint8_t *mask, int mask_stride, int S_max, const double *star_col,
+                              const double *star_row, const float *prf_table, int n_prf, int Ty, int Tx, int oversample,
+                              const int32_t *prf_index, const double *shift0_col, const double *shift0_row, int max_iter, double tol,
+                              double max_step, double max_shift, double column0, double row0, int use_flux_err, int32_t *star_off,
+                              double *time_out, double *flux_out, double *flux_err_out, double *background, double *chi2,
+                              double *shift_col, double *shift_row, double *shift_col_err, double *shift_row_err, double *last_step,
+                              int32_t *n_iter, int32_t *n_used, int8_t *cadence_status, int32_t *status, void *stream) {
+    LK_REQUIRE(h != nullptr, "handle is NULL");
+    LK_HIP_CHECK(hipSetDevice(h->device));
+    return lk::cube_prffit_launch(h, B, N, ny, nx, time, flux, flux_err, mask, mask_stride, S_max, star_col, star_row, prf_table, n_prf,
+                                  Ty, Tx, oversample, prf_index, shift0_col, shift0_row, max_iter, tol, max_step, max_shift, column0,
+                                  row0, use_flux_err, star_off, time_out, flux_out, flux_err_out, background, chi2, shift_col, shift_row,
+                                  shift_col_err, shift_row_err, last_step, n_iter, n_used, cadence_status, status,
+                                  static_cast<hipStream_t>(stream));
+}
+
 int lk_cube_psf_width_batch_dev(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux,
                                 const float *flux_err, const uint8_t *mask, int mask_stride, int S_max, const double *star_col,
                                 const double *star_row, const double *sigma0, const double *shift_col, const double *shift_row,

@@ -459,6 +459,16 @@ int cube_psffit_launch(lk_handle *h, int B, int N, int ny, int nx, const double 
                        double *time_out, double *flux_out, double *flux_err_out, double *background, double *chi2, double *shift_col,
                        double *shift_row, double *shift_col_err, double *shift_row_err, double *last_step, int32_t *n_iter,
                        int32_t *n_used, int8_t *cadence_status, int32_t *status, hipStream_t stream);
+// prffit.hip: cube_psffit_launch with a tabulated PRF in place of the widths (the table arguments of cube_prfphot_launch): the
+// model and its derivative by the shift come from the table by Keys' cubic convolution (lkhip.h)
+int cube_prffit_launch(lk_handle *h, int B, int N, int ny, int nx, const double *time, const float *flux, const float *flux_err,
+                       const uint8_t *mask, int mask_stride, int S_max, const double *star_col_host, const double *star_row_host,
+                       const float *prf_table, int n_prf, int Ty, int Tx, int oversample, const int32_t *prf_index_host,
+                       const double *shift0_col, const double *shift0_row, int max_iter, double tol, double max_step,
+                       double max_shift, double column0, double row0, int use_flux_err, int32_t *star_off_host, double *time_out,
+                       double *flux_out, double *flux_err_out, double *background, double *chi2, double *shift_col,
+                       double *shift_row, double *shift_col_err, double *shift_row_err, double *last_step, int32_t *n_iter,
+                       int32_t *n_used, int8_t *cadence_status, int32_t *status, hipStream_t stream);
 // psfwidth.hip: the PSF width (sigma_col, sigma_row) of every cutout, shared by its cadences, by variable projection from sigma0
 // (host array) at given shifts (nullable device arrays) on the cadences of cadence_mask (nullable device bytes): max_iter + 1
 // pairs of an evaluate and a step kernel.  Everything but the stars and sigma0 on the device; enqueued, no synchronisation

@@ -1,4 +1,4 @@
-// psf_common.hpp — what psfphot.hip (fluxes at given positions), prfphot.hip (the same with a tabulated PRF), psffit.hip (fluxes and a common shift per cadence), psfwidth.hip
+// psf_common.hpp — what psfphot.hip (fluxes at given positions), prfphot.hip (the same with a tabulated PRF), psffit.hip (fluxes and a common shift per cadence), prffit.hip (the same with a tabulated PRF), psfwidth.hip
 // (the width of a cutout) and psfpos.hip (the positions of a cutout's stars) share: the cadence-per-four-lanes mapping, the
 // Gaussian's edge integral, the table of factors and their derivatives by the centre (psffit.hip and psfpos.hip), the sums over
 // a cadence's lanes, a tile's cadences and a wavefront, the Cholesky without pivoting with its singularity test, and the

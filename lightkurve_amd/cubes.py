@@ -55,6 +55,26 @@ def _psf_stars(B, star_col, star_row, sigma):
     return pos, part, np.ascontiguousarray(sg, dtype=np.float64), pos[0].shape[1]
 
 
+def _prf_index(what, B, sigma, prf, prf_index):
+    """The ``prf`` / ``prf_index`` checks of ``psf_photometry`` and ``psf_fit`` -> the table of every cutout, int32 [B], or None
+    without ``prf``."""
+    from .correctors.pldcorrector import TabulatedPRF
+    if (sigma is None) == (prf is None):
+        raise ValueError("%s takes exactly one of sigma and prf" % what)
+    if prf is None:
+        if prf_index is not None:
+            raise ValueError("prf_index needs prf")
+        return None
+    if not isinstance(prf, TabulatedPRF):
+        raise ValueError("prf must be a TabulatedPRF (got %r)" % (type(prf),))
+    pidx = np.zeros(B, dtype=np.int32) if prf_index is None else np.asarray(prf_index)
+    if pidx.ndim > 1 or (pidx.ndim == 1 and pidx.size != B) or pidx.dtype.kind not in "iu":
+        raise ValueError("prf_index must be an integer or one integer per cutout (%d)" % B)
+    if np.any(pidx < 0) or np.any(pidx >= prf.n_prf):
+        raise ValueError("prf_index must be 0 .. %d" % (prf.n_prf - 1))
+    return np.ascontiguousarray(np.broadcast_to(pidx, (B,)), dtype=np.int32)
+
+
 def _prf_device_table(prf, handle, stream):
     """``prf.samples`` in HBM: uploaded once per handle and kept on the ``TabulatedPRF`` (synchronised, so that later calls on
     any stream of the handle may read it)."""
@@ -788,23 +808,10 @@ class DevicePixelCubeBatch(object):
         is then interpolated from the table by Keys' cubic convolution (``lk_cube_prf_photometry_batch_dev``; the definition is
         ``TabulatedPRF``), which carries the wings and asymmetries of a mission PRF that no Gaussian width reproduces.  The
         table goes up once and stays on the ``TabulatedPRF``.  ``prf_index``: None (table 0), a scalar or [B], the table of every
-        cutout.  Everything else, the return value included, is the same; ``psf_fit``, ``psf_width`` and ``psf_positions`` do
-        not take a table."""
-        from .correctors.pldcorrector import TabulatedPRF
+        cutout.  Everything else, the return value included, is the same; ``psf_fit(prf=)`` fits the shifts with the same
+        table, ``psf_width`` and ``psf_positions`` do not take one."""
         h, (B, N, ny, nx) = self.handle, self.shape
-        if (sigma is None) == (prf is None):
-            raise ValueError("psf_photometry takes exactly one of sigma and prf")
-        if prf is not None:
-            if not isinstance(prf, TabulatedPRF):
-                raise ValueError("prf must be a TabulatedPRF (got %r)" % (type(prf),))
-            pidx = np.zeros(B, dtype=np.int32) if prf_index is None else np.asarray(prf_index)
-            if pidx.ndim > 1 or (pidx.ndim == 1 and pidx.size != B) or pidx.dtype.kind not in "iu":
-                raise ValueError("prf_index must be an integer or one integer per cutout (%d)" % B)
-            if np.any(pidx < 0) or np.any(pidx >= prf.n_prf):
-                raise ValueError("prf_index must be 0 .. %d" % (prf.n_prf - 1))
-            pidx = np.ascontiguousarray(np.broadcast_to(pidx, (B,)), dtype=np.int32)
-        elif prf_index is not None:
-            raise ValueError("prf_index needs prf")
+        pidx = _prf_index("psf_photometry", B, sigma, prf, prf_index)
         pos, part, sg, S_max = _psf_stars(B, star_col, star_row, sigma)
         keep = []
         d_shift = self._psf_shift_buffers(shifts, "shifts", keep)
@@ -832,14 +839,14 @@ class DevicePixelCubeBatch(object):
         return self._psf_results(pos, part, (d_t, d_f, d_e), keep + [d for d in d_shift if d is not None], info, _PSF_INFO,
                                  star_off, to_host)
 
-    def psf_fit(self, star_col, star_row, sigma, shifts0=None, max_iter=10, tol=1e-7, max_step=0.5, max_shift=2.0,
-                aperture_mask="all", column=0, row=0, use_flux_err=True, to_host=False):
+    def psf_fit(self, star_col, star_row, sigma=None, shifts0=None, max_iter=10, tol=1e-7, max_step=0.5, max_shift=2.0,
+                aperture_mask="all", column=0, row=0, use_flux_err=True, to_host=False, prf=None, prf_index=None):
         """PSF photometry that fits each cadence's pointing shift: ``psf_photometry`` with ONE common (column, row) shift of all
         stars per cadence fitted next to the fluxes and the background, by variable projection (``lk_cube_psf_fit_batch_dev``;
         the numpy mirror and the definition is ``PixelCube.psf_fit``).  The per-cadence motion shift of
         ``TargetPixelFile.to_lightcurve(method="prf")``: unlike the centroid of the whole blend (``estimate_centroids``) it is
-        not biased by the blending and does not move when one star varies.  Per-star positions, the PSF width, tabulated PRFs,
-        rotation and a background gradient are not fitted.  Stars, ``sigma``, ``aperture_mask``, ``column`` / ``row`` and
+        not biased by the blending and does not move when one star varies.  Per-star positions, the PSF width, rotation and
+        a background gradient are not fitted.  Stars, ``sigma``, ``aperture_mask``, ``column`` / ``row`` and
         ``use_flux_err`` as in ``psf_photometry``.  ``shifts0``: None (start at 0) or a pair (shift_col, shift_row) of host
         arrays [B, N] or of ``DeviceBuffer``s of B x N float64, the initial shifts.  Up to ``max_iter`` (1 .. 64) Gauss-Newton
         steps per cadence, each component clamped to +-``max_step``; a cadence stops when its step is below ``tol`` (``tol`` =
@@ -856,9 +863,19 @@ class DevicePixelCubeBatch(object):
             again, _ = cubes.psf_photometry(star_col, star_row, 1.1, shifts=(info["shift_col"], info["shift_row"]))
 
         Nothing is raised per cadence.  A cutout's outputs have the same bits alone, at any batch position and from run to
-        run."""
+        run.
+        ``prf``: a ``TabulatedPRF`` in place of ``sigma`` (exactly one of the two, else ``ValueError``), ``prf_index`` as in
+        ``psf_photometry``: the model and its derivative by the shift are interpolated from the table
+        (``lk_cube_prf_fit_batch_dev``; the definition is ``PixelCube.psf_fit(prf=)``), so the fitted shifts carry no bias from
+        a Gaussian stand-in and go straight into ``psf_photometry(prf=, shifts=)`` and ``sff_correct``::
+
+            lcs, info = cubes.psf_fit(star_col, star_row, prf=prf)
+            again, _ = cubes.psf_photometry(star_col, star_row, prf=prf, shifts=(info["shift_col"], info["shift_row"]))
+
+        Everything else, the return value included, is the same."""
         from .correctors.pldcorrector import _psf_fit_parameters
         h, (B, N, ny, nx) = self.handle, self.shape
+        pidx = _prf_index("psf_fit", B, sigma, prf, prf_index)
         pos, part, sg, S_max = _psf_stars(B, star_col, star_row, sigma)
         max_iter, tol, max_step, max_shift = _psf_fit_parameters(max_iter, tol, max_step, max_shift)
         keep = []
@@ -869,13 +886,19 @@ class DevicePixelCubeBatch(object):
         d_t, d_f, d_e = (DeviceBuffer(h, rows * N * 8) for _ in range(3))
         info = {key: DeviceBuffer(h, size) for key, _, size in _psf_info_spec(B, N, _PSF_FIT_INFO)}
         star_off = np.zeros(B + 1, dtype=np.int32)
-        _capi._check(_capi._lib.lk_cube_psf_fit_batch_dev(
-            h._h, B, N, ny, nx, _p(self.d_time), _p(self.d_flux), _p(self.d_flux_err), _p(d_mask), stride, S_max,
-            pos[0].ctypes.data_as(_dp), pos[1].ctypes.data_as(_dp), sg.ctypes.data_as(_dp), _p(d_shift[0]), _p(d_shift[1]),
-            max_iter, tol, max_step, max_shift, float(column), float(row), int(bool(use_flux_err)), star_off.ctypes.data_as(_i32p),
-            _p(d_t), _p(d_f), _p(d_e), _p(info["background"]), _p(info["chi2"]), _p(info["shift_col"]), _p(info["shift_row"]),
-            _p(info["shift_col_err"]), _p(info["shift_row_err"]), _p(info["last_step"]), _p(info["n_iter"]), _p(info["n_used"]),
-            _p(info["cadence_status"]), _p(info["status"]), _vp(self.stream or None)))
+        tail = (max_iter, tol, max_step, max_shift, float(column), float(row), int(bool(use_flux_err)), star_off.ctypes.data_as(_i32p),
+                _p(d_t), _p(d_f), _p(d_e), _p(info["background"]), _p(info["chi2"]), _p(info["shift_col"]), _p(info["shift_row"]),
+                _p(info["shift_col_err"]), _p(info["shift_row_err"]), _p(info["last_step"]), _p(info["n_iter"]), _p(info["n_used"]),
+                _p(info["cadence_status"]), _p(info["status"]), _vp(self.stream or None))
+        head = (h._h, B, N, ny, nx, _p(self.d_time), _p(self.d_flux), _p(self.d_flux_err), _p(d_mask), stride, S_max,
+                pos[0].ctypes.data_as(_dp), pos[1].ctypes.data_as(_dp))
+        if prf is None:
+            _capi._check(_capi._lib.lk_cube_psf_fit_batch_dev(*(head + (sg.ctypes.data_as(_dp), _p(d_shift[0]), _p(d_shift[1])) + tail)))
+        else:
+            n_prf, Ty, Tx = prf.samples.shape
+            _capi._check(_capi._lib.lk_cube_prf_fit_batch_dev(*(head + (
+                _p(_prf_device_table(prf, h, self.stream)), n_prf, Ty, Tx, prf.oversample, pidx.ctypes.data_as(_i32p),
+                _p(d_shift[0]), _p(d_shift[1])) + tail)))
         return self._psf_results(pos, part, (d_t, d_f, d_e), keep + [d for d in d_shift if d is not None], info, _PSF_FIT_INFO,
                                  star_off, to_host)
 

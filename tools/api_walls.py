@@ -172,6 +172,14 @@ H / Hs the mirror `PixelCube.psf_photometry(prf=)` per cutout on 16 threads over
 scaled to the batch in the report.  Every timed region ends with a synchronise.  Written to profiles/prfphot_walls.txt.
 `prfphot_trace`: P and Ps twice and nothing else, for `rocprofv3 --kernel-trace --stats` (profiles/prfphot_kernel_stats.txt).
 
+`prffit`: the PSF fit with a pointing shift per cadence and a tabulated PRF on the same batch shape, star count, cubes and table as
+`prfphot`, in ONE process, the routes alternating, `LK_WALLS_REPS` (default 5) times after one warm-up.  F `cubes.psf_fit(star_col,
+star_row, prf=)` with the defaults, from shifts 0; Ps `cubes.psf_photometry(prf=)` of the same cubes GIVEN the true shifts; Fg
+`cubes.psf_fit(star_col, star_row, sigma)`, the Gaussian fit; H the mirror `PixelCube.psf_fit(prf=)` per cutout on 16 threads over the
+first `LK_WALLS_MIRROR_B` (default 16) cutouts, scaled to the batch in the report.  Every timed region ends with a synchronise.
+Written to profiles/prffit_walls.txt.  `prffit_trace`: F and Ps twice and nothing else, for `rocprofv3 --kernel-trace --stats`
+(profiles/prffit_kernel_stats.txt).
+
 `background`: the per-cadence background of the same batch shape with 'background' masks, in ONE process, the routes alternating,
 `LK_WALLS_REPS` (default 5) times after one warm-up.  F `cubes.subtract_background()` (median images, masks, the fused estimate +
 subtraction) and Fm the same with the masks given; E `cubes.estimate_background()`, Em with the masks given, Es with the scatter
@@ -1596,6 +1604,98 @@ def prfphot(which):
         % (med["P"] / med["G"], med["Ps"] / med["Gs"], B, med["H"] * B / Bm / med["P"], med["Hs"] * B / Bm / med["Ps"], floor / 1e6)])
 
 
+def prffit(which):
+    from concurrent.futures import ThreadPoolExecutor
+    from scipy.special import erf
+    from lightkurve_amd.correctors import TabulatedPRF
+    from lightkurve_amd.device import DevicePixelCubeBatch
+    B, N, side, S = (int(os.environ.get(k, d)) for k, d in (("LK_WALLS_B", "500"), ("LK_WALLS_N", "4000"), ("LK_WALLS_SIDE", "11"),
+                                                            ("LK_WALLS_STARS", "4")))
+    reps, Bm = int(os.environ.get("LK_WALLS_REPS", "5")), min(B, int(os.environ.get("LK_WALLS_MIRROR_B", "16")))
+    rng = np.random.default_rng(73)
+    npix = side * side
+    t = 1000.0 + np.arange(N) / 720.0                                    # two-minute cadences
+    sigma = 1.1
+    prf = TabulatedPRF.from_gaussian(sigma, sigma, 50, 5.5)
+    cells = int(np.ceil(np.sqrt(S)))
+    lattice = np.array([((i + 0.5) * side / cells - 0.5, (j + 0.5) * side / cells - 0.5) for j in range(cells) for i in range(cells)][:S])
+    col = lattice[None, :, 0] + rng.uniform(-0.3, 0.3, (B, S))
+    row = lattice[None, :, 1] + rng.uniform(-0.3, 0.3, (B, S))
+    shifts = (rng.uniform(-0.3, 0.3, (B, N)), rng.uniform(-0.3, 0.3, (B, N)))     # the true pointing of every cadence
+    edges = np.arange(side + 1) - 0.5
+    flux = np.empty((B, N, side, side), dtype=np.float32)
+    for b in range(B):                                                  # every cadence rendered at its own shift
+        gx = np.diff(erf((edges[None, None, :] - col[b][None, :, None] - shifts[0][b][:, None, None]) / (np.sqrt(2) * sigma)), axis=2) / 2
+        gy = np.diff(erf((edges[None, None, :] - row[b][None, :, None] - shifts[1][b][:, None, None]) / (np.sqrt(2) * sigma)), axis=2) / 2
+        img = 100.0 + np.einsum("s,nsy,nsx->nyx", rng.uniform(2000.0, 20000.0, S), gy, gx)
+        flux[b] = img.astype(np.float32) + 3.0 * rng.standard_normal((N, side, side), dtype=np.float32)
+    err = np.full_like(flux, 3.0)
+    cubes = DevicePixelCubeBatch.from_arrays(np.tile(t, (B, 1)), flux, err)
+    cubes.synchronize()
+    del flux, err
+    d_shifts = tuple(_upload_f64(cubes, a) for a in shifts)
+
+    def fit(table=True):
+        out = cubes.psf_fit(col, row, prf=prf) if table else cubes.psf_fit(col, row, sigma)
+        cubes.synchronize()
+        return out
+
+    def given():
+        out = cubes.psf_photometry(col, row, prf=prf, shifts=d_shifts)
+        cubes.synchronize()
+        return out
+
+    if "prffit_trace" in which:
+        for _ in range(2):
+            fit()
+            given()
+        return
+
+    host_m = cubes.to_host()[:Bm]
+
+    def mirror():
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            return list(ex.map(lambda b: host_m[b].psf_fit(col[b], row[b], prf=prf), range(Bm)))
+
+    fns = {"F": fit, "Ps": given, "Fg": lambda: fit(False), "H": mirror}
+    first = {k: fn() for k, fn in fns.items()}                           # warm-up of every route
+    lcs, info = first["F"]
+    n_iter = info["n_iter"].download(np.int32, B * N, stream=lcs.stream).reshape(B, N)
+    cstat = info["cadence_status"].download(np.int8, B * N, stream=lcs.stream).reshape(B, N)
+    got = tuple(info[k].download(np.float64, B * N, stream=lcs.stream).reshape(B, N) for k in ("shift_col", "shift_row"))
+    gauss = tuple(first["Fg"][1][k].download(np.float64, B * N, stream=lcs.stream).reshape(B, N) for k in ("shift_col", "shift_row"))
+    off = float(max(np.nanmax(np.abs(g - s)) for g, s in zip(got, shifts)))
+    off_g = float(max(np.nanmax(np.abs(g - s)) for g, s in zip(got, gauss)))
+    f = lcs.flux_host().reshape(B * S, N)[:Bm * S].reshape(Bm, S, N)
+    h = np.stack([o["flux"] for o in first["H"]])
+    rel = float(np.max(np.abs(f - h) / np.max(np.abs(h), axis=(1, 2), keepdims=True)))
+    rel_u = float(max(np.max(np.abs(g[:Bm] - np.stack([o[k] for o in first["H"]]))) for g, k in zip(got, ("shift_col", "shift_row"))))
+    same_iter = bool(np.array_equal(n_iter[:Bm], np.stack([o["n_iter"] for o in first["H"]])))
+    first.clear()
+    del lcs, info
+    ts = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            ts[k].append(timed(fn)[0])
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    evals = float(np.mean(np.max(np.pad(n_iter, ((0, 0), (0, -N % 16))).reshape(B, -1, 16), axis=2))) + 1
+    write_walls("prffit_walls.txt", [
+        "PSF fit with a pointing shift per cadence and a tabulated PRF, %d cutouts x %d cadences x %d x %d float32, %d stars per cutout, "
+        "table %d x %d at os = %d from the Gaussian of %.1f px, true shifts uniform in +-0.3 px (%.1f MB of flux and flux_err resident, "
+        "read once)" % ((B, N, side, side, S) + prf.samples.shape[1:] + (prf.oversample, sigma, B * N * npix * 8 / 1e6)),
+        "  F    cubes.psf_fit(star_col, star_row, prf=), defaults, from shifts 0; everything resident                      %s" % spread(ts["F"]),
+        "  Ps   cubes.psf_photometry(prf=, shifts=(DeviceBuffer, DeviceBuffer)) at the TRUE shifts, the same run           %s" % spread(ts["Ps"]),
+        "  Fg   cubes.psf_fit(star_col, star_row, sigma) of the same cubes, the same run                                   %s" % spread(ts["Fg"]),
+        "  H    PixelCube.psf_fit(prf=) on 16 threads, the first %d cutouts only                                           %s" % (Bm, spread(ts["H"])),
+        "  cadence statuses: %s; iterations per cadence: mean %.2f, max %d; evaluations per tile of 16 cadences (its slowest cadence + 1): "
+        "mean %.2f" % (dict(zip(*(a.tolist() for a in np.unique(cstat, return_counts=True)))), float(n_iter.mean()), int(n_iter.max()), evals),
+        "  largest |fitted - true shift| %.4f px, |shift(prf) - shift(sigma)| %.2e px; first %d cutouts against the mirror: max |flux "
+        "difference| / max |flux| %.2e, max |shift difference| %.2e px, the same n_iter: %s" % (off, off_g, Bm, rel, rel_u, same_iter),
+        "  F / Ps = %.2f (%.2f per evaluation of a tile); F / Fg = %.2f; H scaled to %d cutouts / F = %.0f; kernel times alone: "
+        "profiles/prffit_kernel_stats.txt" % (med["F"] / med["Ps"], med["F"] / med["Ps"] / evals, med["F"] / med["Fg"], B,
+                                              med["H"] * B / Bm / med["F"])])
+
+
 def psffit(which):
     from concurrent.futures import ThreadPoolExecutor
     from scipy.special import erf
@@ -2125,6 +2225,8 @@ def main():
         psfphot(which)
     if {"prfphot", "prfphot_trace"} & set(which):
         prfphot(which)
+    if {"prffit", "prffit_trace"} & set(which):
+        prffit(which)
     if {"psffit", "psffit_trace"} & set(which):
         psffit(which)
     if {"psfwidth", "psfwidth_trace"} & set(which):
